@@ -9,9 +9,13 @@ Workload at N=1: BASELINE.json configs[1] -- UNet depth-4, 8-band 256x256 tiles,
 process per GPU, RCCL over `torch.distributed`, rendezvous on 127.0.0.1) before anything touches the GPU, relays rank
 0's JSON line and exits non-zero if any rank fails; under `python -m torch.distributed.run` it is simply one rank.
 
-One JSON line on stdout (rank 0).  See DESIGN.md "Measurement" for the definitions of `roofline`
-(HIP events around every launch of the dominant kernel, live in the timed region), `cpu_baseline`
-(the oracle's restatement of the reference's torch-CPU step, timed on this box's host cores) and `miou_vs_ref`.
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times --steps steps and reports `value` (tiles/s over
+the timed steps) and `ms_per_step`, and measures nothing else.  `--full` adds the side measurements: `roofline` (HIP
+events around every launch of the dominant kernel in sampled timed steps, plus an un-timed one-stream pass),
+`step_other_mode` (--graph 1), `eval`, `miou_vs_ref`, `data_path` and `cpu_baseline` (the oracle's restatement of the
+reference's torch-CPU step, timed on this box's host cores); see DESIGN.md "Measurement" for their definitions.
+`--dump-outputs DIR` writes what the last timed step computed (loss, parameters after the update, gradients, BatchNorm
+running statistics) as DIR/<name>.npy in float32, from inputs that are identical for identical arguments.
 """
 import argparse
 import hashlib
@@ -58,7 +62,7 @@ def parse(argv=None):
     ap.add_argument("--no-eval", action="store_true", help="skip the eval-forward / stitching side measurement")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("FU_STEP_GRAPH", "0")), choices=[0, 1],
                     help="1: the whole step is captured into a hipGraph once and replayed (N = 1, C-ABI path); the steps whose "
-                         "conv launches are event-timed for the roofline run eagerly either way; with --graph 1 the eager "
+                         "conv launches are event-timed for the roofline run eagerly either way; with --graph 1 --full the eager "
                          "launch mode is measured in a short extra pass and reported as `step_other_mode` (the default line "
                          "no longer replays a graph: DESIGN.md section 5, hipGraph)")
     ap.add_argument("--no-serial-pass", action="store_true",
@@ -68,7 +72,45 @@ def parse(argv=None):
     ap.add_argument("--cpu-steps-b16", type=int, default=3, help="steps of the batch-16 CPU sample (0 = skip)")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous test of the multi-rank launcher on the CPU (gloo): every rank all-reduces its rank")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (event-timed launches and the "
+                         "one-stream pass), the other launch mode (--graph 1), eval forward + stitching, mIoU vs ref, the "
+                         "data path and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; arrays longer "
+                         f"than {DUMP_SAMPLE} elements as a fixed, seeded sample of that many)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_SAMPLE = 4 << 20          # elements kept of a longer output array: 16 MiB of float32
+DUMP_BUDGET = 64 << 20         # bytes of all dumped arrays together
+
+
+def dump_outputs(out_dir, arrays, sample=DUMP_SAMPLE, budget=DUMP_BUDGET):
+    """Write every named tensor of `arrays` as out_dir/<name>.npy in float32.  A tensor of more than `sample` elements is
+    flattened and replaced by the elements at `sample` positions drawn once from a fixed seed (sorted, and the same for
+    every tensor of that length), so that two runs or two builds can be compared output for output."""
+    import numpy as np
+    import torch
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > sample:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), sample, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > budget:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the budget of {budget}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return total
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -508,7 +550,7 @@ def main():
             net = net.to(dev).train()
         else:
             net = HipUNet(args.channels, 3, bilinear=True, base_channels=64, precision=precision).to(dev).train()
-        trainer = DataParallelTrainer(net, lr=1e-4, world_size=world, rank=rank, time_waits=world > 1,
+        trainer = DataParallelTrainer(net, lr=1e-4, world_size=world, rank=rank, time_waits=world > 1 and args.full,
                                       graph=bool(args.graph) and world == 1)
 
     B, Cc, S = args.batch, args.channels, args.size
@@ -530,7 +572,7 @@ def main():
     if world > 1:   # communicator set-up + parameter broadcast outside the steps (also with --warmup 0)
         trainer._sync_initial_state(dev)
     lib = _lib.load()
-    stride = int(os.environ.get("FU_BENCH_EVENT_STRIDE", "8"))
+    stride = int(os.environ.get("FU_BENCH_EVENT_STRIDE", "8")) if args.full else 0      # event-timed steps: --full only
     for w in range(args.warmup):
         # the LAST warm-up step runs with the launch events on: the first event-timed step creates ~100 events and pays their first
         # records -- 2.2 ms on a 5.3 ms step (FU_BENCH_DUMP_STEPS=1: 7.57 / 5.39 / 5.37 ...), a one-time cost that belongs to the
@@ -543,7 +585,7 @@ def main():
         if warm_events:
             _lib.check(lib.fu_profile_enable(net._ctx, 0))
             trainer._graph_off = False
-    if net._ctx is None:      # --warmup 0: the context is created by the first forward; the event profiler needs one
+    if stride > 0 and net._ctx is None:   # --warmup 0: the context is created by the first forward; the event profiler needs one
         trainer.step(x, target, 0)
     # HIP events around every conv / wgrad launch serialise the kernel boundaries (~2 us per pair: 6.39 -> 6.66 ms per
     # step when every step is timed, same box), so the live roofline measurement samples every EVENT_STRIDE-th step of
@@ -585,6 +627,11 @@ def main():
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step on this net: the loss the caller of the timed path received, the parameters its
+        # Adam update left, the gradients and the BatchNorm running statistics of the last timed step
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "params": net.flat_parameters(), "grads": net.flat_grads(),
+                                         "bn_running_mean": net._flat_rm, "bn_running_var": net._flat_rv})
 
     tiles = args.steps * B * world
     value = tiles / dt
@@ -592,7 +639,7 @@ def main():
 
     # ---- roofline of the dominant kernel (HIP events recorded around every launch in the timed region)
     best = None
-    for cls in (0, 1):
+    for cls in ((0, 1) if args.full else ()):
         n, ms, fl, name = C.c_int64(), C.c_double(), C.c_double(), C.c_char_p()
         _lib.check(lib.fu_profile_read(net._ctx, cls, C.byref(n), C.byref(ms), C.byref(fl), C.byref(name)))
         if n.value and (best is None or ms.value > best["ms"]):
@@ -640,7 +687,7 @@ def main():
                 lib.fu_test_bnb_separate(0)
         _lib.check(lib.fu_set_side_stream(net._ctx, 1))
     other_mode = None
-    if world == 1 and args.path == "cabi" and args.model == "unet" and not args.no_serial_pass and args.graph:
+    if world == 1 and args.path == "cabi" and args.model == "unet" and not args.no_serial_pass and args.graph and args.full:
         # the step launched the other way (captured hipGraph -> eager), 20 steps after 3 of warm-up; not part of `value`.
         # Only with --graph 1: round 4 measured the replay of the ONE-chain capture 2 % slower than its eager launches (5.81
         # against 5.67 ms) and the replay of the two-stream capture 60 % slower (8.70 against 5.39) -- a runtime property, not
@@ -732,11 +779,12 @@ def main():
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
         "config": cfg,
         "step_launch_mode": "hipGraph replay" if (args.graph and world == 1 and args.path == "cabi") else "eager launches",
-        "step_other_mode": other_mode,
         "loss": round(float(loss.item()), 6),
-        "roofline": roof,
     }
-    if rank == 0:
+    if args.full:
+        out["step_other_mode"] = other_mode
+        out["roofline"] = roof
+    if rank == 0 and args.full:
         if world == 1 and args.model == "unet" and args.path == "cabi" and not args.no_eval:
             out["eval"] = eval_forward_bench(net, dev, x)
         if world == 1 and not args.no_miou:
@@ -748,6 +796,7 @@ def main():
             out["data_path"] = loader_bench(args, dev, host_budget=6.0, device_epochs=2)
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

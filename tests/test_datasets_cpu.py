@@ -1,5 +1,6 @@
 """Host-side data path: tile grid against vectors produced by the reference's own function,
 TIFF decoding against synthetic files and the bundled rasters' golden checksums, the dataset's item contract."""
+import gzip
 import hashlib
 import json
 import os
@@ -18,7 +19,6 @@ from floodplanet_code_amd.datasets import (CropParams, FloodplanetTiles, TiffErr
                                            resize_lanczos4, resize_nearest, tiff_info, tiff_size)
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-REF = "/root/reference"
 
 
 def test_crop_slices_match_the_reference_function_on_1120_cases():
@@ -93,16 +93,29 @@ def test_tiff_reader_rejects_what_it_does_not_decode(tmp_path):
         read_tiff(p)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "CSDAP_complete")), reason="bundled rasters not mounted")
-def test_bundled_rasters_decode_to_their_golden_checksums():
+def test_bundled_rasters_decode_to_their_golden_checksums(tmp_path):
+    """rasters_golden.json: shape, dtype and checksum of the dataset's 115 rasters.  They come in five TIFF layouts (planar,
+    uncompressed: 7-band float32 L8 with 15 or 18 rows per strip, 2-band float32 S1 with 5 or 6, 1-band uint8 labels with
+    8); tests/golden/rasters/ holds one raster of each layout, gzipped, under its path in the dataset."""
     gold = json.load(open(os.path.join(GOLD, "rasters_golden.json")))
     assert len(gold) == 115
-    for rel, want in gold.items():
-        a = read_tiff(os.path.join(REF, rel))
+    bundled = os.path.join(GOLD, "rasters")
+    rels = sorted(os.path.relpath(os.path.join(d, f), bundled)[:-3] for d, _, fs in os.walk(bundled) for f in fs)
+    layouts = set()
+    for rel in rels:
+        want = gold[rel]
+        path = str(tmp_path / os.path.basename(rel))
+        with gzip.open(os.path.join(bundled, rel + ".gz"), "rb") as src, open(path, "wb") as dst:
+            dst.write(src.read())
+        info = tiff_info(path)
+        layouts.add((info["dtype"], info["samples"], info["rows_per_strip"], info["planar"]))
+        a = read_tiff(path)
         a3 = a[None] if a.ndim == 2 else a
         assert list(a3.shape) == want["shape"] and a3.dtype.name == want["dtype"], rel
         assert hashlib.sha256(np.ascontiguousarray(a3.astype(a3.dtype.newbyteorder("<"))).tobytes()).hexdigest() == \
             want["sha256"], rel
+    assert layouts == {("float32", 7, 15, 2), ("float32", 7, 18, 2), ("float32", 2, 5, 2), ("float32", 2, 6, 2),
+                       ("uint8", 1, 8, 1)}, layouts
 
 
 def test_resampling_conventions():
