@@ -37,6 +37,22 @@ class FuConfig(C.Structure):
     ]
 
 
+class FuStitchEntry(C.Structure):
+    """fu_stitch_entry (include/floodunet.h): one crop of fu_stitch_add_batch."""
+    _fields_ = [
+        ("canvas", C.c_void_p),
+        ("weight", C.c_void_p),
+        ("sample", C.c_int32),
+        ("canvas_h", C.c_int32),
+        ("canvas_w", C.c_int32),
+        ("h0", C.c_int32),
+        ("w0", C.c_int32),
+        ("hE", C.c_int32),
+        ("wE", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class FloodUNetError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"libfloodunet error {status}: {message}")
@@ -83,6 +99,8 @@ SIGNATURES = {
     "fu_zero_grads": (_i, [_p, _p]),
     "fu_stitch_add": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "fu_stitch_finalize": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "fu_stitch_add_batch": (_i, [_p, _i, C.POINTER(FuStitchEntry), _p]),
+    "fu_eval_confusion": (_i, [_p, _p, _i, _p, _p]),
     "fu_augment": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i64, _p]),
     "fu_resize_lanczos4_tiles": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "fu_assemble_tiles": (_i, [C.POINTER(_p), C.POINTER(C.c_int32), _i, _i, _i, _i, _p, _p, _i, _p, _p, _f, _p, _p, _p, _p]),

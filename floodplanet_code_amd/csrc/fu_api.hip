@@ -379,6 +379,8 @@ struct fu_ctx {
   int* guard = nullptr;           // fp16 mode: non-finite flag / skipped steps / back-off exponent / clean steps (k_guard_book)
   unsigned long long* conf_tmp = nullptr;
   int64_t* n_valid = nullptr;
+  StitchJob* stitch_jobs = nullptr;   // fu_stitch_add_batch: device copy of the last table (grown on demand, owned)
+  int stitch_cap = 0;
   float* adam_m = nullptr;        // bound (caller-owned, fu_bind_adam_state): the moments outlive the context
   float* adam_v = nullptr;
   Profiler prof;
@@ -1181,6 +1183,7 @@ int fu_destroy(fu_ctx* c) {
   for (hipEvent_t e : c->ev_fence) if (e) (void)hipEventDestroy(e);   // (fu_backward_fence creates them without a side stream too)
   if (c->arena.base) (void)hipFree(c->arena.base);
   for (void* p : c->extra_allocs) (void)hipFree(p);
+  if (c->stitch_jobs) (void)hipFree(c->stitch_jobs);
   delete c;
   return FU_OK;
 }
@@ -1532,6 +1535,53 @@ int fu_stitch_add(fu_ctx* c, int sample, float* canvas, float* weight, int canva
   if (dh == 0 || dw == 0) return FU_OK;
   const float* lg = c->logits + (int64_t)sample * H * W * c->cfg.n_classes;
   return launch_stitch_add(lg, c->cfg.n_classes, W, canvas, weight, canvas_w, h0, w0, dh, dw, (hipStream_t)stream);
+}
+
+int fu_stitch_add_batch(fu_ctx* c, int n, const fu_stitch_entry* entries, fu_stream stream) {
+  FU_REQUIRE(c && entries && n > 0, "fu_stitch_add_batch: null context / entries or n = %d <= 0", n);
+  FU_REQUIRE(c->last_batch > 0, "fu_stitch_add_batch: no forward pass yet");
+  const int H = c->cfg.height, W = c->cfg.width, k = c->cfg.n_classes;
+  std::vector<StitchJob> jobs((size_t)n);
+  int max_area = 0;
+  for (int i = 0; i < n; ++i) {
+    const fu_stitch_entry& E = entries[i];
+    const int dh = E.hE - E.h0, dw = E.wE - E.w0;
+    FU_REQUIRE(E.canvas && E.weight, "fu_stitch_add_batch: entry %d: null canvas / weight", i);
+    FU_REQUIRE(E.sample >= 0 && E.sample < c->last_batch, "fu_stitch_add_batch: entry %d: sample %d not in the last batch "
+               "(%d)", i, E.sample, c->last_batch);
+    FU_REQUIRE(E.h0 >= 0 && E.w0 >= 0 && dh > 0 && dw > 0 && E.hE <= E.canvas_h && E.wE <= E.canvas_w && dh <= H && dw <= W,
+               "fu_stitch_add_batch: entry %d: crop [%d:%d, %d:%d] is empty or does not fit canvas %dx%d / tile %dx%d", i,
+               E.h0, E.hE, E.w0, E.wE, E.canvas_h, E.canvas_w, H, W);
+    for (int j = 0; j < i; ++j) {   // one thread owns a canvas pixel: canvases must not share a weight or disagree in size
+      const fu_stitch_entry& P = entries[j];
+      FU_REQUIRE((P.canvas == E.canvas) == (P.weight == E.weight) &&
+                 (P.canvas != E.canvas || (P.canvas_h == E.canvas_h && P.canvas_w == E.canvas_w)),
+                 "fu_stitch_add_batch: entries %d and %d share a canvas or a weight but not both (or differ in size)", j, i);
+    }
+    jobs[i] = StitchJob{c->logits + (int64_t)E.sample * H * W * k, E.canvas, E.weight, E.canvas_w, E.h0, E.w0, dh, dw, 0};
+    max_area = std::max(max_area, dh * dw);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (n > c->stitch_cap) {
+    if (c->stitch_jobs) {
+      FU_HIP_CHECK(hipDeviceSynchronize());     // an earlier launch may still read the old table
+      FU_HIP_CHECK(hipFree(c->stitch_jobs));
+      c->stitch_jobs = nullptr;
+      c->stitch_cap = 0;
+    }
+    const int cap = std::max(n, 64);
+    FU_HIP_CHECK(hipMalloc(&c->stitch_jobs, (size_t)cap * sizeof(StitchJob)));
+    c->stitch_cap = cap;
+  }
+  FU_HIP_CHECK(hipMemcpyAsync(c->stitch_jobs, jobs.data(), (size_t)n * sizeof(StitchJob), hipMemcpyHostToDevice, s));
+  return launch_stitch_add_batch(c->stitch_jobs, n, max_area, k, W, s);
+}
+
+int fu_eval_confusion(fu_ctx* c, const int64_t* target, int ignore_index, int64_t* counts_out, fu_stream stream) {
+  FU_REQUIRE(c && target && counts_out, "fu_eval_confusion: null argument");
+  FU_REQUIRE(c->last_batch > 0, "fu_eval_confusion: no forward pass yet");
+  return launch_eval_confusion(c->logits, target, c->cfg.n_classes, ignore_index, c->last_batch,
+                               (int64_t)c->cfg.height * c->cfg.width, counts_out, (hipStream_t)stream);
 }
 
 int fu_stitch_finalize(float* canvas, const float* weight, int n_classes, int canvas_h, int canvas_w,

@@ -410,6 +410,16 @@ int launch_stitch_add(const float* logits_nhwc, int ncls, int cropW, float* canv
                       int w0, int dh, int dw, hipStream_t s);
 int launch_stitch_finalize(float* canvas, const float* weight, int ncls, int64_t npix, int64_t* argmax_out,
                            hipStream_t s);
+// one crop of launch_stitch_add_batch (device copy of a validated fu_stitch_entry)
+struct StitchJob {
+  const float* logits;   // NHWC fp32 logits of the crop's sample (the tile's [0, 0] pixel)
+  float* canvas;
+  float* weight;
+  int canvasW, h0, w0, dh, dw, pad;
+};
+int launch_stitch_add_batch(const StitchJob* jobs_dev, int n, int max_area, int ncls, int cropW, hipStream_t s);
+int launch_eval_confusion(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int B, int64_t hw,
+                          int64_t* counts, hipStream_t s);
 int launch_assemble_tiles(const float* const* srcs, const int* src_channels, int n_src, int B, int H, int W, const int* vh,
                           const int* vw, int norm_mode, const float* gmean, const float* gstd, float pad_value, float* out,
                           float* mean_out, float* std_out, hipStream_t s);

@@ -2188,6 +2188,98 @@ int launch_stitch_finalize(float* canvas, const float* weight, int ncls, int64_t
   return 0;
 }
 
+// Batched stitching: jobs[0..n-1] in one launch, bit-identical to k_stitch_add for each job in table order.  A canvas
+// pixel belongs to the first job that covers it; that thread reads the canvas once, adds the softmax of every covering
+// job in table order with the very expression of k_stitch_add (same rounding sequence), and writes once -- overlapping
+// crops of one batch (stride < crop) never race and need no float atomics.  blockIdx.y walks the jobs, blockIdx.x the
+// pixels of the job's box; the ownership scan over earlier jobs is uniform across the block (scalar loads of the table).
+__device__ __forceinline__ bool stitch_covers(const StitchJob& J, const float* canvas, int cy, int cx) {
+  return J.canvas == canvas && cy >= J.h0 && cy < J.h0 + J.dh && cx >= J.w0 && cx < J.w0 + J.dw;
+}
+
+__global__ void k_stitch_add_batch(const StitchJob* __restrict__ jobs, int n, int ncls, int cropW) {
+  for (int e = blockIdx.y; e < n; e += gridDim.y) {
+    const StitchJob J = jobs[e];
+    const int64_t total = (int64_t)J.dh * J.dw;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * blockDim.x) {
+      const int cy = J.h0 + (int)(idx / J.dw), cx = J.w0 + (int)(idx % J.dw);
+      bool owner = true;
+      for (int j = 0; j < e && owner; ++j) owner = !stitch_covers(jobs[j], J.canvas, cy, cx);
+      if (!owner) continue;
+      const int64_t o = (int64_t)cy * J.canvasW + cx;
+      float acc[HEAD_MAX_CLS], wacc = J.weight[o];
+#pragma unroll
+      for (int k = 0; k < HEAD_MAX_CLS; ++k) acc[k] = k < ncls ? J.canvas[o * ncls + k] : 0.f;
+      for (int j = e; j < n; ++j) {
+        const StitchJob Q = jobs[j];
+        if (!stitch_covers(Q, J.canvas, cy, cx)) continue;
+        const float* z = Q.logits + ((int64_t)(cy - Q.h0) * cropW + (cx - Q.w0)) * ncls;
+        float m = -INFINITY, ex[HEAD_MAX_CLS], se = 0.f;
+#pragma unroll
+        for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) m = fmaxf(m, z[k]);
+#pragma unroll
+        for (int k = 0; k < HEAD_MAX_CLS; ++k) { ex[k] = k < ncls ? expf(z[k] - m) : 0.f; se += ex[k]; }
+        const float inv = 1.f / se;
+#pragma unroll
+        for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) acc[k] += ex[k] * inv;
+        wacc += 1.f;
+      }
+#pragma unroll
+      for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) J.canvas[o * ncls + k] = acc[k];
+      J.weight[o] = wacc;
+    }
+  }
+}
+
+int launch_stitch_add_batch(const StitchJob* jobs_dev, int n, int max_area, int ncls, int cropW, hipStream_t s) {
+  const dim3 grid(grid_for(max_area, 256, 1024), n < 65535 ? n : 65535);
+  hipLaunchKernelGGL(k_stitch_add_batch, grid, dim3(256), 0, s, jobs_dev, n, ncls, cropW);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-sample confusion counts of the resident logits (prediction metrics, predict.py:236-250): the argmax and pixel rule
+// of k_ce_loss without the loss.  blockIdx.y = sample; a block histograms its pixels in LDS, then adds the non-zero bins
+// to counts[b][t * k + p] with 64-bit integer atomics (exact, order-free), so there is no finalisation pass.
+// ------------------------------------------------------------------------------------------------
+__global__ void k_eval_confusion(const float* __restrict__ logits, const int64_t* __restrict__ target, int ncls,
+                                 int ignore_index, int64_t hw, unsigned long long* __restrict__ counts) {
+  __shared__ unsigned int hist[HEAD_MAX_CLS * HEAD_MAX_CLS];
+  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x) hist[i] = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.y * hw;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < hw; q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = base + q;
+    const int64_t t = target[p];
+    if (t == (int64_t)ignore_index || t < 0 || t >= ncls) continue;
+    float m = -INFINITY;
+    int am = 0;
+#pragma unroll
+    for (int k = 0; k < HEAD_MAX_CLS; ++k) {
+      if (k < ncls) {
+        const float z = logits[p * ncls + k];
+        if (z > m) { m = z; am = k; }
+      }
+    }
+    atomicAdd(&hist[(int)t * ncls + am], 1u);
+  }
+  __syncthreads();
+  unsigned long long* out = counts + (int64_t)blockIdx.y * ncls * ncls;
+  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x)
+    if (hist[i]) atomicAdd(&out[i], (unsigned long long)hist[i]);
+}
+
+int launch_eval_confusion(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int B, int64_t hw,
+                          int64_t* counts, hipStream_t s) {
+  const dim3 grid(grid_for(hw, CE_BLOCK, 64), B);
+  hipLaunchKernelGGL(k_eval_confusion, grid, dim3(CE_BLOCK), 0, s, logits_nhwc, target, ncls, ignore_index, hw,
+                     reinterpret_cast<unsigned long long*>(counts));
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam single-tensor update order; water_seg_model.py:200)
 // ------------------------------------------------------------------------------------------------

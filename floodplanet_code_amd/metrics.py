@@ -67,6 +67,26 @@ class SegmentationMetrics:
         p = self.prefix
         return {f"{p}MulticlassF1Score": res[0], f"{p}MulticlassJaccardIndex": res[2], f"{p}MulticlassAccuracy": res[1]}
 
+    def reduce_batch(self, counts: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """_reduce of each matrix of a stack [N, n, n] at once -> {key: [N]} (per-crop metrics of the prediction loop).
+        The sums are exact integers in fp64 and the quotients the same IEEE divisions, so every entry equals
+        _reduce(counts[i]) bit for bit; nothing is accumulated."""
+        w1, w2 = self._reduce_matrices(counts.device)
+        m = counts.reshape(counts.shape[0], 1, -1).double()
+        s = (w1.unsqueeze(0) * m).sum(2)                             # [N, 3]
+        nd = (w2.unsqueeze(0) * s.unsqueeze(1)).sum(2)               # [N, 6]
+        num, den = nd[:, :3], nd[:, 3:]
+        ok = den > 0
+        res = torch.where(ok, num / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den)).float()
+        p = self.prefix
+        return {f"{p}MulticlassF1Score": res[:, 0], f"{p}MulticlassJaccardIndex": res[:, 2],
+                f"{p}MulticlassAccuracy": res[:, 1]}
+
+    def accumulate_counts(self, counts: torch.Tensor) -> None:
+        """Add [n, n] (or [N, n, n], summed) confusion counts to the running total without reducing them."""
+        c = counts.detach().reshape(-1, self.num_classes, self.num_classes).sum(0)
+        self._accumulate(c)
+
     def _reduce_matrices(self, device):
         cache = getattr(self, "_rm", None)
         if cache is not None and cache[0] == device:

@@ -32,6 +32,30 @@ class GpuImageStitcher:
         check(_lib.load().fu_stitch_add(self.net._ctx, int(sample), ptr(cv), ptr(wt), og_height, og_width, int(h0),
                                         int(w0), int(hE), int(wE), torch.cuda.current_stream(self.device).cuda_stream))
 
+    def add_images(self, samples, image_names, crop_info, og_heights, og_widths) -> None:
+        """ImageStitcher_v2.add_images (utils_image.py:386-406) without the image arrays -- crop i is sample samples[i] of
+        the net's last eval forward, still resident on the device.  The whole list goes through ONE fu_stitch_add_batch
+        launch, bit-identical to add_image for each crop in list order (also where crops of the list overlap)."""
+        samples, image_names, crop_info = list(samples), list(image_names), list(crop_info)
+        og_heights, og_widths = list(og_heights), list(og_widths)
+        n = len(samples)
+        if not (len(image_names) == len(crop_info) == len(og_heights) == len(og_widths) == n):
+            raise ValueError("add_images: samples, image_names, crop_info, og_heights and og_widths differ in length")
+        if n == 0:
+            return
+        k = self.net.n_classes
+        table = (_lib.FuStitchEntry * n)()
+        for i, (smp, name, ci, oh, ow) in enumerate(zip(samples, image_names, crop_info, og_heights, og_widths)):
+            h0, w0, hE, wE = ci if isinstance(ci, (tuple, list)) else (ci.h0, ci.w0, ci.hE, ci.wE)
+            if name not in self.image_canvas:
+                self.image_canvas[name] = torch.zeros(oh, ow, k, device=self.device)
+                self.weight_canvas[name] = torch.zeros(oh, ow, device=self.device)
+            cv, wt = self.image_canvas[name], self.weight_canvas[name]
+            table[i] = _lib.FuStitchEntry(ptr(cv), ptr(wt), int(smp), cv.shape[0], cv.shape[1], int(h0), int(w0),
+                                          int(hE), int(wE), 0)
+        check(_lib.load().fu_stitch_add_batch(self.net._ctx, n, table,
+                                              torch.cuda.current_stream(self.device).cuda_stream))
+
     def combine(self, image_name: str) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (probabilities [H, W, n_classes], argmax [H, W]); like _combine_images + the argmax of predict.py."""
         cv, wt = self.image_canvas[image_name], self.weight_canvas[image_name]

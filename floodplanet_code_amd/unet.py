@@ -230,6 +230,7 @@ class HipUNet(nn.Module):
             _lib.load().fu_destroy(self._ctx)
             self._ctx = None
             self._ctx_key = None
+            self._last_batch = 0
 
     def __del__(self):
         try:
@@ -346,6 +347,7 @@ class HipUNet(nn.Module):
             check(lib.fu_forward_srcs(ctx, arr, chs, len(srcs), B, int(training), ptr(logits), self._stream(dev)))
         if training:
             self._generation += 1
+        self._last_batch = B
         return logits
 
     def _loss_raw(self, target: torch.Tensor, ignore_index: int, device, kind: str = "ce",
@@ -376,6 +378,22 @@ class HipUNet(nn.Module):
         out = self._confusion.view(self.n_classes, self.n_classes).clone()
         self._confusion.zero_()
         return out
+
+    def eval_confusion(self, target: torch.Tensor, ignore_index: int) -> torch.Tensor:
+        """Per-sample confusion counts of the last forward's resident logits: int64 [B, k, k] on the device,
+        M[b, t, p] = #pixels of sample b with target t and argmax p (fu_eval_confusion; ignored / out-of-range targets
+        dropped as in the fused loss).  No loss, no logits gradient, no host sync."""
+        B = getattr(self, "_last_batch", 0)
+        if self._ctx is None or B == 0:
+            raise RuntimeError("eval_confusion: no forward pass yet")
+        k, H, W = self.n_classes, self._ctx_key[1], self._ctx_key[2]
+        target = target.contiguous().long()
+        if tuple(target.shape) != (B, H, W):
+            raise ValueError(f"eval_confusion: target must be [{B}, {H}, {W}] like the last forward, got {tuple(target.shape)}")
+        counts = torch.zeros(B, k, k, dtype=torch.int64, device=target.device)
+        check(_lib.load().fu_eval_confusion(self._ctx, ptr(target), int(ignore_index), ptr(counts),
+                                            self._stream(target.device)))
+        return counts
 
     # ---------------------------------------------------------------- public API
     def forward(self, x: torch.Tensor) -> torch.Tensor:

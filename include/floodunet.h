@@ -283,6 +283,29 @@ int fu_stitch_add(fu_ctx* ctx, int sample, float* canvas, float* weight, int can
 /* canvas /= (weight + 1e-5) in place (ImageStitcher_v2._combine_images); argmax_out: optional int64 [canvas_h, canvas_w] */
 int fu_stitch_finalize(float* canvas, const float* weight, int n_classes, int canvas_h, int canvas_w,
                        int64_t* argmax_out, fu_stream stream);
+/* One crop of a batched stitch: sample `sample` of the last fu_forward goes to canvas[h0:hE, w0:wE] as in fu_stitch_add.
+ * Entries that name the same canvas must name the same weight and canvas size; distinct canvases, distinct weights. */
+typedef struct fu_stitch_entry {
+  float* canvas;        /* fp32 [canvas_h, canvas_w, n_classes] */
+  float* weight;        /* fp32 [canvas_h, canvas_w] */
+  int32_t sample;
+  int32_t canvas_h, canvas_w;
+  int32_t h0, w0, hE, wE;
+  int32_t reserved;     /* 0 */
+} fu_stitch_entry;
+/* fu_stitch_add for entries[0..n-1] in one launch, bit-identical to the n calls in table order (canvas and weight), also
+ * when boxes of the table overlap on one canvas: each canvas pixel is written by one thread, which adds the covering
+ * entries' softmax in table order (no float atomics).  `entries` is a host array; every box must be non-empty and lie
+ * inside its canvas and the tile.  The table is copied into a library-owned device buffer ordered on `stream`, so calls
+ * on different streams must be ordered by the caller. */
+int fu_stitch_add_batch(fu_ctx* ctx, int n, const fu_stitch_entry* entries, fu_stream stream);
+
+/* ---- eval metrics ---------------------------------------------------------------------------- */
+/* Per-sample confusion counts of the last fu_forward (eval or training): counts_out[b][t * k + p] += #pixels of sample b
+ * with target t and p = argmax of the resident logits (first maximum wins, as fu_loss_ce), over pixels whose target is
+ * neither ignore_index nor out of [0, k).  counts_out: int64 [last batch][k][k] (k = n_classes), ADDED to.  No loss, no
+ * logits gradient; one launch, integer atomics (exact). */
+int fu_eval_confusion(fu_ctx* ctx, const int64_t* target, int ignore_index, int64_t* counts_out, fu_stream stream);
 
 /* ---- introspection ------------------------------------------------------------------------- */
 int64_t fu_workspace_bytes(const fu_ctx* ctx);
