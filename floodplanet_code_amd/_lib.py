@@ -101,6 +101,9 @@ SIGNATURES = {
     "fu_stitch_finalize": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "fu_stitch_add_batch": (_i, [_p, _i, C.POINTER(FuStitchEntry), _p]),
     "fu_eval_confusion": (_i, [_p, _p, _i, _p, _p]),
+    "fu_forward_views": (_i, [_p, C.POINTER(_p), C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(C.c_int32), _p, _p]),
+    "fu_merge_views": (_i, [_p, _p, _p, _i, _p, _p]),
+    "fu_stitch_add_batch_probs": (_i, [_p, _i, C.POINTER(FuStitchEntry), _p, _i, _p]),
     "fu_augment": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i64, _p]),
     "fu_resize_lanczos4_tiles": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "fu_assemble_tiles": (_i, [C.POINTER(_p), C.POINTER(C.c_int32), _i, _i, _i, _i, _p, _p, _i, _p, _p, _f, _p, _p, _p, _p]),

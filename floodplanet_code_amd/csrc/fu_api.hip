@@ -388,6 +388,9 @@ struct fu_ctx {
   std::vector<PackTable> pack_tabs;   // <= MAX_PACK layers per launch
   // state
   int last_batch = 0;
+  int view_n = 0;                 // fu_forward_views: views of the last forward (0: the last forward was not one) ...
+  int view_batch = 0;             // ... crops per view ...
+  unsigned view_codes = 0;        // ... and their codes, 3 bits per view (fu_merge_views)
   bool fwd_training = false;
   bool have_loss = false;
 };
@@ -835,11 +838,15 @@ int fuse_backward(fu_ctx* c, int B, hipStream_t s) {
 }
 
 int forward_impl(fu_ctx* c, const float* x, const SrcList* srcs, int B, bool training, float* logits_out,
-                 hipStream_t s) {
+                 hipStream_t s, int n_views = 0, unsigned view_codes = 0) {
   const fu_config& f = c->cfg;
+  c->view_n = 0;
   if (c->packed_dirty || c->packed_eval != !training) FU_TRY(repack(c, s, !training));
   for (int e = 0; e < c->nE; ++e) {
-    if (srcs)     // several input tensors side by side (fu_forward_srcs): the concat happens inside the layout conversion
+    if (n_views > 0)   // test-time augmentation (fu_forward_views): sample v * (B / n_views) + b = view v of crop b
+      FU_TRY(launch_gather_views_nchw_to_nhwc(c->prec, *srcs, c->xin[e], B / n_views, n_views, view_codes, c->enc_ch[e],
+                                              f.height, f.width, c->cin_pad0[e], c->enc_coff[e], s));
+    else if (srcs)     // several input tensors side by side (fu_forward_srcs): the concat happens inside the layout conversion
       FU_TRY(launch_gather_nchw_to_nhwc(c->prec, *srcs, c->xin[e], B, c->enc_ch[e], f.height, f.width, c->cin_pad0[e],
                                         c->enc_coff[e], s));
     else
@@ -872,6 +879,9 @@ int forward_impl(fu_ctx* c, const float* x, const SrcList* srcs, int B, bool tra
   FU_TRY(launch_head_fwd(c->prec, last.y, last.a, last.b, P(c, c->p_outw), P(c, c->p_outb), f.base_channels,
                          f.n_classes, B, f.height, f.width, c->logits, logits_out, s));
   c->last_batch = B;
+  c->view_n = n_views;
+  c->view_batch = n_views > 0 ? B / n_views : 0;
+  c->view_codes = view_codes;
   c->fwd_training = training;
   c->have_loss = false;
   c->have_up_scale = false;
@@ -1264,22 +1274,65 @@ int fu_forward(fu_ctx* c, const float* x, int batch, int training, float* logits
   return forward_impl(c, x, nullptr, batch, training != 0, logits_out, (hipStream_t)stream);
 }
 
+namespace {
+int make_src_list(const fu_ctx* c, const char* fn, const float* const* srcs, const int32_t* src_channels, int n_src,
+                  SrcList* S) {
+  S->n = n_src;
+  int off = 0;
+  for (int k = 0; k < n_src; ++k) {
+    FU_REQUIRE(srcs[k] && src_channels[k] >= 1, "%s: bad source %d", fn, k);
+    S->p[k] = srcs[k]; S->c[k] = src_channels[k]; S->coff[k] = off; off += src_channels[k];
+  }
+  S->coff[n_src] = off;
+  FU_REQUIRE(off == c->cfg.n_channels, "%s: the sources have %d channels in all, the model takes %d", fn, off,
+             c->cfg.n_channels);
+  return 0;
+}
+}  // namespace
+
 int fu_forward_srcs(fu_ctx* c, const float* const* srcs, const int32_t* src_channels, int n_src, int batch, int training,
                     float* logits_out, fu_stream stream) {
   FU_REQUIRE(srcs && src_channels && n_src >= 1 && n_src <= 8, "fu_forward_srcs: 1..8 sources");
   FU_TRY(check_fwd_args(c, srcs[0], batch));
   SrcList S;
-  S.n = n_src;
-  int off = 0;
-  for (int k = 0; k < n_src; ++k) {
-    FU_REQUIRE(srcs[k] && src_channels[k] >= 1, "fu_forward_srcs: bad source %d", k);
-    S.p[k] = srcs[k]; S.c[k] = src_channels[k]; S.coff[k] = off; off += src_channels[k];
-  }
-  S.coff[n_src] = off;
-  FU_REQUIRE(off == c->cfg.n_channels, "fu_forward_srcs: the sources have %d channels in all, the model takes %d", off,
-             c->cfg.n_channels);
+  FU_TRY(make_src_list(c, "fu_forward_srcs", srcs, src_channels, n_src, &S));
   SyncScope sc(c, training != 0);
   return forward_impl(c, nullptr, &S, batch, training != 0, logits_out, (hipStream_t)stream);
+}
+
+int fu_forward_views(fu_ctx* c, const float* const* srcs, const int32_t* src_channels, int n_src, int batch, int n_views,
+                     const int32_t* codes, float* logits_out, fu_stream stream) {
+  FU_REQUIRE(c, "fu_forward_views: null context");
+  FU_REQUIRE(srcs && src_channels && n_src >= 1 && n_src <= 8, "fu_forward_views: 1..8 sources");
+  FU_REQUIRE(codes && n_views >= 1 && n_views <= 8, "fu_forward_views: n_views = %d outside 1..8 (or null codes)", n_views);
+  unsigned packed = 0, seen = 0;
+  for (int v = 0; v < n_views; ++v) {
+    const int code = codes[v];
+    FU_REQUIRE(code >= 0 && code <= 7, "fu_forward_views: view %d: code %d outside 0..7", v, code);
+    FU_REQUIRE(!((seen >> code) & 1u), "fu_forward_views: view %d repeats code %d (codes must be distinct)", v, code);
+    FU_REQUIRE(!(code & FU_VIEW_TRANSPOSE) || c->cfg.height == c->cfg.width,
+               "fu_forward_views: view %d: code %d transposes, which needs a square tile (the context's is %dx%d)", v, code,
+               c->cfg.height, c->cfg.width);
+    seen |= 1u << code;
+    packed |= (unsigned)code << (3 * v);
+  }
+  FU_REQUIRE(batch >= 1 && (int64_t)batch * n_views <= c->cfg.max_batch,
+             "fu_forward_views: %d views x batch %d outside 1..%d samples (max_batch)", n_views, batch, c->cfg.max_batch);
+  FU_TRY(check_fwd_args(c, srcs[0], batch * n_views));
+  SrcList S;
+  FU_TRY(make_src_list(c, "fu_forward_views", srcs, src_channels, n_src, &S));
+  SyncScope sc(c, false);
+  return forward_impl(c, nullptr, &S, batch * n_views, false, logits_out, (hipStream_t)stream, n_views, packed);
+}
+
+int fu_merge_views(fu_ctx* c, float* probs_out, const int64_t* target, int ignore_index, int64_t* counts_out,
+                   fu_stream stream) {
+  FU_REQUIRE(c, "fu_merge_views: null context");
+  FU_REQUIRE(c->view_n > 0, "fu_merge_views: the last forward was not fu_forward_views");
+  FU_REQUIRE(probs_out || counts_out, "fu_merge_views: nothing to write (probs_out and counts_out are both null)");
+  FU_REQUIRE((target != nullptr) == (counts_out != nullptr), "fu_merge_views: target and counts_out go together");
+  return launch_merge_views(c->logits, c->cfg.height, c->cfg.width, c->cfg.n_classes, c->view_batch, c->view_n,
+                            c->view_codes, probs_out, target, ignore_index, counts_out, (hipStream_t)stream);
 }
 
 int fu_loss_ce(fu_ctx* c, const int64_t* target, int ignore_index, float* loss_out, int64_t* confusion_out,
@@ -1537,31 +1590,32 @@ int fu_stitch_add(fu_ctx* c, int sample, float* canvas, float* weight, int canva
   return launch_stitch_add(lg, c->cfg.n_classes, W, canvas, weight, canvas_w, h0, w0, dh, dw, (hipStream_t)stream);
 }
 
-int fu_stitch_add_batch(fu_ctx* c, int n, const fu_stitch_entry* entries, fu_stream stream) {
-  FU_REQUIRE(c && entries && n > 0, "fu_stitch_add_batch: null context / entries or n = %d <= 0", n);
-  FU_REQUIRE(c->last_batch > 0, "fu_stitch_add_batch: no forward pass yet");
+namespace {
+// fu_stitch_add_batch / fu_stitch_add_batch_probs: validate the table, copy it to the device, launch.  src: the resident
+// NHWC logits (probs == false) or the caller's probabilities (true), [n_samples, H, W, k] fp32.
+int stitch_batch(fu_ctx* c, const char* fn, const char* batch_name, int n, const fu_stitch_entry* entries, const float* src,
+                 int n_samples, bool probs, hipStream_t s) {
   const int H = c->cfg.height, W = c->cfg.width, k = c->cfg.n_classes;
   std::vector<StitchJob> jobs((size_t)n);
   int max_area = 0;
   for (int i = 0; i < n; ++i) {
     const fu_stitch_entry& E = entries[i];
     const int dh = E.hE - E.h0, dw = E.wE - E.w0;
-    FU_REQUIRE(E.canvas && E.weight, "fu_stitch_add_batch: entry %d: null canvas / weight", i);
-    FU_REQUIRE(E.sample >= 0 && E.sample < c->last_batch, "fu_stitch_add_batch: entry %d: sample %d not in the last batch "
-               "(%d)", i, E.sample, c->last_batch);
+    FU_REQUIRE(E.canvas && E.weight, "%s: entry %d: null canvas / weight", fn, i);
+    FU_REQUIRE(E.sample >= 0 && E.sample < n_samples, "%s: entry %d: sample %d not in the %s (%d)", fn, i, E.sample,
+               batch_name, n_samples);
     FU_REQUIRE(E.h0 >= 0 && E.w0 >= 0 && dh > 0 && dw > 0 && E.hE <= E.canvas_h && E.wE <= E.canvas_w && dh <= H && dw <= W,
-               "fu_stitch_add_batch: entry %d: crop [%d:%d, %d:%d] is empty or does not fit canvas %dx%d / tile %dx%d", i,
+               "%s: entry %d: crop [%d:%d, %d:%d] is empty or does not fit canvas %dx%d / tile %dx%d", fn, i,
                E.h0, E.hE, E.w0, E.wE, E.canvas_h, E.canvas_w, H, W);
     for (int j = 0; j < i; ++j) {   // one thread owns a canvas pixel: canvases must not share a weight or disagree in size
       const fu_stitch_entry& P = entries[j];
       FU_REQUIRE((P.canvas == E.canvas) == (P.weight == E.weight) &&
                  (P.canvas != E.canvas || (P.canvas_h == E.canvas_h && P.canvas_w == E.canvas_w)),
-                 "fu_stitch_add_batch: entries %d and %d share a canvas or a weight but not both (or differ in size)", j, i);
+                 "%s: entries %d and %d share a canvas or a weight but not both (or differ in size)", fn, j, i);
     }
-    jobs[i] = StitchJob{c->logits + (int64_t)E.sample * H * W * k, E.canvas, E.weight, E.canvas_w, E.h0, E.w0, dh, dw, 0};
+    jobs[i] = StitchJob{src + (int64_t)E.sample * H * W * k, E.canvas, E.weight, E.canvas_w, E.h0, E.w0, dh, dw, 0};
     max_area = std::max(max_area, dh * dw);
   }
-  hipStream_t s = (hipStream_t)stream;
   if (n > c->stitch_cap) {
     if (c->stitch_jobs) {
       FU_HIP_CHECK(hipDeviceSynchronize());     // an earlier launch may still read the old table
@@ -1574,7 +1628,24 @@ int fu_stitch_add_batch(fu_ctx* c, int n, const fu_stitch_entry* entries, fu_str
     c->stitch_cap = cap;
   }
   FU_HIP_CHECK(hipMemcpyAsync(c->stitch_jobs, jobs.data(), (size_t)n * sizeof(StitchJob), hipMemcpyHostToDevice, s));
-  return launch_stitch_add_batch(c->stitch_jobs, n, max_area, k, W, s);
+  return probs ? launch_stitch_add_batch_probs(c->stitch_jobs, n, max_area, k, W, s)
+               : launch_stitch_add_batch(c->stitch_jobs, n, max_area, k, W, s);
+}
+}  // namespace
+
+int fu_stitch_add_batch(fu_ctx* c, int n, const fu_stitch_entry* entries, fu_stream stream) {
+  FU_REQUIRE(c && entries && n > 0, "fu_stitch_add_batch: null context / entries or n = %d <= 0", n);
+  FU_REQUIRE(c->last_batch > 0, "fu_stitch_add_batch: no forward pass yet");
+  return stitch_batch(c, "fu_stitch_add_batch", "last batch", n, entries, c->logits, c->last_batch, false,
+                      (hipStream_t)stream);
+}
+
+int fu_stitch_add_batch_probs(fu_ctx* c, int n, const fu_stitch_entry* entries, const float* probs, int batch,
+                              fu_stream stream) {
+  FU_REQUIRE(c && entries && probs && n > 0 && batch >= 1,
+             "fu_stitch_add_batch_probs: null context / entries / probs, n = %d <= 0 or batch = %d < 1", n, batch);
+  return stitch_batch(c, "fu_stitch_add_batch_probs", "probabilities' batch", n, entries, probs, batch, true,
+                      (hipStream_t)stream);
 }
 
 int fu_eval_confusion(fu_ctx* c, const int64_t* target, int ignore_index, int64_t* counts_out, fu_stream stream) {

@@ -333,6 +333,9 @@ struct SrcList { const float* p[8]; int c[8]; int coff[9]; int n; };
 // dst [B,H,W,c_pad] <- channels [ch_off, ch_off + C) of the virtual concatenation (zero padding above C)
 int launch_gather_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B, int C, int H, int W, int c_pad, int ch_off,
                                hipStream_t s);
+// test-time augmentation: dst sample v * B + b (v < n_views) <- view ((codes >> 3v) & 7) of crop b (fu_forward_views)
+int launch_gather_views_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B, int n_views, unsigned codes, int C, int H,
+                                     int W, int c_pad, int ch_off, hipStream_t s);
 
 // BN: finalize forward statistics.  partials [nTiles][C][2]; count = B*H*W.
 // training: writes mean/invstd/a/b, updates running stats (momentum 0.1, unbiased var) and nbt.
@@ -420,6 +423,12 @@ struct StitchJob {
 int launch_stitch_add_batch(const StitchJob* jobs_dev, int n, int max_area, int ncls, int cropW, hipStream_t s);
 int launch_eval_confusion(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int B, int64_t hw,
                           int64_t* counts, hipStream_t s);
+// fu_merge_views: softmax of each view's logits, inverse view, mean in view order -> probs [B, H, W, k] (optional) and
+// confusion counts of its argmax (optional, with target; ADDED to)
+int launch_merge_views(const float* logits_nhwc, int H, int W, int ncls, int B, int n_views, unsigned codes, float* probs,
+                       const int64_t* target, int ignore_index, int64_t* counts, hipStream_t s);
+// launch_stitch_add_batch adding probabilities (StitchJob.logits -> the job's [H, W, k] fp32 probabilities)
+int launch_stitch_add_batch_probs(const StitchJob* jobs_dev, int n, int max_area, int ncls, int cropW, hipStream_t s);
 int launch_assemble_tiles(const float* const* srcs, const int* src_channels, int n_src, int B, int H, int W, const int* vh,
                           const int* vw, int norm_mode, const float* gmean, const float* gstd, float pad_value, float* out,
                           float* mean_out, float* std_out, hipStream_t s);

@@ -170,6 +170,70 @@ int launch_gather_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B, int C
   return 0;
 }
 
+// Test-time augmentation (fu_forward_views): the gather above, where destination sample v * B + b is view codes[v] of
+// crop b -- no transformed copy of the batch is ever written.  A view code is a bit set (1 = flip(-1), 2 = flip(-2),
+// 4 = transpose, applied in the order transpose, flip(-1), flip(-2)); `codes` packs 3 bits per view.  view_src_pixel maps
+// a pixel of the view to the pixel of the image it shows, view_dst_pixel the other way round (the inverse view).  The
+// transposing codes need H == W; their plane reads go down columns.
+__device__ __forceinline__ int view_src_pixel(int code, int y, int x, int H, int W) {
+  if (code & 2) y = H - 1 - y;
+  if (code & 1) x = W - 1 - x;
+  return (code & 4) ? x * W + y : y * W + x;
+}
+
+__device__ __forceinline__ int view_dst_pixel(int code, int y, int x, int H, int W) {
+  if (code & 4) { const int t = y; y = x; x = t; }
+  if (code & 1) x = W - 1 - x;
+  if (code & 2) y = H - 1 - y;
+  return y * W + x;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_gather_views_nchw_to_nhwc(SrcList S, T* __restrict__ dst, int C, int H, int W,
+                                                                    int cpad, int ch_off, int B, unsigned codes) {
+  constexpr int V = VecIO<T>::V;
+  const int HW = H * W;
+  const int p = blockIdx.x * 256 + threadIdx.x;        // pixel inside the view
+  const int o = blockIdx.y, n = blockIdx.z;            // channel vector, destination sample v * B + b
+  if (p >= HW) return;
+  const int v = n / B, b = n - v * B;
+  const int q = view_src_pixel((codes >> (3 * v)) & 7, p / W, p % W, H, W);
+  float val[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    const int c = o * V + j;
+    val[j] = 0.f;
+    if (c < C) {
+      const int cg = ch_off + c;
+      int si = 0;
+      for (int k = 1; k < S.n; ++k) si = cg >= S.coff[k] ? k : si;
+      val[j] = S.p[si][((size_t)b * S.c[si] + (cg - S.coff[si])) * HW + q];
+    }
+  }
+  VecIO<T>::store(dst + ((size_t)n * HW + p) * cpad + o * V, val);
+}
+
+int launch_gather_views_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B, int n_views, unsigned codes, int C, int H,
+                                     int W, int c_pad, int ch_off, hipStream_t s) {
+  const int V = p == PREC_F32 ? 4 : 8;
+  FU_REQUIRE(c_pad % V == 0 && n_views >= 1 && n_views <= 8 && (int64_t)B * n_views <= 65535 && c_pad / V <= 65535,
+             "gather_views_nchw_to_nhwc: bad geometry (c_pad %d, batch %d, views %d)", c_pad, B, n_views);
+  FU_REQUIRE(ch_off >= 0 && ch_off + C <= S.coff[S.n], "gather_views_nchw_to_nhwc: channels [%d, %d) outside the %d source "
+             "channels", ch_off, ch_off + C, S.coff[S.n]);
+  const dim3 g((unsigned)ceil_div(H * W, 256), (unsigned)(c_pad / V), (unsigned)(B * n_views));
+  if (p == PREC_F32)
+    hipLaunchKernelGGL(k_gather_views_nchw_to_nhwc<float>, g, dim3(256), 0, s, S, (float*)dst, C, H, W, c_pad, ch_off, B,
+                       codes);
+  else if (p == PREC_BF16)
+    hipLaunchKernelGGL(k_gather_views_nchw_to_nhwc<bf16_t>, g, dim3(256), 0, s, S, (bf16_t*)dst, C, H, W, c_pad, ch_off,
+                       B, codes);
+  else
+    hipLaunchKernelGGL(k_gather_views_nchw_to_nhwc<f16_t>, g, dim3(256), 0, s, S, (f16_t*)dst, C, H, W, c_pad, ch_off, B,
+                       codes);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_nhwc_to_nchw(Prec p, const void* src, float* dst, int B, int C, int H, int W, int c_pad, hipStream_t s) {
   const int64_t total = (int64_t)B * C * H * W;
   const int g = grid_for(total, 256);
@@ -2276,6 +2340,119 @@ int launch_eval_confusion(const float* logits_nhwc, const int64_t* target, int n
   const dim3 grid(grid_for(hw, CE_BLOCK, 64), B);
   hipLaunchKernelGGL(k_eval_confusion, grid, dim3(CE_BLOCK), 0, s, logits_nhwc, target, ncls, ignore_index, hw,
                      reinterpret_cast<unsigned long long*>(counts));
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Test-time augmentation merge (fu_merge_views): P_b = (sum over views v, in view order, of inverse view codes[v] of
+// softmax(logits of sample v * B + b)) / T, fp32 NHWC [B, H, W, k].  One thread per (crop, pixel): it reads the k logits
+// at the pixel's place in each view (view_dst_pixel), takes the softmax with the expression of k_stitch_add_batch and
+// keeps the sum in registers.  Blocks cover 16 x 16 pixel tiles, so a transposing view reads a 16 x 16 tile of its
+// logits too (whole 16-pixel row segments per block, not one pixel per row).  With counts, argmax P (first maximum wins)
+// is histogrammed against the target as in k_eval_confusion: LDS bins, then 64-bit integer atomics.
+// ------------------------------------------------------------------------------------------------
+static constexpr int MERGE_TILE = 16;
+
+__global__ __launch_bounds__(MERGE_TILE * MERGE_TILE) void k_merge_views(
+    const float* __restrict__ logits, int H, int W, int ncls, int B, int T, unsigned codes, float* __restrict__ probs,
+    const int64_t* __restrict__ target, int ignore_index, unsigned long long* __restrict__ counts) {
+  __shared__ unsigned int hist[HEAD_MAX_CLS * HEAD_MAX_CLS];
+  if (counts) {
+    for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+  }
+  const int b = blockIdx.z;
+  const int x = blockIdx.x * MERGE_TILE + (int)(threadIdx.x % MERGE_TILE);
+  const int y = blockIdx.y * MERGE_TILE + (int)(threadIdx.x / MERGE_TILE);
+  const int64_t hw = (int64_t)H * W;
+  if (y < H && x < W) {
+    float acc[HEAD_MAX_CLS];
+#pragma unroll
+    for (int k = 0; k < HEAD_MAX_CLS; ++k) acc[k] = 0.f;
+    for (int v = 0; v < T; ++v) {
+      const int q = view_dst_pixel((codes >> (3 * v)) & 7, y, x, H, W);
+      const float* z = logits + (((int64_t)v * B + b) * hw + q) * ncls;
+      float m = -INFINITY, ex[HEAD_MAX_CLS], se = 0.f;
+#pragma unroll
+      for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) m = fmaxf(m, z[k]);
+#pragma unroll
+      for (int k = 0; k < HEAD_MAX_CLS; ++k) { ex[k] = k < ncls ? expf(z[k] - m) : 0.f; se += ex[k]; }
+      const float inv = 1.f / se;
+#pragma unroll
+      for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) acc[k] += ex[k] * inv;
+    }
+    const int64_t p = (int64_t)b * hw + (int64_t)y * W + x;
+    const float fT = (float)T;
+    float pm = -INFINITY;
+    int am = 0;
+#pragma unroll
+    for (int k = 0; k < HEAD_MAX_CLS; ++k) {
+      if (k < ncls) {
+        const float pk = acc[k] / fT;
+        if (probs) probs[p * ncls + k] = pk;
+        if (pk > pm) { pm = pk; am = k; }
+      }
+    }
+    if (counts) {
+      const int64_t t = target[p];
+      if (t != (int64_t)ignore_index && t >= 0 && t < ncls) atomicAdd(&hist[(int)t * ncls + am], 1u);
+    }
+  }
+  if (counts) {
+    __syncthreads();
+    unsigned long long* out = counts + (int64_t)b * ncls * ncls;
+    for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x)
+      if (hist[i]) atomicAdd(&out[i], (unsigned long long)hist[i]);
+  }
+}
+
+int launch_merge_views(const float* logits_nhwc, int H, int W, int ncls, int B, int n_views, unsigned codes, float* probs,
+                       const int64_t* target, int ignore_index, int64_t* counts, hipStream_t s) {
+  FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS && B >= 1 && B <= 65535 && n_views >= 1 && n_views <= 8,
+             "merge_views: bad geometry (classes %d, batch %d, views %d)", ncls, B, n_views);
+  const dim3 grid((unsigned)ceil_div(W, MERGE_TILE), (unsigned)ceil_div(H, MERGE_TILE), (unsigned)B);
+  hipLaunchKernelGGL(k_merge_views, grid, dim3(MERGE_TILE * MERGE_TILE), 0, s, logits_nhwc, H, W, ncls, B, n_views, codes,
+                     probs, target, ignore_index, reinterpret_cast<unsigned long long*>(counts));
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// fu_stitch_add_batch_probs: k_stitch_add_batch's ownership scheme and table order (the first job covering a canvas pixel
+// owns it, no float atomics), adding the given probabilities ([batch, H, W, k] fp32; StitchJob.logits points at the
+// job's sample) instead of a softmax of the logits.
+__global__ void k_stitch_add_batch_probs(const StitchJob* __restrict__ jobs, int n, int ncls, int cropW) {
+  for (int e = blockIdx.y; e < n; e += gridDim.y) {
+    const StitchJob J = jobs[e];
+    const int64_t total = (int64_t)J.dh * J.dw;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * blockDim.x) {
+      const int cy = J.h0 + (int)(idx / J.dw), cx = J.w0 + (int)(idx % J.dw);
+      bool owner = true;
+      for (int j = 0; j < e && owner; ++j) owner = !stitch_covers(jobs[j], J.canvas, cy, cx);
+      if (!owner) continue;
+      const int64_t o = (int64_t)cy * J.canvasW + cx;
+      float acc[HEAD_MAX_CLS], wacc = J.weight[o];
+#pragma unroll
+      for (int k = 0; k < HEAD_MAX_CLS; ++k) acc[k] = k < ncls ? J.canvas[o * ncls + k] : 0.f;
+      for (int j = e; j < n; ++j) {
+        const StitchJob Q = jobs[j];
+        if (!stitch_covers(Q, J.canvas, cy, cx)) continue;
+        const float* pr = Q.logits + ((int64_t)(cy - Q.h0) * cropW + (cx - Q.w0)) * ncls;
+#pragma unroll
+        for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) acc[k] += pr[k];
+        wacc += 1.f;
+      }
+#pragma unroll
+      for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) J.canvas[o * ncls + k] = acc[k];
+      J.weight[o] = wacc;
+    }
+  }
+}
+
+int launch_stitch_add_batch_probs(const StitchJob* jobs_dev, int n, int max_area, int ncls, int cropW, hipStream_t s) {
+  const dim3 grid(grid_for(max_area, 256, 1024), n < 65535 ? n : 65535);
+  hipLaunchKernelGGL(k_stitch_add_batch_probs, grid, dim3(256), 0, s, jobs_dev, n, ncls, cropW);
   FU_LAUNCH_CHECK();
   return 0;
 }

@@ -18,8 +18,11 @@ image_predictions/<region>/<image>/{pred_class.tif, pred_softmax.png, cm.png}.  
     width); as in the reference, load_from_checkpoint gets no ignore_index, so the test metrics ignore no class;
   * pred_class.tif is float32, bands first (planar), written by datasets.synthetic.write_strip_tiff (the reference writes
     float16 [H, W, 3] through tifffile; the values are the same 0 / 1); PNGs come from a stdlib zlib writer.
-Out of scope: rgb.png, gt.png and rgb_cm.gif (to_RGB and a GIF encoder), infer.py, test-time augmentation, multi-GPU
-prediction, datasets other than floodplanet.
+Extension: --tta {hflip,flips,d4} (test-time augmentation, floodplanet_code_amd.tta) averages each crop's softmax over
+flips / 90-degree rotations: per batch one forward of T*B view samples (HipUNet.forward_views), one fu_merge_views for
+the averaged probabilities and their confusion counts, one fu_stitch_add_batch_probs; metrics.json gains a "tta" key.
+Out of scope: rgb.png, gt.png and rgb_cm.gif (to_RGB and a GIF encoder), infer.py, multi-GPU prediction, datasets other
+than floodplanet.
 """
 from __future__ import annotations
 
@@ -35,6 +38,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from .tta import VIEW_SETS, view_codes
 # conf/config.yaml + conf/dataset/floodplanet.yaml + conf/model/ef_model.yaml of the reference: what a key missing from
 # the experiment's config takes
 CONFIG_DEFAULTS = dict(
@@ -160,10 +164,12 @@ def conf_matrix_image(pred: np.ndarray, target: np.ndarray) -> np.ndarray:
 
 # ---------------------------------------------------------------------------------------------------------- predict
 def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_images=False, eval_region=None,
-            eval_dataset_split="test", n_workers=0, *, data_root, batch_size=None, device="cuda:0") -> dict:
+            eval_dataset_split="test", n_workers=0, *, data_root, batch_size=None, device="cuda:0", tta=None) -> dict:
     """predict.py:129-400 with batched crops.  Returns {"pred_dir", "metrics", "image_stats_f1", "image_stats_iou",
     "region_stats_f1", "region_stats_iou", "probabilities"} (probabilities: {region/image: [H, W, k] float32} of the
-    stitched canvases when predict_images, else {})."""
+    stitched canvases when predict_images, else {}).  tta: None, a tta.VIEW_SETS name or a list of view codes; with it,
+    every crop's prediction (metrics and canvases) is the mean softmax over its views.  T views run batch_size * T
+    samples per forward: lower batch_size when that does not fit."""
     from .datasets import FloodplanetTiles, TileLoader, generate_image_slice_object
     from .datasets.synthetic import write_strip_tiff
     from .models import build_model
@@ -173,6 +179,9 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
     if eval_dataset_name != "floodplanet":
         raise NotImplementedError(f'prediction supports the "floodplanet" dataset only, not "{eval_dataset_name}"')
     slice_params = generate_image_slice_object(cfg["crop_height"], cfg["crop_width"], cfg["crop_stride"])
+    codes = None
+    if tta is not None:                  # checked before any GPU work (d4 needs square crops)
+        codes = view_codes(tta, cfg["crop_height"], cfg["crop_width"])
     if eval_region:
         cfg["eval_region"] = eval_region
     ds_cfg = cfg["dataset"]
@@ -206,8 +215,13 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
                         ignore_index=cfg["ignore_index"], device_assembly=True, device_resize=True)
     with torch.no_grad():
         for batch in loader:
-            net._forward_raw(model._gather_sources(batch), False, want_logits=False)
-            counts = net.eval_confusion(batch["target"], ignore)              # [B, k, k], one launch
+            probs = None
+            if codes is None:
+                net._forward_raw(model._gather_sources(batch), False, want_logits=False)
+                counts = net.eval_confusion(batch["target"], ignore)          # [B, k, k], one launch
+            else:                                                             # one T*B forward, one merge launch
+                net.forward_views(model._gather_sources(batch), codes)
+                probs, counts = net.merge_views(batch["target"], ignore, want_probs=predict_images)
             metrics.accumulate_counts(counts)                                 # each crop once (see module docstring)
             per_crop = metrics.reduce_batch(counts)
             vals = torch.stack([per_crop[f"{metrics.prefix}MulticlassF1Score"],
@@ -233,7 +247,7 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
                     g = gt[key][cp.h0:cp.hE, cp.w0:cp.wE]
                     torch.maximum(g, (batch["target"][i, :cp.hE - cp.h0, :cp.wE - cp.w0] == 1).to(torch.uint8), out=g)
                 stitcher.add_images(range(len(meta)), keys, crops, [c.og_height for c in crops],
-                                    [c.og_width for c in crops])
+                                    [c.og_width for c in crops], probs=probs)
 
         probabilities = {}
         if predict_images:
@@ -250,6 +264,8 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
 
         all_metrics = {k: v.item() for k, v in metrics.compute().items()}
         all_metrics["eval_dataset"] = eval_dataset_name
+        if codes is not None:
+            all_metrics["tta"] = tta if isinstance(tta, str) else list(codes)
         with open(os.path.join(pred_dir, "metrics.json"), "w") as fh:
             json.dump(all_metrics, fh, indent=4)
         write_ranked_files(pred_dir, image_f1, image_iou, region_f1, region_iou)
@@ -259,8 +275,8 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
             "probabilities": probabilities}
 
 
-def main(argv: Optional[List[str]] = None) -> None:
-    """predict.py:20-70's command line plus --data_root and --batch_size."""
+def build_parser() -> argparse.ArgumentParser:
+    """predict.py:20-70's command line plus --data_root, --batch_size, --device and --tta."""
     ap = argparse.ArgumentParser()
     ap.add_argument("checkpoint_path", type=str)
     ap.add_argument("--eval_dataset_name", type=str)
@@ -272,14 +288,21 @@ def main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--data_root", type=str, required=True, help="directory that holds CSDAP_complete/")
     ap.add_argument("--batch_size", type=int, default=None, help="crops per eval forward (default: the config's)")
     ap.add_argument("--device", type=str, default="cuda:0")
-    args = ap.parse_args(argv)
+    ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
+                    help="test-time augmentation: average each crop's softmax over its flips (hflip, flips) or all eight "
+                         "flips / 90-degree rotations (d4, square crops only); default: none")
+    return ap
+
+
+def main(argv: Optional[List[str]] = None) -> None:
+    args = build_parser().parse_args(argv)
     experiment_dir = "/".join(args.checkpoint_path.split("/")[:-2])
     cfg = resolve_cfg(experiment_dir, args.checkpoint_path)
     name = args.eval_dataset_name if args.eval_dataset_name is not None else cfg["dataset"]["name"]
     n_workers = args.n_workers if args.n_workers is not None else cfg["n_workers"]
     out = predict(cfg, experiment_dir, args.checkpoint_path, eval_dataset_name=name, predict_images=args.predict_images,
                   eval_region=args.eval_region, eval_dataset_split=args.eval_dataset_split, n_workers=n_workers,
-                  data_root=args.data_root, batch_size=args.batch_size, device=args.device)
+                  data_root=args.data_root, batch_size=args.batch_size, device=args.device, tta=args.tta)
     print(json.dumps({"pred_dir": out["pred_dir"], **out["metrics"]}))
 
 

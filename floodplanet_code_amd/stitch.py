@@ -32,10 +32,13 @@ class GpuImageStitcher:
         check(_lib.load().fu_stitch_add(self.net._ctx, int(sample), ptr(cv), ptr(wt), og_height, og_width, int(h0),
                                         int(w0), int(hE), int(wE), torch.cuda.current_stream(self.device).cuda_stream))
 
-    def add_images(self, samples, image_names, crop_info, og_heights, og_widths) -> None:
+    def add_images(self, samples, image_names, crop_info, og_heights, og_widths, probs=None) -> None:
         """ImageStitcher_v2.add_images (utils_image.py:386-406) without the image arrays -- crop i is sample samples[i] of
         the net's last eval forward, still resident on the device.  The whole list goes through ONE fu_stitch_add_batch
-        launch, bit-identical to add_image for each crop in list order (also where crops of the list overlap)."""
+        launch, bit-identical to add_image for each crop in list order (also where crops of the list overlap).
+        With probs (fp32 [N, H, W, k] on the device, e.g. HipUNet.merge_views' test-time-augmented probabilities),
+        crop i adds probs[samples[i]] as it is instead of a softmax of the logits (fu_stitch_add_batch_probs): the same
+        as canvas[box] += probs[s, :dh, :dw]; weight[box] += 1 in list order, bit for bit."""
         samples, image_names, crop_info = list(samples), list(image_names), list(crop_info)
         og_heights, og_widths = list(og_heights), list(og_widths)
         n = len(samples)
@@ -44,6 +47,13 @@ class GpuImageStitcher:
         if n == 0:
             return
         k = self.net.n_classes
+        if probs is not None:
+            if probs.dim() != 4 or probs.shape[3] != k or probs.dtype != torch.float32 or not probs.is_contiguous() \
+                    or not probs.is_cuda:
+                raise ValueError(f"add_images: probs must be contiguous fp32 [N, H, W, {k}] on the GPU, got "
+                                 f"{tuple(probs.shape)} {probs.dtype} on {probs.device}")
+            if self.net._ctx is None or tuple(probs.shape[1:3]) != tuple(self.net._ctx_key[1:3]):
+                raise ValueError(f"add_images: probs tiles {tuple(probs.shape[1:3])} differ from the net's tile")
         table = (_lib.FuStitchEntry * n)()
         for i, (smp, name, ci, oh, ow) in enumerate(zip(samples, image_names, crop_info, og_heights, og_widths)):
             h0, w0, hE, wE = ci if isinstance(ci, (tuple, list)) else (ci.h0, ci.w0, ci.hE, ci.wE)
@@ -53,8 +63,11 @@ class GpuImageStitcher:
             cv, wt = self.image_canvas[name], self.weight_canvas[name]
             table[i] = _lib.FuStitchEntry(ptr(cv), ptr(wt), int(smp), cv.shape[0], cv.shape[1], int(h0), int(w0),
                                           int(hE), int(wE), 0)
-        check(_lib.load().fu_stitch_add_batch(self.net._ctx, n, table,
-                                              torch.cuda.current_stream(self.device).cuda_stream))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if probs is None:
+            check(_lib.load().fu_stitch_add_batch(self.net._ctx, n, table, stream))
+        else:
+            check(_lib.load().fu_stitch_add_batch_probs(self.net._ctx, n, table, ptr(probs), probs.shape[0], stream))
 
     def combine(self, image_name: str) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (probabilities [H, W, n_classes], argmax [H, W]); like _combine_images + the argmax of predict.py."""

@@ -231,6 +231,7 @@ class HipUNet(nn.Module):
             self._ctx = None
             self._ctx_key = None
             self._last_batch = 0
+            self._views = None
 
     def __del__(self):
         try:
@@ -324,15 +325,7 @@ class HipUNet(nn.Module):
         """x: the input tensor [B, n_channels, H, W], or a list / tuple of tensors [B, C_k, H, W] that the model sees side by
         side along the channel axis (ef_model.py:28-44 concatenates them; here fu_forward_srcs gathers them inside the
         NCHW -> NHWC conversion: no concatenated copy)."""
-        srcs = list(x) if isinstance(x, (list, tuple)) else [x]
-        if not srcs or any(t.dim() != 4 for t in srcs) or sum(t.shape[1] for t in srcs) != self.n_channels:
-            raise ValueError(f"expected input [B,{self.n_channels},H,W] (in one tensor or split along C), got "
-                             f"{[tuple(t.shape) for t in srcs]}")
-        srcs = [t.detach().contiguous().float() for t in srcs]
-        B, _, H, W = srcs[0].shape
-        dev = srcs[0].device
-        if any(t.shape[0] != B or t.shape[2:] != (H, W) or t.device != dev for t in srcs):
-            raise ValueError("all input tensors must share batch, tile size and device")
+        srcs, B, H, W, dev = self._sources(x)
         ctx = self._get_ctx(dev, B, H, W)
         lib = _lib.load()
         if training or self._eval_dirty:
@@ -348,7 +341,21 @@ class HipUNet(nn.Module):
         if training:
             self._generation += 1
         self._last_batch = B
+        self._views = None
         return logits
+
+    def _sources(self, x):
+        """x (a tensor or a list of tensors side by side along C) -> (contiguous fp32 sources, B, H, W, device)."""
+        srcs = list(x) if isinstance(x, (list, tuple)) else [x]
+        if not srcs or any(t.dim() != 4 for t in srcs) or sum(t.shape[1] for t in srcs) != self.n_channels:
+            raise ValueError(f"expected input [B,{self.n_channels},H,W] (in one tensor or split along C), got "
+                             f"{[tuple(t.shape) for t in srcs]}")
+        srcs = [t.detach().contiguous().float() for t in srcs]
+        B, _, H, W = srcs[0].shape
+        dev = srcs[0].device
+        if any(t.shape[0] != B or t.shape[2:] != (H, W) or t.device != dev for t in srcs):
+            raise ValueError("all input tensors must share batch, tile size and device")
+        return srcs, B, H, W, dev
 
     def _loss_raw(self, target: torch.Tensor, ignore_index: int, device, kind: str = "ce",
                   dice_weight: float = 1.0) -> torch.Tensor:
@@ -394,6 +401,55 @@ class HipUNet(nn.Module):
         check(_lib.load().fu_eval_confusion(self._ctx, ptr(target), int(ignore_index), ptr(counts),
                                             self._stream(target.device)))
         return counts
+
+    # ---------------------------------------------------------------- test-time augmentation
+    def forward_views(self, x, codes, want_logits: bool = False) -> Optional[torch.Tensor]:
+        """Eval forward of the T views `codes` (a tta.VIEW_SETS name or a list of view codes) of the B crops x (a tensor
+        or a list of tensors side by side along C, as forward): ONE forward of T*B samples, sample v*B + b = view
+        codes[v] of crop b, the views taken inside the input gather (fu_forward_views).  Returns the fp32 NCHW logits
+        [T*B, k, H, W] when want_logits, else None (they stay resident for merge_views).  BatchNorm always uses the
+        running statistics, whatever the module's mode."""
+        from .tta import view_codes
+        srcs, B, H, W, dev = self._sources(x)
+        codes = view_codes(codes, H, W)
+        T = len(codes)
+        ctx = self._get_ctx(dev, T * B, H, W)
+        lib = _lib.load()
+        if self._eval_dirty:
+            check(lib.fu_params_changed(ctx))
+            self._eval_dirty = False
+        logits = torch.empty(T * B, self.n_classes, H, W, dtype=torch.float32, device=dev) if want_logits else None
+        arr = (C.c_void_p * len(srcs))(*[t.data_ptr() for t in srcs])
+        chs = (C.c_int32 * len(srcs))(*[t.shape[1] for t in srcs])
+        cds = (C.c_int32 * T)(*codes)
+        check(lib.fu_forward_views(ctx, arr, chs, len(srcs), B, T, cds, ptr(logits), self._stream(dev)))
+        self._last_batch = T * B
+        self._views = (B, codes)
+        return logits
+
+    def merge_views(self, target: Optional[torch.Tensor] = None, ignore_index: int = -100, want_probs: bool = True):
+        """After forward_views: -> (probs | None, counts | None).  probs: fp32 [B, H, W, k], the mean in view order of
+        the inverse views of each view's softmax.  counts (with target int64 [B, H, W]): int64 [B, k, k] confusion counts
+        of argmax probs, ignored / out-of-range targets dropped as in eval_confusion.  One launch (fu_merge_views)."""
+        views = getattr(self, "_views", None)
+        if self._ctx is None or views is None:
+            raise RuntimeError("merge_views: the last forward was not forward_views")
+        if not want_probs and target is None:
+            raise ValueError("merge_views: nothing to compute (want_probs=False and no target)")
+        B, _ = views
+        k, H, W = self.n_classes, self._ctx_key[1], self._ctx_key[2]
+        dev = self._flat.device
+        probs = torch.empty(B, H, W, k, dtype=torch.float32, device=dev) if want_probs else None
+        counts = None
+        if target is not None:
+            target = target.contiguous().long()
+            if tuple(target.shape) != (B, H, W) or target.device != dev:
+                raise ValueError(f"merge_views: target must be [{B}, {H}, {W}] on {dev}, got {tuple(target.shape)} on "
+                                 f"{target.device}")
+            counts = torch.zeros(B, k, k, dtype=torch.int64, device=dev)
+        check(_lib.load().fu_merge_views(self._ctx, ptr(probs), ptr(target), int(ignore_index), ptr(counts),
+                                         self._stream(dev)))
+        return probs, counts
 
     # ---------------------------------------------------------------- public API
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -300,6 +300,34 @@ typedef struct fu_stitch_entry {
  * on different streams must be ordered by the caller. */
 int fu_stitch_add_batch(fu_ctx* ctx, int n, const fu_stitch_entry* entries, fu_stream stream);
 
+/* ---- test-time augmentation ------------------------------------------------------------------- */
+/* A view code is a bit set; the view of an image t is, in this order and in torch terms:
+ *   if (code & 4) t = t.transpose(-1, -2);  if (code & 1) t = t.flip(-1);  if (code & 2) t = t.flip(-2);
+ * and its inverse runs the three steps in reverse order.  Codes 0..7 are the eight symmetries of the square (3 = rot180,
+ * 5 and 6 = the two 90-degree rotations, 7 = anti-transpose); the transposing codes need a square tile.  The reference
+ * has no test-time augmentation: this section is an extension, and nothing in it restates reference code. */
+enum { FU_VIEW_HFLIP = 1, FU_VIEW_VFLIP = 2, FU_VIEW_TRANSPOSE = 4 };
+/* Eval forward of n_views * batch samples: sample v * batch + b is view codes[v] of crop b of the sources (as
+ * fu_forward_srcs).  The views are taken inside the NCHW -> NHWC input gather of every encoder: no transformed copy of
+ * the batch is written.  codes: HOST array of n_views (1..8) distinct codes in 0..7; n_views * batch <= max_batch.
+ * logits_out: optional fp32 NCHW [n_views * batch, k, H, W].  The context remembers the codes for fu_merge_views; any
+ * later forward forgets them.  A rejected call launches nothing. */
+int fu_forward_views(fu_ctx* ctx, const float* const* srcs, const int32_t* src_channels, int n_src, int batch,
+                     int n_views, const int32_t* codes, float* logits_out, fu_stream stream);
+/* After fu_forward_views, one launch: P_b = (sum over v in view order of inverse view codes[v] of softmax(logits of
+ * sample v * batch + b)) / n_views, the softmax with fu_stitch_add's expression.  probs_out: optional fp32
+ * [batch, H, W, k] = P.  counts_out: optional int64 [batch][k][k], ADDED to, counts_out[b][t * k + p] = #pixels of crop b
+ * with target t and p = argmax P (first maximum wins), over pixels whose target is neither ignore_index nor out of [0, k)
+ * (as fu_eval_confusion); target int64 [batch, H, W] comes with it.  At least one of probs_out / counts_out. */
+int fu_merge_views(fu_ctx* ctx, float* probs_out, const int64_t* target, int ignore_index, int64_t* counts_out,
+                   fu_stream stream);
+/* fu_stitch_add_batch with entries[i].sample indexing probs (fp32 [batch, H, W, k], e.g. fu_merge_views' probs_out)
+ * instead of the resident logits: the probabilities are added as they are (no softmax), with the same ownership scheme,
+ * table order and entry checks -- bit-identical to canvas[box] += probs[sample, :dh, :dw]; weight[box] += 1 in table
+ * order.  Needs no forward pass. */
+int fu_stitch_add_batch_probs(fu_ctx* ctx, int n, const fu_stitch_entry* entries, const float* probs, int batch,
+                              fu_stream stream);
+
 /* ---- eval metrics ---------------------------------------------------------------------------- */
 /* Per-sample confusion counts of the last fu_forward (eval or training): counts_out[b][t * k + p] += #pixels of sample b
  * with target t and p = argmax of the resident logits (first maximum wins, as fu_loss_ce), over pixels whose target is

@@ -3,13 +3,17 @@
   reference_loop  the reference's predict.py shape (predict.py:207-260): batch 1, NCHW logits, fu_stitch_add per crop and
                   a host read of the crop's F1 / IoU per crop;
   batched_gpu     the batched pipeline on resident synthetic tiles (the GPU stage of predict() alone): eval forward,
-                  fu_eval_confusion, per-crop metrics read once per batch, one fu_stitch_add_batch per batch;
+                  fu_eval_confusion, per-crop metrics read once per batch, one fu_stitch_add_batch per batch; with
+                  --tta, one forward of T*B view samples (fu_forward_views), fu_merge_views (probabilities and counts)
+                  and one fu_stitch_add_batch_probs per batch instead;
   predict_e2e     floodplanet_code_amd.predict.predict() end to end on datasets.synthetic.make_s1_tree, next to the host
                   loader alone (TileLoader with device assembly / resampling and nothing else), which names the cap.
 
-    python tools/predict_bench.py [--batch 16] [--precision bf16] [--crop 300] [--stride 150]
+    python tools/predict_bench.py [--batch 16] [--precision bf16] [--crop 300] [--stride 150] [--tta {none,hflip,flips,d4}]
 Prints one JSON line.  Run under `rocprofv3 --kernel-trace --stats -- python tools/predict_bench.py` to count the
-launches: one k_stitch_add_batch and one k_eval_confusion per batch, no k_ce_loss."""
+launches: one k_stitch_add_batch and one k_eval_confusion per batch, no k_ce_loss (with --tta: one
+k_gather_views_nchw_to_nhwc per encoder, one k_merge_views and one k_stitch_add_batch_probs per batch, no
+k_eval_confusion)."""
 from __future__ import annotations
 
 import argparse
@@ -46,18 +50,23 @@ def reference_loop(net, x, target, boxes, H, W, dev):
     return st.combine("img")
 
 
-def batched_gpu(net, x, target, boxes, H, W, dev, B):
+def batched_gpu(net, x, target, boxes, H, W, dev, B, codes=None):
     met = SegmentationMetrics(3, None, "test_")
     st = GpuImageStitcher(net, dev)
     vals = []
     for b0 in range(0, len(boxes), B):
         n = min(B, len(boxes) - b0)
-        net._forward_raw(x[b0:b0 + n], False, want_logits=False)
-        counts = net.eval_confusion(target[b0:b0 + n], -100)
+        probs = None
+        if codes is None:
+            net._forward_raw(x[b0:b0 + n], False, want_logits=False)
+            counts = net.eval_confusion(target[b0:b0 + n], -100)
+        else:
+            net.forward_views(x[b0:b0 + n], codes)
+            probs, counts = net.merge_views(target[b0:b0 + n], -100)
         met.accumulate_counts(counts)
         r = met.reduce_batch(counts)
         vals += torch.stack([r["test_MulticlassF1Score"], r["test_MulticlassJaccardIndex"]]).cpu().tolist()
-        st.add_images(range(n), ["img"] * n, boxes[b0:b0 + n], [H] * n, [W] * n)
+        st.add_images(range(n), ["img"] * n, boxes[b0:b0 + n], [H] * n, [W] * n, probs=probs)
     return st.combine("img")
 
 
@@ -84,7 +93,11 @@ def main():
     ap.add_argument("--label_size", type=int, default=1024)
     ap.add_argument("--n_workers", type=int, default=0)
     ap.add_argument("--skip_e2e", action="store_true")
+    ap.add_argument("--skip_reference", action="store_true", help="skip the reference-shaped loop")
+    ap.add_argument("--tta", default="none", choices=["none", "hflip", "flips", "d4"],
+                    help="test-time augmentation of the batched GPU stage and predict() (default: none)")
     args = ap.parse_args()
+    tta = None if args.tta == "none" else args.tta
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     S = args.crop
@@ -94,12 +107,15 @@ def main():
     x = torch.rand(n, 2, S, S, device=dev)
     target = torch.randint(0, 3, (n, S, S), device=dev)
     res = {"box": torch.cuda.get_device_name(dev), "precision": args.precision, "batch": args.batch, "crop": S,
-           "stride": args.stride, "resident_crops": n}
+           "stride": args.stride, "resident_crops": n, "tta": args.tta}
     with torch.no_grad():
-        res["reference_loop_crops_per_s"] = round(_rate(lambda: reference_loop(net, x, target, boxes, H, W, dev), n, dev,
-                                                        args.reps), 1)
-        res["batched_gpu_crops_per_s"] = round(_rate(lambda: batched_gpu(net, x, target, boxes, H, W, dev, args.batch), n,
-                                                     dev, args.reps), 1)
+        if not args.skip_reference:
+            res["reference_loop_crops_per_s"] = round(_rate(lambda: reference_loop(net, x, target, boxes, H, W, dev), n,
+                                                            dev, args.reps), 1)
+        res["batched_gpu_crops_per_s"] = round(_rate(lambda: batched_gpu(net, x, target, boxes, H, W, dev, args.batch,
+                                                                         tta), n, dev, args.reps), 1)
+    from floodplanet_code_amd import _lib
+    res["context_workspace_gib"] = round(_lib.load().fu_workspace_bytes(net._ctx) / 2**30, 2)   # sized for T * batch samples
     if not args.skip_e2e:
         from floodplanet_code_amd import predict as P
         from floodplanet_code_amd.datasets import FloodplanetTiles, TileLoader, generate_image_slice_object
@@ -129,10 +145,10 @@ def main():
             loader = crops / (time.perf_counter() - t0)
             full_cfg = P.resolve_cfg(exp, ckpt)
             P.predict(full_cfg, exp, ckpt, "floodplanet", n_workers=args.n_workers, data_root=root,
-                      batch_size=args.batch, device=str(dev))           # warm-up (context, packing, caches)
+                      batch_size=args.batch, device=str(dev), tta=tta)           # warm-up (context, packing, caches)
             t0 = time.perf_counter()
             P.predict(full_cfg, exp, ckpt, "floodplanet", n_workers=args.n_workers, data_root=root,
-                      batch_size=args.batch, device=str(dev))
+                      batch_size=args.batch, device=str(dev), tta=tta)
             torch.cuda.synchronize(dev)
             e2e = crops / (time.perf_counter() - t0)
         res.update({"e2e_crops": crops, "predict_e2e_crops_per_s": round(e2e, 1),
