@@ -53,6 +53,19 @@ class FuStitchEntry(C.Structure):
     ]
 
 
+class FuSceneCrop(C.Structure):
+    """fu_scene_crop (include/floodunet.h): one box of a device-resident scene for fu_scene_crops."""
+    _fields_ = [
+        ("scene", C.c_void_p),
+        ("scene_h", C.c_int32),
+        ("scene_w", C.c_int32),
+        ("h0", C.c_int32),
+        ("w0", C.c_int32),
+        ("hE", C.c_int32),
+        ("wE", C.c_int32),
+    ]
+
+
 class FloodUNetError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"libfloodunet error {status}: {message}")
@@ -105,6 +118,7 @@ SIGNATURES = {
     "fu_merge_views": (_i, [_p, _p, _p, _i, _p, _p]),
     "fu_stitch_add_batch_probs": (_i, [_p, _i, C.POINTER(FuStitchEntry), _p, _i, _p]),
     "fu_augment": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i64, _p]),
+    "fu_scene_crops": (_i, [_p, _i, C.POINTER(FuSceneCrop), _i, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p]),
     "fu_resize_lanczos4_tiles": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "fu_assemble_tiles": (_i, [C.POINTER(_p), C.POINTER(C.c_int32), _i, _i, _i, _i, _p, _p, _i, _p, _p, _f, _p, _p, _p, _p]),
     "fu_workspace_bytes": (_i64, [_p]),

@@ -381,6 +381,8 @@ struct fu_ctx {
   int64_t* n_valid = nullptr;
   StitchJob* stitch_jobs = nullptr;   // fu_stitch_add_batch: device copy of the last table (grown on demand, owned)
   int stitch_cap = 0;
+  SceneCropJob* scene_jobs = nullptr; // fu_scene_crops: device copy of the last table (grown on demand, owned)
+  int scene_cap = 0;
   float* adam_m = nullptr;        // bound (caller-owned, fu_bind_adam_state): the moments outlive the context
   float* adam_v = nullptr;
   Profiler prof;
@@ -1194,6 +1196,7 @@ int fu_destroy(fu_ctx* c) {
   if (c->arena.base) (void)hipFree(c->arena.base);
   for (void* p : c->extra_allocs) (void)hipFree(p);
   if (c->stitch_jobs) (void)hipFree(c->stitch_jobs);
+  if (c->scene_jobs) (void)hipFree(c->scene_jobs);
   delete c;
   return FU_OK;
 }
@@ -1678,6 +1681,51 @@ int fu_assemble_tiles(const float* const* srcs, const int32_t* src_channels, int
   FU_REQUIRE(srcs && src_channels && out && B >= 1 && H >= 1 && W >= 1, "fu_assemble_tiles: bad argument");
   return launch_assemble_tiles(srcs, src_channels, n_src, B, H, W, valid_h, valid_w, norm_mode, global_mean, global_std,
                                pad_value, out, mean_out, std_out, (hipStream_t)stream);
+}
+
+int fu_scene_crops(fu_ctx* c, int n, const fu_scene_crop* entries, int C, int tile_h, int tile_w, int norm_mode,
+                   const float* global_mean, const float* global_std, float pad_value, float* out, float* mean_out,
+                   float* std_out, fu_stream stream) {
+  // every check before anything is launched or copied: a rejected call leaves the stream untouched
+  FU_REQUIRE(c && entries && out, "fu_scene_crops: null context / entries / out");
+  FU_REQUIRE(n >= 1 && C >= 1 && tile_h >= 1 && tile_w >= 1, "fu_scene_crops: n = %d, C = %d, tile %dx%d (all must be >= 1)",
+             n, C, tile_h, tile_w);
+  FU_REQUIRE(norm_mode >= 0 && norm_mode <= 2, "fu_scene_crops: norm_mode must be 0 (None), 1 ('local') or 2 ('global'), "
+             "got %d", norm_mode);
+  FU_REQUIRE(norm_mode != 1 || (mean_out && std_out), "fu_scene_crops: norm_mode 'local' needs mean_out / std_out [n, C]");
+  FU_REQUIRE(norm_mode != 2 || (global_mean && global_std), "fu_scene_crops: norm_mode 'global' needs the per-channel "
+             "parameters");
+  FU_REQUIRE((int64_t)n * C <= INT32_MAX && (int64_t)n * C * tile_h * tile_w <= ((int64_t)1 << 40),
+             "fu_scene_crops: %d boxes of %d channels are too many for one call", n, C);
+  std::vector<SceneCropJob> jobs((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const fu_scene_crop& E = entries[i];
+    const int dh = E.hE - E.h0, dw = E.wE - E.w0;
+    FU_REQUIRE(E.scene, "fu_scene_crops: entry %d: null scene", i);
+    FU_REQUIRE(E.scene_h >= 1 && E.scene_w >= 1, "fu_scene_crops: entry %d: bad scene size %dx%d", i, E.scene_h, E.scene_w);
+    FU_REQUIRE(E.h0 >= 0 && E.w0 >= 0 && E.hE <= E.scene_h && E.wE <= E.scene_w,
+               "fu_scene_crops: entry %d: box [%d:%d, %d:%d] lies outside its scene %dx%d", i, E.h0, E.hE, E.w0, E.wE,
+               E.scene_h, E.scene_w);
+    FU_REQUIRE(dh >= 1 && dw >= 1, "fu_scene_crops: entry %d: box [%d:%d, %d:%d] is empty", i, E.h0, E.hE, E.w0, E.wE);
+    FU_REQUIRE(dh <= tile_h && dw <= tile_w, "fu_scene_crops: entry %d: box %dx%d is larger than the tile %dx%d", i, dh, dw,
+               tile_h, tile_w);
+    jobs[i] = SceneCropJob{E.scene, E.scene_h, E.scene_w, E.h0, E.w0, dh, dw};
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  if (n > c->scene_cap) {
+    if (c->scene_jobs) {
+      FU_HIP_CHECK(hipDeviceSynchronize());     // an earlier launch may still read the old table
+      FU_HIP_CHECK(hipFree(c->scene_jobs));
+      c->scene_jobs = nullptr;
+      c->scene_cap = 0;
+    }
+    const int cap = std::max(n, 64);
+    FU_HIP_CHECK(hipMalloc(&c->scene_jobs, (size_t)cap * sizeof(SceneCropJob)));
+    c->scene_cap = cap;
+  }
+  FU_HIP_CHECK(hipMemcpyAsync(c->scene_jobs, jobs.data(), (size_t)n * sizeof(SceneCropJob), hipMemcpyHostToDevice, s));
+  return launch_scene_crops(c->scene_jobs, n, C, tile_h, tile_w, norm_mode, global_mean, global_std, pad_value, out,
+                            mean_out, std_out, s);
 }
 
 int fu_resize_lanczos4_tiles(const float* windows, int B, int C, int win_h, int win_w, const int32_t* iy, const float* wy,

@@ -432,6 +432,15 @@ int launch_stitch_add_batch_probs(const StitchJob* jobs_dev, int n, int max_area
 int launch_assemble_tiles(const float* const* srcs, const int* src_channels, int n_src, int B, int H, int W, const int* vh,
                           const int* vw, int norm_mode, const float* gmean, const float* gstd, float pad_value, float* out,
                           float* mean_out, float* std_out, hipStream_t s);
+// one box of launch_scene_crops (device copy of a validated fu_scene_crop)
+struct SceneCropJob {
+  const float* scene;    // fp32 [C, scene_h, scene_w]
+  int scene_h, scene_w, h0, w0, dh, dw;
+};
+// fu_scene_crops: the boxes jobs_dev[0..n-1] as fu_assemble_tiles would assemble them from a zero batch holding each box
+// in the top-left corner (valid size = the box) -- the same kernels, instantiated on scene-box addressing
+int launch_scene_crops(const SceneCropJob* jobs_dev, int n, int C, int H, int W, int norm_mode, const float* gmean,
+                       const float* gstd, float pad_value, float* out, float* mean_out, float* std_out, hipStream_t s);
 int launch_resize_lanczos4_tiles(const float* win, int B, int C, int win_h, int win_w, const int* iy, const float* wy,
                                  const int* ix, const float* wx, int TH, int TW, int scale_mode, float* out, hipStream_t s);
 int launch_augment(const float* img, const int64_t* tgt, float* img_o, int64_t* tgt_o, const int* flags,

@@ -2042,18 +2042,46 @@ int launch_augment(const float* img, const int64_t* tgt, float* img_o, int64_t* 
 // that is already in HBM, instead of per item in DataLoader workers.
 // ------------------------------------------------------------------------------------------------
 
+// How k_tile_stats / k_assemble_tiles address the (sample, channel) planes they read: the plane's first valid pixel, its
+// row stride and the sample's valid crop size.  Both kernels are instantiated once per form, so fu_scene_crops runs the
+// very arithmetic of fu_assemble_tiles (same values, same order) and equals cut-then-assemble bit for bit.
+struct BatchPlanes {        // fu_assemble_tiles: sample b of the SrcList batch, crop in the top-left corner of the tile
+  SrcList S;
+  int H, W;
+  const int* vh;
+  const int* vw;
+  __device__ __forceinline__ const float* plane(int b, int c) const {
+    int si = 0;
+    for (int k = 1; k < S.n; ++k) si = c >= S.coff[k] ? k : si;
+    return S.p[si] + ((int64_t)b * S.c[si] + (c - S.coff[si])) * H * W;
+  }
+  __device__ __forceinline__ int64_t stride(int) const { return W; }
+  // (the crop sizes come from device memory: clamp, an oversized or negative entry must not read past the plane)
+  __device__ __forceinline__ int valid_h(int b) const { return vh ? min(max(vh[b], 0), H) : H; }
+  __device__ __forceinline__ int valid_w(int b) const { return vw ? min(max(vw[b], 0), W) : W; }
+};
+
+struct ScenePlanes {        // fu_scene_crops: box b of a resident scene [C, scene_h, scene_w] (boxes validated on the host)
+  const SceneCropJob* __restrict__ jobs;
+  __device__ __forceinline__ const float* plane(int b, int c) const {
+    const SceneCropJob& J = jobs[b];
+    return J.scene + ((int64_t)c * J.scene_h + J.h0) * J.scene_w + J.w0;
+  }
+  __device__ __forceinline__ int64_t stride(int b) const { return jobs[b].scene_w; }
+  __device__ __forceinline__ int valid_h(int b) const { return jobs[b].dh; }
+  __device__ __forceinline__ int valid_w(int b) const { return jobs[b].dw; }
+};
+
 // one block per (sample, channel): mean and POPULATION std (numpy .mean / .std, ddof = 0) over the valid crop, two passes
 // (the plane stays in L2), fp64 accumulation, fixed-order block reduction
-__global__ __launch_bounds__(256) void k_tile_stats(SrcList S, int Ctot, int H, int W, const int* __restrict__ vh,
-                                                    const int* __restrict__ vw, float* __restrict__ mean_o,
+template <class Planes>
+__global__ __launch_bounds__(256) void k_tile_stats(Planes P, int Ctot, float* __restrict__ mean_o,
                                                     float* __restrict__ std_o) {
   __shared__ double sm[256];
   const int b = blockIdx.x / Ctot, c = blockIdx.x - b * Ctot;
-  int si = 0;
-  for (int k = 1; k < S.n; ++k) si = c >= S.coff[k] ? k : si;
-  const float* plane = S.p[si] + ((int64_t)b * S.c[si] + (c - S.coff[si])) * H * W;
-  // (the crop sizes come from device memory: clamp, an oversized or negative entry must not read past the plane)
-  const int h = vh ? min(max(vh[b], 0), H) : H, w = vw ? min(max(vw[b], 0), W) : W;
+  const float* plane = P.plane(b, c);
+  const int64_t st = P.stride(b);
+  const int h = P.valid_h(b), w = P.valid_w(b);
   const int n = h * w;
   auto block_sum = [&](double v) {
     sm[threadIdx.x] = v;
@@ -2067,18 +2095,19 @@ __global__ __launch_bounds__(256) void k_tile_stats(SrcList S, int Ctot, int H, 
     return r;
   };
   double a = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) a += (double)plane[(i / w) * W + (i % w)];
+  for (int i = threadIdx.x; i < n; i += 256) a += (double)plane[(i / w) * st + (i % w)];
   const double mean = n > 0 ? block_sum(a) / n : 0.0;
   double q = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) { const double dlt = (double)plane[(i / w) * W + (i % w)] - mean; q += dlt * dlt; }
+  for (int i = threadIdx.x; i < n; i += 256) { const double dlt = (double)plane[(i / w) * st + (i % w)] - mean; q += dlt * dlt; }
   const double var = n > 0 ? block_sum(q) / n : 1.0;
   if (threadIdx.x == 0) { mean_o[blockIdx.x] = (float)mean; std_o[blockIdx.x] = (float)sqrt(var); }
 }
 
 // out[b][c][y][x] = inside the valid crop ? (src - mean[b][c]) / std[b][c] : pad_value
-__global__ void k_assemble_tiles(SrcList S, int Ctot, int H, int W, const int* __restrict__ vh, const int* __restrict__ vw,
-                                 const float* __restrict__ mean, const float* __restrict__ stdv, int per_sample,
-                                 float pad_value, float* __restrict__ out, int64_t total) {
+template <class Planes>
+__global__ void k_assemble_tiles(Planes P, int Ctot, int H, int W, const float* __restrict__ mean,
+                                 const float* __restrict__ stdv, int per_sample, float pad_value, float* __restrict__ out,
+                                 int64_t total) {
 #pragma clang fp contract(off)      // image -= mean; image /= std: two roundings, as numpy does them
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (int64_t)gridDim.x * blockDim.x) {
@@ -2087,12 +2116,10 @@ __global__ void k_assemble_tiles(SrcList S, int Ctot, int H, int W, const int* _
     const int y = (int)(r % H); r /= H;
     const int c = (int)(r % Ctot);
     const int b = (int)(r / Ctot);
-    int si = 0;
-    for (int k = 1; k < S.n; ++k) si = c >= S.coff[k] ? k : si;
-    const bool inside = y < (vh ? min(max(vh[b], 0), H) : H) && x < (vw ? min(max(vw[b], 0), W) : W);
+    const bool inside = y < P.valid_h(b) && x < P.valid_w(b);
     float v = pad_value;
     if (inside) {
-      v = S.p[si][(((int64_t)b * S.c[si] + (c - S.coff[si])) * H + y) * W + x];
+      v = P.plane(b, c)[y * P.stride(b) + x];
       if (mean) {
         const int mi = per_sample ? b * Ctot + c : c;
         const float d = v - mean[mi];
@@ -2101,6 +2128,27 @@ __global__ void k_assemble_tiles(SrcList S, int Ctot, int H, int W, const int* _
     }
     out[idx] = v;
   }
+}
+
+// norm_mode 1 ('local'): k_tile_stats into mean_out / std_out, then k_assemble_tiles; 0 / 2: k_assemble_tiles only.  The
+// callers have checked the arguments.
+template <class Planes>
+int launch_tiles(const Planes& P, int B, int Ctot, int H, int W, int norm_mode, const float* gmean, const float* gstd,
+                 float pad_value, float* out, float* mean_out, float* std_out, hipStream_t s) {
+  const float *mean = nullptr, *stdv = nullptr;
+  int per_sample = 0;
+  if (norm_mode == 1) {
+    hipLaunchKernelGGL(k_tile_stats<Planes>, dim3(B * Ctot), dim3(256), 0, s, P, Ctot, mean_out, std_out);
+    FU_LAUNCH_CHECK();
+    mean = mean_out; stdv = std_out; per_sample = 1;
+  } else if (norm_mode == 2) {
+    mean = gmean; stdv = gstd;
+  }
+  const int64_t total = (int64_t)B * Ctot * H * W;
+  hipLaunchKernelGGL(k_assemble_tiles<Planes>, dim3(grid_for(total, 256)), dim3(256), 0, s, P, Ctot, H, W, mean, stdv,
+                     per_sample, pad_value, out, total);
+  FU_LAUNCH_CHECK();
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -2153,6 +2201,9 @@ __global__ __launch_bounds__(256) void k_resize_lanczos4_tiles(const float* __re
 int launch_resize_lanczos4_tiles(const float* win, int B, int C, int win_h, int win_w, const int* iy, const float* wy,
                                  const int* ix, const float* wx, int TH, int TW, int scale_mode, float* out, hipStream_t s) {
   FU_REQUIRE((int64_t)B * C <= 65535 && TH >= 1 && TW >= 1 && win_h >= 1 && win_w >= 1, "resize_lanczos4_tiles: bad shape");
+  // grid.y walks the output rows 4 at a time, and the kernel indexes a window plane with 32-bit offsets
+  FU_REQUIRE(ceil_div(TH, 4) <= 65535 && (int64_t)win_h * win_w <= INT32_MAX,
+             "resize_lanczos4_tiles: tile of %d rows or window %dx%d too large for one launch", TH, win_h, win_w);
   FU_REQUIRE(scale_mode >= 0 && scale_mode <= 4, "resize_lanczos4_tiles: scale_mode %d", scale_mode);
   hipLaunchKernelGGL(k_resize_lanczos4_tiles, dim3(ceil_div(TW, 64), ceil_div(TH, 4), B * C), dim3(256), 0, s, win, C, win_h,
                      win_w, iy, wy, ix, wx, TH, TW, scale_mode, out);
@@ -2165,33 +2216,26 @@ int launch_assemble_tiles(const float* const* srcs, const int* src_channels, int
                           const int* vw, int norm_mode, const float* gmean, const float* gstd, float pad_value, float* out,
                           float* mean_out, float* std_out, hipStream_t s) {
   FU_REQUIRE(n_src >= 1 && n_src <= 8, "assemble: 1..8 sources (got %d)", n_src);
-  SrcList S;
-  S.n = n_src;
+  BatchPlanes P;
+  P.S.n = n_src;
   int off = 0;
   for (int k = 0; k < n_src; ++k) {
     FU_REQUIRE(srcs[k] && src_channels[k] >= 1, "assemble: bad source %d", k);
-    S.p[k] = srcs[k]; S.c[k] = src_channels[k]; S.coff[k] = off; off += src_channels[k];
+    P.S.p[k] = srcs[k]; P.S.c[k] = src_channels[k]; P.S.coff[k] = off; off += src_channels[k];
   }
-  S.coff[n_src] = off;
-  const int Ctot = off;
-  const float *mean = nullptr, *stdv = nullptr;
-  int per_sample = 0;
-  if (norm_mode == 1) {        // 'local'
-    FU_REQUIRE(mean_out && std_out, "assemble: norm_mode 'local' needs mean_out / std_out [B, sum C]");
-    hipLaunchKernelGGL(k_tile_stats, dim3(B * Ctot), dim3(256), 0, s, S, Ctot, H, W, vh, vw, mean_out, std_out);
-    FU_LAUNCH_CHECK();
-    mean = mean_out; stdv = std_out; per_sample = 1;
-  } else if (norm_mode == 2) { // 'global'
-    FU_REQUIRE(gmean && gstd, "assemble: norm_mode 'global' needs the per-channel parameters");
-    mean = gmean; stdv = gstd;
-  } else {
-    FU_REQUIRE(norm_mode == 0, "assemble: norm_mode must be 0 (None), 1 ('local') or 2 ('global')");
-  }
-  const int64_t total = (int64_t)B * Ctot * H * W;
-  hipLaunchKernelGGL(k_assemble_tiles, dim3(grid_for(total, 256)), dim3(256), 0, s, S, Ctot, H, W, vh, vw, mean, stdv,
-                     per_sample, pad_value, out, total);
-  FU_LAUNCH_CHECK();
-  return 0;
+  P.S.coff[n_src] = off;
+  P.H = H; P.W = W; P.vh = vh; P.vw = vw;
+  FU_REQUIRE(norm_mode >= 0 && norm_mode <= 2, "assemble: norm_mode must be 0 (None), 1 ('local') or 2 ('global')");
+  FU_REQUIRE(norm_mode != 1 || (mean_out && std_out), "assemble: norm_mode 'local' needs mean_out / std_out [B, sum C]");
+  FU_REQUIRE(norm_mode != 2 || (gmean && gstd), "assemble: norm_mode 'global' needs the per-channel parameters");
+  return launch_tiles(P, B, off, H, W, norm_mode, gmean, gstd, pad_value, out, mean_out, std_out, s);
+}
+
+int launch_scene_crops(const SceneCropJob* jobs_dev, int n, int C, int H, int W, int norm_mode, const float* gmean,
+                       const float* gstd, float pad_value, float* out, float* mean_out, float* std_out, hipStream_t s) {
+  ScenePlanes P;
+  P.jobs = jobs_dev;
+  return launch_tiles(P, n, C, H, W, norm_mode, gmean, gstd, pad_value, out, mean_out, std_out, s);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -54,6 +54,51 @@ def assemble_tiles(sources: Sequence[torch.Tensor], norm_mode: Optional[str] = N
     return out, mean.view(B, ctot, 1, 1), std.view(B, ctot, 1, 1)
 
 
+def scene_crops(ctx, boxes, tile_hw: Tuple[int, int], norm_mode: Optional[str] = None,
+                global_params: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pad_value: float = 0.0, out=None):
+    """C ABI fu_scene_crops: boxes = [(scene, (h0, w0, hE, wE)), ...], each scene a contiguous fp32 [C, H_s, W_s] on the
+    ROCm device, each box inside its scene and at most tile_hw.  -> (image [n, C, th, tw], mean, std [n, C, 1, 1]): equal
+    bit for bit to assemble_tiles of the boxes cut into the top-left corner of a zero batch with valid_hw = the box sizes.
+    ctx: the fu_ctx handle that owns the device copy of the table (HipUNet._ctx).  out: optional fp32 [>= n, C, th, tw]
+    buffer whose first n samples receive the crops."""
+    if norm_mode not in NORM_MODES:
+        raise NotImplementedError(f'Normalization mode "{norm_mode}" not implemented.')
+    n = len(boxes)
+    if n == 0:
+        raise ValueError("scene_crops: no boxes")
+    if ctx is None:
+        raise ValueError("scene_crops: no fu_ctx (run or prepare a forward first)")
+    th, tw = int(tile_hw[0]), int(tile_hw[1])
+    dev = boxes[0][0].device
+    Cc = boxes[0][0].shape[0]
+    table = (_lib.FuSceneCrop * n)()
+    for i, (scene, (h0, w0, hE, wE)) in enumerate(boxes):
+        if scene.dim() != 3 or scene.shape[0] != Cc or scene.dtype != torch.float32 or not scene.is_contiguous() \
+                or scene.device != dev or dev.type != "cuda":
+            raise ValueError(f"scene_crops: box {i}: scenes must be contiguous fp32 [{Cc}, H, W] on one ROCm device, got "
+                             f"{tuple(scene.shape)} {scene.dtype} on {scene.device}")
+        table[i] = _lib.FuSceneCrop(scene.data_ptr(), scene.shape[1], scene.shape[2], int(h0), int(w0), int(hE), int(wE))
+    if out is None:
+        out = torch.empty(n, Cc, th, tw, dtype=torch.float32, device=dev)
+    elif tuple(out.shape[1:]) != (Cc, th, tw) or out.shape[0] < n or out.dtype != torch.float32 \
+            or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"scene_crops: out must be contiguous fp32 [>= {n}, {Cc}, {th}, {tw}] on {dev}")
+    mode = NORM_MODES[norm_mode]
+    mean = torch.zeros(n, Cc, dtype=torch.float32, device=dev)
+    std = torch.ones(n, Cc, dtype=torch.float32, device=dev)
+    gm = gs = None
+    if mode == 2:
+        if global_params is None:
+            raise ValueError("norm_mode 'global' needs (mean, std) per channel")
+        gm, gs = (t.to(dev).float().contiguous() for t in global_params)
+        mean[:] = gm
+        std[:] = gs
+    check(_lib.load().fu_scene_crops(ctx, n, table, Cc, th, tw, mode, ptr(gm), ptr(gs), float(pad_value), ptr(out),
+                                     ptr(mean) if mode == 1 else None, ptr(std) if mode == 1 else None,
+                                     torch.cuda.current_stream(dev).cuda_stream))
+    return out[:n], mean.view(n, Cc, 1, 1), std.view(n, Cc, 1, 1)
+
+
 def resize_lanczos4_tiles(windows: torch.Tensor, iy: torch.Tensor, wy: torch.Tensor, ix: torch.Tensor, wx: torch.Tensor,
                           scale_mode: int = 0) -> torch.Tensor:
     """C ABI fu_resize_lanczos4_tiles: windows fp32 [B, C, wh, ww] + the tap tables of `resize.lanczos4_axis_window`

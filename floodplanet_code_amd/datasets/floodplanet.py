@@ -26,10 +26,39 @@ from .resize import lanczos4_axis_window, resize_image
 from .tiff import read_tiff, tiff_size
 from .tiles import CropParams, get_crop_slices
 
-__all__ = ["FloodplanetTiles", "RawTileView", "collate_tiles", "collate_raw_tiles"]
+__all__ = ["FloodplanetTiles", "RawTileView", "collate_tiles", "collate_raw_tiles", "select_bands"]
 
 _N_CHANNELS = {"S2": {"RGB": 3, "RGB_NIR": 4, "ALL": 10}, "PS": {"RGB": 3, "RGB_NIR": 4, "ALL": 4},
                "S1": {"ALL": 2}, "L8": {"ALL": 7}}
+
+
+def select_bands(image: np.ndarray, sensor: str, channels: str):
+    """Band selection of a decoded raster (floodplanet.py:313-337, :399-405, :460-466, :518-524): -> (bands-first float32
+    array in the raster's own resolution, stored-as-uint16 flag -- the PS scaling depends on it)."""
+    s = sensor
+    if s == "S1":
+        if image.ndim == 3 and (image.shape[0] > image.shape[1] or image.shape[0] > image.shape[2]):
+            image = np.transpose(image, (2, 0, 1))
+        image = image[:2]
+        if channels != "ALL":
+            raise NotImplementedError(f'No method to subselect S1 images with "{channels}" channel query.')
+    elif s == "PS":
+        image = np.transpose(image, (2, 0, 1))[:4]
+        sel = {"RGB": [2, 1, 0], "RGB_NIR": [2, 1, 0, 3], "ALL": None}
+        if channels not in sel:
+            raise NotImplementedError(f'No method to subselect PS images with "{channels}" channel query.')
+        image = image if sel[channels] is None else image[sel[channels]]
+    elif s == "S2":
+        sel = {"RGB": [3, 2, 1], "RGB_NIR": [3, 2, 1, 7], "ALL": None}
+        if channels not in sel:
+            raise NotImplementedError(f'No method to subselect S2 images with "{channels}" channel query.')
+        image = image if sel[channels] is None else image[sel[channels]]
+    elif s == "L8":
+        if channels != "ALL":
+            raise NotImplementedError(f'No method to subselect L8 images with "{channels}" channel query.')
+    else:
+        raise NotImplementedError(f'No loader for sensor "{s}"')
+    return np.ascontiguousarray(image, dtype=np.float32), image.dtype == np.uint16
 
 
 class FloodplanetTiles(torch.utils.data.Dataset):
@@ -159,31 +188,7 @@ class FloodplanetTiles(torch.utils.data.Dataset):
         hit = self._raster_cache.get(key)
         if hit is not None:
             return hit
-        image = read_tiff(image_path)
-        s = self.sensor
-        if s == "S1":
-            if image.ndim == 3 and (image.shape[0] > image.shape[1] or image.shape[0] > image.shape[2]):
-                image = np.transpose(image, (2, 0, 1))
-            image = image[:2]
-            if channels != "ALL":
-                raise NotImplementedError(f'No method to subselect S1 images with "{channels}" channel query.')
-        elif s == "PS":
-            image = np.transpose(image, (2, 0, 1))[:4]
-            sel = {"RGB": [2, 1, 0], "RGB_NIR": [2, 1, 0, 3], "ALL": None}
-            if channels not in sel:
-                raise NotImplementedError(f'No method to subselect PS images with "{channels}" channel query.')
-            image = image if sel[channels] is None else image[sel[channels]]
-        elif s == "S2":
-            sel = {"RGB": [3, 2, 1], "RGB_NIR": [3, 2, 1, 7], "ALL": None}
-            if channels not in sel:
-                raise NotImplementedError(f'No method to subselect S2 images with "{channels}" channel query.')
-            image = image if sel[channels] is None else image[sel[channels]]
-        elif s == "L8":
-            if channels != "ALL":
-                raise NotImplementedError(f'No method to subselect L8 images with "{channels}" channel query.')
-        else:
-            raise NotImplementedError(f'No loader for sensor "{s}"')
-        out = (np.ascontiguousarray(image, dtype=np.float32), image.dtype == np.uint16)
+        out = select_bands(read_tiff(image_path), self.sensor, channels)
         if len(self._raster_cache) >= 8:
             self._raster_cache.pop(next(iter(self._raster_cache)))
         self._raster_cache[key] = out

@@ -13,8 +13,20 @@ import numpy as np
 __all__ = ["write_strip_tiff", "make_s1_tree"]
 
 
-def write_strip_tiff(path: str, array: np.ndarray, rows_per_strip: int = 16) -> None:
-    """[H, W] or [bands, H, W] -> uncompressed, planar-separate (PlanarConfiguration 2) strip TIFF, little endian."""
+_TYPE_SIZE = {2: 1, 3: 2, 4: 4, 12: 8}          # ASCII, SHORT, LONG, DOUBLE
+
+
+def _tag_payload(typ: int, vals) -> bytes:
+    if typ == 2:                                 # ASCII: the string and its terminating NUL
+        return vals.encode("ascii") + b"\0"
+    return struct.pack("<" + {3: "H", 4: "I", 12: "d"}[typ] * len(vals), *vals)
+
+
+def write_strip_tiff(path: str, array: np.ndarray, rows_per_strip: int = 16, extra_tags=None) -> None:
+    """[H, W] or [bands, H, W] -> uncompressed, planar-separate (PlanarConfiguration 2) strip TIFF, little endian.
+    extra_tags: optional (tag, type, values) triples written after the image's own tags, in tag order -- type 2 ASCII
+    (values: str), 3 SHORT, 4 LONG or 12 DOUBLE (values: sequence); e.g. GeoTIFF georeferencing.  Without them the file
+    is byte for byte what it always was."""
     a = np.asarray(array)
     if a.ndim == 2:
         a = a[None]
@@ -27,13 +39,19 @@ def write_strip_tiff(path: str, array: np.ndarray, rows_per_strip: int = 16) -> 
     tags = [(256, 3, [W]), (257, 3, [H]), (258, 3, [a.dtype.itemsize * 8] * bands), (259, 3, [1]), (262, 3, [1]),
             (273, 4, [0] * n), (277, 3, [bands]), (278, 3, [rows_per_strip]), (279, 4, [len(s) for s in strips]),
             (284, 3, [2 if bands > 1 else 1]), (339, 3, [fmt_code] * bands)]
-    size = lambda typ, cnt: (2 if typ == 3 else 4) * cnt
+    if extra_tags:
+        own = {t for t, _, _ in tags}
+        for tag, typ, vals in extra_tags:
+            if tag in own or typ not in _TYPE_SIZE:
+                raise ValueError(f"write_strip_tiff: extra tag {tag} of type {typ} is not supported")
+        tags = sorted(tags + [(int(t), int(ty), v) for t, ty, v in extra_tags], key=lambda t: t[0])
     cursor = 8 + 2 + 12 * len(tags) + 4
     where = {}
     for tag, typ, vals in tags:
-        if size(typ, len(vals)) > 4:
+        size = len(_tag_payload(typ, vals))
+        if size > 4:
             where[tag] = cursor
-            cursor += size(typ, len(vals))
+            cursor += size + (size & 1)          # values start on a word boundary
     offs, c = [], cursor
     for st in strips:
         offs.append(c)
@@ -42,12 +60,13 @@ def write_strip_tiff(path: str, array: np.ndarray, rows_per_strip: int = 16) -> 
     for tag, typ, vals in tags:
         if tag == 273:
             vals = offs
-        raw = struct.pack("<" + ("H" if typ == 3 else "I") * len(vals), *vals)
+        raw = _tag_payload(typ, vals)
+        cnt = len(raw) if typ == 2 else len(vals)
         if len(raw) <= 4:
-            entries.append(struct.pack("<HHI", tag, typ, len(vals)) + raw.ljust(4, b"\0"))
+            entries.append(struct.pack("<HHI", tag, typ, cnt) + raw.ljust(4, b"\0"))
         else:
-            entries.append(struct.pack("<HHII", tag, typ, len(vals), where[tag]))
-            blobs.append(raw)
+            entries.append(struct.pack("<HHII", tag, typ, cnt, where[tag]))
+            blobs.append(raw + b"\0" * (len(raw) & 1))
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as fh:
         fh.write(b"II" + struct.pack("<HI", 42, 8) + struct.pack("<H", len(tags)) + b"".join(entries) + struct.pack("<I", 0))

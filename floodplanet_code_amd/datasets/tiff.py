@@ -15,7 +15,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-__all__ = ["TiffError", "read_tiff", "tiff_size", "tiff_info"]
+__all__ = ["TiffError", "read_tiff", "tiff_size", "tiff_info", "read_geotiff_tags", "GEOTIFF_TAGS"]
 
 
 class TiffError(ValueError):
@@ -27,9 +27,14 @@ _TYPE_FMT = {1: "B", 2: "c", 3: "H", 4: "I", 5: "II", 6: "b", 7: "B", 8: "h", 9:
 _TAG_NAMES = {256: "width", 257: "height", 258: "bits", 259: "compression", 262: "photometric", 273: "strip_offsets",
               277: "samples", 278: "rows_per_strip", 279: "strip_bytes", 284: "planar", 339: "sample_format",
               322: "tile_width", 324: "tile_offsets"}
+# GeoTIFF georeferencing (and GDAL's nodata string) -- read by read_geotiff_tags, ignored by the sample decoder
+GEOTIFF_TAGS = {33550: "ModelPixelScale", 33922: "ModelTiepoint", 34264: "ModelTransformation", 34735: "GeoKeyDirectory",
+                34736: "GeoDoubleParams", 34737: "GeoAsciiParams", 42113: "GDAL_NODATA"}
 
 
-def _parse_ifd(buf: memoryview) -> Tuple[str, Dict[str, tuple]]:
+def _parse_ifd(buf: memoryview, keep=()) -> Tuple[str, Dict[str, tuple]]:
+    """-> (byte order, {name: values}) of the first IFD's decoding tags, plus {tag number: values} of the tags in keep
+    (ASCII values as str, without the terminating NUL)."""
     if len(buf) < 8:
         raise TiffError("file too short for a TIFF header")
     head = bytes(buf[:2])
@@ -53,7 +58,7 @@ def _parse_ifd(buf: memoryview) -> Tuple[str, Dict[str, tuple]]:
     for i in range(n):
         e = buf[ifd + 2 + 12 * i: ifd + 14 + 12 * i]
         tag, typ, cnt = struct.unpack(bo + "HHI", e[:8])
-        name = _TAG_NAMES.get(tag)
+        name = _TAG_NAMES.get(tag, tag if tag in keep else None)
         if name is None:
             continue                      # geo keys, nodata, ... : not needed to decode the samples
         fmt = _TYPE_FMT.get(typ)
@@ -68,6 +73,9 @@ def _parse_ifd(buf: memoryview) -> Tuple[str, Dict[str, tuple]]:
             if off + nbytes > len(buf):
                 raise TiffError(f"tag {tag}: value beyond the end of the file")
             raw = bytes(buf[off:off + nbytes])
+        if typ == 2 and tag in keep:
+            tags[name] = raw.split(b"\0", 1)[0].decode("ascii", "replace")
+            continue
         tags[name] = struct.unpack(bo + fmt[0] * (cnt * len(fmt)), raw)
     return bo, tags
 
@@ -114,6 +122,15 @@ def tiff_size(path: str) -> Tuple[int, int]:
     """(height, width) -- what `rasterio.open(path).height, .width` give (floodplanet.py:103-104)."""
     info = tiff_info(path)
     return info["height"], info["width"]
+
+
+def read_geotiff_tags(path: str) -> Dict[int, object]:
+    """The GEOTIFF_TAGS the first IFD carries: {tag: tuple of numbers, or str for ASCII}.  What GDAL / rasterio read as
+    the raster's georeferencing; the samples are not decoded."""
+    with open(path, "rb") as fh:
+        buf = memoryview(fh.read())
+    _, tags = _parse_ifd(buf, keep=GEOTIFF_TAGS)
+    return {k: v for k, v in tags.items() if k in GEOTIFF_TAGS}
 
 
 def read_tiff(path: str) -> np.ndarray:

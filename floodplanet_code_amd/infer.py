@@ -1,0 +1,358 @@
+"""Label-free scene inference: restatement of st_water_seg/infer.py:17-184 (driven over folders of scenes by
+Batch_infer.sh) for machines without omegaconf, tifffile, PIL, scipy or einops.
+
+    python -m floodplanet_code_amd.infer <exp>/checkpoints/<name>.ckpt INPUT... --out_dir DIR [...]
+
+INPUT: .tif files, or directories searched recursively for *.tif.  Per scene it writes <out_dir>/<region>_pred/<image>.tif,
+uint8 [H, W] = clip(argmax of the overlap-averaged softmax, 0, 1) * 255 (infer.py:179-184), and <out_dir>/summary.json.
+The region is the grandparent directory when the parent directory is named after the sensor (CSDAP_complete/<region>/S1/),
+else the parent directory.  What runs differently:
+  * no labels: the output grid is the raster's own size, or --size H W / --scale F (CSDAP chips were trained at their
+    label grid, e.g. --size 1024 1024); the reference's dataset needs a label raster and resamples to it;
+  * the host decodes each scene once (DataLoader workers: TIFF decode + band selection); the scene is uploaded once and
+    resampled once on the device into a resident grid -- fu_resize_lanczos4_tiles with B = 1 and the whole grid as the
+    tile, the tables and sensor scaling training uses -- and every crop is cut, normalised and padded from HBM
+    (fu_scene_crops), so there is no per-crop host work;
+  * crops of consecutive scenes are packed into full batches of batch_size (scene order, then get_crop_slices order);
+    per batch one fu_scene_crops, one eval forward (or views forward + merge with --tta), one batched stitch;
+  * a scene is finalised as soon as its last crop is stitched: class map and class counts on the device, one
+    device-to-host read, then its grid and canvases are released -- memory is bounded by the scenes in flight;
+  * the stride (default min(crop_h, crop_w), infer.py:64-65) is clamped per axis to the grid, so a scene smaller than a
+    crop gets one padded crop where get_crop_slices raises; boxes are clipped to the grid (get_crop_slices' bottom-edge
+    quirk swaps the crop sizes, which only matters for non-square crops);
+  * extension: the input's GeoTIFF georeferencing goes along with the class map (the reference drops it through PIL),
+    rescaled to the output grid (geo_tags_for_grid); GDAL_NODATA is dropped.
+Out of scope: multi-GPU inference, inputs besides ms_image (dem, slope, hand, preflood), probability / RGB outputs,
+BigTIFF or compressed output.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import time
+from collections import OrderedDict
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .predict import CONFIG_DEFAULTS, _merge, resolve_cfg
+from .tta import VIEW_SETS, view_codes
+
+SCALE_MODES = {"S1": 1, "S2": 2, "L8": 3}                    # PS: 4 when stored as uint16, else 0
+EXTRA_SOURCES = ("dem", "slope", "preflood", "pre_post_difference", "chirps", "hand")
+
+
+# ---------------------------------------------------------------------------------------------------------- host side
+def find_inputs(inputs: Sequence[str]) -> List[str]:
+    """.tif files as given, directories searched recursively for *.tif (sorted), in argument order."""
+    out = []
+    for p in inputs:
+        if os.path.isdir(p):
+            found = []
+            for d, _, files in os.walk(p):
+                found += [os.path.join(d, f) for f in files if f.endswith(".tif")]
+            out += sorted(found)
+        elif p.endswith(".tif") and os.path.isfile(p):
+            out.append(p)
+        else:
+            raise FileNotFoundError(f"infer: {p} is neither a .tif file nor a directory")
+    if not out:
+        raise FileNotFoundError(f"infer: no .tif file under {list(inputs)}")
+    return out
+
+
+def region_name(path: str, sensor: str) -> str:
+    parts = os.path.normpath(os.path.abspath(path)).split(os.sep)
+    return parts[-3] if parts[-2] == sensor and len(parts) >= 3 else parts[-2]
+
+
+def output_path(out_dir: str, path: str, sensor: str) -> str:
+    """<out_dir>/<region>_pred/<image>.tif (infer.py:148-150, 180-182)."""
+    name = os.path.splitext(os.path.basename(path))[0]
+    return os.path.join(out_dir, region_name(path, sensor) + "_pred", name + ".tif")
+
+
+def grid_size(src_hw: Tuple[int, int], size: Optional[Sequence[int]] = None, scale: Optional[float] = None):
+    """Output grid of a scene: --size H W, else round(--scale * source size), else the source size."""
+    if size is not None and scale is not None:
+        raise ValueError("infer: --size and --scale are mutually exclusive")
+    if size is not None:
+        h, w = int(size[0]), int(size[1])
+    elif scale is not None:
+        if not scale > 0:
+            raise ValueError(f"infer: --scale must be > 0, got {scale}")
+        h, w = int(round(src_hw[0] * scale)), int(round(src_hw[1] * scale))
+    else:
+        h, w = int(src_hw[0]), int(src_hw[1])
+    if h < 1 or w < 1:
+        raise ValueError(f"infer: empty output grid {h}x{w}")
+    return h, w
+
+
+def crop_boxes(H: int, W: int, crop_h: int, crop_w: int, stride: int) -> List[Tuple[int, int, int, int]]:
+    """(h0, w0, hE, wE) of get_crop_slices(H, W, crop_h, crop_w, (min(stride, H), min(stride, W)), "exact"), clipped to
+    the grid."""
+    from .datasets.tiles import get_crop_slices
+    out = []
+    for h0, w0, h, w in get_crop_slices(H, W, crop_h, crop_w, (min(stride, H), min(stride, W)), mode="exact"):
+        out.append((h0, w0, min(h0 + h, H), min(w0 + w, W)))
+    return out
+
+
+def geo_tags_for_grid(tags: Dict[int, object], src_hw: Tuple[int, int], grid_hw: Tuple[int, int]):
+    """GeoTIFF tags of a source raster -> (tag, type, values) triples for the same footprint on the output grid:
+    GeoKey directory, doubles and ASCII verbatim; ModelPixelScale times source / grid size per axis; ModelTiepoint's raster
+    point scaled with the grid (the usual (0, 0) stays), and under PixelIsPoint (GeoKey 1025 = 2) its world point moved by
+    half the change in pixel size; ModelTransformation's linear part scaled (and its translation moved likewise under
+    PixelIsPoint); GDAL_NODATA dropped -- it does not apply to a 0 / 255 mask."""
+    fy, fx = src_hw[0] / grid_hw[0], src_hw[1] / grid_hw[1]
+    keys = tags.get(34735)
+    point = False
+    if keys is not None and len(keys) >= 4:
+        for i in range(int(keys[3])):
+            k = keys[4 + 4 * i: 8 + 4 * i]
+            if len(k) == 4 and k[0] == 1025 and k[1] == 0:
+                point = k[3] == 2
+    out = []
+    scale = tags.get(33550)
+    if scale is not None:
+        sx, sy = scale[0], scale[1]
+        out.append((33550, 12, [sx * fx, sy * fy] + list(scale[2:])))
+        tie = tags.get(33922)
+        if tie is not None:
+            t = list(tie)
+            for j in range(0, len(t) - 5, 6):
+                t[j] /= fx
+                t[j + 1] /= fy
+                if point:
+                    t[j + 3] += (sx * fx - sx) / 2
+                    t[j + 4] -= (sy * fy - sy) / 2
+            out.append((33922, 12, t))
+    elif 33922 in tags:
+        out.append((33922, 12, list(tags[33922])))
+    mt = tags.get(34264)
+    if mt is not None and len(mt) == 16:
+        m = list(mt)
+        for r in range(3):
+            a, b = m[4 * r], m[4 * r + 1]
+            m[4 * r], m[4 * r + 1] = a * fx, b * fy
+            if point:
+                m[4 * r + 3] += 0.5 * (a * fx - a) + 0.5 * (b * fy - b)
+        out.append((34264, 12, m))
+    if keys is not None:
+        out.append((34735, 3, list(keys)))
+    if 34736 in tags:
+        out.append((34736, 12, list(tags[34736])))
+    if 34737 in tags:
+        out.append((34737, 2, tags[34737]))
+    return out
+
+
+def resident_grid(raster: torch.Tensor, scale_mode: int, grid_hw: Tuple[int, int], device) -> torch.Tensor:
+    """Upload a band-selected raster fp32 [C, h, w] once and resample it once into the output grid fp32 [C, H, W] on the
+    device: fu_resize_lanczos4_tiles with B = 1, the whole raster as the window and the whole grid as the tile, with the
+    tables of lanczos4_axis_window (identity tables when the sizes match) and the sensor scaling training uses -- so
+    every crop of the grid equals the tile TileLoader(device_resize=True) makes of it."""
+    from .datasets.assemble import resize_lanczos4_tiles
+    from .datasets.resize import lanczos4_axis_window
+    dev = torch.device(device)
+    H, W = grid_hw
+    iy, wy, _ = lanczos4_axis_window(raster.shape[1], H, 0, H, H)
+    ix, wx, _ = lanczos4_axis_window(raster.shape[2], W, 0, W, W)
+    tabs = [torch.from_numpy(t)[None].to(dev, non_blocking=True) for t in (iy, wy, ix, wx)]
+    return resize_lanczos4_tiles(raster[None].to(dev, non_blocking=True), *tabs, scale_mode)[0]
+
+
+class SceneFiles(torch.utils.data.Dataset):
+    """Scene i of the input list, decoded: {"raster": fp32 [C, h, w] after band selection, "scale_mode", "tags", "index"}."""
+
+    def __init__(self, paths: Sequence[str], sensor: str, channels: str):
+        self.paths, self.sensor, self.channels = list(paths), sensor, channels
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, i):
+        from .datasets.floodplanet import select_bands
+        from .datasets.tiff import read_geotiff_tags, read_tiff
+        raster, was_u16 = select_bands(read_tiff(self.paths[i]), self.sensor, self.channels)
+        mode = SCALE_MODES.get(self.sensor, 4 if was_u16 else 0)
+        return {"raster": torch.from_numpy(raster), "scale_mode": mode, "tags": read_geotiff_tags(self.paths[i]),
+                "index": i}
+
+
+def check_model_inputs(cfg: dict) -> None:
+    """infer feeds the model ms_image only: reject configs whose model also takes dem / slope / ... (before any GPU work)."""
+    kw = cfg["dataset"].get("dataset_kwargs") or {}
+    extra = [k for k in EXTRA_SOURCES if kw.get(k)]
+    if extra:
+        raise NotImplementedError(f"infer feeds the model the ms_image input only; this model also takes {extra}")
+    if cfg["norm_mode"] not in (None, "local"):
+        raise NotImplementedError(f'infer: norm_mode "{cfg["norm_mode"]}" is not supported (None or "local")')
+
+
+# ---------------------------------------------------------------------------------------------------------- infer
+def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Optional[dict] = None,
+          size: Optional[Sequence[int]] = None, scale: Optional[float] = None, stride: Optional[int] = None,
+          batch_size: Optional[int] = None, tta=None, n_workers: int = 0, device: str = "cuda:0",
+          keep_probabilities: bool = False) -> dict:
+    """Class maps of every input scene (see the module docstring).  cfg: the resolved config (default: resolve_cfg of
+    the checkpoint's experiment).  Returns the summary.json dict; with keep_probabilities also "probabilities"
+    {output path: fp32 [H, W, k] stitched canvas} (one more host read per scene; for tests and comparisons)."""
+    from .datasets.floodplanet import _N_CHANNELS
+    from .models import build_model
+
+    t_start = time.perf_counter()
+    if cfg is None:
+        experiment_dir = "/".join(checkpoint_path.split("/")[:-2])
+        cfg = resolve_cfg(experiment_dir, checkpoint_path)
+    cfg = _merge(CONFIG_DEFAULTS, cfg)
+    ds_cfg = cfg["dataset"]
+    sensor, channels = ds_cfg["sensor"], ds_cfg.get("channels") or "ALL"
+    check_model_inputs(cfg)
+    try:
+        n_channels = {"ms_image": _N_CHANNELS[sensor][channels]}
+    except KeyError:
+        raise NotImplementedError(f'Cannot get number of {sensor} channels for channel query "{channels}"') from None
+    ch, cw = int(cfg["crop_height"]), int(cfg["crop_width"])
+    stride = int(stride) if stride is not None else min(ch, cw)
+    if stride < 1:
+        raise ValueError(f"infer: stride must be >= 1, got {stride}")
+    bs = int(batch_size or cfg["batch_size"])
+    codes = view_codes(tta, ch, cw) if tta is not None else None
+    paths = find_inputs(inputs)
+    outs = [output_path(out_dir, p, sensor) for p in paths]
+    if len(set(outs)) != len(outs):
+        dup = sorted({o for o in outs if outs.count(o) > 1})
+        raise ValueError(f"infer: several inputs map to the same output {dup[:3]}")
+    if size is not None or scale is not None:            # option errors before any GPU work
+        grid_size((1 << 20, 1 << 20), size, scale)
+
+    from .datasets.assemble import scene_crops
+    from .stitch import GpuImageStitcher
+    from .datasets.synthetic import write_strip_tiff
+    dev = torch.device(device)
+    model_kwargs = dict(cfg["model"].get("model_kwargs") or {})
+    model = build_model(cfg["model"]["name"], n_channels, 3, cfg["lr"], log_image_iter=cfg["log_image_iter"],
+                        to_rgb_fcn=None, ignore_index=cfg["ignore_index"], **model_kwargs)
+    model = model.load_from_checkpoint(checkpoint_path, in_channels=n_channels, n_classes=3, lr=cfg["lr"], **model_kwargs)
+    model._set_model_to_eval()
+    model = model.to(dev)
+    net = model.model
+    k = net.n_classes
+    T = len(codes) if codes is not None else 1
+    net._get_ctx(dev, T * bs, ch, cw)                    # the context owns fu_scene_crops' table: make it at full size
+    stitcher = GpuImageStitcher(net, dev)
+    C = n_channels["ms_image"]
+    crop_buf = torch.empty(bs, C, ch, cw, dtype=torch.float32, device=dev)
+    loader = torch.utils.data.DataLoader(SceneFiles(paths, sensor, channels), batch_size=None, shuffle=False,
+                                         num_workers=n_workers, pin_memory=dev.type == "cuda")
+    scenes_it = iter(loader)
+    resident: "OrderedDict[int, dict]" = OrderedDict()   # scene index -> grid, boxes, ...
+    pending: List[Tuple[int, Tuple[int, int, int, int]]] = []   # crops not yet run: (scene, box)
+    records, probabilities = [], {}
+    n_crops = max_resident = 0
+    exhausted = False
+
+    def upload(item):
+        i = int(item["index"])
+        raster = item["raster"]
+        src_hw = (raster.shape[1], raster.shape[2])
+        H, W = grid_size(src_hw, size, scale)
+        grid = resident_grid(raster, int(item["scale_mode"]), (H, W), dev)
+        boxes = crop_boxes(H, W, ch, cw, stride)
+        resident[i] = {"grid": grid, "hw": (H, W), "src_hw": src_hw, "tags": item["tags"], "left": len(boxes),
+                       "n": len(boxes)}
+        pending.extend((i, b) for b in boxes)
+
+    def finalize(i):
+        sc = resident.pop(i)
+        H, W = sc["hw"]
+        key = str(i)
+        prob, am = stitcher.combine(key)
+        cls = (am.clamp(0, 1) * 255).to(torch.uint8)
+        counts = torch.bincount(am.view(-1), minlength=k)
+        packed = torch.cat([counts.view(torch.uint8), cls.view(-1)]).cpu()      # the one device-to-host read
+        if keep_probabilities:
+            probabilities[outs[i]] = prob.cpu().numpy()
+        stitcher.drop(key)
+        class_pixels = packed[:8 * k].view(torch.int64).tolist()
+        cls_h = packed[8 * k:].numpy().reshape(H, W)
+        write_strip_tiff(outs[i], cls_h, extra_tags=geo_tags_for_grid(sc["tags"], sc["src_hw"], (H, W)))
+        records.append({"input": paths[i], "output": outs[i], "source_size": list(sc["src_hw"]),
+                        "grid_size": [H, W], "crops": sc["n"], "class_pixels": class_pixels})
+
+    with torch.no_grad():
+        while True:
+            while len(pending) < bs and not exhausted:
+                try:
+                    upload(next(scenes_it))
+                except StopIteration:
+                    exhausted = True
+                max_resident = max(max_resident, len(resident))
+            if not pending:
+                break
+            batch, pending = pending[:bs], pending[bs:]
+            n = len(batch)
+            x, _, _ = scene_crops(net._ctx, [(resident[i]["grid"], b) for i, b in batch], (ch, cw), cfg["norm_mode"],
+                                  out=crop_buf)
+            probs = None
+            if codes is None:
+                net._forward_raw(model._gather_sources({"image": x}), False, want_logits=False)
+            else:
+                net.forward_views(model._gather_sources({"image": x}), codes)
+                probs, _ = net.merge_views(None, want_probs=True)
+            stitcher.add_images(range(n), [str(i) for i, _ in batch], [b for _, b in batch],
+                                [resident[i]["hw"][0] for i, _ in batch], [resident[i]["hw"][1] for i, _ in batch],
+                                probs=probs)
+            n_crops += n
+            for i, _ in batch:
+                resident[i]["left"] -= 1
+            for i in [i for i, sc in resident.items() if sc["left"] == 0]:
+                finalize(i)
+
+    seconds = time.perf_counter() - t_start
+    summary = {"scenes": records, "n_scenes": len(records), "n_crops": n_crops, "seconds": seconds,
+               "crops_per_s": n_crops / seconds if seconds > 0 else None, "max_resident_scenes": max_resident,
+               "tta": tta if (tta is None or isinstance(tta, str)) else list(codes)}
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "summary.json"), "w") as fh:
+        json.dump(summary, fh, indent=4)
+    if keep_probabilities:
+        summary["probabilities"] = probabilities
+    return summary
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description="Water class maps of unlabelled scenes (infer.py of st_water_seg).")
+    ap.add_argument("checkpoint_path", type=str)
+    ap.add_argument("inputs", nargs="+", help=".tif files or directories (searched recursively for *.tif)")
+    ap.add_argument("--out_dir", type=str, required=True)
+    grid = ap.add_mutually_exclusive_group()
+    grid.add_argument("--size", type=int, nargs=2, metavar=("H", "W"), default=None,
+                      help="output grid of every scene (default: the raster's own size)")
+    grid.add_argument("--scale", type=float, default=None, help="output grid = round(F * the raster's size)")
+    ap.add_argument("--stride", type=int, default=None, help="crop stride (default: min(crop_height, crop_width))")
+    ap.add_argument("--batch_size", type=int, default=None, help="crops per eval forward (default: the config's)")
+    ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
+                    help="test-time augmentation: average each crop's softmax over its flips / rotations")
+    ap.add_argument("--n_workers", type=int, default=0,
+                    help="scene decoding worker processes (default 0: decode in-process, the faster setting measured)")
+    ap.add_argument("--device", type=str, default="cuda:0")
+    return ap
+
+
+def main(argv: Optional[List[str]] = None) -> None:
+    args = build_parser().parse_args(argv)
+    experiment_dir = "/".join(args.checkpoint_path.split("/")[:-2])
+    cfg = resolve_cfg(experiment_dir, args.checkpoint_path)
+    out = infer(args.checkpoint_path, args.inputs, args.out_dir, cfg=cfg, size=args.size, scale=args.scale,
+                stride=args.stride, batch_size=args.batch_size, tta=args.tta, n_workers=args.n_workers,
+                device=args.device)
+    print(json.dumps({k: v for k, v in out.items() if k != "scenes"}))
+
+
+if __name__ == "__main__":
+    main()

@@ -76,3 +76,9 @@ class GpuImageStitcher:
         check(_lib.load().fu_stitch_finalize(ptr(cv), ptr(wt), cv.shape[2], cv.shape[0], cv.shape[1], ptr(am),
                                              torch.cuda.current_stream(self.device).cuda_stream))
         return cv, am
+
+    def drop(self, image_name: str) -> None:
+        """Forget a finished image's canvases (after combine): their memory returns to the allocator, ordered on the
+        current stream, so a run's footprint is bounded by the images in flight rather than by the run."""
+        del self.image_canvas[image_name]
+        del self.weight_canvas[image_name]

@@ -275,6 +275,23 @@ int fu_resize_lanczos4_tiles(const float* windows, int B, int C, int win_h, int 
                              const int32_t* ix, const float* wx, int tile_h, int tile_w, int scale_mode, float* out,
                              fu_stream stream);
 
+/* Crops of scenes that are resident on the device (label-free inference; infer.py of the reference cuts them on the host).
+ * Entry b names a scene (fp32 [C, scene_h, scene_w] on the device) and a box [h0, hE) x [w0, wE) inside it, with
+ * 1 <= hE - h0 <= tile_h and 1 <= wE - w0 <= tile_w.  out: fp32 [n, C, tile_h, tile_w], equal bit for bit to cutting each
+ * box into the top-left corner of a zero [n, C, tile_h, tile_w] batch and calling fu_assemble_tiles on it with
+ * valid_h = hE - h0, valid_w = wE - w0 and the same norm_mode / global parameters / pad_value (mean_out / std_out: fp32
+ * [n, C], needed for 'local').  One launch, two with 'local'.  `entries` is a host array; it is copied into a
+ * library-owned device buffer ordered on `stream`, so calls on different streams must be ordered by the caller.  Every
+ * entry and argument is checked before anything is launched: a rejected call launches nothing. */
+typedef struct fu_scene_crop {
+  const float* scene;        /* fp32 [C, scene_h, scene_w] on the device */
+  int32_t scene_h, scene_w;
+  int32_t h0, w0, hE, wE;    /* the box, inside the scene, at most the tile */
+} fu_scene_crop;
+int fu_scene_crops(fu_ctx* ctx, int n, const fu_scene_crop* entries, int C, int tile_h, int tile_w, int norm_mode,
+                   const float* global_mean, const float* global_std, float pad_value, float* out, float* mean_out,
+                   float* std_out, fu_stream stream);
+
 /* ---- inference stitching (ImageStitcher_v2, utils/utils_image.py:410-494) ------------- */
 /* canvas[h0:hE, w0:wE, :] += softmax(logits of sample `sample` of the last fu_forward)[:hE-h0, :wE-w0, :];
  * weight[h0:hE, w0:wE] += 1.  canvas: fp32 [canvas_h, canvas_w, n_classes], weight: fp32 [canvas_h, canvas_w]. */
