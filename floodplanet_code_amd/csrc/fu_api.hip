@@ -666,7 +666,6 @@ inline float* P(fu_ctx* c, int idx) { return c->P + c->params[idx].off; }
 inline float* G(fu_ctx* c, int idx) { return c->G + c->params[idx].off; }
 
 int repack(fu_ctx* c, hipStream_t s, bool eval) {
-  if (FU_EXP_SKIP(8) && !c->pack_tabs.empty() && c->packed_eval == eval) { c->packed_dirty = false; return 0; }
   const int use_scale = eval ? 1 : 0;
   if (eval) {
     for (int i = 0; i < c->nb; ++i)
@@ -890,10 +889,10 @@ int forward_impl(fu_ctx* c, const float* x, const SrcList* srcs, int B, bool tra
   return 0;
 }
 
-// testing hook (fu_test_bnb_separate) and A/B switch (environment FU_BNB_SEPARATE): 1 = BatchNorm-backward sums always by
-// their own reduce pass, never from the producer of the gradient (BnbFuse, fu_common.h)
-static int g_bnb_separate = getenv("FU_BNB_SEPARATE") != nullptr ? 1 : 0;
-static int g_head_store_g = getenv("FU_HEAD_STORE_G") != nullptr ? 1 : 0;   // testing hook / A-B (fu_test_head_store_g): the head backward stores its data gradient even where the apply pass could recompute it
+// testing hook (fu_test_bnb_separate): 1 = BatchNorm-backward sums always by their own reduce pass, never from the
+// producer of the gradient (BnbFuse, fu_common.h)
+static int g_bnb_separate = 0;
+static int g_head_store_g = 0;   // testing hook (fu_test_head_store_g): the head backward stores its data gradient even where the apply pass could recompute it
 // testing hook (fu_test_perturb_bnb_sums): the fused sums are multiplied by this factor after the kernel that emitted
 // them -- the negative control of the parity tests (a wrong fused sum must make them fail); 1 = off, no launch
 static float g_test_perturb_bnb = 1.f;
@@ -916,7 +915,7 @@ int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
   // The weight-gradient chain of this conv (wgrad, slab reduce, transpose) depends only on gy and on saved activations
   // and nothing in the rest of backward depends on it: it runs on a side stream, concurrently with this conv's dgrad
   // and the next BN backward (its 8-wave workgroups spend more than half of every stage staging with the MFMA pipe
-  // idle, tools/stamp_wgrad.py; the dgrad workgroups that fit beside them on a CU use it).  db partials alternate
+  // idle, measured with s_memtime stamps; the dgrad workgroups that fit beside them on a CU use it).  db partials alternate
   // between two buffers so that the main stream only has to wait for the wgrad of two convs ago.
   const bool side = c->side != nullptr && c->side_mode != 0;
   const int par = c->wg_parity;
@@ -952,7 +951,7 @@ int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
     // this dgrad's destination is dL/d relu(bn(y)) of the block's first conv: a kernel that can (the row-stationary 16-bit
     // one) also leaves that BatchNorm's backward sums in bnb_part, consumed by the very next launch_bn_bwd on this stream
     Conv& v0 = K.c[0];
-    const bool separate = g_bnb_separate != 0;      // testing hook / FU_BNB_SEPARATE: always the separate reduce pass
+    const bool separate = g_bnb_separate != 0;      // testing hook: always the separate reduce pass
     int tiles = 0;
     BnbFuse f;
     if (c->prec != PREC_F32 && !c->sync.hook && !separate) {
@@ -1147,21 +1146,8 @@ int fu_create(const fu_config* cfg, fu_ctx** out) {
   if (st == 0 && c->cfg.bilinear && c->prec != fu::PREC_F32 && !getenv("FU_NO_SIDE_STREAM")) {
     int plo = 0, phi = 0;
     (void)hipDeviceGetStreamPriorityRange(&plo, &phi);      // plo = the lowest priority (numerically largest)
-#ifdef FU_EXPERIMENTS   // A/B knob: FU_SIDE_CU_RESERVE=k keeps k of every 8 CUs (mask bits i with i % 8 < k) out of the side stream
-    if (const char* e = getenv("FU_SIDE_CU_RESERVE")) {
-      const int k = atoi(e);
-      uint32_t mask[8];
-      for (int w = 0; w < 8; ++w) {
-        mask[w] = 0;
-        for (int b = 0; b < 32; ++b) if (((w * 32 + b) % 8) >= k) mask[w] |= 1u << b;
-      }
-      if (hipExtStreamCreateWithCUMask(&c->side_def, 8, mask) != hipSuccess) c->side_def = nullptr;
-      if (c->side_def) setenv("FU_SIDE_PRIO_DEFAULT", "1", 1);   // one masked stream serves both modes
-    } else
-#endif
     if (hipStreamCreateWithFlags(&c->side_def, hipStreamNonBlocking) != hipSuccess) c->side_def = nullptr;
-    if (c->side_def && !getenv("FU_SIDE_PRIO_DEFAULT") &&
-        hipStreamCreateWithPriority(&c->side_lo, hipStreamNonBlocking, plo) != hipSuccess)
+    if (c->side_def && hipStreamCreateWithPriority(&c->side_lo, hipStreamNonBlocking, plo) != hipSuccess)
       c->side_lo = nullptr;
     c->side = c->side_lo ? c->side_lo : c->side_def;        // side_mode starts at 1
     if (c->side) {

@@ -249,20 +249,6 @@ int launch_loss_grad_eff(const float* dlogits, float* out, int64_t n, const floa
 int launch_grad_finite_check(const float* g, int64_t n, int* guard, hipStream_t s);
 int launch_guard_book(int* guard, hipStream_t s);
 
-#ifdef FU_EXPERIMENTS   // ablation-by-skip in variant builds only (tools/build_variant.sh exp -DFU_EXPERIMENTS): FU_EXP_SKIP bit mask,
-// 1 = BN forward finalize, 2 = BN backward finalize, 4 = wgrad slab reduce + transpose, 8 = weight pack, 16 = BN backward apply,
-// 32 = bilinear backward, 64 = pool-folded BN backward passes.  The results are WRONG; only the step time means something.
-#include <stdlib.h>
-static inline int exp_skip() {
-  static int m = -1;
-  if (m < 0) { const char* e = getenv("FU_EXP_SKIP"); m = e ? atoi(e) : 0; }
-  return m;
-}
-#define FU_EXP_SKIP(bit) (::fu::exp_skip() & (bit))
-#else
-#define FU_EXP_SKIP(bit) 0
-#endif
-
 // ---- kernel launchers (implemented in the .hip files) ----------------------------------------
 // All pointers are device pointers; T-typed buffers are `void*` + Prec.
 
@@ -323,7 +309,6 @@ int launch_conv3x3_wgrad_f16(const ConvIn& in, const bf16_t* dy, int Cout, float
                              hipStream_t s);
 int launch_pack_conv3x3_f16(const float* w_oihw, int Cout, int cin_real, int cin_pad, bf16_t* wfwd, bf16_t* wdgrad,
                             hipStream_t s);
-extern int g_bf16_force_cfg;
 
 int launch_nchw_to_nhwc(Prec p, const float* src, void* dst, int B, int C, int H, int W, int c_pad, hipStream_t s,
                         int src_channels = 0, int src_channel_offset = 0);

@@ -76,7 +76,6 @@ __device__ __forceinline__ void static_for(F&& f) {
   } while (0)
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
 
 #ifdef __HIPCC__
 // ---- the element conversions (the only arithmetic that depends on the 16-bit format) ----
@@ -85,44 +84,25 @@ typedef _Float16 e16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ bf16_t f2e(float f) { return f2h(f); }                                   // RNE
 __device__ __forceinline__ float e2f_lo(unsigned v) { return h2f((unsigned short)(v & 0xffffu)); }  // v_cvt_f32_f16
 __device__ __forceinline__ float e2f_hi(unsigned v) { return h2f((unsigned short)(v >> 16)); }      // v_cvt_f32_f16 sdwa WORD_1
-__device__ __forceinline__ f32x2 e2f_pair(unsigned v) {
-  return __builtin_convertvector(__builtin_bit_cast(e16x2, v), f32x2);
-}
 #else
 typedef __bf16 e16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ bf16_t f2e(float f) { return f2bf(f); }
 __device__ __forceinline__ float e2f_lo(unsigned v) { return __uint_as_float(v << 16); }
 __device__ __forceinline__ float e2f_hi(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
-__device__ __forceinline__ f32x2 e2f_pair(unsigned v) {
-  f32x2 x;
-  x.x = __uint_as_float(v << 16);
-  x.y = __uint_as_float(v & 0xffff0000u);
-  return x;
-}
 #endif
 __device__ __forceinline__ unsigned pack_e2(f32x2 v) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, e16x2));    // v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 (RNE)
 }
 
-// relu(a * x + b) on the two 16-bit channels of one dword; one rounding to the element type
-#ifndef FU_PACKED_BN
-#define FU_PACKED_BN 0
-#endif
+// relu(a * x + b) on the two 16-bit channels of one dword; one rounding to the element type.  Plain v_fma_f32 /
+// v_max_f32 per channel: the packed-f32 form (v_pk_fma_f32, ReLU as v_pk_max_i16) is three instructions shorter per pair
+// and was round 1's choice, but packed f32 VALU is slow beside a co-resident wave's MFMAs (MI355X_MICROARCH.md, "price
+// of one filler": +22 cycles per v_pk_fma_f32): s_memtime stamps of the row-stationary kernel's staging phase, 10 units
+// per thread and chunk: 6000 cycles packed, 3300 plain
 __device__ __forceinline__ unsigned bn_relu_pair(unsigned v, f32x2 a, f32x2 b) {
-#if !FU_PACKED_BN
-  // plain v_fma_f32 / v_max_f32 per channel.  The packed-f32 form below is three instructions shorter per pair and was
-  // round 1's choice, but packed f32 VALU is slow beside a co-resident wave's MFMAs (MI355X_MICROARCH.md, "price of one
-  // filler": +22 cycles per v_pk_fma_f32): s_memtime stamps of the row-stationary kernel's staging phase, 10 units per
-  // thread and chunk: 6000 cycles packed, 3300 plain (tools/stamp_rs.py)
   const float lo = fmaxf(fmaf(a.x, e2f_lo(v), b.x), 0.f), hi = fmaxf(fmaf(a.y, e2f_hi(v), b.y), 0.f);
   return pack_e2(f32x2{lo, hi});
-#endif
-  f32x2 x = e2f_pair(v);
-  x = __builtin_elementwise_fma(a, x, b);                                    // v_pk_fma_f32 (= bn_act_fused per lane)
-  const s16x2 h = __builtin_bit_cast(s16x2, pack_e2(x));
-  const s16x2 z = {0, 0};
-  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(h, z));      // v_pk_max_i16: the sign bit test of bf16 AND of
-}                                                                            // fp16 (sign-magnitude, bit 15) = relu
+}
 
 #endif
 
@@ -135,7 +115,6 @@ struct BConvP {
   int C0, C1, Cin, N, D0, D1, B, H, W, tilesX, tilesY, nPix, nCo;
   unsigned rcp_nPix, rcp_tilesX, rcp_tilesY;   // fast path: floor(2^32 / d) + 1 (0 for d == 1)
   unsigned rcp_nCo;                            // row-stationary kernel: channel tile fastest in the workgroup order
-  unsigned long long* dbg;   // optional s_memtime stamps per workgroup (tools/stamp_test.py; FU_CONV_STAMPS builds)
   int center_only;           // 1: every tap but the centre one of wpk is zero (embedded 1x1): the fast kernel skips them
   // row-stationary kernel, dgrad into a BatchNorm's output gradient (BnbFuse, fu_common.h): the raw conv output y of that
   // BatchNorm, its a / b / mean / invstd, and the per-tile sums [nPix][N][2]; all null otherwise

@@ -15,7 +15,6 @@
 #include "fu_common.h"
 #include "fu_conv_bf16.h"
 
-#include <stdlib.h>
 #include <type_traits>
 
 namespace fu {
@@ -363,12 +362,9 @@ static int launch_cfg(BConvP& P, const LaunchOpts& o, hipStream_t s) {
 
 #if FU_HALF      // the hooks live in the bf16 objects; the fp16 kernels obey the same switches
 extern int g_bf16_force_general, g_bf16_force_full_taps, g_wgrad_force_lockstep;
-extern unsigned long long* g_conv_dbg;
 #else
-int g_bf16_force_cfg = -1;  // testing hook: 0 = 256x64 tile, 2 = 256x32 tile
 int g_bf16_force_general = 0;   // testing hook (fu_test_force_general_conv): skip the aligned-shape fast kernel
 int g_bf16_force_full_taps = 0; // testing hook (fu_test_force_full_taps): embedded 1x1 convs run all nine taps
-unsigned long long* g_conv_dbg = nullptr;
 #endif
 
 int launch_conv3x3_bf16(const ConvIn& in, const bf16_t* wpk, const float* bias, bf16_t* dst0, int D0, bf16_t* dst1,
@@ -378,7 +374,6 @@ int launch_conv3x3_bf16(const ConvIn& in, const bf16_t* wpk, const float* bias, 
   P.wpk = wpk; P.bias = bias; P.dst0 = dst0; P.dst1 = dst1; P.stats = stats;
   P.C0 = in.C0; P.C1 = in.src1 ? in.C1 : 0; P.Cin = P.C0 + P.C1; P.N = D0 + D1; P.D0 = D0; P.D1 = D1;
   P.B = B; P.H = H; P.W = W;
-  P.dbg = g_conv_dbg;
   P.center_only = (in.center_only && !g_bf16_force_full_taps) ? 1 : 0;
   P.bnb_y = nullptr; P.bnb_a = P.bnb_b = P.bnb_mean = P.bnb_invstd = nullptr; P.bnb_part = nullptr;
   FU_REQUIRE(P.C0 % 8 == 0 && P.C1 % 8 == 0, "conv3x3_bf16: input channel counts must be multiples of 8 (C0=%d C1=%d)",
@@ -401,7 +396,6 @@ int launch_conv3x3_bf16(const ConvIn& in, const bf16_t* wpk, const float* bias, 
   int cfg;
   if (P.N >= 64 && t256 * ceil_div(P.N, 64) >= 512) cfg = 0;
   else cfg = 2;
-  if (g_bf16_force_cfg == 0 || g_bf16_force_cfg == 2) cfg = g_bf16_force_cfg;
   int st;
   if (cfg == 0) st = launch_cfg<4, 1, 2>(P, in.opt, s);
   else st = launch_cfg<4, 1, 1>(P, in.opt, s);
@@ -417,7 +411,6 @@ struct BWgP {
   float* slab;
   int C0, C1, Cin, Cout, B, H, W, tilesX, tilesY, nPix, nCi, nCo, S, perSplit;
   unsigned rcp_tilesX, rcp_tilesY;   // k_wgrad_bf16_pp<true>: floor(2^32 / d) + 1 (0 for d == 1), as in BConvP
-  unsigned long long* dbg;   // FU_CONV_STAMPS builds: per-workgroup phase sums (tools/stamp_wgrad.py)
 };
 
 // Two transposing reads -> one MFMA fragment.  NOTE (hipcc / ROCm 7.2): the v4i16 form of the builtin followed by
@@ -563,36 +556,15 @@ __global__ __launch_bounds__(128 * WMI) void k_wgrad_bf16(BWgP P) {
 
   const int pt0 = split * P.perSplit;
   const int pt1 = min(P.nPix, pt0 + P.perSplit);
-#ifdef FU_CONV_STAMPS
-  unsigned long long tStage = 0, tIssue = 0, tMfma = 0, tW = 0, tS = 0, tA = __builtin_amdgcn_s_memtime(), tStart = tA;
-#endif
   if (pt0 < pt1) load_tile(pt0);
   for (int pt = pt0; pt < pt1; ++pt) {
-#ifdef FU_CONV_STAMPS
-    tA = __builtin_amdgcn_s_memtime();
-#endif
     __syncthreads();            // previous stage's fragment reads are done (sAB visible on the first pass)
-#ifdef FU_CONV_STAMPS
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-#endif
     store_tile();
-#ifdef FU_CONV_STAMPS
-    const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-#endif
     __syncthreads();
-#ifdef FU_CONV_STAMPS
-    const unsigned long long tB = __builtin_amdgcn_s_memtime();
-    if (pt > pt0) { tW += t1 - tA; tS += t3 - t2; }
-#endif
     // in flight under the MFMA block.  ALWAYS issued (the last stage re-reads its own tile): under `if (pt + 1 < pt1)`
     // the staging registers are phis of a loaded and a not-loaded path, hipcc copies some of them right behind the
     // loads and waits for them (vmcnt) in front of the MFMA block -- with one workgroup per CU nothing covers that
     load_tile(min(pt + 1, pt1 - 1));
-#ifdef FU_CONV_STAMPS
-    const unsigned long long tC = __builtin_amdgcn_s_memtime();
-#endif
     // Walk the halo rows once: the X fragment of (halo row hr, column shift dx) feeds up to three taps
     // (dy = 0..2 with pixel row r = hr - dy), so every fragment is fetched from LDS once; dy fragments of the last
     // three pixel rows stay in a 4-deep register ring.  Next step's fragment is requested before this step's MFMAs.
@@ -635,14 +607,7 @@ __global__ __launch_bounds__(128 * WMI) void k_wgrad_bf16(BWgP P) {
         acc[0] = FU_MFMA32(Af[(3 * (r + 1) + 1) & 1], Bf[r & 3], acc[0]);
       });
     }
-#ifdef FU_CONV_STAMPS
-    const unsigned long long tD = __builtin_amdgcn_s_memtime();
-    if (pt > pt0) { tStage += tB - tA; tIssue += tC - tB; tMfma += tD - tC; }
-#endif
   }
-#ifdef FU_CONV_STAMPS
-  const unsigned long long tE = __builtin_amdgcn_s_memtime();
-#endif
   // slab[split][tap][Cin / 4][Cout][4] (see k_wgrad_transpose<true>): accumulator registers 4j .. 4j+3 of a lane are c_in
   // 8j + 4 lh + {0..3} of its c_out -- one 16-byte store, 512 contiguous bytes per 32 lanes
   const int co = co0 + ni * 32 + l31;
@@ -660,21 +625,13 @@ __global__ __launch_bounds__(128 * WMI) void k_wgrad_bf16(BWgP P) {
       }
     }
   }
-#ifdef FU_CONV_STAMPS
-  if (P.dbg && lane == 0 && blockIdx.x < 256) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned long long* d = P.dbg + ((size_t)blockIdx.x * 8 + wave) * 8;
-    d[0] = tStage; d[1] = tIssue; d[2] = tMfma; d[3] = (unsigned long long)max(pt1 - pt0 - 1, 0);
-    d[4] = __builtin_amdgcn_s_memtime() - tE; d[5] = __builtin_amdgcn_s_memtime() - tStart; d[6] = tW; d[7] = tS;
-  }
-#endif
 }
 
 
 // ------------------------------------------------------------------------------------------------
 // wgrad, ping-pong version for c_in tiles of 128 (8 waves, one workgroup per CU)
 //
-// k_wgrad_bf16<4,8> spends half of every stage with the MFMA pipe idle (tools/stamp_wgrad.py: per stage 4450 cycles of
+// k_wgrad_bf16<4,8> spends half of every stage with the MFMA pipe idle (s_memtime stamps: per stage 4450 cycles of
 // MFMA work for the two waves of a SIMD, 2400 BN/ReLU + LDS store, 1900 load issue at the texture unit's 64 B/clk, all
 // in lock step because the single LDS stage needs two barriers).  Here the stage is double-buffered (rows unpadded and
 // XOR-swizzled by 64-byte chunk instead, 2 x 62.5 KB) and the 8 waves form two groups half a stage apart: while waves
@@ -954,10 +911,7 @@ __global__ __launch_bounds__(512) void k_wgrad_bf16_pp(BWgP P) {
   };
   // x fragments: a ring APD steps ahead of the MFMAs (depths 1-3 measured the same once the first fragments are in flight
   // before the phase starts)
-#ifndef FU_WGRAD_APD
-#define FU_WGRAD_APD 2
-#endif
-  constexpr int APD = FU_WGRAD_APD, NA = APD + 1, NST = 3 * (PTH + 2);
+  constexpr int APD = 2, NA = APD + 1, NST = 3 * (PTH + 2);
   static_assert(APD <= 3, "the fragments requested ahead of the barrier must lie in halo row 0");
   frag8_t Af[NA], Bf[4];
   // fragment addresses = one lane base per (buffer, row residue) + an immediate (ds offsets reach 64 KB, a buffer is 62.5 KB:
@@ -1017,9 +971,6 @@ __global__ __launch_bounds__(512) void k_wgrad_bf16_pp(BWgP P) {
     load_half_any(min(pt0 + 2, pt1 - 1));
     __syncthreads();
   }
-#ifdef FU_CONV_STAMPS
-  unsigned long long tM = 0, tB1 = 0, tSt = 0, tLd = 0, tB2 = 0, tGap = 0, sPrev = 0;
-#endif
   // The loop is unrolled by the buffer parity: with `(n & 1) ? buf1 : buf0` every LDS address of the MFMA phase existed in
   // two variants that hipcc kept in spilled SGPRs and selected at the top of each iteration -- 60 scalar instructions between
   // the barrier and the first fragment read.
@@ -1029,24 +980,11 @@ __global__ __launch_bounds__(512) void k_wgrad_bf16_pp(BWgP P) {
   // Barrier of the loop: this wave's LDS traffic done (lgkmcnt), then s_barrier.  __syncthreads() also waits with vmcnt(0),
   // i.e. for the loads of stage n+2 that the staging half has just issued -- they are needed one whole interval later (round 4:
   // found with the persistent conv kernel, fu_conv_pp.hip; here the staging interval ended with an HBM latency in it).
-#ifdef FU_WGRAD_OLD_BARRIER     // (A/B builds)
-  auto wg_barrier = []() __attribute__((always_inline)) { __syncthreads(); };
-#else
   auto wg_barrier = []() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-#endif
   auto body = [&](auto Par, int n) __attribute__((always_inline)) {
     constexpr int par = decltype(Par)::value;
-#ifdef FU_CONV_STAMPS
-    const unsigned long long s0 = __builtin_amdgcn_s_memtime();
-#endif
     mfma_stage(Par);
-#ifdef FU_CONV_STAMPS
-    const unsigned long long s1 = __builtin_amdgcn_s_memtime();
-#endif
     wg_barrier();
-#ifdef FU_CONV_STAMPS
-    const unsigned long long s2 = __builtin_amdgcn_s_memtime();
-#endif
     // stage n+1+grp (already in registers) -> the other buffer of that stage's parity; past the last stage this stores a
     // copy of the last tile into a buffer nobody reads any more (unconditional on purpose: conditional loads become
     // phis that hipcc waits for in front of the MFMA block)
@@ -1055,20 +993,9 @@ __global__ __launch_bounds__(512) void k_wgrad_bf16_pp(BWgP P) {
     //  the staging group.  The staging phase shrinks by a third in the stamps; the kernel gets 2-3 % SLOWER, one register
     //  spill included.)
     store_half_any(par ? sbuf1 : sbuf0);
-#ifdef FU_CONV_STAMPS
-    const unsigned long long s3 = __builtin_amdgcn_s_memtime();
-#endif
     load_half_any(min(pt0 + n + 2 + grp, pt1 - 1));
     mfma_prefetch(std::integral_constant<int, 1 - par>{});   // (past the last stage: reads of a valid buffer, never used)
-#ifdef FU_CONV_STAMPS
-    const unsigned long long s4 = __builtin_amdgcn_s_memtime();
-#endif
     wg_barrier();
-#ifdef FU_CONV_STAMPS
-    const unsigned long long s5 = __builtin_amdgcn_s_memtime();
-    if (n > 0) { tM += s1 - s0; tB1 += s2 - s1; tSt += s3 - s2; tLd += s4 - s3; tB2 += s5 - s4; tGap += s0 - sPrev; }
-    sPrev = s5;
-#endif
   };
   for (int n = 0; n < T; n += 2) {
     body(std::integral_constant<int, 0>{}, n);
@@ -1076,12 +1003,6 @@ __global__ __launch_bounds__(512) void k_wgrad_bf16_pp(BWgP P) {
     body(std::integral_constant<int, 1>{}, n + 1);
   }
   if (!grp) wg_barrier();                        // group 1's pre-loop barrier
-#ifdef FU_CONV_STAMPS
-  if (P.dbg && lane == 0 && blockIdx.x < 256) {
-    unsigned long long* d = P.dbg + ((size_t)blockIdx.x * 8 + wave) * 8;
-    d[0] = tM; d[1] = tB1; d[2] = tSt; d[3] = (unsigned long long)max(T - 1, 0); d[4] = tLd; d[5] = tB2; d[6] = tGap; d[7] = 0;
-  }
-#endif
 
   const int co = co0 + ni * 32 + l31;             // slab[split][tap][Cin / 4][Cout][4], as in k_wgrad_bf16
   if (co < P.Cout) {
@@ -1371,11 +1292,8 @@ static int launch_wgrad_cfg(BWgP& P, int target_wgs, const LaunchOpts& o, hipStr
   return 0;
 }
 
-#ifndef FU_WGRAD_LOCKSTEP_DEFAULT
-#define FU_WGRAD_LOCKSTEP_DEFAULT 0   // A/B builds: -DFU_WGRAD_LOCKSTEP_DEFAULT=1
-#endif
 #if !FU_HALF
-int g_wgrad_force_lockstep = FU_WGRAD_LOCKSTEP_DEFAULT;   // testing hook (fu_test_force_lockstep_wgrad): 1 = k_wgrad_bf16<4,8> instead of the ping-pong kernel, 2 = the ping-pong kernel with its general staging
+int g_wgrad_force_lockstep = 0;   // testing hook (fu_test_force_lockstep_wgrad): 1 = k_wgrad_bf16<4,8> instead of the ping-pong kernel, 2 = the ping-pong kernel with its general staging
 #endif
 
 static int launch_wgrad_pp(BWgP& P, int target_wgs, const LaunchOpts& o, hipStream_t s) {
@@ -1413,14 +1331,6 @@ static int launch_wgrad_pp(BWgP& P, int target_wgs, const LaunchOpts& o, hipStre
   return 0;
 }
 
-#ifdef FU_EXPERIMENTS
-static int wgrad_mode_env() {
-  static int m = -1;
-  if (m < 0) { const char* e = getenv("FU_WGRAD_MODE"); m = e ? atoi(e) : 0; }
-  return m;
-}
-#endif
-
 // Workgroups of the ping-pong kernel.  Its 8-wave workgroups (248 registers, 125 KB of LDS) take a CU each and live for the
 // whole launch (45-290 us).  At 256 of them -- one per CU, round 2 -- every kernel of the main backward chain that starts while
 // a weight-gradient launch is in flight (BatchNorm-backward finalize / apply, bilinear backward, the next dgrad) waits for
@@ -1431,33 +1341,17 @@ static int wgrad_mode_env() {
 // 856, 208: 5.61 / 5.64 | 830 / 827, 192: 5.58 / 5.61 | 790 / 790, 176: 5.59 / 5.61 | 793 / 789, 160: 5.56 / 5.57 | 780 / 790,
 // 128: 5.67 (another box, against 5.78 at 256).  Below 208 the step gains another 0.5 % while the dgrad launches -- which then
 // share the GPU with the longer-running weight-gradient launch of the layer before -- lose 5 %: 208 takes most of the one
-// without the other.  (FU_WGRAD_TARGET overrides it in -DFU_EXPERIMENTS builds.)
+// without the other.
 // Round 4: 160.  The persistent conv kernel (fu_conv_pp.hip) takes a whole CU per workgroup like this one, so a dgrad launch that
 // starts beside a weight-gradient launch runs on the CUs this kernel leaves and the rest of its grid waits; measured again with
 // that dispatch, two boxes, ms per step | conv class TFLOP/s event-timed in the step: 256: 5.60 | 913, 208: 5.40-5.47 | 890-922,
 // 192: 5.34-5.39 | 853-866, 176: 5.33-5.40 | 848-867, 160: 5.28-5.35 | 834-843, 144: 5.38 | 825, 128: 5.57 | 825 -- the step is the
 // product's metric (-1.8 % at 160); the conv launches' event-timed rate falls with it by construction (they share more of their
 // own duration), their rate with the GPU to themselves (roofline.achieved_serial) does not change.  Capping the dgrad launches'
-// grid to the complement instead (FU_PP_GRID: 128 + 128, 112 + 144, 96 + 160) is no better (5.35-5.40) and slower alone.
-static int wgrad_pp_target() {
-#ifdef FU_EXPERIMENTS
-  static int t = -1;
-  if (t < 0) { const char* e = getenv("FU_WGRAD_TARGET"); t = e ? atoi(e) : 160; }
-  return t;
-#else
-  return 160;
-#endif
-}
-
-static int wgrad_c64_target() {
-#ifdef FU_EXPERIMENTS
-  static int t = -1;
-  if (t < 0) { const char* e = getenv("FU_WGRAD_TARGET64"); t = e ? atoi(e) : 512; }
-  return t;
-#else
-  return 512;
-#endif
-}
+// grid to the complement instead (128 + 128, 112 + 144, 96 + 160) is no better (5.35-5.40) and slower alone.
+static constexpr int WGRAD_PP_TARGET = 160;
+// ... of the narrow launches: the 8-band first conv and k_wgrad_bf16<2,8> (256 threads, two workgroups per CU)
+static constexpr int WGRAD_C64_TARGET = 512;
 
 // upper bound of the slab size over the two configurations below
 int64_t conv3x3_wgrad_slab_elems_bf16(int Cin, int Cout, int B, int H, int W) {
@@ -1478,21 +1372,16 @@ int launch_conv3x3_wgrad_bf16(const ConvIn& in, const bf16_t* dy, int Cout, floa
   P.src0 = (const bf16_t*)in.src0; P.src1 = (const bf16_t*)in.src1; P.a0 = in.a0; P.b0 = in.b0; P.dy = dy;
   P.slab = slab;
   P.C0 = in.C0; P.C1 = in.src1 ? in.C1 : 0; P.Cin = P.C0 + P.C1; P.Cout = Cout; P.B = B; P.H = H; P.W = W;
-  P.dbg = g_conv_dbg;
   FU_REQUIRE(P.C0 % 8 == 0 && P.C1 % 8 == 0 && Cout % 8 == 0, "wgrad_bf16: channel counts must be multiples of 8");
   int st;
   // embedded 1x1 (late-fusion convs): the stage is all staging, so the lock-step kernel (all 8 waves stage together) wins
   // over the ping-pong one; the eight unwritten tap slabs reach only taps of dw_oihw that the caller never reads
   if (in.center_only && !g_bf16_force_full_taps && P.Cin > 64) st = launch_wgrad_cfg<4, 8, 1>(P, 256, in.opt, s);
   else if (in.center_only && !g_bf16_force_full_taps) st = launch_wgrad_cfg<2, 8, 1>(P, 512, in.opt, s);
-#ifdef FU_EXPERIMENTS   // A/B knob (tools/ab_*.sh): FU_WGRAD_MODE=1 the 256-thread 64 x 64 kernel everywhere (512 WGs), 2 = the same at 256 WGs
-  else if (wgrad_mode_env() == 1) st = launch_wgrad_cfg<2, 8>(P, 512, in.opt, s);
-  else if (wgrad_mode_env() == 2) st = launch_wgrad_cfg<2, 8>(P, 256, in.opt, s);
-#endif
-  else if (!g_wgrad_force_lockstep && wgrad_c8_eligible(P)) st = launch_wgrad_c8(P, wgrad_c64_target(), in.opt, s);   // the 8-band first conv: K = 72 stream over dy
-  else if (P.Cin > 64 && g_wgrad_force_lockstep != 1) st = launch_wgrad_pp(P, wgrad_pp_target(), in.opt, s);   // 512 threads, 128 c_in x 64 c_out, one WG per CU
-  else if (P.Cin > 64) st = launch_wgrad_cfg<4, 8>(P, wgrad_pp_target(), in.opt, s);   // (same split as the ping-pong kernel: bit-identical sums)
-  else st = launch_wgrad_cfg<2, 8>(P, wgrad_c64_target(), in.opt, s);   // 256 threads, 64 x 64, two WGs per CU
+  else if (!g_wgrad_force_lockstep && wgrad_c8_eligible(P)) st = launch_wgrad_c8(P, WGRAD_C64_TARGET, in.opt, s);   // the 8-band first conv: K = 72 stream over dy
+  else if (P.Cin > 64 && g_wgrad_force_lockstep != 1) st = launch_wgrad_pp(P, WGRAD_PP_TARGET, in.opt, s);   // 512 threads, 128 c_in x 64 c_out, one WG per CU
+  else if (P.Cin > 64) st = launch_wgrad_cfg<4, 8>(P, WGRAD_PP_TARGET, in.opt, s);   // (same split as the ping-pong kernel: bit-identical sums)
+  else st = launch_wgrad_cfg<2, 8>(P, WGRAD_C64_TARGET, in.opt, s);   // 256 threads, 64 x 64, two WGs per CU
   if (st) return st;
   return launch_wgrad_reduce(slab, P.S, P.Cin, Cout, cin_real, dw_oihw, db_partials, n_db_partials, db, s, true);
 }
@@ -1503,5 +1392,4 @@ int launch_conv3x3_wgrad_bf16(const ConvIn& in, const bf16_t* dy, int Cout, floa
 extern "C" void fu_test_force_general_conv(int on) { fu::g_bf16_force_general = on; }
 extern "C" void fu_test_force_lockstep_wgrad(int on) { fu::g_wgrad_force_lockstep = on; }
 extern "C" void fu_test_force_full_taps(int on) { fu::g_bf16_force_full_taps = on; }
-extern "C" void fu_debug_set_conv_stamps(void* p) { fu::g_conv_dbg = (unsigned long long*)p; }
 #endif

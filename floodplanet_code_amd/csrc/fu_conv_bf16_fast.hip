@@ -3,10 +3,10 @@
 // Same implicit GEMM, LDS image and MFMA schedule as k_conv3x3_bf16 (fu_conv_bf16.hip), rewritten around one
 // measurement: on the 64..128-channel layers the general kernel issues ~900 VALU/SALU instructions per 32-channel
 // chunk and ~1100 in its epilogue against 72 MFMAs per chunk (2300 MFMA cycles), i.e. the waves are VALU-issue bound
-// (s_memtime stamps, tools/stamp_test.py: prologue 6100 + epilogue 6200 cycles around a 10200-cycle main loop).  This
+// (s_memtime stamps: prologue 6100 + epilogue 6200 cycles around a 10200-cycle main loop).  This
 // kernel keeps every per-load / per-store quantity in a register that is computed once per tile:
 //   * global loads   : uniform (SGPR) chunk base + one 32-bit byte offset per staging slot, no per-chunk address math;
-//   * BN+ReLU        : v_pk_fma_f32 on channel pairs, v_cvt_pk_bf16_f32, ReLU as v_pk_max_i16 on the packed pair;
+//   * BN+ReLU        : v_fma_f32 / v_max_f32 per channel, v_cvt_pk_bf16_f32 per pair (bn_relu_pair, fu_conv_bf16.h);
 //   * zero padding   : only border tiles / ragged chunks take the masked variant (workgroup-uniform branch);
 //   * epilogue       : packed statistics (v_pk_add/fma_f32), convert first and transpose the 4x4 lane quad on PACKED
 //                      pairs (2 DPP + 2 v_perm + 1 DPP + 3 selects per 4 registers), stores from a uniform base + a
@@ -14,25 +14,11 @@
 // Shapes it takes (conv3x3_bf16_fast_eligible): a second source only if C0 % 32 == 0, a second destination only if
 // D0 % BN == 0, every tensor < 2 GiB.  Everything else (and only that) runs on the general kernel.
 #include "fu_conv_bf16.h"
-#include <stdlib.h>
 
-#ifndef FU_FAST_LOADS_PER_STEP
-#define FU_FAST_LOADS_PER_STEP 2   // the next chunk's 15 global loads go out 2 per k-step behind that step's MFMAs: as one
-#endif                             // burst in front of the block they hold the wave ~1900 cycles before its first MFMA
-                                   // (texture path: 60 KB per workgroup at 64 B/clk); measured 787 -> 817 TF (0 = burst).
-#ifndef FU_FAST_FRAG_DIST           // Raising the MFMA waves' priority (s_setprio) was measured too: no gain.
-#define FU_FAST_FRAG_DIST 1        // k-steps of fragment prefetch (1: two register buffers, 2: three)
-#endif
-#ifndef FU_FAST_STORE16
-#define FU_FAST_STORE16 1   // interior tiles: 16-byte epilogue stores (0: the 8-byte form); measured 825 -> 858 TF
-#endif
-#ifndef FU_FAST_ROWPERM
-#define FU_FAST_ROWPERM 1
-#endif
-#ifndef FU_FAST_DBG
-#define FU_FAST_DBG 0   // diagnostic builds (make EXTRA=-DFU_FAST_DBG=4): 4 = epilogue without its global stores
-#endif                  // (64->64 @256^2: 114.8 -> 92.2 us).  -DFU_CONV_STAMPS: s_memtime stamps for
-                        // tools/stamp_test.py.  Neither is ever defined in the shipped build.
+// The next chunk's 15 global loads go out 2 per k-step behind that step's MFMAs: as one burst in front of the block they
+// hold the wave ~1900 cycles before its first MFMA (texture path: 60 KB per workgroup at 64 B/clk); measured 787 -> 817 TF.
+// Raising the MFMA waves' priority (s_setprio) was measured too: no gain.
+static constexpr int FAST_LOADS_PER_STEP = 2;
 
 namespace fu {
 
@@ -101,7 +87,6 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
   // 80-byte rows, consecutive rows (20 dwords apart) put unit 3 of one row on the banks of unit 0 of the next (2-way
   // conflict on every write: ~20 % of the LDS-active cycles, profiles/r1_pmc_bf16.json).  Rows 4 apart (80 dwords = 16 mod
   // 32) do not collide, so the two rows of a group are r and r + 4: bits 0 and 2 of the row index are swapped.
-#if FU_FAST_ROWPERM
   const int srow_lin = tid / UPR;
   // 80-byte rows, 4 units per row: the two rows of an 8-lane write group must be 4 apart (bits 0 and 2 swapped).
   // 48-byte rows, 2 units per row (KC = 16): the four rows of a group must be 2 apart -- rows r, r+2, r+4, r+6 put
@@ -109,9 +94,6 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
   // three bits are rotated.
   const int srow = UPR == 4 ? ((srow_lin & ~7) | ((srow_lin & 1) << 2) | ((srow_lin >> 1) & 3))
                             : ((srow_lin & ~7) | ((srow_lin & 3) << 1) | ((srow_lin >> 2) & 1));
-#else
-  const int srow = tid / UPR;
-#endif
   unsigned a_off[A_ITERS];
   unsigned a_ok = 0;
   auto setup_a = [&](int Cs) {
@@ -225,9 +207,6 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
   for (int nt = 0; nt < NTW; ++nt) boff[nt] = (nt * 32 + l31) * KCP + 8 * lh;
 
   const int nChunks = (P.Cin + KC - 1) / KC;
-#ifdef FU_CONV_STAMPS
-  unsigned long long T0 = __builtin_amdgcn_s_memtime(), T1 = 0, T2 = 0;
-#endif
   load_chunk(0);                         // the first chunk's loads go out before anything else
   float biasv[NTW];                      // bias is fetched here: a load in the epilogue would expose a full memory
 #pragma unroll                           // latency (and its vmcnt(0) would also wait for the stores before it)
@@ -238,16 +217,13 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
   if (has_bn) {                          // BN coefficients of source 0 -> LDS (behind the loads above)
     for (int c = tid; c < P.C0; c += NT) { sAB[c] = P.a0[c]; sAB[1024 + c] = P.b0[c]; }
   }
-#ifdef FU_CONV_STAMPS
-  unsigned long long Sbar = 0, Swait = 0, Sstore = 0, Smfma = 0;   // (per-phase sums: only in older diagnostic builds)
-#endif
   // 18 k-steps (9 taps x 2 halves of the 32-channel chunk), software-pipelined by hand: the fragments of step
   // s+1 are requested from LDS before the MFMAs of step s are issued.
   auto mfma_block = [&](auto Lc) {
     constexpr int LOADS = decltype(Lc)::value;   // 0: none; n: next chunk's loads, n per k-step behind its MFMAs
     // (tall tile: 128 accumulator registers; a second fragment buffer would not fit in 256 registers -- its 8 MFMAs per
     //  k-step and the co-resident wave cover the LDS latency instead of a one-step prefetch)
-    constexpr int FD = MT == 4 ? 0 : FU_FAST_FRAG_DIST, NB = FD + 1;
+    constexpr int FD = MT == 4 ? 0 : 1, NB = FD + 1;    // k-steps of fragment prefetch
     frag8_t af[NB][MT], bfr[NB][NTW];
     auto load_frags = [&](auto Sc, auto Bc) {
       constexpr int st = decltype(Sc)::value, buf = decltype(Bc)::value;
@@ -255,7 +231,7 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
       constexpr int gtap = tap + Cfg::TAP0;                           // its position in the 3x3 window
       constexpr int toff = ((gtap / 3) * HWd + (gtap % 3)) * KCP + ks * 16;
       if constexpr (MT == 4) {   // no prefetch buffer: the weight fragments first, so that the first MFMAs of the step
-#pragma unroll                   // wait for 3 of the 6 reads only (FU_TALL_B_FIRST)
+#pragma unroll                   // wait for 3 of the 6 reads only
         for (int nt = 0; nt < NTW; ++nt)
           bfr[buf][nt] = *reinterpret_cast<const frag8_t*>(sW + tap * BN * KCP + boff[nt] + ks * 16);
       }
@@ -299,30 +275,16 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
   for (int ch = 0; ch + 1 < nChunks; ++ch) {
     const int k0 = ch * KC;
     stage(k0);
-#ifdef FU_CONV_STAMPS
-    if (ch == 0) T1 = __builtin_amdgcn_s_memtime();
-#endif
     if (P.src1 != nullptr && k0 + KC == P.C0) setup_a(P.C1);   // next chunk starts the second source
-#if FU_FAST_LOADS_PER_STEP > 0
     load_begin(k0 + KC);
     // all A_ITERS + W_ITERS loads must fit in the block's k-steps: 2 per step over 18 steps, 4 over the 2 of a 1x1
-    constexpr int LPS = Cfg::NSTEPS * FU_FAST_LOADS_PER_STEP >= A_ITERS + W_ITERS
-                            ? FU_FAST_LOADS_PER_STEP : (A_ITERS + W_ITERS + Cfg::NSTEPS - 1) / Cfg::NSTEPS;
+    constexpr int LPS = Cfg::NSTEPS * FAST_LOADS_PER_STEP >= A_ITERS + W_ITERS
+                            ? FAST_LOADS_PER_STEP : (A_ITERS + W_ITERS + Cfg::NSTEPS - 1) / Cfg::NSTEPS;
     static_assert(LPS * Cfg::NSTEPS >= A_ITERS + W_ITERS, "next chunk's loads do not fit behind the k-steps");
     mfma_block(std::integral_constant<int, LPS>{});
-#else
-    load_chunk(k0 + KC);                                      // raw loads stay in flight under the MFMA block
-    mfma_block(std::integral_constant<int, 0>{});
-#endif
   }
   stage((nChunks - 1) * KC);
-#ifdef FU_CONV_STAMPS
-  if (nChunks == 1) T1 = __builtin_amdgcn_s_memtime();
-#endif
   mfma_block(std::integral_constant<int, 0>{});
-#ifdef FU_CONV_STAMPS
-  T2 = __builtin_amdgcn_s_memtime();
-#endif
 
   // ---- epilogue ----------------------------------------------------------------------------------
   // Accumulator layout: lane = channel (l31), registers = 16 pixels.  Values are converted to bf16 pairs first
@@ -337,8 +299,9 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
   const int dstride = to0 ? P.D0 : P.D1;
   float ssum[NTW], ssq[NTW];
 
-  auto epilogue = [&](auto Fc, auto Bc) {
-    constexpr bool FULL = decltype(Fc)::value, BIAS = decltype(Bc)::value;
+  // Border tiles: 8-byte stores, masked per pixel and channel quad.
+  auto epilogue = [&](auto Bc) {
+    constexpr bool BIAS = decltype(Bc)::value;
     unsigned sb[MT][4];    // byte offset of the store of (mt, g) from dbase
     unsigned sok = 0;
 #pragma unroll
@@ -349,7 +312,7 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
         const int oy = y0 + (wm * MT + mt) * 2 + (g >> 1);
         const int ox = x0 + ((g >> 1) ? ((p - 16 - (HWd & 15)) & 15) : p);
         sb[mt][g] = ((unsigned)((bb * P.H + oy) * P.W + ox) * (unsigned)dstride + (unsigned)(l31 & ~3)) * 2u;
-        if constexpr (!FULL) sok |= (oy < P.H && ox < P.W) ? (1u << (mt * 4 + g)) : 0u;
+        sok |= (oy < P.H && ox < P.W) ? (1u << (mt * 4 + g)) : 0u;
       }
 #pragma unroll
     for (int nt = 0; nt < NTW; ++nt) {
@@ -364,18 +327,13 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
         for (int g = 0; g < 4; ++g) {
           f32x2 a01 = {acc[mt][nt][4 * g + 0], acc[mt][nt][4 * g + 1]};
           f32x2 a23 = {acc[mt][nt][4 * g + 2], acc[mt][nt][4 * g + 3]};
-          if constexpr (FULL) {
-            s2 += a01; s2 += a23;
-            q2 = a01 * a01 + q2; q2 = a23 * a23 + q2;
-          } else {
-            const int oy = y0 + (wm * MT + mt) * 2 + (g >> 1);
+          const int oy = y0 + (wm * MT + mt) * 2 + (g >> 1);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const int p = k + 8 * g + 4 * lh;                   // MFMA row -> pixel (second row rotated, see aoff)
-              const int ox = x0 + ((g >> 1) ? ((p - 16 - (HWd & 15)) & 15) : p);
-              const float a = acc[mt][nt][4 * g + k];
-              if (nok && oy < P.H && ox < P.W) { s2.x += a; q2.x = fmaf(a, a, q2.x); }
-            }
+          for (int k = 0; k < 4; ++k) {
+            const int p = k + 8 * g + 4 * lh;                   // MFMA row -> pixel (second row rotated, see aoff)
+            const int ox = x0 + ((g >> 1) ? ((p - 16 - (HWd & 15)) & 15) : p);
+            const float a = acc[mt][nt][4 * g + k];
+            if (nok && oy < P.H && ox < P.W) { s2.x += a; q2.x = fmaf(a, a, q2.x); }
           }
           if constexpr (BIAS) { a01 += bias2; a23 += bias2; }
           const unsigned p01 = pack_e2(a01), p23 = pack_e2(a23);
@@ -388,23 +346,18 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
           uint2 o;
           o.x = q_lo ? A : recv;
           o.y = q_lo ? recv : Bq;
-#if FU_FAST_DBG == 4
-          asm volatile("" ::"v"(o.x), "v"(o.y));
-#else
-          if (FULL || (nqok && ((sok >> (mt * 4 + g)) & 1u)))
+          if (nqok && ((sok >> (mt * 4 + g)) & 1u))
             *reinterpret_cast<uint2*>(dbase + sb[mt][g] + nt * 64) = o;
-#endif
         }
       }
       ssum[nt] = s2.x + s2.y;
       ssq[nt] = q2.x + q2.y;
     }
   };
-#if FU_FAST_STORE16
   // Interior tiles: 16-byte stores.  Three exchange levels inside every group of 8 lanes (xor 1 and xor 2 inside the
   // quads as above, then quad <-> quad through row_shl:4 / row_shr:4 with bank masks) turn 8 accumulator registers
   // (8 pixels x 1 channel per lane) into 8 channels of ONE pixel per lane: half the store instructions of the 8-byte
-  // form (the epilogue is store-issue bound on the shallow layers).
+  // form (the epilogue is store-issue bound on the shallow layers; measured 825 -> 858 TF against the 8-byte form).
   auto epilogue16 = [&](auto Bc) {
     constexpr bool BIAS = decltype(Bc)::value;
     const int li = lane & 7;
@@ -465,24 +418,15 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
       ssq[nt] = q2.x + q2.y;
     }
   };
-#endif
   const bool full = (y0 + TH <= P.H) && (x0 + TW <= P.W) && (n0 + BN <= P.N);   // workgroup-uniform
   if (full) {
-#if FU_FAST_STORE16
     if (P.bias) epilogue16(std::true_type{});
     else epilogue16(std::false_type{});
-#else
-    if (P.bias) epilogue(std::true_type{}, std::true_type{});
-    else epilogue(std::true_type{}, std::false_type{});
-#endif
   } else {
-    if (P.bias) epilogue(std::false_type{}, std::true_type{});
-    else epilogue(std::false_type{}, std::false_type{});
+    if (P.bias) epilogue(std::true_type{});
+    else epilogue(std::false_type{});
   }
 
-#ifdef FU_CONV_STAMPS
-  const unsigned long long T2b = __builtin_amdgcn_s_memtime();
-#endif
   if (P.stats) {
     float* red = reinterpret_cast<float*>(smem_raw);  // [4][BN][2]
 #pragma unroll
@@ -509,24 +453,12 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
       o[1] = q;
     }
   }
-#ifdef FU_CONV_STAMPS
-  const unsigned long long T2c = __builtin_amdgcn_s_memtime();
-  if (P.dbg && tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long T3 = __builtin_amdgcn_s_memtime();
-    unsigned long long* d = P.dbg + (size_t)blockIdx.x * 10;
-    d[0] = T0; d[1] = T1; d[2] = T2; d[3] = T3; d[4] = Sbar; d[5] = Swait; d[6] = Sstore; d[7] = Smfma; d[8] = T2b; d[9] = T2c;
-  }
-#endif
 }
 
-#ifndef FU_TILE_MODE_DEFAULT
-#define FU_TILE_MODE_DEFAULT 0
-#endif
 #if FU_HALF
 extern int g_bf16_tile_mode;
 #else
-int g_bf16_tile_mode = FU_TILE_MODE_DEFAULT;   // 0 = heuristic, 1 = never the tall tile, 2 = tall wherever 64-channel tiles run
+int g_bf16_tile_mode = 0;   // 0 = heuristic, 1 = never the tall tile, 2 = tall wherever 64-channel tiles run
 #endif
 
 bool conv3x3_bf16_fast_eligible(const BConvP& P) {
@@ -575,13 +507,11 @@ int launch_conv3x3_bf16_fast(BConvP& P, const LaunchOpts& o, hipStream_t s) {
   // workgroups.  Measured per layer against the kernels below (bench shapes, forward, tools/conv_modes.py): 5-11 % faster
   // on the 128x128, 64x64 and 32x32 layers with N >= 512 channels x tiles, equal on the two-chunk 256x256 layers, slower
   // below 512 workgroups (16x16 level, 512 -> 256 at 32x32).  Tile mode 3 forces it, modes 1 / 2 exclude it.
-  // persistent ping-pong kernel (fu_conv_pp.hip): tile mode 4 forces it; by default wherever it is eligible (FU_CONV_PP=0: never,
-  // for A/B runs -- bench.py records every FU_* variable of its environment in the line it prints)
+  // persistent ping-pong kernel (fu_conv_pp.hip): tile mode 4 forces it; by default wherever it is preferred
   if (conv3x3_pp_eligible(P)) {
-    static const int pp_default = [] { const char* e = getenv("FU_CONV_PP"); return e ? atoi(e) : 1; }();
     const bool wants_bnb = o.bnb != nullptr && o.bnb->y != nullptr && P.a0 == nullptr && P.dst1 == nullptr && P.stats == nullptr;
     if (g_bf16_tile_mode == 4 ||
-        (g_bf16_tile_mode == 0 && pp_default && (wants_bnb ? conv3x3_pp_preferred_bnb(P) : conv3x3_pp_preferred(P))))
+        (g_bf16_tile_mode == 0 && (wants_bnb ? conv3x3_pp_preferred_bnb(P) : conv3x3_pp_preferred(P))))
       return launch_conv3x3_pp(P, o, s);
   }
   if (conv3x3_rs_eligible(P)) {

@@ -530,7 +530,6 @@ static int launch_wgrad_reduce_sl(const float* slab, int S, int Cin, int Cout, i
 int launch_wgrad_reduce(const float* slab, int S, int Cin, int Cout, int cin_real, float* dw, const float* dbp,
                         int ndb, float* db, hipStream_t s, bool ci4) {
   FU_REQUIRE(!ci4 || Cin % 4 == 0, "wgrad_reduce: the interleaved slab layout needs c_in %% 4 == 0");
-  if (FU_EXP_SKIP(4)) return 0;
   int st;
   if (S >= 64) st = launch_wgrad_reduce_sl<16>(slab, S, Cin, Cout, cin_real, dw, dbp, ndb, db, s);
   else if (S >= 16) st = launch_wgrad_reduce_sl<4>(slab, S, Cin, Cout, cin_real, dw, dbp, ndb, db, s);

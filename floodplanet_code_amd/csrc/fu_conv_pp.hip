@@ -26,7 +26,6 @@
 // k_conv3x3_bf16_rs<8>: outputs, BatchNorm statistics and fused BatchNorm-backward sums are bit-identical to it (tested).
 // Shapes (conv3x3_pp_eligible): the row-stationary kernel's, with H % 32 == 0.
 #include "fu_conv_bf16.h"
-#include <stdlib.h>
 
 namespace fu {
 
@@ -326,12 +325,6 @@ __global__ __launch_bounds__(512) void k_conv3x3_bf16_pp(BConvP P) {
     static_for<0, NOPS>([&](auto Kc) { convert_op(Stg, Set, Kc); });
     advance_convert();
   };
-#ifdef FU_CONV_STAMPS     // diagnostic builds only (tools/stamp_pp.py): s_memtime sums per phase and wave
-  unsigned long long tM = 0, tB1 = 0, tS = 0, tE = 0, tB2 = 0, tSd = 0, tSw = 0, tSc = 0, tSv = 0, tSl = 0;
-#define FU_STAMP(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#else
-#define FU_STAMP(v)
-#endif
 
   // ---- MFMA phase
   f32x4 acc[8][2];
@@ -352,10 +345,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_bf16_pp(BConvP P) {
     }
   }
   frag8_t wf[2][3][2];                     // [block parity][kernel row][subtile q]
-#ifndef FU_PP_PD
-#define FU_PP_PD 3
-#endif
-  constexpr int PD = FU_PP_PD, NR = PD + 2;   // (PD + 2 slots: the slot a read overwrites was last multiplied a whole step ago --
+  constexpr int PD = 3, NR = PD + 2;   // (PD + 2 slots: the slot a read overwrites was last multiplied a whole step ago --
                                               //  with PD + 1 hipcc pads every such read with s_nop wait states behind the MFMA)
   static_assert(PD <= 4, "the rows requested ahead of the barrier (halo rows 8 rg + [0, PD)) must be group 1's: bit 2 clear");
   frag8_t pf[NR];                          // ring of input-row fragments, PD steps ahead of the MFMAs
@@ -407,18 +397,14 @@ __global__ __launch_bounds__(512) void k_conv3x3_bf16_pp(BConvP P) {
         constexpr int dy = (ri < 8 ? 0 : ri - 7) + k / 2, q = k % 2, ro = ri - dy;
         static_assert(ro >= 0 && ro < 8, "kernel row of the k-th MFMA of a step");
         asm volatile(FU_MFMA16_ASM " %0, %1, %2, %0" : "+v"(acc[ro][q]) : "v"(wf[dx & 1][dy][q]), "v"(pf[t % NR]));
-#ifndef FU_PP_EXP_NOREAD     // (timing experiments of diagnostic builds: wrong results)
         if constexpr (k == 0 && t + PD < Cfg::M_STEPS) ld_p(Par, std::integral_constant<int, (t + PD < Cfg::M_STEPS ? t + PD : 0)>{});
         if constexpr (k == (nm > 2 ? 1 : 0) && dx < 2 && ri < 6)     // the next column shift's six weight fragments, one per step
           ld_w(Par, std::integral_constant<int, dx + 1>{}, std::integral_constant<int, (ri < 6 ? ri / 2 : 0)>{}, std::integral_constant<int, ri % 2>{});
-#endif
-#ifndef FU_PP_EXP_NOCONV
         constexpr int g = 48 * dx + pp_step_first_gap(ri) + k;       // gap index in the phase
         constexpr int o0 = pp_ops_before(g), o1 = o0 + pp_gap_free(g);
         static_for<o0, (o1 < NOPS ? o1 : NOPS)>([&](auto Oc) {
           convert_op(std::integral_constant<int, 1 - par>{}, std::integral_constant<int, 1 - par>{}, Oc);
         });
-#endif
         __builtin_amdgcn_sched_barrier(0);
       });
     });
@@ -458,7 +444,6 @@ __global__ __launch_bounds__(512) void k_conv3x3_bf16_pp(BConvP P) {
     for (int ro = 0; ro < 8; ++ro) yr[ro] = *reinterpret_cast<const uint4*>(ybase + (size_t)ro * (size_t)(P.W * P.N) * 2);
   };
   auto epilogue = [&]() __attribute__((always_inline)) {
-    FU_STAMP(e0);
     if constexpr (BNB) bnb_request();
     int pixT, n0, x0, y0, bb;
     decode(mv, pixT, n0, x0, y0, bb);
@@ -506,7 +491,6 @@ __global__ __launch_bounds__(512) void k_conv3x3_bf16_pp(BConvP P) {
       *reinterpret_cast<uint4*>(dp) = make_uint4(o[0], o[1], o[2], o[3]);
       dp += rowb;
     }
-    FU_STAMP(e1);
     float st[16];                                                    // [0, 8): sums, [8, 16): sums of squares
 #pragma unroll
     for (int c = 0; c < 4; ++c) { st[2 * c] = s2[c].x; st[2 * c + 1] = s2[c].y; st[8 + 2 * c] = q2[c].x; st[8 + 2 * c + 1] = q2[c].y; }
@@ -549,9 +533,6 @@ __global__ __launch_bounds__(512) void k_conv3x3_bf16_pp(BConvP P) {
         }
       });
     }
-#ifdef FU_CONV_STAMPS
-    { const unsigned long long e2 = __builtin_amdgcn_s_memtime(); tSd += e1 - e0; tSl += e2 - e1; }
-#endif
     pend = true; pend_pixT = pixT; pend_n0 = n0; pend_par = tpar;
     tpar ^= 1;
     mv += grid;
@@ -577,12 +558,6 @@ __global__ __launch_bounds__(512) void k_conv3x3_bf16_pp(BConvP P) {
     pend = false;
   };
 
-#ifdef FU_CONV_STAMPS
-  const unsigned long long tStart = __builtin_amdgcn_s_memtime();
-  unsigned long long tPro = 0;
-  const unsigned long long rStart = __builtin_amdgcn_s_memrealtime();
-  unsigned long long tLoop = 0;
-#endif
 
   // s_waitcnt vmcnt(5) through the builtin (gfx9 encoding: vmcnt[3:0] | expcnt 7 << 4 | lgkmcnt 15 << 8 | vmcnt[5:4] << 14):
   // hipcc's waitcnt pass sees it and knows the LDS-DMA pieces have landed -- behind an asm wait it still holds them pending
@@ -631,22 +606,10 @@ __global__ __launch_bounds__(512) void k_conv3x3_bf16_pp(BConvP P) {
   // group's MFMA phase at ~10 cycles each and stretched TWO phases per tile from ~2700 to 5000-7500 cycles (group 0's epilogue
   // beside group 1's last MFMA phase, group 1's beside group 0's first of the next tile); with both groups' epilogues in one
   // phase without MFMAs they issue at the VALU's own rate and the matrix pipe idles once per tile instead of waiting twice.
-#ifndef FU_PP_JOINT_EPILOGUE
-#define FU_PP_JOINT_EPILOGUE 1      // (0: the epilogue inside the data-movement phase, A/B builds)
-#endif
   auto body = [&](auto Par) __attribute__((always_inline)) {
     constexpr int par = decltype(Par)::value;
-    FU_STAMP(s0);
-#ifdef FU_PP_MPRIO
-    __builtin_amdgcn_s_setprio(FU_PP_MPRIO);
-#endif
     mfma_phase(Par);
-#ifdef FU_PP_MPRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-    FU_STAMP(s1);
     wg_barrier();
-    FU_STAMP(s2);
     const bool tile_end = mk + 1 == nChunks && mstep < T;            // uniform (an odd step count ends with a dummy step)
     ++mstep;
     auto move_data = [&]() __attribute__((always_inline)) {
@@ -657,84 +620,31 @@ __global__ __launch_bounds__(512) void k_conv3x3_bf16_pp(BConvP P) {
       vm_wait5();                                                    // the DMA pieces have landed (the five loads stay in flight)
       if (wave == 0 && pend) combine();
     };
-#if FU_PP_JOINT_EPILOGUE
     if (tile_end && grp) {                                           // (uniform per wave)
       epilogue(); mk = 0;
-      FU_STAMP(s3);
       wg_barrier();
-      FU_STAMP(s3a);
       move_data();
-      FU_STAMP(s3b);
       mfma_prefetch(std::integral_constant<int, 1 - par>{});
-      FU_STAMP(s4);
       wg_barrier();
-#ifdef FU_CONV_STAMPS
-      const unsigned long long s5 = __builtin_amdgcn_s_memtime();
-      tM += s1 - s0; tB1 += s2 - s1; tSw += s3 - s2; tS += s3b - s3a; tE += s4 - s3b; tB2 += s5 - s4; tSv += s3a - s3; tSc += 1;
-#endif
     } else if (tile_end) {
       move_data();
-      FU_STAMP(s3);
       wg_barrier();
-      FU_STAMP(s3a);
       epilogue(); mk = 0;
-      FU_STAMP(s3b);
       mfma_prefetch(std::integral_constant<int, 1 - par>{});
-      FU_STAMP(s4);
       wg_barrier();
-#ifdef FU_CONV_STAMPS
-      const unsigned long long s5 = __builtin_amdgcn_s_memtime();
-      tM += s1 - s0; tB1 += s2 - s1; tS += s3 - s2; tSw += s3b - s3a; tE += s4 - s3b; tB2 += s5 - s4; tSv += s3a - s3; tSc += 1;
-#endif
     } else {
       move_data();
       ++mk;
-      FU_STAMP(s3);
       mfma_prefetch(std::integral_constant<int, 1 - par>{});         // first fragments of the next MFMA phase (complete: header)
-      FU_STAMP(s4);
       wg_barrier();
-#ifdef FU_CONV_STAMPS
-      const unsigned long long s5 = __builtin_amdgcn_s_memtime();
-      tM += s1 - s0; tB1 += s2 - s1; tS += s3 - s2; tE += s4 - s3; tB2 += s5 - s4;
-#endif
     }
-#else
-    move_data();
-    FU_STAMP(s3);
-    if (tile_end) { epilogue(); mk = 0; } else { ++mk; }
-    FU_STAMP(s3b);
-    mfma_prefetch(std::integral_constant<int, 1 - par>{});           // first fragments of the next MFMA phase (complete: header)
-    FU_STAMP(s4);
-    wg_barrier();
-#ifdef FU_CONV_STAMPS
-    const unsigned long long s5 = __builtin_amdgcn_s_memtime();
-    tM += s1 - s0; tB1 += s2 - s1; tS += s3 - s2; tE += s4 - s3; tB2 += s5 - s4;
-    tSw += s3b - s3; tSc += tile_end ? 1 : 0;
-#endif
-#endif
   };
-#ifdef FU_CONV_STAMPS
-  const unsigned long long tL0 = __builtin_amdgcn_s_memtime();
-  tPro = tL0 - tStart;
-#endif
   for (int s = 0; s < T; s += 2) {
     body(std::integral_constant<int, 0>{});
     body(std::integral_constant<int, 1>{});
   }
-#ifdef FU_CONV_STAMPS
-  tLoop = __builtin_amdgcn_s_memtime() - tL0;
-#endif
   if (!grp) wg_barrier();                                            // group 1's pre-loop barrier
   if (wave == 0 && pend) combine();
-#ifdef FU_CONV_STAMPS
-  if (P.dbg && lane == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unsigned long long* d = P.dbg + ((size_t)blockIdx.x * 8 + wave) * 16;
-    d[0] = tM; d[1] = tB1; d[2] = tS; d[3] = tE; d[4] = tB2; d[5] = tLoop; d[6] = __builtin_amdgcn_s_memtime() - tStart;
-    d[7] = __builtin_amdgcn_s_memrealtime() - rStart; d[8] = (unsigned long long)T; d[9] = tStart;
-    d[10] = tSd; d[11] = tSw; d[12] = tSc; d[13] = tSv; d[14] = tSl; d[15] = tPro;
-  }
-#endif
 }
 
 bool conv3x3_pp_eligible(const BConvP& P) {
@@ -758,12 +668,9 @@ bool conv3x3_pp_preferred(const BConvP& P) {
 // two-workgroup kernel, whose second workgroup covers it); from 256 input channels on it disappears (512 -> 512 at 32 x 32: 63
 // against 74 us).  With the epilogue in a phase of its own (body) the picture is the same -- one-stream trace, pp | rs<8>: 64 -> 64
 // at 256 x 256 125 / 117 | 115 / 114 us, 128 -> 64 at 128 x 128 65 | 54, 256 -> 128 at 64 x 64 49 | 44, 128 -> 128 at 128 x 128 92 | 83
-// (-DFU_PP_BNB_MIN_CIN=64 builds).
-#ifndef FU_PP_BNB_MIN_CIN
-#define FU_PP_BNB_MIN_CIN 256
-#endif
+// (with the threshold at 64).
 bool conv3x3_pp_preferred_bnb(const BConvP& P) {
-  return conv3x3_pp_preferred(P) && P.Cin >= FU_PP_BNB_MIN_CIN;
+  return conv3x3_pp_preferred(P) && P.Cin >= 256;
 }
 
 int launch_conv3x3_pp(BConvP& P, const LaunchOpts& o, hipStream_t s) {
@@ -801,9 +708,6 @@ int launch_conv3x3_pp(BConvP& P, const LaunchOpts& o, hipStream_t s) {
   }
   // one workgroup per CU, a multiple of 8 (the XCD of a workgroup's virtual block ids must not change from tile to tile)
   int grid = P.nTiles < n_cu ? P.nTiles : n_cu;
-#ifdef FU_EXPERIMENTS     // variant builds only: a smaller grid leaves CUs to the weight-gradient stream
-  { static const int cap = [] { const char* e = getenv("FU_PP_GRID"); return e ? atoi(e) : 0; }(); if (cap > 0 && grid > cap && (P.bias == nullptr && P.stats == nullptr)) grid = cap; }
-#endif
   grid &= ~7;
   const ProfSlot ps = o.prof;
   if (ps.start) (void)hipEventRecord(ps.start, s);

@@ -432,7 +432,6 @@ int launch_bn_finalize(const float* partials, int nTiles, int C, int64_t count, 
                        const float* gamma, const float* beta, float eps, float momentum, float* mean, float* invstd,
                        float* a, float* b, float* running_mean, float* running_var, int64_t* nbt, double* dscratch,
                        hipStream_t s) {
-  if (FU_EXP_SKIP(1)) return 0;
   if (sync_world() <= 1 && C % 4 == 0) {
     BnFwdOut o{conv_bias, gamma, beta, eps, momentum, mean, invstd, a, b, running_mean, running_var, nbt};
     hipLaunchKernelGGL((k_bn_stats_fused<0, BnFwdOut>), dim3(C / 4), dim3(256), 0, s, partials, nTiles, C, (double)count, o);
@@ -797,8 +796,7 @@ int launch_bn_bwd(Prec p, void* g, const void* y, int C, int64_t npix, const flo
   const int rows = BNB_THREADS / (C >> 2);
   const size_t sh1 = (size_t)rows * C * 2 * sizeof(float);
   const bool pool = g_pool != nullptr;     // the max-pool backward of this tensor is folded into the two passes
-  if (pool && FU_EXP_SKIP(64)) {
-  } else if (pool) {
+  if (pool) {
     FU_REQUIRE((int64_t)B * H * W == npix && BNB_THREADS % (C >> 2) == 0, "bn_bwd (pooled): bad geometry");
     // both fast_div decodes of k_bn_bwd_pool need n * d < 2^32: windows / Ww and (windows / Ww) / Hw
     FU_REQUIRE(npix < ((int64_t)1 << 31) && (int64_t)B * ((H + 1) / 2) * (int64_t)((W + 1) / 2) * ((W + 1) / 2) < ((int64_t)1 << 32) &&
@@ -819,8 +817,7 @@ int launch_bn_bwd(Prec p, void* g, const void* y, int C, int64_t npix, const flo
     hipLaunchKernelGGL(k_bn_bwd_reduce<f16_t>, dim3(nb), dim3(BNB_THREADS), sh1, s, (const f16_t*)g,
                        (const f16_t*)y, C, npix, a, b, mean, invstd, partials);
   FU_LAUNCH_CHECK();
-  if (FU_EXP_SKIP(2)) {
-  } else if (sync_world() <= 1) {
+  if (sync_world() <= 1) {
     BnBwdOut o{g_grad_unscale, dgamma, dbeta, coef};
     hipLaunchKernelGGL((k_bn_stats_fused<1, BnBwdOut>), dim3(C / 4), dim3(256), 0, s, partials,
                        ext_partials > 0 ? ext_partials : nb, C, (double)npix, o);
@@ -834,8 +831,7 @@ int launch_bn_bwd(Prec p, void* g, const void* y, int C, int64_t npix, const flo
     FU_LAUNCH_CHECK();
   }
   const size_t sh2 = (size_t)rows * C * sizeof(float);
-  if ((pool && FU_EXP_SKIP(64)) || (!pool && FU_EXP_SKIP(16))) {
-  } else if (pool) {
+  if (pool) {
     if (p == PREC_F32) launch_bn_bwd_pool_t<float>(true, nb, sh2, s, g, y, g_pool, C, B, H, W, a, b, mean, invstd, coef, db_partials);
     else if (p == PREC_BF16) launch_bn_bwd_pool_t<bf16_t>(true, nb, sh2, s, g, y, g_pool, C, B, H, W, a, b, mean, invstd, coef, db_partials);
     else launch_bn_bwd_pool_t<f16_t>(true, nb, sh2, s, g, y, g_pool, C, B, H, W, a, b, mean, invstd, coef, db_partials);
@@ -1092,7 +1088,6 @@ int launch_upsample2(Prec p, const void* src, const float* a, const float* b, vo
 
 int launch_upsample2_bwd(Prec p, const void* g_dst, void* g_src, int B, int H, int W, int C, int outH, int outW,
                          const UpTables& t, hipStream_t s) {
-  if (FU_EXP_SKIP(32)) return 0;
   const int py0 = (outH - 2 * H) / 2, px0 = (outW - 2 * W) / 2;
   dim3 g; int CV; unsigned rcp;
   if (p == PREC_F32) {
