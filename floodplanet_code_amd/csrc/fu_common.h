@@ -14,6 +14,15 @@ struct f16_t { unsigned short v; };   // raw IEEE fp16 storage (a distinct type,
 // accumulation, statistics, loss and master weights; the gradient maps carry a power-of-two loss scale (see LossScale).
 enum Prec { PREC_F32 = 0, PREC_BF16 = 1, PREC_F16 = 2 };
 
+// The one place that maps a Prec to an element type: f(T{}) with T = the element type of p.  The launchers pass a generic
+// lambda (`using T = decltype(tag)`); FU_REQUIRE / FU_LAUNCH_CHECK inside it return from the lambda, so such a lambda
+// returns the status (int) and the caller returns or FU_TRYs the call's result.
+template <typename F> auto dispatch_prec(Prec p, F&& f) {
+  if (p == PREC_F32) return f(float{});
+  if (p == PREC_BF16) return f(bf16_t{});
+  return f(f16_t{});
+}
+
 // ---- error plumbing (thread-local message, never exceptions across the ABI) ----------------
 void set_error(const char* fmt, ...);
 const char* get_error();
@@ -25,6 +34,15 @@ const char* get_error();
       ::fu::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
       return 2;                                                                              \
     }                                                                                        \
+  } while (0)
+
+#define FU_LAUNCH_CHECK()                                                       \
+  do {                                                                          \
+    hipError_t _e = hipGetLastError();                                          \
+    if (_e != hipSuccess) {                                                     \
+      ::fu::set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
+      return 2;                                                                 \
+    }                                                                           \
   } while (0)
 
 #define FU_REQUIRE(cond, ...)          \
@@ -127,7 +145,7 @@ __device__ __forceinline__ float bn_act_pre(float a, float y, float b) {
 __device__ __forceinline__ float bn_act(float a, float y, float b) { return fmaxf(bn_act_pre(a, y, b), 0.f); }
 __device__ __forceinline__ float bn_act_fused(float a, float y, float b) { return fmaxf(fmaf(a, y, b), 0.f); }
 
-// 16-byte vector access: V elements of T as floats (V = 4 for fp32, 8 for bf16)
+// 16-byte vector access: V elements of T as floats (V = 4 for fp32, 8 for bf16 and fp16)
 template <typename T> struct VecIO;
 template <> struct VecIO<float> {
   static constexpr int V = 4;

@@ -66,15 +66,6 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-#define FU_LAUNCH_CHECK()                                                       \
-  do {                                                                          \
-    hipError_t _e = hipGetLastError();                                          \
-    if (_e != hipSuccess) {                                                     \
-      set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return 2;                                                                 \
-    }                                                                           \
-  } while (0)
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #ifdef __HIPCC__

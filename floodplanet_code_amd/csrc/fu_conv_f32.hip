@@ -17,15 +17,6 @@ namespace fu {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#define FU_LAUNCH_CHECK()                                                       \
-  do {                                                                          \
-    hipError_t _e = hipGetLastError();                                          \
-    if (_e != hipSuccess) {                                                     \
-      set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return 2;                                                                 \
-    }                                                                           \
-  } while (0)
-
 // ------------------------------------------------------------------------------------------------
 // weight packing (fp32): OIHW -> wf[tap][ci][co] and wd[8-tap][co][ci]
 // ------------------------------------------------------------------------------------------------

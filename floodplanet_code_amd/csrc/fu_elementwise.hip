@@ -38,15 +38,6 @@ void set_error(const char* fmt, ...) {
 }
 const char* get_error() { return g_err; }
 
-#define FU_LAUNCH_CHECK()                                                       \
-  do {                                                                          \
-    hipError_t _e = hipGetLastError();                                          \
-    if (_e != hipSuccess) {                                                     \
-      set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return 2;                                                                 \
-    }                                                                           \
-  } while (0)
-
 static inline int grid_for(int64_t work, int block, int cap = 8192) {
   int64_t g = ceil_div64(work, block);
   if (g > cap) g = cap;
@@ -111,23 +102,20 @@ int launch_nchw_to_nhwc(Prec p, const float* src, void* dst, int B, int C, int H
   src += (int64_t)src_channel_offset * H * W;
   if (p != PREC_F32 && c_pad % 8 == 0 && B <= 65535 && c_pad / 8 <= 65535) {
     const dim3 g8((unsigned)ceil_div(H * W, 256), (unsigned)(c_pad / 8), (unsigned)B);
-    if (p == PREC_BF16)
-      hipLaunchKernelGGL(k_nchw_to_nhwc_v8<bf16_t>, g8, dim3(256), 0, s, src, (bf16_t*)dst, C, H * W, c_pad, srcC);
-    else
-      hipLaunchKernelGGL(k_nchw_to_nhwc_v8<f16_t>, g8, dim3(256), 0, s, src, (f16_t*)dst, C, H * W, c_pad, srcC);
+    return dispatch_prec(p, [&](auto tag) {
+      using T = decltype(tag);
+      if constexpr (sizeof(T) == 2)   // the octet kernel exists for the 16-bit types only
+        hipLaunchKernelGGL(k_nchw_to_nhwc_v8<T>, g8, dim3(256), 0, s, src, (T*)dst, C, H * W, c_pad, srcC);
+      FU_LAUNCH_CHECK();
+      return 0;
+    });
+  }
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_nchw_to_nhwc<T>, dim3(g), dim3(256), 0, s, src, (T*)dst, C, H * W, c_pad, total, srcC);
     FU_LAUNCH_CHECK();
     return 0;
-  }
-  if (p == PREC_F32)
-    hipLaunchKernelGGL(k_nchw_to_nhwc<float>, dim3(g), dim3(256), 0, s, src, (float*)dst, C, H * W, c_pad, total, srcC);
-  else if (p == PREC_BF16)
-    hipLaunchKernelGGL(k_nchw_to_nhwc<bf16_t>, dim3(g), dim3(256), 0, s, src, (bf16_t*)dst, C, H * W, c_pad, total,
-                       srcC);
-  else
-    hipLaunchKernelGGL(k_nchw_to_nhwc<f16_t>, dim3(g), dim3(256), 0, s, src, (f16_t*)dst, C, H * W, c_pad, total,
-                       srcC);
-  FU_LAUNCH_CHECK();
-  return 0;
+  });
 }
 
 // The same conversion from SEVERAL NCHW sources taken side by side along the channel axis (ef_model.py:28-44: the image and
@@ -158,16 +146,17 @@ __global__ __launch_bounds__(256) void k_gather_nchw_to_nhwc(SrcList S, T* __res
 
 int launch_gather_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B, int C, int H, int W, int c_pad, int ch_off,
                                hipStream_t s) {
-  const int V = p == PREC_F32 ? 4 : 8;
-  FU_REQUIRE(c_pad % V == 0 && B <= 65535 && c_pad / V <= 65535, "gather_nchw_to_nhwc: bad geometry (c_pad %d, batch %d)", c_pad, B);
-  FU_REQUIRE(ch_off >= 0 && ch_off + C <= S.coff[S.n], "gather_nchw_to_nhwc: channels [%d, %d) outside the %d source channels",
-             ch_off, ch_off + C, S.coff[S.n]);
-  const dim3 g((unsigned)ceil_div(H * W, 256), (unsigned)(c_pad / V), (unsigned)B);
-  if (p == PREC_F32) hipLaunchKernelGGL(k_gather_nchw_to_nhwc<float>, g, dim3(256), 0, s, S, (float*)dst, C, H * W, c_pad, ch_off);
-  else if (p == PREC_BF16) hipLaunchKernelGGL(k_gather_nchw_to_nhwc<bf16_t>, g, dim3(256), 0, s, S, (bf16_t*)dst, C, H * W, c_pad, ch_off);
-  else hipLaunchKernelGGL(k_gather_nchw_to_nhwc<f16_t>, g, dim3(256), 0, s, S, (f16_t*)dst, C, H * W, c_pad, ch_off);
-  FU_LAUNCH_CHECK();
-  return 0;
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    constexpr int V = VecIO<T>::V;
+    FU_REQUIRE(c_pad % V == 0 && B <= 65535 && c_pad / V <= 65535, "gather_nchw_to_nhwc: bad geometry (c_pad %d, batch %d)", c_pad, B);
+    FU_REQUIRE(ch_off >= 0 && ch_off + C <= S.coff[S.n], "gather_nchw_to_nhwc: channels [%d, %d) outside the %d source channels",
+               ch_off, ch_off + C, S.coff[S.n]);
+    const dim3 g((unsigned)ceil_div(H * W, 256), (unsigned)(c_pad / V), (unsigned)B);
+    hipLaunchKernelGGL(k_gather_nchw_to_nhwc<T>, g, dim3(256), 0, s, S, (T*)dst, C, H * W, c_pad, ch_off);
+    FU_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 // Test-time augmentation (fu_forward_views): the gather above, where destination sample v * B + b is view codes[v] of
@@ -215,38 +204,29 @@ __global__ __launch_bounds__(256) void k_gather_views_nchw_to_nhwc(SrcList S, T*
 
 int launch_gather_views_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B, int n_views, unsigned codes, int C, int H,
                                      int W, int c_pad, int ch_off, hipStream_t s) {
-  const int V = p == PREC_F32 ? 4 : 8;
-  FU_REQUIRE(c_pad % V == 0 && n_views >= 1 && n_views <= 8 && (int64_t)B * n_views <= 65535 && c_pad / V <= 65535,
-             "gather_views_nchw_to_nhwc: bad geometry (c_pad %d, batch %d, views %d)", c_pad, B, n_views);
-  FU_REQUIRE(ch_off >= 0 && ch_off + C <= S.coff[S.n], "gather_views_nchw_to_nhwc: channels [%d, %d) outside the %d source "
-             "channels", ch_off, ch_off + C, S.coff[S.n]);
-  const dim3 g((unsigned)ceil_div(H * W, 256), (unsigned)(c_pad / V), (unsigned)(B * n_views));
-  if (p == PREC_F32)
-    hipLaunchKernelGGL(k_gather_views_nchw_to_nhwc<float>, g, dim3(256), 0, s, S, (float*)dst, C, H, W, c_pad, ch_off, B,
-                       codes);
-  else if (p == PREC_BF16)
-    hipLaunchKernelGGL(k_gather_views_nchw_to_nhwc<bf16_t>, g, dim3(256), 0, s, S, (bf16_t*)dst, C, H, W, c_pad, ch_off,
-                       B, codes);
-  else
-    hipLaunchKernelGGL(k_gather_views_nchw_to_nhwc<f16_t>, g, dim3(256), 0, s, S, (f16_t*)dst, C, H, W, c_pad, ch_off, B,
-                       codes);
-  FU_LAUNCH_CHECK();
-  return 0;
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    constexpr int V = VecIO<T>::V;
+    FU_REQUIRE(c_pad % V == 0 && n_views >= 1 && n_views <= 8 && (int64_t)B * n_views <= 65535 && c_pad / V <= 65535,
+               "gather_views_nchw_to_nhwc: bad geometry (c_pad %d, batch %d, views %d)", c_pad, B, n_views);
+    FU_REQUIRE(ch_off >= 0 && ch_off + C <= S.coff[S.n], "gather_views_nchw_to_nhwc: channels [%d, %d) outside the %d source "
+               "channels", ch_off, ch_off + C, S.coff[S.n]);
+    const dim3 g((unsigned)ceil_div(H * W, 256), (unsigned)(c_pad / V), (unsigned)(B * n_views));
+    hipLaunchKernelGGL(k_gather_views_nchw_to_nhwc<T>, g, dim3(256), 0, s, S, (T*)dst, C, H, W, c_pad, ch_off, B, codes);
+    FU_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int launch_nhwc_to_nchw(Prec p, const void* src, float* dst, int B, int C, int H, int W, int c_pad, hipStream_t s) {
   const int64_t total = (int64_t)B * C * H * W;
   const int g = grid_for(total, 256);
-  if (p == PREC_F32)
-    hipLaunchKernelGGL(k_nhwc_to_nchw<float>, dim3(g), dim3(256), 0, s, (const float*)src, dst, C, H * W, c_pad, total);
-  else if (p == PREC_BF16)
-    hipLaunchKernelGGL(k_nhwc_to_nchw<bf16_t>, dim3(g), dim3(256), 0, s, (const bf16_t*)src, dst, C, H * W, c_pad,
-                       total);
-  else
-    hipLaunchKernelGGL(k_nhwc_to_nchw<f16_t>, dim3(g), dim3(256), 0, s, (const f16_t*)src, dst, C, H * W, c_pad,
-                       total);
-  FU_LAUNCH_CHECK();
-  return 0;
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_nhwc_to_nchw<T>, dim3(g), dim3(256), 0, s, (const T*)src, dst, C, H * W, c_pad, total);
+    FU_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -802,20 +782,18 @@ int launch_bn_bwd(Prec p, void* g, const void* y, int C, int64_t npix, const flo
     FU_REQUIRE(npix < ((int64_t)1 << 31) && (int64_t)B * ((H + 1) / 2) * (int64_t)((W + 1) / 2) * ((W + 1) / 2) < ((int64_t)1 << 32) &&
                    (int64_t)B * ((H + 1) / 2) * (int64_t)((H + 1) / 2) < ((int64_t)1 << 32),
                "bn_bwd (pooled): tensor too large for the 32-bit window decode");
-    if (p == PREC_F32) launch_bn_bwd_pool_t<float>(false, nb, sh1, s, g, y, g_pool, C, B, H, W, a, b, mean, invstd, coef, partials);
-    else if (p == PREC_BF16) launch_bn_bwd_pool_t<bf16_t>(false, nb, sh1, s, g, y, g_pool, C, B, H, W, a, b, mean, invstd, coef, partials);
-    else launch_bn_bwd_pool_t<f16_t>(false, nb, sh1, s, g, y, g_pool, C, B, H, W, a, b, mean, invstd, coef, partials);
+    dispatch_prec(p, [&](auto tag) {
+      launch_bn_bwd_pool_t<decltype(tag)>(false, nb, sh1, s, g, y, g_pool, C, B, H, W, a, b, mean, invstd, coef, partials);
+    });
   } else if (ext_partials > 0) {
     // (nothing to launch)
-  } else if (p == PREC_F32)
-    hipLaunchKernelGGL(k_bn_bwd_reduce<float>, dim3(nb), dim3(BNB_THREADS), sh1, s, (const float*)g, (const float*)y,
-                       C, npix, a, b, mean, invstd, partials);
-  else if (p == PREC_BF16)
-    hipLaunchKernelGGL(k_bn_bwd_reduce<bf16_t>, dim3(nb), dim3(BNB_THREADS), sh1, s, (const bf16_t*)g,
-                       (const bf16_t*)y, C, npix, a, b, mean, invstd, partials);
-  else
-    hipLaunchKernelGGL(k_bn_bwd_reduce<f16_t>, dim3(nb), dim3(BNB_THREADS), sh1, s, (const f16_t*)g,
-                       (const f16_t*)y, C, npix, a, b, mean, invstd, partials);
+  } else {
+    dispatch_prec(p, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL(k_bn_bwd_reduce<T>, dim3(nb), dim3(BNB_THREADS), sh1, s, (const T*)g, (const T*)y, C, npix, a, b,
+                         mean, invstd, partials);
+    });
+  }
   FU_LAUNCH_CHECK();
   if (sync_world() <= 1) {
     BnBwdOut o{g_grad_unscale, dgamma, dbeta, coef};
@@ -832,37 +810,32 @@ int launch_bn_bwd(Prec p, void* g, const void* y, int C, int64_t npix, const flo
   }
   const size_t sh2 = (size_t)rows * C * sizeof(float);
   if (pool) {
-    if (p == PREC_F32) launch_bn_bwd_pool_t<float>(true, nb, sh2, s, g, y, g_pool, C, B, H, W, a, b, mean, invstd, coef, db_partials);
-    else if (p == PREC_BF16) launch_bn_bwd_pool_t<bf16_t>(true, nb, sh2, s, g, y, g_pool, C, B, H, W, a, b, mean, invstd, coef, db_partials);
-    else launch_bn_bwd_pool_t<f16_t>(true, nb, sh2, s, g, y, g_pool, C, B, H, W, a, b, mean, invstd, coef, db_partials);
+    dispatch_prec(p, [&](auto tag) {
+      launch_bn_bwd_pool_t<decltype(tag)>(true, nb, sh2, s, g, y, g_pool, C, B, H, W, a, b, mean, invstd, coef, db_partials);
+    });
   } else if (head) {
     const size_t shh = (size_t)(BNB_THREADS / (C / 8)) * C * sizeof(float);
-#define FU_APPLY_HEAD(TT, NC) \
-    hipLaunchKernelGGL((k_bn_bwd_apply_head<TT, NC>), dim3(nb), dim3(BNB_THREADS), shh, s, head->dl, head->w, head->ncls, \
-                       (TT*)g, (const TT*)y, C, npix, a, b, mean, invstd, coef, db_partials)
-    if (p == PREC_BF16) {
-      switch (head->ncls) {
-        case 2: FU_APPLY_HEAD(bf16_t, 2); break;
-        case 3: FU_APPLY_HEAD(bf16_t, 3); break;
-        default: FU_APPLY_HEAD(bf16_t, 0); break;
+#define FU_APPLY_HEAD(NC) \
+    hipLaunchKernelGGL((k_bn_bwd_apply_head<T, NC>), dim3(nb), dim3(BNB_THREADS), shh, s, head->dl, head->w, head->ncls, \
+                       (T*)g, (const T*)y, C, npix, a, b, mean, invstd, coef, db_partials)
+    dispatch_prec(p, [&](auto tag) {
+      using T = decltype(tag);
+      if constexpr (sizeof(T) == 2) {   // 16-bit element types only (required above)
+        switch (head->ncls) {
+          case 2: FU_APPLY_HEAD(2); break;
+          case 3: FU_APPLY_HEAD(3); break;
+          default: FU_APPLY_HEAD(0); break;
+        }
       }
-    } else {
-      switch (head->ncls) {
-        case 2: FU_APPLY_HEAD(f16_t, 2); break;
-        case 3: FU_APPLY_HEAD(f16_t, 3); break;
-        default: FU_APPLY_HEAD(f16_t, 0); break;
-      }
-    }
+    });
 #undef FU_APPLY_HEAD
-  } else if (p == PREC_F32)
-    hipLaunchKernelGGL(k_bn_bwd_apply<float>, dim3(nb), dim3(BNB_THREADS), sh2, s, (float*)g, (const float*)y, C, npix,
-                       a, b, mean, invstd, coef, db_partials);
-  else if (p == PREC_BF16)
-    hipLaunchKernelGGL(k_bn_bwd_apply<bf16_t>, dim3(nb), dim3(BNB_THREADS), sh2, s, (bf16_t*)g, (const bf16_t*)y, C,
-                       npix, a, b, mean, invstd, coef, db_partials);
-  else
-    hipLaunchKernelGGL(k_bn_bwd_apply<f16_t>, dim3(nb), dim3(BNB_THREADS), sh2, s, (f16_t*)g, (const f16_t*)y, C,
-                       npix, a, b, mean, invstd, coef, db_partials);
+  } else {
+    dispatch_prec(p, [&](auto tag) {
+      using T = decltype(tag);
+      hipLaunchKernelGGL(k_bn_bwd_apply<T>, dim3(nb), dim3(BNB_THREADS), sh2, s, (T*)g, (const T*)y, C, npix, a, b, mean,
+                         invstd, coef, db_partials);
+    });
+  }
   FU_LAUNCH_CHECK();
   *n_db_partials = nb;
   return 0;
@@ -882,7 +855,7 @@ __device__ __forceinline__ void load_act4(const T* p, const float (&av)[4], cons
 }
 
 // Elementwise NHWC kernels below share one indexing scheme: grid = (items of one output row / 256, rows, batch), one
-// 16-byte channel vector (VecIO: 4 fp32 / 8 bf16) per thread, 32-bit index math.  (The first versions decoded a flat
+// 16-byte channel vector (VecIO: 4 fp32 / 8 bf16 or fp16) per thread, 32-bit index math.  (The first versions decoded a flat
 // 64-bit index with four 64-bit divisions per 8-byte vector and ran 2-5x off the HBM roofline on index math alone.)
 template <typename T, int V>
 __device__ __forceinline__ void load_act(const T* p, const float (&av)[V], const float (&bv)[V], bool bn, float (&z)[V]) {
@@ -941,24 +914,15 @@ static bool row_grid(int C, int items_w, int rows, int B, dim3* grid, int* CV, u
 int launch_maxpool2(Prec p, const void* src, const float* a, const float* b, void* dst, int B, int H, int W, int C,
                     hipStream_t s) {
   const int Ho = H / 2, Wo = W / 2;
-  dim3 g; int CV; unsigned rcp;
-  if (p == PREC_F32) {
-    FU_REQUIRE(row_grid<float>(C, Wo, Ho, B, &g, &CV, &rcp), "maxpool: unsupported shape (C=%d H=%d B=%d)", C, H, B);
-    hipLaunchKernelGGL(k_maxpool2<float>, g, dim3(256), 0, s, (const float*)src, a, b, (float*)dst, H, W, C, Ho, Wo, CV,
-                       rcp);
-  } else if (p == PREC_BF16) {
-    FU_REQUIRE(row_grid<bf16_t>(C, Wo, Ho, B, &g, &CV, &rcp), "maxpool: unsupported shape (C=%d H=%d B=%d)", C, H, B);
-    hipLaunchKernelGGL(k_maxpool2<bf16_t>, g, dim3(256), 0, s, (const bf16_t*)src, a, b, (bf16_t*)dst, H, W, C, Ho, Wo,
-                       CV, rcp);
-  } else {
-    FU_REQUIRE(row_grid<f16_t>(C, Wo, Ho, B, &g, &CV, &rcp), "maxpool: unsupported shape (C=%d H=%d B=%d)", C, H, B);
-    hipLaunchKernelGGL(k_maxpool2<f16_t>, g, dim3(256), 0, s, (const f16_t*)src, a, b, (f16_t*)dst, H, W, C, Ho, Wo,
-                       CV, rcp);
-  }
-  FU_LAUNCH_CHECK();
-  return 0;
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    dim3 g; int CV; unsigned rcp;
+    FU_REQUIRE(row_grid<T>(C, Wo, Ho, B, &g, &CV, &rcp), "maxpool: unsupported shape (C=%d H=%d B=%d)", C, H, B);
+    hipLaunchKernelGGL(k_maxpool2<T>, g, dim3(256), 0, s, (const T*)src, a, b, (T*)dst, H, W, C, Ho, Wo, CV, rcp);
+    FU_LAUNCH_CHECK();
+    return 0;
+  });
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // bilinear x2 (align_corners=True) of relu(a*y+b), zero-padded to outH x outW (F.pad of unet.py:57-62)
@@ -1064,10 +1028,10 @@ int launch_upsample2(Prec p, const void* src, const float* a, const float* b, vo
                      int outH, int outW, const UpTables& t, hipStream_t s) {
   FU_REQUIRE(outH >= 2 * H && outW >= 2 * W, "upsample: target smaller than 2x source");
   const int py0 = (outH - 2 * H) / 2, px0 = (outW - 2 * W) / 2;
-  dim3 g; int CV; unsigned rcp;
   // four rows per thread where that still leaves >= 2048 workgroups, else one
-  auto go = [&](auto tag) {
+  return dispatch_prec(p, [&](auto tag) {
     using T = decltype(tag);
+    dim3 g; int CV; unsigned rcp;
     FU_REQUIRE(row_grid<T>(C, outW, outH, B, &g, &CV, &rcp), "upsample: unsupported shape (C=%d H=%d B=%d)", C, outH, B);
     if ((int64_t)g.x * ceil_div(outH, 4) * B >= 2048) {
       g.y = ceil_div(outH, 4);
@@ -1077,34 +1041,23 @@ int launch_upsample2(Prec p, const void* src, const float* a, const float* b, vo
       hipLaunchKernelGGL((k_upsample2<T, 1>), g, dim3(256), 0, s, (const T*)src, a, b, (T*)dst, H, W, C, outH, outW, py0, px0,
                          t, CV, rcp);
     }
+    FU_LAUNCH_CHECK();
     return 0;
-  };
-  if (p == PREC_F32) FU_TRY(go(float{}));
-  else if (p == PREC_BF16) FU_TRY(go(bf16_t{}));
-  else FU_TRY(go(f16_t{}));
-  FU_LAUNCH_CHECK();
-  return 0;
+  });
 }
 
 int launch_upsample2_bwd(Prec p, const void* g_dst, void* g_src, int B, int H, int W, int C, int outH, int outW,
                          const UpTables& t, hipStream_t s) {
   const int py0 = (outH - 2 * H) / 2, px0 = (outW - 2 * W) / 2;
-  dim3 g; int CV; unsigned rcp;
-  if (p == PREC_F32) {
-    FU_REQUIRE(row_grid<float>(C, W, H, B, &g, &CV, &rcp), "upsample_bwd: unsupported shape (C=%d H=%d B=%d)", C, H, B);
-    hipLaunchKernelGGL(k_upsample2_bwd<float>, g, dim3(256), 0, s, (const float*)g_dst, (float*)g_src, H, W, C, outH,
-                       outW, py0, px0, t, CV, rcp);
-  } else if (p == PREC_BF16) {
-    FU_REQUIRE(row_grid<bf16_t>(C, W, H, B, &g, &CV, &rcp), "upsample_bwd: unsupported shape (C=%d H=%d B=%d)", C, H, B);
-    hipLaunchKernelGGL(k_upsample2_bwd<bf16_t>, g, dim3(256), 0, s, (const bf16_t*)g_dst, (bf16_t*)g_src, H, W, C, outH,
-                       outW, py0, px0, t, CV, rcp);
-  } else {
-    FU_REQUIRE(row_grid<f16_t>(C, W, H, B, &g, &CV, &rcp), "upsample_bwd: unsupported shape (C=%d H=%d B=%d)", C, H, B);
-    hipLaunchKernelGGL(k_upsample2_bwd<f16_t>, g, dim3(256), 0, s, (const f16_t*)g_dst, (f16_t*)g_src, H, W, C, outH,
-                       outW, py0, px0, t, CV, rcp);
-  }
-  FU_LAUNCH_CHECK();
-  return 0;
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    dim3 g; int CV; unsigned rcp;
+    FU_REQUIRE(row_grid<T>(C, W, H, B, &g, &CV, &rcp), "upsample_bwd: unsupported shape (C=%d H=%d B=%d)", C, H, B);
+    hipLaunchKernelGGL(k_upsample2_bwd<T>, g, dim3(256), 0, s, (const T*)g_dst, (T*)g_src, H, W, C, outH, outW, py0, px0, t,
+                       CV, rcp);
+    FU_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1224,34 +1177,26 @@ int launch_depth_to_space(Prec p, const void* y4, void* up, int B, int h, int w,
   const int py0 = (outH - 2 * h) / 2, px0 = (outW - 2 * w) / 2;
   const int64_t total = (int64_t)B * outH * outW * (C / 4);
   const int g = grid_for(total, 256);
-  if (p == PREC_F32)
-    hipLaunchKernelGGL(k_depth_to_space<float>, dim3(g), dim3(256), 0, s, (const float*)y4, (float*)up, h, w, C, outH,
-                       outW, py0, px0, total);
-  else if (p == PREC_BF16)
-    hipLaunchKernelGGL(k_depth_to_space<bf16_t>, dim3(g), dim3(256), 0, s, (const bf16_t*)y4, (bf16_t*)up, h, w, C, outH,
-                       outW, py0, px0, total);
-  else
-    hipLaunchKernelGGL(k_depth_to_space<f16_t>, dim3(g), dim3(256), 0, s, (const f16_t*)y4, (f16_t*)up, h, w, C, outH,
-                       outW, py0, px0, total);
-  FU_LAUNCH_CHECK();
-  return 0;
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_depth_to_space<T>, dim3(g), dim3(256), 0, s, (const T*)y4, (T*)up, h, w, C, outH, outW, py0, px0,
+                       total);
+    FU_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int launch_space_to_depth(Prec p, const void* gup, void* g4, int B, int h, int w, int C, int outH, int outW,
                           hipStream_t s) {
   const int py0 = (outH - 2 * h) / 2, px0 = (outW - 2 * w) / 2;
   const int64_t total = (int64_t)B * h * w * 4 * (C / 4);
   const int g = grid_for(total, 256);
-  if (p == PREC_F32)
-    hipLaunchKernelGGL(k_space_to_depth<float>, dim3(g), dim3(256), 0, s, (const float*)gup, (float*)g4, h, w, C, outH,
-                       outW, py0, px0, total);
-  else if (p == PREC_BF16)
-    hipLaunchKernelGGL(k_space_to_depth<bf16_t>, dim3(g), dim3(256), 0, s, (const bf16_t*)gup, (bf16_t*)g4, h, w, C, outH,
-                       outW, py0, px0, total);
-  else
-    hipLaunchKernelGGL(k_space_to_depth<f16_t>, dim3(g), dim3(256), 0, s, (const f16_t*)gup, (f16_t*)g4, h, w, C, outH,
-                       outW, py0, px0, total);
-  FU_LAUNCH_CHECK();
-  return 0;
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_space_to_depth<T>, dim3(g), dim3(256), 0, s, (const T*)gup, (T*)g4, h, w, C, outH, outW, py0, px0,
+                       total);
+    FU_LAUNCH_CHECK();
+    return 0;
+  });
 }
 int launch_colsum_partials(const float* partials, int n, int C, float* out, hipStream_t s) {
   hipLaunchKernelGGL(k_colsum_partials, dim3(ceil_div(C, 64)), dim3(64), 0, s, partials, n, C, g_grad_unscale, out);
@@ -1266,18 +1211,14 @@ int launch_channel_partial_sums(Prec p, const void* g, int C, int64_t npix, floa
   if (nb > 2048) nb = 2048;
   if (nb < 1) nb = 1;
   const size_t sh = (size_t)rows * C * sizeof(float);
-  if (p == PREC_F32)
-    hipLaunchKernelGGL(k_channel_partial_sums<float>, dim3((unsigned)nb), dim3(BNB_THREADS), sh, s, (const float*)g, C,
-                       npix, partials);
-  else if (p == PREC_BF16)
-    hipLaunchKernelGGL(k_channel_partial_sums<bf16_t>, dim3((unsigned)nb), dim3(BNB_THREADS), sh, s, (const bf16_t*)g,
-                       C, npix, partials);
-  else
-    hipLaunchKernelGGL(k_channel_partial_sums<f16_t>, dim3((unsigned)nb), dim3(BNB_THREADS), sh, s, (const f16_t*)g,
-                       C, npix, partials);
-  FU_LAUNCH_CHECK();
-  *n_partials = (int)nb;
-  return 0;
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(k_channel_partial_sums<T>, dim3((unsigned)nb), dim3(BNB_THREADS), sh, s, (const T*)g, C, npix,
+                       partials);
+    FU_LAUNCH_CHECK();
+    *n_partials = (int)nb;
+    return 0;
+  });
 }
 int launch_convT_to_w3(const float* w, const float* b, int Cin, int Cout, float* w3, float* bias4, hipStream_t s) {
   const int64_t total = (int64_t)4 * Cout * Cin * 9;
@@ -1318,21 +1259,17 @@ __global__ void k_copy_channels(const T* __restrict__ src, int srcC, int src_off
 }
 int launch_copy_channels(Prec p, const void* src, int srcC, int src_off, const float* a, const float* b, void* dst,
                          int dstC, int dst_off, int C, int64_t npix, hipStream_t s) {
-  const int V = p == PREC_F32 ? 4 : 8;
-  FU_REQUIRE(C % V == 0 && srcC % V == 0 && dstC % V == 0 && src_off % V == 0 && dst_off % V == 0,
-             "copy_channels: channel counts / offsets must be multiples of %d", V);
-  const int g = grid_for(npix * (C / V), 256);
-  if (p == PREC_F32)
-    hipLaunchKernelGGL((k_copy_channels<float, 4>), dim3(g), dim3(256), 0, s, (const float*)src, srcC, src_off, a, b,
-                       (float*)dst, dstC, dst_off, C, npix);
-  else if (p == PREC_BF16)
-    hipLaunchKernelGGL((k_copy_channels<bf16_t, 8>), dim3(g), dim3(256), 0, s, (const bf16_t*)src, srcC, src_off, a, b,
-                       (bf16_t*)dst, dstC, dst_off, C, npix);
-  else
-    hipLaunchKernelGGL((k_copy_channels<f16_t, 8>), dim3(g), dim3(256), 0, s, (const f16_t*)src, srcC, src_off, a, b,
-                       (f16_t*)dst, dstC, dst_off, C, npix);
-  FU_LAUNCH_CHECK();
-  return 0;
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    constexpr int V = VecIO<T>::V;
+    FU_REQUIRE(C % V == 0 && srcC % V == 0 && dstC % V == 0 && src_off % V == 0 && dst_off % V == 0,
+               "copy_channels: channel counts / offsets must be multiples of %d", V);
+    const int g = grid_for(npix * (C / V), 256);
+    hipLaunchKernelGGL((k_copy_channels<T, V>), dim3(g), dim3(256), 0, s, (const T*)src, srcC, src_off, a, b, (T*)dst, dstC,
+                       dst_off, C, npix);
+    FU_LAUNCH_CHECK();
+    return 0;
+  });
 }
 __global__ void k_center_to_w3(const float* __restrict__ w, float* __restrict__ w3, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n * 9; i += (int64_t)gridDim.x * blockDim.x)
@@ -1451,41 +1388,33 @@ static bool head_geometry(int C, int* LPP) {
   return *LPP >= 1 && *LPP <= 16 && (*LPP & (*LPP - 1)) == 0;
 }
 
-template <typename T>
-static void launch_head_fwd_t(const T* y, const float* a, const float* b, const float* w, const float* bias, int C, int ncls,
-                              int B, int HW, int LPP, float* nhwc, float* nchw, hipStream_t s) {
-  constexpr int U = 4;
-  const int g = ceil_div(ceil_div(HW, (256 / LPP) * U), 2);
-#define FU_HEAD_FWD(NC)                                                                                              \
-  hipLaunchKernelGGL((k_head_fwd<T, NC, U>), dim3(g, B), dim3(256), 0, s, y, a, b, w, bias, C, ncls, HW, LPP, nhwc, nchw)
-  switch (ncls) {
-    case 1: FU_HEAD_FWD(1); break;
-    case 2: FU_HEAD_FWD(2); break;
-    case 3: FU_HEAD_FWD(3); break;
-    case 4: FU_HEAD_FWD(4); break;
-    default: FU_HEAD_FWD(0); break;
-  }
-#undef FU_HEAD_FWD
-}
-
 int launch_head_fwd(Prec p, const void* y, const float* a, const float* b, const float* w, const float* bias, int C,
                     int ncls, int B, int H, int W, float* logits_nhwc, float* logits_nchw, hipStream_t s) {
   FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "head: n_classes must be 1..%d", HEAD_MAX_CLS);
   FU_REQUIRE(B <= 65535, "head: batch too large (%d)", B);
   const int HW = H * W;
-  int LPP;
-  if (p == PREC_F32) {
-    FU_REQUIRE(head_geometry<float>(C, &LPP), "head: base channels must be 4, 8, 16, 32 or 64 in fp32 (got %d)", C);
-    launch_head_fwd_t<float>((const float*)y, a, b, w, bias, C, ncls, B, HW, LPP, logits_nhwc, logits_nchw, s);
-  } else if (p == PREC_BF16) {
-    FU_REQUIRE(head_geometry<bf16_t>(C, &LPP), "head: base channels must be 8, 16, 32, 64 or 128 in bf16 (got %d)", C);
-    launch_head_fwd_t<bf16_t>((const bf16_t*)y, a, b, w, bias, C, ncls, B, HW, LPP, logits_nhwc, logits_nchw, s);
-  } else {
-    FU_REQUIRE(head_geometry<f16_t>(C, &LPP), "head: base channels must be 8, 16, 32, 64 or 128 in fp16 (got %d)", C);
-    launch_head_fwd_t<f16_t>((const f16_t*)y, a, b, w, bias, C, ncls, B, HW, LPP, logits_nhwc, logits_nchw, s);
-  }
-  FU_LAUNCH_CHECK();
-  return 0;
+  const char* name = p == PREC_F32 ? "fp32" : p == PREC_BF16 ? "bf16" : "fp16";   // for the message below
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    constexpr int V = VecIO<T>::V, U = 4;
+    int LPP;
+    FU_REQUIRE(head_geometry<T>(C, &LPP), "head: base channels must be %d, %d, %d, %d or %d in %s (got %d)", V, 2 * V, 4 * V,
+               8 * V, 16 * V, name, C);
+    const int g = ceil_div(ceil_div(HW, (256 / LPP) * U), 2);
+#define FU_HEAD_FWD(NC)                                                                                                  \
+  hipLaunchKernelGGL((k_head_fwd<T, NC, U>), dim3(g, B), dim3(256), 0, s, (const T*)y, a, b, w, bias, C, ncls, HW, LPP, \
+                     logits_nhwc, logits_nchw)
+    switch (ncls) {
+      case 1: FU_HEAD_FWD(1); break;
+      case 2: FU_HEAD_FWD(2); break;
+      case 3: FU_HEAD_FWD(3); break;
+      case 4: FU_HEAD_FWD(4); break;
+      default: FU_HEAD_FWD(0); break;
+    }
+#undef FU_HEAD_FWD
+    FU_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1915,68 +1844,51 @@ int launch_head_bwd(Prec p, const float* dlogits_nhwc, const void* y, const floa
                     int C, int ncls, int64_t npix, void* g, float* partials, float* dw, float* db, hipStream_t s,
                     const BnbFuse* fuse) {
   FU_REQUIRE(npix < ((int64_t)1 << 31), "head_bwd: too many pixels");
-  int LPP;
-  if (p == PREC_F32) FU_REQUIRE(head_geometry<float>(C, &LPP), "head_bwd: unsupported channel count %d", C);
-  else if (p == PREC_BF16) FU_REQUIRE(head_geometry<bf16_t>(C, &LPP), "head_bwd: unsupported channel count %d", C);
-  else FU_REQUIRE(head_geometry<f16_t>(C, &LPP), "head_bwd: unsupported channel count %d", C);
-  constexpr int U = 4;
-  const int ppb = 256 / LPP;
-  int nblk = (int)ceil_div64(npix, (int64_t)ppb * U);
-  if (nblk > HB_BLOCKS) nblk = HB_BLOCKS;
-  const int stride = ncls * C + ncls;
-  // the BatchNorm-backward sums of g, if asked for (16-bit modes with BatchNorm coefficients: the bench path)
-  const bool bnb = fuse && fuse->y == y && fuse->tiles_out && a != nullptr && p != PREC_F32 &&
-                   (int64_t)nblk * C * 2 <= fuse->max_elems;
-  size_t sh = (size_t)ppb * stride * sizeof(float);
-  if (bnb && (size_t)ppb * C * 2 * sizeof(float) > sh) sh = (size_t)ppb * C * 2 * sizeof(float);
-  FU_REQUIRE(sh <= 64 * 1024, "head_bwd: LDS request too large (%zu)", sh);
-  const float* bmean = bnb ? fuse->mean : nullptr;
-  const float* binv = bnb ? fuse->invstd : nullptr;
-  float* bpart = bnb ? fuse->part : nullptr;
-#define FU_HEAD_BWD(TT, NC)                                                                                     \
+  return dispatch_prec(p, [&](auto tag) {
+    using T = decltype(tag);
+    int LPP;
+    FU_REQUIRE(head_geometry<T>(C, &LPP), "head_bwd: unsupported channel count %d", C);
+    constexpr int U = 4;
+    const int ppb = 256 / LPP;
+    int nblk = (int)ceil_div64(npix, (int64_t)ppb * U);
+    if (nblk > HB_BLOCKS) nblk = HB_BLOCKS;
+    const int stride = ncls * C + ncls;
+    // the BatchNorm-backward sums of g, if asked for (16-bit modes with BatchNorm coefficients: the bench path)
+    const bool bnb = fuse && fuse->y == y && fuse->tiles_out && a != nullptr && p != PREC_F32 &&
+                     (int64_t)nblk * C * 2 <= fuse->max_elems;
+    size_t sh = (size_t)ppb * stride * sizeof(float);
+    if (bnb && (size_t)ppb * C * 2 * sizeof(float) > sh) sh = (size_t)ppb * C * 2 * sizeof(float);
+    FU_REQUIRE(sh <= 64 * 1024, "head_bwd: LDS request too large (%zu)", sh);
+    const float* bmean = bnb ? fuse->mean : nullptr;
+    const float* binv = bnb ? fuse->invstd : nullptr;
+    float* bpart = bnb ? fuse->part : nullptr;
+#define FU_HEAD_BWD(NC)                                                                                         \
   do {                                                                                                          \
     if (bnb && fuse->skip_g)                                                                                    \
-      hipLaunchKernelGGL((k_head_bwd<TT, NC, U, true, false>), dim3(nblk), dim3(256), sh, s, dlogits_nhwc, (const TT*)y, a, b, \
-                         w, C, ncls, (int)npix, LPP, (TT*)g, partials, bmean, binv, bpart);                     \
+      hipLaunchKernelGGL((k_head_bwd<T, NC, U, true, false>), dim3(nblk), dim3(256), sh, s, dlogits_nhwc, (const T*)y, a, b, \
+                         w, C, ncls, (int)npix, LPP, (T*)g, partials, bmean, binv, bpart);                      \
     else if (bnb)                                                                                               \
-      hipLaunchKernelGGL((k_head_bwd<TT, NC, U, true>), dim3(nblk), dim3(256), sh, s, dlogits_nhwc, (const TT*)y, a, b, w, C, \
-                         ncls, (int)npix, LPP, (TT*)g, partials, bmean, binv, bpart);                           \
+      hipLaunchKernelGGL((k_head_bwd<T, NC, U, true>), dim3(nblk), dim3(256), sh, s, dlogits_nhwc, (const T*)y, a, b, w, C, \
+                         ncls, (int)npix, LPP, (T*)g, partials, bmean, binv, bpart);                            \
     else                                                                                                        \
-      hipLaunchKernelGGL((k_head_bwd<TT, NC, U, false>), dim3(nblk), dim3(256), sh, s, dlogits_nhwc, (const TT*)y, a, b, w, \
-                         C, ncls, (int)npix, LPP, (TT*)g, partials, bmean, binv, bpart);                         \
+      hipLaunchKernelGGL((k_head_bwd<T, NC, U, false>), dim3(nblk), dim3(256), sh, s, dlogits_nhwc, (const T*)y, a, b, w, \
+                         C, ncls, (int)npix, LPP, (T*)g, partials, bmean, binv, bpart);                         \
   } while (0)
-  if (p == PREC_F32) {
     switch (ncls) {
-      case 1: FU_HEAD_BWD(float, 1); break;
-      case 2: FU_HEAD_BWD(float, 2); break;
-      case 3: FU_HEAD_BWD(float, 3); break;
-      case 4: FU_HEAD_BWD(float, 4); break;
-      default: FU_HEAD_BWD(float, 0); break;
+      case 1: FU_HEAD_BWD(1); break;
+      case 2: FU_HEAD_BWD(2); break;
+      case 3: FU_HEAD_BWD(3); break;
+      case 4: FU_HEAD_BWD(4); break;
+      default: FU_HEAD_BWD(0); break;
     }
-  } else if (p == PREC_BF16) {
-    switch (ncls) {
-      case 1: FU_HEAD_BWD(bf16_t, 1); break;
-      case 2: FU_HEAD_BWD(bf16_t, 2); break;
-      case 3: FU_HEAD_BWD(bf16_t, 3); break;
-      case 4: FU_HEAD_BWD(bf16_t, 4); break;
-      default: FU_HEAD_BWD(bf16_t, 0); break;
-    }
-  } else {
-    switch (ncls) {
-      case 1: FU_HEAD_BWD(f16_t, 1); break;
-      case 2: FU_HEAD_BWD(f16_t, 2); break;
-      case 3: FU_HEAD_BWD(f16_t, 3); break;
-      case 4: FU_HEAD_BWD(f16_t, 4); break;
-      default: FU_HEAD_BWD(f16_t, 0); break;
-    }
-  }
 #undef FU_HEAD_BWD
-  FU_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_head_bwd_finalize, dim3(ceil_div(stride, 8)), dim3(256), 0, s, partials, nblk, C, ncls,
-                     g_grad_unscale, dw, db);
-  FU_LAUNCH_CHECK();
-  if (bnb) *fuse->tiles_out = nblk;
-  return 0;
+    FU_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_head_bwd_finalize, dim3(ceil_div(stride, 8)), dim3(256), 0, s, partials, nblk, C, ncls,
+                       g_grad_unscale, dw, db);
+    FU_LAUNCH_CHECK();
+    if (bnb) *fuse->tiles_out = nblk;
+    return 0;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
