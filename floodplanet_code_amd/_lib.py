@@ -66,6 +66,22 @@ class FuSceneCrop(C.Structure):
     ]
 
 
+class FuBandAccum(C.Structure):
+    """fu_band_accum (include/floodunet.h): the caller-owned device accumulators of fu_band_stats."""
+    _fields_ = [
+        ("count", C.c_void_p),
+        ("sum", C.c_void_p),
+        ("sumsq", C.c_void_p),
+        ("vmin", C.c_void_p),
+        ("vmax", C.c_void_p),
+        ("n_nonfinite", C.c_void_p),
+        ("hist", C.c_void_p),
+        ("n_bins", C.c_int32),
+        ("lo", C.c_float),
+        ("hi", C.c_float),
+    ]
+
+
 class FloodUNetError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"libfloodunet error {status}: {message}")
@@ -121,6 +137,9 @@ SIGNATURES = {
     "fu_scene_crops": (_i, [_p, _i, C.POINTER(FuSceneCrop), _i, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p]),
     "fu_resize_lanczos4_tiles": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "fu_assemble_tiles": (_i, [C.POINTER(_p), C.POINTER(C.c_int32), _i, _i, _i, _i, _p, _p, _i, _p, _p, _f, _p, _p, _p, _p]),
+    "fu_band_stats_workspace_bytes": (_i64, [_i, _i]),
+    "fu_band_stats": (_i, [C.POINTER(_p), C.POINTER(C.c_int32), _i, _i, _i, _i, _p, _p, _i, C.POINTER(FuBandAccum), _p, _i64,
+                           _p]),
     "fu_workspace_bytes": (_i64, [_p]),
     "fu_flops_per_tile": (_i, [_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "fu_profile_enable": (_i, [_p, _i]),

@@ -1714,6 +1714,21 @@ int fu_scene_crops(fu_ctx* c, int n, const fu_scene_crop* entries, int C, int ti
                             mean_out, std_out, s);
 }
 
+int64_t fu_band_stats_workspace_bytes(int n_channels, int n_bins) {
+  if (n_channels < 1 || n_bins < 0) return 0;
+  return band_stats_workspace_bytes(n_channels, n_bins);
+}
+
+int fu_band_stats(const float* const* srcs, const int32_t* src_channels, int n_src, int B, int H, int W,
+                  const int32_t* valid_h, const int32_t* valid_w, int mask_mode, const fu_band_accum* acc,
+                  void* workspace, int64_t workspace_bytes, fu_stream stream) {
+  FU_REQUIRE(srcs && src_channels && acc, "fu_band_stats: null sources / channel list / accumulators");
+  const BandAccum a{acc->count, acc->sum, acc->sumsq, acc->vmin, acc->vmax, acc->n_nonfinite, acc->hist, acc->n_bins,
+                    acc->lo, acc->hi};
+  return launch_band_stats(srcs, src_channels, n_src, B, H, W, valid_h, valid_w, mask_mode, a, workspace,
+                           workspace_bytes, (hipStream_t)stream);
+}
+
 int fu_resize_lanczos4_tiles(const float* windows, int B, int C, int win_h, int win_w, const int32_t* iy, const float* wy,
                              const int32_t* ix, const float* wx, int tile_h, int tile_w, int scale_mode, float* out,
                              fu_stream stream) {

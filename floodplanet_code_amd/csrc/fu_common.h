@@ -444,6 +444,15 @@ struct SceneCropJob {
 // in the top-left corner (valid size = the box) -- the same kernels, instantiated on scene-box addressing
 int launch_scene_crops(const SceneCropJob* jobs_dev, int n, int C, int H, int W, int norm_mode, const float* gmean,
                        const float* gstd, float pad_value, float* out, float* mean_out, float* std_out, hipStream_t s);
+// fu_band_stats: the caller's per-channel accumulators (all ADDED to) and the histogram's geometry
+struct BandAccum {
+  int64_t* count; double* sum; double* sumsq; float* vmin; float* vmax; int64_t* n_nonfinite;
+  int64_t* hist; int n_bins; float lo, hi;
+};
+int64_t band_stats_workspace_bytes(int n_channels, int n_bins);
+int launch_band_stats(const float* const* srcs, const int* src_channels, int n_src, int B, int H, int W, const int* vh,
+                      const int* vw, int mask_mode, const BandAccum& acc, void* workspace, int64_t workspace_bytes,
+                      hipStream_t s);
 int launch_resize_lanczos4_tiles(const float* win, int B, int C, int win_h, int win_w, const int* iy, const float* wy,
                                  const int* ix, const float* wx, int TH, int TW, int scale_mode, float* out, hipStream_t s);
 int launch_augment(const float* img, const int64_t* tgt, float* img_o, int64_t* tgt_o, const int* flags,

@@ -10,8 +10,10 @@ mean, std [C,1,1]} (:644-648).
 Differences, all at the edges of the path: rasters are decoded by `datasets.tiff` (uncompressed strips only) and
 resampled by `datasets.resize` (Lanczos-4 restated, parity unpinned); `transforms` must be None -- flips / rotations
 run on the GPU on whole batches (`floodplanet_code_amd.augment`, C ABI `fu_augment`) instead of per item on the CPU
-(base_dataset.py:494-555); norm_mode 'global' needs a parameter file the reference does not ship and raises; dem /
-slope inputs raise NotImplementedError exactly as the reference does (:107-115)."""
+(base_dataset.py:494-555); norm_mode 'global' takes its parameters from the `norm_params` keyword (the reference's
+pickle {dset_name: {sensor: {"mean", "std"}}}, as a path or as the dict it holds; `datasets.stats` computes and writes
+it) instead of a file beside the package (datasets/utils.py:215-230), and raises without them; dem / slope inputs raise
+NotImplementedError exactly as the reference does (:107-115)."""
 from __future__ import annotations
 
 import os
@@ -65,15 +67,15 @@ class FloodplanetTiles(torch.utils.data.Dataset):
     def __init__(self, root_dir, split, slice_params, eval_region=None, transforms=None, sensor="PS", channels=None,
                  dset_name="floodplanet", seed_num=0, output_metadata=False, norm_mode=None, dem=False, slope=False,
                  preflood=False, pre_post_difference=False, chirps=False, hand=False, ignore_index=-1,
-                 train_split_pct=0.8):
+                 train_split_pct=0.8, norm_params=None):
         if transforms is not None:
             raise NotImplementedError("per-item CPU transforms are replaced by the batched GPU augmentation "
                                       "(floodplanet_code_amd.augment); pass transforms=None")
         if train_split_pct < 0 or train_split_pct > 1:
             raise ValueError(f"Train split pct must be between 0 and 1. Invalid value: {train_split_pct}")
-        if norm_mode == "global":
+        if norm_mode == "global" and norm_params is None:
             raise NotImplementedError("norm_mode 'global' needs the dataset's parameter file, which is not bundled")
-        if norm_mode not in (None, "local"):
+        if norm_mode not in (None, "local", "global"):
             raise NotImplementedError(f'Normalization mode "{norm_mode}" not implemented.')
         self.channels = "ALL" if channels is None else channels
         self.split, self.sensor, self.root_dir, self.seed_num = split, sensor, root_dir, seed_num
@@ -91,6 +93,11 @@ class FloodplanetTiles(torch.utils.data.Dataset):
             np.random.seed(seed_num)
         self._prepare_data(sensor)
         self.n_channels = self._get_n_channels()
+        self.global_norm_params = None
+        if norm_mode == "global":          # base_dataset.py:58-60; looked up by dset_name, then by sensor
+            from .stats import sensor_norm_params
+            mean, std = sensor_norm_params(norm_params, dset_name, sensor, self.n_channels["ms_image"])
+            self.global_norm_params = {sensor: {"mean": mean, "std": std}}
 
     # ---- example list (floodplanet.py:72-139) ------------------------------------------------------------------
     def _prepare_data(self, sensor_name):
@@ -255,6 +262,15 @@ class FloodplanetTiles(torch.utils.data.Dataset):
         return out
 
     def normalize(self, image):
+        if self.norm_mode == "global":
+            # base_dataset.py:91-94, 109-110: fp64 parameters, `image -= mean; image /= std` in place on the fp32 image
+            # (each step computed in fp64 and rounded to fp32); on a copy, the crop may alias the cached raster
+            gp = self.global_norm_params[self.sensor]
+            mean, std = gp["mean"][:, None, None], gp["std"][:, None, None]
+            image = np.array(image, dtype=np.float32)
+            np.subtract(image, mean, out=image, casting="same_kind")
+            np.divide(image, std, out=image, casting="same_kind")
+            return image, mean, std
         if self.norm_mode == "local":
             flat = image.reshape(image.shape[0], -1)
             mean, std = flat.mean(axis=1)[:, None, None], flat.std(axis=1)[:, None, None]

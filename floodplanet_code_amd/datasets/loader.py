@@ -64,7 +64,11 @@ class TileLoader:
             raw = batch["raw"].to(self.device, non_blocking=True)
         vh = batch["valid_h"].to(self.device, non_blocking=True)
         vw = batch["valid_w"].to(self.device, non_blocking=True)
-        image, mean, std = assemble_tiles([raw], self.dataset.norm_mode, (vh, vw))
+        gp = None
+        if self.dataset.norm_mode == "global":       # the kernel takes fp32 parameters: the fp64 ones are rounded once
+            p = self.dataset.global_norm_params[self.dataset.sensor]
+            gp = (torch.from_numpy(p["mean"]).float(), torch.from_numpy(p["std"]).float())
+        image, mean, std = assemble_tiles([raw], self.dataset.norm_mode, (vh, vw), gp)
         out = {"image": image, "mean": mean, "std": std, "target": batch["target"].to(self.device, non_blocking=True)}
         if "metadata" in batch:
             out["metadata"] = batch["metadata"]

@@ -183,12 +183,15 @@ class SceneFiles(torch.utils.data.Dataset):
                 "index": i}
 
 
-def check_model_inputs(cfg: dict) -> None:
-    """infer feeds the model ms_image only: reject configs whose model also takes dem / slope / ... (before any GPU work)."""
+def check_model_inputs(cfg: dict, norm_params=None) -> None:
+    """infer feeds the model ms_image only: reject configs whose model also takes dem / slope / ... (before any GPU work).
+    norm_mode 'global' is accepted only together with its parameters."""
     kw = cfg["dataset"].get("dataset_kwargs") or {}
     extra = [k for k in EXTRA_SOURCES if kw.get(k)]
     if extra:
         raise NotImplementedError(f"infer feeds the model the ms_image input only; this model also takes {extra}")
+    if cfg["norm_mode"] == "global" and norm_params is not None:
+        return
     if cfg["norm_mode"] not in (None, "local"):
         raise NotImplementedError(f'infer: norm_mode "{cfg["norm_mode"]}" is not supported (None or "local")')
 
@@ -197,10 +200,12 @@ def check_model_inputs(cfg: dict) -> None:
 def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Optional[dict] = None,
           size: Optional[Sequence[int]] = None, scale: Optional[float] = None, stride: Optional[int] = None,
           batch_size: Optional[int] = None, tta=None, n_workers: int = 0, device: str = "cuda:0",
-          keep_probabilities: bool = False) -> dict:
+          keep_probabilities: bool = False, norm_params=None) -> dict:
     """Class maps of every input scene (see the module docstring).  cfg: the resolved config (default: resolve_cfg of
     the checkpoint's experiment).  Returns the summary.json dict; with keep_probabilities also "probabilities"
-    {output path: fp32 [H, W, k] stitched canvas} (one more host read per scene; for tests and comparisons)."""
+    {output path: fp32 [H, W, k] stitched canvas} (one more host read per scene; for tests and comparisons).
+    norm_params: the parameter file of norm_mode 'global' (path, or the dict it holds; datasets.stats), looked up by the
+    config's data set name and sensor; without it a 'global' config is rejected."""
     from .datasets.floodplanet import _N_CHANNELS
     from .models import build_model
 
@@ -211,11 +216,17 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     cfg = _merge(CONFIG_DEFAULTS, cfg)
     ds_cfg = cfg["dataset"]
     sensor, channels = ds_cfg["sensor"], ds_cfg.get("channels") or "ALL"
-    check_model_inputs(cfg)
+    norm_params = norm_params if norm_params is not None else cfg.get("norm_params")
+    check_model_inputs(cfg, norm_params)
     try:
         n_channels = {"ms_image": _N_CHANNELS[sensor][channels]}
     except KeyError:
         raise NotImplementedError(f'Cannot get number of {sensor} channels for channel query "{channels}"') from None
+    global_params = None
+    if cfg["norm_mode"] == "global":                     # host only: a bad file fails before any GPU work
+        from .datasets.stats import sensor_norm_params
+        gm, gs = sensor_norm_params(norm_params, ds_cfg.get("name") or "floodplanet", sensor, n_channels["ms_image"])
+        global_params = (torch.from_numpy(gm).float(), torch.from_numpy(gs).float())
     ch, cw = int(cfg["crop_height"]), int(cfg["crop_width"])
     stride = int(stride) if stride is not None else min(ch, cw)
     if stride < 1:
@@ -297,7 +308,7 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
             batch, pending = pending[:bs], pending[bs:]
             n = len(batch)
             x, _, _ = scene_crops(net._ctx, [(resident[i]["grid"], b) for i, b in batch], (ch, cw), cfg["norm_mode"],
-                                  out=crop_buf)
+                                  global_params, out=crop_buf)
             probs = None
             if codes is None:
                 net._forward_raw(model._gather_sources({"image": x}), False, want_logits=False)
@@ -341,6 +352,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--n_workers", type=int, default=0,
                     help="scene decoding worker processes (default 0: decode in-process, the faster setting measured)")
     ap.add_argument("--device", type=str, default="cuda:0")
+    ap.add_argument("--norm_params", type=str, default=None,
+                    help="parameter file of norm_mode 'global' (python -m floodplanet_code_amd.datasets.stats writes it)")
     return ap
 
 
@@ -350,7 +363,7 @@ def main(argv: Optional[List[str]] = None) -> None:
     cfg = resolve_cfg(experiment_dir, args.checkpoint_path)
     out = infer(args.checkpoint_path, args.inputs, args.out_dir, cfg=cfg, size=args.size, scale=args.scale,
                 stride=args.stride, batch_size=args.batch_size, tta=args.tta, n_workers=args.n_workers,
-                device=args.device)
+                device=args.device, norm_params=args.norm_params)
     print(json.dumps({k: v for k, v in out.items() if k != "scenes"}))
 
 

@@ -188,7 +188,8 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
     dataset = FloodplanetTiles(data_root, eval_dataset_split, slice_params, eval_region=copy.copy(cfg["eval_region"]),
                                sensor=ds_cfg["sensor"], channels=ds_cfg["channels"], norm_mode=cfg["norm_mode"],
                                ignore_index=cfg["ignore_index"], seed_num=cfg.get("seed_num"), train_split_pct=0.8,
-                               output_metadata=True, **(ds_cfg.get("dataset_kwargs") or {}))
+                               output_metadata=True, norm_params=cfg.get("norm_params"),
+                               **(ds_cfg.get("dataset_kwargs") or {}))
 
     dev = torch.device(device)
     model_kwargs = dict(cfg["model"].get("model_kwargs") or {})
@@ -291,6 +292,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips (hflip, flips) or all eight "
                          "flips / 90-degree rotations (d4, square crops only); default: none")
+    ap.add_argument("--norm_params", type=str, default=None,
+                    help="parameter file of norm_mode 'global' (config key norm_params; "
+                         "python -m floodplanet_code_amd.datasets.stats writes it)")
     return ap
 
 
@@ -300,6 +304,8 @@ def main(argv: Optional[List[str]] = None) -> None:
     cfg = resolve_cfg(experiment_dir, args.checkpoint_path)
     name = args.eval_dataset_name if args.eval_dataset_name is not None else cfg["dataset"]["name"]
     n_workers = args.n_workers if args.n_workers is not None else cfg["n_workers"]
+    if args.norm_params is not None:
+        cfg["norm_params"] = args.norm_params
     out = predict(cfg, experiment_dir, args.checkpoint_path, eval_dataset_name=name, predict_images=args.predict_images,
                   eval_region=args.eval_region, eval_dataset_split=args.eval_dataset_split, n_workers=n_workers,
                   data_root=args.data_root, batch_size=args.batch_size, device=args.device, tta=args.tta)

@@ -261,6 +261,41 @@ int fu_assemble_tiles(const float* const* srcs, const int32_t* src_channels, int
                       const float* global_std, float pad_value, float* out, float* mean_out, float* std_out,
                       fu_stream stream);
 
+/* Streaming per-band statistics of tiles that are already in HBM (added within ABI 5: purely additive, no version bump).
+ * What st_water_seg/misc/compute_dataset_normalization_parameters.py:12-91 gathers on the host (np.concatenate in a loop,
+ * 10 % of the pixels) as one pass over every pixel on the device; also the percentiles of misc/compute_input_feature_stats.py.
+ * The batch is described as for fu_assemble_tiles: srcs = HOST array of n_src (1..8) device pointers, source k fp32 NCHW
+ * [B, src_channels[k], H, W], at most 16 channels in all; the valid crop of sample b is the top-left valid_h[b] x valid_w[b]
+ * corner (device int32 [B], clamped to the tile; NULL = the whole tile).
+ * mask_mode 0: every pixel of the valid crop counts.  mask_mode 1, the reference's rule (:19-24): a pixel counts when the
+ * fp32 sum, in channel order, of the FIRST source's channels at that pixel is not 0; that one mask applies to every source
+ * (the reference uses the image's mask for dem / slope too).  In both modes a pixel where any channel of any source is NaN
+ * or Inf is left out of every channel and counted in n_nonfinite (the reference would return NaN statistics there).
+ * Every field of fu_band_accum is a CALLER-owned device buffer that the call ADDS to, so a data set is streamed through
+ * batch by batch: count / n_nonfinite int64 [C] (every channel gets the same numbers: the mask is per pixel), sum / sumsq
+ * fp64 [C], vmin / vmax fp32 [C] (the caller initialises them to +inf / -inf, the sums and counts to 0), hist int64
+ * [C][n_bins] or NULL (no histogram): n_bins (1..65536) equal bins over [lo, hi], bin = floor((x - lo) * (n_bins / (hi - lo)))
+ * in fp32 with n_bins / (hi - lo) rounded once, values outside go to the edge bins.
+ * Every input element is read once.  The result is bit-reproducible: no floating-point atomics -- per-workgroup fp64
+ * partials go to `workspace` (device memory, 16-byte aligned, >= fu_band_stats_workspace_bytes(C, n_bins or 0); contents
+ * are scratch) and are folded in a fixed order; the histogram is counted with integer atomics in LDS.  Calls that share
+ * accumulators or a workspace must be ordered on one stream.  A rejected call (FU_ERR_INVALID) launches nothing. */
+typedef struct fu_band_accum {
+  int64_t* count;        /* [C] pixels taken */
+  double* sum;           /* [C] */
+  double* sumsq;         /* [C] */
+  float* vmin;           /* [C], +inf before the first call */
+  float* vmax;           /* [C], -inf before the first call */
+  int64_t* n_nonfinite;  /* [C] pixels left out because a channel was NaN / Inf */
+  int64_t* hist;         /* [C][n_bins], or NULL */
+  int32_t n_bins;
+  float lo, hi;
+} fu_band_accum;
+int64_t fu_band_stats_workspace_bytes(int n_channels, int n_bins);
+int fu_band_stats(const float* const* srcs, const int32_t* src_channels, int n_src, int B, int H, int W,
+                  const int32_t* valid_h, const int32_t* valid_w, int mask_mode, const fu_band_accum* acc,
+                  void* workspace, int64_t workspace_bytes, fu_stream stream);
+
 /* Lanczos-4 resampling of a batch of tiles on the device (ABI 5).  Replaces the per-item WHOLE-RASTER resample of the reference's
  * loader (st_water_seg/datasets/floodplanet.py:338-340 -> utils/utils_image.py:11-54, cv2.INTER_LANCZOS4) by a per-tile one:
  * Lanczos is local, so the tile [Y0, Y0 + tile_h) x [X0, X0 + tile_w) of the resampled raster depends only on a window of the
