@@ -608,7 +608,7 @@ __global__ __launch_bounds__(128 * WMI) void k_wgrad_bf16(BWgP P) {
       });
     }
   }
-  // slab[split][tap][Cin / 4][Cout][4] (see k_wgrad_transpose<true>): accumulator registers 4j .. 4j+3 of a lane are c_in
+  // slab[split][tap][Cin / 4][Cout][4] (see k_wgrad_reduce_oihw): accumulator registers 4j .. 4j+3 of a lane are c_in
   // 8j + 4 lh + {0..3} of its c_out -- one 16-byte store, 512 contiguous bytes per 32 lanes
   const int co = co0 + ni * 32 + l31;
   if (co < P.Cout) {
@@ -1263,8 +1263,8 @@ static int launch_wgrad_c8(BWgP& P, int target_wgs, const LaunchOpts& o, hipStre
   return 0;
 }
 
-int launch_wgrad_reduce(const float* slab, int S, int Cin, int Cout, int cin_real, float* dw, const float* dbp,
-                        int ndb, float* db, hipStream_t s, bool ci4);
+int launch_wgrad_reduce_oihw(const float* slab, int S, int Cin, int Cout, int cin_real, float* dw, const float* dbp,
+                             int ndb, float* db, hipStream_t s);
 
 template <int WMI, int PTH, int TAPS = 9>
 static int launch_wgrad_cfg(BWgP& P, int target_wgs, const LaunchOpts& o, hipStream_t s) {
@@ -1383,7 +1383,7 @@ int launch_conv3x3_wgrad_bf16(const ConvIn& in, const bf16_t* dy, int Cout, floa
   else if (P.Cin > 64) st = launch_wgrad_cfg<4, 8>(P, WGRAD_PP_TARGET, in.opt, s);   // (same split as the ping-pong kernel: bit-identical sums)
   else st = launch_wgrad_cfg<2, 8>(P, WGRAD_C64_TARGET, in.opt, s);   // 256 threads, 64 x 64, two WGs per CU
   if (st) return st;
-  return launch_wgrad_reduce(slab, P.S, P.Cin, Cout, cin_real, dw_oihw, db_partials, n_db_partials, db, s, true);
+  return launch_wgrad_reduce_oihw(slab, P.S, P.Cin, Cout, cin_real, dw_oihw, db_partials, n_db_partials, db, s);
 }
 
 }  // namespace fu

@@ -1,0 +1,178 @@
+"""GPU: the one-pass split-K reduce of the 16-bit weight-gradient paths (k_wgrad_reduce_oihw<16 | 4 | 1>: slabs
+[split][tap][c_in / 4][c_out][4] -> dw OIHW) through fu_op_conv3x3_wgrad against torch on the rounded operands, and through
+whole-net steps for what the op entry does not expose (c_in padded for the kernels, the one-tap launches of late fusion)."""
+from collections import OrderedDict
+
+import pytest
+import torch
+
+from floodplanet_code_amd import _lib
+from floodplanet_code_amd._lib import check, ptr
+from floodplanet_code_amd.latefusion import HipLateFusion
+from floodplanet_code_amd.unet import HipUNet
+from oracle import unet_oracle as O
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+LOWP = {"bf16": dict(code=_lib.FU_BF16, dt=torch.bfloat16), "fp16": dict(code=_lib.FU_F16, dt=torch.float16)}
+
+
+@pytest.fixture(params=["bf16", "fp16"])
+def lowp(request):
+    return request.param
+
+
+def rel_err(a, b):
+    return ((a.double() - b.double()).norm() / (b.double().norm() + 1e-30)).item()
+
+
+def ceil_div(a, b):
+    return -(-a // b)
+
+
+def split_count(B, C0, C1, Cout, H, W, bn):
+    """S of launch_conv3x3_wgrad_bf16 for this shape (fu_conv_bf16.hip: launch_wgrad_c8 / launch_wgrad_pp /
+    launch_wgrad_cfg<2, 8>): workgroup target over channel tiles, at most one split per pixel tile, empty splits dropped."""
+    cin = C0 + C1
+    if C0 == 8 and C1 == 0 and not bn and Cout == 64 and H % 8 == 0 and W % 32 == 0:
+        npix, n_t, target = B * (H // 8) * (W // 32), 1, 512                    # k_wgrad_bf16_c8: 8 x 32 pixel tiles
+    elif cin > 64:
+        npix, n_t, target = B * ceil_div(H, 8) * ceil_div(W, 16), ceil_div(cin, 128) * ceil_div(Cout, 64), 160
+    else:
+        npix, n_t, target = B * ceil_div(H, 8) * ceil_div(W, 16), ceil_div(cin, 64) * ceil_div(Cout, 64), 512
+    s = max(1, min(ceil_div(target, n_t), npix))
+    return ceil_div(npix, ceil_div(npix, s))
+
+
+def split_lanes(S):
+    """SL of the reduce for S slabs (fu_conv_f32.hip: launch_wgrad_reduce_oihw)"""
+    return 16 if S >= 64 else 4 if S >= 16 else 1
+
+
+REDUCE_CASES = [
+    # (B, C0, C1, Cout, H, W, bn_prologue), S, SL
+    # SL = 1: the 32 c_out x 4 c_in x 9 tap tiles.  c_out 40 and 72 leave a partial c_out tile, c_in 96 and 192 a partial
+    # 128-channel tile in the weight-gradient kernel; S = 9 runs two rounds of four slabs and a single step, S = 2 and 1
+    # only single steps
+    ((1, 96, 0, 40, 16, 16, False), 2, 1),
+    ((1, 128, 64, 72, 24, 48, True), 9, 1),
+    ((1, 64, 0, 64, 8, 16, True), 1, 1),
+    ((1, 256, 0, 128, 24, 80, False), 15, 1),
+    # SL = 4: 256-element blocks; 9 * 72 * 40 = 25920 elements leave a quarter-filled last block; c_in <= 64 takes the
+    # two-workgroup kernel, 8 -> 64 without BatchNorm the K = 72 stream kernel (c_in / 4 = 2)
+    ((2, 72, 0, 40, 24, 48, False), 18, 4),
+    ((1, 32, 32, 24, 40, 50, True), 20, 4),
+    ((2, 8, 0, 64, 32, 64, False), 16, 4),
+    ((2, 256, 0, 72, 24, 40, True), 18, 4),
+    # SL = 16: 64-element blocks; one round of four slabs per lane and single steps behind it (90, 128), none (64)
+    ((3, 16, 0, 40, 48, 80, True), 90, 16),
+    ((8, 128, 0, 64, 32, 64, False), 128, 16),
+    ((8, 8, 0, 64, 32, 64, False), 64, 16),
+    ((2, 24, 16, 104, 64, 64, True), 64, 16),
+]
+
+
+def test_parameter_table_covers_the_three_regimes():
+    for shape, S, SL in REDUCE_CASES:
+        assert split_count(*shape) == S and split_lanes(S) == SL, (shape, split_count(*shape))
+    assert {SL for _, _, SL in REDUCE_CASES} == {1, 4, 16}
+    assert any(s[3] % 32 for s, _, _ in REDUCE_CASES) and any((s[1] + s[2]) % 128 for s, _, _ in REDUCE_CASES)
+
+
+@pytest.mark.parametrize("shape,S,SL", REDUCE_CASES)
+def test_wgrad_reduce_writes_every_element_of_dw(shape, S, SL, lowp):
+    B, C0, C1, Cout, H, W, bn = shape
+    assert split_count(*shape) == S and split_lanes(S) == SL
+    code, dt = LOWP[lowp]["code"], LOWP[lowp]["dt"]
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(11)
+    x0 = torch.randn(B, C0, H, W, generator=g)
+    x1 = torch.randn(B, C1, H, W, generator=g) if C1 else None
+    a = (torch.rand(C0, generator=g) + 0.5) if bn else None
+    b = (torch.randn(C0, generator=g) * 0.3) if bn else None
+    dy = torch.randn(B, Cout, H, W, generator=g)
+
+    def r(t):
+        return t.to(dt).float()
+
+    xin = r(torch.relu(r(x0) * a.view(1, -1, 1, 1) + b.view(1, -1, 1, 1))) if bn else r(x0)
+    if x1 is not None:
+        xin = torch.cat([xin, r(x1)], 1)
+    ref = torch.nn.grad.conv2d_weight(xin, (Cout, C0 + C1, 3, 3), r(dy), padding=1)
+
+    def dev(t):
+        return t.permute(0, 2, 3, 1).contiguous().to(dt).to(DEV)
+
+    d0, d1, ddy = dev(x0), (dev(x1) if x1 is not None else None), dev(dy)
+    da, db = (a.to(DEV), b.to(DEV)) if bn else (None, None)
+    dw = torch.full((Cout, C0 + C1, 3, 3), float("nan"), device=DEV)
+    check(lib.fu_op_conv3x3_wgrad(code, ptr(d0), C0, ptr(da), ptr(db), ptr(d1), C1, ptr(ddy), Cout, ptr(dw), B, H, W,
+                                  torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    got = dw.cpu()
+    assert not torch.isnan(got).any(), int(torch.isnan(got).sum())
+    e = rel_err(got, ref)
+    print(f"{lowp} {shape} S={S} SL={SL} rel_err={e:.3e}")
+    assert e < 1e-4   # exact products of 16-bit operands, fp32 accumulation
+
+
+def test_padded_first_conv_equals_the_unpadded_net(lowp):
+    """Nine input bands: the kernels run the first conv at c_in = 16 and the reduce writes 9 of them (cin_real < Cin).  The
+    same net declared with 16 bands, the seven extra ones zero in the input and in the weight, computes the same products:
+    the first conv's dw[:, :9] must agree to the tolerance of the op tests, and no weight gradient of either net stays NaN."""
+    base, B, H, W = 64, 2, 64, 64
+    st9 = O.make_state(9, 3, base, True, seed=3)
+    st16 = OrderedDict((k, v.clone()) for k, v in st9.items())
+    k0 = "inc.double_conv.0.weight"
+    st16[k0] = torch.zeros(base, 16, 3, 3)
+    st16[k0][:, :9] = st9[k0]
+    batch = O.make_batch(B, 9, H, W, seed=5)
+    x9 = batch["image"]
+    x16 = torch.zeros(B, 16, H, W)
+    x16[:, :9] = x9
+    grads = []
+    for n_in, st, x in ((9, st9, x9), (16, st16, x16)):
+        net = HipUNet(n_in, 3, base_channels=base, precision=lowp)
+        net.load_state_dict(st)
+        net.to(DEV).train()
+        loss = net.loss(x.to(DEV), batch["target"].to(DEV), 0)
+        net.flat_grads().fill_(float("nan"))
+        loss.backward()
+        torch.cuda.synchronize()
+        for k, p in net.named_parameters():
+            if p.dim() == 4:
+                assert torch.isfinite(p.grad).all(), (n_in, k)
+        grads.append(dict(net.named_parameters())[k0].grad.detach().cpu().clone())
+    assert grads[0].shape == (base, 9, 3, 3) and grads[0].abs().max() > 0
+    e = rel_err(grads[0], grads[1][:, :9])
+    print(f"{lowp} padded first conv rel_err={e:.3e}")
+    assert e < 1e-4
+
+
+def test_one_tap_launches_of_late_fusion_reach_the_fusion_gradients(lowp):
+    """center_only launches (k_wgrad_bf16<4, 8, 1> / <2, 8, 1>) write the centre tap's slab only: the fusion convs'
+    gradients, read from that tap, are finite and point along the fp32 oracle's (the bound the late-fusion suite states for
+    bf16), as is every other weight gradient of the step."""
+    in_ch = OrderedDict([("ms_image", 4), ("dem", 1), ("slope", 1)])
+    st = O.lf_make_state(in_ch, 3, 64, seed=3)
+    batch = O.make_batch(1, 4, 32, 32, seed=6, extra=("dem", "slope"))
+    st_o = {k: v.clone() for k, v in st.items()}
+    _, _, grads_o = O.lf_loss_and_grads(st_o, batch, in_ch, 0)
+    net = HipLateFusion(in_ch, 3, base_channels=64, precision=lowp)
+    net.load_state_dict(st)
+    net = net.to(DEV).train()
+    x = torch.cat([batch[O.LF_BATCH_KEY.get(k, k)] for k in net.encoder_names], dim=1).to(DEV)
+    loss = net.loss(x, batch["target"].to(DEV), 0)
+    net.flat_grads().fill_(float("nan"))
+    loss.backward()
+    torch.cuda.synchronize()
+    g = {n: p.grad.detach().cpu() for n, p in net.named_parameters()}
+    for k, v in g.items():
+        if v.dim() == 4:
+            assert torch.isfinite(v).all(), k
+    k = "concat_convs.4.weight"
+    a, b = g[k].double().reshape(-1), grads_o[k].double().reshape(-1)
+    cos = (a @ b / (a.norm() * b.norm())).item()
+    print(f"{lowp} {k} cosine={cos:.4f}")
+    assert cos >= 0.9
