@@ -66,6 +66,22 @@ class FuSceneCrop(C.Structure):
     ]
 
 
+class FuSceneTrainEntry(C.Structure):
+    """fu_scene_train_entry (include/floodunet.h): one box, its label raster and its transforms for fu_scene_train_tiles."""
+    _fields_ = [
+        ("scene", C.c_void_p),
+        ("label", C.c_void_p),
+        ("scene_h", C.c_int32),
+        ("scene_w", C.c_int32),
+        ("h0", C.c_int32),
+        ("w0", C.c_int32),
+        ("hE", C.c_int32),
+        ("wE", C.c_int32),
+        ("flags", C.c_int32),
+        ("angle_deg", C.c_float),
+    ]
+
+
 class FuBandAccum(C.Structure):
     """fu_band_accum (include/floodunet.h): the caller-owned device accumulators of fu_band_stats."""
     _fields_ = [
@@ -135,6 +151,8 @@ SIGNATURES = {
     "fu_stitch_add_batch_probs": (_i, [_p, _i, C.POINTER(FuStitchEntry), _p, _i, _p]),
     "fu_augment": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i64, _p]),
     "fu_scene_crops": (_i, [_p, _i, C.POINTER(FuSceneCrop), _i, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p]),
+    "fu_scene_train_tiles": (_i, [_p, _i, C.POINTER(FuSceneTrainEntry), _i, _i, _i, _i, _p, _p, _f, _i64, _i64, _p, _p, _p, _p,
+                                  _p]),
     "fu_resize_lanczos4_tiles": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "fu_assemble_tiles": (_i, [C.POINTER(_p), C.POINTER(C.c_int32), _i, _i, _i, _i, _p, _p, _i, _p, _p, _f, _p, _p, _p, _p]),
     "fu_band_stats_workspace_bytes": (_i64, [_i, _i]),

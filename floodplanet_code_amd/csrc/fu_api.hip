@@ -383,6 +383,8 @@ struct fu_ctx {
   int stitch_cap = 0;
   SceneCropJob* scene_jobs = nullptr; // fu_scene_crops: device copy of the last table (grown on demand, owned)
   int scene_cap = 0;
+  void* train_tab = nullptr;          // fu_scene_train_tiles: device copy of the last table, boxes then transforms (owned)
+  int train_cap = 0;
   float* adam_m = nullptr;        // bound (caller-owned, fu_bind_adam_state): the moments outlive the context
   float* adam_v = nullptr;
   Profiler prof;
@@ -1183,6 +1185,7 @@ int fu_destroy(fu_ctx* c) {
   for (void* p : c->extra_allocs) (void)hipFree(p);
   if (c->stitch_jobs) (void)hipFree(c->stitch_jobs);
   if (c->scene_jobs) (void)hipFree(c->scene_jobs);
+  if (c->train_tab) (void)hipFree(c->train_tab);
   delete c;
   return FU_OK;
 }
@@ -1712,6 +1715,67 @@ int fu_scene_crops(fu_ctx* c, int n, const fu_scene_crop* entries, int C, int ti
   FU_HIP_CHECK(hipMemcpyAsync(c->scene_jobs, jobs.data(), (size_t)n * sizeof(SceneCropJob), hipMemcpyHostToDevice, s));
   return launch_scene_crops(c->scene_jobs, n, C, tile_h, tile_w, norm_mode, global_mean, global_std, pad_value, out,
                             mean_out, std_out, s);
+}
+
+int fu_scene_train_tiles(fu_ctx* c, int n, const fu_scene_train_entry* entries, int C, int tile_h, int tile_w, int norm_mode,
+                         const float* global_mean, const float* global_std, float pad_value, int64_t nodata_value,
+                         int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out, float* std_out,
+                         fu_stream stream) {
+  // every check before anything is launched or copied: a rejected call leaves the stream untouched
+  FU_REQUIRE(c && entries && image_out, "fu_scene_train_tiles: null context / entries / image_out");
+  FU_REQUIRE(n >= 1 && C >= 1 && tile_h >= 1 && tile_w >= 1,
+             "fu_scene_train_tiles: n = %d, C = %d, tile %dx%d (all must be >= 1)", n, C, tile_h, tile_w);
+  FU_REQUIRE(norm_mode >= 0 && norm_mode <= 2, "fu_scene_train_tiles: norm_mode must be 0 (None), 1 ('local') or 2 "
+             "('global'), got %d", norm_mode);
+  FU_REQUIRE(norm_mode != 1 || (mean_out && std_out), "fu_scene_train_tiles: norm_mode 'local' needs mean_out / std_out "
+             "[n, C]");
+  FU_REQUIRE(norm_mode != 2 || (global_mean && global_std), "fu_scene_train_tiles: norm_mode 'global' needs the per-channel "
+             "parameters");
+  // fu_scene_crops' bounds, with the target plane counted; the kernel's grid.y walks a plane 1024 pixel runs at a time, so
+  // 2^25 pixels (32768 rows of blocks with one pixel per run) stay inside the 65535 a launch accepts
+  FU_REQUIRE((int64_t)n * (C + 1) <= INT32_MAX && (int64_t)n * C * tile_h * tile_w <= ((int64_t)1 << 40) &&
+             (int64_t)tile_h * tile_w <= ((int64_t)1 << 25),
+             "fu_scene_train_tiles: %d boxes of %d channels, tile %dx%d, are too many for one call", n, C, tile_h, tile_w);
+  const size_t crop_bytes = (size_t)n * sizeof(SceneCropJob);
+  std::vector<unsigned char> table(crop_bytes + (size_t)n * sizeof(SceneTrainAug));
+  SceneCropJob* jobs = reinterpret_cast<SceneCropJob*>(table.data());
+  SceneTrainAug* augs = reinterpret_cast<SceneTrainAug*>(table.data() + crop_bytes);
+  for (int i = 0; i < n; ++i) {
+    const fu_scene_train_entry& E = entries[i];
+    const int dh = E.hE - E.h0, dw = E.wE - E.w0;
+    FU_REQUIRE(E.scene, "fu_scene_train_tiles: entry %d: null scene", i);
+    FU_REQUIRE(!target_out || E.label, "fu_scene_train_tiles: entry %d: target_out given but the entry has no label", i);
+    FU_REQUIRE(E.scene_h >= 1 && E.scene_w >= 1, "fu_scene_train_tiles: entry %d: bad scene size %dx%d", i, E.scene_h,
+               E.scene_w);
+    FU_REQUIRE(E.h0 >= 0 && E.w0 >= 0 && E.hE <= E.scene_h && E.wE <= E.scene_w,
+               "fu_scene_train_tiles: entry %d: box [%d:%d, %d:%d] lies outside its scene %dx%d", i, E.h0, E.hE, E.w0, E.wE,
+               E.scene_h, E.scene_w);
+    FU_REQUIRE(dh >= 1 && dw >= 1, "fu_scene_train_tiles: entry %d: box [%d:%d, %d:%d] is empty", i, E.h0, E.hE, E.w0, E.wE);
+    FU_REQUIRE(dh <= tile_h && dw <= tile_w, "fu_scene_train_tiles: entry %d: box %dx%d is larger than the tile %dx%d", i,
+               dh, dw, tile_h, tile_w);
+    FU_REQUIRE((E.flags & ~(FU_AUG_HFLIP | FU_AUG_VFLIP | FU_AUG_ROTATE)) == 0,
+               "fu_scene_train_tiles: entry %d: unknown flag bits 0x%x", i, (unsigned)E.flags);
+    FU_REQUIRE(std::isfinite(E.angle_deg), "fu_scene_train_tiles: entry %d: the angle is not finite", i);
+    jobs[i] = SceneCropJob{E.scene, E.scene_h, E.scene_w, E.h0, E.w0, dh, dw};
+    augs[i] = SceneTrainAug{E.label, E.flags, E.angle_deg};
+  }
+  const hipStream_t s = (hipStream_t)stream;
+  if (n > c->train_cap) {
+    if (c->train_tab) {
+      FU_HIP_CHECK(hipDeviceSynchronize());     // an earlier launch may still read the old table
+      FU_HIP_CHECK(hipFree(c->train_tab));
+      c->train_tab = nullptr;
+      c->train_cap = 0;
+    }
+    const int cap = std::max(n, 64);
+    FU_HIP_CHECK(hipMalloc(&c->train_tab, (size_t)cap * (sizeof(SceneCropJob) + sizeof(SceneTrainAug))));
+    c->train_cap = cap;
+  }
+  FU_HIP_CHECK(hipMemcpyAsync(c->train_tab, table.data(), table.size(), hipMemcpyHostToDevice, s));
+  return launch_scene_train_tiles(reinterpret_cast<const SceneCropJob*>(c->train_tab),
+                                  reinterpret_cast<const SceneTrainAug*>((const unsigned char*)c->train_tab + crop_bytes), n,
+                                  C, tile_h, tile_w, norm_mode, global_mean, global_std, pad_value, nodata_value,
+                                  target_fill, image_out, target_out, mean_out, std_out, s);
 }
 
 int64_t fu_band_stats_workspace_bytes(int n_channels, int n_bins) {

@@ -444,6 +444,18 @@ struct SceneCropJob {
 // in the top-left corner (valid size = the box) -- the same kernels, instantiated on scene-box addressing
 int launch_scene_crops(const SceneCropJob* jobs_dev, int n, int C, int H, int W, int norm_mode, const float* gmean,
                        const float* gstd, float pad_value, float* out, float* mean_out, float* std_out, hipStream_t s);
+// what fu_scene_train_tiles adds to box b of a SceneCropJob table: the scene's raw label raster and the sample's transforms
+struct SceneTrainAug {
+  const uint8_t* label;  // uint8 [scene_h, scene_w], or nullptr (no target)
+  int flags;             // FU_AUG_*
+  float angle;           // degrees
+};
+// fu_scene_train_tiles: launch_scene_crops composed with launch_augment and the label decode, with no batch in between;
+// tiles of at most 2^25 pixels: grid.y = ceil(runs / 1024) <= 32768 (the callers have checked the arguments)
+int launch_scene_train_tiles(const SceneCropJob* jobs_dev, const SceneTrainAug* augs_dev, int n, int C, int H, int W,
+                             int norm_mode, const float* gmean, const float* gstd, float pad_value, int64_t nodata_value,
+                             int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out, float* std_out,
+                             hipStream_t s);
 // fu_band_stats: the caller's per-channel accumulators (all ADDED to) and the histogram's geometry
 struct BandAccum {
   int64_t* count; double* sum; double* sumsq; float* vmin; float* vmax; int64_t* n_nonfinite;

@@ -2146,6 +2146,194 @@ int launch_scene_crops(const SceneCropJob* jobs_dev, int n, int C, int H, int W,
 }
 
 // ------------------------------------------------------------------------------------------------
+// Training batches straight from resident scenes (fu_scene_train_tiles): k_assemble_tiles<ScenePlanes> composed with
+// k_augment, and the label decode of FloodplanetTiles._load_label_image, in one pass -- no crop batch is written to HBM
+// and read back.  A block owns one plane (sample b, channel c -- or the sample's target plane) and a run of its pixels;
+// a thread owns PX consecutive pixels of a row at a time and walks the plane, so its stores and those of its wave are
+// contiguous along x (PX = 4: one 16-byte store per image quad, two per int64 target quad; PX = 1 when tile_w % 4 != 0).
+// The flags are uniform per block: samples without the rotate flag take the row copy / reversal loop (16-byte loads too
+// where the source quad is aligned), the others the gather loop with sin / cos evaluated once per thread.  Same fp32
+// operations in the same order as the two kernels it replaces, so the outputs are the same bits.
+// ------------------------------------------------------------------------------------------------
+// the source pixel of output (ox, oy) under rotate: k_augment's arithmetic, operation for operation
+__device__ __forceinline__ bool rotate_source(int ox, int oy, float cs, float sn, int H, int W, int& sx, int& sy) {
+#pragma clang fp contract(off)
+  const float xc = ((float)ox + 0.5f) - 0.5f * (float)W, yc = ((float)oy + 0.5f) - 0.5f * (float)H;
+  const float px = cs * xc, qx = sn * yc, py = sn * xc, qy = cs * yc;
+  const float xs = ((px - qx) + 0.5f * (float)W) - 0.5f;
+  const float ys = ((py + qy) + 0.5f * (float)H) - 0.5f;
+  sx = (int)nearbyintf(xs);
+  sy = (int)nearbyintf(ys);
+  return sx >= 0 && sx < W && sy >= 0 && sy < H;
+}
+
+// (x - mean) / std as k_assemble_tiles rounds it: two operations, two roundings
+__device__ __forceinline__ float normalise(float v, bool norm, float m, float sd) {
+#pragma clang fp contract(off)
+  if (norm) {
+    const float d = v - m;
+    v = d / sd;
+  }
+  return v;
+}
+
+// raw label value -> class (floodplanet.py:586-596): 2 flood -> 1, 0 no data -> nodata_value, anything else -> 0
+__device__ __forceinline__ int64_t decode_label(uint8_t raw, int64_t nodata_value) {
+  return raw == 2 ? (int64_t)1 : (raw == 0 ? nodata_value : (int64_t)0);
+}
+
+template <int PX>
+__device__ __forceinline__ void store_px(float* __restrict__ o, const float (&v)[PX]) {
+  if constexpr (PX == 4) *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+  else o[0] = v[0];
+}
+template <int PX>
+__device__ __forceinline__ void store_px(int64_t* __restrict__ o, const int64_t (&v)[PX]) {
+  if constexpr (PX == 4) {
+    reinterpret_cast<longlong2*>(o)[0] = make_longlong2(v[0], v[1]);
+    reinterpret_cast<longlong2*>(o)[1] = make_longlong2(v[2], v[3]);
+  } else {
+    o[0] = v[0];
+  }
+}
+
+static constexpr int STT_RUNS = 4;     // pixel runs of PX per thread: a block covers 256 * STT_RUNS * PX pixels of its plane
+
+template <int PX>
+__global__ __launch_bounds__(256) void k_scene_train_tiles(const SceneCropJob* __restrict__ jobs,
+                                                           const SceneTrainAug* __restrict__ augs, int C, int H, int W,
+                                                           const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                           int per_sample, float pad_value, int64_t nodata_value,
+                                                           int64_t target_fill, float* __restrict__ img_o,
+                                                           int64_t* __restrict__ tgt_o) {
+  const int planes = C + (tgt_o ? 1 : 0);
+  const int b = blockIdx.x / planes, p = blockIdx.x - b * planes;
+  const SceneCropJob J = jobs[b];
+  const SceneTrainAug A = augs[b];
+  const int QW = W / PX, nq = H * QW;        // PX = 4 only where W % 4 == 0
+  const int q0 = blockIdx.y * (256 * STT_RUNS);
+  const int q1 = min(q0 + 256 * STT_RUNS, nq);
+  const bool is_target = p == C;
+  const bool hf = A.flags & 1, vf = A.flags & 2;
+  // the plane this block reads, from the box's first pixel, and the plane it writes
+  const int64_t box = (int64_t)J.h0 * J.scene_w + J.w0;
+  const float* __restrict__ src = J.scene + (int64_t)(is_target ? 0 : p) * J.scene_h * J.scene_w + box;
+  const uint8_t* __restrict__ lab = A.label ? A.label + box : nullptr;
+  float* __restrict__ io = img_o + ((int64_t)b * C + (is_target ? 0 : p)) * H * W;
+  int64_t* __restrict__ to = tgt_o ? tgt_o + (int64_t)b * H * W : nullptr;
+  const bool norm = mean != nullptr;
+  float m = 0.f, sd = 1.f;
+  if (norm && !is_target) {
+    const int mi = per_sample ? b * C + p : p;
+    m = mean[mi];
+    sd = stdv[mi];
+  }
+
+  if (A.flags & 4) {                          // gather: every pixel has its own source
+    float cs, sn;
+    {
+#pragma clang fp contract(off)
+      const float th = A.angle * 0.017453292519943295f;
+      cs = (float)cos((double)th);
+      sn = (float)sin((double)th);
+    }
+    for (int q = q0 + (int)threadIdx.x; q < q1; q += 256) {
+      const int oy = q / QW, x0 = (q - oy * QW) * PX;
+      int sx[PX], sy[PX];
+      bool in_tile[PX], in_box[PX];
+#pragma unroll
+      for (int j = 0; j < PX; ++j) {
+        in_tile[j] = rotate_source(x0 + j, oy, cs, sn, H, W, sx[j], sy[j]);
+        if (vf) sy[j] = H - 1 - sy[j];        // the rotate input is the v-flipped, h-flipped tile
+        if (hf) sx[j] = W - 1 - sx[j];
+        in_box[j] = in_tile[j] && sy[j] < J.dh && sx[j] < J.dw;
+      }
+      if (is_target) {
+        int64_t v[PX];
+#pragma unroll
+        for (int j = 0; j < PX; ++j)
+          v[j] = in_box[j] ? decode_label(lab[(int64_t)sy[j] * J.scene_w + sx[j]], nodata_value) : target_fill;
+        store_px<PX>(to + (int64_t)oy * W + x0, v);
+      } else {
+        float v[PX];
+#pragma unroll
+        for (int j = 0; j < PX; ++j)
+          v[j] = in_box[j] ? normalise(src[(int64_t)sy[j] * J.scene_w + sx[j]], norm, m, sd)
+                           : (in_tile[j] ? pad_value : 0.f);
+        store_px<PX>(io + (int64_t)oy * W + x0, v);
+      }
+    }
+    return;
+  }
+
+  // no rotation: output row oy is source row oy (or its mirror), copied or reversed
+  for (int q = q0 + (int)threadIdx.x; q < q1; q += 256) {
+    const int oy = q / QW, x0 = (q - oy * QW) * PX;
+    const int sy = vf ? H - 1 - oy : oy;
+    const int lo = hf ? W - PX - x0 : x0;     // source x of the run's lowest address; output j reads lo + (PX - 1 - j) if hf
+    const bool row_in = sy < J.dh;
+    const int64_t off = (int64_t)sy * J.scene_w + lo;
+    if (is_target) {
+      int64_t s[PX], v[PX];
+#pragma unroll
+      for (int k = 0; k < PX; ++k) s[k] = row_in && lo + k < J.dw ? decode_label(lab[off + k], nodata_value) : target_fill;
+#pragma unroll
+      for (int j = 0; j < PX; ++j) v[j] = hf ? s[PX - 1 - j] : s[j];
+      store_px<PX>(to + (int64_t)oy * W + x0, v);
+    } else {
+      float s[PX], v[PX];
+      bool wide = false;
+      if constexpr (PX == 4) {
+        wide = row_in && lo + 3 < J.dw && (reinterpret_cast<uintptr_t>(src + off) & 15) == 0;
+        if (wide) {
+          const float4 t = *reinterpret_cast<const float4*>(src + off);
+          s[0] = t.x; s[1] = t.y; s[2] = t.z; s[3] = t.w;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) s[k] = normalise(s[k], norm, m, sd);
+        }
+      }
+      if (!wide) {
+#pragma unroll
+        for (int k = 0; k < PX; ++k) s[k] = row_in && lo + k < J.dw ? normalise(src[off + k], norm, m, sd) : pad_value;
+      }
+#pragma unroll
+      for (int j = 0; j < PX; ++j) v[j] = hf ? s[PX - 1 - j] : s[j];
+      store_px<PX>(io + (int64_t)oy * W + x0, v);
+    }
+  }
+}
+
+int launch_scene_train_tiles(const SceneCropJob* jobs_dev, const SceneTrainAug* augs_dev, int n, int C, int H, int W,
+                             int norm_mode, const float* gmean, const float* gstd, float pad_value, int64_t nodata_value,
+                             int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out, float* std_out,
+                             hipStream_t s) {
+  const float *mean = nullptr, *stdv = nullptr;
+  int per_sample = 0;
+  if (norm_mode == 1) {                       // the statistics of the un-augmented crop: fu_scene_crops' own kernel
+    ScenePlanes P;
+    P.jobs = jobs_dev;
+    hipLaunchKernelGGL(k_tile_stats<ScenePlanes>, dim3(n * C), dim3(256), 0, s, P, C, mean_out, std_out);
+    FU_LAUNCH_CHECK();
+    mean = mean_out; stdv = std_out; per_sample = 1;
+  } else if (norm_mode == 2) {
+    mean = gmean; stdv = gstd;
+  }
+  const int planes = C + (target_out ? 1 : 0);
+  const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(image_out) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(target_out) & 15) == 0;
+  const int64_t nq = (int64_t)H * (vec ? W / 4 : W);
+  const dim3 grid((unsigned)(n * planes), (unsigned)ceil_div64(nq, (int64_t)256 * STT_RUNS));
+  if (vec)
+    hipLaunchKernelGGL(k_scene_train_tiles<4>, grid, dim3(256), 0, s, jobs_dev, augs_dev, C, H, W, mean, stdv, per_sample,
+                       pad_value, nodata_value, target_fill, image_out, target_out);
+  else
+    hipLaunchKernelGGL(k_scene_train_tiles<1>, grid, dim3(256), 0, s, jobs_dev, augs_dev, C, H, W, mean, stdv, per_sample,
+                       pad_value, nodata_value, target_fill, image_out, target_out);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Streaming per-band statistics of tiles in HBM (fu_band_stats): what misc/compute_dataset_normalization_parameters.py
 // gathers on the host with np.concatenate in a loop -- count, sum, sum of squares, min, max, a histogram and the count of
 // non-finite pixels per channel, ADDED to caller-owned accumulators so that a data set streams through batch by batch.

@@ -99,6 +99,63 @@ def scene_crops(ctx, boxes, tile_hw: Tuple[int, int], norm_mode: Optional[str] =
     return out[:n], mean.view(n, Cc, 1, 1), std.view(n, Cc, 1, 1)
 
 
+def scene_train_tiles(ctx, entries, tile_hw: Tuple[int, int], norm_mode: Optional[str] = None,
+                      global_params: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pad_value: float = 0.0,
+                      nodata_value: int = 0, target_fill: int = 0, out=None):
+    """C ABI fu_scene_train_tiles: entries = [(scene, label, (h0, w0, hE, wE), flags, angle_deg), ...] -- scene a contiguous
+    fp32 [C, H_s, W_s] on the ROCm device, label the scene's raw uint8 [H_s, W_s] label raster there (None for every entry:
+    no target), the box inside the scene and at most tile_hw, flags / angle as augment.sample_transforms draws them.
+    -> (image [n, C, th, tw], target int64 [n, th, tw] or None, mean, std [n, C, 1, 1]): bit for bit scene_crops followed
+    by augment.apply on the decoded label boxes, in one launch (two with 'local') and without the batch in between.
+    global_params: fp32 tensors; pass them on the device to keep the call free of host-to-device copies.
+    out: optional (image, target, mean, std) buffers of those shapes (mean / std [n, C]) to write into."""
+    if norm_mode not in NORM_MODES:
+        raise NotImplementedError(f'Normalization mode "{norm_mode}" not implemented.')
+    n = len(entries)
+    if n == 0:
+        raise ValueError("scene_train_tiles: no entries")
+    if ctx is None:
+        raise ValueError("scene_train_tiles: no fu_ctx (run or prepare a forward first)")
+    th, tw = int(tile_hw[0]), int(tile_hw[1])
+    dev = entries[0][0].device
+    Cc = entries[0][0].shape[0]
+    with_target = entries[0][1] is not None
+    table = (_lib.FuSceneTrainEntry * n)()
+    for i, (scene, label, (h0, w0, hE, wE), flags, angle) in enumerate(entries):
+        if scene.dim() != 3 or scene.shape[0] != Cc or scene.dtype != torch.float32 or not scene.is_contiguous() \
+                or scene.device != dev or dev.type != "cuda":
+            raise ValueError(f"scene_train_tiles: entry {i}: scenes must be contiguous fp32 [{Cc}, H, W] on one ROCm device, "
+                             f"got {tuple(scene.shape)} {scene.dtype} on {scene.device}")
+        if (label is not None) != with_target:
+            raise ValueError("scene_train_tiles: either every entry has a label raster or none has")
+        if label is not None and (label.dtype != torch.uint8 or tuple(label.shape) != tuple(scene.shape[1:])
+                                  or not label.is_contiguous() or label.device != dev):
+            raise ValueError(f"scene_train_tiles: entry {i}: the label must be contiguous uint8 {tuple(scene.shape[1:])} on "
+                             f"{dev}, got {tuple(label.shape)} {label.dtype} on {label.device}")
+        table[i] = _lib.FuSceneTrainEntry(scene.data_ptr(), ptr(label), scene.shape[1], scene.shape[2], int(h0), int(w0),
+                                          int(hE), int(wE), int(flags), float(angle))
+    mode = NORM_MODES[norm_mode]
+    if out is not None:
+        image, target, mean, std = out
+    else:
+        image = torch.empty(n, Cc, th, tw, dtype=torch.float32, device=dev)
+        target = torch.empty(n, th, tw, dtype=torch.int64, device=dev) if with_target else None
+        mean = torch.zeros(n, Cc, dtype=torch.float32, device=dev)
+        std = torch.ones(n, Cc, dtype=torch.float32, device=dev)
+    gm = gs = None
+    if mode == 2:
+        if global_params is None:
+            raise ValueError("norm_mode 'global' needs (mean, std) per channel")
+        gm, gs = (t.to(dev).float().contiguous() for t in global_params)
+        mean[:] = gm
+        std[:] = gs
+    check(_lib.load().fu_scene_train_tiles(ctx, n, table, Cc, th, tw, mode, ptr(gm), ptr(gs), float(pad_value),
+                                           int(nodata_value), int(target_fill), ptr(image),
+                                           ptr(target) if with_target else None, ptr(mean) if mode == 1 else None,
+                                           ptr(std) if mode == 1 else None, torch.cuda.current_stream(dev).cuda_stream))
+    return image, (target if with_target else None), mean.view(n, Cc, 1, 1), std.view(n, Cc, 1, 1)
+
+
 def resize_lanczos4_tiles(windows: torch.Tensor, iy: torch.Tensor, wy: torch.Tensor, ix: torch.Tensor, wx: torch.Tensor,
                           scale_mode: int = 0) -> torch.Tensor:
     """C ABI fu_resize_lanczos4_tiles: windows fp32 [B, C, wh, ww] + the tap tables of `resize.lanczos4_axis_window`

@@ -1,0 +1,209 @@
+"""Training batches cut from scenes that live on the device.
+
+TileLoader streams: DataLoader workers decode, cut windows and build tap tables per tile and per step, and the device then
+runs three passes over each batch (resample, assemble, augment).  A FloodPlanet data set fits the card many times over, so
+SceneTileLoader does what infer.py does for inference: every raster of the data set's example list is decoded ONCE, uploaded
+once and resampled once to its label raster's grid (infer.resident_grid: a crop of that grid is the tile
+TileLoader(device_resize=True) makes), the raw uint8 label raster is uploaded beside it, and from then on a batch is one
+table of boxes and transforms and one fu_scene_train_tiles launch (two with norm_mode 'local') that crops, normalises, pads,
+decodes the labels and applies hflip / vflip / rotate in a single pass.  No tensor enters or leaves the device per step.
+
+What stays on the host: the epoch's order (plan_epoch), the draw of the transforms (augment.sample_transforms, the numpy
+stream TileLoader uses) and the table itself.  What it does not do: stream scenes in and out of HBM -- a data set that
+exceeds the residency budget raises SceneResidencyError; TileLoader is the streaming loader."""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+__all__ = ["SceneTileLoader", "SceneResidencyError", "epoch_order", "plan_epoch", "resident_bytes"]
+
+FREE_MEMORY_FRACTION = 0.5       # default max_resident_bytes: this share of the device's free memory at construction
+
+
+class SceneResidencyError(RuntimeError):
+    """The data set's scenes do not fit the residency budget."""
+
+
+# ------------------------------------------------------------------------------------------------------- epoch planner
+def epoch_order(n_items: int, shuffle: bool, seed: int, epoch: int) -> List[int]:
+    """Data-set order, or with shuffle the (epoch + 1)-th permutation a torch.Generator seeded with `seed` draws: a fresh
+    permutation per epoch, the same for the same seed."""
+    if not shuffle:
+        return list(range(n_items))
+    g = torch.Generator().manual_seed(int(seed))
+    perm = None
+    for _ in range(int(epoch) + 1):
+        perm = torch.randperm(n_items, generator=g)
+    return perm.tolist()
+
+
+def plan_epoch(n_items: int, batch_size: int, epoch: int = 0, shuffle: bool = False, seed: int = 0,
+               drop_last: bool = False, shard: Optional[Tuple[int, int]] = None) -> List[List[int]]:
+    """The batches (lists of data-set indices) of one epoch.  shard = (rank, world): the rank's strided share of the epoch's
+    order, cut to len(order) // world items so that every rank runs the same number of steps (the tail of fewer than
+    `world` items is dropped)."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    order = epoch_order(n_items, shuffle, seed, epoch)
+    if shard is not None:
+        rank, world = int(shard[0]), int(shard[1])
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f"shard = (rank, world) with 0 <= rank < world, got {tuple(shard)}")
+        order = order[rank::world][:len(order) // world]
+    batches = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+    if drop_last and batches and len(batches[-1]) < batch_size:
+        batches.pop()
+    return batches
+
+
+# ------------------------------------------------------------------------------------------------------- residency
+def _scene_list(dataset) -> List[Tuple[str, str, int, int]]:
+    """(image path, label path, label height, label width) of every raster the example list names, in order of first use."""
+    seen, out = set(), []
+    for ex in dataset.dataset:
+        if ex["image_path"] not in seen:
+            seen.add(ex["image_path"])
+            cp = ex["crop_params"]
+            out.append((ex["image_path"], ex["label_path"], cp.og_height, cp.og_width))
+    return out
+
+
+def resident_bytes(dataset) -> int:
+    """Device bytes the data set's scenes occupy once resident, from the TIFF headers alone: per scene the fp32 grid
+    [C, label_h, label_w] and the uint8 label raster, plus the largest source raster (it is on the device only while its
+    scene is resampled)."""
+    from .tiff import tiff_size
+    C = dataset.n_channels["ms_image"]
+    total = transient = 0
+    for image_path, _, H, W in _scene_list(dataset):
+        total += C * H * W * 4 + H * W
+        h, w = tiff_size(image_path)
+        transient = max(transient, C * h * w * 4)
+    return total + transient
+
+
+class _SceneRasters(torch.utils.data.Dataset):
+    """Scene i decoded on the host: the band-selected raster (as infer.SceneFiles makes it) and the raw label raster."""
+
+    def __init__(self, scenes, sensor: str, channels: str):
+        self.scenes, self.sensor, self.channels = scenes, sensor, channels
+
+    def __len__(self):
+        return len(self.scenes)
+
+    def __getitem__(self, i):
+        from . import tiff
+        from ..infer import SCALE_MODES
+        from .floodplanet import select_bands
+        image_path, label_path, H, W = self.scenes[i]
+        raster, was_u16 = select_bands(tiff.read_tiff(image_path), self.sensor, self.channels)
+        label = np.asarray(tiff.read_tiff(label_path))
+        if label.shape != (H, W):
+            raise ValueError(f"label raster {label_path} is {label.shape}, its header says {(H, W)}")
+        if label.dtype != np.uint8:      # only 0 and 2 are told apart from the rest: keep exactly that
+            label = np.where(label == 2, 2, np.where(label == 0, 0, 1)).astype(np.uint8)
+        return {"raster": torch.from_numpy(raster), "label": torch.from_numpy(np.ascontiguousarray(label)),
+                "scale_mode": SCALE_MODES.get(self.sensor, 4 if was_u16 else 0), "index": i}
+
+
+# ------------------------------------------------------------------------------------------------------- loader
+class SceneTileLoader:
+    def __init__(self, dataset, batch_size: int, device, net, shuffle: bool = False, seed: int = 0, drop_last: bool = False,
+                 transforms: Optional[dict] = None, ignore_index: int = 0, max_resident_bytes: Optional[int] = None,
+                 shard: Optional[Sequence[int]] = None, num_workers: int = 0):
+        """dataset: FloodplanetTiles.  net: the HipUNet whose context owns the table's device buffer.  transforms: None, or
+        the reference's `transforms` config dict ({} = its defaults), drawn from RandomState(seed) as TileLoader draws them.
+        ignore_index: the fill of the target where the augmentation leaves the tile; the data set pads edge crops with its
+        own ignore_index, and the kernel has one fill for both, so the two must agree.  max_resident_bytes: the budget of
+        resident_bytes(dataset) (default: FREE_MEMORY_FRACTION of the device's free memory now).  num_workers: processes
+        for the one-time decode."""
+        self.dataset, self.batch_size, self.device = dataset, int(batch_size), torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("SceneTileLoader keeps the scenes on a ROCm GPU and cuts the batches there; there is no CPU "
+                               "fallback (TileLoader assembles on the host)")
+        if int(dataset.ignore_index) != int(ignore_index):
+            raise ValueError(f"SceneTileLoader: the data set pads targets with ignore_index {dataset.ignore_index} and the "
+                             f"augmentation would fill with {ignore_index}; fu_scene_train_tiles has one fill for both")
+        if not 0 <= int(ignore_index) <= 255:
+            # the host path stores decoded labels as uint8: a no-data pixel would read ignore_index % 256 while the padding
+            # and the augmentation fill read ignore_index itself -- two different "ignore" values in one batch
+            raise ValueError(f"SceneTileLoader: ignore_index must lie in 0..255 (labels are decoded as uint8), got {ignore_index}")
+        self.net, self.transforms, self.ignore_index = net, transforms, int(ignore_index)
+        self.shuffle, self.seed, self.drop_last = bool(shuffle), int(seed), bool(drop_last)
+        self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
+        self.num_workers = int(num_workers)
+        plan_epoch(len(dataset), self.batch_size, 0, False, 0, self.drop_last, self.shard)       # argument errors now
+        self.resident_bytes = resident_bytes(dataset)
+        if max_resident_bytes is None:
+            free, _ = torch.cuda.mem_get_info(self.device)
+            max_resident_bytes = int(free * FREE_MEMORY_FRACTION)
+        self.max_resident_bytes = int(max_resident_bytes)
+        if self.resident_bytes > self.max_resident_bytes:
+            raise SceneResidencyError(
+                f"SceneTileLoader: the data set's {len(_scene_list(dataset))} scenes need {self.resident_bytes} bytes on the "
+                f"device, more than max_resident_bytes = {self.max_resident_bytes}; nothing was uploaded. Use TileLoader, "
+                f"which streams tiles from the host, for data sets that do not fit.")
+        self._rng = np.random.RandomState(self.seed)
+        self._epoch = 0
+        self._items = None               # example i -> (grid, label, (h0, w0, hE, wE))
+        self._global = None
+        cp = dataset.dataset[0]["crop_params"] if len(dataset) else None
+        self.tile_hw = (cp.max_crop_height, cp.max_crop_width) if cp is not None else None
+
+    def __len__(self):
+        return len(plan_epoch(len(self.dataset), self.batch_size, 0, False, 0, self.drop_last, self.shard))
+
+    def _make_resident(self):
+        """Decode, upload and resample every scene once; upload its label raster."""
+        from ..infer import resident_grid
+        ds, dev = self.dataset, self.device
+        scenes = _scene_list(ds)
+        loader = torch.utils.data.DataLoader(_SceneRasters(scenes, ds.sensor, ds.channels), batch_size=None, shuffle=False,
+                                             num_workers=self.num_workers, pin_memory=True)
+        store = {}
+        for item in loader:
+            image_path, _, H, W = scenes[int(item["index"])]
+            grid = resident_grid(item["raster"], int(item["scale_mode"]), (H, W), dev)
+            store[image_path] = (grid, item["label"].to(dev, non_blocking=True), H, W)
+        items = []
+        for ex in ds.dataset:
+            grid, label, H, W = store[ex["image_path"]]
+            cp = ex["crop_params"]
+            items.append((grid, label, (cp.h0, cp.w0, min(cp.hE, H), min(cp.wE, W))))     # clipped, as the host's slicing clips
+        if ds.norm_mode == "global":     # the kernel takes fp32 parameters: the fp64 ones are rounded once, as TileLoader does
+            p = ds.global_norm_params[ds.sensor]
+            self._global = (torch.from_numpy(p["mean"]).float().to(dev), torch.from_numpy(p["std"]).float().to(dev))
+        torch.cuda.synchronize(dev)      # the pinned host rasters may go once the uploads are done
+        self._items = items
+
+    def _batch(self, index: List[int]) -> dict:
+        from .. import augment
+        from .assemble import scene_train_tiles
+        n = len(index)
+        if self.transforms is not None:
+            flags, angles = augment.sample_transforms(n, self.transforms, self._rng)
+        else:
+            flags, angles = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float32)
+        th, tw = self.tile_hw
+        ctx = self.net._get_ctx(self.device, self.batch_size, th, tw)
+        entries = [self._items[i] + (int(flags[k]), float(angles[k])) for k, i in enumerate(index)]
+        image, target, mean, std = scene_train_tiles(ctx, entries, (th, tw), self.dataset.norm_mode, self._global,
+                                                     nodata_value=self.ignore_index,
+                                                     target_fill=self.ignore_index)
+        out = {"image": image, "target": target, "mean": mean, "std": std, "index": list(index), "flags": flags,
+               "angles": angles}
+        if self.dataset.output_metadata:
+            out["metadata"] = [{"image_path": ex["image_path"], "crop_params": ex["crop_params"],
+                                "region_name": ex["region_name"]} for ex in (self.dataset.dataset[i] for i in index)]
+        return out
+
+    def __iter__(self):
+        if self._items is None:
+            self._make_resident()
+        epoch, self._epoch = self._epoch, self._epoch + 1
+        for index in plan_epoch(len(self.dataset), self.batch_size, epoch, self.shuffle, self.seed, self.drop_last,
+                                self.shard):
+            yield self._batch(index)

@@ -12,11 +12,23 @@ box).  When those packages exist, use the reference's own fit.py with `floodplan
 `cfg` is a plain nested dict with the reference's key names (conf/config.yaml): lr, batch_size, n_epochs,
 crop_height, crop_width, ignore_index, save_topk_models, limit_train_batches, limit_val_batches,
 model: {name, model_kwargs}, plus `n_channels` (dict) / `n_classes` that the reference reads off the dataset.
-The tile stream is synthetic (SyntheticTiles) because the FloodPlanet rasters and their readers are out of scope.
+fit_model takes any iterable of batches: SyntheticTiles below (tests, benchmarks), or the loaders of
+floodplanet_code_amd.datasets over real rasters, which is what the command line builds:
+
+    python -m floodplanet_code_amd.fit DATA_ROOT --exp_dir DIR [--sensor S1] [--eval_region R ...] [--crop H W] [...]
+
+DATA_ROOT holds CSDAP_complete/.  The train / valid FloodplanetTiles are made as fit.py:25-53 makes them; --loader scene
+(default) keeps every scene on the device and cuts finished batches there (datasets.SceneTileLoader), --loader tile streams
+tiles through DataLoader workers (datasets.TileLoader with device assembly and resampling).  One JSON line comes out: the
+best checkpoint and the per-epoch history.  The checkpoint's hyper_parameters carry the data set keys, so predict / infer
+run on it without a config file.
 """
 from __future__ import annotations
 
+import argparse
+import json
 import os
+import time
 from typing import Dict, Iterable, List, Optional
 
 import torch
@@ -70,13 +82,18 @@ def _limited(loader, limit: Optional[int]):
 
 
 def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int], n_classes: int = 3,
-              exp_dir: Optional[str] = None, device="cuda:0", to_rgb_fcn=None) -> str:
-    """Restatement of fit.py:16-103 without Lightning.  Returns the best checkpoint path ('' if exp_dir is None)."""
+              exp_dir: Optional[str] = None, device="cuda:0", to_rgb_fcn=None, model=None) -> str:
+    """Restatement of fit.py:16-103 without Lightning.  Returns the best checkpoint path ('' if exp_dir is None).
+    model: an already built model to train in place of the build_model call (a loader that needs the network's context,
+    SceneTileLoader, is made before fit_model runs).  The trained model keeps `history`, one dict per epoch: epoch, train_loss
+    (the last step's), val_MulticlassJaccardIndex and train_tiles_per_s -- the tiles of the epoch's training loop over its
+    host time, closed by one device synchronise per epoch (None when the train loader yields nothing)."""
     c = dict(DEFAULTS)
     c.update(cfg or {})
     torch.manual_seed(c["seed_num"])                                         # pl.seed_everything(seed_num)
-    model = build_model(c["model"]["name"], n_channels, n_classes, c["lr"], log_image_iter=c["log_image_iter"],
-                        to_rgb_fcn=to_rgb_fcn, ignore_index=c["ignore_index"], **c["model"].get("model_kwargs", {}))
+    if model is None:
+        model = build_model(c["model"]["name"], n_channels, n_classes, c["lr"], log_image_iter=c["log_image_iter"],
+                            to_rgb_fcn=to_rgb_fcn, ignore_index=c["ignore_index"], **c["model"].get("model_kwargs", {}))
     model = model.to(device)
     opt = model.configure_optimizers()
     best: List = []                                                          # (metric, path), top-k
@@ -86,19 +103,25 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
     history = []
     for epoch in range(c["n_epochs"]):
         model.current_epoch = epoch
+        n_tiles, t0 = 0, time.perf_counter()
         for i, batch in _limited(train_loader, c["limit_train_batches"]):
             opt.zero_grad()
             loss = model.training_step(batch, i)
             loss.backward()
             opt.step()
             model.global_step += 1
+            n_tiles += int(batch["image"].shape[0])
+        if torch.device(device).type == "cuda":
+            torch.cuda.synchronize(device)                                   # one sync: the rate covers finished steps
+        train_seconds = time.perf_counter() - t0
         model.valid_metrics.reset()
         outs = []
         for i, batch in _limited(valid_loader, c["limit_val_batches"]):
             outs.append(model.validation_step(batch, i))
         model.validation_epoch_end(outs)
         miou = float(model.logged.get("val_MulticlassJaccardIndex", torch.zeros(())))
-        history.append({"epoch": epoch, "train_loss": float(loss.detach()), "val_MulticlassJaccardIndex": miou})
+        history.append({"epoch": epoch, "train_loss": float(loss.detach()), "val_MulticlassJaccardIndex": miou,
+                        "train_tiles_per_s": n_tiles / train_seconds if n_tiles and train_seconds > 0 else None})
         if ckpt_dir:
             path = os.path.join(ckpt_dir, f"model-epoch={epoch:02d}-val_MulticlassJaccardIndex={miou:.4f}.ckpt")
             torch.save({"state_dict": model.state_dict(), "epoch": epoch, "hyper_parameters": dict(c)}, path)
@@ -111,3 +134,96 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
     model.history = history
     fit_model.last_model = model
     return best[0][1] if best else ""
+
+
+# ---------------------------------------------------------------------------------------------------------- command line
+def build_parser() -> argparse.ArgumentParser:
+    """Defaults: DEFAULTS above and predict.CONFIG_DEFAULTS (the reference's conf/config.yaml) where they name the key."""
+    from .predict import CONFIG_DEFAULTS as D
+    ap = argparse.ArgumentParser(description="Train a water segmentation model on FloodPlanet rasters (fit.py of st_water_seg).")
+    ap.add_argument("data_root", type=str, help="directory that holds CSDAP_complete/")
+    ap.add_argument("--exp_dir", type=str, required=True, help="experiment directory (checkpoints/ goes under it)")
+    ap.add_argument("--sensor", type=str, default=D["dataset"]["sensor"])
+    ap.add_argument("--channels", type=str, default=D["dataset"]["channels"])
+    ap.add_argument("--eval_region", type=str, nargs="*", default=[D["eval_region"]],
+                    help="validation region(s); give the flag without a value for the seeded random split by image")
+    ap.add_argument("--train_split_pct", type=float, default=D["train_split_pct"])
+    ap.add_argument("--crop", type=int, nargs=2, metavar=("H", "W"), default=[D["crop_height"], D["crop_width"]])
+    ap.add_argument("--stride", type=int, default=D["crop_stride"])
+    ap.add_argument("--batch_size", type=int, default=D["batch_size"])
+    ap.add_argument("--n_epochs", type=int, default=D["n_epochs"])
+    ap.add_argument("--lr", type=float, default=D["lr"])
+    ap.add_argument("--norm_mode", type=str, default="none", choices=["none", "local", "global"])
+    ap.add_argument("--norm_params", type=str, default=None,
+                    help="parameter file of norm_mode 'global' (python -m floodplanet_code_amd.datasets.stats writes it)")
+    ap.add_argument("--model", type=str, default="ms_model", help="ms_model, ef_model or lf_model")
+    ap.add_argument("--base_channels", type=int, default=64)
+    ap.add_argument("--precision", type=str, default="fp32", choices=["fp32", "bf16", "fp16"])
+    ap.add_argument("--loader", type=str, default="scene", choices=["scene", "tile"],
+                    help="scene: device-resident scenes, one launch per batch; tile: DataLoader workers stream tiles")
+    ap.add_argument("--n_workers", type=int, default=D["n_workers"],
+                    help="tile: DataLoader workers; scene: processes of the one-time decode")
+    ap.add_argument("--seed", type=int, default=D["seed_num"])
+    ap.add_argument("--ignore_index", type=int, default=D["ignore_index"])
+    ap.add_argument("--save_topk_models", type=int, default=D["save_topk_models"])
+    ap.add_argument("--no_transforms", action="store_true", help="train without hflip / vflip / rotate")
+    ap.add_argument("--no_shuffle", action="store_true", help="train in data-set order")
+    ap.add_argument("--device", type=str, default="cuda:0")
+    return ap
+
+
+def cfg_from_args(args) -> dict:
+    """The reference-style config of a command line: what fit_model trains with and dumps into the checkpoint."""
+    norm_mode = None if args.norm_mode == "none" else args.norm_mode
+    return dict(lr=args.lr, batch_size=args.batch_size, n_epochs=args.n_epochs, crop_height=args.crop[0],
+                crop_width=args.crop[1], crop_stride=args.stride, ignore_index=args.ignore_index,
+                save_topk_models=args.save_topk_models, seed_num=args.seed, n_workers=args.n_workers,
+                eval_region=list(args.eval_region) if args.eval_region else None, train_split_pct=args.train_split_pct,
+                norm_mode=norm_mode, norm_params=args.norm_params,
+                dataset=dict(name="floodplanet", sensor=args.sensor, channels=args.channels, dataset_kwargs=None),
+                model=dict(name=args.model, model_kwargs=dict(optimizer_name="adam", base_channels=args.base_channels,
+                                                              precision=args.precision)))
+
+
+def main(argv: Optional[List[str]] = None) -> dict:
+    import copy
+    from .datasets import FloodplanetTiles, SceneTileLoader, TileLoader, generate_image_slice_object
+    args = build_parser().parse_args(argv)
+    cfg = cfg_from_args(args)
+    c = dict(DEFAULTS)
+    c.update(cfg)
+    slice_params = generate_image_slice_object(c["crop_height"], c["crop_width"], c["crop_stride"])
+
+    def tiles(split):                                    # fit.py:25-53 (the transforms run on the device, per batch)
+        return FloodplanetTiles(args.data_root, split, slice_params, eval_region=copy.copy(c["eval_region"]),
+                                sensor=args.sensor, channels=args.channels, norm_mode=c["norm_mode"],
+                                ignore_index=c["ignore_index"], seed_num=c["seed_num"],
+                                train_split_pct=c["train_split_pct"], norm_params=c["norm_params"])
+
+    train_ds, valid_ds = tiles("train"), tiles("valid")
+    torch.manual_seed(c["seed_num"])                     # the initial weights are drawn here, not in fit_model
+    model = build_model(c["model"]["name"], train_ds.n_channels, train_ds.n_classes, c["lr"],
+                        log_image_iter=c["log_image_iter"], to_rgb_fcn=None, ignore_index=c["ignore_index"],
+                        **c["model"]["model_kwargs"]).to(args.device)
+    transforms = None if args.no_transforms else {}
+    if args.loader == "scene":
+        common = dict(net=model.model, seed=c["seed_num"], ignore_index=c["ignore_index"], num_workers=args.n_workers)
+        train = SceneTileLoader(train_ds, c["batch_size"], args.device, shuffle=not args.no_shuffle, transforms=transforms,
+                                **common)
+        valid = SceneTileLoader(valid_ds, c["batch_size"], args.device, **common)
+    else:
+        common = dict(seed=c["seed_num"], ignore_index=c["ignore_index"], num_workers=args.n_workers,
+                      device_assembly=True, device_resize=True)
+        train = TileLoader(train_ds, c["batch_size"], args.device, shuffle=not args.no_shuffle, transforms=transforms,
+                           **common)
+        valid = TileLoader(valid_ds, c["batch_size"], args.device, **common)
+    best = fit_model(cfg, train, valid, train_ds.n_channels, train_ds.n_classes, exp_dir=args.exp_dir, device=args.device,
+                     model=model)
+    out = {"checkpoint": best, "loader": args.loader, "train_tiles": len(train_ds), "valid_tiles": len(valid_ds),
+           "history": model.history}
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == "__main__":
+    main()

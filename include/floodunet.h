@@ -20,6 +20,7 @@
  *   fu_adam_step                optim.Adam(self.parameters(), lr).step()     st_water_seg/models/water_seg_model.py:198-205
  *   fu_augment                  torchvision hflip / vflip / rotate of sample_transforms + apply_transforms
  *                                                                            st_water_seg/datasets/base_dataset.py:494-555
+ *   fu_scene_train_tiles        crop + normalise + pad + label decode + augment of resident scenes in one pass (new)
  *   fu_block_param_range        (new) gradient bucket of one backward block, for RCCL all-reduce overlap
  *   fu_dp_* / fu_allreduce_*    (new) the bucketed gradient all-reduce itself, RCCL resolved at run time
  *   fu_op_*                     single operators for per-op parity tests (conv2d, batch_norm, max_pool2d,
@@ -326,6 +327,31 @@ typedef struct fu_scene_crop {
 int fu_scene_crops(fu_ctx* ctx, int n, const fu_scene_crop* entries, int C, int tile_h, int tile_w, int norm_mode,
                    const float* global_mean, const float* global_std, float pad_value, float* out, float* mean_out,
                    float* std_out, fu_stream stream);
+
+/* Finished training batches from scenes that are resident on the device (added within ABI 5: purely additive, no version
+ * bump).  Entry b names a scene and a box as for fu_scene_crops, the scene's label raster (uint8 [scene_h, scene_w] on the
+ * device, the RAW values of the label file; NULL when no target is wanted) and the sample's transforms (FU_AUG_* flags and
+ * the rotation angle in degrees, as fu_augment takes them).  image_out fp32 [n, C, tile_h, tile_w] and target_out int64
+ * [n, tile_h, tile_w] (optional) equal, bit for bit, fu_scene_crops (same norm_mode, parameters, pad_value) followed by
+ * fu_augment (same flags / angles, image fill 0, target_fill), where the un-augmented target of entry b is its label box
+ * decoded as the data set decodes it (raw 2 -> 1, raw 0 -> nodata_value, anything else -> 0) in the top-left corner of a
+ * tile filled with target_fill.  mean_out / std_out: fp32 [n, C], written (and needed) for 'local' only, the statistics of
+ * the un-augmented crop.  One launch, two with 'local'; no intermediate batch is written.  16-byte stores need
+ * tile_w % 4 == 0 and 16-byte aligned outputs; otherwise the kernel stores element by element.  The table is copied into a
+ * library-owned device buffer ordered on `stream`, as for fu_scene_crops, and every entry and argument is checked before
+ * anything is launched (tile_h * tile_w <= 2^25): a rejected call launches nothing. */
+typedef struct fu_scene_train_entry {
+  const float* scene;        /* fp32 [C, scene_h, scene_w] on the device (the resampled, sensor-scaled grid) */
+  const uint8_t* label;      /* uint8 [scene_h, scene_w] on the device, or NULL */
+  int32_t scene_h, scene_w;
+  int32_t h0, w0, hE, wE;    /* the box, inside the scene, at most the tile */
+  int32_t flags;             /* FU_AUG_HFLIP | FU_AUG_VFLIP | FU_AUG_ROTATE */
+  float angle_deg;
+} fu_scene_train_entry;
+int fu_scene_train_tiles(fu_ctx* ctx, int n, const fu_scene_train_entry* entries, int C, int tile_h, int tile_w,
+                         int norm_mode, const float* global_mean, const float* global_std, float pad_value,
+                         int64_t nodata_value, int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out,
+                         float* std_out, fu_stream stream);
 
 /* ---- inference stitching (ImageStitcher_v2, utils/utils_image.py:410-494) ------------- */
 /* canvas[h0:hE, w0:wE, :] += softmax(logits of sample `sample` of the last fu_forward)[:hE-h0, :wE-w0, :];

@@ -1,0 +1,374 @@
+"""GPU: training batches from device-resident scenes -- fu_scene_train_tiles against the chain it fuses
+(fu_scene_crops -> fu_augment on host-decoded targets) and the oracle, SceneTileLoader against TileLoader, and the fit
+command line end to end.  Every comparison is of bits: both sides run the same fp32 operations."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from floodplanet_code_amd import _lib, augment
+from floodplanet_code_amd.datasets import FloodplanetTiles, SceneTileLoader, TileLoader, generate_image_slice_object
+from floodplanet_code_amd.datasets.assemble import scene_crops, scene_train_tiles
+from floodplanet_code_amd.unet import HipUNet
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _bits_equal(a, b):
+    """Bit for bit, NaN included (a 1 x 1 box has std 0 under 'local': 0 / 0 on both sides)."""
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.int32),
+                                                                      b.contiguous().view(torch.int32))
+
+
+def _net(th=32, tw=32):
+    net = HipUNet(2, 3, base_channels=8).to(DEV).eval()
+    net._get_ctx(torch.device(DEV), 1, th, tw)
+    return net                                   # keep the module alive: it owns the context
+
+
+SCENE_SIZES = ((70, 53), (40, 90), (25, 25))
+
+
+def _scenes(C, seed):
+    """Scenes of different sizes with label rasters holding 0, 1, 2 and one stray value."""
+    g = torch.Generator().manual_seed(seed)
+    scenes, labels = [], []
+    for h, w in SCENE_SIZES:
+        scenes.append((torch.rand(C, h, w, generator=g) * 5 - 1).to(DEV))
+        lab = torch.randint(0, 3, (h, w), generator=g, dtype=torch.uint8)
+        lab[h // 2, w // 3] = 7
+        lab[0, 0], lab[0, 1], lab[1, 0] = 0, 1, 2
+        labels.append(lab)
+    return scenes, labels
+
+
+def _boxes(th, tw):
+    """(scene, h0, w0, hE, wE): interior, right-edge, bottom-edge and corner boxes (smaller than the tile), a scene smaller
+    than the tile, a 1 x 1 box."""
+    return [(0, 3, 5, 3 + th, 5 + tw),                                # interior, odd origin
+            (1, 4, 90 - (tw - 5), 4 + th, 90),                        # right edge: narrower than the tile
+            (0, 70 - (th - 9), 8, 70, 8 + tw),                        # bottom edge: shorter than the tile
+            (0, 70 - (th - 6), 53 - (tw - 11), 70, 53),               # corner
+            (2, 0, 0, min(25, th), min(25, tw)),                      # the whole (small) scene
+            (1, 0, 0, th, tw),                                        # interior, aligned origin
+            (2, 10, 3, 25, 20),
+            (1, 39, 0, 40, 1)]
+
+
+# all 8 flag combinations x the angles, plus a sample with no flags at all
+TRANSFORMS = [(f, a) for f in range(8) for a in (0.0, 37.5, 90.0, 180.0, 333.0)] + [(0, 0.0)]
+
+
+def _host_target(labels, boxes, th, tw, nodata, fill):
+    """FloodplanetTiles._load_label_image + _add_buffer on the host: raw 2 -> 1, raw 0 -> nodata, the rest -> 0."""
+    out = np.full((len(boxes), th, tw), fill, dtype=np.int64)
+    for i, (s, h0, w0, hE, wE) in enumerate(boxes):
+        raw = labels[s][h0:hE, w0:wE].numpy()
+        dec = np.zeros(raw.shape, dtype=np.int64)
+        dec[raw == 2] = 1
+        dec[raw == 0] = nodata
+        out[i, :hE - h0, :wE - w0] = dec
+    return torch.from_numpy(out)
+
+
+def _chain(net, scenes, labels, boxes, flags, angles, tile, norm_mode, gp, nodata, fill):
+    image, mean, std = scene_crops(net._ctx, [(scenes[b[0]], b[1:]) for b in boxes], tile, norm_mode, gp)
+    target = _host_target(labels, boxes, tile[0], tile[1], nodata, fill).to(DEV)
+    image, target = augment.apply(image, target, flags, angles, target_fill=fill)
+    return image, target, mean, std
+
+
+def _entries(scenes, labels_dev, boxes, flags, angles, with_label=True):
+    return [(scenes[b[0]], labels_dev[b[0]] if with_label else None, b[1:], int(f), float(a))
+            for b, f, a in zip(boxes, flags, angles)]
+
+
+@pytest.mark.parametrize("fill", [0, 2])
+@pytest.mark.parametrize("tile", [(32, 32), (24, 36), (24, 37)])
+@pytest.mark.parametrize("C", [1, 2, 7])
+@pytest.mark.parametrize("norm_mode", [None, "local", "global"])
+def test_kernel_equals_crops_then_augment_bit_for_bit(norm_mode, C, tile, fill):
+    """(24, 36): non-square with 16-byte stores; (24, 37): tile_w % 4 != 0, the element-wise path."""
+    th, tw = tile
+    net = _net()
+    scenes, labels = _scenes(C, seed=10 * C + th)
+    labels_dev = [l.to(DEV) for l in labels]
+    gp = (torch.linspace(-0.5, 0.7, C), torch.linspace(0.5, 2.0, C)) if norm_mode == "global" else None
+    base = _boxes(th, tw)
+    for shift in (0, 3):                         # every box meets several transforms
+        boxes = [base[(i + shift * (i // len(base))) % len(base)] for i in range(len(TRANSFORMS))]
+        flags = [t[0] for t in TRANSFORMS]
+        angles = [t[1] for t in TRANSFORMS]
+        nodata = fill
+        got = scene_train_tiles(net._ctx, _entries(scenes, labels_dev, boxes, flags, angles), tile, norm_mode, gp,
+                                nodata_value=nodata, target_fill=fill)
+        want = _chain(net, scenes, labels, boxes, flags, angles, tile, norm_mode, gp, nodata, fill)
+        torch.cuda.synchronize()
+        for key, g_, w_ in zip(("image", "target", "mean", "std"), got, want):
+            if key == "target":
+                assert g_.dtype == torch.int64 and torch.equal(g_, w_), (key, norm_mode, C, tile, fill)
+            else:
+                assert _bits_equal(g_, w_), (key, norm_mode, C, tile, fill)
+    # nodata_value and target_fill are separate arguments
+    got = scene_train_tiles(net._ctx, _entries(scenes, labels_dev, boxes, flags, angles), tile, norm_mode, gp,
+                            nodata_value=2 - fill, target_fill=fill)
+    want = _chain(net, scenes, labels, boxes, flags, angles, tile, norm_mode, gp, 2 - fill, fill)
+    torch.cuda.synchronize()
+    assert torch.equal(got[1], want[1]) and _bits_equal(got[0], want[0])
+    # without labels: the image alone, the same bits
+    img_only = scene_train_tiles(net._ctx, _entries(scenes, labels_dev, boxes, flags, angles, with_label=False), tile,
+                                 norm_mode, gp)
+    torch.cuda.synchronize()
+    assert img_only[1] is None and _bits_equal(img_only[0], want[0])
+
+
+def test_kernel_equals_oracle_on_host_tiles(tmp_path):
+    """Against the independent host path: FloodplanetTiles.__getitem__ (host decode, host Lanczos, host label decode and
+    padding) followed by the oracle's augment, norm_mode None."""
+    from oracle import unet_oracle as O
+    from tools.tiff_writer import make_floodplanet_tree
+    from floodplanet_code_amd.infer import resident_grid
+    root = str(tmp_path)
+    made = make_floodplanet_tree(root, regions=("RegA",), images_per_region=2, label_size=90, s1_size=37)
+    # the tree's labels hold 0, 1, 2; put a stray value into one of them
+    from tools.tiff_writer import write_tiff
+    (reg, name), rasters = sorted(made.items())[0]
+    lab = rasters["label"].copy()
+    lab[5, 7] = 9
+    write_tiff(os.path.join(root, "CSDAP_complete", reg, "labels", name + ".tif"), lab, rows_per_strip=8)
+    ds = FloodplanetTiles(root, "test", generate_image_slice_object(32, 32, 24), eval_region=["RegA"], sensor="S1",
+                          ignore_index=0, norm_mode=None)
+    net = _net()
+    grids = {}
+    entries, want_i, want_t = [], [], []
+    rng = np.random.RandomState(3)
+    for i in range(len(ds)):
+        ex = ds.dataset[i]
+        cp = ex["crop_params"]
+        p = ex["image_path"]
+        if p not in grids:
+            raster, _ = ds._load_raw_raster(p, "ALL")
+            from floodplanet_code_amd.datasets.tiff import read_tiff
+            grids[p] = (resident_grid(torch.from_numpy(raster), 1, (cp.og_height, cp.og_width), DEV),
+                        torch.from_numpy(read_tiff(ex["label_path"])).to(DEV))
+        flag, angle = TRANSFORMS[(7 * i + 5) % len(TRANSFORMS)]
+        angle = angle if i % 3 else float(rng.uniform(0, 360))
+        entries.append((grids[p][0], grids[p][1], (cp.h0, cp.w0, cp.hE, cp.wE), flag, angle))
+        item = ds[i]
+        ri, rt = O.augment(item["image"].numpy(), item["target"].numpy(), flag, np.float32(angle), 0)
+        want_i.append(torch.from_numpy(ri))
+        want_t.append(torch.from_numpy(rt))
+    image, target, _, _ = scene_train_tiles(net._ctx, entries, (32, 32), None, nodata_value=0, target_fill=0)
+    torch.cuda.synchronize()
+    assert any((t == 1).any() for t in want_t) and len(entries) == len(ds) >= 16
+    assert _bits_equal(image.cpu(), torch.stack(want_i)) and torch.equal(target.cpu(), torch.stack(want_t))
+
+
+def test_rejected_calls_launch_nothing():
+    lib = _lib.load()
+    net = _net()
+    scenes, labels = _scenes(2, seed=1)
+    label = labels[0].to(DEV)
+    scene = scenes[0]                                                       # [2, 70, 53]
+    n, C, th, tw = 2, 2, 32, 32
+    image = torch.full((n, C, th, tw), -7.0, device=DEV)
+    target = torch.full((n, th, tw), -7, dtype=torch.int64, device=DEV)
+    mean = torch.full((n, C), -7.0, device=DEV)
+    std = torch.full((n, C), -7.0, device=DEV)
+    gm, gs = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+    nan, inf = float("nan"), float("inf")
+
+    def entry(h0=0, w0=0, hE=32, wE=32, flags=0, angle=0.0, lab=label, sc=scene, sh=70, sw=53):
+        return _lib.FuSceneTrainEntry(None if sc is None else sc.data_ptr(), None if lab is None else lab.data_ptr(),
+                                      sh, sw, h0, w0, hE, wE, flags, angle)
+
+    def call(entries, n_=None, mode=0, gmean=None, gstd=None, img=image, tgt=target, m=None, s=None, ctx=net._ctx, C_=C,
+             tile=(th, tw)):
+        table = (_lib.FuSceneTrainEntry * max(len(entries), 1))(*entries)
+        return lib.fu_scene_train_tiles(ctx, len(entries) if n_ is None else n_, table, C_, tile[0], tile[1], mode,
+                                        _lib.ptr(gmean), _lib.ptr(gstd), 0.0, 0, 0, _lib.ptr(img), _lib.ptr(tgt),
+                                        _lib.ptr(m), _lib.ptr(s), stream)
+
+    good = [entry(), entry(8, 8, 40, 40, 7, 33.0)]
+    bad = {
+        "n < 1": lambda: call(good, n_=0),
+        "negative n": lambda: call(good, n_=-3),
+        "too many entries": lambda: call(good, n_=(1 << 31) - 1),
+        "empty box": lambda: call([entry(), entry(4, 4, 4, 20)]),
+        "inverted box": lambda: call([entry(), entry(20, 4, 10, 20)]),
+        "box outside the scene (right)": lambda: call([entry(), entry(0, 30, 32, 54)]),
+        "box outside the scene (bottom)": lambda: call([entry(), entry(60, 0, 71, 32)]),
+        "negative origin": lambda: call([entry(-1, 0, 31, 32), entry()]),
+        "box larger than the tile": lambda: call([entry(), entry(0, 0, 33, 32)]),
+        "unknown flag bits": lambda: call([entry(), entry(flags=8)]),
+        "negative flags": lambda: call([entry(), entry(flags=-1)]),
+        "NaN angle": lambda: call([entry(), entry(flags=4, angle=nan)]),
+        "infinite angle": lambda: call([entry(), entry(flags=4, angle=inf)]),
+        "global without parameters": lambda: call(good, mode=2),
+        "global with half the parameters": lambda: call(good, mode=2, gmean=gm),
+        "local without mean_out / std_out": lambda: call(good, mode=1),
+        "local without std_out": lambda: call(good, mode=1, m=mean),
+        "unknown norm_mode": lambda: call(good, mode=3),
+        "target_out with a NULL label": lambda: call([entry(), entry(lab=None)]),
+        "NULL image_out": lambda: call(good, img=None),
+        "NULL scene": lambda: call([entry(sc=None), entry()]),
+        "NULL context": lambda: call(good, ctx=None),
+        "no channels": lambda: call(good, C_=0),
+        "empty tile": lambda: call(good, tile=(0, 32)),
+        "tile beyond what one launch's grid holds": lambda: call(good, tile=(8192, 8192)),
+    }
+    for what, fn in bad.items():
+        assert fn() == _lib.FU_ERR_INVALID, what
+        assert lib.fu_last_error(), what
+    torch.cuda.synchronize()
+    for buf in (image, mean, std):
+        assert bool((buf == -7.0).all())
+    assert bool((target == -7).all())
+    # and the same table, valid, does run
+    assert call(good, mode=1, m=mean, s=std) == _lib.FU_OK
+    torch.cuda.synchronize()
+    assert not bool((image == -7.0).any()) and not bool((target == -7).any()) and not bool((mean == -7.0).any())
+
+
+# ------------------------------------------------------------------------------------------------------------ loader
+def _tree(tmp_path, norm_mode, metadata=False):
+    from tools.tiff_writer import make_floodplanet_tree
+    root = str(tmp_path)
+    make_floodplanet_tree(root, regions=("RegA", "RegB"), images_per_region=2, label_size=90, s1_size=37)
+    return FloodplanetTiles(root, "test", generate_image_slice_object(32, 32, 24), eval_region=["RegA", "RegB"],
+                            sensor="S1", ignore_index=0, norm_mode=norm_mode, output_metadata=metadata)
+
+
+@pytest.mark.parametrize("norm_mode", [None, "local"])
+def test_loader_equals_tileloader_batch_for_batch(tmp_path, norm_mode):
+    ds = _tree(tmp_path, norm_mode)
+    net = _net()
+    seed = 5
+    scene = SceneTileLoader(ds, 7, DEV, net, shuffle=False, transforms={}, seed=seed)
+    tile = TileLoader(ds, 7, DEV, shuffle=False, transforms={}, seed=seed, device_assembly=True, device_resize=True)
+    assert len(scene) == len(tile)
+    for epoch in range(2):
+        n = n_aug = 0
+        for a, b in zip(scene, tile):
+            torch.cuda.synchronize()
+            for key in ("image", "mean", "std"):
+                assert _bits_equal(a[key], b[key]), (key, epoch, n)
+            assert a["target"].dtype == torch.int64 and torch.equal(a["target"], b["target"]), (epoch, n)
+            assert a["index"] == list(range(n, n + len(a["index"])))
+            n += a["image"].shape[0]
+            n_aug += int((a["flags"] != 0).sum())
+        assert n == len(ds) and n_aug > 0
+
+
+def test_shuffled_loader_batches_are_the_chain_on_their_own_indices(tmp_path):
+    ds = _tree(tmp_path, "local", metadata=True)
+    net = _net()
+    loader = SceneTileLoader(ds, 7, DEV, net, shuffle=True, transforms={}, seed=2)
+    orders = []
+    for epoch in range(2):
+        seen = []
+        for batch in loader:
+            boxes, targets = [], []
+            for k, i in enumerate(batch["index"]):
+                grid, label, box = loader._items[i]
+                boxes.append((grid, box))
+                item = ds[i]                                           # the host's tile: its target is the reference
+                targets.append(item["target"])
+                assert batch["metadata"][k]["image_path"] == ds.dataset[i]["image_path"]
+            image, mean, std = scene_crops(net._ctx, boxes, (32, 32), "local")
+            image, target = augment.apply(image, torch.stack(targets).to(DEV), batch["flags"], batch["angles"],
+                                          target_fill=0)
+            torch.cuda.synchronize()
+            assert _bits_equal(batch["image"], image) and torch.equal(batch["target"], target)
+            assert _bits_equal(batch["mean"], mean) and _bits_equal(batch["std"], std)
+            seen += batch["index"]
+        assert sorted(seen) == list(range(len(ds)))                    # an epoch covers every index once
+        orders.append(seen)
+    assert orders[0] != orders[1] and orders[0] != list(range(len(ds)))
+
+
+def test_second_epoch_reads_no_file_and_allocates_nothing_that_stays(tmp_path, monkeypatch):
+    from floodplanet_code_amd.datasets import floodplanet, tiff
+    ds = _tree(tmp_path, None)
+    net = _net()
+    calls = []
+    real = tiff.read_tiff
+
+    def counting(path, *a, **k):
+        calls.append(path)
+        return real(path, *a, **k)
+    monkeypatch.setattr(tiff, "read_tiff", counting)
+    monkeypatch.setattr(floodplanet, "read_tiff", counting)
+    loader = SceneTileLoader(ds, 7, DEV, net, shuffle=True, transforms={}, seed=0)
+    for batch in loader:
+        pass
+    del batch
+    torch.cuda.synchronize()
+    assert len(calls) == 2 * 4                                         # 4 scenes: one image and one label raster each
+    first = len(calls)
+    base = torch.cuda.memory_allocated()
+    # one batch: image fp32 [7, 2, 32, 32], target int64 [7, 32, 32], mean / std [7, 2] (the allocator rounds up to 512 B)
+    one_batch = 7 * 2 * 32 * 32 * 4 + 7 * 32 * 32 * 8 + 2 * 512
+    peak = 0
+    for batch in loader:
+        peak = max(peak, torch.cuda.memory_allocated() - base)
+    del batch
+    torch.cuda.synchronize()
+    assert len(calls) == first                                         # no TIFF read after the first epoch
+    assert peak <= 2 * one_batch, (peak, one_batch)                    # the batch in hand and the one being made
+    assert torch.cuda.memory_allocated() <= base
+
+
+# ------------------------------------------------------------------------------------------------------------ end to end
+def _fit_args(root, exp, loader, extra=()):
+    return [root, "--exp_dir", exp, "--sensor", "S1", "--eval_region", "RegB", "--crop", "64", "64", "--stride", "32",
+            "--batch_size", "4", "--n_epochs", "2", "--lr", "2e-3", "--base_channels", "8", "--loader", loader,
+            "--n_workers", "0", "--seed", "0", "--save_topk_models", "1", "--device", DEV, *extra]
+
+
+@pytest.fixture(scope="module")
+def tree(tmp_path_factory):
+    from tools.tiff_writer import make_floodplanet_tree
+    root = str(tmp_path_factory.mktemp("tree"))
+    make_floodplanet_tree(root, regions=("RegA", "RegB"), images_per_region=2, label_size=100, s1_size=40)
+    return root
+
+
+def test_fit_cli_trains_from_resident_scenes_and_its_checkpoint_serves_predict_and_infer(tree, tmp_path, capsys):
+    from floodplanet_code_amd import fit, infer, predict
+    exp = str(tmp_path / "exp")
+    out = fit.main(_fit_args(tree, exp, "scene"))
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    ckpt = out["checkpoint"]
+    assert line["checkpoint"] == ckpt and os.path.exists(ckpt) and len(out["history"]) == 2
+    for h in out["history"]:
+        assert np.isfinite(h["train_loss"]) and 0.0 <= h["val_MulticlassJaccardIndex"] <= 1.0
+        assert h["train_tiles_per_s"] > 0
+    hyper = torch.load(ckpt, map_location="cpu", weights_only=False)["hyper_parameters"]
+    assert hyper["dataset"]["sensor"] == "S1" and hyper["crop_height"] == 64 and hyper["eval_region"] == ["RegB"]
+    # the config comes from the checkpoint: no config file anywhere
+    summary = infer.infer(ckpt, [os.path.join(tree, "CSDAP_complete", "RegB", "S1")], str(tmp_path / "maps"))
+    assert summary["n_scenes"] == 3 and all(os.path.exists(r["output"]) for r in summary["scenes"])
+    predict.main([ckpt, "--data_root", tree, "--batch_size", "4"])
+    res = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert os.path.exists(os.path.join(res["pred_dir"], "metrics.json"))
+    assert os.path.isdir(os.path.join(res["pred_dir"], "image_predictions", "RegB"))
+
+
+def test_fit_cli_scene_and_tile_loaders_train_to_the_same_bits(tree, tmp_path, capsys):
+    """Same seed, no transforms, data-set order: the batches are equal, the step is deterministic for equal inputs, so the
+    loss after each epoch's last step -- which depends on every step before it -- is equal bit for bit."""
+    from floodplanet_code_amd import fit
+    hist = {}
+    for loader in ("scene", "tile"):
+        out = fit.main(_fit_args(tree, str(tmp_path / loader), loader, ("--no_transforms", "--no_shuffle")))
+        hist[loader] = out["history"]
+    capsys.readouterr()
+    a, b = hist["scene"][0], hist["tile"][0]
+    print("first-epoch train_loss scene", repr(a["train_loss"]), "tile", repr(b["train_loss"]))
+    assert np.float32(a["train_loss"]).tobytes() == np.float32(b["train_loss"]).tobytes()
+    assert a["val_MulticlassJaccardIndex"] == b["val_MulticlassJaccardIndex"]
