@@ -379,12 +379,7 @@ struct fu_ctx {
   int* guard = nullptr;           // fp16 mode: non-finite flag / skipped steps / back-off exponent / clean steps (k_guard_book)
   unsigned long long* conf_tmp = nullptr;
   int64_t* n_valid = nullptr;
-  StitchJob* stitch_jobs = nullptr;   // fu_stitch_add_batch: device copy of the last table (grown on demand, owned)
-  int stitch_cap = 0;
-  SceneCropJob* scene_jobs = nullptr; // fu_scene_crops: device copy of the last table (grown on demand, owned)
-  int scene_cap = 0;
-  void* train_tab = nullptr;          // fu_scene_train_tiles: device copy of the last table, boxes then transforms (owned)
-  int train_cap = 0;
+  DeviceTable stitch_table, scene_table, train_table;   // fu_stitch_add_batch[_probs] / fu_scene_crops / fu_scene_train_tiles
   float* adam_m = nullptr;        // bound (caller-owned, fu_bind_adam_state): the moments outlive the context
   float* adam_v = nullptr;
   Profiler prof;
@@ -1183,9 +1178,9 @@ int fu_destroy(fu_ctx* c) {
   for (hipEvent_t e : c->ev_fence) if (e) (void)hipEventDestroy(e);   // (fu_backward_fence creates them without a side stream too)
   if (c->arena.base) (void)hipFree(c->arena.base);
   for (void* p : c->extra_allocs) (void)hipFree(p);
-  if (c->stitch_jobs) (void)hipFree(c->stitch_jobs);
-  if (c->scene_jobs) (void)hipFree(c->scene_jobs);
-  if (c->train_tab) (void)hipFree(c->train_tab);
+  c->stitch_table.release();
+  c->scene_table.release();
+  c->train_table.release();
   delete c;
   return FU_OK;
 }
@@ -1582,62 +1577,19 @@ int fu_stitch_add(fu_ctx* c, int sample, float* canvas, float* weight, int canva
   return launch_stitch_add(lg, c->cfg.n_classes, W, canvas, weight, canvas_w, h0, w0, dh, dw, (hipStream_t)stream);
 }
 
-namespace {
-// fu_stitch_add_batch / fu_stitch_add_batch_probs: validate the table, copy it to the device, launch.  src: the resident
-// NHWC logits (probs == false) or the caller's probabilities (true), [n_samples, H, W, k] fp32.
-int stitch_batch(fu_ctx* c, const char* fn, const char* batch_name, int n, const fu_stitch_entry* entries, const float* src,
-                 int n_samples, bool probs, hipStream_t s) {
-  const int H = c->cfg.height, W = c->cfg.width, k = c->cfg.n_classes;
-  std::vector<StitchJob> jobs((size_t)n);
-  int max_area = 0;
-  for (int i = 0; i < n; ++i) {
-    const fu_stitch_entry& E = entries[i];
-    const int dh = E.hE - E.h0, dw = E.wE - E.w0;
-    FU_REQUIRE(E.canvas && E.weight, "%s: entry %d: null canvas / weight", fn, i);
-    FU_REQUIRE(E.sample >= 0 && E.sample < n_samples, "%s: entry %d: sample %d not in the %s (%d)", fn, i, E.sample,
-               batch_name, n_samples);
-    FU_REQUIRE(E.h0 >= 0 && E.w0 >= 0 && dh > 0 && dw > 0 && E.hE <= E.canvas_h && E.wE <= E.canvas_w && dh <= H && dw <= W,
-               "%s: entry %d: crop [%d:%d, %d:%d] is empty or does not fit canvas %dx%d / tile %dx%d", fn, i,
-               E.h0, E.hE, E.w0, E.wE, E.canvas_h, E.canvas_w, H, W);
-    for (int j = 0; j < i; ++j) {   // one thread owns a canvas pixel: canvases must not share a weight or disagree in size
-      const fu_stitch_entry& P = entries[j];
-      FU_REQUIRE((P.canvas == E.canvas) == (P.weight == E.weight) &&
-                 (P.canvas != E.canvas || (P.canvas_h == E.canvas_h && P.canvas_w == E.canvas_w)),
-                 "%s: entries %d and %d share a canvas or a weight but not both (or differ in size)", fn, j, i);
-    }
-    jobs[i] = StitchJob{src + (int64_t)E.sample * H * W * k, E.canvas, E.weight, E.canvas_w, E.h0, E.w0, dh, dw, 0};
-    max_area = std::max(max_area, dh * dw);
-  }
-  if (n > c->stitch_cap) {
-    if (c->stitch_jobs) {
-      FU_HIP_CHECK(hipDeviceSynchronize());     // an earlier launch may still read the old table
-      FU_HIP_CHECK(hipFree(c->stitch_jobs));
-      c->stitch_jobs = nullptr;
-      c->stitch_cap = 0;
-    }
-    const int cap = std::max(n, 64);
-    FU_HIP_CHECK(hipMalloc(&c->stitch_jobs, (size_t)cap * sizeof(StitchJob)));
-    c->stitch_cap = cap;
-  }
-  FU_HIP_CHECK(hipMemcpyAsync(c->stitch_jobs, jobs.data(), (size_t)n * sizeof(StitchJob), hipMemcpyHostToDevice, s));
-  return probs ? launch_stitch_add_batch_probs(c->stitch_jobs, n, max_area, k, W, s)
-               : launch_stitch_add_batch(c->stitch_jobs, n, max_area, k, W, s);
-}
-}  // namespace
-
 int fu_stitch_add_batch(fu_ctx* c, int n, const fu_stitch_entry* entries, fu_stream stream) {
   FU_REQUIRE(c && entries && n > 0, "fu_stitch_add_batch: null context / entries or n = %d <= 0", n);
   FU_REQUIRE(c->last_batch > 0, "fu_stitch_add_batch: no forward pass yet");
-  return stitch_batch(c, "fu_stitch_add_batch", "last batch", n, entries, c->logits, c->last_batch, false,
-                      (hipStream_t)stream);
+  return launch_stitch_add_batch(c->stitch_table, "fu_stitch_add_batch", "last batch", n, entries, c->logits, c->last_batch,
+                                 false, c->cfg.height, c->cfg.width, c->cfg.n_classes, (hipStream_t)stream);
 }
 
 int fu_stitch_add_batch_probs(fu_ctx* c, int n, const fu_stitch_entry* entries, const float* probs, int batch,
                               fu_stream stream) {
   FU_REQUIRE(c && entries && probs && n > 0 && batch >= 1,
              "fu_stitch_add_batch_probs: null context / entries / probs, n = %d <= 0 or batch = %d < 1", n, batch);
-  return stitch_batch(c, "fu_stitch_add_batch_probs", "probabilities' batch", n, entries, probs, batch, true,
-                      (hipStream_t)stream);
+  return launch_stitch_add_batch(c->stitch_table, "fu_stitch_add_batch_probs", "probabilities' batch", n, entries, probs,
+                                 batch, true, c->cfg.height, c->cfg.width, c->cfg.n_classes, (hipStream_t)stream);
 }
 
 int fu_eval_confusion(fu_ctx* c, const int64_t* target, int ignore_index, int64_t* counts_out, fu_stream stream) {
@@ -1675,107 +1627,19 @@ int fu_assemble_tiles(const float* const* srcs, const int32_t* src_channels, int
 int fu_scene_crops(fu_ctx* c, int n, const fu_scene_crop* entries, int C, int tile_h, int tile_w, int norm_mode,
                    const float* global_mean, const float* global_std, float pad_value, float* out, float* mean_out,
                    float* std_out, fu_stream stream) {
-  // every check before anything is launched or copied: a rejected call leaves the stream untouched
   FU_REQUIRE(c && entries && out, "fu_scene_crops: null context / entries / out");
-  FU_REQUIRE(n >= 1 && C >= 1 && tile_h >= 1 && tile_w >= 1, "fu_scene_crops: n = %d, C = %d, tile %dx%d (all must be >= 1)",
-             n, C, tile_h, tile_w);
-  FU_REQUIRE(norm_mode >= 0 && norm_mode <= 2, "fu_scene_crops: norm_mode must be 0 (None), 1 ('local') or 2 ('global'), "
-             "got %d", norm_mode);
-  FU_REQUIRE(norm_mode != 1 || (mean_out && std_out), "fu_scene_crops: norm_mode 'local' needs mean_out / std_out [n, C]");
-  FU_REQUIRE(norm_mode != 2 || (global_mean && global_std), "fu_scene_crops: norm_mode 'global' needs the per-channel "
-             "parameters");
-  FU_REQUIRE((int64_t)n * C <= INT32_MAX && (int64_t)n * C * tile_h * tile_w <= ((int64_t)1 << 40),
-             "fu_scene_crops: %d boxes of %d channels are too many for one call", n, C);
-  std::vector<SceneCropJob> jobs((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    const fu_scene_crop& E = entries[i];
-    const int dh = E.hE - E.h0, dw = E.wE - E.w0;
-    FU_REQUIRE(E.scene, "fu_scene_crops: entry %d: null scene", i);
-    FU_REQUIRE(E.scene_h >= 1 && E.scene_w >= 1, "fu_scene_crops: entry %d: bad scene size %dx%d", i, E.scene_h, E.scene_w);
-    FU_REQUIRE(E.h0 >= 0 && E.w0 >= 0 && E.hE <= E.scene_h && E.wE <= E.scene_w,
-               "fu_scene_crops: entry %d: box [%d:%d, %d:%d] lies outside its scene %dx%d", i, E.h0, E.hE, E.w0, E.wE,
-               E.scene_h, E.scene_w);
-    FU_REQUIRE(dh >= 1 && dw >= 1, "fu_scene_crops: entry %d: box [%d:%d, %d:%d] is empty", i, E.h0, E.hE, E.w0, E.wE);
-    FU_REQUIRE(dh <= tile_h && dw <= tile_w, "fu_scene_crops: entry %d: box %dx%d is larger than the tile %dx%d", i, dh, dw,
-               tile_h, tile_w);
-    jobs[i] = SceneCropJob{E.scene, E.scene_h, E.scene_w, E.h0, E.w0, dh, dw};
-  }
-  const hipStream_t s = (hipStream_t)stream;
-  if (n > c->scene_cap) {
-    if (c->scene_jobs) {
-      FU_HIP_CHECK(hipDeviceSynchronize());     // an earlier launch may still read the old table
-      FU_HIP_CHECK(hipFree(c->scene_jobs));
-      c->scene_jobs = nullptr;
-      c->scene_cap = 0;
-    }
-    const int cap = std::max(n, 64);
-    FU_HIP_CHECK(hipMalloc(&c->scene_jobs, (size_t)cap * sizeof(SceneCropJob)));
-    c->scene_cap = cap;
-  }
-  FU_HIP_CHECK(hipMemcpyAsync(c->scene_jobs, jobs.data(), (size_t)n * sizeof(SceneCropJob), hipMemcpyHostToDevice, s));
-  return launch_scene_crops(c->scene_jobs, n, C, tile_h, tile_w, norm_mode, global_mean, global_std, pad_value, out,
-                            mean_out, std_out, s);
+  return launch_scene_crops(c->scene_table, n, entries, C, tile_h, tile_w, norm_mode, global_mean, global_std, pad_value, out,
+                            mean_out, std_out, (hipStream_t)stream);
 }
 
 int fu_scene_train_tiles(fu_ctx* c, int n, const fu_scene_train_entry* entries, int C, int tile_h, int tile_w, int norm_mode,
                          const float* global_mean, const float* global_std, float pad_value, int64_t nodata_value,
                          int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out, float* std_out,
                          fu_stream stream) {
-  // every check before anything is launched or copied: a rejected call leaves the stream untouched
   FU_REQUIRE(c && entries && image_out, "fu_scene_train_tiles: null context / entries / image_out");
-  FU_REQUIRE(n >= 1 && C >= 1 && tile_h >= 1 && tile_w >= 1,
-             "fu_scene_train_tiles: n = %d, C = %d, tile %dx%d (all must be >= 1)", n, C, tile_h, tile_w);
-  FU_REQUIRE(norm_mode >= 0 && norm_mode <= 2, "fu_scene_train_tiles: norm_mode must be 0 (None), 1 ('local') or 2 "
-             "('global'), got %d", norm_mode);
-  FU_REQUIRE(norm_mode != 1 || (mean_out && std_out), "fu_scene_train_tiles: norm_mode 'local' needs mean_out / std_out "
-             "[n, C]");
-  FU_REQUIRE(norm_mode != 2 || (global_mean && global_std), "fu_scene_train_tiles: norm_mode 'global' needs the per-channel "
-             "parameters");
-  // fu_scene_crops' bounds, with the target plane counted; the kernel's grid.y walks a plane 1024 pixel runs at a time, so
-  // 2^25 pixels (32768 rows of blocks with one pixel per run) stay inside the 65535 a launch accepts
-  FU_REQUIRE((int64_t)n * (C + 1) <= INT32_MAX && (int64_t)n * C * tile_h * tile_w <= ((int64_t)1 << 40) &&
-             (int64_t)tile_h * tile_w <= ((int64_t)1 << 25),
-             "fu_scene_train_tiles: %d boxes of %d channels, tile %dx%d, are too many for one call", n, C, tile_h, tile_w);
-  const size_t crop_bytes = (size_t)n * sizeof(SceneCropJob);
-  std::vector<unsigned char> table(crop_bytes + (size_t)n * sizeof(SceneTrainAug));
-  SceneCropJob* jobs = reinterpret_cast<SceneCropJob*>(table.data());
-  SceneTrainAug* augs = reinterpret_cast<SceneTrainAug*>(table.data() + crop_bytes);
-  for (int i = 0; i < n; ++i) {
-    const fu_scene_train_entry& E = entries[i];
-    const int dh = E.hE - E.h0, dw = E.wE - E.w0;
-    FU_REQUIRE(E.scene, "fu_scene_train_tiles: entry %d: null scene", i);
-    FU_REQUIRE(!target_out || E.label, "fu_scene_train_tiles: entry %d: target_out given but the entry has no label", i);
-    FU_REQUIRE(E.scene_h >= 1 && E.scene_w >= 1, "fu_scene_train_tiles: entry %d: bad scene size %dx%d", i, E.scene_h,
-               E.scene_w);
-    FU_REQUIRE(E.h0 >= 0 && E.w0 >= 0 && E.hE <= E.scene_h && E.wE <= E.scene_w,
-               "fu_scene_train_tiles: entry %d: box [%d:%d, %d:%d] lies outside its scene %dx%d", i, E.h0, E.hE, E.w0, E.wE,
-               E.scene_h, E.scene_w);
-    FU_REQUIRE(dh >= 1 && dw >= 1, "fu_scene_train_tiles: entry %d: box [%d:%d, %d:%d] is empty", i, E.h0, E.hE, E.w0, E.wE);
-    FU_REQUIRE(dh <= tile_h && dw <= tile_w, "fu_scene_train_tiles: entry %d: box %dx%d is larger than the tile %dx%d", i,
-               dh, dw, tile_h, tile_w);
-    FU_REQUIRE((E.flags & ~(FU_AUG_HFLIP | FU_AUG_VFLIP | FU_AUG_ROTATE)) == 0,
-               "fu_scene_train_tiles: entry %d: unknown flag bits 0x%x", i, (unsigned)E.flags);
-    FU_REQUIRE(std::isfinite(E.angle_deg), "fu_scene_train_tiles: entry %d: the angle is not finite", i);
-    jobs[i] = SceneCropJob{E.scene, E.scene_h, E.scene_w, E.h0, E.w0, dh, dw};
-    augs[i] = SceneTrainAug{E.label, E.flags, E.angle_deg};
-  }
-  const hipStream_t s = (hipStream_t)stream;
-  if (n > c->train_cap) {
-    if (c->train_tab) {
-      FU_HIP_CHECK(hipDeviceSynchronize());     // an earlier launch may still read the old table
-      FU_HIP_CHECK(hipFree(c->train_tab));
-      c->train_tab = nullptr;
-      c->train_cap = 0;
-    }
-    const int cap = std::max(n, 64);
-    FU_HIP_CHECK(hipMalloc(&c->train_tab, (size_t)cap * (sizeof(SceneCropJob) + sizeof(SceneTrainAug))));
-    c->train_cap = cap;
-  }
-  FU_HIP_CHECK(hipMemcpyAsync(c->train_tab, table.data(), table.size(), hipMemcpyHostToDevice, s));
-  return launch_scene_train_tiles(reinterpret_cast<const SceneCropJob*>(c->train_tab),
-                                  reinterpret_cast<const SceneTrainAug*>((const unsigned char*)c->train_tab + crop_bytes), n,
-                                  C, tile_h, tile_w, norm_mode, global_mean, global_std, pad_value, nodata_value,
-                                  target_fill, image_out, target_out, mean_out, std_out, s);
+  return launch_scene_train_tiles(c->train_table, n, entries, C, tile_h, tile_w, norm_mode, global_mean, global_std,
+                                  pad_value, nodata_value, target_fill, image_out, target_out, mean_out, std_out,
+                                  (hipStream_t)stream);
 }
 
 int64_t fu_band_stats_workspace_bytes(int n_channels, int n_bins) {

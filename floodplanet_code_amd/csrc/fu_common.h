@@ -5,6 +5,11 @@
 #include <stdio.h>
 #include <string>
 
+// host tables of include/floodunet.h that the launchers below validate
+struct fu_stitch_entry;
+struct fu_scene_crop;
+struct fu_scene_train_entry;
+
 namespace fu {
 
 typedef unsigned short bf16_t;  // raw bf16 storage
@@ -63,6 +68,13 @@ __host__ __device__ static inline int ceil_div(int a, int b) { return (a + b - 1
 __host__ __device__ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 static inline unsigned host_rcp(int d) { return d <= 1 ? 0u : (unsigned)((((unsigned long long)1) << 32) / (unsigned)d + 1); }
+// blocks of a grid-stride launch: ceil(work / block), clamped to [1, cap]
+static inline int grid_for(int64_t work, int block, int cap = 8192) {
+  int64_t g = ceil_div64(work, block);
+  if (g > cap) g = cap;
+  if (g < 1) g = 1;
+  return (int)g;
+}
 
 // ---- device helpers -------------------------------------------------------------------------
 #ifdef __HIPCC__
@@ -199,6 +211,21 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return base + (bid >> 3);
 }
 
+// Test-time-augmentation view codes (1 = flip(-1), 2 = flip(-2), 4 = transpose, applied in the order transpose, flip(-1),
+// flip(-2)): view_src_pixel maps a pixel of the view to the pixel of the image it shows, view_dst_pixel the other way
+// round (the inverse view).
+__device__ __forceinline__ int view_src_pixel(int code, int y, int x, int H, int W) {
+  if (code & 2) y = H - 1 - y;
+  if (code & 1) x = W - 1 - x;
+  return (code & 4) ? x * W + y : y * W + x;
+}
+__device__ __forceinline__ int view_dst_pixel(int code, int y, int x, int H, int W) {
+  if (code & 4) { const int t = y; y = x; x = t; }
+  if (code & 1) x = W - 1 - x;
+  if (code & 2) y = H - 1 - y;
+  return y * W + x;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -266,6 +293,36 @@ int launch_loss_grad_eff(const float* dlogits, float* out, int64_t n, const floa
 // fp16 guard: guard[0] <- 1 if a gradient is not finite; bookkeeping after the (possibly skipped) Adam launch
 int launch_grad_finite_check(const float* g, int64_t n, int* guard, hipStream_t s);
 int launch_guard_book(int* guard, hipStream_t s);
+
+// A library-owned device copy of a small host table that an entry point rebuilds on every call (fu_stitch_add_batch,
+// fu_scene_crops, fu_scene_train_tiles: one table each, in the context).  The buffer is reused from call to call, so the
+// calls that share a table must be ordered on ONE stream: a call on another stream would overwrite the table under a
+// launch that still reads it (include/floodunet.h says so for each entry point).
+struct DeviceTable {
+  void* dev = nullptr;
+  size_t cap = 0;              // bytes
+  // host[0 .. bytes) -> dev, ordered on s; grows to at least 64 entries of entry_bytes
+  int upload(const void* host, size_t bytes, size_t entry_bytes, hipStream_t s) {
+    if (bytes > cap) {
+      if (dev) {
+        FU_HIP_CHECK(hipDeviceSynchronize());     // an earlier launch may still read the old table
+        FU_HIP_CHECK(hipFree(dev));
+        dev = nullptr;
+        cap = 0;
+      }
+      const size_t want = bytes > 64 * entry_bytes ? bytes : 64 * entry_bytes;
+      FU_HIP_CHECK(hipMalloc(&dev, want));
+      cap = want;
+    }
+    FU_HIP_CHECK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s));
+    return 0;
+  }
+  void release() {
+    if (dev) (void)hipFree(dev);
+    dev = nullptr;
+    cap = 0;
+  }
+};
 
 // ---- kernel launchers (implemented in the .hip files) ----------------------------------------
 // All pointers are device pointers; T-typed buffers are `void*` + Prec.
@@ -416,43 +473,29 @@ int launch_stitch_add(const float* logits_nhwc, int ncls, int cropW, float* canv
                       int w0, int dh, int dw, hipStream_t s);
 int launch_stitch_finalize(float* canvas, const float* weight, int ncls, int64_t npix, int64_t* argmax_out,
                            hipStream_t s);
-// one crop of launch_stitch_add_batch (device copy of a validated fu_stitch_entry)
-struct StitchJob {
-  const float* logits;   // NHWC fp32 logits of the crop's sample (the tile's [0, 0] pixel)
-  float* canvas;
-  float* weight;
-  int canvasW, h0, w0, dh, dw, pad;
-};
-int launch_stitch_add_batch(const StitchJob* jobs_dev, int n, int max_area, int ncls, int cropW, hipStream_t s);
+// fu_stitch_add_batch (probs == false: src = the resident NHWC logits) and fu_stitch_add_batch_probs (true: src = the
+// caller's probabilities), src [n_samples, H, W, ncls] fp32: validates the host table (fn / batch_name go into the
+// messages), uploads it and launches; every check comes before anything is copied or launched
+int launch_stitch_add_batch(DeviceTable& table, const char* fn, const char* batch_name, int n, const fu_stitch_entry* entries,
+                            const float* src, int n_samples, bool probs, int H, int W, int ncls, hipStream_t s);
 int launch_eval_confusion(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int B, int64_t hw,
                           int64_t* counts, hipStream_t s);
 // fu_merge_views: softmax of each view's logits, inverse view, mean in view order -> probs [B, H, W, k] (optional) and
 // confusion counts of its argmax (optional, with target; ADDED to)
 int launch_merge_views(const float* logits_nhwc, int H, int W, int ncls, int B, int n_views, unsigned codes, float* probs,
                        const int64_t* target, int ignore_index, int64_t* counts, hipStream_t s);
-// launch_stitch_add_batch adding probabilities (StitchJob.logits -> the job's [H, W, k] fp32 probabilities)
-int launch_stitch_add_batch_probs(const StitchJob* jobs_dev, int n, int max_area, int ncls, int cropW, hipStream_t s);
 int launch_assemble_tiles(const float* const* srcs, const int* src_channels, int n_src, int B, int H, int W, const int* vh,
                           const int* vw, int norm_mode, const float* gmean, const float* gstd, float pad_value, float* out,
                           float* mean_out, float* std_out, hipStream_t s);
-// one box of launch_scene_crops (device copy of a validated fu_scene_crop)
-struct SceneCropJob {
-  const float* scene;    // fp32 [C, scene_h, scene_w]
-  int scene_h, scene_w, h0, w0, dh, dw;
-};
-// fu_scene_crops: the boxes jobs_dev[0..n-1] as fu_assemble_tiles would assemble them from a zero batch holding each box
-// in the top-left corner (valid size = the box) -- the same kernels, instantiated on scene-box addressing
-int launch_scene_crops(const SceneCropJob* jobs_dev, int n, int C, int H, int W, int norm_mode, const float* gmean,
-                       const float* gstd, float pad_value, float* out, float* mean_out, float* std_out, hipStream_t s);
-// what fu_scene_train_tiles adds to box b of a SceneCropJob table: the scene's raw label raster and the sample's transforms
-struct SceneTrainAug {
-  const uint8_t* label;  // uint8 [scene_h, scene_w], or nullptr (no target)
-  int flags;             // FU_AUG_*
-  float angle;           // degrees
-};
+// fu_scene_crops: the boxes as fu_assemble_tiles would assemble them from a zero batch holding each box in the top-left
+// corner (valid size = the box) -- the same kernels, instantiated on scene-box addressing.  Validates every argument and
+// entry, then uploads the table and launches: a rejected call leaves the stream untouched.
+int launch_scene_crops(DeviceTable& table, int n, const fu_scene_crop* entries, int C, int H, int W, int norm_mode,
+                       const float* gmean, const float* gstd, float pad_value, float* out, float* mean_out, float* std_out,
+                       hipStream_t s);
 // fu_scene_train_tiles: launch_scene_crops composed with launch_augment and the label decode, with no batch in between;
-// tiles of at most 2^25 pixels: grid.y = ceil(runs / 1024) <= 32768 (the callers have checked the arguments)
-int launch_scene_train_tiles(const SceneCropJob* jobs_dev, const SceneTrainAug* augs_dev, int n, int C, int H, int W,
+// checked, uploaded and launched in the same way
+int launch_scene_train_tiles(DeviceTable& table, int n, const fu_scene_train_entry* entries, int C, int H, int W,
                              int norm_mode, const float* gmean, const float* gstd, float pad_value, int64_t nodata_value,
                              int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out, float* std_out,
                              hipStream_t s);

@@ -1,5 +1,7 @@
 // Memory-bound kernels of the UNet training path (gfx950): layout conversion, BatchNorm statistics
-// finalisation and backward, max-pool, bilinear x2 resize, 1x1 head + cross entropy, Adam.
+// finalisation and backward, max-pool, bilinear x2 resize, the transposed-conv helpers, 1x1 head + losses, Adam and
+// the fp16 guard; also the error-message storage.  (Data preparation lives in fu_data.hip, stitching and metrics in
+// fu_eval.hip.)
 // All of them are HBM-bound: 16-byte vector accesses along the NHWC channel dimension, fp32 math,
 // deterministic two-level reductions (per-block partials -> fixed-order finalisation), wave64 shuffles.
 #include "fu_common.h"
@@ -37,13 +39,6 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 const char* get_error() { return g_err; }
-
-static inline int grid_for(int64_t work, int block, int cap = 8192) {
-  int64_t g = ceil_div64(work, block);
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
 
 // ------------------------------------------------------------------------------------------------
 // NCHW fp32 <-> NHWC T
@@ -161,22 +156,8 @@ int launch_gather_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B, int C
 
 // Test-time augmentation (fu_forward_views): the gather above, where destination sample v * B + b is view codes[v] of
 // crop b -- no transformed copy of the batch is ever written.  A view code is a bit set (1 = flip(-1), 2 = flip(-2),
-// 4 = transpose, applied in the order transpose, flip(-1), flip(-2)); `codes` packs 3 bits per view.  view_src_pixel maps
-// a pixel of the view to the pixel of the image it shows, view_dst_pixel the other way round (the inverse view).  The
-// transposing codes need H == W; their plane reads go down columns.
-__device__ __forceinline__ int view_src_pixel(int code, int y, int x, int H, int W) {
-  if (code & 2) y = H - 1 - y;
-  if (code & 1) x = W - 1 - x;
-  return (code & 4) ? x * W + y : y * W + x;
-}
-
-__device__ __forceinline__ int view_dst_pixel(int code, int y, int x, int H, int W) {
-  if (code & 4) { const int t = y; y = x; x = t; }
-  if (code & 1) x = W - 1 - x;
-  if (code & 2) y = H - 1 - y;
-  return y * W + x;
-}
-
+// 4 = transpose, applied in the order transpose, flip(-1), flip(-2)); `codes` packs 3 bits per view (view_src_pixel in
+// fu_common.h).  The transposing codes need H == W; their plane reads go down columns.
 template <typename T>
 __global__ __launch_bounds__(256) void k_gather_views_nchw_to_nhwc(SrcList S, T* __restrict__ dst, int C, int H, int W,
                                                                     int cpad, int ch_off, int B, unsigned codes) {
@@ -1889,986 +1870,6 @@ int launch_head_bwd(Prec p, const float* dlogits_nhwc, const void* y, const floa
     if (bnb) *fuse->tiles_out = nblk;
     return 0;
   });
-}
-
-// ------------------------------------------------------------------------------------------------
-// On-GPU tile augmentation (datasets/base_dataset.py:494-555): per sample hflip -> vflip -> rotate(angle) with
-// torchvision's tensor semantics (nearest, expand=False, centre = image centre, zero fill), applied identically to
-// the image [B,C,H,W] fp32 and the target [B,H,W] int64.  One gather pass: the three transforms are composed into a
-// single source coordinate per output pixel.
-// ------------------------------------------------------------------------------------------------
-__global__ void k_augment(const float* __restrict__ img, const int64_t* __restrict__ tgt, float* __restrict__ img_o,
-                          int64_t* __restrict__ tgt_o, const int* __restrict__ flags, const float* __restrict__ angle,
-                          int C, int H, int W, int64_t target_fill, int64_t total) {
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    const int ox = (int)(idx % W);
-    const int64_t r = idx / W;
-    const int oy = (int)(r % H);
-    const int b = (int)(r / H);
-    const int f = flags[b];
-    int sx = ox, sy = oy;
-    bool inside = true;
-    if (f & 4) {
-      // torchvision F.rotate -> affine_grid + grid_sample(nearest, align_corners=False).  Index arithmetic: bit-exact
-      // with oracle/unet_oracle.py:augment -- the same fp32 operations in the same order, each rounded on its own (no
-      // fma contraction), cos / sin evaluated in double and rounded once to float, round-half-even.
-#pragma clang fp contract(off)
-      const float th = angle[b] * 0.017453292519943295f;
-      const float cs = (float)cos((double)th), sn = (float)sin((double)th);
-      const float xc = ((float)ox + 0.5f) - 0.5f * (float)W, yc = ((float)oy + 0.5f) - 0.5f * (float)H;
-      const float px = cs * xc, qx = sn * yc, py = sn * xc, qy = cs * yc;
-      const float xs = ((px - qx) + 0.5f * (float)W) - 0.5f;
-      const float ys = ((py + qy) + 0.5f * (float)H) - 0.5f;
-      sx = (int)nearbyintf(xs);
-      sy = (int)nearbyintf(ys);
-      inside = sx >= 0 && sx < W && sy >= 0 && sy < H;
-    }
-    if (f & 2) sy = H - 1 - sy;   // the rotate input is the v-flipped, h-flipped tile
-    if (f & 1) sx = W - 1 - sx;
-    if (tgt_o) tgt_o[idx] = inside ? tgt[((int64_t)b * H + sy) * W + sx] : target_fill;
-    for (int c = 0; c < C; ++c) {
-      const int64_t o = (((int64_t)b * C + c) * H + oy) * W + ox;
-      img_o[o] = inside ? img[(((int64_t)b * C + c) * H + sy) * W + sx] : 0.f;
-    }
-  }
-}
-
-int launch_augment(const float* img, const int64_t* tgt, float* img_o, int64_t* tgt_o, const int* flags,
-                   const float* angle, int B, int C, int H, int W, int64_t target_fill, hipStream_t s) {
-  const int64_t total = (int64_t)B * H * W;
-  hipLaunchKernelGGL(k_augment, dim3(grid_for(total, 256, 4096)), dim3(256), 0, s, img, tgt, img_o, tgt_o, flags, angle,
-                     C, H, W, target_fill, total);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Tile assembly: per-tile normalisation (base_dataset.py:77-113), edge-crop buffer
-// (base_dataset.py:271-325) and multi-sensor channel concatenation (ef_model.py:28-44 / stacked sensors) of a whole batch
-// that is already in HBM, instead of per item in DataLoader workers.
-// ------------------------------------------------------------------------------------------------
-
-// How k_tile_stats / k_assemble_tiles address the (sample, channel) planes they read: the plane's first valid pixel, its
-// row stride and the sample's valid crop size.  Both kernels are instantiated once per form, so fu_scene_crops runs the
-// very arithmetic of fu_assemble_tiles (same values, same order) and equals cut-then-assemble bit for bit.
-struct BatchPlanes {        // fu_assemble_tiles: sample b of the SrcList batch, crop in the top-left corner of the tile
-  SrcList S;
-  int H, W;
-  const int* vh;
-  const int* vw;
-  __device__ __forceinline__ const float* plane(int b, int c) const {
-    int si = 0;
-    for (int k = 1; k < S.n; ++k) si = c >= S.coff[k] ? k : si;
-    return S.p[si] + ((int64_t)b * S.c[si] + (c - S.coff[si])) * H * W;
-  }
-  __device__ __forceinline__ int64_t stride(int) const { return W; }
-  // (the crop sizes come from device memory: clamp, an oversized or negative entry must not read past the plane)
-  __device__ __forceinline__ int valid_h(int b) const { return vh ? min(max(vh[b], 0), H) : H; }
-  __device__ __forceinline__ int valid_w(int b) const { return vw ? min(max(vw[b], 0), W) : W; }
-};
-
-struct ScenePlanes {        // fu_scene_crops: box b of a resident scene [C, scene_h, scene_w] (boxes validated on the host)
-  const SceneCropJob* __restrict__ jobs;
-  __device__ __forceinline__ const float* plane(int b, int c) const {
-    const SceneCropJob& J = jobs[b];
-    return J.scene + ((int64_t)c * J.scene_h + J.h0) * J.scene_w + J.w0;
-  }
-  __device__ __forceinline__ int64_t stride(int b) const { return jobs[b].scene_w; }
-  __device__ __forceinline__ int valid_h(int b) const { return jobs[b].dh; }
-  __device__ __forceinline__ int valid_w(int b) const { return jobs[b].dw; }
-};
-
-// one block per (sample, channel): mean and POPULATION std (numpy .mean / .std, ddof = 0) over the valid crop, two passes
-// (the plane stays in L2), fp64 accumulation, fixed-order block reduction
-template <class Planes>
-__global__ __launch_bounds__(256) void k_tile_stats(Planes P, int Ctot, float* __restrict__ mean_o,
-                                                    float* __restrict__ std_o) {
-  __shared__ double sm[256];
-  const int b = blockIdx.x / Ctot, c = blockIdx.x - b * Ctot;
-  const float* plane = P.plane(b, c);
-  const int64_t st = P.stride(b);
-  const int h = P.valid_h(b), w = P.valid_w(b);
-  const int n = h * w;
-  auto block_sum = [&](double v) {
-    sm[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-      if ((int)threadIdx.x < off) sm[threadIdx.x] += sm[threadIdx.x + off];
-      __syncthreads();
-    }
-    const double r = sm[0];
-    __syncthreads();
-    return r;
-  };
-  double a = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) a += (double)plane[(i / w) * st + (i % w)];
-  const double mean = n > 0 ? block_sum(a) / n : 0.0;
-  double q = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) { const double dlt = (double)plane[(i / w) * st + (i % w)] - mean; q += dlt * dlt; }
-  const double var = n > 0 ? block_sum(q) / n : 1.0;
-  if (threadIdx.x == 0) { mean_o[blockIdx.x] = (float)mean; std_o[blockIdx.x] = (float)sqrt(var); }
-}
-
-// out[b][c][y][x] = inside the valid crop ? (src - mean[b][c]) / std[b][c] : pad_value
-template <class Planes>
-__global__ void k_assemble_tiles(Planes P, int Ctot, int H, int W, const float* __restrict__ mean,
-                                 const float* __restrict__ stdv, int per_sample, float pad_value, float* __restrict__ out,
-                                 int64_t total) {
-#pragma clang fp contract(off)      // image -= mean; image /= std: two roundings, as numpy does them
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    const int x = (int)(idx % W);
-    int64_t r = idx / W;
-    const int y = (int)(r % H); r /= H;
-    const int c = (int)(r % Ctot);
-    const int b = (int)(r / Ctot);
-    const bool inside = y < P.valid_h(b) && x < P.valid_w(b);
-    float v = pad_value;
-    if (inside) {
-      v = P.plane(b, c)[y * P.stride(b) + x];
-      if (mean) {
-        const int mi = per_sample ? b * Ctot + c : c;
-        const float d = v - mean[mi];
-        v = d / stdv[mi];
-      }
-    }
-    out[idx] = v;
-  }
-}
-
-// norm_mode 1 ('local'): k_tile_stats into mean_out / std_out, then k_assemble_tiles; 0 / 2: k_assemble_tiles only.  The
-// callers have checked the arguments.
-template <class Planes>
-int launch_tiles(const Planes& P, int B, int Ctot, int H, int W, int norm_mode, const float* gmean, const float* gstd,
-                 float pad_value, float* out, float* mean_out, float* std_out, hipStream_t s) {
-  const float *mean = nullptr, *stdv = nullptr;
-  int per_sample = 0;
-  if (norm_mode == 1) {
-    hipLaunchKernelGGL(k_tile_stats<Planes>, dim3(B * Ctot), dim3(256), 0, s, P, Ctot, mean_out, std_out);
-    FU_LAUNCH_CHECK();
-    mean = mean_out; stdv = std_out; per_sample = 1;
-  } else if (norm_mode == 2) {
-    mean = gmean; stdv = gstd;
-  }
-  const int64_t total = (int64_t)B * Ctot * H * W;
-  hipLaunchKernelGGL(k_assemble_tiles<Planes>, dim3(grid_for(total, 256)), dim3(256), 0, s, P, Ctot, H, W, mean, stdv,
-                     per_sample, pad_value, out, total);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------------------
-// Lanczos-4 resampling of a batch of tiles (round 4).  The reference resamples the WHOLE raster to the
-// label raster's size for every item it loads (floodplanet.py:338-340 -> utils_image.py:11-54, cv2.INTER_LANCZOS4) and then cuts
-// the tile out.  Lanczos is local: tile rows [Y0, Y0 + TH) of the resampled raster depend on a window of ~TH * scale + 8 source
-// rows, so the host ships that window and two 8-tap tables per tile axis (index into the window, weight) and the device computes
-//     out[b][c][y][x] = sum_kx wx[b][x][kx] * ( sum_ky wy[b][y][ky] * win[b][c][iy[b][y][ky]][ix[b][x][kx]] )
-// in fp32 with the taps accumulated in order and multiply / add rounded separately -- the arithmetic of the numpy restatement
-// (datasets/resize.py: rows first, then columns), so the tile equals the crop of the host's whole-raster result bit for bit.
-// scale_mode = the sensor scaling that follows the crop in the reference (floodplanet.py:347 / :406 / :467 / :525).
-// One thread per output pixel; the window (a few KB per tile and band) is served from L2.
-// ------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_resize_lanczos4_tiles(const float* __restrict__ win, int C, int win_h, int win_w,
-                                                               const int* __restrict__ iy, const float* __restrict__ wy,
-                                                               const int* __restrict__ ix, const float* __restrict__ wx,
-                                                               int TH, int TW, int scale_mode, float* __restrict__ out) {
-#pragma clang fp contract(off)
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  const int bc = blockIdx.z, b = bc / C;
-  if (x >= TW || y >= TH) return;
-  const float* w = win + (size_t)bc * win_h * win_w;
-  const int* iyb = iy + ((size_t)b * TH + y) * 8;
-  const float* wyb = wy + ((size_t)b * TH + y) * 8;
-  const int* ixb = ix + ((size_t)b * TW + x) * 8;
-  const float* wxb = wx + ((size_t)b * TW + x) * 8;
-  int ry[8], cx[8];
-  float fy[8], fx[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { ry[k] = iyb[k] * win_w; fy[k] = wyb[k]; cx[k] = ixb[k]; fx[k] = wxb[k]; }
-  float o = 0.f;
-#pragma unroll
-  for (int kx = 0; kx < 8; ++kx) {
-    float t = 0.f;
-#pragma unroll
-    for (int ky = 0; ky < 8; ++ky) {
-      const float p = fy[ky] * w[ry[ky] + cx[kx]];      // (two roundings: numpy multiplies, then adds)
-      t = t + p;
-    }
-    const float q = fx[kx] * t;
-    o = o + q;
-  }
-  if (scale_mode == 1) o = fminf(fmaxf((o + 50.f) / 100.f, 0.f), 1.f);            // S1 (dB): clip((x + 50) / 100, 0, 1), NaN -> 0
-  else if (scale_mode == 2) o = fminf(fmaxf(o / 4096.f, 0.f), 1.f);                // S2: clip(x / 2^12, 0, 1)
-  else if (scale_mode == 3) o = fminf(fmaxf(o, 0.f), 18607.72f) / 18607.72f;       // L8: clip(x, 0, 18607.72) / 18607.72
-  else if (scale_mode == 4) o = o / 65536.f;                                       // PS stored as uint16: x / 2^16
-  out[((size_t)bc * TH + y) * TW + x] = o;
-}
-
-int launch_resize_lanczos4_tiles(const float* win, int B, int C, int win_h, int win_w, const int* iy, const float* wy,
-                                 const int* ix, const float* wx, int TH, int TW, int scale_mode, float* out, hipStream_t s) {
-  FU_REQUIRE((int64_t)B * C <= 65535 && TH >= 1 && TW >= 1 && win_h >= 1 && win_w >= 1, "resize_lanczos4_tiles: bad shape");
-  // grid.y walks the output rows 4 at a time, and the kernel indexes a window plane with 32-bit offsets
-  FU_REQUIRE(ceil_div(TH, 4) <= 65535 && (int64_t)win_h * win_w <= INT32_MAX,
-             "resize_lanczos4_tiles: tile of %d rows or window %dx%d too large for one launch", TH, win_h, win_w);
-  FU_REQUIRE(scale_mode >= 0 && scale_mode <= 4, "resize_lanczos4_tiles: scale_mode %d", scale_mode);
-  hipLaunchKernelGGL(k_resize_lanczos4_tiles, dim3(ceil_div(TW, 64), ceil_div(TH, 4), B * C), dim3(256), 0, s, win, C, win_h,
-                     win_w, iy, wy, ix, wx, TH, TW, scale_mode, out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error("k_resize_lanczos4_tiles launch failed: %s", hipGetErrorString(e)); return 2; }
-  return 0;
-}
-
-int launch_assemble_tiles(const float* const* srcs, const int* src_channels, int n_src, int B, int H, int W, const int* vh,
-                          const int* vw, int norm_mode, const float* gmean, const float* gstd, float pad_value, float* out,
-                          float* mean_out, float* std_out, hipStream_t s) {
-  FU_REQUIRE(n_src >= 1 && n_src <= 8, "assemble: 1..8 sources (got %d)", n_src);
-  BatchPlanes P;
-  P.S.n = n_src;
-  int off = 0;
-  for (int k = 0; k < n_src; ++k) {
-    FU_REQUIRE(srcs[k] && src_channels[k] >= 1, "assemble: bad source %d", k);
-    P.S.p[k] = srcs[k]; P.S.c[k] = src_channels[k]; P.S.coff[k] = off; off += src_channels[k];
-  }
-  P.S.coff[n_src] = off;
-  P.H = H; P.W = W; P.vh = vh; P.vw = vw;
-  FU_REQUIRE(norm_mode >= 0 && norm_mode <= 2, "assemble: norm_mode must be 0 (None), 1 ('local') or 2 ('global')");
-  FU_REQUIRE(norm_mode != 1 || (mean_out && std_out), "assemble: norm_mode 'local' needs mean_out / std_out [B, sum C]");
-  FU_REQUIRE(norm_mode != 2 || (gmean && gstd), "assemble: norm_mode 'global' needs the per-channel parameters");
-  return launch_tiles(P, B, off, H, W, norm_mode, gmean, gstd, pad_value, out, mean_out, std_out, s);
-}
-
-int launch_scene_crops(const SceneCropJob* jobs_dev, int n, int C, int H, int W, int norm_mode, const float* gmean,
-                       const float* gstd, float pad_value, float* out, float* mean_out, float* std_out, hipStream_t s) {
-  ScenePlanes P;
-  P.jobs = jobs_dev;
-  return launch_tiles(P, n, C, H, W, norm_mode, gmean, gstd, pad_value, out, mean_out, std_out, s);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Training batches straight from resident scenes (fu_scene_train_tiles): k_assemble_tiles<ScenePlanes> composed with
-// k_augment, and the label decode of FloodplanetTiles._load_label_image, in one pass -- no crop batch is written to HBM
-// and read back.  A block owns one plane (sample b, channel c -- or the sample's target plane) and a run of its pixels;
-// a thread owns PX consecutive pixels of a row at a time and walks the plane, so its stores and those of its wave are
-// contiguous along x (PX = 4: one 16-byte store per image quad, two per int64 target quad; PX = 1 when tile_w % 4 != 0).
-// The flags are uniform per block: samples without the rotate flag take the row copy / reversal loop (16-byte loads too
-// where the source quad is aligned), the others the gather loop with sin / cos evaluated once per thread.  Same fp32
-// operations in the same order as the two kernels it replaces, so the outputs are the same bits.
-// ------------------------------------------------------------------------------------------------
-// the source pixel of output (ox, oy) under rotate: k_augment's arithmetic, operation for operation
-__device__ __forceinline__ bool rotate_source(int ox, int oy, float cs, float sn, int H, int W, int& sx, int& sy) {
-#pragma clang fp contract(off)
-  const float xc = ((float)ox + 0.5f) - 0.5f * (float)W, yc = ((float)oy + 0.5f) - 0.5f * (float)H;
-  const float px = cs * xc, qx = sn * yc, py = sn * xc, qy = cs * yc;
-  const float xs = ((px - qx) + 0.5f * (float)W) - 0.5f;
-  const float ys = ((py + qy) + 0.5f * (float)H) - 0.5f;
-  sx = (int)nearbyintf(xs);
-  sy = (int)nearbyintf(ys);
-  return sx >= 0 && sx < W && sy >= 0 && sy < H;
-}
-
-// (x - mean) / std as k_assemble_tiles rounds it: two operations, two roundings
-__device__ __forceinline__ float normalise(float v, bool norm, float m, float sd) {
-#pragma clang fp contract(off)
-  if (norm) {
-    const float d = v - m;
-    v = d / sd;
-  }
-  return v;
-}
-
-// raw label value -> class (floodplanet.py:586-596): 2 flood -> 1, 0 no data -> nodata_value, anything else -> 0
-__device__ __forceinline__ int64_t decode_label(uint8_t raw, int64_t nodata_value) {
-  return raw == 2 ? (int64_t)1 : (raw == 0 ? nodata_value : (int64_t)0);
-}
-
-template <int PX>
-__device__ __forceinline__ void store_px(float* __restrict__ o, const float (&v)[PX]) {
-  if constexpr (PX == 4) *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-  else o[0] = v[0];
-}
-template <int PX>
-__device__ __forceinline__ void store_px(int64_t* __restrict__ o, const int64_t (&v)[PX]) {
-  if constexpr (PX == 4) {
-    reinterpret_cast<longlong2*>(o)[0] = make_longlong2(v[0], v[1]);
-    reinterpret_cast<longlong2*>(o)[1] = make_longlong2(v[2], v[3]);
-  } else {
-    o[0] = v[0];
-  }
-}
-
-static constexpr int STT_RUNS = 4;     // pixel runs of PX per thread: a block covers 256 * STT_RUNS * PX pixels of its plane
-
-template <int PX>
-__global__ __launch_bounds__(256) void k_scene_train_tiles(const SceneCropJob* __restrict__ jobs,
-                                                           const SceneTrainAug* __restrict__ augs, int C, int H, int W,
-                                                           const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                           int per_sample, float pad_value, int64_t nodata_value,
-                                                           int64_t target_fill, float* __restrict__ img_o,
-                                                           int64_t* __restrict__ tgt_o) {
-  const int planes = C + (tgt_o ? 1 : 0);
-  const int b = blockIdx.x / planes, p = blockIdx.x - b * planes;
-  const SceneCropJob J = jobs[b];
-  const SceneTrainAug A = augs[b];
-  const int QW = W / PX, nq = H * QW;        // PX = 4 only where W % 4 == 0
-  const int q0 = blockIdx.y * (256 * STT_RUNS);
-  const int q1 = min(q0 + 256 * STT_RUNS, nq);
-  const bool is_target = p == C;
-  const bool hf = A.flags & 1, vf = A.flags & 2;
-  // the plane this block reads, from the box's first pixel, and the plane it writes
-  const int64_t box = (int64_t)J.h0 * J.scene_w + J.w0;
-  const float* __restrict__ src = J.scene + (int64_t)(is_target ? 0 : p) * J.scene_h * J.scene_w + box;
-  const uint8_t* __restrict__ lab = A.label ? A.label + box : nullptr;
-  float* __restrict__ io = img_o + ((int64_t)b * C + (is_target ? 0 : p)) * H * W;
-  int64_t* __restrict__ to = tgt_o ? tgt_o + (int64_t)b * H * W : nullptr;
-  const bool norm = mean != nullptr;
-  float m = 0.f, sd = 1.f;
-  if (norm && !is_target) {
-    const int mi = per_sample ? b * C + p : p;
-    m = mean[mi];
-    sd = stdv[mi];
-  }
-
-  if (A.flags & 4) {                          // gather: every pixel has its own source
-    float cs, sn;
-    {
-#pragma clang fp contract(off)
-      const float th = A.angle * 0.017453292519943295f;
-      cs = (float)cos((double)th);
-      sn = (float)sin((double)th);
-    }
-    for (int q = q0 + (int)threadIdx.x; q < q1; q += 256) {
-      const int oy = q / QW, x0 = (q - oy * QW) * PX;
-      int sx[PX], sy[PX];
-      bool in_tile[PX], in_box[PX];
-#pragma unroll
-      for (int j = 0; j < PX; ++j) {
-        in_tile[j] = rotate_source(x0 + j, oy, cs, sn, H, W, sx[j], sy[j]);
-        if (vf) sy[j] = H - 1 - sy[j];        // the rotate input is the v-flipped, h-flipped tile
-        if (hf) sx[j] = W - 1 - sx[j];
-        in_box[j] = in_tile[j] && sy[j] < J.dh && sx[j] < J.dw;
-      }
-      if (is_target) {
-        int64_t v[PX];
-#pragma unroll
-        for (int j = 0; j < PX; ++j)
-          v[j] = in_box[j] ? decode_label(lab[(int64_t)sy[j] * J.scene_w + sx[j]], nodata_value) : target_fill;
-        store_px<PX>(to + (int64_t)oy * W + x0, v);
-      } else {
-        float v[PX];
-#pragma unroll
-        for (int j = 0; j < PX; ++j)
-          v[j] = in_box[j] ? normalise(src[(int64_t)sy[j] * J.scene_w + sx[j]], norm, m, sd)
-                           : (in_tile[j] ? pad_value : 0.f);
-        store_px<PX>(io + (int64_t)oy * W + x0, v);
-      }
-    }
-    return;
-  }
-
-  // no rotation: output row oy is source row oy (or its mirror), copied or reversed
-  for (int q = q0 + (int)threadIdx.x; q < q1; q += 256) {
-    const int oy = q / QW, x0 = (q - oy * QW) * PX;
-    const int sy = vf ? H - 1 - oy : oy;
-    const int lo = hf ? W - PX - x0 : x0;     // source x of the run's lowest address; output j reads lo + (PX - 1 - j) if hf
-    const bool row_in = sy < J.dh;
-    const int64_t off = (int64_t)sy * J.scene_w + lo;
-    if (is_target) {
-      int64_t s[PX], v[PX];
-#pragma unroll
-      for (int k = 0; k < PX; ++k) s[k] = row_in && lo + k < J.dw ? decode_label(lab[off + k], nodata_value) : target_fill;
-#pragma unroll
-      for (int j = 0; j < PX; ++j) v[j] = hf ? s[PX - 1 - j] : s[j];
-      store_px<PX>(to + (int64_t)oy * W + x0, v);
-    } else {
-      float s[PX], v[PX];
-      bool wide = false;
-      if constexpr (PX == 4) {
-        wide = row_in && lo + 3 < J.dw && (reinterpret_cast<uintptr_t>(src + off) & 15) == 0;
-        if (wide) {
-          const float4 t = *reinterpret_cast<const float4*>(src + off);
-          s[0] = t.x; s[1] = t.y; s[2] = t.z; s[3] = t.w;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) s[k] = normalise(s[k], norm, m, sd);
-        }
-      }
-      if (!wide) {
-#pragma unroll
-        for (int k = 0; k < PX; ++k) s[k] = row_in && lo + k < J.dw ? normalise(src[off + k], norm, m, sd) : pad_value;
-      }
-#pragma unroll
-      for (int j = 0; j < PX; ++j) v[j] = hf ? s[PX - 1 - j] : s[j];
-      store_px<PX>(io + (int64_t)oy * W + x0, v);
-    }
-  }
-}
-
-int launch_scene_train_tiles(const SceneCropJob* jobs_dev, const SceneTrainAug* augs_dev, int n, int C, int H, int W,
-                             int norm_mode, const float* gmean, const float* gstd, float pad_value, int64_t nodata_value,
-                             int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out, float* std_out,
-                             hipStream_t s) {
-  const float *mean = nullptr, *stdv = nullptr;
-  int per_sample = 0;
-  if (norm_mode == 1) {                       // the statistics of the un-augmented crop: fu_scene_crops' own kernel
-    ScenePlanes P;
-    P.jobs = jobs_dev;
-    hipLaunchKernelGGL(k_tile_stats<ScenePlanes>, dim3(n * C), dim3(256), 0, s, P, C, mean_out, std_out);
-    FU_LAUNCH_CHECK();
-    mean = mean_out; stdv = std_out; per_sample = 1;
-  } else if (norm_mode == 2) {
-    mean = gmean; stdv = gstd;
-  }
-  const int planes = C + (target_out ? 1 : 0);
-  const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(image_out) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(target_out) & 15) == 0;
-  const int64_t nq = (int64_t)H * (vec ? W / 4 : W);
-  const dim3 grid((unsigned)(n * planes), (unsigned)ceil_div64(nq, (int64_t)256 * STT_RUNS));
-  if (vec)
-    hipLaunchKernelGGL(k_scene_train_tiles<4>, grid, dim3(256), 0, s, jobs_dev, augs_dev, C, H, W, mean, stdv, per_sample,
-                       pad_value, nodata_value, target_fill, image_out, target_out);
-  else
-    hipLaunchKernelGGL(k_scene_train_tiles<1>, grid, dim3(256), 0, s, jobs_dev, augs_dev, C, H, W, mean, stdv, per_sample,
-                       pad_value, nodata_value, target_fill, image_out, target_out);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Streaming per-band statistics of tiles in HBM (fu_band_stats): what misc/compute_dataset_normalization_parameters.py
-// gathers on the host with np.concatenate in a loop -- count, sum, sum of squares, min, max, a histogram and the count of
-// non-finite pixels per channel, ADDED to caller-owned accumulators so that a data set streams through batch by batch.
-// One pass: a thread owns VEC pixels along W of ALL channels (the pixel mask needs every channel of the first source, the
-// finite test every channel of every source), loads them with one 16-byte read per channel, accumulates in registers
-// (fp64 sums), and walks the batch with a grid stride.  Per block: a fixed xor tree over each wave, the waves folded in
-// order through LDS, one row of partials [count, n_nonfinite, C x (sum, sumsq, min, max)] into the workspace; the
-// histogram is counted with integer LDS atomics and written to the workspace once.  k_band_stats_fold then adds the rows
-// in a fixed order (64 strided lanes per channel + xor tree) and k_band_hist_fold the per-block histograms: no
-// floating-point atomic anywhere, so the same calls on the same data give the same bits.
-// ------------------------------------------------------------------------------------------------
-static constexpr int BST_MAX_C = 16;              // channels of all sources together (register accumulators)
-static constexpr int BST_MAX_BLOCKS = 1024;       // rows of partials in the workspace
-static constexpr int BST_HIST_BLOCKS = 256;       // blocks of a histogram launch: one per CU, each with its own LDS histogram
-static constexpr int BST_LDS_WORDS = 38912;       // 152 KiB of the CU's 160 KiB LDS: 9 channels x 4096 bins fit
-static constexpr int BST_MAX_BINS = 65536;
-
-struct BandStatsArgs {
-  BatchPlanes P;
-  int C, B, QW, mask_mode, c_first, n_bins, c_lds;
-  float lo, scale;
-  unsigned* ws_hist;              // [gridDim.x][c_lds * n_bins]
-  unsigned long long* hist;       // [C][n_bins]: channels >= c_lds (an LDS histogram too large) are added here directly
-  double* ws;                     // [gridDim.x][2 + 4 * C]
-};
-
-__device__ __forceinline__ bool bst_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-template <int CMAX, int VEC, bool HIST>
-__global__ __launch_bounds__(HIST ? 512 : 256) void k_band_stats(BandStatsArgs A) {
-  constexpr int T = HIST ? 512 : 256, NW = T / 64;
-  __shared__ double red[NW][2 + 4 * CMAX];
-  __shared__ unsigned sh_hist[HIST ? BST_LDS_WORDS : 1];
-  const int C = A.C, H = A.P.H, W = A.P.W, tid = threadIdx.x;
-  const int nlds = HIST ? A.c_lds * A.n_bins : 0;
-  if (HIST) {
-    for (int i = tid; i < nlds; i += T) sh_hist[i] = 0u;
-    __syncthreads();
-  }
-  double s[CMAX], q[CMAX];
-  float mn[CMAX], mx[CMAX];
-#pragma unroll
-  for (int c = 0; c < CMAX; ++c) { s[c] = 0.0; q[c] = 0.0; mn[c] = INFINITY; mx[c] = -INFINITY; }
-  long long cnt = 0, bad = 0;
-  const unsigned total = (unsigned)A.B * (unsigned)H * (unsigned)A.QW;      // < 2^31 (launch_band_stats checks)
-  for (unsigned idx = blockIdx.x * T + tid; idx < total; idx += gridDim.x * T) {
-    const unsigned r = idx / (unsigned)A.QW;
-    const int x0 = (int)(idx - r * (unsigned)A.QW) * VEC;
-    const int b = (int)(r / (unsigned)H), y = (int)(r - (unsigned)b * (unsigned)H);
-    const int vw = A.P.valid_w(b);
-    if (y >= A.P.valid_h(b) || x0 >= vw) continue;
-    const int off = y * W + x0;
-    float v[CMAX][VEC];
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c) {
-      if (c < C) {
-        const float* p = A.P.plane(b, c) + off;
-        if constexpr (VEC == 4) {
-          const float4 t = *reinterpret_cast<const float4*>(p);
-          v[c][0] = t.x; v[c][1] = t.y; v[c][2] = t.z; v[c][3] = t.w;
-        } else {
-          v[c][0] = *p;
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) v[c][j] = 0.f;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      const bool in = x0 + j < vw;
-      bool fin = true;
-#pragma unroll
-      for (int c = 0; c < CMAX; ++c) fin = fin && bst_finite(v[c][j]);
-      bool take = in && fin;
-      if (A.mask_mode == 1) {       // fp32 sum of the first source's channels, in channel order, is not 0
-        float m = v[0][j];
-#pragma unroll
-        for (int c = 1; c < CMAX; ++c)
-          if (c < A.c_first) m = m + v[c][j];
-        take = take && m != 0.f;
-      }
-      bad += (in && !fin) ? 1 : 0;
-      cnt += take ? 1 : 0;
-#pragma unroll
-      for (int c = 0; c < CMAX; ++c) {
-        if (c < C) {
-          const float x = v[c][j];
-          const double d = take ? (double)x : 0.0;
-          s[c] += d;
-          q[c] += d * d;
-          mn[c] = take ? fminf(mn[c], x) : mn[c];
-          mx[c] = take ? fmaxf(mx[c], x) : mx[c];
-          if (HIST && take) {
-            const float t = (x - A.lo) * A.scale;
-            const int bin = t > 0.f ? (int)fminf(floorf(t), (float)(A.n_bins - 1)) : 0;
-            if (c < A.c_lds) atomicAdd(&sh_hist[c * A.n_bins + bin], 1u);
-            else atomicAdd(&A.hist[(size_t)c * A.n_bins + bin], 1ull);
-          }
-        }
-      }
-    }
-  }
-  // fixed xor tree over the wave, then the waves in order
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o, 64);
-    bad += __shfl_xor(bad, o, 64);
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c) {
-      s[c] += __shfl_xor(s[c], o, 64);
-      q[c] += __shfl_xor(q[c], o, 64);
-      mn[c] = fminf(mn[c], __shfl_xor(mn[c], o, 64));
-      mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], o, 64));
-    }
-  }
-  if (lane == 0) {
-    red[wave][0] = __longlong_as_double(cnt);
-    red[wave][1] = __longlong_as_double(bad);
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c) {
-      red[wave][2 + 4 * c + 0] = s[c];
-      red[wave][2 + 4 * c + 1] = q[c];
-      red[wave][2 + 4 * c + 2] = (double)mn[c];
-      red[wave][2 + 4 * c + 3] = (double)mx[c];
-    }
-  }
-  __syncthreads();
-  double* row = A.ws + (size_t)blockIdx.x * (2 + 4 * C);
-  if (tid < 2) {
-    long long t = 0;
-    for (int w = 0; w < NW; ++w) t += __double_as_longlong(red[w][tid]);
-    row[tid] = __longlong_as_double(t);
-  } else if (tid < 2 + 4 * C) {
-    const int k = (tid - 2) & 3;
-    double t = red[0][tid];
-    for (int w = 1; w < NW; ++w) t = k < 2 ? t + red[w][tid] : (k == 2 ? fmin(t, red[w][tid]) : fmax(t, red[w][tid]));
-    row[tid] = t;
-  }
-  if (HIST) {
-    unsigned* dst = A.ws_hist + (size_t)blockIdx.x * nlds;
-    for (int i = tid; i < nlds; i += T) dst[i] = sh_hist[i];
-  }
-}
-
-// one block of 64 lanes per channel: lane l adds rows l, l + 64, ... in order, then a fixed xor tree; lane 0 adds the
-// result to the caller's accumulators (plain read-modify-write: one owner per channel)
-__global__ __launch_bounds__(64) void k_band_stats_fold(const double* __restrict__ ws, int nblk, int C, BandAccum acc) {
-  const int c = blockIdx.x, l = threadIdx.x;
-  const int stride = 2 + 4 * C;
-  long long cnt = 0, bad = 0;
-  double s = 0.0, q = 0.0, mn = INFINITY, mx = -INFINITY;
-  for (int k = l; k < nblk; k += 64) {
-    const double* row = ws + (size_t)k * stride;
-    cnt += __double_as_longlong(row[0]);
-    bad += __double_as_longlong(row[1]);
-    s += row[2 + 4 * c + 0];
-    q += row[2 + 4 * c + 1];
-    mn = fmin(mn, row[2 + 4 * c + 2]);
-    mx = fmax(mx, row[2 + 4 * c + 3]);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o, 64);
-    bad += __shfl_xor(bad, o, 64);
-    s += __shfl_xor(s, o, 64);
-    q += __shfl_xor(q, o, 64);
-    mn = fmin(mn, __shfl_xor(mn, o, 64));
-    mx = fmax(mx, __shfl_xor(mx, o, 64));
-  }
-  if (l != 0) return;
-  acc.count[c] += cnt;
-  acc.n_nonfinite[c] += bad;
-  acc.sum[c] += s;
-  acc.sumsq[c] += q;
-  acc.vmin[c] = fminf(acc.vmin[c], (float)mn);
-  acc.vmax[c] = fmaxf(acc.vmax[c], (float)mx);
-}
-
-// hist[i] += the blocks' LDS histograms: 64 bins x 4 lanes of blocks per workgroup, one owner per bin
-__global__ __launch_bounds__(256) void k_band_hist_fold(const unsigned* __restrict__ ws_hist, int nblk, int n,
-                                                        long long* __restrict__ hist) {
-  __shared__ long long sm[4][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + tx;
-  long long t = 0;
-  if (i < n) {
-#pragma unroll 8
-    for (int k = ty; k < nblk; k += 4) t += ws_hist[(size_t)k * n + i];
-  }
-  sm[ty][tx] = t;
-  __syncthreads();
-  if (ty == 0 && i < n) hist[i] += (sm[0][tx] + sm[1][tx]) + (sm[2][tx] + sm[3][tx]);
-}
-
-static int band_stats_c_lds(int C, int n_bins) { return n_bins > 0 ? (C < BST_LDS_WORDS / n_bins ? C : BST_LDS_WORDS / n_bins) : 0; }
-static int64_t band_stats_rows_bytes(int C) { return (int64_t)BST_MAX_BLOCKS * (2 + 4 * C) * (int64_t)sizeof(double); }
-
-int64_t band_stats_workspace_bytes(int C, int n_bins) {
-  return band_stats_rows_bytes(C) + (int64_t)BST_HIST_BLOCKS * band_stats_c_lds(C, n_bins) * n_bins * (int64_t)sizeof(unsigned);
-}
-
-template <int CMAX, int VEC>
-static void launch_band_stats_t(bool hist, int nblk, hipStream_t s, const BandStatsArgs& A) {
-  if (hist) hipLaunchKernelGGL((k_band_stats<CMAX, VEC, true>), dim3(nblk), dim3(512), 0, s, A);
-  else hipLaunchKernelGGL((k_band_stats<CMAX, VEC, false>), dim3(nblk), dim3(256), 0, s, A);
-}
-
-// Every check comes before the first launch: a rejected call leaves the stream and the accumulators untouched.
-int launch_band_stats(const float* const* srcs, const int* src_channels, int n_src, int B, int H, int W, const int* vh,
-                      const int* vw, int mask_mode, const BandAccum& acc, void* workspace, int64_t workspace_bytes,
-                      hipStream_t s) {
-  FU_REQUIRE(n_src >= 1 && n_src <= 8, "band_stats: 1..8 sources (got %d)", n_src);
-  FU_REQUIRE(B >= 1 && H >= 1 && W >= 1, "band_stats: B = %d, H = %d, W = %d (all must be >= 1)", B, H, W);
-  FU_REQUIRE(mask_mode == 0 || mask_mode == 1, "band_stats: mask_mode must be 0 (every pixel) or 1 (first source's "
-             "channel sum != 0), got %d", mask_mode);
-  BandStatsArgs A;
-  A.P.S.n = n_src;
-  int off = 0;
-  bool aligned = W % 4 == 0;
-  for (int k = 0; k < n_src; ++k) {
-    FU_REQUIRE(srcs[k] && src_channels[k] >= 1 && src_channels[k] <= BST_MAX_C, "band_stats: bad source %d", k);
-    A.P.S.p[k] = srcs[k]; A.P.S.c[k] = src_channels[k]; A.P.S.coff[k] = off; off += src_channels[k];
-    aligned = aligned && ((uintptr_t)srcs[k] & 15) == 0;
-  }
-  const int C = off;
-  A.P.S.coff[n_src] = C;
-  A.P.H = H; A.P.W = W; A.P.vh = vh; A.P.vw = vw;
-  FU_REQUIRE(C <= BST_MAX_C, "band_stats: %d channels in all, at most %d", C, BST_MAX_C);
-  FU_REQUIRE((int64_t)H * W <= INT32_MAX && (int64_t)B * H * W < ((int64_t)1 << 31),
-             "band_stats: batch of %d tiles of %dx%d is too large for one call", B, H, W);
-  FU_REQUIRE(acc.count && acc.sum && acc.sumsq && acc.vmin && acc.vmax && acc.n_nonfinite,
-             "band_stats: missing accumulators (count, sum, sumsq, min, max, n_nonfinite are all needed)");
-  const bool hist = acc.hist != nullptr;
-  if (hist) {
-    FU_REQUIRE(acc.n_bins >= 1 && acc.n_bins <= BST_MAX_BINS, "band_stats: n_bins = %d out of range 1..%d", acc.n_bins,
-               BST_MAX_BINS);
-    FU_REQUIRE(acc.hi > acc.lo && acc.hi - acc.lo <= 3.0e38f && acc.lo >= -3.0e38f,
-               "band_stats: histogram range needs finite lo < hi (got [%g, %g])", (double)acc.lo, (double)acc.hi);
-  }
-  const int n_bins = hist ? acc.n_bins : 0;
-  FU_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= band_stats_workspace_bytes(C, n_bins),
-             "band_stats: workspace missing, not 16-byte aligned or smaller than fu_band_stats_workspace_bytes = %lld",
-             (long long)band_stats_workspace_bytes(C, n_bins));
-  const int VEC = aligned ? 4 : 1;
-  A.C = C; A.B = B; A.QW = W / VEC; A.mask_mode = mask_mode; A.c_first = src_channels[0];
-  A.n_bins = n_bins; A.c_lds = band_stats_c_lds(C, n_bins);
-  A.lo = acc.lo; A.scale = hist ? (float)n_bins / (acc.hi - acc.lo) : 0.f;
-  A.ws = (double*)workspace;
-  A.ws_hist = (unsigned*)((char*)workspace + band_stats_rows_bytes(C));
-  A.hist = (unsigned long long*)acc.hist;
-  const int T = hist ? 512 : 256;
-  const int64_t units = (int64_t)B * H * A.QW;
-  const int64_t want = ceil_div64(units, T), cap = hist ? BST_HIST_BLOCKS : BST_MAX_BLOCKS;
-  const int nblk = (int)(want < cap ? want : cap);
-#define FU_BST(CM) (VEC == 4 ? launch_band_stats_t<CM, 4>(hist, nblk, s, A) : launch_band_stats_t<CM, 1>(hist, nblk, s, A))
-  if (C <= 4) FU_BST(4);
-  else if (C <= 8) FU_BST(8);
-  else if (C <= 12) FU_BST(12);
-  else FU_BST(16);
-#undef FU_BST
-  FU_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_band_stats_fold, dim3(C), dim3(64), 0, s, (const double*)A.ws, nblk, C, acc);
-  FU_LAUNCH_CHECK();
-  if (hist && A.c_lds > 0) {
-    const int n = A.c_lds * n_bins;
-    hipLaunchKernelGGL(k_band_hist_fold, dim3(ceil_div(n, 64)), dim3(256), 0, s, (const unsigned*)A.ws_hist, nblk, n,
-                       (long long*)acc.hist);
-    FU_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Inference stitching (utils/utils_image.py:410-494, predict.py:329-347): softmax of a crop's logits is added into an
-// overlap-averaging canvas, canvas[h0:hE, w0:wE, :] += p[:dh, :dw, :], weight += 1; finalisation divides by
-// (weight + 1e-5) and emits the argmax map.
-// ------------------------------------------------------------------------------------------------
-__global__ void k_stitch_add(const float* __restrict__ logits_nhwc, int ncls, int cropW, float* __restrict__ canvas,
-                             float* __restrict__ weight, int canvasW, int h0, int w0, int dh, int dw) {
-  const int64_t total = (int64_t)dh * dw;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    const int x = (int)(idx % dw), y = (int)(idx / dw);
-    const float* z = logits_nhwc + ((int64_t)y * cropW + x) * ncls;
-    float m = -INFINITY, e[HEAD_MAX_CLS], se = 0.f;
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) m = fmaxf(m, z[k]);
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k) { e[k] = k < ncls ? expf(z[k] - m) : 0.f; se += e[k]; }
-    const float inv = 1.f / se;
-    const int64_t o = (int64_t)(h0 + y) * canvasW + (w0 + x);
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) canvas[o * ncls + k] += e[k] * inv;
-    weight[o] += 1.f;
-  }
-}
-
-__global__ void k_stitch_finalize(float* __restrict__ canvas, const float* __restrict__ weight, int ncls,
-                                  int64_t npix, int64_t* __restrict__ argmax_out) {
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
-    const float inv = 1.f / (weight[p] + 1e-5f);
-    float best = -INFINITY;
-    int am = 0;
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k) {
-      if (k < ncls) {
-        const float v = canvas[p * ncls + k] * inv;
-        canvas[p * ncls + k] = v;
-        if (v > best) { best = v; am = k; }
-      }
-    }
-    if (argmax_out) argmax_out[p] = am;
-  }
-}
-
-int launch_stitch_add(const float* logits_nhwc, int ncls, int cropW, float* canvas, float* weight, int canvasW, int h0,
-                      int w0, int dh, int dw, hipStream_t s) {
-  hipLaunchKernelGGL(k_stitch_add, dim3(grid_for((int64_t)dh * dw, 256, 2048)), dim3(256), 0, s, logits_nhwc, ncls,
-                     cropW, canvas, weight, canvasW, h0, w0, dh, dw);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-int launch_stitch_finalize(float* canvas, const float* weight, int ncls, int64_t npix, int64_t* argmax_out,
-                           hipStream_t s) {
-  hipLaunchKernelGGL(k_stitch_finalize, dim3(grid_for(npix, 256, 2048)), dim3(256), 0, s, canvas, weight, ncls, npix,
-                     argmax_out);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// Batched stitching: jobs[0..n-1] in one launch, bit-identical to k_stitch_add for each job in table order.  A canvas
-// pixel belongs to the first job that covers it; that thread reads the canvas once, adds the softmax of every covering
-// job in table order with the very expression of k_stitch_add (same rounding sequence), and writes once -- overlapping
-// crops of one batch (stride < crop) never race and need no float atomics.  blockIdx.y walks the jobs, blockIdx.x the
-// pixels of the job's box; the ownership scan over earlier jobs is uniform across the block (scalar loads of the table).
-__device__ __forceinline__ bool stitch_covers(const StitchJob& J, const float* canvas, int cy, int cx) {
-  return J.canvas == canvas && cy >= J.h0 && cy < J.h0 + J.dh && cx >= J.w0 && cx < J.w0 + J.dw;
-}
-
-__global__ void k_stitch_add_batch(const StitchJob* __restrict__ jobs, int n, int ncls, int cropW) {
-  for (int e = blockIdx.y; e < n; e += gridDim.y) {
-    const StitchJob J = jobs[e];
-    const int64_t total = (int64_t)J.dh * J.dw;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-      const int cy = J.h0 + (int)(idx / J.dw), cx = J.w0 + (int)(idx % J.dw);
-      bool owner = true;
-      for (int j = 0; j < e && owner; ++j) owner = !stitch_covers(jobs[j], J.canvas, cy, cx);
-      if (!owner) continue;
-      const int64_t o = (int64_t)cy * J.canvasW + cx;
-      float acc[HEAD_MAX_CLS], wacc = J.weight[o];
-#pragma unroll
-      for (int k = 0; k < HEAD_MAX_CLS; ++k) acc[k] = k < ncls ? J.canvas[o * ncls + k] : 0.f;
-      for (int j = e; j < n; ++j) {
-        const StitchJob Q = jobs[j];
-        if (!stitch_covers(Q, J.canvas, cy, cx)) continue;
-        const float* z = Q.logits + ((int64_t)(cy - Q.h0) * cropW + (cx - Q.w0)) * ncls;
-        float m = -INFINITY, ex[HEAD_MAX_CLS], se = 0.f;
-#pragma unroll
-        for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) m = fmaxf(m, z[k]);
-#pragma unroll
-        for (int k = 0; k < HEAD_MAX_CLS; ++k) { ex[k] = k < ncls ? expf(z[k] - m) : 0.f; se += ex[k]; }
-        const float inv = 1.f / se;
-#pragma unroll
-        for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) acc[k] += ex[k] * inv;
-        wacc += 1.f;
-      }
-#pragma unroll
-      for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) J.canvas[o * ncls + k] = acc[k];
-      J.weight[o] = wacc;
-    }
-  }
-}
-
-int launch_stitch_add_batch(const StitchJob* jobs_dev, int n, int max_area, int ncls, int cropW, hipStream_t s) {
-  const dim3 grid(grid_for(max_area, 256, 1024), n < 65535 ? n : 65535);
-  hipLaunchKernelGGL(k_stitch_add_batch, grid, dim3(256), 0, s, jobs_dev, n, ncls, cropW);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Per-sample confusion counts of the resident logits (prediction metrics, predict.py:236-250): the argmax and pixel rule
-// of k_ce_loss without the loss.  blockIdx.y = sample; a block histograms its pixels in LDS, then adds the non-zero bins
-// to counts[b][t * k + p] with 64-bit integer atomics (exact, order-free), so there is no finalisation pass.
-// ------------------------------------------------------------------------------------------------
-__global__ void k_eval_confusion(const float* __restrict__ logits, const int64_t* __restrict__ target, int ncls,
-                                 int ignore_index, int64_t hw, unsigned long long* __restrict__ counts) {
-  __shared__ unsigned int hist[HEAD_MAX_CLS * HEAD_MAX_CLS];
-  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x) hist[i] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.y * hw;
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < hw; q += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t p = base + q;
-    const int64_t t = target[p];
-    if (t == (int64_t)ignore_index || t < 0 || t >= ncls) continue;
-    float m = -INFINITY;
-    int am = 0;
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k) {
-      if (k < ncls) {
-        const float z = logits[p * ncls + k];
-        if (z > m) { m = z; am = k; }
-      }
-    }
-    atomicAdd(&hist[(int)t * ncls + am], 1u);
-  }
-  __syncthreads();
-  unsigned long long* out = counts + (int64_t)blockIdx.y * ncls * ncls;
-  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x)
-    if (hist[i]) atomicAdd(&out[i], (unsigned long long)hist[i]);
-}
-
-int launch_eval_confusion(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int B, int64_t hw,
-                          int64_t* counts, hipStream_t s) {
-  const dim3 grid(grid_for(hw, CE_BLOCK, 64), B);
-  hipLaunchKernelGGL(k_eval_confusion, grid, dim3(CE_BLOCK), 0, s, logits_nhwc, target, ncls, ignore_index, hw,
-                     reinterpret_cast<unsigned long long*>(counts));
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Test-time augmentation merge (fu_merge_views): P_b = (sum over views v, in view order, of inverse view codes[v] of
-// softmax(logits of sample v * B + b)) / T, fp32 NHWC [B, H, W, k].  One thread per (crop, pixel): it reads the k logits
-// at the pixel's place in each view (view_dst_pixel), takes the softmax with the expression of k_stitch_add_batch and
-// keeps the sum in registers.  Blocks cover 16 x 16 pixel tiles, so a transposing view reads a 16 x 16 tile of its
-// logits too (whole 16-pixel row segments per block, not one pixel per row).  With counts, argmax P (first maximum wins)
-// is histogrammed against the target as in k_eval_confusion: LDS bins, then 64-bit integer atomics.
-// ------------------------------------------------------------------------------------------------
-static constexpr int MERGE_TILE = 16;
-
-__global__ __launch_bounds__(MERGE_TILE * MERGE_TILE) void k_merge_views(
-    const float* __restrict__ logits, int H, int W, int ncls, int B, int T, unsigned codes, float* __restrict__ probs,
-    const int64_t* __restrict__ target, int ignore_index, unsigned long long* __restrict__ counts) {
-  __shared__ unsigned int hist[HEAD_MAX_CLS * HEAD_MAX_CLS];
-  if (counts) {
-    for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x) hist[i] = 0;
-    __syncthreads();
-  }
-  const int b = blockIdx.z;
-  const int x = blockIdx.x * MERGE_TILE + (int)(threadIdx.x % MERGE_TILE);
-  const int y = blockIdx.y * MERGE_TILE + (int)(threadIdx.x / MERGE_TILE);
-  const int64_t hw = (int64_t)H * W;
-  if (y < H && x < W) {
-    float acc[HEAD_MAX_CLS];
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k) acc[k] = 0.f;
-    for (int v = 0; v < T; ++v) {
-      const int q = view_dst_pixel((codes >> (3 * v)) & 7, y, x, H, W);
-      const float* z = logits + (((int64_t)v * B + b) * hw + q) * ncls;
-      float m = -INFINITY, ex[HEAD_MAX_CLS], se = 0.f;
-#pragma unroll
-      for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) m = fmaxf(m, z[k]);
-#pragma unroll
-      for (int k = 0; k < HEAD_MAX_CLS; ++k) { ex[k] = k < ncls ? expf(z[k] - m) : 0.f; se += ex[k]; }
-      const float inv = 1.f / se;
-#pragma unroll
-      for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) acc[k] += ex[k] * inv;
-    }
-    const int64_t p = (int64_t)b * hw + (int64_t)y * W + x;
-    const float fT = (float)T;
-    float pm = -INFINITY;
-    int am = 0;
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k) {
-      if (k < ncls) {
-        const float pk = acc[k] / fT;
-        if (probs) probs[p * ncls + k] = pk;
-        if (pk > pm) { pm = pk; am = k; }
-      }
-    }
-    if (counts) {
-      const int64_t t = target[p];
-      if (t != (int64_t)ignore_index && t >= 0 && t < ncls) atomicAdd(&hist[(int)t * ncls + am], 1u);
-    }
-  }
-  if (counts) {
-    __syncthreads();
-    unsigned long long* out = counts + (int64_t)b * ncls * ncls;
-    for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x)
-      if (hist[i]) atomicAdd(&out[i], (unsigned long long)hist[i]);
-  }
-}
-
-int launch_merge_views(const float* logits_nhwc, int H, int W, int ncls, int B, int n_views, unsigned codes, float* probs,
-                       const int64_t* target, int ignore_index, int64_t* counts, hipStream_t s) {
-  FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS && B >= 1 && B <= 65535 && n_views >= 1 && n_views <= 8,
-             "merge_views: bad geometry (classes %d, batch %d, views %d)", ncls, B, n_views);
-  const dim3 grid((unsigned)ceil_div(W, MERGE_TILE), (unsigned)ceil_div(H, MERGE_TILE), (unsigned)B);
-  hipLaunchKernelGGL(k_merge_views, grid, dim3(MERGE_TILE * MERGE_TILE), 0, s, logits_nhwc, H, W, ncls, B, n_views, codes,
-                     probs, target, ignore_index, reinterpret_cast<unsigned long long*>(counts));
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// fu_stitch_add_batch_probs: k_stitch_add_batch's ownership scheme and table order (the first job covering a canvas pixel
-// owns it, no float atomics), adding the given probabilities ([batch, H, W, k] fp32; StitchJob.logits points at the
-// job's sample) instead of a softmax of the logits.
-__global__ void k_stitch_add_batch_probs(const StitchJob* __restrict__ jobs, int n, int ncls, int cropW) {
-  for (int e = blockIdx.y; e < n; e += gridDim.y) {
-    const StitchJob J = jobs[e];
-    const int64_t total = (int64_t)J.dh * J.dw;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-      const int cy = J.h0 + (int)(idx / J.dw), cx = J.w0 + (int)(idx % J.dw);
-      bool owner = true;
-      for (int j = 0; j < e && owner; ++j) owner = !stitch_covers(jobs[j], J.canvas, cy, cx);
-      if (!owner) continue;
-      const int64_t o = (int64_t)cy * J.canvasW + cx;
-      float acc[HEAD_MAX_CLS], wacc = J.weight[o];
-#pragma unroll
-      for (int k = 0; k < HEAD_MAX_CLS; ++k) acc[k] = k < ncls ? J.canvas[o * ncls + k] : 0.f;
-      for (int j = e; j < n; ++j) {
-        const StitchJob Q = jobs[j];
-        if (!stitch_covers(Q, J.canvas, cy, cx)) continue;
-        const float* pr = Q.logits + ((int64_t)(cy - Q.h0) * cropW + (cx - Q.w0)) * ncls;
-#pragma unroll
-        for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) acc[k] += pr[k];
-        wacc += 1.f;
-      }
-#pragma unroll
-      for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) J.canvas[o * ncls + k] = acc[k];
-      J.weight[o] = wacc;
-    }
-  }
-}
-
-int launch_stitch_add_batch_probs(const StitchJob* jobs_dev, int n, int max_area, int ncls, int cropW, hipStream_t s) {
-  const dim3 grid(grid_for(max_area, 256, 1024), n < 65535 ? n : 65535);
-  hipLaunchKernelGGL(k_stitch_add_batch_probs, grid, dim3(256), 0, s, jobs_dev, n, ncls, cropW);
-  FU_LAUNCH_CHECK();
-  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -16,13 +16,38 @@ from .._lib import check, ptr
 NORM_MODES = {None: 0, "local": 1, "global": 2}
 
 
+def _norm_mode(norm_mode) -> int:
+    if norm_mode not in NORM_MODES:
+        raise NotImplementedError(f'Normalization mode "{norm_mode}" not implemented.')      # base_dataset.py:106-108
+    return NORM_MODES[norm_mode]
+
+
+def _global_norm(mode: int, global_params, dev, mean: torch.Tensor, std: torch.Tensor):
+    """-> the per-channel (mean, std) on dev that the C ABI takes in mode 2 ('global'), else (None, None); in mode 2 the
+    returned mean / std rows are pre-filled with them (the kernels write those only in mode 1)."""
+    if mode != 2:
+        return None, None
+    if global_params is None:
+        raise ValueError("norm_mode 'global' needs (mean, std) per channel")
+    gm, gs = (t.to(dev).float().contiguous() for t in global_params)
+    mean[:] = gm
+    std[:] = gs
+    return gm, gs
+
+
+def _check_scene(where: str, scene: torch.Tensor, Cc: int, dev) -> None:
+    if scene.dim() != 3 or scene.shape[0] != Cc or scene.dtype != torch.float32 or not scene.is_contiguous() \
+            or scene.device != dev or dev.type != "cuda":
+        raise ValueError(f"{where}: scenes must be contiguous fp32 [{Cc}, H, W] on one ROCm device, got "
+                         f"{tuple(scene.shape)} {scene.dtype} on {scene.device}")
+
+
 def assemble_tiles(sources: Sequence[torch.Tensor], norm_mode: Optional[str] = None,
                    valid_hw: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                    global_params: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pad_value: float = 0.0):
     """sources: fp32 NCHW [B, C_k, H, W] tiles on a ROCm device (raw crops in the top-left corner of the nominal tile).
     -> (image [B, sum C, H, W], mean [B, sum C, 1, 1], std [B, sum C, 1, 1]) as the item dict of the reference carries them."""
-    if norm_mode not in NORM_MODES:
-        raise NotImplementedError(f'Normalization mode "{norm_mode}" not implemented.')      # base_dataset.py:106-108
+    mode = _norm_mode(norm_mode)
     if not sources or sources[0].device.type != "cuda":
         raise RuntimeError("assemble_tiles runs only on a ROCm GPU; there is no CPU fallback")
     srcs = [s.contiguous().float() for s in sources]
@@ -33,16 +58,9 @@ def assemble_tiles(sources: Sequence[torch.Tensor], norm_mode: Optional[str] = N
     dev = srcs[0].device
     ctot = sum(s.shape[1] for s in srcs)
     out = torch.empty(B, ctot, H, W, dtype=torch.float32, device=dev)
-    mode = NORM_MODES[norm_mode]
     mean = torch.zeros(B, ctot, dtype=torch.float32, device=dev)
     std = torch.ones(B, ctot, dtype=torch.float32, device=dev)
-    gm = gs = None
-    if mode == 2:
-        if global_params is None:
-            raise ValueError("norm_mode 'global' needs (mean, std) per channel")
-        gm, gs = (t.to(dev).float().contiguous() for t in global_params)
-        mean[:] = gm
-        std[:] = gs
+    gm, gs = _global_norm(mode, global_params, dev, mean, std)
     vh = vw = None
     if valid_hw is not None:
         vh, vw = (t.to(dev).to(torch.int32).contiguous() for t in valid_hw)
@@ -61,8 +79,7 @@ def scene_crops(ctx, boxes, tile_hw: Tuple[int, int], norm_mode: Optional[str] =
     bit for bit to assemble_tiles of the boxes cut into the top-left corner of a zero batch with valid_hw = the box sizes.
     ctx: the fu_ctx handle that owns the device copy of the table (HipUNet._ctx).  out: optional fp32 [>= n, C, th, tw]
     buffer whose first n samples receive the crops."""
-    if norm_mode not in NORM_MODES:
-        raise NotImplementedError(f'Normalization mode "{norm_mode}" not implemented.')
+    mode = _norm_mode(norm_mode)
     n = len(boxes)
     if n == 0:
         raise ValueError("scene_crops: no boxes")
@@ -73,26 +90,16 @@ def scene_crops(ctx, boxes, tile_hw: Tuple[int, int], norm_mode: Optional[str] =
     Cc = boxes[0][0].shape[0]
     table = (_lib.FuSceneCrop * n)()
     for i, (scene, (h0, w0, hE, wE)) in enumerate(boxes):
-        if scene.dim() != 3 or scene.shape[0] != Cc or scene.dtype != torch.float32 or not scene.is_contiguous() \
-                or scene.device != dev or dev.type != "cuda":
-            raise ValueError(f"scene_crops: box {i}: scenes must be contiguous fp32 [{Cc}, H, W] on one ROCm device, got "
-                             f"{tuple(scene.shape)} {scene.dtype} on {scene.device}")
+        _check_scene(f"scene_crops: box {i}", scene, Cc, dev)
         table[i] = _lib.FuSceneCrop(scene.data_ptr(), scene.shape[1], scene.shape[2], int(h0), int(w0), int(hE), int(wE))
     if out is None:
         out = torch.empty(n, Cc, th, tw, dtype=torch.float32, device=dev)
     elif tuple(out.shape[1:]) != (Cc, th, tw) or out.shape[0] < n or out.dtype != torch.float32 \
             or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"scene_crops: out must be contiguous fp32 [>= {n}, {Cc}, {th}, {tw}] on {dev}")
-    mode = NORM_MODES[norm_mode]
     mean = torch.zeros(n, Cc, dtype=torch.float32, device=dev)
     std = torch.ones(n, Cc, dtype=torch.float32, device=dev)
-    gm = gs = None
-    if mode == 2:
-        if global_params is None:
-            raise ValueError("norm_mode 'global' needs (mean, std) per channel")
-        gm, gs = (t.to(dev).float().contiguous() for t in global_params)
-        mean[:] = gm
-        std[:] = gs
+    gm, gs = _global_norm(mode, global_params, dev, mean, std)
     check(_lib.load().fu_scene_crops(ctx, n, table, Cc, th, tw, mode, ptr(gm), ptr(gs), float(pad_value), ptr(out),
                                      ptr(mean) if mode == 1 else None, ptr(std) if mode == 1 else None,
                                      torch.cuda.current_stream(dev).cuda_stream))
@@ -109,8 +116,7 @@ def scene_train_tiles(ctx, entries, tile_hw: Tuple[int, int], norm_mode: Optiona
     by augment.apply on the decoded label boxes, in one launch (two with 'local') and without the batch in between.
     global_params: fp32 tensors; pass them on the device to keep the call free of host-to-device copies.
     out: optional (image, target, mean, std) buffers of those shapes (mean / std [n, C]) to write into."""
-    if norm_mode not in NORM_MODES:
-        raise NotImplementedError(f'Normalization mode "{norm_mode}" not implemented.')
+    mode = _norm_mode(norm_mode)
     n = len(entries)
     if n == 0:
         raise ValueError("scene_train_tiles: no entries")
@@ -122,10 +128,7 @@ def scene_train_tiles(ctx, entries, tile_hw: Tuple[int, int], norm_mode: Optiona
     with_target = entries[0][1] is not None
     table = (_lib.FuSceneTrainEntry * n)()
     for i, (scene, label, (h0, w0, hE, wE), flags, angle) in enumerate(entries):
-        if scene.dim() != 3 or scene.shape[0] != Cc or scene.dtype != torch.float32 or not scene.is_contiguous() \
-                or scene.device != dev or dev.type != "cuda":
-            raise ValueError(f"scene_train_tiles: entry {i}: scenes must be contiguous fp32 [{Cc}, H, W] on one ROCm device, "
-                             f"got {tuple(scene.shape)} {scene.dtype} on {scene.device}")
+        _check_scene(f"scene_train_tiles: entry {i}", scene, Cc, dev)
         if (label is not None) != with_target:
             raise ValueError("scene_train_tiles: either every entry has a label raster or none has")
         if label is not None and (label.dtype != torch.uint8 or tuple(label.shape) != tuple(scene.shape[1:])
@@ -134,7 +137,6 @@ def scene_train_tiles(ctx, entries, tile_hw: Tuple[int, int], norm_mode: Optiona
                              f"{dev}, got {tuple(label.shape)} {label.dtype} on {label.device}")
         table[i] = _lib.FuSceneTrainEntry(scene.data_ptr(), ptr(label), scene.shape[1], scene.shape[2], int(h0), int(w0),
                                           int(hE), int(wE), int(flags), float(angle))
-    mode = NORM_MODES[norm_mode]
     if out is not None:
         image, target, mean, std = out
     else:
@@ -142,13 +144,7 @@ def scene_train_tiles(ctx, entries, tile_hw: Tuple[int, int], norm_mode: Optiona
         target = torch.empty(n, th, tw, dtype=torch.int64, device=dev) if with_target else None
         mean = torch.zeros(n, Cc, dtype=torch.float32, device=dev)
         std = torch.ones(n, Cc, dtype=torch.float32, device=dev)
-    gm = gs = None
-    if mode == 2:
-        if global_params is None:
-            raise ValueError("norm_mode 'global' needs (mean, std) per channel")
-        gm, gs = (t.to(dev).float().contiguous() for t in global_params)
-        mean[:] = gm
-        std[:] = gs
+    gm, gs = _global_norm(mode, global_params, dev, mean, std)
     check(_lib.load().fu_scene_train_tiles(ctx, n, table, Cc, th, tw, mode, ptr(gm), ptr(gs), float(pad_value),
                                            int(nodata_value), int(target_fill), ptr(image),
                                            ptr(target) if with_target else None, ptr(mean) if mode == 1 else None,
