@@ -375,6 +375,7 @@ struct fu_ctx {
   float* ce_part = nullptr;
   float* hb_part = nullptr;
   float* loss_dev = nullptr;
+  float* ce_wsum = nullptr;       // fu_loss_ce_weighted: D = sum of w[target] over the valid pixels, read by its gradient kernel
   float* loss_scale = nullptr;    // fp16 mode: {S, 1/S} of the running backward (fu_common.h, launch_loss_grad_eff)
   int* guard = nullptr;           // fp16 mode: non-finite flag / skipped steps / back-off exponent / clean steps (k_guard_book)
   unsigned long long* conf_tmp = nullptr;
@@ -629,7 +630,8 @@ int alloc_workspace(fu_ctx* c) {
   A.want(&c->db_part2, max_dbp * sizeof(float));
   A.want(&c->dscratch, reduce_scratch_elems(std::max(max_c, 64)) * sizeof(double));
   A.want(&c->slab, max_slab * sizeof(float));
-  A.want(&c->ce_part, 2 * 1024 * sizeof(float));
+  A.want(&c->ce_part, 4 * 1024 * sizeof(float));     // (fu_loss_ce_weighted: four sums per workgroup)
+  A.want(&c->ce_wsum, 256);
   A.want(&c->hb_part, head_bwd_partial_elems(f.base_channels, f.n_classes) * sizeof(float));
   A.want(&c->loss_dev, 256);
   A.want(&c->loss_scale, 256);
@@ -1252,7 +1254,7 @@ int64_t fu_exact_sync_bytes(const fu_ctx* c) {
   if (!c) return 0;
   int max_c = 64;
   for (const BnInfo& b : c->bns) max_c = std::max(max_c, b.C);
-  return std::max<int64_t>(fu::reduce_scratch_elems(max_c) * (int64_t)sizeof(double), 2 * 1024 * (int64_t)sizeof(float));
+  return std::max<int64_t>(fu::reduce_scratch_elems(max_c) * (int64_t)sizeof(double), 4 * 1024 * (int64_t)sizeof(float));
 }
 
 int fu_forward(fu_ctx* c, const float* x, int batch, int training, float* logits_out, fu_stream stream) {
@@ -1333,6 +1335,30 @@ int fu_loss_ce(fu_ctx* c, const int64_t* target, int ignore_index, float* loss_o
                         loss_out ? loss_out : c->loss_dev, c->n_valid, confusion_out, n_valid_out, c->conf_tmp, s));
   if (c->fwd_training) {
     FU_TRY(launch_ce_grad(c->logits, target, c->cfg.n_classes, ignore_index, npix, c->n_valid, c->dlogits, s));
+    c->have_loss = true;
+    c->have_up_scale = false;
+  }
+  return FU_OK;
+}
+
+int fu_loss_ce_weighted(fu_ctx* c, const int64_t* target, int ignore_index, const float* class_weight_dev,
+                        float label_smoothing, float* loss_out, int64_t* confusion_out, int64_t* n_valid_out,
+                        float* weight_sum_out, fu_stream stream) {
+  FU_REQUIRE(c && target, "fu_loss_ce_weighted: null argument");
+  FU_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "fu_loss_ce_weighted: label_smoothing %g outside [0, 1)",
+             (double)label_smoothing);
+  FU_REQUIRE(c->last_batch > 0, "fu_loss_ce_weighted: no forward pass yet");
+  hipStream_t s = (hipStream_t)stream;
+  SyncScope sc(c, c->fwd_training);
+  const int ncls = c->cfg.n_classes;
+  const int64_t npix = (int64_t)c->last_batch * c->cfg.height * c->cfg.width;
+  const float c_nll = (float)(1.0 - (double)label_smoothing), c_smooth = (float)((double)label_smoothing / ncls);
+  FU_TRY(launch_ce_weighted_loss(c->logits, target, ncls, ignore_index, npix, class_weight_dev, c_nll, c_smooth, c->ce_part,
+                                 loss_out ? loss_out : c->loss_dev, c->n_valid, c->ce_wsum, confusion_out, n_valid_out,
+                                 weight_sum_out, c->conf_tmp, s));
+  if (c->fwd_training) {
+    FU_TRY(launch_ce_weighted_grad(c->logits, target, ncls, ignore_index, npix, class_weight_dev, c_nll, c_smooth,
+                                   c->ce_wsum, c->dlogits, s));
     c->have_loss = true;
     c->have_up_scale = false;
   }
@@ -1640,6 +1666,12 @@ int fu_scene_train_tiles(fu_ctx* c, int n, const fu_scene_train_entry* entries, 
   return launch_scene_train_tiles(c->train_table, n, entries, C, tile_h, tile_w, norm_mode, global_mean, global_std,
                                   pad_value, nodata_value, target_fill, image_out, target_out, mean_out, std_out,
                                   (hipStream_t)stream);
+}
+
+int fu_label_class_counts(fu_ctx* c, int n, const fu_scene_train_entry* entries, int64_t nodata_value, int n_classes,
+                          int64_t* counts_out, fu_stream stream) {
+  FU_REQUIRE(c && entries && counts_out, "fu_label_class_counts: null context / entries / counts_out");
+  return launch_label_class_counts(c->train_table, n, entries, nodata_value, n_classes, counts_out, (hipStream_t)stream);
 }
 
 int64_t fu_band_stats_workspace_bytes(int n_channels, int n_bins) {

@@ -457,6 +457,16 @@ int launch_ce_loss(const float* logits_nhwc, const int64_t* target, int ncls, in
 // dlogits (NHWC fp32) from CE: (softmax - onehot)/n_valid on valid pixels
 int launch_ce_grad(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
                    const int64_t* n_valid_dev, float* dlogits_nhwc, hipStream_t s);
+// Class-weighted, label-smoothed CE (fu_loss_ce_weighted).  class_weight: fp32 [ncls] on the device or null (all ones).
+// partials: [nblk][4] (sum w[t] nll, sum smoothing term, sum w[t], valid count) -> finalize; weight_sum_dev receives
+// D = sum w[t] (fp32), which launch_ce_weighted_grad divides by.  c_nll = 1 - eps, c_smooth = eps / ncls.
+int launch_ce_weighted_loss(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
+                            const float* class_weight, float c_nll, float c_smooth, float* partials /* [4 * 1024] */,
+                            float* loss_out, int64_t* n_valid_dev, float* weight_sum_dev, int64_t* confusion_accum,
+                            int64_t* n_valid_out, float* weight_sum_out, unsigned long long* conf_tmp, hipStream_t s);
+int launch_ce_weighted_grad(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
+                            const float* class_weight, float c_nll, float c_smooth, const float* weight_sum_dev,
+                            float* dlogits_nhwc, hipStream_t s);
 // BCE + soft Dice on softmax(z)[1]; partials >= 5*400 floats, coef 4 floats; dlogits may be null (eval)
 int launch_bce_dice(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
                     float dice_w, float* partials, float* coef, float* loss_out, int64_t* n_valid_dev,
@@ -499,6 +509,10 @@ int launch_scene_train_tiles(DeviceTable& table, int n, const fu_scene_train_ent
                              int norm_mode, const float* gmean, const float* gstd, float pad_value, int64_t nodata_value,
                              int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out, float* std_out,
                              hipStream_t s);
+// fu_label_class_counts: counts[d] += #pixels of the entries' label boxes that decode to class d (0 <= d < n_classes);
+// checked, uploaded and launched in the same way
+int launch_label_class_counts(DeviceTable& table, int n, const fu_scene_train_entry* entries, int64_t nodata_value,
+                              int n_classes, int64_t* counts, hipStream_t s);
 // fu_band_stats: the caller's per-channel accumulators (all ADDED to) and the histogram's geometry
 struct BandAccum {
   int64_t* count; double* sum; double* sumsq; float* vmin; float* vmax; int64_t* n_nonfinite;

@@ -1,12 +1,14 @@
 // Data-preparation kernels (gfx950): what turns rasters that are already in HBM into training and inference batches --
 // tile augmentation, tile assembly and scene crops, Lanczos-4 resampling, training tiles straight from resident scenes,
-// streaming band statistics.  None of them runs inside a training step.  The entry points that take a table of host
-// entries (fu_scene_crops, fu_scene_train_tiles) are validated here, next to the kernels that trust the table.
+// label class counts, streaming band statistics.  None of them runs inside a training step.  The entry points that take a
+// table of host entries (fu_scene_crops, fu_scene_train_tiles, fu_label_class_counts) are validated here, next to the
+// kernels that trust the table.
 #include "../../include/floodunet.h"
 #include "fu_common.h"
 
 #include <math.h>
 
+#include <algorithm>
 #include <vector>
 
 namespace fu {
@@ -516,6 +518,72 @@ int launch_scene_train_tiles(DeviceTable& table, int n, const fu_scene_train_ent
   else
     hipLaunchKernelGGL(k_scene_train_tiles<1>, grid, dim3(256), 0, s, jobs_dev, augs_dev, C, H, W, N.mean, N.stdv,
                        N.per_sample, pad_value, nodata_value, target_fill, image_out, target_out);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Class frequencies of resident label rasters (fu_label_class_counts), for "balanced" class weights: every pixel of every
+// box of the table, decoded as k_scene_train_tiles decodes it.  A decoded label is 0, 1 or nodata_value, so a thread counts
+// its pixels in three registers; a block folds them into a three-bin LDS histogram with integer atomics and adds the bins
+// whose class lies in [0, n_classes) to the caller's counts with 64-bit integer atomics (the scheme of k_eval_confusion):
+// exact, whatever the order.  blockIdx.x = box, blockIdx.y = a share of its pixels.
+// ------------------------------------------------------------------------------------------------
+struct LabelBox {          // device copy of a validated fu_scene_train_entry, as far as the counts need it
+  const uint8_t* label;    // first pixel of the box
+  int scene_w, dh, dw;
+};
+
+__global__ __launch_bounds__(256) void k_label_class_counts(const LabelBox* __restrict__ boxes, int64_t nodata_value,
+                                                            int n_classes, unsigned long long* __restrict__ counts) {
+  __shared__ unsigned int bins[3];         // decoded 0, decoded 1, no data
+  if (threadIdx.x < 3) bins[threadIdx.x] = 0u;
+  __syncthreads();
+  const LabelBox J = boxes[blockIdx.x];
+  const unsigned npx = (unsigned)J.dh * (unsigned)J.dw;      // < 2^31 (launch_label_class_counts checks)
+  unsigned c0 = 0, c1 = 0, cn = 0;
+  for (unsigned i = blockIdx.y * 256u + threadIdx.x; i < npx; i += gridDim.y * 256u) {
+    const unsigned y = i / (unsigned)J.dw, x = i - y * (unsigned)J.dw;
+    const uint8_t raw = J.label[(int64_t)y * J.scene_w + x];
+    c1 += raw == 2 ? 1u : 0u;
+    cn += raw == 0 ? 1u : 0u;
+    c0 += (raw != 2 && raw != 0) ? 1u : 0u;
+  }
+  if (c0) atomicAdd(&bins[0], c0);
+  if (c1) atomicAdd(&bins[1], c1);
+  if (cn) atomicAdd(&bins[2], cn);
+  __syncthreads();
+  if (threadIdx.x < 3 && bins[threadIdx.x]) {
+    const int64_t d = threadIdx.x == 2 ? nodata_value : (int64_t)threadIdx.x;     // decode_label's three values
+    if (d >= 0 && d < n_classes) atomicAdd(&counts[d], (unsigned long long)bins[threadIdx.x]);
+  }
+}
+
+// every check before anything is launched or copied: a rejected call leaves the stream and the counts untouched
+int launch_label_class_counts(DeviceTable& table, int n, const fu_scene_train_entry* entries, int64_t nodata_value,
+                              int n_classes, int64_t* counts, hipStream_t s) {
+  const char* fn = "fu_label_class_counts";
+  FU_REQUIRE(n >= 1 && n_classes >= 1, "%s: n = %d, n_classes = %d (both must be >= 1)", fn, n, n_classes);
+  std::vector<LabelBox> boxes((size_t)n);
+  int64_t max_px = 0;
+  for (int i = 0; i < n; ++i) {
+    const fu_scene_train_entry& E = entries[i];
+    const int dh = E.hE - E.h0, dw = E.wE - E.w0;
+    FU_REQUIRE(E.label, "%s: entry %d: null label raster", fn, i);
+    FU_REQUIRE(E.scene_h >= 1 && E.scene_w >= 1 && (int64_t)E.scene_h * E.scene_w <= INT32_MAX,
+               "%s: entry %d: bad raster size %dx%d", fn, i, E.scene_h, E.scene_w);
+    FU_REQUIRE(E.h0 >= 0 && E.w0 >= 0 && E.hE <= E.scene_h && E.wE <= E.scene_w,
+               "%s: entry %d: box [%d:%d, %d:%d] lies outside its raster %dx%d", fn, i, E.h0, E.hE, E.w0, E.wE, E.scene_h,
+               E.scene_w);
+    FU_REQUIRE(dh >= 1 && dw >= 1, "%s: entry %d: box [%d:%d, %d:%d] is empty", fn, i, E.h0, E.hE, E.w0, E.wE);
+    boxes[i] = LabelBox{E.label + (int64_t)E.h0 * E.scene_w + E.w0, E.scene_w, dh, dw};
+    max_px = std::max<int64_t>(max_px, (int64_t)dh * dw);
+  }
+  FU_TRY(table.upload(boxes.data(), (size_t)n * sizeof(LabelBox), sizeof(LabelBox), s));
+  // 16 pixels per thread where the largest box allows it, at most 64 blocks per box
+  const dim3 grid((unsigned)n, (unsigned)grid_for(max_px, 256 * 16, 64));
+  hipLaunchKernelGGL(k_label_class_counts, grid, dim3(256), 0, s, static_cast<const LabelBox*>(table.dev), nodata_value,
+                     n_classes, reinterpret_cast<unsigned long long*>(counts));
   FU_LAUNCH_CHECK();
   return 0;
 }

@@ -1530,6 +1530,216 @@ int launch_ce_grad(const float* logits_nhwc, const int64_t* target, int ncls, in
 }
 
 // ------------------------------------------------------------------------------------------------
+// Class-weighted, label-smoothed cross entropy (fu_loss_ce_weighted; an extension: the reference has no such loss, the
+// specification is torch.nn.functional.cross_entropy(weight, ignore_index, label_smoothing)).  Over the valid pixels, with
+// p = softmax(z), W = sum_c w[c]:
+//   loss = [c_nll * sum_i w[t] (lse - z[t]) + c_smooth * sum_i sum_c w[c] (lse - z[c])] / D,      D = sum_i w[t_i]
+//   dz_k = [c_nll * w[t] (p_k - [k == t]) + c_smooth * (p_k W - w[k])] / D,      c_nll = 1 - eps, c_smooth = eps / C
+// k_ce_loss / k_ce_grad stay as they are (the default path); these kernels keep their grid, their per-thread order, their
+// lse and softmax expressions and their reduction tree, so that w = 1, eps = 0 reproduces their bits (every extra factor is
+// then an exact 1 or 0).  NC as in k_head_fwd: compile-time class count, 0 = any count up to HEAD_MAX_CLS; the weights are
+// uniform values loaded once per thread.  D == 0 gives loss 0 and a zero gradient (the rule of the all-ignored batch).
+// ------------------------------------------------------------------------------------------------
+template <int NC>
+__global__ __launch_bounds__(CE_BLOCK) void k_ce_weighted_loss(const float* __restrict__ logits,
+                                                               const int64_t* __restrict__ target, int ncls_rt,
+                                                               int ignore_index, int64_t npix,
+                                                               const float* __restrict__ class_weight,
+                                                               float* __restrict__ partials,
+                                                               unsigned long long* __restrict__ conf_tmp) {
+  constexpr int KMAX = NC ? NC : HEAD_MAX_CLS;
+  const int ncls = NC ? NC : ncls_rt;
+  __shared__ unsigned int hist[HEAD_MAX_CLS * HEAD_MAX_CLS];
+  __shared__ float wsum[CE_BLOCK / 64][4];
+  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x) hist[i] = 0;
+  __syncthreads();
+  float w[KMAX];
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) w[k] = (k < ncls) ? (class_weight ? class_weight[k] : 1.f) : 0.f;
+  float lsum = 0.f, ssum = 0.f, dsum = 0.f, cnt = 0.f;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t t = target[p];
+    float z[KMAX];
+    float m = -INFINITY;
+    int am = 0;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      if (k < ncls) {
+        z[k] = logits[p * ncls + k];
+        if (z[k] > m) { m = z[k]; am = k; }
+      }
+    }
+    if (t != (int64_t)ignore_index && t >= 0 && t < ncls) {
+      float se = 0.f;
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < ncls) se += expf(z[k] - m);
+      const float lse = m + logf(se);
+      float zt = 0.f, wt = 0.f, sm = 0.f;
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        if (k < ncls) {
+          if (k == (int)t) { zt = z[k]; wt = w[k]; }
+          sm += w[k] * (lse - z[k]);
+        }
+      }
+      lsum += wt * (lse - zt);
+      ssum += sm;
+      dsum += wt;
+      cnt += 1.f;
+      atomicAdd(&hist[(int)t * ncls + am], 1u);
+    }
+  }
+  lsum = wave_sum(lsum);
+  ssum = wave_sum(ssum);
+  dsum = wave_sum(dsum);
+  cnt = wave_sum(cnt);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { wsum[wave][0] = lsum; wsum[wave][1] = ssum; wsum[wave][2] = dsum; wsum[wave][3] = cnt; }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    float s0 = 0.f;
+    for (int wv = 0; wv < CE_BLOCK / 64; ++wv) s0 += wsum[wv][threadIdx.x];
+    partials[blockIdx.x * 4 + threadIdx.x] = s0;
+  }
+  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x)
+    if (hist[i]) atomicAdd(&conf_tmp[i], (unsigned long long)hist[i]);
+}
+
+// k_ce_finalize's fixed fp64 tree over four sums per block instead of two
+__global__ __launch_bounds__(256) void k_ce_weighted_finalize(const float* __restrict__ partials, int nblk, int ncls,
+                                                              float c_nll, float c_smooth, float* __restrict__ loss_out,
+                                                              int64_t* __restrict__ n_valid_dev,
+                                                              float* __restrict__ weight_sum_dev,
+                                                              unsigned long long* __restrict__ conf_tmp,
+                                                              int64_t* __restrict__ conf_accum,
+                                                              int64_t* __restrict__ n_valid_out,
+                                                              float* __restrict__ weight_sum_out) {
+  __shared__ double sm[4][256];
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < nblk; i += 256) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] += (double)partials[i * 4 + j];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) sm[j][threadIdx.x] = a[j];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {   // fixed tree: deterministic
+    if ((int)threadIdx.x < w) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sm[j][threadIdx.x] += sm[j][threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double nll = sm[0][0], smooth = sm[1][0], D = sm[2][0], c = sm[3][0];
+    double num = (double)c_nll * nll;
+    if (c_smooth != 0.f) num += (double)c_smooth * smooth;
+    // mean over the weights of the valid pixels; D == 0: torch's NaN -> 0, the rule of the all-ignored batch
+    const float loss = D > 0.0 ? (float)(num / D) : 0.f;
+    if (loss_out) *loss_out = loss;
+    *weight_sum_dev = (float)D;
+    if (weight_sum_out) *weight_sum_out = (float)D;
+    *n_valid_dev = (int64_t)(c + 0.5);
+    if (n_valid_out) *n_valid_out = (int64_t)(c + 0.5);
+  }
+  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x) {
+    if (conf_accum) conf_accum[i] += (int64_t)conf_tmp[i];
+    conf_tmp[i] = 0ull;
+  }
+}
+
+#define FU_NC_SWITCH(ncls, LAUNCH) \
+  switch (ncls) {                  \
+    case 1: LAUNCH(1); break;      \
+    case 2: LAUNCH(2); break;      \
+    case 3: LAUNCH(3); break;      \
+    case 4: LAUNCH(4); break;      \
+    default: LAUNCH(0); break;     \
+  }
+
+int launch_ce_weighted_loss(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
+                            const float* class_weight, float c_nll, float c_smooth, float* partials, float* loss_out,
+                            int64_t* n_valid_dev, float* weight_sum_dev, int64_t* confusion_accum, int64_t* n_valid_out,
+                            float* weight_sum_out, unsigned long long* conf_tmp, hipStream_t s) {
+  FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "weighted CE: n_classes must be 1..%d", HEAD_MAX_CLS);
+  const int nblk = grid_for(npix, CE_BLOCK, CE_MAX_BLOCKS);
+#define FU_CEW_LOSS(NC)                                                                                                  \
+  hipLaunchKernelGGL((k_ce_weighted_loss<NC>), dim3(nblk), dim3(CE_BLOCK), 0, s, logits_nhwc, target, ncls, ignore_index, \
+                     npix, class_weight, partials, conf_tmp)
+  FU_NC_SWITCH(ncls, FU_CEW_LOSS);
+#undef FU_CEW_LOSS
+  FU_LAUNCH_CHECK();
+  FU_TRY(sync_sum_over_ranks(partials, (int64_t)nblk * 4, false, s));      // exact DP: global sums, D and N_valid
+  hipLaunchKernelGGL(k_ce_weighted_finalize, dim3(1), dim3(256), 0, s, partials, nblk, ncls, c_nll, c_smooth, loss_out,
+                     n_valid_dev, weight_sum_dev, conf_tmp, confusion_accum, n_valid_out, weight_sum_out);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+template <int NC>
+__global__ __launch_bounds__(256) void k_ce_weighted_grad(const float* __restrict__ logits,
+                                                          const int64_t* __restrict__ target, int ncls_rt,
+                                                          int ignore_index, int64_t npix,
+                                                          const float* __restrict__ class_weight, float c_nll,
+                                                          float c_smooth, const float* __restrict__ weight_sum,
+                                                          float* __restrict__ dl) {
+  constexpr int KMAX = NC ? NC : HEAD_MAX_CLS;
+  const int ncls = NC ? NC : ncls_rt;
+  const float D = *weight_sum;
+  const bool live = D > 0.f;
+  const float inv = live ? 1.f / D : 0.f;
+  float w[KMAX];
+  float W = 0.f;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    w[k] = (k < ncls) ? (class_weight ? class_weight[k] : 1.f) : 0.f;
+    W += w[k];
+  }
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t t = target[p];
+    const bool valid = (t != (int64_t)ignore_index && t >= 0 && t < ncls) && live;
+    float z[KMAX];
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < ncls) { z[k] = logits[p * ncls + k]; m = fmaxf(m, z[k]); }
+    float se = 0.f;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < ncls) { z[k] = expf(z[k] - m); se += z[k]; }
+    const float r = 1.f / se;
+    float wt = 0.f;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < ncls && (int)t == k) wt = w[k];
+    const float a = c_nll * wt, rW = r * W;   // (p_k W as e_k (r W): p_k - [k == t] keeps k_ce_grad's own expression)
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      if (k < ncls) {
+        const float g = a * (z[k] * r - ((int)t == k ? 1.f : 0.f)) + c_smooth * (z[k] * rW - w[k]);
+        dl[p * ncls + k] = valid ? g * inv : 0.f;
+      }
+    }
+  }
+}
+
+int launch_ce_weighted_grad(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
+                            const float* class_weight, float c_nll, float c_smooth, const float* weight_sum_dev,
+                            float* dlogits_nhwc, hipStream_t s) {
+  FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "weighted CE: n_classes must be 1..%d", HEAD_MAX_CLS);
+  const int g = grid_for(npix, 256, 4096);
+#define FU_CEW_GRAD(NC)                                                                                              \
+  hipLaunchKernelGGL((k_ce_weighted_grad<NC>), dim3(g), dim3(256), 0, s, logits_nhwc, target, ncls, ignore_index, npix, \
+                     class_weight, c_nll, c_smooth, weight_sum_dev, dlogits_nhwc)
+  FU_NC_SWITCH(ncls, FU_CEW_GRAD);
+#undef FU_CEW_GRAD
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+#undef FU_NC_SWITCH
+
+// ------------------------------------------------------------------------------------------------
 // BCE + soft Dice on p = softmax(z)[1] (north-star extension; the reference has no such loss -> parity is pinned
 // only by oracle/unet_oracle.py:bce_dice_loss).  All spatial reductions in fp32 registers + wave shuffles, fp64 finalize.
 //   BCE  = -(1/N) sum_valid [ t log p + (1-t) log(1-p) ],  Dice = 1 - (2 sum p t + 1) / (sum p + sum t + 1)

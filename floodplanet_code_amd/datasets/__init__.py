@@ -1,5 +1,6 @@
 """Host-side data path for the bundled FloodPlanet rasters: TIFF decoding, tile grid, dataset."""
 from .assemble import assemble_tiles
+from .class_weights import balanced_class_weights, label_class_counts, label_class_counts_host
 from .floodplanet import FloodplanetTiles, collate_tiles
 from .loader import TileLoader
 from .scene_loader import SceneResidencyError, SceneTileLoader
@@ -7,5 +8,5 @@ from .resize import resize_image, resize_lanczos4, resize_nearest
 from .tiff import TiffError, read_tiff, tiff_info, tiff_size
 from .tiles import CropParams, generate_image_slice_object, get_crop_slices
 
-__all__ = ["assemble_tiles", "FloodplanetTiles", "collate_tiles", "TileLoader", "SceneTileLoader", "SceneResidencyError", "resize_image", "resize_lanczos4", "resize_nearest", "TiffError",
+__all__ = ["assemble_tiles", "balanced_class_weights", "label_class_counts", "label_class_counts_host", "FloodplanetTiles", "collate_tiles", "TileLoader", "SceneTileLoader", "SceneResidencyError", "resize_image", "resize_lanczos4", "resize_nearest", "TiffError",
            "read_tiff", "tiff_info", "tiff_size", "CropParams", "generate_image_slice_object", "get_crop_slices"]

@@ -179,6 +179,21 @@ class SceneTileLoader:
         torch.cuda.synchronize(dev)      # the pinned host rasters may go once the uploads are done
         self._items = items
 
+    def class_counts(self) -> torch.Tensor:
+        """Pixels per class over every example of the split: int64 [n_classes] on the device, from the resident label
+        rasters -- one table of all the boxes, one launch (fu_label_class_counts).  Labels decode as the batches' targets
+        do (no data -> ignore_index); overlapping tiles count as often as they are trained on.  A sharded loader still
+        counts the whole split."""
+        from .class_weights import label_class_counts
+        if self._items is None:
+            self._make_resident()
+        n_classes = int(self.dataset.n_classes)
+        if not self._items:
+            return torch.zeros(n_classes, dtype=torch.int64, device=self.device)
+        th, tw = self.tile_hw
+        ctx = self.net._get_ctx(self.device, self.batch_size, th, tw)
+        return label_class_counts(ctx, [(label, box) for _, label, box in self._items], self.ignore_index, n_classes)
+
     def _batch(self, index: List[int]) -> dict:
         from .. import augment
         from .assemble import scene_train_tiles

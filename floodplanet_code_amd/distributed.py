@@ -121,11 +121,14 @@ class DataParallelTrainer:
 
     def __init__(self, net, lr: float, world_size: int = 1, rank: int = 0, betas=(0.9, 0.999), eps: float = 1e-8,
                  group=None, cap_bytes: int = 16 << 20, exact: bool = False, time_waits: bool = False,
-                 graph: bool = False):
+                 graph: bool = False, class_weight=None, label_smoothing: float = 0.0):
         """exact=False: DDP semantics (per-rank BN statistics and 1/N_valid, gradients averaged).
         exact=True: SyncBN statistics and a global N_valid (HipUNet.enable_exact_sync); the ranks together reproduce
-        one device with world_size x the batch, gradients are summed (SURVEY.md 8(e) "exact mode")."""
+        one device with world_size x the batch, gradients are summed (SURVEY.md 8(e) "exact mode").
+        class_weight / label_smoothing: the weighted, label-smoothed cross entropy of HipUNet.loss for every step (defaults:
+        the reference's loss); in exact mode its denominator, the summed weight of the valid pixels, is global too."""
         self.net, self.lr, self.world_size, self.rank = net, lr, world_size, rank
+        self.class_weight, self.label_smoothing = class_weight, float(label_smoothing)
         self.betas, self.eps, self.group, self.cap_bytes = betas, eps, group, cap_bytes
         self.exact = bool(exact) and world_size > 1
         if self.exact:
@@ -195,12 +198,14 @@ class DataParallelTrainer:
         self._gscal_ring = [torch.zeros(7, dtype=torch.float32).pin_memory() for _ in range(8)]
         self._gscal_ev = [None] * 8
         lib = _lib.load()
+        net._class_weight_dev(self.class_weight, dev)                # the weights' upload stays outside the capture
         torch.cuda.synchronize(dev)
         dot = os.environ.get("FU_GRAPH_DOT")                          # diagnostics: hipGraphDebugDotPrint of the captured step (tools/graph_dot.py)
         g = torch.cuda.CUDAGraph(keep_graph=True) if dot else torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             net._forward_raw(self._gx, True, want_logits=False)
-            self._gloss = net._loss_raw(self._gt, self._g_ignore, dev)
+            self._gloss = net._loss_raw(self._gt, self._g_ignore, dev, class_weight=self.class_weight,
+                                        label_smoothing=self.label_smoothing)
             net._backward_raw(None, dev)
             _lib.check(lib.fu_adam_step_dev(net._ctx, self._gscal.data_ptr(), net._stream(dev)))
         net._generation -= 1          # (the capture enqueued nothing; the bookkeeping of _forward_raw is redone per replay)
@@ -241,7 +246,8 @@ class DataParallelTrainer:
         if self.world_size > 1 and not self._synced:
             self._sync_initial_state(x.device)
         net._forward_raw(x, True, want_logits=False)
-        loss = net._loss_raw(target, ignore_index, x.device)
+        loss = net._loss_raw(target, ignore_index, x.device, class_weight=self.class_weight,
+                             label_smoothing=self.label_smoothing)
         if self.world_size <= 1 and not _FORCE_BLOCKS:
             net._backward_raw(None, x.device)
         else:

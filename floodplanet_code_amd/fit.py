@@ -38,6 +38,7 @@ from .models import build_model
 DEFAULTS = dict(lr=1e-4, batch_size=10, n_epochs=11, crop_height=300, crop_width=300, ignore_index=0,
                 save_topk_models=3, limit_train_batches=None, limit_val_batches=None, log_image_iter=200,
                 seed_num=0, model=dict(name="ef_model", model_kwargs=dict(optimizer_name="adam")))
+N_CLASSES = 3          # of the data set the command line trains on (FloodplanetTiles.n_classes)
 
 
 class SyntheticTiles:
@@ -166,15 +167,44 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--seed", type=int, default=D["seed_num"])
     ap.add_argument("--ignore_index", type=int, default=D["ignore_index"])
     ap.add_argument("--save_topk_models", type=int, default=D["save_topk_models"])
+    ap.add_argument("--class_weights", type=str, nargs="+", default=None, metavar="W",
+                    help="cross-entropy class weights: 'balanced' (from the TRAIN split's class frequencies) or one number "
+                         "per class")
+    ap.add_argument("--label_smoothing", type=float, default=0.0, help="cross-entropy label smoothing in [0, 1)")
     ap.add_argument("--no_transforms", action="store_true", help="train without hflip / vflip / rotate")
     ap.add_argument("--no_shuffle", action="store_true", help="train in data-set order")
     ap.add_argument("--device", type=str, default="cuda:0")
     return ap
 
 
-def cfg_from_args(args) -> dict:
-    """The reference-style config of a command line: what fit_model trains with and dumps into the checkpoint."""
+def parse_class_weights(values, n_classes: Optional[int] = None):
+    """--class_weights -> None, the word 'balanced' or a list of floats (n_classes of them when n_classes is known)."""
+    if values is None:
+        return None
+    if len(values) == 1 and values[0] == "balanced":
+        return "balanced"
+    try:
+        w = [float(v) for v in values]
+    except ValueError:
+        raise ValueError(f"--class_weights takes 'balanced' or one number per class, got {list(values)}") from None
+    if n_classes is not None and len(w) != int(n_classes):
+        raise ValueError(f"--class_weights: {len(w)} weights for {n_classes} classes")
+    return w
+
+
+def cfg_from_args(args, class_weights=None) -> dict:
+    """The reference-style config of a command line: what fit_model trains with and dumps into the checkpoint.
+    class_weights: the resolved numeric weights (the data decides 'balanced' and the class count, so main() resolves them);
+    they and --label_smoothing enter model_kwargs only when set, so a plain command line gives the config it always gave."""
     norm_mode = None if args.norm_mode == "none" else args.norm_mode
+    parsed = parse_class_weights(getattr(args, "class_weights", None), N_CLASSES)
+    if class_weights is None and parsed is not None and parsed != "balanced":
+        class_weights = parsed
+    loss_kwargs = {}
+    if class_weights is not None:
+        loss_kwargs["class_weights"] = [float(v) for v in class_weights]
+    if float(getattr(args, "label_smoothing", 0.0)) != 0.0:
+        loss_kwargs["label_smoothing"] = float(args.label_smoothing)
     return dict(lr=args.lr, batch_size=args.batch_size, n_epochs=args.n_epochs, crop_height=args.crop[0],
                 crop_width=args.crop[1], crop_stride=args.stride, ignore_index=args.ignore_index,
                 save_topk_models=args.save_topk_models, seed_num=args.seed, n_workers=args.n_workers,
@@ -182,14 +212,19 @@ def cfg_from_args(args) -> dict:
                 norm_mode=norm_mode, norm_params=args.norm_params,
                 dataset=dict(name="floodplanet", sensor=args.sensor, channels=args.channels, dataset_kwargs=None),
                 model=dict(name=args.model, model_kwargs=dict(optimizer_name="adam", base_channels=args.base_channels,
-                                                              precision=args.precision)))
+                                                              precision=args.precision, **loss_kwargs)))
 
 
 def main(argv: Optional[List[str]] = None) -> dict:
     import copy
     from .datasets import FloodplanetTiles, SceneTileLoader, TileLoader, generate_image_slice_object
-    args = build_parser().parse_args(argv)
-    cfg = cfg_from_args(args)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    try:
+        wanted = parse_class_weights(args.class_weights, N_CLASSES)
+        cfg = cfg_from_args(args)
+    except ValueError as e:
+        ap.error(str(e))
     c = dict(DEFAULTS)
     c.update(cfg)
     slice_params = generate_image_slice_object(c["crop_height"], c["crop_width"], c["crop_stride"])
@@ -201,6 +236,15 @@ def main(argv: Optional[List[str]] = None) -> dict:
                                 train_split_pct=c["train_split_pct"], norm_params=c["norm_params"])
 
     train_ds, valid_ds = tiles("train"), tiles("valid")
+    class_counts = None
+    if wanted is not None and wanted != "balanced" and len(wanted) != train_ds.n_classes:
+        ap.error(f"--class_weights: {len(wanted)} weights for {train_ds.n_classes} classes")
+    if wanted == "balanced" and args.loader == "tile":
+        # the streaming loader's label rasters are on the host: the contract of fu_label_class_counts in numpy, same boxes
+        from .datasets.class_weights import balanced_class_weights, dataset_label_boxes, label_class_counts_host
+        class_counts = label_class_counts_host(dataset_label_boxes(train_ds), c["ignore_index"], train_ds.n_classes)
+        cfg = cfg_from_args(args, balanced_class_weights(class_counts, c["ignore_index"]).tolist())
+        c.update(cfg)
     torch.manual_seed(c["seed_num"])                     # the initial weights are drawn here, not in fit_model
     model = build_model(c["model"]["name"], train_ds.n_channels, train_ds.n_classes, c["lr"],
                         log_image_iter=c["log_image_iter"], to_rgb_fcn=None, ignore_index=c["ignore_index"],
@@ -211,6 +255,12 @@ def main(argv: Optional[List[str]] = None) -> dict:
         train = SceneTileLoader(train_ds, c["batch_size"], args.device, shuffle=not args.no_shuffle, transforms=transforms,
                                 **common)
         valid = SceneTileLoader(valid_ds, c["batch_size"], args.device, **common)
+        if wanted == "balanced":                         # counted on the device, from the label rasters resident there
+            from .datasets.class_weights import balanced_class_weights
+            class_counts = train.class_counts().cpu().numpy()
+            cfg = cfg_from_args(args, balanced_class_weights(class_counts, c["ignore_index"]).tolist())
+            c.update(cfg)
+            model.set_loss_options(cfg["model"]["model_kwargs"]["class_weights"], model.label_smoothing)
     else:
         common = dict(seed=c["seed_num"], ignore_index=c["ignore_index"], num_workers=args.n_workers,
                       device_assembly=True, device_resize=True)
@@ -220,7 +270,9 @@ def main(argv: Optional[List[str]] = None) -> dict:
     best = fit_model(cfg, train, valid, train_ds.n_channels, train_ds.n_classes, exp_dir=args.exp_dir, device=args.device,
                      model=model)
     out = {"checkpoint": best, "loader": args.loader, "train_tiles": len(train_ds), "valid_tiles": len(valid_ds),
-           "history": model.history}
+           "history": model.history,
+           "class_counts": None if class_counts is None else [int(v) for v in class_counts],
+           "class_weights": None if model.class_weights is None else list(model.class_weights)}
     print(json.dumps(out))
     return out
 

@@ -9,7 +9,9 @@ names; the network, the loss, the backward pass and the metric counters run in l
     torchmetrics (absent; parity unpinned).
   * ``ignore_index=None`` is accepted and means "ignore nothing" (-100), where the reference's
     nn.CrossEntropyLoss(ignore_index=None) fails at call time.
-Extra keyword arguments (not in the reference): ``precision`` ('fp32' | 'bf16' | 'fp16'), ``base_channels``.
+Extra keyword arguments (not in the reference): ``precision`` ('fp32' | 'bf16' | 'fp16'), ``base_channels``,
+``class_weights`` (n_classes finite values >= 0) and ``label_smoothing`` in [0, 1): the weighted, label-smoothed cross
+entropy of nn.CrossEntropyLoss(weight, ignore_index, label_smoothing), in the fused loss kernels.
 """
 from __future__ import annotations
 
@@ -20,14 +22,18 @@ import torch.optim as optim
 
 from ..lightning_compat import LightningModule
 from ..metrics import SegmentationMetrics
-from ..unet import HipAdam, HipUNet
+from ..unet import HipAdam, HipUNet, check_class_weight, check_label_smoothing
 
 
 class WaterSegmentationModel(LightningModule):
 
     def __init__(self, in_channels, n_classes, lr, log_image_iter=50, to_rgb_fcn=None, ignore_index=None,
-                 optimizer_name='adam', precision='fp32', base_channels=64):
+                 optimizer_name='adam', precision='fp32', base_channels=64, class_weights=None, label_smoothing=0.0):
         super().__init__()
+        # checked on the host before anything touches the GPU; kept as plain Python numbers (checkpoint hyper_parameters)
+        self.class_weights = (None if class_weights is None
+                              else tuple(float(v) for v in check_class_weight(class_weights, n_classes)))
+        self.label_smoothing = check_label_smoothing(label_smoothing)
         self.lr = lr
         self.n_classes = n_classes
         self.in_channels = in_channels
@@ -43,10 +49,24 @@ class WaterSegmentationModel(LightningModule):
         self.tracked_metrics = self._get_tracked_metrics()
 
         self._loss_ignore = -100 if self.ignore_index is None else int(self.ignore_index)
-        self.loss_func = nn.CrossEntropyLoss(ignore_index=self._loss_ignore)   # kept for API parity (:40)
+        self._make_loss_func()
 
         self.to_rgb_fcn = to_rgb_fcn
         self.log_image_iter = log_image_iter
+
+    def set_loss_options(self, class_weights=None, label_smoothing=0.0):
+        """Replace the loss's class weights / label smoothing after construction (weights that are counted from data the
+        model's own device context serves, fit's `--class_weights balanced`).  Same checks as the constructor."""
+        self.class_weights = (None if class_weights is None
+                              else tuple(float(v) for v in check_class_weight(class_weights, self.n_classes)))
+        self.label_smoothing = check_label_smoothing(label_smoothing)
+        self._make_loss_func()
+        return self
+
+    def _make_loss_func(self):
+        self.loss_func = nn.CrossEntropyLoss(                                  # kept for API parity (:40)
+            weight=None if self.class_weights is None else torch.tensor(self.class_weights, dtype=torch.float32),
+            ignore_index=self._loss_ignore, label_smoothing=self.label_smoothing)
 
     # ------------------------------------------------------------------ construction
     def _get_tracked_metrics(self, average_mode='micro'):
@@ -88,7 +108,8 @@ class WaterSegmentationModel(LightningModule):
         are only written when someone needs them: training_step's image logging is disabled in the reference
         (`if False:`, water_seg_model.py:116), so the training path never does; the counts stay on the device."""
         images = self._gather_sources(batch)
-        out = self.model.loss(images, batch['target'], self._loss_ignore, return_logits=want_logits)
+        out = self.model.loss(images, batch['target'], self._loss_ignore, return_logits=want_logits,
+                              class_weight=self.class_weights, label_smoothing=self.label_smoothing)
         loss, output = out if want_logits else (out, None)
         counts = self.model.pop_confusion()
         return loss, output, counts

@@ -357,11 +357,34 @@ class HipUNet(nn.Module):
             raise ValueError("all input tensors must share batch, tile size and device")
         return srcs, B, H, W, dev
 
+    def _class_weight_dev(self, class_weight, device) -> Optional[torch.Tensor]:
+        """class_weight (None, a sequence or a tensor) -> fp32 [n_classes] on `device`, validated on the host and rounded to
+        fp32 once (check_class_weight).  The device copy is cached and reused while the caller passes the same object (for a
+        tensor: at the same version): one host-side check per set of weights, not one per step."""
+        if class_weight is None:
+            return None
+        key = (id(class_weight), getattr(class_weight, "_version", None), torch.device(device))
+        cached = getattr(self, "_cw_cache", None)
+        if cached is not None and cached[0] == key:
+            return cached[2]
+        w = check_class_weight(class_weight, self.n_classes)
+        dev_w = torch.from_numpy(w).to(device)
+        self._cw_cache = (key, class_weight, dev_w)      # (the source object is kept: its id stays taken)
+        return dev_w
+
+    def last_weighted_sums(self):
+        """(n_valid int64 scalar, weight_sum fp32 scalar) on the device, written by the last fu_loss_ce_weighted call: the
+        valid pixels and D = the sum of their targets' class weights (the loss's denominator).  None before such a call."""
+        return getattr(self, "_wce_sums", None)
+
     def _loss_raw(self, target: torch.Tensor, ignore_index: int, device, kind: str = "ce",
-                  dice_weight: float = 1.0) -> torch.Tensor:
+                  dice_weight: float = 1.0, class_weight=None, label_smoothing: float = 0.0) -> torch.Tensor:
         lib = _lib.load()
         target = target.contiguous().long()
         loss = torch.empty((), dtype=torch.float32, device=device)
+        weighted = class_weight is not None or float(label_smoothing) != 0.0
+        if weighted and kind != "ce":
+            raise ValueError(f"class_weight / label_smoothing belong to kind='ce'; kind={kind!r} takes neither")
         if kind == "bce_dice":
             check(lib.fu_loss_bce_dice(self._ctx, ptr(target), int(ignore_index), float(dice_weight), ptr(loss),
                                        self._stream(device)))
@@ -370,8 +393,18 @@ class HipUNet(nn.Module):
             raise ValueError(f"unknown loss kind {kind!r}")
         if self._confusion is None or self._confusion.device != device:
             self._confusion = torch.zeros(self.n_classes * self.n_classes, dtype=torch.int64, device=device)
-        check(lib.fu_loss_ce(self._ctx, ptr(target), int(ignore_index), ptr(loss), ptr(self._confusion), None,
-                             self._stream(device)))
+        if not weighted:                 # the reference's loss: the same call, the same kernels as ever
+            check(lib.fu_loss_ce(self._ctx, ptr(target), int(ignore_index), ptr(loss), ptr(self._confusion), None,
+                                 self._stream(device)))
+            return loss
+        eps = check_label_smoothing(label_smoothing)
+        cw = self._class_weight_dev(class_weight, device)
+        sums = getattr(self, "_wce_sums", None)
+        if sums is None or sums[0].device != torch.device(device):
+            sums = self._wce_sums = (torch.zeros((), dtype=torch.int64, device=device),
+                                     torch.zeros((), dtype=torch.float32, device=device))
+        check(lib.fu_loss_ce_weighted(self._ctx, ptr(target), int(ignore_index), ptr(cw), eps, ptr(loss),
+                                      ptr(self._confusion), ptr(sums[0]), ptr(sums[1]), self._stream(device)))
         return loss
 
     def _backward_raw(self, dlogits: Optional[torch.Tensor], device):
@@ -460,24 +493,29 @@ class HipUNet(nn.Module):
         return self._forward_raw(x, self.training)
 
     def loss(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int,
-             return_logits: bool = False, kind: str = "ce", dice_weight: float = 1.0):
+             return_logits: bool = False, kind: str = "ce", dice_weight: float = 1.0, class_weight=None,
+             label_smoothing: float = 0.0):
         """Fused forward + CrossEntropyLoss(ignore_index) (+ NaN guard) of water_seg_model.py:101-106
         (kind='ce', the reference's loss) or the BCE + soft-Dice extension (kind='bce_dice').
+        kind='ce' also takes class_weight (n_classes finite values >= 0: a sequence or a tensor) and label_smoothing in
+        [0, 1): nn.CrossEntropyLoss(weight, ignore_index, label_smoothing) in the fused kernels (fu_loss_ce_weighted), with
+        loss 0 and a zero gradient where the summed weight of the valid pixels is 0.  With both at their defaults the
+        reference's loss runs exactly as before.
         The returned loss is differentiable: ``loss.backward()`` runs the HIP backward."""
         if self.training and torch.is_grad_enabled():
             params = [p for _, p, _, _ in self._table]
             out = _UNetLossFn.apply(self, x, target, int(ignore_index), bool(return_logits), kind,
-                                    float(dice_weight), *params)
+                                    float(dice_weight), class_weight, float(label_smoothing), *params)
             return out if return_logits else out[0]
         logits = self._forward_raw(x, self.training, want_logits=return_logits)
-        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight)
+        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, class_weight, label_smoothing)
         return (loss, logits) if return_logits else loss
 
     def train_step(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int, kind: str = "ce",
-                   dice_weight: float = 1.0) -> torch.Tensor:
+                   dice_weight: float = 1.0, class_weight=None, label_smoothing: float = 0.0) -> torch.Tensor:
         """forward + loss + backward without autograd; gradients land in the flat buffer / p.grad."""
         self._forward_raw(x, True, want_logits=False)
-        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight)
+        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, class_weight, label_smoothing)
         self._backward_raw(None, _device_of(x))
         self.attach_grads()
         return loss
@@ -510,6 +548,33 @@ class HipUNet(nn.Module):
             check(lib.fu_block_param_range(self._ctx, b, C.byref(o), C.byref(n)))
             out.append((o.value, n.value))
         return out
+
+
+def check_class_weight(class_weight, n_classes: int):
+    """Class weights of the weighted cross entropy -> numpy fp32 [n_classes], rounded from fp64 once.  ValueError unless
+    they are n_classes finite numbers >= 0.  Host arithmetic only: the C call trusts the device copy it is given."""
+    import numpy as np
+    if isinstance(class_weight, torch.Tensor):
+        class_weight = class_weight.detach().cpu().numpy()
+    try:
+        w = np.asarray(class_weight, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"class weights must be {n_classes} numbers, got {class_weight!r}") from e
+    if w.ndim != 1 or w.shape[0] != int(n_classes):
+        raise ValueError(f"class weights: expected {n_classes} values (one per class), got shape {tuple(w.shape)}")
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError(f"class weights must be finite and >= 0, got {w.tolist()}")
+    w32 = w.astype(np.float32)
+    if not np.all(np.isfinite(w32)):
+        raise ValueError(f"class weights must be finite in fp32, got {w.tolist()}")
+    return w32
+
+
+def check_label_smoothing(label_smoothing) -> float:
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:          # (NaN fails both comparisons)
+        raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing!r}")
+    return eps
 
 
 def _device_of(x):
@@ -583,12 +648,13 @@ class _UNetLossFn(torch.autograd.Function):
     """(loss, logits) = CE(f(x; params), target): the fused training_step path."""
 
     @staticmethod
-    def forward(ctx, module: HipUNet, x, target, ignore_index, want_logits, kind, dice_weight, *params):
+    def forward(ctx, module: HipUNet, x, target, ignore_index, want_logits, kind, dice_weight, class_weight,
+                label_smoothing, *params):
         ctx.module = module
         ctx.device = _device_of(x)
         logits = module._forward_raw(x, True, want_logits=want_logits)
         ctx.generation = module._generation
-        loss = module._loss_raw(target, ignore_index, ctx.device, kind, dice_weight)
+        loss = module._loss_raw(target, ignore_index, ctx.device, kind, dice_weight, class_weight, label_smoothing)
         if logits is None:
             logits = torch.empty(0, device=ctx.device)
         ctx.mark_non_differentiable(logits)
@@ -603,7 +669,7 @@ class _UNetLossFn(torch.autograd.Function):
         check(_lib.load().fu_scale_loss_grad(m._ctx, ptr(dl), m._stream(ctx.device)))
         saved, alias = _save_accumulated(m)
         m._backward_raw(None, ctx.device)
-        return (None, None, None, None, None, None, None) + _return_param_grads(m, saved, alias)
+        return (None,) * 9 + _return_param_grads(m, saved, alias)
 
 
 class HipAdam(torch.optim.Adam):

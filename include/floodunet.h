@@ -15,6 +15,8 @@
  *                                water_seg_model.py:92-96)
  *   fu_loss_ce                  nn.CrossEntropyLoss(ignore_index) + nan_to_num + argmax + metric counts
  *                                                                            st_water_seg/models/water_seg_model.py:40,103-113
+ *   fu_loss_ce_weighted         (new) nn.CrossEntropyLoss(weight, ignore_index, label_smoothing) on the same path
+ *   fu_label_class_counts       (new) class frequencies of resident label rasters, for "balanced" weights
  *   fu_backward[_block]         loss.backward() issued by Lightning's automatic optimisation
  *                                                                            st_water_seg/fit.py:95-97
  *   fu_adam_step                optim.Adam(self.parameters(), lr).step()     st_water_seg/models/water_seg_model.py:198-205
@@ -141,6 +143,23 @@ int fu_forward_srcs(fu_ctx* ctx, const float* const* srcs, const int32_t* src_ch
  * (argmax prediction), ADDED to the existing contents.  n_valid_out: optional device int64 scalar. */
 int fu_loss_ce(fu_ctx* ctx, const int64_t* target, int ignore_index, float* loss_out, int64_t* confusion_out,
                int64_t* n_valid_out, fu_stream stream);
+/* Class-weighted, label-smoothed cross entropy (added within ABI 5: purely additive, no version bump; the reference has no
+ * such loss -- the specification is torch.nn.functional.cross_entropy(logits, target, weight, ignore_index=...,
+ * label_smoothing=...)).  With p = softmax(z), w = class_weight, W = sum_c w[c], eps = label_smoothing, C = n_classes and
+ * the sums over the valid pixels (target != ignore_index, 0 <= target < C):
+ *   loss = [(1 - eps) * sum_i w[t_i] (lse(z_i) - z_i[t_i]) + (eps / C) * sum_i sum_c w[c] (lse(z_i) - z_i[c])] / D,
+ *   D = sum_i w[t_i];  dL/dz_k = [(1 - eps) w[t] (p_k - [k == t]) + (eps / C) (p_k W - w[k])] / D.
+ * D == 0 (every pixel ignored, or only zero-weight classes present): loss 0 and a zero gradient, where torch gives NaN.
+ * class_weight_dev: fp32 [n_classes] on the device, or NULL = all ones.  The call TRUSTS that memory: the weights must be
+ * finite and >= 0, which only a host-side copy could check -- the caller validates them where they come from (HipUNet
+ * does).  label_smoothing must lie in [0, 1).  loss_out / confusion_out / n_valid_out as for fu_loss_ce (the counts are
+ * pixels, not weights); weight_sum_out: optional device fp32 scalar = D.  Reductions as fu_loss_ce: fp32 per-workgroup
+ * partials, a fixed fp64 tree, no floating-point atomics; in exact data-parallel mode the partials are summed over the ranks
+ * so that D is global.  All-ones weights (or NULL) with label_smoothing 0 give fu_loss_ce's loss, counts and gradient bit
+ * for bit.  State rules of fu_loss_ce. */
+int fu_loss_ce_weighted(fu_ctx* ctx, const int64_t* target, int ignore_index, const float* class_weight_dev,
+                        float label_smoothing, float* loss_out, int64_t* confusion_out, int64_t* n_valid_out,
+                        float* weight_sum_out, fu_stream stream);
 /* North-star extension (no reference counterpart; specification = oracle/unet_oracle.py:bce_dice_loss):
  * BCE on p = softmax(z)[1] vs [target == 1] + dice_weight * soft Dice, over target != ignore_index, fp32 wave-shuffle
  * reductions; stores its logits gradient for fu_backward like fu_loss_ce. */
@@ -352,6 +371,17 @@ int fu_scene_train_tiles(fu_ctx* ctx, int n, const fu_scene_train_entry* entries
                          int norm_mode, const float* global_mean, const float* global_std, float pad_value,
                          int64_t nodata_value, int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out,
                          float* std_out, fu_stream stream);
+
+/* Class frequencies of resident label rasters (added within ABI 5: purely additive), for "balanced" class weights.
+ * entries: a host table of n fu_scene_train_entry; only label, scene_h, scene_w and the box are read (scene, flags and
+ * angle_deg are ignored), a NULL label is rejected, and a box may be as large as its raster.  Every pixel of every box is
+ * decoded as fu_scene_train_tiles decodes it (raw 2 -> 1, raw 0 -> nodata_value, anything else -> 0) and counts_out[d]
+ * (device int64 [n_classes], caller-owned) is ADDED to for 0 <= d < n_classes; other values are dropped.  Integer
+ * arithmetic only (LDS histogram per workgroup, then 64-bit integer atomics): exact and order-independent.  One launch.
+ * The table goes through a library-owned device buffer ordered on `stream` (shared with fu_scene_train_tiles), and every
+ * entry is checked before anything is launched: a rejected call launches nothing and leaves counts_out untouched. */
+int fu_label_class_counts(fu_ctx* ctx, int n, const fu_scene_train_entry* entries, int64_t nodata_value, int n_classes,
+                          int64_t* counts_out, fu_stream stream);
 
 /* ---- inference stitching (ImageStitcher_v2, utils/utils_image.py:410-494) ------------- */
 /* canvas[h0:hE, w0:wE, :] += softmax(logits of sample `sample` of the last fu_forward)[:hE-h0, :wE-w0, :];
