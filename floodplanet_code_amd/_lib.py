@@ -142,6 +142,10 @@ SIGNATURES = {
     "fu_fp16_guard_state": (_i, [_p, C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "fu_adam_scalars": (_i, [_d, _d, _d, _d, _i64, _d, C.POINTER(C.c_float)]),
     "fu_adam_step_dev": (_i, [_p, _p, _p]),
+    "fu_bind_ema_state": (_i, [_p, _p, _p, _p]),
+    "fu_adam_ema_step": (_i, [_p, _d, _d, _d, _d, _i64, _d, _d, _p]),
+    "fu_adam_ema_scalars": (_i, [_d, _d, _d, _d, _i64, _d, _d, C.POINTER(C.c_float)]),
+    "fu_adam_ema_step_dev": (_i, [_p, _p, _p]),
     "fu_zero_grads": (_i, [_p, _p]),
     "fu_stitch_add": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "fu_stitch_finalize": (_i, [_p, _p, _i, _i, _i, _p, _p]),

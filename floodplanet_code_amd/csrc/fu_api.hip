@@ -383,6 +383,9 @@ struct fu_ctx {
   DeviceTable stitch_table, scene_table, train_table;   // fu_stitch_add_batch[_probs] / fu_scene_crops / fu_scene_train_tiles
   float* adam_m = nullptr;        // bound (caller-owned, fu_bind_adam_state): the moments outlive the context
   float* adam_v = nullptr;
+  float* ema_p = nullptr;         // bound (caller-owned, fu_bind_ema_state): the weight EMA and the EMA of the running statistics
+  float* ema_rm = nullptr;
+  float* ema_rv = nullptr;
   Profiler prof;
   struct Dp* dp = nullptr;            // fu_dp_init: RCCL communicator, communication stream, events
   std::vector<PackTable> pack_tabs;   // <= MAX_PACK layers per launch
@@ -1221,6 +1224,13 @@ int fu_bind_adam_state(fu_ctx* c, float* exp_avg, float* exp_avg_sq) {
   c->adam_m = exp_avg; c->adam_v = exp_avg_sq;
   return FU_OK;
 }
+int fu_bind_ema_state(fu_ctx* c, float* ema_params, float* ema_running_mean, float* ema_running_var) {
+  FU_REQUIRE(c, "null context");
+  const int given = (ema_params != nullptr) + (ema_running_mean != nullptr) + (ema_running_var != nullptr);
+  FU_REQUIRE(given == 0 || given == 3, "fu_bind_ema_state: give all three buffers, or all NULL to unbind");
+  c->ema_p = ema_params; c->ema_rm = ema_running_mean; c->ema_rv = ema_running_var;
+  return FU_OK;
+}
 int fu_params_changed(fu_ctx* c) {
   FU_REQUIRE(c, "null context");
   c->packed_dirty = true;
@@ -1518,6 +1528,53 @@ int fu_adam_step_dev(fu_ctx* c, const float* scalars_dev, fu_stream stream) {
   if (skip) FU_TRY(launch_guard_book(c->guard, (hipStream_t)stream));
   c->packed_dirty = true;
   return FU_OK;
+}
+
+namespace {
+// the shared tail of fu_adam_ema_step[_dev]: fp16 guard, one launch over the parameters and the BatchNorm channels
+int adam_ema_launch(fu_ctx* c, const char* who, const float sc[8], const float* scalars_dev, fu_stream stream) {
+  if (!c->adam_m || !c->adam_v) {
+    set_error("%s: no moment buffers bound (fu_bind_adam_state)", who);
+    return FU_ERR_STATE;
+  }
+  if (!c->ema_p) {
+    set_error("%s: no EMA buffers bound (fu_bind_ema_state)", who);
+    return FU_ERR_STATE;
+  }
+  const int* skip = nullptr;
+  if (c->prec == PREC_F16) {
+    FU_TRY(launch_grad_finite_check(c->G, c->total_params, c->guard, (hipStream_t)stream));
+    skip = c->guard;
+  }
+  FU_TRY(launch_adam_ema(c->P, c->G, c->adam_m, c->adam_v, c->ema_p, c->total_params, c->ema_rm, c->RM, c->ema_rv, c->RV,
+                         c->total_bn, sc, scalars_dev, (hipStream_t)stream, skip));
+  if (skip) FU_TRY(launch_guard_book(c->guard, (hipStream_t)stream));
+  c->packed_dirty = true;
+  return FU_OK;
+}
+}  // namespace
+
+int fu_adam_ema_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
+                        double ema_weight, float out[8]) {
+  FU_REQUIRE(out && step >= 1, "fu_adam_ema_scalars: bad argument");
+  FU_REQUIRE(ema_weight >= 0.0 && ema_weight <= 1.0, "fu_adam_ema_scalars: ema_weight %g outside [0, 1]", ema_weight);
+  adam_scalars(lr, beta1, beta2, eps, step, grad_scale, out);
+  out[7] = (float)ema_weight;
+  return FU_OK;
+}
+
+int fu_adam_ema_step(fu_ctx* c, double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
+                     double ema_weight, fu_stream stream) {
+  FU_REQUIRE(c && c->P && c->G && c->RM && c->RV, "fu_adam_ema_step: buffers not bound (fu_bind_buffers)");
+  float sc[8];
+  FU_TRY(fu_adam_ema_scalars(lr, beta1, beta2, eps, step, grad_scale, ema_weight, sc));
+  return adam_ema_launch(c, "fu_adam_ema_step", sc, nullptr, stream);
+}
+
+int fu_adam_ema_step_dev(fu_ctx* c, const float* scalars_dev, fu_stream stream) {
+  FU_REQUIRE(c && c->P && c->G && c->RM && c->RV && scalars_dev,
+             "fu_adam_ema_step_dev: buffers not bound (fu_bind_buffers), or null scalars");
+  return adam_ema_launch(c, "fu_adam_ema_step_dev", nullptr, scalars_dev, stream);
 }
 
 int fu_adam_state(fu_ctx* c, float** exp_avg, float** exp_avg_sq) {

@@ -531,5 +531,10 @@ int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double 
 void adam_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale, float out[7]);
 int launch_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* scalars_dev, hipStream_t s,
                     const int* skip = nullptr);
+// Adam + weight EMA in one launch (parameters, then the BatchNorm running statistics): sc = the eight host scalars, or
+// scalars_dev != null = the same eight read on the device (the captured form)
+int launch_adam_ema(float* p, const float* g, float* m, float* v, float* e, int64_t n, float* erm, const float* rm,
+                    float* erv, const float* rv, int64_t nbn, const float sc[8], const float* scalars_dev, hipStream_t s,
+                    const int* skip = nullptr);
 
 }  // namespace fu

@@ -2193,6 +2193,118 @@ int launch_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, con
 }
 
 // ------------------------------------------------------------------------------------------------
+// Adam + weight EMA in one pass: the update of k_adam, then ema = lerp(ema, p_new, w) on the value just written -- 9 streams
+// of n floats where k_adam moves 7, in 16-byte accesses.  The lerp is torch's CPU Tensor.lerp_(end, w) on float32, which in
+// ATen is ONE fused multiply-add in either branch (LerpKernel.cpp, vector and scalar loop alike):
+//   w <  0.5:  fma(w,     end - self, self)
+//   w >= 0.5:  fma(w - 1, end - self, end)         (w - 1 rounded to float first)
+// The branch is taken from the float w, on the device in the captured form (w crosses 0.5 during the warm-up).  The same
+// launch averages the BatchNorm running statistics (nbn channels, two arrays) after the parameters.
+// ------------------------------------------------------------------------------------------------
+struct AdamScalars { float w1, beta2, omb2, bc2_sqrt, eps, neg_step, gscale, ema_w; };
+
+__device__ __forceinline__ float ema_lerp(float self, float end, float wl, bool small) {
+  const float d = end - self;
+  return fmaf(wl, d, small ? self : end);
+}
+// k_adam's float sequence on one element (no contraction), then the EMA of the new parameter
+__device__ __forceinline__ void adam_ema_elem(float& p, float g, float& m, float& v, float& e, const AdamScalars& s, float wl,
+                                              bool small) {
+#pragma clang fp contract(off)
+  const float gi = g * s.gscale;
+  float mi = m, vi = v;
+  const float dm = gi - mi;
+  mi = fmaf(s.w1, dm, mi);
+  const float vb = vi * s.beta2;
+  const float og = s.omb2 * gi;
+  vi = vb + og * gi;
+  const float denom = sqrtf(vi) / s.bc2_sqrt + s.eps;
+  const float num = s.neg_step * mi;
+  p = p + num / denom;
+  m = mi;
+  v = vi;
+  e = ema_lerp(e, p, wl, small);
+}
+// head: the elements in front of the first 16-byte boundary (n when the five arrays are not aligned alike: all scalar)
+__device__ __forceinline__ void adam_ema_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, float* __restrict__ e, int64_t n, int64_t head,
+                                              const AdamScalars& s, float* __restrict__ erm, const float* __restrict__ rm,
+                                              float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn) {
+#pragma clang fp contract(off)
+  const bool small = fabsf(s.ema_w) < 0.5f;
+  const float wl = small ? s.ema_w : s.ema_w - 1.0f;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nvec = (n - head) / 4;
+  for (int64_t j = tid; j < nvec; j += nthr) {
+    const int64_t i = head + 4 * j;
+    float4 p4 = *reinterpret_cast<const float4*>(p + i);
+    const float4 g4 = *reinterpret_cast<const float4*>(g + i);
+    float4 m4 = *reinterpret_cast<const float4*>(m + i);
+    float4 v4 = *reinterpret_cast<const float4*>(v + i);
+    float4 e4 = *reinterpret_cast<const float4*>(e + i);
+    adam_ema_elem(p4.x, g4.x, m4.x, v4.x, e4.x, s, wl, small);
+    adam_ema_elem(p4.y, g4.y, m4.y, v4.y, e4.y, s, wl, small);
+    adam_ema_elem(p4.z, g4.z, m4.z, v4.z, e4.z, s, wl, small);
+    adam_ema_elem(p4.w, g4.w, m4.w, v4.w, e4.w, s, wl, small);
+    *reinterpret_cast<float4*>(p + i) = p4;
+    *reinterpret_cast<float4*>(m + i) = m4;
+    *reinterpret_cast<float4*>(v + i) = v4;
+    *reinterpret_cast<float4*>(e + i) = e4;
+  }
+  const int64_t tail0 = head + 4 * nvec, nrest = head + (n - tail0);      // misaligned head and tail: plain code
+  for (int64_t k = tid; k < nrest; k += nthr) {
+    const int64_t i = k < head ? k : tail0 + (k - head);
+    adam_ema_elem(p[i], g[i], m[i], v[i], e[i], s, wl, small);
+  }
+  for (int64_t i = tid; i < nbn; i += nthr) {
+    erm[i] = ema_lerp(erm[i], rm[i], wl, small);
+    erv[i] = ema_lerp(erv[i], rv[i], wl, small);
+  }
+}
+__global__ __launch_bounds__(256) void k_adam_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, float* __restrict__ e, int64_t n, int64_t head,
+                                                  AdamScalars s, float* __restrict__ erm, const float* __restrict__ rm,
+                                                  float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn,
+                                                  const int* __restrict__ skip) {
+  if (skip && *skip) return;         // fp16 guard: a skipped step leaves the averages untouched too
+  adam_ema_body(p, g, m, v, e, n, head, s, erm, rm, erv, rv, nbn);
+}
+// the scalars (fu_adam_ema_scalars: the seven of k_adam_dev, then the EMA weight) read from device memory
+__global__ __launch_bounds__(256) void k_adam_ema_dev(float* __restrict__ p, const float* __restrict__ g,
+                                                      float* __restrict__ m, float* __restrict__ v, float* __restrict__ e,
+                                                      int64_t n, int64_t head, const float* __restrict__ sc,
+                                                      float* __restrict__ erm, const float* __restrict__ rm,
+                                                      float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn,
+                                                      const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  const AdamScalars s = {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], sc[7]};
+  adam_ema_body(p, g, m, v, e, n, head, s, erm, rm, erv, rv, nbn);
+}
+
+static int64_t adam_ema_head(const float* p, const float* g, const float* m, const float* v, const float* e, int64_t n) {
+  const uintptr_t a = (uintptr_t)p & 15;
+  if (((uintptr_t)g & 15) != a || ((uintptr_t)m & 15) != a || ((uintptr_t)v & 15) != a || ((uintptr_t)e & 15) != a || (a & 3))
+    return n;
+  const int64_t head = (int64_t)(((16 - a) & 15) / 4);
+  return head < n ? head : n;
+}
+int launch_adam_ema(float* p, const float* g, float* m, float* v, float* e, int64_t n, float* erm, const float* rm,
+                    float* erv, const float* rv, int64_t nbn, const float sc[8], const float* scalars_dev, hipStream_t s,
+                    const int* skip) {
+  const int64_t head = adam_ema_head(p, g, m, v, e, n);
+  const dim3 grid(grid_for(ceil_div64(n, 4), 256, 4096));
+  if (scalars_dev) {
+    hipLaunchKernelGGL(k_adam_ema_dev, grid, dim3(256), 0, s, p, g, m, v, e, n, head, scalars_dev, erm, rm, erv, rv, nbn,
+                       skip);
+  } else {
+    const AdamScalars as = {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], sc[7]};
+    hipLaunchKernelGGL(k_adam_ema, grid, dim3(256), 0, s, p, g, m, v, e, n, head, as, erm, rm, erv, rv, nbn, skip);
+  }
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // The gradient the head backward consumes: eff = dlogits * up * S, written OUT OF PLACE (the stored loss gradient stays as
 // fu_loss_* left it, so a second backward of the same loss -- retain_graph, fu_backward_block(0) twice -- sees the same
 // input; in place, the second call would have found max|dl| already in [32, 64), chosen S = 1 and unscaled by 1).

@@ -121,12 +121,18 @@ class DataParallelTrainer:
 
     def __init__(self, net, lr: float, world_size: int = 1, rank: int = 0, betas=(0.9, 0.999), eps: float = 1e-8,
                  group=None, cap_bytes: int = 16 << 20, exact: bool = False, time_waits: bool = False,
-                 graph: bool = False, class_weight=None, label_smoothing: float = 0.0):
+                 graph: bool = False, class_weight=None, label_smoothing: float = 0.0, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = True):
         """exact=False: DDP semantics (per-rank BN statistics and 1/N_valid, gradients averaged).
         exact=True: SyncBN statistics and a global N_valid (HipUNet.enable_exact_sync); the ranks together reproduce
         one device with world_size x the batch, gradients are summed (SURVEY.md 8(e) "exact mode").
         class_weight / label_smoothing: the weighted, label-smoothed cross entropy of HipUNet.loss for every step (defaults:
-        the reference's loss); in exact mode its denominator, the summed weight of the valid pixels, is global too."""
+        the reference's loss); in exact mode its denominator, the summed weight of the valid pixels, is global too.
+        ema_decay: keep a weight EMA on the net (HipUNet.enable_ema(ema_decay, ema_warmup)), moved on inside the fused Adam
+        launch of every path -- eager, exact and captured.  It is rank-local and needs no collective: the ranks' parameters
+        are identical, so their averages are."""
+        if ema_decay is not None:
+            net.enable_ema(ema_decay, ema_warmup)
         self.net, self.lr, self.world_size, self.rank = net, lr, world_size, rank
         self.class_weight, self.label_smoothing = class_weight, float(label_smoothing)
         self.betas, self.eps, self.group, self.cap_bytes = betas, eps, group, cap_bytes
@@ -136,13 +142,15 @@ class DataParallelTrainer:
         self.step_count = 0
         self.time_waits = time_waits
         # graph=True (single device): the whole step -- fu_forward, fu_loss_ce, fu_backward with its side-stream fork / join,
-        # fu_adam_step_dev -- is captured once into a hipGraph (torch.cuda.CUDAGraph on the capture stream the C calls are
-        # issued on) and replayed; only the seven Adam scalars, which depend on the step count, are refreshed per step.  The
+        # fu_adam_step_dev (fu_adam_ema_step_dev with a weight EMA) -- is captured once into a hipGraph (torch.cuda.CUDAGraph on
+        # the capture stream the C calls are issued on) and replayed; only the seven Adam scalars (eight with the EMA weight),
+        # which depend on the step count, are refreshed per step.  The
         # captured launches are valid for ONE (x, target) pair of device buffers: other tensors are copied into them.
         self.graph = bool(graph) and world_size <= 1
         self._graph = None
         self._gx = self._gt = self._gloss = self._gscal = self._gscal_host = None
         self._g_ignore = None
+        self._g_ema = False
         self._reducer: Optional[BucketedReducer] = None
         self._launch_stream = None     # the stream the bucket all-reduces are launched from (mode 2, fu_backward_fence)
         self._synced = False
@@ -170,9 +178,17 @@ class DataParallelTrainer:
     def _adam_scalars_to_device(self, step: int):
         import ctypes as C
         from . import _lib
-        buf = (C.c_float * 7)()
-        _lib.check(_lib.load().fu_adam_scalars(float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                               int(step), 1.0, buf))
+        ema = self.net._ema
+        if self._g_ema:                  # eight scalars: the EMA weight of this update rides behind Adam's seven
+            from .ema import ema_weight
+            buf = (C.c_float * 8)()
+            _lib.check(_lib.load().fu_adam_ema_scalars(float(self.lr), float(self.betas[0]), float(self.betas[1]),
+                                                       float(self.eps), int(step), 1.0,
+                                                       ema_weight(ema[0], int(step), ema[1]), buf))
+        else:
+            buf = (C.c_float * 7)()
+            _lib.check(_lib.load().fu_adam_scalars(float(self.lr), float(self.betas[0]), float(self.betas[1]),
+                                                   float(self.eps), int(step), 1.0, buf))
         # A ring of pinned slots, each guarded by an event recorded behind its host-to-device copy: nothing in a replayed step
         # synchronises, so the host runs steps ahead of the GPU, and ONE pinned buffer would be rewritten for step k+1, k+2, ...
         # before the copy of step k has executed (the replay of step k would then take a later step's bias corrections).
@@ -194,8 +210,10 @@ class DataParallelTrainer:
         self._gx, self._gt, self._g_ignore = torch.empty_like(x), torch.empty_like(target), int(ignore_index)
         self._gx.copy_(x)
         self._gt.copy_(target)
-        self._gscal = torch.zeros(7, dtype=torch.float32, device=dev)
-        self._gscal_ring = [torch.zeros(7, dtype=torch.float32).pin_memory() for _ in range(8)]
+        self._g_ema = net.ema_enabled                                 # which optimiser launch this graph holds
+        n_scal = 8 if self._g_ema else 7
+        self._gscal = torch.zeros(n_scal, dtype=torch.float32, device=dev)
+        self._gscal_ring = [torch.zeros(n_scal, dtype=torch.float32).pin_memory() for _ in range(8)]
         self._gscal_ev = [None] * 8
         lib = _lib.load()
         net._class_weight_dev(self.class_weight, dev)                # the weights' upload stays outside the capture
@@ -207,7 +225,10 @@ class DataParallelTrainer:
             self._gloss = net._loss_raw(self._gt, self._g_ignore, dev, class_weight=self.class_weight,
                                         label_smoothing=self.label_smoothing)
             net._backward_raw(None, dev)
-            _lib.check(lib.fu_adam_step_dev(net._ctx, self._gscal.data_ptr(), net._stream(dev)))
+            if self._g_ema:
+                _lib.check(lib.fu_adam_ema_step_dev(net._ctx, self._gscal.data_ptr(), net._stream(dev)))
+            else:
+                _lib.check(lib.fu_adam_step_dev(net._ctx, self._gscal.data_ptr(), net._stream(dev)))
         net._generation -= 1          # (the capture enqueued nothing; the bookkeeping of _forward_raw is redone per replay)
         if dot:       # (torch's own debug_dump writes nothing on this ROCm build)
             import ctypes
@@ -220,7 +241,8 @@ class DataParallelTrainer:
 
     def _graph_step(self, x, target, ignore_index):
         net = self.net
-        if self._graph is not None and (int(ignore_index) != self._g_ignore or x.shape != self._gx.shape):
+        if self._graph is not None and (int(ignore_index) != self._g_ignore or x.shape != self._gx.shape
+                                        or self._g_ema != net.ema_enabled):
             self._graph = None                                        # another workload: capture again
         if self._graph is None:
             if net._ctx is None or net._ctx_key[1:3] != tuple(x.shape[2:]) or net._ctx_key[3] < x.shape[0]:

@@ -117,15 +117,20 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
         train_seconds = time.perf_counter() - t0
         model.valid_metrics.reset()
         outs = []
-        for i, batch in _limited(valid_loader, c["limit_val_batches"]):
-            outs.append(model.validation_step(batch, i))
+        with model.eval_weights():                                           # the weight EMA, swapped in once per epoch
+            for i, batch in _limited(valid_loader, c["limit_val_batches"]):
+                outs.append(model.validation_step(batch, i))
         model.validation_epoch_end(outs)
         miou = float(model.logged.get("val_MulticlassJaccardIndex", torch.zeros(())))
         history.append({"epoch": epoch, "train_loss": float(loss.detach()), "val_MulticlassJaccardIndex": miou,
                         "train_tiles_per_s": n_tiles / train_seconds if n_tiles and train_seconds > 0 else None})
         if ckpt_dir:
             path = os.path.join(ckpt_dir, f"model-epoch={epoch:02d}-val_MulticlassJaccardIndex={miou:.4f}.ckpt")
-            torch.save({"state_dict": model.state_dict(), "epoch": epoch, "hyper_parameters": dict(c)}, path)
+            ckpt = {"state_dict": model.state_dict(), "epoch": epoch, "hyper_parameters": dict(c)}
+            hook = getattr(model, "on_save_checkpoint", None)                # (the weight EMA: "ema_state_dict")
+            if hook is not None:
+                hook(ckpt)
+            torch.save(ckpt, path)
             best.append((miou, path))
             best.sort(key=lambda t: -t[0])
             for _, stale in best[c["save_topk_models"]:]:
@@ -171,6 +176,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="cross-entropy class weights: 'balanced' (from the TRAIN split's class frequencies) or one number "
                          "per class")
     ap.add_argument("--label_smoothing", type=float, default=0.0, help="cross-entropy label smoothing in [0, 1)")
+    ap.add_argument("--ema_decay", type=float, default=None, metavar="F",
+                    help="keep an exponential moving average of the weights with this decay in [0, 1): validation, the "
+                         "checkpoint choice and the checkpoint's ema_state_dict use it (default: no EMA)")
+    ap.add_argument("--no_ema_warmup", action="store_true",
+                    help="use --ema_decay from the first update on (default: min(decay, (1 + n) / (10 + n)))")
     ap.add_argument("--no_transforms", action="store_true", help="train without hflip / vflip / rotate")
     ap.add_argument("--no_shuffle", action="store_true", help="train in data-set order")
     ap.add_argument("--device", type=str, default="cuda:0")
@@ -195,7 +205,8 @@ def parse_class_weights(values, n_classes: Optional[int] = None):
 def cfg_from_args(args, class_weights=None) -> dict:
     """The reference-style config of a command line: what fit_model trains with and dumps into the checkpoint.
     class_weights: the resolved numeric weights (the data decides 'balanced' and the class count, so main() resolves them);
-    they and --label_smoothing enter model_kwargs only when set, so a plain command line gives the config it always gave."""
+    they, --label_smoothing, --ema_decay and --no_ema_warmup enter model_kwargs only when set, so a plain command line gives
+    the config it always gave."""
     norm_mode = None if args.norm_mode == "none" else args.norm_mode
     parsed = parse_class_weights(getattr(args, "class_weights", None), N_CLASSES)
     if class_weights is None and parsed is not None and parsed != "balanced":
@@ -205,6 +216,12 @@ def cfg_from_args(args, class_weights=None) -> dict:
         loss_kwargs["class_weights"] = [float(v) for v in class_weights]
     if float(getattr(args, "label_smoothing", 0.0)) != 0.0:
         loss_kwargs["label_smoothing"] = float(args.label_smoothing)
+    if getattr(args, "ema_decay", None) is not None:
+        from .ema import check_decay
+        loss_kwargs["ema_decay"] = check_decay(args.ema_decay)
+        loss_kwargs["ema_warmup"] = not getattr(args, "no_ema_warmup", False)
+    elif getattr(args, "no_ema_warmup", False):
+        raise ValueError("--no_ema_warmup needs --ema_decay")
     return dict(lr=args.lr, batch_size=args.batch_size, n_epochs=args.n_epochs, crop_height=args.crop[0],
                 crop_width=args.crop[1], crop_stride=args.stride, ignore_index=args.ignore_index,
                 save_topk_models=args.save_topk_models, seed_num=args.seed, n_workers=args.n_workers,

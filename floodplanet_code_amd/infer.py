@@ -37,7 +37,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .predict import CONFIG_DEFAULTS, _merge, resolve_cfg
+from .predict import CONFIG_DEFAULTS, WEIGHT_CHOICES, _merge, load_checkpoint_model, resolve_cfg
 from .tta import VIEW_SETS, view_codes
 
 SCALE_MODES = {"S1": 1, "S2": 2, "L8": 3}                    # PS: 4 when stored as uint16, else 0
@@ -200,16 +200,19 @@ def check_model_inputs(cfg: dict, norm_params=None) -> None:
 def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Optional[dict] = None,
           size: Optional[Sequence[int]] = None, scale: Optional[float] = None, stride: Optional[int] = None,
           batch_size: Optional[int] = None, tta=None, n_workers: int = 0, device: str = "cuda:0",
-          keep_probabilities: bool = False, norm_params=None) -> dict:
+          keep_probabilities: bool = False, norm_params=None, weights: str = "auto") -> dict:
     """Class maps of every input scene (see the module docstring).  cfg: the resolved config (default: resolve_cfg of
     the checkpoint's experiment).  Returns the summary.json dict; with keep_probabilities also "probabilities"
     {output path: fp32 [H, W, k] stitched canvas} (one more host read per scene; for tests and comparisons).
     norm_params: the parameter file of norm_mode 'global' (path, or the dict it holds; datasets.stats), looked up by the
-    config's data set name and sensor; without it a 'global' config is rejected."""
+    config's data set name and sensor; without it a 'global' config is rejected.  weights: 'auto', 'raw' or 'ema'
+    (predict.checkpoint_weights); the summary records the choice made under "weights"."""
     from .datasets.floodplanet import _N_CHANNELS
     from .models import build_model
 
     t_start = time.perf_counter()
+    if weights not in WEIGHT_CHOICES:
+        raise ValueError(f"weights must be one of {list(WEIGHT_CHOICES)}, got {weights!r}")
     if cfg is None:
         experiment_dir = "/".join(checkpoint_path.split("/")[:-2])
         cfg = resolve_cfg(experiment_dir, checkpoint_path)
@@ -245,10 +248,12 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     from .stitch import GpuImageStitcher
     from .datasets.synthetic import write_strip_tiff
     dev = torch.device(device)
-    model_kwargs = dict(cfg["model"].get("model_kwargs") or {})
+    model_kwargs = {k: v for k, v in (cfg["model"].get("model_kwargs") or {}).items()
+                    if k not in ("ema_decay", "ema_warmup")}
     model = build_model(cfg["model"]["name"], n_channels, 3, cfg["lr"], log_image_iter=cfg["log_image_iter"],
                         to_rgb_fcn=None, ignore_index=cfg["ignore_index"], **model_kwargs)
-    model = model.load_from_checkpoint(checkpoint_path, in_channels=n_channels, n_classes=3, lr=cfg["lr"], **model_kwargs)
+    model, chosen = load_checkpoint_model(model, checkpoint_path, weights, in_channels=n_channels, n_classes=3,
+                                          lr=cfg["lr"], **model_kwargs)
     model._set_model_to_eval()
     model = model.to(dev)
     net = model.model
@@ -327,7 +332,7 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     seconds = time.perf_counter() - t_start
     summary = {"scenes": records, "n_scenes": len(records), "n_crops": n_crops, "seconds": seconds,
                "crops_per_s": n_crops / seconds if seconds > 0 else None, "max_resident_scenes": max_resident,
-               "tta": tta if (tta is None or isinstance(tta, str)) else list(codes)}
+               "tta": tta if (tta is None or isinstance(tta, str)) else list(codes), "weights": chosen}
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "summary.json"), "w") as fh:
         json.dump(summary, fh, indent=4)
@@ -349,6 +354,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch_size", type=int, default=None, help="crops per eval forward (default: the config's)")
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips / rotations")
+    ap.add_argument("--weights", type=str, default="auto", choices=list(WEIGHT_CHOICES),
+                    help="which weights of the checkpoint to serve: state_dict (raw), weight EMA (ema) or the EMA when the "
+                         "checkpoint has one (auto, the default)")
     ap.add_argument("--n_workers", type=int, default=0,
                     help="scene decoding worker processes (default 0: decode in-process, the faster setting measured)")
     ap.add_argument("--device", type=str, default="cuda:0")
@@ -363,7 +371,7 @@ def main(argv: Optional[List[str]] = None) -> None:
     cfg = resolve_cfg(experiment_dir, args.checkpoint_path)
     out = infer(args.checkpoint_path, args.inputs, args.out_dir, cfg=cfg, size=args.size, scale=args.scale,
                 stride=args.stride, batch_size=args.batch_size, tta=args.tta, n_workers=args.n_workers,
-                device=args.device, norm_params=args.norm_params)
+                device=args.device, norm_params=args.norm_params, weights=args.weights)
     print(json.dumps({k: v for k, v in out.items() if k != "scenes"}))
 
 

@@ -41,6 +41,9 @@ except Exception:  # ModuleNotFoundError in this image
             ckpt = torch.load(checkpoint_path, map_location=map_location or "cpu", weights_only=False)
             model = cls(**kwargs)
             model.load_state_dict(ckpt["state_dict"] if "state_dict" in ckpt else ckpt)
+            hook = getattr(model, "on_load_checkpoint", None)       # Lightning's hook: extra top-level checkpoint entries
+            if hook is not None and isinstance(ckpt, dict) and "state_dict" in ckpt:
+                hook(ckpt)
             return model
 
         @property

@@ -11,9 +11,14 @@ names; the network, the loss, the backward pass and the metric counters run in l
     nn.CrossEntropyLoss(ignore_index=None) fails at call time.
 Extra keyword arguments (not in the reference): ``precision`` ('fp32' | 'bf16' | 'fp16'), ``base_channels``,
 ``class_weights`` (n_classes finite values >= 0) and ``label_smoothing`` in [0, 1): the weighted, label-smoothed cross
-entropy of nn.CrossEntropyLoss(weight, ignore_index, label_smoothing), in the fused loss kernels.
+entropy of nn.CrossEntropyLoss(weight, ignore_index, label_smoothing), in the fused loss kernels; ``ema_decay`` in [0, 1)
+and ``ema_warmup``: an exponential moving average of the weights, updated inside the fused Adam launch, that validation and
+test steps evaluate and that checkpoints carry as the top-level entry ``ema_state_dict`` (state_dict() stays the raw
+weights under the reference's keys).
 """
 from __future__ import annotations
+
+import contextlib
 
 import numpy as np
 import torch
@@ -22,18 +27,22 @@ import torch.optim as optim
 
 from ..lightning_compat import LightningModule
 from ..metrics import SegmentationMetrics
+from ..ema import check_decay
 from ..unet import HipAdam, HipUNet, check_class_weight, check_label_smoothing
 
 
 class WaterSegmentationModel(LightningModule):
 
     def __init__(self, in_channels, n_classes, lr, log_image_iter=50, to_rgb_fcn=None, ignore_index=None,
-                 optimizer_name='adam', precision='fp32', base_channels=64, class_weights=None, label_smoothing=0.0):
+                 optimizer_name='adam', precision='fp32', base_channels=64, class_weights=None, label_smoothing=0.0,
+                 ema_decay=None, ema_warmup=True):
         super().__init__()
         # checked on the host before anything touches the GPU; kept as plain Python numbers (checkpoint hyper_parameters)
         self.class_weights = (None if class_weights is None
                               else tuple(float(v) for v in check_class_weight(class_weights, n_classes)))
         self.label_smoothing = check_label_smoothing(label_smoothing)
+        self.ema_decay = None if ema_decay is None else check_decay(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
         self.lr = lr
         self.n_classes = n_classes
         self.in_channels = in_channels
@@ -43,6 +52,8 @@ class WaterSegmentationModel(LightningModule):
         self.base_channels = base_channels
 
         self._build_model()
+        if self.ema_decay is not None:                   # host bookkeeping only: the buffers are made on the module's device
+            self.model.enable_ema(self.ema_decay, self.ema_warmup)
 
         if self.ignore_index == -1:                      # water_seg_model.py:35-36
             self.ignore_index = self.n_classes - 1
@@ -103,6 +114,33 @@ class WaterSegmentationModel(LightningModule):
     def _set_model_to_eval(self):
         self.model.eval()
 
+    def eval_weights(self):
+        """What validation and test steps evaluate: the averaged weights when the model keeps an EMA, else the live ones.
+        A context manager.  Each entry and exit re-binds the network's buffers and repacks its weights once, so a loop over
+        many batches enters it once around the loop (fit_model does); a step outside such a block enters it for itself."""
+        if self.ema_decay is None or self.model.ema_serving:
+            return contextlib.nullcontext()
+        return self.model.ema_weights()
+
+    # the EMA travels beside state_dict(), as its own top-level checkpoint entry (Lightning calls these hooks with the
+    # checkpoint dict; fit_model and the LightningModule stand-in's load_from_checkpoint do the same)
+    # "ema_state_dict" has the keys of this module's state_dict() (so it loads wherever "state_dict" loads): the network's
+    # entries come from the average, anything else (a loss weight buffer) is the live value.
+    @staticmethod
+    def _net_key(key):
+        return key[6:] if key.startswith("model.") else key
+
+    def on_save_checkpoint(self, checkpoint):
+        if self.ema_decay is not None:
+            ema = self.model.ema_state_dict()
+            checkpoint["ema_state_dict"] = {k: ema.get(self._net_key(k), v).detach().cpu()
+                                            for k, v in self.state_dict().items()}
+
+    def on_load_checkpoint(self, checkpoint):
+        ema = checkpoint.get("ema_state_dict") if isinstance(checkpoint, dict) else None
+        if ema is not None and self.ema_decay is not None:
+            self.model.load_ema_state_dict({self._net_key(k): v for k, v in ema.items()})
+
     def _fused_loss(self, batch, want_logits=False):
         """forward + CE(ignore_index) + NaN guard + argmax + confusion counts in the fused kernels.  The fp32 NCHW logits
         are only written when someone needs them: training_step's image logging is disabled in the reference
@@ -124,7 +162,7 @@ class WaterSegmentationModel(LightningModule):
 
     def validation_step(self, batch, batch_idx):
         self._set_model_to_eval()
-        with torch.no_grad():
+        with torch.no_grad(), self.eval_weights():
             loss, output, counts = self._fused_loss(batch)
         metric_output = self.valid_metrics.update_from_counts(counts)
         self.valid_metrics.update_from_counts(counts)    # the reference counts each batch twice (:150-151)
@@ -133,7 +171,7 @@ class WaterSegmentationModel(LightningModule):
 
     def test_step(self, batch, batch_idx):
         self._set_model_to_eval()
-        with torch.no_grad():
+        with torch.no_grad(), self.eval_weights():
             loss, output, counts = self._fused_loss(batch)
         self.test_metrics.update_from_counts(counts)
         self.log_dict({'test_loss': loss}, prog_bar=True, on_step=True, on_epoch=True)
@@ -145,6 +183,9 @@ class WaterSegmentationModel(LightningModule):
             # FU_TORCH_ADAM=1 keeps torch's own optimiser (it works on the same parameters).
             import os
             if os.environ.get("FU_TORCH_ADAM") == "1":
+                if self.ema_decay is not None:
+                    raise NotImplementedError("the weight EMA is part of the fused Adam kernel (HipAdam): FU_TORCH_ADAM=1 "
+                                              "together with ema_decay is not supported")
                 optimizer = optim.Adam(self.parameters(), lr=self.lr)
             else:
                 optimizer = HipAdam(self.model, lr=self.lr)

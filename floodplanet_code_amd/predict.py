@@ -21,6 +21,9 @@ image_predictions/<region>/<image>/{pred_class.tif, pred_softmax.png, cm.png}.  
 Extension: --tta {hflip,flips,d4} (test-time augmentation, floodplanet_code_amd.tta) averages each crop's softmax over
 flips / 90-degree rotations: per batch one forward of T*B view samples (HipUNet.forward_views), one fu_merge_views for
 the averaged probabilities and their confusion counts, one fu_stitch_add_batch_probs; metrics.json gains a "tta" key.
+Extension: --weights {auto,raw,ema} chooses between the checkpoint's state_dict and the weight EMA a run with --ema_decay
+stored beside it as ema_state_dict (auto: the EMA when there is one); metrics.json records the choice under "weights"
+whenever the EMA was served or a choice was given (absent: the state_dict, as always).
 Out of scope: rgb.png, gt.png and rgb_cm.gif (to_RGB and a GIF encoder), infer.py, multi-GPU prediction, datasets other
 than floodplanet.
 """
@@ -79,6 +82,36 @@ def resolve_cfg(experiment_dir: str, checkpoint_path: str) -> dict:
             raise ValueError(f"no config.yaml under {experiment_dir} (or PyYAML missing) and no hyper_parameters in "
                              f"{checkpoint_path}")
     return _merge(CONFIG_DEFAULTS, dict(cfg))
+
+
+WEIGHT_CHOICES = ("auto", "raw", "ema")
+
+
+def checkpoint_weights(ckpt: dict, which: str = "auto", path: Optional[str] = None):
+    """Which weights of a checkpoint to serve -> (state_dict, chosen) with chosen 'raw' or 'ema'.  'raw': the checkpoint's
+    state_dict (a bare state dict counts as one); 'ema': its ema_state_dict, an error naming the file when it has none;
+    'auto': 'ema' when there is one, else 'raw'.  Host only."""
+    if which not in WEIGHT_CHOICES:
+        raise ValueError(f"weights must be one of {list(WEIGHT_CHOICES)}, got {which!r}")
+    ema = ckpt.get("ema_state_dict") if isinstance(ckpt, dict) else None
+    if which == "ema" and ema is None:
+        raise KeyError(f"checkpoint {path if path is not None else '<dict>'} has no ema_state_dict (it was trained without "
+                       f"--ema_decay): use --weights raw or auto")
+    if ema is not None and which in ("auto", "ema"):
+        return ema, "ema"
+    return (ckpt["state_dict"] if "state_dict" in ckpt else ckpt), "raw"
+
+
+def load_checkpoint_model(model, checkpoint_path: str, weights: str, **ctor):
+    """A new model of `model`'s class holding the chosen weights of the checkpoint -> (model, chosen): what
+    load_from_checkpoint(checkpoint_path, **ctor) builds -- cls(**ctor), then load_state_dict -- with the file read once and
+    checkpoint_weights choosing the dict.  The served model keeps no EMA of its own: ema_decay / ema_warmup are training
+    arguments, and the callers keep them out of ctor."""
+    ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
+    sd, chosen = checkpoint_weights(ckpt, weights, checkpoint_path)
+    model = type(model)(**ctor)
+    model.load_state_dict(sd)
+    return model, chosen
 
 
 def prediction_dir(cfg: dict, experiment_dir: str, checkpoint_path: str, eval_dataset_name: str) -> str:
@@ -164,18 +197,22 @@ def conf_matrix_image(pred: np.ndarray, target: np.ndarray) -> np.ndarray:
 
 # ---------------------------------------------------------------------------------------------------------- predict
 def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_images=False, eval_region=None,
-            eval_dataset_split="test", n_workers=0, *, data_root, batch_size=None, device="cuda:0", tta=None) -> dict:
+            eval_dataset_split="test", n_workers=0, *, data_root, batch_size=None, device="cuda:0", tta=None,
+            weights="auto") -> dict:
     """predict.py:129-400 with batched crops.  Returns {"pred_dir", "metrics", "image_stats_f1", "image_stats_iou",
     "region_stats_f1", "region_stats_iou", "probabilities"} (probabilities: {region/image: [H, W, k] float32} of the
     stitched canvases when predict_images, else {}).  tta: None, a tta.VIEW_SETS name or a list of view codes; with it,
     every crop's prediction (metrics and canvases) is the mean softmax over its views.  T views run batch_size * T
-    samples per forward: lower batch_size when that does not fit."""
+    samples per forward: lower batch_size when that does not fit.  weights: 'auto', 'raw' or 'ema' (checkpoint_weights);
+    metrics.json records the choice under "weights" when the EMA was served or weights is not 'auto'."""
     from .datasets import FloodplanetTiles, TileLoader, generate_image_slice_object
     from .datasets.synthetic import write_strip_tiff
     from .models import build_model
     from .stitch import GpuImageStitcher
 
     cfg = _merge(CONFIG_DEFAULTS, cfg)
+    if weights not in WEIGHT_CHOICES:
+        raise ValueError(f"weights must be one of {list(WEIGHT_CHOICES)}, got {weights!r}")
     if eval_dataset_name != "floodplanet":
         raise NotImplementedError(f'prediction supports the "floodplanet" dataset only, not "{eval_dataset_name}"')
     slice_params = generate_image_slice_object(cfg["crop_height"], cfg["crop_width"], cfg["crop_stride"])
@@ -192,12 +229,13 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
                                **(ds_cfg.get("dataset_kwargs") or {}))
 
     dev = torch.device(device)
-    model_kwargs = dict(cfg["model"].get("model_kwargs") or {})
+    model_kwargs = {k: v for k, v in (cfg["model"].get("model_kwargs") or {}).items()
+                    if k not in ("ema_decay", "ema_warmup")}
     model = build_model(cfg["model"]["name"], dataset.n_channels, dataset.n_classes, cfg["lr"],
                         log_image_iter=cfg["log_image_iter"], to_rgb_fcn=None, ignore_index=dataset.ignore_index,
                         **model_kwargs)
-    model = model.load_from_checkpoint(checkpoint_path, in_channels=dataset.n_channels, n_classes=dataset.n_classes,
-                                       lr=cfg["lr"], **model_kwargs)
+    model, chosen = load_checkpoint_model(model, checkpoint_path, weights, in_channels=dataset.n_channels,
+                                          n_classes=dataset.n_classes, lr=cfg["lr"], **model_kwargs)
     model._set_model_to_eval()
     model = model.to(dev)
     net = model.model
@@ -265,6 +303,8 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
 
         all_metrics = {k: v.item() for k, v in metrics.compute().items()}
         all_metrics["eval_dataset"] = eval_dataset_name
+        if chosen == "ema" or weights != "auto":      # (a plain checkpoint under 'auto' writes the file it always wrote)
+            all_metrics["weights"] = chosen
         if codes is not None:
             all_metrics["tta"] = tta if isinstance(tta, str) else list(codes)
         with open(os.path.join(pred_dir, "metrics.json"), "w") as fh:
@@ -292,6 +332,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips (hflip, flips) or all eight "
                          "flips / 90-degree rotations (d4, square crops only); default: none")
+    ap.add_argument("--weights", type=str, default="auto", choices=list(WEIGHT_CHOICES),
+                    help="which weights of the checkpoint to serve: its state_dict (raw), its weight EMA (ema; an error when "
+                         "the checkpoint has none) or the EMA when there is one (auto, the default)")
     ap.add_argument("--norm_params", type=str, default=None,
                     help="parameter file of norm_mode 'global' (config key norm_params; "
                          "python -m floodplanet_code_amd.datasets.stats writes it)")
@@ -308,7 +351,8 @@ def main(argv: Optional[List[str]] = None) -> None:
         cfg["norm_params"] = args.norm_params
     out = predict(cfg, experiment_dir, args.checkpoint_path, eval_dataset_name=name, predict_images=args.predict_images,
                   eval_region=args.eval_region, eval_dataset_split=args.eval_dataset_split, n_workers=n_workers,
-                  data_root=args.data_root, batch_size=args.batch_size, device=args.device, tta=args.tta)
+                  data_root=args.data_root, batch_size=args.batch_size, device=args.device, tta=args.tta,
+                  weights=args.weights)
     print(json.dumps({"pred_dir": out["pred_dir"], **out["metrics"]}))
 
 

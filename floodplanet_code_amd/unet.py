@@ -10,6 +10,7 @@ and BN running statistics), which is what the C side binds to and what data-para
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from typing import Dict, List, Optional, Tuple
@@ -20,6 +21,7 @@ from torch.nn import init
 
 from . import _lib
 from ._lib import FuConfig, check, ptr
+from .ema import check_decay, ema_weight
 
 
 # --------------------------------------------------------------------------------------------------
@@ -139,6 +141,12 @@ class HipUNet(nn.Module):
         # (fu_bind_adam_state), so they survive context re-creation (another tile size, a larger batch, .to(device))
         self._flat_m: Optional[torch.Tensor] = None
         self._flat_v: Optional[torch.Tensor] = None
+        # weight EMA (enable_ema): (decay, warmup) and three more flat caller-owned buffers -- the average of the parameters
+        # and of the BatchNorm running statistics -- bound beside the moments (fu_bind_ema_state)
+        self._ema: Optional[Tuple[float, bool]] = None
+        self._ema_p = self._ema_rm = self._ema_rv = None
+        self._ema_pending: Optional[dict] = None      # load_ema_state_dict before the module reached its device
+        self._ema_swapped = False                     # inside ema_weights(): the context reads the EMA buffers
         self._generation = 0          # counts training forwards: an autograd node may only backward the latest one
         self._flat_valid = False
         self._ctx = None
@@ -197,8 +205,16 @@ class HipUNet(nn.Module):
             else:
                 self._flat_m = torch.zeros(self._total, dtype=torch.float32, device=device)
                 self._flat_v = torch.zeros(self._total, dtype=torch.float32, device=device)
+            if self._ema is not None:
+                if self._ema_p is not None and self._ema_p.numel() == self._total:
+                    self._ema_p, self._ema_rm, self._ema_rv = (t.to(device) for t in (self._ema_p, self._ema_rm, self._ema_rv))
+                else:                                       # the average starts at the live values
+                    self._ema_p, self._ema_rm, self._ema_rv = flat.clone(), rm.clone(), rv.clone()
         self._flat_valid = True
         self._destroy_ctx()
+        if self._ema is not None and self._ema_pending is not None:
+            pending, self._ema_pending = self._ema_pending, None
+            self.load_ema_state_dict(pending)
 
     def flat_parameters(self) -> torch.Tensor:
         return self._flat
@@ -218,6 +234,118 @@ class HipUNet(nn.Module):
         if self._flat_m is not None:
             self._flat_m.zero_()
             self._flat_v.zero_()
+
+    # ---------------------------------------------------------------- weight EMA
+    def enable_ema(self, decay: float, warmup: bool = True):
+        """Keep an exponential moving average of the parameters and of the BatchNorm running statistics, updated inside the
+        fused Adam launch (adam_step / HipAdam.step then call fu_adam_ema_step with ema.ema_weight(decay, step, warmup)).
+        The three flat buffers live on the module's device and start as copies of the live values; on a module that has not
+        reached its device yet they are made when it does.  Enabling again keeps the running average and takes the new
+        decay."""
+        self._ema = (check_decay(decay), bool(warmup))
+        if self._flat_valid and self._flat is not None and self._ema_p is None:
+            with torch.no_grad():
+                self._ema_p, self._ema_rm, self._ema_rv = self._flat.clone(), self._flat_rm.clone(), self._flat_rv.clone()
+        if self._ctx is not None:
+            self._bind(self._ctx)
+        return self
+
+    def disable_ema(self):
+        """Drop the average and its buffers; adam_step launches the plain Adam kernel again."""
+        if self._ema_swapped:
+            raise RuntimeError("disable_ema() inside ema_weights()")
+        self._ema = None
+        self._ema_p = self._ema_rm = self._ema_rv = None
+        self._ema_pending = None
+        if self._ctx is not None:
+            self._bind(self._ctx)
+        return self
+
+    @property
+    def ema_enabled(self) -> bool:
+        return self._ema is not None
+
+    @property
+    def ema_serving(self) -> bool:
+        """True inside ema_weights(): eval forwards read the averaged weights."""
+        return self._ema_swapped
+
+    def ema_buffers(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(EMA of the flat parameters, of running_mean, of running_var): the flat fp32 buffers the kernel updates."""
+        if self._ema is None or self._ema_p is None:
+            raise RuntimeError("no EMA buffers: call enable_ema() and move the module to its device first")
+        return self._ema_p, self._ema_rm, self._ema_rv
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The averaged model under exactly the keys and shapes of state_dict(): parameters and running statistics from the
+        EMA buffers, num_batches_tracked from the live model.  Copies."""
+        ep, erm, erv = self.ema_buffers()
+        src = {}
+        for name, p, off, n in self._table:
+            src[name] = ep[off:off + n].view(p.shape)
+        for name, m, off in self._bn:
+            c = m.weight.numel()
+            src[name + ".running_mean"] = erm[off:off + c]
+            src[name + ".running_var"] = erv[off:off + c]
+        return {k: (src[k] if k in src else v).detach().clone() for k, v in self.state_dict().items()}
+
+    def load_ema_state_dict(self, sd: Dict[str, torch.Tensor]):
+        """Fill the EMA buffers from a dict shaped like state_dict() (num_batches_tracked is ignored: it follows the live
+        model).  Needs enable_ema(); before the module has reached its device the values wait until it has."""
+        if self._ema is None:
+            raise RuntimeError("load_ema_state_dict(): call enable_ema() first")
+        want = [k for k in self.state_dict().keys() if not k.endswith("num_batches_tracked")]
+        missing = [k for k in want if k not in sd]
+        if missing:
+            raise KeyError(f"load_ema_state_dict(): missing keys {missing[:4]}{' ...' if len(missing) > 4 else ''}")
+        if not self._flat_valid or self._ema_p is None:
+            self._ema_pending = {k: sd[k].detach().clone() for k in want}
+            return
+        with torch.no_grad():
+            for name, p, off, n in self._table:
+                if tuple(sd[name].shape) != tuple(p.shape):
+                    raise ValueError(f"load_ema_state_dict(): {name} has shape {tuple(sd[name].shape)}, expected {tuple(p.shape)}")
+                self._ema_p[off:off + n].copy_(sd[name].reshape(-1))
+            for name, m, off in self._bn:
+                c = m.weight.numel()
+                self._ema_rm[off:off + c].copy_(sd[name + ".running_mean"])
+                self._ema_rv[off:off + c].copy_(sd[name + ".running_var"])
+        if self._ema_swapped:                 # the context reads these buffers now: the next eval forward, on whichever
+            self._mark_dirty()                # context serves it, calls fu_params_changed first (as after load_state_dict)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Eval forwards inside the block read the EMA parameters and EMA running statistics: the context is re-bound to the
+        EMA buffers (fu_bind_buffers + fu_params_changed) and back on exit -- the live buffers are never written, so they
+        come back bitwise unchanged.  A training forward or an optimiser step inside the block raises."""
+        if self._ema is None:
+            raise RuntimeError("ema_weights(): call enable_ema() first")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() does not nest")
+        self._ema_swapped = True
+        try:
+            if self._ctx is not None:
+                self._bind(self._ctx)
+            yield self
+        finally:
+            self._ema_swapped = False
+            if self._ctx is not None:
+                self._bind(self._ctx)
+
+    def _bind(self, h):
+        """Bind the flat buffers into context h: the live ones, or inside ema_weights() the EMA ones in their place."""
+        lib = _lib.load()
+        if self._ema_swapped:
+            p, rm, rv = self.ema_buffers()
+        else:
+            p, rm, rv = self._flat, self._flat_rm, self._flat_rv
+        check(lib.fu_bind_buffers(h, ptr(p), ptr(self._flat_grad), ptr(rm), ptr(rv), ptr(self._flat_nbt)))
+        check(lib.fu_bind_adam_state(h, ptr(self._flat_m), ptr(self._flat_v)))
+        have = self._ema is not None and self._ema_p is not None
+        check(lib.fu_bind_ema_state(h, ptr(self._ema_p) if have else None, ptr(self._ema_rm) if have else None,
+                                    ptr(self._ema_rv) if have else None))
+        check(lib.fu_params_changed(h))
+        self._eval_dirty = True
 
     def attach_grads(self):
         """Point every parameter's .grad at its slice of the flat gradient buffer."""
@@ -258,10 +386,7 @@ class HipUNet(nn.Module):
         self._ctx = h
         self._ctx_key = key + (B,)
         self._verify_table()
-        check(lib.fu_bind_buffers(h, ptr(self._flat), ptr(self._flat_grad), ptr(self._flat_rm), ptr(self._flat_rv),
-                                  ptr(self._flat_nbt)))
-        check(lib.fu_bind_adam_state(h, ptr(self._flat_m), ptr(self._flat_v)))
-        self._eval_dirty = True
+        self._bind(h)
         self._install_exact_sync(device)
         return h
 
@@ -325,6 +450,9 @@ class HipUNet(nn.Module):
         """x: the input tensor [B, n_channels, H, W], or a list / tuple of tensors [B, C_k, H, W] that the model sees side by
         side along the channel axis (ef_model.py:28-44 concatenates them; here fu_forward_srcs gathers them inside the
         NCHW -> NHWC conversion: no concatenated copy)."""
+        if training and self._ema_swapped:
+            raise RuntimeError("HipUNet: a training forward inside ema_weights(): the block serves eval forwards of the "
+                               "averaged weights only")
         srcs, B, H, W, dev = self._sources(x)
         ctx = self._get_ctx(dev, B, H, W)
         lib = _lib.load()
@@ -521,10 +649,18 @@ class HipUNet(nn.Module):
         return loss
 
     def adam_step(self, lr: float, step: int, betas=(0.9, 0.999), eps: float = 1e-8, grad_scale: float = 1.0):
-        """Native fused Adam on the flat buffers (torch.optim.Adam semantics, water_seg_model.py:200)."""
+        """Native fused Adam on the flat buffers (torch.optim.Adam semantics, water_seg_model.py:200).  With enable_ema() the
+        same launch also moves the weight EMA on (fu_adam_ema_step; update number = step)."""
         dev = self._flat.device
-        check(_lib.load().fu_adam_step(self._ctx, float(lr), float(betas[0]), float(betas[1]), float(eps), int(step),
-                                       float(grad_scale), self._stream(dev)))
+        if self._ema_swapped:
+            raise RuntimeError("HipUNet: an optimiser step inside ema_weights()")
+        if self._ema is not None:
+            w = ema_weight(self._ema[0], int(step), self._ema[1])
+            check(_lib.load().fu_adam_ema_step(self._ctx, float(lr), float(betas[0]), float(betas[1]), float(eps), int(step),
+                                               float(grad_scale), w, self._stream(dev)))
+        else:
+            check(_lib.load().fu_adam_step(self._ctx, float(lr), float(betas[0]), float(betas[1]), float(eps), int(step),
+                                           float(grad_scale), self._stream(dev)))
         self._eval_dirty = True
 
     def fp16_guard_state(self) -> Tuple[int, int]:
@@ -677,7 +813,9 @@ class HipAdam(torch.optim.Adam):
     step() is ONE launch of libfloodunet's fused Adam kernel on the module's flat parameter / gradient / moment
     buffers (fu_adam_step).  param_groups[0] carries lr / betas / eps as torch's Adam does (LR schedulers work);
     state_dict() holds {step, exp_avg, exp_avg_sq} per parameter like torch.optim.Adam's, the moments being views of the
-    module's flat buffers."""
+    module's flat buffers.  When the module keeps a weight EMA (HipUNet.enable_ema) the step is fu_adam_ema_step, and
+    state_dict() carries one more top-level entry "ema" {decay, warmup, params, running_mean, running_var} -- the flat EMA
+    buffers -- so that a reloaded optimiser continues the same average."""
 
     def __init__(self, net: HipUNet, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
         if not isinstance(net, HipUNet):
@@ -717,6 +855,10 @@ class HipAdam(torch.optim.Adam):
         if self._net._flat_m is not None:
             sd["state"] = {i: {"step": torch.tensor(float(self._step)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
                            for i, (_, m, v) in enumerate(self._views())}
+        net = self._net
+        if net._ema is not None and net._ema_p is not None:
+            sd["ema"] = {"decay": net._ema[0], "warmup": net._ema[1], "params": net._ema_p.clone(),
+                         "running_mean": net._ema_rm.clone(), "running_var": net._ema_rv.clone()}
         return sd
 
     def load_state_dict(self, state_dict):
@@ -730,3 +872,14 @@ class HipAdam(torch.optim.Adam):
                 m.copy_(e["exp_avg"])
                 v.copy_(e["exp_avg_sq"])
                 self._step = int(e["step"])
+        ema = state_dict.get("ema")
+        if ema is not None:
+            net = self._net
+            if net._flat_m is None:
+                raise RuntimeError("HipAdam.load_state_dict(): move the module to its device first")
+            if net._ema is None:
+                net.enable_ema(ema["decay"], ema["warmup"])
+            ep, erm, erv = net.ema_buffers()
+            ep.copy_(ema["params"])
+            erm.copy_(ema["running_mean"])
+            erv.copy_(ema["running_var"])

@@ -224,6 +224,23 @@ int fu_fp16_guard_state(fu_ctx* ctx, int64_t* skipped_steps, int32_t* backoff_ex
  * fu_forward + fu_loss_* + fu_backward + fu_adam_step_dev on one stream into a graph and replay it. */
 int fu_adam_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale, float out[7]);
 int fu_adam_step_dev(fu_ctx* ctx, const float* scalars_dev, fu_stream stream);
+/* Weight EMA fused into the Adam step.  The three buffers are CALLER-owned flat fp32 device memory --
+ * [fu_total_param_elems], [fu_total_bn_channels], [fu_total_bn_channels], in the order of the parameter / running buffers --
+ * initialised by the caller (usually to copies of the live values); like the moments they outlive the context.  All NULL
+ * unbinds.  fu_adam_ema_step is fu_adam_step's update (the same float sequence, bit for bit) followed, in the same pass over
+ * the parameters, by ema = lerp(ema, p_new, w) with w = (float)ema_weight, and in the same launch by
+ * ema_running_mean = lerp(ema_running_mean, running_mean, w) and likewise the variance, the running buffers holding what
+ * this step's training forward left in them.  lerp is torch's CPU Tensor.lerp_(end, w) on float32, one fused multiply-add in
+ * either branch: w < 0.5: fma(w, end - self, self); w >= 0.5: fma(w - 1, end - self, end).  Without bound moments or without
+ * bound EMA buffers the call returns FU_ERR_STATE.  FU_F16: a step the guard skips leaves the EMA buffers untouched too. */
+int fu_bind_ema_state(fu_ctx* ctx, float* ema_params, float* ema_running_mean, float* ema_running_var);
+int fu_adam_ema_step(fu_ctx* ctx, double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
+                     double ema_weight, fu_stream stream);
+/* The captured form: out[0..6] are exactly fu_adam_scalars' seven values, out[7] = (float)ema_weight; the lerp branch is
+ * chosen on the device from out[7], so one captured launch serves a warm-up whose weight crosses 0.5. */
+int fu_adam_ema_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
+                        double ema_weight, float out[8]);
+int fu_adam_ema_step_dev(fu_ctx* ctx, const float* scalars_dev, fu_stream stream);
 int fu_zero_grads(fu_ctx* ctx, fu_stream stream);
 
 /* ---- exact data-parallel mode (SyncBN statistics + global N_valid) ----------------
