@@ -633,7 +633,7 @@ int alloc_workspace(fu_ctx* c) {
   A.want(&c->db_part2, max_dbp * sizeof(float));
   A.want(&c->dscratch, reduce_scratch_elems(std::max(max_c, 64)) * sizeof(double));
   A.want(&c->slab, max_slab * sizeof(float));
-  A.want(&c->ce_part, 4 * 1024 * sizeof(float));     // (fu_loss_ce_weighted: four sums per workgroup)
+  A.want(&c->ce_part, LOSS_PART_FLOATS * sizeof(float));
   A.want(&c->ce_wsum, 256);
   A.want(&c->hb_part, head_bwd_partial_elems(f.base_channels, f.n_classes) * sizeof(float));
   A.want(&c->loss_dev, 256);
@@ -1341,10 +1341,10 @@ int fu_loss_ce(fu_ctx* c, const int64_t* target, int ignore_index, float* loss_o
   hipStream_t s = (hipStream_t)stream;
   SyncScope sc(c, c->fwd_training);
   const int64_t npix = (int64_t)c->last_batch * c->cfg.height * c->cfg.width;
-  FU_TRY(launch_ce_loss(c->logits, target, c->cfg.n_classes, ignore_index, npix, c->ce_part,
+  FU_TRY(launch_ce_loss(c->logits, target, c->cfg.n_classes, ignore_index, npix, nullptr, c->ce_part,
                         loss_out ? loss_out : c->loss_dev, c->n_valid, confusion_out, n_valid_out, c->conf_tmp, s));
   if (c->fwd_training) {
-    FU_TRY(launch_ce_grad(c->logits, target, c->cfg.n_classes, ignore_index, npix, c->n_valid, c->dlogits, s));
+    FU_TRY(launch_ce_grad(c->logits, target, c->cfg.n_classes, ignore_index, npix, nullptr, c->n_valid, c->dlogits, s));
     c->have_loss = true;
     c->have_up_scale = false;
   }
@@ -1362,13 +1362,12 @@ int fu_loss_ce_weighted(fu_ctx* c, const int64_t* target, int ignore_index, cons
   SyncScope sc(c, c->fwd_training);
   const int ncls = c->cfg.n_classes;
   const int64_t npix = (int64_t)c->last_batch * c->cfg.height * c->cfg.width;
-  const float c_nll = (float)(1.0 - (double)label_smoothing), c_smooth = (float)((double)label_smoothing / ncls);
-  FU_TRY(launch_ce_weighted_loss(c->logits, target, ncls, ignore_index, npix, class_weight_dev, c_nll, c_smooth, c->ce_part,
-                                 loss_out ? loss_out : c->loss_dev, c->n_valid, c->ce_wsum, confusion_out, n_valid_out,
-                                 weight_sum_out, c->conf_tmp, s));
+  const CeWeighting cw = {class_weight_dev, (float)(1.0 - (double)label_smoothing),
+                          (float)((double)label_smoothing / ncls), c->ce_wsum, weight_sum_out};
+  FU_TRY(launch_ce_loss(c->logits, target, ncls, ignore_index, npix, &cw, c->ce_part, loss_out ? loss_out : c->loss_dev,
+                        c->n_valid, confusion_out, n_valid_out, c->conf_tmp, s));
   if (c->fwd_training) {
-    FU_TRY(launch_ce_weighted_grad(c->logits, target, ncls, ignore_index, npix, class_weight_dev, c_nll, c_smooth,
-                                   c->ce_wsum, c->dlogits, s));
+    FU_TRY(launch_ce_grad(c->logits, target, ncls, ignore_index, npix, &cw, c->n_valid, c->dlogits, s));
     c->have_loss = true;
     c->have_up_scale = false;
   }
@@ -1476,26 +1475,41 @@ int fu_block_param_range(const fu_ctx* c, int block, int64_t* flat_offset, int64
   return FU_OK;
 }
 
-int fu_adam_step(fu_ctx* c, double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
-                 fu_stream stream) {
-  FU_REQUIRE(c && c->P && c->G, "fu_adam_step: parameter / gradient buffers not bound");
-  FU_REQUIRE(step >= 1, "fu_adam_step: step is 1-based");
+namespace {
+// The one optimiser step behind fu_adam_step[_dev] and fu_adam_ema_step[_dev] (ema: the averages go in the same launch):
+// moments bound?, fp16 guard, launch, guard book.  sc: host scalars, or scalars_dev: the same floats on the device.
+int adam_step(fu_ctx* c, const char* who, bool ema, const float* sc, const float* scalars_dev, fu_stream stream) {
   if (!c->adam_m || !c->adam_v) {
-    set_error("fu_adam_step: no moment buffers bound (fu_bind_adam_state)");
+    set_error("%s: no moment buffers bound (fu_bind_adam_state)", who);
+    return FU_ERR_STATE;
+  }
+  if (ema && !c->ema_p) {
+    set_error("%s: no EMA buffers bound (fu_bind_ema_state)", who);
     return FU_ERR_STATE;
   }
   // fp16: an overflowed gradient map leaves inf / NaN in the gradient buffer -- such a step is skipped and the loss scale
-  // backs off (the guard kernels in fu_elementwise.hip); 13 us of the 69 MB gradient read per step, fp16 mode only
+  // backs off (the guard kernels in fu_optim.hip); 13 us of the 69 MB gradient read per step, fp16 mode only
   const int* skip = nullptr;
   if (c->prec == PREC_F16) {
     FU_TRY(launch_grad_finite_check(c->G, c->total_params, c->guard, (hipStream_t)stream));
     skip = c->guard;
   }
-  FU_TRY(launch_adam(c->P, c->G, c->adam_m, c->adam_v, c->total_params, lr, beta1, beta2, eps, step, grad_scale,
+  const AdamEma avg = {c->ema_p, c->ema_rm, c->RM, c->ema_rv, c->RV, c->total_bn};
+  FU_TRY(launch_adam(c->P, c->G, c->adam_m, c->adam_v, c->total_params, ema ? &avg : nullptr, sc, scalars_dev,
                      (hipStream_t)stream, skip));
   if (skip) FU_TRY(launch_guard_book(c->guard, (hipStream_t)stream));
   c->packed_dirty = true;
   return FU_OK;
+}
+}  // namespace
+
+int fu_adam_step(fu_ctx* c, double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
+                 fu_stream stream) {
+  FU_REQUIRE(c && c->P && c->G, "fu_adam_step: parameter / gradient buffers not bound");
+  FU_REQUIRE(step >= 1, "fu_adam_step: step is 1-based");
+  float sc[7];
+  adam_scalars(lr, beta1, beta2, eps, step, grad_scale, sc);
+  return adam_step(c, "fu_adam_step", false, sc, nullptr, stream);
 }
 
 int fu_fp16_guard_state(fu_ctx* c, int64_t* skipped_steps, int32_t* backoff_exponent) {
@@ -1515,44 +1529,8 @@ int fu_adam_scalars(double lr, double beta1, double beta2, double eps, int64_t s
 
 int fu_adam_step_dev(fu_ctx* c, const float* scalars_dev, fu_stream stream) {
   FU_REQUIRE(c && c->P && c->G && scalars_dev, "fu_adam_step_dev: parameter / gradient buffers not bound, or null scalars");
-  if (!c->adam_m || !c->adam_v) {
-    set_error("fu_adam_step_dev: no moment buffers bound (fu_bind_adam_state)");
-    return FU_ERR_STATE;
-  }
-  const int* skip = nullptr;
-  if (c->prec == PREC_F16) {
-    FU_TRY(launch_grad_finite_check(c->G, c->total_params, c->guard, (hipStream_t)stream));
-    skip = c->guard;
-  }
-  FU_TRY(launch_adam_dev(c->P, c->G, c->adam_m, c->adam_v, c->total_params, scalars_dev, (hipStream_t)stream, skip));
-  if (skip) FU_TRY(launch_guard_book(c->guard, (hipStream_t)stream));
-  c->packed_dirty = true;
-  return FU_OK;
+  return adam_step(c, "fu_adam_step_dev", false, nullptr, scalars_dev, stream);
 }
-
-namespace {
-// the shared tail of fu_adam_ema_step[_dev]: fp16 guard, one launch over the parameters and the BatchNorm channels
-int adam_ema_launch(fu_ctx* c, const char* who, const float sc[8], const float* scalars_dev, fu_stream stream) {
-  if (!c->adam_m || !c->adam_v) {
-    set_error("%s: no moment buffers bound (fu_bind_adam_state)", who);
-    return FU_ERR_STATE;
-  }
-  if (!c->ema_p) {
-    set_error("%s: no EMA buffers bound (fu_bind_ema_state)", who);
-    return FU_ERR_STATE;
-  }
-  const int* skip = nullptr;
-  if (c->prec == PREC_F16) {
-    FU_TRY(launch_grad_finite_check(c->G, c->total_params, c->guard, (hipStream_t)stream));
-    skip = c->guard;
-  }
-  FU_TRY(launch_adam_ema(c->P, c->G, c->adam_m, c->adam_v, c->ema_p, c->total_params, c->ema_rm, c->RM, c->ema_rv, c->RV,
-                         c->total_bn, sc, scalars_dev, (hipStream_t)stream, skip));
-  if (skip) FU_TRY(launch_guard_book(c->guard, (hipStream_t)stream));
-  c->packed_dirty = true;
-  return FU_OK;
-}
-}  // namespace
 
 int fu_adam_ema_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
                         double ema_weight, float out[8]) {
@@ -1568,13 +1546,13 @@ int fu_adam_ema_step(fu_ctx* c, double lr, double beta1, double beta2, double ep
   FU_REQUIRE(c && c->P && c->G && c->RM && c->RV, "fu_adam_ema_step: buffers not bound (fu_bind_buffers)");
   float sc[8];
   FU_TRY(fu_adam_ema_scalars(lr, beta1, beta2, eps, step, grad_scale, ema_weight, sc));
-  return adam_ema_launch(c, "fu_adam_ema_step", sc, nullptr, stream);
+  return adam_step(c, "fu_adam_ema_step", true, sc, nullptr, stream);
 }
 
 int fu_adam_ema_step_dev(fu_ctx* c, const float* scalars_dev, fu_stream stream) {
   FU_REQUIRE(c && c->P && c->G && c->RM && c->RV && scalars_dev,
              "fu_adam_ema_step_dev: buffers not bound (fu_bind_buffers), or null scalars");
-  return adam_ema_launch(c, "fu_adam_ema_step_dev", nullptr, scalars_dev, stream);
+  return adam_step(c, "fu_adam_ema_step_dev", true, nullptr, scalars_dev, stream);
 }
 
 int fu_adam_state(fu_ctx* c, float** exp_avg, float** exp_avg_sq) {

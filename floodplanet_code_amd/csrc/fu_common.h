@@ -450,24 +450,28 @@ int launch_center_from_w3(const float* dw3, int64_t n, float* dw, hipStream_t s)
 int launch_head_fwd(Prec p, const void* y, const float* a, const float* b, const float* w, const float* bias, int C,
                     int ncls, int B, int H, int W, float* logits_nhwc, float* logits_nchw, hipStream_t s);
 static constexpr int HEAD_MAX_CLS = 8;
-// CE loss over stored logits.  partials: [nblk][2] (loss sum, valid count as float) -> finalize
+// the partial buffer of the loss launches (fu_ctx::ce_part), one row of sums per block: the block caps of the loss
+// kernels are derived from, or asserted against, this one size
+static constexpr int LOSS_PART_FLOATS = 4 * 1024;
+// fu_loss_ce_weighted's extras.  class_weight: fp32 [ncls] on the device or null (all ones); c_nll = 1 - eps,
+// c_smooth = eps / ncls; weight_sum_dev receives D = sum w[t] (fp32), which launch_ce_grad divides by.
+struct CeWeighting {
+  const float* class_weight;
+  float c_nll, c_smooth;
+  float* weight_sum_dev;
+  float* weight_sum_out;   // optional
+};
+// CE loss over stored logits, plain (cw == null) or class-weighted and label-smoothed.  partials (LOSS_PART_FLOATS):
+// [nblk][2] (loss sum, valid count as float), weighted [nblk][4] (sum w[t] nll, sum smoothing term, sum w[t], valid
+// count) -> finalize
 int launch_ce_loss(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
-                   float* partials, float* loss_out, int64_t* n_valid_dev, int64_t* confusion_accum,
-                   int64_t* n_valid_out, unsigned long long* conf_tmp /* [64], zero-initialised */, hipStream_t s);
-// dlogits (NHWC fp32) from CE: (softmax - onehot)/n_valid on valid pixels
+                   const CeWeighting* cw, float* partials, float* loss_out, int64_t* n_valid_dev,
+                   int64_t* confusion_accum, int64_t* n_valid_out, unsigned long long* conf_tmp /* [64], zero-initialised */,
+                   hipStream_t s);
+// dlogits (NHWC fp32) from CE: (softmax - onehot)/n_valid on valid pixels; weighted: the gradient of the loss above
 int launch_ce_grad(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
-                   const int64_t* n_valid_dev, float* dlogits_nhwc, hipStream_t s);
-// Class-weighted, label-smoothed CE (fu_loss_ce_weighted).  class_weight: fp32 [ncls] on the device or null (all ones).
-// partials: [nblk][4] (sum w[t] nll, sum smoothing term, sum w[t], valid count) -> finalize; weight_sum_dev receives
-// D = sum w[t] (fp32), which launch_ce_weighted_grad divides by.  c_nll = 1 - eps, c_smooth = eps / ncls.
-int launch_ce_weighted_loss(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
-                            const float* class_weight, float c_nll, float c_smooth, float* partials /* [4 * 1024] */,
-                            float* loss_out, int64_t* n_valid_dev, float* weight_sum_dev, int64_t* confusion_accum,
-                            int64_t* n_valid_out, float* weight_sum_out, unsigned long long* conf_tmp, hipStream_t s);
-int launch_ce_weighted_grad(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
-                            const float* class_weight, float c_nll, float c_smooth, const float* weight_sum_dev,
-                            float* dlogits_nhwc, hipStream_t s);
-// BCE + soft Dice on softmax(z)[1]; partials >= 5*400 floats, coef 4 floats; dlogits may be null (eval)
+                   const CeWeighting* cw, const int64_t* n_valid_dev, float* dlogits_nhwc, hipStream_t s);
+// BCE + soft Dice on softmax(z)[1]; partials: LOSS_PART_FLOATS floats, coef 4 floats; dlogits may be null (eval)
 int launch_bce_dice(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
                     float dice_w, float* partials, float* coef, float* loss_out, int64_t* n_valid_dev,
                     float* dlogits_nhwc, hipStream_t s);
@@ -526,15 +530,18 @@ int launch_resize_lanczos4_tiles(const float* win, int B, int C, int win_h, int 
                                  const int* ix, const float* wx, int TH, int TW, int scale_mode, float* out, hipStream_t s);
 int launch_augment(const float* img, const int64_t* tgt, float* img_o, int64_t* tgt_o, const int* flags,
                    const float* angle, int B, int C, int H, int W, int64_t target_fill, hipStream_t s);
-int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
-                double eps, int64_t step, double grad_scale, hipStream_t s, const int* skip = nullptr);
 void adam_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale, float out[7]);
-int launch_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* scalars_dev, hipStream_t s,
-                    const int* skip = nullptr);
-// Adam + weight EMA in one launch (parameters, then the BatchNorm running statistics): sc = the eight host scalars, or
-// scalars_dev != null = the same eight read on the device (the captured form)
-int launch_adam_ema(float* p, const float* g, float* m, float* v, float* e, int64_t n, float* erm, const float* rm,
-                    float* erv, const float* rv, int64_t nbn, const float sc[8], const float* scalars_dev, hipStream_t s,
-                    const int* skip = nullptr);
+// the weight EMA of launch_adam: the averages of the parameters and of the BatchNorm running statistics (nbn channels)
+struct AdamEma {
+  float* p;
+  float* rm_ema; const float* rm;
+  float* rv_ema; const float* rv;
+  int64_t nbn;
+};
+// Adam in one launch; ema != null: the weight EMA (parameters, then the running statistics) in the same launch.
+// sc = the host scalars (adam_scalars' seven; with ema the EMA weight as the eighth), or scalars_dev != null = the same
+// floats read on the device (the captured form)
+int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, const AdamEma* ema, const float* sc,
+                const float* scalars_dev, hipStream_t s, const int* skip = nullptr);
 
 }  // namespace fu

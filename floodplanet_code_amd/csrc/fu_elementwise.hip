@@ -1,7 +1,7 @@
 // Memory-bound kernels of the UNet training path (gfx950): layout conversion, BatchNorm statistics
-// finalisation and backward, max-pool, bilinear x2 resize, the transposed-conv helpers, 1x1 head + losses, Adam and
-// the fp16 guard; also the error-message storage.  (Data preparation lives in fu_data.hip, stitching and metrics in
-// fu_eval.hip.)
+// finalisation and backward, max-pool, bilinear x2 resize, the transposed-conv helpers, the 1x1 head; also the
+// error-message storage.  (Losses live in fu_loss.hip, Adam and the fp16 guard in fu_optim.hip, data preparation in
+// fu_data.hip, stitching and metrics in fu_eval.hip.)
 // All of them are HBM-bound: 16-byte vector accesses along the NHWC channel dimension, fp32 math,
 // deterministic two-level reductions (per-block partials -> fixed-order finalisation), wave64 shuffles.
 #include "fu_common.h"
@@ -1399,498 +1399,6 @@ int launch_head_fwd(Prec p, const void* y, const float* a, const float* b, const
 }
 
 // ------------------------------------------------------------------------------------------------
-// softmax cross entropy with ignore_index (water_seg_model.py:40,103-107), argmax, confusion counts
-// ------------------------------------------------------------------------------------------------
-static constexpr int CE_BLOCK = 256;
-static constexpr int CE_MAX_BLOCKS = 1024;
-
-__global__ void k_ce_loss(const float* __restrict__ logits, const int64_t* __restrict__ target, int ncls,
-                          int ignore_index, int64_t npix, float* __restrict__ partials,
-                          unsigned long long* __restrict__ conf_tmp) {
-  __shared__ unsigned int hist[HEAD_MAX_CLS * HEAD_MAX_CLS];
-  __shared__ float wsum[CE_BLOCK / 64][2];
-  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x) hist[i] = 0;
-  __syncthreads();
-  float lsum = 0.f, cnt = 0.f;
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t t = target[p];
-    float z[HEAD_MAX_CLS];
-    float m = -INFINITY;
-    int am = 0;
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k) {
-      if (k < ncls) {
-        z[k] = logits[p * ncls + k];
-        if (z[k] > m) { m = z[k]; am = k; }
-      }
-    }
-    if (t != (int64_t)ignore_index && t >= 0 && t < ncls) {
-      float se = 0.f;
-#pragma unroll
-      for (int k = 0; k < HEAD_MAX_CLS; ++k)
-        if (k < ncls) se += expf(z[k] - m);
-      const float lse = m + logf(se);
-      lsum += lse - z[(int)t];
-      cnt += 1.f;
-      atomicAdd(&hist[(int)t * ncls + am], 1u);
-    }
-  }
-  lsum = wave_sum(lsum);
-  cnt = wave_sum(cnt);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { wsum[wave][0] = lsum; wsum[wave][1] = cnt; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s0 = 0.f, s1 = 0.f;
-    for (int wv = 0; wv < CE_BLOCK / 64; ++wv) { s0 += wsum[wv][0]; s1 += wsum[wv][1]; }
-    partials[blockIdx.x * 2 + 0] = s0;
-    partials[blockIdx.x * 2 + 1] = s1;
-  }
-  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x)
-    if (hist[i]) atomicAdd(&conf_tmp[i], (unsigned long long)hist[i]);
-}
-
-__global__ __launch_bounds__(256) void k_ce_finalize(const float* __restrict__ partials, int nblk, int ncls,
-                                                     float* __restrict__ loss_out, int64_t* __restrict__ n_valid_dev,
-                                                     unsigned long long* __restrict__ conf_tmp,
-                                                     int64_t* __restrict__ conf_accum,
-                                                     int64_t* __restrict__ n_valid_out) {
-  __shared__ double sm[2][256];
-  double s = 0.0, c = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += 256) { s += (double)partials[i * 2]; c += (double)partials[i * 2 + 1]; }
-  sm[0][threadIdx.x] = s;
-  sm[1][threadIdx.x] = c;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {   // fixed tree: deterministic
-    if ((int)threadIdx.x < w) {
-      sm[0][threadIdx.x] += sm[0][threadIdx.x + w];
-      sm[1][threadIdx.x] += sm[1][threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    s = sm[0][0]; c = sm[1][0];
-    // CrossEntropyLoss mean over non-ignored pixels; 0/0 = NaN -> nan_to_num -> 0  (water_seg_model.py:104-106)
-    const float loss = c > 0.0 ? (float)(s / c) : 0.f;
-    if (loss_out) *loss_out = loss;
-    *n_valid_dev = (int64_t)(c + 0.5);
-    if (n_valid_out) *n_valid_out = (int64_t)(c + 0.5);
-  }
-  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x) {
-    if (conf_accum) conf_accum[i] += (int64_t)conf_tmp[i];
-    conf_tmp[i] = 0ull;
-  }
-}
-
-int launch_ce_loss(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
-                   float* partials, float* loss_out, int64_t* n_valid_dev, int64_t* confusion_accum,
-                   int64_t* n_valid_out, unsigned long long* conf_tmp, hipStream_t s) {
-  const int nblk = grid_for(npix, CE_BLOCK, CE_MAX_BLOCKS);
-  hipLaunchKernelGGL(k_ce_loss, dim3(nblk), dim3(CE_BLOCK), 0, s, logits_nhwc, target, ncls, ignore_index, npix,
-                     partials, conf_tmp);
-  FU_LAUNCH_CHECK();
-  FU_TRY(sync_sum_over_ranks(partials, (int64_t)nblk * 2, false, s));      // exact DP: global loss sum and N_valid
-  hipLaunchKernelGGL(k_ce_finalize, dim3(1), dim3(256), 0, s, partials, nblk, ncls, loss_out, n_valid_dev, conf_tmp,
-                     confusion_accum, n_valid_out);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-__global__ void k_ce_grad(const float* __restrict__ logits, const int64_t* __restrict__ target, int ncls,
-                          int ignore_index, int64_t npix, const int64_t* __restrict__ n_valid,
-                          float* __restrict__ dl) {
-  const int64_t nv = *n_valid;
-  const float inv = nv > 0 ? 1.f / (float)nv : 0.f;
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t t = target[p];
-    const bool valid = (t != (int64_t)ignore_index && t >= 0 && t < ncls) && nv > 0;
-    float z[HEAD_MAX_CLS];
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k)
-      if (k < ncls) { z[k] = logits[p * ncls + k]; m = fmaxf(m, z[k]); }
-    float se = 0.f;
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k)
-      if (k < ncls) { z[k] = expf(z[k] - m); se += z[k]; }
-    const float r = 1.f / se;
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k)
-      if (k < ncls) dl[p * ncls + k] = valid ? (z[k] * r - ((int)t == k ? 1.f : 0.f)) * inv : 0.f;
-  }
-}
-
-int launch_ce_grad(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
-                   const int64_t* n_valid_dev, float* dlogits_nhwc, hipStream_t s) {
-  const int g = grid_for(npix, 256, 4096);
-  hipLaunchKernelGGL(k_ce_grad, dim3(g), dim3(256), 0, s, logits_nhwc, target, ncls, ignore_index, npix, n_valid_dev,
-                     dlogits_nhwc);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Class-weighted, label-smoothed cross entropy (fu_loss_ce_weighted; an extension: the reference has no such loss, the
-// specification is torch.nn.functional.cross_entropy(weight, ignore_index, label_smoothing)).  Over the valid pixels, with
-// p = softmax(z), W = sum_c w[c]:
-//   loss = [c_nll * sum_i w[t] (lse - z[t]) + c_smooth * sum_i sum_c w[c] (lse - z[c])] / D,      D = sum_i w[t_i]
-//   dz_k = [c_nll * w[t] (p_k - [k == t]) + c_smooth * (p_k W - w[k])] / D,      c_nll = 1 - eps, c_smooth = eps / C
-// k_ce_loss / k_ce_grad stay as they are (the default path); these kernels keep their grid, their per-thread order, their
-// lse and softmax expressions and their reduction tree, so that w = 1, eps = 0 reproduces their bits (every extra factor is
-// then an exact 1 or 0).  NC as in k_head_fwd: compile-time class count, 0 = any count up to HEAD_MAX_CLS; the weights are
-// uniform values loaded once per thread.  D == 0 gives loss 0 and a zero gradient (the rule of the all-ignored batch).
-// ------------------------------------------------------------------------------------------------
-template <int NC>
-__global__ __launch_bounds__(CE_BLOCK) void k_ce_weighted_loss(const float* __restrict__ logits,
-                                                               const int64_t* __restrict__ target, int ncls_rt,
-                                                               int ignore_index, int64_t npix,
-                                                               const float* __restrict__ class_weight,
-                                                               float* __restrict__ partials,
-                                                               unsigned long long* __restrict__ conf_tmp) {
-  constexpr int KMAX = NC ? NC : HEAD_MAX_CLS;
-  const int ncls = NC ? NC : ncls_rt;
-  __shared__ unsigned int hist[HEAD_MAX_CLS * HEAD_MAX_CLS];
-  __shared__ float wsum[CE_BLOCK / 64][4];
-  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x) hist[i] = 0;
-  __syncthreads();
-  float w[KMAX];
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) w[k] = (k < ncls) ? (class_weight ? class_weight[k] : 1.f) : 0.f;
-  float lsum = 0.f, ssum = 0.f, dsum = 0.f, cnt = 0.f;
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t t = target[p];
-    float z[KMAX];
-    float m = -INFINITY;
-    int am = 0;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      if (k < ncls) {
-        z[k] = logits[p * ncls + k];
-        if (z[k] > m) { m = z[k]; am = k; }
-      }
-    }
-    if (t != (int64_t)ignore_index && t >= 0 && t < ncls) {
-      float se = 0.f;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < ncls) se += expf(z[k] - m);
-      const float lse = m + logf(se);
-      float zt = 0.f, wt = 0.f, sm = 0.f;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) {
-        if (k < ncls) {
-          if (k == (int)t) { zt = z[k]; wt = w[k]; }
-          sm += w[k] * (lse - z[k]);
-        }
-      }
-      lsum += wt * (lse - zt);
-      ssum += sm;
-      dsum += wt;
-      cnt += 1.f;
-      atomicAdd(&hist[(int)t * ncls + am], 1u);
-    }
-  }
-  lsum = wave_sum(lsum);
-  ssum = wave_sum(ssum);
-  dsum = wave_sum(dsum);
-  cnt = wave_sum(cnt);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { wsum[wave][0] = lsum; wsum[wave][1] = ssum; wsum[wave][2] = dsum; wsum[wave][3] = cnt; }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    float s0 = 0.f;
-    for (int wv = 0; wv < CE_BLOCK / 64; ++wv) s0 += wsum[wv][threadIdx.x];
-    partials[blockIdx.x * 4 + threadIdx.x] = s0;
-  }
-  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x)
-    if (hist[i]) atomicAdd(&conf_tmp[i], (unsigned long long)hist[i]);
-}
-
-// k_ce_finalize's fixed fp64 tree over four sums per block instead of two
-__global__ __launch_bounds__(256) void k_ce_weighted_finalize(const float* __restrict__ partials, int nblk, int ncls,
-                                                              float c_nll, float c_smooth, float* __restrict__ loss_out,
-                                                              int64_t* __restrict__ n_valid_dev,
-                                                              float* __restrict__ weight_sum_dev,
-                                                              unsigned long long* __restrict__ conf_tmp,
-                                                              int64_t* __restrict__ conf_accum,
-                                                              int64_t* __restrict__ n_valid_out,
-                                                              float* __restrict__ weight_sum_out) {
-  __shared__ double sm[4][256];
-  double a[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < nblk; i += 256) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) a[j] += (double)partials[i * 4 + j];
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) sm[j][threadIdx.x] = a[j];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {   // fixed tree: deterministic
-    if ((int)threadIdx.x < w) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sm[j][threadIdx.x] += sm[j][threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const double nll = sm[0][0], smooth = sm[1][0], D = sm[2][0], c = sm[3][0];
-    double num = (double)c_nll * nll;
-    if (c_smooth != 0.f) num += (double)c_smooth * smooth;
-    // mean over the weights of the valid pixels; D == 0: torch's NaN -> 0, the rule of the all-ignored batch
-    const float loss = D > 0.0 ? (float)(num / D) : 0.f;
-    if (loss_out) *loss_out = loss;
-    *weight_sum_dev = (float)D;
-    if (weight_sum_out) *weight_sum_out = (float)D;
-    *n_valid_dev = (int64_t)(c + 0.5);
-    if (n_valid_out) *n_valid_out = (int64_t)(c + 0.5);
-  }
-  for (int i = threadIdx.x; i < ncls * ncls; i += blockDim.x) {
-    if (conf_accum) conf_accum[i] += (int64_t)conf_tmp[i];
-    conf_tmp[i] = 0ull;
-  }
-}
-
-#define FU_NC_SWITCH(ncls, LAUNCH) \
-  switch (ncls) {                  \
-    case 1: LAUNCH(1); break;      \
-    case 2: LAUNCH(2); break;      \
-    case 3: LAUNCH(3); break;      \
-    case 4: LAUNCH(4); break;      \
-    default: LAUNCH(0); break;     \
-  }
-
-int launch_ce_weighted_loss(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
-                            const float* class_weight, float c_nll, float c_smooth, float* partials, float* loss_out,
-                            int64_t* n_valid_dev, float* weight_sum_dev, int64_t* confusion_accum, int64_t* n_valid_out,
-                            float* weight_sum_out, unsigned long long* conf_tmp, hipStream_t s) {
-  FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "weighted CE: n_classes must be 1..%d", HEAD_MAX_CLS);
-  const int nblk = grid_for(npix, CE_BLOCK, CE_MAX_BLOCKS);
-#define FU_CEW_LOSS(NC)                                                                                                  \
-  hipLaunchKernelGGL((k_ce_weighted_loss<NC>), dim3(nblk), dim3(CE_BLOCK), 0, s, logits_nhwc, target, ncls, ignore_index, \
-                     npix, class_weight, partials, conf_tmp)
-  FU_NC_SWITCH(ncls, FU_CEW_LOSS);
-#undef FU_CEW_LOSS
-  FU_LAUNCH_CHECK();
-  FU_TRY(sync_sum_over_ranks(partials, (int64_t)nblk * 4, false, s));      // exact DP: global sums, D and N_valid
-  hipLaunchKernelGGL(k_ce_weighted_finalize, dim3(1), dim3(256), 0, s, partials, nblk, ncls, c_nll, c_smooth, loss_out,
-                     n_valid_dev, weight_sum_dev, conf_tmp, confusion_accum, n_valid_out, weight_sum_out);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-template <int NC>
-__global__ __launch_bounds__(256) void k_ce_weighted_grad(const float* __restrict__ logits,
-                                                          const int64_t* __restrict__ target, int ncls_rt,
-                                                          int ignore_index, int64_t npix,
-                                                          const float* __restrict__ class_weight, float c_nll,
-                                                          float c_smooth, const float* __restrict__ weight_sum,
-                                                          float* __restrict__ dl) {
-  constexpr int KMAX = NC ? NC : HEAD_MAX_CLS;
-  const int ncls = NC ? NC : ncls_rt;
-  const float D = *weight_sum;
-  const bool live = D > 0.f;
-  const float inv = live ? 1.f / D : 0.f;
-  float w[KMAX];
-  float W = 0.f;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    w[k] = (k < ncls) ? (class_weight ? class_weight[k] : 1.f) : 0.f;
-    W += w[k];
-  }
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t t = target[p];
-    const bool valid = (t != (int64_t)ignore_index && t >= 0 && t < ncls) && live;
-    float z[KMAX];
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < ncls) { z[k] = logits[p * ncls + k]; m = fmaxf(m, z[k]); }
-    float se = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < ncls) { z[k] = expf(z[k] - m); se += z[k]; }
-    const float r = 1.f / se;
-    float wt = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < ncls && (int)t == k) wt = w[k];
-    const float a = c_nll * wt, rW = r * W;   // (p_k W as e_k (r W): p_k - [k == t] keeps k_ce_grad's own expression)
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      if (k < ncls) {
-        const float g = a * (z[k] * r - ((int)t == k ? 1.f : 0.f)) + c_smooth * (z[k] * rW - w[k]);
-        dl[p * ncls + k] = valid ? g * inv : 0.f;
-      }
-    }
-  }
-}
-
-int launch_ce_weighted_grad(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
-                            const float* class_weight, float c_nll, float c_smooth, const float* weight_sum_dev,
-                            float* dlogits_nhwc, hipStream_t s) {
-  FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "weighted CE: n_classes must be 1..%d", HEAD_MAX_CLS);
-  const int g = grid_for(npix, 256, 4096);
-#define FU_CEW_GRAD(NC)                                                                                              \
-  hipLaunchKernelGGL((k_ce_weighted_grad<NC>), dim3(g), dim3(256), 0, s, logits_nhwc, target, ncls, ignore_index, npix, \
-                     class_weight, c_nll, c_smooth, weight_sum_dev, dlogits_nhwc)
-  FU_NC_SWITCH(ncls, FU_CEW_GRAD);
-#undef FU_CEW_GRAD
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-#undef FU_NC_SWITCH
-
-// ------------------------------------------------------------------------------------------------
-// BCE + soft Dice on p = softmax(z)[1] (north-star extension; the reference has no such loss -> parity is pinned
-// only by oracle/unet_oracle.py:bce_dice_loss).  All spatial reductions in fp32 registers + wave shuffles, fp64 finalize.
-//   BCE  = -(1/N) sum_valid [ t log p + (1-t) log(1-p) ],  Dice = 1 - (2 sum p t + 1) / (sum p + sum t + 1)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void bd_pixel(const float* z, int ncls, float& p, float& logp, float& log1mp, float* s,
-                                         float* s1) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) m = fmaxf(m, z[k]);
-  float se = 0.f, se1 = 0.f;
-  float e[HEAD_MAX_CLS];
-#pragma unroll
-  for (int k = 0; k < HEAD_MAX_CLS; ++k) {
-    e[k] = k < ncls ? expf(z[k] - m) : 0.f;
-    se += e[k];
-    if (k != 1) se1 += e[k];
-  }
-  const float inv = 1.f / se, inv1 = se1 > 0.f ? 1.f / se1 : 0.f;
-#pragma unroll
-  for (int k = 0; k < HEAD_MAX_CLS; ++k) { s[k] = e[k] * inv; s1[k] = (k != 1) ? e[k] * inv1 : 0.f; }
-  p = s[1];
-  const float lse = logf(se);
-  logp = (z[1] - m) - lse;
-  log1mp = logf(se1) - lse;
-}
-
-__global__ void k_bd_loss(const float* __restrict__ logits, const int64_t* __restrict__ target, int ncls,
-                          int ignore_index, int64_t npix, float* __restrict__ partials) {
-  __shared__ float wsum[CE_BLOCK / 64][5];
-  float acc[5] = {0, 0, 0, 0, 0};  // bce, p*t, p, t, n
-  for (int64_t px = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; px < npix; px += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t tg = target[px];
-    if (tg != (int64_t)ignore_index && tg >= 0 && tg < ncls) {
-      float z[HEAD_MAX_CLS], s[HEAD_MAX_CLS], s1[HEAD_MAX_CLS];
-#pragma unroll
-      for (int k = 0; k < HEAD_MAX_CLS; ++k) z[k] = k < ncls ? logits[px * ncls + k] : -INFINITY;
-      float p, lp, l1p;
-      bd_pixel(z, ncls, p, lp, l1p, s, s1);
-      const float t = tg == 1 ? 1.f : 0.f;
-      acc[0] -= t > 0.f ? lp : l1p;
-      acc[1] += p * t; acc[2] += p; acc[3] += t; acc[4] += 1.f;
-    }
-  }
-  const int wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    const float v = wave_sum(acc[j]);
-    if ((threadIdx.x & 63) == 0) wsum[wave][j] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    float t = 0.f;
-    for (int wv = 0; wv < CE_BLOCK / 64; ++wv) t += wsum[wv][threadIdx.x];
-    partials[blockIdx.x * 5 + threadIdx.x] = t;
-  }
-}
-
-// coef: [0] = 1/N (0 if N == 0), [1] = D, [2] = 2I+1, [3] = dice weight
-__global__ __launch_bounds__(256) void k_bd_finalize(const float* __restrict__ partials, int nblk, float dice_w,
-                                                     float* __restrict__ loss_out, float* __restrict__ coef,
-                                                     int64_t* __restrict__ n_valid_dev) {
-  __shared__ double sm[5][256];
-  double a[5] = {0, 0, 0, 0, 0};
-  for (int i = threadIdx.x; i < nblk; i += 256)
-#pragma unroll
-    for (int j = 0; j < 5; ++j) a[j] += (double)partials[i * 5 + j];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) sm[j][threadIdx.x] = a[j];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w)
-#pragma unroll
-      for (int j = 0; j < 5; ++j) sm[j][threadIdx.x] += sm[j][threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const double bce = sm[0][0], I = sm[1][0], Sp = sm[2][0], St = sm[3][0], N = sm[4][0];
-    const double D = Sp + St + 1.0, Nn = 2.0 * I + 1.0;
-    const double loss = N > 0.0 ? bce / N + (double)dice_w * (1.0 - Nn / D) : 0.0;
-    if (loss_out) *loss_out = (float)loss;
-    coef[0] = N > 0.0 ? (float)(1.0 / N) : 0.f;
-    coef[1] = (float)D; coef[2] = (float)Nn; coef[3] = N > 0.0 ? dice_w : 0.f;
-    *n_valid_dev = (int64_t)(N + 0.5);
-  }
-}
-
-__global__ void k_bd_grad(const float* __restrict__ logits, const int64_t* __restrict__ target, int ncls,
-                          int ignore_index, int64_t npix, const float* __restrict__ coef, float* __restrict__ dl) {
-  const float invN = coef[0], D = coef[1], Nn = coef[2], w = coef[3];
-  for (int64_t px = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; px < npix; px += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t tg = target[px];
-    const bool valid = tg != (int64_t)ignore_index && tg >= 0 && tg < ncls && invN > 0.f;
-    float z[HEAD_MAX_CLS], s[HEAD_MAX_CLS], s1[HEAD_MAX_CLS];
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k) z[k] = k < ncls ? logits[px * ncls + k] : -INFINITY;
-    float p, lp, l1p;
-    bd_pixel(z, ncls, p, lp, l1p, s, s1);
-    const float t = tg == 1 ? 1.f : 0.f;
-    const float ddice = -(2.f * t * D - Nn) / (D * D);   // d Dice / d p
-#pragma unroll
-    for (int k = 0; k < HEAD_MAX_CLS; ++k) {
-      if (k < ncls) {
-        const float d1 = k == 1 ? 1.f : 0.f;
-        const float gb = (s[k] - t * d1 - (1.f - t) * s1[k]) * invN;
-        const float gd = w * ddice * p * (d1 - s[k]);
-        dl[px * ncls + k] = valid ? gb + gd : 0.f;
-      }
-    }
-  }
-}
-
-int launch_bce_dice(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
-                    float dice_w, float* partials, float* coef, float* loss_out, int64_t* n_valid_dev,
-                    float* dlogits_nhwc, hipStream_t s) {
-  FU_REQUIRE(ncls >= 2, "bce_dice needs n_classes >= 2 (class 1 = flood)");
-  const int nblk = grid_for(npix, CE_BLOCK, 400);   // 5 floats per block must fit the 2*1024-float partial buffer
-  hipLaunchKernelGGL(k_bd_loss, dim3(nblk), dim3(CE_BLOCK), 0, s, logits_nhwc, target, ncls, ignore_index, npix,
-                     partials);
-  FU_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_bd_finalize, dim3(1), dim3(256), 0, s, partials, nblk, dice_w, loss_out, coef, n_valid_dev);
-  FU_LAUNCH_CHECK();
-  if (dlogits_nhwc) {
-    hipLaunchKernelGGL(k_bd_grad, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, s, logits_nhwc, target, ncls,
-                       ignore_index, npix, coef, dlogits_nhwc);
-    FU_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-__global__ void k_dlogits_from_nchw(const float* __restrict__ src, float* __restrict__ dst, int ncls, int HW,
-                                    int64_t total) {
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    const int k = (int)(idx % ncls);
-    const int64_t p = idx / ncls;
-    const int64_t bb = p / HW;
-    const int pp = (int)(p % HW);
-    dst[idx] = src[(bb * ncls + k) * HW + pp];
-  }
-}
-
-int launch_dlogits_from_nchw(const float* dlogits_nchw, float* dlogits_nhwc, int ncls, int B, int H, int W,
-                             hipStream_t s) {
-  const int64_t total = (int64_t)B * H * W * ncls;
-  hipLaunchKernelGGL(k_dlogits_from_nchw, dim3(grid_for(total, 256)), dim3(256), 0, s, dlogits_nchw, dlogits_nhwc, ncls,
-                     H * W, total);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
 // head backward: G[p][c] = sum_k dl[p][k] w[k][c];  dW[k][c] = sum_p dl[p][k] z[p][c];  db[k] = sum_p dl[p][k]
 // ------------------------------------------------------------------------------------------------
 static constexpr int HB_BLOCKS = 2048;
@@ -2080,289 +1588,6 @@ int launch_head_bwd(Prec p, const float* dlogits_nhwc, const void* y, const floa
     if (bnb) *fuse->tiles_out = nblk;
     return 0;
   });
-}
-
-// ------------------------------------------------------------------------------------------------
-// Adam (torch.optim.Adam single-tensor update order; water_seg_model.py:200)
-// ------------------------------------------------------------------------------------------------
-// skip (optional, fp16 mode): device flag set by k_grad_finite_check when a gradient of this step is not finite -- the whole
-// update is then left out (parameters and moments untouched), as a GradScaler skips such a step
-__global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                       float* __restrict__ v, int64_t n, float w1, float beta2, float omb2, float bc2_sqrt,
-                       float eps, float neg_step, float gscale, const int* __restrict__ skip) {
-  // every operation rounds on its own, in ATen's order (no fma contraction): with identical inputs the update is the
-  // same float sequence as torch's CPU Adam (lerp_ / mul_ / addcmul_ / sqrt / div / add_ / addcdiv_)
-#pragma clang fp contract(off)
-  if (skip && *skip) return;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    float mi = m[i], vi = v[i];
-    const float dm = gi - mi;
-    mi = fmaf(w1, dm, mi);                    // exp_avg.lerp_(grad, 1-beta1): the weight < 0.5 branch of ATen's vectorised lerp, fmadd(weight, end - self, self)
-    const float vb = vi * beta2;
-    const float og = omb2 * gi;
-    vi = vb + og * gi;                        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;   // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-    const float num = neg_step * mi;
-    p[i] = p[i] + num / denom;                // param.addcdiv_(exp_avg, denom, value=-step_size): self + value * t1 / t2
-    m[i] = mi;
-    v[i] = vi;
-  }
-}
-
-// the seven float scalars of k_adam: formed in double as torch.optim.Adam forms them in Python, then rounded once to float
-// (the cast ATen applies to a Python scalar operand of a float tensor op)
-void adam_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale, float out[7]) {
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  const double step_size = lr / bc1;
-  const double bc2_sqrt = sqrt(bc2);
-  out[0] = (float)(1.0 - beta1); out[1] = (float)beta2; out[2] = (float)(1.0 - beta2); out[3] = (float)bc2_sqrt;
-  out[4] = (float)eps; out[5] = (float)(-step_size); out[6] = (float)grad_scale;
-}
-
-int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
-                double eps, int64_t step, double grad_scale, hipStream_t s, const int* skip) {
-  float sc[7];
-  adam_scalars(lr, beta1, beta2, eps, step, grad_scale, sc);
-  hipLaunchKernelGGL(k_adam, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, p, g, m, v, n, sc[0], sc[1], sc[2], sc[3],
-                     sc[4], sc[5], sc[6], skip);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// fp16 guard.  The loss scale is chosen once per backward from max|dL/dlogits|; what the chain multiplies on top (a
-// BatchNorm with a tiny variance: gamma * invstd in the hundreds) can still push an fp16 gradient map past 65504.  The inf /
-// NaN then reaches the flat gradient buffer; guard[0] flags it, the Adam launch of that step does nothing, and the next
-// backward's scale is halved once more (guard[2] = back-off exponent, taken back by one every 64 clean steps).
-//   guard[0] non-finite flag of the running step, [1] steps skipped so far, [2] back-off exponent, [3] clean steps since
-__global__ __launch_bounds__(256) void k_grad_finite_check(const float* __restrict__ g, int64_t n, int* __restrict__ guard) {
-  bool bad = false;
-  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 1024) {
-    if (i + 3 < n) {
-      const float4 v = *reinterpret_cast<const float4*>(g + i);
-      bad = bad || !(fabsf(v.x) <= 3.0e38f) || !(fabsf(v.y) <= 3.0e38f) || !(fabsf(v.z) <= 3.0e38f) || !(fabsf(v.w) <= 3.0e38f);
-    } else {
-      for (int64_t k = i; k < n; ++k) bad = bad || !(fabsf(g[k]) <= 3.0e38f);
-    }
-  }
-  if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(guard, 1);
-}
-__global__ void k_guard_book(int* __restrict__ guard) {
-  if (guard[0]) { guard[1] += 1; guard[2] = min(guard[2] + 1, 14); guard[3] = 0; guard[0] = 0; }
-  else if (++guard[3] >= 64) { guard[3] = 0; guard[2] = max(guard[2] - 1, 0); }
-}
-int launch_grad_finite_check(const float* g, int64_t n, int* guard, hipStream_t s) {
-  hipLaunchKernelGGL(k_grad_finite_check, dim3(grid_for(n, 1024 * 4, 2048)), dim3(256), 0, s, g, n, guard);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-int launch_guard_book(int* guard, hipStream_t s) {
-  hipLaunchKernelGGL(k_guard_book, dim3(1), dim3(1), 0, s, guard);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// The same update with its scalars read from DEVICE memory: a captured (hipGraph) step replays this launch unchanged while
-// the step count -- and with it the bias corrections -- moves on; the caller refreshes the seven floats before each replay.
-__global__ void k_adam_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                           float* __restrict__ v, int64_t n, const float* __restrict__ sc, const int* __restrict__ skip) {
-#pragma clang fp contract(off)
-  if (skip && *skip) return;
-  const float w1 = sc[0], beta2 = sc[1], omb2 = sc[2], bc2_sqrt = sc[3], eps = sc[4], neg_step = sc[5], gscale = sc[6];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    float mi = m[i], vi = v[i];
-    const float dm = gi - mi;
-    mi = fmaf(w1, dm, mi);
-    const float vb = vi * beta2;
-    const float og = omb2 * gi;
-    vi = vb + og * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    const float num = neg_step * mi;
-    p[i] = p[i] + num / denom;
-    m[i] = mi;
-    v[i] = vi;
-  }
-}
-int launch_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* scalars_dev, hipStream_t s,
-                    const int* skip) {
-  hipLaunchKernelGGL(k_adam_dev, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, p, g, m, v, n, scalars_dev, skip);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Adam + weight EMA in one pass: the update of k_adam, then ema = lerp(ema, p_new, w) on the value just written -- 9 streams
-// of n floats where k_adam moves 7, in 16-byte accesses.  The lerp is torch's CPU Tensor.lerp_(end, w) on float32, which in
-// ATen is ONE fused multiply-add in either branch (LerpKernel.cpp, vector and scalar loop alike):
-//   w <  0.5:  fma(w,     end - self, self)
-//   w >= 0.5:  fma(w - 1, end - self, end)         (w - 1 rounded to float first)
-// The branch is taken from the float w, on the device in the captured form (w crosses 0.5 during the warm-up).  The same
-// launch averages the BatchNorm running statistics (nbn channels, two arrays) after the parameters.
-// ------------------------------------------------------------------------------------------------
-struct AdamScalars { float w1, beta2, omb2, bc2_sqrt, eps, neg_step, gscale, ema_w; };
-
-__device__ __forceinline__ float ema_lerp(float self, float end, float wl, bool small) {
-  const float d = end - self;
-  return fmaf(wl, d, small ? self : end);
-}
-// k_adam's float sequence on one element (no contraction), then the EMA of the new parameter
-__device__ __forceinline__ void adam_ema_elem(float& p, float g, float& m, float& v, float& e, const AdamScalars& s, float wl,
-                                              bool small) {
-#pragma clang fp contract(off)
-  const float gi = g * s.gscale;
-  float mi = m, vi = v;
-  const float dm = gi - mi;
-  mi = fmaf(s.w1, dm, mi);
-  const float vb = vi * s.beta2;
-  const float og = s.omb2 * gi;
-  vi = vb + og * gi;
-  const float denom = sqrtf(vi) / s.bc2_sqrt + s.eps;
-  const float num = s.neg_step * mi;
-  p = p + num / denom;
-  m = mi;
-  v = vi;
-  e = ema_lerp(e, p, wl, small);
-}
-// head: the elements in front of the first 16-byte boundary (n when the five arrays are not aligned alike: all scalar)
-__device__ __forceinline__ void adam_ema_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                              float* __restrict__ v, float* __restrict__ e, int64_t n, int64_t head,
-                                              const AdamScalars& s, float* __restrict__ erm, const float* __restrict__ rm,
-                                              float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn) {
-#pragma clang fp contract(off)
-  const bool small = fabsf(s.ema_w) < 0.5f;
-  const float wl = small ? s.ema_w : s.ema_w - 1.0f;
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-  const int64_t nvec = (n - head) / 4;
-  for (int64_t j = tid; j < nvec; j += nthr) {
-    const int64_t i = head + 4 * j;
-    float4 p4 = *reinterpret_cast<const float4*>(p + i);
-    const float4 g4 = *reinterpret_cast<const float4*>(g + i);
-    float4 m4 = *reinterpret_cast<const float4*>(m + i);
-    float4 v4 = *reinterpret_cast<const float4*>(v + i);
-    float4 e4 = *reinterpret_cast<const float4*>(e + i);
-    adam_ema_elem(p4.x, g4.x, m4.x, v4.x, e4.x, s, wl, small);
-    adam_ema_elem(p4.y, g4.y, m4.y, v4.y, e4.y, s, wl, small);
-    adam_ema_elem(p4.z, g4.z, m4.z, v4.z, e4.z, s, wl, small);
-    adam_ema_elem(p4.w, g4.w, m4.w, v4.w, e4.w, s, wl, small);
-    *reinterpret_cast<float4*>(p + i) = p4;
-    *reinterpret_cast<float4*>(m + i) = m4;
-    *reinterpret_cast<float4*>(v + i) = v4;
-    *reinterpret_cast<float4*>(e + i) = e4;
-  }
-  const int64_t tail0 = head + 4 * nvec, nrest = head + (n - tail0);      // misaligned head and tail: plain code
-  for (int64_t k = tid; k < nrest; k += nthr) {
-    const int64_t i = k < head ? k : tail0 + (k - head);
-    adam_ema_elem(p[i], g[i], m[i], v[i], e[i], s, wl, small);
-  }
-  for (int64_t i = tid; i < nbn; i += nthr) {
-    erm[i] = ema_lerp(erm[i], rm[i], wl, small);
-    erv[i] = ema_lerp(erv[i], rv[i], wl, small);
-  }
-}
-__global__ __launch_bounds__(256) void k_adam_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, float* __restrict__ e, int64_t n, int64_t head,
-                                                  AdamScalars s, float* __restrict__ erm, const float* __restrict__ rm,
-                                                  float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn,
-                                                  const int* __restrict__ skip) {
-  if (skip && *skip) return;         // fp16 guard: a skipped step leaves the averages untouched too
-  adam_ema_body(p, g, m, v, e, n, head, s, erm, rm, erv, rv, nbn);
-}
-// the scalars (fu_adam_ema_scalars: the seven of k_adam_dev, then the EMA weight) read from device memory
-__global__ __launch_bounds__(256) void k_adam_ema_dev(float* __restrict__ p, const float* __restrict__ g,
-                                                      float* __restrict__ m, float* __restrict__ v, float* __restrict__ e,
-                                                      int64_t n, int64_t head, const float* __restrict__ sc,
-                                                      float* __restrict__ erm, const float* __restrict__ rm,
-                                                      float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn,
-                                                      const int* __restrict__ skip) {
-  if (skip && *skip) return;
-  const AdamScalars s = {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], sc[7]};
-  adam_ema_body(p, g, m, v, e, n, head, s, erm, rm, erv, rv, nbn);
-}
-
-static int64_t adam_ema_head(const float* p, const float* g, const float* m, const float* v, const float* e, int64_t n) {
-  const uintptr_t a = (uintptr_t)p & 15;
-  if (((uintptr_t)g & 15) != a || ((uintptr_t)m & 15) != a || ((uintptr_t)v & 15) != a || ((uintptr_t)e & 15) != a || (a & 3))
-    return n;
-  const int64_t head = (int64_t)(((16 - a) & 15) / 4);
-  return head < n ? head : n;
-}
-int launch_adam_ema(float* p, const float* g, float* m, float* v, float* e, int64_t n, float* erm, const float* rm,
-                    float* erv, const float* rv, int64_t nbn, const float sc[8], const float* scalars_dev, hipStream_t s,
-                    const int* skip) {
-  const int64_t head = adam_ema_head(p, g, m, v, e, n);
-  const dim3 grid(grid_for(ceil_div64(n, 4), 256, 4096));
-  if (scalars_dev) {
-    hipLaunchKernelGGL(k_adam_ema_dev, grid, dim3(256), 0, s, p, g, m, v, e, n, head, scalars_dev, erm, rm, erv, rv, nbn,
-                       skip);
-  } else {
-    const AdamScalars as = {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], sc[7]};
-    hipLaunchKernelGGL(k_adam_ema, grid, dim3(256), 0, s, p, g, m, v, e, n, head, as, erm, rm, erv, rv, nbn, skip);
-  }
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The gradient the head backward consumes: eff = dlogits * up * S, written OUT OF PLACE (the stored loss gradient stays as
-// fu_loss_* left it, so a second backward of the same loss -- retain_graph, fu_backward_block(0) twice -- sees the same
-// input; in place, the second call would have found max|dl| already in [32, 64), chosen S = 1 and unscaled by 1).
-//   up: optional device scalar, the upstream gradient autograd hands to loss.backward() (fu_scale_loss_grad);
-//   S:  fp16 mode only (scale != null): 2^k with max|dl * up| * S in [2^5, 2^6) -- three decades of headroom to fp16's
-//       65504 for what the backward chain multiplies on top, while the bulk of the gradient maps stays in fp16's normal
-//       range; chosen from the data on the device (no host read, any loss, any upstream scale).  scale[0] = S,
-//       scale[1] = 1/S (fu_common.h, g_grad_unscale).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_absmax_partial(const float* __restrict__ x, int64_t n, float* __restrict__ partials) {
-  __shared__ float sm[4];
-  float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float v = fabsf(x[i]);
-    m = (v <= 3.0e38f && v > m) ? v : m;        // (non-finite entries do not define the scale)
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-}
-__global__ __launch_bounds__(256) void k_loss_grad_eff(const float* __restrict__ x, float* __restrict__ out, int64_t n,
-                                                       const float* __restrict__ partials, int nPart,
-                                                       const float* __restrict__ up, float* __restrict__ scale,
-                                                       const int* __restrict__ guard) {
-  __shared__ float sm[4];
-  const float upv = up ? *up : 1.f;
-  float f = upv;
-  if (scale) {                                                        // uniform
-    float m = threadIdx.x < nPart ? partials[threadIdx.x] : 0.f;      // nPart <= 256
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3])) * fabsf(upv);
-    int e = 0;
-    if (m > 0.f && m <= 3.0e38f) { (void)frexpf(m, &e); e = 6 - e; }  // m = f * 2^e', f in [0.5, 1)  ->  m * 2^(6 - e') in [32, 64)
-    if (guard) e -= guard[2];                                        // back-off after overflowed steps (k_guard_book)
-    e = min(max(e, -60), 60);
-    const float S = ldexpf(1.f, e);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { scale[0] = S; scale[1] = ldexpf(1.f, -e); }
-    f = upv * S;                                                      // a power of two: no extra rounding
-  }
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = x[i] * f;
-}
-int launch_loss_grad_eff(const float* dlogits, float* out, int64_t n, const float* up_scale_dev, float* partials,
-                         float* scale, hipStream_t s, const int* guard) {
-  int g = 0;
-  if (scale) {
-    g = grid_for(n, 256 * 16, 256);
-    hipLaunchKernelGGL(k_absmax_partial, dim3(g), dim3(256), 0, s, dlogits, n, partials);
-    FU_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(k_loss_grad_eff, dim3(grid_for(n, 256 * 4, 2048)), dim3(256), 0, s, dlogits, out, n, partials, g,
-                     up_scale_dev, scale, guard);
-  FU_LAUNCH_CHECK();
-  return 0;
 }
 
 }  // namespace fu

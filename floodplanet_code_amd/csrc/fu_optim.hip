@@ -1,0 +1,190 @@
+// Optimiser kernels (gfx950): Adam in torch's single-tensor order, optionally with the weight EMA in the same pass, and the
+// fp16 guard around it (non-finite gradient check, skipped-step book-keeping).
+#include "fu_common.h"
+
+#include <math.h>
+
+namespace fu {
+
+// ------------------------------------------------------------------------------------------------
+// Adam (torch.optim.Adam single-tensor update order; water_seg_model.py:200), optionally with the weight EMA in the same
+// pass: ema = lerp(ema, p_new, w) on the value just written -- 9 streams of n floats where the plain step moves 7, in
+// 16-byte accesses.  The lerp is torch's CPU Tensor.lerp_(end, w) on float32, which in ATen is ONE fused multiply-add in
+// either branch (LerpKernel.cpp, vector and scalar loop alike):
+//   w <  0.5:  fma(w,     end - self, self)
+//   w >= 0.5:  fma(w - 1, end - self, end)         (w - 1 rounded to float first)
+// The branch is taken from the float w, on the device in the captured form (w crosses 0.5 during the warm-up).  The EMA
+// launch also averages the BatchNorm running statistics (nbn channels, two arrays) after the parameters.
+// skip (optional, fp16 mode): device flag set by k_grad_finite_check when a gradient of this step is not finite -- the whole
+// update is then left out (parameters, moments and averages untouched), as a GradScaler skips such a step
+// ------------------------------------------------------------------------------------------------
+struct AdamScalars { float w1, beta2, omb2, bc2_sqrt, eps, neg_step, gscale, ema_w; };
+
+// The update of one element; the ONLY place the sequence is written.  Every operation rounds on its own, in ATen's order
+// (no fma contraction): with identical inputs the update is the same float sequence as torch's CPU Adam
+// (lerp_ / mul_ / addcmul_ / sqrt / div / add_ / addcdiv_)
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamScalars& s) {
+#pragma clang fp contract(off)
+  const float gi = g * s.gscale;
+  float mi = m, vi = v;
+  const float dm = gi - mi;
+  mi = fmaf(s.w1, dm, mi);                  // exp_avg.lerp_(grad, 1-beta1): the weight < 0.5 branch of ATen's vectorised lerp, fmadd(weight, end - self, self)
+  const float vb = vi * s.beta2;
+  const float og = s.omb2 * gi;
+  vi = vb + og * gi;                        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
+  const float denom = sqrtf(vi) / s.bc2_sqrt + s.eps;   // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
+  const float num = s.neg_step * mi;
+  p = p + num / denom;                      // param.addcdiv_(exp_avg, denom, value=-step_size): self + value * t1 / t2
+  m = mi;
+  v = vi;
+}
+__device__ __forceinline__ float ema_lerp(float self, float end, float wl, bool small) {
+  const float d = end - self;
+  return fmaf(wl, d, small ? self : end);
+}
+// head: the elements in front of the first 16-byte boundary (n when the arrays are not aligned alike: all scalar).
+// EMA == false: e, the running statistics and s.ema_w are not touched.
+template <bool EMA>
+__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, float* __restrict__ e, int64_t n, int64_t head,
+                                          const AdamScalars& s, float* __restrict__ erm, const float* __restrict__ rm,
+                                          float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn) {
+#pragma clang fp contract(off)
+  const bool small = EMA && fabsf(s.ema_w) < 0.5f;
+  const float wl = !EMA ? 0.f : small ? s.ema_w : s.ema_w - 1.0f;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nvec = (n - head) / 4;
+  for (int64_t j = tid; j < nvec; j += nthr) {
+    const int64_t i = head + 4 * j;
+    float4 p4 = *reinterpret_cast<const float4*>(p + i);
+    const float4 g4 = *reinterpret_cast<const float4*>(g + i);
+    float4 m4 = *reinterpret_cast<const float4*>(m + i);
+    float4 v4 = *reinterpret_cast<const float4*>(v + i);
+    float4 e4;
+    if constexpr (EMA) e4 = *reinterpret_cast<const float4*>(e + i);
+    adam_elem(p4.x, g4.x, m4.x, v4.x, s);
+    adam_elem(p4.y, g4.y, m4.y, v4.y, s);
+    adam_elem(p4.z, g4.z, m4.z, v4.z, s);
+    adam_elem(p4.w, g4.w, m4.w, v4.w, s);
+    *reinterpret_cast<float4*>(p + i) = p4;
+    *reinterpret_cast<float4*>(m + i) = m4;
+    *reinterpret_cast<float4*>(v + i) = v4;
+    if constexpr (EMA) {
+      e4.x = ema_lerp(e4.x, p4.x, wl, small);
+      e4.y = ema_lerp(e4.y, p4.y, wl, small);
+      e4.z = ema_lerp(e4.z, p4.z, wl, small);
+      e4.w = ema_lerp(e4.w, p4.w, wl, small);
+      *reinterpret_cast<float4*>(e + i) = e4;
+    }
+  }
+  const int64_t tail0 = head + 4 * nvec, nrest = head + (n - tail0);      // misaligned head and tail: plain code
+  for (int64_t k = tid; k < nrest; k += nthr) {
+    const int64_t i = k < head ? k : tail0 + (k - head);
+    adam_elem(p[i], g[i], m[i], v[i], s);
+    if constexpr (EMA) e[i] = ema_lerp(e[i], p[i], wl, small);
+  }
+  if constexpr (EMA) {
+    for (int64_t i = tid; i < nbn; i += nthr) {
+      erm[i] = ema_lerp(erm[i], rm[i], wl, small);
+      erv[i] = ema_lerp(erv[i], rv[i], wl, small);
+    }
+  }
+}
+// The scalars by value, or (fu_adam_scalars: seven; fu_adam_ema_scalars: the EMA weight as the eighth) read from DEVICE
+// memory: a captured (hipGraph) step replays that launch unchanged while the step count -- and with it the bias
+// corrections -- moves on; the caller refreshes the floats before each replay.
+template <bool EMA>
+__device__ __forceinline__ AdamScalars adam_scalars_of(const AdamScalars& s) { return s; }
+template <bool EMA>
+__device__ __forceinline__ AdamScalars adam_scalars_of(const float* __restrict__ sc) {
+  return {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], EMA ? sc[7] : 0.f};
+}
+// four entry kernels over the one body (their names are what a captured graph's dump and a kernel trace show)
+#define FU_ADAM_KERNEL(NAME, EMA, SCALARS)                                                                              \
+  __global__ __launch_bounds__(256) void NAME(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, \
+                                              float* __restrict__ v, float* __restrict__ e, int64_t n, int64_t head,    \
+                                              SCALARS sc, float* __restrict__ erm, const float* __restrict__ rm,        \
+                                              float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn,       \
+                                              const int* __restrict__ skip) {                                           \
+    if (skip && *skip) return;                                                                                          \
+    adam_body<EMA>(p, g, m, v, e, n, head, adam_scalars_of<EMA>(sc), erm, rm, erv, rv, nbn);                            \
+  }
+FU_ADAM_KERNEL(k_adam, false, AdamScalars)
+FU_ADAM_KERNEL(k_adam_ema, true, AdamScalars)
+FU_ADAM_KERNEL(k_adam_dev, false, const float* __restrict__)
+FU_ADAM_KERNEL(k_adam_ema_dev, true, const float* __restrict__)
+#undef FU_ADAM_KERNEL
+
+// the seven float scalars of the update: formed in double as torch.optim.Adam forms them in Python, then rounded once to
+// float (the cast ATen applies to a Python scalar operand of a float tensor op)
+void adam_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale, float out[7]) {
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  const double step_size = lr / bc1;
+  const double bc2_sqrt = sqrt(bc2);
+  out[0] = (float)(1.0 - beta1); out[1] = (float)beta2; out[2] = (float)(1.0 - beta2); out[3] = (float)bc2_sqrt;
+  out[4] = (float)eps; out[5] = (float)(-step_size); out[6] = (float)grad_scale;
+}
+
+static int64_t adam_head(const float* p, const float* g, const float* m, const float* v, const float* e, int64_t n) {
+  const uintptr_t a = (uintptr_t)p & 15;
+  if (((uintptr_t)g & 15) != a || ((uintptr_t)m & 15) != a || ((uintptr_t)v & 15) != a || (e && ((uintptr_t)e & 15) != a) ||
+      (a & 3))
+    return n;
+  const int64_t head = (int64_t)(((16 - a) & 15) / 4);
+  return head < n ? head : n;
+}
+int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, const AdamEma* ema, const float* sc,
+                const float* scalars_dev, hipStream_t s, const int* skip) {
+  static const AdamEma none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  const AdamEma& E = ema ? *ema : none;
+  const int64_t head = adam_head(p, g, m, v, E.p, n);
+  const dim3 grid(grid_for(ceil_div64(n, 4), 256, 4096));
+#define FU_ADAM(K, SC)                                                                                            \
+  hipLaunchKernelGGL(K, grid, dim3(256), 0, s, p, g, m, v, E.p, n, head, SC, E.rm_ema, E.rm, E.rv_ema, E.rv, E.nbn, skip)
+  if (scalars_dev) {
+    if (ema) FU_ADAM(k_adam_ema_dev, scalars_dev);
+    else FU_ADAM(k_adam_dev, scalars_dev);
+  } else {
+    const AdamScalars as = {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], ema ? sc[7] : 0.f};
+    if (ema) FU_ADAM(k_adam_ema, as);
+    else FU_ADAM(k_adam, as);
+  }
+#undef FU_ADAM
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// fp16 guard.  The loss scale is chosen once per backward from max|dL/dlogits|; what the chain multiplies on top (a
+// BatchNorm with a tiny variance: gamma * invstd in the hundreds) can still push an fp16 gradient map past 65504.  The inf /
+// NaN then reaches the flat gradient buffer; guard[0] flags it, the Adam launch of that step does nothing, and the next
+// backward's scale is halved once more (guard[2] = back-off exponent, taken back by one every 64 clean steps).
+//   guard[0] non-finite flag of the running step, [1] steps skipped so far, [2] back-off exponent, [3] clean steps since
+__global__ __launch_bounds__(256) void k_grad_finite_check(const float* __restrict__ g, int64_t n, int* __restrict__ guard) {
+  bool bad = false;
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 1024) {
+    if (i + 3 < n) {
+      const float4 v = *reinterpret_cast<const float4*>(g + i);
+      bad = bad || !(fabsf(v.x) <= 3.0e38f) || !(fabsf(v.y) <= 3.0e38f) || !(fabsf(v.z) <= 3.0e38f) || !(fabsf(v.w) <= 3.0e38f);
+    } else {
+      for (int64_t k = i; k < n; ++k) bad = bad || !(fabsf(g[k]) <= 3.0e38f);
+    }
+  }
+  if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(guard, 1);
+}
+__global__ void k_guard_book(int* __restrict__ guard) {
+  if (guard[0]) { guard[1] += 1; guard[2] = min(guard[2] + 1, 14); guard[3] = 0; guard[0] = 0; }
+  else if (++guard[3] >= 64) { guard[3] = 0; guard[2] = max(guard[2] - 1, 0); }
+}
+int launch_grad_finite_check(const float* g, int64_t n, int* guard, hipStream_t s) {
+  hipLaunchKernelGGL(k_grad_finite_check, dim3(grid_for(n, 1024 * 4, 2048)), dim3(256), 0, s, g, n, guard);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+int launch_guard_book(int* guard, hipStream_t s) {
+  hipLaunchKernelGGL(k_guard_book, dim3(1), dim3(1), 0, s, guard);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace fu

@@ -434,6 +434,53 @@ def test_fused_adam_kernel_equals_torch_adam_on_fixture_gradients():
         assert torch.allclose(v[off:off + n].cpu().view(p.shape), opt["v"][k], rtol=1e-6, atol=1e-30), k
 
 
+@pytest.mark.parametrize("shift", [1, 3])
+def test_fused_adam_kernel_equals_torch_adam_at_misaligned_addresses(shift):
+    """fu_adam_step on flat buffers `shift` floats past a 16-byte boundary, with a parameter count that is no multiple of 4:
+    the kernel's scalar head and tail run, the 16-byte body runs between them.  Three steps, gradients across five decades,
+    against the oracle's torch.optim.Adam restatement on the flat vector, at the bounds of the test above."""
+    from floodplanet_code_amd import _lib
+    lib = _lib.load()
+    net = HipUNet(3, 3, base_channels=8).to(DEV).train()
+    dev = torch.device(DEV)
+    ctx, stream = net._get_ctx(dev, 1, 64, 64), net._stream(dev)
+    n, nb = net._total, net._total_bn
+    assert n % 4 != 0
+    gen = torch.Generator(device=DEV).manual_seed(40 + shift)
+
+    def buf(count):
+        t = torch.zeros(count + 8 + shift, dtype=torch.float32, device=DEV)[shift:shift + count]
+        assert t.data_ptr() % 16 == (4 * shift) % 16
+        return t
+
+    p, g, m, v, rm, rv = buf(n), buf(n), buf(n), buf(n), buf(nb), buf(nb)
+    p.copy_(torch.randn(n, device=DEV, generator=gen) * 0.1)
+    nbt = torch.zeros(len(net._bn), dtype=torch.int64, device=DEV)
+    st_o = {"flat": p.cpu()}
+    opt = {"step": 0, "m": {"flat": torch.zeros(n)}, "v": {"flat": torch.zeros(n)}}
+    lr = 1e-3
+    try:
+        _lib.check(lib.fu_bind_buffers(ctx, p.data_ptr(), g.data_ptr(), rm.data_ptr(), rv.data_ptr(), nbt.data_ptr()))
+        _lib.check(lib.fu_bind_adam_state(ctx, m.data_ptr(), v.data_ptr()))
+        for step in (1, 2, 3):
+            g.copy_(torch.randn(n, device=DEV, generator=gen) * 10.0 ** (torch.arange(n, device=DEV) % 5 - 3.0))
+            _lib.check(lib.fu_adam_step(ctx, lr, O.ADAM_BETA1, O.ADAM_BETA2, O.ADAM_EPS, step, 1.0, stream))
+            O.adam_update(st_o, {"flat": g.cpu()}, opt, lr)
+        torch.cuda.synchronize()
+        ref = st_o["flat"]
+        d = (p.cpu() - ref).abs().max().item()
+        assert d <= 1e-7 * max(1.0, ref.abs().max().item()), d
+        # the first moment decade by decade of the gradient scale (element i keeps decade i % 5), so that the absolute floor
+        # of the test above, 1e-6 of the largest |m|, is taken among elements of one magnitude
+        for dec in range(5):
+            mg, mr = m.cpu()[dec::5], opt["m"]["flat"][dec::5]
+            assert torch.allclose(mg, mr, rtol=1e-6, atol=1e-6 * mr.abs().max().item() + 1e-30), dec
+        assert torch.allclose(v.cpu(), opt["v"]["flat"], rtol=1e-6, atol=1e-30)
+        assert opt["step"] == 3 and float(opt["m"]["flat"].abs().max()) > 0.0
+    finally:
+        net._bind(ctx)
+
+
 def test_adam_state_survives_context_recreation():
     """The Adam moments are caller-owned flat buffers (ABI 3): a validation pass at another tile size, a larger batch or
     a second .to(device) re-creates the device context but must not reset the optimiser.  Interrupted run == plain run."""

@@ -1,8 +1,8 @@
 """Cost of the weight EMA on one GPU, at the bench shape (UNet base 64, 8 bands: 17.27 M parameters).
 
 Optimiser launch alone, on the net's own flat buffers with a random gradient, three ways:
-  (a) fu_adam_step                                              7 streams of n floats
-  (b) fu_adam_ema_step                                          9 streams, one launch (running statistics included)
+  (a) fu_adam_step      (k_adam)                                7 streams of n floats
+  (b) fu_adam_ema_step  (k_adam_ema)                            9 streams, one launch (running statistics included)
   (c) fu_adam_step, then ema.lerp_(params, w) in torch, plus the two running-statistics lerp_ calls
                                                                 10 streams, four launches
 Each sample is the device time of --inner back-to-back calls between two events, divided by --inner; a figure is the
@@ -10,7 +10,7 @@ median of --repeats samples after --warmup untimed ones, with min / max beside i
 (b) <= (c) + the spread (max - min) it measured for (a); `b_not_slower_than_c` says whether it held.
 
 Whole training step (forward + CE + backward + optimiser, batch 16 of 256 x 256 tiles, --precision), eager trainer, EMA
-off and on, same way.  With the EMA off the step launches exactly the kernels it launched before the EMA existed.
+off and on, same way.  With the EMA off the step calls fu_adam_step, as it did before the EMA existed.
 
     python tools/ema_bench.py [--precision bf16] [--repeats 30] [--inner 20]
 Prints one JSON line.  Run it on an otherwise idle GPU."""

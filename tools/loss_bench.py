@@ -1,9 +1,10 @@
 """Time per call of the fused cross-entropy entry points on one GPU, training mode (loss + stored logits gradient), at the
 bench's loss shape: 16 tiles of 256 x 256, 3 classes, ignore_index 0.  Device events around every call, median:
 
-  ce            fu_loss_ce            (k_ce_loss + k_ce_finalize + k_ce_grad): the reference's loss, the default path;
-  ce_weighted   fu_loss_ce_weighted   (k_ce_weighted_loss<3> + k_ce_weighted_finalize + k_ce_weighted_grad<3>) with class
-                weights and label smoothing 0.1;
+  ce            fu_loss_ce            (k_ce_loss<3, false> + k_ce_finalize<false> + k_ce_grad<3, false>): the reference's
+                loss, the default path;
+  ce_weighted   fu_loss_ce_weighted   (k_ce_loss<3, true> + k_ce_finalize<true> + k_ce_grad<3, true>) with class weights and
+                label smoothing 0.1;
   label_counts  fu_label_class_counts on 64 whole label rasters of 1024 x 1024 (64 MiB of uint8), one launch.
 
     python tools/loss_bench.py [--launches 200] [--warmup 20] [--parent_ce_us X]
@@ -11,7 +12,7 @@ bench's loss shape: 16 tiles of 256 x 256, 3 classes, ignore_index 0.  Device ev
 
 --parent_ce_us: `ce_us` of this tool's --ce_only run on the parent commit's build, same box; both per-call numbers are then
 stated against it (`ce_vs_parent`, `ce_weighted_vs_parent`).  Nothing is gated on the ratios: the weighted loss is a
-capability, and the default path launches the kernels it always launched.  Prints one JSON line."""
+capability; both are instantiations of one kernel family (fu_loss.hip).  Prints one JSON line."""
 from __future__ import annotations
 
 import argparse

@@ -1,0 +1,121 @@
+"""SHA-256 digests of what the fused loss and optimiser entry points write, with fixed seeds: two builds of the library
+compute the same bits exactly when their lines are equal.  Select the build with FU_LIB_PATH (floodplanet_code_amd/_lib.py),
+as tools/ab_libs.sh does:
+
+    FU_LIB_PATH=tools/dbglibs/parent.so python tools/step_digest.py
+    python tools/step_digest.py
+
+Losses: base-8 net, batch 3 of 48 x 40, training mode, 2 / 3 / 4 / 6 classes, ignore_index 0 / 2 / -100 and an all-ignored
+batch; fu_loss_ce, fu_loss_ce_weighted (weights [2.5, 0, 1.3, ...], eps 0 and 0.1) and, on 3 classes, fu_loss_bce_dice; each
+digest covers the loss, n_valid, the confusion matrix (the weight sum) and the flat gradient after fu_backward.
+Optimiser: the four Adam entry points, three steps each on flat buffers 0, 1 and 3 floats past a 16-byte boundary, with a
+parameter count that is a multiple of 4 and one that is not, gradients across five decades; one fp16 case with an inf in
+the gradient (the skipped step).  Prints one JSON line."""
+import ctypes as C
+import hashlib
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from floodplanet_code_amd import _lib  # noqa: E402
+from floodplanet_code_amd.unet import HipUNet  # noqa: E402
+
+DEV = torch.device("cuda:0")
+ADAM = (1e-3, 0.9, 0.999, 1e-8)
+
+
+def digest(*tensors):
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+def losses(lib, out):
+    for ncls in (2, 3, 4, 6):
+        torch.manual_seed(ncls)
+        net = HipUNet(4, ncls, base_channels=8).to(DEV).train()
+        x = torch.rand(3, 4, 48, 40, device=DEV)
+        tgt = torch.randint(0, ncls, (3, 48, 40), device=DEV)
+        cw = torch.tensor([2.5, 0.0, 1.3, 0.7, 1.9, 0.4][:ncls], device=DEV)
+        s = net._stream(DEV)
+        for name, t, ign in [(f"ign{i}", tgt, i) for i in (0, 2, -100)] + [("all_ignored", torch.zeros_like(tgt), 0)]:
+            kinds = [("ce", None), ("wce_eps0", 0.0), ("wce_eps0.1", 0.1)] + ([("bce_dice", None)] if ncls == 3 else [])
+            for kind, eps in kinds:
+                net._forward_raw(x, True, want_logits=False)
+                loss, nv, wsum = torch.zeros((), device=DEV), torch.zeros((), dtype=torch.int64, device=DEV), torch.zeros((), device=DEV)
+                conf = torch.zeros(ncls * ncls, dtype=torch.int64, device=DEV)
+                if kind == "ce":
+                    _lib.check(lib.fu_loss_ce(net._ctx, t.data_ptr(), ign, loss.data_ptr(), conf.data_ptr(), nv.data_ptr(), s))
+                elif kind == "bce_dice":
+                    _lib.check(lib.fu_loss_bce_dice(net._ctx, t.data_ptr(), ign, 0.7, loss.data_ptr(), s))
+                else:
+                    _lib.check(lib.fu_loss_ce_weighted(net._ctx, t.data_ptr(), ign, cw.data_ptr(), eps, loss.data_ptr(),
+                                                       conf.data_ptr(), nv.data_ptr(), wsum.data_ptr(), s))
+                net._flat_grad.zero_()
+                net._backward_raw(None, DEV)
+                out[f"{kind}/c{ncls}/{name}"] = digest(loss, nv, conf, wsum, net._flat_grad)
+
+
+def optimiser(lib, out):
+    def dev_scalars(fn, *a):
+        host = (C.c_float * 8)()
+        _lib.check(fn(*a, host))
+        return torch.tensor(list(host), device=DEV)
+
+    for cin, ncls, prec in ((3, 3, "fp32"), (4, 4, "fp32"), (4, 3, "fp16")):      # n % 4 = 3, 0, 3
+        net = HipUNet(cin, ncls, base_channels=8, precision=prec).to(DEV).train()
+        ctx, s = net._get_ctx(DEV, 1, 64, 64), net._stream(DEV)
+        n, nb = net._total, net._total_bn
+        assert (n % 4 == 0) == (ncls == 4)
+        nbt = torch.zeros(len(net._bn), dtype=torch.int64, device=DEV)
+        for shift in (0, 1, 3):
+            for entry in ("adam", "adam_dev", "adam_ema", "adam_ema_dev") if prec == "fp32" else ("adam_ema",):
+                g = torch.Generator(device=DEV).manual_seed(7 + cin + shift)
+
+                def buf(count, rand=False):
+                    t = torch.zeros(count + 8 + shift, device=DEV)[shift:shift + count]
+                    assert t.data_ptr() % 16 == (4 * shift) % 16
+                    return t.copy_(torch.randn(count, device=DEV, generator=g) * 0.1) if rand else t
+
+                p, grad, m, v, rm, rv = buf(n, True), buf(n), buf(n), buf(n), buf(nb, True), buf(nb, True)
+                ep, erm, erv = buf(n, True), buf(nb), buf(nb)
+                _lib.check(lib.fu_bind_buffers(ctx, p.data_ptr(), grad.data_ptr(), rm.data_ptr(), rv.data_ptr(), nbt.data_ptr()))
+                _lib.check(lib.fu_bind_adam_state(ctx, m.data_ptr(), v.data_ptr()))
+                _lib.check(lib.fu_bind_ema_state(ctx, ep.data_ptr(), erm.data_ptr(), erv.data_ptr()))
+                for step in (1, 2, 3):
+                    grad.copy_(torch.randn(n, device=DEV, generator=g) * 10.0 ** (torch.arange(n, device=DEV) % 5 - 3.0))
+                    if prec == "fp16" and step == 2:
+                        grad[n // 2] = float("inf")                      # this step is skipped
+                    w = (0.3, 0.5, 0.999)[step - 1]                       # both lerp branches
+                    if entry == "adam":
+                        _lib.check(lib.fu_adam_step(ctx, *ADAM, step, 0.5, s))
+                    elif entry == "adam_dev":
+                        sc = dev_scalars(lib.fu_adam_scalars, *ADAM, step, 0.5)
+                        _lib.check(lib.fu_adam_step_dev(ctx, sc.data_ptr(), s))
+                    elif entry == "adam_ema":
+                        _lib.check(lib.fu_adam_ema_step(ctx, *ADAM, step, 0.5, w, s))
+                    else:
+                        sc = dev_scalars(lib.fu_adam_ema_scalars, *ADAM, step, 0.5, w)
+                        _lib.check(lib.fu_adam_ema_step_dev(ctx, sc.data_ptr(), s))
+                    torch.cuda.synchronize()
+                out[f"{entry}/{prec}/n{n}/shift{shift}"] = digest(p, m, v, ep, erm, erv)
+        _lib.check(lib.fu_bind_ema_state(ctx, None, None, None))
+        net._bind(ctx)
+
+
+def main():
+    lib, out = _lib.load(), {}
+    losses(lib, out)
+    optimiser(lib, out)
+    torch.cuda.synchronize()
+    out["all"] = hashlib.sha256(json.dumps(out, sort_keys=True).encode()).hexdigest()
+    print(json.dumps(out, sort_keys=True))
+
+
+if __name__ == "__main__":
+    main()
