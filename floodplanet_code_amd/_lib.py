@@ -199,6 +199,9 @@ SIGNATURES = {
     "fu_op_bn_bwd": (_i, [_i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "fu_op_maxpool2": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "fu_op_upsample2": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "fu_op_upsample2_bwd": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "fu_op_depth_to_space": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "fu_op_space_to_depth": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

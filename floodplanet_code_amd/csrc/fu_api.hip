@@ -1980,6 +1980,53 @@ int fu_op_upsample2(int precision, const void* src, const float* bn_a, const flo
   return st;
 }
 
+// ---- op-level test hooks of the decoder's resampling kernels: every argument check precedes the first HIP call, so a
+// rejected call answers on a machine without a GPU ---------------------------------------------------------------------------
+namespace {
+int resample_args(const char* who, int precision, Prec* p, const void* a, const void* b, int vec, int B, int H, int W, int C,
+                  int outH, int outW) {
+  FU_TRY(prec_of(precision, p));
+  FU_REQUIRE(a && b, "%s: null argument", who);
+  FU_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "%s: empty shape (B=%d H=%d W=%d C=%d)", who, B, H, W, C);
+  FU_REQUIRE(C % vec == 0, "%s: C=%d is not a multiple of the %d channels of a vector", who, C, vec);
+  FU_REQUIRE(outH >= 2 * H && outW >= 2 * W, "%s: target %dx%d smaller than 2x the source %dx%d", who, outH, outW, H, W);
+  return 0;
+}
+}  // namespace
+
+int fu_op_upsample2_bwd(int precision, const void* g_dst, void* g_src, int B, int H, int W, int C, int outH, int outW,
+                        fu_stream stream) {
+  Prec p;
+  FU_TRY(resample_args("fu_op_upsample2_bwd", precision, &p, g_dst, g_src, 16 / fu_elem_size(precision), B, H, W, C, outH,
+                       outW));
+  fu_ctx tmp;  // only used as an allocation list for the tables
+  UpTables t;
+  int st = build_up_tables(&tmp, H, W, &t);
+  if (st == 0) st = launch_upsample2_bwd(p, g_dst, g_src, B, H, W, C, outH, outW, t, (hipStream_t)stream);
+  const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+  for (void* q : tmp.extra_allocs) (void)hipFree(q);
+  if (st == 0 && e != hipSuccess) { set_error("fu_op_upsample2_bwd: %s", hipGetErrorString(e)); return FU_ERR_HIP; }
+  return st;
+}
+
+int fu_op_depth_to_space(int precision, const void* y4, void* up, int B, int h, int w, int C, int outH, int outW,
+                         fu_stream stream) {
+  Prec p;
+  FU_TRY(resample_args("fu_op_depth_to_space", precision, &p, y4, up, 4, B, h, w, C, outH, outW));
+  FU_TRY(launch_depth_to_space(p, y4, up, B, h, w, C, outH, outW, (hipStream_t)stream));
+  FU_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  return FU_OK;
+}
+
+int fu_op_space_to_depth(int precision, const void* gup, void* g4, int B, int h, int w, int C, int outH, int outW,
+                         fu_stream stream) {
+  Prec p;
+  FU_TRY(resample_args("fu_op_space_to_depth", precision, &p, gup, g4, 4, B, h, w, C, outH, outW));
+  FU_TRY(launch_space_to_depth(p, gup, g4, B, h, w, C, outH, outW, (hipStream_t)stream));
+  FU_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  return FU_OK;
+}
+
 // ---- op-level test hooks for the code that only runs in the benched dispatch (fused BatchNorm-backward sums) ------------
 namespace {
 // [nTiles][C][2] partial rows -> per-channel sums, fp64 accumulation in tile order

@@ -1029,6 +1029,8 @@ int launch_upsample2(Prec p, const void* src, const float* a, const float* b, vo
 
 int launch_upsample2_bwd(Prec p, const void* g_dst, void* g_src, int B, int H, int W, int C, int outH, int outW,
                          const UpTables& t, hipStream_t s) {
+  // a smaller target makes py0 / px0 negative: the gather would read in front of the row / of g_dst
+  FU_REQUIRE(outH >= 2 * H && outW >= 2 * W, "upsample_bwd: target smaller than 2x source");
   const int py0 = (outH - 2 * H) / 2, px0 = (outW - 2 * W) / 2;
   return dispatch_prec(p, [&](auto tag) {
     using T = decltype(tag);
@@ -1155,6 +1157,9 @@ __global__ void k_colsum_partials(const float* __restrict__ partials, int n, int
 
 int launch_depth_to_space(Prec p, const void* y4, void* up, int B, int h, int w, int C, int outH, int outW,
                           hipStream_t s) {
+  // a smaller target makes py0 / px0 negative (an access in front of the padded map); the kernels move 4 channels at a time
+  FU_REQUIRE(outH >= 2 * h && outW >= 2 * w, "depth_to_space: target smaller than 2x source");
+  FU_REQUIRE(C % 4 == 0, "depth_to_space: channels must be a multiple of 4 (C=%d)", C);
   const int py0 = (outH - 2 * h) / 2, px0 = (outW - 2 * w) / 2;
   const int64_t total = (int64_t)B * outH * outW * (C / 4);
   const int g = grid_for(total, 256);
@@ -1168,6 +1173,9 @@ int launch_depth_to_space(Prec p, const void* y4, void* up, int B, int h, int w,
 }
 int launch_space_to_depth(Prec p, const void* gup, void* g4, int B, int h, int w, int C, int outH, int outW,
                           hipStream_t s) {
+  // a smaller target makes py0 / px0 negative (an access in front of the padded map); the kernels move 4 channels at a time
+  FU_REQUIRE(outH >= 2 * h && outW >= 2 * w, "space_to_depth: target smaller than 2x source");
+  FU_REQUIRE(C % 4 == 0, "space_to_depth: channels must be a multiple of 4 (C=%d)", C);
   const int py0 = (outH - 2 * h) / 2, px0 = (outW - 2 * w) / 2;
   const int64_t total = (int64_t)B * h * w * 4 * (C / 4);
   const int g = grid_for(total, 256);

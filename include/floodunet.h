@@ -539,6 +539,20 @@ int fu_op_maxpool2(int precision, const void* src, const float* bn_a, const floa
 /* bilinear x2, align_corners=True, result zero-padded (F.pad) to [outH, outW] */
 int fu_op_upsample2(int precision, const void* src, const float* bn_a, const float* bn_b, void* dst, int B, int H,
                     int W, int C, int outH, int outW, fu_stream stream);
+/* The three operators below are test hooks like the fu_test_* switches (no ABI promise).  Each checks its arguments
+ * (precision, null pointers, C a multiple of the kernel's channel vector, target >= 2x the source) before its first HIP
+ * call and synchronises the stream before it returns.
+ * backward of fu_op_upsample2 without the prologue: g_src [B,H,W,C] = bilinear^T(crop(g_dst [B,outH,outW,C])); the pad
+ * region of g_dst is ignored.  C: a multiple of 4 (fp32) or 8 (16-bit). */
+int fu_op_upsample2_bwd(int precision, const void* g_dst, void* g_src, int B, int H, int W, int C, int outH, int outW,
+                        fu_stream stream);
+/* the two shuffles of ConvTranspose2d(k=2, s=2): up [B,outH,outW,C] = the four phases of y4 [B,h,w,4C] (channel
+ * (2 ky + kx) C + c -> pixel (2y+ky, 2x+kx)) placed at the F.pad offset with zeros around it, and its adjoint
+ * g4 [B,h,w,4C] from gup [B,outH,outW,C], which drops the pad.  Pure copies; C a multiple of 4. */
+int fu_op_depth_to_space(int precision, const void* y4, void* up, int B, int h, int w, int C, int outH, int outW,
+                         fu_stream stream);
+int fu_op_space_to_depth(int precision, const void* gup, void* g4, int B, int h, int w, int C, int outH, int outW,
+                         fu_stream stream);
 
 /* The operators below exist for the code that only runs in the benched 16-bit dispatch (they are test hooks like the
  * fu_test_* switches: no ABI promise).

@@ -1,6 +1,8 @@
 """GPU: single HIP operators (through the C ABI's fu_op_* entry points) against torch-CPU fp32 references of
 the same op as used in unet.py (F.conv2d / batch-norm+relu prologue / max_pool2d / bilinear upsample)."""
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -9,6 +11,9 @@ import torch.nn.functional as F
 
 from floodplanet_code_amd import _lib
 from floodplanet_code_amd._lib import check, ptr
+
+sys.path.insert(0, os.path.dirname(__file__))
+from tools.resample_ref import fwd_bound, upsample_ref, worst_ratio   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -201,9 +206,10 @@ BF_SHAPES = [
 
 
 # the 16-bit kernels exist for two element types (same sources, fu_conv_bf16.h): every test below runs on both.
-# eps = the element type's rounding unit (bf16: 8 significant bits, fp16: 11)
-LOWP = {"bf16": dict(code=_lib.FU_BF16, dt=torch.bfloat16, eps=2.0 ** -8),
-        "fp16": dict(code=_lib.FU_F16, dt=torch.float16, eps=2.0 ** -11)}
+# eps = the element type's rounding unit (bf16: 8 significant bits, fp16: 11); tiny = half the spacing of its subnormals where
+# results land there (fp16 below 2^-14; the elementwise upsample bound)
+LOWP = {"bf16": dict(code=_lib.FU_BF16, dt=torch.bfloat16, eps=2.0 ** -8, tiny=0.0),
+        "fp16": dict(code=_lib.FU_F16, dt=torch.float16, eps=2.0 ** -11, tiny=2.0 ** -25)}
 _cur = dict(LOWP["bf16"])
 
 
@@ -391,6 +397,10 @@ def test_bf16_memory_bound_ops(lowp):
     u = F.interpolate(z, scale_factor=2, mode="bilinear", align_corners=True)
     ref = F.pad(u, [0, 1, 0, 1])
     assert rel_err(nchw_bf(up), ref) < _cur["eps"]
+    # ... and element by element: a single wrong element sits on that norm's threshold.  z above is the kernel's own float32
+    # activation (a multiply and a separate add, as bn_act); bound and reference as in test_gpu_resample_ops.py
+    ref64, mag = upsample_ref(z.numpy(), 41, 45)
+    assert worst_ratio(nchw_bf(up).numpy(), ref64, fwd_bound(ref64, mag, _cur["eps"], _cur["tiny"])) <= 1.0
 
 
 def test_gpu_augmentation_matches_oracle_and_flip_identities():
