@@ -273,6 +273,13 @@ struct BnbFuse {
   int* tiles_out = nullptr;
   bool skip_g = false;                     // head backward only: g itself is not stored (HeadGrad below recomputes it)
 };
+static inline BnbFuse bnb_fuse(const void* y, const float* a, const float* b, const float* mean, const float* invstd,
+                               float* part, int64_t cap, int* tiles_out) {
+  BnbFuse f;
+  f.y = y; f.a = a; f.b = b; f.mean = mean; f.invstd = invstd;
+  f.part = part; f.max_elems = cap; f.tiles_out = tiles_out;
+  return f;
+}
 // The head's data gradient g[p][c] = sum_k dl[p][k] w[k][c] is two or three FMAs per element: when the head backward has
 // left the BatchNorm-backward sums of g behind (BnbFuse), the apply pass of that BatchNorm recomputes g from dl and w
 // instead of reading a stored copy -- one 134 MB write and one 134 MB read less per step at the bench shape.
@@ -354,6 +361,15 @@ int launch_conv3x3_wgrad(Prec p, const ConvIn& in, const void* dy, int Cout, flo
 int64_t conv3x3_pack_elems(Prec p, int cin_pad, int Cout);
 int launch_pack_conv3x3(Prec p, const float* w_oihw, int Cout, int cin_real, int cin_pad, void* wfwd, void* wdgrad,
                         hipStream_t s);
+
+// the tail of every weight-gradient launch (fu_conv.hip): S split-K slabs -> dw (fp32 OIHW) and db, in a fixed order.
+// fp32 path: [tap][ci][co] slabs; 16-bit paths: [tap][ci / 4][co][4] slabs
+int launch_wgrad_reduce(const float* slab, int S, int Cin, int Cout, int cin_real, float* dw, const float* dbp, int ndb,
+                        float* db, hipStream_t s);
+int launch_wgrad_reduce_oihw(const float* slab, int S, int Cin, int Cout, int cin_real, float* dw, const float* dbp,
+                             int ndb, float* db, hipStream_t s);
+// the split-K plan of the fp32 weight-gradient kernel (fu_conv_f32.hip, in its tile sizes)
+void wgrad_split_shared(int Cin, int Cout, int B, int H, int W, int* nPix, int* S, int* perSplit);
 
 // precision-specific implementations (fu_conv_f32.hip / fu_conv_bf16.hip)
 int conv3x3_num_stat_tiles_f32(int B, int H, int W);

@@ -1263,9 +1263,6 @@ static int launch_wgrad_c8(BWgP& P, int target_wgs, const LaunchOpts& o, hipStre
   return 0;
 }
 
-int launch_wgrad_reduce_oihw(const float* slab, int S, int Cin, int Cout, int cin_real, float* dw, const float* dbp,
-                             int ndb, float* db, hipStream_t s);
-
 template <int WMI, int PTH, int TAPS = 9>
 static int launch_wgrad_cfg(BWgP& P, int target_wgs, const LaunchOpts& o, hipStream_t s) {
   using Cfg = WCfg<WMI, PTH>;

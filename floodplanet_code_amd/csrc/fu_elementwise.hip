@@ -1,44 +1,14 @@
 // Memory-bound kernels of the UNet training path (gfx950): layout conversion, BatchNorm statistics
-// finalisation and backward, max-pool, bilinear x2 resize, the transposed-conv helpers, the 1x1 head; also the
-// error-message storage.  (Losses live in fu_loss.hip, Adam and the fp16 guard in fu_optim.hip, data preparation in
+// finalisation and backward, max-pool, bilinear x2 resize, the transposed-conv helpers, the 1x1 head.
+// (Losses live in fu_loss.hip, Adam and the fp16 guard in fu_optim.hip, data preparation in
 // fu_data.hip, stitching and metrics in fu_eval.hip.)
 // All of them are HBM-bound: 16-byte vector accesses along the NHWC channel dimension, fp32 math,
 // deterministic two-level reductions (per-block partials -> fixed-order finalisation), wave64 shuffles.
 #include "fu_common.h"
 
-#include <stdarg.h>
-
 namespace fu {
 
-thread_local const SyncDesc* g_sync = nullptr;
 thread_local const float* g_grad_unscale = nullptr;
-
-int sync_sum_over_ranks(void* payload, int64_t n_elems, bool is_double, hipStream_t s) {
-  const SyncDesc* d = g_sync;
-  if (!d || !d->hook || d->world <= 1) return 0;
-  const size_t bytes = (size_t)n_elems * (is_double ? 8 : 4);
-  FU_REQUIRE((int64_t)bytes <= d->xbytes, "exact sync: exchange buffer too small (%zu > %lld bytes)", bytes,
-             (long long)d->xbytes);
-  FU_HIP_CHECK(hipMemcpyAsync(d->xbuf, payload, bytes, hipMemcpyDeviceToDevice, s));
-  if (d->hook(d->user, n_elems, is_double ? 1 : 0) != 0) {
-    set_error("exact sync: the all-reduce hook failed");
-    return 3;   // FU_ERR_STATE
-  }
-  FU_HIP_CHECK(hipMemcpyAsync(payload, d->xbuf, bytes, hipMemcpyDeviceToDevice, s));
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// error message storage
-// ------------------------------------------------------------------------------------------------
-static thread_local char g_err[1024] = "";
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-const char* get_error() { return g_err; }
 
 // ------------------------------------------------------------------------------------------------
 // NCHW fp32 <-> NHWC T
@@ -926,7 +896,7 @@ __global__ __launch_bounds__(256) void k_upsample2(const T* __restrict__ src, co
   const bool bn = a != nullptr;
   if (bn) load_coef<V>(a, b, cv * V, av, bv);
   // source index and weight as ATen computes them (area_pixel_compute_scale<float>, align_corners=True): the same
-  // float expressions as the host tables of the backward pass (fu_api.hip build_axis), evaluated here so that no
+  // float expressions as the host tables of the backward pass (fu_plan.hip build_axis), evaluated here so that no
   // load depends on a table load
   const float sx = t.scale_x * (float)ux;
   const int x0 = in_x ? (int)sx : 0;

@@ -1,0 +1,267 @@
+// Single operators behind the C ABI (fu_op_*): one launcher each on caller-owned buffers, with temporary packs and
+// partial buffers of their own -- the hooks of the op-level parity tests -- and fu_test_get_buffer, the only entry
+// point here that looks inside a context.
+#include "fu_ctx.h"
+
+#include <vector>
+
+using namespace fu;
+
+extern "C" {
+
+// ---- single operators --------------------------------------------------------------------------------
+int fu_elem_size(int precision) { return precision == FU_F32 ? 4 : 2; }   /* FU_BF16 and FU_F16: 2 */
+
+static int prec_of(int precision, Prec* p) {
+  FU_REQUIRE(precision == FU_F32 || precision == FU_BF16 || precision == FU_F16, "unknown precision %d", precision);
+  *p = precision == FU_F32 ? PREC_F32 : (precision == FU_BF16 ? PREC_BF16 : PREC_F16);
+  return 0;
+}
+
+int fu_op_nchw_to_nhwc(int precision, const float* src, void* dst, int B, int C, int H, int W, int c_pad,
+                       fu_stream stream) {
+  Prec p; FU_TRY(prec_of(precision, &p));
+  return launch_nchw_to_nhwc(p, src, dst, B, C, H, W, c_pad, (hipStream_t)stream);
+}
+int fu_op_nhwc_to_nchw(int precision, const void* src, float* dst, int B, int C, int H, int W, int c_pad,
+                       fu_stream stream) {
+  Prec p; FU_TRY(prec_of(precision, &p));
+  return launch_nhwc_to_nchw(p, src, dst, B, C, H, W, c_pad, (hipStream_t)stream);
+}
+
+namespace {
+struct TmpBuf {
+  void* p = nullptr;
+  ~TmpBuf() { if (p) (void)hipFree(p); }
+  int get(size_t bytes) { FU_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 16)); return 0; }
+};
+__global__ void k_stats_collapse(const float* part, int nTiles, int C, float* sum, float* sq) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double s = 0, q = 0;
+  for (int t = 0; t < nTiles; ++t) { s += part[((int64_t)t * C + c) * 2]; q += part[((int64_t)t * C + c) * 2 + 1]; }
+  sum[c] = (float)s; sq[c] = (float)q;
+}
+}  // namespace
+
+int fu_op_conv3x3_fwd(int precision, const void* src0, int C0, const float* bn_a0, const float* bn_b0,
+                      const void* src1, int C1, const float* w_oihw, const float* bias, void* y, int Cout, int B, int H,
+                      int W, float* stats_sum, float* stats_sqsum, fu_stream stream) {
+  Prec p; FU_TRY(prec_of(precision, &p));
+  hipStream_t s = (hipStream_t)stream;
+  const int Cin = C0 + (src1 ? C1 : 0);
+  TmpBuf wf, st;
+  FU_TRY(wf.get(conv3x3_pack_elems(p, Cin, Cout) * fu_elem_size(precision)));
+  FU_TRY(launch_pack_conv3x3(p, w_oihw, Cout, Cin, Cin, wf.p, nullptr, s));
+  const bool want_stats = stats_sum && stats_sqsum;
+  if (want_stats) FU_TRY(st.get((size_t)conv3x3_num_stat_tiles(p, B, H, W) * Cout * 2 * sizeof(float)));
+  ConvIn in{src0, C0, bn_a0, bn_b0, src1, src1 ? C1 : 0};
+  int nt = 0;
+  FU_TRY(launch_conv3x3(p, in, wf.p, bias, y, Cout, nullptr, 0, want_stats ? (float*)st.p : nullptr, &nt, B, H, W, s));
+  if (want_stats)
+    hipLaunchKernelGGL(k_stats_collapse, dim3(ceil_div(Cout, 64)), dim3(64), 0, s, (const float*)st.p, nt, Cout,
+                       stats_sum, stats_sqsum);
+  FU_HIP_CHECK(hipStreamSynchronize(s));
+  return FU_OK;
+}
+
+int fu_op_conv3x3_dgrad(int precision, const void* dy, int Cout, const float* w_oihw, void* dx0, int C0, void* dx1,
+                        int C1, int B, int H, int W, fu_stream stream) {
+  Prec p; FU_TRY(prec_of(precision, &p));
+  hipStream_t s = (hipStream_t)stream;
+  const int Cin = C0 + (dx1 ? C1 : 0);
+  TmpBuf wd;
+  FU_TRY(wd.get(conv3x3_pack_elems(p, Cin, Cout) * fu_elem_size(precision)));
+  FU_TRY(launch_pack_conv3x3(p, w_oihw, Cout, Cin, Cin, nullptr, wd.p, s));
+  ConvIn in{dy, Cout, nullptr, nullptr, nullptr, 0};
+  FU_TRY(launch_conv3x3(p, in, wd.p, nullptr, dx0, C0, dx1, dx1 ? C1 : 0, nullptr, nullptr, B, H, W, s));
+  FU_HIP_CHECK(hipStreamSynchronize(s));
+  return FU_OK;
+}
+
+int fu_op_conv3x3_wgrad(int precision, const void* src0, int C0, const float* bn_a0, const float* bn_b0,
+                        const void* src1, int C1, const void* dy, int Cout, float* dw_oihw, int B, int H, int W,
+                        fu_stream stream) {
+  Prec p; FU_TRY(prec_of(precision, &p));
+  hipStream_t s = (hipStream_t)stream;
+  const int Cin = C0 + (src1 ? C1 : 0);
+  TmpBuf slab;
+  FU_TRY(slab.get(conv3x3_wgrad_slab_elems(p, Cin, Cout, B, H, W) * sizeof(float)));
+  ConvIn in{src0, C0, bn_a0, bn_b0, src1, src1 ? C1 : 0};
+  FU_TRY(launch_conv3x3_wgrad(p, in, dy, Cout, (float*)slab.p, dw_oihw, Cin, nullptr, 0, nullptr, B, H, W, s));
+  FU_HIP_CHECK(hipStreamSynchronize(s));
+  return FU_OK;
+}
+
+int fu_op_maxpool2(int precision, const void* src, const float* bn_a, const float* bn_b, void* dst, int B, int H,
+                   int W, int C, fu_stream stream) {
+  Prec p; FU_TRY(prec_of(precision, &p));
+  return launch_maxpool2(p, src, bn_a, bn_b, dst, B, H, W, C, (hipStream_t)stream);
+}
+
+int fu_op_upsample2(int precision, const void* src, const float* bn_a, const float* bn_b, void* dst, int B, int H,
+                    int W, int C, int outH, int outW, fu_stream stream) {
+  Prec p; FU_TRY(prec_of(precision, &p));
+  std::vector<void*> tables;
+  UpTables t;
+  int st = build_up_tables(&tables, H, W, &t);
+  if (st == 0) st = launch_upsample2(p, src, bn_a, bn_b, dst, B, H, W, C, outH, outW, t, (hipStream_t)stream);
+  (void)hipStreamSynchronize((hipStream_t)stream);
+  for (void* q : tables) (void)hipFree(q);
+  return st;
+}
+
+// ---- op-level test hooks of the decoder's resampling kernels: every argument check precedes the first HIP call, so a
+// rejected call answers on a machine without a GPU ---------------------------------------------------------------------------
+namespace {
+int resample_args(const char* who, int precision, Prec* p, const void* a, const void* b, int vec, int B, int H, int W, int C,
+                  int outH, int outW) {
+  FU_TRY(prec_of(precision, p));
+  FU_REQUIRE(a && b, "%s: null argument", who);
+  FU_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "%s: empty shape (B=%d H=%d W=%d C=%d)", who, B, H, W, C);
+  FU_REQUIRE(C % vec == 0, "%s: C=%d is not a multiple of the %d channels of a vector", who, C, vec);
+  FU_REQUIRE(outH >= 2 * H && outW >= 2 * W, "%s: target %dx%d smaller than 2x the source %dx%d", who, outH, outW, H, W);
+  return 0;
+}
+}  // namespace
+
+int fu_op_upsample2_bwd(int precision, const void* g_dst, void* g_src, int B, int H, int W, int C, int outH, int outW,
+                        fu_stream stream) {
+  Prec p;
+  FU_TRY(resample_args("fu_op_upsample2_bwd", precision, &p, g_dst, g_src, 16 / fu_elem_size(precision), B, H, W, C, outH,
+                       outW));
+  std::vector<void*> tables;
+  UpTables t;
+  int st = build_up_tables(&tables, H, W, &t);
+  if (st == 0) st = launch_upsample2_bwd(p, g_dst, g_src, B, H, W, C, outH, outW, t, (hipStream_t)stream);
+  const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+  for (void* q : tables) (void)hipFree(q);
+  if (st == 0 && e != hipSuccess) { set_error("fu_op_upsample2_bwd: %s", hipGetErrorString(e)); return FU_ERR_HIP; }
+  return st;
+}
+
+int fu_op_depth_to_space(int precision, const void* y4, void* up, int B, int h, int w, int C, int outH, int outW,
+                         fu_stream stream) {
+  Prec p;
+  FU_TRY(resample_args("fu_op_depth_to_space", precision, &p, y4, up, 4, B, h, w, C, outH, outW));
+  FU_TRY(launch_depth_to_space(p, y4, up, B, h, w, C, outH, outW, (hipStream_t)stream));
+  FU_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  return FU_OK;
+}
+
+int fu_op_space_to_depth(int precision, const void* gup, void* g4, int B, int h, int w, int C, int outH, int outW,
+                         fu_stream stream) {
+  Prec p;
+  FU_TRY(resample_args("fu_op_space_to_depth", precision, &p, gup, g4, 4, B, h, w, C, outH, outW));
+  FU_TRY(launch_space_to_depth(p, gup, g4, B, h, w, C, outH, outW, (hipStream_t)stream));
+  FU_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  return FU_OK;
+}
+
+// ---- op-level test hooks for the code that only runs in the benched dispatch (fused BatchNorm-backward sums) ------------
+namespace {
+// [nTiles][C][2] partial rows -> per-channel sums, fp64 accumulation in tile order
+int collapse_partials(const float* part, int nTiles, int C, float* s1, float* s2, hipStream_t s) {
+  hipLaunchKernelGGL(k_stats_collapse, dim3(ceil_div(C, 64)), dim3(64), 0, s, part, nTiles, C, s1, s2);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_error("collapse launch failed: %s", hipGetErrorString(e)); return FU_ERR_HIP; }
+  return 0;
+}
+}  // namespace
+
+int fu_op_conv3x3_dgrad_bnsums(int precision, const void* dy, int Cout, const float* w_oihw, void* dx, int C0,
+                               const void* y, const float* bn_a, const float* bn_b, const float* mean,
+                               const float* invstd, float* sum_gm, float* sum_gmx, int B, int H, int W,
+                               fu_stream stream) {
+  Prec p; FU_TRY(prec_of(precision, &p));
+  FU_REQUIRE(p != PREC_F32, "fu_op_conv3x3_dgrad_bnsums: 16-bit precisions only (fp32 keeps the separate reduce pass)");
+  FU_REQUIRE(dy && w_oihw && dx && y && bn_a && bn_b && mean && invstd && sum_gm && sum_gmx, "fu_op_conv3x3_dgrad_bnsums: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  TmpBuf wd, part;
+  FU_TRY(wd.get(conv3x3_pack_elems(p, C0, Cout) * fu_elem_size(precision)));
+  FU_TRY(launch_pack_conv3x3(p, w_oihw, Cout, C0, C0, nullptr, wd.p, s));
+  const int64_t cap = (int64_t)B * ceil_div(H, 16) * ceil_div(W, 16) * C0 * 2;
+  FU_TRY(part.get((size_t)cap * sizeof(float)));
+  int tiles = 0;
+  const BnbFuse f = bnb_fuse(y, bn_a, bn_b, mean, invstd, (float*)part.p, cap, &tiles);
+  ConvIn in{dy, Cout, nullptr, nullptr, nullptr, 0};
+  in.opt.bnb = &f;
+  FU_TRY(launch_conv3x3(p, in, wd.p, nullptr, dx, C0, nullptr, 0, nullptr, nullptr, B, H, W, s));
+  if (tiles <= 0) {
+    set_error("fu_op_conv3x3_dgrad_bnsums: the kernel that ran does not emit the sums for this shape / dispatch");
+    return FU_ERR_UNSUPPORTED;
+  }
+  FU_TRY(perturb_bnb((float*)part.p, tiles, C0, s));
+  FU_TRY(collapse_partials((const float*)part.p, tiles, C0, sum_gm, sum_gmx, s));
+  FU_HIP_CHECK(hipStreamSynchronize(s));
+  return FU_OK;
+}
+
+int fu_op_head_bwd(int precision, const float* dlogits_nhwc, const void* y, const float* bn_a, const float* bn_b,
+                   const float* w, int C, int ncls, int64_t npix, void* g, float* dw, float* db, const float* mean,
+                   const float* invstd, float* sum_gm, float* sum_gmx, fu_stream stream) {
+  Prec p; FU_TRY(prec_of(precision, &p));
+  FU_REQUIRE(dlogits_nhwc && y && w && g && dw && db, "fu_op_head_bwd: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  TmpBuf part, bpart;
+  FU_TRY(part.get((size_t)head_bwd_partial_elems(C, ncls) * sizeof(float)));
+  const bool want = mean && invstd && sum_gm && sum_gmx;
+  const int64_t cap = (int64_t)2048 * C * 2;
+  int tiles = 0;
+  BnbFuse f;
+  if (want) {
+    FU_TRY(bpart.get((size_t)cap * sizeof(float)));
+    f = bnb_fuse(y, bn_a, bn_b, mean, invstd, (float*)bpart.p, cap, &tiles);
+  }
+  FU_TRY(launch_head_bwd(p, dlogits_nhwc, y, bn_a, bn_b, w, C, ncls, npix, g, (float*)part.p, dw, db, s,
+                         want ? &f : nullptr));
+  if (want) {
+    if (tiles <= 0) {
+      set_error("fu_op_head_bwd: the head-backward kernel does not emit the sums in this precision");
+      return FU_ERR_UNSUPPORTED;
+    }
+    FU_TRY(perturb_bnb((float*)bpart.p, tiles, C, s));
+    FU_TRY(collapse_partials((const float*)bpart.p, tiles, C, sum_gm, sum_gmx, s));
+  }
+  FU_HIP_CHECK(hipStreamSynchronize(s));
+  return FU_OK;
+}
+
+int fu_op_bn_bwd(int precision, void* g, const void* y, int C, int B, int H, int W, const float* bn_a,
+                 const float* bn_b, const float* mean, const float* invstd, const void* g_pool, float* dgamma,
+                 float* dbeta, fu_stream stream) {
+  Prec p; FU_TRY(prec_of(precision, &p));
+  FU_REQUIRE(g && y && bn_a && bn_b && mean && invstd && dgamma && dbeta, "fu_op_bn_bwd: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t npix = (int64_t)B * H * W;
+  TmpBuf part, coef, dbp, scr;
+  FU_TRY(part.get((size_t)bn_bwd_partial_elems(C, npix) * sizeof(float)));
+  FU_TRY(coef.get((size_t)C * 2 * sizeof(float)));
+  FU_TRY(dbp.get((size_t)bn_bwd_partial_elems(C, npix) * sizeof(float)));
+  FU_TRY(scr.get((size_t)reduce_scratch_elems(std::max(C, 64)) * sizeof(double)));
+  int ndb = 0;
+  FU_TRY(launch_bn_bwd(p, g, y, C, npix, bn_a, bn_b, mean, invstd, nullptr, dgamma, dbeta, (float*)part.p,
+                       (float*)coef.p, (float*)dbp.p, &ndb, (double*)scr.p, s, g_pool, B, H, W, 0));
+  FU_HIP_CHECK(hipStreamSynchronize(s));
+  return FU_OK;
+}
+
+int fu_test_get_buffer(fu_ctx* c, int block, int which, void** ptr, int64_t* elems) {
+  FU_REQUIRE(c && ptr && elems, "fu_test_get_buffer: null argument");
+  FU_REQUIRE(block >= 0 && block < c->nb, "fu_test_get_buffer: block %d outside 0..%d", block, c->nb - 1);
+  const Block& K = c->blk[block];
+  const int B = c->cfg.max_batch;
+  auto act = [&](int level, int C) { return (int64_t)B * c->Hs[level] * c->Ws[level] * C; };
+  switch (which) {
+    case 0: *ptr = K.c[0].y; *elems = act(K.c[0].level, K.c[0].cout); break;
+    case 1: *ptr = K.c[0].gy; *elems = act(K.c[0].level, K.c[0].cout); break;
+    case 2: *ptr = K.c[1].y; *elems = act(K.c[1].level, K.c[1].cout); break;
+    case 3: *ptr = K.c[1].gy; *elems = act(K.c[1].level, K.c[1].cout); break;
+    case 4: *ptr = K.g_pooled; *elems = K.kind == BK_DOWN ? act(K.level, K.c[0].cin_real) : 0; break;
+    case 5: *ptr = K.g_up; *elems = K.kind == BK_UP ? act(K.level, K.c[0].cin_real - c->ch[K.skip]) : 0; break;
+    default: set_error("fu_test_get_buffer: which must be 0..5"); return FU_ERR_INVALID;
+  }
+  return FU_OK;
+}
+
+}  // extern "C"

@@ -46,7 +46,7 @@ def split_count(B, C0, C1, Cout, H, W, bn):
 
 
 def split_lanes(S):
-    """SL of the reduce for S slabs (fu_conv_f32.hip: launch_wgrad_reduce_oihw)"""
+    """SL of the reduce for S slabs (fu_conv.hip: launch_wgrad_reduce_oihw)"""
     return 16 if S >= 64 else 4 if S >= 16 else 1
 
 

@@ -1,7 +1,7 @@
 """fp64 restatement of the decoder's resampling: bilinear x2 with align_corners=True followed by F.pad, and its adjoint.
 
 The interpolation weights are formed in float32 exactly as ATen forms them (area_pixel_compute_scale<float> and
-compute_source_index_and_lambda, the expressions build_axis in fu_api.hip cites); everything after that is float64.  A pure
+compute_source_index_and_lambda, the expressions build_axis in fu_plan.hip cites); everything after that is float64.  A pure
 float64 reference is about 1e-5 away at these sizes: a kernel within that distance of it could still carry a wrong weight.
 tests/test_resample_ref_cpu.py pins this file to torch on the CPU.
 
