@@ -174,6 +174,9 @@ SIGNATURES = {
     "fu_test_head_store_g": (None, [_i]),
     "fu_test_force_full_taps": (None, [_i]),
     "fu_test_perturb_bnb_sums": (None, [_f]),
+    "fu_test_conv_route": (_i, [_i] * 11),
+    "fu_test_conv_route_name": (C.c_char_p, [_i, _i]),
+    "fu_test_wgrad_slab": (_i, [_i] * 8 + [C.POINTER(_i64), C.POINTER(_i64)]),
     "fu_test_get_buffer": (_i, [_p, _i, _i, C.POINTER(_p), C.POINTER(_i64)]),
     "fu_set_side_stream": (_i, [_p, _i]),
     "fu_backward_join": (_i, [_p, _p]),

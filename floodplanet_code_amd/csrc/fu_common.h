@@ -293,6 +293,25 @@ struct LaunchOpts {
   ProfSlot prof;                  // events around the main kernel
   const BnbFuse* bnb = nullptr;   // dgrad launches: request for the destination BatchNorm's backward sums
 };
+#ifdef __HIPCC__
+// The one way a conv / wgrad main kernel is launched: the opt-in to more dynamic LDS once per kernel, the launch's event pair
+// immediately around the kernel, the launch check.  The opt-in is made from 48 KiB on: the fp32 kernels (44 - 48 KiB) never
+// made it, the 16-bit launchers made it for every kernel, the 36 KiB one-tap tile included, which does not need it.
+template <auto Kernel, typename P>
+int launch_conv_kernel(dim3 grid, dim3 block, size_t smem, const LaunchOpts& o, hipStream_t s, const P& p) {
+  static bool attr_set = false;
+  if (!attr_set && smem > 48 * 1024) {
+    FU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)smem));
+    attr_set = true;
+  }
+  if (o.prof.start) (void)hipEventRecord(o.prof.start, s);
+  hipLaunchKernelGGL(Kernel, grid, block, smem, s, p);
+  if (o.prof.stop) (void)hipEventRecord(o.prof.stop, s);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+#endif
 // out = dlogits * (*up_scale_dev or 1) * (S or 1); scale != null (fp16): S chosen from max|dlogits * up| and written to scale[0..1]
 int launch_loss_grad_eff(const float* dlogits, float* out, int64_t n, const float* up_scale_dev,
                          float* partials /* >= 256 floats */, float* scale /* [2] or null */, hipStream_t s,

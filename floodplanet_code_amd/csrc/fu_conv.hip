@@ -2,8 +2,42 @@
 // to fu_conv_f32.hip / fu_conv_bf16.hip (the latter compiled a second time for fp16), and the tail of every
 // weight-gradient launch, which sums the split-K slabs in a fixed order into fp32 OIHW and the bias gradient.
 #include "fu_common.h"
+#include "fu_conv_bf16.h"
+#include "floodunet.h"
 
 namespace fu {
+
+// ---- the 16-bit convs' testing hooks (include/floodunet.h) and the query for what they and the shapes decide -----------
+ConvHooks g_conv_hooks = {0, 0, 0, 0};
+
+// the parameter blocks as launch_conv3x3_bf16 / launch_conv3x3_wgrad_bf16 fill them, with stand-in non-null pointers: a
+// forward launch carries bias and statistics, a dgrad launch neither, and the fused-sums request when want_bnsums
+static int query_route(int kind, int C0, int has_bn0, int C1, int D0, int D1, int center_only, int want_bnsums, int B, int H,
+                       int W, int64_t* slab_elems) {
+  static const float fake[2] = {0.f, 0.f};
+  const bf16_t* const act = reinterpret_cast<const bf16_t*>(fake);
+  const bool one_tap = center_only && !g_conv_hooks.full_taps;
+  if (kind == 2) {
+    BWgP P = {};
+    P.src0 = act; P.src1 = C1 > 0 ? act : nullptr; P.a0 = has_bn0 ? fake : nullptr; P.b0 = P.a0;
+    P.C0 = C0; P.C1 = C1 > 0 ? C1 : 0; P.Cin = P.C0 + P.C1; P.Cout = D0; P.B = B; P.H = H; P.W = W;
+    const WgradRoute r = conv3x3_wgrad_route(P, one_tap, g_conv_hooks);
+    conv3x3_wgrad_plan(P, r);
+    if (slab_elems) *slab_elems = (int64_t)P.S * 9 * P.Cin * P.Cout;
+    return r;
+  }
+  BConvP P = {};
+  P.src0 = act; P.src1 = C1 > 0 ? act : nullptr; P.a0 = has_bn0 ? fake : nullptr; P.b0 = P.a0;
+  P.dst0 = const_cast<bf16_t*>(act); P.dst1 = D1 > 0 ? P.dst0 : nullptr;
+  if (kind == 0) { P.bias = fake; P.stats = const_cast<float*>(fake); }
+  P.C0 = C0; P.C1 = C1 > 0 ? C1 : 0; P.Cin = P.C0 + P.C1; P.N = D0 + D1; P.D0 = D0; P.D1 = D1; P.B = B; P.H = H; P.W = W;
+  P.center_only = one_tap ? 1 : 0;
+  BnbFuse f;
+  f.y = fake;
+  LaunchOpts o;
+  if (want_bnsums) o.bnb = &f;
+  return conv3x3_route(P, o, g_conv_hooks);
+}
 
 // ---- precision dispatch -------------------------------------------------------------------------
 int conv3x3_num_stat_tiles(Prec p, int B, int H, int W) {
@@ -293,3 +327,28 @@ int launch_wgrad_reduce_oihw(const float* slab, int S, int Cin, int Cout, int ci
 }
 
 }  // namespace fu
+
+extern "C" {
+void fu_test_force_general_conv(int on) { fu::g_conv_hooks.force_general = on; }
+void fu_test_force_lockstep_wgrad(int on) { fu::g_conv_hooks.wgrad_lockstep = on; }
+void fu_test_force_full_taps(int on) { fu::g_conv_hooks.full_taps = on; }
+void fu_test_conv_tile_mode(int mode) { fu::g_conv_hooks.tile_mode = mode; }
+
+int fu_test_conv_route(int kind, int C0, int has_bn0, int C1, int D0, int D1, int center_only, int want_bnsums, int B, int H,
+                       int W) {
+  if (kind < 0 || kind > 2) return -1;
+  return fu::query_route(kind, C0, has_bn0, C1, D0, D1, center_only, want_bnsums, B, H, W, nullptr);
+}
+const char* fu_test_conv_route_name(int kind, int route) {
+  static const char* const conv[fu::CONV_NUM_ROUTES] = {"general64", "general32", "tap1_64", "tap1_32", "c8", "pp",
+                                                        "rs8", "rs4", "fast_tall", "fast64", "fast32"};
+  static const char* const wgrad[fu::WGRAD_NUM_ROUTES] = {"tap1_wide", "tap1_narrow", "c8", "pp", "lockstep128", "lockstep64"};
+  if (kind == 2) return route >= 0 && route < fu::WGRAD_NUM_ROUTES ? wgrad[route] : "?";
+  return (kind == 0 || kind == 1) && route >= 0 && route < fu::CONV_NUM_ROUTES ? conv[route] : "?";
+}
+int fu_test_wgrad_slab(int C0, int has_bn0, int C1, int Cout, int center_only, int B, int H, int W, int64_t* used_elems,
+                       int64_t* bound_elems) {
+  if (bound_elems) *bound_elems = fu::conv3x3_wgrad_slab_elems_bf16(C0 + (C1 > 0 ? C1 : 0), Cout, B, H, W);
+  return fu::query_route(2, C0, has_bn0, C1, Cout, 0, center_only, 0, B, H, W, used_elems);
+}
+}

@@ -5,8 +5,8 @@
 // and the transposing reads are identical -- a 16-bit element is a 16-bit element -- so the only things that change are
 // the four conversions (f2e / e2f_lo / e2f_hi / pack_e2), the fragment vector type and the MFMA / ds_read_tr builtins,
 // all defined below.  Device buffers stay raw 16-bit storage (`bf16_t` = unsigned short in both builds); the fp16 build's
-// entry points and kernels carry `f16` in their names (the #defines at the end of the FU_HALF block), the testing hooks
-// and their globals live in the bf16 objects only.
+// entry points and kernels carry `f16` in their names (the #defines below); the testing hooks (ConvHooks) are defined once,
+// in fu_conv.hip.
 #pragma once
 #include "fu_common.h"
 
@@ -34,8 +34,9 @@
 #define launch_conv3x3_c8 launch_conv3x3_c8_f16
 #define conv3x3_pp_eligible conv3x3_pp_eligible_f16
 #define launch_conv3x3_pp launch_conv3x3_pp_f16
-#define conv3x3_pp_preferred conv3x3_pp_preferred_f16
-#define conv3x3_pp_preferred_bnb conv3x3_pp_preferred_bnb_f16
+#define conv3x3_route conv3x3_route_f16
+#define conv3x3_wgrad_route conv3x3_wgrad_route_f16
+#define conv3x3_wgrad_plan conv3x3_wgrad_plan_f16
 #endif
 
 #include <type_traits>
@@ -113,20 +114,81 @@ struct BConvP {
   int nTiles;                // persistent ping-pong kernel (fu_conv_pp.hip): nPix * nCo, walked by gridDim.x workgroups
 };
 
-// aligned-shape fast path (fu_conv_bf16_fast.hip)
-bool conv3x3_bf16_fast_eligible(const BConvP& P);
-int launch_conv3x3_bf16_fast(BConvP& P, const LaunchOpts& o, hipStream_t s);
-// 8-input-channel forward kernel (fu_conv_rs.hip): the network's first conv
-bool conv3x3_c8_eligible(const BConvP& P);
+// weight-gradient launch parameters (see launch_conv3x3_wgrad_bf16)
+struct BWgP {
+  const bf16_t* src0; const bf16_t* src1; const float* a0; const float* b0; const bf16_t* dy;
+  float* slab;
+  int C0, C1, Cin, Cout, B, H, W, tilesX, tilesY, nPix, nCi, nCo, S, perSplit;
+  unsigned rcp_tilesX, rcp_tilesY;   // k_wgrad_bf16_pp<true>: floor(2^32 / d) + 1 (0 for d == 1), as in BConvP
+};
+
+// the pixel-tile / channel-tile counts of a launch and their reciprocals, for a kernel with tw x th-pixel, bn-channel tiles
+// (the aligned-shape kernels get exact quotients)
+static inline void conv_geometry(BConvP& P, int tw, int th, int bn) {
+  P.tilesX = ceil_div(P.W, tw); P.tilesY = ceil_div(P.H, th);
+  P.nPix = P.B * P.tilesX * P.tilesY; P.nCo = ceil_div(P.N, bn); P.nTiles = P.nPix * P.nCo;
+  P.rcp_nPix = host_rcp(P.nPix); P.rcp_tilesX = host_rcp(P.tilesX); P.rcp_tilesY = host_rcp(P.tilesY);
+  P.rcp_nCo = host_rcp(P.nCo);
+}
+// ... of a weight-gradient launch (c_out tiles of 64), and its split-K plan: about target_wgs workgroups, every split owns
+// at least one pixel tile
+static inline void wgrad_geometry(BWgP& P, int tw, int th, int ci_t, int target_wgs) {
+  P.tilesX = ceil_div(P.W, tw); P.tilesY = ceil_div(P.H, th);
+  P.nPix = P.B * P.tilesX * P.tilesY;
+  P.nCi = ceil_div(P.Cin, ci_t); P.nCo = ceil_div(P.Cout, 64);
+  P.rcp_tilesX = host_rcp(P.tilesX); P.rcp_tilesY = host_rcp(P.tilesY);
+  int S = ceil_div(target_wgs, P.nCi * P.nCo);
+  if (S > P.nPix) S = P.nPix;
+  if (S < 1) S = 1;
+  P.perSplit = ceil_div(P.nPix, S);
+  P.S = ceil_div(P.nPix, P.perSplit);
+}
+
+// BatchNorm-backward sums of the destination (BnbFuse, fu_common.h): the launch is asked for them and is of the kind that
+// can give them (a dgrad into one destination, no BatchNorm prologue) ...
+static inline bool wants_bnb(const BConvP& P, const LaunchOpts& o) {
+  return o.bnb != nullptr && o.bnb->y != nullptr && P.a0 == nullptr && P.dst1 == nullptr && P.stats == nullptr;
+}
+// ... and the rs / pp launcher's answer: with room for `tiles` rows of sums the kernel gets the pointers and the caller the count
+static inline bool attach_bnb(BConvP& P, const LaunchOpts& o, int64_t tiles) {
+  if (!wants_bnb(P, o) || o.bnb->tiles_out == nullptr || tiles * P.N * 2 > o.bnb->max_elems) return false;
+  const BnbFuse& f = *o.bnb;
+  P.bnb_y = (const bf16_t*)f.y; P.bnb_a = f.a; P.bnb_b = f.b; P.bnb_mean = f.mean; P.bnb_invstd = f.invstd;
+  P.bnb_part = f.part;
+  *f.tiles_out = (int)tiles;
+  return true;
+}
+
+// The testing hooks (include/floodunet.h, fu_test_*): one process-wide record, defined with its setters in fu_conv.hip.
+struct ConvHooks {
+  int force_general;    // fu_test_force_general_conv: skip the aligned-shape kernels
+  int full_taps;        // fu_test_force_full_taps: embedded 1x1 convs run all nine taps
+  int tile_mode;        // fu_test_conv_tile_mode: 0 = heuristic, 1 = square fast tiles only, 2 = tall fast tile, 3 = rs, 4 = pp
+  int wgrad_lockstep;   // fu_test_force_lockstep_wgrad: 1 = k_wgrad_bf16<4,8> for the ping-pong kernel, 2 = its general staging
+};
+extern ConvHooks g_conv_hooks;
+
+// Which kernel instantiation a forward / dgrad launch runs (conv3x3_route, fu_conv_bf16.hip: every preference and its
+// measurement) and which a weight gradient (conv3x3_wgrad_route).  Pure host functions of the shapes and of which pointers
+// are null; fu_test_conv_route (fu_conv.hip) answers from them without a GPU.
+enum ConvRoute {
+  CONV_GENERAL_64, CONV_GENERAL_32, CONV_TAP1_64, CONV_TAP1_32, CONV_C8, CONV_PP, CONV_RS8, CONV_RS4, CONV_FAST_TALL,
+  CONV_FAST_64, CONV_FAST_32, CONV_NUM_ROUTES
+};
+enum WgradRoute { WGRAD_TAP1_WIDE, WGRAD_TAP1_NARROW, WGRAD_C8, WGRAD_PP, WGRAD_LOCKSTEP_128, WGRAD_LOCKSTEP_64, WGRAD_NUM_ROUTES };
+ConvRoute conv3x3_route(const BConvP& P, const LaunchOpts& o, const ConvHooks& h);
+WgradRoute conv3x3_wgrad_route(const BWgP& P, bool one_tap, const ConvHooks& h);
+void conv3x3_wgrad_plan(BWgP& P, WgradRoute r);   // the route's tile counts and split-K plan (P.S slabs)
+
+// what each kernel can run (beside the kernels)
+bool conv3x3_bf16_fast_eligible(const BConvP& P);   // aligned-shape fast path (fu_conv_bf16_fast.hip)
+bool conv3x3_c8_eligible(const BConvP& P);          // 8-input-channel forward kernel (fu_conv_rs.hip): the network's first conv
+bool conv3x3_rs_eligible(const BConvP& P);          // row-stationary 16x16x32 kernel (fu_conv_rs.hip)
+bool conv3x3_pp_eligible(const BConvP& P);          // persistent ping-pong row-stationary kernel (fu_conv_pp.hip)
+// ... and their launchers
+int launch_conv3x3_bf16_fast(BConvP& P, ConvRoute r, const LaunchOpts& o, hipStream_t s);   // the one-tap and fast routes
 int launch_conv3x3_c8(BConvP& P, const LaunchOpts& o, hipStream_t s);
-// row-stationary 16x16x32 kernel (fu_conv_rs.hip)
-bool conv3x3_rs_eligible(const BConvP& P);
-int launch_conv3x3_rs(BConvP& P, const LaunchOpts& o, hipStream_t s);
-// persistent ping-pong row-stationary kernel (fu_conv_pp.hip): 8 waves, two LDS stages, one workgroup per CU
-bool conv3x3_pp_eligible(const BConvP& P);
-bool conv3x3_pp_preferred(const BConvP& P);   // ... and worth it: at least one tile per CU
-bool conv3x3_pp_preferred_bnb(const BConvP& P);   // ... when the launch is asked for fused BatchNorm-backward sums
+int launch_conv3x3_rs(BConvP& P, bool rows8, const LaunchOpts& o, hipStream_t s);
 int launch_conv3x3_pp(BConvP& P, const LaunchOpts& o, hipStream_t s);
 
 }  // namespace fu
-

@@ -15,10 +15,10 @@
 #include "fu_common.h"
 #include "fu_conv_bf16.h"
 
+#include <algorithm>
 #include <type_traits>
 
 namespace fu {
-
 
 // ------------------------------------------------------------------------------------------------
 // weight packing (bf16): OIHW fp32 -> wf[tap][co][ci_pad] and wd[8-tap][ci_pad][co]
@@ -344,28 +344,64 @@ int conv3x3_num_stat_tiles_bf16(int B, int H, int W) { return B * ceil_div(H, 16
 template <int WM, int WN, int NTW>
 static int launch_cfg(BConvP& P, const LaunchOpts& o, hipStream_t s) {
   using Cfg = BCfg<WM, WN, NTW>;
-  P.tilesX = ceil_div(P.W, Cfg::TW); P.tilesY = ceil_div(P.H, Cfg::TH);
-  P.nPix = P.B * P.tilesX * P.tilesY; P.nCo = ceil_div(P.N, Cfg::BN);
-  static bool attr_set = false;
-  if (!attr_set) {
-    FU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_bf16<WM, WN, NTW>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM_BYTES));
-    attr_set = true;
-  }
-  const ProfSlot ps = o.prof;
-  if (ps.start) (void)hipEventRecord(ps.start, s);
-  hipLaunchKernelGGL((k_conv3x3_bf16<WM, WN, NTW>), dim3(P.nPix * P.nCo), dim3(Cfg::NT), Cfg::SMEM_BYTES, s, P);
-  if (ps.stop) (void)hipEventRecord(ps.stop, s);
-  FU_LAUNCH_CHECK();
-  return 0;
+  conv_geometry(P, Cfg::TW, Cfg::TH, Cfg::BN);
+  return launch_conv_kernel<k_conv3x3_bf16<WM, WN, NTW>>(dim3(P.nPix * P.nCo), dim3(Cfg::NT), Cfg::SMEM_BYTES, o, s, P);
 }
 
-#if FU_HALF      // the hooks live in the bf16 objects; the fp16 kernels obey the same switches
-extern int g_bf16_force_general, g_bf16_force_full_taps, g_wgrad_force_lockstep;
-#else
-int g_bf16_force_general = 0;   // testing hook (fu_test_force_general_conv): skip the aligned-shape fast kernel
-int g_bf16_force_full_taps = 0; // testing hook (fu_test_force_full_taps): embedded 1x1 convs run all nine taps
-#endif
+// ---- the decision: which kernel a forward / dgrad launch runs.  What a kernel CAN run is its *_eligible predicate, beside
+// the kernel; everything that is PREFERRED is here, with the measurement behind it. ----
+// Workgroups that give every CU two: the threshold of the 64-channel tiles and of the row-stationary kernel.
+static constexpr int CONV_TWO_PER_CU_WGS = 512;
+// Tiles of the persistent kernel (one workgroup per CU for the whole launch): at least one per CU.  128 tiles leave half the
+// chip idle -- 512 -> 256 at 32 x 32 measured 54.8 us against 50.5 on the two-workgroup kernel.
+static constexpr int CONV_PP_MIN_TILES = 256;
+// ... of a dgrad launch that is asked for the BatchNorm-backward sums of its destination: from 8 chunks on.  The sums are ~450
+// vector instructions per wave and tile in the epilogue, which ran beside the other group's MFMA phase at ~8 cycles per
+// instruction; on the two-chunk 256 x 256 layers that is the kernel's critical path (64 -> 64: 125 us against 114 on the
+// two-workgroup kernel, whose second workgroup covers it); from 256 input channels on it disappears (512 -> 512 at 32 x 32: 63
+// against 74 us).  With the epilogue in a phase of its own (fu_conv_pp.hip, body) the picture is the same -- one-stream trace,
+// pp | rs<8>: 64 -> 64 at 256 x 256 125 / 117 | 115 / 114 us, 128 -> 64 at 128 x 128 65 | 54, 256 -> 128 at 64 x 64 49 | 44,
+// 128 -> 128 at 128 x 128 92 | 83 (with the threshold at 64).
+static constexpr int CONV_PP_BNB_MIN_CIN = 256;
+// Tall tile of the fast kernel (16 x 32 pixels, 16-channel chunks).  Measured per layer against the square tile (bench shapes,
+// one stream): 5-9 % faster where it still yields >= 2048 workgroups (the 256x256 layers; the 8-channel first conv 60 -> 46
+// us), within +-4 % at 1024, 10 % slower at <= 512 -- hence the threshold.
+static constexpr int CONV_TALL_MIN_WGS = 2048;
+
+ConvRoute conv3x3_route(const BConvP& P, const LaunchOpts& o, const ConvHooks& h) {
+  // workgroups of 64 channels x 16x16 or 16x32 pixels (exact quotients wherever the rs / pp kernels are eligible)
+  const int64_t nco64 = ceil_div(P.N, 64);
+  const int64_t wg256 = (int64_t)P.B * ceil_div(P.H, 16) * ceil_div(P.W, 16) * nco64;
+  const int64_t wg512 = (int64_t)P.B * ceil_div(P.H, 32) * ceil_div(P.W, 16) * nco64;
+  // Tile choice of the general and the fast kernel (all tiles are 16x16 = 256 output pixels).  Measured on MI355X
+  // (profiles/): two 4-wave workgroups per CU (256x64 tile, 80 KB LDS) overlap one group's LDS staging with the other's MFMA
+  // block and beat the 8-wave 256x128 tile (higher FLOP/byte but lock-step phases) on every layer that yields >= 512
+  // workgroups; 256x32 keeps the small deep levels at >= 256 workgroups.  (Also tried and measured slower, hence not built:
+  // the 8-wave 256x128 tile with single or double-buffered 16-channel LDS stages (810-900 TF where this one reaches 870-1040)
+  // and a warp-specialised 4 loader + 4 compute wave version with two LDS stages (790-915 TF).  Removing the per-chunk
+  // staging altogether lets the same MFMA loop run at 1200-1430 TF, so staging costs ~30 % on the deep layers.)
+  const bool two_per_cu = P.N >= 64 && wg256 >= CONV_TWO_PER_CU_WGS;
+  if (h.force_general || !conv3x3_bf16_fast_eligible(P)) return two_per_cu ? CONV_GENERAL_64 : CONV_GENERAL_32;
+  const bool wide = two_per_cu && (!P.dst1 || P.D0 % 64 == 0);
+  if (P.center_only) return wide ? CONV_TAP1_64 : CONV_TAP1_32;
+  // 8 input channels (the network's first conv): the K = 72 kernel without LDS staging
+  if (h.tile_mode == 0 && conv3x3_c8_eligible(P)) return CONV_C8;
+  // persistent ping-pong kernel: tile mode 4 forces it; by default wherever it is preferred
+  if (conv3x3_pp_eligible(P)) {
+    const bool preferred = wg512 >= CONV_PP_MIN_TILES && (!wants_bnb(P, o) || P.Cin >= CONV_PP_BNB_MIN_CIN);
+    if (h.tile_mode == 4 || (h.tile_mode == 0 && preferred)) return CONV_PP;
+  }
+  // Row-stationary kernel, wherever the shape is eligible and one of its tiles gives every CU two workgroups.  Measured per
+  // layer against the fast kernel (bench shapes, forward, tools/conv_modes.py): 5-11 % faster on the 128x128, 64x64 and 32x32
+  // layers with N >= 512 channels x tiles, equal on the two-chunk 256x256 layers, slower below 512 workgroups (16x16 level,
+  // 512 -> 256 at 32x32).  Tile mode 3 forces it, modes 1 / 2 exclude it.  16 x 32-pixel tiles where they still give every
+  // CU two workgroups, 16 x 16 otherwise.
+  if (conv3x3_rs_eligible(P) && (h.tile_mode == 3 || (h.tile_mode == 0 && wg256 >= CONV_TWO_PER_CU_WGS)))
+    return (P.H % 32) == 0 && wg512 >= CONV_TWO_PER_CU_WGS ? CONV_RS8 : CONV_RS4;
+  const bool tall = h.tile_mode == 2 ? wide : (h.tile_mode == 0 && wide && wg512 >= CONV_TALL_MIN_WGS);
+  if (tall) return CONV_FAST_TALL;
+  return wide ? CONV_FAST_64 : CONV_FAST_32;
+}
 
 int launch_conv3x3_bf16(const ConvIn& in, const bf16_t* wpk, const float* bias, bf16_t* dst0, int D0, bf16_t* dst1,
                         int D1, float* stats, int* n_stat_tiles, int B, int H, int W, hipStream_t s) {
@@ -374,31 +410,25 @@ int launch_conv3x3_bf16(const ConvIn& in, const bf16_t* wpk, const float* bias, 
   P.wpk = wpk; P.bias = bias; P.dst0 = dst0; P.dst1 = dst1; P.stats = stats;
   P.C0 = in.C0; P.C1 = in.src1 ? in.C1 : 0; P.Cin = P.C0 + P.C1; P.N = D0 + D1; P.D0 = D0; P.D1 = D1;
   P.B = B; P.H = H; P.W = W;
-  P.center_only = (in.center_only && !g_bf16_force_full_taps) ? 1 : 0;
+  P.center_only = (in.center_only && !g_conv_hooks.full_taps) ? 1 : 0;
   P.bnb_y = nullptr; P.bnb_a = P.bnb_b = P.bnb_mean = P.bnb_invstd = nullptr; P.bnb_part = nullptr;
   FU_REQUIRE(P.C0 % 8 == 0 && P.C1 % 8 == 0, "conv3x3_bf16: input channel counts must be multiples of 8 (C0=%d C1=%d)",
              P.C0, P.C1);
   FU_REQUIRE(P.a0 == nullptr || P.C0 <= 1024, "conv3x3_bf16: at most 1024 BN-activated channels in source 0 (got %d)",
              P.C0);   // (the LDS table of BN coefficients; a plain source has no such limit)
-  // tile choice (all tiles are 16x16 = 256 output pixels).  Measured on MI355X (profiles/): two 4-wave workgroups
-  // per CU (256x64 tile, 80 KB LDS) overlap one group's LDS staging with the other's MFMA block and beat the
-  // 8-wave 256x128 tile (higher FLOP/byte but lock-step phases) on every layer that yields >= 512 workgroups;
-  // 256x32 keeps the small deep levels at >= 256 workgroups.  (Also tried and measured slower, hence not built: the
-  // 8-wave 256x128 tile with single or double-buffered 16-channel LDS stages (810-900 TF where this one reaches 870-1040)
-  // and a warp-specialised 4 loader + 4 compute wave version with two LDS stages (790-915 TF).  Removing the per-chunk
-  // staging altogether lets the same MFMA loop run at 1200-1430 TF, so staging costs ~30 % on the deep layers.)
-  if (!g_bf16_force_general && conv3x3_bf16_fast_eligible(P)) {
-    const int st = launch_conv3x3_bf16_fast(P, in.opt, s);
-    if (n_stat_tiles) *n_stat_tiles = P.nPix;
-    return st;
+  int st = 1;
+  const ConvRoute r = conv3x3_route(P, in.opt, g_conv_hooks);
+  switch (r) {
+    case CONV_GENERAL_64: st = launch_cfg<4, 1, 2>(P, in.opt, s); break;
+    case CONV_GENERAL_32: st = launch_cfg<4, 1, 1>(P, in.opt, s); break;
+    case CONV_C8: st = launch_conv3x3_c8(P, in.opt, s); break;
+    case CONV_PP: st = launch_conv3x3_pp(P, in.opt, s); break;
+    case CONV_RS8: st = launch_conv3x3_rs(P, true, in.opt, s); break;
+    case CONV_RS4: st = launch_conv3x3_rs(P, false, in.opt, s); break;
+    case CONV_TAP1_64: case CONV_TAP1_32: case CONV_FAST_TALL: case CONV_FAST_64: case CONV_FAST_32:
+      st = launch_conv3x3_bf16_fast(P, r, in.opt, s); break;
+    case CONV_NUM_ROUTES: break;
   }
-  const int64_t t256 = (int64_t)B * ceil_div(H, 16) * ceil_div(W, 16);
-  int cfg;
-  if (P.N >= 64 && t256 * ceil_div(P.N, 64) >= 512) cfg = 0;
-  else cfg = 2;
-  int st;
-  if (cfg == 0) st = launch_cfg<4, 1, 2>(P, in.opt, s);
-  else st = launch_cfg<4, 1, 1>(P, in.opt, s);
   if (n_stat_tiles) *n_stat_tiles = P.nPix;
   return st;
 }
@@ -406,13 +436,6 @@ int launch_conv3x3_bf16(const ConvIn& in, const bf16_t* wpk, const float* bias, 
 // ------------------------------------------------------------------------------------------------
 // wgrad
 // ------------------------------------------------------------------------------------------------
-struct BWgP {
-  const bf16_t* src0; const bf16_t* src1; const float* a0; const float* b0; const bf16_t* dy;
-  float* slab;
-  int C0, C1, Cin, Cout, B, H, W, tilesX, tilesY, nPix, nCi, nCo, S, perSplit;
-  unsigned rcp_tilesX, rcp_tilesY;   // k_wgrad_bf16_pp<true>: floor(2^32 / d) + 1 (0 for d == 1), as in BConvP
-};
-
 // Two transposing reads -> one MFMA fragment.  NOTE (hipcc / ROCm 7.2): the v4i16 form of the builtin followed by
 // per-element bit casts to __bf16 is miscompiled (element 0 is replicated); the v4bf16 form + shufflevector is correct
 // (checked on hardware, tools/probes/tr_probe3.hip).
@@ -1239,93 +1262,21 @@ static bool wgrad_c8_eligible(const BWgP& P) {
          npx * 128 < (int64_t(1) << 40) && npx < (int64_t(1) << 31);
 }
 
-static int launch_wgrad_c8(BWgP& P, int target_wgs, const LaunchOpts& o, hipStream_t s) {
-  using C = WC8;
-  P.tilesX = P.W / C::TW; P.tilesY = P.H / C::TH;
-  P.nPix = P.B * P.tilesX * P.tilesY;
-  P.nCi = 1; P.nCo = 1;
-  int S = target_wgs < P.nPix ? target_wgs : P.nPix;
-  if (S < 1) S = 1;
-  P.perSplit = ceil_div(P.nPix, S);
-  P.S = ceil_div(P.nPix, P.perSplit);     // every split owns at least one tile
-  P.rcp_tilesX = host_rcp(P.tilesX); P.rcp_tilesY = host_rcp(P.tilesY);
-  static bool attr_set = false;
-  if (!attr_set) {
-    FU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_bf16_c8),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM_BYTES));
-    attr_set = true;
-  }
-  const ProfSlot ps = o.prof;
-  if (ps.start) (void)hipEventRecord(ps.start, s);
-  hipLaunchKernelGGL(k_wgrad_bf16_c8, dim3(P.S), dim3(C::NT), C::SMEM_BYTES, s, P);
-  if (ps.stop) (void)hipEventRecord(ps.stop, s);
-  FU_LAUNCH_CHECK();
-  return 0;
+// one launch per route on the grid conv3x3_wgrad_plan laid out: (c_in tile, c_out tile, split) workgroups
+template <auto Kernel, typename Cfg>
+static int launch_wgrad(const BWgP& P, const LaunchOpts& o, hipStream_t s) {
+  return launch_conv_kernel<Kernel>(dim3(P.nCi * P.nCo * P.S), dim3(Cfg::NT), Cfg::SMEM_BYTES, o, s, P);
 }
 
-template <int WMI, int PTH, int TAPS = 9>
-static int launch_wgrad_cfg(BWgP& P, int target_wgs, const LaunchOpts& o, hipStream_t s) {
-  using Cfg = WCfg<WMI, PTH>;
-  P.tilesX = ceil_div(P.W, Cfg::PTW); P.tilesY = ceil_div(P.H, PTH);
-  P.nPix = P.B * P.tilesX * P.tilesY;
-  P.nCi = ceil_div(P.Cin, Cfg::CI_T); P.nCo = ceil_div(P.Cout, Cfg::CO_T);
-  const int nT = P.nCi * P.nCo;
-  int S = ceil_div(target_wgs, nT);
-  if (S > P.nPix) S = P.nPix;
-  if (S < 1) S = 1;
-  P.perSplit = ceil_div(P.nPix, S);
-  P.S = ceil_div(P.nPix, P.perSplit);
-  static bool attr_set = false;
-  if (!attr_set) {
-    FU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_bf16<WMI, PTH, TAPS>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM_BYTES));
-    attr_set = true;
-  }
-  const ProfSlot ps = o.prof;
-  if (ps.start) (void)hipEventRecord(ps.start, s);
-  hipLaunchKernelGGL((k_wgrad_bf16<WMI, PTH, TAPS>), dim3(nT * P.S), dim3(Cfg::NT), Cfg::SMEM_BYTES, s, P);
-  if (ps.stop) (void)hipEventRecord(ps.stop, s);
-  FU_LAUNCH_CHECK();
-  return 0;
-}
-
-#if !FU_HALF
-int g_wgrad_force_lockstep = 0;   // testing hook (fu_test_force_lockstep_wgrad): 1 = k_wgrad_bf16<4,8> instead of the ping-pong kernel, 2 = the ping-pong kernel with its general staging
-#endif
-
-static int launch_wgrad_pp(BWgP& P, int target_wgs, const LaunchOpts& o, hipStream_t s) {
+static int launch_wgrad_pp(const BWgP& P, const LaunchOpts& o, hipStream_t s) {
   using Cfg = WPCfg;
-  P.tilesX = ceil_div(P.W, Cfg::PTW); P.tilesY = ceil_div(P.H, Cfg::PTH);
-  P.nPix = P.B * P.tilesX * P.tilesY;
-  P.nCi = ceil_div(P.Cin, Cfg::CI_T); P.nCo = ceil_div(P.Cout, Cfg::CO_T);
-  const int nT = P.nCi * P.nCo;
-  int S = ceil_div(target_wgs, nT);
-  if (S > P.nPix) S = P.nPix;
-  if (S < 1) S = 1;
-  P.perSplit = ceil_div(P.nPix, S);
-  P.S = ceil_div(P.nPix, P.perSplit);     // every split owns at least one stage
-  P.rcp_tilesX = host_rcp(P.tilesX); P.rcp_tilesY = host_rcp(P.tilesY);
-  static bool attr_set = false;
-  if (!attr_set) {
-    FU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_bf16_pp<true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM_BYTES));
-    FU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_bf16_pp<false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM_BYTES));
-    attr_set = true;
-  }
   // whole pixel tiles, whole channel tiles, 24-bit pixel indices and pixel strides, 32-bit byte offsets inside a source
   const int64_t npx = (int64_t)P.B * P.H * P.W;
   const int cmax = P.C0 > P.C1 ? P.C0 : P.C1;
-  const bool fast = g_wgrad_force_lockstep != 2 && P.H % Cfg::PTH == 0 && P.W % Cfg::PTW == 0 && P.Cin % Cfg::CI_T == 0 &&
+  const bool fast = g_conv_hooks.wgrad_lockstep != 2 && P.H % Cfg::PTH == 0 && P.W % Cfg::PTW == 0 && P.Cin % Cfg::CI_T == 0 &&
                     P.Cout % Cfg::CO_T == 0 && npx < (1 << 24) && npx * cmax * 2 < (int64_t(1) << 32) &&
-                    npx * P.Cout * 2 < (int64_t(1) << 32) && (int64_t)P.nPix * nT < (int64_t(1) << 31);
-  const ProfSlot ps = o.prof;
-  if (ps.start) (void)hipEventRecord(ps.start, s);
-  if (fast) hipLaunchKernelGGL(k_wgrad_bf16_pp<true>, dim3(nT * P.S), dim3(Cfg::NT), Cfg::SMEM_BYTES, s, P);
-  else hipLaunchKernelGGL(k_wgrad_bf16_pp<false>, dim3(nT * P.S), dim3(Cfg::NT), Cfg::SMEM_BYTES, s, P);
-  if (ps.stop) (void)hipEventRecord(ps.stop, s);
-  FU_LAUNCH_CHECK();
-  return 0;
+                    npx * P.Cout * 2 < (int64_t(1) << 32) && (int64_t)P.nPix * P.nCi * P.nCo < (int64_t(1) << 31);
+  return fast ? launch_wgrad<k_wgrad_bf16_pp<true>, Cfg>(P, o, s) : launch_wgrad<k_wgrad_bf16_pp<false>, Cfg>(P, o, s);
 }
 
 // Workgroups of the ping-pong kernel.  Its 8-wave workgroups (248 registers, 125 KB of LDS) take a CU each and live for the
@@ -1349,16 +1300,40 @@ static int launch_wgrad_pp(BWgP& P, int target_wgs, const LaunchOpts& o, hipStre
 static constexpr int WGRAD_PP_TARGET = 160;
 // ... of the narrow launches: the 8-band first conv and k_wgrad_bf16<2,8> (256 threads, two workgroups per CU)
 static constexpr int WGRAD_C64_TARGET = 512;
+// ... of the one-tap launches (embedded 1x1): one 8-wave workgroup per CU, or two 4-wave ones
+static constexpr int WGRAD_TAP1_WIDE_TARGET = 256, WGRAD_TAP1_NARROW_TARGET = 512;
 
-// upper bound of the slab size over the two configurations below
+WgradRoute conv3x3_wgrad_route(const BWgP& P, bool one_tap, const ConvHooks& h) {
+  // embedded 1x1 (late-fusion convs): the stage is all staging, so the lock-step kernel (all 8 waves stage together) wins
+  // over the ping-pong one; the eight unwritten tap slabs reach only taps of dw_oihw that the caller never reads
+  if (one_tap) return P.Cin > 64 ? WGRAD_TAP1_WIDE : WGRAD_TAP1_NARROW;
+  if (!h.wgrad_lockstep && wgrad_c8_eligible(P)) return WGRAD_C8;   // the 8-band first conv: K = 72 stream over dy
+  // 512 threads, 128 c_in x 64 c_out, one WG per CU: the ping-pong kernel, or the lock-step one on the same split
+  // (bit-identical sums); 256 threads, 64 x 64, two WGs per CU below
+  if (P.Cin > 64) return h.wgrad_lockstep != 1 ? WGRAD_PP : WGRAD_LOCKSTEP_128;
+  return WGRAD_LOCKSTEP_64;
+}
+
+void conv3x3_wgrad_plan(BWgP& P, WgradRoute r) {
+  switch (r) {
+    case WGRAD_TAP1_WIDE: wgrad_geometry(P, WCfg<4, 8>::PTW, 8, WCfg<4, 8>::CI_T, WGRAD_TAP1_WIDE_TARGET); break;
+    case WGRAD_TAP1_NARROW: wgrad_geometry(P, WCfg<2, 8>::PTW, 8, WCfg<2, 8>::CI_T, WGRAD_TAP1_NARROW_TARGET); break;
+    case WGRAD_C8: wgrad_geometry(P, WC8::TW, WC8::TH, 8, WGRAD_C64_TARGET); break;   // one tile of its 8 c_in x 64 c_out
+    case WGRAD_PP: wgrad_geometry(P, WPCfg::PTW, WPCfg::PTH, WPCfg::CI_T, WGRAD_PP_TARGET); break;
+    case WGRAD_LOCKSTEP_128: wgrad_geometry(P, WCfg<4, 8>::PTW, 8, WCfg<4, 8>::CI_T, WGRAD_PP_TARGET); break;
+    case WGRAD_LOCKSTEP_64: wgrad_geometry(P, WCfg<2, 8>::PTW, 8, WCfg<2, 8>::CI_T, WGRAD_C64_TARGET); break;
+    case WGRAD_NUM_ROUTES: break;
+  }
+}
+
+// upper bound of the slab size over every plan above: the largest workgroup target of the 128- and of the 64-c_in tiles
+// on 8x16-pixel stages (the 8-band kernel's 8x32 tiles give no more splits), one slab to spare
 int64_t conv3x3_wgrad_slab_elems_bf16(int Cin, int Cout, int B, int H, int W) {
-  const int64_t npix = (int64_t)B * ceil_div(H, 8) * ceil_div(W, 16);
-  const int nT128 = ceil_div(Cin, 128) * ceil_div(Cout, 64);
-  const int nT64 = ceil_div(Cin, 64) * ceil_div(Cout, 64);
-  int64_t s128 = ceil_div(256, nT128), s64 = ceil_div(512, nT64);
-  if (s128 > npix) s128 = npix;
-  if (s64 > npix) s64 = npix;
-  const int64_t smax = s128 > s64 ? s128 : s64;
+  constexpr int T128 = std::max(WGRAD_PP_TARGET, WGRAD_TAP1_WIDE_TARGET), T64 = std::max(WGRAD_C64_TARGET, WGRAD_TAP1_NARROW_TARGET);
+  const int64_t npix = (int64_t)B * ceil_div(H, WPCfg::PTH) * ceil_div(W, WPCfg::PTW);
+  const int nT128 = ceil_div(Cin, WCfg<4, 8>::CI_T) * ceil_div(Cout, 64);
+  const int nT64 = ceil_div(Cin, WCfg<2, 8>::CI_T) * ceil_div(Cout, 64);
+  const int64_t smax = std::min<int64_t>(std::max(ceil_div(T128, nT128), ceil_div(T64, nT64)), npix);
   return (smax + 1) * 9 * (int64_t)Cin * Cout;
 }
 
@@ -1370,23 +1345,20 @@ int launch_conv3x3_wgrad_bf16(const ConvIn& in, const bf16_t* dy, int Cout, floa
   P.slab = slab;
   P.C0 = in.C0; P.C1 = in.src1 ? in.C1 : 0; P.Cin = P.C0 + P.C1; P.Cout = Cout; P.B = B; P.H = H; P.W = W;
   FU_REQUIRE(P.C0 % 8 == 0 && P.C1 % 8 == 0 && Cout % 8 == 0, "wgrad_bf16: channel counts must be multiples of 8");
-  int st;
-  // embedded 1x1 (late-fusion convs): the stage is all staging, so the lock-step kernel (all 8 waves stage together) wins
-  // over the ping-pong one; the eight unwritten tap slabs reach only taps of dw_oihw that the caller never reads
-  if (in.center_only && !g_bf16_force_full_taps && P.Cin > 64) st = launch_wgrad_cfg<4, 8, 1>(P, 256, in.opt, s);
-  else if (in.center_only && !g_bf16_force_full_taps) st = launch_wgrad_cfg<2, 8, 1>(P, 512, in.opt, s);
-  else if (!g_wgrad_force_lockstep && wgrad_c8_eligible(P)) st = launch_wgrad_c8(P, WGRAD_C64_TARGET, in.opt, s);   // the 8-band first conv: K = 72 stream over dy
-  else if (P.Cin > 64 && g_wgrad_force_lockstep != 1) st = launch_wgrad_pp(P, WGRAD_PP_TARGET, in.opt, s);   // 512 threads, 128 c_in x 64 c_out, one WG per CU
-  else if (P.Cin > 64) st = launch_wgrad_cfg<4, 8>(P, WGRAD_PP_TARGET, in.opt, s);   // (same split as the ping-pong kernel: bit-identical sums)
-  else st = launch_wgrad_cfg<2, 8>(P, WGRAD_C64_TARGET, in.opt, s);   // 256 threads, 64 x 64, two WGs per CU
+  const WgradRoute r = conv3x3_wgrad_route(P, in.center_only && !g_conv_hooks.full_taps, g_conv_hooks);
+  conv3x3_wgrad_plan(P, r);
+  int st = 1;
+  switch (r) {
+    case WGRAD_TAP1_WIDE: st = launch_wgrad<k_wgrad_bf16<4, 8, 1>, WCfg<4, 8>>(P, in.opt, s); break;
+    case WGRAD_TAP1_NARROW: st = launch_wgrad<k_wgrad_bf16<2, 8, 1>, WCfg<2, 8>>(P, in.opt, s); break;
+    case WGRAD_C8: st = launch_wgrad<k_wgrad_bf16_c8, WC8>(P, in.opt, s); break;
+    case WGRAD_PP: st = launch_wgrad_pp(P, in.opt, s); break;
+    case WGRAD_LOCKSTEP_128: st = launch_wgrad<k_wgrad_bf16<4, 8>, WCfg<4, 8>>(P, in.opt, s); break;
+    case WGRAD_LOCKSTEP_64: st = launch_wgrad<k_wgrad_bf16<2, 8>, WCfg<2, 8>>(P, in.opt, s); break;
+    case WGRAD_NUM_ROUTES: break;
+  }
   if (st) return st;
   return launch_wgrad_reduce_oihw(slab, P.S, P.Cin, Cout, cin_real, dw_oihw, db_partials, n_db_partials, db, s);
 }
 
 }  // namespace fu
-
-#if !FU_HALF
-extern "C" void fu_test_force_general_conv(int on) { fu::g_bf16_force_general = on; }
-extern "C" void fu_test_force_lockstep_wgrad(int on) { fu::g_wgrad_force_lockstep = on; }
-extern "C" void fu_test_force_full_taps(int on) { fu::g_bf16_force_full_taps = on; }
-#endif

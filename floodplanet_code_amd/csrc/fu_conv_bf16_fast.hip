@@ -455,12 +455,6 @@ __global__ __launch_bounds__(256, MT == 4 ? 2 : 1) void k_conv3x3_bf16_fast(BCon
   }
 }
 
-#if FU_HALF
-extern int g_bf16_tile_mode;
-#else
-int g_bf16_tile_mode = 0;   // 0 = heuristic, 1 = never the tall tile, 2 = tall wherever 64-channel tiles run
-#endif
-
 bool conv3x3_bf16_fast_eligible(const BConvP& P) {
   const int64_t px = (int64_t)P.B * P.H * P.W;
   const int64_t lim = (int64_t)1 << 31;
@@ -475,61 +469,25 @@ bool conv3x3_bf16_fast_eligible(const BConvP& P) {
 template <int NTW, int TAPS = 9, int MT = 2, int KCH = 32>
 static int launch_fast_cfg(BConvP& P, const LaunchOpts& o, hipStream_t s) {
   using Cfg = FCfg<NTW, TAPS, MT, KCH>;
-  P.tilesX = ceil_div(P.W, Cfg::TW); P.tilesY = ceil_div(P.H, Cfg::TH);
-  P.nPix = P.B * P.tilesX * P.tilesY; P.nCo = ceil_div(P.N, Cfg::BN);
-  P.rcp_nPix = host_rcp(P.nPix); P.rcp_tilesX = host_rcp(P.tilesX); P.rcp_tilesY = host_rcp(P.tilesY);
+  conv_geometry(P, Cfg::TW, Cfg::TH, Cfg::BN);
   FU_REQUIRE((int64_t)P.nPix * P.nCo * P.nPix < ((int64_t)1 << 32), "conv3x3_bf16_fast: grid too large (%d x %d)",
              P.nPix, P.nCo);
-  static bool attr_set = false;
-  if (!attr_set) {
-    FU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_bf16_fast<NTW, TAPS, MT, KCH>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM_BYTES));
-    attr_set = true;
-  }
-  const ProfSlot ps = o.prof;
-  if (ps.start) (void)hipEventRecord(ps.start, s);
-  hipLaunchKernelGGL((k_conv3x3_bf16_fast<NTW, TAPS, MT, KCH>), dim3(P.nPix * P.nCo), dim3(Cfg::NT), Cfg::SMEM_BYTES, s,
-                     P);
-  if (ps.stop) (void)hipEventRecord(ps.stop, s);
-  FU_LAUNCH_CHECK();
-  return 0;
+  return launch_conv_kernel<k_conv3x3_bf16_fast<NTW, TAPS, MT, KCH>>(dim3(P.nPix * P.nCo), dim3(Cfg::NT), Cfg::SMEM_BYTES,
+                                                                     o, s, P);
 }
 
-// Tile choice (all tiles are 16x16 = 256 output pixels): 64 output channels per workgroup when that still yields
-// >= 512 workgroups (two per CU), else 32.
-int launch_conv3x3_bf16_fast(BConvP& P, const LaunchOpts& o, hipStream_t s) {
-  const int64_t t256 = (int64_t)P.B * ceil_div(P.H, 16) * ceil_div(P.W, 16);
-  const bool wide = P.N >= 64 && t256 * ceil_div(P.N, 64) >= 512 && (!P.dst1 || P.D0 % 64 == 0);
-  if (P.center_only) return wide ? launch_fast_cfg<2, 1>(P, o, s) : launch_fast_cfg<1, 1>(P, o, s);
-  // 8 input channels (the network's first conv): the K = 72 kernel without LDS staging (fu_conv_rs.hip)
-  if (g_bf16_tile_mode == 0 && conv3x3_c8_eligible(P)) return launch_conv3x3_c8(P, o, s);
-  // Row-stationary kernel (fu_conv_rs.hip), wherever the shape is eligible and one of its tiles gives every CU two
-  // workgroups.  Measured per layer against the kernels below (bench shapes, forward, tools/conv_modes.py): 5-11 % faster
-  // on the 128x128, 64x64 and 32x32 layers with N >= 512 channels x tiles, equal on the two-chunk 256x256 layers, slower
-  // below 512 workgroups (16x16 level, 512 -> 256 at 32x32).  Tile mode 3 forces it, modes 1 / 2 exclude it.
-  // persistent ping-pong kernel (fu_conv_pp.hip): tile mode 4 forces it; by default wherever it is preferred
-  if (conv3x3_pp_eligible(P)) {
-    const bool wants_bnb = o.bnb != nullptr && o.bnb->y != nullptr && P.a0 == nullptr && P.dst1 == nullptr && P.stats == nullptr;
-    if (g_bf16_tile_mode == 4 ||
-        (g_bf16_tile_mode == 0 && (wants_bnb ? conv3x3_pp_preferred_bnb(P) : conv3x3_pp_preferred(P))))
-      return launch_conv3x3_pp(P, o, s);
+// the five instantiations that are dispatched (conv3x3_route, fu_conv_bf16.hip): 64 or 32 output channels per workgroup,
+// one tap or nine, the tall tile
+int launch_conv3x3_bf16_fast(BConvP& P, ConvRoute r, const LaunchOpts& o, hipStream_t s) {
+  switch (r) {
+    case CONV_TAP1_64: return launch_fast_cfg<2, 1>(P, o, s);
+    case CONV_TAP1_32: return launch_fast_cfg<1, 1>(P, o, s);
+    case CONV_FAST_TALL: return launch_fast_cfg<2, 9, 4, 16>(P, o, s);
+    case CONV_FAST_64: return launch_fast_cfg<2>(P, o, s);
+    case CONV_FAST_32: return launch_fast_cfg<1>(P, o, s);
+    default: break;   // the routes of the other kernels (launch_conv3x3_bf16)
   }
-  if (conv3x3_rs_eligible(P)) {
-    const int64_t t256 = (int64_t)P.B * (P.H / 16) * (P.W / 16) * (P.N / 64);
-    if (g_bf16_tile_mode == 3 || (g_bf16_tile_mode == 0 && t256 >= 512)) return launch_conv3x3_rs(P, o, s);
-  }
-  // tall tile (16 x 32 pixels, 16-channel chunks).  Measured per layer against the square tile (bench shapes, one
-  // stream): 5-9 % faster where it still yields >= 2048 workgroups (the 256x256 layers; the 8-channel first conv 60 ->
-  // 46 us), within +-4 % at 1024, 10 % slower at <= 512 -- hence the threshold.
-  const int64_t t512 = (int64_t)P.B * ceil_div(P.H, 32) * ceil_div(P.W, 16);
-  const bool tall = g_bf16_tile_mode == 2 ? wide
-                                          : (g_bf16_tile_mode == 0 && wide && t512 * ceil_div(P.N, 64) >= 2048);
-  if (tall) return launch_fast_cfg<2, 9, 4, 16>(P, o, s);
-  return wide ? launch_fast_cfg<2>(P, o, s) : launch_fast_cfg<1>(P, o, s);
+  FU_REQUIRE(false, "conv3x3_bf16_fast: route %d is not a fast-kernel route", (int)r);
 }
 
 }  // namespace fu
-
-#if !FU_HALF
-extern "C" void fu_test_conv_tile_mode(int mode) { fu::g_bf16_tile_mode = mode; }
-#endif

@@ -255,20 +255,10 @@ int launch_conv3x3_f32(const ConvIn& in, const float* wpk, const float* bias, fl
              "conv3x3_f32: channel counts must be multiples of 4 (C0=%d C1=%d N=%d)", P.C0, P.C1, P.N);
   const int th = conv_pick_th(B, H, W, P.N);
   P.tilesX = ceil_div(W, 16); P.tilesY = ceil_div(H, th); P.nPix = B * P.tilesX * P.tilesY; P.nCo = ceil_div(P.N, 64);
-  const int grid = P.nPix * P.nCo;
+  const dim3 grid(P.nPix * P.nCo), block(256);
   if (n_stat_tiles) *n_stat_tiles = P.nPix;
-  const ProfSlot ps = in.opt.prof;
-  if (ps.start) (void)hipEventRecord(ps.start, s);
-  if (th == 8) {
-    const size_t sh = ConvCfg<8>::SMEM_FLOATS * sizeof(float);
-    hipLaunchKernelGGL(k_conv3x3_f32<8>, dim3(grid), dim3(256), sh, s, P);
-  } else {
-    const size_t sh = ConvCfg<4>::SMEM_FLOATS * sizeof(float);
-    hipLaunchKernelGGL(k_conv3x3_f32<4>, dim3(grid), dim3(256), sh, s, P);
-  }
-  if (ps.stop) (void)hipEventRecord(ps.stop, s);
-  FU_LAUNCH_CHECK();
-  return 0;
+  return th == 8 ? launch_conv_kernel<k_conv3x3_f32<8>>(grid, block, ConvCfg<8>::SMEM_FLOATS * sizeof(float), in.opt, s, P)
+                 : launch_conv_kernel<k_conv3x3_f32<4>>(grid, block, ConvCfg<4>::SMEM_FLOATS * sizeof(float), in.opt, s, P);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -415,13 +405,8 @@ int launch_conv3x3_wgrad_f32(const ConvIn& in, const float* dy, int Cout, float*
   P.tilesX = ceil_div(W, WG_PTW); P.tilesY = ceil_div(H, WG_PTH);
   wgrad_split_shared(P.Cin, Cout, B, H, W, &P.nPix, &P.S, &P.perSplit);
   P.nCi = ceil_div(P.Cin, WG_CT); P.nCo = ceil_div(Cout, WG_CT);
-  const int grid = P.nCi * P.nCo * P.S;
   const size_t sh = (size_t)(WG_NHP * WG_CT + 64 * WG_CT) * sizeof(float);
-  const ProfSlot ps = in.opt.prof;
-  if (ps.start) (void)hipEventRecord(ps.start, s);
-  hipLaunchKernelGGL(k_wgrad_f32, dim3(grid), dim3(256), sh, s, P);
-  if (ps.stop) (void)hipEventRecord(ps.stop, s);
-  FU_LAUNCH_CHECK();
+  FU_TRY(launch_conv_kernel<k_wgrad_f32>(dim3(P.nCi * P.nCo * P.S), dim3(256), sh, in.opt, s, P));
   return launch_wgrad_reduce(slab, P.S, P.Cin, Cout, cin_real, dw_oihw, db_partials, n_db_partials, db, s);
 }
 

@@ -655,43 +655,17 @@ bool conv3x3_pp_eligible(const BConvP& P) {
   return tiles >= 8 && tiles < ((int64_t)1 << 24);
 }
 
-// default dispatch: only where every CU gets at least one tile (one workgroup per CU for the whole launch: 128 tiles leave half
-// the chip idle -- 512 -> 256 at 32 x 32 measured 54.8 us against 50.5 on the two-workgroup kernel)
-bool conv3x3_pp_preferred(const BConvP& P) {
-  const int64_t tiles = (int64_t)P.B * (P.H / 32) * (P.W / 16) * (P.N / 64);
-  return conv3x3_pp_eligible(P) && tiles >= 256;
-}
-
-// ... of a dgrad launch that is asked for the BatchNorm-backward sums of its destination: from 8 chunks on.  The sums are ~450
-// vector instructions per wave and tile in the epilogue, which ran beside the other group's MFMA phase at ~8 cycles per
-// instruction; on the two-chunk 256 x 256 layers that is the kernel's critical path (64 -> 64: 125 us against 114 on the
-// two-workgroup kernel, whose second workgroup covers it); from 256 input channels on it disappears (512 -> 512 at 32 x 32: 63
-// against 74 us).  With the epilogue in a phase of its own (body) the picture is the same -- one-stream trace, pp | rs<8>: 64 -> 64
-// at 256 x 256 125 / 117 | 115 / 114 us, 128 -> 64 at 128 x 128 65 | 54, 256 -> 128 at 64 x 64 49 | 44, 128 -> 128 at 128 x 128 92 | 83
-// (with the threshold at 64).
-bool conv3x3_pp_preferred_bnb(const BConvP& P) {
-  return conv3x3_pp_preferred(P) && P.Cin >= 256;
+template <bool BNB, bool BN, bool FWD>
+static int launch_pp_cfg(int grid, const BConvP& P, const LaunchOpts& o, hipStream_t s) {
+  return launch_conv_kernel<k_conv3x3_bf16_pp<BNB, BN, FWD>>(dim3(grid), dim3(PCfg::NT), PCfg::SMEM_BYTES, o, s, P);
 }
 
 int launch_conv3x3_pp(BConvP& P, const LaunchOpts& o, hipStream_t s) {
-  using Cfg = PCfg;
-  P.tilesX = P.W / Cfg::TW; P.tilesY = P.H / Cfg::TH;
-  P.nPix = P.B * P.tilesX * P.tilesY; P.nCo = P.N / Cfg::BN;
-  P.nTiles = P.nPix * P.nCo;
-  P.rcp_nPix = host_rcp(P.nPix); P.rcp_tilesX = host_rcp(P.tilesX); P.rcp_tilesY = host_rcp(P.tilesY);
-  P.rcp_nCo = host_rcp(P.nCo);
+  conv_geometry(P, PCfg::TW, PCfg::TH, PCfg::BN);
   FU_REQUIRE((int64_t)P.nTiles * P.nPix < ((int64_t)1 << 32) && (int64_t)P.nTiles * P.nCo < ((int64_t)1 << 32),
              "conv3x3_pp: grid too large (%d x %d)", P.nPix, P.nCo);
   // BatchNorm-backward sums of the destination, if the API layer asked for them and this launch can give them
-  static const BnbFuse none;
-  const BnbFuse& f = o.bnb ? *o.bnb : none;
-  if (f.y != nullptr && f.tiles_out != nullptr && P.a0 == nullptr && P.dst1 == nullptr && P.stats == nullptr) {
-    if ((int64_t)P.nPix * P.N * 2 <= f.max_elems) {
-      P.bnb_y = (const bf16_t*)f.y; P.bnb_a = f.a; P.bnb_b = f.b; P.bnb_mean = f.mean; P.bnb_invstd = f.invstd;
-      P.bnb_part = f.part;
-      *f.tiles_out = P.nPix;
-    }
-  }
+  const bool bnb = attach_bnb(P, o, P.nPix);
   static int n_cu = 0;
   if (n_cu == 0) {
     int dev = 0;
@@ -699,28 +673,13 @@ int launch_conv3x3_pp(BConvP& P, const LaunchOpts& o, hipStream_t s) {
     FU_HIP_CHECK(hipGetDevice(&dev));
     FU_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
     n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    const void* ks[5] = {reinterpret_cast<const void*>(&k_conv3x3_bf16_pp<false, false, false>),
-                         reinterpret_cast<const void*>(&k_conv3x3_bf16_pp<false, false, true>),
-                         reinterpret_cast<const void*>(&k_conv3x3_bf16_pp<false, true, false>),
-                         reinterpret_cast<const void*>(&k_conv3x3_bf16_pp<false, true, true>),
-                         reinterpret_cast<const void*>(&k_conv3x3_bf16_pp<true, false, false>)};
-    for (const void* k : ks) FU_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM_BYTES));
   }
   // one workgroup per CU, a multiple of 8 (the XCD of a workgroup's virtual block ids must not change from tile to tile)
-  int grid = P.nTiles < n_cu ? P.nTiles : n_cu;
-  grid &= ~7;
-  const ProfSlot ps = o.prof;
-  if (ps.start) (void)hipEventRecord(ps.start, s);
+  const int grid = (P.nTiles < n_cu ? P.nTiles : n_cu) & ~7;
   const bool fwd = P.bias != nullptr || P.stats != nullptr, bn = P.a0 != nullptr;
-  const dim3 g(grid), b(Cfg::NT);
-  if (P.bnb_y != nullptr) hipLaunchKernelGGL((k_conv3x3_bf16_pp<true, false, false>), g, b, Cfg::SMEM_BYTES, s, P);
-  else if (bn && fwd) hipLaunchKernelGGL((k_conv3x3_bf16_pp<false, true, true>), g, b, Cfg::SMEM_BYTES, s, P);
-  else if (bn) hipLaunchKernelGGL((k_conv3x3_bf16_pp<false, true, false>), g, b, Cfg::SMEM_BYTES, s, P);
-  else if (fwd) hipLaunchKernelGGL((k_conv3x3_bf16_pp<false, false, true>), g, b, Cfg::SMEM_BYTES, s, P);
-  else hipLaunchKernelGGL((k_conv3x3_bf16_pp<false, false, false>), g, b, Cfg::SMEM_BYTES, s, P);
-  if (ps.stop) (void)hipEventRecord(ps.stop, s);
-  FU_LAUNCH_CHECK();
-  return 0;
+  if (bnb) return launch_pp_cfg<true, false, false>(grid, P, o, s);
+  if (bn) return fwd ? launch_pp_cfg<false, true, true>(grid, P, o, s) : launch_pp_cfg<false, true, false>(grid, P, o, s);
+  return fwd ? launch_pp_cfg<false, false, true>(grid, P, o, s) : launch_pp_cfg<false, false, false>(grid, P, o, s);
 }
 
 }  // namespace fu

@@ -552,19 +552,12 @@ bool conv3x3_c8_eligible(const BConvP& P) {
 
 int launch_conv3x3_c8(BConvP& P, const LaunchOpts& o, hipStream_t s) {
   const bool tall = (P.H % 64) == 0;                   // 16 x 64-pixel tiles (fewer statistics rows), else 16 x 16
-  P.tilesX = P.W / 16; P.tilesY = P.H / (tall ? 64 : 16);
-  P.nPix = P.B * P.tilesX * P.tilesY; P.nCo = P.N / 64;
-  P.rcp_nPix = host_rcp(P.nPix); P.rcp_tilesX = host_rcp(P.tilesX); P.rcp_tilesY = host_rcp(P.tilesY);
-  P.rcp_nCo = host_rcp(P.nCo);
+  conv_geometry(P, 16, tall ? 64 : 16, 64);
   FU_REQUIRE((int64_t)P.nPix * P.nCo * P.nPix < ((int64_t)1 << 32) && (int64_t)P.nPix * P.nCo * P.nCo < ((int64_t)1 << 32),
              "conv3x3_c8: grid too large (%d x %d)", P.nPix, P.nCo);
-  const ProfSlot ps = o.prof;
-  if (ps.start) (void)hipEventRecord(ps.start, s);
-  if (tall) hipLaunchKernelGGL(k_conv3x3_bf16_c8<16>, dim3(P.nPix * P.nCo), dim3(256), 0, s, P);
-  else hipLaunchKernelGGL(k_conv3x3_bf16_c8<4>, dim3(P.nPix * P.nCo), dim3(256), 0, s, P);
-  if (ps.stop) (void)hipEventRecord(ps.stop, s);
-  FU_LAUNCH_CHECK();
-  return 0;
+  const dim3 g(P.nPix * P.nCo), b(256);
+  return tall ? launch_conv_kernel<k_conv3x3_bf16_c8<16>>(g, b, 0, o, s, P)
+              : launch_conv_kernel<k_conv3x3_bf16_c8<4>>(g, b, 0, o, s, P);
 }
 
 bool conv3x3_rs_eligible(const BConvP& P) {
@@ -580,46 +573,20 @@ bool conv3x3_rs_eligible(const BConvP& P) {
   return true;
 }
 
+// also gives the BatchNorm-backward sums of the destination, if the API layer asked for them and this launch can
 template <int ROWS_>
 static int launch_rs_cfg(BConvP& P, const LaunchOpts& o, hipStream_t s) {
   using Cfg = RCfg<ROWS_>;
-  P.tilesX = P.W / Cfg::TW; P.tilesY = P.H / Cfg::TH;
-  P.nPix = P.B * P.tilesX * P.tilesY; P.nCo = P.N / Cfg::BN;
-  P.rcp_nPix = host_rcp(P.nPix); P.rcp_tilesX = host_rcp(P.tilesX); P.rcp_tilesY = host_rcp(P.tilesY);
-  P.rcp_nCo = host_rcp(P.nCo);
+  conv_geometry(P, Cfg::TW, Cfg::TH, Cfg::BN);
   FU_REQUIRE((int64_t)P.nPix * P.nCo * P.nPix < ((int64_t)1 << 32) && (int64_t)P.nPix * P.nCo * P.nCo < ((int64_t)1 << 32),
              "conv3x3_rs: grid too large (%d x %d)", P.nPix, P.nCo);
-  static bool attr_set = false;
-  if (!attr_set) {
-    FU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_bf16_rs<ROWS_>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM_BYTES));
-    attr_set = true;
-  }
-  const ProfSlot ps = o.prof;
-  if (ps.start) (void)hipEventRecord(ps.start, s);
-  hipLaunchKernelGGL(k_conv3x3_bf16_rs<ROWS_>, dim3(P.nPix * P.nCo), dim3(Cfg::NT), Cfg::SMEM_BYTES, s, P);
-  if (ps.stop) (void)hipEventRecord(ps.stop, s);
-  FU_LAUNCH_CHECK();
-  return 0;
+  attach_bnb(P, o, P.nPix);
+  return launch_conv_kernel<k_conv3x3_bf16_rs<ROWS_>>(dim3(P.nPix * P.nCo), dim3(Cfg::NT), Cfg::SMEM_BYTES, o, s, P);
 }
 
-// 16 x 32-pixel tiles where they still give every CU two workgroups, 16 x 16 otherwise
-int launch_conv3x3_rs(BConvP& P, const LaunchOpts& o, hipStream_t s) {
-  const int64_t t512 = (int64_t)P.B * (P.H / 32) * (P.W / 16) * (P.N / 64);
-  const bool tall = (P.H % 32) == 0 && t512 >= 512;
-  // BatchNorm-backward sums of the destination, if the API layer asked for them and this launch can give them
-  static const BnbFuse none;
-  const BnbFuse& f = o.bnb ? *o.bnb : none;
-  if (f.y != nullptr && f.tiles_out != nullptr && P.a0 == nullptr && P.dst1 == nullptr && P.stats == nullptr) {
-    const int64_t tiles = (int64_t)P.B * (P.H / (tall ? 32 : 16)) * (P.W / 16);
-    if (tiles * P.N * 2 <= f.max_elems) {
-      P.bnb_y = (const bf16_t*)f.y; P.bnb_a = f.a; P.bnb_b = f.b; P.bnb_mean = f.mean; P.bnb_invstd = f.invstd;
-      P.bnb_part = f.part;
-      *f.tiles_out = (int)tiles;
-    }
-  }
-  if (tall) return launch_rs_cfg<8>(P, o, s);
-  return launch_rs_cfg<4>(P, o, s);
+// rows8: 16 x 32-pixel tiles, else 16 x 16
+int launch_conv3x3_rs(BConvP& P, bool rows8, const LaunchOpts& o, hipStream_t s) {
+  return rows8 ? launch_rs_cfg<8>(P, o, s) : launch_rs_cfg<4>(P, o, s);
 }
 
 }  // namespace fu

@@ -490,7 +490,9 @@ void fu_test_force_general_conv(int on);
 void fu_test_force_lockstep_wgrad(int on);
 /* Testing hook: workgroup tile of the aligned-shape bf16 conv kernel at 64 output channels: 0 = heuristic (default),
  * 1 = never the tall 16x32-pixel tile (nor the row-stationary kernel), 2 = the tall tile wherever 64-channel tiles run,
- * 3 = the row-stationary kernel (fu_conv_rs.hip) wherever the shape is eligible.  Process-wide. */
+ * 3 = the row-stationary kernel (fu_conv_rs.hip) wherever the shape is eligible, 4 = the persistent ping-pong kernel
+ * (fu_conv_pp.hip) wherever the shape is eligible.  Modes 1-4 also keep the first conv off its 8-channel kernel; the
+ * one-tap and the general kernel's launches are not affected.  Process-wide. */
 void fu_test_conv_tile_mode(int mode);
 /* Testing hook: on != 0 computes every BatchNorm-backward pair of sums with its own reduce pass; by default the 16-bit
  * modes take them from the kernel that produces the gradient where it can (row-stationary dgrad, head backward).
@@ -503,6 +505,19 @@ void fu_test_head_store_g(int on);
  * instead of the 1-tap instantiation of the fast kernel; the other eight taps multiply exact zeros, so the results are
  * bit-identical.  Process-wide. */
 void fu_test_force_full_taps(int on);
+
+/* Testing hook: which kernel a 16-bit 3x3 conv launch of these shapes runs under the switches currently set -- the launcher's
+ * own decision, asked without a launch (no HIP call: works without a GPU).  kind 0 = forward (bias and statistics), 1 =
+ * dgrad (want_bnsums: the launch is asked for fused BatchNorm-backward sums), 2 = weight gradient (D0 = c_out; D1 and
+ * want_bnsums ignored).  has_bn0: source 0 carries a BatchNorm + ReLU prologue; C1 / D1 = 0: no second source /
+ * destination.  Returns the route id (-1: unknown kind); fu_test_conv_route_name names it ("pp", "rs8", "fast32", ...). */
+int fu_test_conv_route(int kind, int C0, int has_bn0, int C1, int D0, int D1, int center_only, int want_bnsums, int B,
+                       int H, int W);
+const char* fu_test_conv_route_name(int kind, int route);
+/* Testing hook: the weight-gradient route as above, the split-K slab elements its launch writes (used_elems) and the
+ * bound the workspace is sized from (bound_elems). */
+int fu_test_wgrad_slab(int C0, int has_bn0, int C1, int Cout, int center_only, int B, int H, int W, int64_t* used_elems,
+                       int64_t* bound_elems);
 
 /* Testing hook: every BatchNorm-backward pair of sums that a producer kernel emitted (row-stationary dgrad epilogue, head
  * backward) is multiplied by `factor` before it is consumed -- the negative control of the parity tests (a wrong fused sum

@@ -16,7 +16,13 @@ running statistics), batch 2 of 32 x 32 in fp32 / bf16 / fp16 with bilinear upsa
 (base 64, the only width fu_create takes it at); a 37 x 45 bf16 tile (the pad path); a two-encoder late-fusion net in bf16;
 a bf16 step driven block by block (fu_set_side_stream(2), fu_backward_block, fu_backward_join); an eval fu_forward_srcs of
 two sources; fu_forward_views + fu_merge_views over the four flip codes.
-Arguments: the groups to run (losses, optimiser, steps; all three by default).  Prints one JSON line."""
+Convs: what fu_op_conv3x3_fwd, _dgrad, _dgrad_bnsums and _wgrad write, bf16 and fp16, at the smallest shapes that reach each
+kernel route (tests/test_conv_route_cpu.py names them): 64 -> 64 at 64 x 64 under tile modes 3 (rs4) and 4 (pp: eight 16 x 32
+tiles), 8 -> 64 at 16 x 16 and 64 x 16 (the two c8 variants), 16 -> 24 at 37 x 45 by default (fast) and on the general kernel,
+the weight gradient with 8, 64 and 128 input channels under each fu_test_force_lockstep_wgrad mode; under the default
+dispatch 32 -> 64 at 256 x 256, B = 2 (exactly 512 workgroups) and a dgrad with fused sums below 256 input channels.  The
+one-tap kernels have no operator of their own: a late-fusion step of base 8 runs them with 16 ... 128 input channels.
+Arguments: the groups to run (losses, optimiser, steps, convs; all four by default).  Prints one JSON line."""
 import ctypes as C
 import hashlib
 import json
@@ -38,6 +44,8 @@ ADAM = (1e-3, 0.9, 0.999, 1e-8)
 def digest(*tensors):
     h = hashlib.sha256()
     for t in tensors:
+        if t.dtype in (torch.bfloat16, torch.float16):
+            t = t.view(torch.int16)
         h.update(t.detach().cpu().contiguous().numpy().tobytes())
     return h.hexdigest()
 
@@ -161,15 +169,89 @@ def steps(lib, out):
     out["eval/bf16/views4/32x32"] = digest(logits, probs, counts)
 
 
+def convs(lib, out):
+    ptr, check = _lib.ptr, _lib.check
+    s = torch.cuda.current_stream().cuda_stream
+
+    def operands(dt, B, C0, Cout, H, W):
+        g = torch.Generator().manual_seed(B + C0 + Cout + H + W)
+        r = lambda *shape: torch.randn(*shape, generator=g)
+        t = {"x": r(B, H, W, C0).to(DEV).to(dt), "dy": r(B, H, W, Cout).to(DEV).to(dt), "y": r(B, H, W, C0).to(DEV).to(dt),
+             "w": (r(Cout, C0, 3, 3) / (3.0 * C0 ** 0.5)).to(DEV), "bias": r(Cout).to(DEV),
+             "a": (torch.rand(C0, generator=g) + 0.5).to(DEV), "b": (r(C0) * 0.1).to(DEV),
+             "mean": (r(C0) * 0.1).to(DEV), "invstd": (torch.rand(C0, generator=g) + 0.5).to(DEV)}
+        return t
+
+    def fwd(code, dt, B, C0, Cout, H, W, bn):
+        t = operands(dt, B, C0, Cout, H, W)
+        y, ssum, ssq = torch.zeros(B, H, W, Cout, device=DEV, dtype=dt), torch.zeros(Cout, device=DEV), torch.zeros(Cout, device=DEV)
+        check(lib.fu_op_conv3x3_fwd(code, ptr(t["x"]), C0, ptr(t["a"]) if bn else None, ptr(t["b"]) if bn else None, None, 0,
+                                    ptr(t["w"]), ptr(t["bias"]), ptr(y), Cout, B, H, W, ptr(ssum), ptr(ssq), s))
+        return digest(y, ssum, ssq)
+
+    def dgrad(code, dt, B, C0, Cout, H, W, sums):
+        t = operands(dt, B, C0, Cout, H, W)
+        dx, s1, s2 = torch.zeros(B, H, W, C0, device=DEV, dtype=dt), torch.zeros(C0, device=DEV), torch.zeros(C0, device=DEV)
+        if sums:
+            check(lib.fu_op_conv3x3_dgrad_bnsums(code, ptr(t["dy"]), Cout, ptr(t["w"]), ptr(dx), C0, ptr(t["y"]), ptr(t["a"]),
+                                                 ptr(t["b"]), ptr(t["mean"]), ptr(t["invstd"]), ptr(s1), ptr(s2), B, H, W, s))
+        else:
+            check(lib.fu_op_conv3x3_dgrad(code, ptr(t["dy"]), Cout, ptr(t["w"]), ptr(dx), C0, None, 0, B, H, W, s))
+        return digest(dx, s1, s2)
+
+    def wgrad(code, dt, B, C0, Cout, H, W, bn):
+        t = operands(dt, B, C0, Cout, H, W)
+        dw = torch.zeros(Cout, C0, 3, 3, device=DEV)
+        check(lib.fu_op_conv3x3_wgrad(code, ptr(t["x"]), C0, ptr(t["a"]) if bn else None, ptr(t["b"]) if bn else None, None, 0,
+                                      ptr(t["dy"]), Cout, ptr(dw), B, H, W, s))
+        return digest(dw)
+
+    try:
+        for code, dt, nm in ((_lib.FU_BF16, torch.bfloat16, "bf16"), (_lib.FU_F16, torch.float16, "fp16")):
+            for mode in (3, 4):
+                lib.fu_test_conv_tile_mode(mode)
+                out[f"conv/{nm}/mode{mode}/fwd/64x64"] = fwd(code, dt, 1, 64, 64, 64, 64, True)
+                out[f"conv/{nm}/mode{mode}/dgrad/64x64"] = dgrad(code, dt, 1, 64, 64, 64, 64, False)
+                out[f"conv/{nm}/mode{mode}/dgrad_bnsums/64x64"] = dgrad(code, dt, 1, 64, 64, 64, 64, True)
+            lib.fu_test_conv_tile_mode(0)
+            for H in (16, 64):
+                out[f"conv/{nm}/c8/fwd/{H}x16"] = fwd(code, dt, 1, 8, 64, H, 16, False)
+            for general in (0, 1):
+                lib.fu_test_force_general_conv(general)
+                out[f"conv/{nm}/general{general}/fwd/37x45"] = fwd(code, dt, 2, 16, 24, 37, 45, True)
+                out[f"conv/{nm}/general{general}/dgrad/37x45"] = dgrad(code, dt, 2, 16, 24, 37, 45, False)
+            lib.fu_test_force_general_conv(0)
+            for lock in (0, 1, 2):
+                lib.fu_test_force_lockstep_wgrad(lock)
+                out[f"conv/{nm}/lock{lock}/wgrad/c8"] = wgrad(code, dt, 1, 8, 64, 16, 32, False)
+                out[f"conv/{nm}/lock{lock}/wgrad/c64"] = wgrad(code, dt, 1, 64, 64, 32, 32, True)
+                out[f"conv/{nm}/lock{lock}/wgrad/c128"] = wgrad(code, dt, 1, 128, 64, 32, 32, True)
+                out[f"conv/{nm}/lock{lock}/wgrad/37x45"] = wgrad(code, dt, 2, 16, 24, 37, 45, True)
+            lib.fu_test_force_lockstep_wgrad(0)
+            out[f"conv/{nm}/default/fwd/512wg"] = fwd(code, dt, 2, 32, 64, 256, 256, True)
+            out[f"conv/{nm}/default/dgrad/512wg"] = dgrad(code, dt, 2, 64, 32, 256, 256, False)
+            out[f"conv/{nm}/default/dgrad_bnsums/c64"] = dgrad(code, dt, 2, 64, 64, 256, 256, True)
+            torch.manual_seed(15)
+            x, tgt = torch.rand(2, 5, 32, 32, device=DEV), torch.randint(0, 3, (2, 32, 32), device=DEV)
+            net = HipLateFusion({"ms_image": 3, "dem": 2}, 3, base_channels=8, precision=nm).to(DEV).train()
+            out[f"conv/{nm}/one_tap/latefusion2"] = train_step(lib, net, x, tgt)
+    finally:
+        lib.fu_test_conv_tile_mode(0)
+        lib.fu_test_force_general_conv(0)
+        lib.fu_test_force_lockstep_wgrad(0)
+
+
 def main():
     lib, out = _lib.load(), {}
-    groups = sys.argv[1:] or ["losses", "optimiser", "steps"]
+    groups = sys.argv[1:] or ["losses", "optimiser", "steps", "convs"]
     if "losses" in groups:
         losses(lib, out)
     if "steps" in groups:
         steps(lib, out)
     if "optimiser" in groups:
         optimiser(lib, out)
+    if "convs" in groups:
+        convs(lib, out)
     torch.cuda.synchronize()
     out["all"] = hashlib.sha256(json.dumps(out, sort_keys=True).encode()).hexdigest()
     print(json.dumps(out, sort_keys=True))
