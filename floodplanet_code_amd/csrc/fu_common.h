@@ -434,21 +434,32 @@ int launch_gather_views_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B,
 
 // BN: finalize forward statistics.  partials [nTiles][C][2]; count = B*H*W.
 // training: writes mean/invstd/a/b, updates running stats (momentum 0.1, unbiased var) and nbt.
-int launch_bn_finalize(const float* partials, int nTiles, int C, int64_t count, const float* conv_bias,
-                       const float* gamma, const float* beta, float eps, float momentum, float* mean, float* invstd,
-                       float* a, float* b, float* running_mean, float* running_var, int64_t* nbt, double* dscratch,
+struct BnFwdOut {
+  const float* conv_bias; const float* gamma; const float* beta; float eps, momentum;
+  float *mean, *invstd, *a, *b, *rmean, *rvar; int64_t* nbt;
+};
+int launch_bn_finalize(const BnFwdOut& o, const float* partials, int nTiles, int C, int64_t count, double* dscratch,
                        hipStream_t s);
 // fp64 scratch needed by the two-level reductions: elements for a layer with C channels
 static inline int64_t reduce_scratch_elems(int C) { return (int64_t)32 * C * 2; }
 // backward: g (in place -> dy).  Two launches + finalize inside.  partials scratch: >= bn_bwd_partial_elems.
 int64_t bn_bwd_partial_elems(int C, int64_t npix);
-// g_pool != null: y's 2x2 max-pool ran in forward and g_pool [B, H/2, W/2, C] is dL/d(pooled): the pool's backward is folded
-// into the two passes (g is then the skip gradient only)
-int launch_bn_bwd(Prec p, void* g, const void* y, int C, int64_t npix, const float* a, const float* b,
-                  const float* mean, const float* invstd, const float* gamma, float* dgamma, float* dbeta,
-                  float* partials, float* coef, float* db_partials, int* n_db_partials, double* dscratch,
-                  hipStream_t s, const void* g_pool = nullptr, int B = 0, int H = 0, int W = 0, int ext_partials = 0,
-                  const HeadGrad* head = nullptr);
+struct BnBwdOut { const float* unscale; float *dgamma, *dbeta, *coef; };
+struct BnBwdArgs {
+  void* g = nullptr; const void* y = nullptr;          // NHWC [npix][C]
+  int C = 0; int64_t npix = 0;
+  const float *a = nullptr, *b = nullptr, *mean = nullptr, *invstd = nullptr;
+  float *dgamma = nullptr, *dbeta = nullptr;
+  float *partials = nullptr, *coef = nullptr;          // scratch: the two sums per block; [C][2] s1/N, s2/N
+  float* db_partials = nullptr; int* n_db_partials = nullptr;   // out: per-block sums of dy (the conv's bias gradient) and their count
+  double* dscratch = nullptr;
+  // optional.  g_pool != null: y's 2x2 max-pool ran in forward and g_pool [B, H/2, W/2, C] is dL/d(pooled): the pool's backward
+  // is folded into the two passes (g is then the skip gradient only); B, H, W are needed with it
+  const void* g_pool = nullptr; int B = 0, H = 0, W = 0;
+  int ext_partials = 0;                                // > 0: `partials` already holds that many rows (BnbFuse)
+  const HeadGrad* head = nullptr;                      // g is recomputed from the head's dl and w instead of read
+};
+int launch_bn_bwd(Prec p, const BnBwdArgs& A, hipStream_t s);
 
 int launch_maxpool2(Prec p, const void* src, const float* a, const float* b, void* dst, int B, int H, int W, int C,
                     hipStream_t s);

@@ -240,8 +240,14 @@ int fu_op_bn_bwd(int precision, void* g, const void* y, int C, int B, int H, int
   FU_TRY(dbp.get((size_t)bn_bwd_partial_elems(C, npix) * sizeof(float)));
   FU_TRY(scr.get((size_t)reduce_scratch_elems(std::max(C, 64)) * sizeof(double)));
   int ndb = 0;
-  FU_TRY(launch_bn_bwd(p, g, y, C, npix, bn_a, bn_b, mean, invstd, nullptr, dgamma, dbeta, (float*)part.p,
-                       (float*)coef.p, (float*)dbp.p, &ndb, (double*)scr.p, s, g_pool, B, H, W, 0));
+  BnBwdArgs A;
+  A.g = g; A.y = y; A.C = C; A.npix = npix;
+  A.a = bn_a; A.b = bn_b; A.mean = mean; A.invstd = invstd;
+  A.dgamma = dgamma; A.dbeta = dbeta;
+  A.partials = (float*)part.p; A.coef = (float*)coef.p; A.db_partials = (float*)dbp.p; A.n_db_partials = &ndb;
+  A.dscratch = (double*)scr.p;
+  A.g_pool = g_pool; A.B = B; A.H = H; A.W = W;
+  FU_TRY(launch_bn_bwd(p, A, s));
   FU_HIP_CHECK(hipStreamSynchronize(s));
   return FU_OK;
 }

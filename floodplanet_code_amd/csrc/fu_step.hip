@@ -60,10 +60,14 @@ static int conv_fwd(fu_ctx* c, int i, int j, int B, bool training, hipStream_t s
   FU_TRY(launch_conv3x3(c->prec, in, v.wf, training ? P(c, v.p_b) : v.fold_bias, v.y, v.cout, nullptr, 0,
                         training ? c->stats : nullptr, &nt, B, H, W, s));
   const int64_t off = c->bns[v.bn].off;
-  if (training)
-    FU_TRY(launch_bn_finalize(c->stats, nt, v.cout, (int64_t)B * H * W, P(c, v.p_b), P(c, v.p_g), P(c, v.p_beta),
-                              BN_EPS, BN_MOMENTUM, v.mean, v.invstd, v.a, v.b, c->RM + off, c->RV + off,
-                              c->NBT + v.bn, c->dscratch, s));
+  if (training) {
+    BnFwdOut o;
+    o.conv_bias = P(c, v.p_b); o.gamma = P(c, v.p_g); o.beta = P(c, v.p_beta);
+    o.eps = BN_EPS; o.momentum = BN_MOMENTUM;
+    o.mean = v.mean; o.invstd = v.invstd; o.a = v.a; o.b = v.b;
+    o.rmean = c->RM + off; o.rvar = c->RV + off; o.nbt = c->NBT + v.bn;
+    FU_TRY(launch_bn_finalize(o, c->stats, nt, v.cout, (int64_t)B * H * W, c->dscratch, s));
+  }
   return 0;
 }
 
@@ -196,9 +200,15 @@ static int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
   const int par = c->wg_parity;
   float* dbp = (side && par) ? c->db_part2 : c->db_part;
   if (side && c->wg_pending[par]) FU_HIP_CHECK(hipStreamWaitEvent(s, c->ev_wg[par], 0));   // buffer free again
-  FU_TRY(launch_bn_bwd(c->prec, v.gy, v.y, v.cout, npix, v.a, v.b, v.mean, v.invstd, P(c, v.p_g), G(c, v.p_g),
-                       G(c, v.p_beta), c->bnb_part, v.coef, dbp, &ndb, c->dscratch, s, v.pool_g, B, H, W, v.bnb_tiles,
-                       v.head.dl ? &v.head : nullptr));
+  BnBwdArgs A;
+  A.g = v.gy; A.y = v.y; A.C = v.cout; A.npix = npix;
+  A.a = v.a; A.b = v.b; A.mean = v.mean; A.invstd = v.invstd;
+  A.dgamma = G(c, v.p_g); A.dbeta = G(c, v.p_beta);
+  A.partials = c->bnb_part; A.coef = v.coef; A.db_partials = dbp; A.n_db_partials = &ndb; A.dscratch = c->dscratch;
+  A.g_pool = v.pool_g; A.B = B; A.H = H; A.W = W;
+  A.ext_partials = v.bnb_tiles;
+  A.head = v.head.dl ? &v.head : nullptr;
+  FU_TRY(launch_bn_bwd(c->prec, A, s));
   v.pool_g = nullptr;
   v.bnb_tiles = 0;
   v.head = HeadGrad{};

@@ -58,7 +58,7 @@ def test_wrong_restatements_are_not_aten():
 
 
 def test_the_rows_meant_for_the_four_row_variant_reach_its_threshold():
-    """Host arithmetic of launch_upsample2 (fu_elementwise.hip): ceil(outW * CV / 256) * ceil(outH / 4) * B >= 2048 selects
+    """Host arithmetic of launch_upsample2 (fu_resample.hip): ceil(outW * CV / 256) * ceil(outH / 4) * B >= 2048 selects
     k_upsample2<T, 4>.  The 16-bit runs double C on these rows, so CV (channel vectors per pixel) is 16 in every precision."""
     for shape in ROWS4:
         assert rows4_workgroups(shape, 4) >= 2048, shape

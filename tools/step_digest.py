@@ -22,7 +22,14 @@ tiles), 8 -> 64 at 16 x 16 and 64 x 16 (the two c8 variants), 16 -> 24 at 37 x 4
 the weight gradient with 8, 64 and 128 input channels under each fu_test_force_lockstep_wgrad mode; under the default
 dispatch 32 -> 64 at 256 x 256, B = 2 (exactly 512 workgroups) and a dgrad with fused sums below 256 input channels.  The
 one-tap kernels have no operator of their own: a late-fusion step of base 8 runs them with 16 ... 128 input channels.
-Arguments: the groups to run (losses, optimiser, steps, convs; all four by default).  Prints one JSON line."""
+BN: fu_op_bn_bwd (dL/dy, dgamma, dbeta) in fp32 / bf16 / fp16 at 12 x 5 x 7 (C / 4 = 3 does not divide the block: one thread
+without a pixel row), 8 x 5 x 7 pooled (windows without a pool output) and 2 x 64 x 32 x 48 plain and pooled; fu_op_head_bwd with
+the fused BatchNorm-backward sums in bf16 / fp16 at C = 64 with 2, 3 and 5 classes (the two compile-time class counts and the
+run-time one); one base-8 training step in fp32 and in bf16 under fu_set_exact_sync with world = 2 in this one process -- the
+hook doubles the exchange buffer in place on the call's stream, i.e. two identical ranks -- which is the only way to
+k_bn_finalize / k_bn_bwd_finalize without a second GPU.  (The head-recompute apply, k_bn_bwd_apply_head, already runs in the
+steps group: every 16-bit base-8 step there has 8 | base channels, so its head backward skips the store of g.)
+Arguments: the groups to run (losses, optimiser, steps, convs, bn; all five by default).  Prints one JSON line."""
 import ctypes as C
 import hashlib
 import json
@@ -241,9 +248,63 @@ def convs(lib, out):
         lib.fu_test_force_lockstep_wgrad(0)
 
 
+def bn(lib, out):
+    ptr, check = _lib.ptr, _lib.check
+    s = torch.cuda.current_stream().cuda_stream
+    precs = ((_lib.FU_F32, torch.float32, "fp32"), (_lib.FU_BF16, torch.bfloat16, "bf16"), (_lib.FU_F16, torch.float16, "fp16"))
+
+    def coefficients(g, Cc):
+        r = lambda *shape: torch.randn(*shape, generator=g)
+        return [t.to(DEV) for t in (torch.rand(Cc, generator=g) + 0.5, r(Cc) * 0.1, r(Cc) * 0.1, torch.rand(Cc, generator=g) + 0.5)]
+
+    for code, dt, nm in precs:
+        for (B, Cc, H, W), pooled in (((1, 12, 5, 7), False), ((1, 8, 5, 7), True), ((2, 64, 32, 48), False), ((2, 64, 32, 48), True)):
+            g = torch.Generator().manual_seed(B + Cc + H + W + pooled)
+            y, gy = (torch.randn(B, H, W, Cc, generator=g).to(DEV).to(dt) for _ in range(2))
+            gp = torch.randn(B, H // 2, W // 2, Cc, generator=g).to(DEV).to(dt) if pooled else None
+            a, b, mean, invstd = coefficients(g, Cc)
+            dgamma, dbeta = torch.zeros(Cc, device=DEV), torch.zeros(Cc, device=DEV)
+            check(lib.fu_op_bn_bwd(code, ptr(gy), ptr(y), Cc, B, H, W, ptr(a), ptr(b), ptr(mean), ptr(invstd), ptr(gp),
+                                   ptr(dgamma), ptr(dbeta), s))
+            out[f"bn/{nm}/bn_bwd/{B}x{Cc}x{H}x{W}/{'pooled' if pooled else 'plain'}"] = digest(gy, dgamma, dbeta)
+    for code, dt, nm in precs[1:]:
+        for ncls in (2, 3, 5):
+            Cc, npix = 64, 2 * 40 * 48
+            g = torch.Generator().manual_seed(ncls)
+            y = torch.randn(npix, Cc, generator=g).to(DEV).to(dt)
+            dl, w = (torch.randn(npix, ncls, generator=g) * 1e-3).to(DEV), (torch.randn(ncls, Cc, generator=g) * 0.2).to(DEV)
+            a, b, mean, invstd = coefficients(g, Cc)
+            gout = torch.zeros(npix, Cc, device=DEV, dtype=dt)
+            dw, db, s1, s2 = (torch.zeros(n, device=DEV) for n in (ncls * Cc, ncls, Cc, Cc))
+            check(lib.fu_op_head_bwd(code, ptr(dl), ptr(y), ptr(a), ptr(b), ptr(w), Cc, ncls, npix, ptr(gout), ptr(dw), ptr(db),
+                                     ptr(mean), ptr(invstd), ptr(s1), ptr(s2), s))
+            out[f"bn/{nm}/head_bwd_sums/c{ncls}"] = digest(gout, dw, db, s1, s2)
+    for prec in ("fp32", "bf16"):
+        torch.manual_seed(16)
+        x, tgt = torch.rand(2, 4, 32, 32, device=DEV), torch.randint(0, 3, (2, 32, 32), device=DEV)
+        net = HipUNet(4, 3, base_channels=8, precision=prec).to(DEV).train()
+        ctx = net._get_ctx(DEV, 2, 32, 32)
+        nbytes = int(lib.fu_exact_sync_bytes(ctx))
+        xbuf = torch.zeros(nbytes // 8 + 1, dtype=torch.float64, device=DEV)
+        calls = []
+
+        def hook(_user, n_elems, is_double):
+            (xbuf[:n_elems] if is_double else xbuf.view(torch.float32)[:n_elems]).mul_(2)     # two identical ranks, summed
+            calls.append(n_elems)
+            return 0
+
+        cb = _lib.SYNC_HOOK(hook)
+        check(lib.fu_set_exact_sync(ctx, cb, None, 2, ptr(xbuf), nbytes))
+        try:
+            out[f"bn/{prec}/exact_sync_world2/32x32"] = train_step(lib, net, x, tgt)
+        finally:
+            check(lib.fu_set_exact_sync(ctx, _lib.SYNC_HOOK(0), None, 1, None, 0))
+        assert len(calls) >= 2 * len(net._bn), calls      # every BatchNorm's forward and backward sums went through the hook
+
+
 def main():
     lib, out = _lib.load(), {}
-    groups = sys.argv[1:] or ["losses", "optimiser", "steps", "convs"]
+    groups = sys.argv[1:] or ["losses", "optimiser", "steps", "convs", "bn"]
     if "losses" in groups:
         losses(lib, out)
     if "steps" in groups:
@@ -252,6 +313,8 @@ def main():
         optimiser(lib, out)
     if "convs" in groups:
         convs(lib, out)
+    if "bn" in groups:
+        bn(lib, out)
     torch.cuda.synchronize()
     out["all"] = hashlib.sha256(json.dumps(out, sort_keys=True).encode()).hexdigest()
     print(json.dumps(out, sort_keys=True))
