@@ -390,7 +390,7 @@ int launch_wgrad_reduce_oihw(const float* slab, int S, int Cin, int Cout, int ci
 // the split-K plan of the fp32 weight-gradient kernel (fu_conv_f32.hip, in its tile sizes)
 void wgrad_split_shared(int Cin, int Cout, int B, int H, int W, int* nPix, int* S, int* perSplit);
 
-// precision-specific implementations (fu_conv_f32.hip / fu_conv_bf16.hip)
+// precision-specific implementations (fu_conv_f32.hip / fu_conv_bf16.hip; the 16-bit weight gradient: fu_wgrad_bf16.hip)
 int conv3x3_num_stat_tiles_f32(int B, int H, int W);
 int launch_conv3x3_f32(const ConvIn& in, const float* wpk, const float* bias, float* dst0, int D0, float* dst1, int D1,
                        float* stats, int* n_stat_tiles, int B, int H, int W, hipStream_t s);

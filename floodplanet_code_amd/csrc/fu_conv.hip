@@ -1,5 +1,5 @@
 // What the 3x3 convolutions of all three precisions share (compiled once): the dispatch on the context's precision
-// to fu_conv_f32.hip / fu_conv_bf16.hip (the latter compiled a second time for fp16), and the tail of every
+// to fu_conv_f32.hip / fu_conv_bf16.hip + fu_wgrad_bf16.hip (the latter two compiled a second time for fp16), and the tail of every
 // weight-gradient launch, which sums the split-K slabs in a fixed order into fp32 OIHW and the bias gradient.
 #include "fu_common.h"
 #include "fu_conv_bf16.h"

@@ -1,6 +1,8 @@
-// Private declarations shared by the 16-bit convolution translation units (fu_conv_bf16.hip, fu_conv_bf16_fast.hip).
+// Private declarations shared by the five 16-bit convolution translation units: fu_conv_bf16.hip (weight pack, general
+// forward / dgrad kernel, the forward route conv3x3_route), fu_conv_bf16_fast.hip, fu_conv_rs.hip, fu_conv_pp.hip (the
+// aligned-shape kernels) and fu_wgrad_bf16.hip (the weight gradient, conv3x3_wgrad_route and conv3x3_wgrad_plan).
 //
-// ONE source, TWO element types.  The Makefile compiles both files twice: as they stand (bf16: v_mfma_f32_32x32x16_bf16) and
+// ONE source, TWO element types.  The Makefile compiles every one of them twice: as they stand (bf16: v_mfma_f32_32x32x16_bf16) and
 // with -DFU_HALF=1 (IEEE fp16: v_mfma_f32_32x32x16_f16, the same MFMA rate).  Tiles, LDS images, schedules, address math
 // and the transposing reads are identical -- a 16-bit element is a 16-bit element -- so the only things that change are
 // the four conversions (f2e / e2f_lo / e2f_hi / pack_e2), the fragment vector type and the MFMA / ds_read_tr builtins,
@@ -96,6 +98,30 @@ __device__ __forceinline__ unsigned bn_relu_pair(unsigned v, f32x2 a, f32x2 b) {
   return pack_e2(f32x2{lo, hi});
 }
 
+// relu(a * x + b) on the eight channels of one 16-byte unit (the staging of the general kernel and of the weight gradient)
+__device__ __forceinline__ uint4 bn_relu_pack8(uint4 v, const float4& a0, const float4& a1, const float4& b0,
+                                               const float4& b1) {
+  float x[8];
+  x[0] = e2f_lo(v.x); x[1] = e2f_hi(v.x);
+  x[2] = e2f_lo(v.y); x[3] = e2f_hi(v.y);
+  x[4] = e2f_lo(v.z); x[5] = e2f_hi(v.z);
+  x[6] = e2f_lo(v.w); x[7] = e2f_hi(v.w);
+  x[0] = bn_act_fused(a0.x, x[0], b0.x); x[1] = bn_act_fused(a0.y, x[1], b0.y);
+  x[2] = bn_act_fused(a0.z, x[2], b0.z); x[3] = bn_act_fused(a0.w, x[3], b0.w);
+  x[4] = bn_act_fused(a1.x, x[4], b1.x); x[5] = bn_act_fused(a1.y, x[5], b1.y);
+  x[6] = bn_act_fused(a1.z, x[6], b1.z); x[7] = bn_act_fused(a1.w, x[7], b1.w);
+  uint4 o;
+  o.x = (unsigned)f2e(x[0]) | ((unsigned)f2e(x[1]) << 16);
+  o.y = (unsigned)f2e(x[2]) | ((unsigned)f2e(x[3]) << 16);
+  o.z = (unsigned)f2e(x[4]) | ((unsigned)f2e(x[5]) << 16);
+  o.w = (unsigned)f2e(x[6]) | ((unsigned)f2e(x[7]) << 16);
+  return o;
+}
+
+// Workgroup barrier behind this wave's LDS traffic only (lgkmcnt), then s_barrier.  __syncthreads() also waits with vmcnt(0),
+// i.e. for global loads that were issued to stay in flight across the barrier.
+__device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 #endif
 
 // forward / dgrad launch parameters (see launch_conv3x3_bf16)
@@ -169,7 +195,7 @@ struct ConvHooks {
 extern ConvHooks g_conv_hooks;
 
 // Which kernel instantiation a forward / dgrad launch runs (conv3x3_route, fu_conv_bf16.hip: every preference and its
-// measurement) and which a weight gradient (conv3x3_wgrad_route).  Pure host functions of the shapes and of which pointers
+// measurement) and which a weight gradient (conv3x3_wgrad_route, fu_wgrad_bf16.hip).  Pure host functions of the shapes and of which pointers
 // are null; fu_test_conv_route (fu_conv.hip) answers from them without a GPU.
 enum ConvRoute {
   CONV_GENERAL_64, CONV_GENERAL_32, CONV_TAP1_64, CONV_TAP1_32, CONV_C8, CONV_PP, CONV_RS8, CONV_RS4, CONV_FAST_TALL,

@@ -564,10 +564,9 @@ __global__ __launch_bounds__(512) void k_conv3x3_bf16_pp(BConvP P) {
   // and puts s_waitcnt vmcnt(0) in front of the first ds_write of the next MFMA phase, i.e. waits for the loads that were
   // issued to stay in flight for two phases.
   auto vm_wait5 = []() __attribute__((always_inline)) { __builtin_amdgcn_s_waitcnt(5 | (7 << 4) | (15 << 8)); };
-  // Workgroup barrier of the loop: LDS traffic of this wave done (lgkmcnt), then s_barrier.  __syncthreads() also waits with
+  // Workgroup barrier of the loop, wg_barrier(): LDS traffic of this wave done (lgkmcnt), then s_barrier.  __syncthreads() also waits with
   // vmcnt(0) -- for the activation loads that were issued to stay in flight across two phases (and for the epilogue's stores).
   // The LDS-DMA pieces, which do count in vmcnt, are waited for explicitly where they are issued.
-  auto wg_barrier = []() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   // ---- prologue: coefficient tables, step 0 (both groups convert their halves and DMA the other's weights), the loads of
   //      steps 1 and 2; group 1 then DMAs group 0's weights of step 1 while group 0 runs its first MFMA phase
   if constexpr (BN) {

@@ -1,6 +1,7 @@
 """GPU: single HIP operators (through the C ABI's fu_op_* entry points) against torch-CPU fp32 references of
 the same op as used in unet.py (F.conv2d / batch-norm+relu prologue / max_pool2d / bilinear upsample)."""
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -289,6 +290,12 @@ def test_conv3x3_bf16_dgrad(shape, conv_path, lowp):
     assert rel_err(got, ref) < _cur["eps"]
 
 
+# 256 -> 128 at 80 x 80, B = 2: 100 pixel tiles of 8 x 16 (5 tile columns: interior tiles, whole-tile staging), 4 channel tiles,
+# 34 splits.  33 splits get three stages -- the parity-unrolled loop of the ping-pong kernel leaves at its odd exit after a
+# full round -- and one split a single stage; every other Cin > 64 shape here has 1 or 2 stages per workgroup.
+WGRAD_THREE_STAGES = (2, 256, 0, 128, 80, 80, True)
+
+
 @pytest.fixture(params=["auto", "lockstep"])
 def wgrad_path(request):
     """bf16 wgrad of c_in > 64 has a ping-pong kernel and a lock-step one: run every shape on both."""
@@ -302,10 +309,12 @@ def wgrad_path(request):
                                    (16, 128, 0, 128, 32, 32, True), (3, 256, 0, 72, 19, 50, True),
                                    (1, 128, 128, 64, 8, 16, True), (2, 64, 64, 64, 32, 64, True),
                                    (2, 256, 0, 128, 32, 64, False), (1, 128, 0, 64, 24, 48, True),
-                                   (3, 64, 192, 64, 16, 16, True)])
+                                   (3, 64, 192, 64, 16, 16, True), WGRAD_THREE_STAGES])
 def test_bf16_wgrad_pingpong_kernel_is_bit_identical_to_lockstep(shape, lowp):
     """Three routes to the same sums: ping-pong kernel with whole-tile staging (where eligible), ping-pong kernel with the
-    general staging, lock-step kernel.  Shapes cover interior and border tiles, a channel tile straddling two sources, no BN."""
+    general staging, lock-step kernel.  Shapes cover interior and border tiles, a channel tile straddling two sources, no BN.
+    The three kernels run one fragment walk (wgrad_walk, fu_wgrad_bf16.hip), so this test does not check the walk itself:
+    test_conv3x3_bf16_wgrad does, against torch."""
     B, C0, C1, Cout, H, W, bn = shape
     lib = _lib.load()
     x0, x1, a, b, w, bias, _ = make_conv_case(*shape, seed=5)
@@ -358,10 +367,12 @@ def test_bf16_wgrad_first_conv_kernel(shape, lowp):
         assert rel_err(outs[0], ref) < 1e-4
 
 
-@pytest.mark.parametrize("shape", BF_SHAPES)
-def test_conv3x3_bf16_wgrad(shape, wgrad_path, lowp):
+@functools.lru_cache(maxsize=2)
+def wgrad_case(shape, lowp):
+    """operands and the torch reference of test_conv3x3_bf16_wgrad: the same for both wgrad_path values, computed once.
+    bf() rounds to the element type in _cur, which the test's `lowp` fixture has set before the call: `lowp` is in the key for
+    that reason and must stay there."""
     B, C0, C1, Cout, H, W, bn = shape
-    lib = _lib.load()
     x0, x1, a, b, w, bias, _ = make_conv_case(*shape, seed=2)
     x0r = bf(x0)
     xin = bf(torch.relu(x0r * a.view(1, -1, 1, 1) + b.view(1, -1, 1, 1))) if bn else x0r
@@ -370,6 +381,14 @@ def test_conv3x3_bf16_wgrad(shape, wgrad_path, lowp):
     g = torch.Generator().manual_seed(3)
     dy = torch.randn(B, Cout, H, W, generator=g)
     ref = torch.nn.grad.conv2d_weight(xin, w.shape, bf(dy), padding=1)
+    return x0, x1, a, b, w, dy, ref
+
+
+@pytest.mark.parametrize("shape", BF_SHAPES + [WGRAD_THREE_STAGES])
+def test_conv3x3_bf16_wgrad(shape, wgrad_path, lowp):
+    B, C0, C1, Cout, H, W, bn = shape
+    lib = _lib.load()
+    x0, x1, a, b, w, dy, ref = wgrad_case(shape, lowp)
     dw = torch.full(w.shape, float("nan"), device=DEV)
     d0, d1, ddy = nhwc_bf(x0), (nhwc_bf(x1) if x1 is not None else None), nhwc_bf(dy)
     da, db = (a.to(DEV), b.to(DEV)) if bn else (None, None)

@@ -32,8 +32,8 @@ def ceil_div(a, b):
 
 
 def split_count(B, C0, C1, Cout, H, W, bn):
-    """S of launch_conv3x3_wgrad_bf16 for this shape (fu_conv_bf16.hip: launch_wgrad_c8 / launch_wgrad_pp /
-    launch_wgrad_cfg<2, 8>): workgroup target over channel tiles, at most one split per pixel tile, empty splits dropped."""
+    """S of launch_conv3x3_wgrad_bf16 for this shape, restated from conv3x3_wgrad_route / conv3x3_wgrad_plan / wgrad_geometry
+    (fu_wgrad_bf16.hip, fu_conv_bf16.h): workgroup target over channel tiles, at most one split per pixel tile, empty splits dropped."""
     cin = C0 + C1
     if C0 == 8 and C1 == 0 and not bn and Cout == 64 and H % 8 == 0 and W % 32 == 0:
         npix, n_t, target = B * (H // 8) * (W // 32), 1, 512                    # k_wgrad_bf16_c8: 8 x 32 pixel tiles

@@ -19,7 +19,8 @@ two sources; fu_forward_views + fu_merge_views over the four flip codes.
 Convs: what fu_op_conv3x3_fwd, _dgrad, _dgrad_bnsums and _wgrad write, bf16 and fp16, at the smallest shapes that reach each
 kernel route (tests/test_conv_route_cpu.py names them): 64 -> 64 at 64 x 64 under tile modes 3 (rs4) and 4 (pp: eight 16 x 32
 tiles), 8 -> 64 at 16 x 16 and 64 x 16 (the two c8 variants), 16 -> 24 at 37 x 45 by default (fast) and on the general kernel,
-the weight gradient with 8, 64 and 128 input channels under each fu_test_force_lockstep_wgrad mode; under the default
+the weight gradient with 8, 64 and 128 input channels and 256 -> 128 at 80 x 80, B = 2 (three stages per workgroup of the
+ping-pong kernel: its loop's odd exit after a full round) under each fu_test_force_lockstep_wgrad mode; under the default
 dispatch 32 -> 64 at 256 x 256, B = 2 (exactly 512 workgroups) and a dgrad with fused sums below 256 input channels.  The
 one-tap kernels have no operator of their own: a late-fusion step of base 8 runs them with 16 ... 128 input channels.
 BN: fu_op_bn_bwd (dL/dy, dgamma, dbeta) in fp32 / bf16 / fp16 at 12 x 5 x 7 (C / 4 = 3 does not divide the block: one thread
@@ -234,6 +235,7 @@ def convs(lib, out):
                 out[f"conv/{nm}/lock{lock}/wgrad/c64"] = wgrad(code, dt, 1, 64, 64, 32, 32, True)
                 out[f"conv/{nm}/lock{lock}/wgrad/c128"] = wgrad(code, dt, 1, 128, 64, 32, 32, True)
                 out[f"conv/{nm}/lock{lock}/wgrad/37x45"] = wgrad(code, dt, 2, 16, 24, 37, 45, True)
+                out[f"conv/{nm}/lock{lock}/wgrad/c256_3stages"] = wgrad(code, dt, 2, 256, 128, 80, 80, True)
             lib.fu_test_force_lockstep_wgrad(0)
             out[f"conv/{nm}/default/fwd/512wg"] = fwd(code, dt, 2, 32, 64, 256, 256, True)
             out[f"conv/{nm}/default/dgrad/512wg"] = dgrad(code, dt, 2, 64, 32, 256, 256, False)
