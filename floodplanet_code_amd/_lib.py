@@ -154,6 +154,8 @@ SIGNATURES = {
     "fu_forward_views": (_i, [_p, C.POINTER(_p), C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(C.c_int32), _p, _p]),
     "fu_merge_views": (_i, [_p, _p, _p, _i, _p, _p]),
     "fu_stitch_add_batch_probs": (_i, [_p, _i, C.POINTER(FuStitchEntry), _p, _i, _p]),
+    "fu_stitch_add_batch_windowed": (_i, [_p, _i, C.POINTER(FuStitchEntry), _p, _i, _p, _p, _p]),
+    "fu_stitch_finalize_maps": (_i, [_p, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p, _p]),
     "fu_augment": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i64, _p]),
     "fu_scene_crops": (_i, [_p, _i, C.POINTER(FuSceneCrop), _i, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p]),
     "fu_scene_train_tiles": (_i, [_p, _i, C.POINTER(FuSceneTrainEntry), _i, _i, _i, _i, _p, _p, _f, _i64, _i64, _p, _p, _p, _p,

@@ -12,6 +12,7 @@
 //                packed per-tap copies (forward and tap-reversed dgrad layouts) refreshed after each update.
 #include "fu_ctx.h"
 
+#include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
 
@@ -583,6 +584,17 @@ int fu_stitch_add_batch_probs(fu_ctx* c, int n, const fu_stitch_entry* entries, 
                                  batch, true, c->cfg.height, c->cfg.width, c->cfg.n_classes, (hipStream_t)stream);
 }
 
+int fu_stitch_add_batch_windowed(fu_ctx* c, int n, const fu_stitch_entry* entries, const float* probs, int batch,
+                                 const float* win_y, const float* win_x, fu_stream stream) {
+  FU_REQUIRE(c && entries && n > 0, "fu_stitch_add_batch_windowed: null context / entries or n = %d <= 0", n);
+  FU_REQUIRE(win_y && win_x, "fu_stitch_add_batch_windowed: null window");
+  FU_REQUIRE(!probs || batch >= 1, "fu_stitch_add_batch_windowed: batch = %d < 1", batch);
+  FU_REQUIRE(probs || c->last_batch > 0, "fu_stitch_add_batch_windowed: no forward pass yet");
+  return launch_stitch_add_batch(c->stitch_table, "fu_stitch_add_batch_windowed", probs ? "probabilities' batch" : "last batch",
+                                 n, entries, probs ? probs : c->logits, probs ? batch : c->last_batch, probs != nullptr,
+                                 c->cfg.height, c->cfg.width, c->cfg.n_classes, (hipStream_t)stream, win_y, win_x);
+}
+
 int fu_eval_confusion(fu_ctx* c, const int64_t* target, int ignore_index, int64_t* counts_out, fu_stream stream) {
   FU_REQUIRE(c && target && counts_out, "fu_eval_confusion: null argument");
   FU_REQUIRE(c->last_batch > 0, "fu_eval_confusion: no forward pass yet");
@@ -595,6 +607,20 @@ int fu_stitch_finalize(float* canvas, const float* weight, int n_classes, int ca
   FU_REQUIRE(canvas && weight && n_classes >= 1 && n_classes <= HEAD_MAX_CLS, "fu_stitch_finalize: bad argument");
   return launch_stitch_finalize(canvas, weight, n_classes, (int64_t)canvas_h * canvas_w, argmax_out,
                                 (hipStream_t)stream);
+}
+
+int fu_stitch_finalize_maps(float* canvas, const float* weight, int n_classes, int canvas_h, int canvas_w, float eps,
+                            int normalize_in_place, const uint8_t* class_values, uint8_t* class_out, uint8_t* prob_out,
+                            uint8_t* margin_out, int64_t* counts_out, fu_stream stream) {
+  FU_REQUIRE(canvas && weight, "fu_stitch_finalize_maps: null canvas / weight");
+  FU_REQUIRE(n_classes >= 1 && n_classes <= HEAD_MAX_CLS, "fu_stitch_finalize_maps: n_classes %d not in 1..%d", n_classes,
+             HEAD_MAX_CLS);
+  FU_REQUIRE(canvas_h >= 0 && canvas_w >= 0, "fu_stitch_finalize_maps: canvas %dx%d", canvas_h, canvas_w);
+  FU_REQUIRE(isfinite(eps) && eps >= 0.f, "fu_stitch_finalize_maps: eps %g is negative or not finite", (double)eps);
+  FU_REQUIRE(normalize_in_place || class_out || prob_out || margin_out || counts_out,
+             "fu_stitch_finalize_maps: no output requested");
+  return launch_stitch_finalize_maps(canvas, weight, n_classes, (int64_t)canvas_h * canvas_w, eps, normalize_in_place != 0,
+                                     class_values, class_out, prob_out, margin_out, counts_out, (hipStream_t)stream);
 }
 
 int fu_augment(const float* image, const int64_t* target, float* image_out, int64_t* target_out, const int32_t* flags,

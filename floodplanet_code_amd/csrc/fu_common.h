@@ -536,8 +536,16 @@ int launch_stitch_finalize(float* canvas, const float* weight, int ncls, int64_t
 // fu_stitch_add_batch (probs == false: src = the resident NHWC logits) and fu_stitch_add_batch_probs (true: src = the
 // caller's probabilities), src [n_samples, H, W, ncls] fp32: validates the host table (fn / batch_name go into the
 // messages), uploads it and launches; every check comes before anything is copied or launched
+// win_y / win_x (fu_stitch_add_batch_windowed): fp32 device arrays of H and W elements, both or neither; with them crop
+// pixel (ly, lx) counts with win_y[ly] * win_x[lx] instead of 1
 int launch_stitch_add_batch(DeviceTable& table, const char* fn, const char* batch_name, int n, const fu_stitch_entry* entries,
-                            const float* src, int n_samples, bool probs, int H, int W, int ncls, hipStream_t s);
+                            const float* src, int n_samples, bool probs, int H, int W, int ncls, hipStream_t s,
+                            const float* win_y = nullptr, const float* win_x = nullptr);
+// fu_stitch_finalize_maps: normalised canvas (in place when normalize), uint8 class map / probability bands / top-2
+// margin and int64 pixels per argmax class (ADDED to) in one pass; every output optional.  class_values: HOST bytes or null
+int launch_stitch_finalize_maps(float* canvas, const float* weight, int ncls, int64_t npix, float eps, bool normalize,
+                                const unsigned char* class_values, unsigned char* class_out, unsigned char* prob_out,
+                                unsigned char* margin_out, int64_t* counts, hipStream_t s);
 int launch_eval_confusion(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int B, int64_t hw,
                           int64_t* counts, hipStream_t s);
 // fu_merge_views: softmax of each view's logits, inverse view, mean in view order -> probs [B, H, W, k] (optional) and

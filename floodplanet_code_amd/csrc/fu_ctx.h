@@ -187,7 +187,7 @@ struct fu_ctx {
   int* guard = nullptr;           // fp16 mode: non-finite flag / skipped steps / back-off exponent / clean steps (k_guard_book)
   unsigned long long* conf_tmp = nullptr;
   int64_t* n_valid = nullptr;
-  fu::DeviceTable stitch_table, scene_table, train_table;   // fu_stitch_add_batch[_probs] / fu_scene_crops / fu_scene_train_tiles
+  fu::DeviceTable stitch_table, scene_table, train_table;   // fu_stitch_add_batch[_probs, _windowed] / fu_scene_crops / fu_scene_train_tiles
   float* adam_m = nullptr;        // bound (caller-owned, fu_bind_adam_state): the moments outlive the context
   float* adam_v = nullptr;
   float* ema_p = nullptr;         // bound (caller-owned, fu_bind_ema_state): the weight EMA and the EMA of the running statistics

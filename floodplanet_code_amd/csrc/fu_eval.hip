@@ -146,9 +146,63 @@ __global__ void k_stitch_add_batch(const StitchJob* __restrict__ jobs, int n, in
   }
 }
 
-// Every check comes before the copy and the launch: a rejected call leaves the stream untouched.
+// The windowed form (fu_stitch_add_batch_windowed): the ownership scheme of k_stitch_add_batch, and every covering job
+// counts with w = win_y[ly] * win_x[lx] at its tile-local pixel (ly, lx) -- also in an edge-clipped box -- instead of 1.
+// A kernel of its own: nothing here contracts (each product and each add rounds once, which is what a sequence of
+// elementwise fp32 tensor ops gives), whereas k_stitch_add_batch<false> keeps its fma.  The logits source rounds
+// e[k] * inv first, so it adds exactly what the probs source adds of fu_merge_views' single-view probabilities.
+template <bool PROBS>
+__global__ void k_stitch_add_batch_windowed(const StitchJob* __restrict__ jobs, int n, int ncls, int cropW,
+                                            const float* __restrict__ win_y, const float* __restrict__ win_x) {
+#pragma clang fp contract(off)
+  for (int e = blockIdx.y; e < n; e += gridDim.y) {
+    const StitchJob J = jobs[e];
+    const int64_t total = (int64_t)J.dh * J.dw;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * blockDim.x) {
+      const int cy = J.h0 + (int)(idx / J.dw), cx = J.w0 + (int)(idx % J.dw);
+      bool owner = true;
+      for (int j = 0; j < e && owner; ++j) owner = !stitch_covers(jobs[j], J.canvas, cy, cx);
+      if (!owner) continue;
+      const int64_t o = (int64_t)cy * J.canvasW + cx;
+      float acc[HEAD_MAX_CLS], wacc = J.weight[o];
+#pragma unroll
+      for (int k = 0; k < HEAD_MAX_CLS; ++k) acc[k] = k < ncls ? J.canvas[o * ncls + k] : 0.f;
+      for (int j = e; j < n; ++j) {
+        const StitchJob Q = jobs[j];
+        if (!stitch_covers(Q, J.canvas, cy, cx)) continue;
+        const int ly = cy - Q.h0, lx = cx - Q.w0;
+        const float w = win_y[ly] * win_x[lx];
+        const float* z = Q.logits + ((int64_t)ly * cropW + lx) * ncls;
+        float p[HEAD_MAX_CLS];
+        if constexpr (PROBS) {
+#pragma unroll
+          for (int k = 0; k < HEAD_MAX_CLS; ++k) p[k] = k < ncls ? z[k] : 0.f;
+        } else {
+          float ex[HEAD_MAX_CLS], inv;
+          softmax_terms(z, ncls, ex, inv);
+#pragma unroll
+          for (int k = 0; k < HEAD_MAX_CLS; ++k) p[k] = ex[k] * inv;
+        }
+#pragma unroll
+        for (int k = 0; k < HEAD_MAX_CLS; ++k) {
+          const float wp = w * p[k];
+          acc[k] = acc[k] + wp;
+        }
+        wacc = wacc + w;
+      }
+#pragma unroll
+      for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) J.canvas[o * ncls + k] = acc[k];
+      J.weight[o] = wacc;
+    }
+  }
+}
+
+// Every check comes before the copy and the launch: a rejected call leaves the stream untouched.  win_y / win_x: null for
+// the plain kernels; both given for the windowed one (H and W elements, the caller's).
 int launch_stitch_add_batch(DeviceTable& table, const char* fn, const char* batch_name, int n, const fu_stitch_entry* entries,
-                            const float* src, int n_samples, bool probs, int H, int W, int ncls, hipStream_t s) {
+                            const float* src, int n_samples, bool probs, int H, int W, int ncls, hipStream_t s,
+                            const float* win_y, const float* win_x) {
   std::vector<StitchJob> jobs((size_t)n);
   int max_area = 0;
   for (int i = 0; i < n; ++i) {
@@ -172,8 +226,205 @@ int launch_stitch_add_batch(DeviceTable& table, const char* fn, const char* batc
   FU_TRY(table.upload(jobs.data(), (size_t)n * sizeof(StitchJob), sizeof(StitchJob), s));
   const StitchJob* jobs_dev = static_cast<const StitchJob*>(table.dev);
   const dim3 grid(grid_for(max_area, 256, 1024), n < 65535 ? n : 65535);
-  if (probs) hipLaunchKernelGGL(k_stitch_add_batch<true>, grid, dim3(256), 0, s, jobs_dev, n, ncls, W);
+  if (win_y) {
+    if (probs) hipLaunchKernelGGL(k_stitch_add_batch_windowed<true>, grid, dim3(256), 0, s, jobs_dev, n, ncls, W, win_y, win_x);
+    else hipLaunchKernelGGL(k_stitch_add_batch_windowed<false>, grid, dim3(256), 0, s, jobs_dev, n, ncls, W, win_y, win_x);
+  } else if (probs) hipLaunchKernelGGL(k_stitch_add_batch<true>, grid, dim3(256), 0, s, jobs_dev, n, ncls, W);
   else hipLaunchKernelGGL(k_stitch_add_batch<false>, grid, dim3(256), 0, s, jobs_dev, n, ncls, W);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Fused finalisation (fu_stitch_finalize_maps): one pass over a canvas gives the normalised canvas (k_stitch_finalize's
+// expression, with the caller's eps), the uint8 class map, the uint8 probability bands, the uint8 top-2 margin and the
+// pixels per argmax class.  Memory bound: a thread takes 4 consecutive pixels -- one float4 of weights, K float4 of
+// canvas, one 4-byte store per uint8 map -- between a misaligned head and a tail that run one pixel at a time; an array
+// that is not aligned alike (vec bit clear) is read or written one element at a time inside the groups too.
+// ------------------------------------------------------------------------------------------------
+enum : unsigned { MAPS_VEC_CANVAS = 1, MAPS_VEC_CLASS = 2, MAPS_VEC_PROB = 4, MAPS_VEC_MARGIN = 8 };
+
+struct FinalizeMaps {
+  float* canvas;                   // [npix, K] raw sums
+  const float* weight;             // [npix]
+  unsigned char* class_out;        // [npix] or null
+  unsigned char* prob_out;         // [K, npix] or null
+  unsigned char* margin_out;       // [npix] or null
+  unsigned long long* counts;      // [K] or null, added to
+  int64_t npix, head;              // head: the pixels in front of weight's first 16-byte boundary
+  unsigned long long class_values; // byte k = the class map's value for argmax k
+  float eps;
+  int normalize;                   // write the normalised canvas back
+  unsigned vec;                    // MAPS_VEC_*: the array is aligned for the group's wide access
+};
+
+__device__ __forceinline__ unsigned char quantize_unit(float x) {
+  return (unsigned char)rintf(fminf(fmaxf(x, 0.f), 1.f) * 255.f);
+}
+
+// v: raw sums in, normalised values out.  am: argmax (first maximum wins), margin: v[top1] - v[top2] (v[0] for K == 1).
+template <int K>
+__device__ __forceinline__ bool finalize_pixel(float (&v)[K], float wgt, float eps, int& am, float& margin) {
+#pragma clang fp contract(off)
+  const float s = wgt + eps;
+  const bool covered = s > 0.f;
+  am = 0;
+  margin = 0.f;
+  if (!covered) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = 0.f;
+    return false;
+  }
+  const float inv = 1.f / s;
+  float best = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    v[k] = v[k] * inv;
+    if (v[k] > best) { best = v[k]; am = k; }
+  }
+  if constexpr (K == 1) {
+    margin = v[0];
+  } else {
+    float second = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < K; ++k) if (k != am) second = fmaxf(second, v[k]);
+    margin = v[am] - second;
+  }
+  return true;
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void k_stitch_finalize_maps(const FinalizeMaps a) {
+  __shared__ unsigned int bins[HEAD_MAX_CLS];
+  if (a.counts) {
+    if (threadIdx.x < K) bins[threadIdx.x] = 0;
+    __syncthreads();
+  }
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nvec = (a.npix - a.head) / 4;
+  for (int64_t j = tid; j < nvec; j += nthr) {
+    const int64_t p = a.head + 4 * j;
+    const float4 w4 = *reinterpret_cast<const float4*>(a.weight + p);
+    const float wq[4] = {w4.x, w4.y, w4.z, w4.w};
+    float c[4 * K];
+    if (a.vec & MAPS_VEC_CANVAS) {
+#pragma unroll
+      for (int i = 0; i < K; ++i) {
+        const float4 t = reinterpret_cast<const float4*>(a.canvas + p * K)[i];
+        c[4 * i] = t.x, c[4 * i + 1] = t.y, c[4 * i + 2] = t.z, c[4 * i + 3] = t.w;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4 * K; ++i) c[i] = a.canvas[p * K + i];
+    }
+    unsigned cls = 0, mg = 0, pq[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) pq[k] = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float v[K], margin;
+      int am;
+#pragma unroll
+      for (int k = 0; k < K; ++k) v[k] = c[q * K + k];
+      const bool covered = finalize_pixel<K>(v, wq[q], a.eps, am, margin);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        c[q * K + k] = v[k];
+        pq[k] |= (unsigned)quantize_unit(v[k]) << (8 * q);
+      }
+      cls |= (unsigned)(unsigned char)(a.class_values >> (8 * am)) << (8 * q);
+      mg |= (unsigned)quantize_unit(margin) << (8 * q);
+      if (a.counts && covered) atomicAdd(&bins[am], 1u);
+    }
+    if (a.normalize) {
+      if (a.vec & MAPS_VEC_CANVAS) {
+#pragma unroll
+        for (int i = 0; i < K; ++i)
+          reinterpret_cast<float4*>(a.canvas + p * K)[i] = make_float4(c[4 * i], c[4 * i + 1], c[4 * i + 2], c[4 * i + 3]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4 * K; ++i) a.canvas[p * K + i] = c[i];
+      }
+    }
+    if (a.class_out) {
+      if (a.vec & MAPS_VEC_CLASS) {
+        *reinterpret_cast<unsigned*>(a.class_out + p) = cls;
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a.class_out[p + q] = (unsigned char)(cls >> (8 * q));
+      }
+    }
+    if (a.margin_out) {
+      if (a.vec & MAPS_VEC_MARGIN) {
+        *reinterpret_cast<unsigned*>(a.margin_out + p) = mg;
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a.margin_out[p + q] = (unsigned char)(mg >> (8 * q));
+      }
+    }
+    if (a.prob_out) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        unsigned char* dst = a.prob_out + (int64_t)k * a.npix + p;
+        if (a.vec & MAPS_VEC_PROB) {
+          *reinterpret_cast<unsigned*>(dst) = pq[k];
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) dst[q] = (unsigned char)(pq[k] >> (8 * q));
+        }
+      }
+    }
+  }
+  const int64_t tail0 = a.head + 4 * nvec, nrest = a.head + (a.npix - tail0);   // misaligned head and tail: plain code
+  for (int64_t r = tid; r < nrest; r += nthr) {
+    const int64_t p = r < a.head ? r : tail0 + (r - a.head);
+    float v[K], margin;
+    int am;
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = a.canvas[p * K + k];
+    const bool covered = finalize_pixel<K>(v, a.weight[p], a.eps, am, margin);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (a.normalize) a.canvas[p * K + k] = v[k];
+      if (a.prob_out) a.prob_out[(int64_t)k * a.npix + p] = quantize_unit(v[k]);
+    }
+    if (a.class_out) a.class_out[p] = (unsigned char)(a.class_values >> (8 * am));
+    if (a.margin_out) a.margin_out[p] = quantize_unit(margin);
+    if (a.counts && covered) atomicAdd(&bins[am], 1u);
+  }
+  if (a.counts) {
+    __syncthreads();
+    if (threadIdx.x < K && bins[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)bins[threadIdx.x]);
+  }
+}
+
+int launch_stitch_finalize_maps(float* canvas, const float* weight, int ncls, int64_t npix, float eps, bool normalize,
+                                const unsigned char* class_values, unsigned char* class_out, unsigned char* prob_out,
+                                unsigned char* margin_out, int64_t* counts, hipStream_t s) {
+  if (npix <= 0) return 0;
+  FinalizeMaps a{};
+  a.canvas = canvas, a.weight = weight, a.class_out = class_out, a.prob_out = prob_out, a.margin_out = margin_out;
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.npix = npix, a.eps = eps, a.normalize = normalize ? 1 : 0;
+  for (int k = 0; k < HEAD_MAX_CLS; ++k)
+    a.class_values |= (unsigned long long)(class_values && k < ncls ? class_values[k] : (unsigned char)k) << (8 * k);
+  const uintptr_t wa = reinterpret_cast<uintptr_t>(weight);
+  a.head = wa % 4 ? npix : std::min<int64_t>(npix, (int64_t)((16 - wa % 16) % 16) / 4);
+  const auto aligned = [&](const void* base, int64_t elem_bytes, int64_t per_pixel, unsigned to) {
+    return base && (reinterpret_cast<uintptr_t>(base) + (uintptr_t)(a.head * per_pixel * elem_bytes)) % to == 0;
+  };
+  if (aligned(canvas, 4, ncls, 16)) a.vec |= MAPS_VEC_CANVAS;
+  if (aligned(class_out, 1, 1, 4)) a.vec |= MAPS_VEC_CLASS;
+  if (aligned(margin_out, 1, 1, 4)) a.vec |= MAPS_VEC_MARGIN;
+  if (aligned(prob_out, 1, 1, 4) && (ncls == 1 || npix % 4 == 0)) a.vec |= MAPS_VEC_PROB;   // every band alike
+  const dim3 grid(grid_for(ceil_div64(npix, 4), 256, 2048));
+  switch (ncls) {
+#define FU_MAPS_CASE(K) case K: hipLaunchKernelGGL(k_stitch_finalize_maps<K>, grid, dim3(256), 0, s, a); break;
+    FU_MAPS_CASE(1) FU_MAPS_CASE(2) FU_MAPS_CASE(3) FU_MAPS_CASE(4) FU_MAPS_CASE(5) FU_MAPS_CASE(6) FU_MAPS_CASE(7)
+    FU_MAPS_CASE(8)
+#undef FU_MAPS_CASE
+    default: FU_REQUIRE(false, "stitch_finalize_maps: %d classes", ncls);
+  }
   FU_LAUNCH_CHECK();
   return 0;
 }

@@ -21,9 +21,14 @@ else the parent directory.  What runs differently:
     crop gets one padded crop where get_crop_slices raises; boxes are clipped to the grid (get_crop_slices' bottom-edge
     quirk swaps the crop sizes, which only matters for non-square crops);
   * extension: the input's GeoTIFF georeferencing goes along with the class map (the reference drops it through PIL),
-    rescaled to the output grid (geo_tags_for_grid); GDAL_NODATA is dropped.
-Out of scope: multi-GPU inference, inputs besides ms_image (dem, slope, hand, preflood), probability / RGB outputs,
-BigTIFF or compressed output.
+    rescaled to the output grid (geo_tags_for_grid); GDAL_NODATA is dropped;
+  * extension: --blend linear|hann weights every crop with a window that falls off towards the tile's border
+    (stitch.blend_window), so a pixel is decided by the crops that see it with their interior; the stride then defaults
+    to half the crop.  --write_probs u8|f32 writes the stitched probabilities as <image>_prob.tif ([k, H, W]; u8 =
+    rint(p * 255)), --write_margin the top-1 minus top-2 probability as <image>_margin.tif (uint8 [H, W]), with the class
+    map's georeferencing.  Class map, class counts and these rasters come from one fu_stitch_finalize_maps launch.
+Out of scope: multi-GPU inference, inputs besides ms_image (dem, slope, hand, preflood), RGB outputs, BigTIFF or
+compressed output.
 """
 from __future__ import annotations
 
@@ -38,10 +43,12 @@ import numpy as np
 import torch
 
 from .predict import CONFIG_DEFAULTS, WEIGHT_CHOICES, _merge, load_checkpoint_model, resolve_cfg
+from .stitch import BLEND_KINDS
 from .tta import VIEW_SETS, view_codes
 
 SCALE_MODES = {"S1": 1, "S2": 2, "L8": 3}                    # PS: 4 when stored as uint16, else 0
 EXTRA_SOURCES = ("dem", "slope", "preflood", "pre_post_difference", "chirps", "hand")
+PROB_FORMATS = ("u8", "f32")
 
 
 # ---------------------------------------------------------------------------------------------------------- host side
@@ -72,6 +79,19 @@ def output_path(out_dir: str, path: str, sensor: str) -> str:
     """<out_dir>/<region>_pred/<image>.tif (infer.py:148-150, 180-182)."""
     name = os.path.splitext(os.path.basename(path))[0]
     return os.path.join(out_dir, region_name(path, sensor) + "_pred", name + ".tif")
+
+
+def side_output_path(out_path: str, kind: str) -> str:
+    """<image>_prob.tif / <image>_margin.tif beside the class map <image>.tif."""
+    return out_path[:-len(".tif")] + f"_{kind}.tif"
+
+
+def default_stride(crop_h: int, crop_w: int, blend: str = "uniform", stride: Optional[int] = None) -> int:
+    """An explicit stride wins; else min(crop_h, crop_w) (infer.py:64-65) under "uniform", and half of that under a
+    window blend -- without overlap there is nothing to blend."""
+    if stride is not None:
+        return int(stride)
+    return min(crop_h, crop_w) if blend == "uniform" else max(1, min(crop_h, crop_w) // 2)
 
 
 def grid_size(src_hw: Tuple[int, int], size: Optional[Sequence[int]] = None, scale: Optional[float] = None):
@@ -200,19 +220,25 @@ def check_model_inputs(cfg: dict, norm_params=None) -> None:
 def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Optional[dict] = None,
           size: Optional[Sequence[int]] = None, scale: Optional[float] = None, stride: Optional[int] = None,
           batch_size: Optional[int] = None, tta=None, n_workers: int = 0, device: str = "cuda:0",
-          keep_probabilities: bool = False, norm_params=None, weights: str = "auto") -> dict:
+          keep_probabilities: bool = False, norm_params=None, weights: str = "auto", blend: str = "uniform",
+          write_probs: Optional[str] = None, write_margin: bool = False) -> dict:
     """Class maps of every input scene (see the module docstring).  cfg: the resolved config (default: resolve_cfg of
     the checkpoint's experiment).  Returns the summary.json dict; with keep_probabilities also "probabilities"
     {output path: fp32 [H, W, k] stitched canvas} (one more host read per scene; for tests and comparisons).
     norm_params: the parameter file of norm_mode 'global' (path, or the dict it holds; datasets.stats), looked up by the
     config's data set name and sensor; without it a 'global' config is rejected.  weights: 'auto', 'raw' or 'ema'
-    (predict.checkpoint_weights); the summary records the choice made under "weights"."""
+    (predict.checkpoint_weights); the summary records the choice made under "weights".  blend: "uniform", "linear" or
+    "hann" (stitch.blend_window); write_probs: None, "u8" or "f32"; write_margin: also write the top-2 margin raster."""
     from .datasets.floodplanet import _N_CHANNELS
     from .models import build_model
 
     t_start = time.perf_counter()
     if weights not in WEIGHT_CHOICES:
         raise ValueError(f"weights must be one of {list(WEIGHT_CHOICES)}, got {weights!r}")
+    if blend not in BLEND_KINDS:
+        raise ValueError(f"blend must be one of {list(BLEND_KINDS)}, got {blend!r}")
+    if write_probs is not None and write_probs not in PROB_FORMATS:
+        raise ValueError(f"write_probs must be one of {list(PROB_FORMATS)} or None, got {write_probs!r}")
     if cfg is None:
         experiment_dir = "/".join(checkpoint_path.split("/")[:-2])
         cfg = resolve_cfg(experiment_dir, checkpoint_path)
@@ -231,7 +257,7 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
         gm, gs = sensor_norm_params(norm_params, ds_cfg.get("name") or "floodplanet", sensor, n_channels["ms_image"])
         global_params = (torch.from_numpy(gm).float(), torch.from_numpy(gs).float())
     ch, cw = int(cfg["crop_height"]), int(cfg["crop_width"])
-    stride = int(stride) if stride is not None else min(ch, cw)
+    stride = default_stride(ch, cw, blend, stride)
     if stride < 1:
         raise ValueError(f"infer: stride must be >= 1, got {stride}")
     bs = int(batch_size or cfg["batch_size"])
@@ -260,7 +286,8 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     k = net.n_classes
     T = len(codes) if codes is not None else 1
     net._get_ctx(dev, T * bs, ch, cw)                    # the context owns fu_scene_crops' table: make it at full size
-    stitcher = GpuImageStitcher(net, dev)
+    stitcher = GpuImageStitcher(net, dev, blend=blend)
+    class_values = [0] + [255] * (k - 1)                 # clip(argmax, 0, 1) * 255
     C = n_channels["ms_image"]
     crop_buf = torch.empty(bs, C, ch, cw, dtype=torch.float32, device=dev)
     loader = torch.utils.data.DataLoader(SceneFiles(paths, sensor, channels), batch_size=None, shuffle=False,
@@ -287,18 +314,36 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
         sc = resident.pop(i)
         H, W = sc["hw"]
         key = str(i)
-        prob, am = stitcher.combine(key)
-        cls = (am.clamp(0, 1) * 255).to(torch.uint8)
-        counts = torch.bincount(am.view(-1), minlength=k)
-        packed = torch.cat([counts.view(torch.uint8), cls.view(-1)]).cpu()      # the one device-to-host read
+        maps = stitcher.combine_maps(key, class_values, probs=write_probs == "u8", margin=write_margin, counts=True)
+        parts = [maps["counts"].view(torch.uint8), maps["class"].view(-1)]
+        parts += [maps[m].view(-1) for m in ("probs", "margin") if m in maps]
+        if write_probs == "f32":                         # the normalised canvas itself, as bytes of the same read
+            parts.append(maps["canvas"].view(torch.uint8).view(-1))
+        packed = torch.cat(parts).cpu().numpy()          # one launch above, the one device-to-host read here
         if keep_probabilities:
-            probabilities[outs[i]] = prob.cpu().numpy()
+            probabilities[outs[i]] = maps["canvas"].cpu().numpy()
         stitcher.drop(key)
-        class_pixels = packed[:8 * k].view(torch.int64).tolist()
-        cls_h = packed[8 * k:].numpy().reshape(H, W)
-        write_strip_tiff(outs[i], cls_h, extra_tags=geo_tags_for_grid(sc["tags"], sc["src_hw"], (H, W)))
-        records.append({"input": paths[i], "output": outs[i], "source_size": list(sc["src_hw"]),
-                        "grid_size": [H, W], "crops": sc["n"], "class_pixels": class_pixels})
+        class_pixels = packed[:8 * k].view(np.int64).tolist()
+        at = 8 * k
+        cls_h = packed[at:at + H * W].reshape(H, W)
+        at += H * W
+        tags = geo_tags_for_grid(sc["tags"], sc["src_hw"], (H, W))
+        write_strip_tiff(outs[i], cls_h, extra_tags=tags)
+        rec = {"input": paths[i], "output": outs[i], "source_size": list(sc["src_hw"]), "grid_size": [H, W],
+               "crops": sc["n"], "class_pixels": class_pixels}
+        if write_probs == "u8":
+            rec["probabilities"] = side_output_path(outs[i], "prob")
+            write_strip_tiff(rec["probabilities"], packed[at:at + k * H * W].reshape(k, H, W), extra_tags=tags)
+            at += k * H * W
+        if write_margin:
+            rec["margin"] = side_output_path(outs[i], "margin")
+            write_strip_tiff(rec["margin"], packed[at:at + H * W].reshape(H, W), extra_tags=tags)
+            at += H * W
+        if write_probs == "f32":
+            rec["probabilities"] = side_output_path(outs[i], "prob")
+            canvas_h = packed[at:].view(np.float32).reshape(H, W, k)
+            write_strip_tiff(rec["probabilities"], np.ascontiguousarray(canvas_h.transpose(2, 0, 1)), extra_tags=tags)
+        records.append(rec)
 
     with torch.no_grad():
         while True:
@@ -332,7 +377,8 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     seconds = time.perf_counter() - t_start
     summary = {"scenes": records, "n_scenes": len(records), "n_crops": n_crops, "seconds": seconds,
                "crops_per_s": n_crops / seconds if seconds > 0 else None, "max_resident_scenes": max_resident,
-               "tta": tta if (tta is None or isinstance(tta, str)) else list(codes), "weights": chosen}
+               "tta": tta if (tta is None or isinstance(tta, str)) else list(codes), "weights": chosen,
+               "blend": blend, "stride": stride}
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "summary.json"), "w") as fh:
         json.dump(summary, fh, indent=4)
@@ -350,7 +396,17 @@ def build_parser() -> argparse.ArgumentParser:
     grid.add_argument("--size", type=int, nargs=2, metavar=("H", "W"), default=None,
                       help="output grid of every scene (default: the raster's own size)")
     grid.add_argument("--scale", type=float, default=None, help="output grid = round(F * the raster's size)")
-    ap.add_argument("--stride", type=int, default=None, help="crop stride (default: min(crop_height, crop_width))")
+    ap.add_argument("--stride", type=int, default=None,
+                    help="crop stride (default: min(crop_height, crop_width); half of that with --blend linear / hann, "
+                         "since without overlap there is nothing to blend)")
+    ap.add_argument("--blend", type=str, default="uniform", choices=list(BLEND_KINDS),
+                    help="how overlapping crops are averaged: equal weights (uniform, the default) or a window that "
+                         "falls off towards the crop's border (linear: triangle, hann: raised cosine)")
+    ap.add_argument("--write_probs", type=str, default=None, choices=list(PROB_FORMATS),
+                    help="also write the stitched class probabilities as <image>_prob.tif, [k, H, W]: uint8 "
+                         "rint(p * 255) (u8) or float32 (f32)")
+    ap.add_argument("--write_margin", action="store_true",
+                    help="also write <image>_margin.tif, uint8 [H, W]: rint(255 * (top-1 minus top-2 probability))")
     ap.add_argument("--batch_size", type=int, default=None, help="crops per eval forward (default: the config's)")
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips / rotations")
@@ -371,7 +427,8 @@ def main(argv: Optional[List[str]] = None) -> None:
     cfg = resolve_cfg(experiment_dir, args.checkpoint_path)
     out = infer(args.checkpoint_path, args.inputs, args.out_dir, cfg=cfg, size=args.size, scale=args.scale,
                 stride=args.stride, batch_size=args.batch_size, tta=args.tta, n_workers=args.n_workers,
-                device=args.device, norm_params=args.norm_params, weights=args.weights)
+                device=args.device, norm_params=args.norm_params, weights=args.weights, blend=args.blend,
+                write_probs=args.write_probs, write_margin=args.write_margin)
     print(json.dumps({k: v for k, v in out.items() if k != "scenes"}))
 
 

@@ -198,21 +198,25 @@ def conf_matrix_image(pred: np.ndarray, target: np.ndarray) -> np.ndarray:
 # ---------------------------------------------------------------------------------------------------------- predict
 def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_images=False, eval_region=None,
             eval_dataset_split="test", n_workers=0, *, data_root, batch_size=None, device="cuda:0", tta=None,
-            weights="auto") -> dict:
+            weights="auto", blend="uniform") -> dict:
     """predict.py:129-400 with batched crops.  Returns {"pred_dir", "metrics", "image_stats_f1", "image_stats_iou",
     "region_stats_f1", "region_stats_iou", "probabilities"} (probabilities: {region/image: [H, W, k] float32} of the
     stitched canvases when predict_images, else {}).  tta: None, a tta.VIEW_SETS name or a list of view codes; with it,
     every crop's prediction (metrics and canvases) is the mean softmax over its views.  T views run batch_size * T
     samples per forward: lower batch_size when that does not fit.  weights: 'auto', 'raw' or 'ema' (checkpoint_weights);
-    metrics.json records the choice under "weights" when the EMA was served or weights is not 'auto'."""
+    metrics.json records the choice under "weights" when the EMA was served or weights is not 'auto'.  blend: "uniform",
+    "linear" or "hann" (stitch.blend_window) -- how overlapping crops are averaged in the stitched images; the per-crop
+    metrics come from the crops and do not depend on it.  metrics.json records a blend other than "uniform"."""
     from .datasets import FloodplanetTiles, TileLoader, generate_image_slice_object
     from .datasets.synthetic import write_strip_tiff
     from .models import build_model
-    from .stitch import GpuImageStitcher
+    from .stitch import BLEND_KINDS, GpuImageStitcher
 
     cfg = _merge(CONFIG_DEFAULTS, cfg)
     if weights not in WEIGHT_CHOICES:
         raise ValueError(f"weights must be one of {list(WEIGHT_CHOICES)}, got {weights!r}")
+    if blend not in BLEND_KINDS:
+        raise ValueError(f"blend must be one of {list(BLEND_KINDS)}, got {blend!r}")
     if eval_dataset_name != "floodplanet":
         raise NotImplementedError(f'prediction supports the "floodplanet" dataset only, not "{eval_dataset_name}"')
     slice_params = generate_image_slice_object(cfg["crop_height"], cfg["crop_width"], cfg["crop_stride"])
@@ -247,7 +251,7 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
 
     image_f1, region_f1 = defaultdict(list), defaultdict(list)
     image_iou, region_iou = defaultdict(list), defaultdict(list)
-    stitcher = GpuImageStitcher(net, dev) if predict_images else None
+    stitcher = GpuImageStitcher(net, dev, blend=blend) if predict_images else None
     gt: Dict[str, torch.Tensor] = {}
     where: Dict[str, tuple] = {}         # canvas key -> (region, image name)
     loader = TileLoader(dataset, batch_size or cfg["batch_size"], dev, shuffle=False, num_workers=n_workers,
@@ -307,6 +311,8 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
             all_metrics["weights"] = chosen
         if codes is not None:
             all_metrics["tta"] = tta if isinstance(tta, str) else list(codes)
+        if blend != "uniform":
+            all_metrics["blend"] = blend
         with open(os.path.join(pred_dir, "metrics.json"), "w") as fh:
             json.dump(all_metrics, fh, indent=4)
         write_ranked_files(pred_dir, image_f1, image_iou, region_f1, region_iou)
@@ -332,6 +338,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips (hflip, flips) or all eight "
                          "flips / 90-degree rotations (d4, square crops only); default: none")
+    ap.add_argument("--blend", type=str, default="uniform", choices=["uniform", "linear", "hann"],
+                    help="how overlapping crops are averaged in the stitched images: equal weights (uniform, the default) "
+                         "or a window that falls off towards the crop's border (linear, hann); metrics are per crop and "
+                         "do not change")
     ap.add_argument("--weights", type=str, default="auto", choices=list(WEIGHT_CHOICES),
                     help="which weights of the checkpoint to serve: its state_dict (raw), its weight EMA (ema; an error when "
                          "the checkpoint has none) or the EMA when there is one (auto, the default)")
@@ -352,7 +362,7 @@ def main(argv: Optional[List[str]] = None) -> None:
     out = predict(cfg, experiment_dir, args.checkpoint_path, eval_dataset_name=name, predict_images=args.predict_images,
                   eval_region=args.eval_region, eval_dataset_split=args.eval_dataset_split, n_workers=n_workers,
                   data_root=args.data_root, batch_size=args.batch_size, device=args.device, tta=args.tta,
-                  weights=args.weights)
+                  weights=args.weights, blend=args.blend)
     print(json.dumps({"pred_dir": out["pred_dir"], **out["metrics"]}))
 
 

@@ -2,23 +2,67 @@
 (st_water_seg/utils/utils_image.py:364-494) as predict.py:329-347 uses it: every crop's softmax is added into an
 [H, W, n_classes] canvas at [h0:hE, w0:wE], a weight canvas counts the contributions, the result is
 canvas / (weight + 1e-5).  Here the softmax + accumulate runs on the logits that are still resident in the HIP
-context after an eval forward, so predictions never leave HBM until the final map is read."""
+context after an eval forward, so predictions never leave HBM until the final map is read.
+
+Extension (blend != "uniform"): every crop counts with a separable window that falls off towards the tile's border --
+canvas += w * p, weight += w with w = win[ly] * win[lx] (fu_stitch_add_batch_windowed) -- so a pixel is decided by the
+crops that see it with their interior, and the seam at the end of an overlap goes.  The windows are strictly positive,
+so such a canvas is finalised with eps = 0."""
 from __future__ import annotations
 
-from typing import Dict, Tuple
+import ctypes
+from typing import Dict, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check, ptr
 
 
+BLEND_KINDS = ("uniform", "linear", "hann")
+
+
+def blend_window(kind: str, n: int) -> np.ndarray:
+    """The 1-D blending window of an n-pixel tile axis, float32 (formed in float64, rounded once); the 2-D window of a
+    tile is the outer product of its two axes'.  "uniform": ones.  "linear": min(i + 1, n - i) / ((n + 1) // 2), a
+    triangle that peaks at exactly 1.  "hann": sin^2(pi (i + 0.5) / n), the raised cosine sampled at pixel centres.
+    All are symmetric and strictly positive (hann's minimum at n = 512 is 9.4e-6), so a covered pixel always has a
+    positive weight."""
+    if kind not in BLEND_KINDS:
+        raise ValueError(f"blend must be one of {list(BLEND_KINDS)}, got {kind!r}")
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"blend_window: n must be >= 1, got {n}")
+    i = np.arange(n, dtype=np.float64)
+    if kind == "uniform":
+        w = np.ones(n, dtype=np.float64)
+    elif kind == "linear":
+        w = np.minimum(i + 1, n - i) / ((n + 1) // 2)
+    else:
+        w = np.sin(np.pi * (i + 0.5) / n) ** 2
+    return w.astype(np.float32)
+
+
 class GpuImageStitcher:
-    def __init__(self, net, device):
+    def __init__(self, net, device, blend: str = "uniform"):
+        if blend not in BLEND_KINDS:
+            raise ValueError(f"blend must be one of {list(BLEND_KINDS)}, got {blend!r}")
         self.net = net                      # HipUNet whose last eval forward produced the crops
         self.device = torch.device(device)
+        self.blend = blend
         self.image_canvas: Dict[str, torch.Tensor] = {}
         self.weight_canvas: Dict[str, torch.Tensor] = {}
+        self._windows: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}   # tile (H, W) -> (win_y, win_x)
+
+    def _tile_windows(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The blend's windows for the context's tile size, uploaded once per size."""
+        if self.net._ctx is None:
+            raise RuntimeError("GpuImageStitcher: the net has no context yet (run a forward first)")
+        hw = (int(self.net._ctx_key[1]), int(self.net._ctx_key[2]))
+        if hw not in self._windows:
+            self._windows[hw] = tuple(torch.from_numpy(blend_window(self.blend, n)).to(self.device) for n in hw)
+        return self._windows[hw]
 
     def add_image(self, sample: int, image_name: str, crop_info, og_height: int, og_width: int) -> None:
         """crop_info: object or tuple with h0, w0, hE, wE (datasets/utils.py CropParams)."""
@@ -28,6 +72,8 @@ class GpuImageStitcher:
         if image_name not in self.image_canvas:
             self.image_canvas[image_name] = torch.zeros(og_height, og_width, k, device=self.device)
             self.weight_canvas[image_name] = torch.zeros(og_height, og_width, device=self.device)
+        if self.blend != "uniform":
+            return self.add_images([sample], [image_name], [(h0, w0, hE, wE)], [og_height], [og_width])
         cv, wt = self.image_canvas[image_name], self.weight_canvas[image_name]
         check(_lib.load().fu_stitch_add(self.net._ctx, int(sample), ptr(cv), ptr(wt), og_height, og_width, int(h0),
                                         int(w0), int(hE), int(wE), torch.cuda.current_stream(self.device).cuda_stream))
@@ -38,7 +84,9 @@ class GpuImageStitcher:
         launch, bit-identical to add_image for each crop in list order (also where crops of the list overlap).
         With probs (fp32 [N, H, W, k] on the device, e.g. HipUNet.merge_views' test-time-augmented probabilities),
         crop i adds probs[samples[i]] as it is instead of a softmax of the logits (fu_stitch_add_batch_probs): the same
-        as canvas[box] += probs[s, :dh, :dw]; weight[box] += 1 in list order, bit for bit."""
+        as canvas[box] += probs[s, :dh, :dw]; weight[box] += 1 in list order, bit for bit.
+        With a blend other than "uniform" both forms go through fu_stitch_add_batch_windowed instead: crop pixel
+        (ly, lx) adds w * p to the canvas and w to the weight, w = win_y[ly] * win_x[lx]."""
         samples, image_names, crop_info = list(samples), list(image_names), list(crop_info)
         og_heights, og_widths = list(og_heights), list(og_widths)
         n = len(samples)
@@ -64,18 +112,54 @@ class GpuImageStitcher:
             table[i] = _lib.FuStitchEntry(ptr(cv), ptr(wt), int(smp), cv.shape[0], cv.shape[1], int(h0), int(w0),
                                           int(hE), int(wE), 0)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        if probs is None:
+        if self.blend != "uniform":
+            win_y, win_x = self._tile_windows()
+            check(_lib.load().fu_stitch_add_batch_windowed(self.net._ctx, n, table, ptr(probs),
+                                                           0 if probs is None else probs.shape[0], ptr(win_y), ptr(win_x),
+                                                           stream))
+        elif probs is None:
             check(_lib.load().fu_stitch_add_batch(self.net._ctx, n, table, stream))
         else:
             check(_lib.load().fu_stitch_add_batch_probs(self.net._ctx, n, table, ptr(probs), probs.shape[0], stream))
 
     def combine(self, image_name: str) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (probabilities [H, W, n_classes], argmax [H, W]); like _combine_images + the argmax of predict.py."""
+        if self.blend != "uniform":         # eps = 0 (see combine_maps); the class map widened to combine's int64
+            maps = self.combine_maps(image_name)
+            return maps["canvas"], maps["class"].to(torch.int64)
         cv, wt = self.image_canvas[image_name], self.weight_canvas[image_name]
         am = torch.empty(cv.shape[:2], dtype=torch.int64, device=self.device)
         check(_lib.load().fu_stitch_finalize(ptr(cv), ptr(wt), cv.shape[2], cv.shape[0], cv.shape[1], ptr(am),
                                              torch.cuda.current_stream(self.device).cuda_stream))
         return cv, am
+
+    def combine_maps(self, image_name: str, class_values: Optional[Sequence[int]] = None, probs: bool = False,
+                     margin: bool = False, counts: bool = False) -> dict:
+        """The fused finalisation (fu_stitch_finalize_maps), one launch: the canvas is normalised in place -- by
+        (weight + 1e-5) under "uniform" as combine() does, by the weight alone otherwise (the windows are strictly
+        positive; 1e-5 would bias a corner pixel whose only weight is of that order) -- and the uint8 rasters come out
+        of the same pass.  -> {"canvas": fp32 [H, W, k], "class": uint8 [H, W] = class_values[argmax] (None: the argmax
+        itself), and when asked for "probs": uint8 [k, H, W] = rint(clip(p, 0, 1) * 255), "margin": uint8 [H, W] = the same
+        of top-1 minus top-2, "counts": int64 [k] pixels per argmax class}, all on the device.  Call it once per image,
+        instead of combine()."""
+        cv, wt = self.image_canvas[image_name], self.weight_canvas[image_name]
+        H, W, k = cv.shape
+        if class_values is not None:
+            if len(class_values) != k or any(not 0 <= int(v) <= 255 for v in class_values):
+                raise ValueError(f"combine_maps: class_values must be {k} values in 0..255, got {list(class_values)}")
+            class_values = (ctypes.c_uint8 * k)(*[int(v) for v in class_values])      # a host array, passed by value
+        out = {"canvas": cv, "class": torch.empty(H, W, dtype=torch.uint8, device=self.device)}
+        if probs:
+            out["probs"] = torch.empty(k, H, W, dtype=torch.uint8, device=self.device)
+        if margin:
+            out["margin"] = torch.empty(H, W, dtype=torch.uint8, device=self.device)
+        if counts:
+            out["counts"] = torch.zeros(k, dtype=torch.int64, device=self.device)
+        eps = 1e-5 if self.blend == "uniform" else 0.0
+        check(_lib.load().fu_stitch_finalize_maps(ptr(cv), ptr(wt), k, H, W, eps, 1, class_values, ptr(out["class"]),
+                                                  ptr(out.get("probs")), ptr(out.get("margin")), ptr(out.get("counts")),
+                                                  torch.cuda.current_stream(self.device).cuda_stream))
+        return out
 
     def drop(self, image_name: str) -> None:
         """Forget a finished image's canvases (after combine): their memory returns to the allocator, ordered on the

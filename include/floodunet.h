@@ -453,6 +453,35 @@ int fu_merge_views(fu_ctx* ctx, float* probs_out, const int64_t* target, int ign
 int fu_stitch_add_batch_probs(fu_ctx* ctx, int n, const fu_stitch_entry* entries, const float* probs, int batch,
                               fu_stream stream);
 
+/* fu_stitch_add_batch (probs == NULL: the resident logits of the last forward) or fu_stitch_add_batch_probs (probs given,
+ * `batch` samples) with a separable window: win_y / win_x are caller-owned fp32 DEVICE arrays of H and W elements (the
+ * context's tile size), indexed by the tile-local coordinate ly = cy - h0, lx = cx - w0 of the canvas pixel (cy, cx),
+ * also in an edge-clipped box.  Same ownership scheme, table order and entry checks; per covering entry, each operation
+ * rounding on its own in fp32 (nothing contracts into an fma):
+ *   w = win_y[ly] * win_x[lx];  p[k] = probs[sample][ly][lx][k]  or  e[k] * inv (the softmax terms of fu_stitch_add, the
+ *   product rounded first);  canvas[k] = canvas[k] + w * p[k] (product rounded, then the add);  weight = weight + w
+ * -- bit-identical to canvas[box] += probs[s, :dh, :dw] * (win_y[:dh, None] * win_x[None, :dw])[..., None];
+ * weight[box] += win_y[:dh, None] * win_x[None, :dw] in table order, and the logits source adds what the probs source
+ * adds of fu_merge_views' single-view probabilities.  The library knows nothing about window shapes.  A rejected call
+ * (the checks of fu_stitch_add_batch, or a null window) launches nothing. */
+int fu_stitch_add_batch_windowed(fu_ctx* ctx, int n, const fu_stitch_entry* entries, const float* probs, int batch,
+                                 const float* win_y, const float* win_x, fu_stream stream);
+/* Fused finalisation of a canvas, one launch.  Per pixel, each operation rounding on its own: s = weight + eps; if
+ * s > 0: inv = 1.f / s, v[k] = canvas[k] * inv (fu_stitch_finalize's expression: with eps = 1e-5f the normalised canvas
+ * and the argmax are bit-identical to it); otherwise the pixel is uncovered: v[k] = 0, class index 0, every map 0, and
+ * the pixel is not counted.  The argmax takes the first maximum.  Outputs, each optional (NULL = skip), at least one:
+ *   normalize_in_place != 0: canvas[k] = v[k] (0: the raw sums stay);
+ *   class_out  uint8 [canvas_h, canvas_w] = class_values[argmax]; class_values: HOST array of n_classes bytes, NULL =
+ *              identity (an uncovered pixel gets class_values[0]);
+ *   prob_out   uint8 [n_classes, canvas_h, canvas_w] (bands first) = (uint8) rintf(fminf(fmaxf(v[k], 0), 1) * 255);
+ *   margin_out uint8 [canvas_h, canvas_w] = the same quantisation of v[top1] - v[top2] (v[0] for n_classes == 1; 0 at
+ *              a tie);
+ *   counts_out int64 [n_classes], ADDED to: covered pixels per argmax class (integer atomics: exact, order-free).
+ * eps must be finite and >= 0, n_classes in 1..8.  A rejected call launches nothing. */
+int fu_stitch_finalize_maps(float* canvas, const float* weight, int n_classes, int canvas_h, int canvas_w, float eps,
+                            int normalize_in_place, const uint8_t* class_values, uint8_t* class_out, uint8_t* prob_out,
+                            uint8_t* margin_out, int64_t* counts_out, fu_stream stream);
+
 /* ---- eval metrics ---------------------------------------------------------------------------- */
 /* Per-sample confusion counts of the last fu_forward (eval or training): counts_out[b][t * k + p] += #pixels of sample b
  * with target t and p = argmax of the resident logits (first maximum wins, as fu_loss_ce), over pixels whose target is
