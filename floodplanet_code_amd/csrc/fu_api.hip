@@ -271,7 +271,7 @@ int fu_merge_views(fu_ctx* c, float* probs_out, const int64_t* target, int ignor
 }
 
 namespace {
-// fu_loss_ce (cw == null) and fu_loss_ce_weighted
+// fu_loss_ce (cw == null), fu_loss_ce_weighted and fu_loss_ce_focal
 int loss_ce(fu_ctx* c, const char* who, const int64_t* target, int ignore_index, const CeWeighting* cw, float* loss_out,
             int64_t* confusion_out, int64_t* n_valid_out, fu_stream stream) {
   FU_REQUIRE(c->last_batch > 0, "%s: no forward pass yet", who);
@@ -304,6 +304,17 @@ int fu_loss_ce_weighted(fu_ctx* c, const int64_t* target, int ignore_index, cons
   const CeWeighting cw = {class_weight_dev, (float)(1.0 - (double)label_smoothing),
                           (float)((double)label_smoothing / c->cfg.n_classes), c->ce_wsum, weight_sum_out};
   return loss_ce(c, "fu_loss_ce_weighted", target, ignore_index, &cw, loss_out, confusion_out, n_valid_out, stream);
+}
+
+int fu_loss_ce_focal(fu_ctx* c, const int64_t* target, int ignore_index, const float* class_weight_dev, float focal_gamma,
+                     float* loss_out, int64_t* confusion_out, int64_t* n_valid_out, float* weight_sum_out,
+                     fu_stream stream) {
+  FU_REQUIRE(c && target, "fu_loss_ce_focal: null argument");
+  FU_REQUIRE(focal_gamma >= 0.f && focal_gamma < INFINITY, "fu_loss_ce_focal: focal_gamma %g is not a finite number >= 0",
+             (double)focal_gamma);                          // (NaN fails both comparisons)
+  // gamma == 0: launch_ce_loss / launch_ce_grad run the weighted instantiations -- fu_loss_ce_weighted(eps = 0) itself
+  const CeWeighting cw = {class_weight_dev, 1.f, 0.f, c->ce_wsum, weight_sum_out, focal_gamma};
+  return loss_ce(c, "fu_loss_ce_focal", target, ignore_index, &cw, loss_out, confusion_out, n_valid_out, stream);
 }
 
 int fu_loss_bce_dice(fu_ctx* c, const int64_t* target, int ignore_index, float dice_weight, float* loss_out,

@@ -501,15 +501,18 @@ static constexpr int HEAD_MAX_CLS = 8;
 static constexpr int LOSS_PART_FLOATS = 4 * 1024;
 // fu_loss_ce_weighted's extras.  class_weight: fp32 [ncls] on the device or null (all ones); c_nll = 1 - eps,
 // c_smooth = eps / ncls; weight_sum_dev receives D = sum w[t] (fp32), which launch_ce_grad divides by.
+// focal_gamma > 0 (fu_loss_ce_focal; then c_nll = 1, c_smooth = 0): the focal instantiations, each pixel's term times
+// (1 - p[t])^gamma; 0 = the weighted instantiations, untouched.
 struct CeWeighting {
   const float* class_weight;
   float c_nll, c_smooth;
   float* weight_sum_dev;
   float* weight_sum_out;   // optional
+  float focal_gamma = 0.f;
 };
 // CE loss over stored logits, plain (cw == null) or class-weighted and label-smoothed.  partials (LOSS_PART_FLOATS):
 // [nblk][2] (loss sum, valid count as float), weighted [nblk][4] (sum w[t] nll, sum smoothing term, sum w[t], valid
-// count) -> finalize
+// count; focal: sum w[t] u^gamma nll, 0, sum w[t], valid count) -> finalize
 int launch_ce_loss(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
                    const CeWeighting* cw, float* partials, float* loss_out, int64_t* n_valid_dev,
                    int64_t* confusion_accum, int64_t* n_valid_out, unsigned long long* conf_tmp /* [64], zero-initialised */,

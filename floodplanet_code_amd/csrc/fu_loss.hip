@@ -1,4 +1,4 @@
-// Loss kernels of the training step (gfx950): softmax cross entropy (plain and class-weighted / label-smoothed) and
+// Loss kernels of the training step (gfx950): softmax cross entropy (plain, class-weighted / label-smoothed, focal) and
 // BCE + soft Dice over the resident logits, with their deterministic reductions; the NCHW -> NHWC copy of an external
 // logits gradient; the gradient the head backward consumes (upstream factor, fp16 loss scale).
 #include "fu_common.h"
@@ -76,13 +76,44 @@ __device__ __forceinline__ void partial_rows_sum(const float* __restrict__ parti
 // shared, so w = 1, eps = 0 reproduces the plain bits (every extra factor is then an exact 1 or 0).  NC as in k_head_fwd:
 // compile-time class count, 0 = any count up to HEAD_MAX_CLS; the weights are uniform values loaded once per thread.
 // D == 0 gives loss 0 and a zero gradient (the rule of the all-ignored batch).
+//   FOCAL (a WEIGHTED form, gamma > 0; fu_loss_ce_focal), with q = p[t], u = 1 - q:
+//                       loss = sum_i w[t] u^gamma (-log q) / D
+//                       dz_k = w[t] (p_k - [k == t]) mf / D,   mf = u^gamma - gamma q u^(gamma-1) log q
+// FOCAL is a third compile-time flag: the other instantiations hold none of its code (gamma is an argument they ignore).
+// It fills the weighted row of four
+// sums (the smoothing sum stays 0), so k_ce_finalize<true> with c_nll = 1, c_smooth = 0 and the exact-mode sum over the
+// ranks serve it unchanged.  gamma == 0 never gets here: the launchers send it to the WEIGHTED instantiation.
 // ------------------------------------------------------------------------------------------------
-template <int NC, bool WEIGHTED>
+// The focal terms of one pixel, free of cancellation.  e[k] = exp(z[k] - m); u is the OTHER classes' share of the sum (not
+// 1 - q: that is 0 for every q within 2^-24 of 1); -log q is log(se) - (z[t] - m), and log1p(so) where the target holds
+// the maximum (its exponential is then exactly 1, se = 1 + so).  A target outside 0..ncls-1 (an ignored pixel) gives
+// finite values the callers discard.
+template <int KMAX>
+__device__ __forceinline__ void focal_terms(const float (&z)[KMAX], float m, int ncls, int t, float (&e)[KMAX], float& se,
+                                            float& u, float& q, float& nlq) {
+  float et = 0.f, so = 0.f, zt = m;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    if (k < ncls) {
+      e[k] = expf(z[k] - m);
+      if (k == t) { et = e[k]; zt = z[k]; } else so += e[k];
+    }
+  }
+  se = et + so;
+  u = so / se;
+  q = et / se;
+  nlq = (zt == m) ? log1pf(so) : logf(se) - (zt - m);
+}
+// u^gamma for gamma > 0; u == 0 (the other classes' exponentials underflowed): exactly 0, the pixel drops out
+__device__ __forceinline__ float focal_pow(float u, float gamma) { return u > 0.f ? powf(u, gamma) : 0.f; }
+
+template <int NC, bool WEIGHTED, bool FOCAL>
 __global__ __launch_bounds__(CE_BLOCK) void k_ce_loss(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                       int ncls_rt, int ignore_index, int64_t npix,
                                                       const float* __restrict__ class_weight,
                                                       float* __restrict__ partials,
-                                                      unsigned long long* __restrict__ conf_tmp) {
+                                                      unsigned long long* __restrict__ conf_tmp, float gamma) {
+  static_assert(WEIGHTED || !FOCAL, "the focal form is a weighted form");
   constexpr int KMAX = NC ? NC : HEAD_MAX_CLS;
   constexpr int NS = WEIGHTED ? 4 : 2;   // plain: nll sum, valid count; weighted: w[t] nll, smoothing term, w[t], count
   const int ncls = NC ? NC : ncls_rt;
@@ -110,29 +141,39 @@ __global__ __launch_bounds__(CE_BLOCK) void k_ce_loss(const float* __restrict__ 
       }
     }
     if (t != (int64_t)ignore_index && t >= 0 && t < ncls) {
-      float se = 0.f;
+      if constexpr (FOCAL) {
+        float e[KMAX], se, u, q, nlq, wt = 0.f;
+        focal_terms<KMAX>(z, m, ncls, (int)t, e, se, u, q, nlq);
 #pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < ncls) se += expf(z[k] - m);
-      const float lse = m + logf(se);
-      float zt = 0.f;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < ncls && k == (int)t) zt = z[k];
-      if constexpr (WEIGHTED) {
-        float wt = 0.f, sm = 0.f;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-          if (k < ncls) {
-            if (k == (int)t) wt = w[k];
-            sm += w[k] * (lse - z[k]);
-          }
-        }
-        acc[0] += wt * (lse - zt);
-        acc[1] += sm;
+        for (int k = 0; k < KMAX; ++k)
+          if (k < ncls && k == (int)t) wt = w[k];
+        acc[0] += wt * (focal_pow(u, gamma) * nlq);
         acc[2] += wt;
       } else {
-        acc[0] += lse - zt;
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+          if (k < ncls) se += expf(z[k] - m);
+        const float lse = m + logf(se);
+        float zt = 0.f;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+          if (k < ncls && k == (int)t) zt = z[k];
+        if constexpr (WEIGHTED) {
+          float wt = 0.f, sm = 0.f;
+#pragma unroll
+          for (int k = 0; k < KMAX; ++k) {
+            if (k < ncls) {
+              if (k == (int)t) wt = w[k];
+              sm += w[k] * (lse - z[k]);
+            }
+          }
+          acc[0] += wt * (lse - zt);
+          acc[1] += sm;
+          acc[2] += wt;
+        } else {
+          acc[0] += lse - zt;
+        }
       }
       acc[NS - 1] += 1.f;
       atomicAdd(&hist[(int)t * ncls + am], 1u);
@@ -192,17 +233,22 @@ int launch_ce_loss(const float* logits_nhwc, const int64_t* target, int ncls, in
                    int64_t* confusion_accum, int64_t* n_valid_out, unsigned long long* conf_tmp, hipStream_t s) {
   FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "CE: n_classes must be 1..%d", HEAD_MAX_CLS);
   const int nblk = grid_for(npix, CE_BLOCK, CE_MAX_BLOCKS);
-#define FU_CE_LOSS(NC)                                                                                                    \
-  do {                                                                                                                    \
-    if (cw)                                                                                                               \
-      hipLaunchKernelGGL((k_ce_loss<NC, true>), dim3(nblk), dim3(CE_BLOCK), 0, s, logits_nhwc, target, ncls, ignore_index, \
-                         npix, cw->class_weight, partials, conf_tmp);                                                     \
-    else                                                                                                                  \
-      hipLaunchKernelGGL((k_ce_loss<NC, false>), dim3(nblk), dim3(CE_BLOCK), 0, s, logits_nhwc, target, ncls,              \
-                         ignore_index, npix, nullptr, partials, conf_tmp);                                                \
+  const bool focal = cw && cw->focal_gamma > 0.f;     // gamma == 0 is the weighted loss itself: its instantiation, its bits
+#define FU_CE_LOSS_AS(NC, WEIGHTED, FOCAL, CLASS_WEIGHT, GAMMA)                                                    \
+  hipLaunchKernelGGL((k_ce_loss<NC, WEIGHTED, FOCAL>), dim3(nblk), dim3(CE_BLOCK), 0, s, logits_nhwc, target, ncls, \
+                     ignore_index, npix, CLASS_WEIGHT, partials, conf_tmp, GAMMA)
+#define FU_CE_LOSS(NC)                                                  \
+  do {                                                                  \
+    if (focal)                                                          \
+      FU_CE_LOSS_AS(NC, true, true, cw->class_weight, cw->focal_gamma); \
+    else if (cw)                                                        \
+      FU_CE_LOSS_AS(NC, true, false, cw->class_weight, 0.f);            \
+    else                                                                \
+      FU_CE_LOSS_AS(NC, false, false, nullptr, 0.f);                    \
   } while (0)
   FU_NC_SWITCH(ncls, FU_CE_LOSS);
 #undef FU_CE_LOSS
+#undef FU_CE_LOSS_AS
   FU_LAUNCH_CHECK();
   // exact DP: the global sums (loss, N_valid; weighted: D too) before the division
   FU_TRY(sync_sum_over_ranks(partials, (int64_t)nblk * (cw ? 4 : 2), false, s));
@@ -217,12 +263,13 @@ int launch_ce_loss(const float* logits_nhwc, const int64_t* target, int ncls, in
   return 0;
 }
 
-template <int NC, bool WEIGHTED>
+template <int NC, bool WEIGHTED, bool FOCAL>
 __global__ __launch_bounds__(256) void k_ce_grad(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                  int ncls_rt, int ignore_index, int64_t npix,
                                                  const float* __restrict__ class_weight, float c_nll, float c_smooth,
                                                  const int64_t* __restrict__ n_valid, const float* __restrict__ weight_sum,
-                                                 float* __restrict__ dl) {
+                                                 float* __restrict__ dl, float gamma) {
+  static_assert(WEIGHTED || !FOCAL, "the focal form is a weighted form");
   constexpr int KMAX = NC ? NC : HEAD_MAX_CLS;
   const int ncls = NC ? NC : ncls_rt;
   bool live;
@@ -253,6 +300,21 @@ __global__ __launch_bounds__(256) void k_ce_grad(const float* __restrict__ logit
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
       if (k < ncls) { z[k] = logits[p * ncls + k]; m = fmaxf(m, z[k]); }
+    if constexpr (FOCAL) {
+      float e[KMAX], se, u, q, nlq, wt = 0.f;
+      focal_terms<KMAX>(z, m, ncls, (int)t, e, se, u, q, nlq);
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < ncls && (int)t == k) wt = w[k];
+      // mf = u^gamma (1 + gamma q (-log q) / u): -log q / u stays within [1, -log q], where u^(gamma-1) alone overflows
+      // for a denormal u and gamma < 1; u == 0 drops the pixel (no 0^(gamma-1) * 0)
+      const float mf = u > 0.f ? powf(u, gamma) * (1.f + gamma * q * (nlq / u)) : 0.f;
+      const float a = wt * mf * inv, r = 1.f / se;
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)                        // (p_t - 1 is -u, without the cancellation)
+        if (k < ncls) dl[p * ncls + k] = valid ? a * ((int)t == k ? -u : e[k] * r) : 0.f;
+      continue;
+    }
     float se = 0.f;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
@@ -283,17 +345,22 @@ int launch_ce_grad(const float* logits_nhwc, const int64_t* target, int ncls, in
                    const CeWeighting* cw, const int64_t* n_valid_dev, float* dlogits_nhwc, hipStream_t s) {
   FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "CE: n_classes must be 1..%d", HEAD_MAX_CLS);
   const int g = grid_for(npix, 256, 4096);
-#define FU_CE_GRAD(NC)                                                                                                  \
-  do {                                                                                                                  \
-    if (cw)                                                                                                             \
-      hipLaunchKernelGGL((k_ce_grad<NC, true>), dim3(g), dim3(256), 0, s, logits_nhwc, target, ncls, ignore_index, npix, \
-                         cw->class_weight, cw->c_nll, cw->c_smooth, n_valid_dev, cw->weight_sum_dev, dlogits_nhwc);     \
-    else                                                                                                                \
-      hipLaunchKernelGGL((k_ce_grad<NC, false>), dim3(g), dim3(256), 0, s, logits_nhwc, target, ncls, ignore_index,      \
-                         npix, nullptr, 1.f, 0.f, n_valid_dev, nullptr, dlogits_nhwc);                                  \
+  const bool focal = cw && cw->focal_gamma > 0.f;
+#define FU_CE_GRAD_AS(NC, WEIGHTED, FOCAL, CLASS_WEIGHT, C_NLL, C_SMOOTH, WEIGHT_SUM, GAMMA)                        \
+  hipLaunchKernelGGL((k_ce_grad<NC, WEIGHTED, FOCAL>), dim3(g), dim3(256), 0, s, logits_nhwc, target, ncls,         \
+                     ignore_index, npix, CLASS_WEIGHT, C_NLL, C_SMOOTH, n_valid_dev, WEIGHT_SUM, dlogits_nhwc, GAMMA)
+#define FU_CE_GRAD(NC)                                                                                    \
+  do {                                                                                                    \
+    if (focal)                                                                                            \
+      FU_CE_GRAD_AS(NC, true, true, cw->class_weight, 1.f, 0.f, cw->weight_sum_dev, cw->focal_gamma);     \
+    else if (cw)                                                                                          \
+      FU_CE_GRAD_AS(NC, true, false, cw->class_weight, cw->c_nll, cw->c_smooth, cw->weight_sum_dev, 0.f); \
+    else                                                                                                  \
+      FU_CE_GRAD_AS(NC, false, false, nullptr, 1.f, 0.f, nullptr, 0.f);                                   \
   } while (0)
   FU_NC_SWITCH(ncls, FU_CE_GRAD);
 #undef FU_CE_GRAD
+#undef FU_CE_GRAD_AS
   FU_LAUNCH_CHECK();
   return 0;
 }

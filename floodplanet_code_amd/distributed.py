@@ -122,12 +122,13 @@ class DataParallelTrainer:
     def __init__(self, net, lr: float, world_size: int = 1, rank: int = 0, betas=(0.9, 0.999), eps: float = 1e-8,
                  group=None, cap_bytes: int = 16 << 20, exact: bool = False, time_waits: bool = False,
                  graph: bool = False, class_weight=None, label_smoothing: float = 0.0, ema_decay: Optional[float] = None,
-                 ema_warmup: bool = True):
+                 ema_warmup: bool = True, focal_gamma: float = 0.0):
         """exact=False: DDP semantics (per-rank BN statistics and 1/N_valid, gradients averaged).
         exact=True: SyncBN statistics and a global N_valid (HipUNet.enable_exact_sync); the ranks together reproduce
         one device with world_size x the batch, gradients are summed (SURVEY.md 8(e) "exact mode").
         class_weight / label_smoothing: the weighted, label-smoothed cross entropy of HipUNet.loss for every step (defaults:
         the reference's loss); in exact mode its denominator, the summed weight of the valid pixels, is global too.
+        focal_gamma > 0: the focal form of that loss (HipUNet.loss), on the eager, exact and captured paths alike.
         ema_decay: keep a weight EMA on the net (HipUNet.enable_ema(ema_decay, ema_warmup)), moved on inside the fused Adam
         launch of every path -- eager, exact and captured.  It is rank-local and needs no collective: the ranks' parameters
         are identical, so their averages are."""
@@ -135,6 +136,8 @@ class DataParallelTrainer:
             net.enable_ema(ema_decay, ema_warmup)
         self.net, self.lr, self.world_size, self.rank = net, lr, world_size, rank
         self.class_weight, self.label_smoothing = class_weight, float(label_smoothing)
+        from .unet import check_focal_gamma
+        self.focal_gamma = check_focal_gamma(focal_gamma, label_smoothing)
         self.betas, self.eps, self.group, self.cap_bytes = betas, eps, group, cap_bytes
         self.exact = bool(exact) and world_size > 1
         if self.exact:
@@ -223,7 +226,7 @@ class DataParallelTrainer:
         with torch.cuda.graph(g):
             net._forward_raw(self._gx, True, want_logits=False)
             self._gloss = net._loss_raw(self._gt, self._g_ignore, dev, class_weight=self.class_weight,
-                                        label_smoothing=self.label_smoothing)
+                                        label_smoothing=self.label_smoothing, focal_gamma=self.focal_gamma)
             net._backward_raw(None, dev)
             if self._g_ema:
                 _lib.check(lib.fu_adam_ema_step_dev(net._ctx, self._gscal.data_ptr(), net._stream(dev)))
@@ -269,7 +272,7 @@ class DataParallelTrainer:
             self._sync_initial_state(x.device)
         net._forward_raw(x, True, want_logits=False)
         loss = net._loss_raw(target, ignore_index, x.device, class_weight=self.class_weight,
-                             label_smoothing=self.label_smoothing)
+                             label_smoothing=self.label_smoothing, focal_gamma=self.focal_gamma)
         if self.world_size <= 1 and not _FORCE_BLOCKS:
             net._backward_raw(None, x.device)
         else:

@@ -34,6 +34,7 @@ from typing import Dict, Iterable, List, Optional
 import torch
 
 from .models import build_model
+from .unet import check_focal_gamma
 
 DEFAULTS = dict(lr=1e-4, batch_size=10, n_epochs=11, crop_height=300, crop_width=300, ignore_index=0,
                 save_topk_models=3, limit_train_batches=None, limit_val_batches=None, log_image_iter=200,
@@ -176,6 +177,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="cross-entropy class weights: 'balanced' (from the TRAIN split's class frequencies) or one number "
                          "per class")
     ap.add_argument("--label_smoothing", type=float, default=0.0, help="cross-entropy label smoothing in [0, 1)")
+    ap.add_argument("--focal_gamma", type=float, default=0.0, metavar="F",
+                    help="focal loss: every pixel's cross-entropy term times (1 - p[target])^F, F >= 0 (default 0: plain "
+                         "cross entropy); combines with --class_weights, not with --label_smoothing")
     ap.add_argument("--ema_decay", type=float, default=None, metavar="F",
                     help="keep an exponential moving average of the weights with this decay in [0, 1): validation, the "
                          "checkpoint choice and the checkpoint's ema_state_dict use it (default: no EMA)")
@@ -205,8 +209,8 @@ def parse_class_weights(values, n_classes: Optional[int] = None):
 def cfg_from_args(args, class_weights=None) -> dict:
     """The reference-style config of a command line: what fit_model trains with and dumps into the checkpoint.
     class_weights: the resolved numeric weights (the data decides 'balanced' and the class count, so main() resolves them);
-    they, --label_smoothing, --ema_decay and --no_ema_warmup enter model_kwargs only when set, so a plain command line gives
-    the config it always gave."""
+    they, --label_smoothing, --focal_gamma, --ema_decay and --no_ema_warmup enter model_kwargs only when set, so a plain
+    command line gives the config it always gave."""
     norm_mode = None if args.norm_mode == "none" else args.norm_mode
     parsed = parse_class_weights(getattr(args, "class_weights", None), N_CLASSES)
     if class_weights is None and parsed is not None and parsed != "balanced":
@@ -216,6 +220,9 @@ def cfg_from_args(args, class_weights=None) -> dict:
         loss_kwargs["class_weights"] = [float(v) for v in class_weights]
     if float(getattr(args, "label_smoothing", 0.0)) != 0.0:
         loss_kwargs["label_smoothing"] = float(args.label_smoothing)
+    gamma = check_focal_gamma(getattr(args, "focal_gamma", 0.0), getattr(args, "label_smoothing", 0.0))
+    if gamma != 0.0:
+        loss_kwargs["focal_gamma"] = gamma
     if getattr(args, "ema_decay", None) is not None:
         from .ema import check_decay
         loss_kwargs["ema_decay"] = check_decay(args.ema_decay)
@@ -277,7 +284,7 @@ def main(argv: Optional[List[str]] = None) -> dict:
             class_counts = train.class_counts().cpu().numpy()
             cfg = cfg_from_args(args, balanced_class_weights(class_counts, c["ignore_index"]).tolist())
             c.update(cfg)
-            model.set_loss_options(cfg["model"]["model_kwargs"]["class_weights"], model.label_smoothing)
+            model.set_loss_options(cfg["model"]["model_kwargs"]["class_weights"], model.label_smoothing, model.focal_gamma)
     else:
         common = dict(seed=c["seed_num"], ignore_index=c["ignore_index"], num_workers=args.n_workers,
                       device_assembly=True, device_resize=True)

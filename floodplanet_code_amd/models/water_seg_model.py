@@ -11,7 +11,9 @@ names; the network, the loss, the backward pass and the metric counters run in l
     nn.CrossEntropyLoss(ignore_index=None) fails at call time.
 Extra keyword arguments (not in the reference): ``precision`` ('fp32' | 'bf16' | 'fp16'), ``base_channels``,
 ``class_weights`` (n_classes finite values >= 0) and ``label_smoothing`` in [0, 1): the weighted, label-smoothed cross
-entropy of nn.CrossEntropyLoss(weight, ignore_index, label_smoothing), in the fused loss kernels; ``ema_decay`` in [0, 1)
+entropy of nn.CrossEntropyLoss(weight, ignore_index, label_smoothing), in the fused loss kernels; ``focal_gamma`` >= 0:
+every pixel's cross-entropy term times (1 - p[target])^focal_gamma (the focal loss; not together with label smoothing;
+``loss_func`` stays the plain nn.CrossEntropyLoss); ``ema_decay`` in [0, 1)
 and ``ema_warmup``: an exponential moving average of the weights, updated inside the fused Adam launch, that validation and
 test steps evaluate and that checkpoints carry as the top-level entry ``ema_state_dict`` (state_dict() stays the raw
 weights under the reference's keys).
@@ -28,19 +30,20 @@ import torch.optim as optim
 from ..lightning_compat import LightningModule
 from ..metrics import SegmentationMetrics
 from ..ema import check_decay
-from ..unet import HipAdam, HipUNet, check_class_weight, check_label_smoothing
+from ..unet import HipAdam, HipUNet, check_class_weight, check_focal_gamma, check_label_smoothing
 
 
 class WaterSegmentationModel(LightningModule):
 
     def __init__(self, in_channels, n_classes, lr, log_image_iter=50, to_rgb_fcn=None, ignore_index=None,
                  optimizer_name='adam', precision='fp32', base_channels=64, class_weights=None, label_smoothing=0.0,
-                 ema_decay=None, ema_warmup=True):
+                 ema_decay=None, ema_warmup=True, focal_gamma=0.0):
         super().__init__()
         # checked on the host before anything touches the GPU; kept as plain Python numbers (checkpoint hyper_parameters)
         self.class_weights = (None if class_weights is None
                               else tuple(float(v) for v in check_class_weight(class_weights, n_classes)))
         self.label_smoothing = check_label_smoothing(label_smoothing)
+        self.focal_gamma = check_focal_gamma(focal_gamma, self.label_smoothing)
         self.ema_decay = None if ema_decay is None else check_decay(ema_decay)
         self.ema_warmup = bool(ema_warmup)
         self.lr = lr
@@ -65,12 +68,14 @@ class WaterSegmentationModel(LightningModule):
         self.to_rgb_fcn = to_rgb_fcn
         self.log_image_iter = log_image_iter
 
-    def set_loss_options(self, class_weights=None, label_smoothing=0.0):
-        """Replace the loss's class weights / label smoothing after construction (weights that are counted from data the
-        model's own device context serves, fit's `--class_weights balanced`).  Same checks as the constructor."""
+    def set_loss_options(self, class_weights=None, label_smoothing=0.0, focal_gamma=0.0):
+        """Replace the loss's class weights / label smoothing / focal exponent after construction (weights that are counted
+        from data the model's own device context serves, fit's `--class_weights balanced`).  Same checks as the
+        constructor."""
         self.class_weights = (None if class_weights is None
                               else tuple(float(v) for v in check_class_weight(class_weights, self.n_classes)))
         self.label_smoothing = check_label_smoothing(label_smoothing)
+        self.focal_gamma = check_focal_gamma(focal_gamma, self.label_smoothing)
         self._make_loss_func()
         return self
 
@@ -147,7 +152,8 @@ class WaterSegmentationModel(LightningModule):
         (`if False:`, water_seg_model.py:116), so the training path never does; the counts stay on the device."""
         images = self._gather_sources(batch)
         out = self.model.loss(images, batch['target'], self._loss_ignore, return_logits=want_logits,
-                              class_weight=self.class_weights, label_smoothing=self.label_smoothing)
+                              class_weight=self.class_weights, label_smoothing=self.label_smoothing,
+                              focal_gamma=self.focal_gamma)
         loss, output = out if want_logits else (out, None)
         counts = self.model.pop_confusion()
         return loss, output, counts

@@ -501,12 +501,17 @@ class HipUNet(nn.Module):
         return dev_w
 
     def last_weighted_sums(self):
-        """(n_valid int64 scalar, weight_sum fp32 scalar) on the device, written by the last fu_loss_ce_weighted call: the
-        valid pixels and D = the sum of their targets' class weights (the loss's denominator).  None before such a call."""
+        """(n_valid int64 scalar, weight_sum fp32 scalar) on the device, written by the last fu_loss_ce_weighted or
+        fu_loss_ce_focal call: the valid pixels and D = the sum of their targets' class weights (the loss's denominator).
+        None before such a call."""
         return getattr(self, "_wce_sums", None)
 
     def _loss_raw(self, target: torch.Tensor, ignore_index: int, device, kind: str = "ce",
-                  dice_weight: float = 1.0, class_weight=None, label_smoothing: float = 0.0) -> torch.Tensor:
+                  dice_weight: float = 1.0, class_weight=None, label_smoothing: float = 0.0,
+                  focal_gamma: float = 0.0) -> torch.Tensor:
+        gamma = check_focal_gamma(focal_gamma, label_smoothing)      # on the host, before the library is loaded
+        if gamma != 0.0 and kind != "ce":
+            raise ValueError(f"focal_gamma belongs to kind='ce'; kind={kind!r} does not take it")
         lib = _lib.load()
         target = target.contiguous().long()
         loss = torch.empty((), dtype=torch.float32, device=device)
@@ -521,7 +526,7 @@ class HipUNet(nn.Module):
             raise ValueError(f"unknown loss kind {kind!r}")
         if self._confusion is None or self._confusion.device != device:
             self._confusion = torch.zeros(self.n_classes * self.n_classes, dtype=torch.int64, device=device)
-        if not weighted:                 # the reference's loss: the same call, the same kernels as ever
+        if not weighted and gamma == 0.0:     # the reference's loss: the same call, the same kernels as ever
             check(lib.fu_loss_ce(self._ctx, ptr(target), int(ignore_index), ptr(loss), ptr(self._confusion), None,
                                  self._stream(device)))
             return loss
@@ -531,6 +536,10 @@ class HipUNet(nn.Module):
         if sums is None or sums[0].device != torch.device(device):
             sums = self._wce_sums = (torch.zeros((), dtype=torch.int64, device=device),
                                      torch.zeros((), dtype=torch.float32, device=device))
+        if gamma != 0.0:                 # focal modulation of the (weighted) cross entropy; gamma == 0 stays on its old route
+            check(lib.fu_loss_ce_focal(self._ctx, ptr(target), int(ignore_index), ptr(cw), gamma, ptr(loss),
+                                       ptr(self._confusion), ptr(sums[0]), ptr(sums[1]), self._stream(device)))
+            return loss
         check(lib.fu_loss_ce_weighted(self._ctx, ptr(target), int(ignore_index), ptr(cw), eps, ptr(loss),
                                       ptr(self._confusion), ptr(sums[0]), ptr(sums[1]), self._stream(device)))
         return loss
@@ -622,28 +631,34 @@ class HipUNet(nn.Module):
 
     def loss(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int,
              return_logits: bool = False, kind: str = "ce", dice_weight: float = 1.0, class_weight=None,
-             label_smoothing: float = 0.0):
+             label_smoothing: float = 0.0, focal_gamma: float = 0.0):
         """Fused forward + CrossEntropyLoss(ignore_index) (+ NaN guard) of water_seg_model.py:101-106
         (kind='ce', the reference's loss) or the BCE + soft-Dice extension (kind='bce_dice').
         kind='ce' also takes class_weight (n_classes finite values >= 0: a sequence or a tensor) and label_smoothing in
         [0, 1): nn.CrossEntropyLoss(weight, ignore_index, label_smoothing) in the fused kernels (fu_loss_ce_weighted), with
-        loss 0 and a zero gradient where the summed weight of the valid pixels is 0.  With both at their defaults the
-        reference's loss runs exactly as before.
+        loss 0 and a zero gradient where the summed weight of the valid pixels is 0.  focal_gamma > 0 (kind='ce', without
+        label smoothing) multiplies every pixel's term by (1 - p[target])^focal_gamma, the focal loss of Lin et al.
+        (fu_loss_ce_focal), normalised by the same summed weight.  With all three at their defaults the reference's loss
+        runs exactly as before.
         The returned loss is differentiable: ``loss.backward()`` runs the HIP backward."""
         if self.training and torch.is_grad_enabled():
             params = [p for _, p, _, _ in self._table]
             out = _UNetLossFn.apply(self, x, target, int(ignore_index), bool(return_logits), kind,
-                                    float(dice_weight), class_weight, float(label_smoothing), *params)
+                                    float(dice_weight), class_weight, float(label_smoothing), float(focal_gamma),
+                                    *params)
             return out if return_logits else out[0]
         logits = self._forward_raw(x, self.training, want_logits=return_logits)
-        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, class_weight, label_smoothing)
+        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, class_weight, label_smoothing,
+                              focal_gamma)
         return (loss, logits) if return_logits else loss
 
     def train_step(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int, kind: str = "ce",
-                   dice_weight: float = 1.0, class_weight=None, label_smoothing: float = 0.0) -> torch.Tensor:
+                   dice_weight: float = 1.0, class_weight=None, label_smoothing: float = 0.0,
+                   focal_gamma: float = 0.0) -> torch.Tensor:
         """forward + loss + backward without autograd; gradients land in the flat buffer / p.grad."""
         self._forward_raw(x, True, want_logits=False)
-        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, class_weight, label_smoothing)
+        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, class_weight, label_smoothing,
+                              focal_gamma)
         self._backward_raw(None, _device_of(x))
         self.attach_grads()
         return loss
@@ -711,6 +726,19 @@ def check_label_smoothing(label_smoothing) -> float:
     if not 0.0 <= eps < 1.0:          # (NaN fails both comparisons)
         raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing!r}")
     return eps
+
+
+def check_focal_gamma(focal_gamma, label_smoothing=0.0) -> float:
+    """The focal exponent as a float.  ValueError unless it is finite and >= 0, and 0 wherever label smoothing is set: a
+    smoothed focal loss has no agreed definition."""
+    import math
+    gamma = float(focal_gamma)
+    if not (math.isfinite(gamma) and gamma >= 0.0):
+        raise ValueError(f"focal_gamma must be finite and >= 0, got {focal_gamma!r}")
+    if gamma != 0.0 and float(label_smoothing) != 0.0:
+        raise ValueError(f"focal_gamma={gamma} together with label_smoothing={label_smoothing!r}: a smoothed focal loss "
+                         "is not defined here, set one of them to 0")
+    return gamma
 
 
 def _device_of(x):
@@ -785,12 +813,13 @@ class _UNetLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module: HipUNet, x, target, ignore_index, want_logits, kind, dice_weight, class_weight,
-                label_smoothing, *params):
+                label_smoothing, focal_gamma, *params):
         ctx.module = module
         ctx.device = _device_of(x)
         logits = module._forward_raw(x, True, want_logits=want_logits)
         ctx.generation = module._generation
-        loss = module._loss_raw(target, ignore_index, ctx.device, kind, dice_weight, class_weight, label_smoothing)
+        loss = module._loss_raw(target, ignore_index, ctx.device, kind, dice_weight, class_weight, label_smoothing,
+                                focal_gamma)
         if logits is None:
             logits = torch.empty(0, device=ctx.device)
         ctx.mark_non_differentiable(logits)
@@ -805,7 +834,7 @@ class _UNetLossFn(torch.autograd.Function):
         check(_lib.load().fu_scale_loss_grad(m._ctx, ptr(dl), m._stream(ctx.device)))
         saved, alias = _save_accumulated(m)
         m._backward_raw(None, ctx.device)
-        return (None,) * 9 + _return_param_grads(m, saved, alias)
+        return (None,) * 10 + _return_param_grads(m, saved, alias)
 
 
 class HipAdam(torch.optim.Adam):

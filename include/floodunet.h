@@ -16,6 +16,7 @@
  *   fu_loss_ce                  nn.CrossEntropyLoss(ignore_index) + nan_to_num + argmax + metric counts
  *                                                                            st_water_seg/models/water_seg_model.py:40,103-113
  *   fu_loss_ce_weighted         (new) nn.CrossEntropyLoss(weight, ignore_index, label_smoothing) on the same path
+ *   fu_loss_ce_focal            (new) the same with focal modulation (1 - p[t])^gamma of every pixel's term
  *   fu_label_class_counts       (new) class frequencies of resident label rasters, for "balanced" weights
  *   fu_backward[_block]         loss.backward() issued by Lightning's automatic optimisation
  *                                                                            st_water_seg/fit.py:95-97
@@ -160,6 +161,21 @@ int fu_loss_ce(fu_ctx* ctx, const int64_t* target, int ignore_index, float* loss
 int fu_loss_ce_weighted(fu_ctx* ctx, const int64_t* target, int ignore_index, const float* class_weight_dev,
                         float label_smoothing, float* loss_out, int64_t* confusion_out, int64_t* n_valid_out,
                         float* weight_sum_out, fu_stream stream);
+/* Focal cross entropy (Lin et al., "Focal Loss for Dense Object Detection"), class-weighted (added within ABI 5: purely
+ * additive, no version bump; the reference has no such loss -- the specification is tests/tools/focal_ref.py).  With
+ * p = softmax(z), q = p[t], u = 1 - q, w = class_weight, gamma = focal_gamma and the sums over the valid pixels:
+ *   loss = sum_i w[t_i] u_i^gamma (-log q_i) / D,   D = sum_i w[t_i];
+ *   dL/dz_k = w[t] (p_k - [k == t]) m / D,          m = u^gamma - gamma q u^(gamma-1) log q.
+ * u is formed as the other classes' exponentials over the total and log q as (z_t - max) - log(sum) (log1p of the others'
+ * sum where the target holds the maximum), so neither loses digits for q near 1.  u == 0 (the others' exponentials
+ * underflow in fp32) with gamma > 0: the pixel contributes loss 0 and gradient 0, never a NaN.  D == 0: loss 0 and a
+ * zero gradient, as fu_loss_ce_weighted.  focal_gamma must be finite and >= 0.  focal_gamma == 0 runs
+ * fu_loss_ce_weighted's kernels with label_smoothing 0: the same bits (and with NULL weights fu_loss_ce's).  Label smoothing
+ * has no agreed focal form and no argument here.  Every other argument, the counts (pixels, not weights), the
+ * reductions, exact data-parallel mode and the state rules: as fu_loss_ce_weighted. */
+int fu_loss_ce_focal(fu_ctx* ctx, const int64_t* target, int ignore_index, const float* class_weight_dev,
+                     float focal_gamma, float* loss_out, int64_t* confusion_out, int64_t* n_valid_out,
+                     float* weight_sum_out, fu_stream stream);
 /* North-star extension (no reference counterpart; specification = oracle/unet_oracle.py:bce_dice_loss):
  * BCE on p = softmax(z)[1] vs [target == 1] + dice_weight * soft Dice, over target != ignore_index, fp32 wave-shuffle
  * reductions; stores its logits gradient for fu_backward like fu_loss_ce. */

@@ -1,18 +1,20 @@
 """Time per call of the fused cross-entropy entry points on one GPU, training mode (loss + stored logits gradient), at the
 bench's loss shape: 16 tiles of 256 x 256, 3 classes, ignore_index 0.  Device events around every call, median:
 
-  ce            fu_loss_ce            (k_ce_loss<3, false> + k_ce_finalize<false> + k_ce_grad<3, false>): the reference's
+  ce            fu_loss_ce            (k_ce_loss<3, false, false> + k_ce_finalize<false> + k_ce_grad<3, false, false>): the reference's
                 loss, the default path;
-  ce_weighted   fu_loss_ce_weighted   (k_ce_loss<3, true> + k_ce_finalize<true> + k_ce_grad<3, true>) with class weights and
+  ce_weighted   fu_loss_ce_weighted   (k_ce_loss<3, true, false> + k_ce_finalize<true> + k_ce_grad<3, true, false>) with class weights and
                 label smoothing 0.1;
+  ce_focal      fu_loss_ce_focal      (k_ce_loss<3, true, true> + k_ce_finalize<true> + k_ce_grad<3, true, true>) with the
+                same class weights and gamma = 2, same shape, same run;
   label_counts  fu_label_class_counts on 64 whole label rasters of 1024 x 1024 (64 MiB of uint8), one launch.
 
     python tools/loss_bench.py [--launches 200] [--warmup 20] [--parent_ce_us X]
     python tools/loss_bench.py --ce_only          # uses nothing newer than fu_loss_ce: runs on the parent commit too
 
 --parent_ce_us: `ce_us` of this tool's --ce_only run on the parent commit's build, same box; both per-call numbers are then
-stated against it (`ce_vs_parent`, `ce_weighted_vs_parent`).  Nothing is gated on the ratios: the weighted loss is a
-capability; both are instantiations of one kernel family (fu_loss.hip).  Prints one JSON line."""
+stated against it (`ce_vs_parent`, `ce_weighted_vs_parent`).  Nothing is gated on the ratios or on `ce_focal_us`: the weighted
+and focal losses are capabilities; all three are instantiations of one kernel family (fu_loss.hip).  Prints one JSON line."""
 from __future__ import annotations
 
 import argparse
@@ -66,6 +68,8 @@ def main():
         net._class_weight_dev(w, dev)                      # (validated and uploaded once, outside the timed calls)
         res["ce_weighted_us"] = _median_us(lambda: net._loss_raw(target, IGNORE, dev, class_weight=w, label_smoothing=0.1),
                                            args.launches, args.warmup)
+        res["ce_focal_us"] = _median_us(lambda: net._loss_raw(target, IGNORE, dev, class_weight=w, focal_gamma=2.0),
+                                        args.launches, args.warmup)
         labels = [torch.randint(0, 3, (1024, 1024), device=dev, generator=g, dtype=torch.uint8) for _ in range(64)]
         entries = [(lab, (0, 0, 1024, 1024)) for lab in labels]
         counts = torch.zeros(N_CLASSES, dtype=torch.int64, device=dev)
