@@ -162,6 +162,7 @@ SIGNATURES = {
     "fu_scene_train_tiles": (_i, [_p, _i, C.POINTER(FuSceneTrainEntry), _i, _i, _i, _i, _p, _p, _f, _i64, _i64, _p, _p, _p, _p,
                                   _p]),
     "fu_label_class_counts": (_i, [_p, _i, C.POINTER(FuSceneTrainEntry), _i64, _i, _p, _p]),
+    "fu_label_box_counts": (_i, [_p, _i, C.POINTER(FuSceneTrainEntry), _p, _p]),
     "fu_resize_lanczos4_tiles": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "fu_assemble_tiles": (_i, [C.POINTER(_p), C.POINTER(C.c_int32), _i, _i, _i, _i, _p, _p, _i, _p, _p, _f, _p, _p, _p, _p]),
     "fu_band_stats_workspace_bytes": (_i64, [_i, _i]),

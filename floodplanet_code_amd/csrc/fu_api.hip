@@ -676,6 +676,11 @@ int fu_label_class_counts(fu_ctx* c, int n, const fu_scene_train_entry* entries,
   return launch_label_class_counts(c->train_table, n, entries, nodata_value, n_classes, counts_out, (hipStream_t)stream);
 }
 
+int fu_label_box_counts(fu_ctx* c, int n, const fu_scene_train_entry* entries, int64_t* counts_out, fu_stream stream) {
+  FU_REQUIRE(c && entries && counts_out, "fu_label_box_counts: null context / entries / counts_out");
+  return launch_label_box_counts(c->train_table, n, entries, counts_out, (hipStream_t)stream);
+}
+
 int64_t fu_band_stats_workspace_bytes(int n_channels, int n_bins) {
   if (n_channels < 1 || n_bins < 0) return 0;
   return band_stats_workspace_bytes(n_channels, n_bins);

@@ -574,6 +574,9 @@ int launch_scene_train_tiles(DeviceTable& table, int n, const fu_scene_train_ent
 // checked, uploaded and launched in the same way
 int launch_label_class_counts(DeviceTable& table, int n, const fu_scene_train_entry* entries, int64_t nodata_value,
                               int n_classes, int64_t* counts, hipStream_t s);
+// fu_label_box_counts: counts[i][0..2] = #pixels of entry i's label box by raw category (other / raw 2 / raw 0), written;
+// the same entry check, upload and one launch
+int launch_label_box_counts(DeviceTable& table, int n, const fu_scene_train_entry* entries, int64_t* counts, hipStream_t s);
 // fu_band_stats: the caller's per-channel accumulators (all ADDED to) and the histogram's geometry
 struct BandAccum {
   int64_t* count; double* sum; double* sumsq; float* vmin; float* vmax; int64_t* n_nonfinite;

@@ -1,8 +1,8 @@
 // Data-preparation kernels (gfx950): what turns rasters that are already in HBM into training and inference batches --
 // tile augmentation, tile assembly and scene crops, Lanczos-4 resampling, training tiles straight from resident scenes,
 // label class counts, streaming band statistics.  None of them runs inside a training step.  The entry points that take a
-// table of host entries (fu_scene_crops, fu_scene_train_tiles, fu_label_class_counts) are validated here, next to the
-// kernels that trust the table.
+// table of host entries (fu_scene_crops, fu_scene_train_tiles, fu_label_class_counts, fu_label_box_counts) are validated
+// here, next to the kernels that trust the table.
 #include "../../include/floodunet.h"
 #include "fu_common.h"
 
@@ -354,8 +354,12 @@ __device__ __forceinline__ float normalise(float v, bool norm, float m, float sd
 }
 
 // raw label value -> class (floodplanet.py:586-596): 2 flood -> 1, 0 no data -> nodata_value, anything else -> 0
+// The one statement of "raw label byte -> category": 0 = neither 0 nor 2 (decodes to class 0), 1 = raw 2 (decodes to class
+// 1), 2 = raw 0 (no data).  decode_label and both label-count kernels go through it.
+__device__ __forceinline__ int label_category(uint8_t raw) { return raw == 2 ? 1 : (raw == 0 ? 2 : 0); }
 __device__ __forceinline__ int64_t decode_label(uint8_t raw, int64_t nodata_value) {
-  return raw == 2 ? (int64_t)1 : (raw == 0 ? nodata_value : (int64_t)0);
+  const int k = label_category(raw);
+  return k == 2 ? nodata_value : (int64_t)k;
 }
 
 template <int PX>
@@ -544,10 +548,10 @@ __global__ __launch_bounds__(256) void k_label_class_counts(const LabelBox* __re
   unsigned c0 = 0, c1 = 0, cn = 0;
   for (unsigned i = blockIdx.y * 256u + threadIdx.x; i < npx; i += gridDim.y * 256u) {
     const unsigned y = i / (unsigned)J.dw, x = i - y * (unsigned)J.dw;
-    const uint8_t raw = J.label[(int64_t)y * J.scene_w + x];
-    c1 += raw == 2 ? 1u : 0u;
-    cn += raw == 0 ? 1u : 0u;
-    c0 += (raw != 2 && raw != 0) ? 1u : 0u;
+    const int k = label_category(J.label[(int64_t)y * J.scene_w + x]);
+    c0 += k == 0 ? 1u : 0u;
+    c1 += k == 1 ? 1u : 0u;
+    cn += k == 2 ? 1u : 0u;
   }
   if (c0) atomicAdd(&bins[0], c0);
   if (c1) atomicAdd(&bins[1], c1);
@@ -559,13 +563,12 @@ __global__ __launch_bounds__(256) void k_label_class_counts(const LabelBox* __re
   }
 }
 
-// every check before anything is launched or copied: a rejected call leaves the stream and the counts untouched
-int launch_label_class_counts(DeviceTable& table, int n, const fu_scene_train_entry* entries, int64_t nodata_value,
-                              int n_classes, int64_t* counts, hipStream_t s) {
-  const char* fn = "fu_label_class_counts";
-  FU_REQUIRE(n >= 1 && n_classes >= 1, "%s: n = %d, n_classes = %d (both must be >= 1)", fn, n, n_classes);
-  std::vector<LabelBox> boxes((size_t)n);
-  int64_t max_px = 0;
+// The entry check of both label-count calls (fn goes into the messages): label, raster size and box of every entry, and
+// the device form of each; *max_px, when given, receives the largest box area.  Nothing is copied or launched here.
+static int check_label_boxes(const char* fn, int n, const fu_scene_train_entry* entries, std::vector<LabelBox>& boxes,
+                             int64_t* max_px) {
+  boxes.resize((size_t)n);
+  int64_t mx = 0;
   for (int i = 0; i < n; ++i) {
     const fu_scene_train_entry& E = entries[i];
     const int dh = E.hE - E.h0, dw = E.wE - E.w0;
@@ -577,13 +580,98 @@ int launch_label_class_counts(DeviceTable& table, int n, const fu_scene_train_en
                E.scene_w);
     FU_REQUIRE(dh >= 1 && dw >= 1, "%s: entry %d: box [%d:%d, %d:%d] is empty", fn, i, E.h0, E.hE, E.w0, E.wE);
     boxes[i] = LabelBox{E.label + (int64_t)E.h0 * E.scene_w + E.w0, E.scene_w, dh, dw};
-    max_px = std::max<int64_t>(max_px, (int64_t)dh * dw);
+    mx = std::max<int64_t>(mx, (int64_t)dh * dw);
   }
+  if (max_px) *max_px = mx;
+  return 0;
+}
+
+// every check before anything is launched or copied: a rejected call leaves the stream and the counts untouched
+int launch_label_class_counts(DeviceTable& table, int n, const fu_scene_train_entry* entries, int64_t nodata_value,
+                              int n_classes, int64_t* counts, hipStream_t s) {
+  const char* fn = "fu_label_class_counts";
+  FU_REQUIRE(n >= 1 && n_classes >= 1, "%s: n = %d, n_classes = %d (both must be >= 1)", fn, n, n_classes);
+  std::vector<LabelBox> boxes;
+  int64_t max_px = 0;
+  FU_TRY(check_label_boxes(fn, n, entries, boxes, &max_px));
   FU_TRY(table.upload(boxes.data(), (size_t)n * sizeof(LabelBox), sizeof(LabelBox), s));
   // 16 pixels per thread where the largest box allows it, at most 64 blocks per box
   const dim3 grid((unsigned)n, (unsigned)grid_for(max_px, 256 * 16, 64));
   hipLaunchKernelGGL(k_label_class_counts, grid, dim3(256), 0, s, static_cast<const LabelBox*>(table.dev), nodata_value,
                      n_classes, reinterpret_cast<unsigned long long*>(counts));
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The label content of every box of a table, separately (fu_label_box_counts), for content-aware tile sampling: row i of
+// the output = the pixels of box i by label_category.  One workgroup per box, which owns its row of the output: no global
+// atomic, no pre-zeroing, no dependence on launch order.  A row of the box is seen as the 16-byte aligned chunks of memory
+// it touches, at most cpr = (dw + 30) / 16 of them (15 bytes of head, then whole chunks); the block's threads stride
+// over the dh * cpr (row, chunk) pairs.  A chunk that lies wholly inside the row is one 16-byte load, the partial chunk at
+// either end is read byte by byte, and a pair past the row's last chunk is skipped.  Counters: three registers per
+// thread, a xor tree over the wave, a three-bin LDS fold over the four waves, three 64-bit stores by thread 0.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_label_box_counts(const LabelBox* __restrict__ boxes, int64_t* __restrict__ counts) {
+  __shared__ unsigned int bins[3];
+  if (threadIdx.x < 3) bins[threadIdx.x] = 0u;
+  __syncthreads();
+  const LabelBox J = boxes[blockIdx.x];
+  const unsigned cpr = ((unsigned)J.dw + 30u) / 16u;
+  // dh * dw < 2^31 (check_label_boxes), so dh * cpr <= dh * dw * 31 / 16 < 2^32
+  const unsigned n_items = (unsigned)J.dh * cpr;
+  unsigned c[3] = {0u, 0u, 0u};
+  for (unsigned i = threadIdx.x; i < n_items; i += 256u) {
+    const unsigned y = i / cpr, k = i - y * cpr;
+    const uint8_t* __restrict__ row = J.label + (int64_t)y * J.scene_w;
+    const int head = (int)(reinterpret_cast<uintptr_t>(row) & 15);   // bytes of the first chunk that precede the row
+    const int x0 = (int)k * 16 - head;                               // the chunk is row[x0, x0 + 16)
+    if (x0 >= J.dw) continue;
+    if (x0 >= 0 && x0 + 16 <= J.dw) {
+      const uint4 v = *reinterpret_cast<const uint4*>(row + x0);
+      const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const int cat = label_category((uint8_t)(w[q] >> (8 * b)));
+          c[0] += cat == 0 ? 1u : 0u;
+          c[1] += cat == 1 ? 1u : 0u;
+          c[2] += cat == 2 ? 1u : 0u;
+        }
+      }
+    } else {
+      for (int x = max(x0, 0); x < min(x0 + 16, J.dw); ++x) {
+        const int cat = label_category(row[x]);
+        c[0] += cat == 0 ? 1u : 0u;
+        c[1] += cat == 1 ? 1u : 0u;
+        c[2] += cat == 2 ? 1u : 0u;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    for (int o = 32; o > 0; o >>= 1) c[j] += __shfl_xor(c[j], o, 64);
+    if ((threadIdx.x & 63) == 0 && c[j]) atomicAdd(&bins[j], c[j]);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t* __restrict__ o = counts + (int64_t)blockIdx.x * 3;
+    o[0] = (int64_t)bins[0];
+    o[1] = (int64_t)bins[1];
+    o[2] = (int64_t)bins[2];
+  }
+}
+
+// every check before anything is launched or copied: a rejected call leaves the stream and the counts untouched
+int launch_label_box_counts(DeviceTable& table, int n, const fu_scene_train_entry* entries, int64_t* counts, hipStream_t s) {
+  const char* fn = "fu_label_box_counts";
+  FU_REQUIRE(n >= 1, "%s: n = %d (must be >= 1)", fn, n);
+  std::vector<LabelBox> boxes;
+  FU_TRY(check_label_boxes(fn, n, entries, boxes, nullptr));
+  FU_TRY(table.upload(boxes.data(), (size_t)n * sizeof(LabelBox), sizeof(LabelBox), s));
+  hipLaunchKernelGGL(k_label_box_counts, dim3((unsigned)n), dim3(256), 0, s, static_cast<const LabelBox*>(table.dev),
+                     counts);
   FU_LAUNCH_CHECK();
   return 0;
 }

@@ -23,14 +23,47 @@ __all__ = ["label_class_counts", "label_class_counts_host", "balanced_class_weig
 Box = Tuple[int, int, int, int]         # h0, w0, hE, wE
 
 
-def _check_box(i: int, shape, box) -> Box:
+def _check_box(i: int, shape, box, fn: str = "label_class_counts") -> Box:
     h0, w0, hE, wE = (int(v) for v in box)
     H, W = int(shape[0]), int(shape[1])
     if h0 < 0 or w0 < 0 or hE > H or wE > W:
-        raise ValueError(f"label_class_counts: entry {i}: box [{h0}:{hE}, {w0}:{wE}] lies outside its raster {H}x{W}")
+        raise ValueError(f"{fn}: entry {i}: box [{h0}:{hE}, {w0}:{wE}] lies outside its raster {H}x{W}")
     if hE - h0 < 1 or wE - w0 < 1:
-        raise ValueError(f"label_class_counts: entry {i}: box [{h0}:{hE}, {w0}:{wE}] is empty")
+        raise ValueError(f"{fn}: entry {i}: box [{h0}:{hE}, {w0}:{wE}] is empty")
     return h0, w0, hE, wE
+
+
+def _check_host_entries(entries, fn: str = "label_class_counts") -> List[Tuple[np.ndarray, Box]]:
+    """The entry check both host statements share (label_class_counts_host, sampling.label_box_counts_host)."""
+    checked = []
+    for i, (label, box) in enumerate(entries):
+        if label is None:
+            raise ValueError(f"{fn}: entry {i}: no label raster")
+        label = np.asarray(label)
+        if label.dtype != np.uint8 or label.ndim != 2:
+            raise ValueError(f"{fn}: entry {i}: the label must be uint8 [H, W], got {label.dtype} {label.shape}")
+        checked.append((label, _check_box(i, label.shape, box, fn)))
+    return checked
+
+
+def _device_table(entries, fn: str = "label_class_counts"):
+    """entries = [(uint8 label raster on the ROCm device, box), ...] -> (the fu_scene_train_entry table both device calls
+    take, the device)."""
+    from .. import _lib
+    n = len(entries)
+    if n < 1:
+        raise ValueError(f"{fn}: no entries")
+    dev = entries[0][0].device
+    if dev.type != "cuda":
+        raise RuntimeError(f"{fn} runs only on a ROCm GPU; the host statement is {fn}_host")
+    table = (_lib.FuSceneTrainEntry * n)()
+    for i, (label, (h0, w0, hE, wE)) in enumerate(entries):
+        if label.dtype != torch.uint8 or label.dim() != 2 or not label.is_contiguous() or label.device != dev:
+            raise ValueError(f"{fn}: entry {i}: the label must be contiguous uint8 [H, W] on {dev}, got "
+                             f"{tuple(label.shape)} {label.dtype} on {label.device}")
+        table[i] = _lib.FuSceneTrainEntry(None, label.data_ptr(), label.shape[0], label.shape[1], int(h0), int(w0), int(hE),
+                                          int(wE), 0, 0.0)
+    return table, dev
 
 
 def label_class_counts_host(entries: Sequence[Tuple[np.ndarray, Box]], nodata_value: int, n_classes: int,
@@ -41,14 +74,7 @@ def label_class_counts_host(entries: Sequence[Tuple[np.ndarray, Box]], nodata_va
     n_classes, nodata_value = int(n_classes), int(nodata_value)
     if n_classes < 1 or len(entries) < 1:
         raise ValueError(f"label_class_counts: {len(entries)} entries, n_classes = {n_classes} (both must be >= 1)")
-    checked = []
-    for i, (label, box) in enumerate(entries):
-        if label is None:
-            raise ValueError(f"label_class_counts: entry {i}: no label raster")
-        label = np.asarray(label)
-        if label.dtype != np.uint8 or label.ndim != 2:
-            raise ValueError(f"label_class_counts: entry {i}: the label must be uint8 [H, W], got {label.dtype} {label.shape}")
-        checked.append((label, _check_box(i, label.shape, box)))
+    checked = _check_host_entries(entries)
     out = np.zeros(n_classes, dtype=np.int64) if counts is None else counts
     for label, (h0, w0, hE, wE) in checked:
         raw = np.bincount(label[h0:hE, w0:wE].reshape(-1), minlength=256)
@@ -66,19 +92,8 @@ def label_class_counts(ctx, entries: Sequence[Tuple[torch.Tensor, Box]], nodata_
     from .. import _lib
     if ctx is None:
         raise ValueError("label_class_counts: no fu_ctx (run or prepare a forward first)")
+    table, dev = _device_table(entries)
     n = len(entries)
-    if n < 1:
-        raise ValueError("label_class_counts: no entries")
-    dev = entries[0][0].device
-    if dev.type != "cuda":
-        raise RuntimeError("label_class_counts runs only on a ROCm GPU; the host statement is label_class_counts_host")
-    table = (_lib.FuSceneTrainEntry * n)()
-    for i, (label, (h0, w0, hE, wE)) in enumerate(entries):
-        if label.dtype != torch.uint8 or label.dim() != 2 or not label.is_contiguous() or label.device != dev:
-            raise ValueError(f"label_class_counts: entry {i}: the label must be contiguous uint8 [H, W] on {dev}, got "
-                             f"{tuple(label.shape)} {label.dtype} on {label.device}")
-        table[i] = _lib.FuSceneTrainEntry(None, label.data_ptr(), label.shape[0], label.shape[1], int(h0), int(w0), int(hE),
-                                          int(wE), 0, 0.0)
     if counts is None:
         counts = torch.zeros(int(n_classes), dtype=torch.int64, device=dev)
     elif counts.dtype != torch.int64 or counts.numel() != int(n_classes) or not counts.is_contiguous() or counts.device != dev:

@@ -1,0 +1,188 @@
+"""Content-aware tile sampling and crop jitter for SceneTileLoader: which tiles an epoch trains on, and where they are cut.
+
+Water is a small share of the valid pixels of most chips, and a tile whose labels are all ignored costs a full step for a
+zero gradient.  The scenes are resident on the device, so a crop at any position costs what a grid crop costs.  Both remedies
+need the label content of every candidate box, separately:
+
+  * `label_box_counts` on the device: one table of boxes of resident uint8 label rasters, one launch
+    (fu_label_box_counts; integer arithmetic, exact) -> int64 [n, 3], row i = the pixels of box i by raw label category:
+    column 0 = raw neither 0 nor 2 (decodes to class 0), column 1 = raw 2 (decodes to class 1), column 2 = raw 0 (no data).
+  * `label_box_counts_host`: the same contract in numpy -- the specification the tests compare the device against, NOT a
+    fallback for the device call.
+  * `tile_stats(counts, ignore_index, n_classes)`: (trainable, water) pixels per box under the loader's decode.
+  * `plan_order(stats, tile_area, policy, ...)`: the epoch's order of data-set indices under "all", "labelled" (drop the
+    tiles with nothing to train on) or "balanced" (a fixed share of tiles with water), and what was planned.
+  * `jitter_boxes(boxes, raster_hw, J, seed, epoch)`: every box moved by its own offset in [-J, J]^2, kept inside its raster.
+
+Everything but `label_box_counts` is host arithmetic (numpy / torch CPU) and runs without a GPU."""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .class_weights import Box, _check_host_entries, _device_table
+from .scene_loader import epoch_order
+
+__all__ = ["POLICIES", "label_box_counts", "label_box_counts_host", "tile_stats", "plan_order", "jitter_boxes"]
+
+POLICIES = ("all", "labelled", "balanced")
+JITTER_STREAM = 0x6A177E2        # third word of the jitter stream's seed: a stream of its own, not the transforms'
+BALANCED_STREAM = 0xBA1A2CED     # mixed into the seed of the "balanced" draws
+
+
+# ------------------------------------------------------------------------------------------------------- census
+def label_box_counts_host(entries: Sequence[Tuple[np.ndarray, Box]]) -> np.ndarray:
+    """entries: [(raw uint8 label raster [H, W], (h0, w0, hE, wE)), ...] -> int64 [n, 3]: row i = the pixels of box i that are
+    (neither 0 nor 2, 2, 0).  Every entry is checked before anything is counted."""
+    fn = "label_box_counts"
+    if len(entries) < 1:
+        raise ValueError(f"{fn}: no entries")
+    checked = _check_host_entries(entries, fn)
+    out = np.zeros((len(checked), 3), dtype=np.int64)
+    for i, (label, (h0, w0, hE, wE)) in enumerate(checked):
+        raw = np.bincount(label[h0:hE, w0:wE].reshape(-1), minlength=256)
+        out[i] = (int(raw.sum() - raw[2] - raw[0]), int(raw[2]), int(raw[0]))
+    return out
+
+
+def label_box_counts(ctx, entries: Sequence[Tuple[torch.Tensor, Box]], counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """C ABI fu_label_box_counts: entries = [(raw uint8 label raster [H, W] on the ROCm device, box), ...] -> int64 [n, 3] on
+    that device, WRITTEN (rows of `counts` beyond n are left alone when it is given).  One launch for the whole table.
+    ctx: the fu_ctx whose table buffer the call borrows (HipUNet._get_ctx)."""
+    from .. import _lib
+    fn = "label_box_counts"
+    if ctx is None:
+        raise ValueError(f"{fn}: no fu_ctx (run or prepare a forward first)")
+    table, dev = _device_table(entries, fn)
+    n = len(entries)
+    if counts is None:
+        counts = torch.empty((n, 3), dtype=torch.int64, device=dev)
+    elif (counts.dtype != torch.int64 or counts.dim() != 2 or counts.shape[0] < n or counts.shape[1] != 3 or
+          not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"{fn}: counts must be contiguous int64 [>= {n}, 3] on {dev}")
+    _lib.check(_lib.load().fu_label_box_counts(ctx, n, table, counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return counts
+
+
+def _resolve_ignore(ignore_index: Optional[int], n_classes: int) -> Optional[int]:
+    """The model's rule (balanced_class_weights): None ignores nothing, -1 means the last class."""
+    if ignore_index is None:
+        return None
+    return n_classes - 1 if int(ignore_index) == -1 else int(ignore_index)
+
+
+def tile_stats(counts, ignore_index: Optional[int], n_classes: int) -> Tuple[np.ndarray, np.ndarray]:
+    """counts int64 [n, 3] (label_box_counts) -> (trainable, water), int64 [n] each.  Column 0 decodes to class 0, column 1
+    to class 1, column 2 (no data) to `ignore_index`, the loader's nodata_value.  trainable = the columns whose decoded
+    class lies in [0, n_classes) and is not the ignored class (None ignores nothing, -1 means the last class); water =
+    column 1 unless class 1 is the ignored class."""
+    c = np.asarray(counts)
+    if c.ndim != 2 or c.shape[1] != 3 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"tile_stats: counts must be integer [n, 3], got {c.dtype} {c.shape}")
+    n_classes = int(n_classes)
+    if n_classes < 1:
+        raise ValueError(f"tile_stats: n_classes = {n_classes} (must be >= 1)")
+    ignored = _resolve_ignore(ignore_index, n_classes)
+    decoded = (0, 1, ignored)                    # what columns 0, 1, 2 decode to
+    c = c.astype(np.int64)
+    trainable = np.zeros(c.shape[0], dtype=np.int64)
+    for col, d in enumerate(decoded):
+        if d is not None and 0 <= d < n_classes and d != ignored:
+            trainable += c[:, col]
+    water = c[:, 1].copy() if (1 < n_classes and ignored != 1) else np.zeros(c.shape[0], dtype=np.int64)
+    return trainable, water
+
+
+# ------------------------------------------------------------------------------------------------------- planner
+def _check_frac(name: str, v: float) -> float:
+    v = float(v)
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"{name} must lie in [0, 1], got {v}")
+    return v
+
+
+def _take(stratum: np.ndarray, k: int, g: torch.Generator) -> List[int]:
+    """k items of the stratum from successive fresh permutations of it: every item once before any repeats."""
+    out: List[int] = []
+    while len(out) < k:
+        perm = stratum[torch.randperm(len(stratum), generator=g).numpy()]
+        out += perm[:k - len(out)].tolist()
+    return out
+
+
+def plan_order(stats, tile_area: int, policy: str, *, min_trainable_frac: float = 0.0, water_share: float = 0.5,
+               min_water_frac: float = 0.0, shuffle: bool, seed: int, epoch: int) -> Tuple[List[int], dict]:
+    """-> (order, info): the epoch's data-set indices and what was planned.
+
+    stats: (trainable, water) of every example (tile_stats), or for "all" just the number of examples.
+    "all": epoch_order(n, shuffle, seed, epoch).
+    "labelled": kept = the examples with trainable >= 1 and trainable >= min_trainable_frac * tile_area, ascending; the
+      order is kept[j] for j in epoch_order(len(kept), shuffle, seed, epoch) -- plan_epoch's own when nothing is dropped.
+    "balanced": W = the kept examples with water >= 1 and water >= min_water_frac * tile_area, D = the other kept ones.
+      The epoch has L = len(kept) picks, n_w = round(water_share * L) of them from W and L - n_w from D.  Within a stratum
+      the picks come from successive fresh permutations of it, so multiplicities differ by at most 1.  With shuffle the L
+      picks are permuted together; without, they are the water picks then the dry picks, each ascending.  An empty W or D
+      degrades to "labelled" (info["degraded"]).  The draws come from one torch.Generator seeded from (seed, epoch).
+    info: policy, n_examples, n_kept, n_dropped, n_water (picks from W; None without a census), water_share_planned
+      (n_water / len(order)) and degraded.  Nothing kept raises ValueError."""
+    if policy not in POLICIES:
+        raise ValueError(f"tile_sampling must be one of {POLICIES}, got {policy!r}")
+    min_trainable_frac = _check_frac("min_trainable_frac", min_trainable_frac)
+    water_share = _check_frac("water_share", water_share)
+    min_water_frac = _check_frac("min_water_frac", min_water_frac)
+    info = {"policy": policy, "degraded": False}
+    if policy == "all":
+        n = int(stats) if np.ndim(stats) == 0 else len(stats[0])
+        info.update(n_examples=n, n_kept=n, n_dropped=0, n_water=None, water_share_planned=None)
+        return epoch_order(n, shuffle, seed, epoch), info
+    trainable, water = (np.asarray(v, dtype=np.int64).reshape(-1) for v in stats)
+    if trainable.shape != water.shape:
+        raise ValueError(f"plan_order: {trainable.shape[0]} trainable counts, {water.shape[0]} water counts")
+    n = trainable.shape[0]
+    keep = (trainable >= 1) & (trainable >= min_trainable_frac * tile_area)
+    kept = np.flatnonzero(keep)
+    if kept.size == 0:
+        raise ValueError(f"tile_sampling {policy!r}: none of the {n} tiles has a trainable pixel and at least "
+                         f"min_trainable_frac = {min_trainable_frac} of the tile area ({tile_area} pixels) trainable")
+    is_w = keep & (water >= 1) & (water >= min_water_frac * tile_area)
+    W, D = np.flatnonzero(is_w), np.flatnonzero(keep & ~is_w)
+    L = int(kept.size)
+    info.update(n_examples=n, n_kept=L, n_dropped=n - L)
+    if policy == "balanced" and (W.size == 0 or D.size == 0):
+        info["degraded"] = True
+    if policy == "labelled" or info["degraded"]:
+        order = [int(kept[j]) for j in epoch_order(L, shuffle, seed, epoch)]
+        n_w = int(W.size)
+    else:
+        g = torch.Generator().manual_seed((((int(seed) * 1000003 + int(epoch)) * 2654435761) % (1 << 62)) ^ BALANCED_STREAM)
+        n_w = int(round(water_share * L))
+        picks = sorted(_take(W, n_w, g)) + sorted(_take(D, L - n_w, g))
+        order = [picks[j] for j in torch.randperm(L, generator=g).tolist()] if shuffle else picks
+    info.update(n_water=n_w, water_share_planned=n_w / L)
+    return order, info
+
+
+# ------------------------------------------------------------------------------------------------------- jitter
+def jitter_boxes(boxes: Sequence[Box], raster_hw: Sequence[Tuple[int, int]], J: int, seed: int, epoch: int) -> List[Box]:
+    """Every box moved by its own integer offset (oy, ox), uniform in [-J, J], drawn for all examples in data-set order from
+    RandomState([seed, epoch, JITTER_STREAM]) -- not the transforms' stream, so a run's transforms do not depend on J.
+    h0' = clip(h0 + oy, 0, H - dh), w0' = clip(w0 + ox, 0, W - dw); the size is kept.  J = 0: the boxes, without drawing."""
+    J = int(J)
+    if J < 0:
+        raise ValueError(f"crop_jitter must be >= 0, got {J}")
+    boxes = [tuple(int(v) for v in b) for b in boxes]
+    if len(raster_hw) != len(boxes):
+        raise ValueError(f"jitter_boxes: {len(boxes)} boxes, {len(raster_hw)} raster sizes")
+    if J == 0 or not boxes:
+        return boxes
+    rs = np.random.RandomState([int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, JITTER_STREAM])
+    off = rs.randint(-J, J + 1, size=(len(boxes), 2))
+    out = []
+    for (h0, w0, hE, wE), (H, W), (oy, ox) in zip(boxes, raster_hw, off):
+        dh, dw = hE - h0, wE - w0
+        h0 = min(max(h0 + int(oy), 0), int(H) - dh)
+        w0 = min(max(w0 + int(ox), 0), int(W) - dw)
+        out.append((h0, w0, h0 + dh, w0 + dw))
+    return out

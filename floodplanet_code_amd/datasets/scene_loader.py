@@ -9,7 +9,9 @@ table of boxes and transforms and one fu_scene_train_tiles launch (two with norm
 decodes the labels and applies hflip / vflip / rotate in a single pass.  No tensor enters or leaves the device per step.
 
 What stays on the host: the epoch's order (plan_epoch), the draw of the transforms (augment.sample_transforms, the numpy
-stream TileLoader uses) and the table itself.  What it does not do: stream scenes in and out of HBM -- a data set that
+stream TileLoader uses) and the table itself.  Optionally the loader chooses which tiles an epoch sees and where they are
+cut (tile_sampling, crop_jitter; datasets/sampling.py): the label content of every box comes from one
+fu_label_box_counts launch over the resident label rasters, the plan is host arithmetic.  What it does not do: stream scenes in and out of HBM -- a data set that
 exceeds the residency budget raises SceneResidencyError; TileLoader is the streaming loader."""
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-__all__ = ["SceneTileLoader", "SceneResidencyError", "epoch_order", "plan_epoch", "resident_bytes"]
+__all__ = ["SceneTileLoader", "SceneResidencyError", "epoch_order", "order_batches", "plan_epoch", "resident_bytes"]
 
 FREE_MEMORY_FRACTION = 0.5       # default max_resident_bytes: this share of the device's free memory at construction
 
@@ -40,14 +42,13 @@ def epoch_order(n_items: int, shuffle: bool, seed: int, epoch: int) -> List[int]
     return perm.tolist()
 
 
-def plan_epoch(n_items: int, batch_size: int, epoch: int = 0, shuffle: bool = False, seed: int = 0,
-               drop_last: bool = False, shard: Optional[Tuple[int, int]] = None) -> List[List[int]]:
-    """The batches (lists of data-set indices) of one epoch.  shard = (rank, world): the rank's strided share of the epoch's
-    order, cut to len(order) // world items so that every rank runs the same number of steps (the tail of fewer than
-    `world` items is dropped)."""
+def order_batches(order: List[int], batch_size: int, drop_last: bool = False,
+                  shard: Optional[Tuple[int, int]] = None) -> List[List[int]]:
+    """An epoch's order (any list of data-set indices, repeats allowed) cut into batches.  shard = (rank, world): the rank's
+    strided share of the order, cut to len(order) // world items so that every rank runs the same number of steps (the tail
+    of fewer than `world` items is dropped)."""
     if batch_size < 1:
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")
-    order = epoch_order(n_items, shuffle, seed, epoch)
     if shard is not None:
         rank, world = int(shard[0]), int(shard[1])
         if world < 1 or not 0 <= rank < world:
@@ -57,6 +58,14 @@ def plan_epoch(n_items: int, batch_size: int, epoch: int = 0, shuffle: bool = Fa
     if drop_last and batches and len(batches[-1]) < batch_size:
         batches.pop()
     return batches
+
+
+def plan_epoch(n_items: int, batch_size: int, epoch: int = 0, shuffle: bool = False, seed: int = 0,
+               drop_last: bool = False, shard: Optional[Tuple[int, int]] = None) -> List[List[int]]:
+    """The batches (lists of data-set indices) of one epoch over every item: order_batches of epoch_order."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    return order_batches(epoch_order(n_items, shuffle, seed, epoch), batch_size, drop_last, shard)
 
 
 # ------------------------------------------------------------------------------------------------------- residency
@@ -113,13 +122,26 @@ class _SceneRasters(torch.utils.data.Dataset):
 class SceneTileLoader:
     def __init__(self, dataset, batch_size: int, device, net, shuffle: bool = False, seed: int = 0, drop_last: bool = False,
                  transforms: Optional[dict] = None, ignore_index: int = 0, max_resident_bytes: Optional[int] = None,
-                 shard: Optional[Sequence[int]] = None, num_workers: int = 0):
+                 shard: Optional[Sequence[int]] = None, num_workers: int = 0, tile_sampling: str = "all",
+                 min_trainable_frac: float = 0.0, water_share: float = 0.5, min_water_frac: float = 0.0,
+                 crop_jitter: int = 0):
         """dataset: FloodplanetTiles.  net: the HipUNet whose context owns the table's device buffer.  transforms: None, or
         the reference's `transforms` config dict ({} = its defaults), drawn from RandomState(seed) as TileLoader draws them.
         ignore_index: the fill of the target where the augmentation leaves the tile; the data set pads edge crops with its
         own ignore_index, and the kernel has one fill for both, so the two must agree.  max_resident_bytes: the budget of
         resident_bytes(dataset) (default: FREE_MEMORY_FRACTION of the device's free memory now).  num_workers: processes
-        for the one-time decode."""
+        for the one-time decode.
+
+        tile_sampling: "all" (every box of the grid once per epoch), "labelled" (only tiles with at least one pixel, and at
+        least min_trainable_frac of the tile, that the loss does not ignore) or "balanced" (an epoch of as many tiles, a
+        water_share of them tiles with at least one water pixel and min_water_frac of the tile water); sampling.plan_order
+        states the policies.  crop_jitter = J > 0: every epoch moves every box by its own offset in [-J, J]^2, kept inside
+        its raster (sampling.jitter_boxes).  With a policy other than "all" the label content of the epoch's boxes is
+        counted at the start of the epoch (one fu_label_box_counts launch, one read of [n, 3] counts); without jitter the
+        boxes never change, so it is counted once.  With the defaults nothing of this runs.  While an option is active,
+        batches carry "boxes", the (h0, w0, hE, wE) actually cut (metadata keeps the grid's crop_params), and
+        `last_plan` holds what the latest epoch planned."""
+        from .sampling import POLICIES, _check_frac
         self.dataset, self.batch_size, self.device = dataset, int(batch_size), torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("SceneTileLoader keeps the scenes on a ROCm GPU and cuts the batches there; there is no CPU "
@@ -135,6 +157,18 @@ class SceneTileLoader:
         self.shuffle, self.seed, self.drop_last = bool(shuffle), int(seed), bool(drop_last)
         self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
         self.num_workers = int(num_workers)
+        if tile_sampling not in POLICIES:
+            raise ValueError(f"tile_sampling must be one of {POLICIES}, got {tile_sampling!r}")
+        self.tile_sampling = tile_sampling
+        self.min_trainable_frac = _check_frac("min_trainable_frac", min_trainable_frac)
+        self.water_share = _check_frac("water_share", water_share)
+        self.min_water_frac = _check_frac("min_water_frac", min_water_frac)
+        self.crop_jitter = int(crop_jitter)
+        if self.crop_jitter < 0:
+            raise ValueError(f"crop_jitter must be >= 0, got {crop_jitter}")
+        self.last_plan = None            # what the latest planned epoch holds (sampling.plan_order's info)
+        self._census = None              # (trainable, water) of the grid's boxes: cached, they never change
+        self._planned = None             # (epoch, batches, boxes) of the latest plan
         plan_epoch(len(dataset), self.batch_size, 0, False, 0, self.drop_last, self.shard)       # argument errors now
         self.resident_bytes = resident_bytes(dataset)
         if max_resident_bytes is None:
@@ -153,8 +187,45 @@ class SceneTileLoader:
         cp = dataset.dataset[0]["crop_params"] if len(dataset) else None
         self.tile_hw = (cp.max_crop_height, cp.max_crop_width) if cp is not None else None
 
+    @property
+    def _sampling_active(self) -> bool:
+        return self.tile_sampling != "all" or self.crop_jitter > 0
+
     def __len__(self):
-        return len(plan_epoch(len(self.dataset), self.batch_size, 0, False, 0, self.drop_last, self.shard))
+        """Batches per epoch; under a policy other than "all" the planned number for the next epoch (this takes the
+        census, so the scenes become resident)."""
+        if self.tile_sampling == "all":
+            return len(plan_epoch(len(self.dataset), self.batch_size, 0, False, 0, self.drop_last, self.shard))
+        return len(self._plan(self._epoch)[0])
+
+    def _plan(self, epoch: int):
+        """(batches, boxes) of an epoch under the sampling options: the epoch's boxes (jittered when crop_jitter > 0), their
+        census unless the policy is "all" (every rank counts the whole split), the planned order, sharded and batched."""
+        from . import sampling
+        if self._planned is not None and self._planned[0] == epoch:
+            return self._planned[1:]
+        if self._items is None:
+            self._make_resident()
+        boxes = [box for _, _, box in self._items]
+        if self.crop_jitter > 0:
+            boxes = sampling.jitter_boxes(boxes, [tuple(label.shape) for _, label, _ in self._items], self.crop_jitter,
+                                          self.seed, epoch)
+        th, tw = self.tile_hw
+        stats = len(boxes)
+        if self.tile_sampling != "all":
+            stats = self._census
+            if stats is None:
+                ctx = self.net._get_ctx(self.device, self.batch_size, th, tw)
+                counts = sampling.label_box_counts(ctx, [(label, box) for (_, label, _), box in zip(self._items, boxes)])
+                stats = sampling.tile_stats(counts.cpu().numpy(), self.ignore_index, int(self.dataset.n_classes))
+                if self.crop_jitter == 0:
+                    self._census = stats
+        order, info = sampling.plan_order(stats, th * tw, self.tile_sampling, min_trainable_frac=self.min_trainable_frac,
+                                          water_share=self.water_share, min_water_frac=self.min_water_frac,
+                                          shuffle=self.shuffle, seed=self.seed, epoch=epoch)
+        batches = order_batches(order, self.batch_size, self.drop_last, self.shard)
+        self._planned, self.last_plan = (epoch, batches, boxes), info
+        return batches, boxes
 
     def _make_resident(self):
         """Decode, upload and resample every scene once; upload its label raster."""
@@ -183,7 +254,8 @@ class SceneTileLoader:
         """Pixels per class over every example of the split: int64 [n_classes] on the device, from the resident label
         rasters -- one table of all the boxes, one launch (fu_label_class_counts).  Labels decode as the batches' targets
         do (no data -> ignore_index); overlapping tiles count as often as they are trained on.  A sharded loader still
-        counts the whole split."""
+        counts the whole split.  These are the frequencies of the grid's boxes: under tile_sampling "balanced" (tiles
+        repeated or left out) or crop_jitter the frequencies trained on differ from them."""
         from .class_weights import label_class_counts
         if self._items is None:
             self._make_resident()
@@ -194,7 +266,7 @@ class SceneTileLoader:
         ctx = self.net._get_ctx(self.device, self.batch_size, th, tw)
         return label_class_counts(ctx, [(label, box) for _, label, box in self._items], self.ignore_index, n_classes)
 
-    def _batch(self, index: List[int]) -> dict:
+    def _batch(self, index: List[int], boxes: Optional[List[Tuple[int, int, int, int]]] = None) -> dict:
         from .. import augment
         from .assemble import scene_train_tiles
         n = len(index)
@@ -204,12 +276,17 @@ class SceneTileLoader:
             flags, angles = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float32)
         th, tw = self.tile_hw
         ctx = self.net._get_ctx(self.device, self.batch_size, th, tw)
-        entries = [self._items[i] + (int(flags[k]), float(angles[k])) for k, i in enumerate(index)]
+        if boxes is None:
+            entries = [self._items[i] + (int(flags[k]), float(angles[k])) for k, i in enumerate(index)]
+        else:                            # the epoch's boxes in place of the grid's
+            entries = [self._items[i][:2] + (boxes[i], int(flags[k]), float(angles[k])) for k, i in enumerate(index)]
         image, target, mean, std = scene_train_tiles(ctx, entries, (th, tw), self.dataset.norm_mode, self._global,
                                                      nodata_value=self.ignore_index,
                                                      target_fill=self.ignore_index)
         out = {"image": image, "target": target, "mean": mean, "std": std, "index": list(index), "flags": flags,
                "angles": angles}
+        if boxes is not None:
+            out["boxes"] = [boxes[i] for i in index]
         if self.dataset.output_metadata:
             out["metadata"] = [{"image_path": ex["image_path"], "crop_params": ex["crop_params"],
                                 "region_name": ex["region_name"]} for ex in (self.dataset.dataset[i] for i in index)]
@@ -219,6 +296,11 @@ class SceneTileLoader:
         if self._items is None:
             self._make_resident()
         epoch, self._epoch = self._epoch, self._epoch + 1
+        if self._sampling_active:
+            batches, boxes = self._plan(epoch)
+            for index in batches:
+                yield self._batch(index, boxes)
+            return
         for index in plan_epoch(len(self.dataset), self.batch_size, epoch, self.shuffle, self.seed, self.drop_last,
                                 self.shard):
             yield self._batch(index)

@@ -89,7 +89,8 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
     model: an already built model to train in place of the build_model call (a loader that needs the network's context,
     SceneTileLoader, is made before fit_model runs).  The trained model keeps `history`, one dict per epoch: epoch, train_loss
     (the last step's), val_MulticlassJaccardIndex and train_tiles_per_s -- the tiles of the epoch's training loop over its
-    host time, closed by one device synchronise per epoch (None when the train loader yields nothing)."""
+    host time, closed by one device synchronise per epoch (None when the train loader yields nothing) -- plus `plan`, the
+    train loader's `last_plan`, when it has one."""
     c = dict(DEFAULTS)
     c.update(cfg or {})
     torch.manual_seed(c["seed_num"])                                         # pl.seed_everything(seed_num)
@@ -125,6 +126,9 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
         miou = float(model.logged.get("val_MulticlassJaccardIndex", torch.zeros(())))
         history.append({"epoch": epoch, "train_loss": float(loss.detach()), "val_MulticlassJaccardIndex": miou,
                         "train_tiles_per_s": n_tiles / train_seconds if n_tiles and train_seconds > 0 else None})
+        plan = getattr(train_loader, "last_plan", None)                      # a loader that chooses its tiles says which
+        if plan is not None:
+            history[-1]["plan"] = dict(plan)
         if ckpt_dir:
             path = os.path.join(ckpt_dir, f"model-epoch={epoch:02d}-val_MulticlassJaccardIndex={miou:.4f}.ckpt")
             ckpt = {"state_dict": model.state_dict(), "epoch": epoch, "hyper_parameters": dict(c)}
@@ -185,6 +189,19 @@ def build_parser() -> argparse.ArgumentParser:
                          "checkpoint choice and the checkpoint's ema_state_dict use it (default: no EMA)")
     ap.add_argument("--no_ema_warmup", action="store_true",
                     help="use --ema_decay from the first update on (default: min(decay, (1 + n) / (10 + n)))")
+    ap.add_argument("--tile_sampling", type=str, default=None, choices=["all", "labelled", "balanced"],
+                    help="--loader scene, train split: which tiles an epoch sees -- all (default), labelled (drop the tiles "
+                         "the loss ignores entirely) or balanced (a --water_share of tiles with water)")
+    ap.add_argument("--min_trainable_frac", type=float, default=None, metavar="F",
+                    help="labelled / balanced: keep a tile only if this share of it, in [0, 1], is not ignored (default 0: "
+                         "one pixel)")
+    ap.add_argument("--water_share", type=float, default=None, metavar="F",
+                    help="balanced: the share of an epoch's tiles, in [0, 1], drawn from the tiles with water (default 0.5)")
+    ap.add_argument("--min_water_frac", type=float, default=None, metavar="F",
+                    help="balanced: a tile counts as a water tile if this share of it, in [0, 1], is water (default 0: "
+                         "one pixel)")
+    ap.add_argument("--crop_jitter", type=int, default=None, metavar="J",
+                    help="--loader scene, train split: move every crop by its own offset in [-J, J]^2 each epoch (default 0)")
     ap.add_argument("--no_transforms", action="store_true", help="train without hflip / vflip / rotate")
     ap.add_argument("--no_shuffle", action="store_true", help="train in data-set order")
     ap.add_argument("--device", type=str, default="cuda:0")
@@ -206,11 +223,30 @@ def parse_class_weights(values, n_classes: Optional[int] = None):
     return w
 
 
+SAMPLING_OPTIONS = ("tile_sampling", "min_trainable_frac", "water_share", "min_water_frac", "crop_jitter")
+
+
+def sampling_from_args(args) -> dict:
+    """The tile-sampling options a command line gave ({} for none), checked: they belong to --loader scene, fractions lie in
+    [0, 1], the jitter is >= 0.  The keys are SceneTileLoader's keyword arguments."""
+    given = {k: getattr(args, k, None) for k in SAMPLING_OPTIONS}
+    given = {k: v for k, v in given.items() if v is not None}
+    if given and getattr(args, "loader", "scene") != "scene":
+        raise ValueError("--" + ", --".join(given) + " need --loader scene: the streaming loader cuts a fixed grid")
+    for k in ("min_trainable_frac", "water_share", "min_water_frac"):
+        if k in given and not 0.0 <= given[k] <= 1.0:
+            raise ValueError(f"--{k} must lie in [0, 1], got {given[k]}")
+    if given.get("crop_jitter", 0) < 0:
+        raise ValueError(f"--crop_jitter must be >= 0, got {given['crop_jitter']}")
+    return given
+
+
 def cfg_from_args(args, class_weights=None) -> dict:
     """The reference-style config of a command line: what fit_model trains with and dumps into the checkpoint.
     class_weights: the resolved numeric weights (the data decides 'balanced' and the class count, so main() resolves them);
-    they, --label_smoothing, --focal_gamma, --ema_decay and --no_ema_warmup enter model_kwargs only when set, so a plain
-    command line gives the config it always gave."""
+    they, --label_smoothing, --focal_gamma, --ema_decay and --no_ema_warmup enter model_kwargs only when set, and the
+    tile-sampling options a `sampling` key beside `model` only when given, so a plain command line gives the config it
+    always gave."""
     norm_mode = None if args.norm_mode == "none" else args.norm_mode
     parsed = parse_class_weights(getattr(args, "class_weights", None), N_CLASSES)
     if class_weights is None and parsed is not None and parsed != "balanced":
@@ -229,14 +265,18 @@ def cfg_from_args(args, class_weights=None) -> dict:
         loss_kwargs["ema_warmup"] = not getattr(args, "no_ema_warmup", False)
     elif getattr(args, "no_ema_warmup", False):
         raise ValueError("--no_ema_warmup needs --ema_decay")
-    return dict(lr=args.lr, batch_size=args.batch_size, n_epochs=args.n_epochs, crop_height=args.crop[0],
-                crop_width=args.crop[1], crop_stride=args.stride, ignore_index=args.ignore_index,
-                save_topk_models=args.save_topk_models, seed_num=args.seed, n_workers=args.n_workers,
-                eval_region=list(args.eval_region) if args.eval_region else None, train_split_pct=args.train_split_pct,
-                norm_mode=norm_mode, norm_params=args.norm_params,
-                dataset=dict(name="floodplanet", sensor=args.sensor, channels=args.channels, dataset_kwargs=None),
-                model=dict(name=args.model, model_kwargs=dict(optimizer_name="adam", base_channels=args.base_channels,
-                                                              precision=args.precision, **loss_kwargs)))
+    sampling = sampling_from_args(args)
+    cfg = dict(lr=args.lr, batch_size=args.batch_size, n_epochs=args.n_epochs, crop_height=args.crop[0],
+               crop_width=args.crop[1], crop_stride=args.stride, ignore_index=args.ignore_index,
+               save_topk_models=args.save_topk_models, seed_num=args.seed, n_workers=args.n_workers,
+               eval_region=list(args.eval_region) if args.eval_region else None, train_split_pct=args.train_split_pct,
+               norm_mode=norm_mode, norm_params=args.norm_params,
+               dataset=dict(name="floodplanet", sensor=args.sensor, channels=args.channels, dataset_kwargs=None),
+               model=dict(name=args.model, model_kwargs=dict(optimizer_name="adam", base_channels=args.base_channels,
+                                                             precision=args.precision, **loss_kwargs)))
+    if sampling:
+        cfg["sampling"] = sampling
+    return cfg
 
 
 def main(argv: Optional[List[str]] = None) -> dict:
@@ -277,8 +317,8 @@ def main(argv: Optional[List[str]] = None) -> dict:
     if args.loader == "scene":
         common = dict(net=model.model, seed=c["seed_num"], ignore_index=c["ignore_index"], num_workers=args.n_workers)
         train = SceneTileLoader(train_ds, c["batch_size"], args.device, shuffle=not args.no_shuffle, transforms=transforms,
-                                **common)
-        valid = SceneTileLoader(valid_ds, c["batch_size"], args.device, **common)
+                                **common, **cfg.get("sampling", {}))
+        valid = SceneTileLoader(valid_ds, c["batch_size"], args.device, **common)       # every tile, where the grid puts it
         if wanted == "balanced":                         # counted on the device, from the label rasters resident there
             from .datasets.class_weights import balanced_class_weights
             class_counts = train.class_counts().cpu().numpy()
@@ -297,6 +337,8 @@ def main(argv: Optional[List[str]] = None) -> dict:
            "history": model.history,
            "class_counts": None if class_counts is None else [int(v) for v in class_counts],
            "class_weights": None if model.class_weights is None else list(model.class_weights)}
+    if "sampling" in cfg:
+        out["tile_sampling"] = dict(cfg["sampling"])
     print(json.dumps(out))
     return out
 

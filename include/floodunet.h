@@ -18,6 +18,7 @@
  *   fu_loss_ce_weighted         (new) nn.CrossEntropyLoss(weight, ignore_index, label_smoothing) on the same path
  *   fu_loss_ce_focal            (new) the same with focal modulation (1 - p[t])^gamma of every pixel's term
  *   fu_label_class_counts       (new) class frequencies of resident label rasters, for "balanced" weights
+ *   fu_label_box_counts         (new) the label content of every box of a table, for content-aware tile sampling
  *   fu_backward[_block]         loss.backward() issued by Lightning's automatic optimisation
  *                                                                            st_water_seg/fit.py:95-97
  *   fu_adam_step                optim.Adam(self.parameters(), lr).step()     st_water_seg/models/water_seg_model.py:198-205
@@ -415,6 +416,18 @@ int fu_scene_train_tiles(fu_ctx* ctx, int n, const fu_scene_train_entry* entries
  * entry is checked before anything is launched: a rejected call launches nothing and leaves counts_out untouched. */
 int fu_label_class_counts(fu_ctx* ctx, int n, const fu_scene_train_entry* entries, int64_t nodata_value, int n_classes,
                           int64_t* counts_out, fu_stream stream);
+
+/* The label content of every box of a table, separately (added within ABI 5: purely additive), for content-aware tile
+ * sampling.  entries: as for fu_label_class_counts -- only label, scene_h, scene_w and the box are read, a NULL label is
+ * rejected, and a box may be as large as its raster.  Row i of counts_out (device int64 [n][3], caller-owned) is WRITTEN,
+ * not added to: the pixels of box i by raw label category -- column 0 = raw neither 0 nor 2 (decodes to class 0), column 1
+ * = raw 2 (decodes to class 1), column 2 = raw 0 (no data).  The three sum to the box's area; mapping them to decoded
+ * classes (no data -> nodata_value) is the caller's job.  Integer arithmetic only, exact; one workgroup per box owns its
+ * row, so there are no global atomics and nothing to zero beforehand.  One launch.  The table goes through the same
+ * library-owned device buffer ordered on `stream`, and every entry is checked (the checks and messages of
+ * fu_label_class_counts) before anything is copied or launched: a rejected call launches nothing and leaves counts_out
+ * untouched. */
+int fu_label_box_counts(fu_ctx* ctx, int n, const fu_scene_train_entry* entries, int64_t* counts_out, fu_stream stream);
 
 /* ---- inference stitching (ImageStitcher_v2, utils/utils_image.py:410-494) ------------- */
 /* canvas[h0:hE, w0:wE, :] += softmax(logits of sample `sample` of the last fu_forward)[:hE-h0, :wE-w0, :];
