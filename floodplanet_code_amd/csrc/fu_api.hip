@@ -634,6 +634,37 @@ int fu_stitch_finalize_maps(float* canvas, const float* weight, int n_classes, i
                                      class_values, class_out, prob_out, margin_out, counts_out, (hipStream_t)stream);
 }
 
+// fu_map_components / fu_map_sieve share these checks; every one comes before anything is launched
+static int check_map_args(const char* fn, const void* map, const void* out, int h, int w, int connectivity) {
+  FU_REQUIRE(map && out, "%s: null map / output", fn);
+  FU_REQUIRE(h >= 1 && w >= 1 && (int64_t)h * w <= FU_MAP_MAX_PIXELS, "%s: map %dx%d is empty or has more than 2^28 pixels", fn,
+             h, w);
+  FU_REQUIRE(connectivity == 4 || connectivity == 8, "%s: connectivity %d is neither 4 nor 8", fn, connectivity);
+  return 0;
+}
+
+int64_t fu_sieve_workspace_bytes(int h, int w) {
+  if (h < 1 || w < 1 || (int64_t)h * w > FU_MAP_MAX_PIXELS) return 0;
+  return sieve_workspace_bytes(h, w);
+}
+
+int fu_map_components(const uint8_t* map, int h, int w, int connectivity, int32_t* labels_out, fu_stream stream) {
+  FU_TRY(check_map_args("fu_map_components", map, labels_out, h, w, connectivity));
+  return launch_map_components(map, h, w, connectivity, labels_out, (hipStream_t)stream);
+}
+
+int fu_map_sieve(const uint8_t* map, uint8_t* out, int h, int w, int connectivity, int min_pixels, int frozen_value, int passes,
+                 void* workspace, int64_t workspace_bytes, int64_t* stats_out, fu_stream stream) {
+  FU_TRY(check_map_args("fu_map_sieve", map, out, h, w, connectivity));
+  FU_REQUIRE(frozen_value >= -1 && frozen_value <= 255, "fu_map_sieve: frozen_value %d not in -1..255", frozen_value);
+  FU_REQUIRE(passes >= 1 && passes <= 8, "fu_map_sieve: passes %d not in 1..8", passes);
+  FU_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= sieve_workspace_bytes(h, w),
+             "fu_map_sieve: workspace missing, not 16-byte aligned or smaller than fu_sieve_workspace_bytes = %lld",
+             (long long)sieve_workspace_bytes(h, w));
+  return launch_map_sieve(map, out, h, w, connectivity, min_pixels, frozen_value, passes, workspace, stats_out,
+                          (hipStream_t)stream);
+}
+
 int fu_augment(const float* image, const int64_t* target, float* image_out, int64_t* target_out, const int32_t* flags,
                const float* angles_deg, int B, int C, int H, int W, int64_t target_fill, fu_stream stream) {
   FU_REQUIRE(image && image_out && flags && angles_deg, "fu_augment: null argument");

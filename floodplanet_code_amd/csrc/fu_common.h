@@ -549,6 +549,13 @@ int launch_stitch_add_batch(DeviceTable& table, const char* fn, const char* batc
 int launch_stitch_finalize_maps(float* canvas, const float* weight, int ncls, int64_t npix, float eps, bool normalize,
                                 const unsigned char* class_values, unsigned char* class_out, unsigned char* prob_out,
                                 unsigned char* margin_out, int64_t* counts, hipStream_t s);
+// fu_map_components / fu_map_sieve (fu_post.hip): union-find labelling of a uint8 map (the label of a pixel = the smallest
+// linear index of its component) and the connected-component sieve on top of it; the caller has checked every argument.
+// workspace: sieve_workspace_bytes(h, w) = 16 B per pixel (64-bit donor keys, labels, sizes); stats: int64[2] ADDED to, or null
+int64_t sieve_workspace_bytes(int h, int w);
+int launch_map_components(const unsigned char* map, int h, int w, int connectivity, int* labels, hipStream_t s);
+int launch_map_sieve(const unsigned char* map, unsigned char* out, int h, int w, int connectivity, int min_pixels, int frozen,
+                     int passes, void* workspace, int64_t* stats, hipStream_t s);
 int launch_eval_confusion(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int B, int64_t hw,
                           int64_t* counts, hipStream_t s);
 // fu_merge_views: softmax of each view's logits, inverse view, mean in view order -> probs [B, H, W, k] (optional) and

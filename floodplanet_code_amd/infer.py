@@ -27,6 +27,10 @@ else the parent directory.  What runs differently:
     to half the crop.  --write_probs u8|f32 writes the stitched probabilities as <image>_prob.tif ([k, H, W]; u8 =
     rint(p * 255)), --write_margin the top-1 minus top-2 probability as <image>_margin.tif (uint8 [H, W]), with the class
     map's georeferencing.  Class map, class counts and these rasters come from one fu_stitch_finalize_maps launch.
+  * extension: --sieve N merges every connected patch of the class map smaller than N pixels into its largest
+    neighbouring patch (postprocess.sieve_host is the rule; --sieve_connectivity 4|8, --sieve_passes P), on the device,
+    between the finalisation and the scene's one device-to-host read, which also carries the two counts of what changed.
+    Only the written class map is sieved: class_pixels, the probability and the margin raster stay what the network said.
 Out of scope: multi-GPU inference, inputs besides ms_image (dem, slope, hand, preflood), RGB outputs, BigTIFF or
 compressed output.
 """
@@ -43,6 +47,7 @@ import numpy as np
 import torch
 
 from .predict import CONFIG_DEFAULTS, WEIGHT_CHOICES, _merge, load_checkpoint_model, resolve_cfg
+from .postprocess import check_sieve_options
 from .stitch import BLEND_KINDS
 from .tta import VIEW_SETS, view_codes
 
@@ -221,14 +226,17 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
           size: Optional[Sequence[int]] = None, scale: Optional[float] = None, stride: Optional[int] = None,
           batch_size: Optional[int] = None, tta=None, n_workers: int = 0, device: str = "cuda:0",
           keep_probabilities: bool = False, norm_params=None, weights: str = "auto", blend: str = "uniform",
-          write_probs: Optional[str] = None, write_margin: bool = False) -> dict:
+          write_probs: Optional[str] = None, write_margin: bool = False, sieve: Optional[int] = None,
+          sieve_connectivity: int = 4, sieve_passes: int = 1) -> dict:
     """Class maps of every input scene (see the module docstring).  cfg: the resolved config (default: resolve_cfg of
     the checkpoint's experiment).  Returns the summary.json dict; with keep_probabilities also "probabilities"
     {output path: fp32 [H, W, k] stitched canvas} (one more host read per scene; for tests and comparisons).
     norm_params: the parameter file of norm_mode 'global' (path, or the dict it holds; datasets.stats), looked up by the
     config's data set name and sensor; without it a 'global' config is rejected.  weights: 'auto', 'raw' or 'ema'
     (predict.checkpoint_weights); the summary records the choice made under "weights".  blend: "uniform", "linear" or
-    "hann" (stitch.blend_window); write_probs: None, "u8" or "f32"; write_margin: also write the top-2 margin raster."""
+    "hann" (stitch.blend_window); write_probs: None, "u8" or "f32"; write_margin: also write the top-2 margin raster.
+    sieve: None, or the minimum patch size in pixels of the written class map (postprocess.sieve on the device, with
+    sieve_connectivity 4 or 8 and sieve_passes 1..8); class_pixels and the other rasters stay un-sieved."""
     from .datasets.floodplanet import _N_CHANNELS
     from .models import build_model
 
@@ -239,6 +247,10 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
         raise ValueError(f"blend must be one of {list(BLEND_KINDS)}, got {blend!r}")
     if write_probs is not None and write_probs not in PROB_FORMATS:
         raise ValueError(f"write_probs must be one of {list(PROB_FORMATS)} or None, got {write_probs!r}")
+    sieve_opts = None
+    if sieve is not None:
+        check_sieve_options(sieve, sieve_connectivity, sieve_passes)
+        sieve_opts = {"min_pixels": int(sieve), "connectivity": int(sieve_connectivity), "passes": int(sieve_passes)}
     if cfg is None:
         experiment_dir = "/".join(checkpoint_path.split("/")[:-2])
         cfg = resolve_cfg(experiment_dir, checkpoint_path)
@@ -271,6 +283,7 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
         grid_size((1 << 20, 1 << 20), size, scale)
 
     from .datasets.assemble import scene_crops
+    from .postprocess import sieve as sieve_map
     from .stitch import GpuImageStitcher
     from .datasets.synthetic import write_strip_tiff
     dev = torch.device(device)
@@ -315,10 +328,15 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
         H, W = sc["hw"]
         key = str(i)
         maps = stitcher.combine_maps(key, class_values, probs=write_probs == "u8", margin=write_margin, counts=True)
+        if sieve_opts is not None:                       # in place, on the stream of the launch above; no host read
+            _, sieve_stats = sieve_map(maps["class"], sieve_opts["min_pixels"], sieve_opts["connectivity"],
+                                       passes=sieve_opts["passes"], out=maps["class"])
         parts = [maps["counts"].view(torch.uint8), maps["class"].view(-1)]
         parts += [maps[m].view(-1) for m in ("probs", "margin") if m in maps]
         if write_probs == "f32":                         # the normalised canvas itself, as bytes of the same read
             parts.append(maps["canvas"].view(torch.uint8).view(-1))
+        if sieve_opts is not None:
+            parts.append(sieve_stats.view(torch.uint8))
         packed = torch.cat(parts).cpu().numpy()          # one launch above, the one device-to-host read here
         if keep_probabilities:
             probabilities[outs[i]] = maps["canvas"].cpu().numpy()
@@ -341,8 +359,11 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
             at += H * W
         if write_probs == "f32":
             rec["probabilities"] = side_output_path(outs[i], "prob")
-            canvas_h = packed[at:].view(np.float32).reshape(H, W, k)
+            canvas_h = packed[at:at + 4 * k * H * W].view(np.float32).reshape(H, W, k)
             write_strip_tiff(rec["probabilities"], np.ascontiguousarray(canvas_h.transpose(2, 0, 1)), extra_tags=tags)
+        if sieve_opts is not None:
+            merged, changed = packed[-16:].view(np.int64).tolist()
+            rec["sieve"] = dict(sieve_opts, merged_components=merged, changed_pixels=changed)
         records.append(rec)
 
     with torch.no_grad():
@@ -379,6 +400,9 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
                "crops_per_s": n_crops / seconds if seconds > 0 else None, "max_resident_scenes": max_resident,
                "tta": tta if (tta is None or isinstance(tta, str)) else list(codes), "weights": chosen,
                "blend": blend, "stride": stride}
+    if sieve_opts is not None:
+        summary["sieve"] = dict(sieve_opts, merged_components=sum(r["sieve"]["merged_components"] for r in records),
+                                changed_pixels=sum(r["sieve"]["changed_pixels"] for r in records))
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "summary.json"), "w") as fh:
         json.dump(summary, fh, indent=4)
@@ -407,6 +431,14 @@ def build_parser() -> argparse.ArgumentParser:
                          "rint(p * 255) (u8) or float32 (f32)")
     ap.add_argument("--write_margin", action="store_true",
                     help="also write <image>_margin.tif, uint8 [H, W]: rint(255 * (top-1 minus top-2 probability))")
+    ap.add_argument("--sieve", type=int, default=None, metavar="N",
+                    help="merge every connected patch of the class map smaller than N pixels into its largest neighbouring "
+                         "patch, on the device (default: off).  Only the written class map is sieved: class_pixels, the "
+                         "probability raster and the margin raster stay what the network said, un-sieved")
+    ap.add_argument("--sieve_connectivity", type=int, default=4, choices=[4, 8],
+                    help="neighbours that join pixels of one class into a patch (default 4)")
+    ap.add_argument("--sieve_passes", type=int, default=1, choices=list(range(1, 9)),
+                    help="apply the sieve this many times, each on the previous result (default 1)")
     ap.add_argument("--batch_size", type=int, default=None, help="crops per eval forward (default: the config's)")
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips / rotations")
@@ -428,7 +460,8 @@ def main(argv: Optional[List[str]] = None) -> None:
     out = infer(args.checkpoint_path, args.inputs, args.out_dir, cfg=cfg, size=args.size, scale=args.scale,
                 stride=args.stride, batch_size=args.batch_size, tta=args.tta, n_workers=args.n_workers,
                 device=args.device, norm_params=args.norm_params, weights=args.weights, blend=args.blend,
-                write_probs=args.write_probs, write_margin=args.write_margin)
+                write_probs=args.write_probs, write_margin=args.write_margin, sieve=args.sieve,
+                sieve_connectivity=args.sieve_connectivity, sieve_passes=args.sieve_passes)
     print(json.dumps({k: v for k, v in out.items() if k != "scenes"}))
 
 

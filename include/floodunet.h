@@ -511,6 +511,28 @@ int fu_stitch_finalize_maps(float* canvas, const float* weight, int n_classes, i
                             int normalize_in_place, const uint8_t* class_values, uint8_t* class_out, uint8_t* prob_out,
                             uint8_t* margin_out, int64_t* counts_out, fu_stream stream);
 
+/* ---- class-map post-processing (fu_post.hip); no context needed --------------------------------- */
+#define FU_MAP_MAX_PIXELS (1 << 28)
+/* Connected components of a uint8 map [h, w] on the device: a component is a maximal set of pixels of equal value joined
+ * through 4-neighbours (connectivity 4) or 8-neighbours (8).  labels_out int32 [h, w]: the smallest linear index y * w + x
+ * of the pixel's component -- canonical, so two labellings compare bit for bit (postprocess.label_components_host is the
+ * statement).  Union-find with integer atomics: exact, reproducible; three launches.  1 <= h, w and h * w <= 2^28.  A
+ * rejected call launches nothing. */
+int fu_map_components(const uint8_t* map, int h, int w, int connectivity, int32_t* labels_out, fu_stream stream);
+/* Bytes of fu_map_sieve's workspace: 16 per pixel (labels, component sizes, a 64-bit donor key); 0 for a size it rejects. */
+int64_t fu_sieve_workspace_bytes(int h, int w);
+/* Connected-component sieve (postprocess.sieve_host is the statement, bit for bit, stats included).  One pass: components
+ * and sizes of the pass's input; a component is small when its size < min_pixels and its value is not frozen_value
+ * (-1 = none); a donor of a small component is a component that is not small, not of frozen_value, and shares a pixel
+ * edge with it (edges under both connectivities); the small component takes the value of its largest donor, ties to the
+ * smallest value, and keeps its own when it has no donor.  `passes` (1..8) passes, each on the previous result.
+ * out uint8 [h, w]; out == map (in place) is allowed.  min_pixels <= 1: a copy.  workspace: device memory, 16-byte
+ * aligned, >= fu_sieve_workspace_bytes(h, w), contents undefined before and after.  stats_out: device int64 [2] or NULL,
+ * ADDED to: [0] components re-valued, [1] pixels changed, summed over the passes.  Five launches per pass, no host read.
+ * Every argument is checked before anything is launched: a rejected call leaves out and stats_out untouched. */
+int fu_map_sieve(const uint8_t* map, uint8_t* out, int h, int w, int connectivity, int min_pixels, int frozen_value,
+                 int passes, void* workspace, int64_t workspace_bytes, int64_t* stats_out, fu_stream stream);
+
 /* ---- eval metrics ---------------------------------------------------------------------------- */
 /* Per-sample confusion counts of the last fu_forward (eval or training): counts_out[b][t * k + p] += #pixels of sample b
  * with target t and p = argmax of the resident logits (first maximum wins, as fu_loss_ce), over pixels whose target is
