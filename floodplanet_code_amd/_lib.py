@@ -185,6 +185,7 @@ SIGNATURES = {
     "fu_test_conv_route_name": (C.c_char_p, [_i, _i]),
     "fu_test_wgrad_slab": (_i, [_i] * 8 + [C.POINTER(_i64), C.POINTER(_i64)]),
     "fu_test_get_buffer": (_i, [_p, _i, _i, C.POINTER(_p), C.POINTER(_i64)]),
+    "fu_test_loss_buffers": (_i, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64)]),
     "fu_set_side_stream": (_i, [_p, _i]),
     "fu_backward_join": (_i, [_p, _p]),
     "fu_backward_fence": (_i, [_p, _p, _p]),

@@ -371,26 +371,39 @@ int launch_ce_grad(const float* logits_nhwc, const int64_t* target, int ncls, in
 // only by oracle/unet_oracle.py:bce_dice_loss).  All spatial reductions in fp32 registers + wave shuffles, fp64 finalize.
 //   BCE  = -(1/N) sum_valid [ t log p + (1-t) log(1-p) ],  Dice = 1 - (2 sum p t + 1) / (sum p + sum t + 1)
 // ------------------------------------------------------------------------------------------------
+// One pixel's terms: s = softmax(z), p = s[1], log p, log(1-p), and s1 = the softmax over the classes other than 1 (the
+// derivative of their logsumexp; s1[1] = 0).  The other classes get their OWN maximum m1, as the oracle's logsumexp over
+// them does: log(1-p) = (m1 - m) + log(sum_{k != 1} exp(z[k] - m1)) - log(sum_k exp(z[k] - m)), and -log1p(e[1] / that sum)
+// where they hold the overall maximum (m1 == m: no difference of two nearly equal logs for a small p).  Until this form,
+// both sums shared the maximum m over all classes: once class 1 led every other class by more than ~87.3 their
+// exponentials were denormal (log(1-p) off by 0.02 at a margin of 100) and beyond ~104 they were 0 -- log(1-p) = -inf,
+// the loss of a batch with one such background pixel inf, and s1 = 0, a gradient row that no longer sums to zero.
 __device__ __forceinline__ void bd_pixel(const float* z, int ncls, float& p, float& logp, float& log1mp, float* s,
                                          float* s1) {
-  float m = -INFINITY;
+  float m = -INFINITY, m1 = -INFINITY;
 #pragma unroll
-  for (int k = 0; k < HEAD_MAX_CLS; ++k) if (k < ncls) m = fmaxf(m, z[k]);
-  float se = 0.f, se1 = 0.f;
-  float e[HEAD_MAX_CLS];
+  for (int k = 0; k < HEAD_MAX_CLS; ++k) {
+    if (k < ncls) {
+      m = fmaxf(m, z[k]);
+      if (k != 1) m1 = fmaxf(m1, z[k]);
+    }
+  }
+  float se = 0.f, sf = 0.f;
+  float e[HEAD_MAX_CLS], f[HEAD_MAX_CLS];
 #pragma unroll
   for (int k = 0; k < HEAD_MAX_CLS; ++k) {
     e[k] = k < ncls ? expf(z[k] - m) : 0.f;
+    f[k] = (k < ncls && k != 1) ? expf(z[k] - m1) : 0.f;
     se += e[k];
-    if (k != 1) se1 += e[k];
+    sf += f[k];
   }
-  const float inv = 1.f / se, inv1 = se1 > 0.f ? 1.f / se1 : 0.f;
+  const float inv = 1.f / se, inv1 = 1.f / sf;        // (ncls >= 2: sf holds an exact 1, the class at m1)
 #pragma unroll
-  for (int k = 0; k < HEAD_MAX_CLS; ++k) { s[k] = e[k] * inv; s1[k] = (k != 1) ? e[k] * inv1 : 0.f; }
+  for (int k = 0; k < HEAD_MAX_CLS; ++k) { s[k] = e[k] * inv; s1[k] = f[k] * inv1; }
   p = s[1];
   const float lse = logf(se);
   logp = (z[1] - m) - lse;
-  log1mp = logf(se1) - lse;
+  log1mp = (m1 == m) ? -log1pf(e[1] * inv1) : (m1 - m) + logf(sf) - lse;
 }
 
 __global__ void k_bd_loss(const float* __restrict__ logits, const int64_t* __restrict__ target, int ncls,

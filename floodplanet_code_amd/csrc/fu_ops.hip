@@ -1,6 +1,6 @@
 // Single operators behind the C ABI (fu_op_*): one launcher each on caller-owned buffers, with temporary packs and
-// partial buffers of their own -- the hooks of the op-level parity tests -- and fu_test_get_buffer, the only entry
-// point here that looks inside a context.
+// partial buffers of their own -- the hooks of the op-level parity tests -- and fu_test_get_buffer and
+// fu_test_loss_buffers, the only entry points here that look inside a context.
 #include "fu_ctx.h"
 
 #include <vector>
@@ -267,6 +267,15 @@ int fu_test_get_buffer(fu_ctx* c, int block, int which, void** ptr, int64_t* ele
     case 5: *ptr = K.g_up; *elems = K.kind == BK_UP ? act(K.level, K.c[0].cin_real - c->ch[K.skip]) : 0; break;
     default: set_error("fu_test_get_buffer: which must be 0..5"); return FU_ERR_INVALID;
   }
+  return FU_OK;
+}
+
+int fu_test_loss_buffers(fu_ctx* c, float** logits, float** dlogits, int64_t* elems) {
+  FU_REQUIRE(c && logits && dlogits && elems, "fu_test_loss_buffers: null argument");
+  const fu_config& f = c->cfg;
+  *logits = c->logits;
+  *dlogits = c->dlogits;
+  *elems = (int64_t)f.max_batch * f.height * f.width * f.n_classes;
   return FU_OK;
 }
 

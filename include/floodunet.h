@@ -179,7 +179,9 @@ int fu_loss_ce_focal(fu_ctx* ctx, const int64_t* target, int ignore_index, const
                      float* weight_sum_out, fu_stream stream);
 /* North-star extension (no reference counterpart; specification = oracle/unet_oracle.py:bce_dice_loss):
  * BCE on p = softmax(z)[1] vs [target == 1] + dice_weight * soft Dice, over target != ignore_index, fp32 wave-shuffle
- * reductions; stores its logits gradient for fu_backward like fu_loss_ce. */
+ * reductions; stores its logits gradient for fu_backward like fu_loss_ce.  log(1 - p) is the logsumexp over the other classes
+ * (with their own maximum) minus the logsumexp over all: finite, with a gradient row that sums to zero, however far class 1
+ * leads.  Every pixel ignored: loss 0 and a zero gradient. */
 int fu_loss_bce_dice(fu_ctx* ctx, const int64_t* target, int ignore_index, float dice_weight, float* loss_out,
                      fu_stream stream);
 
@@ -608,6 +610,11 @@ void fu_test_perturb_bnb_sums(float factor);
  * for the second conv, 4 = dL/d(pooled input) (down blocks), 5 = dL/d(upsampled input) (up blocks).  Elements are of
  * the context's precision. */
 int fu_test_get_buffer(fu_ctx* ctx, int block, int which, void** ptr, int64_t* elems);
+/* Testing hook: the context's resident fp32 NHWC logits [B, H, W, n_classes] (what fu_forward leaves and fu_loss_* reads),
+ * the stored loss gradient of the same shape (what fu_loss_* writes in training mode) and their element count at
+ * max_batch.  The op-level loss tests copy constructed logits over the resident ones after a forward, call one fu_loss_*
+ * entry and read the gradient back; nothing in the library calls this. */
+int fu_test_loss_buffers(fu_ctx* ctx, float** logits, float** dlogits, int64_t* elems);
 
 /* ---- single operators (per-op parity tests; NHWC device buffers of the context's precision) -- */
 /* element size of the activation type for `precision` */

@@ -42,6 +42,7 @@ def test_bad_arguments_are_reported_not_crashed():
     assert lib.fu_create(ctypes.byref(cfg), ctypes.byref(h)) == _lib.FU_ERR_INVALID
     with pytest.raises(_lib.FloodUNetError):
         _lib.check(lib.fu_param_info(None, 0, None, None, None, None))
+    assert lib.fu_test_loss_buffers(None, None, None, None) == _lib.FU_ERR_INVALID
 
 
 def test_missing_library_fails_loudly(monkeypatch):

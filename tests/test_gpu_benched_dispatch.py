@@ -16,6 +16,8 @@ at fixture sizes by default), whose dgrad launches also emit the next BatchNorm 
   and a negative control: with the fused sums deliberately multiplied by 1.1 (fu_test_perturb_bnb_sums) (b) and (c) fail.
 """
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -26,6 +28,9 @@ from conftest import case_inputs, is_dead_bias, load_golden
 from floodplanet_code_amd import _lib
 from floodplanet_code_amd._lib import check, ptr
 from floodplanet_code_amd.unet import HipUNet
+
+sys.path.insert(0, os.path.dirname(__file__))
+from tools.hip_mem import memcpy_dtod as _memcpy_dtod  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -424,20 +429,6 @@ def test_negative_control_perturbed_fused_sums_fail_the_op_checks(prec, forced_r
 # ------------------------------------------------------------------------------------------------------------------
 # (c) per backward block at the bench shape: default dispatch == conservative dispatch to the element type's rounding
 # ------------------------------------------------------------------------------------------------------------------
-_hip = None
-
-
-def _memcpy_dtod(dst, src, nbytes):
-    """hipMemcpy device -> device through the process's HIP runtime (the one torch loaded)."""
-    global _hip
-    if _hip is None:
-        _hip = C.CDLL("libamdhip64.so")
-        _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        _hip.hipMemcpy.restype = C.c_int
-    rc = _hip.hipMemcpy(C.c_void_p(dst), C.c_void_p(src), C.c_size_t(nbytes), 3)   # hipMemcpyDeviceToDevice
-    assert rc == 0, rc
-
-
 def _buffer(net, block, which, dt):
     """Snapshot of one context-owned 16-bit tensor (fu_test_get_buffer) as a torch tensor."""
     lib = _lib.load()
