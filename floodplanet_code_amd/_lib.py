@@ -98,6 +98,11 @@ class FuBandAccum(C.Structure):
     ]
 
 
+class FuRegionLoss(C.Structure):
+    """fu_region_loss: the region term of fu_loss_ce_region (a host struct)"""
+    _fields_ = [("weight", C.c_float), ("alpha", C.c_float), ("beta", C.c_float), ("smooth", C.c_float)]
+
+
 class FloodUNetError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"libfloodunet error {status}: {message}")
@@ -131,6 +136,7 @@ SIGNATURES = {
     "fu_loss_ce": (_i, [_p, _p, _i, _p, _p, _p, _p]),
     "fu_loss_ce_weighted": (_i, [_p, _p, _i, _p, _f, _p, _p, _p, _p, _p]),
     "fu_loss_ce_focal": (_i, [_p, _p, _i, _p, _f, _p, _p, _p, _p, _p]),
+    "fu_loss_ce_region": (_i, [_p, _p, _i, _p, _f, _f, C.POINTER(FuRegionLoss), _p, _p, _p, _p, _p, _p]),
     "fu_loss_bce_dice": (_i, [_p, _p, _i, _f, _p, _p]),
     "fu_backward": (_i, [_p, _p, _p]),
     "fu_num_blocks": (_i, [_p]),

@@ -271,17 +271,22 @@ int fu_merge_views(fu_ctx* c, float* probs_out, const int64_t* target, int ignor
 }
 
 namespace {
-// fu_loss_ce (cw == null), fu_loss_ce_weighted and fu_loss_ce_focal
+// fu_loss_ce (cw == null), fu_loss_ce_weighted and fu_loss_ce_focal; fu_loss_ce_region: any of the three, then the region
+// term (rg != null) inside the same SyncScope
 int loss_ce(fu_ctx* c, const char* who, const int64_t* target, int ignore_index, const CeWeighting* cw, float* loss_out,
-            int64_t* confusion_out, int64_t* n_valid_out, fu_stream stream) {
+            int64_t* confusion_out, int64_t* n_valid_out, fu_stream stream, const RegionTerm* rg = nullptr) {
   FU_REQUIRE(c->last_batch > 0, "%s: no forward pass yet", who);
   hipStream_t s = (hipStream_t)stream;
   SyncScope sc(c, c->fwd_training);
   const int64_t npix = (int64_t)c->last_batch * c->cfg.height * c->cfg.width;
   FU_TRY(launch_ce_loss(c->logits, target, c->cfg.n_classes, ignore_index, npix, cw, c->ce_part,
                         loss_out ? loss_out : c->loss_dev, c->n_valid, confusion_out, n_valid_out, c->conf_tmp, s));
-  if (c->fwd_training) {
+  if (c->fwd_training)
     FU_TRY(launch_ce_grad(c->logits, target, c->cfg.n_classes, ignore_index, npix, cw, c->n_valid, c->dlogits, s));
+  if (rg)
+    FU_TRY(launch_region_term(c->logits, target, c->cfg.n_classes, ignore_index, npix, *rg, c->ce_part,
+                              loss_out ? loss_out : c->loss_dev, c->fwd_training ? c->dlogits : nullptr, s));
+  if (c->fwd_training) {
     c->have_loss = true;
     c->have_up_scale = false;
   }
@@ -315,6 +320,41 @@ int fu_loss_ce_focal(fu_ctx* c, const int64_t* target, int ignore_index, const f
   // gamma == 0: launch_ce_loss / launch_ce_grad run the weighted instantiations -- fu_loss_ce_weighted(eps = 0) itself
   const CeWeighting cw = {class_weight_dev, 1.f, 0.f, c->ce_wsum, weight_sum_out, focal_gamma};
   return loss_ce(c, "fu_loss_ce_focal", target, ignore_index, &cw, loss_out, confusion_out, n_valid_out, stream);
+}
+
+int fu_loss_ce_region(fu_ctx* c, const int64_t* target, int ignore_index, const float* class_weight_dev,
+                      float label_smoothing, float focal_gamma, const fu_region_loss* region, float* loss_out,
+                      int64_t* confusion_out, int64_t* n_valid_out, float* weight_sum_out, float* region_out,
+                      fu_stream stream) {
+  FU_REQUIRE(c && target, "fu_loss_ce_region: null argument");
+  FU_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, "fu_loss_ce_region: label_smoothing %g outside [0, 1)",
+             (double)label_smoothing);
+  FU_REQUIRE(focal_gamma >= 0.f && focal_gamma < INFINITY, "fu_loss_ce_region: focal_gamma %g is not a finite number >= 0",
+             (double)focal_gamma);
+  FU_REQUIRE(!(focal_gamma > 0.f && label_smoothing != 0.f),
+             "fu_loss_ce_region: focal_gamma %g together with label_smoothing %g (a smoothed focal loss is not defined)",
+             (double)focal_gamma, (double)label_smoothing);
+  RegionTerm rg = {0.f, 0.f, 0.f, 0.f, c->region_coef, region_out};
+  if (region) {                                             // (NaN fails every comparison below)
+    FU_REQUIRE(region->weight >= 0.f && region->weight < INFINITY,
+               "fu_loss_ce_region: region weight %g is not a finite number >= 0", (double)region->weight);
+    FU_REQUIRE(region->alpha >= 0.f && region->alpha < INFINITY && region->beta >= 0.f && region->beta < INFINITY &&
+                   region->alpha + region->beta > 0.f,
+               "fu_loss_ce_region: alpha %g, beta %g must be finite and >= 0, with alpha + beta > 0", (double)region->alpha,
+               (double)region->beta);
+    FU_REQUIRE(region->smooth > 0.f && region->smooth < INFINITY, "fu_loss_ce_region: smooth %g is not a finite number > 0",
+               (double)region->smooth);
+    FU_REQUIRE(region->weight == 0.f || c->cfg.n_classes >= 2, "fu_loss_ce_region: a region term needs n_classes >= 2");
+    rg.weight = region->weight; rg.alpha = region->alpha; rg.beta = region->beta; rg.smooth = region->smooth;
+  }
+  const RegionTerm* term = rg.weight > 0.f ? &rg : nullptr;   // weight 0: nothing new is launched, the CE form's own bits
+  if (!class_weight_dev && label_smoothing == 0.f && focal_gamma == 0.f)
+    return loss_ce(c, "fu_loss_ce_region", target, ignore_index, nullptr, loss_out, confusion_out, n_valid_out, stream, term);
+  const CeWeighting cw = focal_gamma > 0.f
+                             ? CeWeighting{class_weight_dev, 1.f, 0.f, c->ce_wsum, weight_sum_out, focal_gamma}
+                             : CeWeighting{class_weight_dev, (float)(1.0 - (double)label_smoothing),
+                                           (float)((double)label_smoothing / c->cfg.n_classes), c->ce_wsum, weight_sum_out};
+  return loss_ce(c, "fu_loss_ce_region", target, ignore_index, &cw, loss_out, confusion_out, n_valid_out, stream, term);
 }
 
 int fu_loss_bce_dice(fu_ctx* c, const int64_t* target, int ignore_index, float dice_weight, float* loss_out,

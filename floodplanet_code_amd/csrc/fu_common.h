@@ -520,6 +520,19 @@ int launch_ce_loss(const float* logits_nhwc, const int64_t* target, int ncls, in
 // dlogits (NHWC fp32) from CE: (softmax - onehot)/n_valid on valid pixels; weighted: the gradient of the loss above
 int launch_ce_grad(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
                    const CeWeighting* cw, const int64_t* n_valid_dev, float* dlogits_nhwc, hipStream_t s);
+// fu_loss_ce_region's soft Tversky term (fu_loss.hip), run after launch_ce_loss / launch_ce_grad of the same call on the same
+// stream: adds weight * R to *loss_io and, where dlogits_nhwc is given (training forwards), its gradient to the stored CE
+// gradient.  weight > 0, alpha, beta >= 0 with alpha + beta > 0 and smooth > 0 are the caller's to check.  coef:
+// REGION_COEF_BYTES on the device (the gradient pass's coefficients); region_out: optional device [1 + ncls] = R, TI_k.
+// partials: LOSS_PART_FLOATS floats, free once the CE finalize has run.
+static constexpr int REGION_COEF_BYTES = 256;
+struct RegionTerm {
+  float weight, alpha, beta, smooth;
+  float* coef;
+  float* region_out;   // optional
+};
+int launch_region_term(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
+                       const RegionTerm& rg, float* partials, float* loss_io, float* dlogits_nhwc, hipStream_t s);
 // BCE + soft Dice on softmax(z)[1]; partials: LOSS_PART_FLOATS floats, coef 4 floats; dlogits may be null (eval)
 int launch_bce_dice(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
                     float dice_w, float* partials, float* coef, float* loss_out, int64_t* n_valid_dev,

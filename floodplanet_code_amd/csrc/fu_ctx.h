@@ -183,6 +183,7 @@ struct fu_ctx {
   float* hb_part = nullptr;
   float* loss_dev = nullptr;
   float* ce_wsum = nullptr;       // fu_loss_ce_weighted / _focal: D = sum of w[target] over the valid pixels, read by the gradient kernel
+  float* region_coef = nullptr;   // fu_loss_ce_region: A_k, B_k and lambda of the region term (REGION_COEF_BYTES), read by its gradient pass
   float* loss_scale = nullptr;    // fp16 mode: {S, 1/S} of the running backward (fu_common.h, launch_loss_grad_eff)
   int* guard = nullptr;           // fp16 mode: non-finite flag / skipped steps / back-off exponent / clean steps (k_guard_book)
   unsigned long long* conf_tmp = nullptr;

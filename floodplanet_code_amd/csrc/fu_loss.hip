@@ -1,5 +1,5 @@
-// Loss kernels of the training step (gfx950): softmax cross entropy (plain, class-weighted / label-smoothed, focal) and
-// BCE + soft Dice over the resident logits, with their deterministic reductions; the NCHW -> NHWC copy of an external
+// Loss kernels of the training step (gfx950): softmax cross entropy (plain, class-weighted / label-smoothed, focal), the soft
+// Tversky region term that goes with it, and BCE + soft Dice over the resident logits, with their deterministic reductions; the NCHW -> NHWC copy of an external
 // logits gradient; the gradient the head backward consumes (upstream factor, fp16 loss scale).
 #include "fu_common.h"
 
@@ -362,6 +362,170 @@ int launch_ce_grad(const float* logits_nhwc, const int64_t* target, int ncls, in
 #undef FU_CE_GRAD
 #undef FU_CE_GRAD_AS
   FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The soft Tversky region term added to a cross entropy (fu_loss_ce_region; the reference has no such loss, the
+// specification is tests/tools/region_ref.py).  Over the valid pixels of the CE, p = softmax(z), y_ik = [t_i == k]:
+//   I_k = sum_i p_ik y_ik,  P_k = sum_i p_ik,  T_k = sum_i y_ik,  Num_k = I_k + s,
+//   Den_k = I_k + alpha (P_k - I_k) + beta (T_k - I_k) + s,  TI_k = Num_k / Den_k,
+//   R = sum_{k in K} (1 - TI_k) / |K|,  K = the classes but ignore_index;  loss = CE + lambda R
+//   d(lambda R)/dz_ij = lambda p_ij (g_ij - sum_k g_ik p_ik),  g_ik = y_ik ? A_k : B_k,
+//   A_k = -(alpha (P_k - I_k) + beta (T_k + s)) / (|K| Den_k^2),  B_k = alpha Num_k / (|K| Den_k^2)   (0 outside K)
+// Passes of their own after the CE's, which stay as they are: k_region_sums -> (exact DP: the sum over the ranks) ->
+// k_region_finalize (fp64: R added to the loss the CE finalize wrote, A / B / lambda left on the device) ->
+// k_region_grad_add (training forwards: added to the stored CE gradient, valid pixels only).  The term follows pixel
+// validity, not the CE's summed weight D: valid pixels of zero-weight classes keep it alive.  No valid pixel: every sum is
+// 0, TI_k = s / s, R = 0 exactly, and the gradient pass touches nothing.
+// ------------------------------------------------------------------------------------------------
+// rows of partials per launch: a row is 3 sums for each of KMAX classes (KMAX = the class count up to 4, else HEAD_MAX_CLS),
+// and as many rows as fit the partial buffer are used: 682 / 455 / 341 blocks for 2 / 3 / 4 classes, 170 beyond.  The cap
+// sets the summation order (tests/tools/region_ref.py: region_cap).
+static constexpr int region_max_blocks(int kmax) { return LOSS_PART_FLOATS / (3 * kmax); }
+static_assert(3 * HEAD_MAX_CLS * region_max_blocks(HEAD_MAX_CLS) <= LOSS_PART_FLOATS && region_max_blocks(HEAD_MAX_CLS) >= 1,
+              "region partial rows");
+static_assert(3 * HEAD_MAX_CLS * 256 * sizeof(double) <= 64 * 1024, "partial_rows_sum of a region row: static LDS");
+static constexpr int REGION_COEF_FLOATS = 2 * HEAD_MAX_CLS + 1;   // A[HEAD_MAX_CLS], B[HEAD_MAX_CLS], lambda
+static_assert(REGION_COEF_FLOATS * sizeof(float) <= REGION_COEF_BYTES, "region coefficient buffer");
+
+// row of a block: I[KMAX], P[KMAX], T[KMAX] (T: counts, exact in fp32 -- a block adds fewer than 2^24 pixels)
+template <int NC>
+__global__ __launch_bounds__(CE_BLOCK) void k_region_sums(const float* __restrict__ logits,
+                                                          const int64_t* __restrict__ target, int ncls_rt,
+                                                          int ignore_index, int64_t npix, float* __restrict__ partials) {
+  constexpr int KMAX = NC ? NC : HEAD_MAX_CLS;
+  const int ncls = NC ? NC : ncls_rt;
+  float acc[3 * KMAX];
+#pragma unroll
+  for (int j = 0; j < 3 * KMAX; ++j) acc[j] = 0.f;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t t = target[p];
+    if (t != (int64_t)ignore_index && t >= 0 && t < ncls) {
+      float e[KMAX];
+      float m = -INFINITY, se = 0.f;
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < ncls) { e[k] = logits[p * ncls + k]; m = fmaxf(m, e[k]); }
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < ncls) { e[k] = expf(e[k] - m); se += e[k]; }
+      const float r = 1.f / se;
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        if (k < ncls) {
+          const float pk = e[k] * r;
+          const bool hit = (int)t == k;
+          acc[k] += hit ? pk : 0.f;
+          acc[KMAX + k] += pk;
+          acc[2 * KMAX + k] += hit ? 1.f : 0.f;
+        }
+      }
+    }
+  }
+  block_partial_row<3 * KMAX>(acc, partials + blockIdx.x * (3 * KMAX));
+}
+
+// one block.  coef: A[HEAD_MAX_CLS], B[HEAD_MAX_CLS], lambda; loss_io: the scalar the CE finalize wrote; region_out: optional
+// [1 + ncls] = R, TI_k (1 for the ignored class).  P_k - I_k and T_k - I_k are >= 0 in exact arithmetic; their fp32 partials
+// are rounded separately, so they are held at 0 from below.
+template <int KMAX>
+__global__ __launch_bounds__(256) void k_region_finalize(const float* __restrict__ partials, int nblk, int ncls,
+                                                         int ignore_index, float lambda, float alpha, float beta,
+                                                         float smooth, float* __restrict__ loss_io,
+                                                         float* __restrict__ coef, float* __restrict__ region_out) {
+  double a[3 * KMAX];
+  partial_rows_sum<3 * KMAX>(partials, nblk, a);
+  if (threadIdx.x != 0) return;
+  int nk = 0;
+  for (int k = 0; k < ncls; ++k) nk += (k != ignore_index);
+  const double al = alpha, be = beta, s = smooth;
+  double R = 0.0;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    const bool in = k < ncls && k != ignore_index;
+    const double I = a[k], T = a[2 * KMAX + k];
+    const double fp = fmax(a[KMAX + k] - I, 0.0), fn = fmax(T - I, 0.0);
+    const double num = I + s, den = I + al * fp + be * fn + s;
+    const double ti = num / den, q = in ? 1.0 / ((double)nk * den * den) : 0.0;
+    if (in) R += 1.0 - ti;
+    coef[k] = (float)(-(al * fp + be * (T + s)) * q);
+    coef[HEAD_MAX_CLS + k] = (float)(al * num * q);
+    if (region_out && k < ncls) region_out[1 + k] = in ? (float)ti : 1.f;
+  }
+  for (int k = KMAX; k < HEAD_MAX_CLS; ++k) coef[k] = coef[HEAD_MAX_CLS + k] = 0.f;
+  R = nk > 0 ? R / nk : 0.0;
+  coef[2 * HEAD_MAX_CLS] = lambda;
+  *loss_io += (float)((double)lambda * R);
+  if (region_out) region_out[0] = (float)R;
+}
+
+// dl += lambda p_j (g_j - sum_k g_k p_k) on the valid pixels; the others are not read, not written
+template <int NC>
+__global__ __launch_bounds__(256) void k_region_grad_add(const float* __restrict__ logits,
+                                                         const int64_t* __restrict__ target, int ncls_rt,
+                                                         int ignore_index, int64_t npix, const float* __restrict__ coef,
+                                                         float* __restrict__ dl) {
+  constexpr int KMAX = NC ? NC : HEAD_MAX_CLS;
+  const int ncls = NC ? NC : ncls_rt;
+  float A[KMAX], B[KMAX];
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) { A[k] = coef[k]; B[k] = coef[HEAD_MAX_CLS + k]; }
+  const float lambda = coef[2 * HEAD_MAX_CLS];
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t t = target[p];
+    if (!(t != (int64_t)ignore_index && t >= 0 && t < ncls)) continue;
+    float e[KMAX], g[KMAX];
+    float m = -INFINITY, se = 0.f;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < ncls) { e[k] = logits[p * ncls + k]; m = fmaxf(m, e[k]); }
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < ncls) { e[k] = expf(e[k] - m); se += e[k]; }
+    const float r = 1.f / se;
+    float gp = 0.f;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      if (k < ncls) {
+        e[k] *= r;
+        g[k] = (int)t == k ? A[k] : B[k];
+        gp += g[k] * e[k];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < ncls) dl[p * ncls + k] += lambda * e[k] * (g[k] - gp);
+  }
+}
+
+int launch_region_term(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
+                       const RegionTerm& rg, float* partials, float* loss_io, float* dlogits_nhwc, hipStream_t s) {
+  FU_REQUIRE(ncls >= 2 && ncls <= HEAD_MAX_CLS, "region term: n_classes must be 2..%d", HEAD_MAX_CLS);
+  const int kmax = ncls <= 4 ? ncls : HEAD_MAX_CLS;               // the KMAX of FU_NC_SWITCH's instantiation
+  const int nblk = grid_for(npix, CE_BLOCK, region_max_blocks(kmax));
+#define FU_REGION_SUMS(NC)                                                                                    \
+  hipLaunchKernelGGL((k_region_sums<NC>), dim3(nblk), dim3(CE_BLOCK), 0, s, logits_nhwc, target, ncls, ignore_index, \
+                     npix, partials)
+#define FU_REGION_FINALIZE(NC)                                                                                      \
+  hipLaunchKernelGGL((k_region_finalize<(NC ? NC : HEAD_MAX_CLS)>), dim3(1), dim3(256), 0, s, partials, nblk, ncls, \
+                     ignore_index, rg.weight, rg.alpha, rg.beta, rg.smooth, loss_io, rg.coef, rg.region_out)
+#define FU_REGION_GRAD(NC)                                                                                         \
+  hipLaunchKernelGGL((k_region_grad_add<NC>), dim3(grid_for(npix, 256, 4096)), dim3(256), 0, s, logits_nhwc, target, \
+                     ncls, ignore_index, npix, rg.coef, dlogits_nhwc)
+  FU_NC_SWITCH(ncls, FU_REGION_SUMS);
+  FU_LAUNCH_CHECK();
+  // exact DP: I, P and T of the whole batch, so that every rank forms the same R and the same coefficients
+  FU_TRY(sync_sum_over_ranks(partials, (int64_t)nblk * 3 * kmax, false, s));
+  FU_NC_SWITCH(ncls, FU_REGION_FINALIZE);
+  FU_LAUNCH_CHECK();
+  if (dlogits_nhwc) {
+    FU_NC_SWITCH(ncls, FU_REGION_GRAD);
+    FU_LAUNCH_CHECK();
+  }
+#undef FU_REGION_SUMS
+#undef FU_REGION_FINALIZE
+#undef FU_REGION_GRAD
   return 0;
 }
 #undef FU_NC_SWITCH

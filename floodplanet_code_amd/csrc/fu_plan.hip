@@ -376,6 +376,7 @@ int alloc_workspace(fu_ctx* c) {
   A.want(&c->slab, max_slab * sizeof(float));
   A.want(&c->ce_part, LOSS_PART_FLOATS * sizeof(float));
   A.want(&c->ce_wsum, 256);
+  A.want(&c->region_coef, REGION_COEF_BYTES);
   A.want(&c->hb_part, head_bwd_partial_elems(f.base_channels, f.n_classes) * sizeof(float));
   A.want(&c->loss_dev, 256);
   A.want(&c->loss_scale, 256);

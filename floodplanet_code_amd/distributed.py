@@ -122,13 +122,18 @@ class DataParallelTrainer:
     def __init__(self, net, lr: float, world_size: int = 1, rank: int = 0, betas=(0.9, 0.999), eps: float = 1e-8,
                  group=None, cap_bytes: int = 16 << 20, exact: bool = False, time_waits: bool = False,
                  graph: bool = False, class_weight=None, label_smoothing: float = 0.0, ema_decay: Optional[float] = None,
-                 ema_warmup: bool = True, focal_gamma: float = 0.0):
+                 ema_warmup: bool = True, focal_gamma: float = 0.0, region_weight: float = 0.0, region_alpha: float = 0.5,
+                 region_beta: float = 0.5, region_smooth: float = 1.0):
         """exact=False: DDP semantics (per-rank BN statistics and 1/N_valid, gradients averaged).
         exact=True: SyncBN statistics and a global N_valid (HipUNet.enable_exact_sync); the ranks together reproduce
         one device with world_size x the batch, gradients are summed (SURVEY.md 8(e) "exact mode").
         class_weight / label_smoothing: the weighted, label-smoothed cross entropy of HipUNet.loss for every step (defaults:
         the reference's loss); in exact mode its denominator, the summed weight of the valid pixels, is global too.
         focal_gamma > 0: the focal form of that loss (HipUNet.loss), on the eager, exact and captured paths alike.
+        region_weight > 0: that loss plus region_weight times the soft Tversky region term (region_alpha, region_beta,
+        region_smooth; HipUNet.loss) on the same three paths.  In exact mode its per-class sums are global, so every rank
+        forms the whole batch's term; its coefficients stay on the device and the options are kernel arguments fixed at
+        capture -- nothing is read back.
         ema_decay: keep a weight EMA on the net (HipUNet.enable_ema(ema_decay, ema_warmup)), moved on inside the fused Adam
         launch of every path -- eager, exact and captured.  It is rank-local and needs no collective: the ranks' parameters
         are identical, so their averages are."""
@@ -136,8 +141,12 @@ class DataParallelTrainer:
             net.enable_ema(ema_decay, ema_warmup)
         self.net, self.lr, self.world_size, self.rank = net, lr, world_size, rank
         self.class_weight, self.label_smoothing = class_weight, float(label_smoothing)
-        from .unet import check_focal_gamma
+        from .unet import check_focal_gamma, check_region_loss
         self.focal_gamma = check_focal_gamma(focal_gamma, label_smoothing)
+        self.region_weight, self.region_alpha, self.region_beta, self.region_smooth = check_region_loss(
+            region_weight, region_alpha, region_beta, region_smooth)
+        if self.region_weight > 0.0 and net.n_classes < 2:
+            raise ValueError("a region term (region_weight > 0) needs n_classes >= 2")
         self.betas, self.eps, self.group, self.cap_bytes = betas, eps, group, cap_bytes
         self.exact = bool(exact) and world_size > 1
         if self.exact:
@@ -157,6 +166,10 @@ class DataParallelTrainer:
         self._reducer: Optional[BucketedReducer] = None
         self._launch_stream = None     # the stream the bucket all-reduces are launched from (mode 2, fu_backward_fence)
         self._synced = False
+
+    def _region_kwargs(self) -> dict:
+        return dict(region_weight=self.region_weight, region_alpha=self.region_alpha, region_beta=self.region_beta,
+                    region_smooth=self.region_smooth)
 
     def _side_mode(self) -> int:
         if _DIAG_MODE is not None:
@@ -220,13 +233,16 @@ class DataParallelTrainer:
         self._gscal_ev = [None] * 8
         lib = _lib.load()
         net._class_weight_dev(self.class_weight, dev)                # the weights' upload stays outside the capture
+        if self.region_weight > 0.0:
+            net._region_terms_dev(dev)                               # ... and so does the region report's allocation
         torch.cuda.synchronize(dev)
         dot = os.environ.get("FU_GRAPH_DOT")                          # diagnostics: hipGraphDebugDotPrint of the captured step (tools/graph_dot.py)
         g = torch.cuda.CUDAGraph(keep_graph=True) if dot else torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             net._forward_raw(self._gx, True, want_logits=False)
             self._gloss = net._loss_raw(self._gt, self._g_ignore, dev, class_weight=self.class_weight,
-                                        label_smoothing=self.label_smoothing, focal_gamma=self.focal_gamma)
+                                        label_smoothing=self.label_smoothing, focal_gamma=self.focal_gamma,
+                                        **self._region_kwargs())
             net._backward_raw(None, dev)
             if self._g_ema:
                 _lib.check(lib.fu_adam_ema_step_dev(net._ctx, self._gscal.data_ptr(), net._stream(dev)))
@@ -272,7 +288,7 @@ class DataParallelTrainer:
             self._sync_initial_state(x.device)
         net._forward_raw(x, True, want_logits=False)
         loss = net._loss_raw(target, ignore_index, x.device, class_weight=self.class_weight,
-                             label_smoothing=self.label_smoothing, focal_gamma=self.focal_gamma)
+                             label_smoothing=self.label_smoothing, focal_gamma=self.focal_gamma, **self._region_kwargs())
         if self.world_size <= 1 and not _FORCE_BLOCKS:
             net._backward_raw(None, x.device)
         else:

@@ -34,7 +34,7 @@ from typing import Dict, Iterable, List, Optional
 import torch
 
 from .models import build_model
-from .unet import check_focal_gamma
+from .unet import check_focal_gamma, check_region_loss
 
 DEFAULTS = dict(lr=1e-4, batch_size=10, n_epochs=11, crop_height=300, crop_width=300, ignore_index=0,
                 save_topk_models=3, limit_train_batches=None, limit_val_batches=None, log_image_iter=200,
@@ -88,7 +88,8 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
     """Restatement of fit.py:16-103 without Lightning.  Returns the best checkpoint path ('' if exp_dir is None).
     model: an already built model to train in place of the build_model call (a loader that needs the network's context,
     SceneTileLoader, is made before fit_model runs).  The trained model keeps `history`, one dict per epoch: epoch, train_loss
-    (the last step's), val_MulticlassJaccardIndex and train_tiles_per_s -- the tiles of the epoch's training loop over its
+    (the last step's), train_region (that step's region term R, when the model's region_weight > 0),
+    val_MulticlassJaccardIndex and train_tiles_per_s -- the tiles of the epoch's training loop over its
     host time, closed by one device synchronise per epoch (None when the train loader yields nothing) -- plus `plan`, the
     train loader's `last_plan`, when it has one."""
     c = dict(DEFAULTS)
@@ -117,6 +118,9 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
         if torch.device(device).type == "cuda":
             torch.cuda.synchronize(device)                                   # one sync: the rate covers finished steps
         train_seconds = time.perf_counter() - t0
+        train_region = None                                                  # R of the last step, before validation rewrites it
+        if getattr(model, "region_weight", 0.0) > 0.0 and n_tiles:
+            train_region = float(model.model.last_region_terms()[0])
         model.valid_metrics.reset()
         outs = []
         with model.eval_weights():                                           # the weight EMA, swapped in once per epoch
@@ -126,6 +130,8 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
         miou = float(model.logged.get("val_MulticlassJaccardIndex", torch.zeros(())))
         history.append({"epoch": epoch, "train_loss": float(loss.detach()), "val_MulticlassJaccardIndex": miou,
                         "train_tiles_per_s": n_tiles / train_seconds if n_tiles and train_seconds > 0 else None})
+        if train_region is not None:
+            history[-1]["train_region"] = train_region
         plan = getattr(train_loader, "last_plan", None)                      # a loader that chooses its tiles says which
         if plan is not None:
             history[-1]["plan"] = dict(plan)
@@ -184,6 +190,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--focal_gamma", type=float, default=0.0, metavar="F",
                     help="focal loss: every pixel's cross-entropy term times (1 - p[target])^F, F >= 0 (default 0: plain "
                          "cross entropy); combines with --class_weights, not with --label_smoothing")
+    ap.add_argument("--region_loss", type=str, default=None, choices=["dice", "jaccard", "tversky"],
+                    help="add a soft region term over all classes to the cross entropy: dice (alpha = beta = 0.5), jaccard "
+                         "(alpha = beta = 1) or tversky (--tversky A B); combines with every cross-entropy option")
+    ap.add_argument("--region_weight", type=float, default=None, metavar="F",
+                    help="the region term's weight, >= 0 (default 1 once --region_loss is given)")
+    ap.add_argument("--tversky", type=float, nargs=2, default=None, metavar=("A", "B"),
+                    help="--region_loss tversky: the weights of false positives (A) and false negatives (B)")
+    ap.add_argument("--region_smooth", type=float, default=None, metavar="S",
+                    help="the region term's smoothing, > 0 (default 1)")
     ap.add_argument("--ema_decay", type=float, default=None, metavar="F",
                     help="keep an exponential moving average of the weights with this decay in [0, 1): validation, the "
                          "checkpoint choice and the checkpoint's ema_state_dict use it (default: no EMA)")
@@ -241,10 +256,30 @@ def sampling_from_args(args) -> dict:
     return given
 
 
+REGION_KINDS = {"dice": (0.5, 0.5), "jaccard": (1.0, 1.0)}
+
+
+def region_from_args(args) -> dict:
+    """The region term a command line gave, as model keyword arguments ({} for none), checked: --region_weight, --tversky and
+    --region_smooth need --region_loss, --tversky goes with `tversky` and only with it."""
+    kind = getattr(args, "region_loss", None)
+    weight, tversky, smooth = (getattr(args, k, None) for k in ("region_weight", "tversky", "region_smooth"))
+    if kind is None:
+        given = [n for n, v in (("region_weight", weight), ("tversky", tversky), ("region_smooth", smooth)) if v is not None]
+        if given:
+            raise ValueError("--" + ", --".join(given) + " need --region_loss")
+        return {}
+    if (kind == "tversky") != (tversky is not None):
+        raise ValueError("--region_loss tversky and --tversky A B go together")
+    alpha, beta = tversky if kind == "tversky" else REGION_KINDS[kind]
+    w, a, b, s = check_region_loss(1.0 if weight is None else weight, alpha, beta, 1.0 if smooth is None else smooth)
+    return dict(region_weight=w, region_alpha=a, region_beta=b, region_smooth=s)
+
+
 def cfg_from_args(args, class_weights=None) -> dict:
     """The reference-style config of a command line: what fit_model trains with and dumps into the checkpoint.
     class_weights: the resolved numeric weights (the data decides 'balanced' and the class count, so main() resolves them);
-    they, --label_smoothing, --focal_gamma, --ema_decay and --no_ema_warmup enter model_kwargs only when set, and the
+    they, --label_smoothing, --focal_gamma, --region_loss, --ema_decay and --no_ema_warmup enter model_kwargs only when set, and the
     tile-sampling options a `sampling` key beside `model` only when given, so a plain command line gives the config it
     always gave."""
     norm_mode = None if args.norm_mode == "none" else args.norm_mode
@@ -259,6 +294,7 @@ def cfg_from_args(args, class_weights=None) -> dict:
     gamma = check_focal_gamma(getattr(args, "focal_gamma", 0.0), getattr(args, "label_smoothing", 0.0))
     if gamma != 0.0:
         loss_kwargs["focal_gamma"] = gamma
+    loss_kwargs.update(region_from_args(args))
     if getattr(args, "ema_decay", None) is not None:
         from .ema import check_decay
         loss_kwargs["ema_decay"] = check_decay(args.ema_decay)
@@ -324,7 +360,8 @@ def main(argv: Optional[List[str]] = None) -> dict:
             class_counts = train.class_counts().cpu().numpy()
             cfg = cfg_from_args(args, balanced_class_weights(class_counts, c["ignore_index"]).tolist())
             c.update(cfg)
-            model.set_loss_options(cfg["model"]["model_kwargs"]["class_weights"], model.label_smoothing, model.focal_gamma)
+            model.set_loss_options(cfg["model"]["model_kwargs"]["class_weights"], model.label_smoothing, model.focal_gamma,
+                                   model.region_weight, model.region_alpha, model.region_beta, model.region_smooth)
     else:
         common = dict(seed=c["seed_num"], ignore_index=c["ignore_index"], num_workers=args.n_workers,
                       device_assembly=True, device_resize=True)

@@ -13,7 +13,9 @@ Extra keyword arguments (not in the reference): ``precision`` ('fp32' | 'bf16' |
 ``class_weights`` (n_classes finite values >= 0) and ``label_smoothing`` in [0, 1): the weighted, label-smoothed cross
 entropy of nn.CrossEntropyLoss(weight, ignore_index, label_smoothing), in the fused loss kernels; ``focal_gamma`` >= 0:
 every pixel's cross-entropy term times (1 - p[target])^focal_gamma (the focal loss; not together with label smoothing;
-``loss_func`` stays the plain nn.CrossEntropyLoss); ``ema_decay`` in [0, 1)
+``loss_func`` stays the plain nn.CrossEntropyLoss); ``region_weight`` >= 0 with ``region_alpha``, ``region_beta``,
+``region_smooth``: the cross entropy plus region_weight times the soft Tversky region term over all classes but the ignored
+one (alpha = beta = 0.5: soft Dice, 1 and 1: soft Jaccard; fu_loss_ce_region, HipUNet.loss); ``ema_decay`` in [0, 1)
 and ``ema_warmup``: an exponential moving average of the weights, updated inside the fused Adam launch, that validation and
 test steps evaluate and that checkpoints carry as the top-level entry ``ema_state_dict`` (state_dict() stays the raw
 weights under the reference's keys).
@@ -30,20 +32,22 @@ import torch.optim as optim
 from ..lightning_compat import LightningModule
 from ..metrics import SegmentationMetrics
 from ..ema import check_decay
-from ..unet import HipAdam, HipUNet, check_class_weight, check_focal_gamma, check_label_smoothing
+from ..unet import HipAdam, HipUNet, check_class_weight, check_focal_gamma, check_label_smoothing, check_region_loss
 
 
 class WaterSegmentationModel(LightningModule):
 
     def __init__(self, in_channels, n_classes, lr, log_image_iter=50, to_rgb_fcn=None, ignore_index=None,
                  optimizer_name='adam', precision='fp32', base_channels=64, class_weights=None, label_smoothing=0.0,
-                 ema_decay=None, ema_warmup=True, focal_gamma=0.0):
+                 ema_decay=None, ema_warmup=True, focal_gamma=0.0, region_weight=0.0, region_alpha=0.5, region_beta=0.5,
+                 region_smooth=1.0):
         super().__init__()
         # checked on the host before anything touches the GPU; kept as plain Python numbers (checkpoint hyper_parameters)
         self.class_weights = (None if class_weights is None
                               else tuple(float(v) for v in check_class_weight(class_weights, n_classes)))
         self.label_smoothing = check_label_smoothing(label_smoothing)
         self.focal_gamma = check_focal_gamma(focal_gamma, self.label_smoothing)
+        self._set_region_options(n_classes, region_weight, region_alpha, region_beta, region_smooth)
         self.ema_decay = None if ema_decay is None else check_decay(ema_decay)
         self.ema_warmup = bool(ema_warmup)
         self.lr = lr
@@ -68,14 +72,22 @@ class WaterSegmentationModel(LightningModule):
         self.to_rgb_fcn = to_rgb_fcn
         self.log_image_iter = log_image_iter
 
-    def set_loss_options(self, class_weights=None, label_smoothing=0.0, focal_gamma=0.0):
-        """Replace the loss's class weights / label smoothing / focal exponent after construction (weights that are counted
-        from data the model's own device context serves, fit's `--class_weights balanced`).  Same checks as the
+    def _set_region_options(self, n_classes, weight, alpha, beta, smooth):
+        self.region_weight, self.region_alpha, self.region_beta, self.region_smooth = check_region_loss(weight, alpha, beta,
+                                                                                                        smooth)
+        if self.region_weight > 0.0 and n_classes < 2:
+            raise ValueError("a region term (region_weight > 0) needs n_classes >= 2")
+
+    def set_loss_options(self, class_weights=None, label_smoothing=0.0, focal_gamma=0.0, region_weight=0.0,
+                         region_alpha=0.5, region_beta=0.5, region_smooth=1.0):
+        """Replace the loss's class weights / label smoothing / focal exponent / region term after construction (weights that
+        are counted from data the model's own device context serves, fit's `--class_weights balanced`).  Same checks as the
         constructor."""
         self.class_weights = (None if class_weights is None
                               else tuple(float(v) for v in check_class_weight(class_weights, self.n_classes)))
         self.label_smoothing = check_label_smoothing(label_smoothing)
         self.focal_gamma = check_focal_gamma(focal_gamma, self.label_smoothing)
+        self._set_region_options(self.n_classes, region_weight, region_alpha, region_beta, region_smooth)
         self._make_loss_func()
         return self
 
@@ -153,7 +165,9 @@ class WaterSegmentationModel(LightningModule):
         images = self._gather_sources(batch)
         out = self.model.loss(images, batch['target'], self._loss_ignore, return_logits=want_logits,
                               class_weight=self.class_weights, label_smoothing=self.label_smoothing,
-                              focal_gamma=self.focal_gamma)
+                              focal_gamma=self.focal_gamma, region_weight=self.region_weight,
+                              region_alpha=self.region_alpha, region_beta=self.region_beta,
+                              region_smooth=self.region_smooth)
         loss, output = out if want_logits else (out, None)
         counts = self.model.pop_confusion()
         return loss, output, counts

@@ -506,12 +506,30 @@ class HipUNet(nn.Module):
         None before such a call."""
         return getattr(self, "_wce_sums", None)
 
+    def last_region_terms(self):
+        """fp32 [1 + n_classes] on the device, written by the last fu_loss_ce_region call with a region weight > 0: [0] = R,
+        the mean of 1 - TI_k over the classes but ignore_index (before the weight), [1 + k] = the soft Tversky index TI_k
+        (1.0 for the class equal to ignore_index).  None before such a call."""
+        return getattr(self, "_region_terms", None)
+
+    def _region_terms_dev(self, device) -> torch.Tensor:
+        terms = getattr(self, "_region_terms", None)
+        if terms is None or terms.device != torch.device(device):
+            terms = self._region_terms = torch.zeros(1 + self.n_classes, dtype=torch.float32, device=device)
+        return terms
+
     def _loss_raw(self, target: torch.Tensor, ignore_index: int, device, kind: str = "ce",
                   dice_weight: float = 1.0, class_weight=None, label_smoothing: float = 0.0,
-                  focal_gamma: float = 0.0) -> torch.Tensor:
+                  focal_gamma: float = 0.0, region_weight: float = 0.0, region_alpha: float = 0.5,
+                  region_beta: float = 0.5, region_smooth: float = 1.0) -> torch.Tensor:
         gamma = check_focal_gamma(focal_gamma, label_smoothing)      # on the host, before the library is loaded
         if gamma != 0.0 and kind != "ce":
             raise ValueError(f"focal_gamma belongs to kind='ce'; kind={kind!r} does not take it")
+        region = check_region_loss(region_weight, region_alpha, region_beta, region_smooth)
+        if region[0] != 0.0 and kind != "ce":
+            raise ValueError(f"region_weight belongs to kind='ce'; kind={kind!r} does not take it")
+        if region[0] != 0.0 and self.n_classes < 2:
+            raise ValueError("a region term needs n_classes >= 2")
         lib = _lib.load()
         target = target.contiguous().long()
         loss = torch.empty((), dtype=torch.float32, device=device)
@@ -526,6 +544,21 @@ class HipUNet(nn.Module):
             raise ValueError(f"unknown loss kind {kind!r}")
         if self._confusion is None or self._confusion.device != device:
             self._confusion = torch.zeros(self.n_classes * self.n_classes, dtype=torch.int64, device=device)
+        if region[0] > 0.0:                   # CE (whichever form the other options select) + the region term, one call
+            eps = check_label_smoothing(label_smoothing)
+            cw = self._class_weight_dev(class_weight, device)
+            terms = self._region_terms_dev(device)
+            n_valid = wsum = None
+            if weighted or gamma != 0.0:
+                sums = getattr(self, "_wce_sums", None)
+                if sums is None or sums[0].device != torch.device(device):
+                    sums = self._wce_sums = (torch.zeros((), dtype=torch.int64, device=device),
+                                             torch.zeros((), dtype=torch.float32, device=device))
+                n_valid, wsum = sums
+            check(lib.fu_loss_ce_region(self._ctx, ptr(target), int(ignore_index), ptr(cw), eps, gamma,
+                                        _lib.FuRegionLoss(*region), ptr(loss), ptr(self._confusion), ptr(n_valid),
+                                        ptr(wsum), ptr(terms), self._stream(device)))
+            return loss
         if not weighted and gamma == 0.0:     # the reference's loss: the same call, the same kernels as ever
             check(lib.fu_loss_ce(self._ctx, ptr(target), int(ignore_index), ptr(loss), ptr(self._confusion), None,
                                  self._stream(device)))
@@ -631,34 +664,40 @@ class HipUNet(nn.Module):
 
     def loss(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int,
              return_logits: bool = False, kind: str = "ce", dice_weight: float = 1.0, class_weight=None,
-             label_smoothing: float = 0.0, focal_gamma: float = 0.0):
+             label_smoothing: float = 0.0, focal_gamma: float = 0.0, region_weight: float = 0.0,
+             region_alpha: float = 0.5, region_beta: float = 0.5, region_smooth: float = 1.0):
         """Fused forward + CrossEntropyLoss(ignore_index) (+ NaN guard) of water_seg_model.py:101-106
         (kind='ce', the reference's loss) or the BCE + soft-Dice extension (kind='bce_dice').
         kind='ce' also takes class_weight (n_classes finite values >= 0: a sequence or a tensor) and label_smoothing in
         [0, 1): nn.CrossEntropyLoss(weight, ignore_index, label_smoothing) in the fused kernels (fu_loss_ce_weighted), with
         loss 0 and a zero gradient where the summed weight of the valid pixels is 0.  focal_gamma > 0 (kind='ce', without
         label smoothing) multiplies every pixel's term by (1 - p[target])^focal_gamma, the focal loss of Lin et al.
-        (fu_loss_ce_focal), normalised by the same summed weight.  With all three at their defaults the reference's loss
-        runs exactly as before.
+        (fu_loss_ce_focal), normalised by the same summed weight.  region_weight > 0 (kind='ce') adds region_weight * R, the
+        soft Tversky region term over all classes but ignore_index (fu_loss_ce_region): R = mean_k (1 - TI_k), TI_k =
+        (I + s) / (I + region_alpha (P - I) + region_beta (T - I) + s) with s = region_smooth; alpha = beta = 0.5 is soft
+        Dice, alpha = beta = 1 soft Jaccard; class weights do not enter it (last_region_terms() holds R and TI_k).  With all
+        of them at their defaults the reference's loss runs exactly as before.
         The returned loss is differentiable: ``loss.backward()`` runs the HIP backward."""
         if self.training and torch.is_grad_enabled():
             params = [p for _, p, _, _ in self._table]
             out = _UNetLossFn.apply(self, x, target, int(ignore_index), bool(return_logits), kind,
                                     float(dice_weight), class_weight, float(label_smoothing), float(focal_gamma),
+                                    float(region_weight), float(region_alpha), float(region_beta), float(region_smooth),
                                     *params)
             return out if return_logits else out[0]
         logits = self._forward_raw(x, self.training, want_logits=return_logits)
         loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, class_weight, label_smoothing,
-                              focal_gamma)
+                              focal_gamma, region_weight, region_alpha, region_beta, region_smooth)
         return (loss, logits) if return_logits else loss
 
     def train_step(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int, kind: str = "ce",
                    dice_weight: float = 1.0, class_weight=None, label_smoothing: float = 0.0,
-                   focal_gamma: float = 0.0) -> torch.Tensor:
+                   focal_gamma: float = 0.0, region_weight: float = 0.0, region_alpha: float = 0.5,
+                   region_beta: float = 0.5, region_smooth: float = 1.0) -> torch.Tensor:
         """forward + loss + backward without autograd; gradients land in the flat buffer / p.grad."""
         self._forward_raw(x, True, want_logits=False)
         loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, class_weight, label_smoothing,
-                              focal_gamma)
+                              focal_gamma, region_weight, region_alpha, region_beta, region_smooth)
         self._backward_raw(None, _device_of(x))
         self.attach_grads()
         return loss
@@ -741,6 +780,20 @@ def check_focal_gamma(focal_gamma, label_smoothing=0.0) -> float:
     return gamma
 
 
+def check_region_loss(weight=0.0, alpha=0.5, beta=0.5, smooth=1.0):
+    """The region term's options as floats (weight, alpha, beta, smooth).  ValueError unless weight is finite and >= 0, alpha
+    and beta are finite and >= 0 with alpha + beta > 0, and smooth is finite and > 0 (the rules of fu_loss_ce_region)."""
+    import math
+    w, a, b, s = float(weight), float(alpha), float(beta), float(smooth)
+    if not (math.isfinite(w) and w >= 0.0):
+        raise ValueError(f"region_weight must be finite and >= 0, got {weight!r}")
+    if not (math.isfinite(a) and math.isfinite(b) and a >= 0.0 and b >= 0.0 and a + b > 0.0):
+        raise ValueError(f"region_alpha, region_beta must be finite and >= 0 with alpha + beta > 0, got {alpha!r}, {beta!r}")
+    if not (math.isfinite(s) and s > 0.0):
+        raise ValueError(f"region_smooth must be finite and > 0, got {smooth!r}")
+    return w, a, b, s
+
+
 def _device_of(x):
     return (x[0] if isinstance(x, (list, tuple)) else x).device
 
@@ -813,13 +866,13 @@ class _UNetLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module: HipUNet, x, target, ignore_index, want_logits, kind, dice_weight, class_weight,
-                label_smoothing, focal_gamma, *params):
+                label_smoothing, focal_gamma, region_weight, region_alpha, region_beta, region_smooth, *params):
         ctx.module = module
         ctx.device = _device_of(x)
         logits = module._forward_raw(x, True, want_logits=want_logits)
         ctx.generation = module._generation
         loss = module._loss_raw(target, ignore_index, ctx.device, kind, dice_weight, class_weight, label_smoothing,
-                                focal_gamma)
+                                focal_gamma, region_weight, region_alpha, region_beta, region_smooth)
         if logits is None:
             logits = torch.empty(0, device=ctx.device)
         ctx.mark_non_differentiable(logits)
@@ -834,7 +887,7 @@ class _UNetLossFn(torch.autograd.Function):
         check(_lib.load().fu_scale_loss_grad(m._ctx, ptr(dl), m._stream(ctx.device)))
         saved, alias = _save_accumulated(m)
         m._backward_raw(None, ctx.device)
-        return (None,) * 10 + _return_param_grads(m, saved, alias)
+        return (None,) * 14 + _return_param_grads(m, saved, alias)
 
 
 class HipAdam(torch.optim.Adam):

@@ -17,6 +17,7 @@
  *                                                                            st_water_seg/models/water_seg_model.py:40,103-113
  *   fu_loss_ce_weighted         (new) nn.CrossEntropyLoss(weight, ignore_index, label_smoothing) on the same path
  *   fu_loss_ce_focal            (new) the same with focal modulation (1 - p[t])^gamma of every pixel's term
+ *   fu_loss_ce_region           (new) any of the three plus a soft Dice / Jaccard / Tversky region term over all classes
  *   fu_label_class_counts       (new) class frequencies of resident label rasters, for "balanced" weights
  *   fu_label_box_counts         (new) the label content of every box of a table, for content-aware tile sampling
  *   fu_backward[_block]         loss.backward() issued by Lightning's automatic optimisation
@@ -177,6 +178,38 @@ int fu_loss_ce_weighted(fu_ctx* ctx, const int64_t* target, int ignore_index, co
 int fu_loss_ce_focal(fu_ctx* ctx, const int64_t* target, int ignore_index, const float* class_weight_dev,
                      float focal_gamma, float* loss_out, int64_t* confusion_out, int64_t* n_valid_out,
                      float* weight_sum_out, fu_stream stream);
+/* Cross entropy plus a soft Dice / Jaccard / Tversky region term over all classes (added within ABI 5: purely additive, no
+ * version bump; the reference has no such loss -- the specification is tests/tools/region_ref.py).  With p = softmax(z),
+ * y_ik = [t_i == k], the sums over the valid pixels of fu_loss_ce, lambda = region->weight, s = region->smooth:
+ *   I_k = sum_i p_ik y_ik,  P_k = sum_i p_ik,  T_k = sum_i y_ik,
+ *   TI_k = (I_k + s) / (I_k + alpha (P_k - I_k) + beta (T_k - I_k) + s)                  (the soft Tversky index)
+ *   R = sum_{k in K} (1 - TI_k) / |K|,  K = the classes 0..n_classes-1 without ignore_index;   loss = CE + lambda R.
+ * alpha = beta = 0.5 is soft Dice (with s = 0.5 the (2I + 1) / (P + T + 1) of fu_loss_bce_dice, for every class), alpha =
+ * beta = 1 soft Jaccard; alpha weighs false positives, beta false negatives.  With Num_k and Den_k the fraction's parts,
+ *   d(lambda R)/dz_ij = lambda p_ij (g_ij - sum_k g_ik p_ik),   g_ik = A_k where t_i == k, else B_k,
+ *   A_k = -(alpha (P_k - I_k) + beta (T_k + s)) / (|K| Den_k^2),   B_k = alpha Num_k / (|K| Den_k^2)   (0 outside K).
+ * CE is one of the three forms above, unchanged, with its own normaliser: class_weight_dev == NULL, label_smoothing == 0
+ * and focal_gamma == 0 select fu_loss_ce's kernels; focal_gamma > 0 fu_loss_ce_focal's (rejected together with
+ * label_smoothing != 0); anything else fu_loss_ce_weighted's.  loss_out, the counts and the state rules are that form's;
+ * weight_sum_out is written by the weighted and focal forms only.  Class weights do not enter R.
+ * Zero rules: invalid pixels get a gradient of exactly 0; with no valid pixel R = 0 exactly (TI_k = s / s) and the gradient
+ * is 0.  The region term follows pixel validity, NOT the CE's summed weight D: a batch whose valid pixels all carry class
+ * weight 0 has CE 0 and still a live region term.
+ * region: HOST struct.  weight must be finite and >= 0, alpha and beta finite and >= 0 with alpha + beta > 0, smooth finite
+ * and > 0, n_classes >= 2 when weight > 0; a rejected call launches nothing.  region == NULL or weight == 0 launches nothing
+ * new: loss, counts, D and gradient are then fu_loss_ce's, fu_loss_ce_weighted's or fu_loss_ce_focal's bit for bit.
+ * region_out: optional device fp32 [1 + n_classes]: [0] = R (before lambda), [1 + k] = TI_k, 1.0 for the class equal to
+ * ignore_index; written only when weight > 0.
+ * Reductions: passes of their own after the CE's -- fp32 per-workgroup partials of I, P and T (at most 4096 / (3 KMAX) workgroups
+ * of 256 pixels per trip, KMAX = n_classes up to 4, else 8), a fixed fp64 tree, no floating-point atomics: the same bits on every run.  The coefficients A, B and
+ * lambda stay on the device for the gradient pass (training forwards only), which adds to the stored CE gradient.  In exact
+ * data-parallel mode the partials are summed over the ranks: I, P, T, R, region_out and the coefficients are the whole
+ * batch's on every rank. */
+typedef struct fu_region_loss { float weight, alpha, beta, smooth; } fu_region_loss;
+int fu_loss_ce_region(fu_ctx* ctx, const int64_t* target, int ignore_index, const float* class_weight_dev,
+                      float label_smoothing, float focal_gamma, const fu_region_loss* region, float* loss_out,
+                      int64_t* confusion_out, int64_t* n_valid_out, float* weight_sum_out, float* region_out,
+                      fu_stream stream);
 /* North-star extension (no reference counterpart; specification = oracle/unet_oracle.py:bce_dice_loss):
  * BCE on p = softmax(z)[1] vs [target == 1] + dice_weight * soft Dice, over target != ignore_index, fp32 wave-shuffle
  * reductions; stores its logits gradient for fu_backward like fu_loss_ce.  log(1 - p) is the logsumexp over the other classes

@@ -7,6 +7,9 @@ bench's loss shape: 16 tiles of 256 x 256, 3 classes, ignore_index 0.  Device ev
                 label smoothing 0.1;
   ce_focal      fu_loss_ce_focal      (k_ce_loss<3, true, true> + k_ce_finalize<true> + k_ce_grad<3, true, true>) with the
                 same class weights and gamma = 2, same shape, same run;
+  ce_region     fu_loss_ce_region     (the plain CE's three kernels + k_region_sums<3> + k_region_finalize<3> +
+                k_region_grad_add<3>): plain cross entropy + soft Dice (weight 1, alpha = beta = 0.5, s = 1), same shape,
+                same run;
   label_counts  fu_label_class_counts on 64 whole label rasters of 1024 x 1024 (64 MiB of uint8), one launch.
 
     python tools/loss_bench.py [--launches 200] [--warmup 20] [--parent_ce_us X]
@@ -14,7 +17,8 @@ bench's loss shape: 16 tiles of 256 x 256, 3 classes, ignore_index 0.  Device ev
 
 --parent_ce_us: `ce_us` of this tool's --ce_only run on the parent commit's build, same box; both per-call numbers are then
 stated against it (`ce_vs_parent`, `ce_weighted_vs_parent`).  Nothing is gated on the ratios or on `ce_focal_us`: the weighted
-and focal losses are capabilities; all three are instantiations of one kernel family (fu_loss.hip).  Prints one JSON line."""
+and focal losses and the region term are capabilities; the three CE forms are instantiations of one kernel family, the
+region term is two more passes over logits and target behind them (fu_loss.hip).  Prints one JSON line."""
 from __future__ import annotations
 
 import argparse
@@ -70,6 +74,8 @@ def main():
                                            args.launches, args.warmup)
         res["ce_focal_us"] = _median_us(lambda: net._loss_raw(target, IGNORE, dev, class_weight=w, focal_gamma=2.0),
                                         args.launches, args.warmup)
+        res["ce_region_us"] = _median_us(lambda: net._loss_raw(target, IGNORE, dev, region_weight=1.0), args.launches,
+                                         args.warmup)
         labels = [torch.randint(0, 3, (1024, 1024), device=dev, generator=g, dtype=torch.uint8) for _ in range(64)]
         entries = [(lab, (0, 0, 1024, 1024)) for lab in labels]
         counts = torch.zeros(N_CLASSES, dtype=torch.int64, device=dev)
