@@ -100,8 +100,6 @@ int fu_create(const fu_config* cfg, fu_ctx** out) {
     c->side = c->side_lo ? c->side_lo : c->side_def;        // side_mode starts at 1
     if (c->side) {
       bool ok = hipEventCreateWithFlags(&c->ev_gy, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&c->ev_wg[0], hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&c->ev_wg[1], hipEventDisableTiming) == hipSuccess &&
                 hipEventCreateWithFlags(&c->ev_blk, hipEventDisableTiming) == hipSuccess;
       if (!ok) {
         if (c->side_lo) (void)hipStreamDestroy(c->side_lo);
@@ -124,7 +122,7 @@ int fu_destroy(fu_ctx* c) {
   if (c->side) {
     if (c->side_lo) (void)hipStreamDestroy(c->side_lo);
     if (c->side_def) (void)hipStreamDestroy(c->side_def);
-    for (hipEvent_t e : {c->ev_gy, c->ev_wg[0], c->ev_wg[1], c->ev_blk}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {c->ev_gy, c->ev_blk}) if (e) (void)hipEventDestroy(e);
   }
   for (hipEvent_t e : c->ev_fence) if (e) (void)hipEventDestroy(e);   // (fu_backward_fence creates them without a side stream too)
   if (c->arena.base) (void)hipFree(c->arena.base);

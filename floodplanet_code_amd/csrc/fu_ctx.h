@@ -47,6 +47,8 @@ struct Conv {
   float *fold_scale = nullptr, *fold_bias = nullptr;   // eval pack (k_bn_fold_eval)
   void* y = nullptr;
   void* gy = nullptr;
+  float* db_part = nullptr;       // backward: this conv's OWN bias-gradient partials (written by its BN backward on the caller's
+                                  // stream, read by its slab reduce on a side stream; see backward_conv for the reuse order)
   const void* pool_g = nullptr;   // backward: dL/d(maxpool(this output)), to be folded into this conv's BN backward
   int bnb_tiles = 0;              // backward: > 0 = the producer of gy left this many rows of BN-backward sums in bnb_part
   HeadGrad head;                  // backward, last conv only: gy was not stored, the BN-backward apply recomputes it (dl != null)
@@ -164,18 +166,17 @@ struct fu_ctx {
   float* stats = nullptr;
   float* bnb_part = nullptr;
   int64_t bnb_cap = 0;         // floats
-  float* db_part = nullptr;
-  float* db_part2 = nullptr;      // second bias-gradient partial buffer (side-stream wgrad, alternating per conv)
+  float* db_part = nullptr;       // bias-gradient partials of the launches that run on the caller's stream behind a join: the
+                                  // fusion convs and the ConvTranspose path (every 3x3 conv of the plan has its own: Conv::db_part)
   hipStream_t side = nullptr;     // side stream for the weight-gradient chain (wgrad + slab reduce + transpose): one of ...
   hipStream_t side_lo = nullptr;  // ... lowest priority (mode 1: nothing but the final join waits for that chain; the main chain
                                   //     conv -> BN backward -> conv is the critical path and gets the CUs first: measured
                                   //     5.66 -> 5.64 ms per step and 0.338 -> 0.350 of peak for the conv launches in the step)
   hipStream_t side_def = nullptr; // ... the default priority (mode 2: an all-reduce bucket waits for its weight gradients)
-  hipEvent_t ev_gy = nullptr, ev_wg[2] = {nullptr, nullptr}, ev_blk = nullptr;
+  hipEvent_t ev_gy = nullptr, ev_blk = nullptr;
   hipEvent_t ev_fence[2] = {nullptr, nullptr};   // fu_backward_fence: compute stream / side stream (created on first use)
-  int wg_parity = 0;
   int side_mode = 1;              // fu_set_side_stream: 0 off, 1 on (blocks join), 2 on (the caller joins: fu_backward_join)
-  bool wg_pending[2] = {false, false};
+  bool side_open = false;         // weight-gradient chains were queued on the side stream since the last join_side
   double* dscratch = nullptr;
   fu::SyncDesc sync;           // exact data-parallel mode (fu_set_exact_sync); hook == nullptr: off
   float* slab = nullptr;

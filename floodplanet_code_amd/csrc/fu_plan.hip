@@ -323,7 +323,9 @@ int alloc_workspace(fu_ctx* c) {
       if (!(K.role == 0 && j == 0)) A.want(&v.wd, conv3x3_pack_elems(c->prec, v.cin_pad, v.cout) * es);
       max_stats = std::max<int64_t>(max_stats, (int64_t)conv3x3_num_stat_tiles(c->prec, B, H, W) * v.cout * 2);
       max_bnb = std::max<int64_t>(max_bnb, bn_bwd_partial_elems(v.cout, npix));
-      max_dbp = std::max<int64_t>(max_dbp, bn_bwd_partial_elems(v.cout, npix) / 2);
+      // one row of c_out bias-gradient partials per BN-backward workgroup, per conv (0.5 - 2 MB each, 19.5 MB over the 18
+      // convs of the base-64 net at B = 16, 256 x 256, against 4 MB for the two alternating buffers they replace): nothing inside one backward reuses such a buffer (backward_conv)
+      A.want(&v.db_part, bn_bwd_partial_elems(v.cout, npix) / 2 * sizeof(float));
       max_slab = std::max<int64_t>(max_slab, conv3x3_wgrad_slab_elems(c->prec, v.cin_pad, v.cout, B, H, W));
       max_c = std::max(max_c, v.cout);
     }
@@ -370,8 +372,7 @@ int alloc_workspace(fu_ctx* c) {
   A.want(&c->stats, max_stats * sizeof(float));
   A.want(&c->bnb_part, max_bnb * sizeof(float));
   c->bnb_cap = max_bnb;
-  A.want(&c->db_part, max_dbp * sizeof(float));
-  A.want(&c->db_part2, max_dbp * sizeof(float));
+  A.want(&c->db_part, max_dbp * sizeof(float));   // (the fusion convs and the ConvTranspose path only)
   A.want(&c->dscratch, reduce_scratch_elems(std::max(max_c, 64)) * sizeof(double));
   A.want(&c->slab, max_slab * sizeof(float));
   A.want(&c->ce_part, LOSS_PART_FLOATS * sizeof(float));

@@ -194,12 +194,22 @@ static int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
   // The weight-gradient chain of this conv (wgrad, slab reduce, transpose) depends only on gy and on saved activations
   // and nothing in the rest of backward depends on it: it runs on a side stream, concurrently with this conv's dgrad
   // and the next BN backward (its 8-wave workgroups spend more than half of every stage staging with the MFMA pipe
-  // idle, measured with s_memtime stamps; the dgrad workgroups that fit beside them on a CU use it).  db partials alternate
-  // between two buffers so that the main stream only has to wait for the wgrad of two convs ago.
+  // idle, measured with s_memtime stamps; the dgrad workgroups that fit beside them on a CU use it).
+  // The main stream never waits for that chain inside a backward.  The one buffer the two share, the bias-gradient partials
+  // (written by launch_bn_bwd here, read by the slab reduce there), is this conv's own (Conv::db_part), so nothing inside
+  // one backward reuses it.  Its next writer is the launch_bn_bwd of the SAME conv in the next backward, and every way there
+  // passes a join_side behind this conv's reduce, in the order of the stream that then writes:
+  //   fu_backward                    joins after its last block;
+  //   fu_backward_block, mode 1      joins at the end of this very block;
+  //   fu_backward_block, mode 2      the caller's fu_backward_join after the last block (the optimizer step needs it); a
+  //                                  caller that left it out is caught by the join at block 0 below (side_open);
+  //   mode 0                         there is no second stream;
+  //   a repeated backward of one loss is one of the above twice: the first one's join is in front of the second one's block 0;
+  //   fuse_backward                  joins first and then uses the context's buffer (c->db_part), like the ConvTranspose path,
+  //                                  which exists only without a side stream.
+  // (A backward on another stream than the one that joined is ordered by the caller, as for every other buffer of the context.)
   const bool side = c->side != nullptr && c->side_mode != 0;
-  const int par = c->wg_parity;
-  float* dbp = (side && par) ? c->db_part2 : c->db_part;
-  if (side && c->wg_pending[par]) FU_HIP_CHECK(hipStreamWaitEvent(s, c->ev_wg[par], 0));   // buffer free again
+  float* dbp = v.db_part;
   BnBwdArgs A;
   A.g = v.gy; A.y = v.y; A.C = v.cout; A.npix = npix;
   A.a = v.a; A.b = v.b; A.mean = v.mean; A.invstd = v.invstd;
@@ -220,15 +230,11 @@ static int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
     FU_HIP_CHECK(hipEventRecord(c->ev_gy, s));
     FU_HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_gy, 0));
     ws = c->side;
+    c->side_open = true;
   }
   in.opt.prof = prof_arm(c, FU_K_WGRAD, fl);
   FU_TRY(launch_conv3x3_wgrad(c->prec, in, v.gy, v.cout, c->slab, G(c, v.p_w), v.cin_real, dbp, ndb,
                               G(c, v.p_b), B, H, W, ws));
-  if (side) {
-    FU_HIP_CHECK(hipEventRecord(c->ev_wg[par], c->side));
-    c->wg_pending[par] = true;
-    c->wg_parity ^= 1;
-  }
   // data gradient
   ConvIn din{v.gy, v.cout, nullptr, nullptr, nullptr, 0};
   if (!(K.role == 0 && j == 0)) din.opt.prof = prof_arm(c, FU_K_CONV3X3, fl);
@@ -284,7 +290,7 @@ int join_side(fu_ctx* c, hipStream_t s) {
   if (c->side && c->side_mode != 0) {
     FU_HIP_CHECK(hipEventRecord(c->ev_blk, c->side));
     FU_HIP_CHECK(hipStreamWaitEvent(s, c->ev_blk, 0));
-    c->wg_pending[0] = c->wg_pending[1] = false;
+    c->side_open = false;
   }
   return 0;
 }
@@ -301,6 +307,9 @@ int backward_block_impl(fu_ctx* c, int block, const float* dlogits_ext, hipStrea
   const fu_config& f = c->cfg;
   const int B = c->last_batch;
   if (block == 0) {
+    // a mode-2 caller that started over without fu_backward_join: the chains of the last backward still read the
+    // per-conv bias-gradient partials that this one is about to write (backward_conv)
+    if (c->side_open) FU_TRY(join_side(c, s));
     if (dlogits_ext) {
       FU_TRY(launch_dlogits_from_nchw(dlogits_ext, c->dlogits, f.n_classes, B, f.height, f.width, s));
       c->have_up_scale = false;     // the caller's dlogits IS the whole upstream gradient

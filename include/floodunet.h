@@ -223,9 +223,12 @@ int fu_loss_bce_dice(fu_ctx* ctx, const int64_t* target, int ignore_index, float
  * (not accumulated) into the bound flat gradient buffer. */
 int fu_backward(fu_ctx* ctx, const float* dlogits, fu_stream stream);
 /* The weight-gradient chain of every conv (wgrad, slab reduce, transpose) runs on a context-owned side stream,
- * concurrently with the data-gradient / BatchNorm-backward chain on the caller's stream; fu_backward joins the two
- * before it returns its work to the caller's stream order, fu_backward_block at the end of every block (the block's
- * gradients are then final for a bucketed all-reduce).  mode 0 keeps everything on the caller's stream (the default
+ * concurrently with the data-gradient / BatchNorm-backward chain on the caller's stream, which does not wait for it
+ * anywhere inside a backward (every conv has its own bias-gradient partials; the side stream only ever waits for the
+ * caller's); fu_backward joins the two before it returns its work to the caller's stream order, fu_backward_block at
+ * the end of every block (the block's gradients are then final for a bucketed all-reduce).  After a join every launch
+ * queued on the side stream so far has finished in `stream` order, and only then may the next backward start: one that
+ * finds chains unjoined (mode 2 without fu_backward_join) joins them itself before its first launch.  mode 0 keeps everything on the caller's stream (the default
  * when the environment variable FU_NO_SIDE_STREAM is set at fu_create, for bilinear = 0 and in fp32 mode); mode 1
  * (default) as described; mode 2: fu_backward_block does not join -- the caller calls fu_backward_join(stream) before
  * it consumes gradients on `stream` (e.g. once per all-reduce bucket instead of once per block). */
