@@ -212,6 +212,7 @@ SIGNATURES = {
     "fu_op_conv3x3_dgrad": (_i, [_i, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _p]),
     "fu_op_conv3x3_wgrad": (_i, [_i, _p, _i, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
     "fu_op_conv3x3_dgrad_bnsums": (_i, [_i, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "fu_op_head_fwd": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "fu_op_head_bwd": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "fu_op_bn_bwd": (_i, [_i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "fu_op_maxpool2": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),

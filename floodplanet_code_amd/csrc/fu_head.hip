@@ -145,11 +145,11 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ dl, 
                                                   const float* __restrict__ w, int C, int ncls_rt, int npix, int LPP,
                                                   T* __restrict__ g, float* __restrict__ partials,
                                                   const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                  float* __restrict__ bnpart) {
+                                                  float* __restrict__ bnpart, int kpass) {
   constexpr int V = VecIO<T>::V;
   constexpr int KMAX = NC ? NC : HEAD_MAX_CLS;
   const int ncls = NC ? NC : ncls_rt;
-  extern __shared__ float sm[];  // [groups][ncls*C + ncls]
+  extern __shared__ float sm[];  // [groups][kpass*C + kpass]
   const int lane_in = threadIdx.x & (LPP - 1);
   const int grp = threadIdx.x / LPP;
   const int ppb = 256 / LPP;
@@ -222,19 +222,45 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ dl, 
       }
     }
   }
+  // The block's rows meet in LDS, [groups][ncls*C + ncls], wherever that fits the 64 KiB the launch may ask for: every
+  // specialised count, and the generic one except 8 classes in the 16-bit types, which take the classes kpass at a time in two
+  // passes.  An element's own sum -- the groups in order -- is the same either way.
+  if (NC != 0 || kpass >= ncls) {
 #pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    if (k < ncls) {
+    for (int k = 0; k < KMAX; ++k) {
+      if (k < ncls) {
 #pragma unroll
-      for (int j = 0; j < V; ++j) sm[grp * stride + k * C + lane_in * V + j] = dw[k][j];
-      if (lane_in == 0) sm[grp * stride + ncls * C + k] = db[k];
+        for (int j = 0; j < V; ++j) sm[grp * stride + k * C + lane_in * V + j] = dw[k][j];
+        if (lane_in == 0) sm[grp * stride + ncls * C + k] = db[k];
+      }
     }
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < stride; e += blockDim.x) {
-    float t = 0.f;
-    for (int gq = 0; gq < ppb; ++gq) t += sm[gq * stride + e];
-    partials[(size_t)blockIdx.x * stride + e] = t;
+    __syncthreads();
+    for (int e = threadIdx.x; e < stride; e += blockDim.x) {
+      float t = 0.f;
+      for (int gq = 0; gq < ppb; ++gq) t += sm[gq * stride + e];
+      partials[(size_t)blockIdx.x * stride + e] = t;
+    }
+  } else {
+    for (int k0 = 0; k0 < ncls; k0 += kpass) {
+      const int nk = min(kpass, ncls - k0);
+      const int pstride = nk * C + nk;   // sm: [groups][nk*C + nk], classes k0 .. k0 + nk - 1
+      if (k0 > 0) __syncthreads();
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        if (k >= k0 && k < k0 + nk) {
+#pragma unroll
+          for (int j = 0; j < V; ++j) sm[grp * pstride + (k - k0) * C + lane_in * V + j] = dw[k][j];
+          if (lane_in == 0) sm[grp * pstride + nk * C + (k - k0)] = db[k];
+        }
+      }
+      __syncthreads();
+      for (int e = threadIdx.x; e < pstride; e += blockDim.x) {
+        float t = 0.f;
+        for (int gq = 0; gq < ppb; ++gq) t += sm[gq * pstride + e];
+        const int dst = e < nk * C ? k0 * C + e : ncls * C + k0 + (e - nk * C);
+        partials[(size_t)blockIdx.x * stride + dst] = t;
+      }
+    }
   }
   if constexpr (BNB) {
     __syncthreads();                                   // sm: now [groups][C][2]
@@ -276,6 +302,7 @@ int64_t head_bwd_partial_elems(int C, int ncls) { return (int64_t)HB_BLOCKS * (n
 int launch_head_bwd(Prec p, const float* dlogits_nhwc, const void* y, const float* a, const float* b, const float* w,
                     int C, int ncls, int64_t npix, void* g, float* partials, float* dw, float* db, hipStream_t s,
                     const BnbFuse* fuse) {
+  FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "head_bwd: n_classes must be 1..%d", HEAD_MAX_CLS);
   FU_REQUIRE(npix < ((int64_t)1 << 31), "head_bwd: too many pixels");
   return dispatch_prec(p, [&](auto tag) {
     using T = decltype(tag);
@@ -289,23 +316,27 @@ int launch_head_bwd(Prec p, const float* dlogits_nhwc, const void* y, const floa
     // the BatchNorm-backward sums of g, if asked for (16-bit modes with BatchNorm coefficients: the bench path)
     const bool bnb = fuse && fuse->y == y && fuse->tiles_out && a != nullptr && p != PREC_F32 &&
                      (int64_t)nblk * C * 2 <= fuse->max_elems;
-    size_t sh = (size_t)ppb * stride * sizeof(float);
+    // classes per LDS pass of the block reduction: all of them where the rows fit in 64 KiB, half otherwise (16-bit, 8 classes:
+    // 65536 * (1 + 1/C) bytes in one pass at every width)
+    const int kpass = (size_t)ppb * stride * sizeof(float) <= 64 * 1024 ? ncls : ceil_div(ncls, 2);
+    size_t sh = (size_t)ppb * (kpass * C + kpass) * sizeof(float);
+    FU_REQUIRE(kpass == ncls || ncls > 4, "head_bwd: the specialised class counts reduce in one LDS pass");
     if (bnb && (size_t)ppb * C * 2 * sizeof(float) > sh) sh = (size_t)ppb * C * 2 * sizeof(float);
     FU_REQUIRE(sh <= 64 * 1024, "head_bwd: LDS request too large (%zu)", sh);
     const float* bmean = bnb ? fuse->mean : nullptr;
     const float* binv = bnb ? fuse->invstd : nullptr;
     float* bpart = bnb ? fuse->part : nullptr;
-#define FU_HEAD_BWD(NC)                                                                                         \
-  do {                                                                                                          \
-    if (bnb && fuse->skip_g)                                                                                    \
+#define FU_HEAD_BWD(NC)                                                                                                      \
+  do {                                                                                                                       \
+    if (bnb && fuse->skip_g)                                                                                                 \
       hipLaunchKernelGGL((k_head_bwd<T, NC, U, true, false>), dim3(nblk), dim3(256), sh, s, dlogits_nhwc, (const T*)y, a, b, \
-                         w, C, ncls, (int)npix, LPP, (T*)g, partials, bmean, binv, bpart);                      \
-    else if (bnb)                                                                                               \
-      hipLaunchKernelGGL((k_head_bwd<T, NC, U, true>), dim3(nblk), dim3(256), sh, s, dlogits_nhwc, (const T*)y, a, b, w, C, \
-                         ncls, (int)npix, LPP, (T*)g, partials, bmean, binv, bpart);                            \
-    else                                                                                                        \
-      hipLaunchKernelGGL((k_head_bwd<T, NC, U, false>), dim3(nblk), dim3(256), sh, s, dlogits_nhwc, (const T*)y, a, b, w, \
-                         C, ncls, (int)npix, LPP, (T*)g, partials, bmean, binv, bpart);                         \
+                         w, C, ncls, (int)npix, LPP, (T*)g, partials, bmean, binv, bpart, kpass);                            \
+    else if (bnb)                                                                                                            \
+      hipLaunchKernelGGL((k_head_bwd<T, NC, U, true>), dim3(nblk), dim3(256), sh, s, dlogits_nhwc, (const T*)y, a, b, w, C,  \
+                         ncls, (int)npix, LPP, (T*)g, partials, bmean, binv, bpart, kpass);                                  \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((k_head_bwd<T, NC, U, false>), dim3(nblk), dim3(256), sh, s, dlogits_nhwc, (const T*)y, a, b, w,    \
+                         C, ncls, (int)npix, LPP, (T*)g, partials, bmean, binv, bpart, kpass);                               \
   } while (0)
     switch (ncls) {
       case 1: FU_HEAD_BWD(1); break;

@@ -197,15 +197,53 @@ int fu_op_conv3x3_dgrad_bnsums(int precision, const void* dy, int Cout, const fl
   return FU_OK;
 }
 
+// ---- op-level test hooks of the 1x1 head: like the resampling hooks, every argument check precedes the first HIP call ------
+namespace {
+// precision, class count and the width rule of the head kernels (head_geometry, fu_head.hip): C = V * {1, 2, 4, 8, 16} lanes
+// per pixel, V = 4 (fp32) or 8 (16-bit) channels per 16-byte vector
+int head_args(const char* who, int precision, Prec* p, int C, int ncls) {
+  FU_TRY(prec_of(precision, p));
+  FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "%s: n_classes must be 1..%d (got %d)", who, HEAD_MAX_CLS, ncls);
+  const int V = 16 / fu_elem_size(precision);
+  const int lpp = C > 0 && C % V == 0 ? C / V : 0;
+  FU_REQUIRE(lpp >= 1 && lpp <= 16 && (lpp & (lpp - 1)) == 0, "%s: C must be %d, %d, %d, %d or %d in this precision (got %d)", who,
+             V, 2 * V, 4 * V, 8 * V, 16 * V, C);
+  return 0;
+}
+}  // namespace
+
+int fu_op_head_fwd(int precision, const void* y, const float* bn_a, const float* bn_b, const float* w, const float* bias,
+                   int C, int ncls, int B, int H, int W, float* logits_nhwc, float* logits_nchw, fu_stream stream) {
+  Prec p;
+  FU_TRY(head_args("fu_op_head_fwd", precision, &p, C, ncls));
+  FU_REQUIRE(y && w && bias && logits_nhwc, "fu_op_head_fwd: null argument");
+  FU_REQUIRE(!bn_a == !bn_b, "fu_op_head_fwd: bn_a and bn_b go together (both or neither)");
+  FU_REQUIRE(B > 0 && H > 0 && W > 0, "fu_op_head_fwd: empty shape (B=%d H=%d W=%d)", B, H, W);
+  FU_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), "fu_op_head_fwd: too many pixels per image");
+  FU_TRY(launch_head_fwd(p, y, bn_a, bn_b, w, bias, C, ncls, B, H, W, logits_nhwc, logits_nchw, (hipStream_t)stream));
+  FU_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  return FU_OK;
+}
+
 int fu_op_head_bwd(int precision, const float* dlogits_nhwc, const void* y, const float* bn_a, const float* bn_b,
                    const float* w, int C, int ncls, int64_t npix, void* g, float* dw, float* db, const float* mean,
                    const float* invstd, float* sum_gm, float* sum_gmx, fu_stream stream) {
-  Prec p; FU_TRY(prec_of(precision, &p));
+  Prec p;
+  FU_TRY(head_args("fu_op_head_bwd", precision, &p, C, ncls));
   FU_REQUIRE(dlogits_nhwc && y && w && g && dw && db, "fu_op_head_bwd: null argument");
+  FU_REQUIRE(!bn_a == !bn_b, "fu_op_head_bwd: bn_a and bn_b go together (both or neither)");
+  FU_REQUIRE(npix > 0 && npix < ((int64_t)1 << 31), "fu_op_head_bwd: npix must be 1..2^31-1 (got %lld)", (long long)npix);
+  const bool want = mean && invstd && sum_gm && sum_gmx;
+  FU_REQUIRE(want || !(mean || invstd || sum_gm || sum_gmx),
+             "fu_op_head_bwd: mean, invstd, sum_gm and sum_gmx go together (all or none)");
+  FU_REQUIRE(!want || bn_a, "fu_op_head_bwd: the BatchNorm-backward sums need bn_a and bn_b");
+  if (want && p == PREC_F32) {
+    set_error("fu_op_head_bwd: the head-backward kernel does not emit the sums in this precision");
+    return FU_ERR_UNSUPPORTED;
+  }
   hipStream_t s = (hipStream_t)stream;
   TmpBuf part, bpart;
   FU_TRY(part.get((size_t)head_bwd_partial_elems(C, ncls) * sizeof(float)));
-  const bool want = mean && invstd && sum_gm && sum_gmx;
   const int64_t cap = (int64_t)2048 * C * 2;
   int tiles = 0;
   BnbFuse f;
@@ -217,7 +255,7 @@ int fu_op_head_bwd(int precision, const float* dlogits_nhwc, const void* y, cons
                          want ? &f : nullptr));
   if (want) {
     if (tiles <= 0) {
-      set_error("fu_op_head_bwd: the head-backward kernel does not emit the sums in this precision");
+      set_error("fu_op_head_bwd: the head-backward kernel did not emit the sums");
       return FU_ERR_UNSUPPORTED;
     }
     FU_TRY(perturb_bnb((float*)bpart.p, tiles, C, s));

@@ -703,8 +703,17 @@ int fu_op_conv3x3_dgrad_bnsums(int precision, const void* dy, int Cout, const fl
                                const void* y, const float* bn_a, const float* bn_b, const float* mean,
                                const float* invstd, float* sum_gm, float* sum_gmx, int B, int H, int W,
                                fu_stream stream);
-/* head backward (OutConv 1x1): g = dlogits * W (element type of `precision`), dw [ncls][C], db [ncls]; with mean / invstd /
- * sum_gm / sum_gmx non-null also the BatchNorm-backward sums of g as above (16-bit precisions). */
+/* The two head operators (OutConv 1x1) check every argument before their first HIP call -- precision, null pointers,
+ * ncls in 1..8, C one of V, 2V, 4V, 8V, 16V with V = 4 (fp32) or 8 (16-bit) channels per vector, empty shapes -- and
+ * synchronise the stream before they return.
+ * head forward: logits[p][k] = bias[k] + sum_c z[p][c] * w[k][c] with z = relu(bn_a * y + bn_b), or z = y when bn_a and bn_b
+ * are both null; y [B,H,W,C] of `precision`, w fp32 [ncls][C], logits fp32 NHWC [B,H,W,ncls] and, unless logits_nchw is
+ * null, the same values as NCHW [B,ncls,H,W]. */
+int fu_op_head_fwd(int precision, const void* y, const float* bn_a, const float* bn_b, const float* w, const float* bias,
+                   int C, int ncls, int B, int H, int W, float* logits_nhwc, float* logits_nchw, fu_stream stream);
+/* head backward: g = dlogits * W (element type of `precision`), dw [ncls][C], db [ncls]; z as in the forward (bn_a / bn_b
+ * both null: z = y).  With mean / invstd / sum_gm / sum_gmx non-null (all four or none; needs bn_a / bn_b) also the
+ * BatchNorm-backward sums of g as above: 16-bit precisions only, FU_ERR_UNSUPPORTED in fp32. */
 int fu_op_head_bwd(int precision, const float* dlogits_nhwc, const void* y, const float* bn_a, const float* bn_b,
                    const float* w, int C, int ncls, int64_t npix, void* g, float* dw, float* db, const float* mean,
                    const float* invstd, float* sum_gm, float* sum_gmx, fu_stream stream);
