@@ -22,6 +22,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .loss_options import LossOptions
+
 # rehearsal knob: drive the block-wise backward (the multi-GPU code path) in a single process
 _FORCE_BLOCKS = os.environ.get("FU_DP_FORCE_BLOCKS") == "1"
 _DIAG_MODE = None      # tools/dp_diag.py: override of the side-stream mode
@@ -140,13 +142,11 @@ class DataParallelTrainer:
         if ema_decay is not None:
             net.enable_ema(ema_decay, ema_warmup)
         self.net, self.lr, self.world_size, self.rank = net, lr, world_size, rank
-        self.class_weight, self.label_smoothing = class_weight, float(label_smoothing)
-        from .unet import check_focal_gamma, check_region_loss
-        self.focal_gamma = check_focal_gamma(focal_gamma, label_smoothing)
-        self.region_weight, self.region_alpha, self.region_beta, self.region_smooth = check_region_loss(
-            region_weight, region_alpha, region_beta, region_smooth)
-        if self.region_weight > 0.0 and net.n_classes < 2:
-            raise ValueError("a region term (region_weight > 0) needs n_classes >= 2")
+        # checked on the host, once; every step hands this one object to HipUNet._loss_raw
+        self.loss_options = LossOptions.make(net.n_classes, class_weight=class_weight, label_smoothing=label_smoothing,
+                                             focal_gamma=focal_gamma, region_weight=region_weight,
+                                             region_alpha=region_alpha, region_beta=region_beta,
+                                             region_smooth=region_smooth)
         self.betas, self.eps, self.group, self.cap_bytes = betas, eps, group, cap_bytes
         self.exact = bool(exact) and world_size > 1
         if self.exact:
@@ -167,9 +167,10 @@ class DataParallelTrainer:
         self._launch_stream = None     # the stream the bucket all-reduces are launched from (mode 2, fu_backward_fence)
         self._synced = False
 
-    def _region_kwargs(self) -> dict:
-        return dict(region_weight=self.region_weight, region_alpha=self.region_alpha, region_beta=self.region_beta,
-                    region_smooth=self.region_smooth)
+    def __getattr__(self, name):             # class_weight, label_smoothing, focal_gamma, region_*: read from loss_options
+        if name in LossOptions.__dataclass_fields__:
+            return getattr(self.loss_options, name)
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     def _side_mode(self) -> int:
         if _DIAG_MODE is not None:
@@ -240,9 +241,7 @@ class DataParallelTrainer:
         g = torch.cuda.CUDAGraph(keep_graph=True) if dot else torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             net._forward_raw(self._gx, True, want_logits=False)
-            self._gloss = net._loss_raw(self._gt, self._g_ignore, dev, class_weight=self.class_weight,
-                                        label_smoothing=self.label_smoothing, focal_gamma=self.focal_gamma,
-                                        **self._region_kwargs())
+            self._gloss = net._loss_raw(self._gt, self._g_ignore, dev, options=self.loss_options)
             net._backward_raw(None, dev)
             if self._g_ema:
                 _lib.check(lib.fu_adam_ema_step_dev(net._ctx, self._gscal.data_ptr(), net._stream(dev)))
@@ -287,8 +286,7 @@ class DataParallelTrainer:
         if self.world_size > 1 and not self._synced:
             self._sync_initial_state(x.device)
         net._forward_raw(x, True, want_logits=False)
-        loss = net._loss_raw(target, ignore_index, x.device, class_weight=self.class_weight,
-                             label_smoothing=self.label_smoothing, focal_gamma=self.focal_gamma, **self._region_kwargs())
+        loss = net._loss_raw(target, ignore_index, x.device, options=self.loss_options)
         if self.world_size <= 1 and not _FORCE_BLOCKS:
             net._backward_raw(None, x.device)
         else:

@@ -360,8 +360,7 @@ def main(argv: Optional[List[str]] = None) -> dict:
             class_counts = train.class_counts().cpu().numpy()
             cfg = cfg_from_args(args, balanced_class_weights(class_counts, c["ignore_index"]).tolist())
             c.update(cfg)
-            model.set_loss_options(cfg["model"]["model_kwargs"]["class_weights"], model.label_smoothing, model.focal_gamma,
-                                   model.region_weight, model.region_alpha, model.region_beta, model.region_smooth)
+            model.replace_loss_options(class_weight=cfg["model"]["model_kwargs"]["class_weights"])
     else:
         common = dict(seed=c["seed_num"], ignore_index=c["ignore_index"], num_workers=args.n_workers,
                       device_assembly=True, device_resize=True)

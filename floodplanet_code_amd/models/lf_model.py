@@ -19,15 +19,12 @@ _BATCH_KEY = {"ms_image": "image"}          # lf_model.py:56: encoders['ms_image
 class LateFusionModel(WaterSegmentationModel):
 
     def __init__(self, in_channels, n_classes, lr, log_image_iter=50, to_rgb_fcn=None, ignore_index=None,
-                 optimizer_name='adam', feat_fusion='concat_conv', precision='fp32', base_channels=64, class_weights=None,
-                 label_smoothing=0.0, ema_decay=None, ema_warmup=True, focal_gamma=0.0, region_weight=0.0, region_alpha=0.5,
-                 region_beta=0.5, region_smooth=1.0):
+                 optimizer_name='adam', feat_fusion='concat_conv', **extensions):
+        """extensions: WaterSegmentationModel's keywords beyond the reference's (precision, base_channels, the loss options,
+        the weight EMA), with its defaults."""
         self.feat_fusion = feat_fusion
         super().__init__(in_channels, n_classes, lr, log_image_iter=log_image_iter, to_rgb_fcn=to_rgb_fcn,
-                         ignore_index=ignore_index, optimizer_name=optimizer_name, precision=precision,
-                         base_channels=base_channels, class_weights=class_weights, label_smoothing=label_smoothing,
-                         ema_decay=ema_decay, ema_warmup=ema_warmup, focal_gamma=focal_gamma, region_weight=region_weight,
-                         region_alpha=region_alpha, region_beta=region_beta, region_smooth=region_smooth)
+                         ignore_index=ignore_index, optimizer_name=optimizer_name, **extensions)
 
     def _build_model(self):
         if self.feat_fusion != 'concat_conv':

@@ -32,7 +32,8 @@ import torch.optim as optim
 from ..lightning_compat import LightningModule
 from ..metrics import SegmentationMetrics
 from ..ema import check_decay
-from ..unet import HipAdam, HipUNet, check_class_weight, check_focal_gamma, check_label_smoothing, check_region_loss
+from ..loss_options import LossOptions
+from ..unet import HipAdam, HipUNet, check_class_weight, check_label_smoothing
 
 
 class WaterSegmentationModel(LightningModule):
@@ -42,18 +43,18 @@ class WaterSegmentationModel(LightningModule):
                  ema_decay=None, ema_warmup=True, focal_gamma=0.0, region_weight=0.0, region_alpha=0.5, region_beta=0.5,
                  region_smooth=1.0):
         super().__init__()
-        # checked on the host before anything touches the GPU; kept as plain Python numbers (checkpoint hyper_parameters)
-        self.class_weights = (None if class_weights is None
-                              else tuple(float(v) for v in check_class_weight(class_weights, n_classes)))
-        self.label_smoothing = check_label_smoothing(label_smoothing)
-        self.focal_gamma = check_focal_gamma(focal_gamma, self.label_smoothing)
-        self._set_region_options(n_classes, region_weight, region_alpha, region_beta, region_smooth)
+        self.n_classes = n_classes
+        self.ignore_index = ignore_index
+        if self.ignore_index == -1:                      # water_seg_model.py:35-36
+            self.ignore_index = self.n_classes - 1
+        self._loss_ignore = -100 if self.ignore_index is None else int(self.ignore_index)
+        self._set_loss_options(class_weight=class_weights, label_smoothing=label_smoothing, focal_gamma=focal_gamma,
+                               region_weight=region_weight, region_alpha=region_alpha, region_beta=region_beta,
+                               region_smooth=region_smooth)
         self.ema_decay = None if ema_decay is None else check_decay(ema_decay)
         self.ema_warmup = bool(ema_warmup)
         self.lr = lr
-        self.n_classes = n_classes
         self.in_channels = in_channels
-        self.ignore_index = ignore_index
         self.optimizer_name = optimizer_name
         self.precision = precision
         self.base_channels = base_channels
@@ -62,39 +63,43 @@ class WaterSegmentationModel(LightningModule):
         if self.ema_decay is not None:                   # host bookkeeping only: the buffers are made on the module's device
             self.model.enable_ema(self.ema_decay, self.ema_warmup)
 
-        if self.ignore_index == -1:                      # water_seg_model.py:35-36
-            self.ignore_index = self.n_classes - 1
         self.tracked_metrics = self._get_tracked_metrics()
-
-        self._loss_ignore = -100 if self.ignore_index is None else int(self.ignore_index)
-        self._make_loss_func()
+        self._modules["loss_func"] = self._modules.pop("loss_func")     # made first, with the checks; listed last, as ever
 
         self.to_rgb_fcn = to_rgb_fcn
         self.log_image_iter = log_image_iter
 
-    def _set_region_options(self, n_classes, weight, alpha, beta, smooth):
-        self.region_weight, self.region_alpha, self.region_beta, self.region_smooth = check_region_loss(weight, alpha, beta,
-                                                                                                        smooth)
-        if self.region_weight > 0.0 and n_classes < 2:
-            raise ValueError("a region term (region_weight > 0) needs n_classes >= 2")
+    def _set_loss_options(self, class_weight=None, label_smoothing=0.0, **options):
+        """The one place the model's loss options are set: checked on the host before anything touches the GPU, the class
+        weights kept as a tuple of plain Python numbers (checkpoint hyper_parameters), loss_func remade to match."""
+        if class_weight is not None:
+            class_weight = tuple(float(v) for v in check_class_weight(class_weight, self.n_classes))
+        self.loss_options = LossOptions.make(self.n_classes, class_weight=class_weight,
+                                             label_smoothing=check_label_smoothing(label_smoothing), **options)
+        self.loss_func = nn.CrossEntropyLoss(                                  # kept for API parity (:40)
+            weight=None if class_weight is None else torch.tensor(class_weight, dtype=torch.float32),
+            ignore_index=self._loss_ignore, label_smoothing=self.loss_options.label_smoothing)
+        return self
 
     def set_loss_options(self, class_weights=None, label_smoothing=0.0, focal_gamma=0.0, region_weight=0.0,
                          region_alpha=0.5, region_beta=0.5, region_smooth=1.0):
-        """Replace the loss's class weights / label smoothing / focal exponent / region term after construction (weights that
-        are counted from data the model's own device context serves, fit's `--class_weights balanced`).  Same checks as the
-        constructor."""
-        self.class_weights = (None if class_weights is None
-                              else tuple(float(v) for v in check_class_weight(class_weights, self.n_classes)))
-        self.label_smoothing = check_label_smoothing(label_smoothing)
-        self.focal_gamma = check_focal_gamma(focal_gamma, self.label_smoothing)
-        self._set_region_options(self.n_classes, region_weight, region_alpha, region_beta, region_smooth)
-        self._make_loss_func()
-        return self
+        """Replace the loss's class weights / label smoothing / focal exponent / region term after construction.  Same
+        checks as the constructor."""
+        return self._set_loss_options(class_weights, label_smoothing, focal_gamma=focal_gamma, region_weight=region_weight,
+                                      region_alpha=region_alpha, region_beta=region_beta, region_smooth=region_smooth)
 
-    def _make_loss_func(self):
-        self.loss_func = nn.CrossEntropyLoss(                                  # kept for API parity (:40)
-            weight=None if self.class_weights is None else torch.tensor(self.class_weights, dtype=torch.float32),
-            ignore_index=self._loss_ignore, label_smoothing=self.label_smoothing)
+    def replace_loss_options(self, **changes):
+        """set_loss_options with every option kept but those named, by LossOptions' field names (weights that are counted
+        from data the model's own device context serves, fit's `--class_weights balanced`)."""
+        return self._set_loss_options(**{**self.loss_options.as_kwargs(), **changes})
+
+    class_weights = property(lambda self: self.loss_options.class_weight)
+    label_smoothing = property(lambda self: self.loss_options.label_smoothing)
+    focal_gamma = property(lambda self: self.loss_options.focal_gamma)
+    region_weight = property(lambda self: self.loss_options.region_weight)
+    region_alpha = property(lambda self: self.loss_options.region_alpha)
+    region_beta = property(lambda self: self.loss_options.region_beta)
+    region_smooth = property(lambda self: self.loss_options.region_smooth)
 
     # ------------------------------------------------------------------ construction
     def _get_tracked_metrics(self, average_mode='micro'):
@@ -164,10 +169,7 @@ class WaterSegmentationModel(LightningModule):
         (`if False:`, water_seg_model.py:116), so the training path never does; the counts stay on the device."""
         images = self._gather_sources(batch)
         out = self.model.loss(images, batch['target'], self._loss_ignore, return_logits=want_logits,
-                              class_weight=self.class_weights, label_smoothing=self.label_smoothing,
-                              focal_gamma=self.focal_gamma, region_weight=self.region_weight,
-                              region_alpha=self.region_alpha, region_beta=self.region_beta,
-                              region_smooth=self.region_smooth)
+                              **self.loss_options.as_kwargs())
         loss, output = out if want_logits else (out, None)
         counts = self.model.pop_confusion()
         return loss, output, counts

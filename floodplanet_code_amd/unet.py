@@ -22,6 +22,7 @@ from torch.nn import init
 from . import _lib
 from ._lib import FuConfig, check, ptr
 from .ema import check_decay, ema_weight
+from .loss_options import LossOptions, check_focal_gamma, check_label_smoothing, check_region_loss  # noqa: F401 (re-exported)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -152,8 +153,14 @@ class HipUNet(nn.Module):
         self._ctx = None
         self._ctx_key = None
         self._eval_dirty = True
+        self._last_batch = 0                          # samples of the last forward; (B, codes) after forward_views
+        self._views = None
+        # what the fused loss leaves on the device: confusion counts, (n_valid, weight_sum) of the weighted forms, the region
+        # report; and the class weights' device copy (_class_weight_dev).  Each is made at the first call that needs it.
         self._confusion: Optional[torch.Tensor] = None
+        self._wce_sums = self._region_terms = self._cw_cache = None
         self._exact = None
+        self._xbuf = self._sync_cb = None             # exact sync: the exchange buffer and the live callback object
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._mark_dirty())
 
     def _build_tree(self):
@@ -401,7 +408,7 @@ class HipUNet(nn.Module):
 
     def _install_exact_sync(self, device):
         lib = _lib.load()
-        exact = getattr(self, "_exact", None)
+        exact = self._exact
         if exact is None:
             if self._ctx is not None:
                 check(lib.fu_set_exact_sync(self._ctx, _lib.SYNC_HOOK(0), None, 1, None, 0))   # null hook: off
@@ -492,7 +499,7 @@ class HipUNet(nn.Module):
         if class_weight is None:
             return None
         key = (id(class_weight), getattr(class_weight, "_version", None), torch.device(device))
-        cached = getattr(self, "_cw_cache", None)
+        cached = self._cw_cache
         if cached is not None and cached[0] == key:
             return cached[2]
         w = check_class_weight(class_weight, self.n_classes)
@@ -504,77 +511,65 @@ class HipUNet(nn.Module):
         """(n_valid int64 scalar, weight_sum fp32 scalar) on the device, written by the last fu_loss_ce_weighted or
         fu_loss_ce_focal call: the valid pixels and D = the sum of their targets' class weights (the loss's denominator).
         None before such a call."""
-        return getattr(self, "_wce_sums", None)
+        return self._wce_sums
 
     def last_region_terms(self):
         """fp32 [1 + n_classes] on the device, written by the last fu_loss_ce_region call with a region weight > 0: [0] = R,
         the mean of 1 - TI_k over the classes but ignore_index (before the weight), [1 + k] = the soft Tversky index TI_k
         (1.0 for the class equal to ignore_index).  None before such a call."""
-        return getattr(self, "_region_terms", None)
+        return self._region_terms
 
     def _region_terms_dev(self, device) -> torch.Tensor:
-        terms = getattr(self, "_region_terms", None)
+        terms = self._region_terms
         if terms is None or terms.device != torch.device(device):
             terms = self._region_terms = torch.zeros(1 + self.n_classes, dtype=torch.float32, device=device)
         return terms
 
-    def _loss_raw(self, target: torch.Tensor, ignore_index: int, device, kind: str = "ce",
-                  dice_weight: float = 1.0, class_weight=None, label_smoothing: float = 0.0,
-                  focal_gamma: float = 0.0, region_weight: float = 0.0, region_alpha: float = 0.5,
-                  region_beta: float = 0.5, region_smooth: float = 1.0) -> torch.Tensor:
-        gamma = check_focal_gamma(focal_gamma, label_smoothing)      # on the host, before the library is loaded
-        if gamma != 0.0 and kind != "ce":
-            raise ValueError(f"focal_gamma belongs to kind='ce'; kind={kind!r} does not take it")
-        region = check_region_loss(region_weight, region_alpha, region_beta, region_smooth)
-        if region[0] != 0.0 and kind != "ce":
-            raise ValueError(f"region_weight belongs to kind='ce'; kind={kind!r} does not take it")
-        if region[0] != 0.0 and self.n_classes < 2:
-            raise ValueError("a region term needs n_classes >= 2")
-        lib = _lib.load()
-        target = target.contiguous().long()
-        loss = torch.empty((), dtype=torch.float32, device=device)
-        weighted = class_weight is not None or float(label_smoothing) != 0.0
-        if weighted and kind != "ce":
-            raise ValueError(f"class_weight / label_smoothing belong to kind='ce'; kind={kind!r} takes neither")
-        if kind == "bce_dice":
-            check(lib.fu_loss_bce_dice(self._ctx, ptr(target), int(ignore_index), float(dice_weight), ptr(loss),
-                                       self._stream(device)))
-            return loss
-        if kind != "ce":
-            raise ValueError(f"unknown loss kind {kind!r}")
-        if self._confusion is None or self._confusion.device != device:
-            self._confusion = torch.zeros(self.n_classes * self.n_classes, dtype=torch.int64, device=device)
-        if region[0] > 0.0:                   # CE (whichever form the other options select) + the region term, one call
-            eps = check_label_smoothing(label_smoothing)
-            cw = self._class_weight_dev(class_weight, device)
-            terms = self._region_terms_dev(device)
-            n_valid = wsum = None
-            if weighted or gamma != 0.0:
-                sums = getattr(self, "_wce_sums", None)
-                if sums is None or sums[0].device != torch.device(device):
-                    sums = self._wce_sums = (torch.zeros((), dtype=torch.int64, device=device),
-                                             torch.zeros((), dtype=torch.float32, device=device))
-                n_valid, wsum = sums
-            check(lib.fu_loss_ce_region(self._ctx, ptr(target), int(ignore_index), ptr(cw), eps, gamma,
-                                        _lib.FuRegionLoss(*region), ptr(loss), ptr(self._confusion), ptr(n_valid),
-                                        ptr(wsum), ptr(terms), self._stream(device)))
-            return loss
-        if not weighted and gamma == 0.0:     # the reference's loss: the same call, the same kernels as ever
-            check(lib.fu_loss_ce(self._ctx, ptr(target), int(ignore_index), ptr(loss), ptr(self._confusion), None,
-                                 self._stream(device)))
-            return loss
-        eps = check_label_smoothing(label_smoothing)
-        cw = self._class_weight_dev(class_weight, device)
-        sums = getattr(self, "_wce_sums", None)
+    def _weighted_sums_dev(self, device) -> Tuple[torch.Tensor, torch.Tensor]:
+        sums = self._wce_sums
         if sums is None or sums[0].device != torch.device(device):
             sums = self._wce_sums = (torch.zeros((), dtype=torch.int64, device=device),
                                      torch.zeros((), dtype=torch.float32, device=device))
-        if gamma != 0.0:                 # focal modulation of the (weighted) cross entropy; gamma == 0 stays on its old route
-            check(lib.fu_loss_ce_focal(self._ctx, ptr(target), int(ignore_index), ptr(cw), gamma, ptr(loss),
-                                       ptr(self._confusion), ptr(sums[0]), ptr(sums[1]), self._stream(device)))
-            return loss
-        check(lib.fu_loss_ce_weighted(self._ctx, ptr(target), int(ignore_index), ptr(cw), eps, ptr(loss),
-                                      ptr(self._confusion), ptr(sums[0]), ptr(sums[1]), self._stream(device)))
+        return sums
+
+    def _loss_raw(self, target: torch.Tensor, ignore_index: int, device, kind: str = "ce", dice_weight: float = 1.0,
+                  options: Optional[LossOptions] = None, **loss_kwargs) -> torch.Tensor:
+        """The fused loss of the last forward.  options: a LossOptions (what loss / train_step / the trainer pass), or its
+        fields as keywords, checked here.  Everything is validated on the host before the library is loaded."""
+        if options is None:
+            options = LossOptions.make(self.n_classes, kind, **loss_kwargs)
+        elif loss_kwargs:
+            raise TypeError(f"_loss_raw(): options together with {sorted(loss_kwargs)}; give one or the other")
+        if kind not in ("ce", "bce_dice"):
+            raise ValueError(f"unknown loss kind {kind!r}")
+        gamma = options.focal_gamma
+        region = options.region_weight > 0.0
+        weighted = options.class_weight is not None or options.label_smoothing != 0.0
+        sums = weighted or gamma != 0.0      # the forms that report (n_valid, weight_sum), alone or under a region term
+        eps = check_label_smoothing(options.label_smoothing) if weighted or region else 0.0
+        lib = _lib.load()
+        target = target.contiguous().long()
+        loss = torch.empty((), dtype=torch.float32, device=device)
+        if kind == "bce_dice":
+            fn, args = lib.fu_loss_bce_dice, (float(dice_weight), ptr(loss))
+        else:
+            if self._confusion is None or self._confusion.device != device:
+                self._confusion = torch.zeros(self.n_classes * self.n_classes, dtype=torch.int64, device=device)
+            args = (ptr(loss), ptr(self._confusion))
+            if not (sums or region):      # the reference's loss: the same call, the same kernels as ever
+                fn, args = lib.fu_loss_ce, args + (None,)
+            else:
+                cw = ptr(self._class_weight_dev(options.class_weight, device))
+                n_valid, wsum = self._weighted_sums_dev(device) if sums else (None, None)
+                args += (ptr(n_valid), ptr(wsum))
+                if region:                # CE (whichever form the other options select) + the region term, one call
+                    fn, args = lib.fu_loss_ce_region, (cw, eps, gamma, _lib.FuRegionLoss(*options.region)) + args + (
+                        ptr(self._region_terms_dev(device)),)
+                elif gamma != 0.0:        # focal modulation of the (weighted) cross entropy
+                    fn, args = lib.fu_loss_ce_focal, (cw, gamma) + args
+                else:
+                    fn, args = lib.fu_loss_ce_weighted, (cw, eps) + args
+        check(fn(self._ctx, ptr(target), int(ignore_index), *args, self._stream(device)))
         return loss
 
     def _backward_raw(self, dlogits: Optional[torch.Tensor], device):
@@ -593,7 +588,7 @@ class HipUNet(nn.Module):
         """Per-sample confusion counts of the last forward's resident logits: int64 [B, k, k] on the device,
         M[b, t, p] = #pixels of sample b with target t and argmax p (fu_eval_confusion; ignored / out-of-range targets
         dropped as in the fused loss).  No loss, no logits gradient, no host sync."""
-        B = getattr(self, "_last_batch", 0)
+        B = self._last_batch
         if self._ctx is None or B == 0:
             raise RuntimeError("eval_confusion: no forward pass yet")
         k, H, W = self.n_classes, self._ctx_key[1], self._ctx_key[2]
@@ -634,7 +629,7 @@ class HipUNet(nn.Module):
         """After forward_views: -> (probs | None, counts | None).  probs: fp32 [B, H, W, k], the mean in view order of
         the inverse views of each view's softmax.  counts (with target int64 [B, H, W]): int64 [B, k, k] confusion counts
         of argmax probs, ignored / out-of-range targets dropped as in eval_confusion.  One launch (fu_merge_views)."""
-        views = getattr(self, "_views", None)
+        views = self._views
         if self._ctx is None or views is None:
             raise RuntimeError("merge_views: the last forward was not forward_views")
         if not want_probs and target is None:
@@ -678,16 +673,16 @@ class HipUNet(nn.Module):
         Dice, alpha = beta = 1 soft Jaccard; class weights do not enter it (last_region_terms() holds R and TI_k).  With all
         of them at their defaults the reference's loss runs exactly as before.
         The returned loss is differentiable: ``loss.backward()`` runs the HIP backward."""
+        options = LossOptions.make(self.n_classes, kind, class_weight=class_weight, label_smoothing=label_smoothing,
+                                   focal_gamma=focal_gamma, region_weight=region_weight, region_alpha=region_alpha,
+                                   region_beta=region_beta, region_smooth=region_smooth)
         if self.training and torch.is_grad_enabled():
             params = [p for _, p, _, _ in self._table]
-            out = _UNetLossFn.apply(self, x, target, int(ignore_index), bool(return_logits), kind,
-                                    float(dice_weight), class_weight, float(label_smoothing), float(focal_gamma),
-                                    float(region_weight), float(region_alpha), float(region_beta), float(region_smooth),
-                                    *params)
+            out = _UNetLossFn.apply(self, x, target, int(ignore_index), bool(return_logits), kind, float(dice_weight),
+                                    options, *params)
             return out if return_logits else out[0]
         logits = self._forward_raw(x, self.training, want_logits=return_logits)
-        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, class_weight, label_smoothing,
-                              focal_gamma, region_weight, region_alpha, region_beta, region_smooth)
+        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, options)
         return (loss, logits) if return_logits else loss
 
     def train_step(self, x: torch.Tensor, target: torch.Tensor, ignore_index: int, kind: str = "ce",
@@ -695,9 +690,11 @@ class HipUNet(nn.Module):
                    focal_gamma: float = 0.0, region_weight: float = 0.0, region_alpha: float = 0.5,
                    region_beta: float = 0.5, region_smooth: float = 1.0) -> torch.Tensor:
         """forward + loss + backward without autograd; gradients land in the flat buffer / p.grad."""
+        options = LossOptions.make(self.n_classes, kind, class_weight=class_weight, label_smoothing=label_smoothing,
+                                   focal_gamma=focal_gamma, region_weight=region_weight, region_alpha=region_alpha,
+                                   region_beta=region_beta, region_smooth=region_smooth)
         self._forward_raw(x, True, want_logits=False)
-        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, class_weight, label_smoothing,
-                              focal_gamma, region_weight, region_alpha, region_beta, region_smooth)
+        loss = self._loss_raw(target, ignore_index, _device_of(x), kind, dice_weight, options)
         self._backward_raw(None, _device_of(x))
         self.attach_grads()
         return loss
@@ -760,40 +757,6 @@ def check_class_weight(class_weight, n_classes: int):
     return w32
 
 
-def check_label_smoothing(label_smoothing) -> float:
-    eps = float(label_smoothing)
-    if not 0.0 <= eps < 1.0:          # (NaN fails both comparisons)
-        raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing!r}")
-    return eps
-
-
-def check_focal_gamma(focal_gamma, label_smoothing=0.0) -> float:
-    """The focal exponent as a float.  ValueError unless it is finite and >= 0, and 0 wherever label smoothing is set: a
-    smoothed focal loss has no agreed definition."""
-    import math
-    gamma = float(focal_gamma)
-    if not (math.isfinite(gamma) and gamma >= 0.0):
-        raise ValueError(f"focal_gamma must be finite and >= 0, got {focal_gamma!r}")
-    if gamma != 0.0 and float(label_smoothing) != 0.0:
-        raise ValueError(f"focal_gamma={gamma} together with label_smoothing={label_smoothing!r}: a smoothed focal loss "
-                         "is not defined here, set one of them to 0")
-    return gamma
-
-
-def check_region_loss(weight=0.0, alpha=0.5, beta=0.5, smooth=1.0):
-    """The region term's options as floats (weight, alpha, beta, smooth).  ValueError unless weight is finite and >= 0, alpha
-    and beta are finite and >= 0 with alpha + beta > 0, and smooth is finite and > 0 (the rules of fu_loss_ce_region)."""
-    import math
-    w, a, b, s = float(weight), float(alpha), float(beta), float(smooth)
-    if not (math.isfinite(w) and w >= 0.0):
-        raise ValueError(f"region_weight must be finite and >= 0, got {weight!r}")
-    if not (math.isfinite(a) and math.isfinite(b) and a >= 0.0 and b >= 0.0 and a + b > 0.0):
-        raise ValueError(f"region_alpha, region_beta must be finite and >= 0 with alpha + beta > 0, got {alpha!r}, {beta!r}")
-    if not (math.isfinite(s) and s > 0.0):
-        raise ValueError(f"region_smooth must be finite and > 0, got {smooth!r}")
-    return w, a, b, s
-
-
 def _device_of(x):
     return (x[0] if isinstance(x, (list, tuple)) else x).device
 
@@ -815,6 +778,11 @@ def _save_accumulated(m: "HipUNet"):
     views = m.grad_views()
     alias = [p.grad is not None and p.grad.data_ptr() == v.data_ptr() for (_, p, _, _), v in zip(m._table, views)]
     return (m._flat_grad.clone() if any(alias) else None), alias
+
+
+def _no_grads(forward) -> tuple:
+    """One None per argument of an autograd Function's forward between ctx and *params: the module, the inputs, the options."""
+    return (None,) * (forward.__code__.co_argcount - 1)
 
 
 def _return_param_grads(m: "HipUNet", saved, alias):
@@ -858,21 +826,19 @@ class _UNetFn(torch.autograd.Function):
         _check_generation(ctx)
         saved, alias = _save_accumulated(m)
         m._backward_raw(dlogits.contiguous().float(), ctx.device)
-        return (None, None) + _return_param_grads(m, saved, alias)
+        return _no_grads(_UNetFn.forward) + _return_param_grads(m, saved, alias)
 
 
 class _UNetLossFn(torch.autograd.Function):
     """(loss, logits) = CE(f(x; params), target): the fused training_step path."""
 
     @staticmethod
-    def forward(ctx, module: HipUNet, x, target, ignore_index, want_logits, kind, dice_weight, class_weight,
-                label_smoothing, focal_gamma, region_weight, region_alpha, region_beta, region_smooth, *params):
+    def forward(ctx, module: HipUNet, x, target, ignore_index, want_logits, kind, dice_weight, options, *params):
         ctx.module = module
         ctx.device = _device_of(x)
         logits = module._forward_raw(x, True, want_logits=want_logits)
         ctx.generation = module._generation
-        loss = module._loss_raw(target, ignore_index, ctx.device, kind, dice_weight, class_weight, label_smoothing,
-                                focal_gamma, region_weight, region_alpha, region_beta, region_smooth)
+        loss = module._loss_raw(target, ignore_index, ctx.device, kind, dice_weight, options)
         if logits is None:
             logits = torch.empty(0, device=ctx.device)
         ctx.mark_non_differentiable(logits)
@@ -887,7 +853,7 @@ class _UNetLossFn(torch.autograd.Function):
         check(_lib.load().fu_scale_loss_grad(m._ctx, ptr(dl), m._stream(ctx.device)))
         saved, alias = _save_accumulated(m)
         m._backward_raw(None, ctx.device)
-        return (None,) * 14 + _return_param_grads(m, saved, alias)
+        return _no_grads(_UNetLossFn.forward) + _return_param_grads(m, saved, alias)
 
 
 class HipAdam(torch.optim.Adam):

@@ -239,7 +239,9 @@ def test_trainer_checks_the_region_options_on_the_host(monkeypatch):
     _no_gpu(monkeypatch)
     net = HipUNet(2, 3, base_channels=8)
     tr = DataParallelTrainer(net, lr=1e-3, region_weight=1, region_alpha=1, region_beta=1)
-    assert tr._region_kwargs() == dict(region_weight=1.0, region_alpha=1.0, region_beta=1.0, region_smooth=1.0)
+    o = tr.loss_options
+    assert (o.region_weight, o.region_alpha, o.region_beta, o.region_smooth) == (1.0, 1.0, 1.0, 1.0)
+    assert all(type(v) is float for v in (o.region_weight, o.region_alpha, o.region_beta, o.region_smooth))
     assert DataParallelTrainer(net, lr=1e-3).region_weight == 0.0
     for bad in BAD:
         with pytest.raises(ValueError):
