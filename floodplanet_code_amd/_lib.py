@@ -186,6 +186,8 @@ SIGNATURES = {
     "fu_test_bnb_separate": (None, [_i]),
     "fu_test_head_store_g": (None, [_i]),
     "fu_test_force_full_taps": (None, [_i]),
+    "fu_test_op_center_only": (None, [_i]),
+    "fu_test_conv_f32_tile_rows": (_i, [_i] * 4),
     "fu_test_perturb_bnb_sums": (None, [_f]),
     "fu_test_conv_route": (_i, [_i] * 11),
     "fu_test_conv_route_name": (C.c_char_p, [_i, _i]),

@@ -392,6 +392,8 @@ void wgrad_split_shared(int Cin, int Cout, int B, int H, int W, int* nPix, int* 
 
 // precision-specific implementations (fu_conv_f32.hip / fu_conv_bf16.hip; the 16-bit weight gradient: fu_wgrad_bf16.hip)
 int conv3x3_num_stat_tiles_f32(int B, int H, int W);
+int conv3x3_f32_tile_rows(int B, int H, int W, int N);   // the TH instantiation of k_conv3x3_f32 a launch of this shape runs (8 or 4)
+bool test_op_center_only();                              // fu_test_op_center_only (fu_conv.hip)
 int launch_conv3x3_f32(const ConvIn& in, const float* wpk, const float* bias, float* dst0, int D0, float* dst1, int D1,
                        float* stats, int* n_stat_tiles, int B, int H, int W, hipStream_t s);
 int64_t conv3x3_wgrad_slab_elems_f32(int Cin, int Cout, int B, int H, int W);

@@ -8,7 +8,8 @@
 namespace fu {
 
 // ---- the 16-bit convs' testing hooks (include/floodunet.h) and the query for what they and the shapes decide -----------
-ConvHooks g_conv_hooks = {0, 0, 0, 0};
+ConvHooks g_conv_hooks = {0, 0, 0, 0, 0};
+bool test_op_center_only() { return g_conv_hooks.op_center_only != 0; }
 
 // the parameter blocks as launch_conv3x3_bf16 / launch_conv3x3_wgrad_bf16 fill them, with stand-in non-null pointers: a
 // forward launch carries bias and statistics, a dgrad launch neither, and the fused-sums request when want_bnsums
@@ -333,6 +334,8 @@ void fu_test_force_general_conv(int on) { fu::g_conv_hooks.force_general = on; }
 void fu_test_force_lockstep_wgrad(int on) { fu::g_conv_hooks.wgrad_lockstep = on; }
 void fu_test_force_full_taps(int on) { fu::g_conv_hooks.full_taps = on; }
 void fu_test_conv_tile_mode(int mode) { fu::g_conv_hooks.tile_mode = mode; }
+void fu_test_op_center_only(int on) { fu::g_conv_hooks.op_center_only = on ? 1 : 0; }
+int fu_test_conv_f32_tile_rows(int B, int H, int W, int N) { return fu::conv3x3_f32_tile_rows(B, H, W, N); }
 
 int fu_test_conv_route(int kind, int C0, int has_bn0, int C1, int D0, int D1, int center_only, int want_bnsums, int B, int H,
                        int W) {

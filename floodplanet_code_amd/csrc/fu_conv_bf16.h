@@ -191,6 +191,7 @@ struct ConvHooks {
   int full_taps;        // fu_test_force_full_taps: embedded 1x1 convs run all nine taps
   int tile_mode;        // fu_test_conv_tile_mode: 0 = heuristic, 1 = square fast tiles only, 2 = tall fast tile, 3 = rs, 4 = pp
   int wgrad_lockstep;   // fu_test_force_lockstep_wgrad: 1 = k_wgrad_bf16<4,8> for the ping-pong kernel, 2 = its general staging
+  int op_center_only;   // fu_test_op_center_only: the fu_op_conv3x3_* hooks mark their ConvIn as an embedded 1x1
 };
 extern ConvHooks g_conv_hooks;
 

@@ -242,6 +242,7 @@ static inline int conv_pick_th(int B, int H, int W, int N) {
   return wg8 >= 768 ? 8 : 4;
 }
 
+int conv3x3_f32_tile_rows(int B, int H, int W, int N) { return conv_pick_th(B, H, W, N); }
 int conv3x3_num_stat_tiles_f32(int B, int H, int W) { return B * ceil_div(H, 4) * ceil_div(W, 16); }
 
 int launch_conv3x3_f32(const ConvIn& in, const float* wpk, const float* bias, float* dst0, int D0, float* dst1, int D1,

@@ -56,6 +56,7 @@ int fu_op_conv3x3_fwd(int precision, const void* src0, int C0, const float* bn_a
   const bool want_stats = stats_sum && stats_sqsum;
   if (want_stats) FU_TRY(st.get((size_t)conv3x3_num_stat_tiles(p, B, H, W) * Cout * 2 * sizeof(float)));
   ConvIn in{src0, C0, bn_a0, bn_b0, src1, src1 ? C1 : 0};
+  in.center_only = test_op_center_only();
   int nt = 0;
   FU_TRY(launch_conv3x3(p, in, wf.p, bias, y, Cout, nullptr, 0, want_stats ? (float*)st.p : nullptr, &nt, B, H, W, s));
   if (want_stats)
@@ -74,6 +75,7 @@ int fu_op_conv3x3_dgrad(int precision, const void* dy, int Cout, const float* w_
   FU_TRY(wd.get(conv3x3_pack_elems(p, Cin, Cout) * fu_elem_size(precision)));
   FU_TRY(launch_pack_conv3x3(p, w_oihw, Cout, Cin, Cin, nullptr, wd.p, s));
   ConvIn in{dy, Cout, nullptr, nullptr, nullptr, 0};
+  in.center_only = test_op_center_only();
   FU_TRY(launch_conv3x3(p, in, wd.p, nullptr, dx0, C0, dx1, dx1 ? C1 : 0, nullptr, nullptr, B, H, W, s));
   FU_HIP_CHECK(hipStreamSynchronize(s));
   return FU_OK;
@@ -88,6 +90,11 @@ int fu_op_conv3x3_wgrad(int precision, const void* src0, int C0, const float* bn
   TmpBuf slab;
   FU_TRY(slab.get(conv3x3_wgrad_slab_elems(p, Cin, Cout, B, H, W) * sizeof(float)));
   ConvIn in{src0, C0, bn_a0, bn_b0, src1, src1 ? C1 : 0};
+  in.center_only = test_op_center_only();
+  // a one-tap launch writes the centre tap's slabs only and the reduce reads all nine: zero slabs make dw's other taps 0 here
+  // (in the network they are whatever the workspace held; no caller reads them)
+  if (in.center_only)
+    FU_HIP_CHECK(hipMemsetAsync(slab.p, 0, conv3x3_wgrad_slab_elems(p, Cin, Cout, B, H, W) * sizeof(float), s));
   FU_TRY(launch_conv3x3_wgrad(p, in, dy, Cout, (float*)slab.p, dw_oihw, Cin, nullptr, 0, nullptr, B, H, W, s));
   FU_HIP_CHECK(hipStreamSynchronize(s));
   return FU_OK;

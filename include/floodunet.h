@@ -623,6 +623,13 @@ void fu_test_head_store_g(int on);
  * instead of the 1-tap instantiation of the fast kernel; the other eight taps multiply exact zeros, so the results are
  * bit-identical.  Process-wide. */
 void fu_test_force_full_taps(int on);
+/* Testing hook: on != 0 makes fu_op_conv3x3_fwd, fu_op_conv3x3_dgrad and fu_op_conv3x3_wgrad mark their launch as an embedded
+ * 1x1 (ConvIn::center_only, the late-fusion convs): the caller's weights must be zero off the centre tap, the 16-bit launches
+ * take the one-tap routes (unless fu_test_force_full_taps) and the weight gradient's other taps come back as 0.  Process-wide. */
+void fu_test_op_center_only(int on);
+/* Testing hook: the tile height (8 or 4 rows of 16 pixels) of the fp32 forward / dgrad kernel for a launch of this shape with N
+ * output channels -- the launcher's own choice, asked without a launch. */
+int fu_test_conv_f32_tile_rows(int B, int H, int W, int N);
 
 /* Testing hook: which kernel a 16-bit 3x3 conv launch of these shapes runs under the switches currently set -- the launcher's
  * own decision, asked without a launch (no HIP call: works without a GPU).  kind 0 = forward (bias and statistics), 1 =
