@@ -217,6 +217,8 @@ SIGNATURES = {
     "fu_op_head_fwd": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "fu_op_head_bwd": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "fu_op_bn_bwd": (_i, [_i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "fu_op_bn_bwd_ex": (_i, [_i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _i, _p]),
+    "fu_op_bn_stats": (_i, [_p, _i, _i, _i64, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p]),
     "fu_op_maxpool2": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "fu_op_upsample2": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "fu_op_upsample2_bwd": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),

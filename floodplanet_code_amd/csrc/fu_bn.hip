@@ -360,6 +360,7 @@ __global__ void k_bn_bwd_pool(T* __restrict__ g, const T* __restrict__ y, const 
 }
 
 static int bn_bwd_blocks(int C, int64_t npix) {
+  if (C < 4 || C > 4 * BNB_THREADS) return 1;        // no pixel row fits a block: launch_bn_bwd rejects the width
   const int rows = BNB_THREADS / (C >> 2);
   int64_t nb = ceil_div64(npix, (int64_t)rows * 8);  // ~8 pixels per thread
   if (nb > 2048) nb = 2048;
@@ -382,7 +383,7 @@ int launch_bn_bwd(Prec p, const BnBwdArgs& A, hipStream_t s) {
   const HeadGrad* head = A.head;
   FU_REQUIRE(head == nullptr || (ext_partials > 0 && g_pool == nullptr && p != PREC_F32 && C % 8 == 0 && BNB_THREADS % (C / 8) == 0),
              "bn_bwd: a recomputed head gradient needs the producer's sums, a 16-bit element type and C | 2048");
-  FU_REQUIRE(C % 4 == 0 && C <= 1024, "bn_bwd: channels must be a multiple of 4 and <= 1024 (got %d)", C);
+  FU_REQUIRE(C >= 4 && C % 4 == 0 && C <= 1024, "bn_bwd: channels must be a multiple of 4 and <= 1024 (got %d)", C);
   // ext_partials > 0: `partials` already holds that many [C][2] rows of the two sums (written by the producer of g, see
   // BnbFuse in fu_common.h) -- the reduce pass is skipped, the apply pass keeps its own grid
   FU_REQUIRE(ext_partials == 0 || (g_pool == nullptr && sync_world() <= 1), "bn_bwd: external partial sums with a pooled source / exact sync");
@@ -410,13 +411,13 @@ int launch_bn_bwd(Prec p, const BnBwdArgs& A, hipStream_t s) {
   }
   FU_LAUNCH_CHECK();
   const BnBwdOut o{g_grad_unscale, A.dgamma, A.dbeta, A.coef};
-  if (sync_world() <= 1) {
-    hipLaunchKernelGGL((k_bn_stats_fused<1, BnBwdOut>), dim3(C / 4), dim3(256), 0, s, A.partials,
-                       ext_partials > 0 ? ext_partials : nb, C, (double)npix, o);
+  const int n_rows = ext_partials > 0 ? ext_partials : nb;     // (exact sync never comes with external sums: n_rows = nb there)
+  if (sync_world() <= 1 && !A.two_level) {
+    hipLaunchKernelGGL((k_bn_stats_fused<1, BnBwdOut>), dim3(C / 4), dim3(256), 0, s, A.partials, n_rows, C, (double)npix, o);
     FU_LAUNCH_CHECK();
   } else {
     int G = 0;
-    FU_TRY(reduce_partials<2>(A.partials, A.dscratch, nb, C, s, &G));
+    FU_TRY(reduce_partials<2>(A.partials, A.dscratch, n_rows, C, s, &G));
     FU_TRY(sync_sum_over_ranks(A.dscratch, (int64_t)G * C * 2, true, s));     // exact DP: global sums of g and g*xhat
     hipLaunchKernelGGL(k_bn_bwd_finalize, dim3(ceil_div(C, 8)), dim3(256), 0, s, A.dscratch, G, C,
                        (double)npix * sync_world(), 1.0 / sync_world(), o);

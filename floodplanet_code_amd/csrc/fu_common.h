@@ -460,6 +460,8 @@ struct BnBwdArgs {
   const void* g_pool = nullptr; int B = 0, H = 0, W = 0;
   int ext_partials = 0;                                // > 0: `partials` already holds that many rows (BnbFuse)
   const HeadGrad* head = nullptr;                      // g is recomputed from the head's dl and w instead of read
+  bool two_level = false;                              // test hook: finalise the sums by reduce_partials + k_bn_bwd_finalize (the exact
+                                                       // data-parallel form) with world = 1; needs dscratch
 };
 int launch_bn_bwd(Prec p, const BnBwdArgs& A, hipStream_t s);
 

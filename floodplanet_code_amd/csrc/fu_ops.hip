@@ -2,6 +2,7 @@
 // partial buffers of their own -- the hooks of the op-level parity tests -- and fu_test_get_buffer and
 // fu_test_loss_buffers, the only entry points here that look inside a context.
 #include "fu_ctx.h"
+#include "fu_elem.h"
 
 #include <vector>
 
@@ -103,6 +104,11 @@ int fu_op_conv3x3_wgrad(int precision, const void* src0, int C0, const float* bn
 int fu_op_maxpool2(int precision, const void* src, const float* bn_a, const float* bn_b, void* dst, int B, int H,
                    int W, int C, fu_stream stream) {
   Prec p; FU_TRY(prec_of(precision, &p));
+  const int V = 16 / fu_elem_size(precision);
+  FU_REQUIRE(C > 0 && C % V == 0, "maxpool: unsupported shape (C=%d H=%d B=%d)", C, H, B);
+  FU_REQUIRE(src && dst, "fu_op_maxpool2: null argument");
+  FU_REQUIRE(!bn_a == !bn_b, "fu_op_maxpool2: bn_a and bn_b go together (both or neither)");
+  FU_REQUIRE(B > 0 && H >= 2 && W >= 2, "fu_op_maxpool2: no complete 2x2 window (B=%d H=%d W=%d)", B, H, W);
   return launch_maxpool2(p, src, bn_a, bn_b, dst, B, H, W, C, (hipStream_t)stream);
 }
 
@@ -272,29 +278,96 @@ int fu_op_head_bwd(int precision, const float* dlogits_nhwc, const void* y, cons
   return FU_OK;
 }
 
-int fu_op_bn_bwd(int precision, void* g, const void* y, int C, int B, int H, int W, const float* bn_a,
-                 const float* bn_b, const float* mean, const float* invstd, const void* g_pool, float* dgamma,
-                 float* dbeta, fu_stream stream) {
+// ---- op-level test hooks of the BatchNorm kernels (fu_bn.hip): every argument check precedes the first allocation or HIP call ----
+namespace {
+// rows [n][C] (fp32) -> out[c] = the rows added in fp64 in row order, rounded once
+__global__ void k_rows_collapse(const float* part, int n, int C, float* out) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double s = 0;
+  for (int t = 0; t < n; ++t) s += part[(int64_t)t * C + c];
+  out[c] = (float)s;
+}
+struct UnscaleGuard {     // g_grad_unscale for the duration of one hook call
+  explicit UnscaleGuard(const float* u) { g_grad_unscale = u; }
+  ~UnscaleGuard() { g_grad_unscale = nullptr; }
+};
+}  // namespace
+
+int fu_op_bn_stats(const float* partials, int n_part, int C, int64_t count, const float* conv_bias, const float* gamma,
+                   const float* beta, float eps, float momentum, float* mean, float* invstd, float* a, float* b,
+                   float* rmean, float* rvar, int64_t* nbt, fu_stream stream) {
+  FU_REQUIRE(partials && gamma && beta && mean && invstd && a && b, "fu_op_bn_stats: null argument");
+  FU_REQUIRE(!rmean == !rvar, "fu_op_bn_stats: rmean and rvar go together (both or neither)");
+  FU_REQUIRE(n_part >= 1 && C >= 1 && count >= 1, "fu_op_bn_stats: n_part, C and count must be >= 1 (got %d, %d, %lld)", n_part, C,
+             (long long)count);
+  hipStream_t s = (hipStream_t)stream;
+  TmpBuf scr;
+  FU_TRY(scr.get((size_t)reduce_scratch_elems(C) * sizeof(double)));
+  const BnFwdOut o{conv_bias, gamma, beta, eps, momentum, mean, invstd, a, b, rmean, rvar, nbt};
+  FU_TRY(launch_bn_finalize(o, partials, n_part, C, count, (double*)scr.p, s));
+  FU_HIP_CHECK(hipStreamSynchronize(s));
+  return FU_OK;
+}
+
+int fu_op_bn_bwd_ex(int precision, void* g, const void* y, int C, int B, int H, int W, const float* bn_a,
+                    const float* bn_b, const float* mean, const float* invstd, const void* g_pool, float* dgamma,
+                    float* dbeta, const float* ext_sums, int ext_rows, const float* head_dl, const float* head_w, int ncls,
+                    const float* unscale, float* db, float* coef, int two_level, fu_stream stream) {
   Prec p; FU_TRY(prec_of(precision, &p));
   FU_REQUIRE(g && y && bn_a && bn_b && mean && invstd && dgamma && dbeta, "fu_op_bn_bwd: null argument");
-  hipStream_t s = (hipStream_t)stream;
+  FU_REQUIRE(ext_rows >= 0 && !ext_sums == (ext_rows == 0), "fu_op_bn_bwd: external sums and their row count go together");
+  FU_REQUIRE(!head_dl == !head_w, "fu_op_bn_bwd: head_dl and head_w go together (both or neither)");
+  FU_REQUIRE(B > 0 && H > 0 && W > 0, "fu_op_bn_bwd: empty shape (B=%d H=%d W=%d)", B, H, W);
+  FU_REQUIRE(C >= 4 && C <= 1024 && C % 4 == 0, "fu_op_bn_bwd: channels must be a multiple of 4 in 4..1024 (got %d)", C);
   const int64_t npix = (int64_t)B * H * W;
-  TmpBuf part, coef, dbp, scr;
-  FU_TRY(part.get((size_t)bn_bwd_partial_elems(C, npix) * sizeof(float)));
-  FU_TRY(coef.get((size_t)C * 2 * sizeof(float)));
+  if (g_pool) {
+    FU_REQUIRE(BNB_THREADS % (C / 4) == 0, "fu_op_bn_bwd (pooled): C / 4 must divide %d (got C=%d)", BNB_THREADS, C);
+    FU_REQUIRE(!ext_sums && !head_dl, "fu_op_bn_bwd (pooled): neither external sums nor a recomputed head gradient");
+    FU_REQUIRE(npix < ((int64_t)1 << 31), "fu_op_bn_bwd (pooled): too many pixels");
+  }
+  if (head_dl) {
+    FU_REQUIRE(p != PREC_F32, "fu_op_bn_bwd (head): 16-bit precisions only");
+    FU_REQUIRE(C % 8 == 0 && BNB_THREADS % (C / 8) == 0, "fu_op_bn_bwd (head): C / 8 must divide %d (got C=%d)", BNB_THREADS, C);
+    FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "fu_op_bn_bwd (head): n_classes must be 1..%d (got %d)", HEAD_MAX_CLS, ncls);
+    FU_REQUIRE(ext_sums, "fu_op_bn_bwd (head): the recomputed head gradient needs the external sums");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  TmpBuf part, coefb, dbp, scr;
+  if (!ext_sums) FU_TRY(part.get((size_t)bn_bwd_partial_elems(C, npix) * sizeof(float)));
+  if (!coef) FU_TRY(coefb.get((size_t)C * 2 * sizeof(float)));
   FU_TRY(dbp.get((size_t)bn_bwd_partial_elems(C, npix) * sizeof(float)));
   FU_TRY(scr.get((size_t)reduce_scratch_elems(std::max(C, 64)) * sizeof(double)));
   int ndb = 0;
+  const HeadGrad hg{head_dl, head_w, ncls};
   BnBwdArgs A;
   A.g = g; A.y = y; A.C = C; A.npix = npix;
   A.a = bn_a; A.b = bn_b; A.mean = mean; A.invstd = invstd;
   A.dgamma = dgamma; A.dbeta = dbeta;
-  A.partials = (float*)part.p; A.coef = (float*)coef.p; A.db_partials = (float*)dbp.p; A.n_db_partials = &ndb;
+  A.partials = ext_sums ? const_cast<float*>(ext_sums) : (float*)part.p;      // read only when the rows are the caller's
+  A.coef = coef ? coef : (float*)coefb.p; A.db_partials = (float*)dbp.p; A.n_db_partials = &ndb;
   A.dscratch = (double*)scr.p;
   A.g_pool = g_pool; A.B = B; A.H = H; A.W = W;
-  FU_TRY(launch_bn_bwd(p, A, s));
+  A.ext_partials = ext_rows;
+  A.head = head_dl ? &hg : nullptr;
+  A.two_level = two_level != 0;
+  {
+    UnscaleGuard guard(unscale);
+    FU_TRY(launch_bn_bwd(p, A, s));
+  }
+  if (db) {
+    hipLaunchKernelGGL(k_rows_collapse, dim3(ceil_div(C, 64)), dim3(64), 0, s, (const float*)dbp.p, ndb, C, db);
+    FU_LAUNCH_CHECK();
+  }
   FU_HIP_CHECK(hipStreamSynchronize(s));
   return FU_OK;
+}
+
+int fu_op_bn_bwd(int precision, void* g, const void* y, int C, int B, int H, int W, const float* bn_a,
+                 const float* bn_b, const float* mean, const float* invstd, const void* g_pool, float* dgamma,
+                 float* dbeta, fu_stream stream) {
+  return fu_op_bn_bwd_ex(precision, g, y, C, B, H, W, bn_a, bn_b, mean, invstd, g_pool, dgamma, dbeta, nullptr, 0, nullptr,
+                         nullptr, 0, nullptr, nullptr, nullptr, 0, stream);
 }
 
 int fu_test_get_buffer(fu_ctx* c, int block, int which, void** ptr, int64_t* elems) {

@@ -729,6 +729,28 @@ int fu_op_head_bwd(int precision, const float* dlogits_nhwc, const void* y, cons
 int fu_op_bn_bwd(int precision, void* g, const void* y, int C, int B, int H, int W, const float* bn_a,
                  const float* bn_b, const float* mean, const float* invstd, const void* g_pool, float* dgamma,
                  float* dbeta, fu_stream stream);
+/* The BatchNorm test hooks below, and fu_op_bn_bwd and fu_op_maxpool2, check every argument before their first allocation
+ * or HIP call: precision, null operands, optional groups given whole, B, H, W > 0 (the pool: H, W >= 2), and for the
+ * backward 4 <= C <= 1024 with C % 4 == 0 (pooled: C / 4 divides 256, no external sums, no head; head: a 16-bit type,
+ * C / 8 divides 256, ncls in 1..8, external sums present).
+ * fu_op_bn_bwd with optional extras (fu_op_bn_bwd is this call without them):
+ *   ext_sums [ext_rows][C][2]: the two sums per row as their producer (a dgrad or the head backward) left them; the
+ *     reduce pass is skipped.  Null with ext_rows = 0.
+ *   head_dl [npix][ncls], head_w [ncls][C], ncls: g = dl . w is recomputed in the apply pass (g is output only).
+ *   unscale: a device float installed as the gradient unscale factor (fp16 loss scaling) for this call.
+ *   db [C]: the per-block sums of dy (the producing conv's bias gradient) added in fp64 in block order, rounded once.
+ *   coef [C][2]: s1 / N and s2 / N as the apply pass reads them.
+ *   two_level != 0: the sums are finalised by the two-launch form of the exact data-parallel mode, with one rank. */
+int fu_op_bn_bwd_ex(int precision, void* g, const void* y, int C, int B, int H, int W, const float* bn_a,
+                    const float* bn_b, const float* mean, const float* invstd, const void* g_pool, float* dgamma,
+                    float* dbeta, const float* ext_sums, int ext_rows, const float* head_dl, const float* head_w, int ncls,
+                    const float* unscale, float* db, float* coef, int two_level, fu_stream stream);
+/* BatchNorm forward finalisation from given partial sums: partials [n_part][C][2] fp32 (sum y, sum y*y per tile) over
+ * `count` elements per channel -> mean (+ conv_bias, may be null), invstd, a = gamma * invstd, b = beta - mean * a, and,
+ * unless null, the running statistics rmean / rvar (null together) and nbt (+1 per call). */
+int fu_op_bn_stats(const float* partials, int n_part, int C, int64_t count, const float* conv_bias, const float* gamma,
+                   const float* beta, float eps, float momentum, float* mean, float* invstd, float* a, float* b,
+                   float* rmean, float* rvar, int64_t* nbt, fu_stream stream);
 
 #ifdef __cplusplus
 }

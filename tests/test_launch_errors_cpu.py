@@ -146,3 +146,111 @@ def test_head_backward_sums_are_unsupported_in_fp32_before_any_hip_call():
     lib = _lib.load()
     assert head_bwd(lib, _lib.FU_F32, a=FAKE, b=FAKE, sums=(FAKE,) * 4) == _lib.FU_ERR_UNSUPPORTED
     assert b"fu_op_head_bwd: the head-backward kernel does not emit the sums in this precision" in lib.fu_last_error()
+
+
+# the BatchNorm test hooks and the max-pool hook likewise: every check comes before the first allocation or HIP call
+def bn_bwd(lib, precision, C=64, B=1, H=4, W=4, g=FAKE, y=FAKE, a=FAKE, b=FAKE, mean=FAKE, invstd=FAKE, g_pool=None,
+           dgamma=FAKE, dbeta=FAKE, ext=None, rows=0, dl=None, w=None, ncls=0, two_level=0):
+    return lib.fu_op_bn_bwd_ex(precision, g, y, C, B, H, W, a, b, mean, invstd, g_pool, dgamma, dbeta, ext, rows, dl, w, ncls,
+                               None, None, None, two_level, None)
+
+
+def bn_stats(lib, partials=FAKE, n_part=4, C=8, count=64, gamma=FAKE, beta=FAKE, mean=FAKE, invstd=FAKE, a=FAKE, b=FAKE,
+             rmean=None, rvar=None):
+    return lib.fu_op_bn_stats(partials, n_part, C, count, None, gamma, beta, 1e-5, 0.1, mean, invstd, a, b, rmean, rvar, None,
+                              None)
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("C", [0, 2, 6, -4, 1028, 2048])
+def test_bn_backward_hooks_reject_a_bad_channel_count_and_survive(precision, C):
+    lib = _lib.load()
+    # C < 4 used to end the process with SIGFPE in bn_bwd_partial_elems (256 / (C >> 2)); C = 6 reached hipMalloc first
+    assert bn_bwd(lib, precision, C=C) == _lib.FU_ERR_INVALID
+    assert b"fu_op_bn_bwd: channels must be a multiple of 4 in 4..1024" in lib.fu_last_error()
+    assert lib.fu_op_bn_bwd(precision, FAKE, FAKE, C, 1, 4, 4, FAKE, FAKE, FAKE, FAKE, None, FAKE, FAKE, None) == _lib.FU_ERR_INVALID
+    assert b"fu_op_bn_bwd: channels must be a multiple of 4 in 4..1024" in lib.fu_last_error()
+
+
+@pytest.mark.parametrize("C", [0, 2, 6])
+def test_bn_stats_hook_takes_any_positive_channel_count_but_not_zero(C):
+    lib = _lib.load()
+    # the forward has a form for every C >= 1 (two-level when C % 4 != 0); C = 0, and nulls at C = 2 and 6, are answered on the host
+    if C == 0:
+        assert bn_stats(lib, C=0) == _lib.FU_ERR_INVALID
+        assert b"fu_op_bn_stats: n_part, C and count must be >= 1" in lib.fu_last_error()
+    else:
+        assert bn_stats(lib, C=C, partials=None) == _lib.FU_ERR_INVALID
+        assert b"fu_op_bn_stats: null argument" in lib.fu_last_error()
+
+
+def test_bn_stats_hook_rejects_bad_calls():
+    lib = _lib.load()
+    for name in ("partials", "gamma", "beta", "mean", "invstd", "a", "b"):
+        assert bn_stats(lib, **{name: None}) == _lib.FU_ERR_INVALID, name
+        assert b"fu_op_bn_stats: null argument" in lib.fu_last_error()
+    for rm, rv in ((FAKE, None), (None, FAKE)):
+        assert bn_stats(lib, rmean=rm, rvar=rv) == _lib.FU_ERR_INVALID
+        assert b"rmean and rvar go together" in lib.fu_last_error()
+    for bad in (dict(n_part=0), dict(C=0), dict(count=0), dict(n_part=-1), dict(C=-8)):
+        assert bn_stats(lib, **bad) == _lib.FU_ERR_INVALID, bad
+        assert b"must be >= 1" in lib.fu_last_error()
+
+
+def test_bn_backward_hook_rejects_an_unknown_precision():
+    lib = _lib.load()
+    assert bn_bwd(lib, 7) == _lib.FU_ERR_INVALID
+    assert b"unknown precision" in lib.fu_last_error()
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_bn_backward_hook_rejects_nulls_partial_groups_and_empty_shapes(precision):
+    lib = _lib.load()
+    for name in ("g", "y", "a", "b", "mean", "invstd", "dgamma", "dbeta"):
+        assert bn_bwd(lib, precision, **{name: None}) == _lib.FU_ERR_INVALID, name
+        assert b"fu_op_bn_bwd: null argument" in lib.fu_last_error()
+    for ext, rows in ((FAKE, 0), (None, 3), (FAKE, -1)):
+        assert bn_bwd(lib, precision, ext=ext, rows=rows) == _lib.FU_ERR_INVALID
+        assert b"external sums and their row count go together" in lib.fu_last_error()
+    for dl, w in ((FAKE, None), (None, FAKE)):
+        assert bn_bwd(lib, precision, dl=dl, w=w, ncls=2, ext=FAKE, rows=1) == _lib.FU_ERR_INVALID
+        assert b"head_dl and head_w go together" in lib.fu_last_error()
+    for dims in (dict(B=0), dict(H=0), dict(W=0), dict(H=-2)):
+        assert bn_bwd(lib, precision, **dims) == _lib.FU_ERR_INVALID
+        assert b"fu_op_bn_bwd: empty shape" in lib.fu_last_error()
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_bn_backward_hook_rejects_what_the_pooled_and_head_routes_cannot_do(precision):
+    lib = _lib.load()
+    assert bn_bwd(lib, precision, C=12, g_pool=FAKE) == _lib.FU_ERR_INVALID          # 256 % 3 != 0
+    assert b"(pooled): C / 4 must divide 256" in lib.fu_last_error()
+    assert bn_bwd(lib, precision, g_pool=FAKE, ext=FAKE, rows=2) == _lib.FU_ERR_INVALID
+    assert b"(pooled): neither external sums nor a recomputed head gradient" in lib.fu_last_error()
+    head = dict(dl=FAKE, w=FAKE, ncls=2, ext=FAKE, rows=1)
+    if precision == _lib.FU_F32:
+        assert bn_bwd(lib, precision, **head) == _lib.FU_ERR_INVALID
+        assert b"(head): 16-bit precisions only" in lib.fu_last_error()
+        return
+    for C in (12, 24, 520):                                                           # off the vector; 256 % 3; 256 % 65
+        assert bn_bwd(lib, precision, C=C, **head) == _lib.FU_ERR_INVALID, C
+        assert b"(head): C / 8 must divide 256" in lib.fu_last_error()
+    for ncls in (0, 9, -1):
+        assert bn_bwd(lib, precision, **dict(head, ncls=ncls)) == _lib.FU_ERR_INVALID
+        assert b"(head): n_classes must be 1..8" in lib.fu_last_error()
+    assert bn_bwd(lib, precision, dl=FAKE, w=FAKE, ncls=2) == _lib.FU_ERR_INVALID
+    assert b"(head): the recomputed head gradient needs the external sums" in lib.fu_last_error()
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_maxpool_hook_rejects_nulls_half_a_prologue_and_maps_without_a_window(precision):
+    lib = _lib.load()
+    for src, dst in ((None, FAKE), (FAKE, None)):
+        assert lib.fu_op_maxpool2(precision, src, None, None, dst, 1, 8, 8, 8, None) == _lib.FU_ERR_INVALID
+        assert b"fu_op_maxpool2: null argument" in lib.fu_last_error()
+    for a, b in ((FAKE, None), (None, FAKE)):
+        assert lib.fu_op_maxpool2(precision, FAKE, a, b, FAKE, 1, 8, 8, 8, None) == _lib.FU_ERR_INVALID
+        assert b"bn_a and bn_b go together" in lib.fu_last_error()
+    for B, H, W in ((1, 1, 8), (1, 8, 1), (0, 8, 8), (1, 0, 8)):       # H = 1 used to ask for a grid with a zero dimension
+        assert lib.fu_op_maxpool2(precision, FAKE, None, None, FAKE, B, H, W, 8, None) == _lib.FU_ERR_INVALID
+        assert b"fu_op_maxpool2: no complete 2x2 window" in lib.fu_last_error()
