@@ -153,6 +153,10 @@ SIGNATURES = {
     "fu_adam_ema_step": (_i, [_p, _d, _d, _d, _d, _i64, _d, _d, _p]),
     "fu_adam_ema_scalars": (_i, [_d, _d, _d, _d, _i64, _d, _d, C.POINTER(C.c_float)]),
     "fu_adam_ema_step_dev": (_i, [_p, _p, _p]),
+    "fu_set_grad_clip": (_i, [_p, _d]),
+    "fu_grad_clip_state": (_i, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_i64), C.POINTER(_i64),
+                                C.POINTER(_i64)]),
+    "fu_grad_norms": (_i, [_p, _d, _p, _p]),
     "fu_zero_grads": (_i, [_p, _p]),
     "fu_stitch_add": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "fu_stitch_finalize": (_i, [_p, _p, _i, _i, _i, _p, _p]),

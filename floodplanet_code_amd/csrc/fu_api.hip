@@ -474,10 +474,20 @@ int adam_step(fu_ctx* c, const char* who, bool ema, const float* sc, const float
     FU_TRY(launch_grad_finite_check(c->G, c->total_params, c->guard, (hipStream_t)stream));
     skip = c->guard;
   }
+  // clipping armed (fu_set_grad_clip): the norm pass and its one-workgroup finalize go first and leave the scalars, with the
+  // coefficient folded into the gradient scale, in the context's own eight floats; the Adam launch is the _dev form on those,
+  // whichever entry point was called.  A non-finite norm skips the step (fp16: the guard's flag, set together with it)
+  if (c->clip_max_norm > 0.0) {
+    FU_TRY(launch_grad_sqnorm(c->clip, c->G, (hipStream_t)stream));
+    FU_TRY(launch_grad_clip_finalize(c->clip, sc, scalars_dev, ema, c->clip_max_norm, (hipStream_t)stream));
+    sc = nullptr;
+    scalars_dev = c->clip.scalars;
+    if (!skip) skip = &c->clip.state->skip;
+  }
   const AdamEma avg = {c->ema_p, c->ema_rm, c->RM, c->ema_rv, c->RV, c->total_bn};
   FU_TRY(launch_adam(c->P, c->G, c->adam_m, c->adam_v, c->total_params, ema ? &avg : nullptr, sc, scalars_dev,
                      (hipStream_t)stream, skip));
-  if (skip) FU_TRY(launch_guard_book(c->guard, (hipStream_t)stream));
+  if (c->prec == PREC_F16) FU_TRY(launch_guard_book(c->guard, (hipStream_t)stream));
   c->packed_dirty = true;
   return FU_OK;
 }
@@ -533,6 +543,49 @@ int fu_adam_ema_step_dev(fu_ctx* c, const float* scalars_dev, fu_stream stream) 
   FU_REQUIRE(c && c->P && c->G && c->RM && c->RV && scalars_dev,
              "fu_adam_ema_step_dev: buffers not bound (fu_bind_buffers), or null scalars");
   return adam_step(c, "fu_adam_ema_step_dev", true, nullptr, scalars_dev, stream);
+}
+
+namespace {
+// the chunk table, partials, state block and scalars of the gradient norm: made once per context, at the first use
+int ensure_grad_clip(fu_ctx* c) {
+  if (c->clip.chunks) return FU_OK;
+  std::vector<int64_t> off, numel;
+  for (const ParamInfo& p : c->params) { off.push_back(p.off); numel.push_back(p.numel); }
+  FU_HIP_CHECK(hipSetDevice(c->cfg.device));
+  return build_grad_clip(&c->clip, off.data(), numel.data(), (int)c->params.size(), &c->extra_allocs);
+}
+}  // namespace
+
+int fu_set_grad_clip(fu_ctx* c, double max_norm) {
+  FU_REQUIRE(c, "null context");
+  FU_REQUIRE(isfinite(max_norm) && max_norm >= 0.0, "fu_set_grad_clip: max_norm %g must be finite and >= 0 (0 disarms)", max_norm);
+  if (max_norm > 0.0) FU_TRY(ensure_grad_clip(c));
+  c->clip_max_norm = max_norm;
+  return FU_OK;
+}
+
+int fu_grad_clip_state(fu_ctx* c, float* last_norm, float* last_coef, int64_t* steps, int64_t* clipped_steps,
+                       int64_t* nonfinite_steps) {
+  FU_REQUIRE(c, "null context");
+  ClipState h = {};
+  if (c->clip.state) {
+    FU_HIP_CHECK(hipSetDevice(c->cfg.device));
+    FU_HIP_CHECK(hipDeviceSynchronize());                  // every stream: the step may run on a non-blocking one
+    FU_HIP_CHECK(hipMemcpy(&h, c->clip.state, sizeof(h), hipMemcpyDeviceToHost));
+  }
+  if (last_norm) *last_norm = h.last_norm;
+  if (last_coef) *last_coef = h.last_coef;
+  if (steps) *steps = h.steps;
+  if (clipped_steps) *clipped_steps = h.clipped;
+  if (nonfinite_steps) *nonfinite_steps = h.nonfinite;
+  return FU_OK;
+}
+
+int fu_grad_norms(fu_ctx* c, double grad_scale, float* norms_out_dev, fu_stream stream) {
+  FU_REQUIRE(c && c->G && norms_out_dev, "fu_grad_norms: no gradient buffer bound, or null output");
+  FU_TRY(ensure_grad_clip(c));
+  FU_TRY(launch_grad_sqnorm(c->clip, c->G, (hipStream_t)stream));
+  return launch_grad_norms_out(c->clip, grad_scale, norms_out_dev, (hipStream_t)stream);
 }
 
 int fu_adam_state(fu_ctx* c, float** exp_avg, float** exp_avg_sq) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <vector>
 
 // host tables of include/floodunet.h that the launchers below validate
 struct fu_stitch_entry;
@@ -627,5 +628,32 @@ struct AdamEma {
 // floats read on the device (the captured form)
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, const AdamEma* ema, const float* sc,
                 const float* scalars_dev, hipStream_t s, const int* skip = nullptr);
+
+// Global-norm gradient clipping ahead of the Adam launch (fu_set_grad_clip) and the gradient-norm report (fu_grad_norms).
+// The flat gradient buffer is cut into chunks of at most CLIP_CHUNK floats, none across two parameter tensors; one launch
+// writes every chunk's sum of squares (double), a one-workgroup launch sums them per tensor and in total, in a fixed order.
+constexpr int CLIP_CHUNK = 16384;
+struct ClipChunk { int64_t off; int32_t len; int32_t param; };
+// what the finalize launch leaves behind (fu_grad_clip_state); skip is WRITTEN every step: 1 = the norm was not finite
+struct ClipState { float last_norm, last_coef; int32_t skip, pad_; int64_t steps, clipped, nonfinite; };
+struct GradClip {            // device memory owned by the context, made once (build_grad_clip)
+  ClipChunk* chunks = nullptr;
+  int* first = nullptr;      // [nparams + 1]: tensor t owns the chunks first[t] .. first[t + 1] - 1
+  double* part = nullptr;    // [nchunks] sums of squares
+  ClipState* state = nullptr;
+  float* scalars = nullptr;  // the eight Adam scalars with the clip coefficient folded into slot 6
+  int nchunks = 0, nparams = 0;
+};
+// the chunk table of a parameter table (offsets and sizes in floats), host side; first gets nparams + 1 entries
+void plan_clip_chunks(const int64_t* off, const int64_t* numel, int nparams, std::vector<ClipChunk>* chunks,
+                      std::vector<int>* first);
+int build_grad_clip(GradClip* w, const int64_t* off, const int64_t* numel, int nparams, std::vector<void*>* allocs);
+int launch_grad_sqnorm(const GradClip& w, const float* g, hipStream_t s);
+// sc (eight host floats) or sc_dev (seven device floats, eight with ema): the Adam scalars as the caller formed them; the
+// clipped set goes to w.scalars, the report to w.state
+int launch_grad_clip_finalize(const GradClip& w, const float* sc, const float* sc_dev, bool ema, double max_norm,
+                              hipStream_t s);
+// norms_out[0 .. nparams - 1] = every tensor's L2 norm times |grad_scale|, norms_out[nparams] = the total; nothing else is written
+int launch_grad_norms_out(const GradClip& w, double grad_scale, float* norms_out, hipStream_t s);
 
 }  // namespace fu

@@ -195,6 +195,8 @@ struct fu_ctx {
   float* ema_p = nullptr;         // bound (caller-owned, fu_bind_ema_state): the weight EMA and the EMA of the running statistics
   float* ema_rm = nullptr;
   float* ema_rv = nullptr;
+  double clip_max_norm = 0.0;     // fu_set_grad_clip: > 0 = the optimiser step clips the global gradient norm to it
+  fu::GradClip clip;              // its chunk table, partials, state block and scalars (made at the first use; extra_allocs)
   fu::Profiler prof;
   struct Dp* dp = nullptr;            // fu_dp_init: RCCL communicator, communication stream, events
   std::vector<fu::PackTable> pack_tabs;   // <= MAX_PACK layers per launch

@@ -1,7 +1,9 @@
 // Optimiser kernels (gfx950): Adam in torch's single-tensor order, optionally with the weight EMA in the same pass, and the
-// fp16 guard around it (non-finite gradient check, skipped-step book-keeping).
+// fp16 guard around it (non-finite gradient check, skipped-step book-keeping); the global gradient norm and the clip
+// coefficient ahead of it (two launches of their own: the Adam kernels only ever see another gscale).
 #include "fu_common.h"
 
+#include <algorithm>
 #include <math.h>
 
 namespace fu {
@@ -183,6 +185,180 @@ int launch_grad_finite_check(const float* g, int64_t n, int* guard, hipStream_t 
 }
 int launch_guard_book(int* guard, hipStream_t s) {
   hipLaunchKernelGGL(k_guard_book, dim3(1), dim3(1), 0, s, guard);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) ahead of the Adam launch, and the gradient-norm report.
+// The Adam kernels above are not involved: clipping only replaces the one scalar they multiply every gradient by (gscale,
+// slot 6), computed on the device by two launches: k_grad_sqnorm_chunks streams the gradient buffer once and WRITES one
+// double per chunk (no atomics; the result does not depend on the grid), k_grad_norm_finalize (one workgroup) sums the
+// chunks of each tensor in chunk order, the tensors in parameter order, and forms the coefficient.  Every element is
+// squared in double -- exact for an fp32 value -- so gradients of 1e30 or 1e-30 neither overflow nor vanish.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double sq4_acc(double a, const float4 x) {
+  const double x0 = (double)x.x, x1 = (double)x.y, x2 = (double)x.z, x3 = (double)x.w;
+  a = fma(x0, x0, a);
+  a = fma(x1, x1, a);
+  a = fma(x2, x2, a);
+  return fma(x3, x3, a);
+}
+// One chunk per workgroup turn: scalar head up to the first 16-byte boundary (a chunk starts at any float offset and the
+// buffer is bound at any 4-byte alignment), 16-byte loads four in flight per lane, scalar tail; lane sums in a fixed order,
+// wave butterfly, then the four waves through LDS in wave order.
+__global__ __launch_bounds__(256) void k_grad_sqnorm_chunks(const float* __restrict__ g, const ClipChunk* __restrict__ chunks,
+                                                            int nchunks, double* __restrict__ part) {
+  __shared__ double wsum[4];
+  const int tid = threadIdx.x;
+  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const ClipChunk ck = chunks[c];
+    const float* __restrict__ p = g + ck.off;
+    const int len = ck.len;
+    int head = (int)(((16 - ((uintptr_t)p & 15)) & 15) >> 2);
+    if (head > len) head = len;
+    const int nvec = (len - head) >> 2;
+    const float4* __restrict__ v = reinterpret_cast<const float4*>(p + head);
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    int j = tid;
+    for (; j + 768 < nvec; j += 1024) {
+      const float4 x0 = v[j], x1 = v[j + 256], x2 = v[j + 512], x3 = v[j + 768];
+      a0 = sq4_acc(a0, x0);
+      a1 = sq4_acc(a1, x1);
+      a2 = sq4_acc(a2, x2);
+      a3 = sq4_acc(a3, x3);
+    }
+    for (; j < nvec; j += 256) a0 = sq4_acc(a0, v[j]);
+    const int tail0 = head + 4 * nvec, nrest = head + (len - tail0);      // at most 3 + 3 elements
+    if (tid < nrest) {
+      const double x = (double)p[tid < head ? tid : tail0 + (tid - head)];
+      a1 = fma(x, x, a1);
+    }
+    double a = (a0 + a1) + (a2 + a3);
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    if ((tid & 63) == 0) wsum[tid >> 6] = a;
+    __syncthreads();
+    if (tid == 0) part[c] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    __syncthreads();                                                       // wsum is free for the next chunk
+  }
+}
+
+struct ClipScalars { float v[8]; };
+// src[lo] + src[lo + 1] + ... in that order; the loads of eight terms are issued ahead of their adds, so that the chain
+// costs an add per term, not a memory round trip
+__device__ __forceinline__ double ordered_sum(const double* src, int lo, int hi) {
+  double s = 0.0;
+  int i = lo;
+  for (; i + 8 <= hi; i += 8) {
+    const double x0 = src[i], x1 = src[i + 1], x2 = src[i + 2], x3 = src[i + 3], x4 = src[i + 4], x5 = src[i + 5],
+                 x6 = src[i + 6], x7 = src[i + 7];
+    s += x0; s += x1; s += x2; s += x3; s += x4; s += x5; s += x6; s += x7;
+  }
+  for (; i < hi; ++i) s += src[i];
+  return s;
+}
+constexpr int CLIP_FIN_CHUNKS = 4096;    // partials staged in LDS up to this many chunks (32 KB); more are read in place
+constexpr int CLIP_MAX_PARAMS = 1024;    // per-tensor sums live in LDS (build_grad_clip refuses a longer parameter table)
+// sc_dev == null: the caller's scalars are scv (by value); else nsc floats (7, or 8 with the EMA weight) are read from sc_dev.
+// out_sc == null: no scalar part, no state (fu_grad_norms); norms_out == null: no per-tensor report (the optimiser step).
+__global__ __launch_bounds__(256) void k_grad_norm_finalize(const double* __restrict__ part, const int* __restrict__ first,
+                                                            int nparams, int nchunks, ClipScalars scv,
+                                                            const float* __restrict__ sc_dev, int nsc, double max_norm,
+                                                            float* __restrict__ out_sc, ClipState* __restrict__ st,
+                                                            float* __restrict__ norms_out, double report_scale) {
+#pragma clang fp contract(off)
+  __shared__ double lpart[CLIP_FIN_CHUNKS];
+  __shared__ double tsq[CLIP_MAX_PARAMS];
+  const int tid = threadIdx.x;
+  const bool staged = nchunks <= CLIP_FIN_CHUNKS;
+  float in[8];                                        // read ahead of the sums: nothing below waits for these loads
+  for (int k = 0; k < 8; ++k) in[k] = !out_sc ? 0.f : sc_dev ? (k < nsc ? sc_dev[k] : 0.f) : scv.v[k];
+  if (staged) {
+    for (int i = tid; i < nchunks; i += 256) lpart[i] = part[i];
+    __syncthreads();
+  }
+  for (int t = tid; t < nparams; t += 256) {
+    const int lo = first[t], hi = first[t + 1];
+    tsq[t] = staged ? ordered_sum(lpart, lo, hi) : ordered_sum(part, lo, hi);
+  }
+  __syncthreads();
+  if (norms_out)
+    for (int t = tid; t < nparams; t += 256) norms_out[t] = (float)(sqrt(tsq[t]) * fabs(report_scale));
+  if (tid != 0) return;
+  const double total = ordered_sum(tsq, 0, nparams);
+  if (norms_out) norms_out[nparams] = (float)(sqrt(total) * fabs(report_scale));
+  if (!out_sc) return;
+  const float gscale_in = in[6];
+  const double N = sqrt(total) * fabs((double)gscale_in);
+  const bool finite = isfinite(N);
+  const double r = max_norm / (N + 1e-6);
+  const float coef = (max_norm > 0.0 && finite && r < 1.0) ? (float)r : 1.0f;
+  for (int k = 0; k < 8; ++k) out_sc[k] = in[k];
+  out_sc[6] = gscale_in * coef;
+  st->last_norm = (float)N;
+  st->last_coef = coef;
+  st->skip = finite ? 0 : 1;
+  st->steps += 1;
+  if (coef < 1.0f) st->clipped += 1;
+  if (!finite) st->nonfinite += 1;
+}
+
+void plan_clip_chunks(const int64_t* off, const int64_t* numel, int nparams, std::vector<ClipChunk>* chunks,
+                      std::vector<int>* first) {
+  chunks->clear();
+  first->assign(1, 0);
+  for (int t = 0; t < nparams; ++t) {
+    for (int64_t o = 0; o < numel[t]; o += CLIP_CHUNK)
+      chunks->push_back({off[t] + o, (int32_t)std::min<int64_t>(CLIP_CHUNK, numel[t] - o), t});
+    first->push_back((int)chunks->size());
+  }
+}
+int build_grad_clip(GradClip* w, const int64_t* off, const int64_t* numel, int nparams, std::vector<void*>* allocs) {
+  if (w->chunks) return 0;
+  FU_REQUIRE(nparams >= 1 && nparams <= CLIP_MAX_PARAMS, "gradient norm: %d parameter tensors, at most %d supported", nparams,
+             CLIP_MAX_PARAMS);
+  std::vector<ClipChunk> chunks;
+  std::vector<int> first;
+  plan_clip_chunks(off, numel, nparams, &chunks, &first);
+  const size_t nch = chunks.size();
+  // one allocation: chunks | first | partials | state | scalars, each on a 256-byte boundary
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_first = up(nch * sizeof(ClipChunk)), o_part = o_first + up(first.size() * sizeof(int)),
+               o_state = o_part + up(nch * sizeof(double)), o_scal = o_state + up(sizeof(ClipState)),
+               total = o_scal + up(8 * sizeof(float));
+  char* base = nullptr;
+  FU_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&base), total));
+  allocs->push_back(base);
+  FU_HIP_CHECK(hipMemset(base, 0, total));
+  if (nch) FU_HIP_CHECK(hipMemcpy(base, chunks.data(), nch * sizeof(ClipChunk), hipMemcpyHostToDevice));
+  FU_HIP_CHECK(hipMemcpy(base + o_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice));
+  w->first = reinterpret_cast<int*>(base + o_first);
+  w->part = reinterpret_cast<double*>(base + o_part);
+  w->state = reinterpret_cast<ClipState*>(base + o_state);
+  w->scalars = reinterpret_cast<float*>(base + o_scal);
+  w->nchunks = (int)nch;
+  w->nparams = nparams;
+  w->chunks = reinterpret_cast<ClipChunk*>(base);
+  return 0;
+}
+int launch_grad_sqnorm(const GradClip& w, const float* g, hipStream_t s) {
+  if (w.nchunks == 0) return 0;
+  hipLaunchKernelGGL(k_grad_sqnorm_chunks, dim3(std::min(w.nchunks, 2048)), dim3(256), 0, s, g, w.chunks, w.nchunks, w.part);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+int launch_grad_clip_finalize(const GradClip& w, const float* sc, const float* sc_dev, bool ema, double max_norm,
+                              hipStream_t s) {
+  ClipScalars scv = {};
+  if (!sc_dev) for (int k = 0; k < 8; ++k) scv.v[k] = (k < 7 || ema) ? sc[k] : 0.f;
+  hipLaunchKernelGGL(k_grad_norm_finalize, dim3(1), dim3(256), 0, s, w.part, w.first, w.nparams, w.nchunks, scv, sc_dev,
+                     ema ? 8 : 7, max_norm, w.scalars, w.state, (float*)nullptr, 0.0);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+int launch_grad_norms_out(const GradClip& w, double grad_scale, float* norms_out, hipStream_t s) {
+  hipLaunchKernelGGL(k_grad_norm_finalize, dim3(1), dim3(256), 0, s, w.part, w.first, w.nparams, w.nchunks, ClipScalars{},
+                     (const float*)nullptr, 0, 0.0, (float*)nullptr, (ClipState*)nullptr, norms_out, grad_scale);
   FU_LAUNCH_CHECK();
   return 0;
 }

@@ -125,7 +125,7 @@ class DataParallelTrainer:
                  group=None, cap_bytes: int = 16 << 20, exact: bool = False, time_waits: bool = False,
                  graph: bool = False, class_weight=None, label_smoothing: float = 0.0, ema_decay: Optional[float] = None,
                  ema_warmup: bool = True, focal_gamma: float = 0.0, region_weight: float = 0.0, region_alpha: float = 0.5,
-                 region_beta: float = 0.5, region_smooth: float = 1.0):
+                 region_beta: float = 0.5, region_smooth: float = 1.0, grad_clip_norm: Optional[float] = None):
         """exact=False: DDP semantics (per-rank BN statistics and 1/N_valid, gradients averaged).
         exact=True: SyncBN statistics and a global N_valid (HipUNet.enable_exact_sync); the ranks together reproduce
         one device with world_size x the batch, gradients are summed (SURVEY.md 8(e) "exact mode").
@@ -138,9 +138,15 @@ class DataParallelTrainer:
         capture -- nothing is read back.
         ema_decay: keep a weight EMA on the net (HipUNet.enable_ema(ema_decay, ema_warmup)), moved on inside the fused Adam
         launch of every path -- eager, exact and captured.  It is rank-local and needs no collective: the ranks' parameters
-        are identical, so their averages are."""
+        are identical, so their averages are.
+        grad_clip_norm: clip the global L2 norm of the gradients to it inside the optimiser step of every path
+        (HipUNet.set_grad_clip: two launches ahead of the fused Adam launch, nothing read back).  The norm is that of the
+        gradients as Adam consumes them -- after the all-reduce and times grad_scale, i.e. of the averaged gradient -- so
+        every rank computes the same coefficient and no further collective is needed."""
         if ema_decay is not None:
             net.enable_ema(ema_decay, ema_warmup)
+        if grad_clip_norm is not None:
+            net.set_grad_clip(grad_clip_norm)
         self.net, self.lr, self.world_size, self.rank = net, lr, world_size, rank
         # checked on the host, once; every step hands this one object to HipUNet._loss_raw
         self.loss_options = LossOptions.make(net.n_classes, class_weight=class_weight, label_smoothing=label_smoothing,
@@ -163,6 +169,7 @@ class DataParallelTrainer:
         self._gx = self._gt = self._gloss = self._gscal = self._gscal_host = None
         self._g_ignore = None
         self._g_ema = False
+        self._g_clip = None            # the clip norm the captured step was recorded with (None: no norm launches in it)
         self._reducer: Optional[BucketedReducer] = None
         self._launch_stream = None     # the stream the bucket all-reduces are launched from (mode 2, fu_backward_fence)
         self._synced = False
@@ -228,6 +235,7 @@ class DataParallelTrainer:
         self._gx.copy_(x)
         self._gt.copy_(target)
         self._g_ema = net.ema_enabled                                 # which optimiser launch this graph holds
+        self._g_clip = net.grad_clip                                  # ... and whether the two norm launches go ahead of it
         n_scal = 8 if self._g_ema else 7
         self._gscal = torch.zeros(n_scal, dtype=torch.float32, device=dev)
         self._gscal_ring = [torch.zeros(n_scal, dtype=torch.float32).pin_memory() for _ in range(8)]
@@ -260,7 +268,7 @@ class DataParallelTrainer:
     def _graph_step(self, x, target, ignore_index):
         net = self.net
         if self._graph is not None and (int(ignore_index) != self._g_ignore or x.shape != self._gx.shape
-                                        or self._g_ema != net.ema_enabled):
+                                        or self._g_ema != net.ema_enabled or self._g_clip != net.grad_clip):
             self._graph = None                                        # another workload: capture again
         if self._graph is None:
             if net._ctx is None or net._ctx_key[1:3] != tuple(x.shape[2:]) or net._ctx_key[3] < x.shape[0]:

@@ -34,7 +34,10 @@ from typing import Dict, Iterable, List, Optional
 import torch
 
 from .models import build_model
-from .unet import check_focal_gamma, check_region_loss
+from .schedule import KINDS as LR_SCHEDULES, check_schedule, lr_at
+from .unet import check_focal_gamma, check_grad_clip, check_region_loss
+
+SCHEDULE_OPTIONS = ("lr_schedule", "warmup_steps", "min_lr")       # cfg keys, present only when the command line gave them
 
 DEFAULTS = dict(lr=1e-4, batch_size=10, n_epochs=11, crop_height=300, crop_width=300, ignore_index=0,
                 save_topk_models=3, limit_train_batches=None, limit_val_batches=None, log_image_iter=200,
@@ -91,7 +94,10 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
     (the last step's), train_region (that step's region term R, when the model's region_weight > 0),
     val_MulticlassJaccardIndex and train_tiles_per_s -- the tiles of the epoch's training loop over its
     host time, closed by one device synchronise per epoch (None when the train loader yields nothing) -- plus `plan`, the
-    train loader's `last_plan`, when it has one."""
+    train loader's `last_plan`, when it has one.  With an lr schedule (cfg lr_schedule / warmup_steps / min_lr: schedule.lr_at
+    per optimiser step, over n_epochs x the loader's length) or gradient clipping (the model's grad_clip_norm) an entry also
+    carries `lr`, the last step's; with clipping `grad_norm`, the last step's global gradient norm before clipping, and
+    `clipped_steps`, the steps clipped so far."""
     c = dict(DEFAULTS)
     c.update(cfg or {})
     torch.manual_seed(c["seed_num"])                                         # pl.seed_everything(seed_num)
@@ -100,6 +106,19 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
                             to_rgb_fcn=to_rgb_fcn, ignore_index=c["ignore_index"], **c["model"].get("model_kwargs", {}))
     model = model.to(device)
     opt = model.configure_optimizers()
+    # lr schedule (cfg keys lr_schedule / warmup_steps / min_lr, present only when asked for): one number per optimiser step,
+    # set into the optimiser's param_groups before the step.  Gradient clipping is the model's (grad_clip_norm -> HipAdam)
+    schedule = None
+    if any(k in c for k in SCHEDULE_OPTIONS):
+        kind, warmup, min_lr = check_schedule(c["lr"], c.get("lr_schedule", "constant"), c.get("warmup_steps", 0),
+                                              c.get("min_lr", 0.0))
+        per_epoch = len(train_loader)
+        if c["limit_train_batches"] is not None:
+            per_epoch = min(per_epoch, int(c["limit_train_batches"]))
+        schedule = dict(base_lr=float(c["lr"]), kind=kind, total_steps=per_epoch * int(c["n_epochs"]), warmup_steps=warmup,
+                        min_lr=min_lr)
+    clipping = getattr(model, "grad_clip_norm", None) is not None
+    n_steps = 0
     best: List = []                                                          # (metric, path), top-k
     ckpt_dir = os.path.join(exp_dir, "checkpoints") if exp_dir else None
     if ckpt_dir:
@@ -112,6 +131,9 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
             opt.zero_grad()
             loss = model.training_step(batch, i)
             loss.backward()
+            n_steps += 1
+            if schedule is not None:
+                opt.param_groups[0]["lr"] = lr_at(n_steps, **schedule)
             opt.step()
             model.global_step += 1
             n_tiles += int(batch["image"].shape[0])
@@ -121,6 +143,7 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
         train_region = None                                                  # R of the last step, before validation rewrites it
         if getattr(model, "region_weight", 0.0) > 0.0 and n_tiles:
             train_region = float(model.model.last_region_terms()[0])
+        clip_state = model.model.grad_clip_state() if clipping and n_tiles else None   # read once per epoch, behind the sync
         model.valid_metrics.reset()
         outs = []
         with model.eval_weights():                                           # the weight EMA, swapped in once per epoch
@@ -132,7 +155,12 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
                         "train_tiles_per_s": n_tiles / train_seconds if n_tiles and train_seconds > 0 else None})
         if train_region is not None:
             history[-1]["train_region"] = train_region
-        plan = getattr(train_loader, "last_plan", None)                      # a loader that chooses its tiles says which
+        if schedule is not None or clipping:
+            history[-1]["lr"] = float(opt.param_groups[0]["lr"])             # the last step's
+        if clip_state is not None:
+            history[-1]["grad_norm"] = clip_state["grad_norm"]               # the last step's, before clipping
+            history[-1]["clipped_steps"] = clip_state["clipped_steps"]       # of the run so far
+        plan =getattr(train_loader, "last_plan", None)                      # a loader that chooses its tiles says which
         if plan is not None:
             history[-1]["plan"] = dict(plan)
         if ckpt_dir:
@@ -204,6 +232,16 @@ def build_parser() -> argparse.ArgumentParser:
                          "checkpoint choice and the checkpoint's ema_state_dict use it (default: no EMA)")
     ap.add_argument("--no_ema_warmup", action="store_true",
                     help="use --ema_decay from the first update on (default: min(decay, (1 + n) / (10 + n)))")
+    ap.add_argument("--grad_clip", type=float, default=None, metavar="F",
+                    help="clip the global L2 norm of the gradients to F > 0 inside every optimiser step (clip_grad_norm_ "
+                         "ahead of Adam, on the device; default: no clipping)")
+    ap.add_argument("--lr_schedule", type=str, default=None, choices=list(LR_SCHEDULES),
+                    help="learning rate after the warm-up: constant (default), or linear / cosine / poly (power 0.9) decay "
+                         "from --lr to --min_lr over the run's optimiser steps")
+    ap.add_argument("--warmup_steps", type=int, default=None, metavar="N",
+                    help="raise the learning rate linearly over the first N optimiser steps (default 0)")
+    ap.add_argument("--min_lr", type=float, default=None, metavar="F",
+                    help="the learning rate a decaying --lr_schedule ends at, in [0, --lr] (default 0)")
     ap.add_argument("--tile_sampling", type=str, default=None, choices=["all", "labelled", "balanced"],
                     help="--loader scene, train split: which tiles an epoch sees -- all (default), labelled (drop the tiles "
                          "the loss ignores entirely) or balanced (a --water_share of tiles with water)")
@@ -276,6 +314,15 @@ def region_from_args(args) -> dict:
     return dict(region_weight=w, region_alpha=a, region_beta=b, region_smooth=s)
 
 
+def schedule_from_args(args) -> dict:
+    """The lr-schedule options a command line gave, as top-level config keys ({} for none), checked against --lr."""
+    given = {k: getattr(args, k, None) for k in SCHEDULE_OPTIONS}
+    given = {k: v for k, v in given.items() if v is not None}
+    if given:
+        check_schedule(args.lr, given.get("lr_schedule", "constant"), given.get("warmup_steps", 0), given.get("min_lr", 0.0))
+    return given
+
+
 def cfg_from_args(args, class_weights=None) -> dict:
     """The reference-style config of a command line: what fit_model trains with and dumps into the checkpoint.
     class_weights: the resolved numeric weights (the data decides 'balanced' and the class count, so main() resolves them);
@@ -301,6 +348,12 @@ def cfg_from_args(args, class_weights=None) -> dict:
         loss_kwargs["ema_warmup"] = not getattr(args, "no_ema_warmup", False)
     elif getattr(args, "no_ema_warmup", False):
         raise ValueError("--no_ema_warmup needs --ema_decay")
+    if getattr(args, "grad_clip", None) is not None:
+        clip = check_grad_clip(args.grad_clip)
+        if clip is None:
+            raise ValueError("--grad_clip must be > 0 (leave the option out for no clipping)")
+        loss_kwargs["grad_clip_norm"] = clip
+    schedule = schedule_from_args(args)
     sampling = sampling_from_args(args)
     cfg = dict(lr=args.lr, batch_size=args.batch_size, n_epochs=args.n_epochs, crop_height=args.crop[0],
                crop_width=args.crop[1], crop_stride=args.stride, ignore_index=args.ignore_index,
@@ -312,6 +365,7 @@ def cfg_from_args(args, class_weights=None) -> dict:
                                                              precision=args.precision, **loss_kwargs)))
     if sampling:
         cfg["sampling"] = sampling
+    cfg.update(schedule)
     return cfg
 
 

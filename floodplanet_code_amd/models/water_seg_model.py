@@ -18,7 +18,8 @@ every pixel's cross-entropy term times (1 - p[target])^focal_gamma (the focal lo
 one (alpha = beta = 0.5: soft Dice, 1 and 1: soft Jaccard; fu_loss_ce_region, HipUNet.loss); ``ema_decay`` in [0, 1)
 and ``ema_warmup``: an exponential moving average of the weights, updated inside the fused Adam launch, that validation and
 test steps evaluate and that checkpoints carry as the top-level entry ``ema_state_dict`` (state_dict() stays the raw
-weights under the reference's keys).
+weights under the reference's keys); ``grad_clip_norm`` > 0: the global L2 norm of the gradients is clipped to it inside
+every optimiser step (clip_grad_norm_ ahead of Adam, on the device: HipUNet.set_grad_clip).
 """
 from __future__ import annotations
 
@@ -33,7 +34,7 @@ from ..lightning_compat import LightningModule
 from ..metrics import SegmentationMetrics
 from ..ema import check_decay
 from ..loss_options import LossOptions
-from ..unet import HipAdam, HipUNet, check_class_weight, check_label_smoothing
+from ..unet import HipAdam, HipUNet, check_class_weight, check_grad_clip, check_label_smoothing
 
 
 class WaterSegmentationModel(LightningModule):
@@ -41,8 +42,9 @@ class WaterSegmentationModel(LightningModule):
     def __init__(self, in_channels, n_classes, lr, log_image_iter=50, to_rgb_fcn=None, ignore_index=None,
                  optimizer_name='adam', precision='fp32', base_channels=64, class_weights=None, label_smoothing=0.0,
                  ema_decay=None, ema_warmup=True, focal_gamma=0.0, region_weight=0.0, region_alpha=0.5, region_beta=0.5,
-                 region_smooth=1.0):
+                 region_smooth=1.0, grad_clip_norm=None):
         super().__init__()
+        self.grad_clip_norm = check_grad_clip(grad_clip_norm)
         self.n_classes = n_classes
         self.ignore_index = ignore_index
         if self.ignore_index == -1:                      # water_seg_model.py:35-36
@@ -208,9 +210,12 @@ class WaterSegmentationModel(LightningModule):
                 if self.ema_decay is not None:
                     raise NotImplementedError("the weight EMA is part of the fused Adam kernel (HipAdam): FU_TORCH_ADAM=1 "
                                               "together with ema_decay is not supported")
+                if self.grad_clip_norm is not None:
+                    raise NotImplementedError("gradient clipping runs ahead of the fused Adam kernel (HipAdam): FU_TORCH_ADAM=1 "
+                                              "together with grad_clip_norm is not supported")
                 optimizer = optim.Adam(self.parameters(), lr=self.lr)
             else:
-                optimizer = HipAdam(self.model, lr=self.lr)
+                optimizer = HipAdam(self.model, lr=self.lr, max_grad_norm=self.grad_clip_norm)
         else:
             raise NotImplementedError(f'No implementation for optimizer of name: {self.optimizer_name}')
         return optimizer

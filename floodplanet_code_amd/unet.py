@@ -148,6 +148,8 @@ class HipUNet(nn.Module):
         self._ema_p = self._ema_rm = self._ema_rv = None
         self._ema_pending: Optional[dict] = None      # load_ema_state_dict before the module reached its device
         self._ema_swapped = False                     # inside ema_weights(): the context reads the EMA buffers
+        self._grad_clip: Optional[float] = None       # set_grad_clip: max global gradient norm of the optimiser step
+        self._clip_carry = (0.0, 0.0, 0, 0, 0)        # last norm / coefficient and the counters of the contexts before this one
         self._generation = 0          # counts training forwards: an autograd node may only backward the latest one
         self._flat_valid = False
         self._ctx = None
@@ -362,6 +364,8 @@ class HipUNet(nn.Module):
     # ---------------------------------------------------------------- context
     def _destroy_ctx(self):
         if self._ctx is not None:
+            if self._grad_clip is not None:           # the context's clip counters go with it: keep them on the module
+                self._clip_carry = self._read_clip_state()
             _lib.load().fu_destroy(self._ctx)
             self._ctx = None
             self._ctx_key = None
@@ -394,6 +398,8 @@ class HipUNet(nn.Module):
         self._ctx_key = key + (B,)
         self._verify_table()
         self._bind(h)
+        if self._grad_clip is not None:               # the setting belongs to the module: every new context takes it
+            check(lib.fu_set_grad_clip(h, self._grad_clip))
         self._install_exact_sync(device)
         return h
 
@@ -714,6 +720,58 @@ class HipUNet(nn.Module):
                                            float(grad_scale), self._stream(dev)))
         self._eval_dirty = True
 
+    # ---------------------------------------------------------------- gradient clipping
+    def set_grad_clip(self, max_norm: Optional[float]):
+        """Clip the global L2 norm of the gradients to max_norm inside every optimiser step (adam_step / HipAdam.step /
+        DataParallelTrainer.step): torch.nn.utils.clip_grad_norm_(parameters, max_norm) ahead of the update, computed on the
+        device (fu_set_grad_clip) -- the gradient buffer itself is not rescaled.  None or 0 switches it off.  The setting
+        belongs to the module and is re-applied to every context it makes."""
+        max_norm = check_grad_clip(max_norm)
+        self._grad_clip = max_norm
+        if self._ctx is not None:
+            check(_lib.load().fu_set_grad_clip(self._ctx, 0.0 if max_norm is None else max_norm))
+        return self
+
+    @property
+    def grad_clip(self) -> Optional[float]:
+        return self._grad_clip
+
+    def grad_clip_state(self) -> Dict[str, float]:
+        """What the clipped optimiser steps left on the device (fu_grad_clip_state): of the last one grad_norm (the global norm of the
+        gradients as Adam consumed them, before clipping), clip_coef (the factor applied, 1.0 = not clipped), steps,
+        clipped_steps and nonfinite_steps (such a step is skipped).  The counters run on over a change of context (another
+        tile shape, a larger batch); max_norm is the module's setting.  Synchronises the device."""
+        norm, coef, n, k, bad = self._read_clip_state()
+        return {"max_norm": self._grad_clip, "grad_norm": norm, "clip_coef": coef, "steps": n, "clipped_steps": k,
+                "nonfinite_steps": bad}
+
+    def _read_clip_state(self):
+        """(norm, coef, steps, clipped, nonfinite): the current context's state block on top of what earlier contexts left."""
+        norm0, coef0, n0, k0, bad0 = self._clip_carry
+        if self._ctx is None:
+            return self._clip_carry
+        norm, coef = C.c_float(), C.c_float()
+        n, k, bad = C.c_int64(), C.c_int64(), C.c_int64()
+        check(_lib.load().fu_grad_clip_state(self._ctx, C.byref(norm), C.byref(coef), C.byref(n), C.byref(k), C.byref(bad)))
+        if n.value == 0:                              # no clipped step on this context yet: the last one's figures stand
+            return self._clip_carry
+        return norm.value, coef.value, n0 + n.value, k0 + k.value, bad0 + bad.value
+
+    def grad_norms(self, grad_scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(per_parameter, total): the L2 norm of every parameter's gradient, in the order of grad_norm_names(), and of all
+        of them, times |grad_scale| -- device tensors from one pass over the flat gradient buffer (fu_grad_norms); nothing
+        is copied to the host and no optimiser state changes."""
+        if self._ctx is None:
+            raise RuntimeError("HipUNet.grad_norms() before any forward / backward of the module")
+        dev = self._flat.device
+        out = torch.empty(len(self._table) + 1, dtype=torch.float32, device=dev)
+        check(_lib.load().fu_grad_norms(self._ctx, float(grad_scale), ptr(out), self._stream(dev)))
+        return out[:-1], out[-1]
+
+    def grad_norm_names(self) -> List[str]:
+        """The parameter names grad_norms() reports, in its order (the parameter table's)."""
+        return [name for name, _, _, _ in self._table]
+
     def fp16_guard_state(self) -> Tuple[int, int]:
         """(optimiser steps skipped because a gradient was not finite, current loss-scale back-off exponent) -- fp16 mode;
         (0, 0) otherwise.  Synchronises the device."""
@@ -856,6 +914,16 @@ class _UNetLossFn(torch.autograd.Function):
         return _no_grads(_UNetLossFn.forward) + _return_param_grads(m, saved, alias)
 
 
+def check_grad_clip(max_norm) -> Optional[float]:
+    """None / 0 -> None (off); a finite max_norm > 0 -> float; anything else raises."""
+    if max_norm is None:
+        return None
+    v = float(max_norm)
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError(f"the gradient clipping norm must be finite and >= 0, got {max_norm!r}")
+    return v if v > 0.0 else None
+
+
 class HipAdam(torch.optim.Adam):
     """A torch.optim.Adam (isinstance holds; same param_groups / defaults) (water_seg_model.py:198-205: lr, default betas / eps, no weight decay, no amsgrad) whose
     step() is ONE launch of libfloodunet's fused Adam kernel on the module's flat parameter / gradient / moment
@@ -863,12 +931,16 @@ class HipAdam(torch.optim.Adam):
     state_dict() holds {step, exp_avg, exp_avg_sq} per parameter like torch.optim.Adam's, the moments being views of the
     module's flat buffers.  When the module keeps a weight EMA (HipUNet.enable_ema) the step is fu_adam_ema_step, and
     state_dict() carries one more top-level entry "ema" {decay, warmup, params, running_mean, running_var} -- the flat EMA
-    buffers -- so that a reloaded optimiser continues the same average."""
+    buffers -- so that a reloaded optimiser continues the same average.  max_grad_norm: clip the global L2 norm of the
+    gradients to it inside every step() (clip_grad_norm_ ahead of the update, on the device: HipUNet.set_grad_clip)."""
 
-    def __init__(self, net: HipUNet, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
+    def __init__(self, net: HipUNet, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm: Optional[float] = None):
         if not isinstance(net, HipUNet):
             raise TypeError("HipAdam drives a HipUNet's flat buffers")
         super().__init__([p for _, p, _, _ in net._table], lr=lr, betas=betas, eps=eps)
+        if max_grad_norm is not None:                 # clip_grad_norm_(parameters, max_grad_norm) inside every step()
+            net.set_grad_clip(max_grad_norm)
         self._net = net
         self._step = 0
 

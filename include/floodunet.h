@@ -296,6 +296,34 @@ int fu_adam_ema_step(fu_ctx* ctx, double lr, double beta1, double beta2, double 
 int fu_adam_ema_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
                         double ema_weight, float out[8]);
 int fu_adam_ema_step_dev(fu_ctx* ctx, const float* scalars_dev, fu_stream stream);
+/* Global-norm gradient clipping ahead of the optimiser step: torch.nn.utils.clip_grad_norm_(parameters, max_norm) in front
+ * of optimizer.step() (Lightning's gradient_clip_val), without touching the gradient buffer.  max_norm > 0 arms it, 0
+ * disarms it, a negative or non-finite value is an error.  The first arming call builds a chunk table of the parameter
+ * table and a small state block in device memory (so arm before capturing a step).  While armed, every fu_adam_step[_dev] /
+ * fu_adam_ema_step[_dev] first runs two launches on `stream`: one pass over the gradient buffer that writes the sum of
+ * squares of every chunk (at most 16384 floats, never across two tensors) in double, and one workgroup that sums the chunks
+ * of each tensor in chunk order, the tensors in parameter order (fixed orders: the same gradients give the same bits), and
+ * forms, with gscale_in = the step's (float)grad_scale (slot 6 of the scalars):
+ *     N      = sqrt(total) * fabs((double)gscale_in)            the norm of the gradients as Adam consumes them
+ *     finite = isfinite(N)
+ *     coef   = (finite && max_norm / (N + 1e-6) < 1.0) ? (float)(max_norm / (N + 1e-6)) : 1.0f
+ *     scalars[6] = gscale_in * coef                             one fp32 multiply; the other scalars are copied
+ * The Adam launch then reads these scalars from the context's own memory -- the caller's scalars_dev is only read -- so
+ * the update is, bit for bit, the unclipped update with grad_scale = gscale_in * coef.  Skip rule: a step whose N is not
+ * finite is left out entirely (parameters, moments and EMA buffers untouched), in every precision; the flag is rewritten by
+ * every step.  FU_F16: the existing guard decides (fu_fp16_guard_state) -- a non-finite gradient sets both flags together.
+ * With clipping disarmed the step issues exactly the launches it issues without this feature. */
+int fu_set_grad_clip(fu_ctx* ctx, double max_norm);
+/* What the last armed step left behind (synchronises the device, like fu_fp16_guard_state): (float)N, coef, and three
+ * counters -- armed steps seen, steps clipped (coef < 1), steps with a non-finite norm.  All zero when clipping was never
+ * armed on this context.  Any pointer may be NULL. */
+int fu_grad_clip_state(fu_ctx* ctx, float* last_norm, float* last_coef, int64_t* steps, int64_t* clipped_steps,
+                       int64_t* nonfinite_steps);
+/* The gradient norms without a copy to the host: torch.linalg.vector_norm(p.grad) per parameter and of all of them.
+ * norms_out_dev: fu_num_params() + 1 device floats -- every tensor's L2 norm times |grad_scale| in parameter order, then
+ * the total -- from the same two launches (squares and sums in double, rounded to float once).  Works whether or not
+ * clipping is armed (the first call may allocate: do not capture it); changes neither the clip state nor the optimiser. */
+int fu_grad_norms(fu_ctx* ctx, double grad_scale, float* norms_out_dev, fu_stream stream);
 int fu_zero_grads(fu_ctx* ctx, fu_stream stream);
 
 /* ---- exact data-parallel mode (SyncBN statistics + global N_valid) ----------------
