@@ -103,6 +103,11 @@ class FuRegionLoss(C.Structure):
     _fields_ = [("weight", C.c_float), ("alpha", C.c_float), ("beta", C.c_float), ("smooth", C.c_float)]
 
 
+class FuClassThreshold(C.Structure):
+    """fu_class_threshold: the one-class-versus-rest rule of fu_stitch_finalize_maps_ex (a host struct)"""
+    _fields_ = [("cls", C.c_int32), ("threshold", C.c_float)]
+
+
 class FloodUNetError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"libfloodunet error {status}: {message}")
@@ -167,6 +172,9 @@ SIGNATURES = {
     "fu_stitch_add_batch_probs": (_i, [_p, _i, C.POINTER(FuStitchEntry), _p, _i, _p]),
     "fu_stitch_add_batch_windowed": (_i, [_p, _i, C.POINTER(FuStitchEntry), _p, _i, _p, _p, _p]),
     "fu_stitch_finalize_maps": (_i, [_p, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p, _p]),
+    "fu_stitch_finalize_maps_ex": (_i, [_p, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p, C.POINTER(FuClassThreshold), _p]),
+    "fu_eval_prob_hist": (_i, [_p, _p, _i, _i, _p, _p, _p]),
+    "fu_prob_hist": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p, _p]),
     "fu_sieve_workspace_bytes": (_i64, [_i, _i]),
     "fu_map_components": (_i, [_p, _i, _i, _i, _p, _p]),
     "fu_map_sieve": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _i64, _p, _p]),

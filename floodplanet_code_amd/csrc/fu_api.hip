@@ -714,6 +714,14 @@ int fu_stitch_finalize(float* canvas, const float* weight, int n_classes, int ca
 int fu_stitch_finalize_maps(float* canvas, const float* weight, int n_classes, int canvas_h, int canvas_w, float eps,
                             int normalize_in_place, const uint8_t* class_values, uint8_t* class_out, uint8_t* prob_out,
                             uint8_t* margin_out, int64_t* counts_out, fu_stream stream) {
+  return fu_stitch_finalize_maps_ex(canvas, weight, n_classes, canvas_h, canvas_w, eps, normalize_in_place, class_values,
+                                    class_out, prob_out, margin_out, counts_out, nullptr, stream);
+}
+
+// the messages keep fu_stitch_finalize_maps' name as their prefix: it is the forwarder's too
+int fu_stitch_finalize_maps_ex(float* canvas, const float* weight, int n_classes, int canvas_h, int canvas_w, float eps,
+                               int normalize_in_place, const uint8_t* class_values, uint8_t* class_out, uint8_t* prob_out,
+                               uint8_t* margin_out, int64_t* counts_out, const fu_class_threshold* thr, fu_stream stream) {
   FU_REQUIRE(canvas && weight, "fu_stitch_finalize_maps: null canvas / weight");
   FU_REQUIRE(n_classes >= 1 && n_classes <= HEAD_MAX_CLS, "fu_stitch_finalize_maps: n_classes %d not in 1..%d", n_classes,
              HEAD_MAX_CLS);
@@ -721,8 +729,29 @@ int fu_stitch_finalize_maps(float* canvas, const float* weight, int n_classes, i
   FU_REQUIRE(isfinite(eps) && eps >= 0.f, "fu_stitch_finalize_maps: eps %g is negative or not finite", (double)eps);
   FU_REQUIRE(normalize_in_place || class_out || prob_out || margin_out || counts_out,
              "fu_stitch_finalize_maps: no output requested");
+  if (thr) {
+    FU_REQUIRE(n_classes >= 2, "fu_stitch_finalize_maps_ex: a threshold needs at least 2 classes, got %d", n_classes);
+    FU_REQUIRE(thr->cls >= 0 && thr->cls < n_classes, "fu_stitch_finalize_maps_ex: threshold class %d not in 0..%d",
+               (int)thr->cls, n_classes - 1);
+    FU_REQUIRE(isfinite(thr->threshold) && thr->threshold >= 0.f && thr->threshold <= 1.f,
+               "fu_stitch_finalize_maps_ex: threshold %g is not finite or outside [0, 1]", (double)thr->threshold);
+  }
   return launch_stitch_finalize_maps(canvas, weight, n_classes, (int64_t)canvas_h * canvas_w, eps, normalize_in_place != 0,
-                                     class_values, class_out, prob_out, margin_out, counts_out, (hipStream_t)stream);
+                                     class_values, class_out, prob_out, margin_out, counts_out, thr, (hipStream_t)stream);
+}
+
+int fu_eval_prob_hist(fu_ctx* c, const int64_t* target, int ignore_index, int n_bins, int64_t* hist_out, int64_t* top_out,
+                      fu_stream stream) {
+  FU_REQUIRE(c && target, "fu_eval_prob_hist: null context / target");
+  FU_REQUIRE(c->last_batch > 0, "fu_eval_prob_hist: no forward pass yet");
+  return launch_prob_hist("fu_eval_prob_hist", c->logits, true, target, (int64_t)c->last_batch * c->cfg.height * c->cfg.width,
+                          c->cfg.n_classes, ignore_index, n_bins, hist_out, top_out, (hipStream_t)stream);
+}
+
+int fu_prob_hist(const float* probs, const int64_t* target, int64_t n_pixels, int n_classes, int ignore_index, int n_bins,
+                 int64_t* hist_out, int64_t* top_out, fu_stream stream) {
+  return launch_prob_hist("fu_prob_hist", probs, false, target, n_pixels, n_classes, ignore_index, n_bins, hist_out, top_out,
+                          (hipStream_t)stream);
 }
 
 // fu_map_components / fu_map_sieve share these checks; every one comes before anything is launched

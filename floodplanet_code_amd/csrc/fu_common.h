@@ -10,6 +10,7 @@
 struct fu_stitch_entry;
 struct fu_scene_crop;
 struct fu_scene_train_entry;
+struct fu_class_threshold;
 
 namespace fu {
 
@@ -563,10 +564,11 @@ int launch_stitch_add_batch(DeviceTable& table, const char* fn, const char* batc
                             const float* src, int n_samples, bool probs, int H, int W, int ncls, hipStream_t s,
                             const float* win_y = nullptr, const float* win_x = nullptr);
 // fu_stitch_finalize_maps: normalised canvas (in place when normalize), uint8 class map / probability bands / top-2
-// margin and int64 pixels per argmax class (ADDED to) in one pass; every output optional.  class_values: HOST bytes or null
+// margin and int64 pixels per argmax class (ADDED to) in one pass; every output optional.  class_values: HOST bytes or null.
+// thr (fu_stitch_finalize_maps_ex): null = the argmax; else the class map and the counts follow the thresholded decision
 int launch_stitch_finalize_maps(float* canvas, const float* weight, int ncls, int64_t npix, float eps, bool normalize,
                                 const unsigned char* class_values, unsigned char* class_out, unsigned char* prob_out,
-                                unsigned char* margin_out, int64_t* counts, hipStream_t s);
+                                unsigned char* margin_out, int64_t* counts, const fu_class_threshold* thr, hipStream_t s);
 // fu_map_components / fu_map_sieve (fu_post.hip): union-find labelling of a uint8 map (the label of a pixel = the smallest
 // linear index of its component) and the connected-component sieve on top of it; the caller has checked every argument.
 // workspace: sieve_workspace_bytes(h, w) = 16 B per pixel (64-bit donor keys, labels, sizes); stats: int64[2] ADDED to, or null
@@ -576,6 +578,10 @@ int launch_map_sieve(const unsigned char* map, unsigned char* out, int h, int w,
                      int passes, void* workspace, int64_t* stats, hipStream_t s);
 int launch_eval_confusion(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int B, int64_t hw,
                           int64_t* counts, hipStream_t s);
+// fu_eval_prob_hist (logits: src = the resident NHWC logits) / fu_prob_hist (src = fp32 probabilities [npix, ncls]):
+// hist[c][t][bin] and top[argmax == t][bin], both ADDED to, either optional; checks every argument (fn goes into the messages)
+int launch_prob_hist(const char* fn, const float* src, bool logits, const int64_t* target, int64_t npix, int ncls,
+                     int ignore_index, int n_bins, int64_t* hist, int64_t* top, hipStream_t s);
 // fu_merge_views: softmax of each view's logits, inverse view, mean in view order -> probs [B, H, W, k] (optional) and
 // confusion counts of its argmax (optional, with target; ADDED to)
 int launch_merge_views(const float* logits_nhwc, int H, int W, int ncls, int B, int n_views, unsigned codes, float* probs,

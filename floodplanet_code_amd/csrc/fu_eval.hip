@@ -256,6 +256,8 @@ struct FinalizeMaps {
   float eps;
   int normalize;                   // write the normalised canvas back
   unsigned vec;                    // MAPS_VEC_*: the array is aligned for the group's wide access
+  int thr_cls;                     // fu_stitch_finalize_maps_ex: the thresholded class, -1 = the plain argmax
+  float thr;
 };
 
 __device__ __forceinline__ unsigned char quantize_unit(float x) {
@@ -293,6 +295,21 @@ __device__ __forceinline__ bool finalize_pixel(float (&v)[K], float wgt, float e
   return true;
 }
 
+// The decided class of a covered pixel (fu_stitch_finalize_maps_ex): cls when v[cls] >= thr, otherwise the first maximum
+// over the other classes; cls < 0: the argmax as it is.  K >= 2 whenever cls >= 0.
+template <int K>
+__device__ __forceinline__ int decide_class(const float (&v)[K], int am, int cls, float thr) {
+  if (cls < 0) return am;
+  float vc = 0.f, best = -INFINITY;
+  int other = cls == 0 ? 1 : 0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (k == cls) vc = v[k];
+    else if (v[k] > best) { best = v[k]; other = k; }
+  }
+  return vc >= thr ? cls : other;
+}
+
 template <int K>
 __global__ __launch_bounds__(256) void k_stitch_finalize_maps(const FinalizeMaps a) {
   __shared__ unsigned int bins[HEAD_MAX_CLS];
@@ -327,6 +344,7 @@ __global__ __launch_bounds__(256) void k_stitch_finalize_maps(const FinalizeMaps
 #pragma unroll
       for (int k = 0; k < K; ++k) v[k] = c[q * K + k];
       const bool covered = finalize_pixel<K>(v, wq[q], a.eps, am, margin);
+      if (covered) am = decide_class<K>(v, am, a.thr_cls, a.thr);
 #pragma unroll
       for (int k = 0; k < K; ++k) {
         c[q * K + k] = v[k];
@@ -383,6 +401,7 @@ __global__ __launch_bounds__(256) void k_stitch_finalize_maps(const FinalizeMaps
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = a.canvas[p * K + k];
     const bool covered = finalize_pixel<K>(v, a.weight[p], a.eps, am, margin);
+    if (covered) am = decide_class<K>(v, am, a.thr_cls, a.thr);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       if (a.normalize) a.canvas[p * K + k] = v[k];
@@ -400,9 +419,10 @@ __global__ __launch_bounds__(256) void k_stitch_finalize_maps(const FinalizeMaps
 
 int launch_stitch_finalize_maps(float* canvas, const float* weight, int ncls, int64_t npix, float eps, bool normalize,
                                 const unsigned char* class_values, unsigned char* class_out, unsigned char* prob_out,
-                                unsigned char* margin_out, int64_t* counts, hipStream_t s) {
+                                unsigned char* margin_out, int64_t* counts, const fu_class_threshold* thr, hipStream_t s) {
   if (npix <= 0) return 0;
   FinalizeMaps a{};
+  a.thr_cls = thr ? thr->cls : -1, a.thr = thr ? thr->threshold : 0.f;
   a.canvas = canvas, a.weight = weight, a.class_out = class_out, a.prob_out = prob_out, a.margin_out = margin_out;
   a.counts = reinterpret_cast<unsigned long long*>(counts);
   a.npix = npix, a.eps = eps, a.normalize = normalize ? 1 : 0;
@@ -462,6 +482,210 @@ int launch_eval_confusion(const float* logits_nhwc, const int64_t* target, int n
   const dim3 grid(grid_for(hw, 256, 64), B);
   hipLaunchKernelGGL(k_eval_confusion, grid, dim3(256), 0, s, logits_nhwc, target, ncls, ignore_index, hw,
                      reinterpret_cast<unsigned long long*>(counts));
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Probability histogram (fu_eval_prob_hist / fu_prob_hist): hist[c][t][bin(p[c])] and top[argmax == t][bin(p[argmax])] over
+// the pixels k_eval_confusion counts, p = the softmax of the resident logits (e[c] * inv, the product rounded on its own:
+// what fu_merge_views writes for one view of code 0) or the caller's probabilities.  Memory bound -- K floats and one
+// int64 per pixel; a thread takes 4 consecutive pixels with K 16-byte loads between a misaligned head and a tail that go
+// one pixel at a time (as k_stitch_finalize_maps) -- so what has to be kept off the critical path is LDS-atomic
+// contention: flood scenes are saturated, whole waves of pixels fall into one (class, target, bin).  Two measures:
+//   * the block keeps up to 4 histogram copies while they fit PROB_HIST_COPIES_BYTES (4 copies of 11 KB at K = 3, 256
+//     bins) and wave w adds into copy w % copies, so at most 4 of the block's 16 waves ever meet on an address;
+//   * inside a wave, wave_add elects a leader per round: the first pending lane broadcasts its key, the lanes that hold the
+//     same key are found with one ballot, and the leader adds their number in ONE atomic.  Up to PROB_HIST_ROUNDS rounds,
+//     stopping at the first group below PROB_HIST_GROUP_MIN lanes (diffuse data: one wasted single-lane atomic per
+//     class); the lanes still pending then add 1 each, to mostly distinct addresses.
+// Bins are unsigned int in LDS (the grid keeps a block's share of pixels below 2^32); the flush sums the copies and adds
+// the non-zero bins with 64-bit integer atomics, as ConfusionBins::flush: exact, order-free, no finalisation pass.
+// ------------------------------------------------------------------------------------------------
+// 16 waves per block: the grid is capped at one block per CU (the flush below costs a block up to (K * K + 2) * n_bins
+// global atomics, so blocks are few), and a CU needs that many waves to keep its share of the loads in flight
+static constexpr int PROB_HIST_BLOCK = 1024, PROB_HIST_ROUNDS = 4, PROB_HIST_GROUP_MIN = 4;
+static constexpr int PROB_HIST_COPIES_BYTES = 64 * 1024;   // more than one copy only while they fit this much LDS
+
+struct ProbHist {
+  const float* src;               // [npix, K] logits (LOGITS) or probabilities
+  const int64_t* target;          // [npix]
+  unsigned long long* hist;       // [K][K][n_bins] or null, added to
+  unsigned long long* top;        // [2][n_bins] or null, added to
+  int64_t npix, head;             // head: the pixels in front of src's first 16-byte boundary (npix: no wide loads at all)
+  int ignore_index, n_bins, copies;
+};
+
+// the bin rule of include/floodunet.h: s = p * n_bins is exact for a power of two; NaN and p < 1 / n_bins go to bin 0
+__device__ __forceinline__ int prob_bin(float p, int n_bins) {
+  const float s = p * (float)n_bins;
+  return s >= 1.f ? (s >= (float)n_bins ? n_bins - 1 : (int)s) : 0;
+}
+
+// row[key] += 1 for every lane with `valid`, lanes of one key pre-aggregated (see above).  Called by whole waves: the
+// loops around it have wave-uniform trip counts.
+__device__ __forceinline__ void wave_add(unsigned int* row, int key, bool valid) {
+  unsigned long long todo = __ballot(valid);
+  const int lane = (int)(threadIdx.x & 63);
+  for (int r = 0; r < PROB_HIST_ROUNDS && todo; ++r) {
+    const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+    const int lk = __builtin_amdgcn_readlane(key, leader);
+    const unsigned long long same = __ballot(valid && key == lk) & todo;
+    const int n = __popcll(same);
+    if (lane == leader) atomicAdd(&row[lk], (unsigned int)n);
+    todo &= ~same;
+    if (n < PROB_HIST_GROUP_MIN) break;
+  }
+  if ((todo >> lane) & 1ull) atomicAdd(&row[key], 1u);
+}
+
+// one pixel per lane: z = its K logits or probabilities, t = its target (anything invalid for a lane without a pixel)
+template <int K, bool LOGITS>
+__device__ __forceinline__ void prob_hist_pixel(unsigned int* bins, const float (&z)[K], int64_t t, const ProbHist& a) {
+#pragma clang fp contract(off)
+  const bool valid = t != (int64_t)a.ignore_index && t >= 0 && t < K;
+  float p[K];
+  if constexpr (LOGITS) {
+    float e[HEAD_MAX_CLS], inv;
+    softmax_terms(z, K, e, inv);
+#pragma unroll
+    for (int c = 0; c < K; ++c) p[c] = e[c] * inv;
+  } else {
+#pragma unroll
+    for (int c = 0; c < K; ++c) p[c] = z[c];
+  }
+  const int nb = a.n_bins, tt = valid ? (int)t : 0;
+  if (a.hist) {
+#pragma unroll
+    for (int c = 0; c < K; ++c) wave_add(bins + c * K * nb, tt * nb + prob_bin(p[c], nb), valid);
+  }
+  if (a.top) {
+    float pm = -INFINITY;
+    int am = 0;
+#pragma unroll
+    for (int c = 0; c < K; ++c) if (p[c] > pm) { pm = p[c]; am = c; }
+    wave_add(bins + K * K * nb, (am == tt ? nb : 0) + prob_bin(pm, nb), valid);
+  }
+}
+
+template <int K, bool LOGITS>
+__global__ __launch_bounds__(PROB_HIST_BLOCK) void k_prob_hist(const ProbHist a) {
+  extern __shared__ unsigned int prob_hist_lds[];
+  const int per = (K * K + 2) * a.n_bins;
+  for (int i = threadIdx.x; i < per * a.copies; i += PROB_HIST_BLOCK) prob_hist_lds[i] = 0;
+  __syncthreads();
+  unsigned int* bins = prob_hist_lds + (int)((threadIdx.x >> 6) % (unsigned)a.copies) * per;
+  const int64_t nthr = (int64_t)gridDim.x * PROB_HIST_BLOCK;
+  const int64_t nvec = (a.npix - a.head) / 4;
+  for (int64_t j0 = (int64_t)blockIdx.x * PROB_HIST_BLOCK; j0 < nvec; j0 += nthr) {   // uniform trips: wave_add ballots
+    const int64_t j = j0 + threadIdx.x;
+    const bool in = j < nvec;
+    float c[4 * K];
+    int64_t t[4];
+    if (in) {
+      const int64_t p = a.head + 4 * j;
+#pragma unroll
+      for (int i = 0; i < K; ++i) {
+        const float4 v = reinterpret_cast<const float4*>(a.src + p * K)[i];
+        c[4 * i] = v.x, c[4 * i + 1] = v.y, c[4 * i + 2] = v.z, c[4 * i + 3] = v.w;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) t[q] = a.target[p + q];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4 * K; ++i) c[i] = 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) t[q] = -1;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float z[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) z[k] = c[q * K + k];
+      prob_hist_pixel<K, LOGITS>(bins, z, t[q], a);
+    }
+  }
+  const int64_t tail0 = a.head + 4 * nvec, nrest = a.head + (a.npix - tail0);   // misaligned head and tail: plain code
+  for (int64_t r0 = (int64_t)blockIdx.x * PROB_HIST_BLOCK; r0 < nrest; r0 += nthr) {
+    const int64_t r = r0 + threadIdx.x;
+    float z[K];
+    int64_t t = -1;
+#pragma unroll
+    for (int k = 0; k < K; ++k) z[k] = 0.f;
+    if (r < nrest) {
+      const int64_t p = r < a.head ? r : tail0 + (r - a.head);
+#pragma unroll
+      for (int k = 0; k < K; ++k) z[k] = a.src[p * K + k];
+      t = a.target[p];
+    }
+    prob_hist_pixel<K, LOGITS>(bins, z, t, a);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < per; i += PROB_HIST_BLOCK) {
+    unsigned long long n = 0;
+    for (int cp = 0; cp < a.copies; ++cp) n += prob_hist_lds[cp * per + i];
+    if (!n) continue;
+    const int ih = K * K * a.n_bins;
+    if (i < ih) {
+      if (a.hist) atomicAdd(&a.hist[i], n);
+    } else if (a.top) {
+      atomicAdd(&a.top[i - ih], n);
+    }
+  }
+}
+
+// fu_eval_prob_hist (logits == true: src = the resident NHWC logits) and fu_prob_hist: every check comes before anything
+// is launched, so a rejected call leaves the outputs untouched
+int launch_prob_hist(const char* fn, const float* src, bool logits, const int64_t* target, int64_t npix, int ncls,
+                     int ignore_index, int n_bins, int64_t* hist, int64_t* top, hipStream_t s) {
+  FU_REQUIRE(src && target, "%s: null %s / target", fn, logits ? "logits" : "probs");
+  FU_REQUIRE(hist || top, "%s: nothing to write (hist_out and top_out are both null)", fn);
+  FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "%s: n_classes %d not in 1..%d", fn, ncls, HEAD_MAX_CLS);
+  FU_REQUIRE(n_bins >= 2 && n_bins <= 1024 && (n_bins & (n_bins - 1)) == 0, "%s: n_bins %d is not a power of two in 2..1024",
+             fn, n_bins);
+  FU_REQUIRE(npix >= 1, "%s: n_pixels %lld < 1", fn, (long long)npix);
+  const int64_t copy_bytes = (int64_t)(ncls * ncls + 2) * n_bins * 4;
+  FU_REQUIRE(copy_bytes <= FU_PROB_HIST_LDS_BYTES, "%s: %d classes x %d bins need %lld bytes of LDS, more than the %d reserved",
+             fn, ncls, n_bins, (long long)copy_bytes, FU_PROB_HIST_LDS_BYTES);
+  const uintptr_t sa = reinterpret_cast<uintptr_t>(src);
+  FU_REQUIRE(sa % 4 == 0 && reinterpret_cast<uintptr_t>(target) % 8 == 0, "%s: misaligned %s / target", fn,
+             logits ? "logits" : "probs");
+  ProbHist a{};
+  a.src = src, a.target = target, a.npix = npix, a.ignore_index = ignore_index, a.n_bins = n_bins;
+  a.hist = reinterpret_cast<unsigned long long*>(hist), a.top = reinterpret_cast<unsigned long long*>(top);
+  a.head = npix;   // the first pixel at a 16-byte boundary, if the stride of ncls floats ever reaches one
+  for (int h = 0; h < 4; ++h)
+    if ((sa + (uintptr_t)h * ncls * 4) % 16 == 0) { a.head = std::min<int64_t>(npix, h); break; }
+  a.copies = 4 * copy_bytes <= PROB_HIST_COPIES_BYTES ? 4 : 2 * copy_bytes <= PROB_HIST_COPIES_BYTES ? 2 : 1;
+  const size_t lds = (size_t)(a.copies * copy_bytes);
+  // one block per CU at most (the flush costs a block up to (k * k + 2) * n_bins global atomics), and enough blocks
+  // that a block's share of pixels -- the most one unsigned int bin can receive -- stays below 2^32
+  const int grid = (int)std::max<int64_t>(grid_for(ceil_div64(npix, 4), PROB_HIST_BLOCK, 256), ceil_div64(npix, (int64_t)1 << 31));
+  const void* fn_ptr = nullptr;
+  switch (ncls) {
+#define FU_HIST_CASE(K) case K: fn_ptr = logits ? (const void*)k_prob_hist<K, true> : (const void*)k_prob_hist<K, false>; break;
+    FU_HIST_CASE(1) FU_HIST_CASE(2) FU_HIST_CASE(3) FU_HIST_CASE(4) FU_HIST_CASE(5) FU_HIST_CASE(6) FU_HIST_CASE(7)
+    FU_HIST_CASE(8)
+#undef FU_HIST_CASE
+  }
+  if (lds > 64 * 1024) {   // one copy above the default dynamic-LDS window: the device must have it, and the kernel opts in
+    int dev = 0, have = 0;
+    FU_REQUIRE(hipGetDevice(&dev) == hipSuccess &&
+               hipDeviceGetAttribute(&have, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && (size_t)have >= lds,
+               "%s: %d classes x %d bins need %zu bytes of LDS, the device offers %d per block", fn, ncls, n_bins, lds, have);
+    FU_REQUIRE(hipFuncSetAttribute(fn_ptr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
+               "%s: the device refuses %zu bytes of dynamic LDS", fn, lds);
+  }
+  switch (ncls) {
+#define FU_HIST_CASE(K)                                                                                              \
+  case K:                                                                                                            \
+    if (logits) hipLaunchKernelGGL((k_prob_hist<K, true>), dim3(grid), dim3(PROB_HIST_BLOCK), lds, s, a);            \
+    else hipLaunchKernelGGL((k_prob_hist<K, false>), dim3(grid), dim3(PROB_HIST_BLOCK), lds, s, a);                  \
+    break;
+    FU_HIST_CASE(1) FU_HIST_CASE(2) FU_HIST_CASE(3) FU_HIST_CASE(4) FU_HIST_CASE(5) FU_HIST_CASE(6) FU_HIST_CASE(7)
+    FU_HIST_CASE(8)
+#undef FU_HIST_CASE
+  }
   FU_LAUNCH_CHECK();
   return 0;
 }

@@ -31,6 +31,11 @@ else the parent directory.  What runs differently:
     neighbouring patch (postprocess.sieve_host is the rule; --sieve_connectivity 4|8, --sieve_passes P), on the device,
     between the finalisation and the scene's one device-to-host read, which also carries the two counts of what changed.
     Only the written class map is sieved: class_pixels, the probability and the margin raster stay what the network said.
+  * extension: --water_threshold T [--threshold_class C] replaces the argmax by a one-versus-rest rule -- class C (default
+    1, water) where its stitched probability is >= T, else the best of the other classes -- inside the finalisation launch
+    (fu_stitch_finalize_maps_ex); --calibration FILE takes C and T from the calibration.json of predict --calibrate.
+    class_pixels follows the rule, the sieve runs on the thresholded map, the probability and margin rasters do not
+    change; the summary records the rule under "threshold".
 Out of scope: multi-GPU inference, inputs besides ms_image (dem, slope, hand, preflood), RGB outputs, BigTIFF or
 compressed output.
 """
@@ -208,6 +213,27 @@ class SceneFiles(torch.utils.data.Dataset):
                 "index": i}
 
 
+def threshold_rule(water_threshold: Optional[float] = None, threshold_class: Optional[int] = None,
+                   calibration: Optional[str] = None) -> Optional[dict]:
+    """The decision rule the options ask for -> None (the argmax) or {"class", "threshold", "source"}.  Host only; raises
+    on contradictory options: a threshold together with a calibration file, a class without a threshold."""
+    from .calibration import check_threshold, read_calibration
+    if calibration is not None:
+        if water_threshold is not None or threshold_class is not None:
+            raise ValueError("infer: --calibration already names the class and the threshold; it excludes "
+                             "--water_threshold and --threshold_class")
+        cls, thr = read_calibration(calibration)
+        source = str(calibration)
+    elif water_threshold is not None:
+        cls, thr, source = (1 if threshold_class is None else threshold_class), water_threshold, "option"
+    elif threshold_class is not None:
+        raise ValueError("infer: --threshold_class needs --water_threshold")
+    else:
+        return None
+    cls, thr = check_threshold(thr, cls)
+    return {"class": cls, "threshold": thr, "source": source}
+
+
 def check_model_inputs(cfg: dict, norm_params=None) -> None:
     """infer feeds the model ms_image only: reject configs whose model also takes dem / slope / ... (before any GPU work).
     norm_mode 'global' is accepted only together with its parameters."""
@@ -227,7 +253,8 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
           batch_size: Optional[int] = None, tta=None, n_workers: int = 0, device: str = "cuda:0",
           keep_probabilities: bool = False, norm_params=None, weights: str = "auto", blend: str = "uniform",
           write_probs: Optional[str] = None, write_margin: bool = False, sieve: Optional[int] = None,
-          sieve_connectivity: int = 4, sieve_passes: int = 1) -> dict:
+          sieve_connectivity: int = 4, sieve_passes: int = 1, water_threshold: Optional[float] = None,
+          threshold_class: Optional[int] = None, calibration: Optional[str] = None) -> dict:
     """Class maps of every input scene (see the module docstring).  cfg: the resolved config (default: resolve_cfg of
     the checkpoint's experiment).  Returns the summary.json dict; with keep_probabilities also "probabilities"
     {output path: fp32 [H, W, k] stitched canvas} (one more host read per scene; for tests and comparisons).
@@ -236,7 +263,9 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     (predict.checkpoint_weights); the summary records the choice made under "weights".  blend: "uniform", "linear" or
     "hann" (stitch.blend_window); write_probs: None, "u8" or "f32"; write_margin: also write the top-2 margin raster.
     sieve: None, or the minimum patch size in pixels of the written class map (postprocess.sieve on the device, with
-    sieve_connectivity 4 or 8 and sieve_passes 1..8); class_pixels and the other rasters stay un-sieved."""
+    sieve_connectivity 4 or 8 and sieve_passes 1..8); class_pixels and the other rasters stay un-sieved.
+    water_threshold / threshold_class / calibration: the one-versus-rest decision rule (threshold_rule) in place of the
+    argmax; the summary records it under "threshold"."""
     from .datasets.floodplanet import _N_CHANNELS
     from .models import build_model
 
@@ -247,6 +276,7 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
         raise ValueError(f"blend must be one of {list(BLEND_KINDS)}, got {blend!r}")
     if write_probs is not None and write_probs not in PROB_FORMATS:
         raise ValueError(f"write_probs must be one of {list(PROB_FORMATS)} or None, got {write_probs!r}")
+    rule = threshold_rule(water_threshold, threshold_class, calibration)
     sieve_opts = None
     if sieve is not None:
         check_sieve_options(sieve, sieve_connectivity, sieve_passes)
@@ -297,6 +327,8 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     model = model.to(dev)
     net = model.model
     k = net.n_classes
+    if rule is not None and rule["class"] >= k:
+        raise ValueError(f"infer: threshold class {rule['class']} not in 0..{k - 1}")
     T = len(codes) if codes is not None else 1
     net._get_ctx(dev, T * bs, ch, cw)                    # the context owns fu_scene_crops' table: make it at full size
     stitcher = GpuImageStitcher(net, dev, blend=blend)
@@ -327,7 +359,8 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
         sc = resident.pop(i)
         H, W = sc["hw"]
         key = str(i)
-        maps = stitcher.combine_maps(key, class_values, probs=write_probs == "u8", margin=write_margin, counts=True)
+        maps = stitcher.combine_maps(key, class_values, probs=write_probs == "u8", margin=write_margin, counts=True,
+                                     threshold=None if rule is None else (rule["class"], rule["threshold"]))
         if sieve_opts is not None:                       # in place, on the stream of the launch above; no host read
             _, sieve_stats = sieve_map(maps["class"], sieve_opts["min_pixels"], sieve_opts["connectivity"],
                                        passes=sieve_opts["passes"], out=maps["class"])
@@ -400,6 +433,8 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
                "crops_per_s": n_crops / seconds if seconds > 0 else None, "max_resident_scenes": max_resident,
                "tta": tta if (tta is None or isinstance(tta, str)) else list(codes), "weights": chosen,
                "blend": blend, "stride": stride}
+    if rule is not None:
+        summary["threshold"] = rule
     if sieve_opts is not None:
         summary["sieve"] = dict(sieve_opts, merged_components=sum(r["sieve"]["merged_components"] for r in records),
                                 changed_pixels=sum(r["sieve"]["changed_pixels"] for r in records))
@@ -439,6 +474,14 @@ def build_parser() -> argparse.ArgumentParser:
                     help="neighbours that join pixels of one class into a patch (default 4)")
     ap.add_argument("--sieve_passes", type=int, default=1, choices=list(range(1, 9)),
                     help="apply the sieve this many times, each on the previous result (default 1)")
+    ap.add_argument("--water_threshold", type=float, default=None, metavar="T",
+                    help="declare the threshold class where its stitched probability is >= T (in [0, 1]), else the best of "
+                         "the other classes, instead of the argmax (default: the argmax)")
+    ap.add_argument("--threshold_class", type=int, default=None, metavar="C",
+                    help="the class --water_threshold applies to (default 1, water)")
+    ap.add_argument("--calibration", type=str, default=None, metavar="FILE",
+                    help="take the class and its best-F1 threshold from a calibration.json written by predict --calibrate "
+                         "(excludes --water_threshold / --threshold_class)")
     ap.add_argument("--batch_size", type=int, default=None, help="crops per eval forward (default: the config's)")
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips / rotations")
@@ -455,13 +498,15 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv: Optional[List[str]] = None) -> None:
     args = build_parser().parse_args(argv)
+    threshold_rule(args.water_threshold, args.threshold_class, args.calibration)   # option errors before anything is read
     experiment_dir = "/".join(args.checkpoint_path.split("/")[:-2])
     cfg = resolve_cfg(experiment_dir, args.checkpoint_path)
     out = infer(args.checkpoint_path, args.inputs, args.out_dir, cfg=cfg, size=args.size, scale=args.scale,
                 stride=args.stride, batch_size=args.batch_size, tta=args.tta, n_workers=args.n_workers,
                 device=args.device, norm_params=args.norm_params, weights=args.weights, blend=args.blend,
                 write_probs=args.write_probs, write_margin=args.write_margin, sieve=args.sieve,
-                sieve_connectivity=args.sieve_connectivity, sieve_passes=args.sieve_passes)
+                sieve_connectivity=args.sieve_connectivity, sieve_passes=args.sieve_passes,
+                water_threshold=args.water_threshold, threshold_class=args.threshold_class, calibration=args.calibration)
     print(json.dumps({k: v for k, v in out.items() if k != "scenes"}))
 
 

@@ -24,6 +24,11 @@ the averaged probabilities and their confusion counts, one fu_stitch_add_batch_p
 Extension: --weights {auto,raw,ema} chooses between the checkpoint's state_dict and the weight EMA a run with --ema_decay
 stored beside it as ema_state_dict (auto: the EMA when there is one); metrics.json records the choice under "weights"
 whenever the EMA was served or a choice was given (absent: the state_dict, as always).
+Extension: --calibrate [CLS] (default 1, water) accumulates the histogram of class probability against target class over
+the crops (HipUNet.prob_histogram: one more launch per batch beside the confusion counts, each crop once; with --tta on
+the merged probabilities) and writes calibration.json beside metrics.json: the one-versus-rest threshold sweep of CLS,
+its best-F1 / best-IoU thresholds, average precision and the expected calibration error (calibration.report).
+infer --calibration applies the threshold.  Without the flag nothing new is launched or written.
 Out of scope: rgb.png, gt.png and rgb_cm.gif (to_RGB and a GIF encoder), infer.py, multi-GPU prediction, datasets other
 than floodplanet.
 """
@@ -198,7 +203,7 @@ def conf_matrix_image(pred: np.ndarray, target: np.ndarray) -> np.ndarray:
 # ---------------------------------------------------------------------------------------------------------- predict
 def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_images=False, eval_region=None,
             eval_dataset_split="test", n_workers=0, *, data_root, batch_size=None, device="cuda:0", tta=None,
-            weights="auto", blend="uniform") -> dict:
+            weights="auto", blend="uniform", calibrate=None, calibrate_bins=256) -> dict:
     """predict.py:129-400 with batched crops.  Returns {"pred_dir", "metrics", "image_stats_f1", "image_stats_iou",
     "region_stats_f1", "region_stats_iou", "probabilities"} (probabilities: {region/image: [H, W, k] float32} of the
     stitched canvases when predict_images, else {}).  tta: None, a tta.VIEW_SETS name or a list of view codes; with it,
@@ -206,7 +211,9 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
     samples per forward: lower batch_size when that does not fit.  weights: 'auto', 'raw' or 'ema' (checkpoint_weights);
     metrics.json records the choice under "weights" when the EMA was served or weights is not 'auto'.  blend: "uniform",
     "linear" or "hann" (stitch.blend_window) -- how overlapping crops are averaged in the stitched images; the per-crop
-    metrics come from the crops and do not depend on it.  metrics.json records a blend other than "uniform"."""
+    metrics come from the crops and do not depend on it.  metrics.json records a blend other than "uniform".
+    calibrate: None, or the class whose threshold sweep goes to <pred_dir>/calibration.json (calibration.report over
+    calibrate_bins bins); the result then also holds "best_threshold" and "best_f1"."""
     from .datasets import FloodplanetTiles, TileLoader, generate_image_slice_object
     from .datasets.synthetic import write_strip_tiff
     from .models import build_model
@@ -217,6 +224,11 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
         raise ValueError(f"weights must be one of {list(WEIGHT_CHOICES)}, got {weights!r}")
     if blend not in BLEND_KINDS:
         raise ValueError(f"blend must be one of {list(BLEND_KINDS)}, got {blend!r}")
+    if calibrate is not None:            # checked before any GPU work
+        from .calibration import check_bins
+        calibrate, calibrate_bins = int(calibrate), check_bins(calibrate_bins)
+        if calibrate < 0:
+            raise ValueError(f"calibrate: class {calibrate} is negative")
     if eval_dataset_name != "floodplanet":
         raise NotImplementedError(f'prediction supports the "floodplanet" dataset only, not "{eval_dataset_name}"')
     slice_params = generate_image_slice_object(cfg["crop_height"], cfg["crop_width"], cfg["crop_stride"])
@@ -240,6 +252,8 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
                         **model_kwargs)
     model, chosen = load_checkpoint_model(model, checkpoint_path, weights, in_channels=dataset.n_channels,
                                           n_classes=dataset.n_classes, lr=cfg["lr"], **model_kwargs)
+    if calibrate is not None and calibrate >= dataset.n_classes:
+        raise ValueError(f"calibrate: class {calibrate} not in 0..{dataset.n_classes - 1}")
     model._set_model_to_eval()
     model = model.to(dev)
     net = model.model
@@ -256,6 +270,7 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
     where: Dict[str, tuple] = {}         # canvas key -> (region, image name)
     loader = TileLoader(dataset, batch_size or cfg["batch_size"], dev, shuffle=False, num_workers=n_workers,
                         ignore_index=cfg["ignore_index"], device_assembly=True, device_resize=True)
+    hist = top = None                    # calibrate: int64 device accumulators, read once at the end
     with torch.no_grad():
         for batch in loader:
             probs = None
@@ -264,7 +279,11 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
                 counts = net.eval_confusion(batch["target"], ignore)          # [B, k, k], one launch
             else:                                                             # one T*B forward, one merge launch
                 net.forward_views(model._gather_sources(batch), codes)
-                probs, counts = net.merge_views(batch["target"], ignore, want_probs=predict_images)
+                probs, counts = net.merge_views(batch["target"], ignore,
+                                                want_probs=predict_images or calibrate is not None)
+            if calibrate is not None:                                         # one launch, no host read
+                h, t = net.prob_histogram(batch["target"], ignore, calibrate_bins, probs=probs)
+                hist, top = (h, t) if hist is None else (hist + h, top + t)
             metrics.accumulate_counts(counts)                                 # each crop once (see module docstring)
             per_crop = metrics.reduce_batch(counts)
             vals = torch.stack([per_crop[f"{metrics.prefix}MulticlassF1Score"],
@@ -317,7 +336,18 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
             json.dump(all_metrics, fh, indent=4)
         write_ranked_files(pred_dir, image_f1, image_iou, region_f1, region_iou)
 
-    return {"pred_dir": pred_dir, "metrics": all_metrics, "image_stats_f1": dict(image_f1),
+    extra = {}
+    if calibrate is not None:
+        from .calibration import report
+        if hist is None:
+            raise ValueError("calibrate: the data set has no crops")
+        rep = report(hist.cpu().numpy(), top.cpu().numpy(), calibrate, confusion=metrics.confusion().cpu().numpy())
+        if codes is not None:
+            rep["tta"] = tta if isinstance(tta, str) else list(codes)
+        with open(os.path.join(pred_dir, "calibration.json"), "w") as fh:
+            json.dump(rep, fh)
+        extra = {"best_threshold": rep["best_threshold"], "best_f1": rep["best_f1"]}
+    return {**extra, "pred_dir": pred_dir, "metrics": all_metrics, "image_stats_f1": dict(image_f1),
             "image_stats_iou": dict(image_iou), "region_stats_f1": dict(region_f1), "region_stats_iou": dict(region_iou),
             "probabilities": probabilities}
 
@@ -348,11 +378,22 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--norm_params", type=str, default=None,
                     help="parameter file of norm_mode 'global' (config key norm_params; "
                          "python -m floodplanet_code_amd.datasets.stats writes it)")
+    ap.add_argument("--calibrate", type=int, nargs="?", const=1, default=None, metavar="CLS",
+                    help="also write calibration.json: the threshold sweep (precision / recall / F1 / IoU per threshold), "
+                         "best thresholds, average precision and calibration error of class CLS against the rest "
+                         "(default 1, water), from a probability histogram accumulated over the crops on the device")
+    ap.add_argument("--calibrate_bins", type=int, default=256,
+                    help="histogram bins of --calibrate, a power of two in 2..1024 (default 256)")
     return ap
 
 
 def main(argv: Optional[List[str]] = None) -> None:
     args = build_parser().parse_args(argv)
+    if args.calibrate is not None:       # option errors before anything is read
+        from .calibration import check_bins
+        check_bins(args.calibrate_bins)
+        if args.calibrate < 0:
+            raise ValueError(f"calibrate: class {args.calibrate} is negative")
     experiment_dir = "/".join(args.checkpoint_path.split("/")[:-2])
     cfg = resolve_cfg(experiment_dir, args.checkpoint_path)
     name = args.eval_dataset_name if args.eval_dataset_name is not None else cfg["dataset"]["name"]
@@ -362,7 +403,7 @@ def main(argv: Optional[List[str]] = None) -> None:
     out = predict(cfg, experiment_dir, args.checkpoint_path, eval_dataset_name=name, predict_images=args.predict_images,
                   eval_region=args.eval_region, eval_dataset_split=args.eval_dataset_split, n_workers=n_workers,
                   data_root=args.data_root, batch_size=args.batch_size, device=args.device, tta=args.tta,
-                  weights=args.weights, blend=args.blend)
+                  weights=args.weights, blend=args.blend, calibrate=args.calibrate, calibrate_bins=args.calibrate_bins)
     print(json.dumps({"pred_dir": out["pred_dir"], **out["metrics"]}))
 
 

@@ -134,14 +134,17 @@ class GpuImageStitcher:
         return cv, am
 
     def combine_maps(self, image_name: str, class_values: Optional[Sequence[int]] = None, probs: bool = False,
-                     margin: bool = False, counts: bool = False) -> dict:
+                     margin: bool = False, counts: bool = False,
+                     threshold: Optional[Tuple[int, float]] = None) -> dict:
         """The fused finalisation (fu_stitch_finalize_maps), one launch: the canvas is normalised in place -- by
         (weight + 1e-5) under "uniform" as combine() does, by the weight alone otherwise (the windows are strictly
         positive; 1e-5 would bias a corner pixel whose only weight is of that order) -- and the uint8 rasters come out
         of the same pass.  -> {"canvas": fp32 [H, W, k], "class": uint8 [H, W] = class_values[argmax] (None: the argmax
         itself), and when asked for "probs": uint8 [k, H, W] = rint(clip(p, 0, 1) * 255), "margin": uint8 [H, W] = the same
         of top-1 minus top-2, "counts": int64 [k] pixels per argmax class}, all on the device.  Call it once per image,
-        instead of combine()."""
+        instead of combine().  threshold=(cls, T): the class map and the counts follow the one-versus-rest rule of
+        fu_stitch_finalize_maps_ex instead of the argmax -- cls where its normalised probability is >= T, else the
+        first maximum over the other classes; the other outputs do not change."""
         cv, wt = self.image_canvas[image_name], self.weight_canvas[image_name]
         H, W, k = cv.shape
         if class_values is not None:
@@ -156,9 +159,13 @@ class GpuImageStitcher:
         if counts:
             out["counts"] = torch.zeros(k, dtype=torch.int64, device=self.device)
         eps = 1e-5 if self.blend == "uniform" else 0.0
-        check(_lib.load().fu_stitch_finalize_maps(ptr(cv), ptr(wt), k, H, W, eps, 1, class_values, ptr(out["class"]),
-                                                  ptr(out.get("probs")), ptr(out.get("margin")), ptr(out.get("counts")),
-                                                  torch.cuda.current_stream(self.device).cuda_stream))
+        thr = None
+        if threshold is not None:
+            from .calibration import check_threshold
+            thr = _lib.FuClassThreshold(*check_threshold(threshold[1], threshold[0], k))
+        check(_lib.load().fu_stitch_finalize_maps_ex(ptr(cv), ptr(wt), k, H, W, eps, 1, class_values, ptr(out["class"]),
+                                                     ptr(out.get("probs")), ptr(out.get("margin")), ptr(out.get("counts")),
+                                                     thr, torch.cuda.current_stream(self.device).cuda_stream))
         return out
 
     def drop(self, image_name: str) -> None:

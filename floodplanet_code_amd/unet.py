@@ -606,6 +606,44 @@ class HipUNet(nn.Module):
                                             self._stream(target.device)))
         return counts
 
+    def prob_histogram(self, target: torch.Tensor, ignore_index: int, n_bins: int = 256, probs=None):
+        """Histogram of class probability against target class (calibration.py; include/floodunet.h has the bin rule):
+        -> (hist int64 [k, k, n_bins], top int64 [2, n_bins]) on the device, no host sync, one launch.  probs=None: the
+        softmax of the last forward's resident logits, all samples of that batch (fu_eval_prob_hist; target
+        [last batch, H, W]).  probs: contiguous fp32 [..., k] on the device, e.g. merge_views' output, with target of its
+        leading shape (fu_prob_hist).  Ignored / out-of-range targets are dropped as in eval_confusion."""
+        from .calibration import check_bins
+        n_bins = check_bins(n_bins)
+        k = self.n_classes
+        lib = _lib.load()
+        if probs is None:
+            B = self._last_batch
+            if self._ctx is None or B == 0:
+                raise RuntimeError("prob_histogram: no forward pass yet")
+            H, W = self._ctx_key[1], self._ctx_key[2]
+            target = target.contiguous().long()
+            if tuple(target.shape) != (B, H, W):
+                raise ValueError(f"prob_histogram: target must be [{B}, {H}, {W}] like the last forward, got "
+                                 f"{tuple(target.shape)}")
+        else:
+            if probs.dim() < 2 or probs.shape[-1] != k or probs.dtype != torch.float32 or not probs.is_contiguous() \
+                    or not probs.is_cuda:
+                raise ValueError(f"prob_histogram: probs must be contiguous fp32 [..., {k}] on the GPU, got "
+                                 f"{tuple(probs.shape)} {probs.dtype} on {probs.device}")
+            target = target.contiguous().long()
+            if tuple(target.shape) != tuple(probs.shape[:-1]) or target.device != probs.device or target.numel() == 0:
+                raise ValueError(f"prob_histogram: target must be {tuple(probs.shape[:-1])} on {probs.device} and not empty, "
+                                 f"got {tuple(target.shape)} on {target.device}")
+        hist = torch.zeros(k, k, n_bins, dtype=torch.int64, device=target.device)
+        top = torch.zeros(2, n_bins, dtype=torch.int64, device=target.device)
+        if probs is None:
+            check(lib.fu_eval_prob_hist(self._ctx, ptr(target), int(ignore_index), n_bins, ptr(hist), ptr(top),
+                                        self._stream(target.device)))
+        else:
+            check(lib.fu_prob_hist(ptr(probs), ptr(target), target.numel(), k, int(ignore_index), n_bins, ptr(hist),
+                                   ptr(top), self._stream(target.device)))
+        return hist, top
+
     # ---------------------------------------------------------------- test-time augmentation
     def forward_views(self, x, codes, want_logits: bool = False) -> Optional[torch.Tensor]:
         """Eval forward of the T views `codes` (a tta.VIEW_SETS name or a list of view codes) of the B crops x (a tensor

@@ -577,6 +577,17 @@ int fu_stitch_finalize_maps(float* canvas, const float* weight, int n_classes, i
                             int normalize_in_place, const uint8_t* class_values, uint8_t* class_out, uint8_t* prob_out,
                             uint8_t* margin_out, int64_t* counts_out, fu_stream stream);
 
+/* fu_stitch_finalize_maps with a one-class-versus-rest decision rule.  thr == NULL: fu_stitch_finalize_maps bit for bit
+ * (which forwards here).  Otherwise the decided class index of a covered pixel is thr->cls when v[thr->cls] >=
+ * thr->threshold (v the normalised values above, compared in fp32), and when it is not, the first maximum over the classes
+ * other than thr->cls.  class_out (= class_values[decided]) and counts_out follow the decided class; the normalised canvas,
+ * prob_out, margin_out (still top-1 minus top-2 of v) and the uncovered-pixel rule are unchanged.  Rejected, launching
+ * nothing: n_classes < 2, cls outside [0, n_classes), a threshold that is not finite or lies outside [0, 1]. */
+typedef struct fu_class_threshold { int32_t cls; float threshold; } fu_class_threshold;
+int fu_stitch_finalize_maps_ex(float* canvas, const float* weight, int n_classes, int canvas_h, int canvas_w, float eps,
+                               int normalize_in_place, const uint8_t* class_values, uint8_t* class_out, uint8_t* prob_out,
+                               uint8_t* margin_out, int64_t* counts_out, const fu_class_threshold* thr, fu_stream stream);
+
 /* ---- class-map post-processing (fu_post.hip); no context needed --------------------------------- */
 #define FU_MAP_MAX_PIXELS (1 << 28)
 /* Connected components of a uint8 map [h, w] on the device: a component is a maximal set of pixels of equal value joined
@@ -605,6 +616,37 @@ int fu_map_sieve(const uint8_t* map, uint8_t* out, int h, int w, int connectivit
  * neither ignore_index nor out of [0, k).  counts_out: int64 [last batch][k][k] (k = n_classes), ADDED to.  No loss, no
  * logits gradient; one launch, integer atomics (exact). */
 int fu_eval_confusion(fu_ctx* ctx, const int64_t* target, int ignore_index, int64_t* counts_out, fu_stream stream);
+
+/* Histogram of class probability against target class, one pass, for threshold sweeps and calibration
+ * (floodplanet_code_amd/calibration.py).  Both outputs are int64, ADDED to, and at least one must be given:
+ *   hist_out [k][k][n_bins]: hist_out[c][t][b] += #pixels with target t whose probability of class c falls in bin b;
+ *   top_out  [2][n_bins], optional: row 1 counts the pixels whose argmax (first maximum wins) equals the target, row 0 the
+ *            others, binned by the winning probability.
+ * A pixel counts when its target is neither ignore_index nor out of [0, k): the rule of fu_eval_confusion.
+ * Bin rule.  n_bins is a power of two in 2..1024.  s = p * n_bins in fp32 -- exact, a power of two only moves the
+ * exponent -- and bin = s >= 1 ? min((int)s, n_bins - 1) : 0.  So for 1 <= j < n_bins: bin >= j exactly when s >= j exactly
+ * when p >= j / n_bins, and j / n_bins is itself an fp32 number: a sweep over the histogram's cumulative sums equals, count
+ * for count, thresholding the fp32 probabilities at T = j / n_bins (and T = 0 keeps every counted pixel).  A NaN and a
+ * negative probability go to bin 0 (a NaN never passes p >= T for T > 0), p == 1 and anything above go to the last bin.
+ * Integer counts: exact and order-free, so everything derived from the histogram is reproducible bit for bit, and the
+ * tests compare with equality, without a tolerance.
+ * Limits, all checked before anything is launched (a rejected call launches nothing and leaves the outputs untouched):
+ * k in 1..8; n_pixels >= 1; one histogram copy, (k * k + 2) * n_bins * 4 bytes, must fit the FU_PROB_HIST_LDS_BYTES the
+ * kernel reserves at most (gfx950's LDS per workgroup; k = 8 goes up to 512 bins, k <= 6 up to 1024).
+ * One launch, no finalisation pass, no host read: LDS bins per wave, lanes of one bin pre-aggregated by ballot, 64-bit
+ * integer atomics for the non-zero bins. */
+#define FU_PROB_HIST_LDS_BYTES 163840
+/* The probabilities of the resident logits of the last fu_forward / fu_forward_srcs / fu_forward_views (all samples of
+ * that batch, k = n_classes; target int64 [last batch, H, W]): p[c] = e[c] * inv, the softmax terms of fu_stitch_add with
+ * the product rounded on its own (nothing contracts into an fma) -- bit for bit what fu_merge_views writes to probs_out
+ * for one view of code 0.  That identity is this entry point's test oracle: fu_prob_hist on those probabilities gives
+ * the same counts. */
+int fu_eval_prob_hist(fu_ctx* ctx, const int64_t* target, int ignore_index, int n_bins, int64_t* hist_out,
+                      int64_t* top_out, fu_stream stream);
+/* The same over any fp32 probabilities [n_pixels, n_classes] (fu_merge_views' probs_out, a normalised canvas); needs no
+ * context.  probs 4-byte aligned (16-byte loads are used where the alignment allows), target int64 [n_pixels]. */
+int fu_prob_hist(const float* probs, const int64_t* target, int64_t n_pixels, int n_classes, int ignore_index, int n_bins,
+                 int64_t* hist_out, int64_t* top_out, fu_stream stream);
 
 /* ---- introspection ------------------------------------------------------------------------- */
 int64_t fu_workspace_bytes(const fu_ctx* ctx);
