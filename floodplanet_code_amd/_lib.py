@@ -161,6 +161,9 @@ SIGNATURES = {
     "fu_set_grad_clip": (_i, [_p, _d]),
     "fu_grad_clip_state": (_i, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_i64), C.POINTER(_i64),
                                 C.POINTER(_i64)]),
+    "fu_set_weight_decay": (_i, [_p, _d, C.POINTER(C.c_uint8), _i]),
+    "fu_adamw_scalars": (_i, [_d, _d, _d, _d, _i64, _d, _d, _d, C.POINTER(C.c_float)]),
+    "fu_weight_decay_state": (_i, [_p, C.POINTER(_d), C.POINTER(C.c_uint8), _i]),
     "fu_grad_norms": (_i, [_p, _d, _p, _p]),
     "fu_zero_grads": (_i, [_p, _p]),
     "fu_stitch_add": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),

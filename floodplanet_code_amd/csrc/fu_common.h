@@ -629,11 +629,22 @@ struct AdamEma {
   float* rv_ema; const float* rv;
   int64_t nbn;
 };
+// Decoupled weight decay (AdamW) of launch_adam: which elements of the flat buffer decay, as the sorted bounds of the merged
+// ranges of the decayed tensors -- element i decays when an odd number of bounds is <= i (bounds[2r] = first element of range
+// r, bounds[2r + 1] = one past its last).  nb = 2 x ranges, at most 2 * WD_MAX_RANGES; device memory owned by the context.
+constexpr int WD_MAX_RANGES = 512;       // a parameter table of CLIP_MAX_PARAMS tensors cannot form more
+struct AdamDecay {
+  const int64_t* bounds;
+  int nb;
+};
+// the merged ranges of the flagged tensors of a parameter table (offsets ascending), host side: bounds as above
+void plan_decay_bounds(const int64_t* off, const int64_t* numel, const uint8_t* flag, int nparams, std::vector<int64_t>* bounds);
 // Adam in one launch; ema != null: the weight EMA (parameters, then the running statistics) in the same launch.
 // sc = the host scalars (adam_scalars' seven; with ema the EMA weight as the eighth), or scalars_dev != null = the same
-// floats read on the device (the captured form)
+// floats read on the device (the captured form).  wd != null: the k_adamw* kernels -- the flagged elements are multiplied by
+// the ninth scalar, (float)(1 - lr * weight_decay), ahead of the same update (sc / scalars_dev then hold nine floats)
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, const AdamEma* ema, const float* sc,
-                const float* scalars_dev, hipStream_t s, const int* skip = nullptr);
+                const float* scalars_dev, hipStream_t s, const int* skip = nullptr, const AdamDecay* wd = nullptr);
 
 // Global-norm gradient clipping ahead of the Adam launch (fu_set_grad_clip) and the gradient-norm report (fu_grad_norms).
 // The flat gradient buffer is cut into chunks of at most CLIP_CHUNK floats, none across two parameter tensors; one launch
@@ -647,7 +658,7 @@ struct GradClip {            // device memory owned by the context, made once (b
   int* first = nullptr;      // [nparams + 1]: tensor t owns the chunks first[t] .. first[t + 1] - 1
   double* part = nullptr;    // [nchunks] sums of squares
   ClipState* state = nullptr;
-  float* scalars = nullptr;  // the eight Adam scalars with the clip coefficient folded into slot 6
+  float* scalars = nullptr;  // the nine Adam scalars with the clip coefficient folded into slot 6
   int nchunks = 0, nparams = 0;
 };
 // the chunk table of a parameter table (offsets and sizes in floats), host side; first gets nparams + 1 entries
@@ -655,9 +666,9 @@ void plan_clip_chunks(const int64_t* off, const int64_t* numel, int nparams, std
                       std::vector<int>* first);
 int build_grad_clip(GradClip* w, const int64_t* off, const int64_t* numel, int nparams, std::vector<void*>* allocs);
 int launch_grad_sqnorm(const GradClip& w, const float* g, hipStream_t s);
-// sc (eight host floats) or sc_dev (seven device floats, eight with ema): the Adam scalars as the caller formed them; the
-// clipped set goes to w.scalars, the report to w.state
-int launch_grad_clip_finalize(const GradClip& w, const float* sc, const float* sc_dev, bool ema, double max_norm,
+// sc (nine host floats) or sc_dev (seven device floats, eight with ema, nine with wd): the Adam scalars as the caller
+// formed them; the clipped set goes to w.scalars, the report to w.state
+int launch_grad_clip_finalize(const GradClip& w, const float* sc, const float* sc_dev, bool ema, bool wd, double max_norm,
                               hipStream_t s);
 // norms_out[0 .. nparams - 1] = every tensor's L2 norm times |grad_scale|, norms_out[nparams] = the total; nothing else is written
 int launch_grad_norms_out(const GradClip& w, double grad_scale, float* norms_out, hipStream_t s);

@@ -197,6 +197,10 @@ struct fu_ctx {
   float* ema_rv = nullptr;
   double clip_max_norm = 0.0;     // fu_set_grad_clip: > 0 = the optimiser step clips the global gradient norm to it
   fu::GradClip clip;              // its chunk table, partials, state block and scalars (made at the first use; extra_allocs)
+  double weight_decay = 0.0;      // fu_set_weight_decay: > 0 = the optimiser step decays the flagged tensors (AdamW)
+  std::vector<uint8_t> wd_mask;   // its per-tensor flags in parameter order (empty: never armed)
+  int64_t* wd_bounds = nullptr;   // device: the sorted bounds of the decayed ranges (fu::AdamDecay; extra_allocs, made once)
+  int wd_nb = 0;                  // bounds in use (0: no tensor decays -- the plain kernels run)
   fu::Profiler prof;
   struct Dp* dp = nullptr;            // fu_dp_init: RCCL communicator, communication stream, events
   std::vector<fu::PackTable> pack_tabs;   // <= MAX_PACK layers per launch

@@ -1,6 +1,7 @@
-// Optimiser kernels (gfx950): Adam in torch's single-tensor order, optionally with the weight EMA in the same pass, and the
-// fp16 guard around it (non-finite gradient check, skipped-step book-keeping); the global gradient norm and the clip
-// coefficient ahead of it (two launches of their own: the Adam kernels only ever see another gscale).
+// Optimiser kernels (gfx950): Adam in torch's single-tensor order, optionally with the weight EMA and with AdamW's decoupled
+// weight decay in the same pass, and the fp16 guard around it (non-finite gradient check, skipped-step book-keeping); the
+// global gradient norm and the clip coefficient ahead of it (two launches of their own: the Adam kernels only ever see
+// another gscale).
 #include "fu_common.h"
 
 #include <algorithm>
@@ -20,13 +21,23 @@ namespace fu {
 // skip (optional, fp16 mode): device flag set by k_grad_finite_check when a gradient of this step is not finite -- the whole
 // update is then left out (parameters, moments and averages untouched), as a GradScaler skips such a step
 // ------------------------------------------------------------------------------------------------
-struct AdamScalars { float w1, beta2, omb2, bc2_sqrt, eps, neg_step, gscale, ema_w; };
+// Decoupled weight decay (WD, torch.optim.AdamW's single-tensor path): a decayed element is first multiplied by
+// decay = (float)(1 - lr * weight_decay) -- param.mul_(1 - lr * weight_decay), one fp32 multiply with its own rounding -- and
+// the sequence above then runs on that value; the moments only ever see the gradient.  Which elements decay is a property
+// of their tensor: the kernel gets the sorted bounds of the merged ranges of the decayed tensors (AdamDecay, a few dozen
+// int64), stages them in LDS and looks each 16-byte group up there -- no further stream of memory.
+// ------------------------------------------------------------------------------------------------
+struct AdamScalars { float w1, beta2, omb2, bc2_sqrt, eps, neg_step, gscale, ema_w, decay; };
 
 // The update of one element; the ONLY place the sequence is written.  Every operation rounds on its own, in ATen's order
-// (no fma contraction): with identical inputs the update is the same float sequence as torch's CPU Adam
-// (lerp_ / mul_ / addcmul_ / sqrt / div / add_ / addcdiv_)
-__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamScalars& s) {
+// (no fma contraction): with identical inputs the update is the same float sequence as torch's CPU Adam[W]
+// ([mul_ /] lerp_ / mul_ / addcmul_ / sqrt / div / add_ / addcdiv_).  WD == false: dec and s.decay are not looked at.
+template <bool WD>
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamScalars& s, bool dec) {
 #pragma clang fp contract(off)
+  if constexpr (WD) {
+    if (dec) p = p * s.decay;               // param.mul_(1 - lr * weight_decay): the only place the decay is written
+  }
   const float gi = g * s.gscale;
   float mi = m, vi = v;
   const float dm = gi - mi;
@@ -44,30 +55,67 @@ __device__ __forceinline__ float ema_lerp(float self, float end, float wl, bool 
   const float d = end - self;
   return fmaf(wl, d, small ? self : end);
 }
+// The number of bounds <= i in the sorted bounds bnd[0 .. nb - 1] (LDS): odd = element i lies in a decayed range.  A fixed
+// trip count for every lane (it depends on nb alone), one LDS read per halving.
+__device__ __forceinline__ int decay_rank(const int64_t* bnd, int nb, int64_t i) {
+  int base = 0;
+  for (int len = nb; len > 1;) {
+    const int half = len >> 1;
+    if (bnd[base + half - 1] <= i) base += half;
+    len -= half;
+  }
+  return base + ((nb > 0 && bnd[base] <= i) ? 1 : 0);
+}
+// The decay flags of the four elements i .. i + 3, bit k = element i + k.  One search; a group that no bound cuts -- all but
+// a few dozen of the buffer's -- takes its first element's flag, one that straddles a tensor boundary decides per element.
+__device__ __forceinline__ unsigned decay_flags4(const int64_t* bnd, int nb, int64_t i) {
+  int k = decay_rank(bnd, nb, i);
+  if (k == nb || bnd[k] >= i + 4) return (k & 1) ? 0xFu : 0u;
+  unsigned flags = k & 1;
+  for (int el = 1; el < 4; ++el) {
+    while (k < nb && bnd[k] <= i + el) ++k;
+    flags |= (unsigned)(k & 1) << el;
+  }
+  return flags;
+}
 // head: the elements in front of the first 16-byte boundary (n when the arrays are not aligned alike: all scalar).
-// EMA == false: e, the running statistics and s.ema_w are not touched.
-template <bool EMA>
+// EMA == false: e, the running statistics and s.ema_w are not touched.  WD == false: bnd, wd_nb and s.decay are not
+// looked at; WD: bnd is the workgroup's LDS room for the wd_nb bounds at wd_bounds.  The copy into it is made HERE, behind the
+// first group's 16-byte loads: the table's load then travels with them, where a copy ahead of them left every workgroup of the
+// first wave idle for one more memory round trip.  Every thread reaches the barrier, with or without a group of its own.
+template <bool EMA, bool WD>
 __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                           float* __restrict__ v, float* __restrict__ e, int64_t n, int64_t head,
                                           const AdamScalars& s, float* __restrict__ erm, const float* __restrict__ rm,
-                                          float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn) {
+                                          float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn,
+                                          const int64_t* __restrict__ wd_bounds, int64_t* bnd, int wd_nb) {
 #pragma clang fp contract(off)
   const bool small = EMA && fabsf(s.ema_w) < 0.5f;
   const float wl = !EMA ? 0.f : small ? s.ema_w : s.ema_w - 1.0f;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
   const int64_t nvec = (n - head) / 4;
+  float4 p4, g4, m4, v4, e4;
+  auto load4 = [&](int64_t i) {
+    p4 = *reinterpret_cast<const float4*>(p + i);
+    g4 = *reinterpret_cast<const float4*>(g + i);
+    m4 = *reinterpret_cast<const float4*>(m + i);
+    v4 = *reinterpret_cast<const float4*>(v + i);
+    if constexpr (EMA) e4 = *reinterpret_cast<const float4*>(e + i);
+  };
+  if constexpr (WD) {
+    if (tid < nvec) load4(head + 4 * tid);
+    for (int k = threadIdx.x; k < wd_nb; k += blockDim.x) bnd[k] = wd_bounds[k];
+    __syncthreads();
+  }
   for (int64_t j = tid; j < nvec; j += nthr) {
     const int64_t i = head + 4 * j;
-    float4 p4 = *reinterpret_cast<const float4*>(p + i);
-    const float4 g4 = *reinterpret_cast<const float4*>(g + i);
-    float4 m4 = *reinterpret_cast<const float4*>(m + i);
-    float4 v4 = *reinterpret_cast<const float4*>(v + i);
-    float4 e4;
-    if constexpr (EMA) e4 = *reinterpret_cast<const float4*>(e + i);
-    adam_elem(p4.x, g4.x, m4.x, v4.x, s);
-    adam_elem(p4.y, g4.y, m4.y, v4.y, s);
-    adam_elem(p4.z, g4.z, m4.z, v4.z, s);
-    adam_elem(p4.w, g4.w, m4.w, v4.w, s);
+    if (!WD || j != tid) load4(i);
+    unsigned dec = 0;
+    if constexpr (WD) dec = decay_flags4(bnd, wd_nb, i);       // LDS reads and compares behind the loads above
+    adam_elem<WD>(p4.x, g4.x, m4.x, v4.x, s, dec & 1u);
+    adam_elem<WD>(p4.y, g4.y, m4.y, v4.y, s, dec & 2u);
+    adam_elem<WD>(p4.z, g4.z, m4.z, v4.z, s, dec & 4u);
+    adam_elem<WD>(p4.w, g4.w, m4.w, v4.w, s, dec & 8u);
     *reinterpret_cast<float4*>(p + i) = p4;
     *reinterpret_cast<float4*>(m + i) = m4;
     *reinterpret_cast<float4*>(v + i) = v4;
@@ -82,7 +130,9 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
   const int64_t tail0 = head + 4 * nvec, nrest = head + (n - tail0);      // misaligned head and tail: plain code
   for (int64_t k = tid; k < nrest; k += nthr) {
     const int64_t i = k < head ? k : tail0 + (k - head);
-    adam_elem(p[i], g[i], m[i], v[i], s);
+    bool dec = false;
+    if constexpr (WD) dec = decay_rank(bnd, wd_nb, i) & 1;
+    adam_elem<WD>(p[i], g[i], m[i], v[i], s, dec);
     if constexpr (EMA) e[i] = ema_lerp(e[i], p[i], wl, small);
   }
   if constexpr (EMA) {
@@ -95,11 +145,13 @@ __device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __
 // The scalars by value, or (fu_adam_scalars: seven; fu_adam_ema_scalars: the EMA weight as the eighth) read from DEVICE
 // memory: a captured (hipGraph) step replays that launch unchanged while the step count -- and with it the bias
 // corrections -- moves on; the caller refreshes the floats before each replay.
-template <bool EMA>
+// With decay (fu_adamw_scalars) the device form reads nine: slot 7 stays the EMA weight (ignored by the plain form), slot 8
+// is the decay factor.  Without it slot 8 is never read: the caller's buffer is 7 or 8 floats long.
+template <bool EMA, bool WD>
 __device__ __forceinline__ AdamScalars adam_scalars_of(const AdamScalars& s) { return s; }
-template <bool EMA>
+template <bool EMA, bool WD>
 __device__ __forceinline__ AdamScalars adam_scalars_of(const float* __restrict__ sc) {
-  return {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], EMA ? sc[7] : 0.f};
+  return {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], EMA ? sc[7] : 0.f, WD ? sc[8] : 1.f};
 }
 // four entry kernels over the one body (their names are what a captured graph's dump and a kernel trace show)
 #define FU_ADAM_KERNEL(NAME, EMA, SCALARS)                                                                              \
@@ -109,13 +161,33 @@ __device__ __forceinline__ AdamScalars adam_scalars_of(const float* __restrict__
                                               float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn,       \
                                               const int* __restrict__ skip) {                                           \
     if (skip && *skip) return;                                                                                          \
-    adam_body<EMA>(p, g, m, v, e, n, head, adam_scalars_of<EMA>(sc), erm, rm, erv, rv, nbn);                            \
+    adam_body<EMA, false>(p, g, m, v, e, n, head, adam_scalars_of<EMA, false>(sc), erm, rm, erv, rv, nbn, nullptr,      \
+                          nullptr, 0);                                                                                  \
   }
 FU_ADAM_KERNEL(k_adam, false, AdamScalars)
 FU_ADAM_KERNEL(k_adam_ema, true, AdamScalars)
 FU_ADAM_KERNEL(k_adam_dev, false, const float* __restrict__)
 FU_ADAM_KERNEL(k_adam_ema_dev, true, const float* __restrict__)
 #undef FU_ADAM_KERNEL
+// and their four decay-aware twins: the same launch over the whole flat buffer, the bounds (wd_nb <= 2 * WD_MAX_RANGES of
+// them, 8 KB at the most) copied into LDS by adam_body.  A skipped step returns before anything: it skips the decay too.
+#define FU_ADAMW_KERNEL(NAME, EMA, SCALARS)                                                                             \
+  __global__ __launch_bounds__(256) void NAME(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, \
+                                              float* __restrict__ v, float* __restrict__ e, int64_t n, int64_t head,    \
+                                              SCALARS sc, float* __restrict__ erm, const float* __restrict__ rm,        \
+                                              float* __restrict__ erv, const float* __restrict__ rv, int64_t nbn,       \
+                                              const int* __restrict__ skip, const int64_t* __restrict__ wd_bounds,      \
+                                              int wd_nb) {                                                              \
+    __shared__ int64_t bnd[2 * WD_MAX_RANGES];                                                                          \
+    if (skip && *skip) return;                                                                                          \
+    adam_body<EMA, true>(p, g, m, v, e, n, head, adam_scalars_of<EMA, true>(sc), erm, rm, erv, rv, nbn, wd_bounds, bnd, \
+                         min(wd_nb, 2 * WD_MAX_RANGES));                                                                \
+  }
+FU_ADAMW_KERNEL(k_adamw, false, AdamScalars)
+FU_ADAMW_KERNEL(k_adamw_ema, true, AdamScalars)
+FU_ADAMW_KERNEL(k_adamw_dev, false, const float* __restrict__)
+FU_ADAMW_KERNEL(k_adamw_ema_dev, true, const float* __restrict__)
+#undef FU_ADAMW_KERNEL
 
 // the seven float scalars of the update: formed in double as torch.optim.Adam forms them in Python, then rounded once to
 // float (the cast ATen applies to a Python scalar operand of a float tensor op)
@@ -136,23 +208,46 @@ static int64_t adam_head(const float* p, const float* g, const float* m, const f
   const int64_t head = (int64_t)(((16 - a) & 15) / 4);
   return head < n ? head : n;
 }
+void plan_decay_bounds(const int64_t* off, const int64_t* numel, const uint8_t* flag, int nparams, std::vector<int64_t>* bounds) {
+  bounds->clear();
+  for (int t = 0; t < nparams; ++t) {
+    if (!flag[t] || numel[t] <= 0) continue;
+    if (!bounds->empty() && bounds->back() == off[t]) bounds->back() = off[t] + numel[t];   // adjacent tensors: one range
+    else { bounds->push_back(off[t]); bounds->push_back(off[t] + numel[t]); }
+  }
+}
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, const AdamEma* ema, const float* sc,
-                const float* scalars_dev, hipStream_t s, const int* skip) {
+                const float* scalars_dev, hipStream_t s, const int* skip, const AdamDecay* wd) {
   static const AdamEma none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   const AdamEma& E = ema ? *ema : none;
   const int64_t head = adam_head(p, g, m, v, E.p, n);
   const dim3 grid(grid_for(ceil_div64(n, 4), 256, 4096));
 #define FU_ADAM(K, SC)                                                                                            \
   hipLaunchKernelGGL(K, grid, dim3(256), 0, s, p, g, m, v, E.p, n, head, SC, E.rm_ema, E.rm, E.rv_ema, E.rv, E.nbn, skip)
-  if (scalars_dev) {
+#define FU_ADAMW(K, SC)                                                                                            \
+  hipLaunchKernelGGL(K, grid, dim3(256), 0, s, p, g, m, v, E.p, n, head, SC, E.rm_ema, E.rm, E.rv_ema, E.rv, E.nbn, skip, \
+                     wd->bounds, wd->nb)
+  if (wd) {
+    FU_REQUIRE(wd->bounds && wd->nb >= 2 && wd->nb <= 2 * WD_MAX_RANGES && wd->nb % 2 == 0,
+               "weight decay: %d range bounds, 2 to %d in pairs supported", wd->nb, 2 * WD_MAX_RANGES);
+    if (scalars_dev) {
+      if (ema) FU_ADAMW(k_adamw_ema_dev, scalars_dev);
+      else FU_ADAMW(k_adamw_dev, scalars_dev);
+    } else {
+      const AdamScalars as = {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], ema ? sc[7] : 0.f, sc[8]};
+      if (ema) FU_ADAMW(k_adamw_ema, as);
+      else FU_ADAMW(k_adamw, as);
+    }
+  } else if (scalars_dev) {
     if (ema) FU_ADAM(k_adam_ema_dev, scalars_dev);
     else FU_ADAM(k_adam_dev, scalars_dev);
   } else {
-    const AdamScalars as = {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], ema ? sc[7] : 0.f};
+    const AdamScalars as = {sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], ema ? sc[7] : 0.f, 1.f};
     if (ema) FU_ADAM(k_adam_ema, as);
     else FU_ADAM(k_adam, as);
   }
 #undef FU_ADAM
+#undef FU_ADAMW
   FU_LAUNCH_CHECK();
   return 0;
 }
@@ -243,7 +338,7 @@ __global__ __launch_bounds__(256) void k_grad_sqnorm_chunks(const float* __restr
   }
 }
 
-struct ClipScalars { float v[8]; };
+struct ClipScalars { float v[9]; };
 // src[lo] + src[lo + 1] + ... in that order; the loads of eight terms are issued ahead of their adds, so that the chain
 // costs an add per term, not a memory round trip
 __device__ __forceinline__ double ordered_sum(const double* src, int lo, int hi) {
@@ -259,7 +354,8 @@ __device__ __forceinline__ double ordered_sum(const double* src, int lo, int hi)
 }
 constexpr int CLIP_FIN_CHUNKS = 4096;    // partials staged in LDS up to this many chunks (32 KB); more are read in place
 constexpr int CLIP_MAX_PARAMS = 1024;    // per-tensor sums live in LDS (build_grad_clip refuses a longer parameter table)
-// sc_dev == null: the caller's scalars are scv (by value); else nsc floats (7, or 8 with the EMA weight) are read from sc_dev.
+// sc_dev == null: the caller's scalars are scv (by value); else nsc floats (7, 8 with the EMA weight, 9 with the decay factor)
+// are read from sc_dev.
 // out_sc == null: no scalar part, no state (fu_grad_norms); norms_out == null: no per-tensor report (the optimiser step).
 __global__ __launch_bounds__(256) void k_grad_norm_finalize(const double* __restrict__ part, const int* __restrict__ first,
                                                             int nparams, int nchunks, ClipScalars scv,
@@ -271,8 +367,8 @@ __global__ __launch_bounds__(256) void k_grad_norm_finalize(const double* __rest
   __shared__ double tsq[CLIP_MAX_PARAMS];
   const int tid = threadIdx.x;
   const bool staged = nchunks <= CLIP_FIN_CHUNKS;
-  float in[8];                                        // read ahead of the sums: nothing below waits for these loads
-  for (int k = 0; k < 8; ++k) in[k] = !out_sc ? 0.f : sc_dev ? (k < nsc ? sc_dev[k] : 0.f) : scv.v[k];
+  float in[9];                                        // read ahead of the sums: nothing below waits for these loads
+  for (int k = 0; k < 9; ++k) in[k] = !out_sc ? 0.f : sc_dev ? (k < nsc ? sc_dev[k] : 0.f) : scv.v[k];
   if (staged) {
     for (int i = tid; i < nchunks; i += 256) lpart[i] = part[i];
     __syncthreads();
@@ -293,7 +389,7 @@ __global__ __launch_bounds__(256) void k_grad_norm_finalize(const double* __rest
   const bool finite = isfinite(N);
   const double r = max_norm / (N + 1e-6);
   const float coef = (max_norm > 0.0 && finite && r < 1.0) ? (float)r : 1.0f;
-  for (int k = 0; k < 8; ++k) out_sc[k] = in[k];
+  for (int k = 0; k < 9; ++k) out_sc[k] = in[k];
   out_sc[6] = gscale_in * coef;
   st->last_norm = (float)N;
   st->last_coef = coef;
@@ -325,7 +421,7 @@ int build_grad_clip(GradClip* w, const int64_t* off, const int64_t* numel, int n
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t o_first = up(nch * sizeof(ClipChunk)), o_part = o_first + up(first.size() * sizeof(int)),
                o_state = o_part + up(nch * sizeof(double)), o_scal = o_state + up(sizeof(ClipState)),
-               total = o_scal + up(8 * sizeof(float));
+               total = o_scal + up(9 * sizeof(float));
   char* base = nullptr;
   FU_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&base), total));
   allocs->push_back(base);
@@ -347,12 +443,12 @@ int launch_grad_sqnorm(const GradClip& w, const float* g, hipStream_t s) {
   FU_LAUNCH_CHECK();
   return 0;
 }
-int launch_grad_clip_finalize(const GradClip& w, const float* sc, const float* sc_dev, bool ema, double max_norm,
+int launch_grad_clip_finalize(const GradClip& w, const float* sc, const float* sc_dev, bool ema, bool wd, double max_norm,
                               hipStream_t s) {
   ClipScalars scv = {};
-  if (!sc_dev) for (int k = 0; k < 8; ++k) scv.v[k] = (k < 7 || ema) ? sc[k] : 0.f;
+  if (!sc_dev) for (int k = 0; k < 9; ++k) scv.v[k] = (k < 7 || (k == 7 && ema) || (k == 8 && wd)) ? sc[k] : 0.f;
   hipLaunchKernelGGL(k_grad_norm_finalize, dim3(1), dim3(256), 0, s, w.part, w.first, w.nparams, w.nchunks, scv, sc_dev,
-                     ema ? 8 : 7, max_norm, w.scalars, w.state, (float*)nullptr, 0.0);
+                     wd ? 9 : ema ? 8 : 7, max_norm, w.scalars, w.state, (float*)nullptr, 0.0);
   FU_LAUNCH_CHECK();
   return 0;
 }

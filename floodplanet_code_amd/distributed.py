@@ -125,7 +125,8 @@ class DataParallelTrainer:
                  group=None, cap_bytes: int = 16 << 20, exact: bool = False, time_waits: bool = False,
                  graph: bool = False, class_weight=None, label_smoothing: float = 0.0, ema_decay: Optional[float] = None,
                  ema_warmup: bool = True, focal_gamma: float = 0.0, region_weight: float = 0.0, region_alpha: float = 0.5,
-                 region_beta: float = 0.5, region_smooth: float = 1.0, grad_clip_norm: Optional[float] = None):
+                 region_beta: float = 0.5, region_smooth: float = 1.0, grad_clip_norm: Optional[float] = None,
+                 weight_decay: float = 0.0, decay_all: bool = False):
         """exact=False: DDP semantics (per-rank BN statistics and 1/N_valid, gradients averaged).
         exact=True: SyncBN statistics and a global N_valid (HipUNet.enable_exact_sync); the ranks together reproduce
         one device with world_size x the batch, gradients are summed (SURVEY.md 8(e) "exact mode").
@@ -142,11 +143,17 @@ class DataParallelTrainer:
         grad_clip_norm: clip the global L2 norm of the gradients to it inside the optimiser step of every path
         (HipUNet.set_grad_clip: two launches ahead of the fused Adam launch, nothing read back).  The norm is that of the
         gradients as Adam consumes them -- after the all-reduce and times grad_scale, i.e. of the averaged gradient -- so
-        every rank computes the same coefficient and no further collective is needed."""
+        every rank computes the same coefficient and no further collective is needed.
+        weight_decay > 0: torch.optim.AdamW's decoupled decay inside the fused Adam launch of every path
+        (HipUNet.set_weight_decay), on every tensor with ndim >= 2, or with decay_all on every tensor.  The factor
+        1 - lr * weight_decay is formed from self.lr at every step -- on the captured path it is the ninth of the scalars
+        refreshed per replay -- so self.lr may change between steps.  Rank-local like the EMA."""
         if ema_decay is not None:
             net.enable_ema(ema_decay, ema_warmup)
         if grad_clip_norm is not None:
             net.set_grad_clip(grad_clip_norm)
+        if weight_decay or decay_all:
+            net.set_weight_decay(weight_decay, "all" if decay_all else "weights")
         self.net, self.lr, self.world_size, self.rank = net, lr, world_size, rank
         # checked on the host, once; every step hands this one object to HipUNet._loss_raw
         self.loss_options = LossOptions.make(net.n_classes, class_weight=class_weight, label_smoothing=label_smoothing,
@@ -161,7 +168,7 @@ class DataParallelTrainer:
         self.time_waits = time_waits
         # graph=True (single device): the whole step -- fu_forward, fu_loss_ce, fu_backward with its side-stream fork / join,
         # fu_adam_step_dev (fu_adam_ema_step_dev with a weight EMA) -- is captured once into a hipGraph (torch.cuda.CUDAGraph on
-        # the capture stream the C calls are issued on) and replayed; only the seven Adam scalars (eight with the EMA weight),
+        # the capture stream the C calls are issued on) and replayed; only the seven Adam scalars (eight with the EMA weight, nine with weight decay),
         # which depend on the step count, are refreshed per step.  The
         # captured launches are valid for ONE (x, target) pair of device buffers: other tensors are copied into them.
         self.graph = bool(graph) and world_size <= 1
@@ -170,6 +177,7 @@ class DataParallelTrainer:
         self._g_ignore = None
         self._g_ema = False
         self._g_clip = None            # the clip norm the captured step was recorded with (None: no norm launches in it)
+        self._g_decay = None           # the weight decay and flags it was recorded with (None: the plain Adam launch in it)
         self._reducer: Optional[BucketedReducer] = None
         self._launch_stream = None     # the stream the bucket all-reduces are launched from (mode 2, fu_backward_fence)
         self._synced = False
@@ -203,7 +211,14 @@ class DataParallelTrainer:
         import ctypes as C
         from . import _lib
         ema = self.net._ema
-        if self._g_ema:                  # eight scalars: the EMA weight of this update rides behind Adam's seven
+        if self._g_decay is not None:    # nine scalars: slot 7 the EMA weight (0 without one), slot 8 this step's decay factor
+            from .ema import ema_weight
+            buf = (C.c_float * 9)()
+            _lib.check(_lib.load().fu_adamw_scalars(float(self.lr), float(self.betas[0]), float(self.betas[1]),
+                                                    float(self.eps), int(step), 1.0,
+                                                    ema_weight(ema[0], int(step), ema[1]) if self._g_ema else 0.0,
+                                                    float(self._g_decay[0]), buf))
+        elif self._g_ema:                # eight scalars: the EMA weight of this update rides behind Adam's seven
             from .ema import ema_weight
             buf = (C.c_float * 8)()
             _lib.check(_lib.load().fu_adam_ema_scalars(float(self.lr), float(self.betas[0]), float(self.betas[1]),
@@ -236,7 +251,8 @@ class DataParallelTrainer:
         self._gt.copy_(target)
         self._g_ema = net.ema_enabled                                 # which optimiser launch this graph holds
         self._g_clip = net.grad_clip                                  # ... and whether the two norm launches go ahead of it
-        n_scal = 8 if self._g_ema else 7
+        self._g_decay = net._decay_key()                              # ... and whether the Adam launch is the decay-aware one
+        n_scal = 9 if self._g_decay is not None else 8 if self._g_ema else 7
         self._gscal = torch.zeros(n_scal, dtype=torch.float32, device=dev)
         self._gscal_ring = [torch.zeros(n_scal, dtype=torch.float32).pin_memory() for _ in range(8)]
         self._gscal_ev = [None] * 8
@@ -268,7 +284,8 @@ class DataParallelTrainer:
     def _graph_step(self, x, target, ignore_index):
         net = self.net
         if self._graph is not None and (int(ignore_index) != self._g_ignore or x.shape != self._gx.shape
-                                        or self._g_ema != net.ema_enabled or self._g_clip != net.grad_clip):
+                                        or self._g_ema != net.ema_enabled or self._g_clip != net.grad_clip
+                                        or self._g_decay != net._decay_key()):
             self._graph = None                                        # another workload: capture again
         if self._graph is None:
             if net._ctx is None or net._ctx_key[1:3] != tuple(x.shape[2:]) or net._ctx_key[3] < x.shape[0]:

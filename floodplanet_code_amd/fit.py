@@ -35,7 +35,7 @@ import torch
 
 from .models import build_model
 from .schedule import KINDS as LR_SCHEDULES, check_schedule, lr_at
-from .unet import check_focal_gamma, check_grad_clip, check_region_loss
+from .unet import check_focal_gamma, check_grad_clip, check_region_loss, check_weight_decay
 
 SCHEDULE_OPTIONS = ("lr_schedule", "warmup_steps", "min_lr")       # cfg keys, present only when the command line gave them
 
@@ -97,7 +97,8 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
     train loader's `last_plan`, when it has one.  With an lr schedule (cfg lr_schedule / warmup_steps / min_lr: schedule.lr_at
     per optimiser step, over n_epochs x the loader's length) or gradient clipping (the model's grad_clip_norm) an entry also
     carries `lr`, the last step's; with clipping `grad_norm`, the last step's global gradient norm before clipping, and
-    `clipped_steps`, the steps clipped so far."""
+    `clipped_steps`, the steps clipped so far.  With weight decay (the model's weight_decay) an entry carries `weight_decay`
+    and `decayed_tensors`, the number of tensors it acts on."""
     c = dict(DEFAULTS)
     c.update(cfg or {})
     torch.manual_seed(c["seed_num"])                                         # pl.seed_everything(seed_num)
@@ -160,6 +161,9 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
         if clip_state is not None:
             history[-1]["grad_norm"] = clip_state["grad_norm"]               # the last step's, before clipping
             history[-1]["clipped_steps"] = clip_state["clipped_steps"]       # of the run so far
+        if getattr(model, "weight_decay", 0.0) > 0.0:
+            history[-1]["weight_decay"] = float(opt.param_groups[0]["weight_decay"])
+            history[-1]["decayed_tensors"] = len(model.model.decayed_parameter_names())
         plan =getattr(train_loader, "last_plan", None)                      # a loader that chooses its tiles says which
         if plan is not None:
             history[-1]["plan"] = dict(plan)
@@ -235,6 +239,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--grad_clip", type=float, default=None, metavar="F",
                     help="clip the global L2 norm of the gradients to F > 0 inside every optimiser step (clip_grad_norm_ "
                          "ahead of Adam, on the device; default: no clipping)")
+    ap.add_argument("--weight_decay", type=float, default=None, metavar="F",
+                    help="decoupled weight decay (AdamW) F > 0 inside the fused Adam step, on the conv and head weights "
+                         "(every tensor with ndim >= 2; default: no decay)")
+    ap.add_argument("--decay_all", action="store_true",
+                    help="with --weight_decay: decay every tensor, biases and BatchNorm included")
     ap.add_argument("--lr_schedule", type=str, default=None, choices=list(LR_SCHEDULES),
                     help="learning rate after the warm-up: constant (default), or linear / cosine / poly (power 0.9) decay "
                          "from --lr to --min_lr over the run's optimiser steps")
@@ -353,6 +362,15 @@ def cfg_from_args(args, class_weights=None) -> dict:
         if clip is None:
             raise ValueError("--grad_clip must be > 0 (leave the option out for no clipping)")
         loss_kwargs["grad_clip_norm"] = clip
+    if getattr(args, "weight_decay", None) is not None:
+        decay = check_weight_decay(args.weight_decay)
+        if decay == 0.0:
+            raise ValueError("--weight_decay must be > 0 (leave the option out for no decay)")
+        loss_kwargs["weight_decay"] = decay
+        if getattr(args, "decay_all", False):
+            loss_kwargs["decay_all"] = True
+    elif getattr(args, "decay_all", False):
+        raise ValueError("--decay_all needs --weight_decay")
     schedule = schedule_from_args(args)
     sampling = sampling_from_args(args)
     cfg = dict(lr=args.lr, batch_size=args.batch_size, n_epochs=args.n_epochs, crop_height=args.crop[0],
@@ -429,6 +447,9 @@ def main(argv: Optional[List[str]] = None) -> dict:
            "class_weights": None if model.class_weights is None else list(model.class_weights)}
     if "sampling" in cfg:
         out["tile_sampling"] = dict(cfg["sampling"])
+    if model.weight_decay > 0.0:
+        out["weight_decay"] = model.weight_decay
+        out["decayed_tensors"] = len(model.model.decayed_parameter_names())
     print(json.dumps(out))
     return out
 

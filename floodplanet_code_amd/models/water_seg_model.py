@@ -19,7 +19,9 @@ one (alpha = beta = 0.5: soft Dice, 1 and 1: soft Jaccard; fu_loss_ce_region, Hi
 and ``ema_warmup``: an exponential moving average of the weights, updated inside the fused Adam launch, that validation and
 test steps evaluate and that checkpoints carry as the top-level entry ``ema_state_dict`` (state_dict() stays the raw
 weights under the reference's keys); ``grad_clip_norm`` > 0: the global L2 norm of the gradients is clipped to it inside
-every optimiser step (clip_grad_norm_ ahead of Adam, on the device: HipUNet.set_grad_clip).
+every optimiser step (clip_grad_norm_ ahead of Adam, on the device: HipUNet.set_grad_clip); ``weight_decay`` > 0:
+torch.optim.AdamW's decoupled weight decay inside the fused Adam launch (HipUNet.set_weight_decay), on every tensor with
+ndim >= 2 -- conv and head weights, not biases or BatchNorm -- or with ``decay_all`` on every tensor.
 """
 from __future__ import annotations
 
@@ -34,7 +36,7 @@ from ..lightning_compat import LightningModule
 from ..metrics import SegmentationMetrics
 from ..ema import check_decay
 from ..loss_options import LossOptions
-from ..unet import HipAdam, HipUNet, check_class_weight, check_grad_clip, check_label_smoothing
+from ..unet import HipAdam, HipUNet, check_class_weight, check_grad_clip, check_label_smoothing, check_weight_decay
 
 
 class WaterSegmentationModel(LightningModule):
@@ -42,9 +44,11 @@ class WaterSegmentationModel(LightningModule):
     def __init__(self, in_channels, n_classes, lr, log_image_iter=50, to_rgb_fcn=None, ignore_index=None,
                  optimizer_name='adam', precision='fp32', base_channels=64, class_weights=None, label_smoothing=0.0,
                  ema_decay=None, ema_warmup=True, focal_gamma=0.0, region_weight=0.0, region_alpha=0.5, region_beta=0.5,
-                 region_smooth=1.0, grad_clip_norm=None):
+                 region_smooth=1.0, grad_clip_norm=None, weight_decay=0.0, decay_all=False):
         super().__init__()
         self.grad_clip_norm = check_grad_clip(grad_clip_norm)
+        self.weight_decay = check_weight_decay(weight_decay)
+        self.decay_all = bool(decay_all)
         self.n_classes = n_classes
         self.ignore_index = ignore_index
         if self.ignore_index == -1:                      # water_seg_model.py:35-36
@@ -213,9 +217,13 @@ class WaterSegmentationModel(LightningModule):
                 if self.grad_clip_norm is not None:
                     raise NotImplementedError("gradient clipping runs ahead of the fused Adam kernel (HipAdam): FU_TORCH_ADAM=1 "
                                               "together with grad_clip_norm is not supported")
+                if self.weight_decay > 0.0:
+                    raise NotImplementedError("weight decay is part of the fused Adam kernel (HipAdam): FU_TORCH_ADAM=1 "
+                                              "together with weight_decay is not supported")
                 optimizer = optim.Adam(self.parameters(), lr=self.lr)
             else:
-                optimizer = HipAdam(self.model, lr=self.lr, max_grad_norm=self.grad_clip_norm)
+                optimizer = HipAdam(self.model, lr=self.lr, max_grad_norm=self.grad_clip_norm,
+                                    weight_decay=self.weight_decay, decay_params="all" if self.decay_all else "weights")
         else:
             raise NotImplementedError(f'No implementation for optimizer of name: {self.optimizer_name}')
         return optimizer

@@ -150,6 +150,8 @@ class HipUNet(nn.Module):
         self._ema_swapped = False                     # inside ema_weights(): the context reads the EMA buffers
         self._grad_clip: Optional[float] = None       # set_grad_clip: max global gradient norm of the optimiser step
         self._clip_carry = (0.0, 0.0, 0, 0, 0)        # last norm / coefficient and the counters of the contexts before this one
+        self._weight_decay = 0.0                      # set_weight_decay: AdamW's decoupled decay inside the optimiser step ...
+        self._decay_mask: Optional[List[bool]] = None     # ... and which tensors of the parameter table it acts on
         self._generation = 0          # counts training forwards: an autograd node may only backward the latest one
         self._flat_valid = False
         self._ctx = None
@@ -400,6 +402,8 @@ class HipUNet(nn.Module):
         self._bind(h)
         if self._grad_clip is not None:               # the setting belongs to the module: every new context takes it
             check(lib.fu_set_grad_clip(h, self._grad_clip))
+        if self._weight_decay > 0.0:                  # likewise
+            self._arm_weight_decay(h)
         self._install_exact_sync(device)
         return h
 
@@ -795,6 +799,55 @@ class HipUNet(nn.Module):
             return self._clip_carry
         return norm.value, coef.value, n0 + n.value, k0 + k.value, bad0 + bad.value
 
+    # ---------------------------------------------------------------- weight decay
+    def set_weight_decay(self, weight_decay: Optional[float], params="weights"):
+        """Decoupled weight decay (torch.optim.AdamW) inside every optimiser step (adam_step / HipAdam.step /
+        DataParallelTrainer.step): each element of a decayed tensor is multiplied by float32(1 - lr * weight_decay) ahead of
+        the Adam update, in the same one launch (fu_set_weight_decay).  params: "weights" -- every tensor with ndim >= 2
+        (conv, transposed-conv, fusion and head weights; biases and BatchNorm weight / bias do not decay), "all" -- every
+        tensor, what a bare torch.optim.AdamW(model.parameters()) does -- or an iterable of state-dict names.  None or 0
+        switches it off.  The setting belongs to the module and is re-applied to every context it makes."""
+        weight_decay = check_weight_decay(weight_decay)
+        names = [name for name, _, _, _ in self._table]
+        if isinstance(params, str):
+            if params not in ("weights", "all"):
+                raise ValueError(f"set_weight_decay: params must be 'weights', 'all' or parameter names, got {params!r}")
+            mask = [params == "all" or p.ndim >= 2 for _, p, _, _ in self._table]
+        else:
+            wanted = [str(k) for k in params]
+            unknown = [k for k in wanted if k not in names]
+            if unknown:
+                raise KeyError(f"set_weight_decay: no such parameters {unknown[:4]}{' ...' if len(unknown) > 4 else ''}")
+            mask = [name in set(wanted) for name in names]
+        self._weight_decay = weight_decay
+        self._decay_mask = mask if weight_decay > 0.0 else None
+        if self._ctx is not None:
+            self._arm_weight_decay(self._ctx)
+        return self
+
+    def _arm_weight_decay(self, h):
+        if self._weight_decay > 0.0:
+            mask = (C.c_uint8 * len(self._table))(*[int(f) for f in self._decay_mask])
+            check(_lib.load().fu_set_weight_decay(h, self._weight_decay, mask, len(self._table)))
+        else:
+            check(_lib.load().fu_set_weight_decay(h, 0.0, None, 0))
+
+    @property
+    def weight_decay(self) -> float:
+        return self._weight_decay
+
+    def decayed_parameter_names(self) -> List[str]:
+        """The state-dict names of the tensors the armed weight decay acts on, in parameter order ([] when it is off)."""
+        if self._decay_mask is None:
+            return []
+        return [name for (name, _, _, _), f in zip(self._table, self._decay_mask) if f]
+
+    def _decay_key(self):
+        """What a captured step depends on: (weight_decay, flags) or None when no tensor decays."""
+        if self._weight_decay <= 0.0 or not any(self._decay_mask):
+            return None
+        return self._weight_decay, tuple(self._decay_mask)
+
     def grad_norms(self, grad_scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
         """(per_parameter, total): the L2 norm of every parameter's gradient, in the order of grad_norm_names(), and of all
         of them, times |grad_scale| -- device tensors from one pass over the flat gradient buffer (fu_grad_norms); nothing
@@ -952,6 +1005,16 @@ class _UNetLossFn(torch.autograd.Function):
         return _no_grads(_UNetLossFn.forward) + _return_param_grads(m, saved, alias)
 
 
+def check_weight_decay(weight_decay) -> float:
+    """None -> 0.0 (off); a finite weight_decay >= 0 -> float; anything else raises."""
+    if weight_decay is None:
+        return 0.0
+    v = float(weight_decay)
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError(f"the weight decay must be finite and >= 0, got {weight_decay!r}")
+    return v
+
+
 def check_grad_clip(max_norm) -> Optional[float]:
     """None / 0 -> None (off); a finite max_norm > 0 -> float; anything else raises."""
     if max_norm is None:
@@ -963,22 +1026,31 @@ def check_grad_clip(max_norm) -> Optional[float]:
 
 
 class HipAdam(torch.optim.Adam):
-    """A torch.optim.Adam (isinstance holds; same param_groups / defaults) (water_seg_model.py:198-205: lr, default betas / eps, no weight decay, no amsgrad) whose
+    """A torch.optim.Adam (isinstance holds; same param_groups / defaults) (water_seg_model.py:198-205: lr, default betas / eps, no amsgrad; weight decay only in its decoupled form, below) whose
     step() is ONE launch of libfloodunet's fused Adam kernel on the module's flat parameter / gradient / moment
     buffers (fu_adam_step).  param_groups[0] carries lr / betas / eps as torch's Adam does (LR schedulers work);
     state_dict() holds {step, exp_avg, exp_avg_sq} per parameter like torch.optim.Adam's, the moments being views of the
     module's flat buffers.  When the module keeps a weight EMA (HipUNet.enable_ema) the step is fu_adam_ema_step, and
     state_dict() carries one more top-level entry "ema" {decay, warmup, params, running_mean, running_var} -- the flat EMA
     buffers -- so that a reloaded optimiser continues the same average.  max_grad_norm: clip the global L2 norm of the
-    gradients to it inside every step() (clip_grad_norm_ ahead of the update, on the device: HipUNet.set_grad_clip)."""
+    gradients to it inside every step() (clip_grad_norm_ ahead of the update, on the device: HipUNet.set_grad_clip).
+    weight_decay > 0: torch.optim.AdamW's decoupled decay in the same launch (HipUNet.set_weight_decay) on decay_params --
+    "weights" (every tensor with ndim >= 2), "all" or an iterable of state-dict names.  param_groups[0] carries
+    weight_decay and decoupled_weight_decay=True as torch's does; step() reads weight_decay and lr from there, so schedulers
+    and manual changes work, and state_dict() carries the decayed tensors' names as the top-level entry 'decay_params'."""
 
     def __init__(self, net: HipUNet, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, weight_decay: float = 0.0, decay_params="weights"):
         if not isinstance(net, HipUNet):
             raise TypeError("HipAdam drives a HipUNet's flat buffers")
-        super().__init__([p for _, p, _, _ in net._table], lr=lr, betas=betas, eps=eps)
+        weight_decay = check_weight_decay(weight_decay)
+        super().__init__([p for _, p, _, _ in net._table], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                         decoupled_weight_decay=True)
         if max_grad_norm is not None:                 # clip_grad_norm_(parameters, max_grad_norm) inside every step()
             net.set_grad_clip(max_grad_norm)
+        self._decay_params = decay_params if isinstance(decay_params, str) else [str(k) for k in decay_params]
+        if weight_decay > 0.0 or net.weight_decay > 0.0 or not isinstance(self._decay_params, str):
+            net.set_weight_decay(weight_decay, self._decay_params)        # (also checks the names)
         self._net = net
         self._step = 0
 
@@ -1004,6 +1076,9 @@ class HipAdam(torch.optim.Adam):
         if outside:
             torch._foreach_copy_([a for a, _ in outside], [b for _, b in outside])
         g = self.param_groups[0]
+        wd = check_weight_decay(g.get("weight_decay", 0.0))
+        if wd != net.weight_decay:                    # changed in param_groups since the last step (or loaded)
+            net.set_weight_decay(wd, self._decay_params)
         self._step += 1
         net.adam_step(g["lr"], self._step, g["betas"], g["eps"])
         return loss
@@ -1017,6 +1092,8 @@ class HipAdam(torch.optim.Adam):
         if net._ema is not None and net._ema_p is not None:
             sd["ema"] = {"decay": net._ema[0], "warmup": net._ema[1], "params": net._ema_p.clone(),
                          "running_mean": net._ema_rm.clone(), "running_var": net._ema_rv.clone()}
+        if net.weight_decay > 0.0:
+            sd["decay_params"] = net.decayed_parameter_names()
         return sd
 
     def load_state_dict(self, state_dict):
@@ -1030,6 +1107,9 @@ class HipAdam(torch.optim.Adam):
                 m.copy_(e["exp_avg"])
                 v.copy_(e["exp_avg_sq"])
                 self._step = int(e["step"])
+        if state_dict.get("decay_params") is not None:        # the value itself came with param_groups
+            self._decay_params = [str(k) for k in state_dict["decay_params"]]
+            self._net.set_weight_decay(self.param_groups[0].get("weight_decay", 0.0), self._decay_params)
         ema = state_dict.get("ema")
         if ema is not None:
             net = self._net

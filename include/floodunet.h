@@ -319,6 +319,31 @@ int fu_set_grad_clip(fu_ctx* ctx, double max_norm);
  * armed on this context.  Any pointer may be NULL. */
 int fu_grad_clip_state(fu_ctx* ctx, float* last_norm, float* last_coef, int64_t* steps, int64_t* clipped_steps,
                        int64_t* nonfinite_steps);
+/* Decoupled weight decay (torch.optim.AdamW, single-tensor path) inside the same one launch.  weight_decay > 0 arms it, 0
+ * disarms it, a negative or non-finite value is FU_ERR_INVALID.  decay_mask is a HOST array of n_mask == fu_num_params()
+ * flags in parameter order (non-zero: the tensor decays), or NULL for the default rule: every tensor with ndim >= 2 (conv,
+ * transposed-conv, 1x1 fusion and head weights) decays, biases and BatchNorm weight / bias do not.  A wrong n_mask, or a mask
+ * whose flagged tensors form more than 512 separate ranges of the flat buffer, is FU_ERR_INVALID.  The call copies the
+ * sorted bounds of those ranges into device memory it allocates once per context (and synchronises the device), so arm
+ * before capturing a step; after a change of the setting a captured step must be captured again.
+ * While armed with at least one flagged tensor, every fu_adam_step[_dev] / fu_adam_ema_step[_dev] launches the decay-aware
+ * twin of its kernel (k_adamw, k_adamw_ema, k_adamw_dev, k_adamw_ema_dev): each element of a flagged tensor is first
+ * multiplied by d = (float)(1.0 - lr * weight_decay) -- param.mul_(1 - lr * weight_decay): d formed in double and rounded
+ * once, one fp32 multiply -- and the update of fu_adam_step then runs on that value, the same float sequence bit for bit.
+ * The moments see the gradient only; the gradient norm and the clip coefficient are unaffected; the EMA takes the value
+ * after decay and update; a skipped step (the FU_F16 guard, a non-finite clip norm) skips the decay too.
+ * fu_adam_step / fu_adam_ema_step form d from their own lr.  The _dev forms read NINE floats from scalars_dev while decay is
+ * armed -- fu_adamw_scalars' -- in the plain form too (slot 7, the EMA weight, is then ignored): a buffer of 7 or 8 floats
+ * is TOO SHORT for an armed context.  With decay disarmed, or armed with no tensor flagged, the step issues exactly the
+ * launches it issues without this feature and reads 7 (8) floats. */
+int fu_set_weight_decay(fu_ctx* ctx, double weight_decay, const uint8_t* decay_mask, int n_mask);
+/* The nine scalars of the captured form: out[0..6] are fu_adam_scalars' seven values bit for bit, out[7] = (float)ema_weight
+ * (0 for the plain form), out[8] = (float)(1.0 - lr * weight_decay) -- exactly 1.0f for weight_decay = 0. */
+int fu_adamw_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale, double ema_weight,
+                     double weight_decay, float out[9]);
+/* What is armed: *weight_decay (0 when disarmed) and, in mask_out[0 .. n_mask - 1] with n_mask == fu_num_params(), the
+ * per-tensor flags (all 0 when disarmed).  Either pointer may be NULL.  Host bookkeeping only. */
+int fu_weight_decay_state(const fu_ctx* ctx, double* weight_decay, uint8_t* mask_out, int n_mask);
 /* The gradient norms without a copy to the host: torch.linalg.vector_norm(p.grad) per parameter and of all of them.
  * norms_out_dev: fu_num_params() + 1 device floats -- every tensor's L2 norm times |grad_scale| in parameter order, then
  * the total -- from the same two launches (squares and sums in double, rounded to float once).  Works whether or not
