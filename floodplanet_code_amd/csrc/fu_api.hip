@@ -1,6 +1,6 @@
 // libfloodunet: the C ABI (include/floodunet.h) -- every entry point checks its arguments here and calls into the plan
-// (fu_plan.hip), the step (fu_step.hip) or a launcher; the single operators are in fu_ops.hip, data parallelism in
-// fu_dp.hip, the context itself in fu_ctx.h.  Also the error-message storage.
+// (fu_plan.hip), the step (fu_step.hip) or a launcher; the single operators are in fu_ops.hip, the optimiser's entry points
+// in fu_optim_api.hip, data parallelism in fu_dp.hip, the context itself in fu_ctx.h.  Also the error-message storage.
 //
 // Data layout in HBM (all owned by the context, one arena allocation):
 //   activations  NHWC, element type = precision (fp32 or bf16); for every 3x3 conv only its RAW output y
@@ -161,18 +161,6 @@ int fu_bind_buffers(fu_ctx* c, float* params, float* grads, float* running_mean,
   c->P = params; c->G = grads; c->RM = running_mean; c->RV = running_var; c->NBT = num_batches_tracked;
   c->packed_dirty = true;
   c->pack_tabs.clear();
-  return FU_OK;
-}
-int fu_bind_adam_state(fu_ctx* c, float* exp_avg, float* exp_avg_sq) {
-  FU_REQUIRE(c && exp_avg && exp_avg_sq, "fu_bind_adam_state: null argument");
-  c->adam_m = exp_avg; c->adam_v = exp_avg_sq;
-  return FU_OK;
-}
-int fu_bind_ema_state(fu_ctx* c, float* ema_params, float* ema_running_mean, float* ema_running_var) {
-  FU_REQUIRE(c, "null context");
-  const int given = (ema_params != nullptr) + (ema_running_mean != nullptr) + (ema_running_var != nullptr);
-  FU_REQUIRE(given == 0 || given == 3, "fu_bind_ema_state: give all three buffers, or all NULL to unbind");
-  c->ema_p = ema_params; c->ema_rm = ema_running_mean; c->ema_rv = ema_running_var;
   return FU_OK;
 }
 int fu_params_changed(fu_ctx* c) {
@@ -452,222 +440,6 @@ int fu_block_param_range(const fu_ctx* c, int block, int64_t* flat_offset, int64
   const ParamInfo& z = c->params[first + count - 1];
   if (flat_offset) *flat_offset = a.off;
   if (numel) *numel = z.off + z.numel - a.off;
-  return FU_OK;
-}
-
-namespace {
-// The one optimiser step behind fu_adam_step[_dev] and fu_adam_ema_step[_dev] (ema: the averages go in the same launch):
-// moments bound?, fp16 guard, launch, guard book.  sc: nine host scalars (slots 7 and 8 only read with ema / with decay armed),
-// or scalars_dev: the same floats on the device.
-inline bool decay_armed(const fu_ctx* c) { return c->weight_decay > 0.0 && c->wd_nb > 0; }
-// the ninth scalar of a step called with its own lr: (float)(1 - lr * weight_decay), formed in double and rounded once
-inline float decay_factor(const fu_ctx* c, double lr) { return (float)(1.0 - lr * c->weight_decay); }
-int adam_step(fu_ctx* c, const char* who, bool ema, const float* sc, const float* scalars_dev, fu_stream stream) {
-  if (!c->adam_m || !c->adam_v) {
-    set_error("%s: no moment buffers bound (fu_bind_adam_state)", who);
-    return FU_ERR_STATE;
-  }
-  if (ema && !c->ema_p) {
-    set_error("%s: no EMA buffers bound (fu_bind_ema_state)", who);
-    return FU_ERR_STATE;
-  }
-  // fp16: an overflowed gradient map leaves inf / NaN in the gradient buffer -- such a step is skipped and the loss scale
-  // backs off (the guard kernels in fu_optim.hip); 13 us of the 69 MB gradient read per step, fp16 mode only
-  const int* skip = nullptr;
-  if (c->prec == PREC_F16) {
-    FU_TRY(launch_grad_finite_check(c->G, c->total_params, c->guard, (hipStream_t)stream));
-    skip = c->guard;
-  }
-  // clipping armed (fu_set_grad_clip): the norm pass and its one-workgroup finalize go first and leave the scalars, with the
-  // coefficient folded into the gradient scale, in the context's own eight floats; the Adam launch is the _dev form on those,
-  // whichever entry point was called.  A non-finite norm skips the step (fp16: the guard's flag, set together with it)
-  // decay armed (fu_set_weight_decay) on at least one tensor: the scalars are nine floats and the launch is the k_adamw*
-  // twin, which also gets the bounds of the decayed ranges; otherwise exactly the launch there has always been
-  const bool wd = decay_armed(c);
-  if (c->clip_max_norm > 0.0) {
-    FU_TRY(launch_grad_sqnorm(c->clip, c->G, (hipStream_t)stream));
-    FU_TRY(launch_grad_clip_finalize(c->clip, sc, scalars_dev, ema, wd, c->clip_max_norm, (hipStream_t)stream));
-    sc = nullptr;
-    scalars_dev = c->clip.scalars;
-    if (!skip) skip = &c->clip.state->skip;
-  }
-  const AdamEma avg = {c->ema_p, c->ema_rm, c->RM, c->ema_rv, c->RV, c->total_bn};
-  const AdamDecay dec = {c->wd_bounds, c->wd_nb};
-  FU_TRY(launch_adam(c->P, c->G, c->adam_m, c->adam_v, c->total_params, ema ? &avg : nullptr, sc, scalars_dev,
-                     (hipStream_t)stream, skip, wd ? &dec : nullptr));
-  if (c->prec == PREC_F16) FU_TRY(launch_guard_book(c->guard, (hipStream_t)stream));
-  c->packed_dirty = true;
-  return FU_OK;
-}
-}  // namespace
-
-int fu_adam_step(fu_ctx* c, double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
-                 fu_stream stream) {
-  FU_REQUIRE(c && c->P && c->G, "fu_adam_step: parameter / gradient buffers not bound");
-  FU_REQUIRE(step >= 1, "fu_adam_step: step is 1-based");
-  float sc[9] = {};
-  adam_scalars(lr, beta1, beta2, eps, step, grad_scale, sc);
-  sc[8] = decay_factor(c, lr);
-  return adam_step(c, "fu_adam_step", false, sc, nullptr, stream);
-}
-
-int fu_fp16_guard_state(fu_ctx* c, int64_t* skipped_steps, int32_t* backoff_exponent) {
-  FU_REQUIRE(c, "null context");
-  int h[4] = {0, 0, 0, 0};
-  if (c->prec == PREC_F16) FU_HIP_CHECK(hipMemcpy(h, c->guard, sizeof(h), hipMemcpyDeviceToHost));   // synchronises
-  if (skipped_steps) *skipped_steps = h[1];
-  if (backoff_exponent) *backoff_exponent = h[2];
-  return FU_OK;
-}
-
-int fu_adam_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale, float out[7]) {
-  FU_REQUIRE(out && step >= 1, "fu_adam_scalars: bad argument");
-  adam_scalars(lr, beta1, beta2, eps, step, grad_scale, out);
-  return FU_OK;
-}
-
-int fu_adam_step_dev(fu_ctx* c, const float* scalars_dev, fu_stream stream) {
-  FU_REQUIRE(c && c->P && c->G && scalars_dev, "fu_adam_step_dev: parameter / gradient buffers not bound, or null scalars");
-  return adam_step(c, "fu_adam_step_dev", false, nullptr, scalars_dev, stream);
-}
-
-int fu_adam_ema_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
-                        double ema_weight, float out[8]) {
-  FU_REQUIRE(out && step >= 1, "fu_adam_ema_scalars: bad argument");
-  FU_REQUIRE(ema_weight >= 0.0 && ema_weight <= 1.0, "fu_adam_ema_scalars: ema_weight %g outside [0, 1]", ema_weight);
-  adam_scalars(lr, beta1, beta2, eps, step, grad_scale, out);
-  out[7] = (float)ema_weight;
-  return FU_OK;
-}
-
-int fu_adam_ema_step(fu_ctx* c, double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
-                     double ema_weight, fu_stream stream) {
-  FU_REQUIRE(c && c->P && c->G && c->RM && c->RV, "fu_adam_ema_step: buffers not bound (fu_bind_buffers)");
-  float sc[9] = {};
-  FU_TRY(fu_adam_ema_scalars(lr, beta1, beta2, eps, step, grad_scale, ema_weight, sc));
-  sc[8] = decay_factor(c, lr);
-  return adam_step(c, "fu_adam_ema_step", true, sc, nullptr, stream);
-}
-
-int fu_adam_ema_step_dev(fu_ctx* c, const float* scalars_dev, fu_stream stream) {
-  FU_REQUIRE(c && c->P && c->G && c->RM && c->RV && scalars_dev,
-             "fu_adam_ema_step_dev: buffers not bound (fu_bind_buffers), or null scalars");
-  return adam_step(c, "fu_adam_ema_step_dev", true, nullptr, scalars_dev, stream);
-}
-
-namespace {
-// the chunk table, partials, state block and scalars of the gradient norm: made once per context, at the first use
-int ensure_grad_clip(fu_ctx* c) {
-  if (c->clip.chunks) return FU_OK;
-  std::vector<int64_t> off, numel;
-  for (const ParamInfo& p : c->params) { off.push_back(p.off); numel.push_back(p.numel); }
-  FU_HIP_CHECK(hipSetDevice(c->cfg.device));
-  return build_grad_clip(&c->clip, off.data(), numel.data(), (int)c->params.size(), &c->extra_allocs);
-}
-}  // namespace
-
-int fu_set_grad_clip(fu_ctx* c, double max_norm) {
-  FU_REQUIRE(c, "null context");
-  FU_REQUIRE(isfinite(max_norm) && max_norm >= 0.0, "fu_set_grad_clip: max_norm %g must be finite and >= 0 (0 disarms)", max_norm);
-  if (max_norm > 0.0) FU_TRY(ensure_grad_clip(c));
-  c->clip_max_norm = max_norm;
-  return FU_OK;
-}
-
-int fu_grad_clip_state(fu_ctx* c, float* last_norm, float* last_coef, int64_t* steps, int64_t* clipped_steps,
-                       int64_t* nonfinite_steps) {
-  FU_REQUIRE(c, "null context");
-  ClipState h = {};
-  if (c->clip.state) {
-    FU_HIP_CHECK(hipSetDevice(c->cfg.device));
-    FU_HIP_CHECK(hipDeviceSynchronize());                  // every stream: the step may run on a non-blocking one
-    FU_HIP_CHECK(hipMemcpy(&h, c->clip.state, sizeof(h), hipMemcpyDeviceToHost));
-  }
-  if (last_norm) *last_norm = h.last_norm;
-  if (last_coef) *last_coef = h.last_coef;
-  if (steps) *steps = h.steps;
-  if (clipped_steps) *clipped_steps = h.clipped;
-  if (nonfinite_steps) *nonfinite_steps = h.nonfinite;
-  return FU_OK;
-}
-
-int fu_adamw_scalars(double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale, double ema_weight,
-                     double weight_decay, float out[9]) {
-  FU_REQUIRE(out && step >= 1, "fu_adamw_scalars: bad argument");
-  FU_REQUIRE(isfinite(weight_decay) && weight_decay >= 0.0, "fu_adamw_scalars: weight_decay %g must be finite and >= 0",
-             weight_decay);
-  FU_TRY(fu_adam_ema_scalars(lr, beta1, beta2, eps, step, grad_scale, ema_weight, out));
-  out[8] = (float)(1.0 - lr * weight_decay);
-  return FU_OK;
-}
-
-int fu_set_weight_decay(fu_ctx* c, double weight_decay, const uint8_t* decay_mask, int n_mask) {
-  FU_REQUIRE(c, "null context");
-  FU_REQUIRE(isfinite(weight_decay) && weight_decay >= 0.0,
-             "fu_set_weight_decay: weight_decay %g must be finite and >= 0 (0 disarms)", weight_decay);
-  const int np = (int)c->params.size();
-  FU_REQUIRE(!decay_mask || n_mask == np, "fu_set_weight_decay: a mask of %d flags for %d parameter tensors", n_mask, np);
-  if (weight_decay == 0.0) {
-    c->weight_decay = 0.0;
-    c->wd_nb = 0;
-    c->wd_mask.assign(np, 0);
-    return FU_OK;
-  }
-  // default rule: every tensor with two or more dimensions (conv, transposed-conv, fusion and head weights); biases and
-  // BatchNorm weight / bias do not decay
-  std::vector<uint8_t> mask(np);
-  std::vector<int64_t> off(np), numel(np), bounds;
-  for (int t = 0; t < np; ++t) {
-    const ParamInfo& p = c->params[t];
-    mask[t] = decay_mask ? (decay_mask[t] != 0) : (p.ndim >= 2);
-    off[t] = p.off;
-    numel[t] = p.numel;
-  }
-  plan_decay_bounds(off.data(), numel.data(), mask.data(), np, &bounds);
-  FU_REQUIRE(bounds.size() <= (size_t)2 * WD_MAX_RANGES, "fu_set_weight_decay: the mask forms %d ranges of the flat buffer, at most %d supported",
-             (int)(bounds.size() / 2), WD_MAX_RANGES);
-  if (!bounds.empty()) {
-    FU_HIP_CHECK(hipSetDevice(c->cfg.device));
-    if (!c->wd_bounds) {                 // one table of the full size per context: a later mask is copied over it
-      FU_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->wd_bounds), (size_t)2 * WD_MAX_RANGES * sizeof(int64_t)));
-      c->extra_allocs.push_back(c->wd_bounds);
-    }
-    FU_HIP_CHECK(hipDeviceSynchronize());                    // no step in flight reads the table while it changes
-    FU_HIP_CHECK(hipMemcpy(c->wd_bounds, bounds.data(), bounds.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  }
-  c->weight_decay = weight_decay;
-  c->wd_nb = (int)bounds.size();
-  c->wd_mask = mask;
-  return FU_OK;
-}
-
-int fu_weight_decay_state(const fu_ctx* c, double* weight_decay, uint8_t* mask_out, int n_mask) {
-  FU_REQUIRE(c, "null context");
-  const int np = (int)c->params.size();
-  FU_REQUIRE(!mask_out || n_mask == np, "fu_weight_decay_state: room for %d flags, %d parameter tensors", n_mask, np);
-  if (weight_decay) *weight_decay = c->weight_decay;
-  if (mask_out)
-    for (int t = 0; t < np; ++t) mask_out[t] = (c->weight_decay > 0.0 && t < (int)c->wd_mask.size()) ? c->wd_mask[t] : 0;
-  return FU_OK;
-}
-
-int fu_grad_norms(fu_ctx* c, double grad_scale, float* norms_out_dev, fu_stream stream) {
-  FU_REQUIRE(c && c->G && norms_out_dev, "fu_grad_norms: no gradient buffer bound, or null output");
-  FU_TRY(ensure_grad_clip(c));
-  FU_TRY(launch_grad_sqnorm(c->clip, c->G, (hipStream_t)stream));
-  return launch_grad_norms_out(c->clip, grad_scale, norms_out_dev, (hipStream_t)stream);
-}
-
-int fu_adam_state(fu_ctx* c, float** exp_avg, float** exp_avg_sq) {
-  FU_REQUIRE(c, "null context");
-  if (exp_avg) *exp_avg = c->adam_m;
-  if (exp_avg_sq) *exp_avg_sq = c->adam_v;
-  return FU_OK;
-}
-
-int fu_zero_grads(fu_ctx* c, fu_stream stream) {
-  FU_REQUIRE(c && c->G, "fu_zero_grads: no gradient buffer bound");
-  FU_HIP_CHECK(hipMemsetAsync(c->G, 0, c->total_params * sizeof(float), (hipStream_t)stream));
   return FU_OK;
 }
 

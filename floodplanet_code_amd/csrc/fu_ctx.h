@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/floodunet.h"
 #include "fu_common.h"
+#include "fu_optim.h"
 
 #include <string>
 #include <vector>
@@ -128,6 +129,21 @@ struct Arena {
   }
 };
 
+// The optimiser's state in a context: what fu_optim_api.hip's entry points bind, arm and read
+struct OptimState {
+  float* adam_m = nullptr;        // bound (caller-owned, fu_bind_adam_state): the moments outlive the context
+  float* adam_v = nullptr;
+  float* ema_p = nullptr;         // bound (caller-owned, fu_bind_ema_state): the weight EMA and the EMA of the running statistics
+  float* ema_rm = nullptr;
+  float* ema_rv = nullptr;
+  double clip_max_norm = 0.0;     // fu_set_grad_clip: > 0 = the optimiser step clips the global gradient norm to it
+  GradClip clip;                  // its chunk table, partials, state block and scalars (made at the first use; extra_allocs)
+  double weight_decay = 0.0;      // fu_set_weight_decay: > 0 = the optimiser step decays the flagged tensors (AdamW)
+  std::vector<uint8_t> wd_mask;   // its per-tensor flags in parameter order (empty: never armed)
+  int64_t* wd_bounds = nullptr;   // device: the sorted bounds of the decayed ranges (AdamDecay; extra_allocs, made once)
+  int wd_nb = 0;                  // bounds in use (0: no tensor decays -- the plain kernels run)
+};
+
 }  // namespace fu
 
 struct Dp;   // fu_dp.hip
@@ -190,17 +206,7 @@ struct fu_ctx {
   unsigned long long* conf_tmp = nullptr;
   int64_t* n_valid = nullptr;
   fu::DeviceTable stitch_table, scene_table, train_table;   // fu_stitch_add_batch[_probs, _windowed] / fu_scene_crops / fu_scene_train_tiles
-  float* adam_m = nullptr;        // bound (caller-owned, fu_bind_adam_state): the moments outlive the context
-  float* adam_v = nullptr;
-  float* ema_p = nullptr;         // bound (caller-owned, fu_bind_ema_state): the weight EMA and the EMA of the running statistics
-  float* ema_rm = nullptr;
-  float* ema_rv = nullptr;
-  double clip_max_norm = 0.0;     // fu_set_grad_clip: > 0 = the optimiser step clips the global gradient norm to it
-  fu::GradClip clip;              // its chunk table, partials, state block and scalars (made at the first use; extra_allocs)
-  double weight_decay = 0.0;      // fu_set_weight_decay: > 0 = the optimiser step decays the flagged tensors (AdamW)
-  std::vector<uint8_t> wd_mask;   // its per-tensor flags in parameter order (empty: never armed)
-  int64_t* wd_bounds = nullptr;   // device: the sorted bounds of the decayed ranges (fu::AdamDecay; extra_allocs, made once)
-  int wd_nb = 0;                  // bounds in use (0: no tensor decays -- the plain kernels run)
+  fu::OptimState opt;             // everything the optimiser step keeps (fu_optim_api.hip)
   fu::Profiler prof;
   struct Dp* dp = nullptr;            // fu_dp_init: RCCL communicator, communication stream, events
   std::vector<fu::PackTable> pack_tabs;   // <= MAX_PACK layers per launch

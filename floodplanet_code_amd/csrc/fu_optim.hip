@@ -2,7 +2,7 @@
 // weight decay in the same pass, and the fp16 guard around it (non-finite gradient check, skipped-step book-keeping); the
 // global gradient norm and the clip coefficient ahead of it (two launches of their own: the Adam kernels only ever see
 // another gscale).
-#include "fu_common.h"
+#include "fu_optim.h"
 
 #include <algorithm>
 #include <math.h>
@@ -443,12 +443,11 @@ int launch_grad_sqnorm(const GradClip& w, const float* g, hipStream_t s) {
   FU_LAUNCH_CHECK();
   return 0;
 }
-int launch_grad_clip_finalize(const GradClip& w, const float* sc, const float* sc_dev, bool ema, bool wd, double max_norm,
-                              hipStream_t s) {
+int launch_grad_clip_finalize(const GradClip& w, const float* sc, const float* sc_dev, int n, double max_norm, hipStream_t s) {
   ClipScalars scv = {};
-  if (!sc_dev) for (int k = 0; k < 9; ++k) scv.v[k] = (k < 7 || (k == 7 && ema) || (k == 8 && wd)) ? sc[k] : 0.f;
+  if (!sc_dev) for (int k = 0; k < n; ++k) scv.v[k] = sc[k];
   hipLaunchKernelGGL(k_grad_norm_finalize, dim3(1), dim3(256), 0, s, w.part, w.first, w.nparams, w.nchunks, scv, sc_dev,
-                     wd ? 9 : ema ? 8 : 7, max_norm, w.scalars, w.state, (float*)nullptr, 0.0);
+                     n, max_norm, w.scalars, w.state, (float*)nullptr, 0.0);
   FU_LAUNCH_CHECK();
   return 0;
 }

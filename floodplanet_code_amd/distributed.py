@@ -23,6 +23,7 @@ import torch
 import torch.distributed as dist
 
 from .loss_options import LossOptions
+from .optim_options import OptimOptions, option_properties
 
 # rehearsal knob: drive the block-wise backward (the multi-GPU code path) in a single process
 _FORCE_BLOCKS = os.environ.get("FU_DP_FORCE_BLOCKS") == "1"
@@ -118,6 +119,7 @@ class BucketedReducer:
         self._host_wait_s.clear()
 
 
+@option_properties          # ema_decay, ema_warmup, grad_clip_norm, weight_decay, decay_all: read from optim_options
 class DataParallelTrainer:
     """fwd + CE + block-wise bwd (+ overlapped all-reduce) + fused Adam on a HipUNet."""
 
@@ -148,12 +150,10 @@ class DataParallelTrainer:
         (HipUNet.set_weight_decay), on every tensor with ndim >= 2, or with decay_all on every tensor.  The factor
         1 - lr * weight_decay is formed from self.lr at every step -- on the captured path it is the ninth of the scalars
         refreshed per replay -- so self.lr may change between steps.  Rank-local like the EMA."""
-        if ema_decay is not None:
-            net.enable_ema(ema_decay, ema_warmup)
-        if grad_clip_norm is not None:
-            net.set_grad_clip(grad_clip_norm)
-        if weight_decay or decay_all:
-            net.set_weight_decay(weight_decay, "all" if decay_all else "weights")
+        # checked on the host, once, and armed on the net in one call; a net's own decay stays when this trainer has none
+        self.optim_options = OptimOptions.make(ema_decay=ema_decay, ema_warmup=ema_warmup, grad_clip_norm=grad_clip_norm,
+                                               weight_decay=weight_decay, decay_all=decay_all)
+        net.apply_optim_options(self.optim_options)
         self.net, self.lr, self.world_size, self.rank = net, lr, world_size, rank
         # checked on the host, once; every step hands this one object to HipUNet._loss_raw
         self.loss_options = LossOptions.make(net.n_classes, class_weight=class_weight, label_smoothing=label_smoothing,
@@ -168,16 +168,14 @@ class DataParallelTrainer:
         self.time_waits = time_waits
         # graph=True (single device): the whole step -- fu_forward, fu_loss_ce, fu_backward with its side-stream fork / join,
         # fu_adam_step_dev (fu_adam_ema_step_dev with a weight EMA) -- is captured once into a hipGraph (torch.cuda.CUDAGraph on
-        # the capture stream the C calls are issued on) and replayed; only the seven Adam scalars (eight with the EMA weight, nine with weight decay),
-        # which depend on the step count, are refreshed per step.  The
+        # the capture stream the C calls are issued on) and replayed; only the nine step scalars (Adam's seven, the EMA weight,
+        # the decay factor), which depend on the step count and on lr, are refreshed per step.  The
         # captured launches are valid for ONE (x, target) pair of device buffers: other tensors are copied into them.
         self.graph = bool(graph) and world_size <= 1
         self._graph = None
         self._gx = self._gt = self._gloss = self._gscal = self._gscal_host = None
         self._g_ignore = None
-        self._g_ema = False
-        self._g_clip = None            # the clip norm the captured step was recorded with (None: no norm launches in it)
-        self._g_decay = None           # the weight decay and flags it was recorded with (None: the plain Adam launch in it)
+        self._g_optim = None           # the net's optim_key() the captured step was recorded with: (EMA launch?, clip norm, decay key)
         self._reducer: Optional[BucketedReducer] = None
         self._launch_stream = None     # the stream the bucket all-reduces are launched from (mode 2, fu_backward_fence)
         self._synced = False
@@ -210,24 +208,15 @@ class DataParallelTrainer:
     def _adam_scalars_to_device(self, step: int):
         import ctypes as C
         from . import _lib
-        ema = self.net._ema
-        if self._g_decay is not None:    # nine scalars: slot 7 the EMA weight (0 without one), slot 8 this step's decay factor
-            from .ema import ema_weight
-            buf = (C.c_float * 9)()
-            _lib.check(_lib.load().fu_adamw_scalars(float(self.lr), float(self.betas[0]), float(self.betas[1]),
-                                                    float(self.eps), int(step), 1.0,
-                                                    ema_weight(ema[0], int(step), ema[1]) if self._g_ema else 0.0,
-                                                    float(self._g_decay[0]), buf))
-        elif self._g_ema:                # eight scalars: the EMA weight of this update rides behind Adam's seven
-            from .ema import ema_weight
-            buf = (C.c_float * 8)()
-            _lib.check(_lib.load().fu_adam_ema_scalars(float(self.lr), float(self.betas[0]), float(self.betas[1]),
-                                                       float(self.eps), int(step), 1.0,
-                                                       ema_weight(ema[0], int(step), ema[1]), buf))
-        else:
-            buf = (C.c_float * 7)()
-            _lib.check(_lib.load().fu_adam_scalars(float(self.lr), float(self.betas[0]), float(self.betas[1]),
-                                                   float(self.eps), int(step), 1.0, buf))
+        from .ema import ema_weight
+        # always nine: slots 0-6 are fu_adam_scalars' bits, slot 7 the EMA weight (0 without one), slot 8 this step's decay
+        # factor (1 without decay); the captured launches read the slots their mode uses
+        ema, decay = self.net._ema, self._g_optim[2]
+        buf = (C.c_float * 9)()
+        _lib.check(_lib.load().fu_adamw_scalars(float(self.lr), float(self.betas[0]), float(self.betas[1]),
+                                                float(self.eps), int(step), 1.0,
+                                                ema_weight(ema[0], int(step), ema[1]) if self._g_optim[0] else 0.0,
+                                                float(decay[0]) if decay is not None else 0.0, buf))
         # A ring of pinned slots, each guarded by an event recorded behind its host-to-device copy: nothing in a replayed step
         # synchronises, so the host runs steps ahead of the GPU, and ONE pinned buffer would be rewritten for step k+1, k+2, ...
         # before the copy of step k has executed (the replay of step k would then take a later step's bias corrections).
@@ -249,12 +238,9 @@ class DataParallelTrainer:
         self._gx, self._gt, self._g_ignore = torch.empty_like(x), torch.empty_like(target), int(ignore_index)
         self._gx.copy_(x)
         self._gt.copy_(target)
-        self._g_ema = net.ema_enabled                                 # which optimiser launch this graph holds
-        self._g_clip = net.grad_clip                                  # ... and whether the two norm launches go ahead of it
-        self._g_decay = net._decay_key()                              # ... and whether the Adam launch is the decay-aware one
-        n_scal = 9 if self._g_decay is not None else 8 if self._g_ema else 7
-        self._gscal = torch.zeros(n_scal, dtype=torch.float32, device=dev)
-        self._gscal_ring = [torch.zeros(n_scal, dtype=torch.float32).pin_memory() for _ in range(8)]
+        self._g_optim = net.optim_key()                               # which optimiser launches this graph holds
+        self._gscal = torch.zeros(9, dtype=torch.float32, device=dev)
+        self._gscal_ring = [torch.zeros(9, dtype=torch.float32).pin_memory() for _ in range(8)]
         self._gscal_ev = [None] * 8
         lib = _lib.load()
         net._class_weight_dev(self.class_weight, dev)                # the weights' upload stays outside the capture
@@ -267,7 +253,7 @@ class DataParallelTrainer:
             net._forward_raw(self._gx, True, want_logits=False)
             self._gloss = net._loss_raw(self._gt, self._g_ignore, dev, options=self.loss_options)
             net._backward_raw(None, dev)
-            if self._g_ema:
+            if self._g_optim[0]:
                 _lib.check(lib.fu_adam_ema_step_dev(net._ctx, self._gscal.data_ptr(), net._stream(dev)))
             else:
                 _lib.check(lib.fu_adam_step_dev(net._ctx, self._gscal.data_ptr(), net._stream(dev)))
@@ -284,8 +270,7 @@ class DataParallelTrainer:
     def _graph_step(self, x, target, ignore_index):
         net = self.net
         if self._graph is not None and (int(ignore_index) != self._g_ignore or x.shape != self._gx.shape
-                                        or self._g_ema != net.ema_enabled or self._g_clip != net.grad_clip
-                                        or self._g_decay != net._decay_key()):
+                                        or self._g_optim != net.optim_key()):
             self._graph = None                                        # another workload: capture again
         if self._graph is None:
             if net._ctx is None or net._ctx_key[1:3] != tuple(x.shape[2:]) or net._ctx_key[3] < x.shape[0]:

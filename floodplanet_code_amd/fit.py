@@ -35,7 +35,8 @@ import torch
 
 from .models import build_model
 from .schedule import KINDS as LR_SCHEDULES, check_schedule, lr_at
-from .unet import check_focal_gamma, check_grad_clip, check_region_loss, check_weight_decay
+from .optim_options import OptimOptions
+from .unet import check_focal_gamma, check_region_loss
 
 SCHEDULE_OPTIONS = ("lr_schedule", "warmup_steps", "min_lr")       # cfg keys, present only when the command line gave them
 
@@ -118,7 +119,8 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
             per_epoch = min(per_epoch, int(c["limit_train_batches"]))
         schedule = dict(base_lr=float(c["lr"]), kind=kind, total_steps=per_epoch * int(c["n_epochs"]), warmup_steps=warmup,
                         min_lr=min_lr)
-    clipping = getattr(model, "grad_clip_norm", None) is not None
+    optim = model.optim_options
+    clipping = optim.grad_clip_norm is not None
     n_steps = 0
     best: List = []                                                          # (metric, path), top-k
     ckpt_dir = os.path.join(exp_dir, "checkpoints") if exp_dir else None
@@ -161,7 +163,7 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
         if clip_state is not None:
             history[-1]["grad_norm"] = clip_state["grad_norm"]               # the last step's, before clipping
             history[-1]["clipped_steps"] = clip_state["clipped_steps"]       # of the run so far
-        if getattr(model, "weight_decay", 0.0) > 0.0:
+        if optim.weight_decay > 0.0:
             history[-1]["weight_decay"] = float(opt.param_groups[0]["weight_decay"])
             history[-1]["decayed_tensors"] = len(model.model.decayed_parameter_names())
         plan =getattr(train_loader, "last_plan", None)                      # a loader that chooses its tiles says which
@@ -342,35 +344,16 @@ def cfg_from_args(args, class_weights=None) -> dict:
     parsed = parse_class_weights(getattr(args, "class_weights", None), N_CLASSES)
     if class_weights is None and parsed is not None and parsed != "balanced":
         class_weights = parsed
-    loss_kwargs = {}
+    extension_kwargs = {}                  # the model keywords beyond the reference's: the loss options, then the optimiser's
     if class_weights is not None:
-        loss_kwargs["class_weights"] = [float(v) for v in class_weights]
+        extension_kwargs["class_weights"] = [float(v) for v in class_weights]
     if float(getattr(args, "label_smoothing", 0.0)) != 0.0:
-        loss_kwargs["label_smoothing"] = float(args.label_smoothing)
+        extension_kwargs["label_smoothing"] = float(args.label_smoothing)
     gamma = check_focal_gamma(getattr(args, "focal_gamma", 0.0), getattr(args, "label_smoothing", 0.0))
     if gamma != 0.0:
-        loss_kwargs["focal_gamma"] = gamma
-    loss_kwargs.update(region_from_args(args))
-    if getattr(args, "ema_decay", None) is not None:
-        from .ema import check_decay
-        loss_kwargs["ema_decay"] = check_decay(args.ema_decay)
-        loss_kwargs["ema_warmup"] = not getattr(args, "no_ema_warmup", False)
-    elif getattr(args, "no_ema_warmup", False):
-        raise ValueError("--no_ema_warmup needs --ema_decay")
-    if getattr(args, "grad_clip", None) is not None:
-        clip = check_grad_clip(args.grad_clip)
-        if clip is None:
-            raise ValueError("--grad_clip must be > 0 (leave the option out for no clipping)")
-        loss_kwargs["grad_clip_norm"] = clip
-    if getattr(args, "weight_decay", None) is not None:
-        decay = check_weight_decay(args.weight_decay)
-        if decay == 0.0:
-            raise ValueError("--weight_decay must be > 0 (leave the option out for no decay)")
-        loss_kwargs["weight_decay"] = decay
-        if getattr(args, "decay_all", False):
-            loss_kwargs["decay_all"] = True
-    elif getattr(args, "decay_all", False):
-        raise ValueError("--decay_all needs --weight_decay")
+        extension_kwargs["focal_gamma"] = gamma
+    extension_kwargs.update(region_from_args(args))
+    extension_kwargs.update(OptimOptions.from_args(args).given_kwargs())
     schedule = schedule_from_args(args)
     sampling = sampling_from_args(args)
     cfg = dict(lr=args.lr, batch_size=args.batch_size, n_epochs=args.n_epochs, crop_height=args.crop[0],
@@ -380,7 +363,7 @@ def cfg_from_args(args, class_weights=None) -> dict:
                norm_mode=norm_mode, norm_params=args.norm_params,
                dataset=dict(name="floodplanet", sensor=args.sensor, channels=args.channels, dataset_kwargs=None),
                model=dict(name=args.model, model_kwargs=dict(optimizer_name="adam", base_channels=args.base_channels,
-                                                             precision=args.precision, **loss_kwargs)))
+                                                             precision=args.precision, **extension_kwargs)))
     if sampling:
         cfg["sampling"] = sampling
     cfg.update(schedule)

@@ -34,11 +34,22 @@ import torch.optim as optim
 
 from ..lightning_compat import LightningModule
 from ..metrics import SegmentationMetrics
-from ..ema import check_decay
 from ..loss_options import LossOptions
-from ..unet import HipAdam, HipUNet, check_class_weight, check_grad_clip, check_label_smoothing, check_weight_decay
+from ..optim_options import OptimOptions, option_properties
+from ..unet import HipAdam, HipUNet, check_class_weight, check_label_smoothing
+
+# FU_TORCH_ADAM=1 keeps torch's own optimiser, which has none of these: the refusal of each option that is set
+_TORCH_ADAM_REFUSALS = {
+    "ema_decay": "the weight EMA is part of the fused Adam kernel (HipAdam): FU_TORCH_ADAM=1 together with ema_decay is not "
+                 "supported",
+    "grad_clip_norm": "gradient clipping runs ahead of the fused Adam kernel (HipAdam): FU_TORCH_ADAM=1 together with "
+                      "grad_clip_norm is not supported",
+    "weight_decay": "weight decay is part of the fused Adam kernel (HipAdam): FU_TORCH_ADAM=1 together with weight_decay is "
+                    "not supported",
+}
 
 
+@option_properties          # ema_decay, ema_warmup, grad_clip_norm, weight_decay, decay_all: read from optim_options
 class WaterSegmentationModel(LightningModule):
 
     def __init__(self, in_channels, n_classes, lr, log_image_iter=50, to_rgb_fcn=None, ignore_index=None,
@@ -46,9 +57,9 @@ class WaterSegmentationModel(LightningModule):
                  ema_decay=None, ema_warmup=True, focal_gamma=0.0, region_weight=0.0, region_alpha=0.5, region_beta=0.5,
                  region_smooth=1.0, grad_clip_norm=None, weight_decay=0.0, decay_all=False):
         super().__init__()
-        self.grad_clip_norm = check_grad_clip(grad_clip_norm)
-        self.weight_decay = check_weight_decay(weight_decay)
-        self.decay_all = bool(decay_all)
+        # checked on the host, once; the net is armed from this one object (EMA below, clip and decay with the optimiser)
+        self.optim_options = OptimOptions.make(ema_decay=ema_decay, ema_warmup=ema_warmup, grad_clip_norm=grad_clip_norm,
+                                               weight_decay=weight_decay, decay_all=decay_all)
         self.n_classes = n_classes
         self.ignore_index = ignore_index
         if self.ignore_index == -1:                      # water_seg_model.py:35-36
@@ -57,8 +68,6 @@ class WaterSegmentationModel(LightningModule):
         self._set_loss_options(class_weight=class_weights, label_smoothing=label_smoothing, focal_gamma=focal_gamma,
                                region_weight=region_weight, region_alpha=region_alpha, region_beta=region_beta,
                                region_smooth=region_smooth)
-        self.ema_decay = None if ema_decay is None else check_decay(ema_decay)
-        self.ema_warmup = bool(ema_warmup)
         self.lr = lr
         self.in_channels = in_channels
         self.optimizer_name = optimizer_name
@@ -66,8 +75,8 @@ class WaterSegmentationModel(LightningModule):
         self.base_channels = base_channels
 
         self._build_model()
-        if self.ema_decay is not None:                   # host bookkeeping only: the buffers are made on the module's device
-            self.model.enable_ema(self.ema_decay, self.ema_warmup)
+        self.model.apply_optim_options(self.optim_options, step=False)   # the EMA; host bookkeeping only: the buffers are
+                                                                         # made on the module's device
 
         self.tracked_metrics = self._get_tracked_metrics()
         self._modules["loss_func"] = self._modules.pop("loss_func")     # made first, with the checks; listed last, as ever
@@ -211,19 +220,11 @@ class WaterSegmentationModel(LightningModule):
             # FU_TORCH_ADAM=1 keeps torch's own optimiser (it works on the same parameters).
             import os
             if os.environ.get("FU_TORCH_ADAM") == "1":
-                if self.ema_decay is not None:
-                    raise NotImplementedError("the weight EMA is part of the fused Adam kernel (HipAdam): FU_TORCH_ADAM=1 "
-                                              "together with ema_decay is not supported")
-                if self.grad_clip_norm is not None:
-                    raise NotImplementedError("gradient clipping runs ahead of the fused Adam kernel (HipAdam): FU_TORCH_ADAM=1 "
-                                              "together with grad_clip_norm is not supported")
-                if self.weight_decay > 0.0:
-                    raise NotImplementedError("weight decay is part of the fused Adam kernel (HipAdam): FU_TORCH_ADAM=1 "
-                                              "together with weight_decay is not supported")
+                for name in self.optim_options.set_fields:
+                    raise NotImplementedError(_TORCH_ADAM_REFUSALS[name])
                 optimizer = optim.Adam(self.parameters(), lr=self.lr)
             else:
-                optimizer = HipAdam(self.model, lr=self.lr, max_grad_norm=self.grad_clip_norm,
-                                    weight_decay=self.weight_decay, decay_params="all" if self.decay_all else "weights")
+                optimizer = HipAdam(self.model, lr=self.lr, options=self.optim_options)
         else:
             raise NotImplementedError(f'No implementation for optimizer of name: {self.optimizer_name}')
         return optimizer

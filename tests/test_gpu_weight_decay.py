@@ -473,8 +473,47 @@ def test_a_change_of_the_setting_after_capture_captures_again():
         tra.step(x, t, 0)
         trb.step(x, t, 0)
     torch.cuda.synchronize()
-    assert first is not None and tra._graph is not first and tra._g_decay == (2 * WD, (True,) * len(a._table))
+    assert first is not None and tra._graph is not first and tra._g_optim[2] == (2 * WD, (True,) * len(a._table))
     assert _same(a.flat_parameters(), b.flat_parameters())
+
+
+def test_ema_clipping_and_decay_together_graph_equals_eager():
+    """The weight EMA, gradient clipping and weight decay armed together on one DataParallelTrainer: the captured step equals
+    the eager one bit for bit over 4 steps with a changing lr -- losses, parameters, both moments, the three EMA buffers and
+    the clip state.  The clip norm lies between the smallest and the largest gradient norm of an unclipped eager run, and
+    the test asserts that it clipped some of the four steps and not all."""
+    from floodplanet_code_amd.distributed import DataParallelTrainer
+    st = O.make_state(8, 3, 8, True, seed=11)
+    host = [O.make_batch(2, 8, 32, 32, seed=70 + i) for i in range(4)]
+
+    def run(graph, clip):
+        net = HipUNet(8, 3, base_channels=8, precision="bf16")
+        net.load_state_dict(st)
+        net.to(DEV).train()
+        tr = DataParallelTrainer(net, lr=1e-2, graph=graph, ema_decay=0.9, grad_clip_norm=clip, weight_decay=WD)
+        losses, norms = [], []
+        for it, b in enumerate(host):
+            tr.lr = 1e-2 * _lr(it + 1) / 1e-3
+            losses.append(tr.step(b["image"].to(DEV), b["target"].to(DEV), 0))
+            if clip > 1e29:
+                norms.append(net.grad_clip_state()["grad_norm"])
+        torch.cuda.synchronize()
+        assert (tr._graph is not None) == graph
+        return ([l.item() for l in losses], net.flat_parameters().clone(), *[t.clone() for t in net.adam_state()],
+                *[t.clone() for t in net.ema_buffers()]), net.grad_clip_state(), norms
+
+    _, unclipped, norms = run(False, 1e30)
+    assert unclipped["clipped_steps"] == 0 and len(norms) == 4 and min(norms) < max(norms)
+    clip = 0.5 * (min(norms) + max(norms))
+    eager, eager_state, _ = run(False, clip)
+    graph, graph_state, _ = run(True, clip)
+    print(f"gradient norms of the unclipped run {norms}, clip norm {clip}, clip state {eager_state}")
+    assert 0 < eager_state["clipped_steps"] < 4 and eager_state["steps"] == 4 and eager_state["nonfinite_steps"] == 0
+    assert eager_state == graph_state
+    assert eager[0] == graph[0] and len(set(eager[0])) > 1
+    assert len(eager) == 1 + 1 + 2 + 3
+    for a, b in zip(eager[1:], graph[1:]):
+        assert _same(a, b)
 
 
 def test_late_fusion_takes_the_setting():
