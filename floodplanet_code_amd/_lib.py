@@ -108,6 +108,27 @@ class FuClassThreshold(C.Structure):
     _fields_ = [("cls", C.c_int32), ("threshold", C.c_float)]
 
 
+class FuTestPack(C.Structure):
+    """fu_test_pack (include/floodunet.h): one packed weight copy of a context, as fu_test_get_pack reports it."""
+    _fields_ = [
+        ("wf", C.c_void_p),
+        ("wd", C.c_void_p),
+        ("fold_scale", C.c_void_p),
+        ("fold_bias", C.c_void_p),
+        ("a", C.c_void_p),
+        ("b", C.c_void_p),
+        ("bias4", C.c_void_p),
+        ("present", C.c_int32),
+        ("cout", C.c_int32),
+        ("cin_real", C.c_int32),
+        ("cin_pad", C.c_int32),
+        ("p_weight", C.c_int32),
+        ("p_bias", C.c_int32),
+        ("bn", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class FloodUNetError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"libfloodunet error {status}: {message}")
@@ -209,6 +230,7 @@ SIGNATURES = {
     "fu_test_wgrad_slab": (_i, [_i] * 8 + [C.POINTER(_i64), C.POINTER(_i64)]),
     "fu_test_get_buffer": (_i, [_p, _i, _i, C.POINTER(_p), C.POINTER(_i64)]),
     "fu_test_loss_buffers": (_i, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64)]),
+    "fu_test_get_pack": (_i, [_p, _i, _i, _i, C.POINTER(FuTestPack)]),
     "fu_set_side_stream": (_i, [_p, _i]),
     "fu_backward_join": (_i, [_p, _p]),
     "fu_backward_fence": (_i, [_p, _p, _p]),

@@ -1,6 +1,6 @@
 // Single operators behind the C ABI (fu_op_*): one launcher each on caller-owned buffers, with temporary packs and
-// partial buffers of their own -- the hooks of the op-level parity tests -- and fu_test_get_buffer and
-// fu_test_loss_buffers, the only entry points here that look inside a context.
+// partial buffers of their own -- the hooks of the op-level parity tests -- and fu_test_get_buffer,
+// fu_test_loss_buffers and fu_test_get_pack, the only entry points here that look inside a context.
 #include "fu_ctx.h"
 #include "fu_elem.h"
 
@@ -394,6 +394,48 @@ int fu_test_loss_buffers(fu_ctx* c, float** logits, float** dlogits, int64_t* el
   *logits = c->logits;
   *dlogits = c->dlogits;
   *elems = (int64_t)f.max_batch * f.height * f.width * f.n_classes;
+  return FU_OK;
+}
+
+int fu_test_get_pack(fu_ctx* c, int kind, int index, int which, fu_test_pack* out) {
+  FU_REQUIRE(c && out, "fu_test_get_pack: null argument");
+  fu_test_pack r = {};
+  r.p_weight = r.p_bias = r.bn = -1;
+  if (kind == 0) {
+    FU_REQUIRE(index >= 0 && index < c->nb, "fu_test_get_pack: block %d outside 0..%d", index, c->nb - 1);
+    FU_REQUIRE(which == 0 || which == 1, "fu_test_get_pack: conv %d of a double conv (0 or 1)", which);
+    const Conv& v = c->blk[index].c[which];
+    r.present = 1;
+    r.wf = v.wf; r.wd = v.wd;
+    r.fold_scale = v.fold_scale; r.fold_bias = v.fold_bias; r.a = v.a; r.b = v.b;
+    r.cout = v.cout; r.cin_real = v.cin_real; r.cin_pad = v.cin_pad;
+    r.p_weight = v.p_w; r.p_bias = v.p_b; r.bn = v.bn;
+  } else if (kind == 1) {
+    FU_REQUIRE(index >= 0 && index < 5, "fu_test_get_pack: fusion level %d outside 0..4", index);
+    FU_REQUIRE(which == 0, "fu_test_get_pack: which must be 0 for a fusion conv");
+    if (c->fusion) {
+      const Fuse& F = c->fuse[index];
+      r.present = 1;
+      r.wf = F.wf; r.wd = F.wd;
+      r.cout = F.C; r.cin_real = r.cin_pad = c->nE * F.C;
+      r.p_weight = F.p_w; r.p_bias = F.p_b;
+    }
+  } else if (kind == 2) {
+    FU_REQUIRE(index >= 5 * c->nE && index < c->nb, "fu_test_get_pack: block %d is not an up block (%d..%d)", index,
+               5 * c->nE, c->nb - 1);
+    FU_REQUIRE(which == 0, "fu_test_get_pack: which must be 0 for a transposed conv");
+    if (!c->cfg.bilinear) {
+      const Block& K = c->blk[index];
+      r.present = 1;
+      r.wf = K.ct_wf; r.wd = K.ct_wd; r.bias4 = K.ct_b4;
+      r.cout = 4 * K.ct_cout; r.cin_real = r.cin_pad = K.ct_cin;
+      r.p_weight = K.ct_w; r.p_bias = K.ct_b;
+    }
+  } else {
+    set_error("fu_test_get_pack: kind must be 0 (double conv), 1 (fusion conv) or 2 (transposed conv)");
+    return FU_ERR_INVALID;
+  }
+  *out = r;
   return FU_OK;
 }
 

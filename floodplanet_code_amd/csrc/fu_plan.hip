@@ -33,7 +33,7 @@ __global__ void k_pack_all(const float* __restrict__ params, PackTable tab, int 
       tap = (int)(r / D.cin_pad);
     }
     float v = ci < D.cin_real ? w[((int64_t)co * D.cin_real + ci) * 9 + tap] : 0.f;
-    if (use_scale) v *= D.scale[co];
+    if (use_scale && ci < D.cin_real) v *= D.scale[co];   // (the channel padding stays +0.0 under a negative scale)
     T* wf = (T*)D.wf;
     T* wd = (T*)D.wd;
     if (BF16_LAYOUT) {
@@ -77,7 +77,8 @@ __global__ __launch_bounds__(256) void k_pack_tiles_16(const float* __restrict__
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
       const int u = threadIdx.x + k * 256, co_l = u / 72, q = u - co_l * 72;
-      const float sc = (use_scale && co0 + co_l < D.cout) ? D.scale[co0 + co_l] : 1.f;
+      // (a piece outside the tile's real channels keeps its +0.0: times a negative scale it would be -0.0)
+      const float sc = (use_scale && co0 + co_l < D.cout && 4 * q < run) ? D.scale[co0 + co_l] : 1.f;
       const float vv[4] = {v4[k].x, v4[k].y, v4[k].z, v4[k].w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void k_pack_tiles_16(const float* __restrict__
       const int ci_l = r / 9, tap = r - ci_l * 9;
       const int co = co0 + co_l, ci = ci0 + ci_l;
       float v = (co < D.cout && ci < D.cin_real) ? w[((size_t)co * D.cin_real + ci) * 9 + tap] : 0.f;
-      if (use_scale && co < D.cout) v *= D.scale[co];
+      if (use_scale && co < D.cout && ci < D.cin_real) v *= D.scale[co];
       sT[tap][co_l][ci_l] = cvt16<HALF>(v);
     }
   }
@@ -134,7 +135,13 @@ __global__ void k_bn_fold_eval(int C, const float* __restrict__ gamma, const flo
   const float invstd = (float)(1.0 / sqrt((double)rv[c] + (double)eps));
   const float sc = gamma[c] * invstd;
   scale[c] = sc;
-  fbias[c] = fmaf(sc, bias[c], beta[c] - rm[c] * sc);
+  float shift;   // beta - rm * scale: a product and a difference, each rounded (left to -ffp-contract=fast they became one fma,
+  {              // up to 32 ulp off in fold_bias where the two terms cancel: tests/test_gpu_weight_pack.py)
+#pragma clang fp contract(off)
+    const float p = rm[c] * sc;
+    shift = beta[c] - p;
+  }
+  fbias[c] = fmaf(sc, bias[c], shift);
   a[c] = 1.f;
   b[c] = 0.f;
 }

@@ -753,6 +753,34 @@ int fu_test_get_buffer(fu_ctx* ctx, int block, int which, void** ptr, int64_t* e
  * max_batch.  The op-level loss tests copy constructed logits over the resident ones after a forward, call one fu_loss_*
  * entry and read the gradient back; nothing in the library calls this. */
 int fu_test_loss_buffers(fu_ctx* ctx, float** logits, float** dlogits, int64_t* elems);
+/* Testing hook: where one packed 3x3 weight copy of the context lives and what it was packed from -- what the forward /
+ * dgrad kernels of a real step read (fu_forward packs when the parameters changed or the mode switched; the pack of eval mode
+ * has the BatchNorm behind the conv folded in).  Read-only: launches nothing, synchronises nothing.
+ *   kind 0  a block's double conv: index = plan block (0 .. 5 nE + 3: per encoder inc, down1..4, then up1..4), which = 0 | 1
+ *   kind 1  a late-fusion level's 1x1 conv embedded as a centre tap: index = level 0..4, which = 0; c_in = nE * c_out
+ *   kind 2  an up block's ConvTranspose2d(2, 2) as a 1x1 conv to 4 c_out phase-major channels: index = plan block of
+ *           up1..4, which = 0; c_out here is 4 * (the transposed conv's c_out), bias4[(p, co)] = bias[co], p = 2 ky + kx
+ * present = 0 (everything else zero, the indices -1): the net has no such pack (kind 1 on a plain UNet, kind 2 on a
+ * bilinear net).  Bad indices and null arguments: FU_ERR_INVALID.
+ * Each copy holds 9 * cin_pad * cout elements of the context's precision, value w[co][ci][tap] (tap = 3 ky + kx; zero for
+ * ci >= cin_real; times fold_scale[co] in eval mode, in fp32, then rounded once):
+ *   bf16 / fp16   wf[tap][co][ci_pad]   wd[8 - tap][ci_pad][co]
+ *   fp32          wf[tap][ci_pad][co]   wd[8 - tap][co][ci_pad]
+ * wd is null for the first conv of an encoder (nothing needs its data gradient).  kind 0 only: fold_scale = gamma /
+ * sqrt(running_var + eps) and fold_bias = fma(fold_scale, bias, beta - running_mean * fold_scale), written by the eval pack,
+ * and a / b, the activation coefficients of the conv's consumers (1 / 0 after an eval pack); each [cout] fp32.
+ * p_weight / p_bias: fu_param_info indices; bn: fu_bn_info index (-1: no BatchNorm behind this conv). */
+typedef struct fu_test_pack {
+  void* wf;
+  void* wd;
+  float* fold_scale;
+  float* fold_bias;
+  float* a;
+  float* b;
+  float* bias4;
+  int32_t present, cout, cin_real, cin_pad, p_weight, p_bias, bn, reserved;
+} fu_test_pack;
+int fu_test_get_pack(fu_ctx* ctx, int kind, int index, int which, fu_test_pack* out);
 
 /* ---- single operators (per-op parity tests; NHWC device buffers of the context's precision) -- */
 /* element size of the activation type for `precision` */
