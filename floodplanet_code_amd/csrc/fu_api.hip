@@ -191,7 +191,6 @@ int64_t fu_exact_sync_bytes(const fu_ctx* c) {
 
 int fu_forward(fu_ctx* c, const float* x, int batch, int training, float* logits_out, fu_stream stream) {
   FU_TRY(check_fwd_args(c, x, batch));
-  SyncScope sc(c, training != 0);   // eval-mode BN uses the running statistics: nothing to exchange
   return forward_impl(c, x, nullptr, batch, training != 0, logits_out, (hipStream_t)stream);
 }
 
@@ -217,7 +216,6 @@ int fu_forward_srcs(fu_ctx* c, const float* const* srcs, const int32_t* src_chan
   FU_TRY(check_fwd_args(c, srcs[0], batch));
   SrcList S;
   FU_TRY(make_src_list(c, "fu_forward_srcs", srcs, src_channels, n_src, &S));
-  SyncScope sc(c, training != 0);
   return forward_impl(c, nullptr, &S, batch, training != 0, logits_out, (hipStream_t)stream);
 }
 
@@ -242,7 +240,6 @@ int fu_forward_views(fu_ctx* c, const float* const* srcs, const int32_t* src_cha
   FU_TRY(check_fwd_args(c, srcs[0], batch * n_views));
   SrcList S;
   FU_TRY(make_src_list(c, "fu_forward_views", srcs, src_channels, n_src, &S));
-  SyncScope sc(c, false);
   return forward_impl(c, nullptr, &S, batch * n_views, false, logits_out, (hipStream_t)stream, n_views, packed);
 }
 
@@ -258,20 +255,20 @@ int fu_merge_views(fu_ctx* c, float* probs_out, const int64_t* target, int ignor
 
 namespace {
 // fu_loss_ce (cw == null), fu_loss_ce_weighted and fu_loss_ce_focal; fu_loss_ce_region: any of the three, then the region
-// term (rg != null) inside the same SyncScope
+// term (rg != null) with the same exact-sync descriptor
 int loss_ce(fu_ctx* c, const char* who, const int64_t* target, int ignore_index, const CeWeighting* cw, float* loss_out,
             int64_t* confusion_out, int64_t* n_valid_out, fu_stream stream, const RegionTerm* rg = nullptr) {
   FU_REQUIRE(c->last_batch > 0, "%s: no forward pass yet", who);
   hipStream_t s = (hipStream_t)stream;
-  SyncScope sc(c, c->fwd_training);
+  const SyncDesc* sync = active_sync(c, c->fwd_training);
   const int64_t npix = (int64_t)c->last_batch * c->cfg.height * c->cfg.width;
   FU_TRY(launch_ce_loss(c->logits, target, c->cfg.n_classes, ignore_index, npix, cw, c->ce_part,
-                        loss_out ? loss_out : c->loss_dev, c->n_valid, confusion_out, n_valid_out, c->conf_tmp, s));
+                        loss_out ? loss_out : c->loss_dev, c->n_valid, confusion_out, n_valid_out, c->conf_tmp, sync, s));
   if (c->fwd_training)
     FU_TRY(launch_ce_grad(c->logits, target, c->cfg.n_classes, ignore_index, npix, cw, c->n_valid, c->dlogits, s));
   if (rg)
     FU_TRY(launch_region_term(c->logits, target, c->cfg.n_classes, ignore_index, npix, *rg, c->ce_part,
-                              loss_out ? loss_out : c->loss_dev, c->fwd_training ? c->dlogits : nullptr, s));
+                              loss_out ? loss_out : c->loss_dev, c->fwd_training ? c->dlogits : nullptr, sync, s));
   if (c->fwd_training) {
     c->have_loss = true;
     c->have_up_scale = false;
@@ -388,8 +385,6 @@ int fu_backward_block(fu_ctx* c, int block, const float* dlogits, fu_stream stre
   FU_REQUIRE(block >= 0 && block < num_backward_blocks(c), "fu_backward_block: block %d outside 0..%d", block,
              num_backward_blocks(c) - 1);
   FU_TRY(check_backward(c));
-  SyncScope sc(c, true);
-  UnscaleScope us(c);
   return backward_block_impl(c, block, dlogits, (hipStream_t)stream, c->side_mode != 2);
 }
 
@@ -422,8 +417,6 @@ int fu_backward_fence(fu_ctx* c, fu_stream stream, fu_stream waiter) {
 int fu_backward(fu_ctx* c, const float* dlogits, fu_stream stream) {
   FU_REQUIRE(c, "null context");
   FU_TRY(check_backward(c));
-  SyncScope sc(c, true);
-  UnscaleScope us(c);
   // whole backward: the side stream (weight gradients) is joined once, after the last block
   const int nblk = num_backward_blocks(c);
   for (int b = 0; b < nblk; ++b) FU_TRY(backward_block_impl(c, b, dlogits, (hipStream_t)stream, b == nblk - 1));

@@ -6,8 +6,6 @@
 
 namespace fu {
 
-thread_local const float* g_grad_unscale = nullptr;
-
 // ------------------------------------------------------------------------------------------------
 // two-level per-channel reduction of partials [nPart][C][NV] (fp32) -> [G][C][NV] (fp64)
 // ------------------------------------------------------------------------------------------------
@@ -144,16 +142,17 @@ __global__ __launch_bounds__(256) void k_bn_stats_fused(const float* __restrict_
 }
 
 int launch_bn_finalize(const BnFwdOut& o, const float* partials, int nTiles, int C, int64_t count, double* dscratch,
-                       hipStream_t s) {
-  if (sync_world() <= 1 && C % 4 == 0) {
+                       const SyncDesc* sync, hipStream_t s) {
+  const int world = sync_world(sync);
+  if (world <= 1 && C % 4 == 0) {
     hipLaunchKernelGGL((k_bn_stats_fused<0, BnFwdOut>), dim3(C / 4), dim3(256), 0, s, partials, nTiles, C, (double)count, o);
     FU_LAUNCH_CHECK();
     return 0;
   }
   int G = 0;
   FU_TRY(reduce_partials<2>(partials, dscratch, nTiles, C, s, &G));
-  FU_TRY(sync_sum_over_ranks(dscratch, (int64_t)G * C * 2, true, s));     // exact DP: global batch statistics
-  hipLaunchKernelGGL(k_bn_finalize, dim3(ceil_div(C, 8)), dim3(256), 0, s, dscratch, G, C, (double)count * sync_world(), o);
+  FU_TRY(sync_sum_over_ranks(sync, dscratch, (int64_t)G * C * 2, true, s));     // exact DP: global batch statistics
+  hipLaunchKernelGGL(k_bn_finalize, dim3(ceil_div(C, 8)), dim3(256), 0, s, dscratch, G, C, (double)count * world, o);
   FU_LAUNCH_CHECK();
   return 0;
 }
@@ -381,12 +380,13 @@ int launch_bn_bwd(Prec p, const BnBwdArgs& A, hipStream_t s) {
   const int64_t npix = A.npix;
   const void* g_pool = A.g_pool;
   const HeadGrad* head = A.head;
+  const int world = sync_world(A.sync);
   FU_REQUIRE(head == nullptr || (ext_partials > 0 && g_pool == nullptr && p != PREC_F32 && C % 8 == 0 && BNB_THREADS % (C / 8) == 0),
              "bn_bwd: a recomputed head gradient needs the producer's sums, a 16-bit element type and C | 2048");
   FU_REQUIRE(C >= 4 && C % 4 == 0 && C <= 1024, "bn_bwd: channels must be a multiple of 4 and <= 1024 (got %d)", C);
   // ext_partials > 0: `partials` already holds that many [C][2] rows of the two sums (written by the producer of g, see
   // BnbFuse in fu_common.h) -- the reduce pass is skipped, the apply pass keeps its own grid
-  FU_REQUIRE(ext_partials == 0 || (g_pool == nullptr && sync_world() <= 1), "bn_bwd: external partial sums with a pooled source / exact sync");
+  FU_REQUIRE(ext_partials == 0 || (g_pool == nullptr && world <= 1), "bn_bwd: external partial sums with a pooled source / exact sync");
   const int nb = bn_bwd_blocks(C, npix);
   const int rows = BNB_THREADS / (C >> 2);
   const size_t sh1 = (size_t)rows * C * 2 * sizeof(float);
@@ -410,17 +410,17 @@ int launch_bn_bwd(Prec p, const BnBwdArgs& A, hipStream_t s) {
     });
   }
   FU_LAUNCH_CHECK();
-  const BnBwdOut o{g_grad_unscale, A.dgamma, A.dbeta, A.coef};
+  const BnBwdOut o{A.unscale, A.dgamma, A.dbeta, A.coef};
   const int n_rows = ext_partials > 0 ? ext_partials : nb;     // (exact sync never comes with external sums: n_rows = nb there)
-  if (sync_world() <= 1 && !A.two_level) {
+  if (world <= 1 && !A.two_level) {
     hipLaunchKernelGGL((k_bn_stats_fused<1, BnBwdOut>), dim3(C / 4), dim3(256), 0, s, A.partials, n_rows, C, (double)npix, o);
     FU_LAUNCH_CHECK();
   } else {
     int G = 0;
     FU_TRY(reduce_partials<2>(A.partials, A.dscratch, n_rows, C, s, &G));
-    FU_TRY(sync_sum_over_ranks(A.dscratch, (int64_t)G * C * 2, true, s));     // exact DP: global sums of g and g*xhat
+    FU_TRY(sync_sum_over_ranks(A.sync, A.dscratch, (int64_t)G * C * 2, true, s));     // exact DP: global sums of g and g*xhat
     hipLaunchKernelGGL(k_bn_bwd_finalize, dim3(ceil_div(C, 8)), dim3(256), 0, s, A.dscratch, G, C,
-                       (double)npix * sync_world(), 1.0 / sync_world(), o);
+                       (double)npix * world, 1.0 / world, o);
     FU_LAUNCH_CHECK();
   }
   const size_t sh2 = (size_t)rows * C * sizeof(float);

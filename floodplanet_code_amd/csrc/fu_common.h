@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+#include "fu_device_slots.h"
+
 // host tables of include/floodunet.h that the launchers below validate
 struct fu_stitch_entry;
 struct fu_scene_crop;
@@ -240,8 +242,9 @@ __device__ __forceinline__ float wave_sum(float v) {
 struct ProfSlot { hipEvent_t start = nullptr; hipEvent_t stop = nullptr; };
 
 // Exact data-parallel mode (fu_set_exact_sync): at every statistics reduction the partial sums are summed over the
-// ranks before they are finalised.  The API layer points g_sync at the context's descriptor for the duration of a
-// call; the three launchers with such a reduction (BN forward statistics, BN backward sums, CE loss sums) check it.
+// ranks before they are finalised.  The four launchers with such a reduction (BN forward statistics, BN backward sums,
+// CE loss sums, region-term sums) take the descriptor as an argument, null = off; the step code gets it from
+// active_sync (fu_ctx.h), once per call.
 struct SyncDesc {
   int (*hook)(void* user, int64_t n_elems, int is_double) = nullptr;   // sums xbuf[0..n) over the ranks, in place
   void* user = nullptr;
@@ -249,17 +252,16 @@ struct SyncDesc {
   int64_t xbytes = 0;
   int world = 1;
 };
-extern thread_local const SyncDesc* g_sync;
-// payload (device, n elements of float or double) -> xbuf, hook, back; no-op without an active descriptor
-int sync_sum_over_ranks(void* payload, int64_t n_elems, bool is_double, hipStream_t s);
-static inline int sync_world() { return (g_sync && g_sync->hook) ? g_sync->world : 1; }
+static inline int sync_world(const SyncDesc* d) { return (d && d->hook) ? d->world : 1; }
+// payload (device, n elements of float or double) -> xbuf, hook, back; no-op where sync_world(d) is 1
+int sync_sum_over_ranks(const SyncDesc* d, void* payload, int64_t n_elems, bool is_double, hipStream_t s);
 
 // fp16 mode: the gradient maps (fp16) carry a power-of-two loss scale S chosen on the device from max|dL/dlogits| at the
-// start of every backward (launch_loss_grad_eff).  scale[0] = S, scale[1] = 1/S.  The three places that write PARAMETER
-// gradients (weight-gradient transpose + bias tail, BN backward finalize, head backward finalize) multiply by 1/S, so the
-// flat gradient buffer always holds true gradients.  The API layer points g_grad_unscale at scale + 1 for the duration of
-// a backward call in fp16 mode; nullptr (fp32 / bf16) means 1.
-extern thread_local const float* g_grad_unscale;
+// start of every backward (launch_loss_grad_eff).  scale[0] = S, scale[1] = 1/S.  The places that write PARAMETER
+// gradients (weight-gradient reduce + bias tail, BN backward finalize, head backward finalize, the ConvTranspose bias sum)
+// multiply by 1/S, so the flat gradient buffer always holds true gradients.  Each of them takes the pointer to 1/S with its
+// launch (LaunchOpts::unscale, BnBwdArgs::unscale, an argument); nullptr (fp32 / bf16) means 1.  The backward gets it from
+// grad_unscale (fu_ctx.h).
 
 // BatchNorm-backward sums from the PRODUCER of dL/dz (round 2): a dgrad launch whose single destination g = dL/d relu(bn(y))
 // feeds a BatchNorm backward can emit that backward's two sums (sum g*m, sum g*m*xhat, m = [a*y + b > 0]) per workgroup
@@ -294,18 +296,41 @@ struct HeadGrad {
 struct LaunchOpts {
   ProfSlot prof;                  // events around the main kernel
   const BnbFuse* bnb = nullptr;   // dgrad launches: request for the destination BatchNorm's backward sums
+  const float* unscale = nullptr; // wgrad launches, fp16: device 1 / loss scale, applied where dw / db are written (null = 1)
 };
+
+// Per-device launch facts.  Both are kept per device index in a DeviceSlots (fu_device_slots.h: DeviceSlots::CAP indices,
+// filled once each from whichever host thread comes first; an index beyond asks the runtime every time), so no launch
+// depends on which device launched first, and a launch after the first on its device costs one hipGetDevice.
+// The CU count of the current device (the grid of the persistent conv kernel); *n_cu > 0 on success.
+inline int current_device_cus(int* n_cu) {
+  static DeviceSlots cus;
+  int dev = 0;
+  FU_HIP_CHECK(hipGetDevice(&dev));
+  *n_cu = cus.get(dev, [dev] {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    return n > 0 ? n : 256;
+  });
+  FU_REQUIRE(*n_cu > 0, "the CU count of device %d is not available", dev);
+  return 0;
+}
 #ifdef __HIPCC__
-// The one way a conv / wgrad main kernel is launched: the opt-in to more dynamic LDS once per kernel, the launch's event pair
-// immediately around the kernel, the launch check.  The opt-in is made from 48 KiB on: the fp32 kernels (44 - 48 KiB) never
-// made it, the 16-bit launchers made it for every kernel, the 36 KiB one-tap tile included, which does not need it.
+// The one way a conv / wgrad main kernel is launched: the opt-in to more dynamic LDS once per kernel AND device, the launch's
+// event pair immediately around the kernel, the launch check.  The opt-in is made from 48 KiB on: the fp32 kernels (44 - 48 KiB)
+// never made it, the 16-bit launchers made it for every kernel, the 36 KiB one-tap tile included, which does not need it.
+// (A kernel launches with one LDS size, so the first launch's size serves the later ones.)
 template <auto Kernel, typename P>
 int launch_conv_kernel(dim3 grid, dim3 block, size_t smem, const LaunchOpts& o, hipStream_t s, const P& p) {
-  static bool attr_set = false;
-  if (!attr_set && smem > 48 * 1024) {
-    FU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)smem));
-    attr_set = true;
+  if (smem > 48 * 1024) {
+    static DeviceSlots opted;   // of this kernel: what the opt-in returned on each device
+    int dev = 0;
+    FU_HIP_CHECK(hipGetDevice(&dev));
+    const hipError_t opt_in = (hipError_t)opted.get(dev, [smem] {
+      return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)smem);
+    });
+    FU_HIP_CHECK(opt_in);
   }
   if (o.prof.start) (void)hipEventRecord(o.prof.start, s);
   hipLaunchKernelGGL(Kernel, grid, block, smem, s, p);
@@ -381,11 +406,11 @@ int launch_pack_conv3x3(Prec p, const float* w_oihw, int Cout, int cin_real, int
                         hipStream_t s);
 
 // the tail of every weight-gradient launch (fu_conv.hip): S split-K slabs -> dw (fp32 OIHW) and db, in a fixed order.
-// fp32 path: [tap][ci][co] slabs; 16-bit paths: [tap][ci / 4][co][4] slabs
+// fp32 path: [tap][ci][co] slabs; 16-bit paths: [tap][ci / 4][co][4] slabs.  unscale: LaunchOpts::unscale of the launch
 int launch_wgrad_reduce(const float* slab, int S, int Cin, int Cout, int cin_real, float* dw, const float* dbp, int ndb,
-                        float* db, hipStream_t s);
+                        float* db, const float* unscale, hipStream_t s);
 int launch_wgrad_reduce_oihw(const float* slab, int S, int Cin, int Cout, int cin_real, float* dw, const float* dbp,
-                             int ndb, float* db, hipStream_t s);
+                             int ndb, float* db, const float* unscale, hipStream_t s);
 // the split-K plan of the fp32 weight-gradient kernel (fu_conv_f32.hip, in its tile sizes)
 void wgrad_split_shared(int Cin, int Cout, int B, int H, int W, int* nPix, int* S, int* perSplit);
 
@@ -435,12 +460,13 @@ int launch_gather_views_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B,
 
 // BN: finalize forward statistics.  partials [nTiles][C][2]; count = B*H*W.
 // training: writes mean/invstd/a/b, updates running stats (momentum 0.1, unbiased var) and nbt.
+// sync != null (exact data-parallel mode): the statistics of all ranks' batches.
 struct BnFwdOut {
   const float* conv_bias; const float* gamma; const float* beta; float eps, momentum;
   float *mean, *invstd, *a, *b, *rmean, *rvar; int64_t* nbt;
 };
 int launch_bn_finalize(const BnFwdOut& o, const float* partials, int nTiles, int C, int64_t count, double* dscratch,
-                       hipStream_t s);
+                       const SyncDesc* sync, hipStream_t s);
 // fp64 scratch needed by the two-level reductions: elements for a layer with C channels
 static inline int64_t reduce_scratch_elems(int C) { return (int64_t)32 * C * 2; }
 // backward: g (in place -> dy).  Two launches + finalize inside.  partials scratch: >= bn_bwd_partial_elems.
@@ -454,6 +480,8 @@ struct BnBwdArgs {
   float *partials = nullptr, *coef = nullptr;          // scratch: the two sums per block; [C][2] s1/N, s2/N
   float* db_partials = nullptr; int* n_db_partials = nullptr;   // out: per-block sums of dy (the conv's bias gradient) and their count
   double* dscratch = nullptr;
+  const SyncDesc* sync = nullptr;                      // exact data-parallel mode: the two sums are summed over the ranks
+  const float* unscale = nullptr;                      // fp16: device 1 / loss scale for dgamma / dbeta (null = 1)
   // optional.  g_pool != null: y's 2x2 max-pool ran in forward and g_pool [B, H/2, W/2, C] is dL/d(pooled): the pool's backward
   // is folded into the two passes (g is then the skip gradient only); B, H, W are needed with it
   const void* g_pool = nullptr; int B = 0, H = 0, W = 0;
@@ -485,7 +513,8 @@ int launch_upsample2_bwd(Prec p, const void* g_dst, void* g_src, int B, int H, i
 // pad-region zeroing, bias-gradient partial sums, weight <-> embedded-centre-tap conversions
 int launch_depth_to_space(Prec p, const void* y4, void* up, int B, int h, int w, int C, int outH, int outW, hipStream_t s);
 int launch_space_to_depth(Prec p, const void* gup, void* g4, int B, int h, int w, int C, int outH, int outW, hipStream_t s);
-int launch_colsum_partials(const float* partials, int n, int C, float* out, hipStream_t s);
+int launch_colsum_partials(const float* partials, int n, int C, const float* unscale /* fp16: 1 / loss scale, or null */,
+                           float* out, hipStream_t s);
 int launch_channel_partial_sums(Prec p, const void* g, int C, int64_t npix, float* partials, int* n_partials,
                                 hipStream_t s);
 int launch_convT_to_w3(const float* w, const float* b, int Cin, int Cout, float* w3, float* bias4, hipStream_t s);
@@ -519,7 +548,7 @@ struct CeWeighting {
 int launch_ce_loss(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
                    const CeWeighting* cw, float* partials, float* loss_out, int64_t* n_valid_dev,
                    int64_t* confusion_accum, int64_t* n_valid_out, unsigned long long* conf_tmp /* [64], zero-initialised */,
-                   hipStream_t s);
+                   const SyncDesc* sync /* null, or the sums are taken over the ranks */, hipStream_t s);
 // dlogits (NHWC fp32) from CE: (softmax - onehot)/n_valid on valid pixels; weighted: the gradient of the loss above
 int launch_ce_grad(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
                    const CeWeighting* cw, const int64_t* n_valid_dev, float* dlogits_nhwc, hipStream_t s);
@@ -535,7 +564,8 @@ struct RegionTerm {
   float* region_out;   // optional
 };
 int launch_region_term(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
-                       const RegionTerm& rg, float* partials, float* loss_io, float* dlogits_nhwc, hipStream_t s);
+                       const RegionTerm& rg, float* partials, float* loss_io, float* dlogits_nhwc, const SyncDesc* sync,
+                       hipStream_t s);
 // BCE + soft Dice on softmax(z)[1]; partials: LOSS_PART_FLOATS floats, coef 4 floats; dlogits may be null (eval)
 int launch_bce_dice(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
                     float dice_w, float* partials, float* coef, float* loss_out, int64_t* n_valid_dev,
@@ -545,7 +575,8 @@ int launch_dlogits_from_nchw(const float* dlogits_nchw, float* dlogits_nhwc, int
 // head backward: G[y] = dlogits * W ; dW = sum dlogits (x) z ; db = sum dlogits
 int64_t head_bwd_partial_elems(int C, int ncls);
 int launch_head_bwd(Prec p, const float* dlogits_nhwc, const void* y, const float* a, const float* b, const float* w,
-                    int C, int ncls, int64_t npix, void* g, float* partials, float* dw, float* db, hipStream_t s,
+                    int C, int ncls, int64_t npix, void* g, float* partials, float* dw, float* db,
+                    const float* unscale /* fp16: 1 / loss scale for dw / db, or null */, hipStream_t s,
                     const BnbFuse* fuse = nullptr);
 
 int launch_stitch_add(const float* logits_nhwc, int ncls, int cropW, float* canvas, float* weight, int canvasW, int h0,

@@ -280,51 +280,51 @@ __global__ __launch_bounds__(SL == 1 ? 320 : 256) void k_wgrad_reduce_oihw(
 
 template <int SL>
 static int launch_wgrad_reduce_sl(const float* slab, int S, int Cin, int Cout, const float* dbp, int ndb, float* db,
-                                  hipStream_t s) {
+                                  const float* unscale, hipStream_t s) {
   constexpr int ELEMS = 4 * (256 / SL);
   const int64_t nSlab = (int64_t)9 * Cin * Cout;
   const int64_t blocks = (nSlab + ELEMS - 1) / ELEMS + (db ? (Cout + 15) / 16 : 0);
   hipLaunchKernelGGL(k_wgrad_reduce<SL>, dim3((unsigned)blocks), dim3(256), 0, s, slab, S, Cin, Cout, dbp, ndb, db,
-                     g_grad_unscale);
+                     unscale);
   FU_LAUNCH_CHECK();
   return 0;
 }
 
 // fp32 path: [tap][ci][co] slabs
 int launch_wgrad_reduce(const float* slab, int S, int Cin, int Cout, int cin_real, float* dw, const float* dbp,
-                               int ndb, float* db, hipStream_t s) {
+                        int ndb, float* db, const float* unscale, hipStream_t s) {
   int st;
-  if (S >= 64) st = launch_wgrad_reduce_sl<16>(slab, S, Cin, Cout, dbp, ndb, db, s);
-  else if (S >= 16) st = launch_wgrad_reduce_sl<4>(slab, S, Cin, Cout, dbp, ndb, db, s);
-  else st = launch_wgrad_reduce_sl<1>(slab, S, Cin, Cout, dbp, ndb, db, s);
+  if (S >= 64) st = launch_wgrad_reduce_sl<16>(slab, S, Cin, Cout, dbp, ndb, db, unscale, s);
+  else if (S >= 16) st = launch_wgrad_reduce_sl<4>(slab, S, Cin, Cout, dbp, ndb, db, unscale, s);
+  else st = launch_wgrad_reduce_sl<1>(slab, S, Cin, Cout, dbp, ndb, db, unscale, s);
   if (st) return st;
   const int blocks = ceil_div(Cout, 32) * ceil_div(Cin, 8);
-  hipLaunchKernelGGL(k_wgrad_transpose, dim3(blocks), dim3(256), 0, s, slab, Cin, Cout, cin_real, dw, g_grad_unscale);
+  hipLaunchKernelGGL(k_wgrad_transpose, dim3(blocks), dim3(256), 0, s, slab, Cin, Cout, cin_real, dw, unscale);
   FU_LAUNCH_CHECK();
   return 0;
 }
 
 template <int SL>
 static int launch_wgrad_reduce_oihw_sl(const float* slab, int S, int Cin, int Cout, int cin_real, float* dw,
-                                       const float* dbp, int ndb, float* db, hipStream_t s) {
+                                       const float* dbp, int ndb, float* db, const float* unscale, hipStream_t s) {
   constexpr int ELEMS = 4 * (256 / SL);
   const int64_t nSlab = (int64_t)9 * Cin * Cout;
   const int64_t blocksW = SL == 1 ? (int64_t)ceil_div(Cout, 32) * (Cin >> 2) : (nSlab + ELEMS - 1) / ELEMS;
   const int64_t blocks = blocksW + (db ? (Cout + 15) / 16 : 0);
   hipLaunchKernelGGL(k_wgrad_reduce_oihw<SL>, dim3((unsigned)blocks), dim3(SL == 1 ? 320 : 256), 0, s, slab, S, Cin,
-                     Cout, cin_real, dw, dbp, ndb, db, g_grad_unscale);
+                     Cout, cin_real, dw, dbp, ndb, db, unscale);
   FU_LAUNCH_CHECK();
   return 0;
 }
 
 // 16-bit paths: [tap][ci / 4][co][4] slabs; the same SL for the same S as the fp32 path
 int launch_wgrad_reduce_oihw(const float* slab, int S, int Cin, int Cout, int cin_real, float* dw, const float* dbp,
-                             int ndb, float* db, hipStream_t s) {
+                             int ndb, float* db, const float* unscale, hipStream_t s) {
   FU_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0, "wgrad_reduce_oihw: the interleaved slab layout needs c_in %% 4 == 0 and c_out %% 4 == 0");
   FU_REQUIRE((int64_t)9 * Cin * Cout < (int64_t(1) << 31), "wgrad_reduce_oihw: slab elements are indexed in 32 bits");
-  if (S >= 64) return launch_wgrad_reduce_oihw_sl<16>(slab, S, Cin, Cout, cin_real, dw, dbp, ndb, db, s);
-  if (S >= 16) return launch_wgrad_reduce_oihw_sl<4>(slab, S, Cin, Cout, cin_real, dw, dbp, ndb, db, s);
-  return launch_wgrad_reduce_oihw_sl<1>(slab, S, Cin, Cout, cin_real, dw, dbp, ndb, db, s);
+  if (S >= 64) return launch_wgrad_reduce_oihw_sl<16>(slab, S, Cin, Cout, cin_real, dw, dbp, ndb, db, unscale, s);
+  if (S >= 16) return launch_wgrad_reduce_oihw_sl<4>(slab, S, Cin, Cout, cin_real, dw, dbp, ndb, db, unscale, s);
+  return launch_wgrad_reduce_oihw_sl<1>(slab, S, Cin, Cout, cin_real, dw, dbp, ndb, db, unscale, s);
 }
 
 }  // namespace fu

@@ -665,15 +665,9 @@ int launch_conv3x3_pp(BConvP& P, const LaunchOpts& o, hipStream_t s) {
              "conv3x3_pp: grid too large (%d x %d)", P.nPix, P.nCo);
   // BatchNorm-backward sums of the destination, if the API layer asked for them and this launch can give them
   const bool bnb = attach_bnb(P, o, P.nPix);
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    FU_HIP_CHECK(hipGetDevice(&dev));
-    FU_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  // one workgroup per CU, a multiple of 8 (the XCD of a workgroup's virtual block ids must not change from tile to tile)
+  int n_cu = 0;
+  FU_TRY(current_device_cus(&n_cu));
+  // one workgroup per CU of the launching device, a multiple of 8 (the XCD of a workgroup's virtual block ids must not change from tile to tile)
   const int grid = (P.nTiles < n_cu ? P.nTiles : n_cu) & ~7;
   const bool fwd = P.bias != nullptr || P.stats != nullptr, bn = P.a0 != nullptr;
   if (bnb) return launch_pp_cfg<true, false, false>(grid, P, o, s);

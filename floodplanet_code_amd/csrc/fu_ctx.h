@@ -224,14 +224,12 @@ namespace fu {
 inline float* P(fu_ctx* c, int idx) { return c->P + c->params[idx].off; }
 inline float* G(fu_ctx* c, int idx) { return c->G + c->params[idx].off; }
 
-struct SyncScope {   // makes the context's exact-sync descriptor visible to the launchers for one API call
-  explicit SyncScope(const fu_ctx* c, bool on) { g_sync = (on && c && c->sync.hook) ? &c->sync : nullptr; }
-  ~SyncScope() { g_sync = nullptr; }
-};
-struct UnscaleScope {   // backward calls in fp16 mode: parameter gradients are written times 1 / loss scale
-  explicit UnscaleScope(const fu_ctx* c) { g_grad_unscale = (c && c->prec == PREC_F16) ? c->loss_scale + 1 : nullptr; }
-  ~UnscaleScope() { g_grad_unscale = nullptr; }
-};
+// The exact-sync descriptor that the statistics launchers of one call get: the context's where fu_set_exact_sync armed it
+// and the call reduces batch statistics (a training forward, its loss, a backward), else null.  Eval forwards use the
+// running statistics: nothing to exchange.
+inline const SyncDesc* active_sync(const fu_ctx* c, bool training) { return (training && c->sync.hook) ? &c->sync : nullptr; }
+// fp16 mode: where the backward writes parameter gradients it passes this pointer to 1 / loss scale (null otherwise: 1)
+inline const float* grad_unscale(const fu_ctx* c) { return c->prec == PREC_F16 ? c->loss_scale + 1 : nullptr; }
 
 // fu_plan.hip
 int build_plan(fu_ctx* c);

@@ -1,5 +1,5 @@
 // Data parallelism behind the C ABI: the RCCL communicator of a context (fu_dp_*), the bucketed gradient all-reduce
-// (fu_allreduce_begin / fu_allreduce_wait) and the exact-sync exchange of statistics (sync_sum_over_ranks).
+// (fu_allreduce_begin / fu_allreduce_wait) and the exact-sync exchange of statistics (sync_sum_over_ranks: a function of the descriptor its caller passes, no state here).
 // RCCL is resolved at run time (dlopen): the library has no link-time dependency on it, a process that never calls
 // fu_dp_init never loads it, and inside a torch process the copy torch already loaded is the one that is used.
 #include "fu_ctx.h"
@@ -10,11 +10,8 @@ using namespace fu;
 
 namespace fu {
 
-thread_local const SyncDesc* g_sync = nullptr;
-
-int sync_sum_over_ranks(void* payload, int64_t n_elems, bool is_double, hipStream_t s) {
-  const SyncDesc* d = g_sync;
-  if (!d || !d->hook || d->world <= 1) return 0;
+int sync_sum_over_ranks(const SyncDesc* d, void* payload, int64_t n_elems, bool is_double, hipStream_t s) {
+  if (sync_world(d) <= 1) return 0;
   const size_t bytes = (size_t)n_elems * (is_double ? 8 : 4);
   FU_REQUIRE((int64_t)bytes <= d->xbytes, "exact sync: exchange buffer too small (%zu > %lld bytes)", bytes,
              (long long)d->xbytes);

@@ -300,8 +300,8 @@ __global__ __launch_bounds__(256) void k_head_bwd_finalize(const float* __restri
 int64_t head_bwd_partial_elems(int C, int ncls) { return (int64_t)HB_BLOCKS * (ncls * C + ncls); }
 
 int launch_head_bwd(Prec p, const float* dlogits_nhwc, const void* y, const float* a, const float* b, const float* w,
-                    int C, int ncls, int64_t npix, void* g, float* partials, float* dw, float* db, hipStream_t s,
-                    const BnbFuse* fuse) {
+                    int C, int ncls, int64_t npix, void* g, float* partials, float* dw, float* db,
+                    const float* unscale, hipStream_t s, const BnbFuse* fuse) {
   FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "head_bwd: n_classes must be 1..%d", HEAD_MAX_CLS);
   FU_REQUIRE(npix < ((int64_t)1 << 31), "head_bwd: too many pixels");
   return dispatch_prec(p, [&](auto tag) {
@@ -348,7 +348,7 @@ int launch_head_bwd(Prec p, const float* dlogits_nhwc, const void* y, const floa
 #undef FU_HEAD_BWD
     FU_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_head_bwd_finalize, dim3(ceil_div(stride, 8)), dim3(256), 0, s, partials, nblk, C, ncls,
-                       g_grad_unscale, dw, db);
+                       unscale, dw, db);
     FU_LAUNCH_CHECK();
     if (bnb) *fuse->tiles_out = nblk;
     return 0;

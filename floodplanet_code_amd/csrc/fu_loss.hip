@@ -230,7 +230,8 @@ __global__ __launch_bounds__(256) void k_ce_finalize(const float* __restrict__ p
 
 int launch_ce_loss(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
                    const CeWeighting* cw, float* partials, float* loss_out, int64_t* n_valid_dev,
-                   int64_t* confusion_accum, int64_t* n_valid_out, unsigned long long* conf_tmp, hipStream_t s) {
+                   int64_t* confusion_accum, int64_t* n_valid_out, unsigned long long* conf_tmp, const SyncDesc* sync,
+                   hipStream_t s) {
   FU_REQUIRE(ncls >= 1 && ncls <= HEAD_MAX_CLS, "CE: n_classes must be 1..%d", HEAD_MAX_CLS);
   const int nblk = grid_for(npix, CE_BLOCK, CE_MAX_BLOCKS);
   const bool focal = cw && cw->focal_gamma > 0.f;     // gamma == 0 is the weighted loss itself: its instantiation, its bits
@@ -251,7 +252,7 @@ int launch_ce_loss(const float* logits_nhwc, const int64_t* target, int ncls, in
 #undef FU_CE_LOSS_AS
   FU_LAUNCH_CHECK();
   // exact DP: the global sums (loss, N_valid; weighted: D too) before the division
-  FU_TRY(sync_sum_over_ranks(partials, (int64_t)nblk * (cw ? 4 : 2), false, s));
+  FU_TRY(sync_sum_over_ranks(sync, partials, (int64_t)nblk * (cw ? 4 : 2), false, s));
   if (cw)
     hipLaunchKernelGGL(k_ce_finalize<true>, dim3(1), dim3(256), 0, s, partials, nblk, ncls, cw->c_nll, cw->c_smooth,
                        loss_out, n_valid_dev, cw->weight_sum_dev, conf_tmp, confusion_accum, n_valid_out,
@@ -500,7 +501,8 @@ __global__ __launch_bounds__(256) void k_region_grad_add(const float* __restrict
 }
 
 int launch_region_term(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int64_t npix,
-                       const RegionTerm& rg, float* partials, float* loss_io, float* dlogits_nhwc, hipStream_t s) {
+                       const RegionTerm& rg, float* partials, float* loss_io, float* dlogits_nhwc, const SyncDesc* sync,
+                       hipStream_t s) {
   FU_REQUIRE(ncls >= 2 && ncls <= HEAD_MAX_CLS, "region term: n_classes must be 2..%d", HEAD_MAX_CLS);
   const int kmax = ncls <= 4 ? ncls : HEAD_MAX_CLS;               // the KMAX of FU_NC_SWITCH's instantiation
   const int nblk = grid_for(npix, CE_BLOCK, region_max_blocks(kmax));
@@ -516,7 +518,7 @@ int launch_region_term(const float* logits_nhwc, const int64_t* target, int ncls
   FU_NC_SWITCH(ncls, FU_REGION_SUMS);
   FU_LAUNCH_CHECK();
   // exact DP: I, P and T of the whole batch, so that every rank forms the same R and the same coefficients
-  FU_TRY(sync_sum_over_ranks(partials, (int64_t)nblk * 3 * kmax, false, s));
+  FU_TRY(sync_sum_over_ranks(sync, partials, (int64_t)nblk * 3 * kmax, false, s));
   FU_NC_SWITCH(ncls, FU_REGION_FINALIZE);
   FU_LAUNCH_CHECK();
   if (dlogits_nhwc) {
@@ -678,7 +680,7 @@ int launch_dlogits_from_nchw(const float* dlogits_nchw, float* dlogits_nhwc, int
 //   S:  fp16 mode only (scale != null): 2^k with max|dl * up| * S in [2^5, 2^6) -- three decades of headroom to fp16's
 //       65504 for what the backward chain multiplies on top, while the bulk of the gradient maps stays in fp16's normal
 //       range; chosen from the data on the device (no host read, any loss, any upstream scale).  scale[0] = S,
-//       scale[1] = 1/S (fu_common.h, g_grad_unscale).
+//       scale[1] = 1/S (fu_common.h: what the gradient-writing launches get as `unscale`).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_absmax_partial(const float* __restrict__ x, int64_t n, float* __restrict__ partials) {
   __shared__ float sm[4];

@@ -264,7 +264,7 @@ int fu_op_head_bwd(int precision, const float* dlogits_nhwc, const void* y, cons
     FU_TRY(bpart.get((size_t)cap * sizeof(float)));
     f = bnb_fuse(y, bn_a, bn_b, mean, invstd, (float*)bpart.p, cap, &tiles);
   }
-  FU_TRY(launch_head_bwd(p, dlogits_nhwc, y, bn_a, bn_b, w, C, ncls, npix, g, (float*)part.p, dw, db, s,
+  FU_TRY(launch_head_bwd(p, dlogits_nhwc, y, bn_a, bn_b, w, C, ncls, npix, g, (float*)part.p, dw, db, nullptr, s,
                          want ? &f : nullptr));
   if (want) {
     if (tiles <= 0) {
@@ -288,10 +288,6 @@ __global__ void k_rows_collapse(const float* part, int n, int C, float* out) {
   for (int t = 0; t < n; ++t) s += part[(int64_t)t * C + c];
   out[c] = (float)s;
 }
-struct UnscaleGuard {     // g_grad_unscale for the duration of one hook call
-  explicit UnscaleGuard(const float* u) { g_grad_unscale = u; }
-  ~UnscaleGuard() { g_grad_unscale = nullptr; }
-};
 }  // namespace
 
 int fu_op_bn_stats(const float* partials, int n_part, int C, int64_t count, const float* conv_bias, const float* gamma,
@@ -305,7 +301,7 @@ int fu_op_bn_stats(const float* partials, int n_part, int C, int64_t count, cons
   TmpBuf scr;
   FU_TRY(scr.get((size_t)reduce_scratch_elems(C) * sizeof(double)));
   const BnFwdOut o{conv_bias, gamma, beta, eps, momentum, mean, invstd, a, b, rmean, rvar, nbt};
-  FU_TRY(launch_bn_finalize(o, partials, n_part, C, count, (double*)scr.p, s));
+  FU_TRY(launch_bn_finalize(o, partials, n_part, C, count, (double*)scr.p, nullptr, s));
   FU_HIP_CHECK(hipStreamSynchronize(s));
   return FU_OK;
 }
@@ -351,10 +347,8 @@ int fu_op_bn_bwd_ex(int precision, void* g, const void* y, int C, int B, int H, 
   A.ext_partials = ext_rows;
   A.head = head_dl ? &hg : nullptr;
   A.two_level = two_level != 0;
-  {
-    UnscaleGuard guard(unscale);
-    FU_TRY(launch_bn_bwd(p, A, s));
-  }
+  A.unscale = unscale;
+  FU_TRY(launch_bn_bwd(p, A, s));
   if (db) {
     hipLaunchKernelGGL(k_rows_collapse, dim3(ceil_div(C, 64)), dim3(64), 0, s, (const float*)dbp.p, ndb, C, db);
     FU_LAUNCH_CHECK();

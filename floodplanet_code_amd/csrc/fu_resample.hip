@@ -327,8 +327,8 @@ int launch_space_to_depth(Prec p, const void* gup, void* g4, int B, int h, int w
     return 0;
   });
 }
-int launch_colsum_partials(const float* partials, int n, int C, float* out, hipStream_t s) {
-  hipLaunchKernelGGL(k_colsum_partials, dim3(ceil_div(C, 64)), dim3(64), 0, s, partials, n, C, g_grad_unscale, out);
+int launch_colsum_partials(const float* partials, int n, int C, const float* unscale, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_colsum_partials, dim3(ceil_div(C, 64)), dim3(64), 0, s, partials, n, C, unscale, out);
   FU_LAUNCH_CHECK();
   return 0;
 }

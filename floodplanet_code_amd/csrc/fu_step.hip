@@ -66,7 +66,7 @@ static int conv_fwd(fu_ctx* c, int i, int j, int B, bool training, hipStream_t s
     o.eps = BN_EPS; o.momentum = BN_MOMENTUM;
     o.mean = v.mean; o.invstd = v.invstd; o.a = v.a; o.b = v.b;
     o.rmean = c->RM + off; o.rvar = c->RV + off; o.nbt = c->NBT + v.bn;
-    FU_TRY(launch_bn_finalize(o, c->stats, nt, v.cout, (int64_t)B * H * W, c->dscratch, s));
+    FU_TRY(launch_bn_finalize(o, c->stats, nt, v.cout, (int64_t)B * H * W, c->dscratch, active_sync(c, training), s));
   }
   return 0;
 }
@@ -98,6 +98,7 @@ static int fuse_backward(fu_ctx* c, int B, hipStream_t s) {
     int ndbp = 0;
     FU_TRY(launch_channel_partial_sums(c->prec, F.gy, F.C, npix, c->db_part, &ndbp, s));
     ConvIn in{F.cat, Ccat, nullptr, nullptr, nullptr, 0, true};   // only the centre tap of dw3 is computed (and read)
+    in.opt.unscale = grad_unscale(c);
     FU_TRY(launch_conv3x3_wgrad(c->prec, in, F.gy, F.C, c->slab, F.dw3, Ccat, c->db_part, ndbp, G(c, F.p_b), B, H, W,
                                 s));
     FU_TRY(launch_center_from_w3(F.dw3, (int64_t)F.C * Ccat, G(c, F.p_w), s));
@@ -215,6 +216,7 @@ static int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
   A.a = v.a; A.b = v.b; A.mean = v.mean; A.invstd = v.invstd;
   A.dgamma = G(c, v.p_g); A.dbeta = G(c, v.p_beta);
   A.partials = c->bnb_part; A.coef = v.coef; A.db_partials = dbp; A.n_db_partials = &ndb; A.dscratch = c->dscratch;
+  A.sync = active_sync(c, true); A.unscale = grad_unscale(c);
   A.g_pool = v.pool_g; A.B = B; A.H = H; A.W = W;
   A.ext_partials = v.bnb_tiles;
   A.head = v.head.dl ? &v.head : nullptr;
@@ -233,6 +235,7 @@ static int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
     c->side_open = true;
   }
   in.opt.prof = prof_arm(c, FU_K_WGRAD, fl);
+  in.opt.unscale = A.unscale;
   FU_TRY(launch_conv3x3_wgrad(c->prec, in, v.gy, v.cout, c->slab, G(c, v.p_w), v.cin_real, dbp, ndb,
                               G(c, v.p_b), B, H, W, ws));
   // data gradient
@@ -245,7 +248,7 @@ static int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
     const bool separate = g_bnb_separate != 0;      // testing hook: always the separate reduce pass
     int tiles = 0;
     BnbFuse f;
-    if (c->prec != PREC_F32 && !c->sync.hook && !separate) {
+    if (c->prec != PREC_F32 && !A.sync && !separate) {
       f = bnb_fuse(v0.y, v0.a, v0.b, v0.mean, v0.invstd, c->bnb_part, c->bnb_cap, &tiles);
       din.opt.bnb = &f;
     }
@@ -274,8 +277,9 @@ static int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
       FU_TRY(launch_space_to_depth(c->prec, K.g_up, K.g_u, B, h, w, K.ct_cout, H, W, s));
       int ndbp = 0;
       FU_TRY(launch_channel_partial_sums(c->prec, K.g_u, K.ct_cout, (int64_t)B * h * w * 4, c->db_part, &ndbp, s));
-      FU_TRY(launch_colsum_partials(c->db_part, ndbp, K.ct_cout, G(c, K.ct_b), s));
+      FU_TRY(launch_colsum_partials(c->db_part, ndbp, K.ct_cout, A.unscale, G(c, K.ct_b), s));
       ConvIn lin{pv.y, pv.C, pv.a, pv.b, nullptr, 0, true};
+      lin.opt.unscale = A.unscale;
       FU_TRY(launch_conv3x3_wgrad(c->prec, lin, K.g_u, 4 * K.ct_cout, c->slab, K.ct_dw3, K.ct_cin, nullptr, 0, nullptr, B, h,
                                   w, s));
       FU_TRY(launch_convT_grad_from_w3(K.ct_dw3, K.ct_cin, K.ct_cout, G(c, K.ct_w), s));
@@ -318,7 +322,7 @@ int backward_block_impl(fu_ctx* c, int block, const float* dlogits_ext, hipStrea
     }
     // What the head backward reads: the stored gradient itself, or -- out of place, so that a repeated backward of the same
     // loss starts from the same input -- times the upstream gradient of loss.backward() and, for fp16 gradient maps, the
-    // power-of-two loss scale chosen from max|dL/dlogits| (UnscaleScope removes it where parameter gradients are written)
+    // power-of-two loss scale chosen from max|dL/dlogits| (grad_unscale: taken out again where parameter gradients are written)
     const float* dl = c->dlogits;
     if (c->prec == PREC_F16 || c->have_up_scale) {
       FU_TRY(launch_loss_grad_eff(c->dlogits, c->dlogits_eff, (int64_t)B * f.height * f.width * f.n_classes,
@@ -331,15 +335,15 @@ int backward_block_impl(fu_ctx* c, int block, const float* dlogits_ext, hipStrea
     // the head's data gradient is dL/d relu(bn(y)) of the last conv: it can leave that BatchNorm's backward sums behind
     BnbFuse fz;
     int tiles = 0;
-    const bool want = c->prec != PREC_F32 && !c->sync.hook && !g_bnb_separate;
+    const bool want = c->prec != PREC_F32 && !active_sync(c, true) && !g_bnb_separate;
     if (want) {
       fz = bnb_fuse(last.y, last.a, last.b, last.mean, last.invstd, c->bnb_part, c->bnb_cap, &tiles);
       // ... and then g = dl . w need not be stored at all: the apply pass of that BatchNorm recomputes it (HeadGrad)
       fz.skip_g = last.cout % 8 == 0 && 2048 % last.cout == 0 && !g_head_store_g;
     }
     FU_TRY(launch_head_bwd(c->prec, dl, last.y, last.a, last.b, P(c, c->p_outw), f.base_channels, f.n_classes,
-                           (int64_t)B * f.height * f.width, last.gy, c->hb_part, G(c, c->p_outw), G(c, c->p_outb), s,
-                           want ? &fz : nullptr));
+                           (int64_t)B * f.height * f.width, last.gy, c->hb_part, G(c, c->p_outw), G(c, c->p_outb),
+                           grad_unscale(c), s, want ? &fz : nullptr));
     last.bnb_tiles = tiles;
     FU_REQUIRE(!(want && fz.skip_g) || tiles > 0, "head backward: the fused BatchNorm sums were refused (partials %lld floats)",
                (long long)c->bnb_cap);

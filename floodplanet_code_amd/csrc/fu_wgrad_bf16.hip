@@ -940,7 +940,7 @@ int launch_conv3x3_wgrad_bf16(const ConvIn& in, const bf16_t* dy, int Cout, floa
     case WGRAD_NUM_ROUTES: break;
   }
   if (st) return st;
-  return launch_wgrad_reduce_oihw(slab, P.S, P.Cin, Cout, cin_real, dw_oihw, db_partials, n_db_partials, db, s);
+  return launch_wgrad_reduce_oihw(slab, P.S, P.Cin, Cout, cin_real, dw_oihw, db_partials, n_db_partials, db, in.opt.unscale, s);
 }
 
 }  // namespace fu

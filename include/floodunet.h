@@ -39,6 +39,9 @@
  *   - every function returns FU_OK (0) or an error code; fu_last_error() returns a thread-local
  *     message.  No C++ exception crosses this boundary.
  *   - one context per device per process; calls on one context must be serialised by the caller.
+ *     Contexts are independent of each other: no launch depends on which device launched first or on
+ *     what a call on another context left behind (per-device launch facts are kept per device index,
+ *     exact-sync and fp16 loss-scale state per context).
  */
 #ifndef FLOODUNET_H_
 #define FLOODUNET_H_
