@@ -99,12 +99,25 @@ int fu_create(const fu_config* cfg, fu_ctx** out) {
       c->side_lo = nullptr;
     c->side = c->side_lo ? c->side_lo : c->side_def;        // side_mode starts at 1
     if (c->side) {
-      bool ok = hipEventCreateWithFlags(&c->ev_gy, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&c->ev_blk, hipEventDisableTiming) == hipSuccess;
+      bool ok = hipEventCreateWithFlags(&c->ev_gy, EVENT_FLAGS) == hipSuccess &&
+                hipEventCreateWithFlags(&c->ev_blk, EVENT_FLAGS) == hipSuccess;
       if (!ok) {
         if (c->side_lo) (void)hipStreamDestroy(c->side_lo);
         (void)hipStreamDestroy(c->side_def);
         c->side = c->side_lo = c->side_def = nullptr;
+      }
+    }
+    if (c->side) {
+      // the private split-K workspace of a backward's last weight-gradient chain (backward_conv): only beside a side
+      // stream; without the memory that chain goes to the side stream like every other one
+      const Conv& v = c->blk[0].c[0];
+      const size_t bytes = conv3x3_wgrad_slab_elems(c->prec, v.cin_pad, v.cout, c->cfg.max_batch, c->Hs[0], c->Ws[0]) * sizeof(float);
+      void* p = nullptr;
+      if (hipMalloc(&p, bytes) == hipSuccess) {
+        c->slab_tail = (float*)p;
+        c->extra_allocs.push_back(p);
+      } else {
+        (void)hipGetLastError();
       }
     }
   }
@@ -403,8 +416,8 @@ int fu_backward_join(fu_ctx* c, fu_stream stream) {
 int fu_backward_fence(fu_ctx* c, fu_stream stream, fu_stream waiter) {
   FU_REQUIRE(c, "null context");
   FU_REQUIRE(stream != waiter, "fu_backward_fence: the waiting stream must not be the compute stream (use fu_backward_join)");
-  if (!c->ev_fence[0]) FU_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fence[0], hipEventDisableTiming));
-  if (!c->ev_fence[1]) FU_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fence[1], hipEventDisableTiming));
+  if (!c->ev_fence[0]) FU_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fence[0], EVENT_FLAGS));
+  if (!c->ev_fence[1]) FU_HIP_CHECK(hipEventCreateWithFlags(&c->ev_fence[1], EVENT_FLAGS));
   FU_HIP_CHECK(hipEventRecord(c->ev_fence[0], (hipStream_t)stream));
   FU_HIP_CHECK(hipStreamWaitEvent((hipStream_t)waiter, c->ev_fence[0], 0));
   if (c->side && c->side_mode != 0) {     // (nothing is pending there in mode 1: every block has joined already)

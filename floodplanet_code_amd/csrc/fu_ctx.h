@@ -196,6 +196,8 @@ struct fu_ctx {
   double* dscratch = nullptr;
   fu::SyncDesc sync;           // exact data-parallel mode (fu_set_exact_sync); hook == nullptr: off
   float* slab = nullptr;
+  float* slab_tail = nullptr;     // split-K workspace of the LAST weight-gradient chain of a backward alone (blk[0].c[0], which runs on
+                                  // the caller's stream while the chain before it may still use `slab` on the side stream: backward_conv)
   float* ce_part = nullptr;
   float* hb_part = nullptr;
   float* loss_dev = nullptr;
@@ -237,6 +239,13 @@ int alloc_workspace(fu_ctx* c);
 // the device tables of one bilinear x2 resize; every allocation is appended to *allocs (the caller frees them)
 int build_up_tables(std::vector<void*>* allocs, int H, int W, UpTables* t);
 int repack(fu_ctx* c, hipStream_t s, bool eval);
+// The events of the context hand work from one stream to another on ONE device (ev_gy, ev_blk, the fence pair): their records
+// need no system-scope release, which is there for the host and for other devices (hip_runtime_api.h).  The data-parallel
+// events of fu_dp.hip order work against RCCL and the host and keep it.  The waiter of fu_backward_fence may be the stream
+// that RCCL's all-reduce is launched from: that holds while the collective's kernel on THIS device reads the gradients
+// itself (through the local L2) and sends them on; a transport in which a peer reads the user buffer directly would need
+// the fence back on ev_fence.  Only single-GPU runs have measured and checked this flag.
+constexpr unsigned EVENT_FLAGS = hipEventDisableTiming | hipEventDisableSystemFence;
 
 // fu_step.hip
 int forward_impl(fu_ctx* c, const float* x, const SrcList* srcs, int B, bool training, float* logits_out,

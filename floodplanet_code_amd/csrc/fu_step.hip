@@ -207,7 +207,10 @@ static int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
   //   mode 0                         there is no second stream;
   //   a repeated backward of one loss is one of the above twice: the first one's join is in front of the second one's block 0;
   //   fuse_backward                  joins first and then uses the context's buffer (c->db_part), like the ConvTranspose path,
-  //                                  which exists only without a side stream.
+  //                                  which exists only without a side stream;
+  //   the last chain of a backward   (`tail` below) runs on the caller's stream itself, behind this launch_bn_bwd: the next
+  //                                  writer of its db_part is a launch on that same stream, ordered by the stream with no join
+  //                                  at all -- and so is its private workspace (slab_tail), which no other chain touches.
   // (A backward on another stream than the one that joined is ordered by the caller, as for every other buffer of the context.)
   const bool side = c->side != nullptr && c->side_mode != 0;
   float* dbp = v.db_part;
@@ -227,8 +230,13 @@ static int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
   // weight (and bias) gradient
   ConvIn in = conv_input(c, i, j);
   const double fl = 2.0 * 9 * v.cin_real * v.cout * (double)B * H * W;
+  // The last chain of a backward (the first conv of the encoder that is processed last: no data gradient, so nothing is left
+  // on the caller's stream to run beside it) stays on the caller's stream: the hop to the side stream and back would only add
+  // its hand-off latency in front of the optimiser step.  The chain before it may still be reducing out of c->slab on the
+  // side stream, so this one has a workspace of its own.
+  const bool tail = side && c->slab_tail != nullptr && i == 0 && j == 0;
   hipStream_t ws = s;
-  if (side) {
+  if (side && !tail) {
     FU_HIP_CHECK(hipEventRecord(c->ev_gy, s));
     FU_HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_gy, 0));
     ws = c->side;
@@ -236,7 +244,7 @@ static int backward_conv(fu_ctx* c, int i, int j, int B, hipStream_t s) {
   }
   in.opt.prof = prof_arm(c, FU_K_WGRAD, fl);
   in.opt.unscale = A.unscale;
-  FU_TRY(launch_conv3x3_wgrad(c->prec, in, v.gy, v.cout, c->slab, G(c, v.p_w), v.cin_real, dbp, ndb,
+  FU_TRY(launch_conv3x3_wgrad(c->prec, in, v.gy, v.cout, tail ? c->slab_tail : c->slab, G(c, v.p_w), v.cin_real, dbp, ndb,
                               G(c, v.p_b), B, H, W, ws));
   // data gradient
   ConvIn din{v.gy, v.cout, nullptr, nullptr, nullptr, 0};
