@@ -36,29 +36,33 @@ else the parent directory.  What runs differently:
     (fu_stitch_finalize_maps_ex); --calibration FILE takes C and T from the calibration.json of predict --calibrate.
     class_pixels follows the rule, the sieve runs on the thresholded map, the probability and margin rasters do not
     change; the summary records the rule under "threshold".
+How infer() is put together: the options travel as one checked InferOptions (infer_options.py; the keywords of infer() and
+the command line both go through InferOptions.make); predict.load_eval_model serves the model; a SceneQueue owns the
+scenes in flight and deals their crops out in batches; per batch scene_crops, predict.eval_forward and one batched stitch;
+per finished scene finalize_scene (the launches and the one read, stitch.PackedRead) and write_scene (host only).
 Out of scope: multi-GPU inference, inputs besides ms_image (dem, slope, hand, preflood), RGB outputs, BigTIFF or
 compressed output.
 """
 from __future__ import annotations
 
 import argparse
+import functools
 import json
 import os
 import time
 from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from .predict import CONFIG_DEFAULTS, WEIGHT_CHOICES, _merge, load_checkpoint_model, resolve_cfg
-from .postprocess import check_sieve_options
-from .stitch import BLEND_KINDS
-from .tta import VIEW_SETS, view_codes
+from .infer_options import (BLEND_KINDS, PROB_FORMATS, WEIGHT_CHOICES, InferOptions, default_stride, grid_size,  # noqa: F401
+                            threshold_rule)
+from .predict import CONFIG_DEFAULTS, _merge, eval_forward, load_eval_model, resolve_cfg
+from .tta import VIEW_SETS, recorded
 
 SCALE_MODES = {"S1": 1, "S2": 2, "L8": 3}                    # PS: 4 when stored as uint16, else 0
 EXTRA_SOURCES = ("dem", "slope", "preflood", "pre_post_difference", "chirps", "hand")
-PROB_FORMATS = ("u8", "f32")
 
 
 # ---------------------------------------------------------------------------------------------------------- host side
@@ -94,31 +98,6 @@ def output_path(out_dir: str, path: str, sensor: str) -> str:
 def side_output_path(out_path: str, kind: str) -> str:
     """<image>_prob.tif / <image>_margin.tif beside the class map <image>.tif."""
     return out_path[:-len(".tif")] + f"_{kind}.tif"
-
-
-def default_stride(crop_h: int, crop_w: int, blend: str = "uniform", stride: Optional[int] = None) -> int:
-    """An explicit stride wins; else min(crop_h, crop_w) (infer.py:64-65) under "uniform", and half of that under a
-    window blend -- without overlap there is nothing to blend."""
-    if stride is not None:
-        return int(stride)
-    return min(crop_h, crop_w) if blend == "uniform" else max(1, min(crop_h, crop_w) // 2)
-
-
-def grid_size(src_hw: Tuple[int, int], size: Optional[Sequence[int]] = None, scale: Optional[float] = None):
-    """Output grid of a scene: --size H W, else round(--scale * source size), else the source size."""
-    if size is not None and scale is not None:
-        raise ValueError("infer: --size and --scale are mutually exclusive")
-    if size is not None:
-        h, w = int(size[0]), int(size[1])
-    elif scale is not None:
-        if not scale > 0:
-            raise ValueError(f"infer: --scale must be > 0, got {scale}")
-        h, w = int(round(src_hw[0] * scale)), int(round(src_hw[1] * scale))
-    else:
-        h, w = int(src_hw[0]), int(src_hw[1])
-    if h < 1 or w < 1:
-        raise ValueError(f"infer: empty output grid {h}x{w}")
-    return h, w
 
 
 def crop_boxes(H: int, W: int, crop_h: int, crop_w: int, stride: int) -> List[Tuple[int, int, int, int]]:
@@ -213,27 +192,6 @@ class SceneFiles(torch.utils.data.Dataset):
                 "index": i}
 
 
-def threshold_rule(water_threshold: Optional[float] = None, threshold_class: Optional[int] = None,
-                   calibration: Optional[str] = None) -> Optional[dict]:
-    """The decision rule the options ask for -> None (the argmax) or {"class", "threshold", "source"}.  Host only; raises
-    on contradictory options: a threshold together with a calibration file, a class without a threshold."""
-    from .calibration import check_threshold, read_calibration
-    if calibration is not None:
-        if water_threshold is not None or threshold_class is not None:
-            raise ValueError("infer: --calibration already names the class and the threshold; it excludes "
-                             "--water_threshold and --threshold_class")
-        cls, thr = read_calibration(calibration)
-        source = str(calibration)
-    elif water_threshold is not None:
-        cls, thr, source = (1 if threshold_class is None else threshold_class), water_threshold, "option"
-    elif threshold_class is not None:
-        raise ValueError("infer: --threshold_class needs --water_threshold")
-    else:
-        return None
-    cls, thr = check_threshold(thr, cls)
-    return {"class": cls, "threshold": thr, "source": source}
-
-
 def check_model_inputs(cfg: dict, norm_params=None) -> None:
     """infer feeds the model ms_image only: reject configs whose model also takes dem / slope / ... (before any GPU work).
     norm_mode 'global' is accepted only together with its parameters."""
@@ -248,43 +206,10 @@ def check_model_inputs(cfg: dict, norm_params=None) -> None:
 
 
 # ---------------------------------------------------------------------------------------------------------- infer
-def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Optional[dict] = None,
-          size: Optional[Sequence[int]] = None, scale: Optional[float] = None, stride: Optional[int] = None,
-          batch_size: Optional[int] = None, tta=None, n_workers: int = 0, device: str = "cuda:0",
-          keep_probabilities: bool = False, norm_params=None, weights: str = "auto", blend: str = "uniform",
-          write_probs: Optional[str] = None, write_margin: bool = False, sieve: Optional[int] = None,
-          sieve_connectivity: int = 4, sieve_passes: int = 1, water_threshold: Optional[float] = None,
-          threshold_class: Optional[int] = None, calibration: Optional[str] = None) -> dict:
-    """Class maps of every input scene (see the module docstring).  cfg: the resolved config (default: resolve_cfg of
-    the checkpoint's experiment).  Returns the summary.json dict; with keep_probabilities also "probabilities"
-    {output path: fp32 [H, W, k] stitched canvas} (one more host read per scene; for tests and comparisons).
-    norm_params: the parameter file of norm_mode 'global' (path, or the dict it holds; datasets.stats), looked up by the
-    config's data set name and sensor; without it a 'global' config is rejected.  weights: 'auto', 'raw' or 'ema'
-    (predict.checkpoint_weights); the summary records the choice made under "weights".  blend: "uniform", "linear" or
-    "hann" (stitch.blend_window); write_probs: None, "u8" or "f32"; write_margin: also write the top-2 margin raster.
-    sieve: None, or the minimum patch size in pixels of the written class map (postprocess.sieve on the device, with
-    sieve_connectivity 4 or 8 and sieve_passes 1..8); class_pixels and the other rasters stay un-sieved.
-    water_threshold / threshold_class / calibration: the one-versus-rest decision rule (threshold_rule) in place of the
-    argmax; the summary records it under "threshold"."""
+def model_inputs(cfg: dict, norm_params=None):
+    """What the config's model is fed -> (sensor, channels, {"ms_image": C}, the 'global' norm's (mean, std) or None).
+    Host only: an unsupported model or a bad parameter file fails here, before any GPU work."""
     from .datasets.floodplanet import _N_CHANNELS
-    from .models import build_model
-
-    t_start = time.perf_counter()
-    if weights not in WEIGHT_CHOICES:
-        raise ValueError(f"weights must be one of {list(WEIGHT_CHOICES)}, got {weights!r}")
-    if blend not in BLEND_KINDS:
-        raise ValueError(f"blend must be one of {list(BLEND_KINDS)}, got {blend!r}")
-    if write_probs is not None and write_probs not in PROB_FORMATS:
-        raise ValueError(f"write_probs must be one of {list(PROB_FORMATS)} or None, got {write_probs!r}")
-    rule = threshold_rule(water_threshold, threshold_class, calibration)
-    sieve_opts = None
-    if sieve is not None:
-        check_sieve_options(sieve, sieve_connectivity, sieve_passes)
-        sieve_opts = {"min_pixels": int(sieve), "connectivity": int(sieve_connectivity), "passes": int(sieve_passes)}
-    if cfg is None:
-        experiment_dir = "/".join(checkpoint_path.split("/")[:-2])
-        cfg = resolve_cfg(experiment_dir, checkpoint_path)
-    cfg = _merge(CONFIG_DEFAULTS, cfg)
     ds_cfg = cfg["dataset"]
     sensor, channels = ds_cfg["sensor"], ds_cfg.get("channels") or "ALL"
     norm_params = norm_params if norm_params is not None else cfg.get("norm_params")
@@ -294,154 +219,200 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     except KeyError:
         raise NotImplementedError(f'Cannot get number of {sensor} channels for channel query "{channels}"') from None
     global_params = None
-    if cfg["norm_mode"] == "global":                     # host only: a bad file fails before any GPU work
+    if cfg["norm_mode"] == "global":
         from .datasets.stats import sensor_norm_params
         gm, gs = sensor_norm_params(norm_params, ds_cfg.get("name") or "floodplanet", sensor, n_channels["ms_image"])
         global_params = (torch.from_numpy(gm).float(), torch.from_numpy(gs).float())
-    ch, cw = int(cfg["crop_height"]), int(cfg["crop_width"])
-    stride = default_stride(ch, cw, blend, stride)
-    if stride < 1:
-        raise ValueError(f"infer: stride must be >= 1, got {stride}")
-    bs = int(batch_size or cfg["batch_size"])
-    codes = view_codes(tta, ch, cw) if tta is not None else None
+    return sensor, channels, n_channels, global_params
+
+
+def scene_outputs(inputs: Sequence[str], out_dir: str, sensor: str) -> Tuple[List[str], List[str]]:
+    """-> (the input scenes, their class maps' paths); two inputs may not share an output."""
     paths = find_inputs(inputs)
     outs = [output_path(out_dir, p, sensor) for p in paths]
     if len(set(outs)) != len(outs):
         dup = sorted({o for o in outs if outs.count(o) > 1})
         raise ValueError(f"infer: several inputs map to the same output {dup[:3]}")
-    if size is not None or scale is not None:            # option errors before any GPU work
-        grid_size((1 << 20, 1 << 20), size, scale)
+    return paths, outs
 
-    from .datasets.assemble import scene_crops
-    from .postprocess import sieve as sieve_map
-    from .stitch import GpuImageStitcher
-    from .datasets.synthetic import write_strip_tiff
-    dev = torch.device(device)
-    model_kwargs = {k: v for k, v in (cfg["model"].get("model_kwargs") or {}).items()
-                    if k not in ("ema_decay", "ema_warmup")}
-    model = build_model(cfg["model"]["name"], n_channels, 3, cfg["lr"], log_image_iter=cfg["log_image_iter"],
-                        to_rgb_fcn=None, ignore_index=cfg["ignore_index"], **model_kwargs)
-    model, chosen = load_checkpoint_model(model, checkpoint_path, weights, in_channels=n_channels, n_classes=3,
-                                          lr=cfg["lr"], **model_kwargs)
-    model._set_model_to_eval()
-    model = model.to(dev)
-    net = model.model
-    k = net.n_classes
-    if rule is not None and rule["class"] >= k:
-        raise ValueError(f"infer: threshold class {rule['class']} not in 0..{k - 1}")
-    T = len(codes) if codes is not None else 1
-    net._get_ctx(dev, T * bs, ch, cw)                    # the context owns fu_scene_crops' table: make it at full size
-    stitcher = GpuImageStitcher(net, dev, blend=blend)
-    class_values = [0] + [255] * (k - 1)                 # clip(argmax, 0, 1) * 255
-    C = n_channels["ms_image"]
-    crop_buf = torch.empty(bs, C, ch, cw, dtype=torch.float32, device=dev)
-    loader = torch.utils.data.DataLoader(SceneFiles(paths, sensor, channels), batch_size=None, shuffle=False,
-                                         num_workers=n_workers, pin_memory=dev.type == "cuda")
-    scenes_it = iter(loader)
-    resident: "OrderedDict[int, dict]" = OrderedDict()   # scene index -> grid, boxes, ...
-    pending: List[Tuple[int, Tuple[int, int, int, int]]] = []   # crops not yet run: (scene, box)
-    records, probabilities = [], {}
-    n_crops = max_resident = 0
-    exhausted = False
 
-    def upload(item):
-        i = int(item["index"])
-        raster = item["raster"]
-        src_hw = (raster.shape[1], raster.shape[2])
-        H, W = grid_size(src_hw, size, scale)
-        grid = resident_grid(raster, int(item["scale_mode"]), (H, W), dev)
-        boxes = crop_boxes(H, W, ch, cw, stride)
-        resident[i] = {"grid": grid, "hw": (H, W), "src_hw": src_hw, "tags": item["tags"], "left": len(boxes),
-                       "n": len(boxes)}
-        pending.extend((i, b) for b in boxes)
+def upload_scene(item: dict, options: InferOptions, crop_hw: Tuple[int, int], device):
+    """A decoded scene (SceneFiles) -> (its index, the scene as it stays resident: its grid on the device, sizes, tags
+    and crop count, its crop boxes)."""
+    raster = item["raster"]
+    src_hw = (raster.shape[1], raster.shape[2])
+    H, W = options.grid(src_hw)
+    grid = resident_grid(raster, int(item["scale_mode"]), (H, W), device)
+    boxes = crop_boxes(H, W, crop_hw[0], crop_hw[1], options.stride)
+    return int(item["index"]), {"grid": grid, "hw": (H, W), "src_hw": src_hw, "tags": item["tags"], "n": len(boxes)}, boxes
 
-    def finalize(i):
-        sc = resident.pop(i)
-        H, W = sc["hw"]
-        key = str(i)
-        maps = stitcher.combine_maps(key, class_values, probs=write_probs == "u8", margin=write_margin, counts=True,
-                                     threshold=None if rule is None else (rule["class"], rule["threshold"]))
-        if sieve_opts is not None:                       # in place, on the stream of the launch above; no host read
-            _, sieve_stats = sieve_map(maps["class"], sieve_opts["min_pixels"], sieve_opts["connectivity"],
-                                       passes=sieve_opts["passes"], out=maps["class"])
-        parts = [maps["counts"].view(torch.uint8), maps["class"].view(-1)]
-        parts += [maps[m].view(-1) for m in ("probs", "margin") if m in maps]
-        if write_probs == "f32":                         # the normalised canvas itself, as bytes of the same read
-            parts.append(maps["canvas"].view(torch.uint8).view(-1))
-        if sieve_opts is not None:
-            parts.append(sieve_stats.view(torch.uint8))
-        packed = torch.cat(parts).cpu().numpy()          # one launch above, the one device-to-host read here
-        if keep_probabilities:
-            probabilities[outs[i]] = maps["canvas"].cpu().numpy()
-        stitcher.drop(key)
-        class_pixels = packed[:8 * k].view(np.int64).tolist()
-        at = 8 * k
-        cls_h = packed[at:at + H * W].reshape(H, W)
-        at += H * W
-        tags = geo_tags_for_grid(sc["tags"], sc["src_hw"], (H, W))
-        write_strip_tiff(outs[i], cls_h, extra_tags=tags)
-        rec = {"input": paths[i], "output": outs[i], "source_size": list(sc["src_hw"]), "grid_size": [H, W],
-               "crops": sc["n"], "class_pixels": class_pixels}
-        if write_probs == "u8":
-            rec["probabilities"] = side_output_path(outs[i], "prob")
-            write_strip_tiff(rec["probabilities"], packed[at:at + k * H * W].reshape(k, H, W), extra_tags=tags)
-            at += k * H * W
-        if write_margin:
-            rec["margin"] = side_output_path(outs[i], "margin")
-            write_strip_tiff(rec["margin"], packed[at:at + H * W].reshape(H, W), extra_tags=tags)
-            at += H * W
-        if write_probs == "f32":
-            rec["probabilities"] = side_output_path(outs[i], "prob")
-            canvas_h = packed[at:at + 4 * k * H * W].view(np.float32).reshape(H, W, k)
-            write_strip_tiff(rec["probabilities"], np.ascontiguousarray(canvas_h.transpose(2, 0, 1)), extra_tags=tags)
-        if sieve_opts is not None:
-            merged, changed = packed[-16:].view(np.int64).tolist()
-            rec["sieve"] = dict(sieve_opts, merged_components=merged, changed_pixels=changed)
-        records.append(rec)
 
-    with torch.no_grad():
+class SceneQueue:
+    """The scenes in flight and their crops that have not run yet.  scenes: an iterable of decoded scenes; upload(scene)
+    -> (scene index, what stays resident of it, its crop boxes).  batches() yields lists of up to batch_size
+    (scene index, box), in scene order and then box order, and uploads the next scene only while fewer than batch_size
+    crops are pending; after a batch is stitched, stitched(batch) hands out the scenes it completed, in scene order,
+    and forgets them.  resident: scene index -> the uploaded scene; max_resident: the most there were at once."""
+
+    def __init__(self, scenes: Iterable, upload: Callable, batch_size: int):
+        self._scenes, self._upload, self._batch_size = iter(scenes), upload, int(batch_size)
+        self.resident: "OrderedDict[int, object]" = OrderedDict()
+        self.max_resident = 0
+        self._left: Dict[int, int] = {}                  # scene index -> crops not yet stitched
+        self._pending: List[Tuple[int, tuple]] = []      # crops not yet run: (scene index, box)
+        self._exhausted = False
+
+    def batches(self) -> Iterator[List[Tuple[int, tuple]]]:
         while True:
-            while len(pending) < bs and not exhausted:
+            while len(self._pending) < self._batch_size and not self._exhausted:
                 try:
-                    upload(next(scenes_it))
+                    i, scene, boxes = self._upload(next(self._scenes))
+                    self.resident[i], self._left[i] = scene, len(boxes)
+                    self._pending.extend((i, b) for b in boxes)
                 except StopIteration:
-                    exhausted = True
-                max_resident = max(max_resident, len(resident))
-            if not pending:
-                break
-            batch, pending = pending[:bs], pending[bs:]
-            n = len(batch)
-            x, _, _ = scene_crops(net._ctx, [(resident[i]["grid"], b) for i, b in batch], (ch, cw), cfg["norm_mode"],
-                                  global_params, out=crop_buf)
-            probs = None
-            if codes is None:
-                net._forward_raw(model._gather_sources({"image": x}), False, want_logits=False)
-            else:
-                net.forward_views(model._gather_sources({"image": x}), codes)
-                probs, _ = net.merge_views(None, want_probs=True)
-            stitcher.add_images(range(n), [str(i) for i, _ in batch], [b for _, b in batch],
-                                [resident[i]["hw"][0] for i, _ in batch], [resident[i]["hw"][1] for i, _ in batch],
-                                probs=probs)
-            n_crops += n
-            for i, _ in batch:
-                resident[i]["left"] -= 1
-            for i in [i for i, sc in resident.items() if sc["left"] == 0]:
-                finalize(i)
+                    self._exhausted = True
+                self.max_resident = max(self.max_resident, len(self.resident))
+            if not self._pending:
+                return
+            batch, self._pending = self._pending[:self._batch_size], self._pending[self._batch_size:]
+            yield batch
 
-    seconds = time.perf_counter() - t_start
+    def stitched(self, batch: Sequence[Tuple[int, tuple]]) -> List[Tuple[int, object]]:
+        for i, _ in batch:
+            self._left[i] -= 1
+        done = [i for i in self.resident if self._left[i] == 0]
+        for i in done:
+            del self._left[i]
+        return [(i, self.resident.pop(i)) for i in done]
+
+
+def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: InferOptions) -> Dict[str, np.ndarray]:
+    """A stitched scene -> its host arrays, with one finalisation launch, the optional sieve (in place, on the same
+    stream) and ONE device-to-host read: "counts" int64 [k], "class" uint8 [H, W], and as the options ask "probs" uint8
+    [k, H, W], "margin" uint8 [H, W], "canvas" fp32 [H, W, k] (write_probs "f32"), "sieve" int64 [2].  With
+    keep_probabilities one more read: "kept", the canvas.  The scene's canvases are dropped."""
+    from .postprocess import sieve as sieve_map
+    from .stitch import PackedRead
+    maps = stitcher.combine_maps(key, class_values, probs=options.write_probs == "u8", margin=options.write_margin,
+                                 counts=True, threshold=None if options.threshold is None else options.threshold[:2])
+    read = PackedRead()
+    for name in ("counts", "class", "probs", "margin"):
+        if name in maps:
+            read.add(name, maps[name])
+    if options.write_probs == "f32":
+        read.add("canvas", maps["canvas"])
+    if options.sieve is not None:
+        min_pixels, connectivity, passes = options.sieve
+        _, stats = sieve_map(maps["class"], min_pixels, connectivity, passes=passes, out=maps["class"])
+        read.add("sieve", stats)
+    arrays = read.read()
+    if options.keep_probabilities:
+        arrays["kept"] = maps["canvas"].cpu().numpy()
+    stitcher.drop(key)
+    return arrays
+
+
+def write_scene(arrays: Dict[str, np.ndarray], scene: dict, options: InferOptions, path: str, out_path: str) -> dict:
+    """Host only: write a scene's class map and the side rasters the options ask for from finalize_scene's arrays, with
+    the input's georeferencing on the output grid (scene: "tags", "src_hw", "hw", "n") -> its summary.json record."""
+    from .datasets.synthetic import write_strip_tiff
+    H, W = scene["hw"]
+    tags = geo_tags_for_grid(scene["tags"], scene["src_hw"], (H, W))
+    write_strip_tiff(out_path, arrays["class"], extra_tags=tags)
+    rec = {"input": path, "output": out_path, "source_size": list(scene["src_hw"]), "grid_size": [H, W],
+           "crops": scene["n"], "class_pixels": arrays["counts"].tolist()}
+    if options.write_probs == "u8":
+        rec["probabilities"] = side_output_path(out_path, "prob")
+        write_strip_tiff(rec["probabilities"], arrays["probs"], extra_tags=tags)
+    if options.write_margin:
+        rec["margin"] = side_output_path(out_path, "margin")
+        write_strip_tiff(rec["margin"], arrays["margin"], extra_tags=tags)
+    if options.write_probs == "f32":
+        rec["probabilities"] = side_output_path(out_path, "prob")
+        write_strip_tiff(rec["probabilities"], np.ascontiguousarray(arrays["canvas"].transpose(2, 0, 1)), extra_tags=tags)
+    if options.sieve is not None:
+        merged, changed = arrays["sieve"].tolist()
+        rec["sieve"] = dict(options.sieve_options, merged_components=merged, changed_pixels=changed)
+    return rec
+
+
+def run_summary(records: List[dict], n_crops: int, seconds: float, max_resident: int, options: InferOptions,
+                weights: str) -> dict:
+    """summary.json of a run from its scene records and the resolved options."""
     summary = {"scenes": records, "n_scenes": len(records), "n_crops": n_crops, "seconds": seconds,
                "crops_per_s": n_crops / seconds if seconds > 0 else None, "max_resident_scenes": max_resident,
-               "tta": tta if (tta is None or isinstance(tta, str)) else list(codes), "weights": chosen,
-               "blend": blend, "stride": stride}
-    if rule is not None:
-        summary["threshold"] = rule
-    if sieve_opts is not None:
-        summary["sieve"] = dict(sieve_opts, merged_components=sum(r["sieve"]["merged_components"] for r in records),
+               "tta": recorded(options.tta, options.codes), "weights": weights, "blend": options.blend,
+               "stride": options.stride}
+    if options.threshold is not None:
+        summary["threshold"] = options.rule
+    if options.sieve is not None:
+        summary["sieve"] = dict(options.sieve_options,
+                                merged_components=sum(r["sieve"]["merged_components"] for r in records),
                                 changed_pixels=sum(r["sieve"]["changed_pixels"] for r in records))
+    return summary
+
+
+def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Optional[dict] = None, norm_params=None,
+          options: Optional[InferOptions] = None, **keywords) -> dict:
+    """Class maps of every input scene (see the module docstring).  cfg: the resolved config (default: resolve_cfg of
+    the checkpoint's experiment).  norm_params: the parameter file of norm_mode 'global' (path, or the dict it holds;
+    datasets.stats), looked up by the config's data set name and sensor; without it a 'global' config is rejected.
+    options: an InferOptions, or in its place the keywords of InferOptions.make (infer_options.KEYWORDS) -- size / scale,
+    stride, batch_size, tta, weights ('auto', 'raw' or 'ema'), blend, write_probs (None, "u8" or "f32"), write_margin,
+    sieve / sieve_connectivity / sieve_passes (only the written class map is sieved), water_threshold / threshold_class
+    / calibration (the one-versus-rest rule in place of the argmax), n_workers, device, keep_probabilities.  Returns the
+    summary.json dict, which records the weights served, the blend, the stride and, when set, "threshold" and "sieve";
+    with keep_probabilities also "probabilities" {output path: fp32 [H, W, k] stitched canvas} (one more host read per
+    scene; for tests and comparisons)."""
+    from .datasets.assemble import scene_crops
+    from .stitch import GpuImageStitcher
+
+    t_start = time.perf_counter()
+    if options is None:
+        options = InferOptions.make(**keywords)
+    elif keywords:
+        raise TypeError(f"infer(): options together with the keywords {sorted(keywords)}; give one or the other")
+    if cfg is None:
+        cfg = resolve_cfg("/".join(checkpoint_path.split("/")[:-2]), checkpoint_path)
+    cfg = _merge(CONFIG_DEFAULTS, cfg)
+    sensor, channels, n_channels, global_params = model_inputs(cfg, norm_params)
+    ch, cw = int(cfg["crop_height"]), int(cfg["crop_width"])
+    options = options.resolve(ch, cw, cfg["batch_size"])
+    paths, outs = scene_outputs(inputs, out_dir, sensor)
+
+    dev = torch.device(options.device)
+    model, chosen = load_eval_model(cfg, checkpoint_path, options.weights, n_channels, 3, dev)
+    net = model.model
+    options.check_classes(net.n_classes)
+    net._get_ctx(dev, options.n_views * options.batch_size, ch, cw)   # the context owns fu_scene_crops' table: full size
+    stitcher = GpuImageStitcher(net, dev, blend=options.blend)
+    class_values = [0] + [255] * (net.n_classes - 1)     # clip(argmax, 0, 1) * 255
+    crop_buf = torch.empty(options.batch_size, n_channels["ms_image"], ch, cw, dtype=torch.float32, device=dev)
+    loader = torch.utils.data.DataLoader(SceneFiles(paths, sensor, channels), batch_size=None, shuffle=False,
+                                         num_workers=options.n_workers, pin_memory=dev.type == "cuda")
+    queue = SceneQueue(loader, functools.partial(upload_scene, options=options, crop_hw=(ch, cw), device=dev),
+                       options.batch_size)
+    records, probabilities, n_crops = [], {}, 0
+    with torch.no_grad():
+        for batch in queue.batches():
+            scenes = [queue.resident[i] for i, _ in batch]
+            x, _, _ = scene_crops(net._ctx, [(sc["grid"], b) for sc, (_, b) in zip(scenes, batch)], (ch, cw),
+                                  cfg["norm_mode"], global_params, out=crop_buf)
+            probs, _ = eval_forward(net, model._gather_sources({"image": x}), options.codes, want_probs=True)
+            stitcher.add_images(range(len(batch)), [str(i) for i, _ in batch], [b for _, b in batch],
+                                [sc["hw"][0] for sc in scenes], [sc["hw"][1] for sc in scenes], probs=probs)
+            n_crops += len(batch)
+            for i, scene in queue.stitched(batch):
+                arrays = finalize_scene(stitcher, str(i), class_values, options)
+                if options.keep_probabilities:
+                    probabilities[outs[i]] = arrays.pop("kept")
+                records.append(write_scene(arrays, scene, options, paths[i], outs[i]))
+
+    summary = run_summary(records, n_crops, time.perf_counter() - t_start, queue.max_resident, options, chosen)
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "summary.json"), "w") as fh:
         json.dump(summary, fh, indent=4)
-    if keep_probabilities:
+    if options.keep_probabilities:
         summary["probabilities"] = probabilities
     return summary
 
@@ -498,15 +469,10 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv: Optional[List[str]] = None) -> None:
     args = build_parser().parse_args(argv)
-    threshold_rule(args.water_threshold, args.threshold_class, args.calibration)   # option errors before anything is read
+    options = InferOptions.from_args(args)               # option errors before anything is read
     experiment_dir = "/".join(args.checkpoint_path.split("/")[:-2])
     cfg = resolve_cfg(experiment_dir, args.checkpoint_path)
-    out = infer(args.checkpoint_path, args.inputs, args.out_dir, cfg=cfg, size=args.size, scale=args.scale,
-                stride=args.stride, batch_size=args.batch_size, tta=args.tta, n_workers=args.n_workers,
-                device=args.device, norm_params=args.norm_params, weights=args.weights, blend=args.blend,
-                write_probs=args.write_probs, write_margin=args.write_margin, sieve=args.sieve,
-                sieve_connectivity=args.sieve_connectivity, sieve_passes=args.sieve_passes,
-                water_threshold=args.water_threshold, threshold_class=args.threshold_class, calibration=args.calibration)
+    out = infer(args.checkpoint_path, args.inputs, args.out_dir, cfg=cfg, norm_params=args.norm_params, options=options)
     print(json.dumps({k: v for k, v in out.items() if k != "scenes"}))
 
 

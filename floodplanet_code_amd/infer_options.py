@@ -1,0 +1,169 @@
+"""InferOptions: the options of label-free scene inference (infer.infer) as one checked value.
+
+The command line (from_args) and infer()'s keywords both build one through InferOptions.make, which performs every check
+that needs no config; what depends on the model's crop size -- the default stride, the batch size, the view codes of
+test-time augmentation -- is filled in by resolve().  infer() reads the options and decides nothing about them itself.
+predict() shares check_weights, check_blend and tta.view_codes.  A new option is one field here, its keyword and check
+in make, and one flag in infer.build_parser.  Host arithmetic only: neither torch nor the GPU library is imported.
+"""
+from __future__ import annotations
+
+import dataclasses
+from typing import Optional, Sequence, Tuple, Union
+
+WEIGHT_CHOICES = ("auto", "raw", "ema")          # predict.checkpoint_weights
+BLEND_KINDS = ("uniform", "linear", "hann")      # stitch.blend_window
+PROB_FORMATS = ("u8", "f32")
+# the keywords of InferOptions.make, which are infer()'s option keywords and, but for keep_probabilities, its flags
+KEYWORDS = ("size", "scale", "stride", "batch_size", "tta", "n_workers", "device", "keep_probabilities", "weights",
+            "blend", "write_probs", "write_margin", "sieve", "sieve_connectivity", "sieve_passes", "water_threshold",
+            "threshold_class", "calibration")
+
+
+def check_weights(weights) -> str:
+    if weights not in WEIGHT_CHOICES:
+        raise ValueError(f"weights must be one of {list(WEIGHT_CHOICES)}, got {weights!r}")
+    return weights
+
+
+def check_blend(blend) -> str:
+    if blend not in BLEND_KINDS:
+        raise ValueError(f"blend must be one of {list(BLEND_KINDS)}, got {blend!r}")
+    return blend
+
+
+def check_write_probs(write_probs) -> Optional[str]:
+    if write_probs is not None and write_probs not in PROB_FORMATS:
+        raise ValueError(f"write_probs must be one of {list(PROB_FORMATS)} or None, got {write_probs!r}")
+    return write_probs
+
+
+def default_stride(crop_h: int, crop_w: int, blend: str = "uniform", stride: Optional[int] = None) -> int:
+    """An explicit stride wins; else min(crop_h, crop_w) (infer.py:64-65) under "uniform", and half of that under a
+    window blend -- without overlap there is nothing to blend."""
+    if stride is not None:
+        return int(stride)
+    return min(crop_h, crop_w) if blend == "uniform" else max(1, min(crop_h, crop_w) // 2)
+
+
+def grid_size(src_hw: Tuple[int, int], size: Optional[Sequence[int]] = None, scale: Optional[float] = None):
+    """Output grid of a scene: --size H W, else round(--scale * source size), else the source size."""
+    if size is not None and scale is not None:
+        raise ValueError("infer: --size and --scale are mutually exclusive")
+    if size is not None:
+        h, w = int(size[0]), int(size[1])
+    elif scale is not None:
+        if not scale > 0:
+            raise ValueError(f"infer: --scale must be > 0, got {scale}")
+        h, w = int(round(src_hw[0] * scale)), int(round(src_hw[1] * scale))
+    else:
+        h, w = int(src_hw[0]), int(src_hw[1])
+    if h < 1 or w < 1:
+        raise ValueError(f"infer: empty output grid {h}x{w}")
+    return h, w
+
+
+def threshold_rule(water_threshold: Optional[float] = None, threshold_class: Optional[int] = None,
+                   calibration: Optional[str] = None) -> Optional[dict]:
+    """The decision rule the options ask for -> None (the argmax) or {"class", "threshold", "source"}.  Host only; raises
+    on contradictory options: a threshold together with a calibration file, a class without a threshold."""
+    from .calibration import check_threshold, read_calibration
+    if calibration is not None:
+        if water_threshold is not None or threshold_class is not None:
+            raise ValueError("infer: --calibration already names the class and the threshold; it excludes "
+                             "--water_threshold and --threshold_class")
+        cls, thr = read_calibration(calibration)
+        source = str(calibration)
+    elif water_threshold is not None:
+        cls, thr, source = (1 if threshold_class is None else threshold_class), water_threshold, "option"
+    elif threshold_class is not None:
+        raise ValueError("infer: --threshold_class needs --water_threshold")
+    else:
+        return None
+    cls, thr = check_threshold(thr, cls)
+    return {"class": cls, "threshold": thr, "source": source}
+
+
+@dataclasses.dataclass(frozen=True)
+class InferOptions:
+    """size / scale: the output grid (grid_size); None, None: the raster's own.  stride and batch_size None: the
+    default_stride of the crop and the config's batch size, set by resolve().  tta: None, a tta.VIEW_SETS name or a
+    tuple of view codes; codes: its checked codes, set by resolve().  sieve: None or (min pixels, connectivity,
+    passes).  threshold: None (the argmax) or (class, threshold, source), threshold_rule's dict as a tuple."""
+    size: Optional[Tuple[int, int]] = None
+    scale: Optional[float] = None
+    stride: Optional[int] = None
+    batch_size: Optional[int] = None
+    tta: Union[None, str, Tuple[int, ...]] = None
+    weights: str = "auto"
+    blend: str = "uniform"
+    write_probs: Optional[str] = None
+    write_margin: bool = False
+    sieve: Optional[Tuple[int, int, int]] = None
+    threshold: Optional[Tuple[int, float, str]] = None
+    keep_probabilities: bool = False
+    n_workers: int = 0
+    device: str = "cuda:0"
+    codes: Optional[Tuple[int, ...]] = None
+
+    @classmethod
+    def make(cls, *, size=None, scale=None, stride=None, batch_size=None, tta=None, n_workers=0, device="cuda:0",
+             keep_probabilities=False, weights="auto", blend="uniform", write_probs=None, write_margin=False, sieve=None,
+             sieve_connectivity=4, sieve_passes=1, water_threshold=None, threshold_class=None,
+             calibration=None) -> "InferOptions":
+        """The options checked, in the order infer() always checked them: weights, blend, write_probs, the decision
+        rule (threshold_rule), the sieve (postprocess.check_sieve_options), an explicit stride, the grid."""
+        from .postprocess import check_sieve_options
+        check_weights(weights)
+        check_blend(blend)
+        check_write_probs(write_probs)
+        rule = threshold_rule(water_threshold, threshold_class, calibration)
+        if sieve is not None:
+            check_sieve_options(sieve, sieve_connectivity, sieve_passes)
+            sieve = (int(sieve), int(sieve_connectivity), int(sieve_passes))
+        if stride is not None and int(stride) < 1:
+            raise ValueError(f"infer: stride must be >= 1, got {int(stride)}")
+        if size is not None or scale is not None:
+            grid_size((1 << 20, 1 << 20), size, scale)
+        return cls(size=None if size is None else (int(size[0]), int(size[1])), scale=scale,
+                   stride=None if stride is None else int(stride), batch_size=int(batch_size) if batch_size else None,
+                   tta=tta if tta is None or isinstance(tta, str) else tuple(int(c) for c in tta), weights=weights,
+                   blend=blend, write_probs=write_probs, write_margin=bool(write_margin), sieve=sieve,
+                   threshold=None if rule is None else (rule["class"], rule["threshold"], rule["source"]),
+                   keep_probabilities=bool(keep_probabilities), n_workers=int(n_workers), device=str(device))
+
+    @classmethod
+    def from_args(cls, args) -> "InferOptions":
+        """The options an infer command line gave (infer.build_parser); keep_probabilities has no flag."""
+        return cls.make(**{k: getattr(args, k) for k in KEYWORDS if k != "keep_probabilities"})
+
+    def resolve(self, crop_height: int, crop_width: int, batch_size: Optional[int] = None) -> "InferOptions":
+        """The options for a model of crop_height x crop_width crops whose config has batch_size: stride and batch_size
+        filled in where they were left open, codes = tta.view_codes of tta (the d4 set needs square crops)."""
+        from .tta import view_codes
+        ch, cw = int(crop_height), int(crop_width)
+        codes = view_codes(self.tta, ch, cw) if self.tta is not None else None
+        return dataclasses.replace(self, stride=default_stride(ch, cw, self.blend, self.stride),
+                                   batch_size=int(self.batch_size or batch_size), codes=codes)
+
+    def check_classes(self, n_classes: int) -> None:
+        """The threshold's class against the served model's class count."""
+        if self.threshold is not None and self.threshold[0] >= n_classes:
+            raise ValueError(f"infer: threshold class {self.threshold[0]} not in 0..{n_classes - 1}")
+
+    def grid(self, src_hw: Tuple[int, int]) -> Tuple[int, int]:
+        return grid_size(src_hw, self.size, self.scale)
+
+    @property
+    def n_views(self) -> int:
+        return len(self.codes) if self.codes is not None else 1
+
+    @property
+    def rule(self) -> Optional[dict]:
+        """threshold as threshold_rule returns it, the summary's "threshold"."""
+        return None if self.threshold is None else dict(zip(("class", "threshold", "source"), self.threshold))
+
+    @property
+    def sieve_options(self) -> Optional[dict]:
+        """sieve under the names of the summary's "sieve"."""
+        return None if self.sieve is None else dict(zip(("min_pixels", "connectivity", "passes"), self.sieve))

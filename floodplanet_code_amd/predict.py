@@ -46,7 +46,8 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from .tta import VIEW_SETS, view_codes
+from .infer_options import WEIGHT_CHOICES, check_blend, check_weights
+from .tta import VIEW_SETS, recorded, view_codes
 # conf/config.yaml + conf/dataset/floodplanet.yaml + conf/model/ef_model.yaml of the reference: what a key missing from
 # the experiment's config takes
 CONFIG_DEFAULTS = dict(
@@ -89,15 +90,11 @@ def resolve_cfg(experiment_dir: str, checkpoint_path: str) -> dict:
     return _merge(CONFIG_DEFAULTS, dict(cfg))
 
 
-WEIGHT_CHOICES = ("auto", "raw", "ema")
-
-
 def checkpoint_weights(ckpt: dict, which: str = "auto", path: Optional[str] = None):
     """Which weights of a checkpoint to serve -> (state_dict, chosen) with chosen 'raw' or 'ema'.  'raw': the checkpoint's
     state_dict (a bare state dict counts as one); 'ema': its ema_state_dict, an error naming the file when it has none;
     'auto': 'ema' when there is one, else 'raw'.  Host only."""
-    if which not in WEIGHT_CHOICES:
-        raise ValueError(f"weights must be one of {list(WEIGHT_CHOICES)}, got {which!r}")
+    check_weights(which)
     ema = ckpt.get("ema_state_dict") if isinstance(ckpt, dict) else None
     if which == "ema" and ema is None:
         raise KeyError(f"checkpoint {path if path is not None else '<dict>'} has no ema_state_dict (it was trained without "
@@ -117,6 +114,32 @@ def load_checkpoint_model(model, checkpoint_path: str, weights: str, **ctor):
     model = type(model)(**ctor)
     model.load_state_dict(sd)
     return model, chosen
+
+
+def load_eval_model(cfg: dict, checkpoint_path: str, weights: str, n_channels, n_classes: int, device):
+    """The model the config describes, holding the chosen weights of the checkpoint, in eval mode on the device ->
+    (model, chosen).  build_model only names the class: the served model is the one load_checkpoint_model builds, which
+    as load_from_checkpoint gets no ignore_index."""
+    from .models import build_model
+    model_kwargs = {k: v for k, v in (cfg["model"].get("model_kwargs") or {}).items()
+                    if k not in ("ema_decay", "ema_warmup")}
+    model = build_model(cfg["model"]["name"], n_channels, n_classes, cfg["lr"], log_image_iter=cfg["log_image_iter"],
+                        to_rgb_fcn=None, ignore_index=cfg["ignore_index"], **model_kwargs)
+    model, chosen = load_checkpoint_model(model, checkpoint_path, weights, in_channels=n_channels, n_classes=n_classes,
+                                          lr=cfg["lr"], **model_kwargs)
+    model._set_model_to_eval()
+    return model.to(device), chosen
+
+
+def eval_forward(net, sources, codes=None, target=None, ignore_index: int = -100, want_probs: bool = False):
+    """One eval forward of a batch on the device -> (probs | None, counts | None).  codes None: the plain forward, whose
+    logits stay resident in the context (probs is None), plus eval_confusion when there is a target.  With view codes:
+    one forward of all views and one merge_views launch for the averaged probabilities (when wanted) and the counts."""
+    if codes is None:
+        net._forward_raw(sources, False, want_logits=False)
+        return None, (net.eval_confusion(target, ignore_index) if target is not None else None)
+    net.forward_views(sources, codes)
+    return net.merge_views(target, ignore_index, want_probs=want_probs)
 
 
 def prediction_dir(cfg: dict, experiment_dir: str, checkpoint_path: str, eval_dataset_name: str) -> str:
@@ -216,14 +239,11 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
     calibrate_bins bins); the result then also holds "best_threshold" and "best_f1"."""
     from .datasets import FloodplanetTiles, TileLoader, generate_image_slice_object
     from .datasets.synthetic import write_strip_tiff
-    from .models import build_model
-    from .stitch import BLEND_KINDS, GpuImageStitcher
+    from .stitch import GpuImageStitcher
 
     cfg = _merge(CONFIG_DEFAULTS, cfg)
-    if weights not in WEIGHT_CHOICES:
-        raise ValueError(f"weights must be one of {list(WEIGHT_CHOICES)}, got {weights!r}")
-    if blend not in BLEND_KINDS:
-        raise ValueError(f"blend must be one of {list(BLEND_KINDS)}, got {blend!r}")
+    check_weights(weights)
+    check_blend(blend)
     if calibrate is not None:            # checked before any GPU work
         from .calibration import check_bins
         calibrate, calibrate_bins = int(calibrate), check_bins(calibrate_bins)
@@ -245,17 +265,9 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
                                **(ds_cfg.get("dataset_kwargs") or {}))
 
     dev = torch.device(device)
-    model_kwargs = {k: v for k, v in (cfg["model"].get("model_kwargs") or {}).items()
-                    if k not in ("ema_decay", "ema_warmup")}
-    model = build_model(cfg["model"]["name"], dataset.n_channels, dataset.n_classes, cfg["lr"],
-                        log_image_iter=cfg["log_image_iter"], to_rgb_fcn=None, ignore_index=dataset.ignore_index,
-                        **model_kwargs)
-    model, chosen = load_checkpoint_model(model, checkpoint_path, weights, in_channels=dataset.n_channels,
-                                          n_classes=dataset.n_classes, lr=cfg["lr"], **model_kwargs)
     if calibrate is not None and calibrate >= dataset.n_classes:
         raise ValueError(f"calibrate: class {calibrate} not in 0..{dataset.n_classes - 1}")
-    model._set_model_to_eval()
-    model = model.to(dev)
+    model, chosen = load_eval_model(cfg, checkpoint_path, weights, dataset.n_channels, dataset.n_classes, dev)
     net = model.model
     metrics = model.test_metrics
     ignore = model._loss_ignore          # -100 when the model has no ignore_index (as load_from_checkpoint builds it)
@@ -273,14 +285,8 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
     hist = top = None                    # calibrate: int64 device accumulators, read once at the end
     with torch.no_grad():
         for batch in loader:
-            probs = None
-            if codes is None:
-                net._forward_raw(model._gather_sources(batch), False, want_logits=False)
-                counts = net.eval_confusion(batch["target"], ignore)          # [B, k, k], one launch
-            else:                                                             # one T*B forward, one merge launch
-                net.forward_views(model._gather_sources(batch), codes)
-                probs, counts = net.merge_views(batch["target"], ignore,
-                                                want_probs=predict_images or calibrate is not None)
+            probs, counts = eval_forward(net, model._gather_sources(batch), codes, batch["target"], ignore,
+                                         want_probs=predict_images or calibrate is not None)   # counts: [B, k, k]
             if calibrate is not None:                                         # one launch, no host read
                 h, t = net.prob_histogram(batch["target"], ignore, calibrate_bins, probs=probs)
                 hist, top = (h, t) if hist is None else (hist + h, top + t)
@@ -329,7 +335,7 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
         if chosen == "ema" or weights != "auto":      # (a plain checkpoint under 'auto' writes the file it always wrote)
             all_metrics["weights"] = chosen
         if codes is not None:
-            all_metrics["tta"] = tta if isinstance(tta, str) else list(codes)
+            all_metrics["tta"] = recorded(tta, codes)
         if blend != "uniform":
             all_metrics["blend"] = blend
         with open(os.path.join(pred_dir, "metrics.json"), "w") as fh:
@@ -343,7 +349,7 @@ def predict(cfg, experiment_dir, checkpoint_path, eval_dataset_name, predict_ima
             raise ValueError("calibrate: the data set has no crops")
         rep = report(hist.cpu().numpy(), top.cpu().numpy(), calibrate, confusion=metrics.confusion().cpu().numpy())
         if codes is not None:
-            rep["tta"] = tta if isinstance(tta, str) else list(codes)
+            rep["tta"] = recorded(tta, codes)
         with open(os.path.join(pred_dir, "calibration.json"), "w") as fh:
             json.dump(rep, fh)
         extra = {"best_threshold": rep["best_threshold"], "best_f1": rep["best_f1"]}

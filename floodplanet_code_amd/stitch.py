@@ -18,9 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-
-
-BLEND_KINDS = ("uniform", "linear", "hann")
+from .infer_options import BLEND_KINDS
 
 
 def blend_window(kind: str, n: int) -> np.ndarray:
@@ -173,3 +171,27 @@ class GpuImageStitcher:
         current stream, so a run's footprint is bounded by the images in flight rather than by the run."""
         del self.image_canvas[image_name]
         del self.weight_canvas[image_name]
+
+
+class PackedRead:
+    """Several device tensors read by ONE device-to-host copy.  add(name, tensor) registers a contiguous tensor under a
+    name; read() concatenates their bytes in the order they were added (torch.cat of uint8 views: one launch), copies
+    that to the host once and returns {name: numpy array} with each tensor's dtype and shape.  The arrays are views of
+    the one host buffer; one that starts at a byte offset its dtype does not divide is unaligned, which numpy handles."""
+
+    def __init__(self):
+        self._parts = []                    # (name, the tensor's bytes uint8 [nbytes], numpy dtype, shape)
+
+    def add(self, name: str, tensor: torch.Tensor) -> None:
+        if any(name == n for n, *_ in self._parts):
+            raise ValueError(f"PackedRead: {name!r} is registered twice")
+        dtype = torch.empty(0, dtype=tensor.dtype).numpy().dtype
+        self._parts.append((name, tensor.view(-1).view(torch.uint8), dtype, tuple(tensor.shape)))
+
+    def read(self) -> Dict[str, np.ndarray]:
+        packed = torch.cat([b for _, b, _, _ in self._parts]).cpu().numpy()
+        out, at = {}, 0
+        for name, b, dtype, shape in self._parts:
+            out[name] = packed[at:at + b.numel()].view(dtype).reshape(shape)
+            at += b.numel()
+        return out

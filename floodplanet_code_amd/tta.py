@@ -15,9 +15,10 @@ apply_view / invert_view are the torch reference semantics; the device path neve
 """
 from __future__ import annotations
 
-from typing import Sequence, Tuple, Union
+from typing import TYPE_CHECKING, List, Optional, Sequence, Tuple, Union
 
-import torch
+if TYPE_CHECKING:                    # annotations only: the views are tensor methods, and view_codes is host arithmetic
+    import torch
 
 HFLIP, VFLIP, TRANSPOSE = 1, 2, 4
 
@@ -47,6 +48,11 @@ def view_codes(spec: Union[str, Sequence[int]], H: int, W: int) -> Tuple[int, ..
         raise ValueError(f"view codes {[c for c in codes if c & TRANSPOSE]} transpose the tile, which needs a square tile; "
                          f"got {H}x{W} (use 'flips' or 'hflip')")
     return tuple(codes)
+
+
+def recorded(spec: Union[None, str, Sequence[int]], codes: Optional[Sequence[int]]) -> Union[None, str, List[int]]:
+    """What a summary.json / metrics.json / calibration.json holds under "tta": None, the set's name, or the list of codes."""
+    return spec if spec is None or isinstance(spec, str) else list(codes)
 
 
 def apply_view(t: torch.Tensor, code: int) -> torch.Tensor:

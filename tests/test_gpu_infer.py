@@ -258,3 +258,37 @@ def test_resident_scenes_stay_bounded(trained, tmp_path):
     assert out["n_scenes"] == 12 and out["n_crops"] == len(owners)
     assert 1 <= out["max_resident_scenes"] <= bound < 12
     assert len(os.listdir(tmp_path / "out" / "Scenes_pred")) == 12
+
+
+OPTION_SETS = [dict(), dict(tta="flips", blend="hann", write_probs="u8", write_margin=True),
+               dict(write_probs="f32", sieve=4, water_threshold=0.4)]
+
+
+@pytest.mark.parametrize("kw", OPTION_SETS, ids=["defaults", "flips+hann+u8+margin", "f32+sieve+threshold"])
+def test_infer_with_options_equals_infer_with_keywords(trained, tmp_path, kw):
+    """One InferOptions and the loose keywords are the same run: byte-identical rasters, equal summaries (but for the two
+    timings).  A scene smaller than a crop, one of several crops and one of exactly a crop, batches that straddle them."""
+    from floodplanet_code_amd import predict as P
+    from floodplanet_code_amd.infer_options import InferOptions
+    root, exp, ckpt = trained
+    cfg = P.resolve_cfg(exp, ckpt)
+    _write_scenes(str(tmp_path), [(40, 50), (70, 90), (64, 64)], seed=11)
+    kw = dict(kw, stride=32, batch_size=3)
+    runs = {}
+    for form in ("options", "keywords"):
+        out_dir = tmp_path / form
+        how = dict(options=InferOptions.make(**kw)) if form == "options" else kw
+        out = I.infer(ckpt, [str(tmp_path / "Scenes")], str(out_dir), cfg=cfg, **how)
+        files = sorted(os.listdir(out_dir / "Scenes_pred"))
+        text = (out_dir / "summary.json").read_text()
+        assert out == json.loads(text)                                         # what it returns is what it wrote
+        summary = json.loads(text.replace(str(out_dir), "OUT"))
+        del summary["seconds"], summary["crops_per_s"]
+        runs[form] = (files, [open(out_dir / "Scenes_pred" / f, "rb").read() for f in files], summary)
+    files, blobs, summary = runs["options"]
+    assert len(files) == 3 * (1 + ("write_probs" in kw) + ("write_margin" in kw))
+    assert runs["keywords"][0] == files and runs["keywords"][1] == blobs                         # byte-identical rasters
+    assert runs["keywords"][2] == summary
+    assert [s["crops"] for s in summary["scenes"]] == [1, 4, 4] and summary["n_crops"] == 9     # batches straddle scenes
+    assert summary["max_resident_scenes"] == 2 and summary["stride"] == 32
+    assert ("sieve" in summary) == ("sieve" in kw) and ("threshold" in summary) == ("water_threshold" in kw)
