@@ -82,6 +82,19 @@ class FuSceneTrainEntry(C.Structure):
     ]
 
 
+class FuSceneAug(C.Structure):
+    """fu_scene_aug (include/floodunet.h): the radiometric and zoom parts of fu_scene_train_tiles_ex (HOST arrays)."""
+    _fields_ = [
+        ("gain", C.c_void_p),
+        ("bias", C.c_void_p),
+        ("sigma", C.c_void_p),
+        ("noise_stream", C.c_void_p),
+        ("noise_key", C.c_uint64),
+        ("out_h", C.c_void_p),
+        ("out_w", C.c_void_p),
+    ]
+
+
 class FuBandAccum(C.Structure):
     """fu_band_accum (include/floodunet.h): the caller-owned device accumulators of fu_band_stats."""
     _fields_ = [
@@ -206,6 +219,8 @@ SIGNATURES = {
     "fu_scene_crops": (_i, [_p, _i, C.POINTER(FuSceneCrop), _i, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p]),
     "fu_scene_train_tiles": (_i, [_p, _i, C.POINTER(FuSceneTrainEntry), _i, _i, _i, _i, _p, _p, _f, _i64, _i64, _p, _p, _p, _p,
                                   _p]),
+    "fu_scene_train_tiles_ex": (_i, [_p, _i, C.POINTER(FuSceneTrainEntry), _i, _i, _i, _i, _p, _p, _f, _i64, _i64, _p, _p, _p,
+                                     _p, C.POINTER(FuSceneAug), _p]),
     "fu_label_class_counts": (_i, [_p, _i, C.POINTER(FuSceneTrainEntry), _i64, _i, _p, _p]),
     "fu_label_box_counts": (_i, [_p, _i, C.POINTER(FuSceneTrainEntry), _p, _p]),
     "fu_resize_lanczos4_tiles": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p]),

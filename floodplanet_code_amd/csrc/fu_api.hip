@@ -669,6 +669,16 @@ int fu_scene_train_tiles(fu_ctx* c, int n, const fu_scene_train_entry* entries, 
                                   (hipStream_t)stream);
 }
 
+int fu_scene_train_tiles_ex(fu_ctx* c, int n, const fu_scene_train_entry* entries, int C, int tile_h, int tile_w,
+                            int norm_mode, const float* global_mean, const float* global_std, float pad_value,
+                            int64_t nodata_value, int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out,
+                            float* std_out, const fu_scene_aug* aug, fu_stream stream) {
+  FU_REQUIRE(c && entries && image_out, "fu_scene_train_tiles_ex: null context / entries / image_out");
+  return launch_scene_train_tiles_ex(c->train_table, n, entries, C, tile_h, tile_w, norm_mode, global_mean, global_std,
+                                     pad_value, nodata_value, target_fill, image_out, target_out, mean_out, std_out, aug,
+                                     (hipStream_t)stream);
+}
+
 int fu_label_class_counts(fu_ctx* c, int n, const fu_scene_train_entry* entries, int64_t nodata_value, int n_classes,
                           int64_t* counts_out, fu_stream stream) {
   FU_REQUIRE(c && entries && counts_out, "fu_label_class_counts: null context / entries / counts_out");

@@ -207,7 +207,7 @@ struct fu_ctx {
   int* guard = nullptr;           // fp16 mode: non-finite flag / skipped steps / back-off exponent / clean steps (k_guard_book)
   unsigned long long* conf_tmp = nullptr;
   int64_t* n_valid = nullptr;
-  fu::DeviceTable stitch_table, scene_table, train_table;   // fu_stitch_add_batch[_probs, _windowed] / fu_scene_crops / fu_scene_train_tiles
+  fu::DeviceTable stitch_table, scene_table, train_table;   // fu_stitch_add_batch[_probs, _windowed] / fu_scene_crops / fu_scene_train_tiles[_ex]
   fu::OptimState opt;             // everything the optimiser step keeps (fu_optim_api.hip)
   fu::Profiler prof;
   struct Dp* dp = nullptr;            // fu_dp_init: RCCL communicator, communication stream, events

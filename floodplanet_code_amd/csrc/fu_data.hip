@@ -1,7 +1,7 @@
 // Data-preparation kernels (gfx950): what turns rasters that are already in HBM into training and inference batches --
 // tile augmentation, tile assembly and scene crops, Lanczos-4 resampling, training tiles straight from resident scenes,
 // label class counts, streaming band statistics.  None of them runs inside a training step.  The entry points that take a
-// table of host entries (fu_scene_crops, fu_scene_train_tiles, fu_label_class_counts, fu_label_box_counts) are validated
+// table of host entries (fu_scene_crops, fu_scene_train_tiles[_ex], fu_label_class_counts, fu_label_box_counts) are validated
 // here, next to the kernels that trust the table.
 #include "../../include/floodunet.h"
 #include "fu_common.h"
@@ -522,6 +522,285 @@ int launch_scene_train_tiles(DeviceTable& table, int n, const fu_scene_train_ent
   else
     hipLaunchKernelGGL(k_scene_train_tiles<1>, grid, dim3(256), 0, s, jobs_dev, augs_dev, C, H, W, N.mean, N.stdv,
                        N.per_sample, pad_value, nodata_value, target_fill, image_out, target_out);
+  FU_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same pass with radiometric and zoom augmentation (fu_scene_train_tiles_ex; include/floodunet.h states the arithmetic).
+// A sibling of k_scene_train_tiles, which stays as it is: with zoom every pixel has its own source in any case, so this
+// kernel has one loop -- per output pixel the flips and the rotation yield an integer pixel of the un-augmented tile, ZOOM
+// maps it into the box (four taps served from L2, x first, then y; labels nearest-exact), the value is normalised, and
+// PHOTO applies gain, bias and sigma * z.  The same plane / run decomposition, so the stores are the same 16-byte stores.
+// z comes from Philox4x32-10 keyed by the OUTPUT pixel, the channel and the sample's stream: 40 32-bit integer multiplies
+// per value, independent of every load, and no transcendental.  Without ZOOM and PHOTO this kernel is not instantiated.
+// ------------------------------------------------------------------------------------------------
+struct SceneAugEx {        // what box b carries for this kernel besides its SceneCropJob and SceneTrainAug
+  int out_h, out_w;        // ZOOM: the region of the tile the box is resampled onto (else unused)
+  uint32_t stream_lo, stream_hi;
+};
+
+struct ScenePhoto {        // device [n * C] each, null = that term is skipped
+  const float* gain;
+  const float* bias;
+  const float* sigma;
+  uint32_t key_lo, key_hi;
+  float k;                 // (float)(1 / sqrt(32 * (65536^2 - 1) / 12)): 2 * S - 524280 has that variance's inverse
+};
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&o)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+
+// the unit-variance draw of (output pixel, channel, stream): |2 * S - 524280| < 2^24, so the convert is exact
+__device__ __forceinline__ float unit_noise(uint32_t pixel, uint32_t channel, uint32_t stream_lo, uint32_t stream_hi,
+                                            const ScenePhoto& T) {
+  uint32_t o[4];
+  philox4x32_10(pixel, channel, stream_lo, stream_hi, T.key_lo, T.key_hi, o);
+  int S = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) S += (int)(o[i] & 0xffffu) + (int)(o[i] >> 16);
+  return (float)(2 * S - 524280) * T.k;
+}
+
+// one axis of the zoom: pixel i of `out` -> the two taps and the weight of the bilinear image, the index of the label
+__device__ __forceinline__ void zoom_axis(int i, int src, int out, int& i0, int& i1, float& w, int& nearest) {
+#pragma clang fp contract(off)
+  const float scale = (float)src / (float)out;
+  const float c = ((float)i + 0.5f) * scale;
+  const float f = fmaxf(c - 0.5f, 0.f);
+  i0 = min((int)floorf(f), src - 1);
+  i1 = min(i0 + 1, src - 1);
+  w = f - (float)i0;
+  nearest = min((int)floorf(c), src - 1);
+}
+
+__device__ __forceinline__ float lerp_sep(float p, float q, float w) {
+#pragma clang fp contract(off)
+  const float d = q - p;
+  const float e = w * d;
+  return p + e;
+}
+
+template <int PX, bool ZOOM, bool PHOTO>
+__global__ __launch_bounds__(256) void k_scene_train_tiles_aug(const SceneCropJob* __restrict__ jobs,
+                                                               const SceneTrainAug* __restrict__ augs,
+                                                               const SceneAugEx* __restrict__ exs, ScenePhoto T, int C, int H,
+                                                               int W, const float* __restrict__ mean,
+                                                               const float* __restrict__ stdv, int per_sample,
+                                                               float pad_value, int64_t nodata_value, int64_t target_fill,
+                                                               float* __restrict__ img_o, int64_t* __restrict__ tgt_o) {
+#pragma clang fp contract(off)
+  const int planes = C + (tgt_o ? 1 : 0);
+  const int b = blockIdx.x / planes, p = blockIdx.x - b * planes;
+  const SceneCropJob J = jobs[b];
+  const SceneTrainAug A = augs[b];
+  const SceneAugEx X = exs[b];
+  const int QW = W / PX, nq = H * QW;        // PX = 4 only where W % 4 == 0
+  const int q0 = blockIdx.y * (256 * STT_RUNS);
+  const int q1 = min(q0 + 256 * STT_RUNS, nq);
+  const bool is_target = p == C;
+  const bool hf = A.flags & 1, vf = A.flags & 2, rot = A.flags & 4;
+  const int64_t box = (int64_t)J.h0 * J.scene_w + J.w0;
+  const float* __restrict__ src = J.scene + (int64_t)(is_target ? 0 : p) * J.scene_h * J.scene_w + box;
+  const uint8_t* __restrict__ lab = A.label ? A.label + box : nullptr;
+  float* __restrict__ io = img_o + ((int64_t)b * C + (is_target ? 0 : p)) * H * W;
+  int64_t* __restrict__ to = tgt_o ? tgt_o + (int64_t)b * H * W : nullptr;
+  const int vh = ZOOM ? X.out_h : J.dh, vw = ZOOM ? X.out_w : J.dw;      // the valid region of the un-augmented tile
+  const bool norm = mean != nullptr;
+  float m = 0.f, sd = 1.f, gain = 1.f, bias = 0.f, sigma = 0.f;
+  if (!is_target) {
+    if (norm) {
+      const int mi = per_sample ? b * C + p : p;
+      m = mean[mi];
+      sd = stdv[mi];
+    }
+    if (PHOTO) {
+      const int gi = b * C + p;
+      if (T.gain) gain = T.gain[gi];
+      if (T.bias) bias = T.bias[gi];
+      if (T.sigma) sigma = T.sigma[gi];
+    }
+  }
+  float cs = 1.f, sn = 0.f;
+  if (rot) rotation_of(A.angle, cs, sn);
+
+  for (int q = q0 + (int)threadIdx.x; q < q1; q += 256) {
+    const int oy = q / QW, x0 = (q - oy * QW) * PX;
+    float fv[PX];
+    int64_t tv[PX];
+#pragma unroll
+    for (int j = 0; j < PX; ++j) {
+      const int ox = x0 + j;
+      int sx = ox, sy = oy;
+      bool in_tile = true;
+      if (rot) in_tile = rotate_source(ox, oy, cs, sn, H, W, sx, sy);
+      if (vf) sy = H - 1 - sy;                // the rotate input is the v-flipped, h-flipped tile
+      if (hf) sx = W - 1 - sx;
+      const bool in_box = in_tile && sy < vh && sx < vw;
+      if (is_target) {
+        int64_t v = target_fill;
+        if (in_box) {
+          int ly = sy, lx = sx;
+          if (ZOOM) {
+            int a0, a1; float w;
+            zoom_axis(sy, J.dh, X.out_h, a0, a1, w, ly);
+            zoom_axis(sx, J.dw, X.out_w, a0, a1, w, lx);
+          }
+          v = decode_label(lab[(int64_t)ly * J.scene_w + lx], nodata_value);
+        }
+        tv[j] = v;
+      } else {
+        float v = in_tile ? pad_value : 0.f;
+        if (in_box) {
+          if (ZOOM) {
+            int y0, y1, x0s, x1s, nn;
+            float wy, wx;
+            zoom_axis(sy, J.dh, X.out_h, y0, y1, wy, nn);
+            zoom_axis(sx, J.dw, X.out_w, x0s, x1s, wx, nn);
+            const float* __restrict__ r0 = src + (int64_t)y0 * J.scene_w;
+            const float* __restrict__ r1 = src + (int64_t)y1 * J.scene_w;
+            const float top = lerp_sep(r0[x0s], r0[x1s], wx);
+            const float bot = lerp_sep(r1[x0s], r1[x1s], wx);
+            v = lerp_sep(top, bot, wy);
+          } else {
+            v = src[(int64_t)sy * J.scene_w + sx];
+          }
+          v = normalise(v, norm, m, sd);
+          if (PHOTO) {
+            if (T.gain) v = v * gain;
+            if (T.bias) v = v + bias;
+            if (T.sigma) {
+              const float z = unit_noise((uint32_t)(oy * W + ox), (uint32_t)p, X.stream_lo, X.stream_hi, T);
+              const float e = sigma * z;
+              v = v + e;
+            }
+          }
+        }
+        fv[j] = v;
+      }
+    }
+    if (is_target) store_px<PX>(to + (int64_t)oy * W + x0, tv);
+    else store_px<PX>(io + (int64_t)oy * W + x0, fv);
+  }
+}
+
+// every check before anything is launched or copied: a rejected call leaves the stream untouched
+int launch_scene_train_tiles_ex(DeviceTable& table, int n, const fu_scene_train_entry* entries, int C, int H, int W,
+                                int norm_mode, const float* gmean, const float* gstd, float pad_value, int64_t nodata_value,
+                                int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out, float* std_out,
+                                const fu_scene_aug* aug, hipStream_t s) {
+  const char* fn = "fu_scene_train_tiles_ex";
+  const bool photo = aug && (aug->gain || aug->bias || aug->sigma);
+  const bool zoom = aug && (aug->out_h || aug->out_w);
+  if (!photo && !zoom)                        // nothing switched on: the plain call, its kernel and its bits
+    return launch_scene_train_tiles(table, n, entries, C, H, W, norm_mode, gmean, gstd, pad_value, nodata_value,
+                                    target_fill, image_out, target_out, mean_out, std_out, s);
+  FU_REQUIRE(n >= 1 && C >= 1 && H >= 1 && W >= 1, "%s: n = %d, C = %d, tile %dx%d (all must be >= 1)", fn, n, C, H, W);
+  FU_TRY(check_norm_mode(fn, "[n, C]", norm_mode, gmean, gstd, mean_out, std_out));
+  FU_REQUIRE((int64_t)n * (C + 1) <= INT32_MAX && (int64_t)n * C * H * W <= ((int64_t)1 << 40) &&
+             (int64_t)H * W <= ((int64_t)1 << 25),
+             "%s: %d boxes of %d channels, tile %dx%d, are too many for one call", fn, n, C, H, W);
+  FU_REQUIRE(!zoom || (aug->out_h && aug->out_w), "%s: out_h and out_w go together", fn);
+  FU_REQUIRE(!(aug->sigma) || aug->noise_stream, "%s: sigma needs noise_stream", fn);
+  const size_t nc = (size_t)n * (size_t)C;
+  for (size_t i = 0; i < nc; ++i) {
+    FU_REQUIRE(!aug->gain || std::isfinite(aug->gain[i]), "%s: gain[%zu] is not finite", fn, i);
+    FU_REQUIRE(!aug->bias || std::isfinite(aug->bias[i]), "%s: bias[%zu] is not finite", fn, i);
+    FU_REQUIRE(!aug->sigma || (std::isfinite(aug->sigma[i]) && aug->sigma[i] >= 0.f),
+               "%s: sigma[%zu] = %g must be finite and >= 0", fn, i, aug->sigma ? (double)aug->sigma[i] : 0.0);
+  }
+  // one table: the boxes, the transforms, the per-sample extras, then the per-(sample, channel) terms that are given
+  const size_t crop_bytes = (size_t)n * sizeof(SceneCropJob), aug_bytes = (size_t)n * sizeof(SceneTrainAug);
+  const size_t ex_bytes = (size_t)n * sizeof(SceneAugEx), term_bytes = nc * sizeof(float);
+  const int n_terms = (aug->gain ? 1 : 0) + (aug->bias ? 1 : 0) + (aug->sigma ? 1 : 0);
+  std::vector<unsigned char> host(crop_bytes + aug_bytes + ex_bytes + (size_t)n_terms * term_bytes);
+  SceneCropJob* jobs = reinterpret_cast<SceneCropJob*>(host.data());
+  SceneTrainAug* augs = reinterpret_cast<SceneTrainAug*>(host.data() + crop_bytes);
+  SceneAugEx* exs = reinterpret_cast<SceneAugEx*>(host.data() + crop_bytes + aug_bytes);
+  for (int i = 0; i < n; ++i) {
+    const fu_scene_train_entry& E = entries[i];
+    if (zoom) {                               // a check of its own: the box may exceed the tile, the out size may not
+      const int dh = E.hE - E.h0, dw = E.wE - E.w0;
+      FU_REQUIRE(E.scene, "%s: entry %d: null scene", fn, i);
+      FU_REQUIRE(E.scene_h >= 1 && E.scene_w >= 1, "%s: entry %d: bad scene size %dx%d", fn, i, E.scene_h, E.scene_w);
+      FU_REQUIRE(E.h0 >= 0 && E.w0 >= 0 && E.hE <= E.scene_h && E.wE <= E.scene_w,
+                 "%s: entry %d: box [%d:%d, %d:%d] lies outside its scene %dx%d", fn, i, E.h0, E.hE, E.w0, E.wE, E.scene_h,
+                 E.scene_w);
+      FU_REQUIRE(dh >= 1 && dw >= 1, "%s: entry %d: box [%d:%d, %d:%d] is empty", fn, i, E.h0, E.hE, E.w0, E.wE);
+      FU_REQUIRE((int64_t)dh * dw <= INT32_MAX, "%s: entry %d: box %dx%d is too large", fn, i, dh, dw);
+      FU_REQUIRE(aug->out_h[i] >= 1 && aug->out_h[i] <= H && aug->out_w[i] >= 1 && aug->out_w[i] <= W,
+                 "%s: entry %d: out size %dx%d must lie within 1x1 and the tile %dx%d", fn, i, aug->out_h[i], aug->out_w[i],
+                 H, W);
+      jobs[i] = SceneCropJob{E.scene, E.scene_h, E.scene_w, E.h0, E.w0, dh, dw};
+    } else {
+      FU_TRY(check_scene_box(fn, i, E, H, W, jobs[i]));
+    }
+    FU_REQUIRE(!target_out || E.label, "%s: entry %d: target_out given but the entry has no label", fn, i);
+    FU_REQUIRE((E.flags & ~(FU_AUG_HFLIP | FU_AUG_VFLIP | FU_AUG_ROTATE)) == 0, "%s: entry %d: unknown flag bits 0x%x", fn, i,
+               (unsigned)E.flags);
+    FU_REQUIRE(std::isfinite(E.angle_deg), "%s: entry %d: the angle is not finite", fn, i);
+    augs[i] = SceneTrainAug{E.label, E.flags, E.angle_deg};
+    const uint64_t st = aug->noise_stream ? aug->noise_stream[i] : 0;
+    exs[i] = SceneAugEx{zoom ? aug->out_h[i] : 0, zoom ? aug->out_w[i] : 0, (uint32_t)st, (uint32_t)(st >> 32)};
+  }
+  size_t term_off[3] = {0, 0, 0};
+  {
+    size_t off = crop_bytes + aug_bytes + ex_bytes;
+    const float* terms[3] = {aug->gain, aug->bias, aug->sigma};
+    for (int k = 0; k < 3; ++k) {
+      if (!terms[k]) continue;
+      std::copy(terms[k], terms[k] + nc, reinterpret_cast<float*>(host.data() + off));
+      term_off[k] = off;
+      off += term_bytes;
+    }
+  }
+  FU_TRY(table.upload(host.data(), host.size(),
+                      sizeof(SceneCropJob) + sizeof(SceneTrainAug) + sizeof(SceneAugEx) + 3 * (size_t)C * sizeof(float), s));
+  const unsigned char* dev = static_cast<const unsigned char*>(table.dev);
+  const SceneCropJob* jobs_dev = reinterpret_cast<const SceneCropJob*>(dev);
+  const SceneTrainAug* augs_dev = reinterpret_cast<const SceneTrainAug*>(dev + crop_bytes);
+  const SceneAugEx* exs_dev = reinterpret_cast<const SceneAugEx*>(dev + crop_bytes + aug_bytes);
+  ScenePhoto T;
+  T.gain = aug->gain ? reinterpret_cast<const float*>(dev + term_off[0]) : nullptr;
+  T.bias = aug->bias ? reinterpret_cast<const float*>(dev + term_off[1]) : nullptr;
+  T.sigma = aug->sigma ? reinterpret_cast<const float*>(dev + term_off[2]) : nullptr;
+  T.key_lo = (uint32_t)aug->noise_key;
+  T.key_hi = (uint32_t)(aug->noise_key >> 32);
+  T.k = (float)(1.0 / sqrt(32.0 * (65536.0 * 65536.0 - 1.0) / 12.0));
+  ScenePlanes P;
+  P.jobs = jobs_dev;
+  NormParams N;                               // 'local': the statistics of the source box's own pixels
+  FU_TRY(resolve_norm(P, n, C, norm_mode, gmean, gstd, mean_out, std_out, s, N));
+  const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(image_out) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(target_out) & 15) == 0;
+  const int64_t nq = (int64_t)H * (vec ? W / 4 : W);
+  const dim3 grid((unsigned)(n * (C + (target_out ? 1 : 0))), (unsigned)ceil_div64(nq, (int64_t)256 * STT_RUNS));
+#define FU_STT_AUG(PX, Z, PH)                                                                                           \
+  hipLaunchKernelGGL((k_scene_train_tiles_aug<PX, Z, PH>), grid, dim3(256), 0, s, jobs_dev, augs_dev, exs_dev, T, C, H, W, \
+                     N.mean, N.stdv, N.per_sample, pad_value, nodata_value, target_fill, image_out, target_out)
+  if (vec) {
+    if (zoom && photo) FU_STT_AUG(4, true, true);
+    else if (zoom) FU_STT_AUG(4, true, false);
+    else FU_STT_AUG(4, false, true);
+  } else {
+    if (zoom && photo) FU_STT_AUG(1, true, true);
+    else if (zoom) FU_STT_AUG(1, true, false);
+    else FU_STT_AUG(1, false, true);
+  }
+#undef FU_STT_AUG
   FU_LAUNCH_CHECK();
   return 0;
 }

@@ -106,16 +106,54 @@ def scene_crops(ctx, boxes, tile_hw: Tuple[int, int], norm_mode: Optional[str] =
     return out[:n], mean.view(n, Cc, 1, 1), std.view(n, Cc, 1, 1)
 
 
+def _scene_aug(n: int, Cc: int, photometric: Optional[dict], zoom):
+    """-> (fu_scene_aug, the numpy arrays it points into) from scene_train_tiles' photometric / zoom arguments; shapes are
+    checked here, values by the library."""
+    import numpy as np
+    aug, keep = _lib.FuSceneAug(), []
+
+    def host(v, dtype, size, name):
+        if v is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(v).reshape(-1), dtype=dtype)
+        if a.size != size:
+            raise ValueError(f"scene_train_tiles: {name} has {a.size} values, expected {size}")
+        keep.append(a)
+        return a.ctypes.data
+
+    ph = dict(photometric or {})
+    unknown = sorted(set(ph) - {"gain", "bias", "sigma", "noise_key", "noise_stream"})
+    if unknown:
+        raise ValueError(f"scene_train_tiles: unknown photometric keys {unknown}")
+    aug.gain = host(ph.get("gain"), np.float32, n * Cc, "photometric gain")
+    aug.bias = host(ph.get("bias"), np.float32, n * Cc, "photometric bias")
+    aug.sigma = host(ph.get("sigma"), np.float32, n * Cc, "photometric sigma")
+    aug.noise_stream = host(ph.get("noise_stream"), np.uint64, n, "photometric noise_stream")
+    aug.noise_key = int(ph.get("noise_key") or 0) & (2 ** 64 - 1)
+    if zoom is not None:
+        out_h, out_w = zoom
+        aug.out_h = host(out_h, np.int32, n, "zoom out_h")
+        aug.out_w = host(out_w, np.int32, n, "zoom out_w")
+    return aug, keep
+
+
 def scene_train_tiles(ctx, entries, tile_hw: Tuple[int, int], norm_mode: Optional[str] = None,
                       global_params: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pad_value: float = 0.0,
-                      nodata_value: int = 0, target_fill: int = 0, out=None):
+                      nodata_value: int = 0, target_fill: int = 0, out=None, photometric: Optional[dict] = None,
+                      zoom=None):
     """C ABI fu_scene_train_tiles: entries = [(scene, label, (h0, w0, hE, wE), flags, angle_deg), ...] -- scene a contiguous
     fp32 [C, H_s, W_s] on the ROCm device, label the scene's raw uint8 [H_s, W_s] label raster there (None for every entry:
     no target), the box inside the scene and at most tile_hw, flags / angle as augment.sample_transforms draws them.
     -> (image [n, C, th, tw], target int64 [n, th, tw] or None, mean, std [n, C, 1, 1]): bit for bit scene_crops followed
     by augment.apply on the decoded label boxes, in one launch (two with 'local') and without the batch in between.
     global_params: fp32 tensors; pass them on the device to keep the call free of host-to-device copies.
-    out: optional (image, target, mean, std) buffers of those shapes (mean / std [n, C]) to write into."""
+    out: optional (image, target, mean, std) buffers of those shapes (mean / std [n, C]) to write into.
+
+    photometric / zoom (both None: the call above, unchanged) go to fu_scene_train_tiles_ex.  photometric: a dict with any of
+    gain, bias, sigma (float [n, C], None = that term is skipped) and, for sigma, noise_key (int) and noise_stream (uint64
+    [n]); augment.photometric_host states what they do.  zoom: (out_h, out_w), int [n] each -- entry b's box, of any size
+    inside its scene, is resampled onto the top-left out_h[b] x out_w[b] region of the tile (sampling.zoom_tile_host);
+    under 'local' mean / std are then the source box's."""
     mode = _norm_mode(norm_mode)
     n = len(entries)
     if n == 0:
@@ -145,10 +183,16 @@ def scene_train_tiles(ctx, entries, tile_hw: Tuple[int, int], norm_mode: Optiona
         mean = torch.zeros(n, Cc, dtype=torch.float32, device=dev)
         std = torch.ones(n, Cc, dtype=torch.float32, device=dev)
     gm, gs = _global_norm(mode, global_params, dev, mean, std)
-    check(_lib.load().fu_scene_train_tiles(ctx, n, table, Cc, th, tw, mode, ptr(gm), ptr(gs), float(pad_value),
-                                           int(nodata_value), int(target_fill), ptr(image),
-                                           ptr(target) if with_target else None, ptr(mean) if mode == 1 else None,
-                                           ptr(std) if mode == 1 else None, torch.cuda.current_stream(dev).cuda_stream))
+    args = (ctx, n, table, Cc, th, tw, mode, ptr(gm), ptr(gs), float(pad_value), int(nodata_value), int(target_fill),
+            ptr(image), ptr(target) if with_target else None, ptr(mean) if mode == 1 else None,
+            ptr(std) if mode == 1 else None)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if photometric is None and zoom is None:
+        check(_lib.load().fu_scene_train_tiles(*args, stream))
+    else:
+        aug, keep = _scene_aug(n, Cc, photometric, zoom)       # keep: the host arrays the struct points into
+        check(_lib.load().fu_scene_train_tiles_ex(*args, C.byref(aug), stream))
+        del keep
     return image, (target if with_target else None), mean.view(n, Cc, 1, 1), std.view(n, Cc, 1, 1)
 
 

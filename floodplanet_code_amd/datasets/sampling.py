@@ -25,10 +25,14 @@ import torch
 from .class_weights import Box, _check_host_entries, _device_table
 from .scene_loader import epoch_order
 
-__all__ = ["POLICIES", "label_box_counts", "label_box_counts_host", "tile_stats", "plan_order", "jitter_boxes"]
+__all__ = ["POLICIES", "label_box_counts", "label_box_counts_host", "tile_stats", "plan_order", "jitter_boxes", "zoom_boxes",
+           "zoom_tile_host", "zoom_axis_host", "check_zoom_range"]
 
 POLICIES = ("all", "labelled", "balanced")
 JITTER_STREAM = 0x6A177E2        # third word of the jitter stream's seed: a stream of its own, not the transforms'
+ZOOM_STREAM = 0x200A5CA1         # ... and of the zoom stream's
+PHOTOMETRIC_STREAM = 0x9A0705    # ... and of the radiometric draws'
+ZOOM_LIMITS = (0.5, 2.0)         # bilinear resampling without a pre-filter aliases beyond this range
 BALANCED_STREAM = 0xBA1A2CED     # mixed into the seed of the "balanced" draws
 
 
@@ -186,3 +190,79 @@ def jitter_boxes(boxes: Sequence[Box], raster_hw: Sequence[Tuple[int, int]], J: 
         w0 = min(max(w0 + int(ox), 0), int(W) - dw)
         out.append((h0, w0, h0 + dh, w0 + dw))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------- zoom
+def check_zoom_range(zoom_range) -> Tuple[float, float]:
+    """(zmin, zmax) with 0 < zmin <= zmax, both inside ZOOM_LIMITS."""
+    try:
+        zmin, zmax = (float(v) for v in zoom_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"zoom takes (zmin, zmax), got {zoom_range!r}") from None
+    if not 0.0 < zmin <= zmax:
+        raise ValueError(f"zoom needs 0 < zmin <= zmax, got ({zmin}, {zmax})")
+    if zmin < ZOOM_LIMITS[0] or zmax > ZOOM_LIMITS[1]:
+        raise ValueError(f"zoom ({zmin}, {zmax}) must stay within [{ZOOM_LIMITS[0]}, {ZOOM_LIMITS[1]}]: bilinear resampling "
+                         f"without a pre-filter aliases beyond it")
+    return zmin, zmax
+
+
+def zoom_boxes(boxes: Sequence[Box], raster_shapes: Sequence[Tuple[int, int]], zoom_range, seed: int,
+               epoch: int) -> Tuple[List[Box], List[Tuple[int, int]]]:
+    """-> (source boxes, output sizes).  Every box gets its own factor z, log-uniform in [zmin, zmax] (z > 1 magnifies),
+    drawn for all examples in data-set order from RandomState([seed, epoch, ZOOM_STREAM]).  Per axis the source size is
+    clamp(round(d / z), 1, raster size); the source box keeps the box's centre (to the half pixel below) and is shifted to
+    lie inside its raster.  The output size stays the box's own (dh, dw), so an edge tile keeps its valid region."""
+    zmin, zmax = check_zoom_range(zoom_range)
+    boxes = [tuple(int(v) for v in b) for b in boxes]
+    if len(raster_shapes) != len(boxes):
+        raise ValueError(f"zoom_boxes: {len(boxes)} boxes, {len(raster_shapes)} raster sizes")
+    rs = np.random.RandomState([int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, ZOOM_STREAM])
+    z = np.exp(rs.uniform(np.log(zmin), np.log(zmax), size=len(boxes)))
+    src, out = [], []
+    for (h0, w0, hE, wE), (H, W), zi in zip(boxes, raster_shapes, z):
+        dh, dw = hE - h0, wE - w0
+        sh = min(max(int(round(dh / zi)), 1), int(H))
+        sw = min(max(int(round(dw / zi)), 1), int(W))
+        a = min(max((h0 + hE - sh) // 2, 0), int(H) - sh)
+        b = min(max((w0 + wE - sw) // 2, 0), int(W) - sw)
+        src.append((a, b, a + sh, b + sw))
+        out.append((dh, dw))
+    return src, out
+
+
+def zoom_axis_host(src: int, out: int):
+    """One axis of the zoom of fu_scene_train_tiles_ex, for the pixels 0 .. out - 1 at once, in float32 with every operation
+    rounded on its own: scale = src / out; c = (i + 0.5) * scale; f = max(c - 0.5, 0); i0 = min(floor(f), src - 1);
+    i1 = min(i0 + 1, src - 1); w = f - i0; nearest = min(floor(c), src - 1).  -> (i0, i1, w float32, nearest)."""
+    scale = np.float32(src) / np.float32(out)
+    c = (np.arange(out, dtype=np.float32) + np.float32(0.5)) * scale
+    f = np.maximum(c - np.float32(0.5), np.float32(0.0))
+    i0 = np.minimum(np.floor(f).astype(np.int64), src - 1)
+    i1 = np.minimum(i0 + 1, src - 1)
+    w = f - i0.astype(np.float32)
+    nearest = np.minimum(np.floor(c).astype(np.int64), src - 1)
+    return i0, i1, w.astype(np.float32), nearest
+
+
+def zoom_tile_host(image: Optional[np.ndarray], label: Optional[np.ndarray], out_hw: Tuple[int, int]):
+    """The numpy statement of the zoom: image float32 [C, sh, sw] and / or raw label [sh, sw] -> (image [C, oh, ow], label
+    [oh, ow]) (None where not given).  Half-pixel centres; the image is interpolated along x first, then along y, with
+    lerp(p, q, w) = p + w * (q - p) in float32; the label takes the byte at `nearest` per axis (torch's 'nearest-exact').
+    src == out returns the input's values.  This, not torch, is the definition the device is compared against."""
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    sh, sw = (image.shape[1:] if image is not None else label.shape)
+    y0, y1, wy, ny = zoom_axis_host(int(sh), oh)
+    x0, x1, wx, nx = zoom_axis_host(int(sw), ow)
+    img = lab = None
+    if image is not None:
+        a = np.asarray(image, dtype=np.float32)
+        rows = []
+        for yy in (y0, y1):
+            p, q = a[:, yy][:, :, x0], a[:, yy][:, :, x1]
+            rows.append(p + wx[None, None, :] * (q - p))
+        img = rows[0] + wy[None, :, None] * (rows[1] - rows[0])
+        assert img.dtype == np.float32
+    if label is not None:
+        lab = np.asarray(label)[ny][:, nx]
+    return img, lab

@@ -11,7 +11,9 @@ decodes the labels and applies hflip / vflip / rotate in a single pass.  No tens
 What stays on the host: the epoch's order (plan_epoch), the draw of the transforms (augment.sample_transforms, the numpy
 stream TileLoader uses) and the table itself.  Optionally the loader chooses which tiles an epoch sees and where they are
 cut (tile_sampling, crop_jitter; datasets/sampling.py): the label content of every box comes from one
-fu_label_box_counts launch over the resident label rasters, the plan is host arithmetic.  What it does not do: stream scenes in and out of HBM -- a data set that
+fu_label_box_counts launch over the resident label rasters, the plan is host arithmetic.  Optionally the same launch varies the
+input as well (photometric, zoom: fu_scene_train_tiles_ex -- per-band gain, bias and noise, a per-sample resampling of a
+smaller or larger source box); the host only draws the parameters.  What it does not do: stream scenes in and out of HBM -- a data set that
 exceeds the residency budget raises SceneResidencyError; TileLoader is the streaming loader."""
 from __future__ import annotations
 
@@ -124,7 +126,7 @@ class SceneTileLoader:
                  transforms: Optional[dict] = None, ignore_index: int = 0, max_resident_bytes: Optional[int] = None,
                  shard: Optional[Sequence[int]] = None, num_workers: int = 0, tile_sampling: str = "all",
                  min_trainable_frac: float = 0.0, water_share: float = 0.5, min_water_frac: float = 0.0,
-                 crop_jitter: int = 0):
+                 crop_jitter: int = 0, photometric: Optional[dict] = None, zoom: Optional[Sequence[float]] = None):
         """dataset: FloodplanetTiles.  net: the HipUNet whose context owns the table's device buffer.  transforms: None, or
         the reference's `transforms` config dict ({} = its defaults), drawn from RandomState(seed) as TileLoader draws them.
         ignore_index: the fill of the target where the augmentation leaves the tile; the data set pads edge crops with its
@@ -140,8 +142,20 @@ class SceneTileLoader:
         counted at the start of the epoch (one fu_label_box_counts launch, one read of [n, 3] counts); without jitter the
         boxes never change, so it is counted once.  With the defaults nothing of this runs.  While an option is active,
         batches carry "boxes", the (h0, w0, hE, wE) actually cut (metadata keeps the grid's crop_params), and
-        `last_plan` holds what the latest epoch planned."""
-        from .sampling import POLICIES, _check_frac
+        `last_plan` holds what the latest epoch planned.
+
+        photometric: None, or augment.sample_photometric's config dict (gain, band_gain, brightness, noise, band_drop,
+        likelihood; units of the normalised batch) -- gain, bias and noise applied by the batch's own launch
+        (fu_scene_train_tiles_ex) to the pixels that come from the scene.  zoom = (zmin, zmax): every epoch every box is
+        replaced by a source box 1 / z its size around the same centre, z log-uniform in the range, resampled to the box's
+        own size in the same launch (sampling.zoom_boxes; bilinear image, nearest-exact labels).  Both draw for all examples
+        in data-set order from RandomStates of their own, seeded with (seed, epoch, purpose): the stream of the transforms
+        is consumed as before, and with both off every batch is what it was.  The noise of an example is keyed by
+        noise_stream = epoch * len(dataset) + its index and a noise_key derived from `seed`.  Batches then carry
+        "photometric" (the gain / bias / sigma rows, noise_key, noise_stream) and, with zoom, "src_boxes" (the boxes read)
+        beside "boxes" (the boxes they stand for).  The tile-sampling census keeps counting the grid's (jittered) boxes,
+        not the zoomed ones; under 'local' mean / std are those of the zoomed source box."""
+        from .sampling import POLICIES, _check_frac, check_zoom_range
         self.dataset, self.batch_size, self.device = dataset, int(batch_size), torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("SceneTileLoader keeps the scenes on a ROCm GPU and cuts the batches there; there is no CPU "
@@ -166,6 +180,13 @@ class SceneTileLoader:
         self.crop_jitter = int(crop_jitter)
         if self.crop_jitter < 0:
             raise ValueError(f"crop_jitter must be >= 0, got {crop_jitter}")
+        self.zoom = None if zoom is None else check_zoom_range(zoom)
+        self.photometric = None if photometric is None else dict(photometric)
+        if self.photometric is not None:                     # argument errors now
+            from ..augment import sample_photometric
+            sample_photometric(1, 1, self.photometric, np.random.RandomState(0))
+        self.noise_key = (self.seed * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03) & (2 ** 64 - 1)
+        self._drawn = None               # (epoch, photometric draws, zoomed boxes) of the latest epoch
         self.last_plan = None            # what the latest planned epoch holds (sampling.plan_order's info)
         self._census = None              # (trainable, water) of the grid's boxes: cached, they never change
         self._planned = None             # (epoch, batches, boxes) of the latest plan
@@ -189,7 +210,7 @@ class SceneTileLoader:
 
     @property
     def _sampling_active(self) -> bool:
-        return self.tile_sampling != "all" or self.crop_jitter > 0
+        return self.tile_sampling != "all" or self.crop_jitter > 0 or self.zoom is not None
 
     def __len__(self):
         """Batches per epoch; under a policy other than "all" the planned number for the next epoch (this takes the
@@ -266,10 +287,28 @@ class SceneTileLoader:
         ctx = self.net._get_ctx(self.device, self.batch_size, th, tw)
         return label_class_counts(ctx, [(label, box) for _, label, box in self._items], self.ignore_index, n_classes)
 
-    def _batch(self, index: List[int], boxes: Optional[List[Tuple[int, int, int, int]]] = None) -> dict:
+    def _draws(self, epoch: int, boxes):
+        """(photometric draws, (zoomed source boxes, output sizes)) of an epoch, for every example in data-set order, each
+        from a RandomState of its own; None for an option that is off.  boxes: the epoch's boxes (zoom needs them)."""
+        from .. import augment
+        from . import sampling
+        if self._drawn is not None and self._drawn[0] == epoch:
+            return self._drawn[1:]
+        photo = zoomed = None
+        if self.photometric is not None:
+            rs = np.random.RandomState([self.seed & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, sampling.PHOTOMETRIC_STREAM])
+            photo = augment.sample_photometric(len(self.dataset), self.dataset.n_channels["ms_image"], self.photometric, rs)
+        if self.zoom is not None:
+            zoomed = sampling.zoom_boxes(boxes, [tuple(label.shape) for _, label, _ in self._items], self.zoom, self.seed,
+                                         epoch)
+        self._drawn = (epoch, photo, zoomed)
+        return photo, zoomed
+
+    def _batch(self, index: List[int], boxes: Optional[List[Tuple[int, int, int, int]]] = None, epoch: int = 0) -> dict:
         from .. import augment
         from .assemble import scene_train_tiles
         n = len(index)
+        photo, zoomed = self._draws(epoch, boxes) if (self.photometric is not None or self.zoom is not None) else (None, None)
         if self.transforms is not None:
             flags, angles = augment.sample_transforms(n, self.transforms, self._rng)
         else:
@@ -278,15 +317,28 @@ class SceneTileLoader:
         ctx = self.net._get_ctx(self.device, self.batch_size, th, tw)
         if boxes is None:
             entries = [self._items[i] + (int(flags[k]), float(angles[k])) for k, i in enumerate(index)]
-        else:                            # the epoch's boxes in place of the grid's
-            entries = [self._items[i][:2] + (boxes[i], int(flags[k]), float(angles[k])) for k, i in enumerate(index)]
+        else:                            # the epoch's boxes (zoomed: the source boxes) in place of the grid's
+            cut = boxes if zoomed is None else zoomed[0]
+            entries = [self._items[i][:2] + (cut[i], int(flags[k]), float(angles[k])) for k, i in enumerate(index)]
+        extra = {}
+        if photo is not None:
+            rows = np.asarray(index, dtype=np.int64)
+            extra["photometric"] = {k: (None if v is None else np.ascontiguousarray(v[rows])) for k, v in photo.items()}
+            extra["photometric"]["noise_key"] = self.noise_key
+            extra["photometric"]["noise_stream"] = (int(epoch) * len(self.dataset) + rows).astype(np.uint64)
+        if zoomed is not None:
+            extra["zoom"] = ([zoomed[1][i][0] for i in index], [zoomed[1][i][1] for i in index])
         image, target, mean, std = scene_train_tiles(ctx, entries, (th, tw), self.dataset.norm_mode, self._global,
                                                      nodata_value=self.ignore_index,
-                                                     target_fill=self.ignore_index)
+                                                     target_fill=self.ignore_index, **extra)
         out = {"image": image, "target": target, "mean": mean, "std": std, "index": list(index), "flags": flags,
                "angles": angles}
         if boxes is not None:
             out["boxes"] = [boxes[i] for i in index]
+        if photo is not None:
+            out["photometric"] = extra["photometric"]
+        if zoomed is not None:
+            out["src_boxes"] = [zoomed[0][i] for i in index]
         if self.dataset.output_metadata:
             out["metadata"] = [{"image_path": ex["image_path"], "crop_params": ex["crop_params"],
                                 "region_name": ex["region_name"]} for ex in (self.dataset.dataset[i] for i in index)]
@@ -299,8 +351,8 @@ class SceneTileLoader:
         if self._sampling_active:
             batches, boxes = self._plan(epoch)
             for index in batches:
-                yield self._batch(index, boxes)
+                yield self._batch(index, boxes, epoch)
             return
         for index in plan_epoch(len(self.dataset), self.batch_size, epoch, self.shuffle, self.seed, self.drop_last,
                                 self.shard):
-            yield self._batch(index)
+            yield self._batch(index, None, epoch)

@@ -266,6 +266,22 @@ def build_parser() -> argparse.ArgumentParser:
                          "one pixel)")
     ap.add_argument("--crop_jitter", type=int, default=None, metavar="J",
                     help="--loader scene, train split: move every crop by its own offset in [-J, J]^2 each epoch (default 0)")
+    ap.add_argument("--aug_gain", type=float, default=None, metavar="G",
+                    help="--loader scene, train split: one gain per sample, uniform in [1 - G, 1 + G], in units of the "
+                         "normalised batch (like every --aug_* option; default: none of them)")
+    ap.add_argument("--aug_band_gain", type=float, default=None, metavar="G",
+                    help="one more gain per band, uniform in [1 - G, 1 + G]")
+    ap.add_argument("--aug_brightness", type=float, default=None, metavar="B",
+                    help="one bias per sample, uniform in [-B, B]")
+    ap.add_argument("--aug_noise", type=float, default=None, metavar="S",
+                    help="additive unit-variance noise times a per-sample sigma, uniform in [0, S]")
+    ap.add_argument("--aug_band_drop", type=float, default=None, metavar="P",
+                    help="zero each band with probability P in [0, 1), never every band of a sample")
+    ap.add_argument("--aug_likelihood", type=float, default=None, metavar="L",
+                    help="one coin per sample for the gain / brightness / noise / band-drop group (default 1)")
+    ap.add_argument("--aug_zoom", type=float, nargs=2, default=None, metavar=("ZMIN", "ZMAX"),
+                    help="--loader scene, train split: resample every crop by its own factor, log-uniform in [ZMIN, ZMAX] "
+                         "within [0.5, 2] (bilinear image, nearest labels; above 1 magnifies)")
     ap.add_argument("--no_transforms", action="store_true", help="train without hflip / vflip / rotate")
     ap.add_argument("--no_shuffle", action="store_true", help="train in data-set order")
     ap.add_argument("--device", type=str, default="cuda:0")
@@ -303,6 +319,39 @@ def sampling_from_args(args) -> dict:
     if given.get("crop_jitter", 0) < 0:
         raise ValueError(f"--crop_jitter must be >= 0, got {given['crop_jitter']}")
     return given
+
+
+# --aug_* flag -> the key of augment.sample_photometric's config
+PHOTOMETRIC_FLAGS = {"aug_gain": "gain", "aug_band_gain": "band_gain", "aug_brightness": "brightness", "aug_noise": "noise",
+                     "aug_band_drop": "band_drop", "aug_likelihood": "likelihood"}
+
+
+def augmentation_from_args(args) -> dict:
+    """The radiometric and zoom options a command line gave ({} for none), checked, as SceneTileLoader's keyword arguments
+    `photometric` (augment.sample_photometric's config) and `zoom` (zmin, zmax).  They belong to --loader scene;
+    --aug_likelihood alone varies nothing and is an error."""
+    import numpy as np
+    from .augment import sample_photometric
+    from .datasets.sampling import check_zoom_range
+    photo = {key: getattr(args, flag, None) for flag, key in PHOTOMETRIC_FLAGS.items()}
+    photo = {k: float(v) for k, v in photo.items() if v is not None}
+    zoom = getattr(args, "aug_zoom", None)
+    given = ["aug_" + k for k in photo] + (["aug_zoom"] if zoom is not None else [])
+    if given and getattr(args, "loader", "scene") != "scene":
+        raise ValueError("--" + ", --".join(given) + " need --loader scene: the fused scene-tile kernel applies them")
+    out = {}
+    if photo:
+        if set(photo) == {"likelihood"}:
+            raise ValueError("--aug_likelihood needs one of --aug_gain, --aug_band_gain, --aug_brightness, --aug_noise, "
+                             "--aug_band_drop")
+        try:
+            sample_photometric(1, 1, photo, np.random.RandomState(0))
+        except ValueError as e:
+            raise ValueError(str(e).replace("photometric:", "--aug_*:")) from None
+        out["photometric"] = photo
+    if zoom is not None:
+        out["zoom"] = list(check_zoom_range(zoom))
+    return out
 
 
 REGION_KINDS = {"dice": (0.5, 0.5), "jaccard": (1.0, 1.0)}
@@ -366,6 +415,9 @@ def cfg_from_args(args, class_weights=None) -> dict:
                                                              precision=args.precision, **extension_kwargs)))
     if sampling:
         cfg["sampling"] = sampling
+    augmentation = augmentation_from_args(args)
+    if augmentation:                       # the training recipe's record; predict and infer do not read it
+        cfg["augmentation"] = augmentation
     cfg.update(schedule)
     return cfg
 
@@ -408,7 +460,7 @@ def main(argv: Optional[List[str]] = None) -> dict:
     if args.loader == "scene":
         common = dict(net=model.model, seed=c["seed_num"], ignore_index=c["ignore_index"], num_workers=args.n_workers)
         train = SceneTileLoader(train_ds, c["batch_size"], args.device, shuffle=not args.no_shuffle, transforms=transforms,
-                                **common, **cfg.get("sampling", {}))
+                                **common, **cfg.get("sampling", {}), **cfg.get("augmentation", {}))
         valid = SceneTileLoader(valid_ds, c["batch_size"], args.device, **common)       # every tile, where the grid puts it
         if wanted == "balanced":                         # counted on the device, from the label rasters resident there
             from .datasets.class_weights import balanced_class_weights
@@ -430,6 +482,8 @@ def main(argv: Optional[List[str]] = None) -> dict:
            "class_weights": None if model.class_weights is None else list(model.class_weights)}
     if "sampling" in cfg:
         out["tile_sampling"] = dict(cfg["sampling"])
+    if "augmentation" in cfg:
+        out["augmentation"] = dict(cfg["augmentation"])
     if model.weight_decay > 0.0:
         out["weight_decay"] = model.weight_decay
         out["decayed_tensors"] = len(model.model.decayed_parameter_names())

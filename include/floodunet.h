@@ -26,6 +26,7 @@
  *   fu_augment                  torchvision hflip / vflip / rotate of sample_transforms + apply_transforms
  *                                                                            st_water_seg/datasets/base_dataset.py:494-555
  *   fu_scene_train_tiles        crop + normalise + pad + label decode + augment of resident scenes in one pass (new)
+ *   fu_scene_train_tiles_ex     (new) the same pass with per-band gain / bias / counter-based noise and a per-sample zoom
  *   fu_block_param_range        (new) gradient bucket of one backward block, for RCCL all-reduce overlap
  *   fu_dp_* / fu_allreduce_*    (new) the bucketed gradient all-reduce itself, RCCL resolved at run time
  *   fu_op_*                     single operators for per-op parity tests (conv2d, batch_norm, max_pool2d,
@@ -499,6 +500,52 @@ int fu_scene_train_tiles(fu_ctx* ctx, int n, const fu_scene_train_entry* entries
                          int norm_mode, const float* global_mean, const float* global_std, float pad_value,
                          int64_t nodata_value, int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out,
                          float* std_out, fu_stream stream);
+
+/* fu_scene_train_tiles with radiometric and zoom augmentation in the same pass (added within ABI 5: purely additive).
+ * aug == NULL, or a struct whose gain, bias, sigma, out_h and out_w are all NULL, IS fu_scene_train_tiles: the same
+ * launch, the same bits.  Every array of the struct is a HOST array; they travel in the same library-owned device table
+ * as the boxes, one upload ordered on `stream`.
+ *
+ * Radiometric part (gain / bias / sigma: fp32 [n * C], sample-major, each optional -- a NULL term is skipped).  Every image
+ * pixel that comes from the scene becomes, after normalisation and with each operation rounded on its own,
+ *     t = v * gain[b][c];  t = t + bias[b][c];  t = t + sigma[b][c] * z
+ * in units of the normalised batch.  Pad pixels keep pad_value, rotation corners 0, targets are untouched.  z is a
+ * unit-variance pseudo-normal without a transcendental: Philox4x32-10 with key = (low, high word of noise_key) and counter
+ * = (oy * tile_w + ox of the OUTPUT pixel, channel, low word of noise_stream[b], high word of noise_stream[b]); S = the sum
+ * of the eight 16-bit halves of the four output words; z = (float)(2 * S - 524280) * k, k = (float)(1 / sqrt(32 * (65536^2
+ * - 1) / 12)).  So the noise of a sample depends on its stream and the pixel alone, not on its place in the batch, the
+ * launch grid or the store width.  sigma needs noise_stream (uint64 [n]).  gain and bias must be finite, sigma finite and
+ * >= 0.  floodplanet_code_amd/augment.py (photometric_host) restates all of it in numpy, bit for bit.
+ *
+ * Zoom part (out_h, out_w: int32 [n], both or neither; 1 <= out_h[b] <= tile_h, 1 <= out_w[b] <= tile_w).  With them the
+ * box of entry b may be any non-empty box inside its scene, LARGER THAN THE TILE INCLUDED, and is resampled onto the
+ * top-left out_h x out_w region of the tile; the rest is padded as before.  Flips and the rotation yield an integer pixel
+ * of the un-augmented tile as they always did; zoom maps that pixel into the box, per axis and in fp32 with every
+ * operation rounded on its own (src = the box's size, out = the out size, i = the pixel):
+ *     scale = (float)src / (float)out;  f = max(((float)i + 0.5f) * scale - 0.5f, 0);
+ *     i0 = min((int)floorf(f), src - 1);  i1 = min(i0 + 1, src - 1);  w = f - (float)i0
+ * The image is interpolated along x, then along y, with lerp(p, q, w) = p + w * (q - p), and normalised after that (then
+ * the radiometric part).  Labels take the raw byte at min((int)floorf(((float)i + 0.5f) * scale), src - 1) per axis
+ * (torch's 'nearest-exact') and are decoded as usual.  src == out gives w = 0 and the source pixel itself.  Under norm_mode
+ * 'local' the statistics are those of the SOURCE BOX's own pixels (the stats kernel of fu_scene_crops, which has no
+ * tile-size limit), not of the resampled tile; at zoom 1 that is fu_scene_train_tiles' behaviour.
+ * floodplanet_code_amd/datasets/sampling.py (zoom_tile_host) is the numpy statement.
+ *
+ * Every entry and every array element is checked before anything is copied or launched: a rejected call launches
+ * nothing.  Without the zoom part a box is still at most the tile. */
+typedef struct fu_scene_aug {
+  const float* gain;             /* host fp32 [n * C] or NULL */
+  const float* bias;             /* host fp32 [n * C] or NULL */
+  const float* sigma;            /* host fp32 [n * C] or NULL */
+  const uint64_t* noise_stream;  /* host uint64 [n]; needed with sigma */
+  uint64_t noise_key;
+  const int32_t* out_h;          /* host int32 [n] or NULL (with out_w) */
+  const int32_t* out_w;
+} fu_scene_aug;
+int fu_scene_train_tiles_ex(fu_ctx* ctx, int n, const fu_scene_train_entry* entries, int C, int tile_h, int tile_w,
+                            int norm_mode, const float* global_mean, const float* global_std, float pad_value,
+                            int64_t nodata_value, int64_t target_fill, float* image_out, int64_t* target_out,
+                            float* mean_out, float* std_out, const fu_scene_aug* aug, fu_stream stream);
 
 /* Class frequencies of resident label rasters (added within ABI 5: purely additive), for "balanced" class weights.
  * entries: a host table of n fu_scene_train_entry; only label, scene_h, scene_w and the box are read (scene, flags and
