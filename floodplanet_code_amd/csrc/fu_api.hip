@@ -665,7 +665,7 @@ int fu_scene_train_tiles(fu_ctx* c, int n, const fu_scene_train_entry* entries, 
                          fu_stream stream) {
   FU_REQUIRE(c && entries && image_out, "fu_scene_train_tiles: null context / entries / image_out");
   return launch_scene_train_tiles(c->train_table, n, entries, C, tile_h, tile_w, norm_mode, global_mean, global_std,
-                                  pad_value, nodata_value, target_fill, image_out, target_out, mean_out, std_out,
+                                  pad_value, nodata_value, target_fill, image_out, target_out, mean_out, std_out, nullptr,
                                   (hipStream_t)stream);
 }
 
@@ -674,9 +674,9 @@ int fu_scene_train_tiles_ex(fu_ctx* c, int n, const fu_scene_train_entry* entrie
                             int64_t nodata_value, int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out,
                             float* std_out, const fu_scene_aug* aug, fu_stream stream) {
   FU_REQUIRE(c && entries && image_out, "fu_scene_train_tiles_ex: null context / entries / image_out");
-  return launch_scene_train_tiles_ex(c->train_table, n, entries, C, tile_h, tile_w, norm_mode, global_mean, global_std,
-                                     pad_value, nodata_value, target_fill, image_out, target_out, mean_out, std_out, aug,
-                                     (hipStream_t)stream);
+  return launch_scene_train_tiles(c->train_table, n, entries, C, tile_h, tile_w, norm_mode, global_mean, global_std,
+                                  pad_value, nodata_value, target_fill, image_out, target_out, mean_out, std_out, aug,
+                                  (hipStream_t)stream);
 }
 
 int fu_label_class_counts(fu_ctx* c, int n, const fu_scene_train_entry* entries, int64_t nodata_value, int n_classes,

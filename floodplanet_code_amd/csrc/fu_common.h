@@ -624,18 +624,14 @@ int launch_assemble_tiles(const float* const* srcs, const int* src_channels, int
 int launch_scene_crops(DeviceTable& table, int n, const fu_scene_crop* entries, int C, int H, int W, int norm_mode,
                        const float* gmean, const float* gstd, float pad_value, float* out, float* mean_out, float* std_out,
                        hipStream_t s);
-// fu_scene_train_tiles: launch_scene_crops composed with launch_augment and the label decode, with no batch in between;
-// checked, uploaded and launched in the same way
+// fu_scene_train_tiles[_ex] (fu_scene_train.hip): launch_scene_crops composed with launch_augment and the label decode, with
+// no batch in between, and the radiometric and zoom parts of `aug` applied in the same pass; checked, uploaded and launched
+// in the same way, every array of `aug` included.  A null or all-off `aug` is fu_scene_train_tiles: its table, its messages
+// and its kernel.
 int launch_scene_train_tiles(DeviceTable& table, int n, const fu_scene_train_entry* entries, int C, int H, int W,
                              int norm_mode, const float* gmean, const float* gstd, float pad_value, int64_t nodata_value,
                              int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out, float* std_out,
-                             hipStream_t s);
-// fu_scene_train_tiles_ex: the same with the radiometric and zoom parts of `aug` applied in the pass; a null or all-off
-// `aug` IS launch_scene_train_tiles.  Every array of `aug` is checked before anything is copied or launched.
-int launch_scene_train_tiles_ex(DeviceTable& table, int n, const fu_scene_train_entry* entries, int C, int H, int W,
-                                int norm_mode, const float* gmean, const float* gstd, float pad_value, int64_t nodata_value,
-                                int64_t target_fill, float* image_out, int64_t* target_out, float* mean_out, float* std_out,
-                                const fu_scene_aug* aug, hipStream_t s);
+                             const fu_scene_aug* aug, hipStream_t s);
 // fu_label_class_counts: counts[d] += #pixels of the entries' label boxes that decode to class d (0 <= d < n_classes);
 // checked, uploaded and launched in the same way
 int launch_label_class_counts(DeviceTable& table, int n, const fu_scene_train_entry* entries, int64_t nodata_value,

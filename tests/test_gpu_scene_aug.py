@@ -276,7 +276,7 @@ def test_vector_and_scalar_stores_give_the_same_values(net, scenes, norm_mode):
     entries = _entries(scenes, [b for b, _ in zb])
     zoom = ([o[0] for _, o in zb], [o[1] for _, o in zb])
     kw = dict(pad_value=PAD, nodata_value=NODATA, target_fill=FILL)
-    for options in (dict(photometric=_photo(seed=2)), dict(zoom=zoom), dict(zoom=zoom, photometric=_photo(seed=2))):
+    for options in (dict(photometric=_photo(seed=2)), dict(zoom=zoom), dict(zoom=zoom, photometric=_photo(seed=2)), {}):
         ent = entries if "zoom" in options else _entries(scenes, _plain_boxes(th, tw))
         want = scene_train_tiles(net._ctx, ent, tile, norm_mode, **options, **kw)
         image = torch.full((N * C_ * th * tw + 4,), 9.0, device=DEV)
