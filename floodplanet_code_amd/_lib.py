@@ -276,6 +276,10 @@ SIGNATURES = {
     "fu_op_upsample2_bwd": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "fu_op_depth_to_space": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "fu_op_space_to_depth": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "fu_op_loss_grad_eff": (_i, [_p, _p, _i64, _p, _p, _p, _p, _p]),
+    "fu_op_fp16_guard": (_i, [_p, _i64, _p, _i, _p]),
+    "fu_test_fp16_state": (_i, [_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "fu_test_set_fp16_backoff": (_i, [_p, _i, _i, _p]),
 }
 
 _lib: Optional[C.CDLL] = None

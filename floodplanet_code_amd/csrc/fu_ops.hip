@@ -1,8 +1,10 @@
 // Single operators behind the C ABI (fu_op_*): one launcher each on caller-owned buffers, with temporary packs and
 // partial buffers of their own -- the hooks of the op-level parity tests -- and fu_test_get_buffer,
-// fu_test_loss_buffers and fu_test_get_pack, the only entry points here that look inside a context.
+// fu_test_loss_buffers, fu_test_get_pack, fu_test_fp16_state and fu_test_set_fp16_backoff, the only entry points here that
+// look inside a context.
 #include "fu_ctx.h"
 #include "fu_elem.h"
+#include "fu_optim.h"
 
 #include <vector>
 
@@ -362,6 +364,44 @@ int fu_op_bn_bwd(int precision, void* g, const void* y, int C, int B, int H, int
                  float* dbeta, fu_stream stream) {
   return fu_op_bn_bwd_ex(precision, g, y, C, B, H, W, bn_a, bn_b, mean, invstd, g_pool, dgamma, dbeta, nullptr, 0, nullptr,
                          nullptr, 0, nullptr, nullptr, nullptr, 0, stream);
+}
+
+// ---- op-level test hooks of the fp16 loss scale and overflow guard (fu_loss.hip, fu_optim.hip) ---------------------------
+int fu_op_loss_grad_eff(const float* dlogits, float* out, int64_t n, const float* up_dev, float* partials, float* scale,
+                        const int* guard, fu_stream stream) {
+  FU_REQUIRE(dlogits && out && partials, "fu_op_loss_grad_eff: null argument");
+  FU_REQUIRE(n >= 1, "fu_op_loss_grad_eff: n must be >= 1 (got %lld)", (long long)n);
+  return launch_loss_grad_eff(dlogits, out, n, up_dev, partials, scale, (hipStream_t)stream, guard);
+}
+
+int fu_op_fp16_guard(const float* g, int64_t n, int* guard, int book, fu_stream stream) {
+  FU_REQUIRE(g && guard, "fu_op_fp16_guard: null argument");
+  FU_REQUIRE(n >= 1, "fu_op_fp16_guard: n must be >= 1 (got %lld)", (long long)n);
+  FU_TRY(launch_grad_finite_check(g, n, guard, (hipStream_t)stream));
+  if (book) FU_TRY(launch_guard_book(guard, (hipStream_t)stream));
+  return FU_OK;
+}
+
+int fu_test_fp16_state(fu_ctx* c, float scale[2], int32_t guard[4]) {
+  FU_REQUIRE(c && scale && guard, "fu_test_fp16_state: null argument");
+  scale[0] = scale[1] = 0.f;
+  guard[0] = guard[1] = guard[2] = guard[3] = 0;
+  if (c->prec != PREC_F16) return FU_OK;
+  FU_HIP_CHECK(hipSetDevice(c->cfg.device));
+  FU_HIP_CHECK(hipDeviceSynchronize());                  // every stream: the step may run on a non-blocking one
+  FU_HIP_CHECK(hipMemcpy(scale, c->loss_scale, 2 * sizeof(float), hipMemcpyDeviceToHost));
+  FU_HIP_CHECK(hipMemcpy(guard, c->guard, 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return FU_OK;
+}
+
+int fu_test_set_fp16_backoff(fu_ctx* c, int exponent, int clean_steps, fu_stream stream) {
+  FU_REQUIRE(c, "fu_test_set_fp16_backoff: null context");
+  FU_REQUIRE(c->prec == PREC_F16, "fu_test_set_fp16_backoff: the context is not fp16");
+  FU_REQUIRE(exponent >= 0 && exponent <= 14, "fu_test_set_fp16_backoff: exponent %d outside 0..14", exponent);
+  FU_REQUIRE(clean_steps >= 0 && clean_steps <= 63, "fu_test_set_fp16_backoff: clean_steps %d outside 0..63", clean_steps);
+  FU_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(c->guard + 2), exponent, 1, (hipStream_t)stream));
+  FU_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(c->guard + 3), clean_steps, 1, (hipStream_t)stream));
+  return FU_OK;
 }
 
 int fu_test_get_buffer(fu_ctx* c, int block, int which, void** ptr, int64_t* elems) {

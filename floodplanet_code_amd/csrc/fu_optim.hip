@@ -257,16 +257,22 @@ int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, const A
 // NaN then reaches the flat gradient buffer; guard[0] flags it, the Adam launch of that step does nothing, and the next
 // backward's scale is halved once more (guard[2] = back-off exponent, taken back by one every 64 clean steps).
 //   guard[0] non-finite flag of the running step, [1] steps skipped so far, [2] back-off exponent, [3] clean steps since
+// Every element is examined once: a scalar head up to the first 16-byte boundary (the gradient buffer is bound at any 4-byte
+// alignment, as for adam_body and k_grad_sqnorm_chunks), 16-byte loads over the body, a scalar tail -- head and tail, at
+// most 3 + 3 elements, by the first lanes of workgroup 0.
 __global__ __launch_bounds__(256) void k_grad_finite_check(const float* __restrict__ g, int64_t n, int* __restrict__ guard) {
+  int64_t head = (int64_t)(((16 - ((uintptr_t)g & 15)) & 15) >> 2);
+  if (head > n) head = n;
+  const int64_t nvec = (n - head) >> 2;
+  const float4* __restrict__ body = reinterpret_cast<const float4*>(g + head);
   bool bad = false;
-  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 1024) {
-    if (i + 3 < n) {
-      const float4 v = *reinterpret_cast<const float4*>(g + i);
-      bad = bad || !(fabsf(v.x) <= 3.0e38f) || !(fabsf(v.y) <= 3.0e38f) || !(fabsf(v.z) <= 3.0e38f) || !(fabsf(v.w) <= 3.0e38f);
-    } else {
-      for (int64_t k = i; k < n; ++k) bad = bad || !(fabsf(g[k]) <= 3.0e38f);
-    }
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < nvec; j += (int64_t)gridDim.x * 256) {
+    const float4 v = body[j];
+    bad = bad || !(fabsf(v.x) <= 3.0e38f) || !(fabsf(v.y) <= 3.0e38f) || !(fabsf(v.z) <= 3.0e38f) || !(fabsf(v.w) <= 3.0e38f);
   }
+  const int64_t tail0 = head + 4 * nvec, nrest = head + (n - tail0);
+  if (blockIdx.x == 0 && threadIdx.x < nrest)
+    bad = bad || !(fabsf(g[threadIdx.x < head ? (int64_t)threadIdx.x : tail0 + (threadIdx.x - head)]) <= 3.0e38f);
   if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(guard, 1);
 }
 __global__ void k_guard_book(int* __restrict__ guard) {

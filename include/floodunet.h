@@ -925,6 +925,27 @@ int fu_op_bn_stats(const float* partials, int n_part, int C, int64_t count, cons
                    const float* beta, float eps, float momentum, float* mean, float* invstd, float* a, float* b,
                    float* rmean, float* rvar, int64_t* nbt, fu_stream stream);
 
+/* The fp16 loss scale and overflow guard, one operator at a time (test hooks like the fu_test_* switches: no ABI promise).
+ * None of the two operators synchronises; every buffer is device memory.
+ * out[i] = dlogits[i] * f, dlogits never written.  scale == NULL: f = *up_dev (1 when NULL); partials is not touched.
+ * scale != NULL (what an fp16 backward runs): f = *up_dev * S with S = 2^e, e = 6 - frexp(m).exponent for
+ * m = max|dlogits| * |*up_dev| over the entries with |x| <= 3.0e38 (e = 0 when m is 0), minus guard[2] when guard is given,
+ * clamped to [-60, 60]; scale[0] = S, scale[1] = 1 / S.  partials: at least 256 floats of scratch.  Null dlogits / out /
+ * partials or n < 1: FU_ERR_INVALID. */
+int fu_op_loss_grad_eff(const float* dlogits, float* out, int64_t n, const float* up_dev, float* partials, float* scale,
+                        const int* guard, fu_stream stream);
+/* guard[0] |= 1 when an element of g[0..n) is not |x| <= 3.0e38 (inf, NaN and the finite values above it); g at any
+ * 4-byte alignment.  book != 0: then the bookkeeping launch of the optimiser step on guard[0..3] = {flag, skipped steps,
+ * back-off exponent, clean steps}: a set flag counts a skipped step, raises the exponent (at most 14) and clears the clean
+ * count and the flag; otherwise the 64th clean step in a row lowers the exponent (not below 0) and restarts the count. */
+int fu_op_fp16_guard(const float* g, int64_t n, int* guard, int book, fu_stream stream);
+/* Testing hook: the context's {S, 1 / S} of the last backward and its four guard integers, read after synchronising the
+ * device; all zero for a context that is not FU_F16 (as fu_fp16_guard_state). */
+int fu_test_fp16_state(fu_ctx* ctx, float scale[2], int32_t guard[4]);
+/* Testing hook: writes the guard's back-off exponent (0..14) and clean-step count (0..63) in `stream`'s order, as if that
+ * many steps had overflowed / passed.  Outside those ranges, or on a context that is not FU_F16: FU_ERR_INVALID. */
+int fu_test_set_fp16_backoff(fu_ctx* ctx, int exponent, int clean_steps, fu_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
