@@ -121,6 +121,19 @@ class FuClassThreshold(C.Structure):
     _fields_ = [("cls", C.c_int32), ("threshold", C.c_float)]
 
 
+class FuMaskBox(C.Structure):
+    """fu_mask_box (include/floodunet.h): one box of a device uint8 mask for fu_mask_box_counts."""
+    _fields_ = [
+        ("mask", C.c_void_p),
+        ("mask_h", C.c_int32),
+        ("mask_w", C.c_int32),
+        ("h0", C.c_int32),
+        ("w0", C.c_int32),
+        ("hE", C.c_int32),
+        ("wE", C.c_int32),
+    ]
+
+
 class FuTestPack(C.Structure):
     """fu_test_pack (include/floodunet.h): one packed weight copy of a context, as fu_test_get_pack reports it."""
     _fields_ = [
@@ -210,6 +223,10 @@ SIGNATURES = {
     "fu_stitch_add_batch_windowed": (_i, [_p, _i, C.POINTER(FuStitchEntry), _p, _i, _p, _p, _p]),
     "fu_stitch_finalize_maps": (_i, [_p, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p, _p]),
     "fu_stitch_finalize_maps_ex": (_i, [_p, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p, C.POINTER(FuClassThreshold), _p]),
+    "fu_stitch_finalize_maps_masked": (_i, [_p, _p, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p, C.POINTER(FuClassThreshold),
+                                            _p, _i, _p]),
+    "fu_scene_valid_mask": (_i, [_p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    "fu_mask_box_counts": (_i, [_p, _i, C.POINTER(FuMaskBox), _p, _p]),
     "fu_eval_prob_hist": (_i, [_p, _p, _i, _i, _p, _p, _p]),
     "fu_prob_hist": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p, _p]),
     "fu_sieve_workspace_bytes": (_i64, [_i, _i]),

@@ -570,6 +570,15 @@ int fu_stitch_finalize_maps(float* canvas, const float* weight, int n_classes, i
 int fu_stitch_finalize_maps_ex(float* canvas, const float* weight, int n_classes, int canvas_h, int canvas_w, float eps,
                                int normalize_in_place, const uint8_t* class_values, uint8_t* class_out, uint8_t* prob_out,
                                uint8_t* margin_out, int64_t* counts_out, const fu_class_threshold* thr, fu_stream stream) {
+  return fu_stitch_finalize_maps_masked(canvas, weight, n_classes, canvas_h, canvas_w, eps, normalize_in_place, class_values,
+                                        class_out, prob_out, margin_out, counts_out, thr, nullptr, 0, stream);
+}
+
+// valid == NULL: fu_stitch_finalize_maps_ex, its checks, its messages and its kernels (nodata_value is not looked at)
+int fu_stitch_finalize_maps_masked(float* canvas, const float* weight, int n_classes, int canvas_h, int canvas_w, float eps,
+                                   int normalize_in_place, const uint8_t* class_values, uint8_t* class_out, uint8_t* prob_out,
+                                   uint8_t* margin_out, int64_t* counts_out, const fu_class_threshold* thr,
+                                   const uint8_t* valid, int nodata_value, fu_stream stream) {
   FU_REQUIRE(canvas && weight, "fu_stitch_finalize_maps: null canvas / weight");
   FU_REQUIRE(n_classes >= 1 && n_classes <= HEAD_MAX_CLS, "fu_stitch_finalize_maps: n_classes %d not in 1..%d", n_classes,
              HEAD_MAX_CLS);
@@ -584,8 +593,31 @@ int fu_stitch_finalize_maps_ex(float* canvas, const float* weight, int n_classes
     FU_REQUIRE(isfinite(thr->threshold) && thr->threshold >= 0.f && thr->threshold <= 1.f,
                "fu_stitch_finalize_maps_ex: threshold %g is not finite or outside [0, 1]", (double)thr->threshold);
   }
+  if (valid) {
+    const char* fn = "fu_stitch_finalize_maps_masked";
+    FU_REQUIRE(canvas_h >= 1 && canvas_w >= 1 && (int64_t)canvas_h * canvas_w <= FU_MAP_MAX_PIXELS,
+               "%s: canvas %dx%d is empty or has more than 2^28 pixels", fn, canvas_h, canvas_w);
+    FU_REQUIRE(nodata_value >= 0 && nodata_value <= 255, "%s: nodata_value %d not in 0..255", fn, nodata_value);
+    FU_REQUIRE(class_values || nodata_value >= n_classes,
+               "%s: nodata_value %d is a class index (identity class values 0..%d)", fn, nodata_value, n_classes - 1);
+    for (int k = 0; class_values && k < n_classes; ++k)
+      FU_REQUIRE(class_values[k] != nodata_value, "%s: nodata_value %d is the value of class %d", fn, nodata_value, k);
+  }
   return launch_stitch_finalize_maps(canvas, weight, n_classes, (int64_t)canvas_h * canvas_w, eps, normalize_in_place != 0,
-                                     class_values, class_out, prob_out, margin_out, counts_out, thr, (hipStream_t)stream);
+                                     class_values, class_out, prob_out, margin_out, counts_out, thr, (hipStream_t)stream,
+                                     valid, nodata_value);
+}
+
+int fu_scene_valid_mask(const float* raster, int C, int src_h, int src_w, int use_nodata, float nodata, const int32_t* iy,
+                        const float* wy, const int32_t* ix, const float* wx, int grid_h, int grid_w, uint8_t* src_valid,
+                        uint8_t* valid_out, int64_t* n_valid_out, fu_stream stream) {
+  return launch_scene_valid_mask(raster, C, src_h, src_w, use_nodata != 0, nodata, iy, wy, ix, wx, grid_h, grid_w, src_valid,
+                                 valid_out, n_valid_out, (hipStream_t)stream);
+}
+
+int fu_mask_box_counts(fu_ctx* c, int n, const fu_mask_box* entries, int64_t* counts_out, fu_stream stream) {
+  FU_REQUIRE(c && entries && counts_out, "fu_mask_box_counts: null context / entries / counts_out");
+  return launch_mask_box_counts(c->scene_table, n, entries, counts_out, (hipStream_t)stream);
 }
 
 int fu_eval_prob_hist(fu_ctx* c, const int64_t* target, int ignore_index, int n_bins, int64_t* hist_out, int64_t* top_out,

@@ -14,6 +14,7 @@ struct fu_scene_crop;
 struct fu_scene_train_entry;
 struct fu_scene_aug;
 struct fu_class_threshold;
+struct fu_mask_box;
 
 namespace fu {
 
@@ -597,7 +598,17 @@ int launch_stitch_add_batch(DeviceTable& table, const char* fn, const char* batc
 // thr (fu_stitch_finalize_maps_ex): null = the argmax; else the class map and the counts follow the thresholded decision
 int launch_stitch_finalize_maps(float* canvas, const float* weight, int ncls, int64_t npix, float eps, bool normalize,
                                 const unsigned char* class_values, unsigned char* class_out, unsigned char* prob_out,
-                                unsigned char* margin_out, int64_t* counts, const fu_class_threshold* thr, hipStream_t s);
+                                unsigned char* margin_out, int64_t* counts, const fu_class_threshold* thr, hipStream_t s,
+                                const unsigned char* valid = nullptr, int nodata_value = 0);
+// fu_scene_valid_mask / fu_mask_box_counts (fu_valid_mask.hip): the valid-pixel mask of a resident scene on its grid and its
+// count (n_valid: WRITTEN, zeroed on s first), and the non-zero bytes of every box of a table of masks (counts[i] WRITTEN).
+// Both check every argument before anything is copied or launched.  valid / nodata_value above
+// (fu_stitch_finalize_maps_masked): null = the unmasked kernels; else a pixel whose byte is 0 is finalised as an uncovered
+// one, with class byte nodata_value
+int launch_scene_valid_mask(const float* raster, int C, int src_h, int src_w, bool use_nodata, float nodata, const int* iy,
+                            const float* wy, const int* ix, const float* wx, int grid_h, int grid_w,
+                            unsigned char* src_valid, unsigned char* valid, int64_t* n_valid, hipStream_t s);
+int launch_mask_box_counts(DeviceTable& table, int n, const fu_mask_box* entries, int64_t* counts, hipStream_t s);
 // fu_map_components / fu_map_sieve (fu_post.hip): union-find labelling of a uint8 map (the label of a pixel = the smallest
 // linear index of its component) and the connected-component sieve on top of it; the caller has checked every argument.
 // workspace: sieve_workspace_bytes(h, w) = 16 B per pixel (64-bit donor keys, labels, sizes); stats: int64[2] ADDED to, or null

@@ -241,8 +241,11 @@ int launch_stitch_add_batch(DeviceTable& table, const char* fn, const char* batc
 // pixels per argmax class.  Memory bound: a thread takes 4 consecutive pixels -- one float4 of weights, K float4 of
 // canvas, one 4-byte store per uint8 map -- between a misaligned head and a tail that run one pixel at a time; an array
 // that is not aligned alike (vec bit clear) is read or written one element at a time inside the groups too.
+// MASKED (fu_stitch_finalize_maps_masked with a mask): one more byte per pixel, read 4 at a time where aligned; a pixel whose
+// byte is 0 goes the uncovered pixel's way, except that its class byte is nodata_value.  The unmasked instantiations are
+// the kernels they were.
 // ------------------------------------------------------------------------------------------------
-enum : unsigned { MAPS_VEC_CANVAS = 1, MAPS_VEC_CLASS = 2, MAPS_VEC_PROB = 4, MAPS_VEC_MARGIN = 8 };
+enum : unsigned { MAPS_VEC_CANVAS = 1, MAPS_VEC_CLASS = 2, MAPS_VEC_PROB = 4, MAPS_VEC_MARGIN = 8, MAPS_VEC_VALID = 16 };
 
 struct FinalizeMaps {
   float* canvas;                   // [npix, K] raw sums
@@ -258,6 +261,8 @@ struct FinalizeMaps {
   unsigned vec;                    // MAPS_VEC_*: the array is aligned for the group's wide access
   int thr_cls;                     // fu_stitch_finalize_maps_ex: the thresholded class, -1 = the plain argmax
   float thr;
+  const unsigned char* valid;      // MASKED: [npix], 0 = no data
+  unsigned nodata_value;           // MASKED: the class map's byte of such a pixel
 };
 
 __device__ __forceinline__ unsigned char quantize_unit(float x) {
@@ -310,7 +315,17 @@ __device__ __forceinline__ int decide_class(const float (&v)[K], int am, int cls
   return vc >= thr ? cls : other;
 }
 
+// MASKED: a pixel without data -> the uncovered pixel's values; false: it is no pixel to count or to classify
 template <int K>
+__device__ __forceinline__ bool mask_pixel(bool has_data, bool covered, float (&v)[K], float& margin) {
+  if (has_data) return covered;
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = 0.f;
+  margin = 0.f;
+  return false;
+}
+
+template <int K, bool MASKED>
 __global__ __launch_bounds__(256) void k_stitch_finalize_maps(const FinalizeMaps a) {
   __shared__ unsigned int bins[HEAD_MAX_CLS];
   if (a.counts) {
@@ -334,7 +349,16 @@ __global__ __launch_bounds__(256) void k_stitch_finalize_maps(const FinalizeMaps
 #pragma unroll
       for (int i = 0; i < 4 * K; ++i) c[i] = a.canvas[p * K + i];
     }
-    unsigned cls = 0, mg = 0, pq[K];
+    unsigned cls = 0, mg = 0, pq[K], vm = 0x01010101u;
+    if constexpr (MASKED) {
+      if (a.vec & MAPS_VEC_VALID) {
+        vm = *reinterpret_cast<const unsigned*>(a.valid + p);
+      } else {
+        vm = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) vm |= (unsigned)a.valid[p + q] << (8 * q);
+      }
+    }
 #pragma unroll
     for (int k = 0; k < K; ++k) pq[k] = 0;
 #pragma unroll
@@ -343,14 +367,19 @@ __global__ __launch_bounds__(256) void k_stitch_finalize_maps(const FinalizeMaps
       int am;
 #pragma unroll
       for (int k = 0; k < K; ++k) v[k] = c[q * K + k];
-      const bool covered = finalize_pixel<K>(v, wq[q], a.eps, am, margin);
+      bool covered = finalize_pixel<K>(v, wq[q], a.eps, am, margin);
+      bool has_data = true;
+      if constexpr (MASKED) {
+        has_data = ((vm >> (8 * q)) & 0xffu) != 0u;
+        covered = mask_pixel<K>(has_data, covered, v, margin);
+      }
       if (covered) am = decide_class<K>(v, am, a.thr_cls, a.thr);
 #pragma unroll
       for (int k = 0; k < K; ++k) {
         c[q * K + k] = v[k];
         pq[k] |= (unsigned)quantize_unit(v[k]) << (8 * q);
       }
-      cls |= (unsigned)(unsigned char)(a.class_values >> (8 * am)) << (8 * q);
+      cls |= (has_data ? (unsigned)(unsigned char)(a.class_values >> (8 * am)) : a.nodata_value) << (8 * q);
       mg |= (unsigned)quantize_unit(margin) << (8 * q);
       if (a.counts && covered) atomicAdd(&bins[am], 1u);
     }
@@ -400,14 +429,19 @@ __global__ __launch_bounds__(256) void k_stitch_finalize_maps(const FinalizeMaps
     int am;
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = a.canvas[p * K + k];
-    const bool covered = finalize_pixel<K>(v, a.weight[p], a.eps, am, margin);
+    bool covered = finalize_pixel<K>(v, a.weight[p], a.eps, am, margin);
+    bool has_data = true;
+    if constexpr (MASKED) {
+      has_data = a.valid[p] != 0;
+      covered = mask_pixel<K>(has_data, covered, v, margin);
+    }
     if (covered) am = decide_class<K>(v, am, a.thr_cls, a.thr);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       if (a.normalize) a.canvas[p * K + k] = v[k];
       if (a.prob_out) a.prob_out[(int64_t)k * a.npix + p] = quantize_unit(v[k]);
     }
-    if (a.class_out) a.class_out[p] = (unsigned char)(a.class_values >> (8 * am));
+    if (a.class_out) a.class_out[p] = has_data ? (unsigned char)(a.class_values >> (8 * am)) : (unsigned char)a.nodata_value;
     if (a.margin_out) a.margin_out[p] = quantize_unit(margin);
     if (a.counts && covered) atomicAdd(&bins[am], 1u);
   }
@@ -419,9 +453,11 @@ __global__ __launch_bounds__(256) void k_stitch_finalize_maps(const FinalizeMaps
 
 int launch_stitch_finalize_maps(float* canvas, const float* weight, int ncls, int64_t npix, float eps, bool normalize,
                                 const unsigned char* class_values, unsigned char* class_out, unsigned char* prob_out,
-                                unsigned char* margin_out, int64_t* counts, const fu_class_threshold* thr, hipStream_t s) {
+                                unsigned char* margin_out, int64_t* counts, const fu_class_threshold* thr, hipStream_t s,
+                                const unsigned char* valid, int nodata_value) {
   if (npix <= 0) return 0;
   FinalizeMaps a{};
+  a.valid = valid, a.nodata_value = valid ? (unsigned)nodata_value : 0u;
   a.thr_cls = thr ? thr->cls : -1, a.thr = thr ? thr->threshold : 0.f;
   a.canvas = canvas, a.weight = weight, a.class_out = class_out, a.prob_out = prob_out, a.margin_out = margin_out;
   a.counts = reinterpret_cast<unsigned long long*>(counts);
@@ -436,10 +472,15 @@ int launch_stitch_finalize_maps(float* canvas, const float* weight, int ncls, in
   if (aligned(canvas, 4, ncls, 16)) a.vec |= MAPS_VEC_CANVAS;
   if (aligned(class_out, 1, 1, 4)) a.vec |= MAPS_VEC_CLASS;
   if (aligned(margin_out, 1, 1, 4)) a.vec |= MAPS_VEC_MARGIN;
+  if (aligned(valid, 1, 1, 4)) a.vec |= MAPS_VEC_VALID;
   if (aligned(prob_out, 1, 1, 4) && (ncls == 1 || npix % 4 == 0)) a.vec |= MAPS_VEC_PROB;   // every band alike
   const dim3 grid(grid_for(ceil_div64(npix, 4), 256, 2048));
   switch (ncls) {
-#define FU_MAPS_CASE(K) case K: hipLaunchKernelGGL(k_stitch_finalize_maps<K>, grid, dim3(256), 0, s, a); break;
+#define FU_MAPS_CASE(K)                                                                               \
+  case K:                                                                                             \
+    if (valid) hipLaunchKernelGGL((k_stitch_finalize_maps<K, true>), grid, dim3(256), 0, s, a);       \
+    else hipLaunchKernelGGL((k_stitch_finalize_maps<K, false>), grid, dim3(256), 0, s, a);            \
+    break;
     FU_MAPS_CASE(1) FU_MAPS_CASE(2) FU_MAPS_CASE(3) FU_MAPS_CASE(4) FU_MAPS_CASE(5) FU_MAPS_CASE(6) FU_MAPS_CASE(7)
     FU_MAPS_CASE(8)
 #undef FU_MAPS_CASE

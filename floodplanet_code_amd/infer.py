@@ -21,7 +21,8 @@ else the parent directory.  What runs differently:
     crop gets one padded crop where get_crop_slices raises; boxes are clipped to the grid (get_crop_slices' bottom-edge
     quirk swaps the crop sizes, which only matters for non-square crops);
   * extension: the input's GeoTIFF georeferencing goes along with the class map (the reference drops it through PIL),
-    rescaled to the output grid (geo_tags_for_grid); GDAL_NODATA is dropped;
+    rescaled to the output grid (geo_tags_for_grid); the input's GDAL_NODATA does not go along (it does not describe a
+    0 / 255 mask) -- with --nodata the class map carries one of its own, see below;
   * extension: --blend linear|hann weights every crop with a window that falls off towards the tile's border
     (stitch.blend_window), so a pixel is decided by the crops that see it with their interior; the stride then defaults
     to half the crop.  --write_probs u8|f32 writes the stitched probabilities as <image>_prob.tif ([k, H, W]; u8 =
@@ -36,6 +37,23 @@ else the parent directory.  What runs differently:
     (fu_stitch_finalize_maps_ex); --calibration FILE takes C and T from the calibration.json of predict --calibrate.
     class_pixels follows the rule, the sieve runs on the thresholded map, the probability and margin rasters do not
     change; the summary records the rule under "threshold".
+  * extension: --nodata auto|V makes the run aware of pixels that hold no data (swath edges, collars, fill).  The rule is
+    datasets/valid_mask.py's: a source pixel is valid when every band is finite and not every band equals V (auto: the
+    scene's GDAL_NODATA tag when it parses as a finite number, else 0), a grid pixel when nothing it was resampled from
+    was fill.  The mask is derived on the device from the uploaded scene (fu_scene_valid_mask), next to the resample and
+    from the same upload and tables.  Where it is 0 the class map is --nodata_out N (default 127) instead of 0 / 255, the
+    probability and margin rasters are 0, the pixel is not counted in class_pixels and, under --sieve, is neither merged
+    nor a donor (frozen_value) -- all inside the one finalisation launch (fu_stitch_finalize_maps_masked).  The class map
+    carries GDAL_NODATA = "N" (tag 42113); the probability and margin rasters carry none, 0 is a value there.  Crops
+    without a single valid pixel are not forwarded (one census launch per scene, fu_mask_box_counts, and one small read;
+    --keep_empty_crops forwards them): a valid pixel lies only in boxes that contain it, so it loses no covering crop and
+    its sequence of stitch additions does not change.  A scene without any valid pixel never enters a batch and is
+    written as all N.  --write_valid writes the mask as <image>_valid.tif (uint8 0 / 1).  The records gain
+    "valid_pixels", "skipped_crops" and "nodata" (the value used), "crops" counts the crops forwarded, and the summary
+    gains "nodata".  Not part of it: norm_mode 'local' still takes a crop's statistics over all its pixels, fill included,
+    exactly as without the option, so a valid pixel's probabilities are the same with and without --nodata; the
+    resampling is not mask-aware; predict (labelled evaluation) and training are not touched.  Without --nodata nothing
+    of this runs and every file is byte for byte what it was.
 How infer() is put together: the options travel as one checked InferOptions (infer_options.py; the keywords of infer() and
 the command line both go through InferOptions.make); predict.load_eval_model serves the model; a SceneQueue owns the
 scenes in flight and deals their crops out in batches; per batch scene_crops, predict.eval_forward and one batched stitch;
@@ -56,8 +74,8 @@ from typing import Callable, Dict, Iterable, Iterator, List, Optional, Sequence,
 import numpy as np
 import torch
 
-from .infer_options import (BLEND_KINDS, PROB_FORMATS, WEIGHT_CHOICES, InferOptions, default_stride, grid_size,  # noqa: F401
-                            threshold_rule)
+from .infer_options import (BLEND_KINDS, NODATA_OUT_DEFAULT, PROB_FORMATS, WEIGHT_CHOICES, InferOptions,  # noqa: F401
+                            default_stride, grid_size, scene_nodata, threshold_rule)
 from .predict import CONFIG_DEFAULTS, _merge, eval_forward, load_eval_model, resolve_cfg
 from .tta import VIEW_SETS, recorded
 
@@ -115,7 +133,8 @@ def geo_tags_for_grid(tags: Dict[int, object], src_hw: Tuple[int, int], grid_hw:
     GeoKey directory, doubles and ASCII verbatim; ModelPixelScale times source / grid size per axis; ModelTiepoint's raster
     point scaled with the grid (the usual (0, 0) stays), and under PixelIsPoint (GeoKey 1025 = 2) its world point moved by
     half the change in pixel size; ModelTransformation's linear part scaled (and its translation moved likewise under
-    PixelIsPoint); GDAL_NODATA dropped -- it does not apply to a 0 / 255 mask."""
+    PixelIsPoint); the source's GDAL_NODATA is not copied -- it does not apply to a 0 / 255 mask (write_scene adds the
+    class map's own under --nodata)."""
     fy, fx = src_hw[0] / grid_hw[0], src_hw[1] / grid_hw[1]
     keys = tags.get(34735)
     point = False
@@ -165,13 +184,21 @@ def resident_grid(raster: torch.Tensor, scale_mode: int, grid_hw: Tuple[int, int
     tables of lanczos4_axis_window (identity tables when the sizes match) and the sensor scaling training uses -- so
     every crop of the grid equals the tile TileLoader(device_resize=True) makes of it."""
     from .datasets.assemble import resize_lanczos4_tiles
+    source, tabs = upload_source(raster, grid_hw, device)
+    return resize_lanczos4_tiles(source[None], *tabs, scale_mode)[0]
+
+
+def upload_source(raster: torch.Tensor, grid_hw: Tuple[int, int], device):
+    """The one upload of a scene -> (the raster fp32 [C, h, w] on the device, the four tap tables of
+    lanczos4_axis_window for the whole grid, each with resize_lanczos4_tiles' leading 1).  Both the resample and the
+    valid mask are taken from these."""
     from .datasets.resize import lanczos4_axis_window
     dev = torch.device(device)
     H, W = grid_hw
     iy, wy, _ = lanczos4_axis_window(raster.shape[1], H, 0, H, H)
     ix, wx, _ = lanczos4_axis_window(raster.shape[2], W, 0, W, W)
     tabs = [torch.from_numpy(t)[None].to(dev, non_blocking=True) for t in (iy, wy, ix, wx)]
-    return resize_lanczos4_tiles(raster[None].to(dev, non_blocking=True), *tabs, scale_mode)[0]
+    return raster.to(dev, non_blocking=True), tabs
 
 
 class SceneFiles(torch.utils.data.Dataset):
@@ -236,15 +263,32 @@ def scene_outputs(inputs: Sequence[str], out_dir: str, sensor: str) -> Tuple[Lis
     return paths, outs
 
 
-def upload_scene(item: dict, options: InferOptions, crop_hw: Tuple[int, int], device):
+def upload_scene(item: dict, options: InferOptions, crop_hw: Tuple[int, int], device, ctx=None):
     """A decoded scene (SceneFiles) -> (its index, the scene as it stays resident: its grid on the device, sizes, tags
-    and crop count, its crop boxes)."""
+    and crop count, its crop boxes).  With options.nodata the scene also holds "valid" (uint8 [H, W] on the device),
+    "n_valid" (int64 [1] there), "nodata" (the value used) and "skipped"; with skip_empty only the boxes with at least one
+    valid pixel are returned (one census launch through ctx, a zero-argument callable that gives the fu_ctx, and one
+    small read).  A scene left without a box keeps nothing on the device."""
+    from .datasets.assemble import resize_lanczos4_tiles
     raster = item["raster"]
     src_hw = (raster.shape[1], raster.shape[2])
     H, W = options.grid(src_hw)
-    grid = resident_grid(raster, int(item["scale_mode"]), (H, W), device)
+    source, tabs = upload_source(raster, (H, W), device)
+    grid = resize_lanczos4_tiles(source[None], *tabs, int(item["scale_mode"]))[0]
     boxes = crop_boxes(H, W, crop_hw[0], crop_hw[1], options.stride)
-    return int(item["index"]), {"grid": grid, "hw": (H, W), "src_hw": src_hw, "tags": item["tags"], "n": len(boxes)}, boxes
+    scene = {"grid": grid, "hw": (H, W), "src_hw": src_hw, "tags": item["tags"], "n": len(boxes)}
+    if options.nodata is not None:
+        from .datasets.valid_mask import box_valid_counts, scene_valid_mask
+        value = scene_nodata(options.nodata, item["tags"])
+        valid, n_valid = scene_valid_mask(source, value, tabs)
+        scene.update(valid=valid, n_valid=n_valid, nodata=value, skipped=0)
+        if options.skip_empty:
+            counts = box_valid_counts(ctx(), valid, boxes).cpu().tolist()
+            boxes = [b for b, c in zip(boxes, counts) if c > 0]
+            scene.update(skipped=scene["n"] - len(boxes), n=len(boxes))
+            if not boxes:
+                scene.update(grid=None, valid=None, n_valid=None)
+    return int(item["index"]), scene, boxes
 
 
 class SceneQueue:
@@ -252,7 +296,10 @@ class SceneQueue:
     -> (scene index, what stays resident of it, its crop boxes).  batches() yields lists of up to batch_size
     (scene index, box), in scene order and then box order, and uploads the next scene only while fewer than batch_size
     crops are pending; after a batch is stitched, stitched(batch) hands out the scenes it completed, in scene order,
-    and forgets them.  resident: scene index -> the uploaded scene; max_resident: the most there were at once."""
+    and forgets them.  resident: scene index -> the uploaded scene; max_resident: the most there were at once.
+    A scene whose box list is empty (all fill: it holds nothing on the device) never enters resident or a batch: it waits
+    in scene order -- uploads come in increasing scene index -- and stitched() hands it out as completed once no earlier
+    scene is in flight; after the last batch, stitched(()) hands out those that came behind the last crop."""
 
     def __init__(self, scenes: Iterable, upload: Callable, batch_size: int):
         self._scenes, self._upload, self._batch_size = iter(scenes), upload, int(batch_size)
@@ -260,6 +307,7 @@ class SceneQueue:
         self.max_resident = 0
         self._left: Dict[int, int] = {}                  # scene index -> crops not yet stitched
         self._pending: List[Tuple[int, tuple]] = []      # crops not yet run: (scene index, box)
+        self._empty: List[Tuple[int, object]] = []       # scenes without a box, not handed out yet
         self._exhausted = False
 
     def batches(self) -> Iterator[List[Tuple[int, tuple]]]:
@@ -267,6 +315,9 @@ class SceneQueue:
             while len(self._pending) < self._batch_size and not self._exhausted:
                 try:
                     i, scene, boxes = self._upload(next(self._scenes))
+                    if not boxes:
+                        self._empty.append((i, scene))
+                        continue
                     self.resident[i], self._left[i] = scene, len(boxes)
                     self._pending.extend((i, b) for b in boxes)
                 except StopIteration:
@@ -283,18 +334,51 @@ class SceneQueue:
         done = [i for i in self.resident if self._left[i] == 0]
         for i in done:
             del self._left[i]
-        return [(i, self.resident.pop(i)) for i in done]
+        out = [(i, self.resident.pop(i)) for i in done]
+        while self._empty and all(self._empty[0][0] < i for i in self.resident):
+            out.append(self._empty.pop(0))
+        return sorted(out, key=lambda t: t[0])
 
 
-def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: InferOptions) -> Dict[str, np.ndarray]:
+def empty_scene_arrays(scene: dict, n_classes: int, options: InferOptions) -> Dict[str, np.ndarray]:
+    """finalize_scene's arrays for a scene without a valid pixel, which never had a canvas: the class map all
+    nodata_out, zero side rasters, zero counts.  Host only."""
+    H, W = scene["hw"]
+    arrays = {"counts": np.zeros(n_classes, dtype=np.int64), "class": np.full((H, W), options.nodata_out, dtype=np.uint8),
+              "n_valid": np.zeros(1, dtype=np.int64)}
+    if options.write_probs == "u8":
+        arrays["probs"] = np.zeros((n_classes, H, W), dtype=np.uint8)
+    if options.write_margin:
+        arrays["margin"] = np.zeros((H, W), dtype=np.uint8)
+    if options.write_probs == "f32":
+        arrays["canvas"] = np.zeros((H, W, n_classes), dtype=np.float32)
+    if options.sieve is not None:
+        arrays["sieve"] = np.zeros(2, dtype=np.int64)
+    if options.write_valid:
+        arrays["valid"] = np.zeros((H, W), dtype=np.uint8)
+    if options.keep_probabilities:
+        arrays["kept"] = np.zeros((H, W, n_classes), dtype=np.float32)
+    return arrays
+
+
+def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: InferOptions,
+                   scene: Optional[dict] = None) -> Dict[str, np.ndarray]:
     """A stitched scene -> its host arrays, with one finalisation launch, the optional sieve (in place, on the same
     stream) and ONE device-to-host read: "counts" int64 [k], "class" uint8 [H, W], and as the options ask "probs" uint8
     [k, H, W], "margin" uint8 [H, W], "canvas" fp32 [H, W, k] (write_probs "f32"), "sieve" int64 [2].  With
-    keep_probabilities one more read: "kept", the canvas.  The scene's canvases are dropped."""
+    keep_probabilities one more read: "kept", the canvas.  The scene's canvases are dropped.  With options.nodata (scene:
+    the uploaded scene, which holds the mask) the finalisation is the masked one, the sieve freezes nodata_out, and the
+    read also carries "n_valid" int64 [1] and, with write_valid, "valid" uint8 [H, W]; a scene without a crop has no
+    canvas: empty_scene_arrays."""
     from .postprocess import sieve as sieve_map
     from .stitch import PackedRead
+    masked = options.nodata is not None
+    if masked and scene["n"] == 0:
+        return empty_scene_arrays(scene, len(class_values), options)
     maps = stitcher.combine_maps(key, class_values, probs=options.write_probs == "u8", margin=options.write_margin,
-                                 counts=True, threshold=None if options.threshold is None else options.threshold[:2])
+                                 counts=True, threshold=None if options.threshold is None else options.threshold[:2],
+                                 valid=scene["valid"] if masked else None,
+                                 nodata_value=options.nodata_out if masked else None)
     read = PackedRead()
     for name in ("counts", "class", "probs", "margin"):
         if name in maps:
@@ -303,8 +387,13 @@ def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: Inf
         read.add("canvas", maps["canvas"])
     if options.sieve is not None:
         min_pixels, connectivity, passes = options.sieve
-        _, stats = sieve_map(maps["class"], min_pixels, connectivity, passes=passes, out=maps["class"])
+        _, stats = sieve_map(maps["class"], min_pixels, connectivity, passes=passes, out=maps["class"],
+                             **({"frozen_value": options.nodata_out} if masked else {}))
         read.add("sieve", stats)
+    if masked:
+        read.add("n_valid", scene["n_valid"])
+        if options.write_valid:
+            read.add("valid", scene["valid"])
     arrays = read.read()
     if options.keep_probabilities:
         arrays["kept"] = maps["canvas"].cpu().numpy()
@@ -314,13 +403,23 @@ def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: Inf
 
 def write_scene(arrays: Dict[str, np.ndarray], scene: dict, options: InferOptions, path: str, out_path: str) -> dict:
     """Host only: write a scene's class map and the side rasters the options ask for from finalize_scene's arrays, with
-    the input's georeferencing on the output grid (scene: "tags", "src_hw", "hw", "n") -> its summary.json record."""
+    the input's georeferencing on the output grid (scene: "tags", "src_hw", "hw", "n") -> its summary.json record.  With
+    options.nodata (scene: also "nodata", "skipped"; arrays: also "n_valid") the class map carries GDAL_NODATA =
+    str(nodata_out) (tag 42113) beside the georeferencing -- the side rasters do not, 0 is a value there -- and
+    write_valid writes arrays["valid"] as <image>_valid.tif."""
     from .datasets.synthetic import write_strip_tiff
     H, W = scene["hw"]
     tags = geo_tags_for_grid(scene["tags"], scene["src_hw"], (H, W))
-    write_strip_tiff(out_path, arrays["class"], extra_tags=tags)
+    masked = options.nodata is not None
+    write_strip_tiff(out_path, arrays["class"],
+                     extra_tags=tags + [(42113, 2, str(options.nodata_out))] if masked else tags)
     rec = {"input": path, "output": out_path, "source_size": list(scene["src_hw"]), "grid_size": [H, W],
            "crops": scene["n"], "class_pixels": arrays["counts"].tolist()}
+    if masked:
+        rec.update(valid_pixels=int(arrays["n_valid"][0]), skipped_crops=int(scene["skipped"]), nodata=scene["nodata"])
+        if options.write_valid:
+            rec["valid"] = side_output_path(out_path, "valid")
+            write_strip_tiff(rec["valid"], arrays["valid"], extra_tags=tags)
     if options.write_probs == "u8":
         rec["probabilities"] = side_output_path(out_path, "prob")
         write_strip_tiff(rec["probabilities"], arrays["probs"], extra_tags=tags)
@@ -349,6 +448,10 @@ def run_summary(records: List[dict], n_crops: int, seconds: float, max_resident:
         summary["sieve"] = dict(options.sieve_options,
                                 merged_components=sum(r["sieve"]["merged_components"] for r in records),
                                 changed_pixels=sum(r["sieve"]["changed_pixels"] for r in records))
+    if options.nodata is not None:
+        summary["nodata"] = {"value": options.nodata, "out": options.nodata_out, "skip_empty": options.skip_empty,
+                             "valid_pixels": sum(r["valid_pixels"] for r in records),
+                             "skipped_crops": sum(r["skipped_crops"] for r in records)}
     return summary
 
 
@@ -360,7 +463,8 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     options: an InferOptions, or in its place the keywords of InferOptions.make (infer_options.KEYWORDS) -- size / scale,
     stride, batch_size, tta, weights ('auto', 'raw' or 'ema'), blend, write_probs (None, "u8" or "f32"), write_margin,
     sieve / sieve_connectivity / sieve_passes (only the written class map is sieved), water_threshold / threshold_class
-    / calibration (the one-versus-rest rule in place of the argmax), n_workers, device, keep_probabilities.  Returns the
+    / calibration (the one-versus-rest rule in place of the argmax), nodata / nodata_out / skip_empty / write_valid (the
+    valid-pixel mask, see the module docstring), n_workers, device, keep_probabilities.  Returns the
     summary.json dict, which records the weights served, the blend, the stride and, when set, "threshold" and "sieve";
     with keep_probabilities also "probabilities" {output path: fp32 [H, W, k] stitched canvas} (one more host read per
     scene; for tests and comparisons)."""
@@ -390,9 +494,17 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     crop_buf = torch.empty(options.batch_size, n_channels["ms_image"], ch, cw, dtype=torch.float32, device=dev)
     loader = torch.utils.data.DataLoader(SceneFiles(paths, sensor, channels), batch_size=None, shuffle=False,
                                          num_workers=options.n_workers, pin_memory=dev.type == "cuda")
-    queue = SceneQueue(loader, functools.partial(upload_scene, options=options, crop_hw=(ch, cw), device=dev),
-                       options.batch_size)
+    queue = SceneQueue(loader, functools.partial(upload_scene, options=options, crop_hw=(ch, cw), device=dev,
+                                                 ctx=lambda: net._ctx), options.batch_size)
     records, probabilities, n_crops = [], {}, 0
+
+    def finish(done):
+        for i, scene in done:
+            arrays = finalize_scene(stitcher, str(i), class_values, options, scene)
+            if options.keep_probabilities:
+                probabilities[outs[i]] = arrays.pop("kept")
+            records.append(write_scene(arrays, scene, options, paths[i], outs[i]))
+
     with torch.no_grad():
         for batch in queue.batches():
             scenes = [queue.resident[i] for i, _ in batch]
@@ -402,11 +514,8 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
             stitcher.add_images(range(len(batch)), [str(i) for i, _ in batch], [b for _, b in batch],
                                 [sc["hw"][0] for sc in scenes], [sc["hw"][1] for sc in scenes], probs=probs)
             n_crops += len(batch)
-            for i, scene in queue.stitched(batch):
-                arrays = finalize_scene(stitcher, str(i), class_values, options)
-                if options.keep_probabilities:
-                    probabilities[outs[i]] = arrays.pop("kept")
-                records.append(write_scene(arrays, scene, options, paths[i], outs[i]))
+            finish(queue.stitched(batch))
+        finish(queue.stitched(()))                       # all-fill scenes behind the last crop (none without --nodata)
 
     summary = run_summary(records, n_crops, time.perf_counter() - t_start, queue.max_resident, options, chosen)
     os.makedirs(out_dir, exist_ok=True)
@@ -453,6 +562,18 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--calibration", type=str, default=None, metavar="FILE",
                     help="take the class and its best-F1 threshold from a calibration.json written by predict --calibrate "
                          "(excludes --water_threshold / --threshold_class)")
+    ap.add_argument("--nodata", type=str, default=None, metavar="auto|V",
+                    help="treat pixels that hold no data as such: a pixel is fill when a band is not finite or every band "
+                         "equals V (auto: the scene's GDAL_NODATA tag, else 0).  Fill gets --nodata_out in the class map, 0 "
+                         "in the probability and margin rasters, is not counted in class_pixels, and crops that are all fill "
+                         "are not forwarded (default: off, every pixel is classified)")
+    ap.add_argument("--nodata_out", type=int, default=NODATA_OUT_DEFAULT, metavar="N",
+                    help="the class map's value of a pixel without data, in 1..254 (default 127); written as the class map's "
+                         "GDAL_NODATA tag.  Needs --nodata")
+    ap.add_argument("--keep_empty_crops", dest="skip_empty", action="store_false",
+                    help="forward also the crops without a single valid pixel (default: skip them).  Needs --nodata")
+    ap.add_argument("--write_valid", action="store_true",
+                    help="also write the valid-pixel mask as <image>_valid.tif, uint8 [H, W] 0 / 1.  Needs --nodata")
     ap.add_argument("--batch_size", type=int, default=None, help="crops per eval forward (default: the config's)")
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips / rotations")

@@ -17,7 +17,8 @@ PROB_FORMATS = ("u8", "f32")
 # the keywords of InferOptions.make, which are infer()'s option keywords and, but for keep_probabilities, its flags
 KEYWORDS = ("size", "scale", "stride", "batch_size", "tta", "n_workers", "device", "keep_probabilities", "weights",
             "blend", "write_probs", "write_margin", "sieve", "sieve_connectivity", "sieve_passes", "water_threshold",
-            "threshold_class", "calibration")
+            "threshold_class", "calibration", "nodata", "nodata_out", "skip_empty", "write_valid")
+NODATA_OUT_DEFAULT = 127                         # the class map's byte where the input holds no data
 
 
 def check_weights(weights) -> str:
@@ -84,12 +85,42 @@ def threshold_rule(water_threshold: Optional[float] = None, threshold_class: Opt
     return {"class": cls, "threshold": thr, "source": source}
 
 
+def check_nodata(nodata) -> Union[None, str, float]:
+    """--nodata: None (off), "auto" (the input's GDAL_NODATA tag, else 0) or a finite number (also as a string)."""
+    if nodata is None or nodata == "auto":
+        return nodata
+    try:
+        value = float(nodata)
+    except (TypeError, ValueError):
+        raise ValueError(f"infer: nodata must be 'auto' or a finite number, got {nodata!r}") from None
+    if isinstance(nodata, bool) or value != value or value in (float("inf"), float("-inf")):
+        raise ValueError(f"infer: nodata must be 'auto' or a finite number, got {nodata!r}")
+    return value
+
+
+def scene_nodata(nodata: Union[str, float], tags: dict) -> float:
+    """The value a scene's mask is taken with: the option's number, or under "auto" the scene's GDAL_NODATA tag (42113)
+    when it parses as a finite float, else 0."""
+    if nodata != "auto":
+        return float(nodata)
+    tag = tags.get(42113) if tags else None
+    if isinstance(tag, bytes):
+        tag = tag.decode("ascii", "replace")
+    try:
+        value = float(str(tag).strip().strip("\x00").strip()) if tag is not None else 0.0
+    except ValueError:
+        return 0.0
+    return value if value == value and value not in (float("inf"), float("-inf")) else 0.0
+
+
 @dataclasses.dataclass(frozen=True)
 class InferOptions:
     """size / scale: the output grid (grid_size); None, None: the raster's own.  stride and batch_size None: the
     default_stride of the crop and the config's batch size, set by resolve().  tta: None, a tta.VIEW_SETS name or a
     tuple of view codes; codes: its checked codes, set by resolve().  sieve: None or (min pixels, connectivity,
-    passes).  threshold: None (the argmax) or (class, threshold, source), threshold_rule's dict as a tuple."""
+    passes).  threshold: None (the argmax) or (class, threshold, source), threshold_rule's dict as a tuple.
+    A run without --nodata is this value, field for field what it always was; its four nodata attributes are the class
+    constants below (off).  A run with --nodata is a NodataInferOptions, which appends them as fields."""
     size: Optional[Tuple[int, int]] = None
     scale: Optional[float] = None
     stride: Optional[int] = None
@@ -105,14 +136,19 @@ class InferOptions:
     n_workers: int = 0
     device: str = "cuda:0"
     codes: Optional[Tuple[int, ...]] = None
+    nodata = None                        # not fields here: see NodataInferOptions
+    nodata_out = NODATA_OUT_DEFAULT
+    skip_empty = True
+    write_valid = False
 
     @classmethod
     def make(cls, *, size=None, scale=None, stride=None, batch_size=None, tta=None, n_workers=0, device="cuda:0",
              keep_probabilities=False, weights="auto", blend="uniform", write_probs=None, write_margin=False, sieve=None,
              sieve_connectivity=4, sieve_passes=1, water_threshold=None, threshold_class=None,
-             calibration=None) -> "InferOptions":
+             calibration=None, nodata=None, nodata_out=NODATA_OUT_DEFAULT, skip_empty=True,
+             write_valid=False) -> "InferOptions":
         """The options checked, in the order infer() always checked them: weights, blend, write_probs, the decision
-        rule (threshold_rule), the sieve (postprocess.check_sieve_options), an explicit stride, the grid."""
+        rule (threshold_rule), the sieve (postprocess.check_sieve_options), an explicit stride, the grid, nodata."""
         from .postprocess import check_sieve_options
         check_weights(weights)
         check_blend(blend)
@@ -125,12 +161,22 @@ class InferOptions:
             raise ValueError(f"infer: stride must be >= 1, got {int(stride)}")
         if size is not None or scale is not None:
             grid_size((1 << 20, 1 << 20), size, scale)
+        nodata = check_nodata(nodata)
+        if isinstance(nodata_out, bool) or int(nodata_out) != nodata_out or not 1 <= int(nodata_out) <= 254:
+            raise ValueError(f"infer: nodata_out must be an integer in 1..254, got {nodata_out!r}")
+        if nodata is None and (int(nodata_out) != NODATA_OUT_DEFAULT or not skip_empty or write_valid):
+            raise ValueError("infer: --nodata_out, --keep_empty_crops and --write_valid need --nodata")
+        extra = {}
+        if nodata is not None:
+            cls, extra = NodataInferOptions, dict(nodata=nodata, nodata_out=int(nodata_out), skip_empty=bool(skip_empty),
+                                                  write_valid=bool(write_valid))
         return cls(size=None if size is None else (int(size[0]), int(size[1])), scale=scale,
                    stride=None if stride is None else int(stride), batch_size=int(batch_size) if batch_size else None,
                    tta=tta if tta is None or isinstance(tta, str) else tuple(int(c) for c in tta), weights=weights,
                    blend=blend, write_probs=write_probs, write_margin=bool(write_margin), sieve=sieve,
                    threshold=None if rule is None else (rule["class"], rule["threshold"], rule["source"]),
-                   keep_probabilities=bool(keep_probabilities), n_workers=int(n_workers), device=str(device))
+                   keep_probabilities=bool(keep_probabilities), n_workers=int(n_workers), device=str(device),
+                   **extra)
 
     @classmethod
     def from_args(cls, args) -> "InferOptions":
@@ -167,3 +213,15 @@ class InferOptions:
     def sieve_options(self) -> Optional[dict]:
         """sieve under the names of the summary's "sieve"."""
         return None if self.sieve is None else dict(zip(("min_pixels", "connectivity", "passes"), self.sieve))
+
+
+@dataclasses.dataclass(frozen=True)
+class NodataInferOptions(InferOptions):
+    """InferOptions of a run with --nodata: the four nodata options appended after codes.  nodata: "auto" or a finite
+    float (scene_nodata gives a scene's value); nodata_out: the class map's value where the input holds no data, in
+    1..254; skip_empty: crops without a valid pixel are not forwarded; write_valid: also write <image>_valid.tif.
+    InferOptions.make builds it when nodata is given; resolve() keeps it."""
+    nodata: Union[None, str, float] = None
+    nodata_out: int = NODATA_OUT_DEFAULT
+    skip_empty: bool = True
+    write_valid: bool = False

@@ -133,7 +133,8 @@ class GpuImageStitcher:
 
     def combine_maps(self, image_name: str, class_values: Optional[Sequence[int]] = None, probs: bool = False,
                      margin: bool = False, counts: bool = False,
-                     threshold: Optional[Tuple[int, float]] = None) -> dict:
+                     threshold: Optional[Tuple[int, float]] = None, valid: Optional[torch.Tensor] = None,
+                     nodata_value: Optional[int] = None) -> dict:
         """The fused finalisation (fu_stitch_finalize_maps), one launch: the canvas is normalised in place -- by
         (weight + 1e-5) under "uniform" as combine() does, by the weight alone otherwise (the windows are strictly
         positive; 1e-5 would bias a corner pixel whose only weight is of that order) -- and the uint8 rasters come out
@@ -142,7 +143,10 @@ class GpuImageStitcher:
         of top-1 minus top-2, "counts": int64 [k] pixels per argmax class}, all on the device.  Call it once per image,
         instead of combine().  threshold=(cls, T): the class map and the counts follow the one-versus-rest rule of
         fu_stitch_finalize_maps_ex instead of the argmax -- cls where its normalised probability is >= T, else the
-        first maximum over the other classes; the other outputs do not change."""
+        first maximum over the other classes; the other outputs do not change.  valid (uint8 [H, W] on the device, with
+        nodata_value in 0..255 that is none of the class map's values): fu_stitch_finalize_maps_masked -- a pixel whose
+        byte is 0 comes out as an uncovered one (canvas, "probs", "margin" 0, not counted), with "class" =
+        nodata_value; without it the call and its results are what they were."""
         cv, wt = self.image_canvas[image_name], self.weight_canvas[image_name]
         H, W, k = cv.shape
         if class_values is not None:
@@ -161,9 +165,23 @@ class GpuImageStitcher:
         if threshold is not None:
             from .calibration import check_threshold
             thr = _lib.FuClassThreshold(*check_threshold(threshold[1], threshold[0], k))
-        check(_lib.load().fu_stitch_finalize_maps_ex(ptr(cv), ptr(wt), k, H, W, eps, 1, class_values, ptr(out["class"]),
-                                                     ptr(out.get("probs")), ptr(out.get("margin")), ptr(out.get("counts")),
-                                                     thr, torch.cuda.current_stream(self.device).cuda_stream))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if valid is None:
+            if nodata_value is not None:
+                raise ValueError("combine_maps: nodata_value comes with valid")
+            check(_lib.load().fu_stitch_finalize_maps_ex(ptr(cv), ptr(wt), k, H, W, eps, 1, class_values, ptr(out["class"]),
+                                                         ptr(out.get("probs")), ptr(out.get("margin")),
+                                                         ptr(out.get("counts")), thr, stream))
+            return out
+        if tuple(valid.shape) != (H, W) or valid.dtype != torch.uint8 or not valid.is_contiguous() \
+                or valid.device != cv.device:
+            raise ValueError(f"combine_maps: valid must be contiguous uint8 [{H}, {W}] on {cv.device}, got "
+                             f"{tuple(valid.shape)} {valid.dtype} on {valid.device}")
+        if nodata_value is None:
+            raise ValueError("combine_maps: valid needs nodata_value, the class map's byte of a pixel without data")
+        check(_lib.load().fu_stitch_finalize_maps_masked(ptr(cv), ptr(wt), k, H, W, eps, 1, class_values, ptr(out["class"]),
+                                                         ptr(out.get("probs")), ptr(out.get("margin")),
+                                                         ptr(out.get("counts")), thr, ptr(valid), int(nodata_value), stream))
         return out
 
     def drop(self, image_name: str) -> None:

@@ -20,6 +20,8 @@
  *   fu_loss_ce_region           (new) any of the three plus a soft Dice / Jaccard / Tversky region term over all classes
  *   fu_label_class_counts       (new) class frequencies of resident label rasters, for "balanced" weights
  *   fu_label_box_counts         (new) the label content of every box of a table, for content-aware tile sampling
+ *   fu_scene_valid_mask         (new) which pixels of a resident scene hold data, on its output grid, for infer --nodata
+ *   fu_mask_box_counts          (new) the valid pixels of every crop box of such a mask, so all-fill crops are not forwarded
  *   fu_backward[_block]         loss.backward() issued by Lightning's automatic optimisation
  *                                                                            st_water_seg/fit.py:95-97
  *   fu_adam_step                optim.Adam(self.parameters(), lr).step()     st_water_seg/models/water_seg_model.py:198-205
@@ -663,8 +665,46 @@ int fu_stitch_finalize_maps_ex(float* canvas, const float* weight, int n_classes
                                int normalize_in_place, const uint8_t* class_values, uint8_t* class_out, uint8_t* prob_out,
                                uint8_t* margin_out, int64_t* counts_out, const fu_class_threshold* thr, fu_stream stream);
 
-/* ---- class-map post-processing (fu_post.hip); no context needed --------------------------------- */
 #define FU_MAP_MAX_PIXELS (1 << 28)
+
+/* ---- nodata in scene inference (added within ABI 5: purely additive) ---------------------------- */
+/* fu_stitch_finalize_maps_ex with a valid-pixel mask.  valid == NULL: fu_stitch_finalize_maps_ex bit for bit (which
+ * forwards here; nodata_value is then not looked at).  Otherwise valid is a device uint8 [canvas_h, canvas_w], and a pixel
+ * with valid[p] == 0 is treated as the uncovered pixel is -- v[k] = 0, prob_out and margin_out 0, not counted in
+ * counts_out, normalised canvas 0 -- except that class_out = nodata_value.  One launch; the mask is one more byte per
+ * pixel.  Rejected, launching nothing and leaving every output untouched: what fu_stitch_finalize_maps_ex rejects, and with
+ * a mask a canvas that is empty or has more than FU_MAP_MAX_PIXELS pixels, a nodata_value outside 0..255, a nodata_value
+ * below n_classes when class_values == NULL, a nodata_value equal to one of class_values. */
+int fu_stitch_finalize_maps_masked(float* canvas, const float* weight, int n_classes, int canvas_h, int canvas_w, float eps,
+                                   int normalize_in_place, const uint8_t* class_values, uint8_t* class_out,
+                                   uint8_t* prob_out, uint8_t* margin_out, int64_t* counts_out,
+                                   const fu_class_threshold* thr, const uint8_t* valid, int nodata_value, fu_stream stream);
+
+/* The valid-pixel mask of a resident scene on its output grid (floodplanet_code_amd/datasets/valid_mask.py holds the numpy
+ * statements, source_valid_host then grid_valid_host; integer-exact).  raster: fp32 [C, src_h, src_w] as uploaded, before
+ * sensor scaling.  A source pixel is valid when every band is finite and, with use_nodata != 0, not every band == nodata
+ * (fp32 ==).  iy / wy [grid_h][8], ix / wx [grid_w][8]: the tables of fu_resize_lanczos4_tiles for the whole grid (B = 1);
+ * grid pixel (Y, X) is valid when every source pixel (iy[Y][a], ix[X][b]) with wy[Y][a] != 0 and wx[X][b] != 0 is valid;
+ * a tap index is clamped into the source before it is used.  src_valid: caller-owned scratch uint8 [src_h, src_w] (holds
+ * the source mask afterwards); valid_out: uint8 [grid_h, grid_w], 0 / 1; n_valid_out: int64 [1], WRITTEN (zeroed on
+ * `stream`, then one integer atomic per workgroup): the number of valid grid pixels.  Two launches, no host read.  Every
+ * argument is checked before anything is launched -- null pointers, C outside 1..16, a size < 1 or above
+ * FU_MAP_MAX_PIXELS pixels, a non-finite nodata with use_nodata -- and a rejected call leaves the outputs untouched. */
+int fu_scene_valid_mask(const float* raster, int C, int src_h, int src_w, int use_nodata, float nodata, const int32_t* iy,
+                        const float* wy, const int32_t* ix, const float* wx, int grid_h, int grid_w, uint8_t* src_valid,
+                        uint8_t* valid_out, int64_t* n_valid_out, fu_stream stream);
+
+/* The census of a table of boxes of byte masks, the twin of fu_label_box_counts: counts_out[i] (device int64 [n],
+ * caller-owned) is WRITTEN, not added to: the non-zero bytes of mask[h0:hE, w0:wE].  A box may be as large as its mask.
+ * One workgroup per box owns its cell: no global atomics, nothing to zero beforehand.  One launch.  `entries` is a host
+ * array; the table goes through the library-owned device buffer of fu_scene_crops, ordered on `stream`.  Every entry is
+ * checked before anything is copied or launched (n < 1, a null mask, a mask that is empty or above FU_MAP_MAX_PIXELS, a
+ * box that is empty or lies outside its mask): a rejected call launches nothing and leaves counts_out untouched. */
+typedef struct fu_mask_box { const uint8_t* mask; int32_t mask_h, mask_w; int32_t h0, w0, hE, wE; } fu_mask_box;
+int fu_mask_box_counts(fu_ctx* ctx, int n, const fu_mask_box* entries, int64_t* counts_out /* [n], WRITTEN */,
+                       fu_stream stream);
+
+/* ---- class-map post-processing (fu_post.hip); no context needed --------------------------------- */
 /* Connected components of a uint8 map [h, w] on the device: a component is a maximal set of pixels of equal value joined
  * through 4-neighbours (connectivity 4) or 8-neighbours (8).  labels_out int32 [h, w]: the smallest linear index y * w + x
  * of the pixel's component -- canonical, so two labellings compare bit for bit (postprocess.label_components_host is the
