@@ -620,6 +620,11 @@ int fu_mask_box_counts(fu_ctx* c, int n, const fu_mask_box* entries, int64_t* co
   return launch_mask_box_counts(c->scene_table, n, entries, counts_out, (hipStream_t)stream);
 }
 
+int fu_tiff_unpack(const uint8_t* src, int64_t n_bytes, fu_tiff_layout layout, const int32_t* bands, int n_bands, float* out,
+                   fu_stream stream) {
+  return launch_tiff_unpack(src, n_bytes, layout, bands, n_bands, out, (hipStream_t)stream);
+}
+
 int fu_eval_prob_hist(fu_ctx* c, const int64_t* target, int ignore_index, int n_bins, int64_t* hist_out, int64_t* top_out,
                       fu_stream stream) {
   FU_REQUIRE(c && target, "fu_eval_prob_hist: null context / target");

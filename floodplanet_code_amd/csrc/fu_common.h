@@ -15,6 +15,7 @@ struct fu_scene_train_entry;
 struct fu_scene_aug;
 struct fu_class_threshold;
 struct fu_mask_box;
+struct fu_tiff_layout;
 
 namespace fu {
 
@@ -609,6 +610,10 @@ int launch_scene_valid_mask(const float* raster, int C, int src_h, int src_w, bo
                             const float* wy, const int* ix, const float* wx, int grid_h, int grid_w,
                             unsigned char* src_valid, unsigned char* valid, int64_t* n_valid, hipStream_t s);
 int launch_mask_box_counts(DeviceTable& table, int n, const fu_mask_box* entries, int64_t* counts, hipStream_t s);
+// fu_tiff_unpack (fu_tiff_unpack.hip): the entropy-decoded segments of a TIFF -> fp32 [n_bands, height, width], one launch;
+// checks every argument (n_bytes against the layout's arithmetic total included) before it launches
+int launch_tiff_unpack(const uint8_t* src, int64_t n_bytes, const fu_tiff_layout& layout, const int32_t* bands, int n_bands,
+                       float* out, hipStream_t s);
 // fu_map_components / fu_map_sieve (fu_post.hip): union-find labelling of a uint8 map (the label of a pixel = the smallest
 // linear index of its component) and the connected-component sieve on top of it; the caller has checked every argument.
 // workspace: sieve_workspace_bytes(h, w) = 16 B per pixel (64-bit donor keys, labels, sizes); stats: int64[2] ADDED to, or null

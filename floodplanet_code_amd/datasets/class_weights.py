@@ -107,14 +107,14 @@ def dataset_label_boxes(dataset) -> List[Tuple[np.ndarray, Box]]:
     """The (raw uint8 label raster, box) of every example of a FloodplanetTiles split, each label file decoded once: the
     rasters SceneTileLoader keeps on the device and the boxes it cuts, on the host."""
     from .resize import resize_image
-    from .tiff import read_tiff
+    from .floodplanet import read_image
     rasters, out = {}, []
     for ex in dataset.dataset:
         cp = ex["crop_params"]
         H, W = cp.og_height, cp.og_width
         label = rasters.get(ex["label_path"])
         if label is None:
-            label = np.asarray(read_tiff(ex["label_path"]))
+            label = np.asarray(read_image(ex["label_path"]))
             if label.shape != (H, W):
                 label = resize_image(label, H, W, resize_mode="nearest")
             if label.dtype != np.uint8:      # only 0 and 2 are told apart from the rest: keep exactly that

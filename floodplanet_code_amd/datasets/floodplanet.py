@@ -7,7 +7,8 @@ crop of `get_crop_slices(label_h, label_w, ..., mode="exact")`), same per-sensor
 padding of edge crops to the nominal tile size (:271-325), and the item dict {image f32 [C,h,w], target i64 [h,w],
 mean, std [C,1,1]} (:644-648).
 
-Differences, all at the edges of the path: rasters are decoded by `datasets.tiff` (uncompressed strips only) and
+Differences, all at the edges of the path: rasters are decoded by `datasets.tiff` (uncompressed strips) or, where that
+reader rejects the file (tiles, compression, BigTIFF), by `datasets.geotiff.read_raster` (`read_image`), and
 resampled by `datasets.resize` (Lanczos-4 restated, parity unpinned); `transforms` must be None -- flips / rotations
 run on the GPU on whole batches (`floodplanet_code_amd.augment`, C ABI `fu_augment`) instead of per item on the CPU
 (base_dataset.py:494-555); norm_mode 'global' takes its parameters from the `norm_params` keyword (the reference's
@@ -25,13 +26,20 @@ import numpy as np
 import torch
 
 from .resize import lanczos4_axis_window, resize_image
-from .tiff import read_tiff, tiff_size
+from .geotiff import raster_size, read_raster, strict_reader_accepts
+from .tiff import read_tiff, tiff_size  # noqa: F401
 from .tiles import CropParams, get_crop_slices
 
-__all__ = ["FloodplanetTiles", "RawTileView", "collate_tiles", "collate_raw_tiles", "select_bands"]
+__all__ = ["FloodplanetTiles", "RawTileView", "collate_tiles", "collate_raw_tiles", "select_bands", "select_band_indices"]
 
 _N_CHANNELS = {"S2": {"RGB": 3, "RGB_NIR": 4, "ALL": 10}, "PS": {"RGB": 3, "RGB_NIR": 4, "ALL": 4},
                "S1": {"ALL": 2}, "L8": {"ALL": 7}}
+
+
+def read_image(path: str) -> np.ndarray:
+    """A file the strict reader takes goes through it, as always; a tiled, compressed or BigTIFF file through
+    geotiff.read_raster (the host statement), so such images and label rasters train too."""
+    return read_tiff(path) if strict_reader_accepts(path) else read_raster(path)
 
 
 def select_bands(image: np.ndarray, sensor: str, channels: str):
@@ -61,6 +69,45 @@ def select_bands(image: np.ndarray, sensor: str, channels: str):
     else:
         raise NotImplementedError(f'No loader for sensor "{s}"')
     return np.ascontiguousarray(image, dtype=np.float32), image.dtype == np.uint16
+
+
+def select_band_indices(shape, band_axis: int, sensor: str, channels: str):
+    """The band list select_bands picks, without the samples: for a decoded raster of this shape (read_tiff's
+    conventions: [bands, H, W] for planar-separate files, band_axis 0; [H, W, bands] for chunky ones, band_axis 2) ->
+    the file's sample indices in output order, so that select_bands(image)[0][n] == float32 of sample bands[n].  What
+    fu_tiff_unpack is given in place of running select_bands on the host.  ValueError where select_bands does not take
+    that axis for the bands (it follows the reference: S1 guesses the layout from the sizes, PS transposes always, S2 and
+    L8 never), so its output is not a band selection of the file."""
+    if len(shape) != 3 or band_axis not in (0, 2):
+        raise ValueError(f"select_band_indices: needs a multi-band raster [bands, H, W] or [H, W, bands], got shape {shape}")
+    s = sensor
+    if s == "S1":
+        if channels != "ALL":
+            raise NotImplementedError(f'No method to subselect S1 images with "{channels}" channel query.')
+        taken_axis, first, sel = (2 if shape[0] > shape[1] or shape[0] > shape[2] else 0), 2, None
+    elif s == "PS":
+        table = {"RGB": [2, 1, 0], "RGB_NIR": [2, 1, 0, 3], "ALL": None}
+        if channels not in table:
+            raise NotImplementedError(f'No method to subselect PS images with "{channels}" channel query.')
+        taken_axis, first, sel = 2, 4, table[channels]
+    elif s == "S2":
+        table = {"RGB": [3, 2, 1], "RGB_NIR": [3, 2, 1, 7], "ALL": None}
+        if channels not in table:
+            raise NotImplementedError(f'No method to subselect S2 images with "{channels}" channel query.')
+        taken_axis, first, sel = 0, None, table[channels]
+    elif s == "L8":
+        if channels != "ALL":
+            raise NotImplementedError(f'No method to subselect L8 images with "{channels}" channel query.')
+        taken_axis, first, sel = 0, None, None
+    else:
+        raise NotImplementedError(f'No loader for sensor "{s}"')
+    if taken_axis != band_axis:
+        raise ValueError(f"select_band_indices: select_bands takes axis {taken_axis} of a {s} raster of shape {tuple(shape)} "
+                         f"for its bands, the file's samples lie along axis {band_axis}")
+    n = shape[band_axis] if first is None else min(first, shape[band_axis])
+    if sel is not None and max(sel) >= n:
+        raise ValueError(f'select_band_indices: channel query "{channels}" needs band {max(sel)}, the raster has {n}')
+    return list(range(n)) if sel is None else list(sel)
 
 
 class FloodplanetTiles(torch.utils.data.Dataset):
@@ -114,7 +161,7 @@ class FloodplanetTiles(torch.utils.data.Dataset):
                 # bundled sample has 3 such images (US-Nebraska S1 x2, L8 x1): they are skipped and counted
                 self.skipped_without_label.append(image_path)
                 continue
-            label_height, label_width = tiff_size(label_path)
+            label_height, label_width = raster_size(label_path)
             if self.dem:
                 raise NotImplementedError(f'DEM finding not implemented for "{self.dset_name}" dataset.')
             if self.slope:
@@ -195,7 +242,7 @@ class FloodplanetTiles(torch.utils.data.Dataset):
         hit = self._raster_cache.get(key)
         if hit is not None:
             return hit
-        out = select_bands(read_tiff(image_path), self.sensor, channels)
+        out = select_bands(read_image(image_path), self.sensor, channels)
         if len(self._raster_cache) >= 8:
             self._raster_cache.pop(next(iter(self._raster_cache)))
         self._raster_cache[key] = out
@@ -203,7 +250,7 @@ class FloodplanetTiles(torch.utils.data.Dataset):
 
     def _load_norm_raster(self, image_path, channels, resize_dims):
         crop_params = None
-        image = read_tiff(image_path)
+        image = read_image(image_path)
         s = self.sensor
         if s == "S1":
             if image.ndim == 3 and (image.shape[0] > image.shape[1] or image.shape[0] > image.shape[2]):
@@ -248,7 +295,7 @@ class FloodplanetTiles(torch.utils.data.Dataset):
         key = ("label", label_path, desired_height, desired_width)
         label = self._raster_cache.get(key)
         if label is None:
-            label = read_tiff(label_path)
+            label = read_image(label_path)
             if label.shape != (desired_height, desired_width):
                 label = resize_image(label, desired_height, desired_width, resize_mode="nearest")
             if len(self._raster_cache) >= 8:

@@ -86,12 +86,12 @@ def resident_bytes(dataset) -> int:
     """Device bytes the data set's scenes occupy once resident, from the TIFF headers alone: per scene the fp32 grid
     [C, label_h, label_w] and the uint8 label raster, plus the largest source raster (it is on the device only while its
     scene is resampled)."""
-    from .tiff import tiff_size
+    from .geotiff import raster_size
     C = dataset.n_channels["ms_image"]
     total = transient = 0
     for image_path, _, H, W in _scene_list(dataset):
         total += C * H * W * 4 + H * W
-        h, w = tiff_size(image_path)
+        h, w = raster_size(image_path)
         transient = max(transient, C * h * w * 4)
     return total + transient
 
@@ -106,12 +106,11 @@ class _SceneRasters(torch.utils.data.Dataset):
         return len(self.scenes)
 
     def __getitem__(self, i):
-        from . import tiff
         from ..infer import SCALE_MODES
-        from .floodplanet import select_bands
+        from .floodplanet import read_image, select_bands
         image_path, label_path, H, W = self.scenes[i]
-        raster, was_u16 = select_bands(tiff.read_tiff(image_path), self.sensor, self.channels)
-        label = np.asarray(tiff.read_tiff(label_path))
+        raster, was_u16 = select_bands(read_image(image_path), self.sensor, self.channels)
+        label = np.asarray(read_image(label_path))
         if label.shape != (H, W):
             raise ValueError(f"label raster {label_path} is {label.shape}, its header says {(H, W)}")
         if label.dtype != np.uint8:      # only 0 and 2 are told apart from the rest: keep exactly that

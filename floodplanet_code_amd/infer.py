@@ -54,6 +54,16 @@ else the parent directory.  What runs differently:
     exactly as without the option, so a valid pixel's probabilities are the same with and without --nodata; the
     resampling is not mask-aware; predict (labelled evaluation) and training are not touched.  Without --nodata nothing
     of this runs and every file is byte for byte what it was.
+  * extension: scenes need not be classic uncompressed strip TIFFs.  datasets/geotiff.py reads classic and BigTIFF, strips
+    and tiles, Deflate / LZW / PackBits, predictors 2 and 3, and with them the georeferencing and GDAL_NODATA of a BigTIFF
+    scene.  --decode auto|host|device (InferOptions.decode) says where the samples are unpacked: under auto, the default, a
+    file the strict reader takes goes exactly the way it always went -- nothing new runs, every output byte is what it
+    was -- and every other file is entropy-decoded on the host (--decode_threads threads, default 4) and its bytes are
+    uploaded as stored and unpacked by ONE kernel launch (fu_tiff_unpack: predictor, byte swap, tiles, band choice,
+    conversion) into the very fp32 tensor the host route uploads; device does so for every file, host puts every file
+    through the numpy statement.  Everything behind that tensor is the same code, so the routes write identical files.
+    Out of scope: writing compressed or BigTIFF outputs, JPEG / ZSTD / LERC, sub-byte samples, overviews and mask IFDs
+    (the first IFD is the scene), entropy decoding on the GPU.
 How infer() is put together: the options travel as one checked InferOptions (infer_options.py; the keywords of infer() and
 the command line both go through InferOptions.make); predict.load_eval_model serves the model; a SceneQueue owns the
 scenes in flight and deals their crops out in batches; per batch scene_crops, predict.eval_forward and one batched stitch;
@@ -74,8 +84,9 @@ from typing import Callable, Dict, Iterable, Iterator, List, Optional, Sequence,
 import numpy as np
 import torch
 
-from .infer_options import (BLEND_KINDS, NODATA_OUT_DEFAULT, PROB_FORMATS, WEIGHT_CHOICES, InferOptions,  # noqa: F401
-                            default_stride, grid_size, scene_nodata, threshold_rule)
+from .infer_options import (BLEND_KINDS, DECODE_CHOICES, DECODE_THREADS_DEFAULT, NODATA_OUT_DEFAULT,  # noqa: F401
+                            PROB_FORMATS, WEIGHT_CHOICES, InferOptions, default_stride, grid_size, scene_nodata,
+                            threshold_rule)
 from .predict import CONFIG_DEFAULTS, _merge, eval_forward, load_eval_model, resolve_cfg
 from .tta import VIEW_SETS, recorded
 
@@ -188,35 +199,64 @@ def resident_grid(raster: torch.Tensor, scale_mode: int, grid_hw: Tuple[int, int
     return resize_lanczos4_tiles(source[None], *tabs, scale_mode)[0]
 
 
-def upload_source(raster: torch.Tensor, grid_hw: Tuple[int, int], device):
+def upload_source(raster, grid_hw: Tuple[int, int], device):
     """The one upload of a scene -> (the raster fp32 [C, h, w] on the device, the four tap tables of
     lanczos4_axis_window for the whole grid, each with resize_lanczos4_tiles' leading 1).  Both the resample and the
-    valid mask are taken from these."""
+    valid mask are taken from these.  raster: the band-selected fp32 tensor, or the encoded item of SceneFiles
+    ({"encoded", "layout", "bands"}): its bytes are uploaded as stored and unpacked there (geotiff.unpack_on_device, one
+    launch) into the same tensor."""
+    from .datasets import geotiff
     from .datasets.resize import lanczos4_axis_window
     dev = torch.device(device)
     H, W = grid_hw
-    iy, wy, _ = lanczos4_axis_window(raster.shape[1], H, 0, H, H)
-    ix, wx, _ = lanczos4_axis_window(raster.shape[2], W, 0, W, W)
+    encoded = isinstance(raster, dict)
+    h, w = (int(raster["layout"]["height"]), int(raster["layout"]["width"])) if encoded else raster.shape[1:]
+    iy, wy, _ = lanczos4_axis_window(h, H, 0, H, H)
+    ix, wx, _ = lanczos4_axis_window(w, W, 0, W, W)
     tabs = [torch.from_numpy(t)[None].to(dev, non_blocking=True) for t in (iy, wy, ix, wx)]
+    if encoded:
+        return geotiff.unpack_on_device(raster["encoded"], raster["layout"], raster["bands"], dev), tabs
     return raster.to(dev, non_blocking=True), tabs
 
 
 class SceneFiles(torch.utils.data.Dataset):
-    """Scene i of the input list, decoded: {"raster": fp32 [C, h, w] after band selection, "scale_mode", "tags", "index"}."""
+    """Scene i of the input list, decoded: {"raster": fp32 [C, h, w] after band selection, "scale_mode", "tags", "index"},
+    or, on the device route, entropy-decoded only: {"encoded": uint8 [n] (geotiff.read_raster_encoded), "layout", "bands"
+    (select_band_indices), "scale_mode", "tags", "index"} -- the host neither widens, transposes nor selects.  decode:
+    "auto" -- a file the strict reader takes (classic, strips, uncompressed) gives the first item through that reader, as
+    always, every other file the second; "host" -- the first item for every file, through geotiff.read_raster; "device" --
+    the second for every file."""
 
-    def __init__(self, paths: Sequence[str], sensor: str, channels: str):
+    def __init__(self, paths: Sequence[str], sensor: str, channels: str, decode: str = "auto", decode_threads: int = 4):
+        from .infer_options import check_decode
         self.paths, self.sensor, self.channels = list(paths), sensor, channels
+        self.decode, self.decode_threads = check_decode(decode, decode_threads)
 
     def __len__(self):
         return len(self.paths)
 
     def __getitem__(self, i):
-        from .datasets.floodplanet import select_bands
-        from .datasets.tiff import read_geotiff_tags, read_tiff
-        raster, was_u16 = select_bands(read_tiff(self.paths[i]), self.sensor, self.channels)
+        from .datasets import geotiff
+        from .datasets.floodplanet import select_band_indices, select_bands
+        from .datasets.tiff import read_tiff
+        path = self.paths[i]
+        tags = geotiff.raster_geotiff_tags(path)
+        route = self.decode
+        if route == "auto":
+            route = "strict" if geotiff.strict_reader_accepts(path) else "device"
+        if route == "device":
+            encoded, layout = geotiff.read_raster_encoded(path, self.decode_threads)
+            h, w, n = layout["height"], layout["width"], layout["samples"]
+            shape, axis = ((h, w), 0) if n == 1 else ((n, h, w), 0) if layout["planar"] else ((h, w, n), 2)
+            bands = select_band_indices(shape, axis, self.sensor, self.channels)
+            was_u16 = layout["sample_kind"] == 1 and layout["bytes_per_sample"] == 2
+            mode = SCALE_MODES.get(self.sensor, 4 if was_u16 else 0)
+            return {"encoded": torch.from_numpy(encoded), "layout": layout, "bands": bands, "scale_mode": mode,
+                    "tags": tags, "index": i}
+        image = read_tiff(path) if route == "strict" else geotiff.read_raster(path, self.decode_threads)
+        raster, was_u16 = select_bands(image, self.sensor, self.channels)
         mode = SCALE_MODES.get(self.sensor, 4 if was_u16 else 0)
-        return {"raster": torch.from_numpy(raster), "scale_mode": mode, "tags": read_geotiff_tags(self.paths[i]),
-                "index": i}
+        return {"raster": torch.from_numpy(raster), "scale_mode": mode, "tags": tags, "index": i}
 
 
 def check_model_inputs(cfg: dict, norm_params=None) -> None:
@@ -264,14 +304,18 @@ def scene_outputs(inputs: Sequence[str], out_dir: str, sensor: str) -> Tuple[Lis
 
 
 def upload_scene(item: dict, options: InferOptions, crop_hw: Tuple[int, int], device, ctx=None):
-    """A decoded scene (SceneFiles) -> (its index, the scene as it stays resident: its grid on the device, sizes, tags
-    and crop count, its crop boxes).  With options.nodata the scene also holds "valid" (uint8 [H, W] on the device),
+    """A decoded scene (SceneFiles, either item) -> (its index, the scene as it stays resident: its grid on the device,
+    sizes, tags and crop count, its crop boxes).  With options.nodata the scene also holds "valid" (uint8 [H, W] on the device),
     "n_valid" (int64 [1] there), "nodata" (the value used) and "skipped"; with skip_empty only the boxes with at least one
     valid pixel are returned (one census launch through ctx, a zero-argument callable that gives the fu_ctx, and one
     small read).  A scene left without a box keeps nothing on the device."""
     from .datasets.assemble import resize_lanczos4_tiles
-    raster = item["raster"]
-    src_hw = (raster.shape[1], raster.shape[2])
+    if "encoded" in item:                                # the device route: upload_source unpacks the bytes there
+        raster = item
+        src_hw = (int(item["layout"]["height"]), int(item["layout"]["width"]))
+    else:
+        raster = item["raster"]
+        src_hw = (raster.shape[1], raster.shape[2])
     H, W = options.grid(src_hw)
     source, tabs = upload_source(raster, (H, W), device)
     grid = resize_lanczos4_tiles(source[None], *tabs, int(item["scale_mode"]))[0]
@@ -464,7 +508,8 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     stride, batch_size, tta, weights ('auto', 'raw' or 'ema'), blend, write_probs (None, "u8" or "f32"), write_margin,
     sieve / sieve_connectivity / sieve_passes (only the written class map is sieved), water_threshold / threshold_class
     / calibration (the one-versus-rest rule in place of the argmax), nodata / nodata_out / skip_empty / write_valid (the
-    valid-pixel mask, see the module docstring), n_workers, device, keep_probabilities.  Returns the
+    valid-pixel mask, see the module docstring), decode / decode_threads (where a scene's samples are unpacked),
+    n_workers, device, keep_probabilities.  Returns the
     summary.json dict, which records the weights served, the blend, the stride and, when set, "threshold" and "sieve";
     with keep_probabilities also "probabilities" {output path: fp32 [H, W, k] stitched canvas} (one more host read per
     scene; for tests and comparisons)."""
@@ -492,7 +537,8 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     stitcher = GpuImageStitcher(net, dev, blend=options.blend)
     class_values = [0] + [255] * (net.n_classes - 1)     # clip(argmax, 0, 1) * 255
     crop_buf = torch.empty(options.batch_size, n_channels["ms_image"], ch, cw, dtype=torch.float32, device=dev)
-    loader = torch.utils.data.DataLoader(SceneFiles(paths, sensor, channels), batch_size=None, shuffle=False,
+    loader = torch.utils.data.DataLoader(SceneFiles(paths, sensor, channels, options.decode, options.decode_threads),
+                                         batch_size=None, shuffle=False,
                                          num_workers=options.n_workers, pin_memory=dev.type == "cuda")
     queue = SceneQueue(loader, functools.partial(upload_scene, options=options, crop_hw=(ch, cw), device=dev,
                                                  ctx=lambda: net._ctx), options.batch_size)
@@ -574,6 +620,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="forward also the crops without a single valid pixel (default: skip them).  Needs --nodata")
     ap.add_argument("--write_valid", action="store_true",
                     help="also write the valid-pixel mask as <image>_valid.tif, uint8 [H, W] 0 / 1.  Needs --nodata")
+    ap.add_argument("--decode", type=str, default="auto", choices=list(DECODE_CHOICES),
+                    help="how a scene's samples reach the device.  auto (the default): a classic, uncompressed strip TIFF "
+                         "is decoded on the host as always, every other file (tiles, Deflate / LZW / PackBits, predictors, "
+                         "BigTIFF) is entropy-decoded on the host and unpacked on the device; device: every file that way; "
+                         "host: every file through the numpy reader")
+    ap.add_argument("--decode_threads", type=int, default=DECODE_THREADS_DEFAULT,
+                    help="threads that inflate a scene's tiles or strips, 1..16 (default 4)")
     ap.add_argument("--batch_size", type=int, default=None, help="crops per eval forward (default: the config's)")
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips / rotations")

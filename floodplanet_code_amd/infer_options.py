@@ -17,8 +17,11 @@ PROB_FORMATS = ("u8", "f32")
 # the keywords of InferOptions.make, which are infer()'s option keywords and, but for keep_probabilities, its flags
 KEYWORDS = ("size", "scale", "stride", "batch_size", "tta", "n_workers", "device", "keep_probabilities", "weights",
             "blend", "write_probs", "write_margin", "sieve", "sieve_connectivity", "sieve_passes", "water_threshold",
-            "threshold_class", "calibration", "nodata", "nodata_out", "skip_empty", "write_valid")
+            "threshold_class", "calibration", "nodata", "nodata_out", "skip_empty", "write_valid", "decode",
+            "decode_threads")
 NODATA_OUT_DEFAULT = 127                         # the class map's byte where the input holds no data
+DECODE_CHOICES = ("auto", "host", "device")      # how a scene's samples reach the device (infer.SceneFiles)
+DECODE_THREADS_DEFAULT, DECODE_THREADS_MAX = 4, 16   # datasets/geotiff.py's; never sized from the machine's CPU count
 
 
 def check_weights(weights) -> str:
@@ -113,6 +116,16 @@ def scene_nodata(nodata: Union[str, float], tags: dict) -> float:
     return value if value == value and value not in (float("inf"), float("-inf")) else 0.0
 
 
+def check_decode(decode, decode_threads) -> Tuple[str, int]:
+    """--decode auto|host|device and --decode_threads 1..16 (the segment decoders' thread pool)."""
+    if decode not in DECODE_CHOICES:
+        raise ValueError(f"infer: decode must be one of {list(DECODE_CHOICES)}, got {decode!r}")
+    if isinstance(decode_threads, bool) or not isinstance(decode_threads, (int, float)) or \
+            int(decode_threads) != decode_threads or not 1 <= int(decode_threads) <= DECODE_THREADS_MAX:
+        raise ValueError(f"infer: decode_threads must be an integer in 1..{DECODE_THREADS_MAX}, got {decode_threads!r}")
+    return decode, int(decode_threads)
+
+
 @dataclasses.dataclass(frozen=True)
 class InferOptions:
     """size / scale: the output grid (grid_size); None, None: the raster's own.  stride and batch_size None: the
@@ -120,7 +133,10 @@ class InferOptions:
     tuple of view codes; codes: its checked codes, set by resolve().  sieve: None or (min pixels, connectivity,
     passes).  threshold: None (the argmax) or (class, threshold, source), threshold_rule's dict as a tuple.
     A run without --nodata is this value, field for field what it always was; its four nodata attributes are the class
-    constants below (off).  A run with --nodata is a NodataInferOptions, which appends them as fields."""
+    constants below (off).  A run with --nodata is a NodataInferOptions, which appends them as fields.  Likewise decode
+    ("auto": a file the strict TIFF reader takes goes the way it always went, every other file is unpacked on the
+    device) and decode_threads: class constants here, fields of DecodeInferOptions / NodataDecodeInferOptions when either
+    differs from its default."""
     size: Optional[Tuple[int, int]] = None
     scale: Optional[float] = None
     stride: Optional[int] = None
@@ -140,15 +156,17 @@ class InferOptions:
     nodata_out = NODATA_OUT_DEFAULT
     skip_empty = True
     write_valid = False
+    decode = "auto"                      # not fields here: see DecodeInferOptions
+    decode_threads = DECODE_THREADS_DEFAULT
 
     @classmethod
     def make(cls, *, size=None, scale=None, stride=None, batch_size=None, tta=None, n_workers=0, device="cuda:0",
              keep_probabilities=False, weights="auto", blend="uniform", write_probs=None, write_margin=False, sieve=None,
              sieve_connectivity=4, sieve_passes=1, water_threshold=None, threshold_class=None,
              calibration=None, nodata=None, nodata_out=NODATA_OUT_DEFAULT, skip_empty=True,
-             write_valid=False) -> "InferOptions":
+             write_valid=False, decode="auto", decode_threads=DECODE_THREADS_DEFAULT) -> "InferOptions":
         """The options checked, in the order infer() always checked them: weights, blend, write_probs, the decision
-        rule (threshold_rule), the sieve (postprocess.check_sieve_options), an explicit stride, the grid, nodata."""
+        rule (threshold_rule), the sieve (postprocess.check_sieve_options), an explicit stride, the grid, nodata, decode."""
         from .postprocess import check_sieve_options
         check_weights(weights)
         check_blend(blend)
@@ -170,6 +188,10 @@ class InferOptions:
         if nodata is not None:
             cls, extra = NodataInferOptions, dict(nodata=nodata, nodata_out=int(nodata_out), skip_empty=bool(skip_empty),
                                                   write_valid=bool(write_valid))
+        decode, decode_threads = check_decode(decode, decode_threads)
+        if (decode, decode_threads) != ("auto", DECODE_THREADS_DEFAULT):
+            cls = NodataDecodeInferOptions if nodata is not None else DecodeInferOptions
+            extra.update(decode=decode, decode_threads=decode_threads)
         return cls(size=None if size is None else (int(size[0]), int(size[1])), scale=scale,
                    stride=None if stride is None else int(stride), batch_size=int(batch_size) if batch_size else None,
                    tta=tta if tta is None or isinstance(tta, str) else tuple(int(c) for c in tta), weights=weights,
@@ -225,3 +247,19 @@ class NodataInferOptions(InferOptions):
     nodata_out: int = NODATA_OUT_DEFAULT
     skip_empty: bool = True
     write_valid: bool = False
+
+
+@dataclasses.dataclass(frozen=True)
+class DecodeInferOptions(InferOptions):
+    """InferOptions of a run whose --decode or --decode_threads is not the default, appended after codes.  decode: "auto",
+    "host" (datasets/geotiff.py's numpy statement for every file) or "device" (every file through fu_tiff_unpack);
+    decode_threads: the segment decoders' thread pool, 1..16."""
+    decode: str = "auto"
+    decode_threads: int = DECODE_THREADS_DEFAULT
+
+
+@dataclasses.dataclass(frozen=True)
+class NodataDecodeInferOptions(NodataInferOptions):
+    """Both: the nodata fields, then the decode fields."""
+    decode: str = "auto"
+    decode_threads: int = DECODE_THREADS_DEFAULT

@@ -22,6 +22,10 @@
  *   fu_label_box_counts         (new) the label content of every box of a table, for content-aware tile sampling
  *   fu_scene_valid_mask         (new) which pixels of a resident scene hold data, on its output grid, for infer --nodata
  *   fu_mask_box_counts          (new) the valid pixels of every crop box of such a mask, so all-fill crops are not forwarded
+ *   fu_tiff_unpack              (new) decoded TIFF segments -> the fp32 band raster, on the device: predictor, byte swap,
+ *                               tiles, band choice and conversion in one launch (tifffile.imread + the host's astype)
+ *   fu_tiff_lzw_decode /        (new) the host's LZW and PackBits decoders in front of it
+ *   fu_tiff_packbits_decode
  *   fu_backward[_block]         loss.backward() issued by Lightning's automatic optimisation
  *                                                                            st_water_seg/fit.py:95-97
  *   fu_adam_step                optim.Adam(self.parameters(), lr).step()     st_water_seg/models/water_seg_model.py:198-205
@@ -703,6 +707,50 @@ int fu_scene_valid_mask(const float* raster, int C, int src_h, int src_w, int us
 typedef struct fu_mask_box { const uint8_t* mask; int32_t mask_h, mask_w; int32_t h0, w0, hE, wE; } fu_mask_box;
 int fu_mask_box_counts(fu_ctx* ctx, int n, const fu_mask_box* entries, int64_t* counts_out /* [n], WRITTEN */,
                        fu_stream stream);
+
+/* ---- tiled / compressed / BigTIFF scenes (added within ABI 5: purely additive); no context needed ---- */
+/* The host's entropy decoders (csrc/fu_tiff_codec.cpp: plain C++, no HIP call -- using them never opens the GPU).  Both
+ * read src[0, n_src) only and write dst[0, n_dst) only, on any input: they stop at n_dst or at the end of the stream and
+ * return the bytes written (fewer than n_dst when the stream ends first), or a negative code: -1 a null buffer or negative
+ * size, -2 a corrupt stream (a code that cannot occur; a PackBits run cut off), -3 the LSB-first LZW of old writers.
+ * LZW is TIFF 6.0's: MSB-first codes of 9 to 12 bits, Clear 256, EndOfInformation 257, the width growing one code early,
+ * the code-equals-next-free-entry case.  floodplanet_code_amd/datasets/geotiff.py holds the Python statements
+ * (lzw_decode_host, packbits_decode_host). */
+int64_t fu_tiff_lzw_decode(const uint8_t* src, int64_t n_src, uint8_t* dst, int64_t n_dst);
+int64_t fu_tiff_packbits_decode(const uint8_t* src, int64_t n_src, uint8_t* dst, int64_t n_dst);
+
+#define FU_TIFF_MAX_BANDS 16
+#define FU_TIFF_UNPACK_CHUNK 256 /* pixels of a segment row a wave takes per pass; longer rows carry the scan along */
+enum fu_tiff_sample_kind { FU_TIFF_UINT = 1, FU_TIFF_INT = 2, FU_TIFF_FLOAT = 3 }; /* TIFF SampleFormat */
+/* How the decoded segments of a TIFF's first image lie in one buffer.  Segments follow each other in the order of the
+ * file's offset array (PlanarConfiguration 2: plane after plane), each at its nominal size: a tile is always seg_h x seg_w
+ * (an edge tile is full size; what lies outside the image is dropped), strip s holds min(seg_h, height - s * seg_h) rows of
+ * the image's width.  So every offset is arithmetic and no table is needed. */
+typedef struct fu_tiff_layout {
+  int32_t width, height;
+  int32_t samples;          /* samples per pixel, 1..64 */
+  int32_t bytes_per_sample; /* 1, 2, 4 or 8 */
+  int32_t sample_kind;      /* enum fu_tiff_sample_kind */
+  int32_t big_endian;       /* the file's byte order is MM */
+  int32_t planar;           /* PlanarConfiguration 2: one plane of segments per sample */
+  int32_t tiled;            /* segments are tiles (0: strips, seg_w == width, seg_h = RowsPerStrip) */
+  int32_t seg_w, seg_h;
+  int32_t predictor;        /* 1 none, 2 horizontal differencing (integers), 3 floating point (IEEE samples) */
+  int32_t reserved;         /* 0 */
+} fu_tiff_layout;
+/* Decoded segments -> out fp32 [n_bands, height, width], out[n] = sample bands[n] (host array, n_bands in
+ * 1..FU_TIFF_MAX_BANDS, output order; an index may repeat): undo the predictor, swap bytes, take tiles apart, pick bands,
+ * convert -- bit for bit np.float32 of datasets/geotiff.py's read_raster: 8- and 16-bit integers exactly, 32- and 64-bit
+ * integers and float64 rounded to nearest even (subnormal results kept), float32 copied bit for bit.  Predictor 2 sums
+ * modulo 2^bits after the byte swap, per sample component, per segment row; predictor 3 sums bytes modulo 2^8 with stride
+ * samples-per-pixel-in-the-segment along the row, whose byte b (most significant first) of value i is then byte
+ * b * (seg_w * samples in the segment) + i, in both byte orders.  src: device, 8-byte aligned, n_bytes long.  ONE launch
+ * (a wave per segment row, wave-level scan with a carry along the row; under predictor 3 the row is read twice, the plane
+ * totals first), no atomics, no host read.  Every argument is checked first -- null pointers, sizes (an image or segment
+ * above FU_MAP_MAX_PIXELS pixels), n_bytes != the layout's arithmetic total, a band index >= samples, predictor 3 on
+ * integers, predictor 2 on floats -- and a rejected call launches nothing and leaves out untouched. */
+int fu_tiff_unpack(const uint8_t* src, int64_t n_bytes, fu_tiff_layout layout, const int32_t* bands, int n_bands, float* out,
+                   fu_stream stream);
 
 /* ---- class-map post-processing (fu_post.hip); no context needed --------------------------------- */
 /* Connected components of a uint8 map [h, w] on the device: a component is a maximal set of pixels of equal value joined
