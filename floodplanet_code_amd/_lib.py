@@ -241,6 +241,10 @@ SIGNATURES = {
     "fu_sieve_workspace_bytes": (_i64, [_i, _i]),
     "fu_map_components": (_i, [_p, _i, _i, _i, _p, _p]),
     "fu_map_sieve": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _i64, _p, _p]),
+    "fu_map_edges_workspace_bytes": (_i64, [_i, _i]),
+    "fu_map_edge_offsets": (_i, [_p, _i, _i, _p, _p, _p, _i64, _p]),
+    "fu_map_rings_workspace_bytes": (_i64, [_i64]),
+    "fu_map_edge_rings": (_i, [_p, _p, _i, _i, _p, _i, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "fu_augment": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i64, _p]),
     "fu_scene_crops": (_i, [_p, _i, C.POINTER(FuSceneCrop), _i, _i, _i, _i, _p, _p, _f, _p, _p, _p, _p]),
     "fu_scene_train_tiles": (_i, [_p, _i, C.POINTER(FuSceneTrainEntry), _i, _i, _i, _i, _p, _p, _f, _i64, _i64, _p, _p, _p, _p,

@@ -670,6 +670,22 @@ int fu_map_sieve(const uint8_t* map, uint8_t* out, int h, int w, int connectivit
                           (hipStream_t)stream);
 }
 
+int64_t fu_map_edges_workspace_bytes(int h, int w) { return map_edges_workspace_bytes(h, w); }
+
+int fu_map_edge_offsets(const uint8_t* map, int h, int w, const uint8_t* select, int32_t* offsets_out, void* workspace,
+                        int64_t workspace_bytes, fu_stream stream) {
+  return launch_map_edge_offsets(map, h, w, select, offsets_out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int64_t fu_map_rings_workspace_bytes(int64_t capacity) { return map_rings_workspace_bytes(capacity); }
+
+int fu_map_edge_rings(const uint8_t* map, const int32_t* labels, int h, int w, const uint8_t* select, int connectivity,
+                      const int32_t* offsets, int64_t capacity, int32_t* start_out, int32_t* comp_out, int32_t* ring_out,
+                      int32_t* rank_out, int32_t* flags_out, void* workspace, int64_t workspace_bytes, fu_stream stream) {
+  return launch_map_edge_rings(map, labels, h, w, select, connectivity, offsets, capacity, start_out, comp_out, ring_out,
+                               rank_out, flags_out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int fu_augment(const float* image, const int64_t* target, float* image_out, int64_t* target_out, const int32_t* flags,
                const float* angles_deg, int B, int C, int H, int W, int64_t target_fill, fu_stream stream) {
   FU_REQUIRE(image && image_out && flags && angles_deg, "fu_augment: null argument");

@@ -621,6 +621,16 @@ int64_t sieve_workspace_bytes(int h, int w);
 int launch_map_components(const unsigned char* map, int h, int w, int connectivity, int* labels, hipStream_t s);
 int launch_map_sieve(const unsigned char* map, unsigned char* out, int h, int w, int connectivity, int min_pixels, int frozen,
                      int passes, void* workspace, int64_t* stats, hipStream_t s);
+// fu_map_edge_offsets / fu_map_edge_rings (fu_vector.hip): the crack edges of a class map's selected values (select: host
+// [256]) and their rings; both check every argument before anything is launched.  The *_workspace_bytes give 0 for a size
+// the calls reject.
+int64_t map_edges_workspace_bytes(int h, int w);
+int64_t map_rings_workspace_bytes(int64_t capacity);
+int launch_map_edge_offsets(const unsigned char* map, int h, int w, const unsigned char* select, int* offsets, void* workspace,
+                            int64_t workspace_bytes, hipStream_t s);
+int launch_map_edge_rings(const unsigned char* map, const int* labels, int h, int w, const unsigned char* select, int connectivity,
+                          const int* offsets, int64_t capacity, int* start, int* comp, int* ring, int* rank, int* flags,
+                          void* workspace, int64_t workspace_bytes, hipStream_t s);
 int launch_eval_confusion(const float* logits_nhwc, const int64_t* target, int ncls, int ignore_index, int B, int64_t hw,
                           int64_t* counts, hipStream_t s);
 // fu_eval_prob_hist (logits: src = the resident NHWC logits) / fu_prob_hist (src = fp32 probabilities [npix, ncls]):

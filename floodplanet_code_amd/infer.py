@@ -64,6 +64,20 @@ else the parent directory.  What runs differently:
     through the numpy statement.  Everything behind that tensor is the same code, so the routes write identical files.
     Out of scope: writing compressed or BigTIFF outputs, JPEG / ZSTD / LERC, sub-byte samples, overviews and mask IFDs
     (the first IFD is the scene), entropy decoding on the GPU.
+  * extension: --write_vectors writes the water bodies as polygons, <image>.geojson beside <image>.tif: one Polygon
+    feature, outer ring and holes, per connected patch (--vector_connectivity 4|8, default the sieve's, else 4) of the
+    values --vector_values (default 255) of the class map as written, so after the threshold, the mask and the sieve.
+    vectorize.py holds the rule.  On the device, between the sieve and the scene's one large read: components
+    (fu_map_components), the pixel edges between unlike pixels and their device-wide scan (fu_map_edge_offsets), one
+    4-byte read of the edge count, each edge's successor and the rings by pointer jumping (fu_map_edge_rings); the five
+    int32 arrays per edge ride in that read, and the host sorts them into rings, keeps the corners and writes.  The
+    properties are value, label, pixels, area (pixels times the pixel area in CRS units, null without georeferencing)
+    and bbox_px; coordinates stay in the raster's CRS (no reprojection) and an EPSG code in the GeoKeys becomes the "crs"
+    member.  A scene with more than --vector_max_edges edges (default 2^24) gets "vectors": {"skipped"} in its record
+    and no file; a scene without a selected pixel, or without a crop under --nodata, an empty FeatureCollection.  The
+    records and the summary gain "vectors".  Without --write_vectors nothing of this runs and every file is byte for
+    byte what it was.  Out of scope: simplification and smoothing, MultiPolygons by value, Shapefile / GeoPackage,
+    vectors in predict.
 How infer() is put together: the options travel as one checked InferOptions (infer_options.py; the keywords of infer() and
 the command line both go through InferOptions.make); predict.load_eval_model serves the model; a SceneQueue owns the
 scenes in flight and deals their crops out in batches; per batch scene_crops, predict.eval_forward and one batched stitch;
@@ -89,6 +103,7 @@ from .infer_options import (BLEND_KINDS, DECODE_CHOICES, DECODE_THREADS_DEFAULT,
                             threshold_rule)
 from .predict import CONFIG_DEFAULTS, _merge, eval_forward, load_eval_model, resolve_cfg
 from .tta import VIEW_SETS, recorded
+from .vectorize import ARRAYS as VECTOR_ARRAYS
 
 SCALE_MODES = {"S1": 1, "S2": 2, "L8": 3}                    # PS: 4 when stored as uint16, else 0
 EXTRA_SOURCES = ("dem", "slope", "preflood", "pre_post_difference", "chirps", "hand")
@@ -402,6 +417,8 @@ def empty_scene_arrays(scene: dict, n_classes: int, options: InferOptions) -> Di
         arrays["valid"] = np.zeros((H, W), dtype=np.uint8)
     if options.keep_probabilities:
         arrays["kept"] = np.zeros((H, W, n_classes), dtype=np.float32)
+    if options.write_vectors:
+        arrays.update({k: np.zeros(0, dtype=np.int32) for k in VECTOR_ARRAYS}, edges=0)      # no crop: no polygon
     return arrays
 
 
@@ -413,7 +430,10 @@ def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: Inf
     keep_probabilities one more read: "kept", the canvas.  The scene's canvases are dropped.  With options.nodata (scene:
     the uploaded scene, which holds the mask) the finalisation is the masked one, the sieve freezes nodata_out, and the
     read also carries "n_valid" int64 [1] and, with write_valid, "valid" uint8 [H, W]; a scene without a crop has no
-    canvas: empty_scene_arrays."""
+    canvas: empty_scene_arrays.  With options.write_vectors the crack edges of the written map's vector_values and their
+    rings are taken on the same stream after the sieve (vectorize.count_and_rings: components, offsets, one 4-byte read
+    of the edge count, rings) and the read also carries "start", "comp", "ring", "rank", "flags" int32 [n_edges]; "edges"
+    is the count, and a scene with more than vector_max_edges has the count alone."""
     from .postprocess import sieve as sieve_map
     from .stitch import PackedRead
     masked = options.nodata is not None
@@ -438,7 +458,15 @@ def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: Inf
         read.add("n_valid", scene["n_valid"])
         if options.write_valid:
             read.add("valid", scene["valid"])
+    if options.write_vectors:                            # of the map as it is written: after the sieve
+        from .vectorize import count_and_rings, select_flags
+        n_edges, rings = count_and_rings(maps["class"], select_flags(options.vector_values), options.vector_connectivity,
+                                         max_edges=options.vector_max_edges)
+        for name in VECTOR_ARRAYS if rings is not None else ():
+            read.add(name, rings[name])
     arrays = read.read()
+    if options.write_vectors:
+        arrays["edges"] = n_edges                        # without the five arrays: the scene is over vector_max_edges
     if options.keep_probabilities:
         arrays["kept"] = maps["canvas"].cpu().numpy()
     stitcher.drop(key)
@@ -450,7 +478,8 @@ def write_scene(arrays: Dict[str, np.ndarray], scene: dict, options: InferOption
     the input's georeferencing on the output grid (scene: "tags", "src_hw", "hw", "n") -> its summary.json record.  With
     options.nodata (scene: also "nodata", "skipped"; arrays: also "n_valid") the class map carries GDAL_NODATA =
     str(nodata_out) (tag 42113) beside the georeferencing -- the side rasters do not, 0 is a value there -- and
-    write_valid writes arrays["valid"] as <image>_valid.tif."""
+    write_valid writes arrays["valid"] as <image>_valid.tif.  With options.write_vectors (arrays: also the ring arrays
+    and "edges") it writes <image>.geojson: write_scene_vectors."""
     from .datasets.synthetic import write_strip_tiff
     H, W = scene["hw"]
     tags = geo_tags_for_grid(scene["tags"], scene["src_hw"], (H, W))
@@ -476,7 +505,28 @@ def write_scene(arrays: Dict[str, np.ndarray], scene: dict, options: InferOption
     if options.sieve is not None:
         merged, changed = arrays["sieve"].tolist()
         rec["sieve"] = dict(options.sieve_options, merged_components=merged, changed_pixels=changed)
+    if options.write_vectors:
+        rec["vectors"] = write_scene_vectors(arrays, scene, options, vector_output_path(out_path))
     return rec
+
+
+def vector_output_path(out_path: str) -> str:
+    """<image>.geojson beside the class map <image>.tif."""
+    return out_path[:-len(".tif")] + ".geojson"
+
+
+def write_scene_vectors(arrays: Dict[str, np.ndarray], scene: dict, options: InferOptions, path: str) -> dict:
+    """Host only: the polygons of a scene's written class map (vectorize.rings_to_polygons of finalize_scene's ring arrays,
+    one per connected patch of options.vector_values) as GeoJSON in the raster's CRS -> the record's "vectors".  A scene
+    over vector_max_edges gets {"skipped"} and no file; a scene without a selected pixel an empty FeatureCollection."""
+    from .vectorize import crs_from_tags, grid_transform, rings_to_polygons, write_geojson
+    if "start" not in arrays:
+        return {"skipped": f"{arrays['edges']} edges > {options.vector_max_edges}"}
+    polygons = rings_to_polygons(arrays, scene["hw"], arrays["class"])
+    write_geojson(path, polygons, grid_transform(scene["tags"], scene["src_hw"], scene["hw"]), crs_from_tags(scene["tags"]))
+    return {"path": path, "polygons": len(polygons), "rings": sum(len(p["rings"]) for p in polygons),
+            "edges": int(arrays["edges"]), "values": list(options.vector_values),
+            "connectivity": options.vector_connectivity}
 
 
 def run_summary(records: List[dict], n_crops: int, seconds: float, max_resident: int, options: InferOptions,
@@ -496,6 +546,12 @@ def run_summary(records: List[dict], n_crops: int, seconds: float, max_resident:
         summary["nodata"] = {"value": options.nodata, "out": options.nodata_out, "skip_empty": options.skip_empty,
                              "valid_pixels": sum(r["valid_pixels"] for r in records),
                              "skipped_crops": sum(r["skipped_crops"] for r in records)}
+    if options.write_vectors:
+        written = [r["vectors"] for r in records if "skipped" not in r["vectors"]]
+        summary["vectors"] = {"values": list(options.vector_values), "connectivity": options.vector_connectivity,
+                              "max_edges": options.vector_max_edges, "polygons": sum(v["polygons"] for v in written),
+                              "rings": sum(v["rings"] for v in written), "edges": sum(v["edges"] for v in written),
+                              "skipped_scenes": len(records) - len(written)}
     return summary
 
 
@@ -509,6 +565,7 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     sieve / sieve_connectivity / sieve_passes (only the written class map is sieved), water_threshold / threshold_class
     / calibration (the one-versus-rest rule in place of the argmax), nodata / nodata_out / skip_empty / write_valid (the
     valid-pixel mask, see the module docstring), decode / decode_threads (where a scene's samples are unpacked),
+    write_vectors / vector_values / vector_connectivity / vector_max_edges (polygons of the written class map),
     n_workers, device, keep_probabilities.  Returns the
     summary.json dict, which records the weights served, the blend, the stride and, when set, "threshold" and "sieve";
     with keep_probabilities also "probabilities" {output path: fp32 [H, W, k] stitched canvas} (one more host read per
@@ -627,6 +684,17 @@ def build_parser() -> argparse.ArgumentParser:
                          "host: every file through the numpy reader")
     ap.add_argument("--decode_threads", type=int, default=DECODE_THREADS_DEFAULT,
                     help="threads that inflate a scene's tiles or strips, 1..16 (default 4)")
+    ap.add_argument("--write_vectors", action="store_true",
+                    help="also write <image>.geojson: one polygon, with its holes, per connected patch of the written class "
+                         "map (after --sieve), traced on the device, in the raster's CRS (default: off)")
+    ap.add_argument("--vector_values", type=int, nargs="+", default=None, metavar="V",
+                    help="the class-map values that get polygons, each in 0..255 (default 255, water).  Needs --write_vectors")
+    ap.add_argument("--vector_connectivity", type=int, default=None, choices=[4, 8],
+                    help="neighbours that join pixels into one polygon (default: --sieve_connectivity under --sieve, else "
+                         "4).  Needs --write_vectors")
+    ap.add_argument("--vector_max_edges", type=int, default=None, metavar="N",
+                    help="a scene whose polygons have more than N pixel edges gets no .geojson; its record says so "
+                         "(default 16777216).  Needs --write_vectors")
     ap.add_argument("--batch_size", type=int, default=None, help="crops per eval forward (default: the config's)")
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips / rotations")

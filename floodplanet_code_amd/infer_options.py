@@ -18,10 +18,11 @@ PROB_FORMATS = ("u8", "f32")
 KEYWORDS = ("size", "scale", "stride", "batch_size", "tta", "n_workers", "device", "keep_probabilities", "weights",
             "blend", "write_probs", "write_margin", "sieve", "sieve_connectivity", "sieve_passes", "water_threshold",
             "threshold_class", "calibration", "nodata", "nodata_out", "skip_empty", "write_valid", "decode",
-            "decode_threads")
+            "decode_threads", "write_vectors", "vector_values", "vector_connectivity", "vector_max_edges")
 NODATA_OUT_DEFAULT = 127                         # the class map's byte where the input holds no data
 DECODE_CHOICES = ("auto", "host", "device")      # how a scene's samples reach the device (infer.SceneFiles)
 DECODE_THREADS_DEFAULT, DECODE_THREADS_MAX = 4, 16   # datasets/geotiff.py's; never sized from the machine's CPU count
+VECTOR_MAX_EDGES_DEFAULT = 1 << 24               # a scene with more crack edges gets no polygons (vectorize.py)
 
 
 def check_weights(weights) -> str:
@@ -126,6 +127,32 @@ def check_decode(decode, decode_threads) -> Tuple[str, int]:
     return decode, int(decode_threads)
 
 
+def check_vectors(write_vectors, vector_values, vector_connectivity, vector_max_edges, sieve, nodata_out) -> Optional[dict]:
+    """--write_vectors and its options -> None (off) or the four vector fields.  vector_values: the class-map values that
+    get polygons, default every written class value except 0 and nodata_out, which is [255]; vector_connectivity: 4 or 8,
+    default the sieve's when the run sieves, else 4; vector_max_edges: default 2^24."""
+    given = [name for name, v in (("--vector_values", vector_values), ("--vector_connectivity", vector_connectivity),
+                                  ("--vector_max_edges", vector_max_edges)) if v is not None]
+    if not write_vectors:
+        if given:
+            raise ValueError(f"infer: {', '.join(given)} need{'s' if len(given) == 1 else ''} --write_vectors")
+        return None
+    values = [255] if vector_values is None else list(vector_values)
+    for v in values:
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or not 0 <= int(v) <= 255:
+            raise ValueError(f"infer: vector_values must be integers in 0..255, got {v!r}")
+    if vector_connectivity is None:
+        vector_connectivity = sieve[1] if sieve is not None else 4
+    if vector_connectivity not in (4, 8):
+        raise ValueError(f"infer: vector_connectivity must be 4 or 8, got {vector_connectivity!r}")
+    if vector_max_edges is None:
+        vector_max_edges = VECTOR_MAX_EDGES_DEFAULT
+    if isinstance(vector_max_edges, bool) or int(vector_max_edges) != vector_max_edges or int(vector_max_edges) < 0:
+        raise ValueError(f"infer: vector_max_edges must be an integer >= 0, got {vector_max_edges!r}")
+    return dict(write_vectors=True, vector_values=tuple(sorted({int(v) for v in values})),
+                vector_connectivity=int(vector_connectivity), vector_max_edges=int(vector_max_edges))
+
+
 @dataclasses.dataclass(frozen=True)
 class InferOptions:
     """size / scale: the output grid (grid_size); None, None: the raster's own.  stride and batch_size None: the
@@ -136,7 +163,8 @@ class InferOptions:
     constants below (off).  A run with --nodata is a NodataInferOptions, which appends them as fields.  Likewise decode
     ("auto": a file the strict TIFF reader takes goes the way it always went, every other file is unpacked on the
     device) and decode_threads: class constants here, fields of DecodeInferOptions / NodataDecodeInferOptions when either
-    differs from its default."""
+    differs from its default.  And write_vectors with vector_values, vector_connectivity and vector_max_edges: off here,
+    fields of the Vector* classes under --write_vectors."""
     size: Optional[Tuple[int, int]] = None
     scale: Optional[float] = None
     stride: Optional[int] = None
@@ -158,15 +186,21 @@ class InferOptions:
     write_valid = False
     decode = "auto"                      # not fields here: see DecodeInferOptions
     decode_threads = DECODE_THREADS_DEFAULT
+    write_vectors = False                # not fields here: see vector_options_class
+    vector_values = (255,)
+    vector_connectivity = 4
+    vector_max_edges = VECTOR_MAX_EDGES_DEFAULT
 
     @classmethod
     def make(cls, *, size=None, scale=None, stride=None, batch_size=None, tta=None, n_workers=0, device="cuda:0",
              keep_probabilities=False, weights="auto", blend="uniform", write_probs=None, write_margin=False, sieve=None,
              sieve_connectivity=4, sieve_passes=1, water_threshold=None, threshold_class=None,
              calibration=None, nodata=None, nodata_out=NODATA_OUT_DEFAULT, skip_empty=True,
-             write_valid=False, decode="auto", decode_threads=DECODE_THREADS_DEFAULT) -> "InferOptions":
+             write_valid=False, decode="auto", decode_threads=DECODE_THREADS_DEFAULT, write_vectors=False,
+             vector_values=None, vector_connectivity=None, vector_max_edges=None) -> "InferOptions":
         """The options checked, in the order infer() always checked them: weights, blend, write_probs, the decision
-        rule (threshold_rule), the sieve (postprocess.check_sieve_options), an explicit stride, the grid, nodata, decode."""
+        rule (threshold_rule), the sieve (postprocess.check_sieve_options), an explicit stride, the grid, nodata, decode,
+        vectors."""
         from .postprocess import check_sieve_options
         check_weights(weights)
         check_blend(blend)
@@ -192,6 +226,10 @@ class InferOptions:
         if (decode, decode_threads) != ("auto", DECODE_THREADS_DEFAULT):
             cls = NodataDecodeInferOptions if nodata is not None else DecodeInferOptions
             extra.update(decode=decode, decode_threads=decode_threads)
+        vectors = check_vectors(write_vectors, vector_values, vector_connectivity, vector_max_edges, sieve, nodata_out)
+        if vectors is not None:
+            cls = vector_options_class(cls)
+            extra.update(vectors)
         return cls(size=None if size is None else (int(size[0]), int(size[1])), scale=scale,
                    stride=None if stride is None else int(stride), batch_size=int(batch_size) if batch_size else None,
                    tta=tta if tta is None or isinstance(tta, str) else tuple(int(c) for c in tta), weights=weights,
@@ -263,3 +301,28 @@ class NodataDecodeInferOptions(NodataInferOptions):
     """Both: the nodata fields, then the decode fields."""
     decode: str = "auto"
     decode_threads: int = DECODE_THREADS_DEFAULT
+
+
+def vector_options_class(base):
+    """The options class of a run with --write_vectors: `base` (any of the four above) with the four vector fields appended.
+    write_vectors: True; vector_values: the class-map values that get polygons, sorted; vector_connectivity: 4 or 8;
+    vector_max_edges: a scene with more crack edges gets no polygons."""
+    return _VECTOR_CLASSES[base]
+
+
+def _vector_class(base):
+    cls = dataclasses.make_dataclass(
+        "Vector" + base.__name__, [("write_vectors", bool, False), ("vector_values", Tuple[int, ...], (255,)),
+                                   ("vector_connectivity", int, 4), ("vector_max_edges", int, VECTOR_MAX_EDGES_DEFAULT)],
+        bases=(base,), frozen=True)
+    cls.__module__ = __name__
+    cls.__doc__ = f"{base.__name__} of a run with --write_vectors: the four vector fields appended (vector_options_class)."
+    return cls
+
+
+VectorInferOptions = _vector_class(InferOptions)
+VectorNodataInferOptions = _vector_class(NodataInferOptions)
+VectorDecodeInferOptions = _vector_class(DecodeInferOptions)
+VectorNodataDecodeInferOptions = _vector_class(NodataDecodeInferOptions)
+_VECTOR_CLASSES = {InferOptions: VectorInferOptions, NodataInferOptions: VectorNodataInferOptions,
+                   DecodeInferOptions: VectorDecodeInferOptions, NodataDecodeInferOptions: VectorNodataDecodeInferOptions}

@@ -773,6 +773,35 @@ int64_t fu_sieve_workspace_bytes(int h, int w);
 int fu_map_sieve(const uint8_t* map, uint8_t* out, int h, int w, int connectivity, int min_pixels, int frozen_value,
                  int passes, void* workspace, int64_t workspace_bytes, int64_t* stats_out, fu_stream stream);
 
+/* Vector output (fu_vector.hip; added within ABI 5: purely additive).  floodplanet_code_amd/vectorize.py holds the numpy
+ * statements, edge_offsets_host and edge_rings_host, and the definitions: a pixel whose value v has select[v] != 0 (select:
+ * HOST uint8 [256]) owns a directed unit edge on every side -- 0 top, 1 right, 2 bottom, 3 left, heading E, S, W, N with the
+ * pixel on its right -- where the neighbour lies outside the map or has another value; edges are numbered by owner pixel
+ * y * w + x, then side.  Everything is integer-exact and canonical.  1 <= h, w and h * w <= FU_MAP_MAX_PIXELS, so the edge
+ * count is at most 2^30 and every vertex index y * (w + 1) + x fits an int32.
+ * fu_map_edge_offsets: offsets_out device int32 [h * w + 1] = the exclusive prefix sum of the per-pixel edge counts; the
+ * last element is n_edges.  Three launches (block-local scan with block totals, scan of the totals, add) ordered by the
+ * stream; no workgroup waits for another.  workspace: device, 16-byte aligned, >= fu_map_edges_workspace_bytes(h, w)
+ * (4 B per 2048 pixels; 0 for a size the call rejects). */
+int64_t fu_map_edges_workspace_bytes(int h, int w);
+int fu_map_edge_offsets(const uint8_t* map, int h, int w, const uint8_t* select /* host [256] */,
+                        int32_t* offsets_out /* device [h*w+1] */, void* workspace, int64_t workspace_bytes, fu_stream stream);
+/* fu_map_edge_rings: labels = fu_map_components of the map under `connectivity`, offsets = fu_map_edge_offsets of the map
+ * and select.  The five outputs are device int32 [capacity]: start (the edge's start vertex), comp (its owner's label),
+ * ring (the smallest edge index on the edge's cycle under the successor rule of vectorize.py), rank (the steps from that
+ * edge), flags (heading | corner << 2; corner: the predecessor has another heading).  One emit launch, then pointer
+ * jumping with ping-pong buffers, ceil(log2(max(capacity, 2))) rounds for ring and as many for rank; no host read.  The
+ * kernels take n = offsets[h * w] on the device: n > capacity writes nothing, otherwise every store and every gather
+ * through the successor array is guarded by n and elements at n and beyond stay untouched, so a stale offsets array
+ * can give wrong rings but no access outside the buffers.  capacity == 0 launches nothing.  workspace: device, 16-byte
+ * aligned, >= fu_map_rings_workspace_bytes(capacity) (20 B per edge; 0 for a capacity outside 0..2^30).
+ * Both calls check every argument before anything is launched -- null pointers, sizes, connectivity, workspace bytes and
+ * alignment -- and a rejected call leaves the outputs untouched. */
+int64_t fu_map_rings_workspace_bytes(int64_t capacity);
+int fu_map_edge_rings(const uint8_t* map, const int32_t* labels, int h, int w, const uint8_t* select, int connectivity,
+                      const int32_t* offsets, int64_t capacity, int32_t* start_out, int32_t* comp_out, int32_t* ring_out,
+                      int32_t* rank_out, int32_t* flags_out, void* workspace, int64_t workspace_bytes, fu_stream stream);
+
 /* ---- eval metrics ---------------------------------------------------------------------------- */
 /* Per-sample confusion counts of the last fu_forward (eval or training): counts_out[b][t * k + p] += #pixels of sample b
  * with target t and p = argmax of the resident logits (first maximum wins, as fu_loss_ce), over pixels whose target is
