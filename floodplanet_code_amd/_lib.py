@@ -292,6 +292,11 @@ SIGNATURES = {
     "fu_elem_size": (_i, [_i]),
     "fu_op_nchw_to_nhwc": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _p]),
     "fu_op_nhwc_to_nchw": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "fu_op_nchw_to_nhwc_window": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "fu_op_gather_nchw_to_nhwc": (_i, [_i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "fu_op_copy_channels": (_i, [_i, _p, _i, _i, _p, _p, _p, _i, _i, _i, _i64, _p]),
+    "fu_op_center_to_w3": (_i, [_p, _i64, _p, _p]),
+    "fu_op_center_from_w3": (_i, [_p, _i64, _p, _p]),
     "fu_op_conv3x3_fwd": (_i, [_i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "fu_op_conv3x3_dgrad": (_i, [_i, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _p]),
     "fu_op_conv3x3_wgrad": (_i, [_i, _p, _i, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _p]),

@@ -208,17 +208,12 @@ int fu_forward(fu_ctx* c, const float* x, int batch, int training, float* logits
 }
 
 namespace {
-int make_src_list(const fu_ctx* c, const char* fn, const float* const* srcs, const int32_t* src_channels, int n_src,
-                  SrcList* S) {
-  S->n = n_src;
-  int off = 0;
-  for (int k = 0; k < n_src; ++k) {
-    FU_REQUIRE(srcs[k] && src_channels[k] >= 1, "%s: bad source %d", fn, k);
-    S->p[k] = srcs[k]; S->c[k] = src_channels[k]; S->coff[k] = off; off += src_channels[k];
-  }
-  S->coff[n_src] = off;
-  FU_REQUIRE(off == c->cfg.n_channels, "%s: the sources have %d channels in all, the model takes %d", fn, off,
-             c->cfg.n_channels);
+// the sources of one forward: make_src_list's checks (fu_layout.hip), and their channels add up to the model's
+int model_src_list(const fu_ctx* c, const char* fn, const float* const* srcs, const int32_t* src_channels, int n_src,
+                   SrcList* S) {
+  FU_TRY(make_src_list(fn, srcs, src_channels, n_src, S));
+  FU_REQUIRE(S->coff[n_src] == c->cfg.n_channels, "%s: the sources have %d channels in all, the model takes %d", fn,
+             S->coff[n_src], c->cfg.n_channels);
   return 0;
 }
 }  // namespace
@@ -228,7 +223,7 @@ int fu_forward_srcs(fu_ctx* c, const float* const* srcs, const int32_t* src_chan
   FU_REQUIRE(srcs && src_channels && n_src >= 1 && n_src <= 8, "fu_forward_srcs: 1..8 sources");
   FU_TRY(check_fwd_args(c, srcs[0], batch));
   SrcList S;
-  FU_TRY(make_src_list(c, "fu_forward_srcs", srcs, src_channels, n_src, &S));
+  FU_TRY(model_src_list(c, "fu_forward_srcs", srcs, src_channels, n_src, &S));
   return forward_impl(c, nullptr, &S, batch, training != 0, logits_out, (hipStream_t)stream);
 }
 
@@ -236,23 +231,15 @@ int fu_forward_views(fu_ctx* c, const float* const* srcs, const int32_t* src_cha
                      const int32_t* codes, float* logits_out, fu_stream stream) {
   FU_REQUIRE(c, "fu_forward_views: null context");
   FU_REQUIRE(srcs && src_channels && n_src >= 1 && n_src <= 8, "fu_forward_views: 1..8 sources");
-  FU_REQUIRE(codes && n_views >= 1 && n_views <= 8, "fu_forward_views: n_views = %d outside 1..8 (or null codes)", n_views);
-  unsigned packed = 0, seen = 0;
-  for (int v = 0; v < n_views; ++v) {
-    const int code = codes[v];
-    FU_REQUIRE(code >= 0 && code <= 7, "fu_forward_views: view %d: code %d outside 0..7", v, code);
-    FU_REQUIRE(!((seen >> code) & 1u), "fu_forward_views: view %d repeats code %d (codes must be distinct)", v, code);
-    FU_REQUIRE(!(code & FU_VIEW_TRANSPOSE) || c->cfg.height == c->cfg.width,
-               "fu_forward_views: view %d: code %d transposes, which needs a square tile (the context's is %dx%d)", v, code,
-               c->cfg.height, c->cfg.width);
-    seen |= 1u << code;
-    packed |= (unsigned)code << (3 * v);
-  }
+  unsigned packed = 0;
+  FU_TRY(pack_view_codes("fu_forward_views", codes, n_views, true, &packed));
+  // the square-tile rule of the transposing codes, in the words of the views gather's launcher (check_view_geometry)
+  FU_TRY(check_view_geometry("fu_forward_views", n_views, packed, c->cfg.height, c->cfg.width));
   FU_REQUIRE(batch >= 1 && (int64_t)batch * n_views <= c->cfg.max_batch,
              "fu_forward_views: %d views x batch %d outside 1..%d samples (max_batch)", n_views, batch, c->cfg.max_batch);
   FU_TRY(check_fwd_args(c, srcs[0], batch * n_views));
   SrcList S;
-  FU_TRY(make_src_list(c, "fu_forward_views", srcs, src_channels, n_src, &S));
+  FU_TRY(model_src_list(c, "fu_forward_views", srcs, src_channels, n_src, &S));
   return forward_impl(c, nullptr, &S, batch * n_views, false, logits_out, (hipStream_t)stream, n_views, packed);
 }
 

@@ -454,6 +454,14 @@ int launch_nchw_to_nhwc(Prec p, const float* src, void* dst, int B, int C, int H
 int launch_nhwc_to_nchw(Prec p, const void* src, float* dst, int B, int C, int H, int W, int c_pad, hipStream_t s);
 // up to 8 fp32 NCHW tensors [B, c[k], H, W] taken side by side along the channel axis; coff = prefix sums of c
 struct SrcList { const float* p[8]; int c[8]; int coff[9]; int n; };
+// The SrcList of n_src caller sources (fu_forward_srcs, fu_forward_views, fu_op_gather_nchw_to_nhwc): rejects a null table,
+// n_src outside 1..8, a null source and a channel count below 1; `who` names the caller in the message.
+int make_src_list(const char* who, const float* const* srcs, const int32_t* src_channels, int n_src, SrcList* S);
+// n_views view codes packed 3 bits each, the form the views gather takes: rejects null codes, n_views outside 1..8, a code
+// outside 0..7 and, where `distinct` is set (fu_forward_views), a repeated code.
+int pack_view_codes(const char* who, const int32_t* codes, int n_views, bool distinct, unsigned* packed);
+// The one statement of the square-tile rule: a transposing code (bit 4) among the n_views packed ones needs H == W.
+int check_view_geometry(const char* who, int n_views, unsigned codes, int H, int W);
 // dst [B,H,W,c_pad] <- channels [ch_off, ch_off + C) of the virtual concatenation (zero padding above C)
 int launch_gather_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B, int C, int H, int W, int c_pad, int ch_off,
                                hipStream_t s);

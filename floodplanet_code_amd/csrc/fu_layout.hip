@@ -1,6 +1,7 @@
 // Layout kernels of the UNet path (gfx950): NCHW fp32 <-> NHWC conversion, the gathers that concatenate several NCHW sources
 // (and take test-time-augmentation views) on the way, channel-window copies and the centre-tap embedding of 1x1 weights.
 // HBM-bound: 16-byte vector accesses along the NHWC channel dimension.
+// Every kernel here runs on its own, bit for bit against a host statement, in tests/test_gpu_layout_ops.py (hooks: fu_ops.hip).
 #include "fu_common.h"
 
 namespace fu {
@@ -104,6 +105,40 @@ __global__ __launch_bounds__(256) void k_gather_nchw_to_nhwc(SrcList S, T* __res
   VecIO<T>::store(dst + ((size_t)b * HW + p) * cpad + o * V, v);
 }
 
+int make_src_list(const char* who, const float* const* srcs, const int32_t* src_channels, int n_src, SrcList* S) {
+  FU_REQUIRE(srcs && src_channels && n_src >= 1 && n_src <= 8, "%s: 1..8 sources", who);
+  S->n = n_src;
+  int off = 0;
+  for (int k = 0; k < n_src; ++k) {
+    FU_REQUIRE(srcs[k] && src_channels[k] >= 1, "%s: bad source %d", who, k);
+    S->p[k] = srcs[k]; S->c[k] = src_channels[k]; S->coff[k] = off; off += src_channels[k];
+  }
+  S->coff[n_src] = off;
+  return 0;
+}
+
+int pack_view_codes(const char* who, const int32_t* codes, int n_views, bool distinct, unsigned* packed) {
+  FU_REQUIRE(codes && n_views >= 1 && n_views <= 8, "%s: n_views = %d outside 1..8 (or null codes)", who, n_views);
+  unsigned pk = 0, seen = 0;
+  for (int v = 0; v < n_views; ++v) {
+    const int code = codes[v];
+    FU_REQUIRE(code >= 0 && code <= 7, "%s: view %d: code %d outside 0..7", who, v, code);
+    FU_REQUIRE(!distinct || !((seen >> code) & 1u), "%s: view %d repeats code %d (codes must be distinct)", who, v, code);
+    seen |= 1u << code;
+    pk |= (unsigned)code << (3 * v);
+  }
+  *packed = pk;
+  return 0;
+}
+
+int check_view_geometry(const char* who, int n_views, unsigned codes, int H, int W) {
+  for (int v = 0; v < n_views && v < 8; ++v) {
+    const int code = (int)((codes >> (3 * v)) & 7u);
+    FU_REQUIRE(!(code & 4) || H == W, "%s: view %d: code %d transposes, which needs a square tile (got %dx%d)", who, v, code, H, W);
+  }
+  return 0;
+}
+
 int launch_gather_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B, int C, int H, int W, int c_pad, int ch_off,
                                hipStream_t s) {
   return dispatch_prec(p, [&](auto tag) {
@@ -150,6 +185,7 @@ __global__ __launch_bounds__(256) void k_gather_views_nchw_to_nhwc(SrcList S, T*
 
 int launch_gather_views_nchw_to_nhwc(Prec p, const SrcList& S, void* dst, int B, int n_views, unsigned codes, int C, int H,
                                      int W, int c_pad, int ch_off, hipStream_t s) {
+  FU_TRY(check_view_geometry("gather_views_nchw_to_nhwc", n_views, codes, H, W));   // x * W + y is a pixel only where H == W
   return dispatch_prec(p, [&](auto tag) {
     using T = decltype(tag);
     constexpr int V = VecIO<T>::V;

@@ -32,6 +32,73 @@ int fu_op_nhwc_to_nchw(int precision, const void* src, float* dst, int B, int C,
   return launch_nhwc_to_nchw(p, src, dst, B, C, H, W, c_pad, (hipStream_t)stream);
 }
 
+// ---- op-level test hooks of the layout kernels (fu_layout.hip): every argument check precedes the launch, so a rejected call
+// answers on a machine without a GPU and launches nothing; none of them synchronises ------------------------------------------
+namespace {
+int layout_shape(const char* who, int B, int C, int H, int W, int c_pad) {
+  FU_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "%s: empty shape (B=%d C=%d H=%d W=%d)", who, B, C, H, W);
+  FU_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), "%s: too many pixels per image", who);
+  FU_REQUIRE(c_pad >= C, "%s: c_pad = %d below the %d channels", who, c_pad, C);
+  return 0;
+}
+}  // namespace
+
+int fu_op_nchw_to_nhwc_window(int precision, const float* src, void* dst, int B, int C, int H, int W, int c_pad,
+                              int src_channels, int src_channel_offset, fu_stream stream) {
+  const char* who = "fu_op_nchw_to_nhwc_window";
+  Prec p; FU_TRY(prec_of(precision, &p));
+  FU_REQUIRE(src && dst, "%s: null argument", who);
+  FU_TRY(layout_shape(who, B, C, H, W, c_pad));
+  const int srcC = src_channels > 0 ? src_channels : C;
+  FU_REQUIRE(src_channels >= 0 && src_channel_offset >= 0 && src_channel_offset <= srcC - C,
+             "%s: channels [%d, %d) outside the %d source channels", who, src_channel_offset, src_channel_offset + C, srcC);
+  return launch_nchw_to_nhwc(p, src, dst, B, C, H, W, c_pad, (hipStream_t)stream, src_channels, src_channel_offset);
+}
+
+int fu_op_gather_nchw_to_nhwc(int precision, const float* const* srcs, const int32_t* src_channels, int n_src, void* dst,
+                              int B, int C, int H, int W, int c_pad, int ch_off, int n_views, const int32_t* view_codes,
+                              fu_stream stream) {
+  const char* who = "fu_op_gather_nchw_to_nhwc";
+  Prec p; FU_TRY(prec_of(precision, &p));
+  FU_REQUIRE(dst, "%s: null argument", who);
+  FU_TRY(layout_shape(who, B, C, H, W, c_pad));
+  SrcList S;
+  FU_TRY(make_src_list(who, srcs, src_channels, n_src, &S));
+  FU_REQUIRE(ch_off >= 0 && ch_off <= S.coff[S.n] - C, "%s: channels [%d, %d) outside the %d source channels", who, ch_off,
+             ch_off + C, S.coff[S.n]);
+  FU_REQUIRE(n_views >= 0, "%s: n_views = %d outside 0..8", who, n_views);
+  if (n_views == 0) return launch_gather_nchw_to_nhwc(p, S, dst, B, C, H, W, c_pad, ch_off, (hipStream_t)stream);
+  unsigned packed = 0;
+  FU_TRY(pack_view_codes(who, view_codes, n_views, false, &packed));
+  return launch_gather_views_nchw_to_nhwc(p, S, dst, B, n_views, packed, C, H, W, c_pad, ch_off, (hipStream_t)stream);
+}
+
+int fu_op_copy_channels(int precision, const void* src, int srcC, int src_off, const float* bn_a, const float* bn_b,
+                        void* dst, int dstC, int dst_off, int C, int64_t npix, fu_stream stream) {
+  const char* who = "fu_op_copy_channels";
+  Prec p; FU_TRY(prec_of(precision, &p));
+  FU_REQUIRE(src && dst, "%s: null argument", who);
+  FU_REQUIRE(!bn_a == !bn_b, "%s: bn_a and bn_b go together (both or neither)", who);
+  FU_REQUIRE(C > 0 && npix > 0, "%s: empty shape (C=%d npix=%lld)", who, C, (long long)npix);
+  FU_REQUIRE(src_off >= 0 && src_off <= srcC - C, "%s: channels [%d, %d) outside the %d source channels", who, src_off,
+             src_off + C, srcC);
+  FU_REQUIRE(dst_off >= 0 && dst_off <= dstC - C, "%s: channels [%d, %d) outside the %d destination channels", who, dst_off,
+             dst_off + C, dstC);
+  return launch_copy_channels(p, src, srcC, src_off, bn_a, bn_b, dst, dstC, dst_off, C, npix, (hipStream_t)stream);
+}
+
+int fu_op_center_to_w3(const float* w, int64_t n, float* w3, fu_stream stream) {
+  FU_REQUIRE(w && w3, "fu_op_center_to_w3: null argument");
+  FU_REQUIRE(n >= 1, "fu_op_center_to_w3: n must be >= 1 (got %lld)", (long long)n);
+  return launch_center_to_w3(w, n, w3, (hipStream_t)stream);
+}
+
+int fu_op_center_from_w3(const float* dw3, int64_t n, float* dw, fu_stream stream) {
+  FU_REQUIRE(dw3 && dw, "fu_op_center_from_w3: null argument");
+  FU_REQUIRE(n >= 1, "fu_op_center_from_w3: n must be >= 1 (got %lld)", (long long)n);
+  return launch_center_from_w3(dw3, n, dw, (hipStream_t)stream);
+}
+
 namespace {
 struct TmpBuf {
   void* p = nullptr;

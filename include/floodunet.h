@@ -957,6 +957,32 @@ int fu_op_nchw_to_nhwc(int precision, const float* src, void* dst, int B, int C,
                        fu_stream stream);
 int fu_op_nhwc_to_nchw(int precision, const void* src, float* dst, int B, int C, int H, int W, int c_pad,
                        fu_stream stream);
+/* The five operators below are test hooks of the layout kernels (like the fu_test_* switches: no ABI promise).  Each checks
+ * every argument before it launches (FU_ERR_INVALID, the cause in fu_last_error, nothing launched) and none synchronises.
+ * V = 4 (FU_F32) or 8 (16-bit) elements per 16-byte vector.
+ * fu_op_nchw_to_nhwc on a channel window: dst [B,H,W,c_pad] <- channels [src_channel_offset, src_channel_offset + C) of
+ * an fp32 NCHW tensor with src_channels per sample (0 = C), zeros above C.  Launches k_nchw_to_nhwc_v8 for a 16-bit type
+ * with c_pad % 8 == 0 and k_nchw_to_nhwc otherwise, as every encoder's input conversion does. */
+int fu_op_nchw_to_nhwc_window(int precision, const float* src, void* dst, int B, int C, int H, int W, int c_pad,
+                              int src_channels, int src_channel_offset, fu_stream stream);
+/* dst [B,H,W,c_pad] <- channels [ch_off, ch_off + C) of the n_src (1..8) fp32 NCHW tensors srcs[k] [B,src_channels[k],H,W]
+ * taken side by side along the channel axis, zeros above C; c_pad a multiple of V.  n_views == 0 launches
+ * k_gather_nchw_to_nhwc (the input conversion of fu_forward_srcs).  n_views in 1..8 launches k_gather_views_nchw_to_nhwc
+ * (fu_forward_views): dst [n_views * B,H,W,c_pad], sample v * B + b = view view_codes[v] (0..7, repeats allowed here) of
+ * sample b; a transposing code needs H == W. */
+int fu_op_gather_nchw_to_nhwc(int precision, const float* const* srcs, const int32_t* src_channels, int n_src, void* dst,
+                              int B, int C, int H, int W, int c_pad, int ch_off, int n_views, const int32_t* view_codes,
+                              fu_stream stream);
+/* k_copy_channels, the late-fusion concat and the split of its gradient: dst [npix][dstC] channels [dst_off, dst_off + C)
+ * <- src [npix][srcC] channels [src_off, src_off + C), as they are (bn_a, bn_b null) or as relu(bn_a[c] * x + bn_b[c]) with
+ * c counted from the window's start (both fp32 [C]; given together).  Every channel count and offset a multiple of V; the
+ * rest of dst is not written. */
+int fu_op_copy_channels(int precision, const void* src, int srcC, int src_off, const float* bn_a, const float* bn_b,
+                        void* dst, int dstC, int dst_off, int C, int64_t npix, fu_stream stream);
+/* k_center_to_w3: w3 [n][9] fp32 <- w [n] on tap 4 (the centre of a 3x3 kernel), +0.0 on the other eight.
+ * k_center_from_w3: dw [n] <- dw3 [n][9]'s tap 4; the other taps are not read. */
+int fu_op_center_to_w3(const float* w, int64_t n, float* w3, fu_stream stream);
+int fu_op_center_from_w3(const float* dw3, int64_t n, float* dw, fu_stream stream);
 /* y = conv3x3(cat(relu(a0*src0+b0) or src0, src1), w) + bias; w: fp32 OIHW [Cout, C0+C1, 3, 3].
  * stats_sum/stats_sqsum: optional fp32 [Cout] outputs (per-channel sum / sum of squares of y - bias). */
 int fu_op_conv3x3_fwd(int precision, const void* src0, int C0, const float* bn_a0, const float* bn_b0,
