@@ -107,6 +107,24 @@ def photometric_host(image, gain, bias, sigma, noise_key: int = 0, noise_stream=
     return t
 
 
+def check_photometric(cfg: Optional[dict], spoken_as: str = "photometric"):
+    """sample_photometric's config, checked without a draw: -> (active, (gain, band_gain, brightness, noise, band_drop,
+    likelihood)) as floats, the defaults for what the config leaves out.  ValueError for a key that is not one of
+    PHOTOMETRIC_KEYS (or `active`) and for a value outside its range; spoken_as opens the message (the command line says
+    "--aug_*")."""
+    cfg = dict(cfg or {})
+    active = cfg.pop("active", True)
+    unknown = sorted(set(cfg) - set(PHOTOMETRIC_KEYS))
+    if unknown:
+        raise ValueError(f"{spoken_as}: unknown keys {unknown} (known: {list(PHOTOMETRIC_KEYS)})")
+    G, Gb, B, S, P = (float(cfg.get(k, 0.0)) for k in ("gain", "band_gain", "brightness", "noise", "band_drop"))
+    L = float(cfg.get("likelihood", 1.0))
+    if not (0.0 <= G <= 1.0 and 0.0 <= Gb <= 1.0 and B >= 0.0 and S >= 0.0 and 0.0 <= P < 1.0 and 0.0 <= L <= 1.0):
+        raise ValueError(f"{spoken_as}: need 0 <= gain, band_gain <= 1, brightness, noise >= 0, 0 <= band_drop < 1 and "
+                         f"0 <= likelihood <= 1, got {cfg}")
+    return active, (G, Gb, B, S, P, L)
+
+
 def sample_photometric(n: int, C: int, cfg: Optional[dict], rng: np.random.RandomState) -> Optional[dict]:
     """The radiometric draws of n samples of C bands from a config dict, in units of the batch the net sees (after
     normalisation): `gain` G -- one factor per sample, uniform in [1 - G, 1 + G]; `band_gain` Gb -- one more factor per
@@ -116,16 +134,7 @@ def sample_photometric(n: int, C: int, cfg: Optional[dict], rng: np.random.Rando
     for the whole group: a sample that loses it keeps gain 1, bias 0, sigma 0.  Every draw is made whatever the values, in
     a fixed order, so one option does not move another's stream.  -> {"gain", "bias", "sigma"}: float32 [n, C] each, or
     None for a term the config cannot move; None when the group is inactive ({"active": False}, or nothing to vary)."""
-    cfg = dict(cfg or {})
-    active = cfg.pop("active", True)
-    unknown = sorted(set(cfg) - set(PHOTOMETRIC_KEYS))
-    if unknown:
-        raise ValueError(f"photometric: unknown keys {unknown} (known: {list(PHOTOMETRIC_KEYS)})")
-    G, Gb, B, S, P = (float(cfg.get(k, 0.0)) for k in ("gain", "band_gain", "brightness", "noise", "band_drop"))
-    L = float(cfg.get("likelihood", 1.0))
-    if not (0.0 <= G <= 1.0 and 0.0 <= Gb <= 1.0 and B >= 0.0 and S >= 0.0 and 0.0 <= P < 1.0 and 0.0 <= L <= 1.0):
-        raise ValueError(f"photometric: need 0 <= gain, band_gain <= 1, brightness, noise >= 0, 0 <= band_drop < 1 and "
-                         f"0 <= likelihood <= 1, got {cfg}")
+    active, (G, Gb, B, S, P, L) = check_photometric(cfg)
     if not active or (G == 0.0 and Gb == 0.0 and B == 0.0 and S == 0.0 and P == 0.0) or L == 0.0:
         return None
     on = rng.rand(n) < L

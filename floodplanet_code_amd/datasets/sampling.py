@@ -13,20 +13,24 @@ need the label content of every candidate box, separately:
   * `plan_order(stats, tile_area, policy, ...)`: the epoch's order of data-set indices under "all", "labelled" (drop the
     tiles with nothing to train on) or "balanced" (a fixed share of tiles with water), and what was planned.
   * `jitter_boxes(boxes, raster_hw, J, seed, epoch)`: every box moved by its own offset in [-J, J]^2, kept inside its raster.
+  * `TileOptions`: the loader's whole recipe -- these options, the radiometric config and the zoom range -- as one checked
+    value, built by `make` (keywords), `from_args` (the fit command line) or `from_cfg` (a fit config).
 
 Everything but `label_box_counts` is host arithmetic (numpy / torch CPU) and runs without a GPU."""
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+import dataclasses
+from typing import Any, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
+from ..augment import PHOTOMETRIC_KEYS, check_photometric
 from .class_weights import Box, _check_host_entries, _device_table
 from .scene_loader import epoch_order
 
 __all__ = ["POLICIES", "label_box_counts", "label_box_counts_host", "tile_stats", "plan_order", "jitter_boxes", "zoom_boxes",
-           "zoom_tile_host", "zoom_axis_host", "check_zoom_range"]
+           "zoom_tile_host", "zoom_axis_host", "check_zoom_range", "TileOptions"]
 
 POLICIES = ("all", "labelled", "balanced")
 JITTER_STREAM = 0x6A177E2        # third word of the jitter stream's seed: a stream of its own, not the transforms'
@@ -229,6 +233,109 @@ def zoom_boxes(boxes: Sequence[Box], raster_shapes: Sequence[Tuple[int, int]], z
         src.append((a, b, a + sh, b + sw))
         out.append((dh, dw))
     return src, out
+
+
+# ------------------------------------------------------------------------------------------------------- the recipe
+FRACTIONS = ("min_trainable_frac", "water_share", "min_water_frac")
+SAMPLING_KEYWORDS = ("tile_sampling",) + FRACTIONS + ("crop_jitter",)           # the keys of a config's `sampling`
+PHOTOMETRIC_FLAGS = {"aug_" + k: k for k in PHOTOMETRIC_KEYS}                   # --aug_* flag -> photometric key
+
+
+def _check_sampling(dash: str, tile_sampling, min_trainable_frac, water_share, min_water_frac, crop_jitter):
+    """The five tile-sampling options checked, in TileOptions' field order; dash: "--" where they are named as flags."""
+    if tile_sampling not in POLICIES:
+        raise ValueError(f"{dash}tile_sampling must be one of {POLICIES}, got {tile_sampling!r}")
+    fractions = [_check_frac(dash + k, v) for k, v in zip(FRACTIONS, (min_trainable_frac, water_share, min_water_frac))]
+    if int(crop_jitter) < 0:
+        raise ValueError(f"{dash}crop_jitter must be >= 0, got {crop_jitter}")
+    return (tile_sampling, *fractions, int(crop_jitter))
+
+
+def _photometric_items(photometric, spoken_as: str):
+    """A photometric config checked (augment.check_photometric), as the tuple of items TileOptions keeps; None stays None."""
+    if photometric is None:
+        return None
+    check_photometric(photometric, spoken_as)
+    return tuple(dict(photometric).items())
+
+
+@dataclasses.dataclass(frozen=True)
+class TileOptions:
+    """SceneTileLoader's sampling and augmentation recipe as one checked value; SceneTileLoader.__init__ says what each
+    option does.  photometric_items holds the `photometric` config's items (read it as `photometric`, a dict of its own per
+    read); `given` names the options a command line or a config stated, which is what a config records, and does not
+    enter comparisons."""
+    tile_sampling: str = "all"
+    min_trainable_frac: float = 0.0
+    water_share: float = 0.5
+    min_water_frac: float = 0.0
+    crop_jitter: int = 0
+    photometric_items: Optional[Tuple[Tuple[str, Any], ...]] = None
+    zoom: Optional[Tuple[float, float]] = None
+    given: Tuple[str, ...] = dataclasses.field(default=(), compare=False)
+
+    @classmethod
+    def make(cls, *, tile_sampling="all", min_trainable_frac=0.0, water_share=0.5, min_water_frac=0.0, crop_jitter=0,
+             photometric=None, zoom=None) -> "TileOptions":
+        """The recipe checked, every check once (SceneTileLoader's keywords, in the order it checked them)."""
+        sampling = _check_sampling("", tile_sampling, min_trainable_frac, water_share, min_water_frac, crop_jitter)
+        zoom = None if zoom is None else check_zoom_range(zoom)
+        return cls(*sampling, _photometric_items(photometric, "photometric"), zoom)
+
+    @classmethod
+    def from_args(cls, args) -> "TileOptions":
+        """The recipe a fit command line gave: make's checks, with an option named as its flag, and between them, where fit
+        always ran them, the rules that hold on the command line only -- the options belong to --loader scene, and
+        --aug_likelihood alone varies nothing."""
+        sampling = {k: getattr(args, k, None) for k in SAMPLING_KEYWORDS}
+        sampling = {k: v for k, v in sampling.items() if v is not None}
+        photometric = {key: getattr(args, flag, None) for flag, key in PHOTOMETRIC_FLAGS.items()}
+        photometric = {k: float(v) for k, v in photometric.items() if v is not None}
+        zoom = getattr(args, "aug_zoom", None)
+        streaming = getattr(args, "loader", "scene") != "scene"
+        if sampling and streaming:
+            raise ValueError("--" + ", --".join(sampling) + " need --loader scene: the streaming loader cuts a fixed grid")
+        checked = _check_sampling("--", **{**{k: getattr(cls, k) for k in SAMPLING_KEYWORDS}, **sampling})
+        augmentation = ["aug_" + k for k in photometric] + (["aug_zoom"] if zoom is not None else [])
+        if augmentation and streaming:
+            raise ValueError("--" + ", --".join(augmentation) + " need --loader scene: the fused scene-tile kernel applies them")
+        if set(photometric) == {"likelihood"}:
+            raise ValueError("--aug_likelihood needs one of --aug_gain, --aug_band_gain, --aug_brightness, --aug_noise, "
+                             "--aug_band_drop")
+        given = tuple(sampling) + (("photometric",) if photometric else ()) + (("zoom",) if zoom is not None else ())
+        return cls(*checked, _photometric_items(photometric or None, "--aug_*"),
+                   None if zoom is None else check_zoom_range(zoom), given)
+
+    @classmethod
+    def from_cfg(cls, cfg: dict) -> "TileOptions":
+        """The recipe a config records under `sampling` and `augmentation` (either may be absent)."""
+        keywords = {**cfg.get("sampling", {}), **cfg.get("augmentation", {})}
+        return dataclasses.replace(cls.make(**keywords), given=tuple(keywords))
+
+    @property
+    def photometric(self) -> Optional[dict]:
+        return None if self.photometric_items is None else dict(self.photometric_items)
+
+    def sampling_cfg(self) -> dict:
+        """A config's `sampling`: the tile-sampling options that were given, {} for none."""
+        return {k: getattr(self, k) for k in SAMPLING_KEYWORDS if k in self.given}
+
+    def augmentation_cfg(self) -> dict:
+        """A config's `augmentation`: `photometric` and `zoom` (a list) where given, {} for neither."""
+        out = {"photometric": self.photometric} if "photometric" in self.given else {}
+        if "zoom" in self.given:
+            out["zoom"] = list(self.zoom)
+        return out
+
+    @property
+    def needs_plan(self) -> bool:
+        """Does an epoch need sampling's plan (its own boxes or order) rather than the grid's?"""
+        return self.tile_sampling != "all" or self.crop_jitter > 0 or self.zoom is not None
+
+    @property
+    def needs_draws(self) -> bool:
+        """Does an epoch draw per-example parameters (radiometric terms, zoomed source boxes)?"""
+        return self.photometric_items is not None or self.zoom is not None
 
 
 def zoom_axis_host(src: int, out: int):

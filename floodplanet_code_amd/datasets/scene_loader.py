@@ -13,8 +13,11 @@ stream TileLoader uses) and the table itself.  Optionally the loader chooses whi
 cut (tile_sampling, crop_jitter; datasets/sampling.py): the label content of every box comes from one
 fu_label_box_counts launch over the resident label rasters, the plan is host arithmetic.  Optionally the same launch varies the
 input as well (photometric, zoom: fu_scene_train_tiles_ex -- per-band gain, bias and noise, a per-sample resampling of a
-smaller or larger source box); the host only draws the parameters.  What it does not do: stream scenes in and out of HBM -- a data set that
-exceeds the residency budget raises SceneResidencyError; TileLoader is the streaming loader."""
+smaller or larger source box); the host only draws the parameters.  These options are one checked value,
+sampling.TileOptions, which the loader holds as `options` and reads nowhere else: a new one is a field and its check in
+TileOptions.make, its flag in TileOptions.from_args and fit.build_parser, and the place below that acts on it.  What the
+loader does not do: stream scenes in and out of HBM -- a data set that exceeds the residency budget raises
+SceneResidencyError; TileLoader is the streaming loader."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
@@ -125,13 +128,15 @@ class SceneTileLoader:
                  transforms: Optional[dict] = None, ignore_index: int = 0, max_resident_bytes: Optional[int] = None,
                  shard: Optional[Sequence[int]] = None, num_workers: int = 0, tile_sampling: str = "all",
                  min_trainable_frac: float = 0.0, water_share: float = 0.5, min_water_frac: float = 0.0,
-                 crop_jitter: int = 0, photometric: Optional[dict] = None, zoom: Optional[Sequence[float]] = None):
+                 crop_jitter: int = 0, photometric: Optional[dict] = None, zoom: Optional[Sequence[float]] = None,
+                 options=None):
         """dataset: FloodplanetTiles.  net: the HipUNet whose context owns the table's device buffer.  transforms: None, or
         the reference's `transforms` config dict ({} = its defaults), drawn from RandomState(seed) as TileLoader draws them.
         ignore_index: the fill of the target where the augmentation leaves the tile; the data set pads edge crops with its
         own ignore_index, and the kernel has one fill for both, so the two must agree.  max_resident_bytes: the budget of
         resident_bytes(dataset) (default: FREE_MEMORY_FRACTION of the device's free memory now).  num_workers: processes
-        for the one-time decode.
+        for the one-time decode.  options: the sampling and augmentation recipe as a sampling.TileOptions, in place of
+        the seven keywords that follow (TileOptions.make checks them), not beside them; the loader reads `self.options` only:
 
         tile_sampling: "all" (every box of the grid once per epoch), "labelled" (only tiles with at least one pixel, and at
         least min_trainable_frac of the tile, that the loss does not ignore) or "balanced" (an epoch of as many tiles, a
@@ -154,7 +159,7 @@ class SceneTileLoader:
         "photometric" (the gain / bias / sigma rows, noise_key, noise_stream) and, with zoom, "src_boxes" (the boxes read)
         beside "boxes" (the boxes they stand for).  The tile-sampling census keeps counting the grid's (jittered) boxes,
         not the zoomed ones; under 'local' mean / std are those of the zoomed source box."""
-        from .sampling import POLICIES, _check_frac, check_zoom_range
+        from .sampling import TileOptions
         self.dataset, self.batch_size, self.device = dataset, int(batch_size), torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("SceneTileLoader keeps the scenes on a ROCm GPU and cuts the batches there; there is no CPU "
@@ -170,20 +175,14 @@ class SceneTileLoader:
         self.shuffle, self.seed, self.drop_last = bool(shuffle), int(seed), bool(drop_last)
         self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
         self.num_workers = int(num_workers)
-        if tile_sampling not in POLICIES:
-            raise ValueError(f"tile_sampling must be one of {POLICIES}, got {tile_sampling!r}")
-        self.tile_sampling = tile_sampling
-        self.min_trainable_frac = _check_frac("min_trainable_frac", min_trainable_frac)
-        self.water_share = _check_frac("water_share", water_share)
-        self.min_water_frac = _check_frac("min_water_frac", min_water_frac)
-        self.crop_jitter = int(crop_jitter)
-        if self.crop_jitter < 0:
-            raise ValueError(f"crop_jitter must be >= 0, got {crop_jitter}")
-        self.zoom = None if zoom is None else check_zoom_range(zoom)
-        self.photometric = None if photometric is None else dict(photometric)
-        if self.photometric is not None:                     # argument errors now
-            from ..augment import sample_photometric
-            sample_photometric(1, 1, self.photometric, np.random.RandomState(0))
+        stated = TileOptions.make(tile_sampling=tile_sampling, min_trainable_frac=min_trainable_frac, water_share=water_share,
+                                  min_water_frac=min_water_frac, crop_jitter=crop_jitter, photometric=photometric,
+                                  zoom=zoom)                                           # argument errors now
+        if options is not None and not isinstance(options, TileOptions):
+            raise TypeError(f"SceneTileLoader(): options must be a TileOptions, got {type(options).__name__}")
+        if options is not None and stated != TileOptions():
+            raise TypeError("SceneTileLoader(): options together with recipe keywords; give one or the other")
+        self.options = stated if options is None else options
         self.noise_key = (self.seed * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03) & (2 ** 64 - 1)
         self._drawn = None               # (epoch, photometric draws, zoomed boxes) of the latest epoch
         self.last_plan = None            # what the latest planned epoch holds (sampling.plan_order's info)
@@ -207,14 +206,10 @@ class SceneTileLoader:
         cp = dataset.dataset[0]["crop_params"] if len(dataset) else None
         self.tile_hw = (cp.max_crop_height, cp.max_crop_width) if cp is not None else None
 
-    @property
-    def _sampling_active(self) -> bool:
-        return self.tile_sampling != "all" or self.crop_jitter > 0 or self.zoom is not None
-
     def __len__(self):
         """Batches per epoch; under a policy other than "all" the planned number for the next epoch (this takes the
         census, so the scenes become resident)."""
-        if self.tile_sampling == "all":
+        if self.options.tile_sampling == "all":
             return len(plan_epoch(len(self.dataset), self.batch_size, 0, False, 0, self.drop_last, self.shard))
         return len(self._plan(self._epoch)[0])
 
@@ -222,26 +217,27 @@ class SceneTileLoader:
         """(batches, boxes) of an epoch under the sampling options: the epoch's boxes (jittered when crop_jitter > 0), their
         census unless the policy is "all" (every rank counts the whole split), the planned order, sharded and batched."""
         from . import sampling
+        o = self.options
         if self._planned is not None and self._planned[0] == epoch:
             return self._planned[1:]
         if self._items is None:
             self._make_resident()
         boxes = [box for _, _, box in self._items]
-        if self.crop_jitter > 0:
-            boxes = sampling.jitter_boxes(boxes, [tuple(label.shape) for _, label, _ in self._items], self.crop_jitter,
+        if o.crop_jitter > 0:
+            boxes = sampling.jitter_boxes(boxes, [tuple(label.shape) for _, label, _ in self._items], o.crop_jitter,
                                           self.seed, epoch)
         th, tw = self.tile_hw
         stats = len(boxes)
-        if self.tile_sampling != "all":
+        if o.tile_sampling != "all":
             stats = self._census
             if stats is None:
                 ctx = self.net._get_ctx(self.device, self.batch_size, th, tw)
                 counts = sampling.label_box_counts(ctx, [(label, box) for (_, label, _), box in zip(self._items, boxes)])
                 stats = sampling.tile_stats(counts.cpu().numpy(), self.ignore_index, int(self.dataset.n_classes))
-                if self.crop_jitter == 0:
+                if o.crop_jitter == 0:
                     self._census = stats
-        order, info = sampling.plan_order(stats, th * tw, self.tile_sampling, min_trainable_frac=self.min_trainable_frac,
-                                          water_share=self.water_share, min_water_frac=self.min_water_frac,
+        order, info = sampling.plan_order(stats, th * tw, o.tile_sampling, min_trainable_frac=o.min_trainable_frac,
+                                          water_share=o.water_share, min_water_frac=o.min_water_frac,
                                           shuffle=self.shuffle, seed=self.seed, epoch=epoch)
         batches = order_batches(order, self.batch_size, self.drop_last, self.shard)
         self._planned, self.last_plan = (epoch, batches, boxes), info
@@ -294,12 +290,12 @@ class SceneTileLoader:
         if self._drawn is not None and self._drawn[0] == epoch:
             return self._drawn[1:]
         photo = zoomed = None
-        if self.photometric is not None:
+        photometric, zoom = self.options.photometric, self.options.zoom
+        if photometric is not None:
             rs = np.random.RandomState([self.seed & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, sampling.PHOTOMETRIC_STREAM])
-            photo = augment.sample_photometric(len(self.dataset), self.dataset.n_channels["ms_image"], self.photometric, rs)
-        if self.zoom is not None:
-            zoomed = sampling.zoom_boxes(boxes, [tuple(label.shape) for _, label, _ in self._items], self.zoom, self.seed,
-                                         epoch)
+            photo = augment.sample_photometric(len(self.dataset), self.dataset.n_channels["ms_image"], photometric, rs)
+        if zoom is not None:
+            zoomed = sampling.zoom_boxes(boxes, [tuple(label.shape) for _, label, _ in self._items], zoom, self.seed, epoch)
         self._drawn = (epoch, photo, zoomed)
         return photo, zoomed
 
@@ -307,7 +303,7 @@ class SceneTileLoader:
         from .. import augment
         from .assemble import scene_train_tiles
         n = len(index)
-        photo, zoomed = self._draws(epoch, boxes) if (self.photometric is not None or self.zoom is not None) else (None, None)
+        photo, zoomed = self._draws(epoch, boxes) if self.options.needs_draws else (None, None)
         if self.transforms is not None:
             flags, angles = augment.sample_transforms(n, self.transforms, self._rng)
         else:
@@ -347,7 +343,7 @@ class SceneTileLoader:
         if self._items is None:
             self._make_resident()
         epoch, self._epoch = self._epoch, self._epoch + 1
-        if self._sampling_active:
+        if self.options.needs_plan:
             batches, boxes = self._plan(epoch)
             for index in batches:
                 yield self._batch(index, boxes, epoch)

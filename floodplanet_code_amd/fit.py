@@ -22,6 +22,12 @@ DATA_ROOT holds CSDAP_complete/.  The train / valid FloodplanetTiles are made as
 tiles through DataLoader workers (datasets.TileLoader with device assembly and resampling).  One JSON line comes out: the
 best checkpoint and the per-epoch history.  The checkpoint's hyper_parameters carry the data set keys, so predict / infer
 run on it without a config file.
+
+fit_model is made of train_epoch, validate, history_entry and TopKCheckpoints; main of cfg_from_args, build_datasets,
+build_loaders and run_summary.  The command line's options belong to four values, each built in one place and handed down
+unchanged: LossOptions (loss_options.py), OptimOptions (optim_options.py), TileOptions (datasets/sampling.py) and LrSchedule
+(schedule.py).  A new training option is one field and one check there, read in that class's from_args, and one flag in
+build_parser below; cfg_from_args and main do not change for it.
 """
 from __future__ import annotations
 
@@ -33,12 +39,11 @@ from typing import Dict, Iterable, List, Optional
 
 import torch
 
+from .datasets.sampling import SAMPLING_KEYWORDS as SAMPLING_OPTIONS, TileOptions
+from .loss_options import BALANCED, LossOptions, parse_class_weights  # noqa: F401 (parse_class_weights: callers find it here)
 from .models import build_model
-from .schedule import KINDS as LR_SCHEDULES, check_schedule, lr_at
 from .optim_options import OptimOptions
-from .unet import check_focal_gamma, check_region_loss
-
-SCHEDULE_OPTIONS = ("lr_schedule", "warmup_steps", "min_lr")       # cfg keys, present only when the command line gave them
+from .schedule import CFG_KEYS as SCHEDULE_OPTIONS, KINDS as LR_SCHEDULES, LrSchedule
 
 DEFAULTS = dict(lr=1e-4, batch_size=10, n_epochs=11, crop_height=300, crop_width=300, ignore_index=0,
                 save_topk_models=3, limit_train_batches=None, limit_val_batches=None, log_image_iter=200,
@@ -87,6 +92,93 @@ def _limited(loader, limit: Optional[int]):
         yield i, b
 
 
+# ---------------------------------------------------------------------------------------------------- fit_model's parts
+def train_epoch(model, opt, loader, limit: Optional[int], schedule: Optional[LrSchedule], n_steps: int, device="cuda:0"):
+    """One epoch of Lightning's automatic optimisation over at most `limit` batches -> (the last step's loss, tiles trained,
+    host seconds, n_steps).  n_steps counts the run's optimiser steps: with a schedule, step n runs at schedule.lr(n), set
+    into the optimiser before it.  The seconds are closed by the epoch's one device synchronise, so they cover finished
+    steps; what the caller reads off the device afterwards sits behind it."""
+    loss, n_tiles, t0 = None, 0, time.perf_counter()
+    for i, batch in _limited(loader, limit):
+        opt.zero_grad()
+        loss = model.training_step(batch, i)
+        loss.backward()
+        n_steps += 1
+        if schedule is not None:
+            opt.param_groups[0]["lr"] = schedule.lr(n_steps)
+        opt.step()
+        model.global_step += 1
+        n_tiles += int(batch["image"].shape[0])
+    if torch.device(device).type == "cuda":
+        torch.cuda.synchronize(device)
+    return loss, n_tiles, time.perf_counter() - t0, n_steps
+
+
+def validate(model, loader, limit: Optional[int]) -> float:
+    """The validation loop over at most `limit` batches, on the weight EMA where the model keeps one (swapped in once) ->
+    val_MulticlassJaccardIndex."""
+    model.valid_metrics.reset()
+    outs = []
+    with model.eval_weights():
+        for i, batch in _limited(loader, limit):
+            outs.append(model.validation_step(batch, i))
+    model.validation_epoch_end(outs)
+    return float(model.logged.get("val_MulticlassJaccardIndex", torch.zeros(())))
+
+
+def history_entry(epoch: int, train_loss: float, miou: float, n_tiles: int, seconds: float, *, train_region=None, lr=None,
+                  clip_state=None, weight_decay=None, decayed_tensors=None, plan=None) -> dict:
+    """An epoch's entry of model.history from the numbers collected; a key after the first four is there only when its
+    number is (fit_model's docstring says when that is)."""
+    entry = {"epoch": epoch, "train_loss": train_loss, "val_MulticlassJaccardIndex": miou,
+             "train_tiles_per_s": n_tiles / seconds if n_tiles and seconds > 0 else None}
+    if train_region is not None:
+        entry["train_region"] = train_region
+    if lr is not None:
+        entry["lr"] = lr                                                     # the last step's
+    if clip_state is not None:
+        entry["grad_norm"] = clip_state["grad_norm"]                         # the last step's, before clipping
+        entry["clipped_steps"] = clip_state["clipped_steps"]                 # of the run so far
+    if weight_decay is not None:
+        entry["weight_decay"] = weight_decay
+        entry["decayed_tensors"] = decayed_tensors
+    if plan is not None:
+        entry["plan"] = dict(plan)
+    return entry
+
+
+class TopKCheckpoints:
+    """The k best checkpoints by val_MulticlassJaccardIndex under exp_dir/checkpoints, named as the reference's fit.py:80-85
+    names them.  Among equal metrics the earlier epoch ranks first.  Without an exp_dir nothing is written and `best`
+    stays ''."""
+
+    def __init__(self, exp_dir: Optional[str], k: int, hyper_parameters: dict):
+        self.dir, self.k, self.hyper_parameters = os.path.join(exp_dir, "checkpoints") if exp_dir else None, k, hyper_parameters
+        self.kept: List = []                                                 # (metric, path), best first
+        if self.dir:
+            os.makedirs(self.dir, exist_ok=True)
+
+    def save(self, model, epoch: int, miou: float) -> None:
+        if not self.dir:
+            return
+        path = os.path.join(self.dir, f"model-epoch={epoch:02d}-val_MulticlassJaccardIndex={miou:.4f}.ckpt")
+        ckpt = {"state_dict": model.state_dict(), "epoch": epoch, "hyper_parameters": dict(self.hyper_parameters)}
+        hook = getattr(model, "on_save_checkpoint", None)                    # (the weight EMA: "ema_state_dict")
+        if hook is not None:
+            hook(ckpt)
+        torch.save(ckpt, path)
+        self.kept.append((miou, path))
+        self.kept.sort(key=lambda t: -t[0])                                  # stable: a tie keeps the earlier epoch ahead
+        for _, stale in self.kept[self.k:]:
+            if os.path.exists(stale):
+                os.remove(stale)
+        self.kept = self.kept[:self.k]
+
+    @property
+    def best(self) -> str:
+        return self.kept[0][1] if self.kept else ""
+
+
 def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int], n_classes: int = 3,
               exp_dir: Optional[str] = None, device="cuda:0", to_rgb_fcn=None, model=None) -> str:
     """Restatement of fit.py:16-103 without Lightning.  Returns the best checkpoint path ('' if exp_dir is None).
@@ -108,83 +200,34 @@ def fit_model(cfg: dict, train_loader, valid_loader, n_channels: Dict[str, int],
                             to_rgb_fcn=to_rgb_fcn, ignore_index=c["ignore_index"], **c["model"].get("model_kwargs", {}))
     model = model.to(device)
     opt = model.configure_optimizers()
-    # lr schedule (cfg keys lr_schedule / warmup_steps / min_lr, present only when asked for): one number per optimiser step,
-    # set into the optimiser's param_groups before the step.  Gradient clipping is the model's (grad_clip_norm -> HipAdam)
-    schedule = None
-    if any(k in c for k in SCHEDULE_OPTIONS):
-        kind, warmup, min_lr = check_schedule(c["lr"], c.get("lr_schedule", "constant"), c.get("warmup_steps", 0),
-                                              c.get("min_lr", 0.0))
-        per_epoch = len(train_loader)
-        if c["limit_train_batches"] is not None:
-            per_epoch = min(per_epoch, int(c["limit_train_batches"]))
-        schedule = dict(base_lr=float(c["lr"]), kind=kind, total_steps=per_epoch * int(c["n_epochs"]), warmup_steps=warmup,
-                        min_lr=min_lr)
+    # one lr per optimiser step where the config has a schedule; gradient clipping is the model's (grad_clip_norm -> HipAdam)
+    # (the loader's length only where it is needed: a loader that plans its epochs takes its census for it)
+    schedule = LrSchedule.from_cfg(c, len(train_loader)) if any(k in c for k in SCHEDULE_OPTIONS) else None
     optim = model.optim_options
     clipping = optim.grad_clip_norm is not None
     n_steps = 0
-    best: List = []                                                          # (metric, path), top-k
-    ckpt_dir = os.path.join(exp_dir, "checkpoints") if exp_dir else None
-    if ckpt_dir:
-        os.makedirs(ckpt_dir, exist_ok=True)
+    checkpoints = TopKCheckpoints(exp_dir, c["save_topk_models"], c)
     history = []
     for epoch in range(c["n_epochs"]):
         model.current_epoch = epoch
-        n_tiles, t0 = 0, time.perf_counter()
-        for i, batch in _limited(train_loader, c["limit_train_batches"]):
-            opt.zero_grad()
-            loss = model.training_step(batch, i)
-            loss.backward()
-            n_steps += 1
-            if schedule is not None:
-                opt.param_groups[0]["lr"] = lr_at(n_steps, **schedule)
-            opt.step()
-            model.global_step += 1
-            n_tiles += int(batch["image"].shape[0])
-        if torch.device(device).type == "cuda":
-            torch.cuda.synchronize(device)                                   # one sync: the rate covers finished steps
-        train_seconds = time.perf_counter() - t0
-        train_region = None                                                  # R of the last step, before validation rewrites it
-        if getattr(model, "region_weight", 0.0) > 0.0 and n_tiles:
-            train_region = float(model.model.last_region_terms()[0])
-        clip_state = model.model.grad_clip_state() if clipping and n_tiles else None   # read once per epoch, behind the sync
-        model.valid_metrics.reset()
-        outs = []
-        with model.eval_weights():                                           # the weight EMA, swapped in once per epoch
-            for i, batch in _limited(valid_loader, c["limit_val_batches"]):
-                outs.append(model.validation_step(batch, i))
-        model.validation_epoch_end(outs)
-        miou = float(model.logged.get("val_MulticlassJaccardIndex", torch.zeros(())))
-        history.append({"epoch": epoch, "train_loss": float(loss.detach()), "val_MulticlassJaccardIndex": miou,
-                        "train_tiles_per_s": n_tiles / train_seconds if n_tiles and train_seconds > 0 else None})
-        if train_region is not None:
-            history[-1]["train_region"] = train_region
-        if schedule is not None or clipping:
-            history[-1]["lr"] = float(opt.param_groups[0]["lr"])             # the last step's
-        if clip_state is not None:
-            history[-1]["grad_norm"] = clip_state["grad_norm"]               # the last step's, before clipping
-            history[-1]["clipped_steps"] = clip_state["clipped_steps"]       # of the run so far
-        if optim.weight_decay > 0.0:
-            history[-1]["weight_decay"] = float(opt.param_groups[0]["weight_decay"])
-            history[-1]["decayed_tensors"] = len(model.model.decayed_parameter_names())
-        plan =getattr(train_loader, "last_plan", None)                      # a loader that chooses its tiles says which
-        if plan is not None:
-            history[-1]["plan"] = dict(plan)
-        if ckpt_dir:
-            path = os.path.join(ckpt_dir, f"model-epoch={epoch:02d}-val_MulticlassJaccardIndex={miou:.4f}.ckpt")
-            ckpt = {"state_dict": model.state_dict(), "epoch": epoch, "hyper_parameters": dict(c)}
-            hook = getattr(model, "on_save_checkpoint", None)                # (the weight EMA: "ema_state_dict")
-            if hook is not None:
-                hook(ckpt)
-            torch.save(ckpt, path)
-            best.append((miou, path))
-            best.sort(key=lambda t: -t[0])
-            for _, stale in best[c["save_topk_models"]:]:
-                if os.path.exists(stale):
-                    os.remove(stale)
-            best = best[:c["save_topk_models"]]
+        loss, n_tiles, seconds, n_steps = train_epoch(model, opt, train_loader, c["limit_train_batches"], schedule, n_steps,
+                                                      device)
+        # read once per epoch, behind train_epoch's synchronise: R of the last step, before validation rewrites it
+        region = getattr(model, "region_weight", 0.0) > 0.0 and n_tiles
+        train_region = float(model.model.last_region_terms()[0]) if region else None
+        clip_state = model.model.grad_clip_state() if clipping and n_tiles else None
+        miou = validate(model, valid_loader, c["limit_val_batches"])
+        decaying = optim.weight_decay > 0.0
+        history.append(history_entry(
+            epoch, float(loss.detach()), miou, n_tiles, seconds, train_region=train_region, clip_state=clip_state,
+            lr=float(opt.param_groups[0]["lr"]) if schedule is not None or clipping else None,
+            weight_decay=float(opt.param_groups[0]["weight_decay"]) if decaying else None,
+            decayed_tensors=len(model.model.decayed_parameter_names()) if decaying else None,
+            plan=getattr(train_loader, "last_plan", None)))                  # a loader that chooses its tiles says which
+        checkpoints.save(model, epoch, miou)
     model.history = history
     fit_model.last_model = model
-    return best[0][1] if best else ""
+    return checkpoints.best
 
 
 # ---------------------------------------------------------------------------------------------------------- command line
@@ -288,195 +331,80 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
-def parse_class_weights(values, n_classes: Optional[int] = None):
-    """--class_weights -> None, the word 'balanced' or a list of floats (n_classes of them when n_classes is known)."""
-    if values is None:
-        return None
-    if len(values) == 1 and values[0] == "balanced":
-        return "balanced"
-    try:
-        w = [float(v) for v in values]
-    except ValueError:
-        raise ValueError(f"--class_weights takes 'balanced' or one number per class, got {list(values)}") from None
-    if n_classes is not None and len(w) != int(n_classes):
-        raise ValueError(f"--class_weights: {len(w)} weights for {n_classes} classes")
-    return w
-
-
-SAMPLING_OPTIONS = ("tile_sampling", "min_trainable_frac", "water_share", "min_water_frac", "crop_jitter")
-
-
-def sampling_from_args(args) -> dict:
-    """The tile-sampling options a command line gave ({} for none), checked: they belong to --loader scene, fractions lie in
-    [0, 1], the jitter is >= 0.  The keys are SceneTileLoader's keyword arguments."""
-    given = {k: getattr(args, k, None) for k in SAMPLING_OPTIONS}
-    given = {k: v for k, v in given.items() if v is not None}
-    if given and getattr(args, "loader", "scene") != "scene":
-        raise ValueError("--" + ", --".join(given) + " need --loader scene: the streaming loader cuts a fixed grid")
-    for k in ("min_trainable_frac", "water_share", "min_water_frac"):
-        if k in given and not 0.0 <= given[k] <= 1.0:
-            raise ValueError(f"--{k} must lie in [0, 1], got {given[k]}")
-    if given.get("crop_jitter", 0) < 0:
-        raise ValueError(f"--crop_jitter must be >= 0, got {given['crop_jitter']}")
-    return given
-
-
-# --aug_* flag -> the key of augment.sample_photometric's config
-PHOTOMETRIC_FLAGS = {"aug_gain": "gain", "aug_band_gain": "band_gain", "aug_brightness": "brightness", "aug_noise": "noise",
-                     "aug_band_drop": "band_drop", "aug_likelihood": "likelihood"}
-
-
-def augmentation_from_args(args) -> dict:
-    """The radiometric and zoom options a command line gave ({} for none), checked, as SceneTileLoader's keyword arguments
-    `photometric` (augment.sample_photometric's config) and `zoom` (zmin, zmax).  They belong to --loader scene;
-    --aug_likelihood alone varies nothing and is an error."""
-    import numpy as np
-    from .augment import sample_photometric
-    from .datasets.sampling import check_zoom_range
-    photo = {key: getattr(args, flag, None) for flag, key in PHOTOMETRIC_FLAGS.items()}
-    photo = {k: float(v) for k, v in photo.items() if v is not None}
-    zoom = getattr(args, "aug_zoom", None)
-    given = ["aug_" + k for k in photo] + (["aug_zoom"] if zoom is not None else [])
-    if given and getattr(args, "loader", "scene") != "scene":
-        raise ValueError("--" + ", --".join(given) + " need --loader scene: the fused scene-tile kernel applies them")
-    out = {}
-    if photo:
-        if set(photo) == {"likelihood"}:
-            raise ValueError("--aug_likelihood needs one of --aug_gain, --aug_band_gain, --aug_brightness, --aug_noise, "
-                             "--aug_band_drop")
-        try:
-            sample_photometric(1, 1, photo, np.random.RandomState(0))
-        except ValueError as e:
-            raise ValueError(str(e).replace("photometric:", "--aug_*:")) from None
-        out["photometric"] = photo
-    if zoom is not None:
-        out["zoom"] = list(check_zoom_range(zoom))
-    return out
-
-
-REGION_KINDS = {"dice": (0.5, 0.5), "jaccard": (1.0, 1.0)}
-
-
-def region_from_args(args) -> dict:
-    """The region term a command line gave, as model keyword arguments ({} for none), checked: --region_weight, --tversky and
-    --region_smooth need --region_loss, --tversky goes with `tversky` and only with it."""
-    kind = getattr(args, "region_loss", None)
-    weight, tversky, smooth = (getattr(args, k, None) for k in ("region_weight", "tversky", "region_smooth"))
-    if kind is None:
-        given = [n for n, v in (("region_weight", weight), ("tversky", tversky), ("region_smooth", smooth)) if v is not None]
-        if given:
-            raise ValueError("--" + ", --".join(given) + " need --region_loss")
-        return {}
-    if (kind == "tversky") != (tversky is not None):
-        raise ValueError("--region_loss tversky and --tversky A B go together")
-    alpha, beta = tversky if kind == "tversky" else REGION_KINDS[kind]
-    w, a, b, s = check_region_loss(1.0 if weight is None else weight, alpha, beta, 1.0 if smooth is None else smooth)
-    return dict(region_weight=w, region_alpha=a, region_beta=b, region_smooth=s)
-
-
-def schedule_from_args(args) -> dict:
-    """The lr-schedule options a command line gave, as top-level config keys ({} for none), checked against --lr."""
-    given = {k: getattr(args, k, None) for k in SCHEDULE_OPTIONS}
-    given = {k: v for k, v in given.items() if v is not None}
-    if given:
-        check_schedule(args.lr, given.get("lr_schedule", "constant"), given.get("warmup_steps", 0), given.get("min_lr", 0.0))
-    return given
+MODEL_KEYWORDS = ("optimizer_name", "base_channels", "precision")      # the reference's; the extensions follow them
 
 
 def cfg_from_args(args, class_weights=None) -> dict:
-    """The reference-style config of a command line: what fit_model trains with and dumps into the checkpoint.
-    class_weights: the resolved numeric weights (the data decides 'balanced' and the class count, so main() resolves them);
-    they, --label_smoothing, --focal_gamma, --region_loss, --ema_decay and --no_ema_warmup enter model_kwargs only when set, and the
-    tile-sampling options a `sampling` key beside `model` only when given, so a plain command line gives the config it
-    always gave."""
-    norm_mode = None if args.norm_mode == "none" else args.norm_mode
-    parsed = parse_class_weights(getattr(args, "class_weights", None), N_CLASSES)
-    if class_weights is None and parsed is not None and parsed != "balanced":
-        class_weights = parsed
-    extension_kwargs = {}                  # the model keywords beyond the reference's: the loss options, then the optimiser's
-    if class_weights is not None:
-        extension_kwargs["class_weights"] = [float(v) for v in class_weights]
-    if float(getattr(args, "label_smoothing", 0.0)) != 0.0:
-        extension_kwargs["label_smoothing"] = float(args.label_smoothing)
-    gamma = check_focal_gamma(getattr(args, "focal_gamma", 0.0), getattr(args, "label_smoothing", 0.0))
-    if gamma != 0.0:
-        extension_kwargs["focal_gamma"] = gamma
-    extension_kwargs.update(region_from_args(args))
-    extension_kwargs.update(OptimOptions.from_args(args).given_kwargs())
-    schedule = schedule_from_args(args)
-    sampling = sampling_from_args(args)
+    """The reference-style config of a command line: what fit_model trains with and dumps into the checkpoint.  Each concern
+    is read and checked by its own options value -- LossOptions, OptimOptions, TileOptions, LrSchedule (.from_args) -- and
+    recorded only where the command line set it, so a plain command line gives the config it always gave: the loss and
+    optimiser keywords in model_kwargs, `sampling` and `augmentation` beside `model`, the schedule's keys at the top level.
+    class_weights: the resolved numeric weights in place of the command line's (the data decides 'balanced', so main()
+    resolves it; set_class_weights does the same to a finished config)."""
+    loss, optim = LossOptions.from_args(args, N_CLASSES), OptimOptions.from_args(args)
+    schedule, tiles = LrSchedule.from_args(args), TileOptions.from_args(args)
     cfg = dict(lr=args.lr, batch_size=args.batch_size, n_epochs=args.n_epochs, crop_height=args.crop[0],
                crop_width=args.crop[1], crop_stride=args.stride, ignore_index=args.ignore_index,
                save_topk_models=args.save_topk_models, seed_num=args.seed, n_workers=args.n_workers,
                eval_region=list(args.eval_region) if args.eval_region else None, train_split_pct=args.train_split_pct,
-               norm_mode=norm_mode, norm_params=args.norm_params,
+               norm_mode=None if args.norm_mode == "none" else args.norm_mode, norm_params=args.norm_params,
                dataset=dict(name="floodplanet", sensor=args.sensor, channels=args.channels, dataset_kwargs=None),
                model=dict(name=args.model, model_kwargs=dict(optimizer_name="adam", base_channels=args.base_channels,
-                                                             precision=args.precision, **extension_kwargs)))
-    if sampling:
-        cfg["sampling"] = sampling
-    augmentation = augmentation_from_args(args)
-    if augmentation:                       # the training recipe's record; predict and infer do not read it
-        cfg["augmentation"] = augmentation
-    cfg.update(schedule)
+                                                             precision=args.precision,
+                                                             **loss.given_kwargs(getattr(args, "region_loss", None) is not None),
+                                                             **optim.given_kwargs())))
+    if class_weights is not None:
+        set_class_weights(cfg, class_weights)
+    if tiles.sampling_cfg():
+        cfg["sampling"] = tiles.sampling_cfg()
+    if tiles.augmentation_cfg():               # the training recipe's record; predict and infer do not read it
+        cfg["augmentation"] = tiles.augmentation_cfg()
+    if schedule is not None:
+        cfg.update(schedule.given_cfg())
     return cfg
 
 
-def main(argv: Optional[List[str]] = None) -> dict:
+def set_class_weights(cfg: dict, weights) -> None:
+    """The one class_weights entry of the config's model_kwargs, where cfg_from_args lists it: first of the extensions."""
+    kwargs = cfg["model"]["model_kwargs"]
+    items = [(k, v) for k, v in kwargs.items() if k != "class_weights"]
+    items.insert(len(MODEL_KEYWORDS), ("class_weights", [float(v) for v in weights]))
+    kwargs.clear()
+    kwargs.update(items)
+
+
+# --------------------------------------------------------------------------------------------------------- main's parts
+def build_datasets(args, cfg: dict):
+    """(train, valid) FloodplanetTiles as fit.py:25-53 makes them (the transforms run on the device, per batch)."""
     import copy
-    from .datasets import FloodplanetTiles, SceneTileLoader, TileLoader, generate_image_slice_object
-    ap = build_parser()
-    args = ap.parse_args(argv)
-    try:
-        wanted = parse_class_weights(args.class_weights, N_CLASSES)
-        cfg = cfg_from_args(args)
-    except ValueError as e:
-        ap.error(str(e))
-    c = dict(DEFAULTS)
-    c.update(cfg)
-    slice_params = generate_image_slice_object(c["crop_height"], c["crop_width"], c["crop_stride"])
+    from .datasets import FloodplanetTiles, generate_image_slice_object
+    slice_params = generate_image_slice_object(cfg["crop_height"], cfg["crop_width"], cfg["crop_stride"])
+    return tuple(FloodplanetTiles(args.data_root, split, slice_params, eval_region=copy.copy(cfg["eval_region"]),
+                                  sensor=args.sensor, channels=args.channels, norm_mode=cfg["norm_mode"],
+                                  ignore_index=cfg["ignore_index"], seed_num=cfg["seed_num"],
+                                  train_split_pct=cfg["train_split_pct"], norm_params=cfg["norm_params"])
+                 for split in ("train", "valid"))
 
-    def tiles(split):                                    # fit.py:25-53 (the transforms run on the device, per batch)
-        return FloodplanetTiles(args.data_root, split, slice_params, eval_region=copy.copy(c["eval_region"]),
-                                sensor=args.sensor, channels=args.channels, norm_mode=c["norm_mode"],
-                                ignore_index=c["ignore_index"], seed_num=c["seed_num"],
-                                train_split_pct=c["train_split_pct"], norm_params=c["norm_params"])
 
-    train_ds, valid_ds = tiles("train"), tiles("valid")
-    class_counts = None
-    if wanted is not None and wanted != "balanced" and len(wanted) != train_ds.n_classes:
-        ap.error(f"--class_weights: {len(wanted)} weights for {train_ds.n_classes} classes")
-    if wanted == "balanced" and args.loader == "tile":
-        # the streaming loader's label rasters are on the host: the contract of fu_label_class_counts in numpy, same boxes
-        from .datasets.class_weights import balanced_class_weights, dataset_label_boxes, label_class_counts_host
-        class_counts = label_class_counts_host(dataset_label_boxes(train_ds), c["ignore_index"], train_ds.n_classes)
-        cfg = cfg_from_args(args, balanced_class_weights(class_counts, c["ignore_index"]).tolist())
-        c.update(cfg)
-    torch.manual_seed(c["seed_num"])                     # the initial weights are drawn here, not in fit_model
-    model = build_model(c["model"]["name"], train_ds.n_channels, train_ds.n_classes, c["lr"],
-                        log_image_iter=c["log_image_iter"], to_rgb_fcn=None, ignore_index=c["ignore_index"],
-                        **c["model"]["model_kwargs"]).to(args.device)
-    transforms = None if args.no_transforms else {}
+def build_loaders(args, cfg: dict, model, train_ds, valid_ds):
+    """(train, valid) loaders of --loader.  The scene loader borrows the device context of the model's net, so the model
+    comes first; only the train split is shuffled, transformed and cut by the config's recipe (TileOptions.from_cfg)."""
+    from .datasets import SceneTileLoader, TileLoader
+    common = dict(seed=cfg["seed_num"], ignore_index=cfg["ignore_index"], num_workers=args.n_workers)
+    train_only = dict(shuffle=not args.no_shuffle, transforms=None if args.no_transforms else {})
     if args.loader == "scene":
-        common = dict(net=model.model, seed=c["seed_num"], ignore_index=c["ignore_index"], num_workers=args.n_workers)
-        train = SceneTileLoader(train_ds, c["batch_size"], args.device, shuffle=not args.no_shuffle, transforms=transforms,
-                                **common, **cfg.get("sampling", {}), **cfg.get("augmentation", {}))
-        valid = SceneTileLoader(valid_ds, c["batch_size"], args.device, **common)       # every tile, where the grid puts it
-        if wanted == "balanced":                         # counted on the device, from the label rasters resident there
-            from .datasets.class_weights import balanced_class_weights
-            class_counts = train.class_counts().cpu().numpy()
-            cfg = cfg_from_args(args, balanced_class_weights(class_counts, c["ignore_index"]).tolist())
-            c.update(cfg)
-            model.replace_loss_options(class_weight=cfg["model"]["model_kwargs"]["class_weights"])
-    else:
-        common = dict(seed=c["seed_num"], ignore_index=c["ignore_index"], num_workers=args.n_workers,
-                      device_assembly=True, device_resize=True)
-        train = TileLoader(train_ds, c["batch_size"], args.device, shuffle=not args.no_shuffle, transforms=transforms,
-                           **common)
-        valid = TileLoader(valid_ds, c["batch_size"], args.device, **common)
-    best = fit_model(cfg, train, valid, train_ds.n_channels, train_ds.n_classes, exp_dir=args.exp_dir, device=args.device,
-                     model=model)
-    out = {"checkpoint": best, "loader": args.loader, "train_tiles": len(train_ds), "valid_tiles": len(valid_ds),
+        train_only["options"] = TileOptions.from_cfg(cfg)
+
+    def make(ds, **kw):
+        if args.loader == "scene":
+            return SceneTileLoader(ds, cfg["batch_size"], args.device, net=model.model, **common, **kw)
+        return TileLoader(ds, cfg["batch_size"], args.device, device_assembly=True, device_resize=True, **common, **kw)
+    return make(train_ds, **train_only), make(valid_ds)              # valid: every tile, where the grid puts it
+
+
+def run_summary(cfg: dict, loader: str, checkpoint: str, n_train: int, n_valid: int, model, class_counts) -> dict:
+    """The record main() prints as one JSON line."""
+    out = {"checkpoint": checkpoint, "loader": loader, "train_tiles": n_train, "valid_tiles": n_valid,
            "history": model.history,
            "class_counts": None if class_counts is None else [int(v) for v in class_counts],
            "class_weights": None if model.class_weights is None else list(model.class_weights)}
@@ -487,6 +415,39 @@ def main(argv: Optional[List[str]] = None) -> dict:
     if model.weight_decay > 0.0:
         out["weight_decay"] = model.weight_decay
         out["decayed_tensors"] = len(model.model.decayed_parameter_names())
+    return out
+
+
+def main(argv: Optional[List[str]] = None) -> dict:
+    from .datasets.class_weights import balanced_class_weights, dataset_label_boxes, label_class_counts_host
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    try:
+        cfg = {**DEFAULTS, **cfg_from_args(args)}          # the one config: what fit_model merges and the checkpoint holds
+    except ValueError as e:
+        ap.error(str(e))
+    balanced = parse_class_weights(args.class_weights) == BALANCED
+    train_ds, valid_ds = build_datasets(args, cfg)
+    wanted = cfg["model"]["model_kwargs"].get("class_weights")
+    if wanted is not None and len(wanted) != train_ds.n_classes:
+        ap.error(f"--class_weights: {len(wanted)} weights for {train_ds.n_classes} classes")
+    class_counts = None
+    if balanced and args.loader == "tile":
+        # the streaming loader's label rasters are on the host: the contract of fu_label_class_counts in numpy, same boxes
+        class_counts = label_class_counts_host(dataset_label_boxes(train_ds), cfg["ignore_index"], train_ds.n_classes)
+        set_class_weights(cfg, balanced_class_weights(class_counts, cfg["ignore_index"]))
+    torch.manual_seed(cfg["seed_num"])                     # the initial weights are drawn here, not in fit_model
+    model = build_model(cfg["model"]["name"], train_ds.n_channels, train_ds.n_classes, cfg["lr"],
+                        log_image_iter=cfg["log_image_iter"], to_rgb_fcn=None, ignore_index=cfg["ignore_index"],
+                        **cfg["model"]["model_kwargs"]).to(args.device)
+    train, valid = build_loaders(args, cfg, model, train_ds, valid_ds)
+    if balanced and args.loader == "scene":                # counted on the device, from the label rasters resident there
+        class_counts = train.class_counts().cpu().numpy()
+        set_class_weights(cfg, balanced_class_weights(class_counts, cfg["ignore_index"]))
+        model.replace_loss_options(class_weight=cfg["model"]["model_kwargs"]["class_weights"])
+    best = fit_model(cfg, train, valid, train_ds.n_channels, train_ds.n_classes, exp_dir=args.exp_dir, device=args.device,
+                     model=model)
+    out = run_summary(cfg, args.loader, best, len(train_ds), len(valid_ds), model, class_counts)
     print(json.dumps(out))
     return out
 

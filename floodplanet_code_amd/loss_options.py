@@ -1,9 +1,10 @@
 """LossOptions: the options of the fused cross entropy (HipUNet.loss) as one checked value.
 
-The command line, the models, the data-parallel trainer and HipUNet.loss / train_step all build one through
+The command line (from_args), the models, the data-parallel trainer and HipUNet.loss / train_step all build one through
 LossOptions.make and hand that single object down to HipUNet._loss_raw, which picks the C entry point from it.  A new
-option is one field here, its keyword and check in make, and one argument at the library call.  Host arithmetic only: neither torch
-nor the GPU library is imported.
+option is one field here, its keyword and check in make, its flag in from_args and its keyword in given_kwargs (what a
+fit config records), and one argument at the library call.  Host arithmetic only: neither torch nor the GPU library is
+imported.
 """
 from __future__ import annotations
 
@@ -44,6 +45,25 @@ def check_region_loss(weight=0.0, alpha=0.5, beta=0.5, smooth=1.0):
     return w, a, b, s
 
 
+REGION_KINDS = {"dice": (0.5, 0.5), "jaccard": (1.0, 1.0)}      # --region_loss -> (alpha, beta); tversky takes its own
+BALANCED = "balanced"                                           # --class_weights balanced, until the data resolves it
+
+
+def parse_class_weights(values, n_classes: Optional[int] = None):
+    """--class_weights -> None, the word 'balanced' or a list of floats (n_classes of them when n_classes is known)."""
+    if values is None:
+        return None
+    if len(values) == 1 and values[0] == BALANCED:
+        return BALANCED
+    try:
+        w = [float(v) for v in values]
+    except ValueError:
+        raise ValueError(f"--class_weights takes 'balanced' or one number per class, got {list(values)}") from None
+    if n_classes is not None and len(w) != int(n_classes):
+        raise ValueError(f"--class_weights: {len(w)} weights for {n_classes} classes")
+    return w
+
+
 @dataclasses.dataclass(frozen=True)
 class LossOptions:
     """class_weight is kept as the object it was given (None, a sequence or a tensor): HipUNet._class_weight_dev checks and
@@ -75,6 +95,45 @@ class LossOptions:
         if kind != "ce" and region[1:] != (cls.region_alpha, cls.region_beta, cls.region_smooth):      # (the defaults)
             raise ValueError(f"region_alpha / region_beta / region_smooth belong to kind='ce'; kind={kind!r} takes none")
         return cls(class_weight, eps, gamma, *region)
+
+    @classmethod
+    def from_args(cls, args, n_classes: Optional[int] = None) -> "LossOptions":
+        """The options a fit command line gave.  On top of make's checks, the rules that hold on the command line only:
+        --region_weight, --tversky and --region_smooth need --region_loss, and --tversky goes with `tversky` and only with
+        it.  --class_weights balanced stays the word BALANCED in class_weight: the data decides it, so the caller does."""
+        weights = parse_class_weights(getattr(args, "class_weights", None), n_classes)       # reported first, as ever;
+        smoothing = getattr(args, "label_smoothing", 0.0)
+        gamma = check_focal_gamma(getattr(args, "focal_gamma", 0.0), smoothing)              # then the focal exponent
+        kind = getattr(args, "region_loss", None)
+        weight, tversky, smooth = (getattr(args, k, None) for k in ("region_weight", "tversky", "region_smooth"))
+        region = {}
+        if kind is None:
+            given = [n for n, v in (("region_weight", weight), ("tversky", tversky), ("region_smooth", smooth)) if v is not None]
+            if given:
+                raise ValueError("--" + ", --".join(given) + " need --region_loss")
+        else:
+            if (kind == "tversky") != (tversky is not None):
+                raise ValueError("--region_loss tversky and --tversky A B go together")
+            alpha, beta = tversky if kind == "tversky" else REGION_KINDS[kind]
+            region = dict(region_weight=1.0 if weight is None else weight, region_alpha=alpha, region_beta=beta,
+                          region_smooth=1.0 if smooth is None else smooth)
+        return cls.make(n_classes, class_weight=weights, label_smoothing=smoothing, focal_gamma=gamma, **region)
+
+    def given_kwargs(self, region: Optional[bool] = None) -> dict:
+        """The model keywords of what is switched on, in the order a fit config lists them: class_weights (the model's
+        plural; not while it is still BALANCED), label_smoothing, focal_gamma, then the four region_* together.  region:
+        whether the region term was named -- a command line that names --region_loss records its four numbers whatever
+        they are, a weight of 0 included; None: when they are not the defaults."""
+        out = {}
+        if self.class_weight is not None and not isinstance(self.class_weight, str):
+            out["class_weights"] = [float(v) for v in self.class_weight]
+        if self.label_smoothing != 0.0:
+            out["label_smoothing"] = self.label_smoothing
+        if self.focal_gamma != 0.0:
+            out["focal_gamma"] = self.focal_gamma
+        if self.region != LossOptions().region if region is None else region:
+            out.update(zip(("region_weight", "region_alpha", "region_beta", "region_smooth"), self.region))
+        return out
 
     @property
     def region(self) -> Tuple[float, float, float, float]:

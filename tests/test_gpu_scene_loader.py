@@ -323,6 +323,40 @@ def test_second_epoch_reads_no_file_and_allocates_nothing_that_stays(tmp_path, m
     assert torch.cuda.memory_allocated() <= base
 
 
+def test_options_and_keywords_build_the_same_loader(tmp_path):
+    """SceneTileLoader(options=TileOptions.make(...)) against the same recipe as keywords, everything switched on: the one
+    place where the two construction routes could part.  Two epochs, every tensor bit and every record equal."""
+    from floodplanet_code_amd.datasets.sampling import TileOptions
+    ds = _tree(tmp_path, "local")
+    net = HipUNet(2, 3, base_channels=4).to(DEV).eval()
+    recipe = dict(tile_sampling="balanced", water_share=0.4, min_trainable_frac=0.05, min_water_frac=0.25, crop_jitter=5,
+                  photometric=dict(gain=0.2, band_gain=0.05, brightness=0.1, noise=0.05, band_drop=0.2, likelihood=0.8),
+                  zoom=(0.7, 1.4))
+    common = dict(shuffle=True, transforms={}, seed=11)
+    by_options = SceneTileLoader(ds, 4, DEV, net, options=TileOptions.make(**recipe), **common)
+    by_keywords = SceneTileLoader(ds, 4, DEV, net, **recipe, **common)
+    assert by_options.options == by_keywords.options and by_options.options.needs_plan and by_options.options.needs_draws
+    for epoch in range(2):
+        a_epoch, b_epoch = list(by_options), list(by_keywords)
+        torch.cuda.synchronize()
+        assert len(a_epoch) == len(b_epoch) > 1
+        assert by_options.last_plan == by_keywords.last_plan and not by_options.last_plan["degraded"]
+        for a, b in zip(a_epoch, b_epoch):
+            assert set(a) == set(b) >= {"boxes", "src_boxes", "photometric"}
+            for key in ("image", "mean", "std"):
+                assert _bits_equal(a[key], b[key]), (key, epoch)
+            assert torch.equal(a["target"], b["target"])
+            assert a["index"] == b["index"] and a["boxes"] == b["boxes"] and a["src_boxes"] == b["src_boxes"]
+            assert np.array_equal(a["flags"], b["flags"]) and np.array_equal(a["angles"], b["angles"])
+            pa, pb = a["photometric"], b["photometric"]
+            assert set(pa) == set(pb) and pa["noise_key"] == pb["noise_key"]
+            for key in ("gain", "bias", "sigma", "noise_stream"):
+                assert pa[key].dtype == pb[key].dtype and np.array_equal(pa[key], pb[key]), (key, epoch)
+        assert any(s != g for a in a_epoch for s, g in zip(a["src_boxes"], a["boxes"]))      # (the recipe did act)
+    with pytest.raises(TypeError):
+        SceneTileLoader(ds, 4, DEV, net, options=by_options.options, crop_jitter=5)
+
+
 # ------------------------------------------------------------------------------------------------------------ end to end
 def _fit_args(root, exp, loader, extra=()):
     return [root, "--exp_dir", exp, "--sensor", "S1", "--eval_region", "RegB", "--crop", "64", "64", "--stride", "32",
