@@ -135,7 +135,7 @@ class FuMaskBox(C.Structure):
 
 
 class FuTiffLayout(C.Structure):
-    """fu_tiff_layout (include/floodunet.h): how a TIFF's decoded segments lie in one buffer, for fu_tiff_unpack."""
+    """fu_tiff_layout (include/floodunet.h): how a TIFF's decoded segments lie in one buffer, for fu_tiff_unpack and fu_tiff_pack."""
     _fields_ = [(name, C.c_int32) for name in ("width", "height", "samples", "bytes_per_sample", "sample_kind", "big_endian",
                                                "planar", "tiled", "seg_w", "seg_h", "predictor", "reserved")]
 
@@ -236,6 +236,7 @@ SIGNATURES = {
     "fu_tiff_lzw_decode": (_i64, [_p, _i64, _p, _i64]),
     "fu_tiff_packbits_decode": (_i64, [_p, _i64, _p, _i64]),
     "fu_tiff_unpack": (_i, [_p, _i64, FuTiffLayout, C.POINTER(C.c_int32), _i, _p, _p]),
+    "fu_tiff_pack": (_i, [_p, _i64, _i64, _i64, FuTiffLayout, _p, _i64, _p]),
     "fu_eval_prob_hist": (_i, [_p, _p, _i, _i, _p, _p, _p]),
     "fu_prob_hist": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p, _p]),
     "fu_sieve_workspace_bytes": (_i64, [_i, _i]),

@@ -612,6 +612,11 @@ int fu_tiff_unpack(const uint8_t* src, int64_t n_bytes, fu_tiff_layout layout, c
   return launch_tiff_unpack(src, n_bytes, layout, bands, n_bands, out, (hipStream_t)stream);
 }
 
+int fu_tiff_pack(const void* src, int64_t band_stride, int64_t row_stride, int64_t col_stride, fu_tiff_layout layout,
+                 uint8_t* dst, int64_t n_bytes, fu_stream stream) {
+  return launch_tiff_pack(src, band_stride, row_stride, col_stride, layout, dst, n_bytes, (hipStream_t)stream);
+}
+
 int fu_eval_prob_hist(fu_ctx* c, const int64_t* target, int ignore_index, int n_bins, int64_t* hist_out, int64_t* top_out,
                       fu_stream stream) {
   FU_REQUIRE(c && target, "fu_eval_prob_hist: null context / target");

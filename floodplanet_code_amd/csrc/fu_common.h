@@ -622,6 +622,10 @@ int launch_mask_box_counts(DeviceTable& table, int n, const fu_mask_box* entries
 // checks every argument (n_bytes against the layout's arithmetic total included) before it launches
 int launch_tiff_unpack(const uint8_t* src, int64_t n_bytes, const fu_tiff_layout& layout, const int32_t* bands, int n_bands,
                        float* out, hipStream_t s);
+// fu_tiff_pack (fu_tiff_pack.hip): the inverse -- a strided device raster -> the predictor-applied, tile- or strip-cut byte
+// buffer of a TIFF writer, one launch; checks every argument (n_bytes against the layout's total included) before it launches
+int launch_tiff_pack(const void* src, int64_t band_stride, int64_t row_stride, int64_t col_stride, const fu_tiff_layout& layout,
+                     uint8_t* dst, int64_t n_bytes, hipStream_t s);
 // fu_map_components / fu_map_sieve (fu_post.hip): union-find labelling of a uint8 map (the label of a pixel = the smallest
 // linear index of its component) and the connected-component sieve on top of it; the caller has checked every argument.
 // workspace: sieve_workspace_bytes(h, w) = 16 B per pixel (64-bit donor keys, labels, sizes); stats: int64[2] ADDED to, or null

@@ -26,7 +26,7 @@ per pixel in the segment, per segment row a byte-wise running sum modulo 256 wit
 then byte b (most significant first) of value i is byte b * wc + i of the row, in both file byte orders.
 
 Not supported (TiffError naming the cause): JPEG, ZSTD, LERC, WebP and every other scheme, sub-byte samples, mixed sample
-types.  Writing compressed or BigTIFF files is out of scope.
+types.  Writing is datasets/geotiff_write.py: pack_host there is the exact inverse of unpack_host here.
 """
 from __future__ import annotations
 

@@ -62,8 +62,8 @@ else the parent directory.  What runs differently:
     uploaded as stored and unpacked by ONE kernel launch (fu_tiff_unpack: predictor, byte swap, tiles, band choice,
     conversion) into the very fp32 tensor the host route uploads; device does so for every file, host puts every file
     through the numpy statement.  Everything behind that tensor is the same code, so the routes write identical files.
-    Out of scope: writing compressed or BigTIFF outputs, JPEG / ZSTD / LERC, sub-byte samples, overviews and mask IFDs
-    (the first IFD is the scene), entropy decoding on the GPU.
+    Out of scope: JPEG / ZSTD / LERC, sub-byte samples, overviews and mask IFDs (the first IFD is the scene), entropy
+    decoding on the GPU.
   * extension: --write_vectors writes the water bodies as polygons, <image>.geojson beside <image>.tif: one Polygon
     feature, outer ring and holes, per connected patch (--vector_connectivity 4|8, default the sieve's, else 4) of the
     values --vector_values (default 255) of the class map as written, so after the threshold, the mask and the sieve.
@@ -78,12 +78,27 @@ else the parent directory.  What runs differently:
     records and the summary gain "vectors".  Without --write_vectors nothing of this runs and every file is byte for
     byte what it was.  Out of scope: simplification and smoothing, MultiPolygons by value, Shapefile / GeoPackage,
     vectors in predict.
+  * extension: the rasters need not be classic uncompressed strip TIFFs either.  --out_compress deflate [--out_level 1..9]
+    [--out_predictor auto|off], --out_tile [N], --out_bigtiff auto|yes|no and --out_threads T choose Deflate (zlib, per
+    segment, on a pool of T threads, default 4), the predictor (auto: horizontal differencing for the uint8 rasters, the
+    floating-point predictor for fp32), N x N tiles (N a multiple of 16, 256 when the flag stands alone) instead of 16-row
+    strips, and BigTIFF (auto: only where classic TIFF cannot hold the file).  datasets/geotiff_write.py holds the byte
+    layout (pack_host) and the container (write_raster).  With any of them set, what happens to the samples ahead of the
+    entropy coder -- planes, tiles, edge padding by replication, the predictor -- happens on the device, one launch per
+    raster (fu_tiff_pack, the inverse of fu_tiff_unpack) on the same stream after the sieve: the class map as written,
+    "probs", "margin", "valid" and the fp32 canvas straight from its [H, W, k] strides (no host transpose), and the packed
+    buffers ride in the scene's one read in place of the tensors (the one-byte class map rides along when
+    --write_vectors needs it on the host).  The host deflates segments and writes the container, with the georeferencing
+    and the class map's GDAL_NODATA as always; a scene without a valid pixel is packed on the host (pack_host).  The
+    records and the summary gain "output_format".  With every out_* option at its default nothing of this runs and every
+    file is byte for byte what it was -- except that a file classic TIFF cannot hold (above 4 GiB; that only raised) is
+    written as BigTIFF strips by the new writer.  Out of scope: LZW / PackBits / ZSTD encoders, overviews and COG block
+    ordering, chunky or big-endian output, predict's outputs, entropy coding on the GPU.
 How infer() is put together: the options travel as one checked InferOptions (infer_options.py; the keywords of infer() and
 the command line both go through InferOptions.make); predict.load_eval_model serves the model; a SceneQueue owns the
 scenes in flight and deals their crops out in batches; per batch scene_crops, predict.eval_forward and one batched stitch;
 per finished scene finalize_scene (the launches and the one read, stitch.PackedRead) and write_scene (host only).
-Out of scope: multi-GPU inference, inputs besides ms_image (dem, slope, hand, preflood), RGB outputs, BigTIFF or
-compressed output.
+Out of scope: multi-GPU inference, inputs besides ms_image (dem, slope, hand, preflood), RGB outputs.
 """
 from __future__ import annotations
 
@@ -99,8 +114,9 @@ import numpy as np
 import torch
 
 from .infer_options import (BLEND_KINDS, DECODE_CHOICES, DECODE_THREADS_DEFAULT, NODATA_OUT_DEFAULT,  # noqa: F401
-                            PROB_FORMATS, WEIGHT_CHOICES, InferOptions, default_stride, grid_size, scene_nodata,
-                            threshold_rule)
+                            OUT_BIGTIFF_CHOICES, OUT_COMPRESS_CHOICES, OUT_LEVEL_DEFAULT, OUT_PREDICTOR_CHOICES,
+                            OUT_THREADS_DEFAULT, OUT_TILE_FLAG, PROB_FORMATS, WEIGHT_CHOICES, InferOptions, default_stride,
+                            grid_size, scene_nodata, threshold_rule)
 from .predict import CONFIG_DEFAULTS, _merge, eval_forward, load_eval_model, resolve_cfg
 from .tta import VIEW_SETS, recorded
 from .vectorize import ARRAYS as VECTOR_ARRAYS
@@ -419,7 +435,26 @@ def empty_scene_arrays(scene: dict, n_classes: int, options: InferOptions) -> Di
         arrays["kept"] = np.zeros((H, W, n_classes), dtype=np.float32)
     if options.write_vectors:
         arrays.update({k: np.zeros(0, dtype=np.int32) for k in VECTOR_ARRAYS}, edges=0)      # no crop: no polygon
+    if options.packed_output:                            # what finalize_scene packs on the device, here on the host
+        from .datasets.geotiff_write import pack_host
+        for name in PACKED_RASTERS:
+            if name in arrays:
+                raster = arrays[name].transpose(2, 0, 1) if name == "canvas" else arrays[name]
+                arrays["packed_" + name] = pack_host(raster, output_layout(options, raster.dtype, raster.shape))
+                if name != "class" or not options.write_vectors:
+                    del arrays[name]
     return arrays
+
+
+PACKED_RASTERS = ("class", "probs", "margin", "valid", "canvas")     # the arrays of finalize_scene that become files
+
+
+def output_layout(options: InferOptions, dtype, shape) -> dict:
+    """The byte layout (fu_tiff_layout dict) of an output raster [H, W] or [k, H, W] under the out_* options: out_tile x
+    out_tile tiles or 16-row strips, the predictor of options.predictor_for."""
+    from .datasets.geotiff_write import raster_layout
+    samples, (H, W) = (1 if len(shape) == 2 else int(shape[0])), shape[-2:]
+    return raster_layout(dtype, int(H), int(W), samples, tile=options.out_tile, predictor=options.predictor_for(dtype))
 
 
 def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: InferOptions,
@@ -433,7 +468,10 @@ def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: Inf
     canvas: empty_scene_arrays.  With options.write_vectors the crack edges of the written map's vector_values and their
     rings are taken on the same stream after the sieve (vectorize.count_and_rings: components, offsets, one 4-byte read
     of the edge count, rings) and the read also carries "start", "comp", "ring", "rank", "flags" int32 [n_edges]; "edges"
-    is the count, and a scene with more than vector_max_edges has the count alone."""
+    is the count, and a scene with more than vector_max_edges has the count alone.  With options.packed_output (an out_*
+    option is set) every raster that becomes a file is packed for its writer on the same stream after the sieve
+    (geotiff_write.pack_on_device, one launch each; the canvas from its [H, W, k] strides) and the read carries
+    "packed_class", "packed_probs", ... uint8 [n] in place of the rasters; "class" itself only under write_vectors."""
     from .postprocess import sieve as sieve_map
     from .stitch import PackedRead
     masked = options.nodata is not None
@@ -444,11 +482,19 @@ def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: Inf
                                  valid=scene["valid"] if masked else None,
                                  nodata_value=options.nodata_out if masked else None)
     read = PackedRead()
+    packed = options.packed_output
+    rasters = {}                                         # the tensors that become files, by their array names
     for name in ("counts", "class", "probs", "margin"):
         if name in maps:
-            read.add(name, maps[name])
+            if packed and name != "counts":
+                rasters[name] = maps[name]
+            else:
+                read.add(name, maps[name])
     if options.write_probs == "f32":
-        read.add("canvas", maps["canvas"])
+        if packed:
+            rasters["canvas"] = maps["canvas"].permute(2, 0, 1)
+        else:
+            read.add("canvas", maps["canvas"])
     if options.sieve is not None:
         min_pixels, connectivity, passes = options.sieve
         _, stats = sieve_map(maps["class"], min_pixels, connectivity, passes=passes, out=maps["class"],
@@ -457,7 +503,17 @@ def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: Inf
     if masked:
         read.add("n_valid", scene["n_valid"])
         if options.write_valid:
-            read.add("valid", scene["valid"])
+            if packed:
+                rasters["valid"] = scene["valid"]
+            else:
+                read.add("valid", scene["valid"])
+    if packed:                                           # after the sieve: the class map as it is written
+        from .datasets.geotiff_write import pack_on_device
+        for name, t in rasters.items():
+            dtype = np.float32 if t.dtype == torch.float32 else np.uint8
+            read.add("packed_" + name, pack_on_device(t, output_layout(options, dtype, tuple(t.shape))))
+        if options.write_vectors:
+            read.add("class", maps["class"])             # one byte per pixel: the host sorts the rings with it
     if options.write_vectors:                            # of the map as it is written: after the sieve
         from .vectorize import count_and_rings, select_flags
         n_edges, rings = count_and_rings(maps["class"], select_flags(options.vector_values), options.vector_connectivity,
@@ -479,35 +535,64 @@ def write_scene(arrays: Dict[str, np.ndarray], scene: dict, options: InferOption
     options.nodata (scene: also "nodata", "skipped"; arrays: also "n_valid") the class map carries GDAL_NODATA =
     str(nodata_out) (tag 42113) beside the georeferencing -- the side rasters do not, 0 is a value there -- and
     write_valid writes arrays["valid"] as <image>_valid.tif.  With options.write_vectors (arrays: also the ring arrays
-    and "edges") it writes <image>.geojson: write_scene_vectors."""
-    from .datasets.synthetic import write_strip_tiff
+    and "edges") it writes <image>.geojson: write_scene_vectors.  With options.packed_output the arrays hold the packed
+    bytes ("packed_class", ...) and every raster goes through geotiff_write.write_raster (write_output_raster); the record
+    gains "output_format", with "bigtiff" per file."""
     H, W = scene["hw"]
     tags = geo_tags_for_grid(scene["tags"], scene["src_hw"], (H, W))
     masked = options.nodata is not None
-    write_strip_tiff(out_path, arrays["class"],
-                     extra_tags=tags + [(42113, 2, str(options.nodata_out))] if masked else tags)
+    big = {}                                             # file kind -> whether it was written as BigTIFF
+
+    def put(file_path, kind, name, extra_tags):
+        big[kind] = write_output_raster(file_path, arrays, name, options, extra_tags, (H, W))
+        return file_path
+
+    put(out_path, "class", "class", tags + [(42113, 2, str(options.nodata_out))] if masked else tags)
     rec = {"input": path, "output": out_path, "source_size": list(scene["src_hw"]), "grid_size": [H, W],
            "crops": scene["n"], "class_pixels": arrays["counts"].tolist()}
     if masked:
         rec.update(valid_pixels=int(arrays["n_valid"][0]), skipped_crops=int(scene["skipped"]), nodata=scene["nodata"])
         if options.write_valid:
-            rec["valid"] = side_output_path(out_path, "valid")
-            write_strip_tiff(rec["valid"], arrays["valid"], extra_tags=tags)
+            rec["valid"] = put(side_output_path(out_path, "valid"), "valid", "valid", tags)
     if options.write_probs == "u8":
-        rec["probabilities"] = side_output_path(out_path, "prob")
-        write_strip_tiff(rec["probabilities"], arrays["probs"], extra_tags=tags)
+        rec["probabilities"] = put(side_output_path(out_path, "prob"), "probabilities", "probs", tags)
     if options.write_margin:
-        rec["margin"] = side_output_path(out_path, "margin")
-        write_strip_tiff(rec["margin"], arrays["margin"], extra_tags=tags)
+        rec["margin"] = put(side_output_path(out_path, "margin"), "margin", "margin", tags)
     if options.write_probs == "f32":
-        rec["probabilities"] = side_output_path(out_path, "prob")
-        write_strip_tiff(rec["probabilities"], np.ascontiguousarray(arrays["canvas"].transpose(2, 0, 1)), extra_tags=tags)
+        rec["probabilities"] = put(side_output_path(out_path, "prob"), "probabilities", "canvas", tags)
+    if options.packed_output or any(big.values()):
+        rec["output_format"] = options.output_format(big)
     if options.sieve is not None:
         merged, changed = arrays["sieve"].tolist()
         rec["sieve"] = dict(options.sieve_options, merged_components=merged, changed_pixels=changed)
     if options.write_vectors:
         rec["vectors"] = write_scene_vectors(arrays, scene, options, vector_output_path(out_path))
     return rec
+
+
+def write_output_raster(file_path: str, arrays: Dict[str, np.ndarray], name: str, options: InferOptions, extra_tags,
+                        hw: Tuple[int, int]) -> bool:
+    """Write one raster of finalize_scene's arrays ("class", "probs", "margin", "valid", or "canvas", which is written as
+    [k, H, W]) -> whether the file is BigTIFF.  With every out_* option at its default: write_strip_tiff, as always, but for
+    a file classic TIFF cannot hold, which goes through geotiff_write.write_raster as BigTIFF strips (the canvas as a
+    transposed view, cut per strip).  Else arrays["packed_" + name], the bytes finalize_scene packed, through
+    write_raster."""
+    from .datasets.geotiff_write import CLASSIC_LIMIT, classic_size, raster_layout, write_raster
+    from .datasets.synthetic import write_strip_tiff
+    if options.packed_output:
+        shape = ((len(arrays["counts"]),) if name in ("probs", "canvas") else ()) + tuple(hw)
+        layout = output_layout(options, np.float32 if name == "canvas" else np.uint8, shape)
+        return write_raster(file_path, arrays["packed_" + name], layout, compress=options.out_compress,
+                            level=options.out_level, bigtiff=options.out_bigtiff, extra_tags=extra_tags,
+                            threads=options.out_threads)["bigtiff"]
+    array = arrays["canvas"].transpose(2, 0, 1) if name == "canvas" else arrays[name]
+    n_segments = (1 if array.ndim == 2 else array.shape[0]) * -(-array.shape[-2] // 16)
+    if classic_size(array.nbytes, n_segments, extra_tags) <= CLASSIC_LIMIT:
+        write_strip_tiff(file_path, np.ascontiguousarray(array), extra_tags=extra_tags)
+        return False
+    layout = raster_layout(array.dtype, array.shape[-2], array.shape[-1], 1 if array.ndim == 2 else array.shape[0])
+    return write_raster(file_path, array, layout, bigtiff="auto", extra_tags=extra_tags,
+                        classic_limit=CLASSIC_LIMIT)["bigtiff"]
 
 
 def vector_output_path(out_path: str) -> str:
@@ -552,6 +637,9 @@ def run_summary(records: List[dict], n_crops: int, seconds: float, max_resident:
                               "max_edges": options.vector_max_edges, "polygons": sum(v["polygons"] for v in written),
                               "rings": sum(v["rings"] for v in written), "edges": sum(v["edges"] for v in written),
                               "skipped_scenes": len(records) - len(written)}
+    formats = [r["output_format"] for r in records if "output_format" in r]
+    if options.packed_output or formats:                 # "bigtiff": whether any file of the run is BigTIFF
+        summary["output_format"] = options.output_format(any(any(f["bigtiff"].values()) for f in formats))
     return summary
 
 
@@ -566,6 +654,7 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     / calibration (the one-versus-rest rule in place of the argmax), nodata / nodata_out / skip_empty / write_valid (the
     valid-pixel mask, see the module docstring), decode / decode_threads (where a scene's samples are unpacked),
     write_vectors / vector_values / vector_connectivity / vector_max_edges (polygons of the written class map),
+    out_compress / out_level / out_predictor / out_tile / out_bigtiff / out_threads (the format of the written rasters),
     n_workers, device, keep_probabilities.  Returns the
     summary.json dict, which records the weights served, the blend, the stride and, when set, "threshold" and "sieve";
     with keep_probabilities also "probabilities" {output path: fp32 [H, W, k] stitched canvas} (one more host read per
@@ -695,6 +784,20 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--vector_max_edges", type=int, default=None, metavar="N",
                     help="a scene whose polygons have more than N pixel edges gets no .geojson; its record says so "
                          "(default 16777216).  Needs --write_vectors")
+    ap.add_argument("--out_compress", type=str, default="none", choices=list(OUT_COMPRESS_CHOICES),
+                    help="compression of the written rasters: none (the default) or deflate (zlib, per strip or tile)")
+    ap.add_argument("--out_level", type=int, default=OUT_LEVEL_DEFAULT, metavar="L",
+                    help="zlib level, 1..9 (default 6).  Needs --out_compress deflate")
+    ap.add_argument("--out_predictor", type=str, default="auto", choices=list(OUT_PREDICTOR_CHOICES),
+                    help="auto (the default): under deflate, horizontal differencing for the uint8 rasters and the "
+                         "floating-point predictor for float32 probabilities; off: no predictor")
+    ap.add_argument("--out_tile", type=int, nargs="?", const=OUT_TILE_FLAG, default=None, metavar="N",
+                    help="write N x N tiles instead of 16-row strips; N a multiple of 16 (256 when the flag stands alone)")
+    ap.add_argument("--out_bigtiff", type=str, default="auto", choices=list(OUT_BIGTIFF_CHOICES),
+                    help="auto (the default): BigTIFF only for a file classic TIFF cannot hold; yes: always; no: never, and "
+                         "a file above 4 GiB is an error")
+    ap.add_argument("--out_threads", type=int, default=OUT_THREADS_DEFAULT, metavar="T",
+                    help="threads that deflate a raster's strips or tiles, 1..16 (default 4)")
     ap.add_argument("--batch_size", type=int, default=None, help="crops per eval forward (default: the config's)")
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips / rotations")

@@ -18,11 +18,16 @@ PROB_FORMATS = ("u8", "f32")
 KEYWORDS = ("size", "scale", "stride", "batch_size", "tta", "n_workers", "device", "keep_probabilities", "weights",
             "blend", "write_probs", "write_margin", "sieve", "sieve_connectivity", "sieve_passes", "water_threshold",
             "threshold_class", "calibration", "nodata", "nodata_out", "skip_empty", "write_valid", "decode",
-            "decode_threads", "write_vectors", "vector_values", "vector_connectivity", "vector_max_edges")
+            "decode_threads", "write_vectors", "vector_values", "vector_connectivity", "vector_max_edges", "out_compress",
+            "out_level", "out_predictor", "out_tile", "out_bigtiff", "out_threads")
 NODATA_OUT_DEFAULT = 127                         # the class map's byte where the input holds no data
 DECODE_CHOICES = ("auto", "host", "device")      # how a scene's samples reach the device (infer.SceneFiles)
 DECODE_THREADS_DEFAULT, DECODE_THREADS_MAX = 4, 16   # datasets/geotiff.py's; never sized from the machine's CPU count
 VECTOR_MAX_EDGES_DEFAULT = 1 << 24               # a scene with more crack edges gets no polygons (vectorize.py)
+OUT_COMPRESS_CHOICES = ("none", "deflate")       # how the output rasters are written (datasets/geotiff_write.py)
+OUT_PREDICTOR_CHOICES = ("auto", "off")
+OUT_BIGTIFF_CHOICES = ("auto", "yes", "no")
+OUT_LEVEL_DEFAULT, OUT_THREADS_DEFAULT, OUT_THREADS_MAX, OUT_TILE_FLAG = 6, 4, 16, 256
 
 
 def check_weights(weights) -> str:
@@ -153,6 +158,41 @@ def check_vectors(write_vectors, vector_values, vector_connectivity, vector_max_
                 vector_connectivity=int(vector_connectivity), vector_max_edges=int(vector_max_edges))
 
 
+def _is_int(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and int(v) == v
+
+
+def check_output(out_compress, out_level, out_predictor, out_tile, out_bigtiff, out_threads) -> Optional[dict]:
+    """The six output-format options -> None (every one at its default: the rasters are written as they always were) or
+    the six fields.  out_compress: "none" or "deflate"; out_level: zlib's 1..9, needs deflate; out_predictor: "auto" (under
+    deflate 2 for the uint8 rasters and 3 for fp32, else 1) or "off"; out_tile: None (strips) or the tile side, a multiple
+    of 16; out_bigtiff: "auto" (BigTIFF only where classic TIFF cannot hold the file), "yes" or "no"; out_threads: the
+    deflate thread pool, 1..16."""
+    if out_compress not in OUT_COMPRESS_CHOICES:
+        raise ValueError(f"infer: out_compress must be one of {list(OUT_COMPRESS_CHOICES)}, got {out_compress!r}")
+    if not _is_int(out_level) or not 1 <= int(out_level) <= 9:
+        raise ValueError(f"infer: out_level must be an integer in 1..9, got {out_level!r}")
+    if out_compress != "deflate" and int(out_level) != OUT_LEVEL_DEFAULT:
+        raise ValueError("infer: --out_level needs --out_compress deflate")
+    if out_predictor not in OUT_PREDICTOR_CHOICES:
+        raise ValueError(f"infer: out_predictor must be one of {list(OUT_PREDICTOR_CHOICES)}, got {out_predictor!r}")
+    if out_tile is not None and (not _is_int(out_tile) or int(out_tile) < 16 or int(out_tile) % 16):
+        raise ValueError(f"infer: out_tile must be a multiple of 16 that is at least 16, got {out_tile!r}")
+    if out_bigtiff not in OUT_BIGTIFF_CHOICES:
+        raise ValueError(f"infer: out_bigtiff must be one of {list(OUT_BIGTIFF_CHOICES)}, got {out_bigtiff!r}")
+    if not _is_int(out_threads) or not 1 <= int(out_threads) <= OUT_THREADS_MAX:
+        raise ValueError(f"infer: out_threads must be an integer in 1..{OUT_THREADS_MAX}, got {out_threads!r}")
+    fields = dict(out_compress=out_compress, out_level=int(out_level), out_predictor=out_predictor,
+                  out_tile=None if out_tile is None else int(out_tile), out_bigtiff=out_bigtiff, out_threads=int(out_threads))
+    if fields == _OUTPUT_DEFAULTS:
+        return None
+    return fields
+
+
+_OUTPUT_DEFAULTS = dict(out_compress="none", out_level=OUT_LEVEL_DEFAULT, out_predictor="auto", out_tile=None,
+                        out_bigtiff="auto", out_threads=OUT_THREADS_DEFAULT)
+
+
 @dataclasses.dataclass(frozen=True)
 class InferOptions:
     """size / scale: the output grid (grid_size); None, None: the raster's own.  stride and batch_size None: the
@@ -164,7 +204,9 @@ class InferOptions:
     ("auto": a file the strict TIFF reader takes goes the way it always went, every other file is unpacked on the
     device) and decode_threads: class constants here, fields of DecodeInferOptions / NodataDecodeInferOptions when either
     differs from its default.  And write_vectors with vector_values, vector_connectivity and vector_max_edges: off here,
-    fields of the Vector* classes under --write_vectors."""
+    fields of the Vector* classes under --write_vectors.  And the six out_* options of the output format: the defaults
+    here (the rasters go through write_strip_tiff, byte for byte as always), fields of output_options_class(...) when any
+    is set; packed_output says which."""
     size: Optional[Tuple[int, int]] = None
     scale: Optional[float] = None
     stride: Optional[int] = None
@@ -190,6 +232,14 @@ class InferOptions:
     vector_values = (255,)
     vector_connectivity = 4
     vector_max_edges = VECTOR_MAX_EDGES_DEFAULT
+    out_compress = "none"                # not fields here: see output_options_class
+    out_level = OUT_LEVEL_DEFAULT
+    out_predictor = "auto"
+    out_tile = None
+    out_bigtiff = "auto"
+    out_threads = OUT_THREADS_DEFAULT
+    packed_output = False                # True on the Output* classes: the rasters are packed on the device and go
+    #                                      through geotiff_write.write_raster
 
     @classmethod
     def make(cls, *, size=None, scale=None, stride=None, batch_size=None, tta=None, n_workers=0, device="cuda:0",
@@ -197,10 +247,12 @@ class InferOptions:
              sieve_connectivity=4, sieve_passes=1, water_threshold=None, threshold_class=None,
              calibration=None, nodata=None, nodata_out=NODATA_OUT_DEFAULT, skip_empty=True,
              write_valid=False, decode="auto", decode_threads=DECODE_THREADS_DEFAULT, write_vectors=False,
-             vector_values=None, vector_connectivity=None, vector_max_edges=None) -> "InferOptions":
+             vector_values=None, vector_connectivity=None, vector_max_edges=None, out_compress="none",
+             out_level=OUT_LEVEL_DEFAULT, out_predictor="auto", out_tile=None, out_bigtiff="auto",
+             out_threads=OUT_THREADS_DEFAULT) -> "InferOptions":
         """The options checked, in the order infer() always checked them: weights, blend, write_probs, the decision
         rule (threshold_rule), the sieve (postprocess.check_sieve_options), an explicit stride, the grid, nodata, decode,
-        vectors."""
+        vectors, the output format."""
         from .postprocess import check_sieve_options
         check_weights(weights)
         check_blend(blend)
@@ -230,6 +282,10 @@ class InferOptions:
         if vectors is not None:
             cls = vector_options_class(cls)
             extra.update(vectors)
+        output = check_output(out_compress, out_level, out_predictor, out_tile, out_bigtiff, out_threads)
+        if output is not None:
+            cls = output_options_class(cls)
+            extra.update(output)
         return cls(size=None if size is None else (int(size[0]), int(size[1])), scale=scale,
                    stride=None if stride is None else int(stride), batch_size=int(batch_size) if batch_size else None,
                    tta=tta if tta is None or isinstance(tta, str) else tuple(int(c) for c in tta), weights=weights,
@@ -273,6 +329,19 @@ class InferOptions:
     def sieve_options(self) -> Optional[dict]:
         """sieve under the names of the summary's "sieve"."""
         return None if self.sieve is None else dict(zip(("min_pixels", "connectivity", "passes"), self.sieve))
+
+    def predictor_for(self, dtype) -> int:
+        """The TIFF predictor of an output raster of this sample type: under out_predictor "auto" with deflate 2 for
+        integers and 3 for floats, else 1."""
+        if self.out_compress != "deflate" or self.out_predictor == "off":
+            return 1
+        import numpy as np
+        return 3 if np.dtype(dtype).kind == "f" else 2
+
+    def output_format(self, bigtiff) -> dict:
+        """The records' and the summary's "output_format"; bigtiff: whether the file, or any file of the run, is BigTIFF."""
+        return {"compress": self.out_compress, "level": self.out_level if self.out_compress == "deflate" else None,
+                "predictor": self.out_predictor, "tile": self.out_tile, "bigtiff": bigtiff, "threads": self.out_threads}
 
 
 @dataclasses.dataclass(frozen=True)
@@ -326,3 +395,26 @@ VectorDecodeInferOptions = _vector_class(DecodeInferOptions)
 VectorNodataDecodeInferOptions = _vector_class(NodataDecodeInferOptions)
 _VECTOR_CLASSES = {InferOptions: VectorInferOptions, NodataInferOptions: VectorNodataInferOptions,
                    DecodeInferOptions: VectorDecodeInferOptions, NodataDecodeInferOptions: VectorNodataDecodeInferOptions}
+
+
+def output_options_class(base):
+    """The options class of a run with an out_* option set: `base` (any of the eight above) with the six output-format
+    fields appended.  out_compress: "none" or "deflate"; out_level: 1..9; out_predictor: "auto" or "off"; out_tile: None
+    or the tile side; out_bigtiff: "auto", "yes" or "no"; out_threads: 1..16."""
+    return _OUTPUT_CLASSES[base]
+
+
+def _output_class(base):
+    cls = dataclasses.make_dataclass(
+        "Output" + base.__name__, [("out_compress", str, "none"), ("out_level", int, OUT_LEVEL_DEFAULT),
+                                   ("out_predictor", str, "auto"), ("out_tile", Optional[int], None),
+                                   ("out_bigtiff", str, "auto"), ("out_threads", int, OUT_THREADS_DEFAULT)],
+        bases=(base,), namespace={"packed_output": True}, frozen=True)
+    cls.__module__ = __name__
+    cls.__doc__ = f"{base.__name__} of a run with an out_* option set: the six fields appended (output_options_class)."
+    globals()[cls.__name__] = cls
+    return cls
+
+
+_OUTPUT_CLASSES = {base: _output_class(base) for base in (InferOptions, NodataInferOptions, DecodeInferOptions,
+                                                          NodataDecodeInferOptions) + tuple(_VECTOR_CLASSES.values())}

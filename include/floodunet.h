@@ -26,6 +26,8 @@
  *                               tiles, band choice and conversion in one launch (tifffile.imread + the host's astype)
  *   fu_tiff_lzw_decode /        (new) the host's LZW and PackBits decoders in front of it
  *   fu_tiff_packbits_decode
+ *   fu_tiff_pack                (new) the inverse for the rasters infer writes: a strided device raster -> the byte buffer
+ *                               a TIFF writer deflates -- planes, tiles or strips, edge padding, predictor -- in one launch
  *   fu_backward[_block]         loss.backward() issued by Lightning's automatic optimisation
  *                                                                            st_water_seg/fit.py:95-97
  *   fu_adam_step                optim.Adam(self.parameters(), lr).step()     st_water_seg/models/water_seg_model.py:198-205
@@ -751,6 +753,25 @@ typedef struct fu_tiff_layout {
  * integers, predictor 2 on floats -- and a rejected call launches nothing and leaves out untouched. */
 int fu_tiff_unpack(const uint8_t* src, int64_t n_bytes, fu_tiff_layout layout, const int32_t* bands, int n_bands, float* out,
                    fu_stream stream);
+/* The inverse, for writing: a device-resident raster -> dst, the bytes a TIFF writer hands its entropy coder, bit for bit
+ * datasets/geotiff_write.py's pack_host, every byte of dst included; fu_tiff_unpack of dst with the same layout gives the
+ * raster back.  src: the base pointer of sample (band 0, row 0, column 0); sample (b, y, x) lies at element b * band_stride +
+ * y * row_stride + x * col_stride (strides in elements, >= 0; element size and kind from the layout), so an [H, W, k] canvas
+ * (strides 1, W * k, k) and a [k, H, W] tensor are both sources without a copy.  Segments lie back to back at their nominal
+ * size in the order of the offset array: a tile is always seg_h x seg_w and a position outside the image holds the nearest
+ * image pixel (the index clamped per axis), padded before the predictor so that padding differences to zeros; the last
+ * strip holds the rows that are left.  Predictor 2: per segment row v[x] - v[x - 1] modulo 2^bits, the first value as it is.
+ * Predictor 3: the row's values as bytes_per_sample byte planes of seg_w bytes, most significant first, then the whole row
+ * differenced byte-wise, across the plane boundaries, the first byte as it is.  Supported: little-endian (big_endian 0),
+ * bytes_per_sample 1, 2 or 4, float samples of 4 bytes, samples 1..FU_TIFF_MAX_BANDS and planar != 0 whenever samples > 1
+ * (chunky output is rejected), strips (seg_w == width) or tiles whose sides are multiples of 16.  dst: device, 16-byte
+ * aligned, n_bytes long.  ONE launch, a streaming gather: a lane produces whole 16-byte groups of dst (where rows are
+ * multiples of 16 values it loads 16 values once and stores a group in each byte plane), no atomics, no host read, 64-bit
+ * byte offsets.  Every argument is checked first -- null pointers, alignment, negative strides, sizes (an image or segment
+ * above FU_MAP_MAX_PIXELS pixels), n_bytes != the layout's arithmetic total, an unsupported layout, predictor 3 on integers,
+ * predictor 2 on floats -- and a rejected call launches nothing and leaves dst untouched. */
+int fu_tiff_pack(const void* src, int64_t band_stride, int64_t row_stride, int64_t col_stride, fu_tiff_layout layout,
+                 uint8_t* dst, int64_t n_bytes, fu_stream stream);
 
 /* ---- class-map post-processing (fu_post.hip); no context needed --------------------------------- */
 /* Connected components of a uint8 map [h, w] on the device: a component is a maximal set of pixels of equal value joined
