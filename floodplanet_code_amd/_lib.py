@@ -237,6 +237,7 @@ SIGNATURES = {
     "fu_tiff_packbits_decode": (_i64, [_p, _i64, _p, _i64]),
     "fu_tiff_unpack": (_i, [_p, _i64, FuTiffLayout, C.POINTER(C.c_int32), _i, _p, _p]),
     "fu_tiff_pack": (_i, [_p, _i64, _i64, _i64, FuTiffLayout, _p, _i64, _p]),
+    "fu_map_overviews": (_i, [_p, _i64, _i64, _i64, _i, _i, _i, _i, _p, _i, _i, _p, _i64, _p, _p]),
     "fu_eval_prob_hist": (_i, [_p, _p, _i, _i, _p, _p, _p]),
     "fu_prob_hist": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p, _p]),
     "fu_sieve_workspace_bytes": (_i64, [_i, _i]),

@@ -617,6 +617,13 @@ int fu_tiff_pack(const void* src, int64_t band_stride, int64_t row_stride, int64
   return launch_tiff_pack(src, band_stride, row_stride, col_stride, layout, dst, n_bytes, (hipStream_t)stream);
 }
 
+int fu_map_overviews(const void* src, int64_t band_stride, int64_t row_stride, int64_t col_stride, int bands, int h, int w,
+                     int kind, const uint8_t* valid, int nodata_value, int n_levels, void* dst, int64_t dst_elems,
+                     uint8_t* valid_dst, fu_stream stream) {
+  return launch_map_overviews(src, band_stride, row_stride, col_stride, bands, h, w, kind, valid, nodata_value, n_levels, dst,
+                              dst_elems, valid_dst, (hipStream_t)stream);
+}
+
 int fu_eval_prob_hist(fu_ctx* c, const int64_t* target, int ignore_index, int n_bins, int64_t* hist_out, int64_t* top_out,
                       fu_stream stream) {
   FU_REQUIRE(c && target, "fu_eval_prob_hist: null context / target");

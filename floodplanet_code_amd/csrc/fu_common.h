@@ -626,6 +626,11 @@ int launch_tiff_unpack(const uint8_t* src, int64_t n_bytes, const fu_tiff_layout
 // buffer of a TIFF writer, one launch; checks every argument (n_bytes against the layout's total included) before it launches
 int launch_tiff_pack(const void* src, int64_t band_stride, int64_t row_stride, int64_t col_stride, const fu_tiff_layout& layout,
                      uint8_t* dst, int64_t n_bytes, hipStream_t s);
+// fu_map_overviews (fu_overview.hip): the ceil-halved overview levels of a strided device raster, six per launch from one
+// LDS-resident base tile; checks every argument before it launches
+int launch_map_overviews(const void* src, int64_t band_stride, int64_t row_stride, int64_t col_stride, int bands, int h, int w,
+                         int kind, const uint8_t* valid, int nodata_value, int n_levels, void* dst, int64_t dst_elems,
+                         uint8_t* valid_dst, hipStream_t s);
 // fu_map_components / fu_map_sieve (fu_post.hip): union-find labelling of a uint8 map (the label of a pixel = the smallest
 // linear index of its component) and the connected-component sieve on top of it; the caller has checked every argument.
 // workspace: sieve_workspace_bytes(h, w) = 16 B per pixel (64-bit donor keys, labels, sizes); stats: int64[2] ADDED to, or null

@@ -1,6 +1,8 @@
 """Reader for the GeoTIFFs people actually have: classic and BigTIFF, both byte orders, strips and tiles, chunky and
 planar-separate samples, compression none / Deflate (8, 32946) / LZW (5) / PackBits (32773), predictor 1 / 2 / 3, 8/16/32/64-
-bit unsigned / signed / IEEE samples.  First IFD only (overviews and mask IFDs are ignored).  `datasets/tiff.py` stays the
+bit unsigned / signed / IEEE samples.  The first IFD unless asked otherwise: raster_ifds counts a file's images and the ifd
+keyword of raster_info / raster_size / read_raster / read_raster_encoded picks one (an overview, a mask); cog_report checks
+the cloud-optimised layout geotiff_write.write_raster(overviews=...) writes.  `datasets/tiff.py` stays the
 strict reader of the rasters bundled with the reference and is not touched; for a file it accepts, read_raster returns
 read_tiff's array.
 
@@ -40,9 +42,9 @@ import numpy as np
 
 from .tiff import GEOTIFF_TAGS, TiffError
 
-__all__ = ["raster_info", "raster_size", "raster_geotiff_tags", "read_raster", "read_raster_encoded", "unpack_host",
-           "unpack_on_device", "lzw_decode_host", "packbits_decode_host", "strict_reader_accepts", "check_decode_threads",
-           "DECODE_THREADS_DEFAULT", "DECODE_THREADS_MAX", "UNPACK_CHUNK", "UNPACK_MAX_BANDS"]
+__all__ = ["raster_info", "raster_size", "raster_ifds", "cog_report", "raster_geotiff_tags", "read_raster",
+           "read_raster_encoded", "unpack_host", "unpack_on_device", "lzw_decode_host", "packbits_decode_host",
+           "strict_reader_accepts", "check_decode_threads", "DECODE_THREADS_DEFAULT", "DECODE_THREADS_MAX", "UNPACK_CHUNK", "UNPACK_MAX_BANDS"]
 
 DECODE_THREADS_DEFAULT, DECODE_THREADS_MAX = 4, 16
 UNPACK_CHUNK = 256         # FU_TIFF_UNPACK_CHUNK: the pixels of a segment row fu_tiff_unpack takes per pass
@@ -74,9 +76,8 @@ def _map(path: str):
             raise TiffError("file too short for a TIFF header") from None
 
 
-def _parse_ifd(buf, keep=()) -> Tuple[str, bool, Dict[int, object]]:
-    """-> (byte order, is BigTIFF, {tag number: values}) of the first IFD: the decoding tags and the tags in keep.  Offsets
-    and byte counts come as int64 arrays, ASCII values of kept tags as str, everything else as tuples."""
+def _header(buf) -> Tuple[str, bool, int]:
+    """-> (byte order, is BigTIFF, offset of the first IFD)."""
     size = len(buf)
     if size < 8:
         raise TiffError("file too short for a TIFF header")
@@ -89,31 +90,76 @@ def _parse_ifd(buf, keep=()) -> Tuple[str, bool, Dict[int, object]]:
         raise TiffError("not a TIFF file (bad byte-order mark)")
     (magic,) = struct.unpack(bo + "H", buf[2:4])
     if magic == 42:
-        big = False
         (ifd,) = struct.unpack(bo + "I", buf[4:8])
-    elif magic == 43:
+        return bo, False, ifd
+    if magic == 43:
         if size < 16:
             raise TiffError("file too short for a BigTIFF header")
         off_size, zero, ifd = struct.unpack(bo + "HHQ", buf[4:16])
         if off_size != 8 or zero != 0:
             raise TiffError(f"BigTIFF with {off_size}-byte offsets is not supported")
-        big = True
-    else:
-        raise TiffError(f"not a TIFF file (magic {magic})")
-    count_fmt, entry_size, inline, off_fmt = ("Q", 20, 8, "Q") if big else ("H", 12, 4, "I")
-    count_size = struct.calcsize(count_fmt)
-    if ifd + count_size > size:
+        return bo, True, ifd
+    raise TiffError(f"not a TIFF file (magic {magic})")
+
+
+def _ifd_extent(buf, bo: str, big: bool, ifd: int) -> Tuple[int, int]:
+    """-> (number of entries, offset of the next IFD or 0) of the IFD at `ifd`, checked against the file's size."""
+    count_fmt, entry_size, off_fmt = ("Q", 20, "Q") if big else ("H", 12, "I")
+    count_size, off_size = struct.calcsize(count_fmt), struct.calcsize(off_fmt)
+    if ifd + count_size > len(buf):
         raise TiffError("IFD offset beyond the end of the file")
     (n,) = struct.unpack(bo + count_fmt, buf[ifd:ifd + count_size])
-    if ifd + count_size + entry_size * n > size:
+    end = ifd + count_size + entry_size * n
+    if end > len(buf):
         raise TiffError("truncated IFD")
+    following = struct.unpack(bo + off_fmt, buf[end:end + off_size])[0] if end + off_size <= len(buf) else 0
+    return n, following
+
+
+def _ifd_offsets(buf) -> Tuple[str, bool, List[int]]:
+    """-> (byte order, is BigTIFF, the offsets of the chain's IFDs in order); a chain that loops raises TiffError."""
+    bo, big, ifd = _header(buf)
+    chain: List[int] = []
+    while ifd:
+        if ifd in chain:
+            raise TiffError("the IFD chain loops")
+        chain.append(ifd)
+        ifd = _ifd_extent(buf, bo, big, ifd)[1]
+    if not chain:
+        raise TiffError("the file has no IFD")
+    return bo, big, chain
+
+
+def _parse_ifd(buf, keep=(), ifd: int = 0, spans=None) -> Tuple[str, bool, Dict[int, object]]:
+    """-> (byte order, is BigTIFF, {tag number: values}) of IFD number `ifd` of the chain (0: the first, which needs no walk):
+    the decoding tags and the tags in keep.  Offsets and byte counts come as int64 arrays, ASCII values of kept tags as str,
+    everything else as tuples.  spans: a list that receives (start, end) of the IFD and of every value stored outside it."""
+    size = len(buf)
+    if isinstance(ifd, bool) or int(ifd) != ifd or int(ifd) < 0:
+        raise ValueError(f"ifd must be an integer >= 0, got {ifd!r}")
+    if ifd == 0:
+        bo, big, at = _header(buf)
+    else:
+        bo, big, chain = _ifd_offsets(buf)
+        if ifd >= len(chain):
+            raise TiffError(f"IFD {ifd} lies beyond the chain of {len(chain)} image{'s' if len(chain) != 1 else ''}")
+        at = chain[int(ifd)]
+    ifd = at
+    count_fmt, entry_size, inline, off_fmt = ("Q", 20, 8, "Q") if big else ("H", 12, 4, "I")
+    count_size = struct.calcsize(count_fmt)
+    n, _ = _ifd_extent(buf, bo, big, ifd)
+    if spans is not None:
+        spans.append((ifd, ifd + count_size + entry_size * n + struct.calcsize(off_fmt)))
     tags: Dict[int, object] = {}
     for i in range(n):
         e = buf[ifd + count_size + entry_size * i: ifd + count_size + entry_size * (i + 1)]
         tag, typ, cnt = struct.unpack(bo + ("HHQ" if big else "HHI"), e[:entry_size - inline])
+        fmt = _TYPE_FMT.get(typ)
+        if spans is not None and fmt is not None and struct.calcsize(bo + fmt) * cnt > inline:
+            (off,) = struct.unpack(bo + off_fmt, e[entry_size - inline:])
+            spans.append((off, off + struct.calcsize(bo + fmt) * cnt))
         if tag not in _DECODE_TAGS and tag not in keep:
             continue
-        fmt = _TYPE_FMT.get(typ)
         if fmt is None:
             raise TiffError(f"tag {tag}: unknown field type {typ}")
         nbytes = struct.calcsize(bo + fmt) * cnt
@@ -202,17 +248,68 @@ def _describe(bo: str, big: bool, tags: Dict[int, object]) -> dict:
             "bytes_per_sample": bits // 8, "offsets": offsets, "counts": counts}
 
 
-def raster_info(path: str) -> dict:
-    """Header fields only (first IFD): tiff_info's keys -- height, width, samples, dtype, planar, rows_per_strip (None
-    for tiles), byteorder -- plus bigtiff, tiled, seg_w, seg_h, compression, predictor."""
-    info = _describe(*_parse_ifd(_map(path)))
+def raster_info(path: str, ifd: int = 0) -> dict:
+    """Header fields only (image number `ifd` of the file; 0, the default, is the first IFD): tiff_info's keys -- height,
+    width, samples, dtype, planar, rows_per_strip (None for tiles), byteorder -- plus bigtiff, tiled, seg_w, seg_h,
+    compression, predictor.  An ifd beyond the chain raises TiffError."""
+    info = _describe(*_parse_ifd(_map(path), ifd=ifd))
     return {k: v for k, v in info.items() if k not in ("offsets", "counts", "kind", "bytes_per_sample")}
 
 
-def raster_size(path: str) -> Tuple[int, int]:
+def raster_size(path: str, ifd: int = 0) -> Tuple[int, int]:
     """(height, width), as tiff_size."""
-    info = raster_info(path)
+    info = raster_info(path, ifd)
     return info["height"], info["width"]
+
+
+def raster_ifds(path: str) -> int:
+    """The number of images (IFDs) in the file: 1 + its overviews and whatever else its chain holds."""
+    return len(_ifd_offsets(_map(path))[2])
+
+
+def cog_report(path: str) -> List[str]:
+    """The rules of the published cloud-optimised GeoTIFF layout the file violates; an empty list means compliant.  Host
+    only, the statement the tests use:
+      * every image is tiled;
+      * every IFD and tag payload lies before the first byte of segment data;
+      * the IFDs are in decreasing size, and every one but the first is marked reduced-resolution (NewSubfileType bit 0);
+      * each image's data lies after the data of every smaller image;
+      * an image with a side above its tile side has overviews down to at most one tile.
+    Not looked at: GDAL's structural-metadata ghost block and the per-tile leaders / trailers, which are optional."""
+    buf = _map(path)
+    n = len(_ifd_offsets(buf)[2])
+    spans: List[Tuple[int, int]] = []
+    images = []
+    for i in range(n):
+        bo, big, tags = _parse_ifd(buf, keep=(254,), ifd=i, spans=spans)
+        images.append((_describe(bo, big, tags), _first(tags, 254, 0)))
+    out = []
+    for i, (info, _) in enumerate(images):
+        if not info["tiled"]:
+            out.append(f"every image is tiled: IFD {i} is stored in strips")
+    stored = [(int(info["offsets"][info["counts"] > 0].min(initial=len(buf))),
+               int((info["offsets"] + info["counts"]).max())) for info, _ in images]
+    first_data = min(s[0] for s in stored)
+    late = max(end for _, end in spans)
+    if late > first_data:
+        out.append(f"every IFD and tag payload lies before the segment data: directory bytes end at {late}, the data "
+                   f"starts at {first_data}")
+    for i in range(1, n):
+        (a, _), (b, sub) = images[i - 1], images[i]
+        if b["height"] > a["height"] or b["width"] > a["width"] or (b["height"], b["width"]) == (a["height"], a["width"]):
+            out.append(f"the IFDs are in decreasing size: IFD {i} is {b['height']}x{b['width']} after "
+                       f"{a['height']}x{a['width']}")
+        if not sub & 1:
+            out.append(f"every IFD but the first is marked reduced-resolution: IFD {i} has NewSubfileType {sub}")
+        if stored[i - 1][0] < stored[i][1]:
+            out.append(f"each image's data lies after the data of every smaller image: IFD {i - 1} starts at "
+                       f"{stored[i - 1][0]}, IFD {i} ends at {stored[i][1]}")
+    full, smallest = images[0][0], images[-1][0]
+    if full["tiled"] and (full["height"] > full["seg_h"] or full["width"] > full["seg_w"]) and \
+            (smallest["height"] > full["seg_h"] or smallest["width"] > full["seg_w"]):
+        out.append(f"an image larger than its tile has overviews down to at most one tile: the smallest image is "
+                   f"{smallest['height']}x{smallest['width']}, the tile {full['seg_h']}x{full['seg_w']}")
+    return out
 
 
 def raster_geotiff_tags(path: str) -> Dict[int, object]:
@@ -348,18 +445,19 @@ def _segments(L: dict) -> List[Tuple[int, int, int, int, int]]:
     return out
 
 
-def read_raster_encoded(path: str, decode_threads: int = DECODE_THREADS_DEFAULT, codec: str = "native"):
+def read_raster_encoded(path: str, decode_threads: int = DECODE_THREADS_DEFAULT, codec: str = "native", ifd: int = 0):
     """-> (the entropy-decoded segments as one contiguous uint8 array, layout): what fu_tiff_unpack / unpack_on_device and
     unpack_host take.  Every segment lies at its nominal size (a tile seg_h x seg_w, strip s min(seg_h, height - s * seg_h)
     rows), back to back in the order of the file's offset array; a segment that decodes to more is truncated, one that
     decodes to less -- or lies beyond the file -- raises TiffError.  layout: the fields of fu_tiff_layout as a dict of ints
     (width, height, samples, bytes_per_sample, sample_kind 1 uint / 2 int / 3 float, big_endian, planar, tiled, seg_w,
-    seg_h, predictor).  codec: "native" (the library's LZW / PackBits decoders) or "python" (the statements here)."""
+    seg_h, predictor).  codec: "native" (the library's LZW / PackBits decoders) or "python" (the statements here).  ifd:
+    which image of the file (0: the first; an overview is 1, 2, ...); beyond the chain: TiffError."""
     if codec not in ("native", "python"):
         raise ValueError(f"codec must be 'native' or 'python', got {codec!r}")
     threads = check_decode_threads(decode_threads)
     buf = _map(path)
-    info = _describe(*_parse_ifd(buf))
+    info = _describe(*_parse_ifd(buf, ifd=ifd))
     layout = {"width": info["width"], "height": info["height"], "samples": info["samples"],
               "bytes_per_sample": info["bytes_per_sample"], "sample_kind": {"u": 1, "i": 2, "f": 3}[info["kind"]],
               "big_endian": int(info["byteorder"] == ">"), "planar": int(info["planar"] == 2 and info["samples"] > 1),
@@ -434,9 +532,10 @@ def unpack_host(encoded: np.ndarray, layout: dict) -> np.ndarray:
     return out[0, :, :, 0] if spp == 1 else out[0]
 
 
-def read_raster(path: str, decode_threads: int = DECODE_THREADS_DEFAULT, codec: str = "native") -> np.ndarray:
-    """Decode the first image of the file, with read_tiff's return conventions (see the module docstring)."""
-    return np.ascontiguousarray(unpack_host(*read_raster_encoded(path, decode_threads, codec)))
+def read_raster(path: str, decode_threads: int = DECODE_THREADS_DEFAULT, codec: str = "native", ifd: int = 0) -> np.ndarray:
+    """Decode image number `ifd` of the file (0, the default: the first), with read_tiff's return conventions (see the
+    module docstring)."""
+    return np.ascontiguousarray(unpack_host(*read_raster_encoded(path, decode_threads, codec, ifd)))
 
 
 def layout_struct(layout: dict):

@@ -22,8 +22,13 @@ unpack_host(pack_host(a, L), L) == a, bit for bit.
     whenever there are several (inside a segment there is always one sample per pixel), strips or tiles whose sides are
     multiples of 16.
 
-Out of scope: LZW / PackBits / ZSTD encoders, overviews and COG block ordering, chunky or big-endian output, entropy coding
-on the GPU.
+Several images in one file: write_raster(overviews=[...]) puts reduced-resolution images (datasets/overviews.py) behind the
+full resolution in the order of the published cloud-optimised layout -- every IFD and tag payload in front of the data,
+the data of the smallest image first -- which geotiff.cog_report checks.
+
+Out of scope: LZW / PackBits / ZSTD encoders, GDAL's structural-metadata ghost block and per-tile leaders / trailers (their
+exact text cannot be checked without GDAL, and validators treat them as optional), chunky or big-endian output, entropy
+coding on the GPU.
 """
 from __future__ import annotations
 
@@ -181,39 +186,48 @@ def _payload(typ: int, vals) -> bytes:
     return struct.pack("<" + _TYPE_FMT[typ] * len(vals), *vals)
 
 
-def _directory(tags, counts: np.ndarray, offsets_tag: int, big: bool) -> Tuple[bytes, np.ndarray]:
-    """Header, IFD and tag payloads of a file whose segments follow them with the byte counts `counts` -> (those bytes,
-    the segments' offsets).  Payloads longer than an entry's value field start on word boundaries, in tag order."""
+def _directories(images, big: bool) -> Tuple[bytes, List[np.ndarray]]:
+    """Header and, for every image in file order, its IFD and tag payloads; images: [(tags, counts, offsets_tag)].  The
+    segments follow them, the LAST image's first and the first image's last, inside an image with the byte counts `counts`
+    in their order -> (those bytes, the segments' offsets per image).  Payloads longer than an entry's value field start
+    on word boundaries, in tag order; the IFDs are chained through their next-IFD fields."""
     head, entry, inline = (16, 20, 8) if big else (8, 12, 4)
-    cursor = head + (8 if big else 2) + entry * len(tags) + (8 if big else 4)
-    raws, where = {}, {}
-    for tag, typ, vals in tags:
-        if tag == offsets_tag:
-            size = _TYPE_SIZE[typ] * len(counts)
-        else:
-            raws[tag] = _payload(typ, vals)
-            size = len(raws[tag])
-        if size > inline:
-            where[tag] = cursor
-            cursor += size + (size & 1)
-    offsets = cursor + np.concatenate([[0], np.cumsum(counts[:-1], dtype=np.int64)]).astype(np.int64)
-    entries, blobs = [], []
-    for tag, typ, vals in tags:
-        raw = _payload(typ, offsets) if tag == offsets_tag else raws[tag]
-        cnt = len(raw) // _TYPE_SIZE[typ]
-        e = struct.pack("<HHQ" if big else "<HHI", tag, typ, cnt)
-        if len(raw) <= inline:
-            entries.append(e + raw.ljust(inline, b"\0"))
-        else:
-            entries.append(e + struct.pack("<Q" if big else "<I", where[tag]))
-            blobs.append(raw + b"\0" * (len(raw) & 1))
-    if big:
-        top = b"II" + struct.pack("<HHHQ", 43, 8, 0, 16) + struct.pack("<Q", len(tags))
-        tail = struct.pack("<Q", 0)
-    else:
-        top = b"II" + struct.pack("<HI", 42, 8) + struct.pack("<H", len(tags))
-        tail = struct.pack("<I", 0)
-    return top + b"".join(entries) + tail + b"".join(blobs), offsets
+    cursor = head
+    raws, where, starts = [], [], []
+    for tags, counts, offsets_tag in images:
+        starts.append(cursor)
+        cursor += (8 if big else 2) + entry * len(tags) + (8 if big else 4)
+        raws.append({}), where.append({})
+        for tag, typ, vals in tags:
+            if tag == offsets_tag:
+                size = _TYPE_SIZE[typ] * len(counts)
+            else:
+                raws[-1][tag] = _payload(typ, vals)
+                size = len(raws[-1][tag])
+            if size > inline:
+                where[-1][tag] = cursor
+                cursor += size + (size & 1)
+    offsets: List = [None] * len(images)
+    for i in reversed(range(len(images))):                           # the data: the smallest image first
+        counts = images[i][1]
+        offsets[i] = cursor + np.concatenate([[0], np.cumsum(counts[:-1], dtype=np.int64)]).astype(np.int64)
+        cursor = int(offsets[i][-1] + counts[-1])
+    out = [b"II" + (struct.pack("<HHHQ", 43, 8, 0, 16) if big else struct.pack("<HI", 42, 8))]
+    for i, (tags, counts, offsets_tag) in enumerate(images):
+        entries, blobs = [], []
+        for tag, typ, vals in tags:
+            raw = _payload(typ, offsets[i]) if tag == offsets_tag else raws[i][tag]
+            cnt = len(raw) // _TYPE_SIZE[typ]
+            e = struct.pack("<HHQ" if big else "<HHI", tag, typ, cnt)
+            if len(raw) <= inline:
+                entries.append(e + raw.ljust(inline, b"\0"))
+            else:
+                entries.append(e + struct.pack("<Q" if big else "<I", where[i][tag]))
+                blobs.append(raw + b"\0" * (len(raw) & 1))
+        following = starts[i + 1] if i + 1 < len(images) else 0
+        out.append(struct.pack("<Q" if big else "<H", len(tags)) + b"".join(entries)
+                   + struct.pack("<Q" if big else "<I", following) + b"".join(blobs))
+    return b"".join(out), offsets
 
 
 def _image_tags(layout: dict, compression: int, counts, big: bool, extra_tags) -> Tuple[list, int]:
@@ -248,18 +262,40 @@ def classic_size(array_bytes: int, n_segments: int, extra_tags=None) -> int:
     return 8 + 2 + 12 * 16 + 4 + 8 * n_segments + 64 * PACK_MAX_SAMPLES + extra + array_bytes
 
 
+NODATA_TAG = 42113              # GDAL_NODATA: the one extra tag that goes on the overview IFDs as well
+
+
+def _segment_views(segments_or_array, layout: dict) -> List:
+    """The packed bytes of one image (or the image itself, through pack_host) cut into its segments."""
+    total = check_pack_layout(layout)
+    data = np.asarray(segments_or_array)
+    if not (data.ndim == 1 and data.dtype == np.uint8 and data.size == total):
+        data = pack_host(data, layout)
+    view = memoryview(np.ascontiguousarray(data))
+    bounds = np.concatenate([[0], np.cumsum([s[4] for s in _segments(layout)], dtype=np.int64)])
+    return [view[int(a):int(b)] for a, b in zip(bounds[:-1], bounds[1:])]
+
+
 def write_raster(path: str, segments_or_array, layout: dict, *, compress: str = "none", level: int = 6,
                  bigtiff: str = "auto", extra_tags=None, threads: int = WRITE_THREADS_DEFAULT,
-                 classic_limit: int = CLASSIC_LIMIT) -> dict:
-    """Write the first and only image of a TIFF.  segments_or_array: the packed bytes (uint8 [n] with n the layout's total:
-    pack_host's or pack_on_device's buffer, read to the host) or the image itself ([H, W] or [samples, H, W]), which goes
-    through pack_host.  compress: "none" (Compression 1) or "deflate" (8: zlib.compress(segment, level) per segment, level
-    1..9).  bigtiff: "auto" -- classic TIFF if and only if the finished file's size is <= classic_limit, else BigTIFF
-    (version 43, 8-byte offsets, 20-byte entries, LONG8 offsets and byte counts); "yes" forces BigTIFF; "no" forces classic
-    and raises a TiffError naming the size when the file does not fit.  extra_tags: (tag, type, values) triples with
-    write_strip_tiff's rules (type 2 ASCII, 3 SHORT, 4 LONG, 12 DOUBLE; none of the image's own tags), e.g. the
-    georeferencing.  File order: directory, tag payloads on word boundaries, segments.  All compressed segments are held
-    in memory before the directory is written, so every offset is exact.  -> {"bigtiff", "size", "segments"}."""
+                 classic_limit: int = CLASSIC_LIMIT, overviews=None) -> dict:
+    """Write a TIFF: its full-resolution image and, with `overviews`, the reduced-resolution images behind it.
+    segments_or_array: the packed bytes (uint8 [n] with n the layout's total: pack_host's or pack_on_device's buffer, read
+    to the host) or the image itself ([H, W] or [samples, H, W]), which goes through pack_host.  compress: "none"
+    (Compression 1) or "deflate" (8: zlib.compress(segment, level) per segment, level 1..9).  bigtiff: "auto" -- classic
+    TIFF if and only if the finished file's size is <= classic_limit, else BigTIFF (version 43, 8-byte offsets, 20-byte
+    entries, LONG8 offsets and byte counts); "yes" forces BigTIFF; "no" forces classic and raises a TiffError naming the
+    size when the file does not fit.  extra_tags: (tag, type, values) triples with write_strip_tiff's rules (type 2 ASCII, 3
+    SHORT, 4 LONG, 12 DOUBLE; none of the image's own tags), e.g. the georeferencing.  File order: directory, tag payloads
+    on word boundaries, segments.  All compressed segments are held in memory before the directory is written, so every
+    offset is exact.  -> {"bigtiff", "size", "segments"}.
+    overviews: None (the file is byte for byte what it always was) or [(segments_or_array, layout), ...] in decreasing
+    size, e.g. datasets/overviews.py's levels.  Then the file is laid out as a cloud-optimised reader wants it: the header;
+    IFD 0 with its payloads; every overview IFD with its payloads, in decreasing size, chained through the next-IFD
+    pointers; then the segment data, the smallest overview first and the full resolution last.  Overview IFDs carry
+    NewSubfileType (254) = 1; extra_tags go on IFD 0 only, except GDAL_NODATA (42113), which every IFD of a file that has
+    it carries.  The classic / BigTIFF decision is made on the size of the whole file, and the segments of all images are
+    deflated on one thread pool.  The result also has "overviews": their number, and "segments" counts all images'."""
     if compress not in ("none", "deflate"):
         raise ValueError(f"compress must be 'none' or 'deflate', got {compress!r}")
     if isinstance(level, bool) or int(level) != level or not 1 <= int(level) <= 9:
@@ -267,14 +303,13 @@ def write_raster(path: str, segments_or_array, layout: dict, *, compress: str = 
     if bigtiff not in ("auto", "yes", "no"):
         raise ValueError(f"bigtiff must be 'auto', 'yes' or 'no', got {bigtiff!r}")
     threads = check_write_threads(threads)
-    total = check_pack_layout(layout)
-    data = np.asarray(segments_or_array)
-    if not (data.ndim == 1 and data.dtype == np.uint8 and data.size == total):
-        data = pack_host(data, layout)
-    data = np.ascontiguousarray(data)
-    bounds = np.concatenate([[0], np.cumsum([s[4] for s in _segments(layout)], dtype=np.int64)])
-    view = memoryview(data)
-    parts: List = [view[int(a):int(b)] for a, b in zip(bounds[:-1], bounds[1:])]
+    layouts = [layout] + [L for _, L in overviews or ()]
+    for big_one, small in zip(layouts[:-1], layouts[1:]):
+        if small["width"] > big_one["width"] or small["height"] > big_one["height"] or \
+                (small["width"], small["height"]) == (big_one["width"], big_one["height"]):
+            raise ValueError("write_raster: overviews come in decreasing size")
+    per_image = [_segment_views(segments_or_array, layout)] + [_segment_views(a, L) for a, L in overviews or ()]
+    parts: List = [seg for image in per_image for seg in image]
     if compress == "deflate":
         deflate = lambda seg: zlib.compress(seg, int(level))                        # noqa: E731
         if threads > 1 and len(parts) > 1:
@@ -282,25 +317,36 @@ def write_raster(path: str, segments_or_array, layout: dict, *, compress: str = 
                 parts = list(pool.map(deflate, parts))
         else:
             parts = [deflate(seg) for seg in parts]
-    counts = np.array([len(p) for p in parts], dtype=np.int64)
+    ends = np.cumsum([len(image) for image in per_image])
+    per_image = [parts[int(e) - len(image):int(e)] for e, image in zip(ends, per_image)]
+    counts = [np.array([len(p) for p in image], dtype=np.int64) for image in per_image]
     scheme = 8 if compress == "deflate" else 1
+    reduced_tags = [(254, 4, [1])] + [t for t in extra_tags or () if t[0] == NODATA_TAG]
+
+    def directories(big):
+        images = [_image_tags(L, scheme, c, big, reduced_tags if i else extra_tags) + (c,)
+                  for i, (L, c) in enumerate(zip(layouts, counts))]
+        head, offsets = _directories([(tags, c, offsets_tag) for tags, offsets_tag, c in images], big)
+        return head, int(offsets[0][-1] + counts[0][-1])             # the full resolution's data ends the file
+
     big = bigtiff == "yes"
     if not big:
-        tags, offsets_tag = _image_tags(layout, scheme, counts, False, extra_tags)
-        head, offsets = _directory(tags, counts, offsets_tag, False)
-        size = int(offsets[-1] + counts[-1])
+        head, size = directories(False)
         if size > classic_limit:
             if bigtiff == "no":
                 raise TiffError(f"{path}: a file of {size} bytes does not fit classic TIFF (limit {classic_limit}); "
                                 "write it as BigTIFF")
             big = True
     if big:
-        tags, offsets_tag = _image_tags(layout, scheme, counts, True, extra_tags)
-        head, offsets = _directory(tags, counts, offsets_tag, True)
-        size = int(offsets[-1] + counts[-1])
+        head, size = directories(True)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as fh:
         fh.write(head)
-        for p in parts:
-            fh.write(p)
-    return {"bigtiff": big, "size": size, "segments": len(parts)}
+        for image in reversed(per_image):
+            for p in image:
+                fh.write(p)
+    result = {"bigtiff": big, "size": size, "segments": len(parts)}
+    if overviews is not None:
+        result["overviews"] = len(overviews)
+    return result
+

@@ -62,8 +62,8 @@ else the parent directory.  What runs differently:
     uploaded as stored and unpacked by ONE kernel launch (fu_tiff_unpack: predictor, byte swap, tiles, band choice,
     conversion) into the very fp32 tensor the host route uploads; device does so for every file, host puts every file
     through the numpy statement.  Everything behind that tensor is the same code, so the routes write identical files.
-    Out of scope: JPEG / ZSTD / LERC, sub-byte samples, overviews and mask IFDs (the first IFD is the scene), entropy
-    decoding on the GPU.
+    Out of scope: JPEG / ZSTD / LERC, sub-byte samples, reading a scene from an overview or a mask IFD (the first IFD is the
+    scene; geotiff.read_raster(ifd=...) reads the others), entropy decoding on the GPU.
   * extension: --write_vectors writes the water bodies as polygons, <image>.geojson beside <image>.tif: one Polygon
     feature, outer ring and holes, per connected patch (--vector_connectivity 4|8, default the sieve's, else 4) of the
     values --vector_values (default 255) of the class map as written, so after the threshold, the mask and the sieve.
@@ -92,8 +92,18 @@ else the parent directory.  What runs differently:
     and the class map's GDAL_NODATA as always; a scene without a valid pixel is packed on the host (pack_host).  The
     records and the summary gain "output_format".  With every out_* option at its default nothing of this runs and every
     file is byte for byte what it was -- except that a file classic TIFF cannot hold (above 4 GiB; that only raised) is
-    written as BigTIFF strips by the new writer.  Out of scope: LZW / PackBits / ZSTD encoders, overviews and COG block
-    ordering, chunky or big-endian output, predict's outputs, entropy coding on the GPU.
+    written as BigTIFF strips by the new writer.  Out of scope: LZW / PackBits / ZSTD encoders, chunky or big-endian
+    output, predict's outputs, entropy coding on the GPU.
+  * extension: --out_overviews auto|N puts N reduced-resolution images behind every written raster, and --out_cog is the
+    preset for cloud-optimised files (tiles of 512 and overviews "auto" unless given).  The levels are cut on the device,
+    after the sieve and from the rasters as they are written (datasets/overviews.py holds the rule; fu_map_overviews, six
+    levels per launch from one read of the raster): the class map by its most frequent value (ties to the smaller value,
+    nodata_out never wins under --nodata), probabilities, margin and the fp32 canvas by the mean over the valid pixels, the
+    valid raster by `any`.  Each level goes through fu_tiff_pack with a layout of its own size and rides in the scene's one
+    read; write_raster puts every directory in front of the data and the smallest image's data first.  Such a run is a
+    packed-output run; the records' "output_format" gains "overviews" and "cog" (geotiff.cog_report of the written files).
+    Without either flag nothing of this runs.  Out of scope: GDAL's ghost block and tile leaders, overviews of predict's
+    outputs, other resampling kinds, reading a scene from an overview under --scale.
 How infer() is put together: the options travel as one checked InferOptions (infer_options.py; the keywords of infer() and
 the command line both go through InferOptions.make); predict.load_eval_model serves the model; a SceneQueue owns the
 scenes in flight and deals their crops out in batches; per batch scene_crops, predict.eval_forward and one batched stitch;
@@ -115,8 +125,8 @@ import torch
 
 from .infer_options import (BLEND_KINDS, DECODE_CHOICES, DECODE_THREADS_DEFAULT, NODATA_OUT_DEFAULT,  # noqa: F401
                             OUT_BIGTIFF_CHOICES, OUT_COMPRESS_CHOICES, OUT_LEVEL_DEFAULT, OUT_PREDICTOR_CHOICES,
-                            OUT_THREADS_DEFAULT, OUT_TILE_FLAG, PROB_FORMATS, WEIGHT_CHOICES, InferOptions, default_stride,
-                            grid_size, scene_nodata, threshold_rule)
+                            OUT_THREADS_DEFAULT, OUT_TILE_FLAG, OUT_TILE_STRIPS, PROB_FORMATS, WEIGHT_CHOICES, InferOptions,
+                            default_stride, grid_size, scene_nodata, threshold_rule)
 from .predict import CONFIG_DEFAULTS, _merge, eval_forward, load_eval_model, resolve_cfg
 from .tta import VIEW_SETS, recorded
 from .vectorize import ARRAYS as VECTOR_ARRAYS
@@ -441,12 +451,35 @@ def empty_scene_arrays(scene: dict, n_classes: int, options: InferOptions) -> Di
             if name in arrays:
                 raster = arrays[name].transpose(2, 0, 1) if name == "canvas" else arrays[name]
                 arrays["packed_" + name] = pack_host(raster, output_layout(options, raster.dtype, raster.shape))
+                levels = raster_overviews(raster, name, options, np.zeros((H, W), dtype=np.uint8))
+                for l, level in enumerate(levels, 1):
+                    arrays[f"packed_{name}_ov{l}"] = pack_host(level, output_layout(options, level.dtype, level.shape))
                 if name != "class" or not options.write_vectors:
                     del arrays[name]
     return arrays
 
 
 PACKED_RASTERS = ("class", "probs", "margin", "valid", "canvas")     # the arrays of finalize_scene that become files
+# how each of them is reduced to its overview levels (datasets/overviews.py)
+OVERVIEW_KINDS = {"class": "mode_u8", "probs": "mean_u8", "margin": "mean_u8", "valid": "any_u8", "canvas": "mean_f32"}
+
+
+def raster_overviews(raster, name: str, options: InferOptions, valid) -> list:
+    """The overview levels of one output raster ([H, W] or [k, H, W]; a device tensor goes through fu_map_overviews, an
+    array through the numpy statement), options.overview_levels of them: the class map by mode_u8 with nodata_out as the
+    nodata value under --nodata, probabilities and margin by mean_u8 and the fp32 canvas by mean_f32 over the scene's valid
+    mask (valid: uint8 [H, W], looked at under --nodata only), the valid raster by any_u8."""
+    from .datasets.overviews import overviews_host, overviews_on_device
+    n_levels = options.overview_levels(tuple(raster.shape[-2:]))
+    if n_levels == 0:
+        return []
+    reduce = overviews_on_device if torch.is_tensor(raster) else overviews_host
+    kind, masked = OVERVIEW_KINDS[name], options.nodata is not None
+    if kind == "mode_u8":
+        return reduce(raster, kind, n_levels, nodata_value=options.nodata_out if masked else None)
+    if kind == "any_u8":
+        return reduce(raster, kind, n_levels)
+    return reduce(raster, kind, n_levels, valid=valid if masked else None)[0]
 
 
 def output_layout(options: InferOptions, dtype, shape) -> dict:
@@ -471,7 +504,10 @@ def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: Inf
     is the count, and a scene with more than vector_max_edges has the count alone.  With options.packed_output (an out_*
     option is set) every raster that becomes a file is packed for its writer on the same stream after the sieve
     (geotiff_write.pack_on_device, one launch each; the canvas from its [H, W, k] strides) and the read carries
-    "packed_class", "packed_probs", ... uint8 [n] in place of the rasters; "class" itself only under write_vectors."""
+    "packed_class", "packed_probs", ... uint8 [n] in place of the rasters; "class" itself only under write_vectors.  With
+    options.out_overviews each of those rasters is reduced to its overview levels after the sieve, from the raster as it is
+    written (raster_overviews: fu_map_overviews, one launch per six levels), every level is packed with a layout of its own
+    size, and the read also carries "packed_class_ov1", "packed_class_ov2", ..."""
     from .postprocess import sieve as sieve_map
     from .stitch import PackedRead
     masked = options.nodata is not None
@@ -512,6 +548,8 @@ def finalize_scene(stitcher, key: str, class_values: Sequence[int], options: Inf
         for name, t in rasters.items():
             dtype = np.float32 if t.dtype == torch.float32 else np.uint8
             read.add("packed_" + name, pack_on_device(t, output_layout(options, dtype, tuple(t.shape))))
+            for l, level in enumerate(raster_overviews(t, name, options, scene["valid"] if masked else None), 1):
+                read.add(f"packed_{name}_ov{l}", pack_on_device(level, output_layout(options, dtype, tuple(level.shape))))
         if options.write_vectors:
             read.add("class", maps["class"])             # one byte per pixel: the host sorts the rings with it
     if options.write_vectors:                            # of the map as it is written: after the sieve
@@ -537,14 +575,20 @@ def write_scene(arrays: Dict[str, np.ndarray], scene: dict, options: InferOption
     write_valid writes arrays["valid"] as <image>_valid.tif.  With options.write_vectors (arrays: also the ring arrays
     and "edges") it writes <image>.geojson: write_scene_vectors.  With options.packed_output the arrays hold the packed
     bytes ("packed_class", ...) and every raster goes through geotiff_write.write_raster (write_output_raster); the record
-    gains "output_format", with "bigtiff" per file."""
+    gains "output_format", with "bigtiff" per file.  With options.out_overviews every file also holds its overview images
+    ("packed_class_ov1", ...; write_raster's overviews) and "output_format" gains "overviews", their number, and "cog":
+    --out_cog was given and geotiff.cog_report of every file written is empty."""
     H, W = scene["hw"]
     tags = geo_tags_for_grid(scene["tags"], scene["src_hw"], (H, W))
     masked = options.nodata is not None
     big = {}                                             # file kind -> whether it was written as BigTIFF
+    cog = {}                                             # ... -> whether it follows the cloud-optimised layout
 
     def put(file_path, kind, name, extra_tags):
         big[kind] = write_output_raster(file_path, arrays, name, options, extra_tags, (H, W))
+        if options.out_cog:
+            from .datasets.geotiff import cog_report
+            cog[kind] = not cog_report(file_path)
         return file_path
 
     put(out_path, "class", "class", tags + [(42113, 2, str(options.nodata_out))] if masked else tags)
@@ -561,7 +605,7 @@ def write_scene(arrays: Dict[str, np.ndarray], scene: dict, options: InferOption
     if options.write_probs == "f32":
         rec["probabilities"] = put(side_output_path(out_path, "prob"), "probabilities", "canvas", tags)
     if options.packed_output or any(big.values()):
-        rec["output_format"] = options.output_format(big)
+        rec["output_format"] = options.output_format(big, options.overview_levels((H, W)), bool(cog) and all(cog.values()))
     if options.sieve is not None:
         merged, changed = arrays["sieve"].tolist()
         rec["sieve"] = dict(options.sieve_options, merged_components=merged, changed_pixels=changed)
@@ -581,10 +625,16 @@ def write_output_raster(file_path: str, arrays: Dict[str, np.ndarray], name: str
     from .datasets.synthetic import write_strip_tiff
     if options.packed_output:
         shape = ((len(arrays["counts"]),) if name in ("probs", "canvas") else ()) + tuple(hw)
-        layout = output_layout(options, np.float32 if name == "canvas" else np.uint8, shape)
+        dtype = np.float32 if name == "canvas" else np.uint8
+        layout = output_layout(options, dtype, shape)
+        overviews = None
+        if options.out_overviews is not None:
+            from .datasets.overviews import overview_sizes
+            overviews = [(arrays[f"packed_{name}_ov{l}"], output_layout(options, dtype, shape[:-2] + size))
+                         for l, size in enumerate(overview_sizes(hw[0], hw[1], options.overview_levels(hw)), 1)]
         return write_raster(file_path, arrays["packed_" + name], layout, compress=options.out_compress,
                             level=options.out_level, bigtiff=options.out_bigtiff, extra_tags=extra_tags,
-                            threads=options.out_threads)["bigtiff"]
+                            threads=options.out_threads, overviews=overviews)["bigtiff"]
     array = arrays["canvas"].transpose(2, 0, 1) if name == "canvas" else arrays[name]
     n_segments = (1 if array.ndim == 2 else array.shape[0]) * -(-array.shape[-2] // 16)
     if classic_size(array.nbytes, n_segments, extra_tags) <= CLASSIC_LIMIT:
@@ -639,7 +689,9 @@ def run_summary(records: List[dict], n_crops: int, seconds: float, max_resident:
                               "skipped_scenes": len(records) - len(written)}
     formats = [r["output_format"] for r in records if "output_format" in r]
     if options.packed_output or formats:                 # "bigtiff": whether any file of the run is BigTIFF
-        summary["output_format"] = options.output_format(any(any(f["bigtiff"].values()) for f in formats))
+        summary["output_format"] = options.output_format(any(any(f["bigtiff"].values()) for f in formats),
+                                                         max((f.get("overviews") or 0 for f in formats), default=0),
+                                                         bool(formats) and all(f.get("cog") for f in formats))
     return summary
 
 
@@ -655,6 +707,7 @@ def infer(checkpoint_path: str, inputs: Sequence[str], out_dir: str, *, cfg: Opt
     valid-pixel mask, see the module docstring), decode / decode_threads (where a scene's samples are unpacked),
     write_vectors / vector_values / vector_connectivity / vector_max_edges (polygons of the written class map),
     out_compress / out_level / out_predictor / out_tile / out_bigtiff / out_threads (the format of the written rasters),
+    out_overviews / out_cog (overview images behind them, in the cloud-optimised order),
     n_workers, device, keep_probabilities.  Returns the
     summary.json dict, which records the weights served, the blend, the stride and, when set, "threshold" and "sieve";
     with keep_probabilities also "probabilities" {output path: fp32 [H, W, k] stitched canvas} (one more host read per
@@ -791,13 +844,25 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--out_predictor", type=str, default="auto", choices=list(OUT_PREDICTOR_CHOICES),
                     help="auto (the default): under deflate, horizontal differencing for the uint8 rasters and the "
                          "floating-point predictor for float32 probabilities; off: no predictor")
-    ap.add_argument("--out_tile", type=int, nargs="?", const=OUT_TILE_FLAG, default=None, metavar="N",
-                    help="write N x N tiles instead of 16-row strips; N a multiple of 16 (256 when the flag stands alone)")
+    def tile_side(text):                                 # N, or the explicit spelling of the default layout
+        return text if text == OUT_TILE_STRIPS else int(text)
+
+    ap.add_argument("--out_tile", type=tile_side, nargs="?", const=OUT_TILE_FLAG,
+                    default=None, metavar="N",
+                    help="write N x N tiles instead of 16-row strips; N a multiple of 16 (256 when the flag stands alone); "
+                         "'strips' says the default explicitly")
     ap.add_argument("--out_bigtiff", type=str, default="auto", choices=list(OUT_BIGTIFF_CHOICES),
                     help="auto (the default): BigTIFF only for a file classic TIFF cannot hold; yes: always; no: never, and "
                          "a file above 4 GiB is an error")
     ap.add_argument("--out_threads", type=int, default=OUT_THREADS_DEFAULT, metavar="T",
                     help="threads that deflate a raster's strips or tiles, 1..16 (default 4)")
+    ap.add_argument("--out_overviews", type=str, default=None, metavar="auto|N",
+                    help="put N reduced-resolution images (each half the size of the one before) behind every written "
+                         "raster, cut on the device; auto: until the smallest fits one tile (256 pixels for strips).  "
+                         "Directories first, the smallest image's data first: the cloud-optimised order (default: none)")
+    ap.add_argument("--out_cog", action="store_true",
+                    help="cloud-optimised GeoTIFFs: --out_tile 512 and --out_overviews auto unless given; the records say "
+                         "whether every written file passes the layout check")
     ap.add_argument("--batch_size", type=int, default=None, help="crops per eval forward (default: the config's)")
     ap.add_argument("--tta", type=str, default=None, choices=sorted(VIEW_SETS),
                     help="test-time augmentation: average each crop's softmax over its flips / rotations")

@@ -19,7 +19,7 @@ KEYWORDS = ("size", "scale", "stride", "batch_size", "tta", "n_workers", "device
             "blend", "write_probs", "write_margin", "sieve", "sieve_connectivity", "sieve_passes", "water_threshold",
             "threshold_class", "calibration", "nodata", "nodata_out", "skip_empty", "write_valid", "decode",
             "decode_threads", "write_vectors", "vector_values", "vector_connectivity", "vector_max_edges", "out_compress",
-            "out_level", "out_predictor", "out_tile", "out_bigtiff", "out_threads")
+            "out_level", "out_predictor", "out_tile", "out_bigtiff", "out_threads", "out_overviews", "out_cog")
 NODATA_OUT_DEFAULT = 127                         # the class map's byte where the input holds no data
 DECODE_CHOICES = ("auto", "host", "device")      # how a scene's samples reach the device (infer.SceneFiles)
 DECODE_THREADS_DEFAULT, DECODE_THREADS_MAX = 4, 16   # datasets/geotiff.py's; never sized from the machine's CPU count
@@ -28,6 +28,8 @@ OUT_COMPRESS_CHOICES = ("none", "deflate")       # how the output rasters are wr
 OUT_PREDICTOR_CHOICES = ("auto", "off")
 OUT_BIGTIFF_CHOICES = ("auto", "yes", "no")
 OUT_LEVEL_DEFAULT, OUT_THREADS_DEFAULT, OUT_THREADS_MAX, OUT_TILE_FLAG = 6, 4, 16, 256
+OUT_TILE_STRIPS = "strips"                       # out_tile: strips, said explicitly (None says so by default)
+OUT_TILE_COG = 512                               # the tile side --out_cog chooses unless --out_tile gives one
 
 
 def check_weights(weights) -> str:
@@ -193,6 +195,35 @@ _OUTPUT_DEFAULTS = dict(out_compress="none", out_level=OUT_LEVEL_DEFAULT, out_pr
                         out_bigtiff="auto", out_threads=OUT_THREADS_DEFAULT)
 
 
+def check_overviews(out_overviews, out_cog, out_tile):
+    """--out_overviews auto|N and the preset --out_cog -> (the two pyramid fields or None when neither is given, out_tile
+    as check_output takes it).  out_overviews: None (no overview images), "auto" (levels until the smallest fits one tile,
+    or 256 pixels for strips: overviews.auto_levels) or an integer >= 0 (also as a string; clamped per scene to the levels
+    down to 1 x 1).  out_cog: tiles of 512 unless out_tile gives the side, overviews "auto" unless given; it excludes an
+    explicit strip layout (out_tile "strips")."""
+    if out_overviews is not None and out_overviews != "auto":
+        try:
+            n = int(out_overviews) if isinstance(out_overviews, str) else out_overviews
+        except ValueError:
+            n = None
+        if n is None or not _is_int(n) or int(n) < 0:
+            raise ValueError(f"infer: out_overviews must be 'auto' or an integer >= 0, got {out_overviews!r}")
+        out_overviews = int(n)
+    strips = isinstance(out_tile, str) and out_tile == OUT_TILE_STRIPS
+    if strips:
+        out_tile = None
+    if out_cog:
+        if strips:
+            raise ValueError("infer: --out_cog writes tiles; it excludes --out_tile strips")
+        if out_tile is None:
+            out_tile = OUT_TILE_COG
+        if out_overviews is None:
+            out_overviews = "auto"
+    if out_overviews is None:
+        return None, out_tile
+    return dict(out_overviews=out_overviews, out_cog=bool(out_cog)), out_tile
+
+
 @dataclasses.dataclass(frozen=True)
 class InferOptions:
     """size / scale: the output grid (grid_size); None, None: the raster's own.  stride and batch_size None: the
@@ -206,7 +237,9 @@ class InferOptions:
     differs from its default.  And write_vectors with vector_values, vector_connectivity and vector_max_edges: off here,
     fields of the Vector* classes under --write_vectors.  And the six out_* options of the output format: the defaults
     here (the rasters go through write_strip_tiff, byte for byte as always), fields of output_options_class(...) when any
-    is set; packed_output says which."""
+    is set; packed_output says which.  And out_overviews / out_cog, the overview images behind every written raster: off
+    here, fields of overview_options_class(...) -- the Output* class of the run with the two appended -- when either is
+    given; such a run is a packed-output run."""
     size: Optional[Tuple[int, int]] = None
     scale: Optional[float] = None
     stride: Optional[int] = None
@@ -238,6 +271,8 @@ class InferOptions:
     out_tile = None
     out_bigtiff = "auto"
     out_threads = OUT_THREADS_DEFAULT
+    out_overviews = None                 # not fields here: see overview_options_class
+    out_cog = False
     packed_output = False                # True on the Output* classes: the rasters are packed on the device and go
     #                                      through geotiff_write.write_raster
 
@@ -249,10 +284,10 @@ class InferOptions:
              write_valid=False, decode="auto", decode_threads=DECODE_THREADS_DEFAULT, write_vectors=False,
              vector_values=None, vector_connectivity=None, vector_max_edges=None, out_compress="none",
              out_level=OUT_LEVEL_DEFAULT, out_predictor="auto", out_tile=None, out_bigtiff="auto",
-             out_threads=OUT_THREADS_DEFAULT) -> "InferOptions":
+             out_threads=OUT_THREADS_DEFAULT, out_overviews=None, out_cog=False) -> "InferOptions":
         """The options checked, in the order infer() always checked them: weights, blend, write_probs, the decision
         rule (threshold_rule), the sieve (postprocess.check_sieve_options), an explicit stride, the grid, nodata, decode,
-        vectors, the output format."""
+        vectors, the overviews (which can choose the tile side), the output format."""
         from .postprocess import check_sieve_options
         check_weights(weights)
         check_blend(blend)
@@ -282,10 +317,14 @@ class InferOptions:
         if vectors is not None:
             cls = vector_options_class(cls)
             extra.update(vectors)
+        pyramid, out_tile = check_overviews(out_overviews, out_cog, out_tile)
         output = check_output(out_compress, out_level, out_predictor, out_tile, out_bigtiff, out_threads)
-        if output is not None:
+        if output is not None or pyramid is not None:        # a run with overviews is a packed-output run
             cls = output_options_class(cls)
-            extra.update(output)
+            extra.update(output or _OUTPUT_DEFAULTS)
+        if pyramid is not None:
+            cls = overview_options_class(cls)
+            extra.update(pyramid)
         return cls(size=None if size is None else (int(size[0]), int(size[1])), scale=scale,
                    stride=None if stride is None else int(stride), batch_size=int(batch_size) if batch_size else None,
                    tta=tta if tta is None or isinstance(tta, str) else tuple(int(c) for c in tta), weights=weights,
@@ -338,10 +377,25 @@ class InferOptions:
         import numpy as np
         return 3 if np.dtype(dtype).kind == "f" else 2
 
-    def output_format(self, bigtiff) -> dict:
-        """The records' and the summary's "output_format"; bigtiff: whether the file, or any file of the run, is BigTIFF."""
-        return {"compress": self.out_compress, "level": self.out_level if self.out_compress == "deflate" else None,
-                "predictor": self.out_predictor, "tile": self.out_tile, "bigtiff": bigtiff, "threads": self.out_threads}
+    def output_format(self, bigtiff, overviews=None, cog=None) -> dict:
+        """The records' and the summary's "output_format"; bigtiff: whether the file, or any file of the run, is BigTIFF.
+        A run with overviews also records "overviews", the overview images written per file (the summary: the most any
+        scene got), and "cog": the preset was asked for and geotiff.cog_report of every written file is empty."""
+        fmt = {"compress": self.out_compress, "level": self.out_level if self.out_compress == "deflate" else None,
+               "predictor": self.out_predictor, "tile": self.out_tile, "bigtiff": bigtiff, "threads": self.out_threads}
+        if self.out_overviews is not None:
+            fmt.update(overviews=overviews, cog=bool(cog))
+        return fmt
+
+    def overview_levels(self, hw: Tuple[int, int]) -> int:
+        """The overview images a raster of hw gets: 0 without out_overviews; under "auto" the levels until the smallest
+        fits one tile (256 pixels for strips); else the count asked for, clamped to the levels down to 1 x 1."""
+        if self.out_overviews is None:
+            return 0
+        from .datasets.overviews import STRIP_SIDE, auto_levels, max_levels
+        if self.out_overviews == "auto":
+            return auto_levels(hw[0], hw[1], self.out_tile or STRIP_SIDE)
+        return min(self.out_overviews, max_levels(hw[0], hw[1]))
 
 
 @dataclasses.dataclass(frozen=True)
@@ -418,3 +472,23 @@ def _output_class(base):
 
 _OUTPUT_CLASSES = {base: _output_class(base) for base in (InferOptions, NodataInferOptions, DecodeInferOptions,
                                                           NodataDecodeInferOptions) + tuple(_VECTOR_CLASSES.values())}
+
+
+def overview_options_class(base):
+    """The options class of a run with --out_overviews or --out_cog: `base` (any of the Output* classes) with the two
+    pyramid fields appended.  out_overviews: "auto" or the number of overview images; out_cog: the preset was asked for,
+    and the records say whether the written files follow the cloud-optimised layout."""
+    return _OVERVIEW_CLASSES[base]
+
+
+def _overview_class(base):
+    cls = dataclasses.make_dataclass(
+        "Overview" + base.__name__, [("out_overviews", Union[str, int], "auto"), ("out_cog", bool, False)], bases=(base,),
+        frozen=True)
+    cls.__module__ = __name__
+    cls.__doc__ = f"{base.__name__} of a run with overviews: the two pyramid fields appended (overview_options_class)."
+    globals()[cls.__name__] = cls
+    return cls
+
+
+_OVERVIEW_CLASSES = {base: _overview_class(base) for base in _OUTPUT_CLASSES.values()}

@@ -28,6 +28,8 @@
  *   fu_tiff_packbits_decode
  *   fu_tiff_pack                (new) the inverse for the rasters infer writes: a strided device raster -> the byte buffer
  *                               a TIFF writer deflates -- planes, tiles or strips, edge padding, predictor -- in one launch
+ *   fu_map_overviews            (new) the overview pyramid of such a raster: mode / mean / any over 2 x 2 blocks, six levels
+ *                               per launch from one read of the base (gdaladdo's role, on the device)
  *   fu_backward[_block]         loss.backward() issued by Lightning's automatic optimisation
  *                                                                            st_water_seg/fit.py:95-97
  *   fu_adam_step                optim.Adam(self.parameters(), lr).step()     st_water_seg/models/water_seg_model.py:198-205
@@ -772,6 +774,36 @@ int fu_tiff_unpack(const uint8_t* src, int64_t n_bytes, fu_tiff_layout layout, c
  * predictor 2 on floats -- and a rejected call launches nothing and leaves dst untouched. */
 int fu_tiff_pack(const void* src, int64_t band_stride, int64_t row_stride, int64_t col_stride, fu_tiff_layout layout,
                  uint8_t* dst, int64_t n_bytes, fu_stream stream);
+
+/* ---- overview pyramids of the rasters infer writes (fu_overview.hip; added within ABI 5: purely additive) ---------- */
+/* The reduced-resolution levels of a device-resident raster, bit for bit datasets/overviews.py's overviews_host.  src,
+ * the strides (in elements, >= 0), bands (1..FU_TIFF_MAX_BANDS), h and w (h * w <= FU_MAP_MAX_PIXELS) describe the raster
+ * as for fu_tiff_pack, so an [H, W, k] canvas and a [k, H, W] tensor are both sources without a copy.  Level l >= 1 is
+ * ceil(h / 2^l) x ceil(w / 2^l); its pixel (y, x) is reduced from the pixels (2y..2y+1, 2x..2x+1) of level l - 1 that exist
+ * -- one, two or four -- so the levels are a cascade, never taken from the base.  kind:
+ *   FU_OVERVIEW_MODE_U8   uint8: the most frequent value among the block's pixels that differ from nodata_value (-1..255;
+ *                         -1: none is excluded), ties to the smaller value; nodata_value where every pixel is nodata.
+ *   FU_OVERVIEW_MEAN_U8   uint8: over the block's valid pixels (2 * sum + n) / (2 * n) in integers, which rounds half up; 0
+ *                         where none is valid.
+ *   FU_OVERVIEW_MEAN_F32  fp32: the valid pixels summed in row-major order from +0, one rounding per add, then ONE correctly
+ *                         rounded division by float(n); 0 where none is valid.
+ *   FU_OVERVIEW_ANY_U8    uint8: 1 where a pixel of the block is non-zero, else 0.
+ * valid: device uint8 [h, w] or NULL (every pixel valid), the mean kinds only; a pixel is valid where its byte is non-zero,
+ * and the mask of level l is `any` of the mask of level l - 1.  nodata_value is -1 for every kind but mode_u8.
+ * dst: the levels back to back, each a contiguous [bands, h_l, w_l] of the source's sample type; dst_elems >= bands * the sum
+ * of h_l * w_l.  valid_dst: the mask levels back to back, uint8 [h_l, w_l] each (the sum of h_l * w_l bytes, caller-owned);
+ * required exactly when valid is given.  n_levels: 0 .. the number of levels down to 1 x 1, ceil(log2(max(h, w))).
+ * One pass per launch: a workgroup loads a 64 x 64 base tile (and the mask's) into LDS once, 16-byte loads where col_stride
+ * == 1, reduces it there level by level and writes every level's block, so one launch gives six levels and reads the base
+ * once; deeper levels come from one further launch per six whose source is the last level written.  wave64, no atomics, no
+ * workgroup waits for another, 64-bit offsets, no host read.  Every argument is checked first -- null src / dst, an unknown
+ * kind, bands, sizes, negative strides, n_levels, valid without valid_dst or the reverse, valid with a kind that takes none,
+ * nodata_value, alignment to the sample size, a short dst_elems -- and a rejected call launches nothing and leaves dst
+ * untouched.  n_levels = 0 is FU_OK with no launch. */
+enum fu_overview_kind { FU_OVERVIEW_MODE_U8 = 0, FU_OVERVIEW_MEAN_U8 = 1, FU_OVERVIEW_MEAN_F32 = 2, FU_OVERVIEW_ANY_U8 = 3 };
+int fu_map_overviews(const void* src, int64_t band_stride, int64_t row_stride, int64_t col_stride, int bands, int h, int w,
+                     int kind, const uint8_t* valid, int nodata_value, int n_levels, void* dst, int64_t dst_elems,
+                     uint8_t* valid_dst, fu_stream stream);
 
 /* ---- class-map post-processing (fu_post.hip); no context needed --------------------------------- */
 /* Connected components of a uint8 map [h, w] on the device: a component is a maximal set of pixels of equal value joined
